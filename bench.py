@@ -14,10 +14,11 @@ x 50k samples (500 GB), STRONG-scaled: rank g scans variants [g*10M/N, (g+1)*10M
 A rank's shard is cut into tiles of at most --tile-gb (126 GB: SURVEY 8d row M).
 When the whole shard fits the GPU's free memory (N >= 2 on a 288 GiB part) it is
 resident and the K steps are timed in ONE region, barrier + device sync on both
-sides (the contract).  When it does not fit (N = 1: 500 GB) ONE tile buffer is
-regenerated on the device before each tile's scan, OUTSIDE the timed region: the
-timed region is then the sum of the per-tile segments, each bracketed by a device
-sync (+ barrier), and `config.timed_region` says so.  The other workloads are
+sides (the contract).  When it does not fit (N = 1: 500 GB) each tile is generated
+once into ONE tile buffer on the device, OUTSIDE the timed region, and its W warmup
+and K timed segments follow: the timed region is then the sum of the per-tile
+segments, each bracketed by a device sync (+ barrier), and `config.timed_region`
+says so.  The other workloads are
 one resident shard per rank (weak scaling): c2 / c3 / c4 / c5 are BASELINE
 configs[1..4]'s single-GPU shapes, m8 the 1/8 shard of the metric cohort, stats
 the vcf-stats counters + Hardy-Weinberg on 1M x 10k.
@@ -27,7 +28,11 @@ ranks: the parent makes no GPU call, spawns one fresh child per rank (RANK /
 LOCAL_RANK / WORLD_SIZE / MASTER_* set, rendezvous on 127.0.0.1) and relays rank
 0's JSON line.  Under torch.distributed.run the ranks are used as given.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run does only what that line's figure
+needs: set-up, warmup, the K timed steps.  --full adds the rest: the oracle's
+parity check of the timed run's outputs, the CPU baselines, the streaming-read
+probe and, on the default line, c2 / c3 / c4 / stats under "configs".
+--dump-outputs DIR writes a seeded sample of the last step's results as .npy.
 """
 import argparse
 import importlib
@@ -70,6 +75,29 @@ METRIC = {"chisq": "variants/s chi2 assoc", "fisher": "variants/s fisher assoc",
           "stats": "variants/s vcf stats"}
 # (bytes of integer tallies at the front of a result block, bytes of a result record = SURVEY 8d payload)
 RESULT = {"chisq": (16, 40), "fisher": (16, 32), "tdt": (8, 32), "stats": (32, 48)}
+# names of a result block's int32 tallies and f64 arrays (include/hpgv.h), the files --dump-outputs writes
+OUT_INTS = {"chisq": ("A1", "A2", "U1", "U2"), "fisher": ("A1", "A2", "U1", "U2"), "tdt": ("t1", "t2"),
+            "stats": ("n_00", "n_01", "n_10", "n_11", "missing_genotypes", "missing_alleles", "allele0", "allele1")}
+OUT_F64 = {"chisq": ("odds", "chisq", "p"), "fisher": ("odds", "p"), "tdt": ("odds", "chisq", "p"), "stats": ("hwe_chi2", "hwe_p")}
+# --single-process: which of a set's three f64 arrays hold them (worker_group)
+GROUP_F64 = {"chisq": (1, 2, 3), "fisher": (1, 3), "tdt": (1, 2, 3), "stats": (2, 3)}
+DUMP_VARIANTS = 1_000_000   # --dump-outputs: variants sampled from the last step's results (seeded): at most 56 MB of .npy files
+
+
+def dump_outputs(out_dir, kind, n_variants, fetch):
+    """Writes a fixed seeded sample of DUMP_VARIANTS of the cohort's n_variants results to out_dir: variant.npy (the
+    indices, float64), the tallies as float32 (exact below 2^24) and the statistics as float64.  fetch(sorted indices)
+    returns (int32 tallies [n, len(OUT_INTS[kind])], [f64 array [n] per OUT_F64[kind]])."""
+    import numpy as np
+    rng = np.random.default_rng(0)
+    idx = np.sort(rng.choice(n_variants, size=min(n_variants, DUMP_VARIANTS), replace=False))
+    ints, f64 = fetch(idx)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "variant.npy"), idx.astype(np.float64))
+    for j, name in enumerate(OUT_INTS[kind]):
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(ints[:, j], dtype=np.float32))
+    for name, a in zip(OUT_F64[kind], f64):
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def parse_args(argv=None):
@@ -92,7 +120,7 @@ def parse_args(argv=None):
     ap.add_argument("--fisher-pieces", type=int, default=1,
                     help="Fisher workload, experiment: pieces of a tile whose Fisher pass runs on a second stream beside the next piece's scan "
                          "(measured: no gain, profiles/experiments_that_did_not_pay.md; 1 = one after the other)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--single-process", action="store_true",
                     help="ONE process drives all N GPUs through the C ABI's group context (hpgv_create_multi + hpgv_group_*: "
                          "shards scanned on per-device streams, results gathered onto device 0 over the communicator the "
@@ -102,13 +130,19 @@ def parse_args(argv=None):
                     help="N = 1: initialise the process group all the same and send the result blocks through its gather "
                          "(one real RCCL rank through the N > 1 code path; a check, not a measurement)")
     ap.add_argument("--configs", choices=["auto", "none", "all"], default="auto",
-                    help="attach BASELINE configs[1..3] + stats (c2, c3, c4, stats) as \"configs\" to the line: auto = when "
-                         "the default workload runs at N = 1 without overrides")
+                    help="attach BASELINE configs[1..3] + stats (c2, c3, c4, stats) as \"configs\" to the line: auto = with "
+                         "--full, when the default workload runs at N = 1 without overrides")
     ap.add_argument("--config-steps", type=int, default=10)
     ap.add_argument("--config-warmup", type=int, default=3)
     ap.add_argument("--config-cpu-seconds", type=float, default=3.0)
     ap.add_argument("--cpu-seconds", type=float, default=8.0, help="target wall time of each CPU baseline leg")
     ap.add_argument("--option", action="append", default=[], help="engine option key=value")
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline figure does not need: the oracle's parity check of the timed run's outputs, the "
+                         "CPU baselines, the streaming-read probe, the attached configs (--configs auto) and, with "
+                         "--single-process, the scan timed alone")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write a fixed seeded sample of what the last step computed as DIR/<name>.npy")
     return ap.parse_args(argv)
 
 
@@ -436,18 +470,19 @@ def measure(args, wl, steps, warmup, cpu_seconds, main, world, rank, dev, dev_in
         barrier()
         elapsed = time.perf_counter() - t0
     else:
-        for k in range(warmup + steps):
-            timed = k >= warmup
-            g = step_no[0] % gens
-            step_no[0] += 1
-            for ti in range(n_tiles):
-                generate(ti, gt[0])                     # outside the timed region: the tile is resident when its segment starts
+        # each tile is generated once, outside the timed region, and its warmup and timed segments follow: regenerating
+        # every tile before every step took about ten times as long as the step, all of it outside the timed region
+        for ti in range(n_tiles):
+            generate(ti, gt[0])
+            for k in range(warmup + steps):
+                timed = k >= warmup
                 barrier()
                 t0 = time.perf_counter()
-                pending[:] = run_tile(ti, g, gt[0], maybe_events(timed))
+                pending[:] = run_tile(ti, k % gens, gt[0], maybe_events(timed))
                 barrier()
                 if timed:
                     elapsed += time.perf_counter() - t0
+        step_no[0] = warmup + steps
     if pg:
         t = torch.tensor([elapsed], dtype=torch.float64, device=comm_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -461,7 +496,7 @@ def measure(args, wl, steps, warmup, cpu_seconds, main, world, rank, dev, dev_in
 
     # ---- measured streaming-read ceiling of the same buffer (report both fractions) -----------
     probe_gbps = None
-    if rank == 0 and world == 1 and main:
+    if rank == 0 and world == 1 and main and args.full:
         try:
             nb = scan_variants * pitch
             probe_ms = eng.read_probe(gt[0].data_ptr(), nb, 5)
@@ -469,13 +504,38 @@ def measure(args, wl, steps, warmup, cpu_seconds, main, world, rank, dev, dev_in
         except Exception:
             probe_gbps = None
 
+    # ---- --dump-outputs: a seeded sample of what the last step computed over the whole cohort of this line -----------
+    g_last = (step_no[0] - 1) % gens
+    if rank == 0 and main and args.dump_outputs:
+        # the last step's result blocks and the variants they hold: every rank's as gathered on rank 0, or this rank's own
+        held = []
+        if pg:
+            for r in range(world):
+                p_r = sharding.plan_tiles(r, world, V_all, pitch, max(tile_bytes, pitch), strong=(scaling == "strong"))
+                held += [(recv[g_last][ti][r], p_r["v_lo"] + p_r["tiles"][ti][0], plan["counts"][ti][r])
+                         for ti in range(n_tiles) if plan["counts"][ti][r] > 0]
+        else:
+            held = [(blocks[g_last][ti], v_lo + lo, hi - lo) for ti, (lo, hi) in enumerate(tiles) if hi > lo]
+
+        def fetch(idx):
+            ints = np.empty((len(idx), head // 4), np.int32)
+            f64 = np.empty(((res_bytes - head) // 8, len(idx)), np.float64)
+            for blk, start, n in held:
+                a, z = np.searchsorted(idx, [start, start + n])
+                if z > a:
+                    sel = torch.from_numpy(idx[a:z] - start).to(blk.device)
+                    ints[a:z] = blk[: head * n].view(torch.int32).view(n, head // 4).index_select(0, sel).cpu().numpy()
+                    f64[:, a:z] = blk[head * n: res_bytes * n].view(torch.float64).view(-1, n).index_select(1, sel).cpu().numpy()
+            return ints, list(f64)
+        dump_outputs(args.dump_outputs, kind, sum(n for _, _, n in held), fetch)
+
     # ---- parity spot check: the oracle as CHECKER of the timed run's outputs (not timed, not on the product path)
     parity = None
     parity_failed = False
     out = None
-    if rank == 0:
+    fisher_terms_mean, fisher_terms_n = None, 0
+    if rank == 0 and args.full:
         from oracle import pyoracle as orc
-        g_last = (step_no[0] - 1) % gens
         # blocks to check: this rank's first and last tile and, for N > 1, the last tile GATHERED from the last rank
         sources = [(blocks[g_last][0], v_lo + tiles[0][0], tiles[0][1] - tiles[0][0])]
         if n_tiles > 1 and tiles[-1][1] > tiles[-1][0]:
@@ -543,7 +603,8 @@ def measure(args, wl, steps, warmup, cpu_seconds, main, world, rank, dev, dev_in
                   "resident": bool(resident), "hbm_total_GB": round(total_b / 1e9, 1),
                   "timed_region": ("one region over all steps, barrier + device sync on both sides" if resident else
                                    "sum over steps and tiles of [scan + statistics%s of one tile], each segment between device syncs%s; "
-                                   "the tile buffer (%.1f GB) is regenerated on the device before its segment, outside the timed region"
+                                   "each tile is generated once into the one tile buffer (%.1f GB), on the device and outside the timed "
+                                   "region, and its warmup and timed segments follow"
                                    % (" + gather" if pg else "", " and barriers" if pg else "", per_tile * pitch / 1e9)),
                   "parallelism": par}
         roof = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
@@ -613,8 +674,9 @@ def measure(args, wl, steps, warmup, cpu_seconds, main, world, rank, dev, dev_in
             out["roofline"] = roof
             out["roofline"]["stats_kernel"] = stats_name
             out["roofline"]["stats_kernel_ms"] = stats_ms
-        out["parity"] = parity
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            out["parity"] = parity
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(kind, N if kind != "tdt" else 3 * (N // 3), cond, fam, lf_table, cpu_seconds)
         if parity is not None and not parity["ok"]:
             print("bench.py: workload %s: the timed run's outputs DIFFER from the oracle on the sampled variants: its number is invalid" % wl,
@@ -660,7 +722,7 @@ def worker(args):
 
     out, failed = measure(args, args.workload, args.steps, args.warmup, args.cpu_seconds, True, world, rank, dev, dev_index, pg)
     # ---- the other BASELINE configs in the same driver-timed line (N = 1, default workload, no overrides): a few seconds each
-    want_configs = args.configs == "all" or (args.configs == "auto" and args.workload == "m" and world == 1
+    want_configs = args.configs == "all" or (args.configs == "auto" and args.full and args.workload == "m" and world == 1
                                               and not args.variants and not args.samples and not args.option)
     if rank == 0 and world == 1 and want_configs and out is not None:
         out["configs"] = {}
@@ -757,64 +819,14 @@ def worker_group(args):
     grp.group_sync()
     elapsed = time.perf_counter() - t0
 
-    # the scan kernel alone on member 0's shard (HIP events on its stream, option "profile"), for the roofline line
-    lo0, hi0 = grp.group_shard(V, 0)
-    m0.set_option("profile", 1)
-    tmp = m0.alloc(head * max(hi0 - lo0, 1))
-    scan_ms = []
-    for _ in range(3):
-        if kind == "tdt":
-            m0.tdt_scan(shards[0], hi0 - lo0, tmp, None, None)
-        elif kind == "stats":
-            m0.stats_scan(shards[0], hi0 - lo0, tmp, None)
-        else:
-            m0.assoc_scan(shards[0], hi0 - lo0, tmp, None, None)
-        scan_ms.append(m0.last_kernel_ms()[0])
-    m0.set_option("profile", 0)
-    scan_ms = float(np.median(scan_ms))
-    achieved = (hi0 - lo0) * (N + res_bytes) / (scan_ms * 1e-3) / 1e9
-
-    # parity: the GATHERED arrays on member 0 against the oracle, sampled over every member's shard
-    from oracle import pyoracle as orc
     last = sets[(args.warmup + args.steps - 1) & 1]
-    idx = []
-    for k in range(G):
-        lo, hi = grp.group_shard(V, k)
-        n = hi - lo
-        if n:
-            idx.append(lo + np.unique(np.concatenate([np.arange(min(64, n)), np.arange(0, n, max(1000, n // 100)), np.arange(max(0, n - 64), n)])))
-    idx = np.concatenate(idx) if idx else np.zeros(0, np.int64)
-    if kind in ("fisher", "stats"):
-        idx = idx[:: max(1, len(idx) // 400)]
-    ints = m0.d2h(last[0], (V, head // 4), np.int32)
-    fl = [m0.d2h(last[i], (V,), np.float64) for i in (1, 2, 3)]
-    ncol = N if kind != "tdt" else 3 * (N // 3)
+    if args.dump_outputs:
+        # the arrays gathered on member 0 by the last step: what a caller of hpgv_group_* receives
+        def fetch(idx):
+            return (m0.d2h(last[0], (V, head // 4), np.int32)[idx],
+                    [m0.d2h(last[i], (V,), np.float64)[idx] for i in GROUP_F64[kind]])
+        dump_outputs(args.dump_outputs, kind, V, fetch)
 
-    def same(got, exp):
-        with np.errstate(invalid="ignore"):
-            return bool(np.all((np.abs(got - exp) <= 1e-10 * np.maximum(1, np.abs(exp))) | (np.isnan(got) & np.isnan(exp))))
-    ok = True
-    for a in range(0, len(idx), 256):
-        sel = idx[a: a + 256]
-        rows = np.stack([orc.synth_matrix(int(v), 1, ncol, ncol)[0] for v in sel])
-        if kind == "tdt":
-            t1, t2 = orc.tdt_counts(rows, *fam)
-            exp = orc.tdt_stats(t1, t2)
-            ok &= bool(np.array_equal(ints[sel], np.stack([t1, t2], 1))) and all(same(fl[j][sel], exp[j]) for j in range(3))
-        elif kind == "stats":
-            for j, v in enumerate(sel):
-                vs = orc.variant_stats(rows[j], 2)
-                exp8 = list(vs.genotypes_count)[:4] + [vs.missing_genotypes, vs.missing_alleles, vs.alleles_count[0], vs.alleles_count[1]]
-                ok &= list(ints[v]) == exp8 and same(fl[1][v: v + 1], np.array([vs.hw_chi2])) and same(fl[2][v: v + 1], np.array([vs.hw_p]))
-        else:
-            A1, A2, U1, U2 = orc.assoc_counts(rows, cond)
-            ok &= bool(np.array_equal(ints[sel], np.stack([A1, A2, U1, U2], 1)))
-            if kind == "chisq":
-                exp = orc.assoc_stats(orc.TASK_CHISQ, A1, A2, U1, U2)
-                ok &= all(same(fl[j][sel], exp[j]) for j in range(3))
-            else:
-                odds, _, p = orc.assoc_stats(orc.TASK_FISHER, A1, A2, U1, U2, lf_table)
-                ok &= same(fl[0][sel], odds) and same(fl[2][sel], p)
     out = {
         "metric": METRIC[kind], "value": V * args.steps / elapsed, "unit": "variants/s", "n_gpus": G, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": scaling,
@@ -827,12 +839,71 @@ def worker_group(args):
                                   "per-device streams, results gathered onto device 0 over the group's own communicator "
                                   "(ncclCommInitAll), each step's gather under the next step's scans" % G},
         "rccl_ranks": ranks,
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
-                     "traffic": None, "traffic_source": None, "measured_in_this_run": ["achieved", "frac", "kernel_ms"],
-                     "kernel": "scan kernel of member 0's shard, alone", "kernel_ms": scan_ms,
-                     "algorithmic_bytes_per_variant": N + res_bytes, "variants_per_launch": hi0 - lo0},
-        "parity": {"checked_variants": int(len(idx)), "ok": bool(ok), "what": "arrays gathered on member 0 vs the oracle, sampled over every member's shard"},
     }
+    ok = True
+    if args.full:
+        # the scan kernel alone on member 0's shard (HIP events on its stream, option "profile"), for the roofline line
+        lo0, hi0 = grp.group_shard(V, 0)
+        m0.set_option("profile", 1)
+        tmp = m0.alloc(head * max(hi0 - lo0, 1))
+        scan_ms = []
+        for _ in range(3):
+            if kind == "tdt":
+                m0.tdt_scan(shards[0], hi0 - lo0, tmp, None, None)
+            elif kind == "stats":
+                m0.stats_scan(shards[0], hi0 - lo0, tmp, None)
+            else:
+                m0.assoc_scan(shards[0], hi0 - lo0, tmp, None, None)
+            scan_ms.append(m0.last_kernel_ms()[0])
+        m0.set_option("profile", 0)
+        scan_ms = float(np.median(scan_ms))
+        achieved = (hi0 - lo0) * (N + res_bytes) / (scan_ms * 1e-3) / 1e9
+
+        # parity: the GATHERED arrays on member 0 against the oracle, sampled over every member's shard
+        from oracle import pyoracle as orc
+        idx = []
+        for k in range(G):
+            lo, hi = grp.group_shard(V, k)
+            n = hi - lo
+            if n:
+                idx.append(lo + np.unique(np.concatenate([np.arange(min(64, n)), np.arange(0, n, max(1000, n // 100)), np.arange(max(0, n - 64), n)])))
+        idx = np.concatenate(idx) if idx else np.zeros(0, np.int64)
+        if kind in ("fisher", "stats"):
+            idx = idx[:: max(1, len(idx) // 400)]
+        ints = m0.d2h(last[0], (V, head // 4), np.int32)
+        fl = [m0.d2h(last[i], (V,), np.float64) for i in (1, 2, 3)]
+        ncol = N if kind != "tdt" else 3 * (N // 3)
+
+        def same(got, exp):
+            with np.errstate(invalid="ignore"):
+                return bool(np.all((np.abs(got - exp) <= 1e-10 * np.maximum(1, np.abs(exp))) | (np.isnan(got) & np.isnan(exp))))
+        for a in range(0, len(idx), 256):
+            sel = idx[a: a + 256]
+            rows = np.stack([orc.synth_matrix(int(v), 1, ncol, ncol)[0] for v in sel])
+            if kind == "tdt":
+                t1, t2 = orc.tdt_counts(rows, *fam)
+                exp = orc.tdt_stats(t1, t2)
+                ok &= bool(np.array_equal(ints[sel], np.stack([t1, t2], 1))) and all(same(fl[j][sel], exp[j]) for j in range(3))
+            elif kind == "stats":
+                for j, v in enumerate(sel):
+                    vs = orc.variant_stats(rows[j], 2)
+                    exp8 = list(vs.genotypes_count)[:4] + [vs.missing_genotypes, vs.missing_alleles, vs.alleles_count[0], vs.alleles_count[1]]
+                    ok &= list(ints[v]) == exp8 and same(fl[1][v: v + 1], np.array([vs.hw_chi2])) and same(fl[2][v: v + 1], np.array([vs.hw_p]))
+            else:
+                A1, A2, U1, U2 = orc.assoc_counts(rows, cond)
+                ok &= bool(np.array_equal(ints[sel], np.stack([A1, A2, U1, U2], 1)))
+                if kind == "chisq":
+                    exp = orc.assoc_stats(orc.TASK_CHISQ, A1, A2, U1, U2)
+                    ok &= all(same(fl[j][sel], exp[j]) for j in range(3))
+                else:
+                    odds, _, p = orc.assoc_stats(orc.TASK_FISHER, A1, A2, U1, U2, lf_table)
+                    ok &= same(fl[0][sel], odds) and same(fl[2][sel], p)
+        out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
+                           "traffic": None, "traffic_source": None, "measured_in_this_run": ["achieved", "frac", "kernel_ms"],
+                           "kernel": "scan kernel of member 0's shard, alone", "kernel_ms": scan_ms,
+                           "algorithmic_bytes_per_variant": N + res_bytes, "variants_per_launch": hi0 - lo0}
+        out["parity"] = {"checked_variants": int(len(idx)), "ok": bool(ok),
+                         "what": "arrays gathered on member 0 vs the oracle, sampled over every member's shard"}
     print(json.dumps(out))
     sys.stdout.flush()
     for m in members:

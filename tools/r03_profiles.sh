@@ -9,7 +9,7 @@ O=$R/gpurun_out
 mkdir -p $O
 cd $R
 python3 __graft_entry__.py > $O/${TAG}_build.log 2>&1 || exit 1
-python3 bench.py > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err || { tail -5 $O/${TAG}_bench_default.err; exit 1; }
+python3 bench.py --full > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err || { tail -5 $O/${TAG}_bench_default.err; exit 1; }
 echo "default bench done"
 ( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats -d $O/${TAG}_prof_m -o m --output-format csv -- python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --configs none > $O/${TAG}_bench_m_under_rocprof.json 2> $O/${TAG}_prof_m.err ) || { tail -5 $O/${TAG}_prof_m.err; exit 1; }
 cp $(find $O/${TAG}_prof_m -name '*kernel_stats.csv' | head -1) $O/${TAG}_bench_m_kernel_stats.csv
@@ -20,7 +20,7 @@ for w in c2 c4 stats; do STEPS=3 bash tools/pmc_traffic.sh $w $TAG || exit 1; do
 echo "pmc traffic done"
 cd $R
 for w in c2 c3 c4 stats c5; do
-    python3 bench.py --workload $w --steps 10 --warmup 2 > $O/${TAG}_bench_$w.json 2> $O/${TAG}_bench_$w.err || { tail -5 $O/${TAG}_bench_$w.err; exit 1; }
+    python3 bench.py --full --workload $w --steps 10 --warmup 2 > $O/${TAG}_bench_$w.json 2> $O/${TAG}_bench_$w.err || { tail -5 $O/${TAG}_bench_$w.err; exit 1; }
 done
 echo "workloads done"
 python3 tools/bench_tokenize.py 10000 16000 > $O/${TAG}_tokenizer_10k_samples.json 2>> $O/${TAG}_text.err || exit 1

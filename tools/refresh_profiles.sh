@@ -8,9 +8,9 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out
 mkdir -p $O
 cd $R
-python bench.py > $O/${TAG}_bench_c2.json 2> $O/${TAG}_bench_c2.err || exit 1
+python bench.py --full > $O/${TAG}_bench_c2.json 2> $O/${TAG}_bench_c2.err || exit 1
 for w in m8 c3 c4 c5; do
-    python bench.py --workload $w --steps 10 --warmup 2 --no-cpu-baseline > $O/${TAG}_bench_$w.json 2> $O/${TAG}_bench_$w.err || exit 1
+    python bench.py --full --workload $w --steps 10 --warmup 2 --no-cpu-baseline > $O/${TAG}_bench_$w.json 2> $O/${TAG}_bench_$w.err || exit 1
 done
 python tools/bench_epistasis.py 16384 10000 10 --cpu > $O/${TAG}_epi_bench_16k.json 2> $O/${TAG}_epi.err || exit 1
 python tools/bench_epistasis.py 16384 10000 5 > $O/${TAG}_epi_bench_16k_5folds.json 2>> $O/${TAG}_epi.err || exit 1

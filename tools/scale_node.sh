@@ -34,22 +34,22 @@ run() {  # name, command...
 for N in $NS; do
     if [ "$REHEARSE" = 1 ]; then
         [ "$N" -gt 4 ] && continue                                   # a GPU box allows few processes on its card
-        SMALL="--variants 400000 --samples 10000 --steps 3 --warmup 1 --no-cpu-baseline --configs none"
+        SMALL="--full --variants 400000 --samples 10000 --steps 3 --warmup 1 --no-cpu-baseline --configs none"
         if [ "$N" = 1 ]; then run "ranks_n$N" python3 bench.py --gpus 1 $SMALL
         else run "ranks_n$N" python3 bench.py --gpus "$N" --backend gloo $SMALL; fi
         DEV=$(python3 -c "print(','.join(['0'] * $N))")
         run "group_n$N" python3 bench.py --gpus "$N" --single-process --devices "$DEV" $SMALL
     else
         [ "$N" -gt "$HAVE" ] && { echo "== N=$N skipped: the node shows $HAVE GPU(s)"; continue; }
-        run "ranks_n$N" python3 bench.py --gpus "$N"
-        run "group_n$N" python3 bench.py --gpus "$N" --single-process --no-cpu-baseline
+        run "ranks_n$N" python3 bench.py --full --gpus "$N"
+        run "group_n$N" python3 bench.py --full --gpus "$N" --single-process --no-cpu-baseline
     fi
 done
 if [ "$REHEARSE" = 1 ]; then
-    run "c5full_rehearsal" python3 bench.py --workload c5full --gpus 2 --backend gloo --variants 200000 --samples 100000 --steps 1 --warmup 0 --no-cpu-baseline
+    run "c5full_rehearsal" python3 bench.py --full --workload c5full --gpus 2 --backend gloo --variants 200000 --samples 100000 --steps 1 --warmup 0 --no-cpu-baseline
     HPGV_DEVICES=0,0 run "file_runner_devices" python3 tools/bench_file_runner.py 2000 20000 bgzf 64
 else
-    [ "$HAVE" -ge 2 ] && run "c5full_n$HAVE" python3 bench.py --workload c5full --gpus "$HAVE" --steps 1 --warmup 0
+    [ "$HAVE" -ge 2 ] && run "c5full_n$HAVE" python3 bench.py --full --workload c5full --gpus "$HAVE" --steps 1 --warmup 0
     HPGV_DEVICES=all run "file_runner_devices" python3 tools/bench_file_runner.py 10000 200000 bgzf 256
 fi
 python3 - "$OUT" <<'PY'
