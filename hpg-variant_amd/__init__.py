@@ -19,6 +19,12 @@ OK = 0
 ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_NOMEM, ERR_STATE, ERR_UNSUPPORTED = 1, 2, 3, 4, 5, 6
 TASK_CHISQ, TASK_FISHER = 1, 2
 EPI_TESTING, EPI_TRAINING = 0, 1
+# the scan kernel a ranking call ran (hpgv_epi_last_rank_info; HPGV_EPI_KERNEL_* of include/hpgv.h)
+(EPI_KERNEL_NONE, EPI_KERNEL_PAIRS_MFMA, EPI_KERNEL_PAIRS_VALU, EPI_KERNEL_TRIPLES_MFMA, EPI_KERNEL_TRIPLES3, EPI_KERNEL_TRIPLES1,
+ EPI_KERNEL_TRIPLES, EPI_KERNEL_COMBS) = range(8)
+EPI_KERNEL_NAMES = {EPI_KERNEL_NONE: "none", EPI_KERNEL_PAIRS_MFMA: "k_epi_pairs_mfma", EPI_KERNEL_PAIRS_VALU: "k_epi_pairs",
+                    EPI_KERNEL_TRIPLES_MFMA: "k_epi_triples_mfma", EPI_KERNEL_TRIPLES3: "k_epi_triples3",
+                    EPI_KERNEL_TRIPLES1: "k_epi_triples1", EPI_KERNEL_TRIPLES: "k_epi_triples", EPI_KERNEL_COMBS: "k_epi_combs"}
 COND_UNAFFECTED, COND_AFFECTED, COND_OTHER = 0, 1, 2
 SEX_MALE, SEX_FEMALE, SEX_UNKNOWN = 0, 1, 2
 LAYOUT_ASSOC, LAYOUT_TDT, LAYOUT_STATS, LAYOUT_STATS_GROUPS, LAYOUT_MENDEL, LAYOUT_EPI = 0, 1, 2, 3, 4, 5
@@ -42,11 +48,17 @@ SYMBOLS = [
     "hpgv_epi_dataset_text", "hpgv_set_text_filters", "hpgv_stats_text", "hpgv_stats_text_groups", "hpgv_epi_set_dataset", "hpgv_epi_set_folds", "hpgv_epi_set_fold_masks", "hpgv_epi_counts",
     "hpgv_epi_counts_all_folds", "hpgv_epi_scan_pairs", "hpgv_epi_rank_pairs", "hpgv_epi_rank_pairs_rows", "hpgv_epi_scan_triples", "hpgv_epi_rank_triples", "hpgv_epi_eval_combs", "hpgv_epi_rank_order", "hpgv_epi_rank_order_rows", "hpgv_read_probe",
     "hpgv_group_comm_init", "hpgv_group_comm_ranks", "hpgv_group_rccl_probe", "hpgv_group_shard", "hpgv_group_assoc", "hpgv_group_tdt", "hpgv_group_stats", "hpgv_group_sync", "hpgv_group_epi_share", "hpgv_group_epi_rank", "hpgv_epi_rank_triples_rows", "hpgv_text_alias_tiles", "hpgv_text_tiles_bytes", "hpgv_bgzf_verify_tiles_dev", "hpgv_memset_dev",
+    "hpgv_epi_last_rank_info",
 ]
 
 
 class HpgvError(RuntimeError):
     pass
+
+
+class EpiRankInfo(C.Structure):
+    """hpgv_epi_rank_info"""
+    _fields_ = [("kernel", C.c_int32), ("launches", C.c_int32), ("relaunches", C.c_int32), ("reserved", C.c_int32)]
 
 
 _lib = None
@@ -173,6 +185,7 @@ def load():
     L.hpgv_group_epi_share.argtypes = [vp, i32, i32, vp, vp]
     L.hpgv_group_epi_rank.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, C.POINTER(C.c_float)]
     L.hpgv_epi_rank_triples_rows.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_float)]
+    L.hpgv_epi_last_rank_info.argtypes = [vp, C.POINTER(EpiRankInfo)]
     _lib = L
     return L
 
@@ -465,6 +478,14 @@ class Engine:
         lo, hi = (0, self._epi[0]) if rows is None else rows
         self._chk(self.L.hpgv_epi_rank_order_rows(self.h, order, lo, hi, subset, n, _ptr(combs), _ptr(acc), _ptr(mask), _ptr(cnt), C.byref(ms)))
         return dict(combs=combs, accuracy=acc, risky=mask, n=cnt, scan_ms=ms.value)
+
+    def epi_last_rank_info(self):
+        """what the last epi_rank_pairs / _triples / _order call ran: kernel (EPI_KERNEL_*), scan launches, and the launches
+        that were repeated because a candidate list overflowed"""
+        info = EpiRankInfo()
+        self._chk(self.L.hpgv_epi_last_rank_info(self.h, C.byref(info)))
+        return dict(kernel=info.kernel, kernel_name=EPI_KERNEL_NAMES.get(info.kernel, "?"), launches=info.launches,
+                    relaunches=info.relaunches)
 
     def epi_dataset(self, gt):
         gt = _np(gt, np.uint8)

@@ -26,6 +26,12 @@ void epi_free_folds(EpiState &E) {
     E.have_folds = false;
 }
 
+// a scan launch of a ranking call (hpgv_epi_last_rank_info): the kernel as the dispatch chose it
+void epi_note_launch(EpiState &E, int kernel) {
+    E.rank_info.kernel = kernel;
+    ++E.rank_info.launches;
+}
+
 void epi_free(EpiState &E) {
     epi_free_folds(E);
     if (E.d_data) (void)hipFree(E.d_data);
@@ -100,7 +106,7 @@ int epi_build_folds(hpgv_ctx *ctx, const int32_t *fold_of_sample, int num_folds)
     HIPCHK(ctx, hipMalloc(&d_src, src.size() * sizeof(int32_t)));
     hipError_t e = hipMemcpy(d_src, src.data(), src.size() * sizeof(int32_t), hipMemcpyHostToDevice);
     // + slack: the LDS-DMA staging fetches whole 32-word rows.  Behind the planes, while the scans' 32-bit word offsets reach it, their
-    // copy with the low seven bits of every byte reversed (hpgv_epi_mfma_kernels.h)
+    // copy with bits 0 and 2 of every nibble swapped (epm_swap02, hpgv_epi_mfma_kernels.h: the matrix-core scans' column side)
     const size_t plane_words = (size_t)E.V_alloc * 3 * (size_t)E.W + hpgv::EPI_CH;
     E.rev_off = 2 * plane_words < (1ull << 32) ? (uint32_t)plane_words : 0u;
     if (e == hipSuccess) {
@@ -186,6 +192,7 @@ int epi_launch_pairs_mfma(hpgv_ctx *ctx, int i_begin, int i_end, hipStream_t st)
     const unsigned n_tiles = (unsigned)total;
     const dim3 grid((n_tiles + 7u) / 8u * 8u);
     if (int rc = epi_upload_folds<TRAINING>(ctx, st)) return rc;
+    epi_note_launch(E, HPGV_EPI_KERNEL_PAIRS_MFMA);
 #define HPGV_EPM_LAUNCH(COMPLETEV)                                                                                                   \
     hipLaunchKernelGGL((hpgv::k_epi_pairs_mfma<TRAINING, BALANCED, COMPLETEV>), grid, dim3(256), 0, st, E.d_planes, E.d_marg, E.rev_off, E.W, \
                        E.V, i_begin, i_first, i_end, E.d_tile_base, n_cols, n_tiles, E.d_chunks, E.d_chunk_cls, E.n_chunks, E.d_folds, E.num_folds, E.nA, E.nU, E.d_thr, E.d_cand, E.d_cand_count, E.cand_cap)
@@ -228,6 +235,7 @@ int epi_launch_pairs2(hpgv_ctx *ctx, int i_begin, int i_end, double *d_acc, uint
     const unsigned n_tiles = (unsigned)total;
     const dim3 grid((n_tiles + 7u) / 8u * 8u);                       // eight spans, one per XCD
     if (int rc = epi_upload_folds<TRAINING>(ctx, st)) return rc;
+    if (candidates) epi_note_launch(E, HPGV_EPI_KERNEL_PAIRS_VALU);
 #define HPGV_EPI_LAUNCH(KK)                                                                                                         \
     hipLaunchKernelGGL((hpgv::k_epi_pairs<KK, TRAINING, BALANCED, COMPLETEV>), grid, dim3(256), 0, st, E.d_planes, E.d_marg, E.W, E.V, i_begin, i_first, i_end, \
                        E.d_tile_base, n_cols, n_tiles, E.d_chunks, E.n_chunks, E.d_folds, E.nA, E.nU, d_acc, d_mask, n_pairs_out, rank_base,                          \
@@ -289,7 +297,10 @@ int hpgv_epi_set_dataset(hpgv_ctx *ctx, const uint8_t *genotypes, int n_variants
     HIPCHK(ctx, hipMalloc(&E.d_data, bytes ? bytes : 16));
     if (bytes) HIPCHK(ctx, hipMemcpy(E.d_data, genotypes, bytes, hipMemcpyHostToDevice));
     E.have_data = true;
-    return epi_build_folds(ctx, nullptr, 1);                         // until folds are given: one fold holding everybody
+    // until folds are given: one fold holding everybody -- unless a class is too large for one (fold, class) group of 16-bit
+    // counts; such a cohort is scanned after hpgv_epi_set_folds splits it
+    if (n_affected >= 65536 || n_unaffected >= 65536) return HPGV_OK;
+    return epi_build_folds(ctx, nullptr, 1);
 }
 
 int hpgv_epi_set_folds(hpgv_ctx *ctx, const int32_t *fold_of_sample, int num_folds) {
@@ -334,7 +345,7 @@ static int epi_cells(int order) { int c = 1; for (int k = 0; k < order; ++k) c *
 // in-fold counts of listed combinations: host vector [(comb * n_groups + g) * cells + c]
 static int epi_infold_counts(hpgv_ctx *ctx, int order, const int32_t *combs, int n_combs, std::vector<int32_t> &out) {
     EpiState &E = ctx->epi;
-    if (!E.have_folds) return fail(ctx, HPGV_ERR_STATE, "hpgv_epi_set_dataset has not been called");
+    if (!E.have_folds) return fail(ctx, HPGV_ERR_STATE, "no folds: hpgv_epi_set_dataset has not been called, or a class of 65536 samples or more waits for hpgv_epi_set_folds");
     if (order < 2 || order > 5) return fail(ctx, HPGV_ERR_UNSUPPORTED, "combinations of %d SNPs are not supported (2 to 5)", order);
     if (n_combs < 0 || (n_combs > 0 && !combs)) return fail(ctx, HPGV_ERR_INVALID, "bad combination list");
     for (int k = 0; k < n_combs * order; ++k)
@@ -413,7 +424,7 @@ int hpgv_epi_scan_pairs(hpgv_ctx *ctx, int i_begin, int i_end, int subset, doubl
     ctx = first_member(ctx);
     if (!ctx) return HPGV_ERR_INVALID;
     EpiState &E = ctx->epi;
-    if (!E.have_folds) return fail(ctx, HPGV_ERR_STATE, "hpgv_epi_set_dataset has not been called");
+    if (!E.have_folds) return fail(ctx, HPGV_ERR_STATE, "no folds: hpgv_epi_set_dataset has not been called, or a class of 65536 samples or more waits for hpgv_epi_set_folds");
     if (subset != HPGV_EPI_TESTING && subset != HPGV_EPI_TRAINING) return fail(ctx, HPGV_ERR_INVALID, "subset must be HPGV_EPI_TESTING or HPGV_EPI_TRAINING");
     if (i_begin < 0 || i_end < i_begin || i_end > E.V) return fail(ctx, HPGV_ERR_INVALID, "rows [%d, %d) outside the dataset", i_begin, i_end);
     const unsigned long long V = (unsigned long long)E.V;
@@ -457,12 +468,13 @@ int hpgv_epi_rank_pairs_rows(hpgv_ctx *ctx, int i_begin, int i_end, int subset, 
     EpiState &E = ctx->epi;
     if (i_begin < 0 || i_end < i_begin || i_end > E.V || (i_begin % 64 && i_begin != i_end))
         return fail(ctx, HPGV_ERR_INVALID, "rows [%d, %d): the band must lie in the dataset and start on a multiple of 64", i_begin, i_end);
-    if (!E.have_folds) return fail(ctx, HPGV_ERR_STATE, "hpgv_epi_set_dataset has not been called");
+    if (!E.have_folds) return fail(ctx, HPGV_ERR_STATE, "no folds: hpgv_epi_set_dataset has not been called, or a class of 65536 samples or more waits for hpgv_epi_set_folds");
     if (subset != HPGV_EPI_TESTING && subset != HPGV_EPI_TRAINING) return fail(ctx, HPGV_ERR_INVALID, "subset must be HPGV_EPI_TESTING or HPGV_EPI_TRAINING");
     if (max_ranking_size < 1 || max_ranking_size > 65536 || !comb_i || !comb_j || !accuracy || !risky_mask || !n_ranked)
         return fail(ctx, HPGV_ERR_INVALID, "bad ranking arguments");
     DeviceGuard g(ctx->device);
     std::lock_guard<std::mutex> lk(ctx->epi_mu);
+    E.rank_info = hpgv_epi_rank_info{};
     const int nf = E.num_folds, N = max_ranking_size;
     const unsigned cap = (unsigned)std::max<long long>(1ll << 20, 64ll * E.V);      // a band of 64 rows with no threshold yet fits
     if (!E.d_cand || E.cand_cap != cap) {
@@ -518,6 +530,7 @@ int hpgv_epi_rank_pairs_rows(hpgv_ctx *ctx, int i_begin, int i_end, int subset, 
         unsigned worst = 0;
         for (int f = 0; f < nf; ++f) worst = count[(size_t)f] > worst ? count[(size_t)f] : worst;
         if (worst > cap) {                                           // some list overflowed: this band again, in smaller pieces
+            ++E.rank_info.relaunches;
             if (e_row - i <= 64) { rc = fail(ctx, HPGV_ERR_UNSUPPORTED, "more than %u models of 64 rows reach a fold's threshold: too many SNPs for the candidate lists", cap); break; }
             band_pairs = pairs / 2 > 0 ? pairs / 2 : 1;
             continue;
@@ -555,6 +568,14 @@ int hpgv_epi_rank_pairs_rows(hpgv_ctx *ctx, int i_begin, int i_end, int subset, 
     if (scan_ms) *scan_ms = total_ms;
     return HPGV_OK;
     HPGV_ABI_CATCH(ctx)
+}
+
+int hpgv_epi_last_rank_info(hpgv_ctx *ctx, hpgv_epi_rank_info *info) {
+    ctx = first_member(ctx);
+    if (!ctx || !info) return HPGV_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(ctx->epi_mu);
+    *info = ctx->epi.rank_info;
+    return HPGV_OK;
 }
 
 // ---- order 3 -------------------------------------------------------------------------------------------------
@@ -612,6 +633,7 @@ int epi_launch_triples(hpgv_ctx *ctx, int i_first, int n_i, double *d_acc, uint3
         if (total16 > (0x7FFFFFFFull >> 8)) return fail(ctx, HPGV_ERR_UNSUPPORTED, "too many first SNPs for one launch of the triple scan");
         HIPCHK(ctx, hipMemcpyAsync(d_jbp, jbp16.data(), jbp16.size() * sizeof(unsigned), hipMemcpyHostToDevice, nullptr));    // (no longer than the lists above: same buffer)
         HIPCHK(ctx, hipMemcpyAsync(d_rb, rb16.data(), rb16.size() * sizeof(unsigned), hipMemcpyHostToDevice, nullptr));
+        epi_note_launch(E, HPGV_EPI_KERNEL_TRIPLES_MFMA);
 #define HPGV_EPM3_LAUNCH(KK, BAL)                                                                                                               \
         hipLaunchKernelGGL((hpgv::k_epi_triples_mfma<KK, TRAINING, BAL>), dim3((unsigned)total16), dim3(256), 0, nullptr, E.d_planes, E.rev_off, E.W, E.V, i_first, d_rb, n_i, \
                            d_jbp, n_jb16, E.d_chunks, E.n_chunks, E.d_folds, E.num_folds, E.nA, E.nU, E.d_thr, d_cand, E.d_cand_count, cap)
@@ -626,6 +648,7 @@ int epi_launch_triples(hpgv_ctx *ctx, int i_first, int n_i, double *d_acc, uint3
     // ranking, at most 10 folds, classes below 65 536 samples: the 27 cells nine at a time (hpgv_epi_triples3_kernels.h): three walks
     // over the samples with a third of the state each, three waves per SIMD
     if (ctx->epi_triples_1pass == 1 && candidates && !d_acc && E.num_folds <= 10 && E.nA < 65536 && E.nU < 65536) {
+        epi_note_launch(E, HPGV_EPI_KERNEL_TRIPLES3);
 #define HPGV_EPI3B_LAUNCH(KK, BAL)                                                                                                              \
         hipLaunchKernelGGL((hpgv::k_epi_triples3<KK, TRAINING, BAL>), grid, dim3(256), 0, nullptr, E.d_planes, E.W, E.V, i_first, d_rb, n_i, d_jbp, n_jb, \
                            E.d_chunks, E.n_chunks, E.d_folds, E.nA, E.nU, E.d_thr, d_cand, E.d_cand_count, cap)
@@ -639,6 +662,7 @@ int epi_launch_triples(hpgv_ctx *ctx, int i_first, int n_i, double *d_acc, uint3
     // (option epi_triples_1pass = 2: the one-pass kernel it replaced -- all 27 K counts in one lane, one wave per SIMD.  Not for unequal
     // classes above 5 folds: that instantiation does not fit the register file)
     if (ctx->epi_triples_1pass == 2 && candidates && !d_acc && E.num_folds <= 10 && E.nA < 65536 && E.nU < 65536 && (balanced || E.num_folds <= 5)) {
+        epi_note_launch(E, HPGV_EPI_KERNEL_TRIPLES1);
 #define HPGV_EPI3_LAUNCH(KK, BAL)                                                                                                               \
         hipLaunchKernelGGL((hpgv::k_epi_triples1<KK, TRAINING, BAL>), grid, dim3(256), 0, nullptr, E.d_planes, E.W, E.V, i_first, d_rb, n_i, d_jbp, n_jb, \
                            E.d_chunks, E.n_chunks, E.d_folds, E.nA, E.nU, E.d_thr, d_cand, E.d_cand_count, cap)
@@ -649,6 +673,7 @@ int epi_launch_triples(hpgv_ctx *ctx, int i_first, int n_i, double *d_acc, uint3
         return HPGV_OK;
     }
 #endif
+    if (candidates) epi_note_launch(E, HPGV_EPI_KERNEL_TRIPLES);
     if (balanced)
         hipLaunchKernelGGL((hpgv::k_epi_triples<TRAINING, true>), grid, dim3(256), 0, nullptr, E.d_planes, E.W, E.V, i_first, d_rb, n_i, d_jbp, n_jb, E.d_chunks, E.n_chunks,
                            E.num_folds, E.d_folds, E.nA, E.nU, d_acc, d_mask, candidates ? E.d_thr : nullptr, d_cand, E.d_cand_count, cap);
@@ -661,7 +686,7 @@ int epi_launch_triples(hpgv_ctx *ctx, int i_first, int n_i, double *d_acc, uint3
 
 int epi_triples_check(hpgv_ctx *ctx, int subset) {
     EpiState &E = ctx->epi;
-    if (!E.have_folds) return fail(ctx, HPGV_ERR_STATE, "hpgv_epi_set_dataset has not been called");
+    if (!E.have_folds) return fail(ctx, HPGV_ERR_STATE, "no folds: hpgv_epi_set_dataset has not been called, or a class of 65536 samples or more waits for hpgv_epi_set_folds");
     if (subset != HPGV_EPI_TESTING && subset != HPGV_EPI_TRAINING) return fail(ctx, HPGV_ERR_INVALID, "subset must be HPGV_EPI_TESTING or HPGV_EPI_TRAINING");
     if (E.nA > 65535 || E.nU > 65535) return fail(ctx, HPGV_ERR_UNSUPPORTED, "the triple scan keeps 16-bit totals: at most 65535 samples per class");
     for (int f = 0; f < E.num_folds; ++f)
@@ -721,6 +746,7 @@ int hpgv_epi_rank_triples_rows(hpgv_ctx *ctx, int i_begin, int i_end, int subset
         return fail(ctx, HPGV_ERR_INVALID, "bad ranking arguments");
     DeviceGuard g(ctx->device);
     std::lock_guard<std::mutex> lk(ctx->epi_mu);
+    E.rank_info = hpgv_epi_rank_info{};
     const int nf = E.num_folds, N = max_ranking_size;
     const long long V = E.V;
     // one first SNP i gives (V - i - 1)(V - i - 2) / 2 triples; a launch without thresholds lists them all
@@ -775,6 +801,7 @@ int hpgv_epi_rank_triples_rows(hpgv_ctx *ctx, int i_begin, int i_end, int subset
         unsigned worst = 0;
         for (int f = 0; f < nf; ++f) worst = std::max(worst, count[(size_t)f]);
         if (worst > cap) {                                           // a list overflowed: the same first SNPs again, fewer at a time
+            ++E.rank_info.relaunches;
             if (n_i <= 1) { rc = fail(ctx, HPGV_ERR_UNSUPPORTED, "more than %u models of one first SNP reach a fold's threshold", cap); break; }
             step = std::max(1, n_i / 2);
             continue;

@@ -17,7 +17,7 @@ struct DevFree { void *p = nullptr; ~DevFree() { if (p) (void)hipFree(p); } };
 
 int generic_check(hpgv_ctx *ctx, int order) {
     EpiState &E = ctx->epi;
-    if (!E.have_folds) return fail(ctx, HPGV_ERR_STATE, "hpgv_epi_set_dataset has not been called");
+    if (!E.have_folds) return fail(ctx, HPGV_ERR_STATE, "no folds: hpgv_epi_set_dataset has not been called, or a class of 65536 samples or more waits for hpgv_epi_set_folds");
     if (order < 2 || order > 5) return fail(ctx, HPGV_ERR_UNSUPPORTED, "combinations of %d SNPs are not supported (2 to 5)", order);
     if (E.nA > 65535 || E.nU > 65535) return fail(ctx, HPGV_ERR_UNSUPPORTED, "the listed-combination kernel keeps 16-bit class totals: at most 65535 samples per class");
     return HPGV_OK;
@@ -41,6 +41,10 @@ int launch_combs(hpgv_ctx *ctx, int order, bool training, const int32_t *d_combs
     EpiState &E = ctx->epi;
     if (n_combs <= 0) return HPGV_OK;
     const hpgv::EpiFold *folds = evaluate ? E.d_folds : nullptr;
+    if (d_cand) {                                                    // a ranking call's launch (hpgv_epi_last_rank_info)
+        E.rank_info.kernel = HPGV_EPI_KERNEL_COMBS;
+        ++E.rank_info.launches;
+    }
 #define HPGV_COMBS(ORD, TR)                                                                                                       \
     hipLaunchKernelGGL((hpgv::k_epi_combs<ORD, TR>), dim3((unsigned)((n_combs + (256 / hpgv::EpiCells<ORD>::value) - 1) / (256 / hpgv::EpiCells<ORD>::value))), \
                        dim3(256), 0, nullptr, E.d_planes, E.W, d_combs, n_combs, E.d_group_w0, E.num_folds, folds, E.nA, E.nU, d_counts, \
@@ -127,6 +131,7 @@ int hpgv_epi_rank_order_rows(hpgv_ctx *ctx, int order, int i_begin, int i_end, i
     if (i_begin < 0 || i_end < i_begin || i_end > E.V) return fail(ctx, HPGV_ERR_INVALID, "first SNPs [%d, %d) outside the dataset", i_begin, i_end);
     if (max_ranking_size < 1 || max_ranking_size > 65536 || !combs_out || !accuracy || !risky_mask || !n_ranked)
         return fail(ctx, HPGV_ERR_INVALID, "bad ranking arguments");
+    E.rank_info = hpgv_epi_rank_info{};
     const int nf = E.num_folds, N = max_ranking_size, V = E.V;
     struct Model { double accuracy; unsigned long long rank; int32_t c[5]; uint32_t risky[hpgv::EPI_MASK_WORDS]; };
     std::vector<std::vector<Model>> top((size_t)nf);

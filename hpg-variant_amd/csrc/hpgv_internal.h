@@ -52,7 +52,8 @@ struct EpiState {
     int V = 0, nA = 0, nU = 0, num_folds = 0, W = 0, V_alloc = 0, n_chunks = 0;
     uint8_t *d_data = nullptr;
     uint32_t *d_planes = nullptr;
-    uint32_t rev_off = 0;             // words from the planes to their copy with the low seven bits of every byte reversed (0: none; k_epi_pairs_mfma's column side)
+    uint32_t rev_off = 0;             // words from the planes to their copy with bits 0 and 2 of every nibble swapped (epm_swap02; 0: no copy, the matrix-core scans do not run)
+    hpgv_epi_rank_info rank_info{};   // what the last ranking call ran (hpgv_epi_last_rank_info): set where the launches decide
     uint32_t *d_marg = nullptr;       // per SNP and (fold, class) group: samples with genotype 0 / 1 (16 bits each)
     bool complete = false;            // the dataset holds no call other than 0 / 1 / 2
     hpgv::EpiChunk *d_chunks = nullptr;
@@ -100,8 +101,9 @@ struct hpgv_ctx {
     long pipe_waves = 4;       // register budget of the pipelined scan, as waves per SIMD (4, 6 or 8)
     long fisher_cut_exp = 22;  // Fisher tails stop after a round whose terms are all below 10^-this of the tail's largest term
     long epi_complete = 1;     // epistasis pair scan on a dataset without missing calls: count four cells, derive the other five
-    long epi_pairs_mfma = 1;   // epistasis pair ranking, <= 10 folds, data with missing calls: cell counts on the matrix cores (k_epi_pairs_mfma); 0 = k_epi_pairs
-    long epi_triples_mfma = 1; // epistasis triple ranking, <= 10 folds: cell counts on the matrix cores (k_epi_triples_mfma); 0 = the vector-ALU scans below
+    long epi_pairs_mfma = 1;   // epistasis pair ranking, any fold count, data with or without missing calls: cell counts on the matrix cores (k_epi_pairs_mfma) while
+                               // both classes stay below 65 536 samples, the samples fit EPM_MAX_CHUNKS staging chunks and the planes' swapped copy exists (rev_off); 0 = k_epi_pairs
+    long epi_triples_mfma = 1; // epistasis triple ranking, any fold count: cell counts on the matrix cores (k_epi_triples_mfma) under the same three conditions; 0 = the vector-ALU scans below
     long epi_triples_1pass = 1; // epistasis triple ranking with at most 10 folds: 1 = the 27 cells nine at a time (three walks, three waves per SIMD); 0 = the two-pass kernel; 2 (ablation build) = one pass with all counts in one lane
     long scan_lds = 0;         // bytes of (unused) LDS per workgroup of the stats / tdt scans: caps the waves in flight per CU
     long fisher_width = 16;    // lanes per variant in the Fisher p-pass (64, 32, 16 or 8): 64 / width variants per wave

@@ -93,7 +93,10 @@ const char *hpgv_last_error(const hpgv_ctx *ctx);
  *   "batch_fused" 0/1, "batch_copy" 0/1   per-batch host entry points: one fused kernel reading page-locked rows in place
  *                                (default) / the kernel chain / copy the rows first
  *   "epi_complete" 0/1, "epi_triples_1pass" 0/1     epistasis scans: the shortcuts for data without missing calls / <= 10 folds
- *   "epi_pairs_mfma", "epi_triples_mfma" 0/1 (default 1)   epistasis pair / triple ranking: cell counts on the matrix cores (0: the vector-ALU scans)
+ *   "epi_pairs_mfma", "epi_triples_mfma" 0/1 (default 1)   epistasis pair / triple ranking: cell counts on the matrix cores (0: the vector-ALU scans;
+ *                                    whatever the option, the vector ALU when a class holds 65 536 samples or more or the
+ *                                    samples with their padding need more than 128 staging chunks or the genotype planes'
+ *                                    second copy finds no room: hpgv_epi_last_rank_info says which ran)
  *   "group_self_exchange" 0/1    (group contexts; tests) member 0 hands its results over through the communicator too
  * Every kernel ships in ONE form.  The forms that lost their A/B comparisons (profiles/experiments_that_did_not_pay.md) are
  * compiled only into an ablation build (-DHPGV_ABLATION: tools/build_ablation.py, used by tools/ only); there the keys
@@ -381,7 +384,8 @@ int  hpgv_epi_dataset_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, i
  * (get_genotype_combinations, dataset.c:170-200): order 2 -> cell = g_i * 3 + g_j. */
 enum { HPGV_EPI_TESTING = 0, HPGV_EPI_TRAINING = 1 };                 /* enum evaluation_subset, model.h:73 */
 
-/* copies the dataset to the device; until folds are given all samples form one fold */
+/* copies the dataset to the device; until folds are given all samples form one fold (none when a class holds 65536 samples
+ * or more: such a cohort needs hpgv_epi_set_folds before any scan) */
 int  hpgv_epi_set_dataset(hpgv_ctx *ctx, const uint8_t *genotypes, int n_variants, int n_affected, int n_unaffected);
 /* k-fold cross-validation: fold_of_sample[s] in [0, num_folds) = the fold whose TESTING part holds sample s
  * (get_k_folds, cross_validation.c:16-100); num_folds <= 16, fewer than 65536 samples per class and fold */
@@ -447,6 +451,28 @@ int  hpgv_epi_rank_order(hpgv_ctx *ctx, int order, int subset, int max_ranking_s
                          uint32_t *risky_mask, int32_t *n_ranked, float *scan_ms);
 int  hpgv_epi_rank_order_rows(hpgv_ctx *ctx, int order, int i_begin, int i_end, int subset, int max_ranking_size,
                               int32_t *combs_out, double *accuracy, uint32_t *risky_mask, int32_t *n_ranked, float *scan_ms);
+
+/* what the last hpgv_epi_rank_pairs[_rows] / _triples[_rows] / _order[_rows] call of this context ran: the scan kernel its
+ * launches used (as the dispatch chose it: the options ask for a kernel, the dataset's shape can rule it out), the number of
+ * scan launches, and how many of them had to be repeated because a fold's candidate list overflowed.
+ * kernel = HPGV_EPI_KERNEL_NONE when the call launched nothing. */
+enum {
+    HPGV_EPI_KERNEL_NONE = 0,
+    HPGV_EPI_KERNEL_PAIRS_MFMA = 1,      /* k_epi_pairs_mfma: pair cell counts on the matrix cores */
+    HPGV_EPI_KERNEL_PAIRS_VALU = 2,      /* k_epi_pairs: pair cell counts on the vector ALU */
+    HPGV_EPI_KERNEL_TRIPLES_MFMA = 3,    /* k_epi_triples_mfma */
+    HPGV_EPI_KERNEL_TRIPLES3 = 4,        /* k_epi_triples3: the 27 cells nine at a time */
+    HPGV_EPI_KERNEL_TRIPLES1 = 5,        /* k_epi_triples1 (ablation builds only) */
+    HPGV_EPI_KERNEL_TRIPLES = 6,         /* k_epi_triples: two passes */
+    HPGV_EPI_KERNEL_COMBS = 7            /* k_epi_combs: listed combinations of any order */
+};
+typedef struct hpgv_epi_rank_info {
+    int32_t kernel;                      /* HPGV_EPI_KERNEL_* */
+    int32_t launches;                    /* scan launches, relaunches included */
+    int32_t relaunches;                  /* launches whose candidate list overflowed: their rows were scanned again, fewer at a time */
+    int32_t reserved;
+} hpgv_epi_rank_info;
+int  hpgv_epi_last_rank_info(hpgv_ctx *ctx, hpgv_epi_rank_info *info);
 
 /* Mendelian errors of a host batch: errors[v] per variant (may be NULL) and child_errors[t] per trio of
  * hpgv_set_pedigree, ACCUMULATED into (may be NULL) */

@@ -52,17 +52,17 @@ void orc_epi_counts_all_folds(int order, const uint8_t *const *rows, int n_affec
                               const uint8_t *fold_masks, int num_folds,
                               int32_t *counts_aff, int32_t *counts_unaff) {
     const int cells = ipow3(order), n = n_affected + n_unaffected;
-    for (int f = 0; f < num_folds; f++)
-        for (int c = 0; c < cells; c++) {
-            int aff = 0, unaff = 0;
-            for (int s = 0; s < n; s++) {
-                if (!(fold_masks[(size_t)f * n + s] & 1)) continue;
-                int match = 1;
-                for (int j = 0; j < order && match; j++) match = rows[j][s] == cell_genotype(order, c, j);
-                if (match) { if (s < n_affected) aff++; else unaff++; }
-            }
-            counts_aff[f * cells + c] = aff; counts_unaff[f * cells + c] = unaff;
-        }
+    for (int i = 0; i < num_folds * cells; i++) counts_aff[i] = counts_unaff[i] = 0;
+    /* sample by sample: its cell (the genotypes as base-3 digits, the last SNP the lowest: the numbering of
+     * cell_genotype), none when a call is missing; then one count in every fold whose training part holds it */
+    for (int s = 0; s < n; s++) {
+        int c = 0, j = 0;
+        for (; j < order && rows[j][s] <= 2; j++) c = c * 3 + rows[j][s];
+        if (j < order) continue;
+        int32_t *counts = s < n_affected ? counts_aff : counts_unaff;
+        for (int f = 0; f < num_folds; f++)
+            if (fold_masks[(size_t)f * n + s] & 1) counts[f * cells + c]++;
+    }
 }
 
 /* mdr_high_risk_combinations, mdr.c:23-42 (double arithmetic; used by the reference's tests) */
@@ -190,5 +190,28 @@ void orc_epi_scan_pairs(const uint8_t *dataset, int n_variants, int n_affected, 
             orc_epi_model(2, rows, n_affected, n_unaffected, fold_masks, num_folds, subset, acc, rm, NULL);
             for (int f = 0; f < num_folds; f++) { accuracy[(size_t)f * n_pairs + p] = acc[f]; risky_mask[(size_t)f * n_pairs + p] = rm[f]; }
         }
+    }
+}
+
+/* every triple i < j < k of the dataset, the same model of order 3: accuracy[f * n_triples + t],
+ * risky_mask[f * n_triples + t] with t = the triple's rank in lexicographic order
+ * ((0,1,2), (0,1,3), ..., (0,2,3), ..., (1,2,3), ...) */
+void orc_epi_scan_triples(const uint8_t *dataset, int n_variants, int n_affected, int n_unaffected,
+                          const uint8_t *fold_masks, int num_folds, int subset,
+                          double *accuracy, uint32_t *risky_mask) {
+    const size_t n = (size_t)(n_affected + n_unaffected), V = n_variants > 0 ? (size_t)n_variants : 0;
+    const size_t n_triples = V >= 3 ? V * (V - 1) * (V - 2) / 6 : 0;
+    #pragma omp parallel for schedule(dynamic, 1)
+    for (int i = 0; i < n_variants; i++) {
+        double acc[64]; uint32_t rm[64];
+        /* triples before the first one of i: those whose first SNP is below i */
+        const size_t r = (size_t)i, after = V - r;
+        size_t t = n_triples - (after >= 3 ? after * (after - 1) * (after - 2) / 6 : 0);
+        for (int j = i + 1; j < n_variants; j++)
+            for (int k = j + 1; k < n_variants; k++, t++) {
+                const uint8_t *rows[3] = { dataset + (size_t)i * n, dataset + (size_t)j * n, dataset + (size_t)k * n };
+                orc_epi_model(3, rows, n_affected, n_unaffected, fold_masks, num_folds, subset, acc, rm, NULL);
+                for (int f = 0; f < num_folds; f++) { accuracy[(size_t)f * n_triples + t] = acc[f]; risky_mask[(size_t)f * n_triples + t] = rm[f]; }
+            }
     }
 }

@@ -196,6 +196,9 @@ void orc_epi_model_wide(int order, const uint8_t *const *rows, int n_affected, i
 void orc_epi_scan_pairs(const uint8_t *dataset, int n_variants, int n_affected, int n_unaffected,
                         const uint8_t *fold_masks, int num_folds, int subset,
                         double *accuracy, uint32_t *risky_mask);
+void orc_epi_scan_triples(const uint8_t *dataset, int n_variants, int n_affected, int n_unaffected,
+                          const uint8_t *fold_masks, int num_folds, int subset,
+                          double *accuracy, uint32_t *risky_mask);
 
 #ifdef __cplusplus
 }

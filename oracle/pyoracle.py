@@ -450,6 +450,19 @@ def epi_scan_pairs(dataset, n_affected, n_unaffected, fold_masks, subset):
     return acc, rm
 
 
+def epi_scan_triples(dataset, n_affected, n_unaffected, fold_masks, subset):
+    """Every triple i < j < k in lexicographic order: accuracy[f][t], risky_mask[f][t]."""
+    d = np.ascontiguousarray(dataset, dtype=np.uint8)
+    fm = np.ascontiguousarray(fold_masks, dtype=np.uint8)
+    v, k = d.shape[0], fm.shape[0]
+    assert k <= 64 and d.shape[1] == n_affected + n_unaffected == fm.shape[1]
+    n_triples = v * (v - 1) * (v - 2) // 6
+    acc, rm = np.zeros((k, n_triples), np.float64), np.zeros((k, n_triples), np.uint32)
+    lib().orc_epi_scan_triples(_p(d, C.c_uint8), v, n_affected, n_unaffected, _p(fm, C.c_uint8), k, subset,
+                               _p(acc, C.c_double), _p(rm, C.c_uint32))
+    return acc, rm
+
+
 def fold_masks_from_assignment(fold_of_sample, num_folds):
     """get_k_folds_masks (cross_validation.c:247-281) without the SSE padding: mask[f][s] = 0 when sample s
     is in the testing part of fold f, 1 otherwise."""

@@ -175,3 +175,32 @@ def epi_counts_from_reference_masks(kat_masks, num_affected, num_unaffected, ord
         aff.append(int(np.unpackbits(x[:num_affected]).sum() // 8))
         unaff.append(int(np.unpackbits(x[pad_a: pad_a + num_unaffected]).sum() // 8))
     return aff, unaff
+
+
+def oracle_top(acc, rm, combs, N):
+    """The per-fold ranking contract of include/hpgv.h (hpgv_epi_rank_pairs / _triples): of the models of a dense oracle scan
+    (acc, rm: folds x models; combs: models x order SNP indices in lexicographic order) the best N per fold, ordered by
+    (-accuracy, i, j[, k]), NaN accuracies left out: n = min(N, non-NaN models).  Arrays shaped like the engine's outputs
+    (folds x N; entries past n are 0)."""
+    acc, rm, combs = np.asarray(acc), np.asarray(rm), np.asarray(combs)
+    k, order = acc.shape[0], combs.shape[1]
+    out = {key: np.zeros((k, N), np.int32) for key in "ijk"[:order]}
+    out.update(accuracy=np.zeros((k, N), np.float64), risky=np.zeros((k, N), np.uint32), n=np.zeros(k, np.int32))
+    for f in range(k):
+        ok = np.flatnonzero(~np.isnan(acc[f]))
+        # the models are listed in lexicographic order: a stable sort by accuracy alone breaks ties by (i, j[, k])
+        best = ok[np.argsort(-acc[f][ok], kind="stable")[:N]]
+        n = len(best)
+        out["n"][f] = n
+        for s, key in enumerate("ijk"[:order]):
+            out[key][f][:n] = combs[best, s]
+        out["accuracy"][f][:n] = acc[f][best]
+        out["risky"][f][:n] = rm[f][best]
+    return out
+
+
+def all_combs(n_variants, order):
+    """Every combination i < j [< k] of n_variants SNPs in lexicographic order (the oracle scans' model order)."""
+    import itertools
+    c = np.array(list(itertools.combinations(range(n_variants), order)), np.int32)
+    return c.reshape(-1, order)

@@ -4,7 +4,7 @@ against an independent numpy statement of the same definitions.  CPU only."""
 import numpy as np
 import pytest
 
-from helpers import epi_counts_from_reference_masks, epi_random_dataset, epi_random_folds, epi_unpad
+from helpers import all_combs, epi_counts_from_reference_masks, epi_random_dataset, epi_random_folds, epi_unpad, oracle_top
 from oracle import pyoracle as orc
 
 
@@ -229,3 +229,45 @@ def test_count_invariants_of_the_oracle():
     a01, _ = orc.epi_counts([data[0], data[1]], nA, nU)
     a10, _ = orc.epi_counts([data[1], data[0]], nA, nU)
     assert np.array_equal(a01.reshape(3, 3), a10.reshape(3, 3).T)
+
+
+@pytest.mark.parametrize("v,nA,nU,k,p_missing", [(13, 41, 37, 3, 0.05), (9, 20, 20, 1, 0.0), (11, 2, 25, 4, 0.1)])
+def test_triple_scan_is_the_model_triple_by_triple(v, nA, nU, k, p_missing):
+    # the dense triple scan (what the GPU triple rankings are checked against) is orc_epi_model(3, ...) of every triple, in
+    # lexicographic order, both subsets; the last shape has folds without cases (NaN accuracies)
+    rng = np.random.default_rng(v * 5 + k)
+    data = epi_random_dataset(rng, v, nA, nU, p_missing=p_missing)
+    data[4] = 1                                                       # a monomorphic SNP: empty cells
+    fold = np.asarray(epi_random_folds(rng, nA, nU, k))
+    masks = orc.fold_masks_from_assignment(fold, k)
+    triples = all_combs(v, 3)
+    assert len(triples) == v * (v - 1) * (v - 2) // 6
+    for subset in (0, 1):
+        acc, rm = orc.epi_scan_triples(data, nA, nU, masks, subset)
+        assert acc.shape == rm.shape == (k, len(triples))
+        for t, (a, b, c) in enumerate(triples):
+            ea, em, _ = orc.epi_model([data[a], data[b], data[c]], nA, nU, masks, subset)
+            assert np.array_equal(rm[:, t], em), (a, b, c)
+            assert np.all((acc[:, t] == ea) | (np.isnan(acc[:, t]) & np.isnan(ea))), (a, b, c)
+        if nA < k and subset == 0:                                    # testing parts without cases: 0/0
+            assert np.isnan(acc).any()
+        # the ranking contract on it: (-accuracy, i, j, k), NaN left out
+        top = oracle_top(acc, rm, triples, 7)
+        for f in range(k):
+            keys = sorted((-acc[f][t], tuple(triples[t])) for t in range(len(triples)) if not np.isnan(acc[f][t]))[:7]
+            n = len(keys)
+            assert top["n"][f] == n
+            assert [(int(x), int(y), int(z)) for x, y, z in zip(top["i"][f][:n], top["j"][f][:n], top["k"][f][:n])] == [c for _, c in keys]
+            assert np.array_equal(top["accuracy"][f][:n], np.array([-a for a, _ in keys]))
+
+
+def test_pair_scan_order_is_all_combs():
+    # the pair scan's model order is that of all_combs (what oracle_top reads the SNP indices from)
+    rng = np.random.default_rng(3)
+    v, nA, nU, k = 10, 30, 25, 2
+    data = epi_random_dataset(rng, v, nA, nU)
+    masks = orc.fold_masks_from_assignment(np.asarray(epi_random_folds(rng, nA, nU, k)), k)
+    acc, rm = orc.epi_scan_pairs(data, nA, nU, masks, 0)
+    for p, (a, b) in enumerate(all_combs(v, 2)):
+        ea, em, _ = orc.epi_model([data[a], data[b]], nA, nU, masks, 0)
+        assert np.array_equal(rm[:, p], em) and np.all((acc[:, p] == ea) | (np.isnan(ea) & np.isnan(acc[:, p])))

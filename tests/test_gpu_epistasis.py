@@ -281,6 +281,8 @@ def test_matrix_core_ranking_is_the_vector_alu_ranking(eng, v, nA, nU, k, p_miss
                 for mfma in (1, 0):
                     eng.set_option("epi_pairs_mfma", mfma)
                     res[mfma] = eng.epi_rank_pairs(subset, n)
+                    # the scan that ran, as the library reports it: the two sides are two different kernels
+                    assert eng.epi_last_rank_info()["kernel"] == (hpgv.EPI_KERNEL_PAIRS_MFMA if mfma else hpgv.EPI_KERNEL_PAIRS_VALU)
                 for f in range(k):
                     m = int(res[0]["n"][f])
                     assert int(res[1]["n"][f]) == m and m > 0
@@ -309,6 +311,8 @@ def test_matrix_core_triple_ranking_is_the_vector_alu_ranking(eng, v, nA, nU, k,
                 for mfma in (1, 0):
                     eng.set_option("epi_triples_mfma", mfma)
                     res[mfma] = eng.epi_rank_triples(subset, n)
+                    assert eng.epi_last_rank_info()["kernel"] == (hpgv.EPI_KERNEL_TRIPLES_MFMA if mfma else
+                                                                  hpgv.EPI_KERNEL_TRIPLES3 if k <= 10 else hpgv.EPI_KERNEL_TRIPLES)
                 for f in range(k):
                     m = int(res[0]["n"][f])
                     assert int(res[1]["n"][f]) == m and m > 0

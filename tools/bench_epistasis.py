@@ -54,6 +54,7 @@ if ORDER == 3:
         res = e.epi_rank_triples(hpgv.EPI_TESTING, 10)
         runs.append((time.perf_counter() - t0, res["scan_ms"]))
     wall, scan_ms = min(runs)
+    ran = e.epi_last_rank_info()["kernel_name"]                # the kernel the library ran, not the one the options asked for
     triples = V * (V - 1) * (V - 2) // 6
     words = (-(-(nA // K) // 128) + -(-(nU // K) // 128)) * 4 * K
     wave_instr = triples * words * 54 / 64
@@ -63,17 +64,14 @@ if ORDER == 3:
             "roofline": {"bound": "valu", "achieved": wave_instr / (scan_ms * 1e-3) / 1e9, "peak": peak / 1e9,
                          "unit": "G wave64 VALU instructions/s", "frac": wave_instr / (scan_ms * 1e-3) / peak,
                          "algorithmic_ops_per_triple_word": 54}}
-    opts = dict(a[len('--option='):].split('=') for a in sys.argv[1:] if a.startswith('--option='))
-    if int(opts.get("epi_triples_mfma", 1)) and K <= 16:
+    line["kernel"] = ran
+    if ran == "k_epi_triples_mfma":
         # the matrix-core scan (k_epi_triples_mfma): 27 cells x samples (padded) x 2 flop per triple are the algorithm's; dense FP4
         # peak from MI355X_MICROARCH.md (see the pair line's note on the issue rate measured here)
         flops = triples * 27 * words * 32 * 2
-        line["kernel"] = "k_epi_triples_mfma"
         line["roofline_vector_scan_equivalent"] = line["roofline"]
         line["roofline"] = {"bound": "mfma", "achieved": flops / (scan_ms * 1e-3) / 1e12, "peak": 10000.0, "unit": "TFLOP/s (FP4, dense)",
                             "frac": flops / (scan_ms * 1e-3) / 1e16, "algorithmic_flop_per_triple_and_sample": 54}
-    else:
-        line["kernel"] = "k_epi_triples3" if K <= 10 and int(opts.get("epi_triples_1pass", 1)) else "k_epi_triples"
     print(json.dumps(line))
     e.close()
     sys.exit(0)
@@ -84,6 +82,7 @@ for _ in range(3):
     res = e.epi_rank_pairs(hpgv.EPI_TESTING, 10)
     runs.append((time.perf_counter() - t0, res["scan_ms"]))
 wall, scan_ms = min(runs)
+ran = e.epi_last_rank_info()["kernel_name"]                    # the kernel the library ran, not the one the options asked for
 pairs = V * (V - 1) // 2
 words = (-(-(nA // K) // 128) + -(-(nU // K) // 128)) * 4 * K   # words per row after padding every (fold, class) run to 4 words
 ops = pairs * words * 18
@@ -98,19 +97,16 @@ wave_instr = ops / 64
 out["roofline"] = {"bound": "valu", "achieved": wave_instr / (scan_ms * 1e-3) / 1e9, "peak": peak_wave_instr / 1e9,
                    "unit": "G wave64 VALU instructions/s", "frac": wave_instr / (scan_ms * 1e-3) / peak_wave_instr,
                    "algorithmic_ops_per_pair_word": 18}
-opts = dict(a[len('--option='):].split('=') for a in sys.argv[1:] if a.startswith('--option='))
-if int(opts.get("epi_pairs_mfma", 1)):                        # (data without missing calls takes the matrix-core scan too)
+out["kernel"] = ran
+if ran == "k_epi_pairs_mfma":                                  # (data without missing calls takes the matrix-core scan too)
     # the matrix-core scan (hpgv_epi_mfma_kernels.h): 9 cells x samples (padded to 128 per group) x 2 flop per pair are the
     # algorithm's; the kernel walks the samples twice.  Peak: dense FP4 (MI355X_MICROARCH.md); the kernel is vector-issue
     # bound (16.7 k vector instructions per 256 pairs) and v_mfma_scale_f32_16x16x128_f8f6f4 issues every 33 cycles here
     # back to back (tools/exp/mfma_rate.hip), about half the rate that peak assumes
     flops = pairs * 9 * words * 32 * 2
-    out["kernel"] = "k_epi_pairs_mfma"
     out["roofline_vector_scan_equivalent"] = out["roofline"]
     out["roofline"] = {"bound": "mfma", "achieved": flops / (scan_ms * 1e-3) / 1e12, "peak": 10000.0, "unit": "TFLOP/s (FP4, dense)",
                        "frac": flops / (scan_ms * 1e-3) / 1e16, "algorithmic_flop_per_pair_and_sample": 18}
-else:
-    out["kernel"] = "k_epi_pairs"
 if COMPLETE and out["kernel"] == "k_epi_pairs":
     out["roofline"]["note"] = "complete data: 8 operations per pair and word are executed; frac is quoted at the general case's 18"
     out["roofline"]["frac_at_8_ops"] = out["roofline"]["frac"] * 8 / 18
