@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include "hpgv_text_kernels.h"
 #include "hpgv_text2_kernels.h"
+#include "hpgv_partition_kernels.h"
 #include "hpgv_batch_kernels.h"
 
 namespace {
@@ -419,6 +420,9 @@ int hpgv_set_option(hpgv_ctx *ctx, const char *key, long value) {
     } else if (!strcmp(key, "persistent")) {
         HPGV_SHIPPED_ONLY(value == 0, "persistent = 1")
         ctx->persistent = value ? 1 : 0;
+    } else if (!strcmp(key, "part_aligned_loads")) {
+        HPGV_SHIPPED_ONLY(value == 0, "part_aligned_loads = 1")
+        ctx->part_aligned = value ? 1 : 0;
     } else if (!strcmp(key, "blocks_per_cu")) {
         if (value < 1 || value > 8) return fail(ctx, HPGV_ERR_INVALID, "blocks_per_cu must be in 1..8");
         ctx->blocks_per_cu = value;
@@ -2431,6 +2435,147 @@ int hpgv_epi_dataset_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, in
     }
     HIPCHK(ctx, hipStreamSynchronize(s->stream));
     return HPGV_OK;
+}
+
+/* ---- stable partition of lines: kept lines, then the others (hpg-var-vcf filter: .filtered / .rejected) ---- */
+
+size_t hpgv_lines_partition_scratch_bytes(int n_lines) {
+    if (n_lines <= 0) return 0;
+    const size_t hb = ((size_t)n_lines + 1023) / 1024;
+    return ((size_t)n_lines + 1 + hb) * sizeof(unsigned long long);
+}
+
+// the launches of one partition on `st`: kept_off and the block sums in d_scratch, then the copy
+static int partition_launch(hpgv_ctx *ctx, const char *d_text, const unsigned long long *d_line_off, int n_lines,
+                            const uint8_t *d_keep, char *d_out, unsigned long long *d_kept_bytes, void *d_scratch, hipStream_t st) {
+    if (n_lines == 0) {
+        if (d_kept_bytes) HIPCHK(ctx, hipMemsetAsync(d_kept_bytes, 0, sizeof(unsigned long long), st));
+        return HPGV_OK;
+    }
+    const int hb = (n_lines + 1023) / 1024;
+    unsigned long long *kept_off = (unsigned long long *)d_scratch, *block = kept_off + (size_t)n_lines + 1;
+    hipLaunchKernelGGL(hpgv::k_kept_sums, dim3((unsigned)hb), dim3(1024), 0, st, d_line_off, d_keep, n_lines, block);
+    hipLaunchKernelGGL(hpgv::k_head_bases, dim3(1), dim3(1024), 0, st, block, hb);
+    hipLaunchKernelGGL(hpgv::k_kept_offsets, dim3((unsigned)hb), dim3(1024), 0, st, d_line_off, d_keep, n_lines,
+                       (const unsigned long long *)block, kept_off);
+    // whole waves striding over the lines: at least one line per wave, at most 8 workgroups of 4 waves per CU
+    const long cap = 8L * (ctx->n_cus > 0 ? ctx->n_cus : 256);
+    const long blocks = std::min<long>(((long)n_lines + 3) / 4, cap);
+#ifdef HPGV_ABLATION
+    if (ctx->part_aligned)
+        hipLaunchKernelGGL(hpgv::k_part_copy<1>, dim3((unsigned)blocks), dim3(256), 0, st, d_text, d_line_off, n_lines, d_keep,
+                           (const unsigned long long *)kept_off, d_out, d_kept_bytes);
+    else
+#endif
+        hipLaunchKernelGGL(hpgv::k_part_copy<0>, dim3((unsigned)blocks), dim3(256), 0, st, d_text, d_line_off, n_lines, d_keep,
+                           (const unsigned long long *)kept_off, d_out, d_kept_bytes);
+    HIPCHK(ctx, hipGetLastError());
+    return HPGV_OK;
+}
+
+int hpgv_lines_partition_dev(hpgv_ctx *ctx, const char *d_text, const uint64_t *d_line_off, int n_lines, const uint8_t *d_keep,
+                             char *d_out, uint64_t *d_kept_bytes, void *d_scratch, void *stream) {
+    HPGV_ABI_TRY
+    ctx = first_member(ctx);
+    if (!ctx) return HPGV_ERR_INVALID;
+    if (n_lines < 0 || (n_lines > 0 && (!d_text || !d_line_off || !d_keep || !d_out || !d_scratch)))
+        return fail(ctx, HPGV_ERR_INVALID, "bad lines_partition_dev arguments");
+    DeviceGuard g(ctx->device);
+    return partition_launch(ctx, d_text, (const unsigned long long *)d_line_off, n_lines, d_keep, d_out,
+                            (unsigned long long *)d_kept_bytes, d_scratch, (hipStream_t)stream);
+    HPGV_ABI_CATCH(ctx)
+}
+
+// the hold hpgv_filter_text left on `host_text` (taken out of the list), or false
+static bool take_held(hpgv_ctx *ctx, const char *host_text, hpgv_ctx::TextHeld *out) {
+    std::lock_guard<std::mutex> lk(ctx->alias_mu);
+    for (size_t i = 0; i < ctx->text_held.size(); ++i)
+        if (ctx->text_held[i].host_text == host_text) { *out = ctx->text_held[i]; ctx->text_held.erase(ctx->text_held.begin() + (long)i); return true; }
+    return false;
+}
+
+int hpgv_filter_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, int max_lines, int *n_lines,
+                     uint64_t *line_off, uint32_t *field_off, int32_t *status) {
+    HPGV_ABI_TRY
+    if (is_group(ctx)) {
+        for (hpgv_ctx *m : ctx->members) (void)hpgv_text_partition(m, text, nullptr, 0, nullptr, 0, nullptr, nullptr);   // an earlier hold on this text
+        if (hpgv_ctx *m_ = alias_owner(ctx, text)) return hpgv_filter_text(m_, text, text_bytes, max_lines, n_lines, line_off, field_off, status);
+        Dealt d_(ctx); hpgv_ctx *m_ = d_.m; return hpgv_filter_text(m_, text, text_bytes, max_lines, n_lines, line_off, field_off, status);
+    }
+    if (!ctx) return HPGV_ERR_INVALID;
+    if (!ctx->stats.set) return fail(ctx, HPGV_ERR_STATE, "hpgv_set_stats_cohort has not been called");
+    if (!n_lines || max_lines < 0 || !text || (max_lines > 0 && (!line_off || !field_off || !status)))
+        return fail(ctx, HPGV_ERR_INVALID, "bad filter_text arguments");
+    (void)hpgv_text_partition(ctx, text, nullptr, 0, nullptr, 0, nullptr, nullptr);
+    *n_lines = 0;
+    if (max_lines == 0) return HPGV_OK;
+    DeviceGuard g(ctx->device);
+    SlotLease lease(ctx);
+    int rc = acquire_slot(ctx, &lease.s);
+    if (rc) return rc;
+    Slot *s = lease.s;
+    int nl = 0;
+    if ((rc = text_front(ctx, s, HPGV_LAYOUT_STATS, ctx->stats, text, text_bytes, max_lines, n_lines, line_off, field_off, status, &nl, false))) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(s->stream));
+    if (*n_lines > max_lines) return HPGV_OK;                      // the caller grows its arrays and calls again
+    const char *d_src = text_on_device(ctx, text);
+    hpgv_ctx::TextHeld h{text, s, d_src ? d_src : (const char *)s->buf[0], (const unsigned long long *)((char *)s->buf[6] + 16), nl};
+    {
+        std::lock_guard<std::mutex> lk(ctx->alias_mu);
+        ctx->text_held.push_back(h);
+    }
+    lease.s = nullptr;                                              // the slot stays leased to the hold
+    return HPGV_OK;
+    HPGV_ABI_CATCH(ctx)
+}
+
+int hpgv_text_partition(hpgv_ctx *ctx, const char *text, const uint8_t *keep, int n_lines, char *out, size_t out_cap,
+                        uint64_t *kept_bytes, uint64_t *total_bytes) {
+    HPGV_ABI_TRY
+    if (is_group(ctx)) {
+        int rc = HPGV_OK, found = 0;
+        for (hpgv_ctx *m : ctx->members) {
+            bool held;
+            { std::lock_guard<std::mutex> lk(m->alias_mu); held = false; for (const auto &h : m->text_held) if (h.host_text == text) held = true; }
+            if (held) { found = 1; rc = hpgv_text_partition(m, text, keep, n_lines, out, out_cap, kept_bytes, total_bytes); }
+        }
+        if (!found && keep) return fail(ctx, HPGV_ERR_STATE, "no hpgv_filter_text call holds this text");
+        return rc;
+    }
+    if (!ctx) return HPGV_ERR_INVALID;
+    hpgv_ctx::TextHeld h;
+    if (!take_held(ctx, text, &h)) return keep ? fail(ctx, HPGV_ERR_STATE, "no hpgv_filter_text call holds this text") : HPGV_OK;
+    DeviceGuard g(ctx->device);
+    SlotLease lease(ctx);
+    lease.s = h.slot;                                               // handed back whatever happens below
+    if (!keep) return HPGV_OK;                                      // only the hold released
+    Slot *s = h.slot;
+    if (n_lines != h.n_lines) return fail(ctx, HPGV_ERR_INVALID, "n_lines %d, but hpgv_filter_text tokenized %d lines", n_lines, h.n_lines);
+    if (n_lines == 0) { if (kept_bytes) *kept_bytes = 0; if (total_bytes) *total_bytes = 0; return HPGV_OK; }
+    unsigned long long ends[2];
+    HIPCHK(ctx, hipMemcpyAsync(&ends[0], h.d_line_off, sizeof ends[0], hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(ctx, hipMemcpyAsync(&ends[1], h.d_line_off + n_lines, sizeof ends[1], hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(ctx, hipStreamSynchronize(s->stream));
+    const size_t total = (size_t)(ends[1] - ends[0]);
+    if (!out || total > out_cap) return fail(ctx, HPGV_ERR_INVALID, "the lines take %zu bytes, out has room for %zu", total, out_cap);
+    const size_t n = (size_t)n_lines, scratch = hpgv_lines_partition_scratch_bytes(n_lines);
+    const size_t off_keep = round_up(scratch + sizeof(unsigned long long), 256);
+    int rc;
+    if ((rc = ensure(ctx, s, 3, off_keep + n + 16))) return rc;
+    if ((rc = ensure(ctx, s, 1, total + 16))) return rc;
+    char *d_aux = (char *)s->buf[3];
+    unsigned long long *d_kept = (unsigned long long *)(d_aux + scratch);
+    uint8_t *d_keep = (uint8_t *)d_aux + off_keep;
+    HIPCHK(ctx, hipMemcpyAsync(d_keep, keep, n, hipMemcpyHostToDevice, s->stream));
+    if ((rc = partition_launch(ctx, h.d_text, h.d_line_off, n_lines, d_keep, (char *)s->buf[1], d_kept, d_aux, s->stream))) return rc;
+    unsigned long long kept = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&kept, d_kept, sizeof kept, hipMemcpyDeviceToHost, s->stream));
+    if (total) HIPCHK(ctx, hipMemcpyAsync(out, s->buf[1], total, hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(ctx, hipStreamSynchronize(s->stream));
+    if (kept_bytes) *kept_bytes = kept;
+    if (total_bytes) *total_bytes = total;
+    return HPGV_OK;
+    HPGV_ABI_CATCH(ctx)
 }
 
 int hpgv_read_probe(hpgv_ctx *ctx, const uint8_t *d_buf, size_t bytes, int iters, float *ms) {

@@ -94,6 +94,10 @@ struct hpgv_ctx {
     std::vector<std::pair<const char *, const char *>> text_alias;   // host text buffer -> the same text already on the device
     struct TextTiles { const char *d_text, *d_base; const void *d_tiles; uint64_t n_tiles; };
     std::vector<TextTiles> text_tiles;                               // device windows whose text comes with the decoder's tile records (hpgv_text_alias_tiles)
+    // hpgv_filter_text keeps its slot -- the device text it tokenized and that text's line starts -- until hpgv_text_partition
+    struct TextHeld { const char *host_text; Slot *slot; const char *d_text; const unsigned long long *d_line_off; int n_lines; };
+    std::vector<TextHeld> text_held;                                 // (under alias_mu)
+    long part_aligned = 0;     // hpgv_lines_partition_dev: 0 = unaligned dwordx4 loads of the source; 1 = aligned loads + v_alignbyte (ablation build)
     long scan_unroll = 4;
     long persistent = 0;       // 0: one wave per vpw consecutive rows; 1: persistent strided grid
     long blocks_per_cu = 8;

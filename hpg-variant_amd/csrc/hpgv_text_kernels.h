@@ -321,12 +321,32 @@ __device__ __forceinline__ unsigned long long head_block_scan(unsigned long long
     __syncthreads();
     return v + before;
 }
-static __global__ __launch_bounds__(1024) void k_head_sums(const unsigned long long *__restrict__ line_off, const uint32_t *__restrict__ field_off,
-                                                    int n_lines, unsigned long long *__restrict__ block_sum) {
+// The three launches are generic over the length summed (Len: a functor i -> length of line i): the heads here, the kept
+// lines of the partition (hpgv_partition_kernels.h).  k_head_bases scans the block sums whatever they are sums of.
+template <typename Len>
+__device__ __forceinline__ void len_block_sums(Len len, int n_lines, unsigned long long *__restrict__ block_sum) {
     __shared__ unsigned long long s_w[16];
     const int i = blockIdx.x * 1024 + threadIdx.x;
-    const unsigned long long inc = head_block_scan(i < n_lines ? head_len(line_off, field_off, i) : 0ull, s_w);
+    const unsigned long long inc = head_block_scan(i < n_lines ? len(i) : 0ull, s_w);
     if (threadIdx.x == 1023) block_sum[blockIdx.x] = inc;
+}
+template <typename Len>
+__device__ __forceinline__ void len_offsets(Len len, int n_lines, const unsigned long long *__restrict__ block_base,
+                                            unsigned long long *__restrict__ off) {
+    __shared__ unsigned long long s_w[16];
+    const int i = blockIdx.x * 1024 + threadIdx.x;
+    const unsigned long long l = i < n_lines ? len(i) : 0ull;
+    const unsigned long long inc = head_block_scan(l, s_w) + block_base[blockIdx.x];
+    if (i < n_lines) off[i] = inc - l;
+    if (i == n_lines - 1) off[n_lines] = inc;
+}
+struct HeadLen {
+    const unsigned long long *__restrict__ line_off; const uint32_t *__restrict__ field_off;
+    __device__ __forceinline__ unsigned long long operator()(int i) const { return head_len(line_off, field_off, i); }
+};
+static __global__ __launch_bounds__(1024) void k_head_sums(const unsigned long long *__restrict__ line_off, const uint32_t *__restrict__ field_off,
+                                                    int n_lines, unsigned long long *__restrict__ block_sum) {
+    len_block_sums(HeadLen{line_off, field_off}, n_lines, block_sum);
 }
 static __global__ __launch_bounds__(1024) void k_head_bases(unsigned long long *__restrict__ block_sum, int n_blocks) {
     __shared__ unsigned long long s_w[16];
@@ -347,12 +367,7 @@ static __global__ __launch_bounds__(1024) void k_head_bases(unsigned long long *
 static __global__ __launch_bounds__(1024) void k_head_offsets(const unsigned long long *__restrict__ line_off, const uint32_t *__restrict__ field_off,
                                                        int n_lines, const unsigned long long *__restrict__ block_base,
                                                        unsigned long long *__restrict__ head_off) {
-    __shared__ unsigned long long s_w[16];
-    const int i = blockIdx.x * 1024 + threadIdx.x;
-    const unsigned long long len = i < n_lines ? head_len(line_off, field_off, i) : 0ull;
-    const unsigned long long inc = head_block_scan(len, s_w) + block_base[blockIdx.x];
-    if (i < n_lines) head_off[i] = inc - len;
-    if (i == n_lines - 1) head_off[n_lines] = inc;
+    len_offsets(HeadLen{line_off, field_off}, n_lines, block_base, head_off);
 }
 static __global__ __launch_bounds__(64) void k_copy_heads(const char *__restrict__ text, const unsigned long long *__restrict__ line_off,
                                                    const unsigned long long *__restrict__ head_off, int n_lines, char *__restrict__ heads) {

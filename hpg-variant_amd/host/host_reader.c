@@ -285,7 +285,12 @@ int vcf_header_read(line_reader_t *rd, char **hdr_out, char ***names_out, size_t
         while (*p == '#') {
             char *eol = (char *)memchr(p, '\n', have - (size_t)(p - hdr));
             if (!eol) { p = NULL; break; }
-            if (!strncmp(p, "#CHROM", 6)) { chrom = p; *eol = 0; data_start = (size_t)(eol + 1 - hdr); break; }
+            if (!strncmp(p, "#CHROM", 6)) {
+                free(rd->chrom_line);                /* the line as written, newline included (the filter tool copies it) */
+                rd->chrom_len = (size_t)(eol + 1 - p);
+                if ((rd->chrom_line = (char *)malloc(rd->chrom_len))) memcpy(rd->chrom_line, p, rd->chrom_len); else rd->chrom_len = 0;
+                chrom = p; *eol = 0; data_start = (size_t)(eol + 1 - hdr); break;
+            }
             p = eol + 1;
         }
         if (chrom) {

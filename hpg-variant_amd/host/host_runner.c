@@ -1,4 +1,5 @@
-/* host_runner.c -- the file runners: reader -> engine threads -> writer (hpgv_run_assoc / tdt / aggregate / stats / vcf2epi).
+/* host_runner.c -- the file runners: reader -> engine threads -> writer (hpgv_run_assoc / tdt / aggregate / stats / vcf2epi /
+ * filter).
  * Part of libhpgv_host.so (see hpgv_host_internal.h for the map of its units). */
 #include "hpgv_host_internal.h"
 
@@ -6,6 +7,7 @@
 /* batches in rotation and engine threads: two engine threads per device (one batch's bus copies beside the other's
  * kernels) and three more batches than engines (reader ahead, writer behind); one device: 5 batches, 2 engines */
 enum { B_FREE = 0, B_FILLED = 1, B_BUSY = 2, B_DONE = 3 };
+static long g_filter_rejected;                           /* filter: records written to (or meant for) .rejected by the last run */
 typedef struct {
     pthread_mutex_t mu; pthread_cond_t cv;
     run_batch_t bt[RUN_NB_MAX]; int state[RUN_NB_MAX]; long seq[RUN_NB_MAX];
@@ -52,6 +54,32 @@ static void *pipe_reader(void *v) {
     }
 }
 
+/* the filter tool's engine step after hpgv_filter_text, while the batch's text is still on the device: the verdict of every
+ * line (record_passes: the heads are enough), then the lines partitioned there into the batch's own page-locked buffer --
+ * the kept lines first, then the others, both in file order */
+static int filter_partition(run_batch_t *b) {
+    const int n = b->n_lines;
+    if (n > b->max_lines) return HPGV_ERR_UNSUPPORTED;                /* (hpgv_filter_text kept nothing then) */
+    b->n_pass = b->n_rej = 0; b->n_blank = 0; b->part_kept = b->part_total = 0;
+    if (b->keep_cap < n) {
+        free(b->keep);
+        b->keep = (uint8_t *)malloc((size_t)n + 1);
+        b->keep_cap = b->keep ? n : 0;
+        if (!b->keep) { (void)hpgv_text_partition(g_ctx, b->text, NULL, 0, NULL, 0, NULL, NULL); return HPGV_ERR_NOMEM; }
+    }
+    for (int i = 0; i < n; i++) {
+        const int k = record_passes(b, i);
+        b->keep[i] = (uint8_t)k;
+        if (k) b->n_pass++;
+        else if (b->line_off[i + 1] - b->line_off[i] == 1 && b->text[b->line_off[i]] == '\n') b->n_blank++;      /* an empty line */
+        else b->n_rej++;
+    }
+    uint64_t kept = 0, total = 0;
+    const int rc = hpgv_text_partition(g_ctx, b->text, b->keep, n, b->text, b->text_cap, &kept, &total);
+    b->part_kept = kept; b->part_total = total;
+    return rc;
+}
+
 static void *pipe_engine(void *v) {
     run_pipe_t *P = (run_pipe_t *)v;
     const int kind = P->kind;
@@ -88,7 +116,9 @@ static void *pipe_engine(void *v) {
                 rc = hpgv_stats_text_groups(g_ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status, b->c8, b->hw, b->hw + m,
                                             kind == 6 ? b->smiss : NULL, b->midx, b->mtab, &b->n_multi, mend ? b->merr : NULL, mend ? b->cerr : NULL,
                                             b->n_groups ? b->gc8 : NULL, b->n_groups ? b->ghw : NULL, b->n_groups ? b->ghw + gm : NULL);
-            } else if (kind == 4)
+            } else if (kind == 7)
+                rc = hpgv_filter_text(g_ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status);
+            else if (kind == 4)
                 rc = hpgv_epi_dataset_text(g_ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status, b->rows);
             else if (kind == 3)
                 rc = hpgv_tdt_text(g_ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status,
@@ -109,13 +139,14 @@ static void *pipe_engine(void *v) {
             free(b->mtab); b->mtab = NULL;
             if (run_batch_reserve(b, b->n_lines)) { rc = HPGV_ERR_NOMEM; break; }
         }
+        if (kind == 7 && !rc) rc = filter_partition(b);               /* before the alias is dropped: the window is the source */
         if (b->dev_text) (void)hpgv_text_alias(b->dev_ctx ? b->dev_ctx : g_ctx, b->text, NULL);
         const double dt = now_s() - t0;
         pthread_mutex_lock(&P->mu);
         P->t_engine += dt;
         if (rc) {
             char msg[256];
-            snprintf(msg, sizeof msg, "%s failed (%d): %s", kind >= 5 ? "hpgv_stats_text" : kind == 4 ? "hpgv_epi_dataset_text" : kind == 3 ? "hpgv_tdt_text" : "hpgv_assoc_text", rc,
+            snprintf(msg, sizeof msg, "%s failed (%d): %s", kind == 7 ? "hpgv_filter_text / hpgv_text_partition" : kind >= 5 ? "hpgv_stats_text" : kind == 4 ? "hpgv_epi_dataset_text" : kind == 3 ? "hpgv_tdt_text" : "hpgv_assoc_text", rc,
                      rc == HPGV_ERR_NOMEM ? "out of memory" : hpgv_last_error(g_ctx));
             pipe_fail(P, rc, msg);
             pthread_mutex_unlock(&P->mu);
@@ -215,6 +246,37 @@ static void write_group_lines(FILE **gfd, const run_batch_t *b) {
         }
 }
 
+/* hpg-var-vcf filter: the lines of one batch in its two files.  The kept region holds no empty line; the rejected one
+ * holds n_blank of them, each a '\n' at the region's start or right behind another '\n', and they go to neither file.  The
+ * file's last line may lack its newline: it gets one. */
+static int write_region(FILE *f, const char *p, size_t n, int blanks) {
+    size_t i = 0;
+    while (blanks > 0 && i < n) {
+        if (p[i] == '\n') { i++; blanks--; continue; }
+        const char *q = (const char *)memmem(p + i, n - i, "\n\n", 2);
+        const size_t e = q ? (size_t)(q - p) + 1 : n;
+        if (fwrite(p + i, 1, e - i, f) != e - i) return 1;
+        i = e;
+    }
+    if (i < n && fwrite(p + i, 1, n - i, f) != n - i) return 1;
+    if (n && p[n - 1] != '\n' && putc('\n', f) == EOF) return 1;
+    return 0;
+}
+static int write_filter_batch(FILE *kept, FILE *rejected, const run_batch_t *b) {
+    if (write_region(kept, b->text, (size_t)b->part_kept, 0)) return 1;
+    return rejected && write_region(rejected, b->text + b->part_kept, (size_t)(b->part_total - b->part_kept), b->n_blank);
+}
+/* the header of both files (filter_runner.c:129-137): the input's meta lines, one ##FILTER line per active filter, #CHROM */
+static int write_filter_header(FILE *f, const char *hdr, size_t chrom_off, const char *chrom_line, size_t chrom_len) {
+    if (chrom_off && fwrite(hdr, 1, chrom_off, f) != chrom_off) return 1;
+    if (g_filters.min_maf >= 0.0) fprintf(f, "##FILTER=<ID=maf,Description=\"Minor allele frequency >= %g\">\n", g_filters.min_maf);
+    if (g_filters.max_missing >= 0.0) fprintf(f, "##FILTER=<ID=missing,Description=\"Rate of missing genotypes <= %g\">\n", g_filters.max_missing);
+    if (g_filters.max_mendel_errors >= 0) fprintf(f, "##FILTER=<ID=mendel,Description=\"Mendelian errors <= %g\">\n", (double)g_filters.max_mendel_errors);
+    if (g_filters.num_alleles >= 0) fprintf(f, "##FILTER=<ID=alleles,Description=\"Number of alleles == %g\">\n", (double)g_filters.num_alleles);
+    if (g_filters.min_quality >= 0.0) fprintf(f, "##FILTER=<ID=quality,Description=\"Quality >= %g\">\n", g_filters.min_quality);
+    return chrom_len && fwrite(chrom_line, 1, chrom_len, f) != chrom_len;
+}
+
 static int run_file(const char *vcf_path, const char *ped_path, const char *out_path, int kind, size_t batch_bytes,
                     long *n_variants_out) {
     host_env_read();                                               /* the environment: once per run (hpgv_host.h "Environment") */
@@ -242,7 +304,7 @@ static int run_file(const char *vcf_path, const char *ped_path, const char *out_
     const double t_opened = now_s();
     const int n_samples = vcf_header_read(&rd, &hdr, &names, &chrom_off);
     const double t_header = now_s();
-    if (n_samples < 0) { source_close(&rd.src); free(rd.carry); free(hdr); ped_table_free(&ped); snprintf(g_err, sizeof g_err, "%s%sno #CHROM header line in %s", g_input_err, g_input_err[0] ? "; " : "", vcf_path); return HPGV_ERR_INVALID; }
+    if (n_samples < 0) { source_close(&rd.src); free(rd.carry); free(rd.chrom_line); free(hdr); ped_table_free(&ped); snprintf(g_err, sizeof g_err, "%s%sno #CHROM header line in %s", g_input_err, g_input_err[0] ? "; " : "", vcf_path); return HPGV_ERR_INVALID; }
 
     /* cohort: PED rows looked up by sample name (associate_samples_and_positions + sort_individuals) */
     sample_ids_t *ids = sample_ids_new((size_t)n_samples);
@@ -387,13 +449,19 @@ static int run_file(const char *vcf_path, const char *ped_path, const char *out_
      * above, and an adapter or another runner with a different cohort waits instead of swapping them mid-file */
     sample_ids_free(ids);
 
-    char *path6 = NULL;
-    if (kind == 6) {
+    char *path6 = NULL, *path_rej = NULL;                /* stats: <prefix>.stats-variants; filter: <prefix>.filtered, .rejected */
+    if (kind == 6 || kind == 7) {
         path6 = (char *)malloc(strlen(out_path) + 32);
-        if (path6) sprintf(path6, "%s.stats-variants", out_path); else rc = rc ? rc : HPGV_ERR_NOMEM;
+        if (path6) sprintf(path6, kind == 6 ? "%s.stats-variants" : "%s.filtered", out_path); else rc = rc ? rc : HPGV_ERR_NOMEM;
     }
-    FILE *out = rc ? NULL : fopen(kind == 6 ? path6 : out_path, "wb");
-    if (!rc && !out) { snprintf(g_err, sizeof g_err, "cannot create %s", kind == 6 ? path6 : out_path); rc = HPGV_ERR_INVALID; }
+    if (kind == 7) {
+        path_rej = (char *)malloc(strlen(out_path) + 32);
+        if (path_rej) sprintf(path_rej, "%s.rejected", out_path); else rc = rc ? rc : HPGV_ERR_NOMEM;
+    }
+    FILE *out = rc ? NULL : fopen(path6 ? path6 : out_path, "wb");
+    if (!rc && !out) { snprintf(g_err, sizeof g_err, "cannot create %s", path6 ? path6 : out_path); rc = HPGV_ERR_INVALID; }
+    FILE *out_rej = rc || kind != 7 ? NULL : fopen(path_rej, "wb");     /* created empty without save_rejected (filter_runner.c:63-68) */
+    if (!rc && kind == 7 && !out_rej) { snprintf(g_err, sizeof g_err, "cannot create %s", path_rej); rc = HPGV_ERR_INVALID; }
     FILE **gfd = NULL;
     if (!rc && kind == 6 && n_groups > 0) {               /* one file per phenotype (stats_runner.c:267-297) */
         gfd = (FILE **)calloc((size_t)n_groups, sizeof(FILE *));
@@ -413,6 +481,7 @@ static int run_file(const char *vcf_path, const char *ped_path, const char *out_
         if (!RS || !RS->smiss || !RS->serr) rc = HPGV_ERR_NOMEM;
     }
     if (out) setvbuf(out, NULL, _IOFBF, 1u << 20);
+    if (out_rej) setvbuf(out_rej, NULL, _IOFBF, 1u << 20);
     long written = 0;
     double t_sort = 0;
     order_track_t ord;
@@ -442,7 +511,7 @@ static int run_file(const char *vcf_path, const char *ped_path, const char *out_
         if (w > ((size_t)256 << 20)) w = (size_t)256 << 20;
         if (w > batch_bytes) batch_bytes = w;
     }
-    for (; !rc && have < P->nb; have++) rc = run_batch_alloc(&P->bt[have], batch_bytes, n_samples, kind == 4 ? n_samples : 0, kind >= 5, n_trios, n_groups);
+    for (; !rc && have < P->nb; have++) rc = run_batch_alloc(&P->bt[have], batch_bytes, n_samples, kind == 4 ? n_samples : 0, kind == 5 || kind == 6, n_trios, n_groups);
     if (rc == HPGV_ERR_NOMEM) snprintf(g_err, sizeof g_err, "out of memory for the batch buffers");
     if (!rc) {
         if (kind == 5) {
@@ -456,6 +525,9 @@ static int run_file(const char *vcf_path, const char *ped_path, const char *out_
             fprintf(out, "##INFO=<ID=%sAN,Number=1,Type=Integer,Description=\"%sTotal number of alleles in called genotypes\">\n", pre, by);
             fprintf(out, "##INFO=<ID=HPG_GTC,Number=.,Type=String,Description=\"Calculated by HPG Variant: Genotype counts, in pairs genotype:count\">\n");
             fprintf(out, "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n");
+        } else if (kind == 7) {
+            if (write_filter_header(out, hdr, chrom_off, rd.chrom_line, rd.chrom_len) ||
+                (g_filter_save_rejected && write_filter_header(out_rej, hdr, chrom_off, rd.chrom_line, rd.chrom_len))) rc = HPGV_ERR_INVALID;
         } else if (kind == 6) {
             fprintf(out, "#CHROM\tPOS\tREF\tALT\tNUM_ALLELES\tALLELES_COUNT\tALLELES_FREQ\tGENOTYPES_COUNT\tMISS_AL\tMISS_GT\tMAF\tMEND_ER\tHWE_CHI2\tHWE_P\n");
         } else if (kind == 4) {                          /* room for the number of variants, then the class sizes (dataset_creator.c:186-193) */
@@ -486,7 +558,7 @@ static int run_file(const char *vcf_path, const char *ped_path, const char *out_
         file_writer_t fw;
         memset(&fw, 0, sizeof fw);
         /* (the vcf2epi rows are written out of the batch itself, and the stats tool's group files by this thread) */
-        const int use_fw = kind != 4 && !g_env.no_writer_thread && file_writer_start(&fw, out);
+        const int use_fw = kind != 4 && kind != 7 && !g_env.no_writer_thread && file_writer_start(&fw, out);
         int fmt_set = 0;
         pthread_t th[1 + RUN_ENGINES_MAX];
         int n_th = 0;
@@ -506,9 +578,11 @@ static int run_file(const char *vcf_path, const char *ped_path, const char *out_
             pthread_mutex_unlock(&P->mu);
             const double t0 = now_s();
             const run_batch_t *b = &P->bt[k];
-            const int bad = write_batch(out, kind, b, fmt + (fmt_set ? RUN_FMT_BUFS / 2 : 0), n_fmt, &wpool, &ord, use_fw ? &fw : NULL);
+            const int bad = kind == 7 ? write_filter_batch(out, g_filter_save_rejected ? out_rej : NULL, b)       /* two fwrites */
+                                      : write_batch(out, kind, b, fmt + (fmt_set ? RUN_FMT_BUFS / 2 : 0), n_fmt, &wpool, &ord, use_fw ? &fw : NULL);
             fmt_set ^= use_fw;
-            for (int i = 0; i < b->n_lines; i++) if (record_passes(b, i)) written++;
+            if (kind == 7) { written += b->n_pass; g_filter_rejected += b->n_rej; }      /* (the batch's text is the partition now) */
+            else for (int i = 0; i < b->n_lines; i++) if (record_passes(b, i)) written++;
             if (kind == 6 && !bad) run_stats_add(RS, b, n_samples, trio_child);
             if (kind == 6 && !bad && gfd) write_group_lines(gfd, b);
             const double dt = now_s() - t0;
@@ -531,7 +605,8 @@ static int run_file(const char *vcf_path, const char *ped_path, const char *out_
         const uint32_t nv = (uint32_t)written;
         if (fseek(out, 0, SEEK_SET) != 0 || fwrite(&nv, sizeof nv, 1, out) != 1) { snprintf(g_err, sizeof g_err, "cannot write %s", out_path); rc = HPGV_ERR_INVALID; }
     }
-    if (out && fclose(out) != 0 && !rc) { snprintf(g_err, sizeof g_err, "cannot write %s", out_path); rc = HPGV_ERR_INVALID; }
+    if (out && fclose(out) != 0 && !rc) { snprintf(g_err, sizeof g_err, "cannot write %s", path6 ? path6 : out_path); rc = HPGV_ERR_INVALID; }
+    if (out_rej && fclose(out_rej) != 0 && !rc) { snprintf(g_err, sizeof g_err, "cannot write %s", path_rej); rc = HPGV_ERR_INVALID; }
     {
         const double t0 = now_s();
         /* (in order as written: nothing to do; HPGV_ALWAYS_SORT=1 reads the file back and checks all the same) */
@@ -546,7 +621,7 @@ static int run_file(const char *vcf_path, const char *ped_path, const char *out_
     if (RS) { free(RS->smiss); free(RS->serr); free(RS); }
     for (int k = 0; gfd && k < n_groups; k++) if (gfd[k]) fclose(gfd[k]);
     free(gfd); free(group_names);
-    free(path6); free(trio_child);
+    free(path6); free(path_rej); free(trio_child);
     for (int k = 0; P && k < have; k++) run_batch_free(&P->bt[k]);
     for (int k = 0; fmt && k < RUN_FMT_BUFS; k++) free(fmt[k].p);
     free(fmt);
@@ -559,7 +634,7 @@ static int run_file(const char *vcf_path, const char *ped_path, const char *out_
         fprintf(stderr, "hpgv run: %ld records, %.0f batches, %d io threads: read %.3f s, engine %.3f s (%d threads), write %.3f s (stages overlap), sort %.3f s, total %.3f s\n",
                 written, g_run_times[5], io_threads, g_run_times[0], g_run_times[1], n_engines_used, g_run_times[2], t_sort, g_run_times[4]);
     const double t_done = now_s();
-    source_close(&rd.src); free(rd.carry); free(rd.tailbuf); free(hdr); free(names); ped_table_free(&ped);
+    source_close(&rd.src); free(rd.carry); free(rd.tailbuf); free(rd.chrom_line); free(hdr); free(names); ped_table_free(&ped);
     if (n_variants_out) *n_variants_out = written;
     pthread_rwlock_unlock(&g_cohort_lock);
     if (g_env.run_trace)
@@ -598,7 +673,7 @@ int hpgv_host_copy_lines(const char *in_path, const char *out_path, size_t batch
     }
     if (out) fclose(out);
     pool_destroy(&pool);
-    free(buf); free(rd.carry); source_close(&rd.src);
+    free(buf); free(rd.carry); free(rd.chrom_line); source_close(&rd.src);
     if (n_batches) *n_batches = nb;
     return rc;
 }
@@ -633,6 +708,27 @@ int hpgv_run_stats(const char *vcf_path, const char *ped_path, const char *out_p
     hpgv_run_set_filters(NULL);
     const int rc = run_file(vcf_path, ped_path, out_prefix, 6, batch_bytes, n_variants_out);
     g_filters = saved;
+    return rc;
+}
+
+/* run_filter (src/vcf-tools/filter/filter_runner.c:23-260): the records of the VCF that pass the filters of
+ * hpgv_run_set_filters, and those that do not, in two files; without a filter nothing is written (hpg_variant_utils.c:220-226) */
+int g_filter_save_rejected = 0;
+int hpgv_run_filter(const char *vcf_path, const char *ped_path, const char *out_prefix, int save_rejected, size_t batch_bytes,
+                    long *n_passed_out, long *n_rejected_out) {
+    if (n_passed_out) *n_passed_out = 0;
+    if (n_rejected_out) *n_rejected_out = 0;
+    const hpgv_run_filters_t F = g_filters;
+    if (!vcf_path || !out_prefix) { snprintf(g_err, sizeof g_err, "vcf_path and out_prefix must not be NULL"); return HPGV_ERR_INVALID; }
+    if (F.min_maf < 0.0 && F.max_missing < 0.0 && F.max_mendel_errors < 0 && F.num_alleles < 0 && F.min_quality < 0.0) {
+        snprintf(g_err, sizeof g_err, "no filter is set (hpgv_run_set_filters): the filter tool writes nothing without one");
+        return HPGV_ERR_INVALID;
+    }
+    if (F.max_mendel_errors >= 0 && !ped_path) { snprintf(g_err, sizeof g_err, "the Mendelian error filter needs a PED file (ped_path is NULL)"); return HPGV_ERR_INVALID; }
+    g_filter_save_rejected = save_rejected ? 1 : 0;
+    g_filter_rejected = 0;
+    const int rc = run_file(vcf_path, ped_path, out_prefix, 7, batch_bytes, n_passed_out);
+    if (n_rejected_out) *n_rejected_out = g_filter_rejected;
     return rc;
 }
 

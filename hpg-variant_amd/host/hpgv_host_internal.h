@@ -129,6 +129,7 @@ typedef struct {
     const char *last_base; const void *last_tiles; size_t last_n_tiles;      /* ... where that device text begins, and its tile records */
     int devwin;                                         /* batches are windows of the device text; nothing but their cut points is read back */
     char *tailbuf; size_t tailcap;
+    char *chrom_line; size_t chrom_len;                 /* the #CHROM line as written (vcf_header_read), or NULL */
 } line_reader_t;
 
 typedef struct {
@@ -144,6 +145,9 @@ typedef struct {
     int32_t *c8, *merr, *midx, *mtab, *smiss, *cerr; double *hw;
     int n_multi, multi_cap, n_smiss, n_cerr;
     int n_groups; int32_t *gc8; double *ghw;              /* stats: per-phenotype counters, [g * max_lines + v] */
+    uint8_t *keep; int keep_cap;                         /* filter: record_passes per line, then the partitioned text in `text` */
+    uint64_t part_kept, part_total;                      /* ... its kept bytes first, part_total bytes in all */
+    long n_pass, n_rej; int n_blank;                     /* ... records kept, records rejected, empty lines (in neither file) */
 } run_batch_t;
 
 typedef struct { int na, miss_al, miss_gt, ac[15], gc[225]; } vcounts_t;
@@ -284,6 +288,7 @@ extern hpgv_run_filters_t g_filters;   /* host_source.c */
 extern double g_run_times[6];   /* host_source.c */
 extern char g_input_err[192];   /* host_bgzf.c */
 extern int g_aggregate_overwrite;   /* host_format.c */
+extern int g_filter_save_rejected;   /* host_runner.c */
 extern double g_write_split[2];   /* host_format.c */
 
 #pragma GCC visibility pop

@@ -98,6 +98,8 @@ const char *hpgv_last_error(const hpgv_ctx *ctx);
  *                                    samples with their padding need more than 128 staging chunks or the genotype planes'
  *                                    second copy finds no room: hpgv_epi_last_rank_info says which ran)
  *   "group_self_exchange" 0/1    (group contexts; tests) member 0 hands its results over through the communicator too
+ *   "part_aligned_loads" 0/1     hpgv_lines_partition_dev: the source of a granule by two aligned loads and v_alignbyte
+ *                                (ablation build) instead of one unaligned dwordx4 load (shipped: 0)
  * Every kernel ships in ONE form.  The forms that lost their A/B comparisons (profiles/experiments_that_did_not_pay.md) are
  * compiled only into an ablation build (-DHPGV_ABLATION: tools/build_ablation.py, used by tools/ only); there the keys
  * "pipeline", "persistent", "scan_unroll", "pipe_waves", "nontemporal", "fisher_width", "inflate_wave", "tokenizer_tiles"
@@ -370,6 +372,30 @@ int  hpgv_stats_text_groups(hpgv_ctx *ctx, const char *text, size_t text_bytes, 
  * filters need hpgv_set_stats_cohort(n_samples), the Mendel filter hpgv_set_pedigree over the same columns. */
 #define HPGV_LINE_FILTERED 0x100
 int  hpgv_set_text_filters(hpgv_ctx *ctx, double min_maf, double max_missing, long max_mendel_errors);
+
+/* hpg-var-vcf filter (filter_runner.c:23-260): the record filters alone.  hpgv_filter_text tokenizes a batch of VCF text
+ * as the other *_text calls do (line_off, field_off, status as there; the text on the device when hpgv_text_alias says so),
+ * applies the device filters of hpgv_set_text_filters (HPGV_LINE_FILTERED in status) and runs no tool's scan.  The count
+ * filters read the layout of hpgv_set_stats_cohort, which this call needs whatever the filters.  The call keeps the device
+ * text it tokenized, and that text's line starts, for hpgv_text_partition on the same `text`: until that call, or the next
+ * hpgv_filter_text on `text`, one of the context's stream slots stays with it.  When *n_lines > max_lines nothing is kept. */
+int  hpgv_filter_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, int max_lines, int *n_lines,
+                      uint64_t *line_off, uint32_t *field_off, int32_t *status);
+/* The lines the last hpgv_filter_text on `text` tokenized, partitioned on the device that holds them (the uploaded copy,
+ * or the aliased window on its member's device): keep[i] != 0 lines first, in line order, then the others in line order,
+ * copied into `out` (out_cap bytes; page-locked memory is copied at the bus rate).  *total_bytes = the bytes of the lines
+ * (line_off[n_lines] - line_off[0] on the device), *kept_bytes = those of the kept lines; both may be NULL.  n_lines must
+ * be what hpgv_filter_text returned.  keep = NULL only releases the hold.  Synchronous. */
+int  hpgv_text_partition(hpgv_ctx *ctx, const char *text, const uint8_t *keep, int n_lines, char *out, size_t out_cap,
+                         uint64_t *kept_bytes, uint64_t *total_bytes);
+/* The device primitive: lines i = 0 .. n_lines - 1 of d_text, line i = bytes [d_line_off[i], d_line_off[i + 1]), into d_out:
+ * every line with d_keep[i] != 0, byte for byte and back to back in line order, then every other line in line order.  d_out
+ * receives exactly d_line_off[n_lines] - d_line_off[0] bytes and nothing outside them is stored; d_text and d_out may have
+ * any alignment.  *d_kept_bytes (device memory, may be NULL) = the bytes of the kept lines.  d_scratch:
+ * hpgv_lines_partition_scratch_bytes(n_lines) bytes of device memory (8-byte aligned).  Asynchronous on `stream`. */
+size_t hpgv_lines_partition_scratch_bytes(int n_lines);
+int  hpgv_lines_partition_dev(hpgv_ctx *ctx, const char *d_text, const uint64_t *d_line_off, int n_lines, const uint8_t *d_keep,
+                              char *d_out, uint64_t *d_kept_bytes, void *d_scratch, void *stream);
 
 /* the same rows from a batch of VCF text (tokenized on the device like hpgv_assoc_text): row v of `out` belongs to
  * line v; lines that are not records (field_off[10 v + 5] == 0xFFFFFFFF) leave their row undefined */

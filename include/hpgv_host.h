@@ -308,6 +308,26 @@ typedef struct {
 } hpgv_run_filters_t;
 void hpgv_run_set_filters(const hpgv_run_filters_t *filters);
 
+/* run_filter (src/vcf-tools/filter/filter_runner.c:23-260, hpg-var-vcf filter): the records that pass the filters of
+ * hpgv_run_set_filters to <out_prefix>.filtered, the others to <out_prefix>.rejected when save_rejected != 0 (--save-rejected,
+ * main_filter.c:85; without it .rejected is created empty, filter_runner.c:63-68).  Without any filter set, or with NULL paths,
+ * or with --mendel and no PED, it returns HPGV_ERR_INVALID before the engine starts and writes no file (the reference writes
+ * nothing without a filter chain, hpg_variant_utils.c:220-226).  ped_path may be NULL; the count filters use every VCF column
+ * (as hpgv_run_stats does), the Mendelian one the PED's trios whose three members are VCF columns.
+ * Each file: the input header verbatim up to its #CHROM line, then one line per active filter, in this order and with the
+ * thresholds printed by %g --
+ *   ##FILTER=<ID=maf,Description="Minor allele frequency >= 0.1">
+ *   ##FILTER=<ID=missing,Description="Rate of missing genotypes <= 0.1">
+ *   ##FILTER=<ID=mendel,Description="Mendelian errors <= 1">
+ *   ##FILTER=<ID=alleles,Description="Number of alleles == 2">
+ *   ##FILTER=<ID=quality,Description="Quality >= 30">
+ * -- then the #CHROM line as written, then the records byte for byte in file order (the reference writes its batches as its
+ * workers finish them).  A last line without a newline gets one; a line with fewer than CHROM .. ALT is rejected; empty lines
+ * go to neither file.  The lines of a batch are partitioned on the device that tokenized them (hpgv_text_partition), whatever
+ * the input's compression.  *n_passed_out / *n_rejected_out (may be NULL): the records kept / rejected (counted with or
+ * without save_rejected). */
+int  hpgv_run_filter(const char *vcf_path, const char *ped_path, const char *out_prefix, int save_rejected,
+                     size_t batch_bytes, long *n_passed_out, long *n_rejected_out);
 /* create_dataset_from_vcf (src/vcf-tools/vcf2epi/dataset_creator.c:24-222) without its filters: the binary
  * dataset hpgv_run_epistasis reads -- uint32 num_variants, num_affected, num_unaffected, then per variant
  * one byte per sample, cases first (0 "0/0", 1 heterozygous, 2 homozygous non-reference, 255 missing);
