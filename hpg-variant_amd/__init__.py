@@ -49,6 +49,7 @@ SYMBOLS = [
     "hpgv_epi_counts_all_folds", "hpgv_epi_scan_pairs", "hpgv_epi_rank_pairs", "hpgv_epi_rank_pairs_rows", "hpgv_epi_scan_triples", "hpgv_epi_rank_triples", "hpgv_epi_eval_combs", "hpgv_epi_rank_order", "hpgv_epi_rank_order_rows", "hpgv_read_probe",
     "hpgv_group_comm_init", "hpgv_group_comm_ranks", "hpgv_group_rccl_probe", "hpgv_group_shard", "hpgv_group_assoc", "hpgv_group_tdt", "hpgv_group_stats", "hpgv_group_sync", "hpgv_group_epi_share", "hpgv_group_epi_rank", "hpgv_epi_rank_triples_rows", "hpgv_text_alias_tiles", "hpgv_text_tiles_bytes", "hpgv_bgzf_verify_tiles_dev", "hpgv_memset_dev",
     "hpgv_epi_last_rank_info", "hpgv_filter_text", "hpgv_text_partition", "hpgv_lines_partition_scratch_bytes", "hpgv_lines_partition_dev",
+    "hpgv_text_multisplit", "hpgv_lines_multisplit_scratch_bytes", "hpgv_lines_multisplit_dev",
 ]
 
 

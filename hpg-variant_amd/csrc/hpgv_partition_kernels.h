@@ -104,4 +104,78 @@ __global__ __launch_bounds__(256) void k_part_copy(const char *__restrict__ text
     }
 }
 
+
+// ---- the multi-way form (hpgv_lines_multisplit_dev, hpgv_text_multisplit; the split tool, hpg-var-vcf split): bucket b's
+// lines back to back in line order from bucket_off[b], the buckets in id order; a line whose id is >= n_buckets goes nowhere.
+//
+//   k_msplit_tile_sums                          : tiles of 64 lines, one wave each.  tile_sum[b][t] = the bytes of bucket b in
+//                                                 tile t; in_tile[i] = the bytes of the earlier lines of i's tile in i's bucket
+//                                                 (one readlane loop over the 64 lanes, whatever n_buckets is)
+//   k_mtile_sums / k_head_bases / k_mtile_offsets : tile_base = exclusive sum of tile_sum in bucket-major order (the same
+//                                                 three-launch scan, over n_buckets x n_tiles entries), tile_base[nb nt] = end
+//   k_msplit_copy                               : line i to tile_base[b][i / 64] + in_tile[i] by part_copy_line, as k_part_copy
+static __global__ __launch_bounds__(256) void k_msplit_tile_sums(const unsigned long long *__restrict__ line_off, const uint8_t *__restrict__ bucket,
+                                                                 int n_lines, int n_buckets, int n_tiles,
+                                                                 unsigned long long *__restrict__ tile_sum, unsigned long long *__restrict__ in_tile) {
+    const int lane = (int)(threadIdx.x & 63);
+    const int tile = (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+    if (tile >= n_tiles) return;                                    // (a whole wave)
+    const long long i = (long long)tile * 64 + lane;
+    const unsigned id = i < n_lines ? (unsigned)bucket[i] : 0xFFFFFFFFu;
+    const unsigned long long len = id < (unsigned)n_buckets ? line_off[i + 1] - line_off[i] : 0ull;
+    unsigned long long off = 0, s0 = 0, s1 = 0, s2 = 0, s3 = 0;     // s_q: bucket lane + 64 q of this tile
+    const unsigned len_lo = (unsigned)len, len_hi = (unsigned)(len >> 32);
+    for (int j = 0; j < 64; ++j) {
+        const unsigned idj = (unsigned)__builtin_amdgcn_readlane((int)id, j);
+        const unsigned long long lj = (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)len_lo, j)
+                                    | ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)len_hi, j) << 32);
+        if (j < lane && idj == id) off += lj;
+        const unsigned d = idj - (unsigned)lane;                    // lanes of a dropped id carry 0 bytes
+        if (d == 0) s0 += lj; else if (d == 64) s1 += lj; else if (d == 128) s2 += lj; else if (d == 192) s3 += lj;
+    }
+    if (i < n_lines) in_tile[i] = off;
+    const size_t nt = (size_t)n_tiles;
+    if (lane < n_buckets) tile_sum[(size_t)lane * nt + tile] = s0;
+    if (lane + 64 < n_buckets) tile_sum[(size_t)(lane + 64) * nt + tile] = s1;
+    if (lane + 128 < n_buckets) tile_sum[(size_t)(lane + 128) * nt + tile] = s2;
+    if (lane + 192 < n_buckets) tile_sum[(size_t)(lane + 192) * nt + tile] = s3;
+}
+
+struct TileLen {
+    const unsigned long long *__restrict__ tile_sum;
+    __device__ __forceinline__ unsigned long long operator()(int i) const { return tile_sum[i]; }
+};
+static __global__ __launch_bounds__(1024) void k_mtile_sums(const unsigned long long *__restrict__ tile_sum, int n, unsigned long long *__restrict__ block_sum) {
+    len_block_sums(TileLen{tile_sum}, n, block_sum);
+}
+static __global__ __launch_bounds__(1024) void k_mtile_offsets(const unsigned long long *__restrict__ tile_sum, int n,
+                                                               const unsigned long long *__restrict__ block_base,
+                                                               unsigned long long *__restrict__ tile_base) {
+    len_offsets(TileLen{tile_sum}, n, block_base, tile_base);
+}
+
+// lanes per line and the grid as k_part_copy; block 0 also writes bucket_off (bucket b starts at its tile 0's base)
+static __global__ __launch_bounds__(256) void k_msplit_copy(const char *__restrict__ text, const unsigned long long *__restrict__ line_off,
+                                                     int n_lines, const uint8_t *__restrict__ bucket, int n_buckets, int n_tiles,
+                                                     const unsigned long long *__restrict__ tile_base,
+                                                     const unsigned long long *__restrict__ in_tile, char *__restrict__ out,
+                                                     unsigned long long *__restrict__ bucket_off) {
+    const size_t nt = (size_t)n_tiles;
+    if (blockIdx.x == 0)
+        for (int b = (int)threadIdx.x; b <= n_buckets; b += (int)blockDim.x) bucket_off[b] = tile_base[(size_t)b * nt];
+    const unsigned long long mean = (line_off[n_lines] - line_off[0]) / (unsigned long long)n_lines;
+    int T = 1;
+    while (T < 64 && 64ull * (unsigned long long)T < mean) T <<= 1;
+    const int lane = (int)(threadIdx.x & 63), per_wave = 64 / T;
+    const long long wave = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const long long stride = (long long)gridDim.x * (blockDim.x >> 6) * per_wave;
+    for (long long i = wave * per_wave + lane / T; i < n_lines; i += stride) {
+        const unsigned id = bucket[i];
+        if (id >= (unsigned)n_buckets) continue;                   // (the whole team: one line)
+        const unsigned long long lo = line_off[i], n = line_off[i + 1] - lo;
+        const unsigned long long d = tile_base[(size_t)id * nt + (size_t)(i >> 6)] + in_tile[i];
+        part_copy_line<0>(text + lo, out + d, n, lane & (T - 1), T);
+    }
+}
+
 }  // namespace hpgv

@@ -63,6 +63,7 @@ void run_batch_free(run_batch_t *b) {
     free(b->line_off); free(b->field_off); free(b->status); free(b->ints); free(b->dbl); free(b->rows);
     free(b->c8); free(b->hw); free(b->merr); free(b->midx); free(b->mtab); free(b->smiss); free(b->cerr); free(b->gc8); free(b->ghw);
     free(b->keep);
+    free(b->sp_range); free(b->sp_len); free(b->sp_name); free(b->sp_names);
 }
 
 /* ---- number formatting of the result lines: the characters printf would give, without printf ------------- */

@@ -1,7 +1,9 @@
 /* host_runner.c -- the file runners: reader -> engine threads -> writer (hpgv_run_assoc / tdt / aggregate / stats / vcf2epi /
- * filter).
+ * filter / split).
  * Part of libhpgv_host.so (see hpgv_host_internal.h for the map of its units). */
 #include "hpgv_host_internal.h"
+#include <errno.h>
+#include <limits.h>
 
 /* ---- the runners' pipeline: reader -> engine threads -> writer, batches in rotation ------------------ */
 /* batches in rotation and engine threads: two engine threads per device (one batch's bus copies beside the other's
@@ -80,6 +82,195 @@ static int filter_partition(run_batch_t *b) {
     return rc;
 }
 
+/* ---- hpg-var-vcf split (split.c:37-122, split_runner.c:23-190): every record to a file picked by its CHROM or its DP ---- */
+enum { SPLIT_RANGE_BUCKETS = 255, SPLIT_NO_FILE = 255, SPLIT_OPEN_MAX = 64 };
+static int g_split_criterion;                            /* HPGV_SPLIT_CHROMOSOME / HPGV_SPLIT_COVERAGE of the current run */
+static long *g_split_iv; static int g_split_n_iv;        /* coverage: the ascending interval bounds */
+static const char *g_split_dir; static char g_split_base[512];      /* <out_dir>/<split name>_<base> */
+static long g_split_files, g_split_skipped;              /* files created and lines that went to no file, last run */
+static long g_split_key_ns;                              /* host time of split_keys over the engine threads, last run (HPGV_RUN_TRACE) */
+
+static inline unsigned char ascii_lower(unsigned char c) { return c >= 'A' && c <= 'Z' ? (unsigned char)(c | 0x20) : c; }
+static uint64_t hash_icase(const char *p, size_t n) {   /* FNV-1a of the lower-cased bytes: the key of cp_hash_istring */
+    uint64_t h = 1469598103934665603ull;
+    for (size_t k = 0; k < n; k++) h = (h ^ ascii_lower((unsigned char)p[k])) * 1099511628211ull;
+    return h;
+}
+static int eq_icase(const char *a, size_t na, const char *b, size_t nb) {
+    if (na != nb) return 0;
+    for (size_t k = 0; k < na; k++) if (ascii_lower((unsigned char)a[k]) != ascii_lower((unsigned char)b[k])) return 0;
+    return 1;
+}
+
+/* INFO's DP as atoi reads it: the first ';'-separated entry whose key is exactly DP; optional sign, then digits up to the
+ * first non-digit, none giving 0, saturated at the int64 range.  0 when there is no such entry or it is a bare flag. */
+static int info_dp(const char *info, size_t n, long long *v) {
+    size_t k = 0;
+    while (k <= n) {
+        size_t e = k;
+        while (e < n && info[e] != ';') e++;
+        if (e - k >= 2 && info[k] == 'D' && info[k + 1] == 'P' && (e - k == 2 || info[k + 2] == '=')) {
+            if (e - k == 2) return 0;                         /* a bare flag */
+            size_t q = k + 3;
+            int neg = 0;
+            if (q < e && (info[q] == '-' || info[q] == '+')) neg = info[q++] == '-';
+            unsigned long long m = 0, lim = neg ? (unsigned long long)LLONG_MAX + 1ull : (unsigned long long)LLONG_MAX;
+            for (; q < e && info[q] >= '0' && info[q] <= '9'; q++) {
+                const unsigned d = (unsigned)(info[q] - '0');
+                m = m > (lim - d) / 10 ? lim : m * 10 + d;
+            }
+            *v = neg ? (m == (unsigned long long)LLONG_MAX + 1ull ? LLONG_MIN : -(long long)m) : (long long)m;
+            return 1;
+        }
+        k = e + 1;
+    }
+    return 0;
+}
+
+/* the split name of coverage bucket j (0 .. n_iv: the intervals, n_iv + 1: no DP) */
+static int coverage_name(char *out, size_t cap, int j) {
+    const long *iv = g_split_iv; const int n = g_split_n_iv;
+    if (j > n) return snprintf(out, cap, "coverage_missing");
+    if (j == n) return snprintf(out, cap, "coverage_%ld_N", iv[n - 1]);
+    return snprintf(out, cap, "coverage_%ld_%ld", j ? iv[j - 1] : 0L, iv[j]);
+}
+
+/* a bucket named pre || body */
+static int sp_add_bucket(run_batch_t *b, const char *pre, size_t npre, const char *body, size_t nbody) {
+    if (b->sp_n_buckets == b->sp_bucket_cap) {
+        const int c = b->sp_bucket_cap ? 2 * b->sp_bucket_cap : 256;
+        uint64_t *l = (uint64_t *)realloc(b->sp_len, sizeof(uint64_t) * (size_t)c);
+        if (l) b->sp_len = l;
+        int *nm = (int *)realloc(b->sp_name, sizeof(int) * (size_t)c);
+        if (nm) b->sp_name = nm;
+        if (!l || !nm) return HPGV_ERR_NOMEM;
+        b->sp_bucket_cap = c;
+    }
+    const size_t len = npre + nbody;
+    if (b->sp_names_len + len + 1 > b->sp_names_cap) {
+        const size_t c = 2 * (b->sp_names_len + len + 1) + 4096;
+        char *p = c > (size_t)INT32_MAX ? NULL : (char *)realloc(b->sp_names, c);
+        if (!p) return HPGV_ERR_NOMEM;
+        b->sp_names = p; b->sp_names_cap = c;
+    }
+    b->sp_name[b->sp_n_buckets] = (int)b->sp_names_len;
+    b->sp_len[b->sp_n_buckets++] = 0;
+    memcpy(b->sp_names + b->sp_names_len, pre, npre);
+    memcpy(b->sp_names + b->sp_names_len + npre, body, nbody);
+    b->sp_names[b->sp_names_len + len] = 0;
+    b->sp_names_len += len + 1;
+    return HPGV_OK;
+}
+static int sp_add_range(run_batch_t *b, int first, int n, int nb) {
+    if (b->sp_n_ranges == b->sp_range_cap) {
+        const int c = b->sp_range_cap ? 2 * b->sp_range_cap : 16;
+        int *r = (int *)realloc(b->sp_range, sizeof(int) * 3 * (size_t)c);
+        if (!r) return HPGV_ERR_NOMEM;
+        b->sp_range = r; b->sp_range_cap = c;
+    }
+    int *r = b->sp_range + 3 * b->sp_n_ranges++;
+    r[0] = first; r[1] = n; r[2] = nb;
+    return HPGV_OK;
+}
+
+/* the bucket of every line, from the heads (CHROM and INFO are in them whatever the text's residence); a batch with more than
+ * SPLIT_RANGE_BUCKETS split names is cut into consecutive line ranges of at most that many.  A line with the CHROM of the line
+ * before it takes its bucket without a lookup. */
+static int split_keys(run_batch_t *b) {
+    const int n = b->n_lines;
+    int tab[512];                                         /* open addressing over the range's buckets (<= 255): bucket + 1 */
+    size_t tab_len[SPLIT_RANGE_BUCKETS];                  /* chromosome: the CHROM length of each bucket of the range */
+    int *cov = (int *)malloc(sizeof(int) * ((size_t)g_split_n_iv + 2));      /* coverage: bucket of interval j in the range, or -1 */
+    char name[96];
+    if (!cov) return HPGV_ERR_NOMEM;
+    memset(tab, 0, sizeof tab);
+    for (int j = 0; j < g_split_n_iv + 2; j++) cov[j] = -1;
+    int first = 0, nb = 0, base = 0, prev = -1, rc = HPGV_OK;           /* base: global index of the range's bucket 0 */
+    const char *pc = NULL; size_t pl = 0;
+    for (int i = 0; i < n; i++) {
+        const uint32_t *fo = b->field_off + 10 * (size_t)i;
+        if (fo[7] == 0xFFFFFFFFu) { b->keep[i] = SPLIT_NO_FILE; b->n_skip++; continue; }     /* fewer than CHROM .. INFO, or empty */
+        const char *l = b->text + b->line_off[i];
+        int id = -1, j = 0;
+        const char *c = l; const size_t cl = fo[1] - 1;
+        uint64_t h = 0;
+        if (g_split_criterion == HPGV_SPLIT_CHROMOSOME) {
+            if (prev >= 0 && cl == pl && !memcmp(c, pc, cl)) id = prev;
+            else {
+                h = hash_icase(c, cl);
+                for (size_t s = h & 511; tab[s]; s = (s + 1) & 511) {
+                    const int t = tab[s] - 1;
+                    if (eq_icase(c, cl, b->sp_names + b->sp_name[base + t] + 11, tab_len[t])) { id = t; break; }
+                }
+            }
+        } else {
+            size_t ie = fo[8] != 0xFFFFFFFFu ? (size_t)fo[8] - 1 : (size_t)(b->line_off[i + 1] - b->line_off[i]);
+            if (fo[8] == 0xFFFFFFFFu && ie > fo[7] && l[ie - 1] == '\n') ie--;
+            long long v = 0;
+            if (!info_dp(l + fo[7], ie - fo[7], &v)) j = g_split_n_iv + 1;
+            else {                                        /* the first bound >= v, or n_iv */
+                int lo = 0, hi = g_split_n_iv;
+                while (lo < hi) { const int mid = (lo + hi) >> 1; if (v > (long long)g_split_iv[mid]) lo = mid + 1; else hi = mid; }
+                j = lo;
+            }
+            id = cov[j];
+        }
+        if (id < 0) {                                     /* a split name new to the range */
+            if (nb == SPLIT_RANGE_BUCKETS) {
+                if (sp_add_range(b, first, i - first, nb)) { rc = HPGV_ERR_NOMEM; break; }
+                first = i; base += nb; nb = 0; prev = -1;
+                memset(tab, 0, sizeof tab);
+                for (int k = 0; k < g_split_n_iv + 2; k++) cov[k] = -1;
+            }
+            id = nb++;
+            if (g_split_criterion == HPGV_SPLIT_CHROMOSOME) {
+                size_t t = h & 511;
+                while (tab[t]) t = (t + 1) & 511;
+                tab[t] = id + 1; tab_len[id] = cl;
+                if (sp_add_bucket(b, "chromosome_", 11, c, cl)) { rc = HPGV_ERR_NOMEM; break; }
+            } else {
+                cov[j] = id;
+                const int len = coverage_name(name, sizeof name, j);
+                if (sp_add_bucket(b, name, (size_t)len, "", 0)) { rc = HPGV_ERR_NOMEM; break; }
+            }
+        }
+        b->keep[i] = (uint8_t)id; b->n_pass++;
+        prev = id; pc = c; pl = cl;
+    }
+    if (!rc && nb > 0 && sp_add_range(b, first, n - first, nb)) rc = HPGV_ERR_NOMEM;
+    free(cov);
+    return rc;
+}
+
+/* the split tool's engine step after hpgv_filter_text, while the batch's text is still on the device: the bucket of every
+ * line, then each line range split there into the next part of the batch's own page-locked buffer */
+static int split_partition(run_batch_t *b) {
+    const int n = b->n_lines;
+    if (n > b->max_lines) return HPGV_ERR_UNSUPPORTED;
+    b->n_pass = 0; b->n_skip = 0; b->sp_n_ranges = 0; b->sp_n_buckets = 0; b->sp_names_len = 0;
+    int rc = HPGV_OK;
+    if (b->keep_cap < n) {
+        free(b->keep);
+        b->keep = (uint8_t *)malloc((size_t)n + 1);
+        b->keep_cap = b->keep ? n : 0;
+        if (!b->keep) rc = HPGV_ERR_NOMEM;
+    }
+    const double t0 = now_s();
+    if (!rc) rc = split_keys(b);                           /* every key before the first copy back overwrites the heads */
+    __atomic_add_fetch(&g_split_key_ns, (long)((now_s() - t0) * 1e9), __ATOMIC_RELAXED);
+    uint64_t boff[SPLIT_RANGE_BUCKETS + 1];
+    size_t pos = 0;
+    for (int r = 0, k = 0; !rc && r < b->sp_n_ranges; r++) {
+        const int *R = b->sp_range + 3 * r;
+        rc = hpgv_text_multisplit(g_ctx, b->text, b->keep + R[0], R[0], R[1], R[2], b->text + pos, b->text_cap - pos, boff);
+        if (rc) break;
+        for (int j = 0; j < R[2]; j++) b->sp_len[k++] = boff[j + 1] - boff[j];
+        pos += (size_t)boff[R[2]];
+    }
+    (void)hpgv_text_partition(g_ctx, b->text, NULL, 0, NULL, 0, NULL, NULL);     /* the hold released */
+    return rc;
+}
+
 static void *pipe_engine(void *v) {
     run_pipe_t *P = (run_pipe_t *)v;
     const int kind = P->kind;
@@ -116,7 +307,7 @@ static void *pipe_engine(void *v) {
                 rc = hpgv_stats_text_groups(g_ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status, b->c8, b->hw, b->hw + m,
                                             kind == 6 ? b->smiss : NULL, b->midx, b->mtab, &b->n_multi, mend ? b->merr : NULL, mend ? b->cerr : NULL,
                                             b->n_groups ? b->gc8 : NULL, b->n_groups ? b->ghw : NULL, b->n_groups ? b->ghw + gm : NULL);
-            } else if (kind == 7)
+            } else if (kind == 7 || kind == 8)
                 rc = hpgv_filter_text(g_ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status);
             else if (kind == 4)
                 rc = hpgv_epi_dataset_text(g_ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status, b->rows);
@@ -140,13 +331,14 @@ static void *pipe_engine(void *v) {
             if (run_batch_reserve(b, b->n_lines)) { rc = HPGV_ERR_NOMEM; break; }
         }
         if (kind == 7 && !rc) rc = filter_partition(b);               /* before the alias is dropped: the window is the source */
+        if (kind == 8 && !rc) rc = split_partition(b);
         if (b->dev_text) (void)hpgv_text_alias(b->dev_ctx ? b->dev_ctx : g_ctx, b->text, NULL);
         const double dt = now_s() - t0;
         pthread_mutex_lock(&P->mu);
         P->t_engine += dt;
         if (rc) {
             char msg[256];
-            snprintf(msg, sizeof msg, "%s failed (%d): %s", kind == 7 ? "hpgv_filter_text / hpgv_text_partition" : kind >= 5 ? "hpgv_stats_text" : kind == 4 ? "hpgv_epi_dataset_text" : kind == 3 ? "hpgv_tdt_text" : "hpgv_assoc_text", rc,
+            snprintf(msg, sizeof msg, "%s failed (%d): %s", kind == 7 ? "hpgv_filter_text / hpgv_text_partition" : kind == 8 ? "hpgv_filter_text / hpgv_text_multisplit" : kind >= 5 ? "hpgv_stats_text" : kind == 4 ? "hpgv_epi_dataset_text" : kind == 3 ? "hpgv_tdt_text" : "hpgv_assoc_text", rc,
                      rc == HPGV_ERR_NOMEM ? "out of memory" : hpgv_last_error(g_ctx));
             pipe_fail(P, rc, msg);
             pthread_mutex_unlock(&P->mu);
@@ -275,6 +467,108 @@ static int write_filter_header(FILE *f, const char *hdr, size_t chrom_off, const
     if (g_filters.num_alleles >= 0) fprintf(f, "##FILTER=<ID=alleles,Description=\"Number of alleles == %g\">\n", (double)g_filters.num_alleles);
     if (g_filters.min_quality >= 0.0) fprintf(f, "##FILTER=<ID=quality,Description=\"Quality >= %g\">\n", g_filters.min_quality);
     return chrom_len && fwrite(chrom_line, 1, chrom_len, f) != chrom_len;
+}
+
+/* hpg-var-vcf split: the output files, by split name (case-insensitive, as the reference's cp_hash_istring table).  A file is
+ * created by the first record it receives, with the input header, and named after that record; at most SPLIT_OPEN_MAX are
+ * open at once -- the least recently written is closed and reopened later for appending. */
+typedef struct { char *name, *path; FILE *fd; long last; int created; } split_file_t;
+typedef struct {
+    split_file_t *f; int n, cap;
+    int *tab; size_t tab_cap;                            /* open addressing: file + 1 */
+    int open[SPLIT_OPEN_MAX]; int n_open; long clock;
+    const char *hdr; size_t chrom_off; const char *chrom_line; size_t chrom_len;
+} split_files_t;
+
+static FILE *split_file(split_files_t *S, const char *name) {
+    snprintf(g_err, sizeof g_err, "out of memory for the split files");
+    if (!S->tab) {
+        S->tab_cap = 256;
+        if (!(S->tab = (int *)calloc(S->tab_cap, sizeof(int)))) { S->tab_cap = 0; return NULL; }
+    }
+    const size_t nl = strlen(name);
+    const uint64_t h = hash_icase(name, nl);
+    size_t t = h & (S->tab_cap - 1);
+    for (; S->tab[t]; t = (t + 1) & (S->tab_cap - 1))
+        if (eq_icase(name, nl, S->f[S->tab[t] - 1].name, strlen(S->f[S->tab[t] - 1].name))) break;
+    int k = S->tab[t] - 1;
+    if (k < 0) {                                         /* a new file: <out_dir>/<split name, '/' and '%' escaped>_<base> */
+        if (S->n == S->cap || 2 * (size_t)(S->n + 1) > S->tab_cap) {
+            const int c = S->cap ? 2 * S->cap : 64;
+            split_file_t *f = (split_file_t *)realloc(S->f, sizeof *f * (size_t)c);
+            if (!f) return NULL;
+            S->f = f; S->cap = c;
+            int *tab = (int *)calloc(4 * (size_t)c, sizeof(int));
+            if (!tab) return NULL;
+            free(S->tab); S->tab = tab; S->tab_cap = 4 * (size_t)c;
+            for (int q = 0; q < S->n; q++) {
+                const char *nm = S->f[q].name;
+                size_t u = hash_icase(nm, strlen(nm)) & (S->tab_cap - 1);
+                while (S->tab[u]) u = (u + 1) & (S->tab_cap - 1);
+                S->tab[u] = q + 1;
+            }
+            for (t = h & (S->tab_cap - 1); S->tab[t]; t = (t + 1) & (S->tab_cap - 1)) {}
+        }
+        split_file_t *F = &S->f[S->n];
+        memset(F, 0, sizeof *F);
+        const size_t dl = strlen(g_split_dir), bl = strlen(g_split_base);
+        F->name = dupn(name, (int)nl);
+        F->path = (char *)malloc(dl + 3 * nl + bl + 3);
+        if (!F->name || !F->path) { free(F->name); free(F->path); return NULL; }
+        char *p = F->path;
+        memcpy(p, g_split_dir, dl); p += dl; *p++ = '/';
+        for (size_t q = 0; q < nl; q++) {
+            if (name[q] == '/') { memcpy(p, "%2F", 3); p += 3; }
+            else if (name[q] == '%') { memcpy(p, "%25", 3); p += 3; }
+            else *p++ = name[q];
+        }
+        *p++ = '_'; memcpy(p, g_split_base, bl + 1);
+        k = S->n++;
+        S->tab[t] = k + 1;
+    }
+    split_file_t *F = &S->f[k];
+    F->last = ++S->clock;
+    if (F->fd) return F->fd;
+    if (S->n_open == SPLIT_OPEN_MAX) {                   /* close the least recently written */
+        int o = 0;
+        for (int q = 1; q < S->n_open; q++) if (S->f[S->open[q]].last < S->f[S->open[o]].last) o = q;
+        split_file_t *G = &S->f[S->open[o]];
+        const int bad = fclose(G->fd) != 0;
+        G->fd = NULL;
+        S->open[o] = S->open[--S->n_open];
+        if (bad) { snprintf(g_err, sizeof g_err, "cannot write %s", G->path); return NULL; }
+    }
+    const int created = !F->created;
+    F->fd = fopen(F->path, created ? "wb" : "ab");       /* only the first open in a run truncates */
+    if (!F->fd) { snprintf(g_err, sizeof g_err, "cannot create %s", F->path); return NULL; }
+    S->open[S->n_open++] = k;
+    if (created) {
+        F->created = 1; g_split_files++;
+        if ((S->chrom_off && fwrite(S->hdr, 1, S->chrom_off, F->fd) != S->chrom_off) ||
+            (S->chrom_len && fwrite(S->chrom_line, 1, S->chrom_len, F->fd) != S->chrom_len)) { snprintf(g_err, sizeof g_err, "cannot write %s", F->path); return NULL; }
+    }
+    return F->fd;
+}
+static int write_split_batch(split_files_t *S, const run_batch_t *b) {
+    size_t pos = 0;
+    for (int k = 0; k < b->sp_n_buckets; k++) {
+        const char *name = b->sp_names + b->sp_name[k];
+        FILE *fd = split_file(S, name);
+        if (!fd) return 1;
+        if (write_region(fd, b->text + pos, (size_t)b->sp_len[k], 0)) { snprintf(g_err, sizeof g_err, "cannot write the file of %s", name); return 1; }
+        pos += (size_t)b->sp_len[k];
+    }
+    return 0;
+}
+static int split_files_close(split_files_t *S) {
+    int bad = 0;
+    for (int k = 0; k < S->n; k++) {
+        if (S->f[k].fd && fclose(S->f[k].fd) != 0 && !bad) { bad = 1; snprintf(g_err, sizeof g_err, "cannot write %s", S->f[k].path); }
+        free(S->f[k].name); free(S->f[k].path);
+    }
+    free(S->f); free(S->tab);
+    memset(S, 0, sizeof *S);
+    return bad;
 }
 
 static int run_file(const char *vcf_path, const char *ped_path, const char *out_path, int kind, size_t batch_bytes,
@@ -458,8 +752,8 @@ static int run_file(const char *vcf_path, const char *ped_path, const char *out_
         path_rej = (char *)malloc(strlen(out_path) + 32);
         if (path_rej) sprintf(path_rej, "%s.rejected", out_path); else rc = rc ? rc : HPGV_ERR_NOMEM;
     }
-    FILE *out = rc ? NULL : fopen(path6 ? path6 : out_path, "wb");
-    if (!rc && !out) { snprintf(g_err, sizeof g_err, "cannot create %s", path6 ? path6 : out_path); rc = HPGV_ERR_INVALID; }
+    FILE *out = rc || kind == 8 ? NULL : fopen(path6 ? path6 : out_path, "wb");      /* (split: its files as records come) */
+    if (!rc && kind != 8 && !out) { snprintf(g_err, sizeof g_err, "cannot create %s", path6 ? path6 : out_path); rc = HPGV_ERR_INVALID; }
     FILE *out_rej = rc || kind != 7 ? NULL : fopen(path_rej, "wb");     /* created empty without save_rejected (filter_runner.c:63-68) */
     if (!rc && kind == 7 && !out_rej) { snprintf(g_err, sizeof g_err, "cannot create %s", path_rej); rc = HPGV_ERR_INVALID; }
     FILE **gfd = NULL;
@@ -474,6 +768,9 @@ static int run_file(const char *vcf_path, const char *ped_path, const char *out_
         free(gp);
         if (!gfd) rc = HPGV_ERR_NOMEM;
     }
+    split_files_t SF;
+    memset(&SF, 0, sizeof SF);
+    SF.hdr = hdr; SF.chrom_off = chrom_off; SF.chrom_line = rd.chrom_line; SF.chrom_len = rd.chrom_len;
     run_stats_t *RS = NULL;
     if (!rc && kind == 6) {
         RS = (run_stats_t *)calloc(1, sizeof *RS);
@@ -558,7 +855,7 @@ static int run_file(const char *vcf_path, const char *ped_path, const char *out_
         file_writer_t fw;
         memset(&fw, 0, sizeof fw);
         /* (the vcf2epi rows are written out of the batch itself, and the stats tool's group files by this thread) */
-        const int use_fw = kind != 4 && kind != 7 && !g_env.no_writer_thread && file_writer_start(&fw, out);
+        const int use_fw = kind != 4 && kind != 7 && kind != 8 && !g_env.no_writer_thread && file_writer_start(&fw, out);
         int fmt_set = 0;
         pthread_t th[1 + RUN_ENGINES_MAX];
         int n_th = 0;
@@ -579,16 +876,23 @@ static int run_file(const char *vcf_path, const char *ped_path, const char *out_
             const double t0 = now_s();
             const run_batch_t *b = &P->bt[k];
             const int bad = kind == 7 ? write_filter_batch(out, g_filter_save_rejected ? out_rej : NULL, b)       /* two fwrites */
+                          : kind == 8 ? write_split_batch(&SF, b)                                                   /* one fwrite per bucket */
                                       : write_batch(out, kind, b, fmt + (fmt_set ? RUN_FMT_BUFS / 2 : 0), n_fmt, &wpool, &ord, use_fw ? &fw : NULL);
             fmt_set ^= use_fw;
             if (kind == 7) { written += b->n_pass; g_filter_rejected += b->n_rej; }      /* (the batch's text is the partition now) */
+            else if (kind == 8) { written += b->n_pass; g_split_skipped += b->n_skip; }
             else for (int i = 0; i < b->n_lines; i++) if (record_passes(b, i)) written++;
             if (kind == 6 && !bad) run_stats_add(RS, b, n_samples, trio_child);
             if (kind == 6 && !bad && gfd) write_group_lines(gfd, b);
             const double dt = now_s() - t0;
             pthread_mutex_lock(&P->mu);
             P->t_write += dt;
-            if (bad) { pipe_fail(P, HPGV_ERR_INVALID, "cannot write the result file"); break; }
+            if (bad) {
+                char msg[200];
+                snprintf(msg, sizeof msg, "%.199s", kind == 8 ? g_err : "cannot write the result file");      /* (split: what split_file said) */
+                pipe_fail(P, HPGV_ERR_INVALID, msg);
+                break;
+            }
             P->state[k] = B_FREE; P->n_written++;
             pthread_cond_broadcast(&P->cv);
         }
@@ -607,6 +911,7 @@ static int run_file(const char *vcf_path, const char *ped_path, const char *out_
     }
     if (out && fclose(out) != 0 && !rc) { snprintf(g_err, sizeof g_err, "cannot write %s", path6 ? path6 : out_path); rc = HPGV_ERR_INVALID; }
     if (out_rej && fclose(out_rej) != 0 && !rc) { snprintf(g_err, sizeof g_err, "cannot write %s", path_rej); rc = HPGV_ERR_INVALID; }
+    if (split_files_close(&SF) && !rc) rc = HPGV_ERR_INVALID;
     {
         const double t0 = now_s();
         /* (in order as written: nothing to do; HPGV_ALWAYS_SORT=1 reads the file back and checks all the same) */
@@ -633,6 +938,8 @@ static int run_file(const char *vcf_path, const char *ped_path, const char *out_
     if (g_env.run_trace)
         fprintf(stderr, "hpgv run: %ld records, %.0f batches, %d io threads: read %.3f s, engine %.3f s (%d threads), write %.3f s (stages overlap), sort %.3f s, total %.3f s\n",
                 written, g_run_times[5], io_threads, g_run_times[0], g_run_times[1], n_engines_used, g_run_times[2], t_sort, g_run_times[4]);
+    if (g_env.run_trace && kind == 8)
+        fprintf(stderr, "hpgv run: split keys %.4f s (host, summed over the engine threads)\n", (double)g_split_key_ns * 1e-9);
     const double t_done = now_s();
     source_close(&rd.src); free(rd.carry); free(rd.tailbuf); free(rd.chrom_line); free(hdr); free(names); ped_table_free(&ped);
     if (n_variants_out) *n_variants_out = written;
@@ -729,6 +1036,51 @@ int hpgv_run_filter(const char *vcf_path, const char *ped_path, const char *out_
     g_filter_rejected = 0;
     const int rc = run_file(vcf_path, ped_path, out_prefix, 7, batch_bytes, n_passed_out);
     if (n_rejected_out) *n_rejected_out = g_filter_rejected;
+    return rc;
+}
+
+/* run_split (src/vcf-tools/split/split_runner.c:23-190, split_options_parsing.c:114-140): every record of the VCF to
+ * <out_dir>/<split name>_<base of the input>, the split name from its CHROM or from INFO's DP */
+int hpgv_run_split(const char *vcf_path, const char *out_dir, int criterion, const long *intervals, int n_intervals,
+                   size_t batch_bytes, long *n_records_out, long *n_files_out, long *n_skipped_out) {
+    if (n_records_out) *n_records_out = 0;
+    if (n_files_out) *n_files_out = 0;
+    if (n_skipped_out) *n_skipped_out = 0;
+    if (!vcf_path || !out_dir) { snprintf(g_err, sizeof g_err, "vcf_path and out_dir must not be NULL"); return HPGV_ERR_INVALID; }
+    if (criterion != HPGV_SPLIT_CHROMOSOME && criterion != HPGV_SPLIT_COVERAGE) {
+        snprintf(g_err, sizeof g_err, "unknown split criterion %d", criterion);
+        return HPGV_ERR_INVALID;
+    }
+    if (criterion == HPGV_SPLIT_COVERAGE) {
+        if (!intervals || n_intervals < 1) { snprintf(g_err, sizeof g_err, "the coverage criterion needs at least one interval"); return HPGV_ERR_INVALID; }
+        for (int j = 1; j < n_intervals; j++)
+            if (intervals[j] <= intervals[j - 1]) { snprintf(g_err, sizeof g_err, "the coverage intervals must be strictly increasing"); return HPGV_ERR_INVALID; }
+    }
+    const char *slash = strrchr(vcf_path, '/');
+    const char *base = slash ? slash + 1 : vcf_path;
+    size_t bl = strlen(base);
+    if (bl > 3 && !strcmp(base + bl - 3, ".gz")) bl -= 3;                   /* the files hold plain text */
+    else if (bl > 4 && !strcmp(base + bl - 4, ".bgz")) bl -= 4;
+    if (bl >= sizeof g_split_base) { snprintf(g_err, sizeof g_err, "the input's file name is too long"); return HPGV_ERR_INVALID; }
+    struct stat st;
+    if (mkdir(out_dir, 0777) != 0 && !(errno == EEXIST && stat(out_dir, &st) == 0 && S_ISDIR(st.st_mode))) {     /* create_directory: one level */
+        snprintf(g_err, sizeof g_err, "cannot create the output directory %s", out_dir);
+        return HPGV_ERR_INVALID;
+    }
+    memcpy(g_split_base, base, bl); g_split_base[bl] = 0;
+    g_split_dir = out_dir; g_split_criterion = criterion;
+    g_split_n_iv = criterion == HPGV_SPLIT_COVERAGE ? n_intervals : 0;
+    g_split_iv = (long *)malloc(sizeof(long) * ((size_t)g_split_n_iv + 1));
+    if (!g_split_iv) return HPGV_ERR_NOMEM;
+    if (g_split_n_iv) memcpy(g_split_iv, intervals, sizeof(long) * (size_t)g_split_n_iv);
+    g_split_files = g_split_skipped = 0; g_split_key_ns = 0;
+    const hpgv_run_filters_t saved = g_filters;            /* split has no record filters: every record goes to a file */
+    hpgv_run_set_filters(NULL);
+    const int rc = run_file(vcf_path, NULL, out_dir, 8, batch_bytes, n_records_out);
+    g_filters = saved;
+    free(g_split_iv); g_split_iv = NULL; g_split_n_iv = 0;
+    if (n_files_out) *n_files_out = g_split_files;
+    if (n_skipped_out) *n_skipped_out = g_split_skipped;
     return rc;
 }
 

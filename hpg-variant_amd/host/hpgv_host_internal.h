@@ -148,6 +148,13 @@ typedef struct {
     uint8_t *keep; int keep_cap;                         /* filter: record_passes per line, then the partitioned text in `text` */
     uint64_t part_kept, part_total;                      /* ... its kept bytes first, part_total bytes in all */
     long n_pass, n_rej; int n_blank;                     /* ... records kept, records rejected, empty lines (in neither file) */
+    /* split: the bucket of every line in keep (SPLIT_NO_FILE: none), the line ranges of one hpgv_text_multisplit each, and per
+     * bucket (over all ranges, in order) its split name and its bytes; the buckets' lines back to back in `text`.  n_pass:
+     * records written, n_skip: lines that go to no file */
+    int *sp_range; int sp_n_ranges, sp_range_cap;         /* per range: first line, lines, buckets */
+    uint64_t *sp_len; int *sp_name; int sp_n_buckets, sp_bucket_cap;      /* per bucket: bytes, offset of its name in sp_names */
+    char *sp_names; size_t sp_names_len, sp_names_cap;    /* the split names, NUL-terminated, back to back */
+    long n_skip;
 } run_batch_t;
 
 typedef struct { int na, miss_al, miss_gt, ac[15], gc[225]; } vcounts_t;

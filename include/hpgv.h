@@ -396,6 +396,25 @@ int  hpgv_text_partition(hpgv_ctx *ctx, const char *text, const uint8_t *keep, i
 size_t hpgv_lines_partition_scratch_bytes(int n_lines);
 int  hpgv_lines_partition_dev(hpgv_ctx *ctx, const char *d_text, const uint64_t *d_line_off, int n_lines, const uint8_t *d_keep,
                               char *d_out, uint64_t *d_kept_bytes, void *d_scratch, void *stream);
+/* hpg-var-vcf split (split_runner.c:23-190): the same partition with n_buckets ways.  Lines [first_line, first_line +
+ * n_lines) of the text the last hpgv_filter_text on `text` holds, line first_line + k going to bucket bucket[k]: every line
+ * of bucket 0 back to back in line order, then those of bucket 1, ..., copied into `out`.  bucket_off (host, n_buckets + 1
+ * entries): bucket b occupies out[bucket_off[b] .. bucket_off[b + 1]), bucket_off[n_buckets] = the bytes stored, which must
+ * fit in out_cap.  A line whose id is >= n_buckets goes nowhere.  n_buckets: 1 .. 256.  Unlike hpgv_text_partition this
+ * releases nothing: call it for as many line ranges as needed, then hpgv_text_partition(..., keep = NULL, ...).  The
+ * uploaded copy, an aliased window and group contexts as there.  Synchronous. */
+int  hpgv_text_multisplit(hpgv_ctx *ctx, const char *text, const uint8_t *bucket, int first_line, int n_lines, int n_buckets,
+                          char *out, size_t out_cap, uint64_t *bucket_off);
+/* The device primitive: lines i = 0 .. n_lines - 1 of d_text (as for hpgv_lines_partition_dev) into d_out, the lines of
+ * bucket b = d_bucket[i] back to back in line order from d_bucket_off[b], the buckets one after another in id order,
+ * d_bucket_off[n_buckets] = the end (device memory, n_buckets + 1 entries).  A line with d_bucket[i] >= n_buckets is not
+ * stored; nothing outside [d_out, d_out + d_bucket_off[n_buckets]) is stored; d_text and d_out may have any alignment.
+ * n_buckets = 2 with d_bucket = !keep gives hpgv_lines_partition_dev's bytes.  n_buckets: 1 .. 256, and n_buckets x
+ * ceil(n_lines / 64) below INT_MAX.  d_scratch: hpgv_lines_multisplit_scratch_bytes(n_lines, n_buckets) bytes of device
+ * memory (8-byte aligned).  Asynchronous on `stream`. */
+size_t hpgv_lines_multisplit_scratch_bytes(int n_lines, int n_buckets);
+int  hpgv_lines_multisplit_dev(hpgv_ctx *ctx, const char *d_text, const uint64_t *d_line_off, int n_lines, const uint8_t *d_bucket,
+                               int n_buckets, char *d_out, uint64_t *d_bucket_off, void *d_scratch, void *stream);
 
 /* the same rows from a batch of VCF text (tokenized on the device like hpgv_assoc_text): row v of `out` belongs to
  * line v; lines that are not records (field_off[10 v + 5] == 0xFFFFFFFF) leave their row undefined */

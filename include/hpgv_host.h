@@ -328,6 +328,33 @@ void hpgv_run_set_filters(const hpgv_run_filters_t *filters);
  * without save_rejected). */
 int  hpgv_run_filter(const char *vcf_path, const char *ped_path, const char *out_prefix, int save_rejected,
                      size_t batch_bytes, long *n_passed_out, long *n_rejected_out);
+/* run_split (src/vcf-tools/split/split_runner.c:23-190, split.c:37-122, hpg-var-vcf split): every record of the VCF to
+ * <out_dir>/<split name>_<base>, <base> being the input's file name.  Split names (split_options_parsing.c:114-140):
+ *   HPGV_SPLIT_CHROMOSOME   chromosome_<CHROM>
+ *   HPGV_SPLIT_COVERAGE     by v = INFO's DP against the ascending bounds intervals[0 .. n_intervals - 1] = I0 < I1 < ...:
+ *                           coverage_0_<I0> for v <= I0 (the low end is 0 whatever v), coverage_<Ij-1>_<Ij> for
+ *                           Ij-1 < v <= Ij, coverage_<In-1>_N for v > In-1; numbers as %ld
+ * Names are compared case-insensitively, as the reference's table of open files does (cp_hash_istring): chr1 and CHR1 go to
+ * one file, named after the first such record in file order.  A file is created by its first record (a bucket without records
+ * has no file) with the input header verbatim up to and including its #CHROM line, then holds its records byte for byte.
+ * out_dir is created when missing (one level, as create_directory).  Where this differs from the reference on purpose:
+ *   - records are written in file order within each file (the reference writes them as its workers finish);
+ *   - a record whose INFO has no entry with the key exactly DP, or only a bare DP flag, goes to coverage_missing (the
+ *     reference crashes in atoi(NULL)); entries are ';'-separated and the first DP counts; its value is read as atoi does --
+ *     an optional sign, then digits up to the first non-digit, none giving 0 -- saturated at the int64 range;
+ *   - a trailing .gz / .bgz is dropped from <base>: the files hold plain text;
+ *   - in file names only, '/' is written %2F and '%' is written %25, so no CHROM names a path outside out_dir;
+ *   - lines with fewer than 8 fields (CHROM .. INFO), empty lines included, go to no file; a sites-only VCF is valid input;
+ *   - a last line without a newline gets one;
+ *   - at most 64 files are open at once (the reference keeps all open; a contig-rich assembly would run out of
+ *     descriptors): the least recently written is closed and reopened later for appending.
+ * NULL paths, an unknown criterion, coverage without intervals or with intervals that do not strictly increase, and an out_dir
+ * that cannot be created return HPGV_ERR_INVALID before the engine starts, and no file is written.  The lines of a batch
+ * are bucketed on the device that tokenized them (hpgv_text_multisplit), whatever the input's compression.
+ * *n_records_out: records written; *n_files_out: files created; *n_skipped_out: lines that went to no file (each may be NULL). */
+enum { HPGV_SPLIT_CHROMOSOME = 1, HPGV_SPLIT_COVERAGE = 2 };
+int  hpgv_run_split(const char *vcf_path, const char *out_dir, int criterion, const long *intervals, int n_intervals,
+                    size_t batch_bytes, long *n_records_out, long *n_files_out, long *n_skipped_out);
 /* create_dataset_from_vcf (src/vcf-tools/vcf2epi/dataset_creator.c:24-222) without its filters: the binary
  * dataset hpgv_run_epistasis reads -- uint32 num_variants, num_affected, num_unaffected, then per variant
  * one byte per sample, cases first (0 "0/0", 1 heterozygous, 2 homozygous non-reference, 255 missing);
