@@ -20,30 +20,9 @@ static int run_batch_stats_arrays(run_batch_t *b) {
     return (b->c8 && b->hw && b->merr && b->midx && b->smiss && b->cerr) ? HPGV_OK : HPGV_ERR_NOMEM;
 }
 
-int run_batch_alloc(run_batch_t *b, size_t cap_bytes, int n_samples, int row_width, int stats, int n_trios, int n_groups) {
-    memset(b, 0, sizeof *b);
-    b->row_width = row_width;
-    b->stats = stats; b->n_smiss = n_samples; b->n_cerr = n_trios; b->n_groups = n_groups;
-    size_t min_line = (size_t)(2 * (n_samples > 0 ? n_samples : 1) + 18);
-    b->max_lines = (int)(cap_bytes / min_line) + 2;
-    b->text = NULL; b->text_cap = cap_bytes + 1;         /* taken by the reader at the batch's first use: the pipeline starts meanwhile */
-    b->line_off = (uint64_t *)malloc(sizeof(uint64_t) * ((size_t)b->max_lines + 1));
-    b->field_off = (uint32_t *)malloc(sizeof(uint32_t) * 10 * (size_t)b->max_lines);
-    b->status = (int32_t *)malloc(sizeof(int32_t) * (size_t)b->max_lines);
-    b->ints = (int32_t *)malloc(sizeof(int32_t) * 4 * (size_t)b->max_lines);
-    b->dbl = (double *)malloc(sizeof(double) * 3 * (size_t)b->max_lines);
-    if (b->row_width > 0) {
-        b->rows_cap = (size_t)b->max_lines * (size_t)b->row_width;
-        if (!(b->rows = (uint8_t *)malloc(b->rows_cap + 1))) return HPGV_ERR_NOMEM;
-    }
-    if (run_batch_stats_arrays(b)) return HPGV_ERR_NOMEM;
-    return (b->line_off && b->field_off && b->status && b->ints && b->dbl) ? HPGV_OK : HPGV_ERR_NOMEM;
-}
-/* makes room for `lines` records (short or truncated lines can exceed the estimate) */
-int run_batch_reserve(run_batch_t *b, int lines) {
-    if (lines <= b->max_lines) return HPGV_OK;
+/* the per-line arrays for max_lines lines (the ones there before freed) */
+static int run_batch_lines(run_batch_t *b) {
     free(b->line_off); free(b->field_off); free(b->status); free(b->ints); free(b->dbl);
-    b->max_lines = lines + lines / 8 + 2;
     b->line_off = (uint64_t *)malloc(sizeof(uint64_t) * ((size_t)b->max_lines + 1));
     b->field_off = (uint32_t *)malloc(sizeof(uint32_t) * 10 * (size_t)b->max_lines);
     b->status = (int32_t *)malloc(sizeof(int32_t) * (size_t)b->max_lines);
@@ -56,6 +35,22 @@ int run_batch_reserve(run_batch_t *b, int lines) {
     }
     if (run_batch_stats_arrays(b)) return HPGV_ERR_NOMEM;
     return (b->line_off && b->field_off && b->status && b->ints && b->dbl) ? HPGV_OK : HPGV_ERR_NOMEM;
+}
+int run_batch_alloc(run_batch_t *b, run_t *run, size_t cap_bytes, int n_samples, int n_trios, int n_groups) {
+    memset(b, 0, sizeof *b);
+    b->run = run;
+    b->row_width = run->tool == RUN_VCF2EPI ? n_samples : 0;        /* vcf2epi: one dataset row per line */
+    b->stats = tool_counts(run->tool); b->n_smiss = n_samples; b->n_cerr = n_trios; b->n_groups = n_groups;
+    size_t min_line = (size_t)(2 * (n_samples > 0 ? n_samples : 1) + 18);
+    b->max_lines = (int)(cap_bytes / min_line) + 2;
+    b->text = NULL; b->text_cap = cap_bytes + 1;         /* taken by the reader at the batch's first use: the pipeline starts meanwhile */
+    return run_batch_lines(b);
+}
+/* makes room for `lines` records (short or truncated lines can exceed the estimate) */
+int run_batch_reserve(run_batch_t *b, int lines) {
+    if (lines <= b->max_lines) return HPGV_OK;
+    b->max_lines = lines + lines / 8 + 2;
+    return run_batch_lines(b);
 }
 void run_batch_free(run_batch_t *b) {
     text_buf_put(b->text, b->text_cap);
@@ -119,9 +114,10 @@ int hpgv_host_format_f6(double x, char *dst) {
 static int format_aggregate(char *dst, size_t room, const run_batch_t *b, int i);
 static int format_stats_variant(char *dst, size_t room, const run_batch_t *b, int i);
 
-static int format_record(char *dst, size_t room, int kind /* CHI_SQUARE, FISHER, 3 = tdt, 5 = aggregate, 6 = stats */, const run_batch_t *b, int i) {
-    if (kind == 5) return format_aggregate(dst, room, b, i);
-    if (kind == 6) return format_stats_variant(dst, room, b, i);
+static int format_record(char *dst, size_t room, const run_batch_t *b, int i) {
+    const run_tool_t tool = b->run->tool;
+    if (tool == RUN_AGGREGATE) return format_aggregate(dst, room, b, i);
+    if (tool == RUN_STATS) return format_stats_variant(dst, room, b, i);
     const int m = b->max_lines;
     const uint32_t *fo = b->field_off + 10 * (size_t)i;
     const char *l = b->text + b->line_off[i];
@@ -138,7 +134,7 @@ static int format_record(char *dst, size_t room, int kind /* CHI_SQUARE, FISHER,
     p = put_i64(p, atol(l + fo[1])); *p++ = '\t';
     p = PUT_STR(p, l + fo[2], li); *p++ = '\t';
     p = PUT_STR(p, l + fo[3], lr); *p++ = '\t';
-    if (kind == 3) {
+    if (tool == RUN_TDT) {
         const int t1 = b->ints[i], t2 = b->ints[m + i];
         p = PUT_STR(p, l + fo[4], la); *p++ = '\t';
         p = put_i64(p, t1); *p++ = '\t'; p = put_i64(p, t2); *p++ = '\t';
@@ -156,7 +152,7 @@ static int format_record(char *dst, size_t room, int kind /* CHI_SQUARE, FISHER,
     p = put_i64(p, A2); *p++ = '\t'; p = put_i64(p, U2); *p++ = '\t';
     p = PUT_F6(p, fa2); *p++ = '\t'; p = PUT_F6(p, fu2); *p++ = '\t';
     p = PUT_F6(p, b->dbl[i]); *p++ = '\t';                            /* odds ratio */
-    if (kind == CHI_SQUARE) { p = PUT_F6(p, b->dbl[m + i]); *p++ = '\t'; }
+    if (tool == RUN_CHISQ) { p = PUT_F6(p, b->dbl[m + i]); *p++ = '\t'; }
     p = PUT_F6(p, b->dbl[2 * m + i]);
     *p++ = '\n'; *p = 0;
     return (int)(p - dst);
@@ -166,21 +162,22 @@ static int format_record(char *dst, size_t room, int kind /* CHI_SQUARE, FISHER,
  * rejected it (--maf / --missing / --mendel), or when it fails --alleles (1 + number of ALT alleles, "." = none) or
  * --quality (QUAL >= minimum; a missing QUAL fails) */
 int record_passes(const run_batch_t *b, int i) {
+    const hpgv_run_filters_t *F = &b->run->filters;
     const uint32_t *fo = b->field_off + 10 * (size_t)i;
     if (fo[5] == 0xFFFFFFFFu) return 0;
     if (b->status[i] & HPGV_LINE_FILTERED) return 0;
     const char *l = b->text + b->line_off[i];
-    if (g_filters.num_alleles >= 0) {
+    if (F->num_alleles >= 0) {
         const char *alt = l + fo[4];
         const int la = (int)(fo[5] - 1 - fo[4]);
         int n = (la <= 0 || (la == 1 && alt[0] == '.')) ? 1 : 2;
         for (int k = 0; k < la; k++) if (alt[k] == ',') n++;
-        if (n != g_filters.num_alleles) return 0;
+        if (n != F->num_alleles) return 0;
     }
-    if (g_filters.min_quality >= 0.0) {
+    if (F->min_quality >= 0.0) {
         if (fo[6] == 0xFFFFFFFFu) return 0;
         const char *q = l + fo[5];
-        if (*q == '.' || *q == '\t' || strtod(q, NULL) < g_filters.min_quality) return 0;
+        if (*q == '.' || *q == '\t' || strtod(q, NULL) < F->min_quality) return 0;
     }
     return 1;
 }
@@ -235,8 +232,6 @@ static int append_gtc(char *dst, size_t room, size_t o0, const vcounts_t *v) {
     return (int)(o - o0);
 }
 
-int g_aggregate_overwrite = 0;
-
 /* one line of the aggregated VCF (aggregate_runner.c:176-199): the record without its samples, INFO = the original
  * fields (AC / AF / AN dropped when overwriting) followed by [HPG_]AC, [HPG_]AF, [HPG_]AN and HPG_GTC
  * (merge_info_and_stats, :262-365; the reference emits the fields in the order of a hash table) */
@@ -245,6 +240,7 @@ static int format_aggregate(char *dst, size_t room, const run_batch_t *b, int i)
     const char *l = b->text + b->line_off[i];
     const char *eol = b->text + b->line_off[i + 1];
     while (eol > l && (eol[-1] == '\n' || eol[-1] == '\r')) eol--;
+    const int overwrite = b->run->overwrite;
     size_t o = 0;
     vcounts_t v;
     record_counts(b, i, l + fo[4], (int)(fo[5] - 1 - fo[4]), &v);
@@ -263,12 +259,12 @@ static int format_aggregate(char *dst, size_t room, const run_batch_t *b, int i)
             const char *e = (const char *)memchr(p, ';', (size_t)(ine - p));
             if (!e) e = ine;
             const int klen = (int)((const char *)memchr(p, '=', (size_t)(e - p)) ? (const char *)memchr(p, '=', (size_t)(e - p)) - p : e - p);
-            const int drop = g_aggregate_overwrite && klen == 2 && (!strncmp(p, "AC", 2) || !strncmp(p, "AF", 2) || !strncmp(p, "AN", 2));
+            const int drop = overwrite && klen == 2 && (!strncmp(p, "AC", 2) || !strncmp(p, "AF", 2) || !strncmp(p, "AN", 2));
             if (!drop && e > p) APPEND("%.*s;", (int)(e - p), p);
             p = e + 1;
         }
     }
-    const char *pre = g_aggregate_overwrite ? "" : "HPG_";
+    const char *pre = overwrite ? "" : "HPG_";
     int ta = 0;
     for (int k = 0; k < v.na; k++) ta += v.ac[k];
     APPEND("%sAC=", pre);
@@ -312,7 +308,7 @@ static int format_stats_variant(char *dst, size_t room, const run_batch_t *b, in
 
 /* formats the records of a batch by a thread team (one contiguous range of lines and one growing buffer per
  * task), then writes the buffers in line order */
-typedef struct { const run_batch_t *b; out_buf_t *bufs; int kind, n, parts, bad; } fmt_job_t;
+typedef struct { const run_batch_t *b; out_buf_t *bufs; int n, parts, bad; } fmt_job_t;
 
 /* Is the result file in `sort -k1,1h -k2,2n` order as it is written?  (It is for a position-sorted VCF, and reading two
  * million lines back to find that out took 0.09 of a 0.21 s run.)  Neighbouring records with the same CHROM bytes and a
@@ -338,6 +334,7 @@ static void fmt_task(void *v, int t) {
     fmt_job_t *j = (fmt_job_t *)v;
     const run_batch_t *b = j->b;
     out_buf_t *o = &j->bufs[t];
+    const int track = tool_sorts(b->run->tool) && b->field_off;      /* results that are sorted afterwards: in order so far? */
     o->len = 0;
     o->disorder = 0;
     const int lo = (int)((long)j->n * t / j->parts), hi = (int)((long)j->n * (t + 1) / j->parts);
@@ -345,9 +342,9 @@ static void fmt_task(void *v, int t) {
     for (int i = lo; i < hi; i++) {
         if (!record_passes(b, i)) continue;
         for (;;) {
-            int need = o->cap > o->len ? format_record(o->p + o->len, o->cap - o->len, j->kind, b, i) : -2;
+            int need = o->cap > o->len ? format_record(o->p + o->len, o->cap - o->len, b, i) : -2;
             if (need >= 0 && (size_t)need < o->cap - o->len) {
-                if (j->kind < 4 && b->field_off) {                  /* results that are sorted afterwards: in order so far? */
+                if (track) {
                     const uint32_t *fo = b->field_off + 10 * (size_t)i;
                     const char *l = b->text + b->line_off[i];
                     const char *c = l + fo[0]; const size_t clen = fo[1] - 1 - fo[0];
@@ -428,8 +425,8 @@ int file_writer_stop(file_writer_t *w) {          /* everything handed over is w
 }
 
 /* fw (may be NULL: written here) takes the formatted set; the caller alternates between two sets of n_bufs buffers */
-int write_batch(FILE *fd, int kind, const run_batch_t *b, out_buf_t *bufs, int n_bufs, io_pool_t *pool, order_track_t *ord, file_writer_t *fw) {
-    if (kind == 4) {                                     /* vcf2epi: the rows of the records, in line order (dataset_creator.c:196-199) */
+int write_batch(FILE *fd, const run_batch_t *b, out_buf_t *bufs, int n_bufs, io_pool_t *pool, order_track_t *ord, file_writer_t *fw) {
+    if (b->run->tool == RUN_VCF2EPI) {                   /* vcf2epi: the rows of the records, in line order (dataset_creator.c:196-199) */
         const int n = b->n_lines < b->max_lines ? b->n_lines : b->max_lines;
         const size_t w = (size_t)b->row_width;
         int i = 0;
@@ -443,7 +440,7 @@ int write_batch(FILE *fd, int kind, const run_batch_t *b, out_buf_t *bufs, int n
         return 0;
     }
     fmt_job_t j;
-    j.b = b; j.bufs = bufs; j.kind = kind; j.bad = 0;
+    j.b = b; j.bufs = bufs; j.bad = 0;
     j.n = b->n_lines < b->max_lines ? b->n_lines : b->max_lines;
     j.parts = j.n >= 2048 ? n_bufs : 1;
     const double t_f0 = now_s();
@@ -453,7 +450,7 @@ int write_batch(FILE *fd, int kind, const run_batch_t *b, out_buf_t *bufs, int n
     const double t_w0 = now_s();
     for (int t = 0; t < j.parts; t++) {
         if (!bufs[t].len) continue;
-        if (ord && kind < 4) {                                       /* the seam before this task's lines, and its own verdict */
+        if (ord && tool_sorts(b->run->tool)) {                       /* the seam before this task's lines, and its own verdict */
             const char *first_end = (const char *)memchr(bufs[t].p, '\n', bufs[t].len);
             const char *lastl = (const char *)memrchr(bufs[t].p, '\n', bufs[t].len - 1);
             lastl = lastl ? lastl + 1 : bufs[t].p;

@@ -16,7 +16,8 @@
  *   host_bgzf.c        bgzip files staged and decoded on the device(s)
  *   host_reader.c      whole-line batches, the VCF header
  *   host_format.c      result lines of a batch, the writer thread
- *   host_runner.c      the file runners' pipeline (hpgv_run_*)
+ *   host_vcftools.c    the VCF tools' batch steps and writers: filter partition, split keys and files
+ *   host_runner.c      the file runners' pipeline and their runs (hpgv_run_*), the stats report
  */
 #ifndef HPGV_HOST_INTERNAL_H
 #define HPGV_HOST_INTERNAL_H
@@ -132,7 +133,13 @@ typedef struct {
     char *chrom_line; size_t chrom_len;                 /* the #CHROM line as written (vcf_header_read), or NULL */
 } line_reader_t;
 
+/* the file runners' tools.  The first two are the assoc tasks, as hpgv_assoc_text takes them */
+typedef enum { RUN_CHISQ = CHI_SQUARE, RUN_FISHER = FISHER, RUN_TDT, RUN_VCF2EPI, RUN_AGGREGATE, RUN_STATS, RUN_FILTER, RUN_SPLIT } run_tool_t;
+static inline int tool_sorts(run_tool_t t) { return t == RUN_CHISQ || t == RUN_FISHER || t == RUN_TDT; }   /* output sorted afterwards */
+static inline int tool_counts(run_tool_t t) { return t == RUN_AGGREGATE || t == RUN_STATS; }   /* engine: hpgv_stats_text_groups */
+
 typedef struct {
+    struct run *run;                                     /* the run the batch belongs to */
     char *text; size_t text_cap;                         /* page-locked, taken from the cache when the batch is first filled */
     const char *dev_text;                                /* the same bytes on the device (BGZF decoded there), or NULL */
     hpgv_ctx *dev_ctx;                                   /* the member context of that device (a file staged in parts), or NULL */
@@ -170,6 +177,34 @@ typedef struct {
 } file_writer_t;
 
 typedef struct { const char *line; int neg1, order1; long double v1; int neg2; long double v2; } sort_key_t;
+
+/* hpg-var-vcf stats: what the run accumulates besides the per-variant lines (sample_stats_t, file_stats_t) */
+typedef struct {
+    long *smiss, *serr;                                   /* per VCF column: missing genotypes, Mendelian errors as a child */
+    long variants, biallelic, multiallelic, snps, indels, transitions, transversions, pass, with_quality;
+    double quality_sum;
+} run_stats_t;
+
+/* hpg-var-vcf split: the output files, by lower-cased split name (host_vcftools.c) */
+enum { SPLIT_OPEN_MAX = 64 };
+typedef struct { char *name, *path; FILE *fd; long last; int created; } split_file_t;
+typedef struct { split_file_t *f; int n, cap; sample_ids_t *ids; char *key; size_t key_cap; int open[SPLIT_OPEN_MAX], n_open; long clock; } split_files_t;
+
+/* one file run: built by its public entry (hpgv_run_*), its stages and the pipeline's threads (through the batches) share it */
+typedef struct run {
+    run_tool_t tool;
+    hpgv_run_filters_t filters;                          /* the record filters as the run started (stats, split: all off) */
+    int overwrite, save_rejected;                        /* aggregate: AC / AF / AN replaced; filter: the others to .rejected */
+    int criterion, n_iv; const long *iv; const char *dir; char base[512];  /* split: HPGV_SPLIT_*, coverage bounds, <dir>/<name>_<base> */
+    long written, rejected;                              /* records written; filter: records written to (or meant for) .rejected */
+    long files, skipped, key_ns;                         /* split: files created, lines to no file, host time of split_keys */
+    line_reader_t rd; char *hdr, **names; size_t chrom_off; int n_samples, io_threads, n_engines; ped_table_t ped;
+    int n_trios, n_groups; int32_t *trio_child; char **group_names;     /* stats: trios' child columns, phenotypes (PED text) */
+    uint32_t epi_aff, epi_unaff;                         /* vcf2epi: the class sizes */
+    char *path, *path_rej; FILE *out, *out_rej, **gfd;   /* gfd: stats, one file per phenotype */
+    split_files_t SF; run_stats_t *RS; order_track_t ord;
+    double t_opened, t_header, t_sort;
+} run_t;
 
 enum { RUN_ENGINES_MAX = 16, RUN_NB_MAX = RUN_ENGINES_MAX + 3, RUN_FMT_BUFS = 64 };
 
@@ -279,7 +314,7 @@ size_t read_lines_dev(line_reader_t *r, char *buf, size_t bufcap, size_t cap);
 size_t read_lines(line_reader_t *r, char *buf, size_t cap);
 int vcf_header_read(line_reader_t *rd, char **hdr_out, char ***names_out, size_t *chrom_off);
 /* host_format.c */
-int run_batch_alloc(run_batch_t *b, size_t cap_bytes, int n_samples, int row_width, int stats, int n_trios, int n_groups);
+int run_batch_alloc(run_batch_t *b, run_t *run, size_t cap_bytes, int n_samples, int n_trios, int n_groups);
 int run_batch_reserve(run_batch_t *b, int lines);
 void run_batch_free(run_batch_t *b);
 int record_passes(const run_batch_t *b, int i);
@@ -287,15 +322,20 @@ void record_counts(const run_batch_t *b, int i, const char *alt, int la, vcounts
 void order_track_keep(order_track_t *o, const char *line, size_t len);
 int file_writer_start(file_writer_t *w, FILE *fd);
 int file_writer_stop(file_writer_t *w);
-int write_batch(FILE *fd, int kind, const run_batch_t *b, out_buf_t *bufs, int n_bufs, io_pool_t *pool, order_track_t *ord, file_writer_t *fw);
+int write_batch(FILE *fd, const run_batch_t *b, out_buf_t *bufs, int n_bufs, io_pool_t *pool, order_track_t *ord, file_writer_t *fw);
+/* host_vcftools.c */
+int filter_partition(run_batch_t *b);
+int split_partition(run_batch_t *b);
+int write_filter_header(FILE *f, const run_t *R);
+int write_filter_batch(FILE *kept, FILE *rejected, const run_batch_t *b);
+int write_split_batch(run_t *R, const run_batch_t *b);
+int split_files_close(split_files_t *S);
 
 extern pthread_rwlock_t g_cohort_lock;   /* host_engine.c */
 extern char g_err[512];   /* host_engine.c */
 extern hpgv_run_filters_t g_filters;   /* host_source.c */
 extern double g_run_times[6];   /* host_source.c */
 extern char g_input_err[192];   /* host_bgzf.c */
-extern int g_aggregate_overwrite;   /* host_format.c */
-extern int g_filter_save_rejected;   /* host_runner.c */
 extern double g_write_split[2];   /* host_format.c */
 
 #pragma GCC visibility pop
