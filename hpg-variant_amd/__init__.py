@@ -50,6 +50,7 @@ SYMBOLS = [
     "hpgv_group_comm_init", "hpgv_group_comm_ranks", "hpgv_group_rccl_probe", "hpgv_group_shard", "hpgv_group_assoc", "hpgv_group_tdt", "hpgv_group_stats", "hpgv_group_sync", "hpgv_group_epi_share", "hpgv_group_epi_rank", "hpgv_epi_rank_triples_rows", "hpgv_text_alias_tiles", "hpgv_text_tiles_bytes", "hpgv_bgzf_verify_tiles_dev", "hpgv_memset_dev",
     "hpgv_epi_last_rank_info", "hpgv_filter_text", "hpgv_text_partition", "hpgv_lines_partition_scratch_bytes", "hpgv_lines_partition_dev",
     "hpgv_text_multisplit", "hpgv_lines_multisplit_scratch_bytes", "hpgv_lines_multisplit_dev",
+    "hpgv_inheritance_scan_dev", "hpgv_set_text_inheritance_filters",
 ]
 
 
@@ -159,6 +160,8 @@ def load():
     L.hpgv_stats_text.argtypes = [vp, C.c_char_p, sz, i32, C.POINTER(i32), vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i32), vp, vp]
     L.hpgv_stats_text_groups.argtypes = [vp, C.c_char_p, sz, i32, C.POINTER(i32), vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i32), vp, vp, vp, vp, vp]
     L.hpgv_set_text_filters.argtypes = [vp, C.c_double, C.c_double, C.c_long]
+    L.hpgv_set_text_inheritance_filters.argtypes = [vp, C.c_double, C.c_double]
+    L.hpgv_inheritance_scan_dev.argtypes = [vp, vp, i32, vp, vp]
     L.hpgv_epi_dataset_text.argtypes = [vp, C.c_char_p, sz, i32, C.POINTER(i32), vp, vp, vp, vp]
     L.hpgv_epi_set_dataset.argtypes = [vp, vp, i32, i32, i32]
     L.hpgv_epi_set_folds.argtypes = [vp, vp, i32]
@@ -300,6 +303,10 @@ class Engine:
         p = C.c_size_t()
         self._chk(self.L.hpgv_mendel_layout(self.h, C.byref(p)))
         return p.value
+
+    def set_text_inheritance_filters(self, min_dominant=-1.0, min_recessive=-1.0):
+        """--inh-dom / --inh-rec of the *_text entry points (negative: off)"""
+        self._chk(self.L.hpgv_set_text_inheritance_filters(self.h, min_dominant, min_recessive))
 
     def mendel_scan(self, d_gt, n_variants, d_errors, d_is_x=None, stream=None):
         self._chk(self.L.hpgv_mendel_scan_dev(self.h, d_gt, n_variants, d_is_x, d_errors, stream))
@@ -641,6 +648,9 @@ class Engine:
 
     def stats_filter(self, d_counts8, n_variants, d_keep, min_maf=-1.0, max_maf=-1.0, max_missing=-1.0, stream=None):
         self._chk(self.L.hpgv_stats_filter_dev(self.h, d_counts8, n_variants, min_maf, max_maf, max_missing, d_keep, stream))
+
+    def inheritance_scan(self, d_gt, n_variants, d_counts8, stream=None):
+        self._chk(self.L.hpgv_inheritance_scan_dev(self.h, d_gt, n_variants, d_counts8, stream))
 
     def last_kernel_ms(self):
         a, b = C.c_float(), C.c_float()

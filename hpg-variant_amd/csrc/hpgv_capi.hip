@@ -9,6 +9,7 @@
 #include "hpgv_text2_kernels.h"
 #include "hpgv_partition_kernels.h"
 #include "hpgv_batch_kernels.h"
+#include "hpgv_inherit_kernels.h"
 
 namespace {
 
@@ -1348,6 +1349,29 @@ int hpgv_stats_filter_dev(hpgv_ctx *ctx, const int32_t *d_counts8, int n_variant
     return HPGV_OK;
 }
 
+int hpgv_inheritance_scan_dev(hpgv_ctx *ctx, const uint8_t *d_gt, int n_variants, int32_t *d_counts8, void *stream) {
+    ctx = first_member(ctx);
+    if (!ctx) return HPGV_ERR_INVALID;
+    if (!ctx->assoc.set) return fail(ctx, HPGV_ERR_STATE, "hpgv_set_cohort has not been called");
+    if (n_variants < 0 || (n_variants > 0 && (!d_gt || !d_counts8))) return fail(ctx, HPGV_ERR_INVALID, "bad scan arguments");
+    if (n_variants == 0) return HPGV_OK;
+    if (((uintptr_t)d_gt & 15) || ((uintptr_t)d_counts8 & 15)) return fail(ctx, HPGV_ERR_INVALID, "device buffers must be 16-byte aligned");
+    DeviceGuard g(ctx->device);
+    const Layout &L = ctx->assoc;
+    const int vpw = (int)ctx->vpw;
+    const long waves = ((long)n_variants + vpw - 1) / vpw;
+    const unsigned blocks = (unsigned)((waves + 3) / 4);
+    hipStream_t st = (hipStream_t)stream;
+    return launch_profiled(ctx, st, 0, [&] {
+        if (ctx->nontemporal)
+            hipLaunchKernelGGL((hpgv::k_inherit_scan<true, 4>), dim3(blocks), dim3(256), 0, st, d_gt, L.pitch, n_variants, ctx->chunksA,
+                               L.chunks, (int4 *)d_counts8, vpw);
+        else
+            hipLaunchKernelGGL((hpgv::k_inherit_scan<false, 4>), dim3(blocks), dim3(256), 0, st, d_gt, L.pitch, n_variants, ctx->chunksA,
+                               L.chunks, (int4 *)d_counts8, vpw);
+    });
+}
+
 int hpgv_sample_missing_dev(hpgv_ctx *ctx, const uint8_t *d_gt, int n_variants, int32_t *d_missing, void *stream) {
     ctx = first_member(ctx);
     if (!ctx) return HPGV_ERR_INVALID;
@@ -2043,12 +2067,30 @@ static int text_front(hpgv_ctx *ctx, Slot *s, int which, const Layout &L, const 
         if (line_off) HIPCHK(ctx, hipMemcpyAsync(line_off, d_head_off, ((size_t)nl + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream));
     } else if (line_off) HIPCHK(ctx, hipMemcpyAsync(line_off, meta + off_lines, ((size_t)nl + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream));
     if (field_off) HIPCHK(ctx, hipMemcpyAsync(field_off, meta + off_fields, (size_t)nl * 10 * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
-    // ---- record filters (--maf, --missing, --mendel: shared_options.c:44-46,101-115), from the same matrix ----
+    // ---- record filters (--maf, --missing, --mendel, --inh-dom, --inh-rec: shared_options.c:44-56,101-173), from the same matrix ----
     const bool f_counts = ctx->filt_min_maf >= 0.0 || ctx->filt_max_missing >= 0.0, f_mendel = ctx->filt_max_mendel >= 0;
-    if (status && (f_counts || f_mendel)) {
+    const bool f_inh = ctx->filt_min_dom >= 0.0 || ctx->filt_min_rec >= 0.0;
+    if (status && (f_counts || f_mendel || f_inh)) {
         const size_t n = (size_t)nl;
-        std::vector<uint8_t> keep;
+        std::vector<uint8_t> keep, ikeep;
         std::vector<int32_t> merr;
+        if (f_inh) {
+            // the assoc layout of the raw matrix, its inheritance counts and verdicts (buf[3] behind the count filters' n * 33 bytes)
+            if (!ctx->assoc.set || ctx->assoc.n_samples != L.n_samples)
+                return fail(ctx, HPGV_ERR_STATE, "the inheritance filters need hpgv_set_cohort over %d columns", L.n_samples);
+            const size_t off8 = round_up(n * 33 + 64, 256);
+            if ((rc = ensure(ctx, s, 1, n * std::max(ctx->assoc.pitch, L.pitch) + 16))) return rc;
+            if ((rc = ensure(ctx, s, 3, off8 + n * 33 + 64))) return rc;
+            int32_t *d_c8 = (int32_t *)((char *)s->buf[3] + off8);
+            uint8_t *d_ikeep = (uint8_t *)d_c8 + n * 32;
+            if ((rc = hpgv_layout_dev(ctx, HPGV_LAYOUT_ASSOC, (const uint8_t *)s->buf[7], raw_pitch, nl, (uint8_t *)s->buf[1], s->stream))) return rc;
+            if ((rc = hpgv_inheritance_scan_dev(ctx, (const uint8_t *)s->buf[1], nl, d_c8, s->stream))) return rc;
+            hipLaunchKernelGGL(hpgv::k_inherit_filter, dim3((nl + 255) / 256), dim3(256), 0, s->stream, (const int4 *)d_c8, nl,
+                               ctx->filt_min_dom, ctx->filt_min_rec, d_ikeep);
+            HIPCHK(ctx, hipGetLastError());
+            ikeep.resize(n);
+            HIPCHK(ctx, hipMemcpyAsync(ikeep.data(), d_ikeep, n, hipMemcpyDeviceToHost, s->stream));
+        }
         if (f_counts) {
             if (!ctx->stats.set || ctx->stats.n_samples != L.n_samples)
                 return fail(ctx, HPGV_ERR_STATE, "the count filters need hpgv_set_stats_cohort(%d)", L.n_samples);
@@ -2073,7 +2115,7 @@ static int text_front(hpgv_ctx *ctx, Slot *s, int which, const Layout &L, const 
         }
         HIPCHK(ctx, hipStreamSynchronize(s->stream));
         for (size_t i = 0; i < n; ++i) {
-            const bool out = (f_counts && !keep[i]) || (f_mendel && (long)merr[i] > ctx->filt_max_mendel);
+            const bool out = (f_counts && !keep[i]) || (f_mendel && (long)merr[i] > ctx->filt_max_mendel) || (f_inh && !ikeep[i]);
             if (out) status[i] |= HPGV_LINE_FILTERED;
         }
     }
@@ -2086,6 +2128,15 @@ int hpgv_set_text_filters(hpgv_ctx *ctx, double min_maf, double max_missing, lon
     if (!ctx) return HPGV_ERR_INVALID;
     if (min_maf > 0.5 || max_missing > 1.0) return fail(ctx, HPGV_ERR_INVALID, "min_maf is at most 0.5, max_missing at most 1");
     ctx->filt_min_maf = min_maf; ctx->filt_max_missing = max_missing; ctx->filt_max_mendel = max_mendel_errors;
+    return HPGV_OK;
+}
+
+int hpgv_set_text_inheritance_filters(hpgv_ctx *ctx, double min_dominant, double min_recessive) {
+    GROUP_ALL(ctx, hpgv_set_text_inheritance_filters(m_, min_dominant, min_recessive))
+    if (!ctx) return HPGV_ERR_INVALID;
+    if (!(min_dominant <= 1.0) || !(min_recessive <= 1.0)) return fail(ctx, HPGV_ERR_INVALID, "the inheritance thresholds are at most 1");
+    ctx->filt_min_dom = min_dominant < 0.0 ? -1.0 : min_dominant;
+    ctx->filt_min_rec = min_recessive < 0.0 ? -1.0 : min_recessive;
     return HPGV_OK;
 }
 

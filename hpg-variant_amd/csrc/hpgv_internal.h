@@ -182,6 +182,7 @@ struct hpgv_ctx {
     // record filters of the text entry points (hpgv_set_text_filters); negative = off
     double filt_min_maf = -1.0, filt_max_missing = -1.0;
     long filt_max_mendel = -1;
+    double filt_min_dom = -1.0, filt_min_rec = -1.0;   // hpgv_set_text_inheritance_filters
     // epistasis (calls are serialised by epi_mu)
     std::mutex epi_mu;
     EpiState epi;

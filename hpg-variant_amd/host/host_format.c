@@ -159,8 +159,8 @@ static int format_record(char *dst, size_t room, const run_batch_t *b, int i) {
 }
 
 /* does line i of the batch give an output record?  Not when it has fewer than CHROM..ALT, when a device-side filter
- * rejected it (--maf / --missing / --mendel), or when it fails --alleles (1 + number of ALT alleles, "." = none) or
- * --quality (QUAL >= minimum; a missing QUAL fails) */
+ * rejected it (--maf / --missing / --mendel / --inh-dom / --inh-rec), when it fails --alleles (1 + number of ALT alleles,
+ * "." = none) or --quality (QUAL >= minimum; a missing QUAL fails), or a field filter of hpgv_run_set_record_filters */
 int record_passes(const run_batch_t *b, int i) {
     const hpgv_run_filters_t *F = &b->run->filters;
     const uint32_t *fo = b->field_off + 10 * (size_t)i;
@@ -179,7 +179,7 @@ int record_passes(const run_batch_t *b, int i) {
         const char *q = l + fo[5];
         if (*q == '.' || *q == '\t' || strtod(q, NULL) < F->min_quality) return 0;
     }
-    return 1;
+    return !b->run->rf || rec_filters_pass(b->run->rf, b, i);       /* the filters of hpgv_run_set_record_filters */
 }
 
 /* ---- aggregate / stats: the counters of one record as variant_stats_t holds them (get_variants_stats above) ---- */

@@ -276,6 +276,21 @@ static int run_cohort(run_t *R, const char *vcf_path, const char *ped_path) {
     }
     if (!rc && f->max_mendel_errors >= 0) rc = set_trios(R, ids, 0);
     if (!rc) (void)hpgv_set_text_filters(g_ctx, f->min_maf, f->max_missing, (long)f->max_mendel_errors);
+    /* --inh-dom / --inh-rec scan the assoc layout: the tools that have not installed it get it from the PED (PHENO 2
+     * affected, 1 unaffected, as the assoc runner); vcf2epi keeps its own classes */
+    if (!rc && rec_filters_inheritance(R->rf)) {
+        if (R->tool != RUN_CHISQ && R->tool != RUN_FISHER && R->tool != RUN_VCF2EPI) {
+            uint8_t *cond = (uint8_t *)malloc((size_t)n_samples + 1);
+            if (!cond) rc = HPGV_ERR_NOMEM;
+            for (int j = 0; cond && j < n_samples; j++) cond[j] = HPGV_COND_OTHER;
+            for (int i = 0; cond && i < ped->n; i++) { const int j = sample_ids_get(ids, ped->iid[i]); if (j >= 0) cond[j] = (uint8_t)ped->pheno[i]; }
+            if (!rc && (rc = hpgv_set_cohort(g_ctx, cond, n_samples))) host_fail("hpgv_set_cohort", rc);
+            g_assoc_key.set = 0;
+            free(cond);
+        }
+        const hpgv_run_record_filters_t *rf = rec_filters_of(R->rf);
+        if (!rc && (rc = hpgv_set_text_inheritance_filters(g_ctx, rf->min_dominant, rf->min_recessive))) host_fail("hpgv_set_text_inheritance_filters", rc);
+    }
     sample_ids_free(ids);
     return rc;
 }
@@ -565,10 +580,25 @@ static int run_finish(run_t *R, int rc, const char *out_path) {
     free(R->ord.last); free(R->gfd); free(R->group_names); free(R->path); free(R->path_rej); free(R->trio_child);
     const hpgv_run_filters_t *f = &R->filters;
     if (f->min_maf >= 0.0 || f->max_missing >= 0.0 || f->max_mendel_errors >= 0) (void)hpgv_set_text_filters(g_ctx, -1.0, -1.0, -1);
+    if (rec_filters_inheritance(R->rf) && g_ctx) (void)hpgv_set_text_inheritance_filters(g_ctx, -1.0, -1.0);
     return rc;
 }
 
+static int run_file_held(run_t *R, const char *vcf_path, const char *ped_path, const char *out_path, size_t batch_bytes, long *n_variants_out);
+/* the run holds the record filters of hpgv_run_set_record_filters as they are when it starts (stats and split: none) */
 static int run_file(run_t *R, const char *vcf_path, const char *ped_path, const char *out_path, size_t batch_bytes, long *n_variants_out) {
+    R->rf = R->tool == RUN_STATS || R->tool == RUN_SPLIT ? NULL : rec_filters_take();
+    int rc = HPGV_OK;
+    if (rec_filters_inheritance(R->rf) && !ped_path) {                /* filter_options_parsing.c:149-153 */
+        snprintf(g_err, sizeof g_err, "the inheritance filters (--inh-dom / --inh-rec) need a PED file (ped_path is NULL)");
+        rc = HPGV_ERR_INVALID;
+    } else rc = run_file_held(R, vcf_path, ped_path, out_path, batch_bytes, n_variants_out);
+    rec_filters_put(R->rf);
+    R->rf = NULL;
+    return rc;
+}
+
+static int run_file_held(run_t *R, const char *vcf_path, const char *ped_path, const char *out_path, size_t batch_bytes, long *n_variants_out) {
     host_env_read();                                               /* the environment: once per run (hpgv_host.h "Environment") */
     const double t_enter = now_s();
     g_write_split[0] = g_write_split[1] = 0;
@@ -680,8 +710,11 @@ int hpgv_run_filter(const char *vcf_path, const char *ped_path, const char *out_
     run_t R = { .tool = RUN_FILTER, .filters = g_filters, .save_rejected = save_rejected ? 1 : 0 };
     const hpgv_run_filters_t *F = &R.filters;
     if (!vcf_path || !out_prefix) { snprintf(g_err, sizeof g_err, "vcf_path and out_prefix must not be NULL"); return HPGV_ERR_INVALID; }
-    if (F->min_maf < 0.0 && F->max_missing < 0.0 && F->max_mendel_errors < 0 && F->num_alleles < 0 && F->min_quality < 0.0) {
-        snprintf(g_err, sizeof g_err, "no filter is set (hpgv_run_set_filters): the filter tool writes nothing without one"); return HPGV_ERR_INVALID;
+    rec_filters_t *rf = rec_filters_take();
+    const int any_rec = rf != NULL;                       /* (a setting without an active filter is stored as none) */
+    rec_filters_put(rf);
+    if (F->min_maf < 0.0 && F->max_missing < 0.0 && F->max_mendel_errors < 0 && F->num_alleles < 0 && F->min_quality < 0.0 && !any_rec) {
+        snprintf(g_err, sizeof g_err, "no filter is set (hpgv_run_set_filters, hpgv_run_set_record_filters): the filter tool writes nothing without one"); return HPGV_ERR_INVALID;
     }
     if (F->max_mendel_errors >= 0 && !ped_path) { snprintf(g_err, sizeof g_err, "the Mendelian error filter needs a PED file (ped_path is NULL)"); return HPGV_ERR_INVALID; }
     const int rc = run_file(&R, vcf_path, ped_path, out_prefix, batch_bytes, n_passed_out);

@@ -46,31 +46,6 @@ static int eq_icase(const char *a, size_t na, const char *b, size_t nb) {
     return 1;
 }
 
-/* INFO's DP as atoi reads it: the first ';'-separated entry whose key is exactly DP; optional sign, then digits up to the
- * first non-digit, none giving 0, saturated at the int64 range.  0 when there is no such entry or it is a bare flag. */
-static int info_dp(const char *info, size_t n, long long *v) {
-    size_t k = 0;
-    while (k <= n) {
-        size_t e = k;
-        while (e < n && info[e] != ';') e++;
-        if (e - k >= 2 && info[k] == 'D' && info[k + 1] == 'P' && (e - k == 2 || info[k + 2] == '=')) {
-            if (e - k == 2) return 0;                         /* a bare flag */
-            size_t q = k + 3;
-            int neg = 0;
-            if (q < e && (info[q] == '-' || info[q] == '+')) neg = info[q++] == '-';
-            unsigned long long m = 0, lim = neg ? (unsigned long long)LLONG_MAX + 1ull : (unsigned long long)LLONG_MAX;
-            for (; q < e && info[q] >= '0' && info[q] <= '9'; q++) {
-                const unsigned d = (unsigned)(info[q] - '0');
-                m = m > (lim - d) / 10 ? lim : m * 10 + d;
-            }
-            *v = neg ? (m == (unsigned long long)LLONG_MAX + 1ull ? LLONG_MIN : -(long long)m) : (long long)m;
-            return 1;
-        }
-        k = e + 1;
-    }
-    return 0;
-}
-
 /* the split name of coverage bucket j (0 .. n_iv: the intervals, n_iv + 1: no DP) */
 static int coverage_name(char *out, size_t cap, const run_t *R, int j) {
     const long *iv = R->iv; const int n = R->n_iv;
@@ -149,10 +124,9 @@ static int split_keys(run_batch_t *b) {
                 }
             }
         } else {
-            size_t ie = fo[8] != 0xFFFFFFFFu ? (size_t)fo[8] - 1 : (size_t)(b->line_off[i + 1] - b->line_off[i]);
-            if (fo[8] == 0xFFFFFFFFu && ie > fo[7] && l[ie - 1] == '\n') ie--;
+            const char *info; size_t ni;
             long long v = 0;
-            if (!info_dp(l + fo[7], ie - fo[7], &v)) j = R->n_iv + 1;
+            if (!record_info(b, i, &info, &ni) || !info_dp(info, ni, &v)) j = R->n_iv + 1;
             else {                                        /* the first bound >= v, or n_iv */
                 int lo = 0, hi = R->n_iv;
                 while (lo < hi) { const int mid = (lo + hi) >> 1; if (v > (long long)R->iv[mid]) lo = mid + 1; else hi = mid; }
@@ -239,6 +213,7 @@ int write_filter_header(FILE *f, const run_t *R) {
     if (F->max_mendel_errors >= 0) fprintf(f, "##FILTER=<ID=mendel,Description=\"Mendelian errors <= %g\">\n", (double)F->max_mendel_errors);
     if (F->num_alleles >= 0) fprintf(f, "##FILTER=<ID=alleles,Description=\"Number of alleles == %g\">\n", (double)F->num_alleles);
     if (F->min_quality >= 0.0) fprintf(f, "##FILTER=<ID=quality,Description=\"Quality >= %g\">\n", F->min_quality);
+    rec_filters_header(f, R->rf);
     return R->rd.chrom_len && fwrite(R->rd.chrom_line, 1, R->rd.chrom_len, f) != R->rd.chrom_len;
 }
 

@@ -17,6 +17,7 @@
  *   host_reader.c      whole-line batches, the VCF header
  *   host_format.c      result lines of a batch, the writer thread
  *   host_vcftools.c    the VCF tools' batch steps and writers: filter partition, split keys and files
+ *   host_records.c     the record filters of hpgv_run_set_record_filters: regions, coverage, variant types, inheritance
  *   host_runner.c      the file runners' pipeline and their runs (hpgv_run_*), the stats report
  */
 #ifndef HPGV_HOST_INTERNAL_H
@@ -190,10 +191,14 @@ enum { SPLIT_OPEN_MAX = 64 };
 typedef struct { char *name, *path; FILE *fd; long last; int created; } split_file_t;
 typedef struct { split_file_t *f; int n, cap; sample_ids_t *ids; char *key; size_t key_cap; int open[SPLIT_OPEN_MAX], n_open; long clock; } split_files_t;
 
+/* the parsed setting of hpgv_run_set_record_filters (host_records.c), shared by reference with the runs started under it */
+typedef struct rec_filters rec_filters_t;
+
 /* one file run: built by its public entry (hpgv_run_*), its stages and the pipeline's threads (through the batches) share it */
 typedef struct run {
     run_tool_t tool;
     hpgv_run_filters_t filters;                          /* the record filters as the run started (stats, split: all off) */
+    rec_filters_t *rf;                                   /* ... and those of hpgv_run_set_record_filters (NULL: all off), held by run_file */
     int overwrite, save_rejected;                        /* aggregate: AC / AF / AN replaced; filter: the others to .rejected */
     int criterion, n_iv; const long *iv; const char *dir; char base[512];  /* split: HPGV_SPLIT_*, coverage bounds, <dir>/<name>_<base> */
     long written, rejected;                              /* records written; filter: records written to (or meant for) .rejected */
@@ -330,6 +335,16 @@ int write_filter_header(FILE *f, const run_t *R);
 int write_filter_batch(FILE *kept, FILE *rejected, const run_batch_t *b);
 int write_split_batch(run_t *R, const run_batch_t *b);
 int split_files_close(split_files_t *S);
+
+/* host_records.c */
+int info_dp(const char *info, size_t n, long long *v);
+int record_info(const run_batch_t *b, int i, const char **info, size_t *n);
+rec_filters_t *rec_filters_take(void);                   /* the current setting, referenced (NULL: all off) */
+void rec_filters_put(rec_filters_t *r);
+const hpgv_run_record_filters_t *rec_filters_of(const rec_filters_t *r);
+int rec_filters_inheritance(const rec_filters_t *r);     /* --inh-dom or --inh-rec is set */
+int rec_filters_pass(const rec_filters_t *r, const run_batch_t *b, int i);
+void rec_filters_header(FILE *f, const rec_filters_t *r);
 
 extern pthread_rwlock_t g_cohort_lock;   /* host_engine.c */
 extern char g_err[512];   /* host_engine.c */

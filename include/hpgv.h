@@ -266,6 +266,16 @@ int  hpgv_stats_filter_dev(hpgv_ctx *ctx, const int32_t *d_counts8, int n_varian
                            double min_maf, double max_maf, double max_missing,
                            uint8_t *d_keep, void *stream);
 
+/* the counts behind the inheritance filters (--inh-dom / --inh-rec, shared_options.c:42-56): d_gt in the
+ * HPGV_LAYOUT_ASSOC layout -> per variant 8 x int32
+ *   {c0 affected calls counted, c1 affected calls with a non-reference allele (byte != 0x00), c2 affected calls with
+ *    both alleles non-reference, c3 unaffected calls counted, c4 unaffected calls 0/0 (byte == 0x00), c5 unaffected
+ *    calls with both alleles non-reference, 0, 0}
+ * A call is counted when neither allele nibble is 0xF (missing and half-missing genotypes are not); multi-allelic codes
+ * count by the same rules.  Exact for any class size the cohort takes.  Needs hpgv_set_cohort (else HPGV_ERR_STATE);
+ * d_gt and d_counts8 16-byte aligned.  Asynchronous on `stream`. */
+int  hpgv_inheritance_scan_dev(hpgv_ctx *ctx, const uint8_t *d_gt, int n_variants, int32_t *d_counts8, void *stream);
+
 /* ---- the variant-sharded resident scan of a GROUP context: what the runner's worker loop
  *      (assoc_runner.c:106-207, tdt_runner.c:150-200, stats_runner.c:176-215) becomes when the cohort lies in the HBM of
  *      the group's devices.  Variants are independent (assoc.c:38-82, tdt.c:41-271), so member g owns the contiguous
@@ -372,10 +382,22 @@ int  hpgv_stats_text_groups(hpgv_ctx *ctx, const char *text, size_t text_bytes, 
  * filters need hpgv_set_stats_cohort(n_samples), the Mendel filter hpgv_set_pedigree over the same columns. */
 #define HPGV_LINE_FILTERED 0x100
 int  hpgv_set_text_filters(hpgv_ctx *ctx, double min_maf, double max_missing, long max_mendel_errors);
+/* the inheritance filters of the same text entry points: --inh-dom (min_dominant) and --inh-rec (min_recessive),
+ * shared_options.c:42-56.  The filter bodies live in hpg-libs; the definitions here, on the counts c0 .. c5 of
+ * hpgv_inheritance_scan_dev:
+ *   dominant followers  = c1 + c4          (affected carriers, unaffected 0/0)
+ *   recessive followers = c2 + (c3 - c5)   (affected homozygous non-reference, unaffected not so)
+ *   fraction            = followers / (c0 + c3), computed in double
+ * A record is kept when every active fraction >= its threshold; a record with no counted call fails.  A negative value
+ * switches that filter off; a value above 1 is HPGV_ERR_INVALID.  A group context applies it to every member.  A batch
+ * with an inheritance filter set lays the raw matrix out as HPGV_LAYOUT_ASSOC and scans it: it needs hpgv_set_cohort
+ * over the same columns (else HPGV_ERR_STATE). */
+int  hpgv_set_text_inheritance_filters(hpgv_ctx *ctx, double min_dominant, double min_recessive);
 
 /* hpg-var-vcf filter (filter_runner.c:23-260): the record filters alone.  hpgv_filter_text tokenizes a batch of VCF text
  * as the other *_text calls do (line_off, field_off, status as there; the text on the device when hpgv_text_alias says so),
- * applies the device filters of hpgv_set_text_filters (HPGV_LINE_FILTERED in status) and runs no tool's scan.  The count
+ * applies the device filters of hpgv_set_text_filters and hpgv_set_text_inheritance_filters (HPGV_LINE_FILTERED in status)
+ * and runs no tool's scan.  The count
  * filters read the layout of hpgv_set_stats_cohort, which this call needs whatever the filters.  The call keeps the device
  * text it tokenized, and that text's line starts, for hpgv_text_partition on the same `text`: until that call, or the next
  * hpgv_filter_text on `text`, one of the context's stream slots stays with it.  When *n_lines > max_lines nothing is kept. */

@@ -307,11 +307,57 @@ typedef struct {
     double min_quality;
 } hpgv_run_filters_t;
 void hpgv_run_set_filters(const hpgv_run_filters_t *filters);
+/* the rest of the reference's record filters (shared_options.c:42-56,86-173; --gene needs the CellBase web service and
+ * is not here).  The filter bodies live in hpg-libs: these are the definitions used here.  Off as marked below.
+ *   min_coverage   --coverage      keep records whose INFO has DP >= min_coverage (DP read as the split runner reads it:
+ *                                  the first ';'-separated entry with the key DP; a record without DP, or with a bare DP
+ *                                  flag, fails)
+ *   regions        --region        keep records inside the regions: a comma-separated list of CHROM (the whole
+ *                                  sequence), CHROM:POS or CHROM:START-END (1-based, inclusive, START <= END; the last
+ *                                  ':' of an item separates CHROM, positions are decimal digits >= 1)
+ *   region_file    --region-file   keep records inside the regions of a GFF file: tab-separated rows, blank and '#'
+ *                                  lines skipped, column 1 the sequence, 3 the feature, 4 and 5 start and end (at least
+ *                                  5 columns, start <= end)
+ *   region_type    --region-type   with region_file: only the rows whose feature is exactly this (NULL: every row)
+ *   snp            --snp           1 include: keep records whose ID is not "."; 0 exclude: keep those whose ID is "."
+ *   var_type       --var-type      keep records of this type (HPGV_VAR_*):
+ *                                    structural: some ALT allele is symbolic (begins with '<') or a breakend (holds
+ *                                                '[' or ']');
+ *                                    snv:        REF is one base and every ALT allele one base (the stats tool's SNP);
+ *                                    indel:      not structural, and some ALT allele's length differs from REF's;
+ *                                  an MNP, or ALT ".", is none of the three
+ *   indel          --indel         1 include: keep what var_type HPGV_VAR_INDEL keeps; 0 exclude: keep every other record
+ *   min_dominant   --inh-dom       keep records whose fraction of samples following a dominant / recessive inheritance
+ *   min_recessive  --inh-rec       pattern is >= the threshold (definitions: hpgv.h hpgv_set_text_inheritance_filters;
+ *                                  counted on the GPU).  Affected = PED PHENO 2, unaffected = PHENO 1 (vcf2epi: its own
+ *                                  classes, every sample not affected being unaffected, dataset_creator.c:279-300);
+ *                                  they need a PED: a runner started without one (aggregate always) returns
+ *                                  HPGV_ERR_INVALID before the engine starts and writes no file
+ * Regions match CHROM byte for byte; they are kept sorted and merged per sequence and looked up by binary search.  With
+ * both regions and region_file set a record must fall in both.  A record whose POS is not a number (decimal digits)
+ * fails a region filter.  The filters apply together with those of hpgv_run_set_filters in the assoc, tdt, aggregate,
+ * filter and vcf2epi runners (stats and split ignore them).  The setter copies the strings and reads / parses the regions
+ * when it is called; a malformed item or row, a file that cannot be read, a threshold above 1 or a value out of range
+ * returns HPGV_ERR_INVALID (message in hpgv_host_last_error) and the previous setting stays in force.  NULL switches all
+ * off.  The setting applies to the runs started afterwards on this process. */
+enum { HPGV_VAR_SNV = 1, HPGV_VAR_INDEL = 2, HPGV_VAR_STRUCTURAL = 3 };
+typedef struct {
+    long min_coverage;                 /* --coverage     < 0 off */
+    const char *regions;               /* --region       NULL off */
+    const char *region_file;           /* --region-file  NULL off (GFF) */
+    const char *region_type;           /* --region-type  NULL: every feature */
+    int snp;                           /* --snp          -1 off, 0 exclude, 1 include */
+    int var_type;                      /* --var-type     -1 off, HPGV_VAR_* */
+    int indel;                         /* --indel        -1 off, 0 exclude, 1 include */
+    double min_dominant, min_recessive;/* --inh-dom / --inh-rec  < 0 off, <= 1 */
+} hpgv_run_record_filters_t;
+int hpgv_run_set_record_filters(const hpgv_run_record_filters_t *f);
 
 /* run_filter (src/vcf-tools/filter/filter_runner.c:23-260, hpg-var-vcf filter): the records that pass the filters of
  * hpgv_run_set_filters to <out_prefix>.filtered, the others to <out_prefix>.rejected when save_rejected != 0 (--save-rejected,
- * main_filter.c:85; without it .rejected is created empty, filter_runner.c:63-68).  Without any filter set, or with NULL paths,
- * or with --mendel and no PED, it returns HPGV_ERR_INVALID before the engine starts and writes no file (the reference writes
+ * main_filter.c:85; without it .rejected is created empty, filter_runner.c:63-68) -- with those of hpgv_run_set_record_filters
+ * too.  Without any filter set (of either setter), or with NULL paths, or with --mendel, --inh-dom or --inh-rec and no PED,
+ * it returns HPGV_ERR_INVALID before the engine starts and writes no file (the reference writes
  * nothing without a filter chain, hpg_variant_utils.c:220-226).  ped_path may be NULL; the count filters use every VCF column
  * (as hpgv_run_stats does), the Mendelian one the PED's trios whose three members are VCF columns.
  * Each file: the input header verbatim up to its #CHROM line, then one line per active filter, in this order and with the
@@ -321,6 +367,17 @@ void hpgv_run_set_filters(const hpgv_run_filters_t *filters);
  *   ##FILTER=<ID=mendel,Description="Mendelian errors <= 1">
  *   ##FILTER=<ID=alleles,Description="Number of alleles == 2">
  *   ##FILTER=<ID=quality,Description="Quality >= 30">
+ * and then, for hpgv_run_set_record_filters (the strings verbatim, '"' and '\' written \" and \\; region-file in its second
+ * form with a region_type; snp / indel "exclude", var-type "indel" / "structural" as set) --
+ *   ##FILTER=<ID=coverage,Description="Coverage >= 10">
+ *   ##FILTER=<ID=region,Description="Regions 6:29000000-34000000">
+ *   ##FILTER=<ID=region-file,Description="Regions of file genes.gff">
+ *   ##FILTER=<ID=region-file,Description="Regions of file genes.gff of type exon">
+ *   ##FILTER=<ID=snp,Description="SNP include">
+ *   ##FILTER=<ID=var-type,Description="Variant type == snv">
+ *   ##FILTER=<ID=indel,Description="Indels include">
+ *   ##FILTER=<ID=inh-dom,Description="Samples following a dominant inheritance pattern >= 0.9">
+ *   ##FILTER=<ID=inh-rec,Description="Samples following a recessive inheritance pattern >= 0.9">
  * -- then the #CHROM line as written, then the records byte for byte in file order (the reference writes its batches as its
  * workers finish them).  A last line without a newline gets one; a line with fewer than CHROM .. ALT is rejected; empty lines
  * go to neither file.  The lines of a batch are partitioned on the device that tokenized them (hpgv_text_partition), whatever
