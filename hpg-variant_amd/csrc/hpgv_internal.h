@@ -1,6 +1,8 @@
 // hpgv_internal.h -- the context behind include/hpgv.h and the helpers shared by the translation units of
-// libhpgv.so (hpgv_capi.hip: association / TDT / stats / text / batch entry points; hpgv_epi_capi.hip: the
-// epistasis entry points, whose many kernel instantiations compile on their own).
+// libhpgv.so: hpgv_capi.hip (contexts, options, cohorts, memory, streams, text aliases), hpgv_scan_capi.hip (the
+// device-resident *_dev launchers), hpgv_tool_capi.hip (tokenizer, per-batch and text entry points),
+// hpgv_lines_capi.hip (partition / multisplit of lines), and the units whose kernel instantiations compile on their
+// own (hpgv_epi_capi.hip, hpgv_epi_generic_capi.hip, hpgv_statsall_capi.hip, hpgv_inflate_capi.hip, hpgv_group_capi.hip).
 #pragma once
 #include "../../include/hpgv.h"
 #include "hpgv_kernels.h"
@@ -44,6 +46,19 @@ struct Slot {
     size_t res_cap = 0;
     void *cnt_buf = nullptr;           // k_stats_all2's per-row counters between its two kernels
     size_t cnt_cap = 0;
+};
+
+// the genotype matrix of one synchronous call once it is on the device: what the per-tool back halves of
+// hpgv_tool_capi.hip read, whether a batch (batch_sources / stage_batch) or a text (text_front) put it there
+struct Staged {
+    const uint8_t *d_raw = nullptr;   // VCF column order: slot buf[0] or the caller's mapped rows (batch), buf[7] (text)
+    size_t raw_pitch = 0;
+    const uint8_t *d_laid = nullptr;  // slot buf[1] in layout `which`; null when a one-pass kernel reads d_raw itself
+    int which = 0;                    // HPGV_LAYOUT_* of d_laid
+    const uint8_t *d_isx = nullptr;
+    int n = 0;                        // rows
+    size_t out_stride = 0;            // stride of the per-group outputs: n_variants (batch), max_lines (text)
+    bool text = false;                // the tokenizer wrote d_raw: the only matrix k_assoc_rows is run on
 };
 
 // epistasis / MDR state: the vcf2epi dataset on the device, its bit planes for the current folds
@@ -240,6 +255,12 @@ struct Dealt {
     }
 #define GROUP_DEAL(ctx, CALL)                                                               \
     if (is_group(ctx)) { Dealt d_(ctx); hpgv_ctx *m_ = d_.m; return CALL; }
+// a *_text call goes to the member on whose device the text already lies (hpgv_text_alias), else it is dealt
+#define GROUP_DEAL_TEXT(ctx, text, CALL)                                                    \
+    if (is_group(ctx)) {                                                                    \
+        if (hpgv_ctx *m_ = alias_owner(ctx, text)) return CALL;                             \
+        Dealt d_(ctx); hpgv_ctx *m_ = d_.m; return CALL;                                    \
+    }
 
 #define HIPCHK(ctx, call)                                                                   \
     do {                                                                                    \
@@ -262,6 +283,8 @@ struct DeviceGuard {
 };
 
 [[maybe_unused]] size_t round_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+// pitch of the VCF-order matrix the tokenizer writes for the *_text entry points
+[[maybe_unused]] size_t raw_pitch_of(int n_samples) { return n_samples > 0 ? round_up((size_t)n_samples, 16) : 16; }
 
 [[maybe_unused]] int upload_layout(hpgv_ctx *ctx, Layout &L) {
     // the table is kept when it is large enough: hipFree waits for every stream of the device, and a file run sets its
@@ -323,6 +346,15 @@ struct SlotLease {
     }
 };
 
+// the opening of a synchronous entry point once its arguments are checked: the device current, a slot `s` leased until
+// the call returns, `rc` for what follows
+#define HPGV_LEASE_SLOT(ctx)                  \
+    DeviceGuard g(ctx->device);               \
+    SlotLease lease(ctx);                     \
+    int rc = acquire_slot(ctx, &lease.s);     \
+    if (rc) return rc;                        \
+    Slot *s = lease.s;
+
 template <typename F>
 [[maybe_unused]] int launch_profiled(hpgv_ctx *ctx, hipStream_t st, int which /*0 scan,1 stats*/, F &&launch) {
     if (ctx->profile) HIPCHK(ctx, hipEventRecord(ctx->ev[2 * which], st));
@@ -335,8 +367,25 @@ template <typename F>
     return HPGV_OK;
 }
 
+// Fisher's exact test needs the log-factorial table, long enough for the cohort's allele count
+[[maybe_unused]] int logfact_check(const hpgv_ctx *ctx) {
+    if (!ctx->d_lf) return fail(ctx, HPGV_ERR_STATE, "hpgv_set_logfact has not been called");
+    if (ctx->assoc.set && ctx->n_lf < (size_t)2 * (ctx->nA + ctx->nU) + 1)
+        return fail(ctx, HPGV_ERR_STATE, "log-factorial table has %zu entries, need %d", ctx->n_lf, 2 * (ctx->nA + ctx->nU) + 1);
+    return HPGV_OK;
+}
+
 }  // namespace
 
+// defined in hpgv_capi.hip: the text aliases of a context (hpgv_text_alias, hpgv_text_alias_tiles)
+bool tiles_of_device_text(hpgv_ctx *ctx, const char *d_text, hpgv_ctx::TextTiles *out);
+const char *text_on_device(hpgv_ctx *ctx, const char *host_text);
+hpgv_ctx *alias_owner(hpgv_ctx *group, const char *host_text);    // the member of a group on whose device `host_text` lies, or nullptr
+// defined in hpgv_tool_capi.hip: the largest raw-row window the one-pass kernels may stage in LDS on this device (hpgv_create)
+long hpgv_batch_lds_optin(const hipDeviceProp_t &prop, long fallback);
+// shared front half of the *_text entry points (and of hpgv_filter_text): text -> device, tokenize, record filters, lay out
+int text_front(hpgv_ctx *ctx, Slot *s, int which, const Layout &L, const char *text, size_t text_bytes, int max_lines, int *n_lines,
+               uint64_t *line_off, uint32_t *field_off, int32_t *status, Staged *S, bool final_layout = true);
 
 // defined in hpgv_statsall_capi.hip: k_stats_all2 on a batch (0 = launched, 1 = not a batch it takes: run k_stats_all)
 namespace hpgv { struct StatsAllArgs; }

@@ -11,7 +11,7 @@
 // by two lines and no store covers a neighbour's bytes.  The source of an interior granule is an unaligned dwordx4 load
 // (shipped) or two aligned ones shifted into place with v_alignbyte (option "part_aligned_loads", ablation build); DESIGN.md
 // "Partition of lines" has the A/B.
-// Included by hpgv_capi.hip only, after hpgv_text_kernels.h.
+// Included by hpgv_lines_capi.hip only, after hpgv_text_kernels.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
