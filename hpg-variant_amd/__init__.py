@@ -461,12 +461,14 @@ class Engine:
         self._chk(self.L.hpgv_epi_scan_triples(self.h, subset, _ptr(acc), _ptr(mask)))
         return acc, mask
 
-    def epi_rank_triples(self, subset, max_ranking_size):
+    def epi_rank_triples(self, subset, max_ranking_size, rows=None):
         k, n = self._epi[3], max_ranking_size
         ci, cj, ck = (np.zeros((k, n), np.int32) for _ in range(3))
         acc, mask, cnt = np.zeros((k, n), np.float64), np.zeros((k, n), np.uint32), np.zeros(k, np.int32)
         ms = C.c_float(0)
-        self._chk(self.L.hpgv_epi_rank_triples(self.h, subset, n, _ptr(ci), _ptr(cj), _ptr(ck), _ptr(acc), _ptr(mask), _ptr(cnt), C.byref(ms)))
+        lo, hi = (0, self._epi[0]) if rows is None else rows
+        self._chk(self.L.hpgv_epi_rank_triples_rows(self.h, lo, hi, subset, n, _ptr(ci), _ptr(cj), _ptr(ck), _ptr(acc), _ptr(mask), _ptr(cnt),
+                                                    C.byref(ms)))
         return dict(i=ci, j=cj, k=ck, accuracy=acc, risky=mask, n=cnt, scan_ms=ms.value)
 
     def epi_eval_combs(self, combs, subset):

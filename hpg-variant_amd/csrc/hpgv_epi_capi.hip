@@ -1,16 +1,10 @@
 // hpgv_epi_capi.hip -- C ABI of the epistasis / MDR path (its own translation unit of libhpgv.so: the pair and triple
 // scans are instantiated per fold count and compile for minutes).
-#include "hpgv_internal.h"
+#include "hpgv_epi_host.h"
 #include "hpgv_epi_triples3_kernels.h"
 #include "hpgv_epi_mfma_kernels.h"
 
-
 namespace {
-
-struct EventPair {                                                   // the two timing events of a ranking call
-    hipEvent_t a = nullptr, b = nullptr;
-    ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-};
 
 void epi_free_folds(EpiState &E) {
     if (E.d_planes) (void)hipFree(E.d_planes);
@@ -36,8 +30,7 @@ void epi_free(EpiState &E) {
     epi_free_folds(E);
     if (E.d_data) (void)hipFree(E.d_data);
     if (E.d_cand) (void)hipFree(E.d_cand);
-    if (E.d_cand3) (void)hipFree(E.d_cand3);
-    E.d_cand3 = nullptr; E.cand3_cap = 0;
+    E.cand_bytes = 0;
     if (E.d_cand_count) (void)hipFree(E.d_cand_count);
     if (E.d_thr) (void)hipFree(E.d_thr);
     if (E.d_tile_base) (void)hipFree(E.d_tile_base);
@@ -149,57 +142,40 @@ int epi_build_folds(hpgv_ctx *ctx, const int32_t *fold_of_sample, int num_folds)
     return HPGV_OK;
 }
 
-// per fold: testing sizes and the reciprocals of the evaluated part's sizes (RN(1 / y): IEEE double division on the host), for
-// the scan kernels' evaluation
-template <bool TRAINING>
-int epi_upload_folds(hpgv_ctx *ctx, hipStream_t st) {
+// room for `words` entries of tile tables (kept between calls)
+int epi_tile_room(hpgv_ctx *ctx, size_t words) {
     EpiState &E = ctx->epi;
-    hpgv::EpiFold folds[hpgv::EPI_MAX_FOLDS];
-    for (int f = 0; f < hpgv::EPI_MAX_FOLDS; ++f) {
-        folds[f].test_a = E.group_size[(size_t)2 * f]; folds[f].test_u = E.group_size[(size_t)2 * f + 1];
-        const int sa = TRAINING ? E.nA - folds[f].test_a : folds[f].test_a, su = TRAINING ? E.nU - folds[f].test_u : folds[f].test_u;
-        folds[f].inv_a = 1.0 / (double)sa; folds[f].inv_u = 1.0 / (double)su;
-    }
-    HIPCHK(ctx, hipMemcpyAsync(E.d_folds, folds, sizeof folds, hipMemcpyHostToDevice, st));
+    if (E.tile_base_cap >= words) return HPGV_OK;
+    if (E.d_tile_base) (void)hipFree(E.d_tile_base);
+    E.d_tile_base = nullptr; E.tile_base_cap = 0;
+    HIPCHK(ctx, hipMalloc(&E.d_tile_base, (words + 64) * sizeof(unsigned)));
+    E.tile_base_cap = words + 64;
     return HPGV_OK;
 }
 
-// the ranking scan with the cell counts on the matrix cores (hpgv_epi_mfma_kernels.h): tiles of 16 rows x 64 columns
-template <bool TRAINING, bool BALANCED>
-int epi_launch_pairs_mfma(hpgv_ctx *ctx, int i_begin, int i_end, hipStream_t st) {
+// The pair scans' tiles of `ti` rows x 64 columns that hold at least one pair of rows [i_begin, i_end), numbered column tile by
+// column tile: column tile tj0 + c pairs with the row blocks from the band's first row down to the diagonal, min(row_blocks,
+// (64 / ti) (c + 1)) of them.  Uploads the first tile of every column tile; the numbering starts on a multiple of 64 (i_begin is
+// rounded down: rows before the caller's emit nothing).  n_tiles = 0: nothing to launch.
+int epi_pair_tiles(hpgv_ctx *ctx, int ti, int &i_begin, int i_end, hipStream_t st, int &n_cols, unsigned &n_tiles) {
     EpiState &E = ctx->epi;
-    const int i_first = i_begin;
+    n_tiles = 0;
     i_begin = i_begin / 64 * 64;
-    const int tiles_j = (E.V + hpgv::EPI_TJ - 1) / hpgv::EPI_TJ, row_blocks = (i_end - i_begin + hpgv::EPM_TI - 1) / hpgv::EPM_TI;
-    const int n_cols = tiles_j - i_begin / 64;
+    const int tiles_j = (E.V + hpgv::EPI_TJ - 1) / hpgv::EPI_TJ, row_blocks = (i_end - i_begin + ti - 1) / ti;
+    n_cols = tiles_j - i_begin / 64;
     if (n_cols <= 0 || row_blocks <= 0) return HPGV_OK;
     std::vector<unsigned> tile_base((size_t)n_cols + 1);
     unsigned long long total = 0;
-    for (int c = 0; c < n_cols; ++c) {                               // column tile c holds pairs with the rows above its last column
+    for (int c = 0; c < n_cols; ++c) {
         tile_base[(size_t)c] = (unsigned)total;
-        total += (unsigned long long)std::min<long long>(row_blocks, (64ll / hpgv::EPM_TI) * (c + 1));
+        total += (unsigned long long)std::min<long long>(row_blocks, (64ll / ti) * (c + 1));
     }
     tile_base[(size_t)n_cols] = (unsigned)total;
     if (total + 8 > 0x7FFFFFFFull / 256) return fail(ctx, HPGV_ERR_UNSUPPORTED, "row band too large for one launch");
     if (total == 0) return HPGV_OK;
-    if (E.tile_base_cap < tile_base.size()) {
-        if (E.d_tile_base) (void)hipFree(E.d_tile_base);
-        E.d_tile_base = nullptr; E.tile_base_cap = 0;
-        HIPCHK(ctx, hipMalloc(&E.d_tile_base, (tile_base.size() + 64) * sizeof(unsigned)));
-        E.tile_base_cap = tile_base.size() + 64;
-    }
+    if (int rc = epi_tile_room(ctx, tile_base.size())) return rc;
     HIPCHK(ctx, hipMemcpyAsync(E.d_tile_base, tile_base.data(), tile_base.size() * sizeof(unsigned), hipMemcpyHostToDevice, st));
-    const unsigned n_tiles = (unsigned)total;
-    const dim3 grid((n_tiles + 7u) / 8u * 8u);
-    if (int rc = epi_upload_folds<TRAINING>(ctx, st)) return rc;
-    epi_note_launch(E, HPGV_EPI_KERNEL_PAIRS_MFMA);
-#define HPGV_EPM_LAUNCH(COMPLETEV)                                                                                                   \
-    hipLaunchKernelGGL((hpgv::k_epi_pairs_mfma<TRAINING, BALANCED, COMPLETEV>), grid, dim3(256), 0, st, E.d_planes, E.d_marg, E.rev_off, E.W, \
-                       E.V, i_begin, i_first, i_end, E.d_tile_base, n_cols, n_tiles, E.d_chunks, E.d_chunk_cls, E.n_chunks, E.d_folds, E.num_folds, E.nA, E.nU, E.d_thr, E.d_cand, E.d_cand_count, E.cand_cap)
-    if (E.complete && ctx->epi_complete) HPGV_EPM_LAUNCH(true);      // no missing call in the dataset: four cells counted, five derived
-    else HPGV_EPM_LAUNCH(false);
-#undef HPGV_EPM_LAUNCH
-    HIPCHK(ctx, hipGetLastError());
+    n_tiles = (unsigned)total;
     return HPGV_OK;
 }
 
@@ -207,58 +183,35 @@ template <bool TRAINING, bool BALANCED>
 int epi_launch_pairs2(hpgv_ctx *ctx, int i_begin, int i_end, double *d_acc, uint16_t *d_mask, unsigned long long n_pairs_out,
                       unsigned long long rank_base, bool candidates, hipStream_t st) {
     EpiState &E = ctx->epi;
-    if (candidates && !d_acc && ctx->epi_pairs_mfma && E.rev_off && E.n_chunks <= hpgv::EPM_MAX_CHUNKS && E.nA < 65536 && E.nU < 65536)
-        return epi_launch_pairs_mfma<TRAINING, BALANCED>(ctx, i_begin, i_end, st);
-    // tiles that hold at least one pair, numbered column tile by column tile: column tile tj0 + c pairs with the row
-    // blocks from the band's first row down to the diagonal, min(row_blocks, 16 (c + 1)) of them
+    // ranking: the cell counts on the matrix cores (hpgv_epi_mfma_kernels.h), tiles of 16 rows x 64 columns
+    const bool mfma = candidates && !d_acc && ctx->epi_pairs_mfma && E.rev_off && E.n_chunks <= hpgv::EPM_MAX_CHUNKS && E.nA < 65536 && E.nU < 65536;
     const int i_first = i_begin;
-    i_begin = i_begin / 64 * 64;                                     // the tile numbering starts on a multiple of 64; rows before i_first emit nothing
-    const int tiles_j = (E.V + hpgv::EPI_TJ - 1) / hpgv::EPI_TJ, row_blocks = (i_end - i_begin + hpgv::EPI_TI - 1) / hpgv::EPI_TI;
-    const int n_cols = tiles_j - i_begin / 64;
-    if (n_cols <= 0 || row_blocks <= 0) return HPGV_OK;
-    std::vector<unsigned> tile_base((size_t)n_cols + 1);
-    unsigned long long total = 0;
-    for (int c = 0; c < n_cols; ++c) {
-        tile_base[(size_t)c] = (unsigned)total;
-        total += (unsigned long long)std::min<long long>(row_blocks, 16ll * (c + 1));
-    }
-    tile_base[(size_t)n_cols] = (unsigned)total;
-    if (total + 8 > 0x7FFFFFFFull / 256) return fail(ctx, HPGV_ERR_UNSUPPORTED, "row band too large for one launch");
-    if (total == 0) return HPGV_OK;
-    if (E.tile_base_cap < tile_base.size()) {
-        if (E.d_tile_base) (void)hipFree(E.d_tile_base);
-        E.d_tile_base = nullptr; E.tile_base_cap = 0;
-        HIPCHK(ctx, hipMalloc(&E.d_tile_base, (tile_base.size() + 64) * sizeof(unsigned)));
-        E.tile_base_cap = tile_base.size() + 64;
-    }
-    HIPCHK(ctx, hipMemcpyAsync(E.d_tile_base, tile_base.data(), tile_base.size() * sizeof(unsigned), hipMemcpyHostToDevice, st));
-    const unsigned n_tiles = (unsigned)total;
+    int n_cols = 0;
+    unsigned n_tiles = 0;
+    if (int rc = epi_pair_tiles(ctx, mfma ? hpgv::EPM_TI : hpgv::EPI_TI, i_begin, i_end, st, n_cols, n_tiles)) return rc;
+    if (!n_tiles) return HPGV_OK;
     const dim3 grid((n_tiles + 7u) / 8u * 8u);                       // eight spans, one per XCD
-    if (int rc = epi_upload_folds<TRAINING>(ctx, st)) return rc;
-    if (candidates) epi_note_launch(E, HPGV_EPI_KERNEL_PAIRS_VALU);
-#define HPGV_EPI_LAUNCH(KK)                                                                                                         \
+    if (int rc = epi_upload_folds(ctx, TRAINING, st)) return rc;
+    if (candidates) epi_note_launch(E, mfma ? HPGV_EPI_KERNEL_PAIRS_MFMA : HPGV_EPI_KERNEL_PAIRS_VALU);
+    hpgv::EpiCand *d_cand = candidates ? (hpgv::EpiCand *)E.d_cand : nullptr;
+#define HPGV_EPM_LAUNCH(COMPLETEV)                                                                                                   \
+    hipLaunchKernelGGL((hpgv::k_epi_pairs_mfma<TRAINING, BALANCED, COMPLETEV>), grid, dim3(256), 0, st, E.d_planes, E.d_marg, E.rev_off, E.W, \
+                       E.V, i_begin, i_first, i_end, E.d_tile_base, n_cols, n_tiles, E.d_chunks, E.d_chunk_cls, E.n_chunks, E.d_folds, E.num_folds, E.nA, E.nU, E.d_thr, d_cand, E.d_cand_count, E.cand_cap)
+#define HPGV_EPI_LAUNCH(KK, COMPLETEV)                                                                                              \
     hipLaunchKernelGGL((hpgv::k_epi_pairs<KK, TRAINING, BALANCED, COMPLETEV>), grid, dim3(256), 0, st, E.d_planes, E.d_marg, E.W, E.V, i_begin, i_first, i_end, \
                        E.d_tile_base, n_cols, n_tiles, E.d_chunks, E.n_chunks, E.d_folds, E.nA, E.nU, d_acc, d_mask, n_pairs_out, rank_base,                          \
-                       candidates ? E.d_thr : nullptr, candidates ? E.d_cand : nullptr, E.d_cand_count, E.cand_cap)
-    const int k = E.num_folds;
-    if (E.complete && ctx->epi_complete) {
-        constexpr bool COMPLETEV = true;                                 // no missing call in the dataset: four cells counted, five derived
-        if (k <= 2) HPGV_EPI_LAUNCH(2);
-        else if (k <= 4) HPGV_EPI_LAUNCH(4);
-        else if (k <= 5) HPGV_EPI_LAUNCH(5);
-        else if (k <= 8) HPGV_EPI_LAUNCH(8);
-        else if (k <= 10) HPGV_EPI_LAUNCH(10);
-        else HPGV_EPI_LAUNCH(16);
-    } else {
-        constexpr bool COMPLETEV = false;
-        if (k <= 2) HPGV_EPI_LAUNCH(2);
-        else if (k <= 4) HPGV_EPI_LAUNCH(4);
-        else if (k <= 5) HPGV_EPI_LAUNCH(5);
-        else if (k <= 8) HPGV_EPI_LAUNCH(8);
-        else if (k <= 10) HPGV_EPI_LAUNCH(10);
-        else HPGV_EPI_LAUNCH(16);                                    // 11 .. 16 folds: two waves per SIMD
-    }
+                       candidates ? E.d_thr : nullptr, d_cand, E.d_cand_count, E.cand_cap)
+#define HPGV_EPI_LAUNCH_K(COMPLETEV)                                                                                                \
+    do { const int k = E.num_folds;                                                                                                 \
+         if (mfma) HPGV_EPM_LAUNCH(COMPLETEV);                                                                                      \
+         else if (k <= 2) HPGV_EPI_LAUNCH(2, COMPLETEV); else if (k <= 4) HPGV_EPI_LAUNCH(4, COMPLETEV); else if (k <= 5) HPGV_EPI_LAUNCH(5, COMPLETEV);       \
+         else if (k <= 8) HPGV_EPI_LAUNCH(8, COMPLETEV); else if (k <= 10) HPGV_EPI_LAUNCH(10, COMPLETEV);                             \
+         else HPGV_EPI_LAUNCH(16, COMPLETEV); } while (0)             /* 11 .. 16 folds: two waves per SIMD */
+    if (E.complete && ctx->epi_complete) HPGV_EPI_LAUNCH_K(true);    // no missing call in the dataset: four cells counted, five derived
+    else HPGV_EPI_LAUNCH_K(false);
+#undef HPGV_EPI_LAUNCH_K
 #undef HPGV_EPI_LAUNCH
+#undef HPGV_EPM_LAUNCH
     HIPCHK(ctx, hipGetLastError());
     return HPGV_OK;
 }
@@ -345,7 +298,7 @@ static int epi_cells(int order) { int c = 1; for (int k = 0; k < order; ++k) c *
 // in-fold counts of listed combinations: host vector [(comb * n_groups + g) * cells + c]
 static int epi_infold_counts(hpgv_ctx *ctx, int order, const int32_t *combs, int n_combs, std::vector<int32_t> &out) {
     EpiState &E = ctx->epi;
-    if (!E.have_folds) return fail(ctx, HPGV_ERR_STATE, "no folds: hpgv_epi_set_dataset has not been called, or a class of 65536 samples or more waits for hpgv_epi_set_folds");
+    if (int rc = epi_check_folds(ctx)) return rc;
     if (order < 2 || order > 5) return fail(ctx, HPGV_ERR_UNSUPPORTED, "combinations of %d SNPs are not supported (2 to 5)", order);
     if (n_combs < 0 || (n_combs > 0 && !combs)) return fail(ctx, HPGV_ERR_INVALID, "bad combination list");
     for (int k = 0; k < n_combs * order; ++k)
@@ -353,9 +306,10 @@ static int epi_infold_counts(hpgv_ctx *ctx, int order, const int32_t *combs, int
     const int cells = epi_cells(order), ng = E.num_folds * 2;
     out.assign((size_t)n_combs * ng * cells, 0);
     if (n_combs == 0) return HPGV_OK;
-    int32_t *d_combs = nullptr, *d_out = nullptr;
-    HIPCHK(ctx, hipMalloc(&d_combs, (size_t)n_combs * order * sizeof(int32_t)));
-    hipError_t e = hipMalloc(&d_out, out.size() * sizeof(int32_t));
+    DevFree dc, dout;
+    HIPCHK(ctx, hipMalloc(&dc.p, (size_t)n_combs * order * sizeof(int32_t)));
+    hipError_t e = hipMalloc(&dout.p, out.size() * sizeof(int32_t));
+    int32_t *d_combs = (int32_t *)dc.p, *d_out = (int32_t *)dout.p;
     if (e == hipSuccess) e = hipMemcpy(d_combs, combs, (size_t)n_combs * order * sizeof(int32_t), hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         const dim3 grid((unsigned)((n_combs + 3) / 4));
@@ -364,12 +318,26 @@ static int epi_infold_counts(hpgv_ctx *ctx, int order, const int32_t *combs, int
         else if (order == 3) hipLaunchKernelGGL((hpgv::k_epi_counts<3>), grid, dim3(256), 0, nullptr, E.d_planes, E.W, d_combs, n_combs, E.d_group_w0, ng, d_out);
         else rc4 = hpgv_epi_generic_counts(ctx, order, d_combs, n_combs, d_out);      // one lane per cell (hpgv_epi_generic_kernels.h)
         e = hipGetLastError();
-        if (rc4) { (void)hipFree(d_combs); (void)hipFree(d_out); return rc4; }
+        if (rc4) return rc4;
     }
     if (e == hipSuccess) e = hipMemcpy(out.data(), d_out, out.size() * sizeof(int32_t), hipMemcpyDeviceToHost);
-    (void)hipFree(d_combs);
-    if (d_out) (void)hipFree(d_out);
     if (e != hipSuccess) return fail(ctx, HPGV_ERR_HIP, "epistasis counts failed: %s", hipGetErrorString(e));
+    return HPGV_OK;
+}
+
+// the shared half of hpgv_epi_counts / _all_folds: the in-fold counts `in` of `nf` folds, and per combination and cell the sums over
+// the folds' cases and controls in sum_a / sum_u
+static int epi_counts_front(hpgv_ctx *ctx, int order, const int32_t *combs, int n_combs, const int32_t *counts_aff, const int32_t *counts_unaff,
+                            std::vector<int32_t> &in, int &nf, std::vector<int32_t> &sum_a, std::vector<int32_t> &sum_u) {
+    if (n_combs > 0 && (!counts_aff || !counts_unaff)) return fail(ctx, HPGV_ERR_INVALID, "count outputs are NULL");
+    DeviceGuard g(ctx->device);
+    std::lock_guard<std::mutex> lk(ctx->epi_mu);
+    if (int rc = epi_infold_counts(ctx, order, combs, n_combs, in)) return rc;
+    nf = ctx->epi.num_folds;
+    const size_t cells = (size_t)epi_cells(order), ng = (size_t)nf * 2, n = (size_t)n_combs * cells;
+    sum_a.assign(n, 0); sum_u.assign(n, 0);
+    for (size_t o = 0; o < n; ++o)
+        for (size_t gi = 0; gi < ng; gi += 2) { sum_a[o] += in[(o / cells * ng + gi) * cells + o % cells]; sum_u[o] += in[(o / cells * ng + gi + 1) * cells + o % cells]; }
     return HPGV_OK;
 }
 
@@ -377,19 +345,10 @@ int hpgv_epi_counts(hpgv_ctx *ctx, int order, const int32_t *combs, int n_combs,
     HPGV_ABI_TRY
     ctx = first_member(ctx);
     if (!ctx) return HPGV_ERR_INVALID;
-    if (n_combs > 0 && (!counts_aff || !counts_unaff)) return fail(ctx, HPGV_ERR_INVALID, "count outputs are NULL");
-    DeviceGuard g(ctx->device);
-    std::lock_guard<std::mutex> lk(ctx->epi_mu);
-    std::vector<int32_t> in;
-    int rc = epi_infold_counts(ctx, order, combs, n_combs, in);
-    if (rc) return rc;
-    const int cells = epi_cells(order), ng = ctx->epi.num_folds * 2;
-    for (int k = 0; k < n_combs; ++k)
-        for (int c = 0; c < cells; ++c) {
-            int a = 0, u = 0;
-            for (int gi = 0; gi < ng; gi += 2) { a += in[((size_t)k * ng + gi) * cells + c]; u += in[((size_t)k * ng + gi + 1) * cells + c]; }
-            counts_aff[(size_t)k * cells + c] = a; counts_unaff[(size_t)k * cells + c] = u;
-        }
+    std::vector<int32_t> in, a, u;
+    int nf = 0;
+    if (int rc = epi_counts_front(ctx, order, combs, n_combs, counts_aff, counts_unaff, in, nf, a, u)) return rc;
+    std::copy(a.begin(), a.end(), counts_aff); std::copy(u.begin(), u.end(), counts_unaff);
     return HPGV_OK;
     HPGV_ABI_CATCH(ctx)
 }
@@ -398,34 +357,44 @@ int hpgv_epi_counts_all_folds(hpgv_ctx *ctx, int order, const int32_t *combs, in
     HPGV_ABI_TRY
     ctx = first_member(ctx);
     if (!ctx) return HPGV_ERR_INVALID;
-    if (n_combs > 0 && (!counts_aff || !counts_unaff)) return fail(ctx, HPGV_ERR_INVALID, "count outputs are NULL");
-    DeviceGuard g(ctx->device);
-    std::lock_guard<std::mutex> lk(ctx->epi_mu);
-    std::vector<int32_t> in;
-    int rc = epi_infold_counts(ctx, order, combs, n_combs, in);
-    if (rc) return rc;
-    const int cells = epi_cells(order), nf = ctx->epi.num_folds, ng = nf * 2;
-    for (int k = 0; k < n_combs; ++k)
-        for (int c = 0; c < cells; ++c) {
-            int a = 0, u = 0;
-            for (int gi = 0; gi < ng; gi += 2) { a += in[((size_t)k * ng + gi) * cells + c]; u += in[((size_t)k * ng + gi + 1) * cells + c]; }
-            for (int f = 0; f < nf; ++f) {                           // training part of fold f = everybody but its own group
-                const size_t o = ((size_t)f * n_combs + k) * cells + c;   // model.c:166-168
-                counts_aff[o] = a - in[((size_t)k * ng + 2 * f) * cells + c];
-                counts_unaff[o] = u - in[((size_t)k * ng + 2 * f + 1) * cells + c];
-            }
+    std::vector<int32_t> in, a, u;
+    int nf = 0;
+    if (int rc = epi_counts_front(ctx, order, combs, n_combs, counts_aff, counts_unaff, in, nf, a, u)) return rc;
+    const size_t cells = (size_t)epi_cells(order), n = a.size();
+    for (size_t f = 0; f < (size_t)nf; ++f)                          // training part of fold f = everybody but its own group (model.c:166-168)
+        for (size_t o = 0; o < n; ++o) {
+            const size_t own = (o / cells * (size_t)nf * 2 + 2 * f) * cells + o % cells;
+            counts_aff[f * n + o] = a[o] - in[own]; counts_unaff[f * n + o] = u[o] - in[own + cells];
         }
     return HPGV_OK;
     HPGV_ABI_CATCH(ctx)
 }
 
+// the dense scans' device side: n accuracies and n masks made by `launch` and copied back (clear: cells the launch leaves
+// alone read as NaN / 0)
+template <class Mask, class Launch>
+static int epi_dense_scan(hpgv_ctx *ctx, size_t n, bool clear, double *accuracy, Mask *mask, const char *what, Launch &&launch) {
+    DevFree da, dm;
+    HIPCHK(ctx, hipMalloc(&da.p, n * sizeof(double)));
+    hipError_t e = hipMalloc(&dm.p, n * sizeof(Mask));
+    if (e == hipSuccess && clear) e = hipMemset(da.p, 0xFF, n * sizeof(double));
+    if (e == hipSuccess && clear) e = hipMemset(dm.p, 0, n * sizeof(Mask));
+    if (e == hipSuccess) {
+        if (int rc = launch((double *)da.p, (Mask *)dm.p)) return rc;
+        e = hipMemcpy(accuracy, da.p, n * sizeof(double), hipMemcpyDeviceToHost);
+    }
+    if (e == hipSuccess) e = hipMemcpy(mask, dm.p, n * sizeof(Mask), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(ctx, HPGV_ERR_HIP, "epistasis %s scan failed: %s", what, hipGetErrorString(e));
+    return HPGV_OK;
+}
+
 int hpgv_epi_scan_pairs(hpgv_ctx *ctx, int i_begin, int i_end, int subset, double *accuracy, uint16_t *risky_mask,
                         unsigned long long *n_pairs) {
+    HPGV_ABI_TRY
     ctx = first_member(ctx);
     if (!ctx) return HPGV_ERR_INVALID;
     EpiState &E = ctx->epi;
-    if (!E.have_folds) return fail(ctx, HPGV_ERR_STATE, "no folds: hpgv_epi_set_dataset has not been called, or a class of 65536 samples or more waits for hpgv_epi_set_folds");
-    if (subset != HPGV_EPI_TESTING && subset != HPGV_EPI_TRAINING) return fail(ctx, HPGV_ERR_INVALID, "subset must be HPGV_EPI_TESTING or HPGV_EPI_TRAINING");
+    if (int rc = epi_check(ctx, subset)) return rc;
     if (i_begin < 0 || i_end < i_begin || i_end > E.V) return fail(ctx, HPGV_ERR_INVALID, "rows [%d, %d) outside the dataset", i_begin, i_end);
     const unsigned long long V = (unsigned long long)E.V;
     const unsigned long long base = epi_rank(V, (unsigned long long)i_begin);
@@ -435,22 +404,86 @@ int hpgv_epi_scan_pairs(hpgv_ctx *ctx, int i_begin, int i_end, int subset, doubl
     if (!accuracy || !risky_mask) return fail(ctx, HPGV_ERR_INVALID, "accuracy and risky_mask go together");
     DeviceGuard g(ctx->device);
     std::lock_guard<std::mutex> lk(ctx->epi_mu);
-    const size_t nf = (size_t)E.num_folds;
-    double *d_acc = nullptr; uint16_t *d_mask = nullptr;
-    HIPCHK(ctx, hipMalloc(&d_acc, nf * np * sizeof(double)));
-    hipError_t e = hipMalloc(&d_mask, nf * np * sizeof(uint16_t));
-    int rc = HPGV_OK;
-    if (e == hipSuccess) {
-        rc = subset == HPGV_EPI_TRAINING ? epi_launch_pairs<true>(ctx, i_begin, i_end, d_acc, d_mask, np, base, false, nullptr)
-                                         : epi_launch_pairs<false>(ctx, i_begin, i_end, d_acc, d_mask, np, base, false, nullptr);
-        if (!rc) e = hipMemcpy(accuracy, d_acc, nf * np * sizeof(double), hipMemcpyDeviceToHost);
-        if (!rc && e == hipSuccess) e = hipMemcpy(risky_mask, d_mask, nf * np * sizeof(uint16_t), hipMemcpyDeviceToHost);
+    return epi_dense_scan(ctx, (size_t)E.num_folds * np, false, accuracy, risky_mask, "pair", [&](double *d_acc, uint16_t *d_mask) {
+        return subset == HPGV_EPI_TRAINING ? epi_launch_pairs<true>(ctx, i_begin, i_end, d_acc, d_mask, np, base, false, nullptr)
+                                           : epi_launch_pairs<false>(ctx, i_begin, i_end, d_acc, d_mask, np, base, false, nullptr);
+    });
+    HPGV_ABI_CATCH(ctx)
+}
+
+namespace {
+
+// what the pair and triple policies share: the lists live in the context
+template <class C>
+struct EpiTileOrder {
+    using Cand = C;
+    hpgv_ctx *ctx; EpiState &E; const bool training; const long long V, i_begin;
+    Cand *d_cand = nullptr; unsigned cap = 0;
+    long long hi;                                                    // what is left: [i_begin, hi)
+    EpiTileOrder(hpgv_ctx *c, int subset, int begin, long long last) : ctx(c), E(c->epi), training(subset == HPGV_EPI_TRAINING), V(c->epi.V), i_begin(begin), hi(last) {}
+    int room(size_t lists, unsigned cap_) {                          // (kept between calls and only ever grown: 240 MB for the triples of 1 024 SNPs)
+        const size_t bytes = lists * cap_ * sizeof(Cand);
+        if (E.cand_bytes < bytes) {
+            if (E.d_cand) (void)hipFree(E.d_cand);
+            E.d_cand = nullptr; E.cand_bytes = 0;
+            HIPCHK(ctx, hipMalloc(&E.d_cand, bytes));
+            E.cand_bytes = bytes;
+        }
+        d_cand = (Cand *)E.d_cand; cap = E.cand_cap = cap_;
+        return HPGV_OK;
     }
-    (void)hipFree(d_acc);
-    if (d_mask) (void)hipFree(d_mask);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(ctx, HPGV_ERR_HIP, "epistasis pair scan failed: %s", hipGetErrorString(e));
-    return HPGV_OK;
+    bool more() const { return hi > i_begin; }
+    static const Cand &keep(const Cand &c) { return c; }
+};
+
+// Pairs.  Bands from the LAST rows up: row r begins V - 1 - r pairs, so the first launches list a few thousand models and leave
+// thresholds behind for the long rows (no pre-pass for starting thresholds).  Pairs per launch: a small first band, growing
+// while the candidate lists stay short.
+struct EpiPairOrder : EpiTileOrder<hpgv::EpiCand> {
+    long long band_pairs, lo = 0, pairs = 0;
+    EpiPairOrder(hpgv_ctx *c, int subset, int begin, int end, int N)
+        : EpiTileOrder(c, subset, begin, std::min<long long>(c->epi.V - 1, end)), band_pairs(std::max<long long>(8192, 2ll * N)) {}      // row V - 1 has no pair
+    int setup() { return room(hpgv::EPI_MAX_FOLDS, (unsigned)std::max<long long>(1ll << 20, 64ll * V)); }     // a band of 64 rows with no threshold yet fits
+    int launch() {
+        // whole blocks of 64 rows (the tile numbering wants bands that start on a multiple of 64), at least one
+        pairs = 0; lo = hi;
+        while (lo > i_begin) {
+            const long long nxt = std::max<long long>(i_begin, (lo - 1) / 64 * 64);
+            long long add = 0;
+            for (long long r = nxt; r < lo; ++r) add += V - 1 - r;
+            if (lo < hi && pairs + add > band_pairs) break;
+            pairs += add; lo = nxt;
+        }
+        return training ? epi_launch_pairs<true>(ctx, (int)lo, (int)hi, nullptr, nullptr, 0, 0, true, nullptr)
+                        : epi_launch_pairs<false>(ctx, (int)lo, (int)hi, nullptr, nullptr, 0, 0, true, nullptr);
+    }
+    int shrink() {
+        if (hi - lo <= 64) return fail(ctx, HPGV_ERR_UNSUPPORTED, "more than %u models of 64 rows reach a fold's threshold: too many SNPs for the candidate lists", cap);
+        band_pairs = pairs / 2 > 0 ? pairs / 2 : 1;
+        return HPGV_OK;
+    }
+    int advance(unsigned worst) {
+        // (a launch of a few tiles takes as long as one workgroup's whole scan: once thresholds exist and the lists stay
+        // nearly empty the bands grow fast)
+        if (worst < cap / 64 && band_pairs < (long long)cap * 1024) band_pairs *= 32;
+        else if (worst < cap / 8 && band_pairs < (long long)cap * 1024) band_pairs *= 4;
+        hi = lo;
+        return HPGV_OK;
+    }
+};
+
+}  // namespace
+
+int hpgv_epi_pairs_models(hpgv_ctx *ctx, int i_begin, int i_end, int subset, int N, bool have_outputs, std::vector<EpiModel> &out, float *scan_ms) {
+    EpiState &E = ctx->epi;
+    if (i_begin < 0 || i_end < i_begin || i_end > E.V || (i_begin % 64 && i_begin != i_end))
+        return fail(ctx, HPGV_ERR_INVALID, "rows [%d, %d): the band must lie in the dataset and start on a multiple of 64", i_begin, i_end);
+    if (int rc = epi_check(ctx, subset)) return rc;
+    if (N < 1 || N > 65536 || !have_outputs) return fail(ctx, HPGV_ERR_INVALID, "bad ranking arguments");
+    DeviceGuard g(ctx->device);
+    std::lock_guard<std::mutex> lk(ctx->epi_mu);
+    EpiPairOrder o(ctx, subset, i_begin, i_end, N);
+    return epi_rank_loop(ctx, o, N, out, scan_ms);
 }
 
 int hpgv_epi_rank_pairs(hpgv_ctx *ctx, int subset, int max_ranking_size, int32_t *comb_i, int32_t *comb_j, double *accuracy,
@@ -465,107 +498,10 @@ int hpgv_epi_rank_pairs_rows(hpgv_ctx *ctx, int i_begin, int i_end, int subset, 
     HPGV_ABI_TRY
     ctx = first_member(ctx);
     if (!ctx) return HPGV_ERR_INVALID;
-    EpiState &E = ctx->epi;
-    if (i_begin < 0 || i_end < i_begin || i_end > E.V || (i_begin % 64 && i_begin != i_end))
-        return fail(ctx, HPGV_ERR_INVALID, "rows [%d, %d): the band must lie in the dataset and start on a multiple of 64", i_begin, i_end);
-    if (!E.have_folds) return fail(ctx, HPGV_ERR_STATE, "no folds: hpgv_epi_set_dataset has not been called, or a class of 65536 samples or more waits for hpgv_epi_set_folds");
-    if (subset != HPGV_EPI_TESTING && subset != HPGV_EPI_TRAINING) return fail(ctx, HPGV_ERR_INVALID, "subset must be HPGV_EPI_TESTING or HPGV_EPI_TRAINING");
-    if (max_ranking_size < 1 || max_ranking_size > 65536 || !comb_i || !comb_j || !accuracy || !risky_mask || !n_ranked)
-        return fail(ctx, HPGV_ERR_INVALID, "bad ranking arguments");
-    DeviceGuard g(ctx->device);
-    std::lock_guard<std::mutex> lk(ctx->epi_mu);
-    E.rank_info = hpgv_epi_rank_info{};
-    const int nf = E.num_folds, N = max_ranking_size;
-    const unsigned cap = (unsigned)std::max<long long>(1ll << 20, 64ll * E.V);      // a band of 64 rows with no threshold yet fits
-    if (!E.d_cand || E.cand_cap != cap) {
-        if (E.d_cand) (void)hipFree(E.d_cand);
-        E.d_cand = nullptr;
-        HIPCHK(ctx, hipMalloc(&E.d_cand, (size_t)hpgv::EPI_MAX_FOLDS * cap * sizeof(hpgv::EpiCand)));
-        E.cand_cap = cap;
-    }
-    if (!E.d_cand_count) HIPCHK(ctx, hipMalloc(&E.d_cand_count, hpgv::EPI_MAX_FOLDS * sizeof(unsigned)));
-    if (!E.d_thr) HIPCHK(ctx, hipMalloc(&E.d_thr, hpgv::EPI_MAX_FOLDS * sizeof(double)));
-    std::vector<std::vector<hpgv::EpiCand>> top((size_t)nf);
-    std::vector<double> thr(hpgv::EPI_MAX_FOLDS, -HUGE_VAL);
-    std::vector<unsigned> count(hpgv::EPI_MAX_FOLDS);
-    std::vector<hpgv::EpiCand> buf;
-    auto better = [](const hpgv::EpiCand &a, const hpgv::EpiCand &b) {
-        if (a.accuracy != b.accuracy) return a.accuracy > b.accuracy;
-        if (a.i != b.i) return a.i < b.i;
-        return a.j < b.j;
-    };
-    EventPair evs;                                                   // destroyed on every return path
-    hipEvent_t &ev0 = evs.a, &ev1 = evs.b;
-    float total_ms = 0.f;
-    if (scan_ms) { HIPCHK(ctx, hipEventCreate(&ev0)); HIPCHK(ctx, hipEventCreate(&ev1)); }
-    const long long V = E.V;
-    const long long last = std::min<long long>(V - 1, i_end);          // row V - 1 has no pair
-    // Bands from the LAST rows up: row r begins V - 1 - r pairs, so the first launches list a few thousand models and leave
-    // thresholds behind for the long rows (no pre-pass for starting thresholds; the order of the launches does not show in the
-    // ranking: ties go by (i, j)).  Pairs per launch: a small first band, growing while the candidate lists stay short.
-    long long band_pairs = std::max<long long>(8192, 2ll * N);
-    long long hi = last;
-    int rc = HPGV_OK;
-    while (hi > i_begin && !rc) {
-        long long pairs = 0;
-        long long lo = hi;
-        // whole blocks of 64 rows (the tile numbering wants bands that start on a multiple of 64), at least one
-        while (lo > i_begin) {
-            const long long nxt = std::max<long long>(i_begin, (lo - 1) / 64 * 64);
-            long long add = 0;
-            for (long long r = nxt; r < lo; ++r) add += V - 1 - r;
-            if (lo < hi && pairs + add > band_pairs) break;
-            pairs += add; lo = nxt;
-        }
-        const int i = (int)lo, e_row = (int)hi;
-        HIPCHK(ctx, hipMemsetAsync(E.d_cand_count, 0, hpgv::EPI_MAX_FOLDS * sizeof(unsigned), nullptr));
-        HIPCHK(ctx, hipMemcpyAsync(E.d_thr, thr.data(), hpgv::EPI_MAX_FOLDS * sizeof(double), hipMemcpyHostToDevice, nullptr));
-        if (scan_ms) HIPCHK(ctx, hipEventRecord(ev0, nullptr));
-        rc = subset == HPGV_EPI_TRAINING ? epi_launch_pairs<true>(ctx, i, e_row, nullptr, nullptr, 0, 0, true, nullptr)
-                                         : epi_launch_pairs<false>(ctx, i, e_row, nullptr, nullptr, 0, 0, true, nullptr);
-        if (rc) break;
-        if (scan_ms) HIPCHK(ctx, hipEventRecord(ev1, nullptr));
-        HIPCHK(ctx, hipMemcpy(count.data(), E.d_cand_count, hpgv::EPI_MAX_FOLDS * sizeof(unsigned), hipMemcpyDeviceToHost));
-        if (scan_ms) { float ms = 0.f; HIPCHK(ctx, hipEventElapsedTime(&ms, ev0, ev1)); total_ms += ms; }
-        unsigned worst = 0;
-        for (int f = 0; f < nf; ++f) worst = count[(size_t)f] > worst ? count[(size_t)f] : worst;
-        if (worst > cap) {                                           // some list overflowed: this band again, in smaller pieces
-            ++E.rank_info.relaunches;
-            if (e_row - i <= 64) { rc = fail(ctx, HPGV_ERR_UNSUPPORTED, "more than %u models of 64 rows reach a fold's threshold: too many SNPs for the candidate lists", cap); break; }
-            band_pairs = pairs / 2 > 0 ? pairs / 2 : 1;
-            continue;
-        }
-        for (int f = 0; f < nf && !rc; ++f) {
-            const unsigned n = count[(size_t)f];
-            if (!n) continue;
-            buf.resize(n);
-            HIPCHK(ctx, hipMemcpy(buf.data(), E.d_cand + (size_t)f * cap, (size_t)n * sizeof(hpgv::EpiCand), hipMemcpyDeviceToHost));
-            auto &t = top[(size_t)f];
-            t.insert(t.end(), buf.begin(), buf.end());
-            if ((int)t.size() > N) {
-                std::partial_sort(t.begin(), t.begin() + N, t.end(), better);
-                t.resize((size_t)N);
-            } else {
-                std::sort(t.begin(), t.end(), better);
-            }
-            if ((int)t.size() >= N && t.back().accuracy > thr[(size_t)f]) thr[(size_t)f] = t.back().accuracy;
-        }
-        // (a launch of a few tiles takes as long as one workgroup's whole scan: once thresholds exist and the lists stay
-        // nearly empty the bands grow fast)
-        if (worst < cap / 64 && band_pairs < (long long)cap * 1024) band_pairs *= 32;
-        else if (worst < cap / 8 && band_pairs < (long long)cap * 1024) band_pairs *= 4;
-        hi = lo;
-    }
-    if (rc) return rc;
-    for (int f = 0; f < nf; ++f) {
-        const auto &t = top[(size_t)f];
-        n_ranked[f] = (int32_t)t.size();
-        for (size_t k = 0; k < t.size(); ++k) {
-            comb_i[(size_t)f * N + k] = t[k].i; comb_j[(size_t)f * N + k] = t[k].j;
-            accuracy[(size_t)f * N + k] = t[k].accuracy; risky_mask[(size_t)f * N + k] = t[k].risky;
-        }
-    }
-    if (scan_ms) *scan_ms = total_ms;
+    std::vector<EpiModel> m;
+    if (int rc = hpgv_epi_pairs_models(ctx, i_begin, i_end, subset, max_ranking_size, comb_i && comb_j && accuracy && risky_mask && n_ranked, m, scan_ms)) return rc;
+    int32_t *const comb[2] = {comb_i, comb_j};
+    epi_scatter(m, max_ranking_size, 2, comb, 1, accuracy, risky_mask, 1, n_ranked);
     return HPGV_OK;
     HPGV_ABI_CATCH(ctx)
 }
@@ -582,61 +518,54 @@ int hpgv_epi_last_rank_info(hpgv_ctx *ctx, hpgv_epi_rank_info *info) {
 
 namespace {
 
-template <bool TRAINING>
-int epi_launch_triples(hpgv_ctx *ctx, int i_first, int n_i, double *d_acc, uint32_t *d_mask, bool candidates,
-                       hpgv::EpiCand3 *d_cand, unsigned cap) {
+// The triple scans' tiles that hold a triple, for blocks of `tj` second SNPs: for the j block jb (rows tj jb .. tj jb + tj - 1) the
+// k tiles from the one that holds tj jb + 1 on (d_jbp: their running count); a first SNP i takes the j blocks from (i + 1) / tj
+// on (d_rb: the first tile of each of the n_i first SNPs from i_first; total: all of them).
+int epi_triple_tiles(hpgv_ctx *ctx, int tj, int i_first, int n_i, int &n_jb, unsigned &total_out, unsigned *&d_jbp, unsigned *&d_rb) {
     EpiState &E = ctx->epi;
-    if (int rc = epi_upload_folds<TRAINING>(ctx, nullptr)) return rc;
-    // tiles that hold a triple: for the j block jb (rows 4 jb .. 4 jb + 3) the k tiles from the one that holds 4 jb + 1
-    // on; a first SNP i takes the j blocks from (i + 1) / 4 on
-    const int n_kt = (E.V + hpgv::EPI_TJ - 1) / hpgv::EPI_TJ, n_jb = (E.V + hpgv::EPI_TI - 1) / hpgv::EPI_TI;
+    total_out = 0;
+    const int n_kt = (E.V + hpgv::EPI_TJ - 1) / hpgv::EPI_TJ;
+    n_jb = (E.V + tj - 1) / tj;
     std::vector<unsigned> jbp((size_t)n_jb + 1), rb((size_t)n_i + 1);
     unsigned long long acc = 0;
-    for (int jb = 0; jb < n_jb; ++jb) { jbp[(size_t)jb] = (unsigned)acc; acc += (unsigned long long)std::max(0, n_kt - ((4 * jb + 1) >> 6)); }
+    for (int jb = 0; jb < n_jb; ++jb) { jbp[(size_t)jb] = (unsigned)acc; acc += (unsigned long long)std::max(0, n_kt - ((tj * jb + 1) >> 6)); }
     jbp[(size_t)n_jb] = (unsigned)acc;
     if (acc > 0x7FFFFFFFull) return fail(ctx, HPGV_ERR_UNSUPPORTED, "too many SNPs for the triple scan");
     unsigned long long total = 0;
     for (int r = 0; r < n_i; ++r) {
         rb[(size_t)r] = (unsigned)total;
-        const int jb_min = std::min(n_jb, (i_first + r + 1) >> 2);
-        total += acc - jbp[(size_t)jb_min];
+        total += acc - jbp[(size_t)std::min(n_jb, (i_first + r + 1) / tj)];
     }
     rb[(size_t)n_i] = (unsigned)total;
     if (total > (0x7FFFFFFFull >> 8)) return fail(ctx, HPGV_ERR_UNSUPPORTED, "too many first SNPs for one launch of the triple scan");
     if (total == 0) return HPGV_OK;
-    const size_t need = jbp.size() + rb.size();
-    if (E.tile_base_cap < need) {
-        if (E.d_tile_base) (void)hipFree(E.d_tile_base);
-        E.d_tile_base = nullptr; E.tile_base_cap = 0;
-        HIPCHK(ctx, hipMalloc(&E.d_tile_base, (need + 64) * sizeof(unsigned)));
-        E.tile_base_cap = need + 64;
-    }
-    unsigned *d_jbp = E.d_tile_base, *d_rb = E.d_tile_base + jbp.size();
+    if (int rc = epi_tile_room(ctx, jbp.size() + rb.size())) return rc;
+    d_jbp = E.d_tile_base; d_rb = E.d_tile_base + jbp.size();
     HIPCHK(ctx, hipMemcpyAsync(d_jbp, jbp.data(), jbp.size() * sizeof(unsigned), hipMemcpyHostToDevice, nullptr));
     HIPCHK(ctx, hipMemcpyAsync(d_rb, rb.data(), rb.size() * sizeof(unsigned), hipMemcpyHostToDevice, nullptr));
+    total_out = (unsigned)total;
+    return HPGV_OK;
+}
+
+template <bool TRAINING>
+int epi_launch_triples(hpgv_ctx *ctx, int i_first, int n_i, double *d_acc, uint32_t *d_mask, bool candidates,
+                       hpgv::EpiCand3 *d_cand, unsigned cap) {
+    EpiState &E = ctx->epi;
+    if (int rc = epi_upload_folds(ctx, TRAINING, nullptr)) return rc;
     const bool balanced = E.nA == E.nU && E.nA < (1 << 22);
     // ranking, classes below 65 536 samples: the cell counts on the matrix cores (hpgv_epi_mfma_kernels.h:
     // k_epi_triples_mfma), tiles of one first SNP x 16 second x 64 third
-    if (ctx->epi_triples_mfma && candidates && !d_acc && E.rev_off && E.n_chunks <= hpgv::EPM_MAX_CHUNKS && E.nA < 65536 && E.nU < 65536) {
-        const int n_jb16 = (E.V + hpgv::EPM_TI - 1) / hpgv::EPM_TI;
-        std::vector<unsigned> jbp16((size_t)n_jb16 + 1), rb16((size_t)n_i + 1);
-        unsigned long long acc16 = 0;
-        for (int jb = 0; jb < n_jb16; ++jb) { jbp16[(size_t)jb] = (unsigned)acc16; acc16 += (unsigned long long)std::max(0, n_kt - ((hpgv::EPM_TI * jb + 1) >> 6)); }
-        jbp16[(size_t)n_jb16] = (unsigned)acc16;
-        unsigned long long total16 = 0;
-        for (int r = 0; r < n_i; ++r) {
-            rb16[(size_t)r] = (unsigned)total16;
-            total16 += acc16 - jbp16[(size_t)std::min(n_jb16, (i_first + r + 1) >> 4)];
-        }
-        rb16[(size_t)n_i] = (unsigned)total16;
-        if (total16 == 0) return HPGV_OK;
-        if (total16 > (0x7FFFFFFFull >> 8)) return fail(ctx, HPGV_ERR_UNSUPPORTED, "too many first SNPs for one launch of the triple scan");
-        HIPCHK(ctx, hipMemcpyAsync(d_jbp, jbp16.data(), jbp16.size() * sizeof(unsigned), hipMemcpyHostToDevice, nullptr));    // (no longer than the lists above: same buffer)
-        HIPCHK(ctx, hipMemcpyAsync(d_rb, rb16.data(), rb16.size() * sizeof(unsigned), hipMemcpyHostToDevice, nullptr));
+    const bool mfma = ctx->epi_triples_mfma && candidates && !d_acc && E.rev_off && E.n_chunks <= hpgv::EPM_MAX_CHUNKS && E.nA < 65536 && E.nU < 65536;
+    int n_jb = 0;
+    unsigned total = 0;
+    unsigned *d_jbp = nullptr, *d_rb = nullptr;
+    if (int rc = epi_triple_tiles(ctx, mfma ? hpgv::EPM_TI : hpgv::EPI_TI, i_first, n_i, n_jb, total, d_jbp, d_rb)) return rc;
+    if (!total) return HPGV_OK;
+    if (mfma) {
         epi_note_launch(E, HPGV_EPI_KERNEL_TRIPLES_MFMA);
 #define HPGV_EPM3_LAUNCH(KK, BAL)                                                                                                               \
-        hipLaunchKernelGGL((hpgv::k_epi_triples_mfma<KK, TRAINING, BAL>), dim3((unsigned)total16), dim3(256), 0, nullptr, E.d_planes, E.rev_off, E.W, E.V, i_first, d_rb, n_i, \
-                           d_jbp, n_jb16, E.d_chunks, E.n_chunks, E.d_folds, E.num_folds, E.nA, E.nU, E.d_thr, d_cand, E.d_cand_count, cap)
+        hipLaunchKernelGGL((hpgv::k_epi_triples_mfma<KK, TRAINING, BAL>), dim3(total), dim3(256), 0, nullptr, E.d_planes, E.rev_off, E.W, E.V, i_first, d_rb, n_i, \
+                           d_jbp, n_jb, E.d_chunks, E.n_chunks, E.d_folds, E.num_folds, E.nA, E.nU, E.d_thr, d_cand, E.d_cand_count, cap)
         if (E.num_folds <= 5) { if (balanced) HPGV_EPM3_LAUNCH(5, true); else HPGV_EPM3_LAUNCH(5, false); }
         else if (E.num_folds <= 10) { if (balanced) HPGV_EPM3_LAUNCH(10, true); else HPGV_EPM3_LAUNCH(10, false); }
         else { if (balanced) HPGV_EPM3_LAUNCH(16, true); else HPGV_EPM3_LAUNCH(16, false); }      // one wave per SIMD
@@ -644,7 +573,7 @@ int epi_launch_triples(hpgv_ctx *ctx, int i_first, int n_i, double *d_acc, uint3
         HIPCHK(ctx, hipGetLastError());
         return HPGV_OK;
     }
-    const dim3 grid((unsigned)total);
+    const dim3 grid(total);
     // ranking, at most 10 folds, classes below 65 536 samples: the 27 cells nine at a time (hpgv_epi_triples3_kernels.h): three walks
     // over the samples with a third of the state each, three waves per SIMD
     if (ctx->epi_triples_1pass == 1 && candidates && !d_acc && E.num_folds <= 10 && E.nA < 65536 && E.nU < 65536) {
@@ -686,8 +615,7 @@ int epi_launch_triples(hpgv_ctx *ctx, int i_first, int n_i, double *d_acc, uint3
 
 int epi_triples_check(hpgv_ctx *ctx, int subset) {
     EpiState &E = ctx->epi;
-    if (!E.have_folds) return fail(ctx, HPGV_ERR_STATE, "no folds: hpgv_epi_set_dataset has not been called, or a class of 65536 samples or more waits for hpgv_epi_set_folds");
-    if (subset != HPGV_EPI_TESTING && subset != HPGV_EPI_TRAINING) return fail(ctx, HPGV_ERR_INVALID, "subset must be HPGV_EPI_TESTING or HPGV_EPI_TRAINING");
+    if (int rc = epi_check(ctx, subset)) return rc;
     if (E.nA > 65535 || E.nU > 65535) return fail(ctx, HPGV_ERR_UNSUPPORTED, "the triple scan keeps 16-bit totals: at most 65535 samples per class");
     for (int f = 0; f < E.num_folds; ++f)
         if (E.group_size[(size_t)2 * f] + E.group_size[(size_t)2 * f + 1] == 0)
@@ -695,9 +623,43 @@ int epi_triples_check(hpgv_ctx *ctx, int subset) {
     return HPGV_OK;
 }
 
+// Triples.  First SNPs from the LAST one down: a first SNP i begins (V - i - 1)(V - i - 2) / 2 triples, so the first launches list
+// a handful of models each and leave thresholds behind for the long rows (from the first SNP up, the very first launch listed
+// every triple of SNP 0 -- half a million models per fold at 1 024 SNPs, 125 MB over the bus and a sort: 50 ms of a 130 ms call).
+struct EpiTripleOrder : EpiTileOrder<hpgv::EpiCand3> {
+    int step = 1, n_i = 0, max_rows = 1;
+    EpiTripleOrder(hpgv_ctx *c, int subset, int begin, int end)
+        : EpiTileOrder(c, subset, begin, std::min<long long>(c->epi.V - 2, end)) {}      // first SNPs V - 2 and V - 1 begin no triple
+    int setup() {
+        // one first SNP i gives (V - i - 1)(V - i - 2) / 2 triples; a launch without thresholds lists them all
+        const unsigned long long per_i0 = V > 2 ? (unsigned long long)(V - 1) * (unsigned long long)(V - 2) / 2 : 1;
+        if (per_i0 > (1ull << 28)) return fail(ctx, HPGV_ERR_UNSUPPORTED, "too many SNPs for the candidate lists of the triple scan");
+        // a launch stays below 2^23 tiles: at most n_jb * n_kt tiles per first SNP
+        const long long per_row_tiles = ((V + hpgv::EPI_TI - 1) / hpgv::EPI_TI) * ((V + hpgv::EPI_TJ - 1) / hpgv::EPI_TJ) + 1;
+        max_rows = (int)std::max<long long>(1, (1ll << 23) / per_row_tiles);
+        return room((size_t)E.num_folds, (unsigned)std::max<unsigned long long>(1ull << 20, per_i0));
+    }
+    int launch() {
+        n_i = (int)std::min<long long>(std::min<long long>(step, max_rows), hi - i_begin);
+        return training ? epi_launch_triples<true>(ctx, (int)hi - n_i, n_i, nullptr, nullptr, true, d_cand, cap)
+                        : epi_launch_triples<false>(ctx, (int)hi - n_i, n_i, nullptr, nullptr, true, d_cand, cap);
+    }
+    int shrink() {                                                   // the same first SNPs again, fewer at a time
+        if (n_i <= 1) return fail(ctx, HPGV_ERR_UNSUPPORTED, "more than %u models of one first SNP reach a fold's threshold", cap);
+        step = std::max(1, n_i / 2);
+        return HPGV_OK;
+    }
+    int advance(unsigned worst) {
+        hi -= n_i;
+        if (worst < cap / 8 && step < 4096) step *= 2;
+        return HPGV_OK;
+    }
+};
+
 }  // namespace
 
 int hpgv_epi_scan_triples(hpgv_ctx *ctx, int subset, double *accuracy, uint32_t *risky_mask) {
+    HPGV_ABI_TRY
     ctx = first_member(ctx);
     if (!ctx) return HPGV_ERR_INVALID;
     int rc = epi_triples_check(ctx, subset);
@@ -709,22 +671,21 @@ int hpgv_epi_scan_triples(hpgv_ctx *ctx, int subset, double *accuracy, uint32_t 
     std::lock_guard<std::mutex> lk(ctx->epi_mu);
     const size_t V = (size_t)E.V, total = (size_t)E.num_folds * V * V * V;
     if (total == 0) return HPGV_OK;
-    double *d_acc = nullptr; uint32_t *d_mask = nullptr;
-    HIPCHK(ctx, hipMalloc(&d_acc, total * sizeof(double)));
-    hipError_t e = hipMalloc(&d_mask, total * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemset(d_acc, 0xFF, total * sizeof(double));            // cells that are no triple i < j < k read as NaN
-    if (e == hipSuccess) e = hipMemset(d_mask, 0, total * sizeof(uint32_t));
-    if (e == hipSuccess) {
-        rc = subset == HPGV_EPI_TRAINING ? epi_launch_triples<true>(ctx, 0, E.V, d_acc, d_mask, false, nullptr, 0)
-                                         : epi_launch_triples<false>(ctx, 0, E.V, d_acc, d_mask, false, nullptr, 0);
-        if (!rc) e = hipMemcpy(accuracy, d_acc, total * sizeof(double), hipMemcpyDeviceToHost);
-        if (!rc && e == hipSuccess) e = hipMemcpy(risky_mask, d_mask, total * sizeof(uint32_t), hipMemcpyDeviceToHost);
-    }
-    (void)hipFree(d_acc);
-    if (d_mask) (void)hipFree(d_mask);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(ctx, HPGV_ERR_HIP, "epistasis triple scan failed: %s", hipGetErrorString(e));
-    return HPGV_OK;
+    return epi_dense_scan(ctx, total, true, accuracy, risky_mask, "triple", [&](double *d_acc, uint32_t *d_mask) {      // cells that are no triple i < j < k read as NaN
+        return subset == HPGV_EPI_TRAINING ? epi_launch_triples<true>(ctx, 0, E.V, d_acc, d_mask, false, nullptr, 0)
+                                           : epi_launch_triples<false>(ctx, 0, E.V, d_acc, d_mask, false, nullptr, 0);
+    });
+    HPGV_ABI_CATCH(ctx)
+}
+
+int hpgv_epi_triples_models(hpgv_ctx *ctx, int i_begin, int i_end, int subset, int N, bool have_outputs, std::vector<EpiModel> &out, float *scan_ms) {
+    if (int rc = epi_triples_check(ctx, subset)) return rc;
+    if (i_begin < 0 || i_end < i_begin || i_end > ctx->epi.V) return fail(ctx, HPGV_ERR_INVALID, "first SNPs [%d, %d) outside the dataset", i_begin, i_end);
+    if (N < 1 || N > 65536 || !have_outputs) return fail(ctx, HPGV_ERR_INVALID, "bad ranking arguments");
+    DeviceGuard g(ctx->device);
+    std::lock_guard<std::mutex> lk(ctx->epi_mu);
+    EpiTripleOrder o(ctx, subset, i_begin, i_end);
+    return epi_rank_loop(ctx, o, N, out, scan_ms);
 }
 
 int hpgv_epi_rank_triples(hpgv_ctx *ctx, int subset, int max_ranking_size, int32_t *comb_i, int32_t *comb_j, int32_t *comb_k,
@@ -738,98 +699,10 @@ int hpgv_epi_rank_triples_rows(hpgv_ctx *ctx, int i_begin, int i_end, int subset
     HPGV_ABI_TRY
     ctx = first_member(ctx);
     if (!ctx) return HPGV_ERR_INVALID;
-    int rc = epi_triples_check(ctx, subset);
-    if (rc) return rc;
-    EpiState &E = ctx->epi;
-    if (i_begin < 0 || i_end < i_begin || i_end > E.V) return fail(ctx, HPGV_ERR_INVALID, "first SNPs [%d, %d) outside the dataset", i_begin, i_end);
-    if (max_ranking_size < 1 || max_ranking_size > 65536 || !comb_i || !comb_j || !comb_k || !accuracy || !risky_mask || !n_ranked)
-        return fail(ctx, HPGV_ERR_INVALID, "bad ranking arguments");
-    DeviceGuard g(ctx->device);
-    std::lock_guard<std::mutex> lk(ctx->epi_mu);
-    E.rank_info = hpgv_epi_rank_info{};
-    const int nf = E.num_folds, N = max_ranking_size;
-    const long long V = E.V;
-    // one first SNP i gives (V - i - 1)(V - i - 2) / 2 triples; a launch without thresholds lists them all
-    const unsigned long long per_i0 = V > 2 ? (unsigned long long)(V - 1) * (unsigned long long)(V - 2) / 2 : 1;
-    if (per_i0 > (1ull << 28)) return fail(ctx, HPGV_ERR_UNSUPPORTED, "too many SNPs for the candidate lists of the triple scan");
-    const unsigned cap = (unsigned)std::max<unsigned long long>(1ull << 20, per_i0);
-    if (!E.d_cand3 || E.cand3_cap < (size_t)nf * cap) {              // (kept between calls: 240 MB at 1 024 SNPs)
-        if (E.d_cand3) (void)hipFree(E.d_cand3);
-        E.d_cand3 = nullptr; E.cand3_cap = 0;
-        HIPCHK(ctx, hipMalloc(&E.d_cand3, (size_t)nf * cap * sizeof(hpgv::EpiCand3)));
-        E.cand3_cap = (size_t)nf * cap;
-    }
-    hpgv::EpiCand3 *d_cand = E.d_cand3;
-    if (!E.d_cand_count) HIPCHK(ctx, hipMalloc(&E.d_cand_count, hpgv::EPI_MAX_FOLDS * sizeof(unsigned)));
-    if (!E.d_thr) HIPCHK(ctx, hipMalloc(&E.d_thr, hpgv::EPI_MAX_FOLDS * sizeof(double)));
-    std::vector<std::vector<hpgv::EpiCand3>> top((size_t)nf);
-    std::vector<double> thr(hpgv::EPI_MAX_FOLDS, -HUGE_VAL);
-    std::vector<unsigned> count(hpgv::EPI_MAX_FOLDS);
-    std::vector<hpgv::EpiCand3> buf;
-    auto better = [](const hpgv::EpiCand3 &a, const hpgv::EpiCand3 &b) {
-        if (a.accuracy != b.accuracy) return a.accuracy > b.accuracy;
-        if (a.i != b.i) return a.i < b.i;
-        if (a.j != b.j) return a.j < b.j;
-        return a.k < b.k;
-    };
-    EventPair evs;                                                   // destroyed on every return path
-    hipEvent_t &ev0 = evs.a, &ev1 = evs.b;
-    float total_ms = 0.f;
-    if (scan_ms) { HIPCHK(ctx, hipEventCreate(&ev0)); HIPCHK(ctx, hipEventCreate(&ev1)); }
-    // a launch stays below 2^23 tiles: at most n_jb * n_kt tiles per first SNP
-    const long long per_row_tiles = ((V + hpgv::EPI_TI - 1) / hpgv::EPI_TI) * ((V + hpgv::EPI_TJ - 1) / hpgv::EPI_TJ) + 1;
-    const int max_rows = (int)std::max<long long>(1, (1ll << 23) / per_row_tiles);
-    const long long i_last = std::min<long long>(V - 2, i_end);    // first SNPs V - 2 and V - 1 begin no triple
-    // From the LAST first SNP down: a first SNP i begins (V - i - 1)(V - i - 2) / 2 triples, so the first launches list a handful
-    // of models each and leave thresholds behind for the long rows (from the first SNP up, the very first launch listed every
-    // triple of SNP 0 -- half a million models per fold at 1 024 SNPs, 125 MB over the bus and a sort: 50 ms of a 130 ms call).
-    // The order of the launches does not show in the ranking: ties go by (i, j, k).
-    long long hi = i_last;
-    int step = 1;
-    while (hi > i_begin && !rc) {
-        const int n_i = (int)std::min<long long>(std::min<long long>(step, max_rows), hi - i_begin);
-        const int i = (int)(hi - n_i);
-        HIPCHK(ctx, hipMemsetAsync(E.d_cand_count, 0, hpgv::EPI_MAX_FOLDS * sizeof(unsigned), nullptr));
-        HIPCHK(ctx, hipMemcpyAsync(E.d_thr, thr.data(), hpgv::EPI_MAX_FOLDS * sizeof(double), hipMemcpyHostToDevice, nullptr));
-        if (scan_ms) HIPCHK(ctx, hipEventRecord(ev0, nullptr));
-        rc = subset == HPGV_EPI_TRAINING ? epi_launch_triples<true>(ctx, i, n_i, nullptr, nullptr, true, d_cand, cap)
-                                         : epi_launch_triples<false>(ctx, i, n_i, nullptr, nullptr, true, d_cand, cap);
-        if (rc) break;
-        if (scan_ms) HIPCHK(ctx, hipEventRecord(ev1, nullptr));
-        HIPCHK(ctx, hipMemcpy(count.data(), E.d_cand_count, hpgv::EPI_MAX_FOLDS * sizeof(unsigned), hipMemcpyDeviceToHost));
-        if (scan_ms) { float ms = 0.f; HIPCHK(ctx, hipEventElapsedTime(&ms, ev0, ev1)); total_ms += ms; }
-        unsigned worst = 0;
-        for (int f = 0; f < nf; ++f) worst = std::max(worst, count[(size_t)f]);
-        if (worst > cap) {                                           // a list overflowed: the same first SNPs again, fewer at a time
-            ++E.rank_info.relaunches;
-            if (n_i <= 1) { rc = fail(ctx, HPGV_ERR_UNSUPPORTED, "more than %u models of one first SNP reach a fold's threshold", cap); break; }
-            step = std::max(1, n_i / 2);
-            continue;
-        }
-        for (int f = 0; f < nf && !rc; ++f) {
-            const unsigned n = count[(size_t)f];
-            if (!n) continue;
-            buf.resize(n);
-            HIPCHK(ctx, hipMemcpy(buf.data(), d_cand + (size_t)f * cap, (size_t)n * sizeof(hpgv::EpiCand3), hipMemcpyDeviceToHost));
-            auto &t = top[(size_t)f];
-            t.insert(t.end(), buf.begin(), buf.end());
-            if ((int)t.size() > N) { std::partial_sort(t.begin(), t.begin() + N, t.end(), better); t.resize((size_t)N); }
-            else std::sort(t.begin(), t.end(), better);
-            if ((int)t.size() >= N && t.back().accuracy > thr[(size_t)f]) thr[(size_t)f] = t.back().accuracy;
-        }
-        hi = i;
-        if (worst < cap / 8 && step < 4096) step *= 2;
-    }
-    if (rc) return rc;
-    for (int f = 0; f < nf; ++f) {
-        const auto &t = top[(size_t)f];
-        n_ranked[f] = (int32_t)t.size();
-        for (size_t e = 0; e < t.size(); ++e) {
-            comb_i[(size_t)f * N + e] = t[e].i; comb_j[(size_t)f * N + e] = t[e].j; comb_k[(size_t)f * N + e] = t[e].k;
-            accuracy[(size_t)f * N + e] = t[e].accuracy; risky_mask[(size_t)f * N + e] = t[e].risky;
-        }
-    }
-    if (scan_ms) *scan_ms = total_ms;
+    std::vector<EpiModel> m;
+    if (int rc = hpgv_epi_triples_models(ctx, i_begin, i_end, subset, max_ranking_size, comb_i && comb_j && comb_k && accuracy && risky_mask && n_ranked, m, scan_ms)) return rc;
+    int32_t *const comb[3] = {comb_i, comb_j, comb_k};
+    epi_scatter(m, max_ranking_size, 3, comb, 1, accuracy, risky_mask, 1, n_ranked);
     return HPGV_OK;
     HPGV_ABI_CATCH(ctx)
 }

@@ -4,34 +4,15 @@
 // counts behind hpgv_epi_counts / hpgv_epi_counts_all_folds for the orders the pair / triple kernels do not take.
 // Kernel: hpgv_epi_generic_kernels.h (one lane per cell).  Its own translation unit: the pair and triple scans of
 // hpgv_epi_capi.hip compile for minutes.
-#include "hpgv_internal.h"
+#include "hpgv_epi_host.h"
 #include "hpgv_epi_generic_kernels.h"
 
 namespace {
 
-struct EventPair2 {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~EventPair2() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-};
-struct DevFree { void *p = nullptr; ~DevFree() { if (p) (void)hipFree(p); } };
-
 int generic_check(hpgv_ctx *ctx, int order) {
     EpiState &E = ctx->epi;
-    if (!E.have_folds) return fail(ctx, HPGV_ERR_STATE, "no folds: hpgv_epi_set_dataset has not been called, or a class of 65536 samples or more waits for hpgv_epi_set_folds");
     if (order < 2 || order > 5) return fail(ctx, HPGV_ERR_UNSUPPORTED, "combinations of %d SNPs are not supported (2 to 5)", order);
     if (E.nA > 65535 || E.nU > 65535) return fail(ctx, HPGV_ERR_UNSUPPORTED, "the listed-combination kernel keeps 16-bit class totals: at most 65535 samples per class");
-    return HPGV_OK;
-}
-
-int upload_folds(hpgv_ctx *ctx, bool training) {
-    EpiState &E = ctx->epi;
-    hpgv::EpiFold folds[hpgv::EPI_MAX_FOLDS];
-    for (int f = 0; f < hpgv::EPI_MAX_FOLDS; ++f) {
-        folds[f].test_a = E.group_size[(size_t)2 * f]; folds[f].test_u = E.group_size[(size_t)2 * f + 1];
-        const int sa = training ? E.nA - folds[f].test_a : folds[f].test_a, su = training ? E.nU - folds[f].test_u : folds[f].test_u;
-        folds[f].inv_a = 1.0 / (double)sa; folds[f].inv_u = 1.0 / (double)su;
-    }
-    HIPCHK(ctx, hipMemcpyAsync(E.d_folds, folds, sizeof folds, hipMemcpyHostToDevice, nullptr));
     return HPGV_OK;
 }
 
@@ -72,6 +53,54 @@ bool next_comb(int32_t *c, int order, int V) {
     return true;
 }
 
+// Any order.  Every combination is listed, in lexicographic order, `limit` of them per launch = at most the capacity of a fold's
+// candidate list, so no list overflows.  The first launch has no thresholds and lists every combination it evaluates: a short
+// one, so that the long ones that follow have bounds to filter with (131 072 models x folds x 64 bytes over the bus and a sort
+// otherwise).
+struct EpiListOrder {
+    using Cand = hpgv::EpiCandN;
+    static constexpr unsigned CHUNK = 1u << 17;
+    hpgv_ctx *ctx; EpiState &E; const int order, i_end; const bool training;
+    Cand *d_cand = nullptr; unsigned cap = CHUNK;
+    DevFree dc, dcand;
+    std::vector<int32_t> list;                                       // the launch's combinations
+    int32_t cur[5];                                                  // the next one
+    bool any;
+    unsigned n = 0, limit;
+    EpiListOrder(hpgv_ctx *c, int order_, int i_begin, int i_end_, int subset, int N)
+        : ctx(c), E(c->epi), order(order_), i_end(i_end_), training(subset == HPGV_EPI_TRAINING),
+          any(!(E.V < order || i_begin >= i_end || i_begin > E.V - order)), limit(std::min<unsigned>(CHUNK, (unsigned)std::max(4096, 4 * N))) {
+        for (int s = 0; s < 5; ++s) cur[s] = i_begin + s;
+    }
+    int setup() {
+        if (!any) return HPGV_OK;
+        HIPCHK(ctx, hipMalloc(&dc.p, (size_t)CHUNK * (size_t)order * sizeof(int32_t)));
+        HIPCHK(ctx, hipMalloc(&dcand.p, (size_t)E.num_folds * CHUNK * sizeof(Cand)));
+        d_cand = (Cand *)dcand.p;
+        list.resize((size_t)CHUNK * (size_t)order);
+        if (int rc = epi_upload_folds(ctx, training, nullptr)) return rc;
+        return stage();
+    }
+    int stage() {                                                    // the next launch's list, on the device before its launch is timed
+        for (n = 0; any && n < limit; ++n) {
+            std::copy(cur, cur + order, &list[(size_t)n * (size_t)order]);
+            any = next_comb(cur, order, E.V) && cur[0] < i_end;
+        }
+        if (n) HIPCHK(ctx, hipMemcpyAsync(dc.p, list.data(), (size_t)n * (size_t)order * sizeof(int32_t), hipMemcpyHostToDevice, nullptr));
+        return HPGV_OK;
+    }
+    bool more() const { return n > 0; }
+    int launch() { return launch_combs(ctx, order, training, (const int32_t *)dc.p, (int)n, nullptr, true, nullptr, nullptr, E.d_thr, d_cand, E.d_cand_count, CHUNK); }
+    int shrink() { return fail(ctx, HPGV_ERR_UNSUPPORTED, "a launch of %u listed combinations overflowed a candidate list", n); }
+    int advance(unsigned) { limit = CHUNK; return stage(); }
+    EpiModel keep(const Cand &e) const {
+        EpiModel m{e.accuracy, {-1, -1, -1, -1, -1}, 1, {}};
+        std::copy(&list[(size_t)e.index * (size_t)order], &list[(size_t)e.index * (size_t)order] + order, m.c);
+        std::copy(e.risky, e.risky + hpgv::EPI_MASK_WORDS, m.risky);
+        return m;
+    }
+};
+
 }  // namespace
 
 // in-fold counts of listed combinations, device to device: d_out[(comb * n_groups + g) * 3^order + cell] (epi_infold_counts of
@@ -90,10 +119,11 @@ int hpgv_epi_eval_combs(hpgv_ctx *ctx, int order, const int32_t *combs, int n_co
     if (!ctx) return HPGV_ERR_INVALID;
     DeviceGuard g(ctx->device);
     std::lock_guard<std::mutex> lk(ctx->epi_mu);
-    int rc = generic_check(ctx, order);
+    int rc = epi_check_folds(ctx);
+    if (!rc) rc = generic_check(ctx, order);
+    if (!rc) rc = epi_check_subset(ctx, subset);
     if (rc) return rc;
     EpiState &E = ctx->epi;
-    if (subset != HPGV_EPI_TESTING && subset != HPGV_EPI_TRAINING) return fail(ctx, HPGV_ERR_INVALID, "subset must be HPGV_EPI_TESTING or HPGV_EPI_TRAINING");
     if (n_combs < 0 || (n_combs > 0 && (!combs || !accuracy))) return fail(ctx, HPGV_ERR_INVALID, "bad combination list");
     for (long k = 0; k < (long)n_combs * order; ++k)
         if (combs[k] < 0 || combs[k] >= E.V) return fail(ctx, HPGV_ERR_INVALID, "SNP index %d outside the dataset", combs[k]);
@@ -106,7 +136,7 @@ int hpgv_epi_eval_combs(hpgv_ctx *ctx, int order, const int32_t *combs, int n_co
     HIPCHK(ctx, hipMemcpy(dc.p, combs, n * (size_t)order * sizeof(int32_t), hipMemcpyHostToDevice));
     HIPCHK(ctx, hipMemset(da.p, 0xFF, n * nf * sizeof(double)));      // (a fold without samples keeps NaN)
     if (dm.p) HIPCHK(ctx, hipMemset(dm.p, 0, n * nf * hpgv::EPI_MASK_WORDS * sizeof(uint32_t)));
-    rc = upload_folds(ctx, subset == HPGV_EPI_TRAINING);
+    rc = epi_upload_folds(ctx, subset == HPGV_EPI_TRAINING, nullptr);
     if (rc) return rc;
     rc = launch_combs(ctx, order, subset == HPGV_EPI_TRAINING, (const int32_t *)dc.p, n_combs, nullptr, true, (double *)da.p, (uint32_t *)dm.p,
                       nullptr, nullptr, nullptr, 0);
@@ -122,96 +152,10 @@ int hpgv_epi_rank_order_rows(hpgv_ctx *ctx, int order, int i_begin, int i_end, i
     HPGV_ABI_TRY
     ctx = first_member(ctx);
     if (!ctx) return HPGV_ERR_INVALID;
-    DeviceGuard g(ctx->device);
-    std::lock_guard<std::mutex> lk(ctx->epi_mu);
-    int rc = generic_check(ctx, order);
-    if (rc) return rc;
-    EpiState &E = ctx->epi;
-    if (subset != HPGV_EPI_TESTING && subset != HPGV_EPI_TRAINING) return fail(ctx, HPGV_ERR_INVALID, "subset must be HPGV_EPI_TESTING or HPGV_EPI_TRAINING");
-    if (i_begin < 0 || i_end < i_begin || i_end > E.V) return fail(ctx, HPGV_ERR_INVALID, "first SNPs [%d, %d) outside the dataset", i_begin, i_end);
-    if (max_ranking_size < 1 || max_ranking_size > 65536 || !combs_out || !accuracy || !risky_mask || !n_ranked)
-        return fail(ctx, HPGV_ERR_INVALID, "bad ranking arguments");
-    E.rank_info = hpgv_epi_rank_info{};
-    const int nf = E.num_folds, N = max_ranking_size, V = E.V;
-    struct Model { double accuracy; unsigned long long rank; int32_t c[5]; uint32_t risky[hpgv::EPI_MASK_WORDS]; };
-    std::vector<std::vector<Model>> top((size_t)nf);
-    // listed in lexicographic order, so the position in the listing IS the tie-break of add_to_model_ranking
-    // (model.c:478-517: higher accuracy, then the smaller combination)
-    auto better = [](const Model &a, const Model &b) { return a.accuracy != b.accuracy ? a.accuracy > b.accuracy : a.rank < b.rank; };
-    for (int f = 0; f < nf; ++f) n_ranked[f] = 0;
-    if (V < order || i_begin >= i_end || i_begin > V - order) { if (scan_ms) *scan_ms = 0.f; return HPGV_OK; }
-    constexpr unsigned CHUNK = 1u << 17;                             // combinations per launch = capacity of a fold's candidate list
-    DevFree dc, dcand, dcount, dthr;
-    HIPCHK(ctx, hipMalloc(&dc.p, (size_t)CHUNK * (size_t)order * sizeof(int32_t)));
-    HIPCHK(ctx, hipMalloc(&dcand.p, (size_t)nf * CHUNK * sizeof(hpgv::EpiCandN)));
-    HIPCHK(ctx, hipMalloc(&dcount.p, hpgv::EPI_MAX_FOLDS * sizeof(unsigned)));
-    HIPCHK(ctx, hipMalloc(&dthr.p, hpgv::EPI_MAX_FOLDS * sizeof(double)));
-    rc = upload_folds(ctx, subset == HPGV_EPI_TRAINING);
-    if (rc) return rc;
-    std::vector<int32_t> list((size_t)CHUNK * (size_t)order);
-    std::vector<double> thr(hpgv::EPI_MAX_FOLDS, -HUGE_VAL);
-    std::vector<unsigned> count(hpgv::EPI_MAX_FOLDS);
-    std::vector<hpgv::EpiCandN> buf;
-    EventPair2 evs;
-    float total_ms = 0.f;
-    if (scan_ms) { HIPCHK(ctx, hipEventCreate(&evs.a)); HIPCHK(ctx, hipEventCreate(&evs.b)); }
-    int32_t cur[5];
-    for (int s = 0; s < order; ++s) cur[s] = i_begin + s;
-    bool more = true;
-    unsigned long long listed = 0;
-    // the first launch has no thresholds and lists every combination it evaluates: a short one, so that the long ones that follow
-    // have bounds to filter with (131 072 models x folds x 64 bytes over the bus and a sort otherwise)
-    unsigned limit = std::min<unsigned>(CHUNK, (unsigned)std::max(4096, 4 * N));
-    while (more) {
-        unsigned n = 0;
-        while (more && n < limit && cur[0] < i_end) {
-            for (int s = 0; s < order; ++s) list[(size_t)n * (size_t)order + (size_t)s] = cur[s];
-            ++n;
-            more = next_comb(cur, order, V);
-        }
-        if (cur[0] >= i_end) more = false;
-        if (n == 0) break;
-        HIPCHK(ctx, hipMemcpyAsync(dc.p, list.data(), (size_t)n * (size_t)order * sizeof(int32_t), hipMemcpyHostToDevice, nullptr));
-        HIPCHK(ctx, hipMemsetAsync(dcount.p, 0, hpgv::EPI_MAX_FOLDS * sizeof(unsigned), nullptr));
-        HIPCHK(ctx, hipMemcpyAsync(dthr.p, thr.data(), hpgv::EPI_MAX_FOLDS * sizeof(double), hipMemcpyHostToDevice, nullptr));
-        if (scan_ms) HIPCHK(ctx, hipEventRecord(evs.a, nullptr));
-        rc = launch_combs(ctx, order, subset == HPGV_EPI_TRAINING, (const int32_t *)dc.p, (int)n, nullptr, true, nullptr, nullptr,
-                          (const double *)dthr.p, (hpgv::EpiCandN *)dcand.p, (unsigned *)dcount.p, CHUNK);
-        if (rc) return rc;
-        if (scan_ms) HIPCHK(ctx, hipEventRecord(evs.b, nullptr));
-        HIPCHK(ctx, hipMemcpy(count.data(), dcount.p, hpgv::EPI_MAX_FOLDS * sizeof(unsigned), hipMemcpyDeviceToHost));
-        if (scan_ms) { float ms = 0.f; HIPCHK(ctx, hipEventElapsedTime(&ms, evs.a, evs.b)); total_ms += ms; }
-        for (int f = 0; f < nf; ++f) {
-            const unsigned m = std::min(count[(size_t)f], CHUNK);      // (a list holds every combination of a launch: it cannot overflow)
-            if (!m) continue;
-            buf.resize(m);
-            HIPCHK(ctx, hipMemcpy(buf.data(), (hpgv::EpiCandN *)dcand.p + (size_t)f * CHUNK, (size_t)m * sizeof(hpgv::EpiCandN), hipMemcpyDeviceToHost));
-            auto &t = top[(size_t)f];
-            for (const hpgv::EpiCandN &e : buf) {
-                Model md;
-                md.accuracy = e.accuracy; md.rank = listed + e.index;
-                for (int s = 0; s < 5; ++s) md.c[s] = s < order ? list[(size_t)e.index * (size_t)order + (size_t)s] : -1;
-                for (int w = 0; w < hpgv::EPI_MASK_WORDS; ++w) md.risky[w] = e.risky[w];
-                t.push_back(md);
-            }
-            if ((int)t.size() > N) { std::partial_sort(t.begin(), t.begin() + N, t.end(), better); t.resize((size_t)N); }
-            else std::sort(t.begin(), t.end(), better);
-            if ((int)t.size() >= N && t.back().accuracy > thr[(size_t)f]) thr[(size_t)f] = t.back().accuracy;
-        }
-        listed += n;
-        limit = CHUNK;
-    }
-    for (int f = 0; f < nf; ++f) {
-        const auto &t = top[(size_t)f];
-        n_ranked[f] = (int32_t)t.size();
-        for (size_t e = 0; e < t.size(); ++e) {
-            const size_t o = (size_t)f * (size_t)N + e;
-            for (int s = 0; s < order; ++s) combs_out[o * (size_t)order + (size_t)s] = t[e].c[s];
-            accuracy[o] = t[e].accuracy;
-            for (int w = 0; w < hpgv::EPI_MASK_WORDS; ++w) risky_mask[o * hpgv::EPI_MASK_WORDS + (size_t)w] = t[e].risky[w];
-        }
-    }
-    if (scan_ms) *scan_ms = total_ms;
+    std::vector<EpiModel> m;
+    if (int rc = hpgv_epi_order_models(ctx, order, i_begin, i_end, subset, max_ranking_size, combs_out && accuracy && risky_mask && n_ranked, m, scan_ms)) return rc;
+    int32_t *const comb[5] = {combs_out, combs_out + 1, combs_out + 2, combs_out + 3, combs_out + 4};
+    epi_scatter(m, max_ranking_size, order, comb, (size_t)order, accuracy, risky_mask, hpgv::EPI_MASK_WORDS, n_ranked);
     return HPGV_OK;
     HPGV_ABI_CATCH(ctx)
 }
@@ -223,3 +167,16 @@ int hpgv_epi_rank_order(hpgv_ctx *ctx, int order, int subset, int max_ranking_si
 }
 
 }  // extern "C"
+
+int hpgv_epi_order_models(hpgv_ctx *ctx, int order, int i_begin, int i_end, int subset, int N, bool have_outputs, std::vector<EpiModel> &out, float *scan_ms) {
+    DeviceGuard g(ctx->device);
+    std::lock_guard<std::mutex> lk(ctx->epi_mu);
+    int rc = epi_check_folds(ctx);
+    if (!rc) rc = generic_check(ctx, order);
+    if (!rc) rc = epi_check_subset(ctx, subset);
+    if (rc) return rc;
+    if (i_begin < 0 || i_end < i_begin || i_end > ctx->epi.V) return fail(ctx, HPGV_ERR_INVALID, "first SNPs [%d, %d) outside the dataset", i_begin, i_end);
+    if (N < 1 || N > 65536 || !have_outputs) return fail(ctx, HPGV_ERR_INVALID, "bad ranking arguments");
+    EpiListOrder o(ctx, order, i_begin, i_end, subset, N);
+    return epi_rank_loop(ctx, o, N, out, scan_ms);
+}

@@ -14,7 +14,7 @@
 // Streams: every member has a scan stream and a transfer stream.  A call queues, per member: [wait until the transfer
 // that last read this generation's scratch is done] scan + statistics kernels -> event -> (transfer stream) send of the
 // pieces.  Two generations of scratch per member let the transfers of call k run under the scans of call k + 1.
-#include "hpgv_internal.h"
+#include "hpgv_epi_host.h"
 
 #include <dlfcn.h>
 #include <thread>
@@ -575,15 +575,12 @@ int hpgv_group_stats(hpgv_ctx *g, const uint8_t *const *d_gt, int64_t V, int32_t
 // ---- the epistasis scan over the devices of a group (the reference deals block coordinates to its workers,
 //      singlenode/epistasis_runner.c:114-145).  Every combination of `order` SNPs belongs to its FIRST SNP; the first SNPs are
 //      cut into G runs of (nearly) equal numbers of combinations -- for pairs at multiples of 64 rows, the tile scan's unit --
-//      member g ranks its run on its own device (hpgv_epi_rank_{pairs,triples,order}_rows, one host thread per member), and the
+//      member g ranks its run on its own device (hpgv_epi_{pairs,triples,order}_models, one host thread per member), and the
 //      ONE exchange is the gather of the members' per-fold top lists (num_folds x max_ranking_size records of 64 bytes) onto
 //      member 0 over the group's communicator, where they merge into the whole ranking: a model is in the whole top N only if
 //      it is in the top N of its own share.
 
 namespace {
-
-struct EpiRec { double accuracy; int32_t c[5]; int32_t used; uint32_t risky[8]; };     // 64 bytes; used = 0: an empty slot
-static_assert(sizeof(EpiRec) == 64, "one record of the gathered top lists");
 
 // combinations of `order` SNPs out of V that begin with one of the first `rows` SNPs
 long double epi_combs_before(int V, int order, int rows) {
@@ -636,9 +633,9 @@ int hpgv_group_epi_rank(hpgv_ctx *g, int order, int subset, int max_ranking_size
     for (int k = 1; k < G; ++k)
         if (!g->members[(size_t)k]->epi.have_folds || g->members[(size_t)k]->epi.V != g->members[0]->epi.V || g->members[(size_t)k]->epi.num_folds != nf)
             return fail(g, HPGV_ERR_STATE, "member %d does not hold the dataset and folds of member 0: set them through the group context", k);
-    const size_t n_rec = (size_t)nf * (size_t)N, bytes = n_rec * sizeof(EpiRec);
+    const size_t n_rec = (size_t)nf * (size_t)N, bytes = n_rec * sizeof(EpiModel);
     // ---- every member ranks its share on a host thread of its own ----
-    std::vector<std::vector<EpiRec>> lists((size_t)G, std::vector<EpiRec>(n_rec));
+    std::vector<std::vector<EpiModel>> lists((size_t)G);
     std::vector<int> rcs((size_t)G, HPGV_OK);
     std::vector<float> ms((size_t)G, 0.f);
     {
@@ -649,26 +646,11 @@ int hpgv_group_epi_rank(hpgv_ctx *g, int order, int subset, int max_ranking_size
                     hpgv_ctx *mc = g->members[(size_t)k];
                     int lo = 0, hi = 0;
                     (void)hpgv_group_epi_share(g, order, k, &lo, &hi);
-                    std::vector<int32_t> ci(n_rec), cj(n_rec), ck(n_rec), cn(n_rec * (size_t)order), cnt((size_t)hpgv::EPI_MAX_FOLDS, 0);
-                    std::vector<uint32_t> rk(n_rec * 8, 0u);
-                    std::vector<double> acc(n_rec, 0.0);
-                    int r = HPGV_OK;
-                    if (order == 2) r = hpgv_epi_rank_pairs_rows(mc, lo, hi, subset, N, ci.data(), cj.data(), acc.data(), rk.data(), cnt.data(), scan_ms ? &ms[(size_t)k] : nullptr);
-                    else if (order == 3) r = hpgv_epi_rank_triples_rows(mc, lo, hi, subset, N, ci.data(), cj.data(), ck.data(), acc.data(), rk.data(), cnt.data(), scan_ms ? &ms[(size_t)k] : nullptr);
-                    else r = hpgv_epi_rank_order_rows(mc, order, lo, hi, subset, N, cn.data(), acc.data(), rk.data(), cnt.data(), scan_ms ? &ms[(size_t)k] : nullptr);
-                    rcs[(size_t)k] = r;
-                    if (r) return;
+                    float *t_ms = scan_ms ? &ms[(size_t)k] : nullptr;
                     auto &L = lists[(size_t)k];
-                    std::memset(L.data(), 0, bytes);
-                    for (int f = 0; f < nf; ++f)
-                        for (int e = 0; e < cnt[(size_t)f]; ++e) {
-                            const size_t o = (size_t)f * (size_t)N + (size_t)e;
-                            EpiRec &R = L[o];
-                            R.accuracy = acc[o]; R.used = 1;
-                            for (int s2 = 0; s2 < 5; ++s2) R.c[s2] = -1;
-                            if (order <= 3) { R.c[0] = ci[o]; R.c[1] = cj[o]; if (order == 3) R.c[2] = ck[o]; R.risky[0] = rk[o]; }      // one mask word per model
-                            else { for (int s2 = 0; s2 < order; ++s2) R.c[s2] = cn[o * (size_t)order + (size_t)s2]; for (int w = 0; w < 8; ++w) R.risky[w] = rk[o * 8 + (size_t)w]; }
-                        }
+                    rcs[(size_t)k] = order == 2 ? hpgv_epi_pairs_models(mc, lo, hi, subset, N, true, L, t_ms)
+                                   : order == 3 ? hpgv_epi_triples_models(mc, lo, hi, subset, N, true, L, t_ms)
+                                                : hpgv_epi_order_models(mc, order, lo, hi, subset, N, true, L, t_ms);
                 } catch (...) { rcs[(size_t)k] = HPGV_ERR_NOMEM; }
             });
         for (auto &t : th) t.join();
@@ -707,21 +689,16 @@ int hpgv_group_epi_rank(hpgv_ctx *g, int order, int subset, int max_ranking_size
         NCCLCHK(g, S, S->GroupEnd());
     }
     for (int k = 0; k < G; ++k) { DeviceGuard dg(g->members[(size_t)k]->device); HIPCHK(g, hipStreamSynchronize(S->m[(size_t)k].xfer)); }
-    std::vector<EpiRec> all(n_rec * (size_t)G);
+    std::vector<EpiModel> all(n_rec * (size_t)G);
     { DeviceGuard dg(dev0); HIPCHK(g, hipMemcpy(all.data(), d_all, bytes * (size_t)G, hipMemcpyDeviceToHost)); }
     // ---- merge: per fold the best N of the members' lists (add_to_model_ranking, model.c:478-517: higher accuracy, then the
     //      smaller combination) ----
-    auto better = [](const EpiRec &a, const EpiRec &b) {
-        if (a.accuracy != b.accuracy) return a.accuracy > b.accuracy;
-        for (int s2 = 0; s2 < 5; ++s2) if (a.c[s2] != b.c[s2]) return a.c[s2] < b.c[s2];
-        return false;
-    };
-    std::vector<EpiRec> t;
+    std::vector<EpiModel> t;
     for (int f = 0; f < nf; ++f) {
         t.clear();
         for (int k = 0; k < G; ++k)
-            for (int e = 0; e < N; ++e) { const EpiRec &R = all[(size_t)k * n_rec + (size_t)f * (size_t)N + (size_t)e]; if (R.used) t.push_back(R); }
-        std::sort(t.begin(), t.end(), better);
+            for (int e = 0; e < N; ++e) { const EpiModel &R = all[(size_t)k * n_rec + (size_t)f * (size_t)N + (size_t)e]; if (R.used) t.push_back(R); }
+        std::sort(t.begin(), t.end(), epi_better<EpiModel>);
         if ((int)t.size() > N) t.resize((size_t)N);
         n_ranked[f] = (int32_t)t.size();
         for (size_t e = 0; e < t.size(); ++e) {

@@ -3,6 +3,7 @@
 // device-resident *_dev launchers), hpgv_tool_capi.hip (tokenizer, per-batch and text entry points),
 // hpgv_lines_capi.hip (partition / multisplit of lines), and the units whose kernel instantiations compile on their
 // own (hpgv_epi_capi.hip, hpgv_epi_generic_capi.hip, hpgv_statsall_capi.hip, hpgv_inflate_capi.hip, hpgv_group_capi.hip).
+// The host side the epistasis units share is in hpgv_epi_host.h.
 #pragma once
 #include "../../include/hpgv.h"
 #include "hpgv_kernels.h"
@@ -76,11 +77,10 @@ struct EpiState {
     hpgv::EpiFold *d_folds = nullptr;
     uint32_t *d_group_w0 = nullptr;
     std::vector<int32_t> group_size;
-    hpgv::EpiCand *d_cand = nullptr;
-    hpgv::EpiCand3 *d_cand3 = nullptr;    // the triple ranking's candidate lists, kept between calls
-    size_t cand3_cap = 0;
+    void *d_cand = nullptr;           // the pair and triple rankings' candidate lists (EpiCand / EpiCand3), kept between calls and only ever grown
+    size_t cand_bytes = 0;
     unsigned *d_cand_count = nullptr;
-    unsigned cand_cap = 0;
+    unsigned cand_cap = 0;            // records per fold's list in the current ranking call
     double *d_thr = nullptr;
     unsigned *d_tile_base = nullptr;
     size_t tile_base_cap = 0;

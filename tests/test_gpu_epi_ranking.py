@@ -349,3 +349,62 @@ def test_consecutive_calls_with_the_state_changing(eng):
     triples_call(grown, nA3, nU3, m, hpgv.EPI_TRAINING, 25)
     pairs_call(grown, nA3, nU3, m, hpgv.EPI_TESTING, 300)
     triples_call(grown, nA3, nU3, m, hpgv.EPI_TESTING, 5)
+
+
+# ---- 7. shares of first SNPs, and the any-order ranking across launches --------------------------------------------------
+
+@pytest.fixture(scope="module")
+def cohort40():
+    """V = 40, 60 cases, 52 controls, 3 folds, missing calls: the dataset, the fold of every sample, and per subset the oracle's
+    dense triple scan (computed once, read by both tests)"""
+    rng = np.random.default_rng(40)
+    v, nA, nU, k = 40, 60, 52, 3
+    data = epi_random_dataset(rng, v, nA, nU, p_missing=0.04)
+    fold = epi_random_folds(rng, nA, nU, k)
+    masks = orc.fold_masks_from_assignment(fold, k)
+    scans = {subset: orc.epi_scan_triples(data, nA, nU, masks, subset) for subset in SUBSETS}
+    return data, nA, nU, fold, k, scans
+
+
+def test_triple_ranking_by_shares_of_first_snps(eng, cohort40):
+    # hpgv_epi_rank_triples_rows as one GPU of a group calls it: the lists of the shares [0, 7), [7, 19), [19, 40) merge into the
+    # whole ranking; first SNPs 38 and 39 begin no triple
+    data, nA, nU, fold, k, scans = cohort40
+    _load(eng, data, nA, nU, fold, k)
+    v, N = data.shape[0], 25
+    triples = all_combs(v, 3)
+    for subset in SUBSETS:
+        exp = oracle_top(*scans[subset], triples, N)
+        _same_ranking(eng.epi_rank_triples(subset, N), exp, 3, ("whole", subset))
+        parts = [eng.epi_rank_triples(subset, N, rows=rows) for rows in ((0, 7), (7, 19), (19, 40))]
+        for f in range(k):
+            merged = sorted((-float(p["accuracy"][f][e]), int(p["i"][f][e]), int(p["j"][f][e]), int(p["k"][f][e]), int(p["risky"][f][e]))
+                            for p in parts for e in range(int(p["n"][f])))[:N]
+            n = int(exp["n"][f])
+            assert [(-a, i, j, kk, r) for a, i, j, kk, r in merged] == [
+                (float(exp["accuracy"][f][e]), int(exp["i"][f][e]), int(exp["j"][f][e]), int(exp["k"][f][e]), int(exp["risky"][f][e]))
+                for e in range(n)], (subset, f)
+        empty = eng.epi_rank_triples(subset, N, rows=(38, 40))
+        assert not empty["n"].any(), empty["n"]
+
+
+def test_order_ranking_across_launches_with_thresholds(eng, cohort40):
+    # order 3 through the listed-combination kernel: the first launch takes 4 096 of the 9 880 combinations, the second the rest
+    # and lists only what reaches the thresholds of the first; ties go by the combination, wherever a launch listed it
+    data, nA, nU, fold, k, scans = cohort40
+    _load(eng, data, nA, nU, fold, k)
+    N = 9
+    triples = all_combs(data.shape[0], 3)
+    assert len(triples) == 9880
+    for subset in SUBSETS:
+        exp = oracle_top(*scans[subset], triples, N)
+        res = eng.epi_rank_order(3, subset, N)
+        info = eng.epi_last_rank_info()
+        assert info["kernel"] == hpgv.EPI_KERNEL_COMBS and info["launches"] >= 2, info
+        for f in range(k):
+            n = int(exp["n"][f])
+            assert int(res["n"][f]) == n, (subset, f)
+            want = np.stack([exp[key][f][:n] for key in "ijk"], axis=1)
+            assert np.array_equal(res["combs"][f][:n], want), (subset, f)
+            assert np.array_equal(res["accuracy"][f][:n], exp["accuracy"][f][:n]), (subset, f)
+            assert np.array_equal(res["risky"][f][:n, 0], exp["risky"][f][:n]), (subset, f)
