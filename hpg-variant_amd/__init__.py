@@ -51,6 +51,8 @@ SYMBOLS = [
     "hpgv_epi_last_rank_info", "hpgv_filter_text", "hpgv_text_partition", "hpgv_lines_partition_scratch_bytes", "hpgv_lines_partition_dev",
     "hpgv_text_multisplit", "hpgv_lines_multisplit_scratch_bytes", "hpgv_lines_multisplit_dev",
     "hpgv_inheritance_scan_dev", "hpgv_set_text_inheritance_filters",
+    "hpgv_bgzf_deflate_bound", "hpgv_bgzf_deflate_scratch_bytes", "hpgv_bgzf_deflate_dev", "hpgv_bgzf_compress",
+    "hpgv_text_partition_bgzf", "hpgv_text_multisplit_bgzf",
 ]
 
 
@@ -190,6 +192,14 @@ def load():
     L.hpgv_group_epi_rank.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, C.POINTER(C.c_float)]
     L.hpgv_epi_rank_triples_rows.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_float)]
     L.hpgv_epi_last_rank_info.argtypes = [vp, C.POINTER(EpiRankInfo)]
+    L.hpgv_bgzf_deflate_bound.argtypes = [u64, i32]
+    L.hpgv_bgzf_deflate_bound.restype = sz
+    L.hpgv_bgzf_deflate_scratch_bytes.argtypes = [u64, i32]
+    L.hpgv_bgzf_deflate_scratch_bytes.restype = sz
+    L.hpgv_bgzf_deflate_dev.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
+    L.hpgv_bgzf_compress.argtypes = [vp, vp, sz, vp, sz, C.POINTER(sz)]
+    L.hpgv_text_partition_bgzf.argtypes = [vp, vp, vp, i32, vp, sz, i32, vp, vp, vp, vp]
+    L.hpgv_text_multisplit_bgzf.argtypes = [vp, vp, vp, i32, i32, i32, vp, sz, vp, vp]
     _lib = L
     return L
 

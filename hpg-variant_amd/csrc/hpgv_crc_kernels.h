@@ -137,6 +137,50 @@ __device__ __forceinline__ void bgzf_tiles_clipped(const char *__restrict__ text
     }
 }
 
+// The pieces of the wave's CRC that other kernels share (k_bgzf_crc below; the compressor, hpgv_deflate_kernels.h).
+// bytes one at a time: in front of the first aligned dword, behind the last full 256-byte row
+__device__ __forceinline__ uint32_t crc_bytes(const uint32_t *t0, uint32_t s, const uint8_t *__restrict__ p, uint32_t n) {
+    for (uint32_t i = 0; i < n; ++i) s = t0[(s ^ p[i]) & 0xFFu] ^ (s >> 8);
+    return s;
+}
+// rows k .. steps - 1 of the interleaved part (q = the lane's dword of row 0, k < steps): the last row is XORed in, not advanced over
+__device__ __forceinline__ uint32_t crc_rows(const uint32_t *s_tab, const uint32_t *__restrict__ q, uint32_t a, uint32_t k, uint32_t steps) {
+    const uint32_t *w0 = s_tab + CRC_W, *w1 = w0 + 256, *w2 = w0 + 512, *w3 = w0 + 768;
+    uint32_t d = q[64 * (size_t)k];
+    for (++k; k < steps; ++k) {
+        const uint32_t nx = q[64 * (size_t)k];
+        a ^= d;
+        a = w0[a & 0xFFu] ^ w1[(a >> 8) & 0xFFu] ^ w2[(a >> 16) & 0xFFu] ^ w3[a >> 24];
+        d = nx;
+    }
+    return a ^ d;
+}
+// the lanes' registers, each 64 - lane dwords before the end of the rows, advanced to that end and XORed together
+__device__ __forceinline__ uint32_t crc_fold(const uint32_t *s_tab, uint32_t a, int lane) {
+    const uint32_t adv = 64u - (uint32_t)lane;
+    #pragma unroll 1
+    for (int bit = 0; bit < 7; ++bit)
+        if ((adv >> bit) & 1u) a = crc_multmodp(s_tab[CRC_X2N + bit], a);
+    #pragma unroll
+    for (int off = 32; off > 0; off >>= 1) a ^= __shfl_xor(a, off);
+    return a;
+}
+// CRC-32 of the L bytes at p (any alignment) by one wave, tables in LDS at s_tab; every lane returns it
+__device__ __forceinline__ uint32_t crc_wave(const uint32_t *s_tab, const uint8_t *__restrict__ p, uint32_t L) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t *t0 = s_tab + CRC_T0;
+    uint32_t head = (uint32_t)((4 - ((uintptr_t)p & 3)) & 3);
+    if (head > L) head = L;
+    uint32_t s = crc_bytes(t0, 0xFFFFFFFFu, p, head);
+    p += head; L -= head;
+    const uint32_t steps = L >> 8;
+    if (steps) {
+        s = crc_fold(s_tab, crc_rows(s_tab, (const uint32_t *)p + lane, lane == 0 ? s : 0u, 0, steps), lane);
+        p += (size_t)steps << 8; L -= steps << 8;
+    }
+    return ~crc_bytes(t0, s, p, L);
+}
+
 template <bool AGG>
 static __global__ __launch_bounds__(256) void k_bgzf_crc(const uint8_t *__restrict__ comp, const uint64_t *__restrict__ in_off,
                                                    const uint32_t *__restrict__ in_len, const uint64_t *__restrict__ out_off,
@@ -164,7 +208,7 @@ static __global__ __launch_bounds__(256) void k_bgzf_crc(const uint8_t *__restri
     uint32_t s = 0xFFFFFFFFu;
     uint32_t head = (uint32_t)((4 - ((uintptr_t)p & 3)) & 3);
     if (head > L) head = L;
-    for (uint32_t i = 0; i < head; ++i) s = t0[(s ^ p[i]) & 0xFFu] ^ (s >> 8);
+    s = crc_bytes(t0, s, p, head);
     p += head; L -= head;
     const uint32_t steps = L >> 8;                              // dwords per lane
     // Rows are taken eight at a time: 2 KiB that straddle the SAME point of the tile grid in every group of the block -- the
@@ -224,27 +268,11 @@ static __global__ __launch_bounds__(256) void k_bgzf_crc(const uint8_t *__restri
             }
             k = 8 * ng;
         }
-        if (k < steps) {                                         // (the rows that do not fill a group; every row without the records)
-            uint32_t d = q[64 * (size_t)k];
-            for (++k; k < steps; ++k) {
-                const uint32_t nx = q[64 * (size_t)k];
-                a ^= d;
-                a = w0[a & 0xFFu] ^ w1[(a >> 8) & 0xFFu] ^ w2[(a >> 16) & 0xFFu] ^ w3[a >> 24];
-                d = nx;
-            }
-            a ^= d;
-        }
-        // a stands 64 - lane dwords before the end of the rows
-        const uint32_t adv = 64u - (uint32_t)lane;
-        #pragma unroll 1
-        for (int bit = 0; bit < 7; ++bit)
-            if ((adv >> bit) & 1u) a = crc_multmodp(s_tab[CRC_X2N + bit], a);
-        #pragma unroll
-        for (int off = 32; off > 0; off >>= 1) a ^= __shfl_xor(a, off);
-        s = a;
+        if (k < steps) a = crc_rows(s_tab, q, a, k, steps);      // (the rows that do not fill a group; every row without the records)
+        s = crc_fold(s_tab, a, lane);                            // a stands 64 - lane dwords before the end of the rows
         p += (size_t)steps << 8; L -= steps << 8;
     }
-    for (uint32_t i = 0; i < L; ++i) s = t0[(s ^ p[i]) & 0xFFu] ^ (s >> 8);
+    s = crc_bytes(t0, s, p, L);
     if (lane == 0 && ~s != stored) status[b] = BGZF_STATUS_BAD_CRC;
     if constexpr (AGG) if (fused && ng > g_a) {                  // the tiles behind the last one the loop completed
         const size_t from = T0 + ng;

@@ -8,6 +8,18 @@
 #include "hpgv_bgzf_kernels.h"
 #include "hpgv_crc_kernels.h"
 
+// the CRC-32 tables on the context's device (ctx->d_crc_tab), built at first use; the device is current
+int hpgv_crc_tables(hpgv_ctx *ctx) {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->d_crc_tab) return HPGV_OK;
+    static_assert(HPGV_BLOCK_BAD_CRC == hpgv::BGZF_STATUS_BAD_CRC, "status code of the header and of the kernel");
+    std::vector<uint32_t> tab(hpgv::CRC_TAB_WORDS);
+    hpgv::crc_build_tables(tab.data());
+    HIPCHK(ctx, hipMalloc(&ctx->d_crc_tab, tab.size() * sizeof(uint32_t)));
+    HIPCHK(ctx, hipMemcpy(ctx->d_crc_tab, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return HPGV_OK;
+}
+
 extern "C" {
 
 // raw-DEFLATE blocks (the payloads of BGZF blocks) -> text, all on the device: block b occupies d_comp[in_off[b] .. +in_len[b])
@@ -88,16 +100,7 @@ int hpgv_bgzf_verify_tiles_dev(hpgv_ctx *ctx, const uint8_t *d_comp, const uint6
         return fail(ctx, HPGV_ERR_INVALID, "bad block check arguments");
     if (n_blocks == 0) return HPGV_OK;
     DeviceGuard g(ctx->device);
-    {
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        if (!ctx->d_crc_tab) {
-            static_assert(HPGV_BLOCK_BAD_CRC == hpgv::BGZF_STATUS_BAD_CRC, "status code of the header and of the kernel");
-            std::vector<uint32_t> tab(hpgv::CRC_TAB_WORDS);
-            hpgv::crc_build_tables(tab.data());
-            HIPCHK(ctx, hipMalloc(&ctx->d_crc_tab, tab.size() * sizeof(uint32_t)));
-            HIPCHK(ctx, hipMemcpy(ctx->d_crc_tab, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        }
-    }
+    if (const int rc = hpgv_crc_tables(ctx)) return rc;
     if (d_tiles && n_tiles > 0)
         hipLaunchKernelGGL(hpgv::k_bgzf_crc<true>, dim3((unsigned)((n_blocks + 3) / 4)), dim3(256), 0, (hipStream_t)stream, d_comp, d_in_off, d_in_len,
                            d_out_off, d_out_len, n_blocks, d_text, d_status, (const uint32_t *)ctx->d_crc_tab, (hpgv::TokAgg2 *)d_tiles, (long)n_tiles);

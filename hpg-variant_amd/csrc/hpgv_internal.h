@@ -396,5 +396,10 @@ int hpgv_launch_assoc_rows(hpgv_ctx *ctx, const uint8_t *d_src, size_t src_pitch
 void hpgv_epi_release(EpiState &E);
 // defined in hpgv_epi_generic_capi.hip: in-fold counts of listed combinations of order 2 .. 5, device to device (the caller holds epi_mu)
 int hpgv_epi_generic_counts(hpgv_ctx *ctx, int order, const int32_t *d_combs, int n_combs, int32_t *d_out);
+// defined in hpgv_inflate_capi.hip: the CRC-32 tables of hpgv_crc_kernels.h in ctx->d_crc_tab, built at first use
+int hpgv_crc_tables(hpgv_ctx *ctx);
+// defined in hpgv_deflate_capi.hip: the launches of hpgv_bgzf_deflate_dev on `st` (the arguments checked, the device current)
+int hpgv_bgzf_deflate_launch(hpgv_ctx *ctx, const char *d_text, const unsigned long long *d_seg_off, int n_segs, uint8_t *d_out,
+                             unsigned long long *d_seg_out_off, void *d_scratch, hipStream_t st);
 // defined in hpgv_group_capi.hip: streams, scratch and communicator of a group context (before its members go)
 void hpgv_group_release(hpgv_ctx *group);

@@ -94,15 +94,44 @@ int hpgv_filter_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, int max
     HPGV_ABI_CATCH(ctx)
 }
 
-int hpgv_text_partition(hpgv_ctx *ctx, const char *text, const uint8_t *keep, int n_lines, char *out, size_t out_cap,
-                        uint64_t *kept_bytes, uint64_t *total_bytes) {
-    HPGV_ABI_TRY
+// what the _bgzf twins ask for beyond the plain call: the parts deflated into BGZF members on the device before they are
+// copied back (hpgv_bgzf_deflate_dev with the primitive's own device-side offsets as segment bounds)
+struct BgzfWant {
+    int want_rest = 1;                  // partition: 0 = the other lines are neither deflated nor copied
+    uint64_t *comp = nullptr;           // partition: the two parts' member bytes
+    uint8_t *last = nullptr;            // the last text byte of every part ('\n' for an empty one)
+};
+
+// the parts' last bytes, for a writer that must end a file's last line
+static __global__ void k_seg_last_bytes(const char *__restrict__ text, const unsigned long long *__restrict__ seg_off, int n_segs, uint8_t *__restrict__ last) {
+    for (int s = (int)threadIdx.x; s < n_segs; s += (int)blockDim.x) last[s] = seg_off[s + 1] > seg_off[s] ? (uint8_t)text[seg_off[s + 1] - 1] : (uint8_t)'\n';
+}
+// the two segments of a partition: [0, kept) and [kept, total) -- the second empty when the caller does not want it
+static __global__ void k_part_segs(const unsigned long long *__restrict__ kept, unsigned long long total, int want_rest, unsigned long long *__restrict__ seg_off) {
+    if (threadIdx.x == 0) { seg_off[0] = 0; seg_off[1] = *kept; seg_off[2] = want_rest ? total : *kept; }
+}
+
+// the text in s->buf[1], n_segs segments bounded by d_seg_off, as members in s->buf[2]; d_res: seg_out_off[n_segs + 1], then a
+// last byte per segment.  Queued on the slot's stream.
+static int deflate_parts(hpgv_ctx *ctx, Slot *s, size_t total, const unsigned long long *d_seg_off, int n_segs, unsigned long long *d_res) {
+    int rc;
+    if ((rc = ensure(ctx, s, 2, hpgv_bgzf_deflate_bound(total, n_segs) + 16))) return rc;
+    if ((rc = ensure(ctx, s, 4, hpgv_bgzf_deflate_scratch_bytes(total, n_segs) + 16))) return rc;
+    if ((rc = hpgv_bgzf_deflate_launch(ctx, (const char *)s->buf[1], d_seg_off, n_segs, (uint8_t *)s->buf[2], d_res, s->buf[4], s->stream))) return rc;
+    hipLaunchKernelGGL(k_seg_last_bytes, dim3(1), dim3(256), 0, s->stream, (const char *)s->buf[1], d_seg_off, n_segs, (uint8_t *)(d_res + n_segs + 1));
+    HIPCHK(ctx, hipGetLastError());
+    return HPGV_OK;
+}
+
+static int text_partition(hpgv_ctx *ctx, const char *text, const uint8_t *keep, int n_lines, char *out, size_t out_cap,
+                          uint64_t *kept_bytes, uint64_t *total_bytes, const BgzfWant *Z) {
+    {
     if (is_group(ctx)) {
         int rc = HPGV_OK, found = 0;
         for (hpgv_ctx *m : ctx->members) {
             bool held;
             { std::lock_guard<std::mutex> lk(m->alias_mu); held = false; for (const auto &h : m->text_held) if (h.host_text == text) held = true; }
-            if (held) { found = 1; rc = hpgv_text_partition(m, text, keep, n_lines, out, out_cap, kept_bytes, total_bytes); }
+            if (held) { found = 1; rc = text_partition(m, text, keep, n_lines, out, out_cap, kept_bytes, total_bytes, Z); }
         }
         if (!found && keep) return fail(ctx, HPGV_ERR_STATE, "no hpgv_filter_text call holds this text");
         return rc;
@@ -116,17 +145,19 @@ int hpgv_text_partition(hpgv_ctx *ctx, const char *text, const uint8_t *keep, in
     if (!keep) return HPGV_OK;                                      // only the hold released
     Slot *s = h.slot;
     if (n_lines != h.n_lines) return fail(ctx, HPGV_ERR_INVALID, "n_lines %d, but hpgv_filter_text tokenized %d lines", n_lines, h.n_lines);
+    if (Z && Z->comp) Z->comp[0] = Z->comp[1] = 0;
+    if (Z && Z->last) Z->last[0] = Z->last[1] = '\n';
     if (n_lines == 0) { if (kept_bytes) *kept_bytes = 0; if (total_bytes) *total_bytes = 0; return HPGV_OK; }
     unsigned long long ends[2];
     HIPCHK(ctx, hipMemcpyAsync(&ends[0], h.d_line_off, sizeof ends[0], hipMemcpyDeviceToHost, s->stream));
     HIPCHK(ctx, hipMemcpyAsync(&ends[1], h.d_line_off + n_lines, sizeof ends[1], hipMemcpyDeviceToHost, s->stream));
     HIPCHK(ctx, hipStreamSynchronize(s->stream));
     const size_t total = (size_t)(ends[1] - ends[0]);
-    if (!out || total > out_cap) return fail(ctx, HPGV_ERR_INVALID, "the lines take %zu bytes, out has room for %zu", total, out_cap);
+    if (!out || (!Z && total > out_cap)) return fail(ctx, HPGV_ERR_INVALID, "the lines take %zu bytes, out has room for %zu", total, out_cap);
     const size_t n = (size_t)n_lines, scratch = hpgv_lines_partition_scratch_bytes(n_lines);
-    const size_t off_keep = round_up(scratch + sizeof(unsigned long long), 256);
+    const size_t off_keep = round_up(scratch + sizeof(unsigned long long), 256), off_seg = round_up(off_keep + n, 256);
     int rc;
-    if ((rc = ensure(ctx, s, 3, off_keep + n + 16))) return rc;
+    if ((rc = ensure(ctx, s, 3, off_seg + 64 + 16))) return rc;
     if ((rc = ensure(ctx, s, 1, total + 16))) return rc;
     char *d_aux = (char *)s->buf[3];
     unsigned long long *d_kept = (unsigned long long *)(d_aux + scratch);
@@ -135,11 +166,38 @@ int hpgv_text_partition(hpgv_ctx *ctx, const char *text, const uint8_t *keep, in
     if ((rc = partition_launch(ctx, h.d_text, h.d_line_off, n_lines, d_keep, (char *)s->buf[1], d_kept, d_aux, s->stream))) return rc;
     unsigned long long kept = 0;
     HIPCHK(ctx, hipMemcpyAsync(&kept, d_kept, sizeof kept, hipMemcpyDeviceToHost, s->stream));
-    if (total) HIPCHK(ctx, hipMemcpyAsync(out, s->buf[1], total, hipMemcpyDeviceToHost, s->stream));
+    if (Z) {                                                        // seg_off[3] | seg_out_off[3], last[2]
+        unsigned long long *d_seg = (unsigned long long *)(d_aux + off_seg), res[4] = {0, 0, 0, 0};
+        hipLaunchKernelGGL(k_part_segs, dim3(1), dim3(64), 0, s->stream, (const unsigned long long *)d_kept, (unsigned long long)total, Z->want_rest, d_seg);
+        if ((rc = deflate_parts(ctx, s, total, d_seg, 2, d_seg + 3))) return rc;
+        HIPCHK(ctx, hipMemcpyAsync(res, d_seg + 3, sizeof res, hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(ctx, hipStreamSynchronize(s->stream));
+        const size_t made = (size_t)res[2];
+        if (made > out_cap) return fail(ctx, HPGV_ERR_INVALID, "the members take %zu bytes, out has room for %zu", made, out_cap);
+        if (made) HIPCHK(ctx, hipMemcpyAsync(out, s->buf[2], made, hipMemcpyDeviceToHost, s->stream));
+        if (Z->comp) { Z->comp[0] = res[1]; Z->comp[1] = res[2] - res[1]; }
+        if (Z->last) memcpy(Z->last, &res[3], 2);
+    } else if (total) HIPCHK(ctx, hipMemcpyAsync(out, s->buf[1], total, hipMemcpyDeviceToHost, s->stream));
     HIPCHK(ctx, hipStreamSynchronize(s->stream));
     if (kept_bytes) *kept_bytes = kept;
     if (total_bytes) *total_bytes = total;
     return HPGV_OK;
+    }
+}
+
+int hpgv_text_partition(hpgv_ctx *ctx, const char *text, const uint8_t *keep, int n_lines, char *out, size_t out_cap,
+                        uint64_t *kept_bytes, uint64_t *total_bytes) {
+    HPGV_ABI_TRY
+    return text_partition(ctx, text, keep, n_lines, out, out_cap, kept_bytes, total_bytes, nullptr);
+    HPGV_ABI_CATCH(ctx)
+}
+
+int hpgv_text_partition_bgzf(hpgv_ctx *ctx, const char *text, const uint8_t *keep, int n_lines, uint8_t *out, size_t out_cap, int want_rest,
+                             uint64_t *kept_bytes, uint64_t *total_bytes, uint64_t *comp_bytes, uint8_t *last_byte) {
+    HPGV_ABI_TRY
+    BgzfWant Z;
+    Z.want_rest = want_rest ? 1 : 0; Z.comp = comp_bytes; Z.last = last_byte;
+    return text_partition(ctx, text, keep, n_lines, (char *)out, out_cap, kept_bytes, total_bytes, &Z);
     HPGV_ABI_CATCH(ctx)
 }
 
@@ -204,13 +262,13 @@ static bool peek_held(hpgv_ctx *ctx, const char *host_text, hpgv_ctx::TextHeld *
     return false;
 }
 
-int hpgv_text_multisplit(hpgv_ctx *ctx, const char *text, const uint8_t *bucket, int first_line, int n_lines, int n_buckets,
-                         char *out, size_t out_cap, uint64_t *bucket_off) {
-    HPGV_ABI_TRY
+static int text_multisplit(hpgv_ctx *ctx, const char *text, const uint8_t *bucket, int first_line, int n_lines, int n_buckets,
+                           char *out, size_t out_cap, uint64_t *bucket_off, const BgzfWant *Z) {
+    {
     if (is_group(ctx)) {
         hpgv_ctx::TextHeld h;
         for (hpgv_ctx *m : ctx->members)
-            if (peek_held(m, text, &h)) return hpgv_text_multisplit(m, text, bucket, first_line, n_lines, n_buckets, out, out_cap, bucket_off);
+            if (peek_held(m, text, &h)) return text_multisplit(m, text, bucket, first_line, n_lines, n_buckets, out, out_cap, bucket_off, Z);
         return fail(ctx, HPGV_ERR_STATE, "no hpgv_filter_text call holds this text");
     }
     if (!ctx) return HPGV_ERR_INVALID;
@@ -220,6 +278,7 @@ int hpgv_text_multisplit(hpgv_ctx *ctx, const char *text, const uint8_t *bucket,
         return fail(ctx, HPGV_ERR_INVALID, "lines [%d, %d + %d), but hpgv_filter_text tokenized %d lines", first_line, first_line, n_lines, h.n_lines);
     if (n_buckets < 1 || n_buckets > 256 || !bucket_off || (n_lines > 0 && !bucket))
         return fail(ctx, HPGV_ERR_INVALID, "bad text_multisplit arguments");
+    if (Z && Z->last) memset(Z->last, '\n', (size_t)n_buckets);
     if (n_lines == 0) { memset(bucket_off, 0, sizeof(uint64_t) * ((size_t)n_buckets + 1)); return HPGV_OK; }
     if (!msplit_entries(n_lines, n_buckets))
         return fail(ctx, HPGV_ERR_INVALID, "%d lines in %d buckets: more than INT_MAX (bucket, tile) sums", n_lines, n_buckets);
@@ -232,7 +291,8 @@ int hpgv_text_multisplit(hpgv_ctx *ctx, const char *text, const uint8_t *bucket,
     HIPCHK(ctx, hipStreamSynchronize(s->stream));
     const size_t total = (size_t)(ends[1] - ends[0]), n = (size_t)n_lines, nb1 = (size_t)n_buckets + 1;
     const size_t scratch = hpgv_lines_multisplit_scratch_bytes(n_lines, n_buckets);
-    const size_t off_boff = round_up(scratch, 256), off_bucket = round_up(off_boff + nb1 * sizeof(unsigned long long), 256);
+    // bucket_off[nb1] | the members' offsets [nb1], the parts' last bytes | bucket
+    const size_t off_boff = round_up(scratch, 256), off_bucket = round_up(off_boff + (2 * nb1 + 33) * sizeof(unsigned long long), 256);
     int rc;
     if ((rc = ensure(ctx, s, 3, off_bucket + n + 16))) return rc;
     if ((rc = ensure(ctx, s, 1, total + 16))) return rc;
@@ -241,6 +301,21 @@ int hpgv_text_multisplit(hpgv_ctx *ctx, const char *text, const uint8_t *bucket,
     uint8_t *d_bucket = (uint8_t *)d_aux + off_bucket;
     HIPCHK(ctx, hipMemcpyAsync(d_bucket, bucket, n, hipMemcpyHostToDevice, s->stream));
     if ((rc = multisplit_launch(ctx, h.d_text, d_line_off, n_lines, d_bucket, n_buckets, (char *)s->buf[1], d_boff, d_aux, s->stream))) return rc;
+    if (Z) {
+        if ((rc = deflate_parts(ctx, s, total, d_boff, n_buckets, d_boff + nb1))) return rc;
+        std::vector<uint64_t> res(nb1 + 33);
+        HIPCHK(ctx, hipMemcpyAsync(res.data(), d_boff + nb1, nb1 * sizeof(uint64_t) + (size_t)n_buckets, hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(ctx, hipStreamSynchronize(s->stream));
+        const size_t made = (size_t)res[n_buckets];
+        if (made > out_cap || (made && !out)) return fail(ctx, HPGV_ERR_INVALID, "the members take %zu bytes, out has room for %zu", made, out_cap);
+        memcpy(bucket_off, res.data(), nb1 * sizeof(uint64_t));
+        if (Z->last) memcpy(Z->last, res.data() + nb1, (size_t)n_buckets);
+        if (made) {
+            HIPCHK(ctx, hipMemcpyAsync(out, s->buf[2], made, hipMemcpyDeviceToHost, s->stream));
+            HIPCHK(ctx, hipStreamSynchronize(s->stream));
+        }
+        return HPGV_OK;
+    }
     HIPCHK(ctx, hipMemcpyAsync(bucket_off, d_boff, nb1 * sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream));
     HIPCHK(ctx, hipStreamSynchronize(s->stream));
     const size_t stored = (size_t)bucket_off[n_buckets];
@@ -250,6 +325,22 @@ int hpgv_text_multisplit(hpgv_ctx *ctx, const char *text, const uint8_t *bucket,
         HIPCHK(ctx, hipStreamSynchronize(s->stream));
     }
     return HPGV_OK;
+    }
+}
+
+int hpgv_text_multisplit(hpgv_ctx *ctx, const char *text, const uint8_t *bucket, int first_line, int n_lines, int n_buckets,
+                         char *out, size_t out_cap, uint64_t *bucket_off) {
+    HPGV_ABI_TRY
+    return text_multisplit(ctx, text, bucket, first_line, n_lines, n_buckets, out, out_cap, bucket_off, nullptr);
+    HPGV_ABI_CATCH(ctx)
+}
+
+int hpgv_text_multisplit_bgzf(hpgv_ctx *ctx, const char *text, const uint8_t *bucket, int first_line, int n_lines, int n_buckets,
+                              uint8_t *out, size_t out_cap, uint64_t *bucket_off, uint8_t *last_byte) {
+    HPGV_ABI_TRY
+    BgzfWant Z;
+    Z.last = last_byte;
+    return text_multisplit(ctx, text, bucket, first_line, n_lines, n_buckets, (char *)out, out_cap, bucket_off, &Z);
     HPGV_ABI_CATCH(ctx)
 }
 

@@ -391,9 +391,9 @@ static int create_out(FILE **f, char **path, const char *prefix, const char *suf
 /* the tool's output files (split: its files as the records come).  The filter tool's .rejected is created empty without
  * save_rejected (filter_runner.c:63-68); stats: one file per phenotype (stats_runner.c:267-297), and its accumulator */
 static int run_outputs(run_t *R, const char *out_path) {
-    const char *suffix = R->tool == RUN_STATS ? ".stats-variants" : R->tool == RUN_FILTER ? ".filtered" : "";
+    const char *suffix = R->tool == RUN_STATS ? ".stats-variants" : R->tool == RUN_FILTER ? (R->out_bgzf ? ".filtered.gz" : ".filtered") : "";
     int rc = R->tool == RUN_SPLIT ? HPGV_OK : create_out(&R->out, &R->path, out_path, suffix);
-    if (!rc && R->tool == RUN_FILTER) rc = create_out(&R->out_rej, &R->path_rej, out_path, ".rejected");
+    if (!rc && R->tool == RUN_FILTER) rc = create_out(&R->out_rej, &R->path_rej, out_path, R->out_bgzf ? ".rejected.gz" : ".rejected");
     if (rc || R->tool != RUN_STATS) return rc;
     if (R->n_groups > 0) {
         R->gfd = (FILE **)calloc((size_t)R->n_groups, sizeof(FILE *));
@@ -476,7 +476,7 @@ static int run_pipeline(run_t *R, size_t batch_bytes) {
         if (w > ((size_t)256 << 20)) w = (size_t)256 << 20;
         if (w > batch_bytes) batch_bytes = w;
     }
-    for (; !rc && have < P->nb; have++) rc = run_batch_alloc(&P->bt[have], R, batch_bytes, R->n_samples, R->n_trios, R->n_groups);
+    for (; !rc && have < P->nb; have++) rc = run_batch_alloc(&P->bt[have], R, out_batch_cap(R, batch_bytes), R->n_samples, R->n_trios, R->n_groups);
     if (rc == HPGV_ERR_NOMEM) snprintf(g_err, sizeof g_err, "out of memory for the batch buffers");
     if (!rc) rc = run_headers(R);
     if (!rc) {
@@ -562,9 +562,12 @@ static int run_finish(run_t *R, int rc, const char *out_path) {
         const uint32_t nv = (uint32_t)R->written;
         if (fseek(R->out, 0, SEEK_SET) != 0 || fwrite(&nv, sizeof nv, 1, R->out) != 1) { snprintf(g_err, sizeof g_err, "cannot write %s", out_path); rc = HPGV_ERR_INVALID; }
     }
+    if (R->tool == RUN_FILTER && R->out_bgzf && ((R->out && bgzf_write_eof(R->out)) || (R->out_rej && bgzf_write_eof(R->out_rej))) && !rc) {      /* (.rejected.gz without save_rejected: a valid, empty bgzip file) */
+        snprintf(g_err, sizeof g_err, "cannot write %s", out_path); rc = HPGV_ERR_INVALID;
+    }
     if (R->out && fclose(R->out) != 0 && !rc) { snprintf(g_err, sizeof g_err, "cannot write %s", R->path); rc = HPGV_ERR_INVALID; }
     if (R->out_rej && fclose(R->out_rej) != 0 && !rc) { snprintf(g_err, sizeof g_err, "cannot write %s", R->path_rej); rc = HPGV_ERR_INVALID; }
-    if (split_files_close(&R->SF) && !rc) rc = HPGV_ERR_INVALID;
+    if (split_files_close(&R->SF, R->out_bgzf) && !rc) rc = HPGV_ERR_INVALID;
     for (int k = 0; R->gfd && k < R->n_groups; k++) if (R->gfd[k]) fclose(R->gfd[k]);
     if (tool_sorts(R->tool)) {
         /* assoc_runner.c:255-261 (only a warning there); in order as written: nothing to do (HPGV_ALWAYS_SORT=1 reads the file
@@ -707,7 +710,7 @@ int hpgv_run_filter(const char *vcf_path, const char *ped_path, const char *out_
                     long *n_passed_out, long *n_rejected_out) {
     if (n_passed_out) *n_passed_out = 0;
     if (n_rejected_out) *n_rejected_out = 0;
-    run_t R = { .tool = RUN_FILTER, .filters = g_filters, .save_rejected = save_rejected ? 1 : 0 };
+    run_t R = { .tool = RUN_FILTER, .filters = g_filters, .save_rejected = save_rejected ? 1 : 0, .out_bgzf = out_compression_now() == HPGV_OUT_BGZF };
     const hpgv_run_filters_t *F = &R.filters;
     if (!vcf_path || !out_prefix) { snprintf(g_err, sizeof g_err, "vcf_path and out_prefix must not be NULL"); return HPGV_ERR_INVALID; }
     rec_filters_t *rf = rec_filters_take();
@@ -737,11 +740,11 @@ int hpgv_run_split(const char *vcf_path, const char *out_dir, int criterion, con
             if (intervals[j] <= intervals[j - 1]) { snprintf(g_err, sizeof g_err, "the coverage intervals must be strictly increasing"); return HPGV_ERR_INVALID; }
     }
     run_t R = { .tool = RUN_SPLIT, .filters = filters_off, .criterion = criterion, .iv = intervals,      /* no record filters: every record to a file */
-                .n_iv = criterion == HPGV_SPLIT_COVERAGE ? n_intervals : 0, .dir = out_dir };
+                .n_iv = criterion == HPGV_SPLIT_COVERAGE ? n_intervals : 0, .dir = out_dir, .out_bgzf = out_compression_now() == HPGV_OUT_BGZF };
     const char *slash = strrchr(vcf_path, '/');
     const char *base = slash ? slash + 1 : vcf_path;
     size_t bl = strlen(base);
-    if (bl > 3 && !strcmp(base + bl - 3, ".gz")) bl -= 3;                   /* the files hold plain text */
+    if (bl > 3 && !strcmp(base + bl - 3, ".gz")) bl -= 3;                   /* the files hold plain text, or get their own .gz (HPGV_OUT_BGZF) */
     else if (bl > 4 && !strcmp(base + bl - 4, ".bgz")) bl -= 4;
     if (bl >= sizeof R.base) { snprintf(g_err, sizeof g_err, "the input's file name is too long"); return HPGV_ERR_INVALID; }
     struct stat st;

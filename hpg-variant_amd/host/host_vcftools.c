@@ -3,6 +3,57 @@
 #include "hpgv_host_internal.h"
 #include <limits.h>
 
+/* ---- HPGV_OUT_BGZF: the filter and split tools' files as bgzip.  The records are deflated on the device that holds them
+ *      (hpgv_text_partition_bgzf, hpgv_text_multisplit_bgzf); what the host adds -- headers, a missing last newline, a batch
+ *      whose empty lines must be taken out first -- goes through zlib, in whole members of at most 65 280 text bytes ---- */
+static int g_out_mode = HPGV_OUT_PLAIN;
+int hpgv_run_set_output_compression(int mode) {
+    if (mode != HPGV_OUT_PLAIN && mode != HPGV_OUT_BGZF) { snprintf(g_err, sizeof g_err, "unknown output compression %d", mode); return HPGV_ERR_INVALID; }
+    g_out_mode = mode;
+    return HPGV_OK;
+}
+int out_compression_now(void) { return g_out_mode; }
+/* bgzip members never outgrow the text by more than 31 bytes per block; split: a batch's ranges have 255 buckets each */
+size_t out_batch_cap(const run_t *R, size_t batch_bytes) {
+    return R->out_bgzf ? hpgv_bgzf_deflate_bound(batch_bytes, R->tool == RUN_SPLIT ? 256 : 2) : batch_bytes;
+}
+
+int bgzf_write_eof(FILE *f) {
+    static const unsigned char eof[28] = { 0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 0x42, 0x43, 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+    return fwrite(eof, 1, sizeof eof, f) != sizeof eof;
+}
+enum { BGZF_TEXT = HPGV_BGZF_BLOCK_TEXT, BGZF_MEMBER = 65536 };
+/* n bytes of text as members; level 0 (stored) when the deflated block would not fit a member */
+static int bgzf_write_text(FILE *f, const char *p, size_t n) {
+    unsigned char *m = (unsigned char *)malloc(BGZF_MEMBER);
+    if (!m) return 1;
+    int bad = 0;
+    for (size_t at = 0; at < n && !bad; at += BGZF_TEXT) {
+        const size_t len = n - at < BGZF_TEXT ? n - at : BGZF_TEXT;
+        size_t pay = 0;
+        for (int level = Z_DEFAULT_COMPRESSION, done = 0; !done && !bad; level = 0) {
+            z_stream z;
+            memset(&z, 0, sizeof z);
+            if (deflateInit2(&z, level, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) { bad = 1; break; }
+            z.next_in = (Bytef *)(p + at); z.avail_in = (uInt)len;
+            z.next_out = m + 18; z.avail_out = BGZF_MEMBER - 26;
+            done = deflate(&z, Z_FINISH) == Z_STREAM_END;
+            pay = z.total_out;
+            deflateEnd(&z);
+            if (!done && level == 0) bad = 1;
+        }
+        if (bad) break;
+        static const unsigned char head[16] = { 0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 0x42, 0x43, 2, 0 };
+        memcpy(m, head, 16);
+        const uint32_t bsize = (uint32_t)pay + 25, crc = (uint32_t)crc32(crc32(0L, Z_NULL, 0), (const Bytef *)(p + at), (uInt)len), isize = (uint32_t)len;
+        m[16] = (unsigned char)bsize; m[17] = (unsigned char)(bsize >> 8);
+        for (int k = 0; k < 4; k++) { m[18 + pay + k] = (unsigned char)(crc >> (8 * k)); m[22 + pay + k] = (unsigned char)(isize >> (8 * k)); }
+        bad = fwrite(m, 1, pay + 26, f) != pay + 26;
+    }
+    free(m);
+    return bad;
+}
+
 static int keep_reserve(run_batch_t *b, int n) {      /* room in b->keep for a byte per line */
     if (b->keep_cap >= n) return HPGV_OK;
     free(b->keep);
@@ -26,6 +77,16 @@ int filter_partition(run_batch_t *b) {
         else b->n_rej++;
     }
     uint64_t kept = 0, total = 0;
+    const run_t *R = b->run;
+    /* bgzip output: both parts deflated where they lie.  A batch with empty lines among the rejected ones comes back as text:
+     * the writer takes them out first (write_region) and deflates on the host */
+    b->part_bgzf = R->out_bgzf && !(R->save_rejected && b->n_blank > 0);
+    if (b->part_bgzf) {
+        uint64_t comp[2] = {0, 0};
+        const int rc = hpgv_text_partition_bgzf(g_ctx, b->text, b->keep, n, (uint8_t *)b->text, b->text_cap, R->save_rejected, &kept, &total, comp, b->part_last);
+        b->part_kept = comp[0]; b->part_total = comp[0] + comp[1];
+        return rc;
+    }
     const int rc = hpgv_text_partition(g_ctx, b->text, b->keep, n, b->text, b->text_cap, &kept, &total);
     b->part_kept = kept; b->part_total = total;
     return rc;
@@ -175,9 +236,14 @@ int split_partition(run_batch_t *b) {
     size_t pos = 0;
     for (int r = 0, k = 0; !rc && r < b->sp_n_ranges; r++) {
         const int *R = b->sp_range + 3 * r;
-        rc = hpgv_text_multisplit(g_ctx, b->text, b->keep + R[0], R[0], R[1], R[2], b->text + pos, b->text_cap - pos, boff);
+        uint8_t last[SPLIT_RANGE_BUCKETS];
+        /* bgzip output: the buckets deflated where they lie; a range whose members do not fit the buffer's rest comes back as
+         * text, which the writer deflates on the host */
+        int members = b->run->out_bgzf;
+        if (members && hpgv_text_multisplit_bgzf(g_ctx, b->text, b->keep + R[0], R[0], R[1], R[2], (uint8_t *)b->text + pos, b->text_cap - pos, boff, last)) members = 0;
+        if (!members) rc = hpgv_text_multisplit(g_ctx, b->text, b->keep + R[0], R[0], R[1], R[2], b->text + pos, b->text_cap - pos, boff);
         if (rc) break;
-        for (int j = 0; j < R[2]; j++) b->sp_len[k++] = boff[j + 1] - boff[j];
+        for (int j = 0; j < R[2]; j++) b->sp_len[k++] = (boff[j + 1] - boff[j]) | (members ? SP_MEMBERS | (last[j] != '\n' ? SP_NEEDS_NL : 0) : 0);
         pos += (size_t)boff[R[2]];
     }
     (void)hpgv_text_partition(g_ctx, b->text, NULL, 0, NULL, 0, NULL, NULL);     /* the hold released */
@@ -187,25 +253,64 @@ int split_partition(run_batch_t *b) {
 /* hpg-var-vcf filter: the lines of one batch in its two files.  The kept region holds no empty line; the rejected one
  * holds n_blank of them, each a '\n' at the region's start or right behind another '\n', and they go to neither file.  The
  * file's last line may lack its newline: it gets one. */
-static int write_region(FILE *f, const char *p, size_t n, int blanks) {
+typedef struct { FILE *f; char *buf; size_t len; } region_sink_t;       /* to the file, or (buf != NULL) gathered for the host's deflate */
+static int sink_put(region_sink_t *s, const char *p, size_t n) {
+    if (s->buf) { memcpy(s->buf + s->len, p, n); s->len += n; return 0; }
+    return fwrite(p, 1, n, s->f) != n;
+}
+static int region_put(region_sink_t *s, const char *p, size_t n, int blanks) {
     size_t i = 0;
     while (blanks > 0 && i < n) {
         if (p[i] == '\n') { i++; blanks--; continue; }
         const char *q = (const char *)memmem(p + i, n - i, "\n\n", 2);
         const size_t e = q ? (size_t)(q - p) + 1 : n;
-        if (fwrite(p + i, 1, e - i, f) != e - i) return 1;
+        if (sink_put(s, p + i, e - i)) return 1;
         i = e;
     }
-    if (i < n && fwrite(p + i, 1, n - i, f) != n - i) return 1;
-    if (n && p[n - 1] != '\n' && putc('\n', f) == EOF) return 1;
+    if (i < n && sink_put(s, p + i, n - i)) return 1;
+    if (n && p[n - 1] != '\n' && sink_put(s, "\n", 1)) return 1;
     return 0;
 }
+static int write_region(FILE *f, const char *p, size_t n, int blanks) {
+    region_sink_t s = { f, NULL, 0 };
+    return region_put(&s, p, n, blanks);
+}
+/* the same bytes as BGZF members, deflated on the host */
+static int write_region_bgzf(FILE *f, const char *p, size_t n, int blanks) {
+    region_sink_t s = { f, (char *)malloc(n + 1), 0 };
+    if (!s.buf) return 1;
+    const int bad = region_put(&s, p, n, blanks) || bgzf_write_text(f, s.buf, s.len);
+    free(s.buf);
+    return bad;
+}
+/* members the device made, and the newline their text's last line lacks */
+static int write_members(FILE *f, const char *p, size_t n, int needs_nl) {
+    if (n && fwrite(p, 1, n, f) != n) return 1;
+    return needs_nl && bgzf_write_text(f, "\n", 1);
+}
 int write_filter_batch(FILE *kept, FILE *rejected, const run_batch_t *b) {
-    if (write_region(kept, b->text, (size_t)b->part_kept, 0)) return 1;
-    return rejected && write_region(rejected, b->text + b->part_kept, (size_t)(b->part_total - b->part_kept), b->n_blank);
+    const size_t nk = (size_t)b->part_kept, nr = (size_t)(b->part_total - b->part_kept);
+    if (b->part_bgzf)
+        return write_members(kept, b->text, nk, b->part_last[0] != '\n') || (rejected && write_members(rejected, b->text + nk, nr, b->part_last[1] != '\n'));
+    if (b->run->out_bgzf)
+        return write_region_bgzf(kept, b->text, nk, 0) || (rejected && write_region_bgzf(rejected, b->text + nk, nr, b->n_blank));
+    if (write_region(kept, b->text, nk, 0)) return 1;
+    return rejected && write_region(rejected, b->text + nk, nr, b->n_blank);
 }
 /* the header of both files (filter_runner.c:129-137): the input's meta lines, one ##FILTER line per active filter, #CHROM */
+static int filter_header_text(FILE *f, const run_t *R);
 int write_filter_header(FILE *f, const run_t *R) {
+    if (!R->out_bgzf) return filter_header_text(f, R);
+    char *buf = NULL; size_t len = 0;                     /* the same text, as members */
+    FILE *mem = open_memstream(&buf, &len);
+    if (!mem) return 1;
+    int bad = filter_header_text(mem, R);
+    bad = fclose(mem) != 0 || bad;
+    if (!bad) bad = bgzf_write_text(f, buf, len);
+    free(buf);
+    return bad;
+}
+static int filter_header_text(FILE *f, const run_t *R) {
     const hpgv_run_filters_t *F = &R->filters;
     if (R->chrom_off && fwrite(R->hdr, 1, R->chrom_off, f) != R->chrom_off) return 1;
     if (F->min_maf >= 0.0) fprintf(f, "##FILTER=<ID=maf,Description=\"Minor allele frequency >= %g\">\n", F->min_maf);
@@ -241,7 +346,7 @@ static FILE *split_file(run_t *R, const char *name) {
         const char *dir = R->dir, *base = R->base;
         const size_t dl = strlen(dir), bl = strlen(base);
         F->name = dupn(S->key, (int)nl);                 /* the table's key */
-        F->path = (char *)malloc(dl + 3 * nl + bl + 3);
+        F->path = (char *)malloc(dl + 3 * nl + bl + 3 + 3);
         if (!F->name || !F->path) { free(F->name); free(F->path); return NULL; }
         char *p = F->path;
         memcpy(p, dir, dl); p += dl; *p++ = '/';
@@ -251,6 +356,7 @@ static FILE *split_file(run_t *R, const char *name) {
             else *p++ = name[q];
         }
         *p++ = '_'; memcpy(p, base, bl + 1);
+        if (R->out_bgzf) memcpy(p + bl, ".gz", 4);
         if (!sample_ids_put(S->ids, F->name, S->n)) { free(F->name); free(F->path); return NULL; }
         k = S->n++;
     }
@@ -272,8 +378,10 @@ static FILE *split_file(run_t *R, const char *name) {
     S->open[S->n_open++] = k;
     if (created) {
         F->created = 1; R->files++;
-        if ((R->chrom_off && fwrite(R->hdr, 1, R->chrom_off, F->fd) != R->chrom_off) ||
-            (R->rd.chrom_len && fwrite(R->rd.chrom_line, 1, R->rd.chrom_len, F->fd) != R->rd.chrom_len)) { snprintf(g_err, sizeof g_err, "cannot write %s", F->path); return NULL; }
+        const int bad = R->out_bgzf ? bgzf_write_text(F->fd, R->hdr, R->chrom_off) || bgzf_write_text(F->fd, R->rd.chrom_line, R->rd.chrom_len)
+                                    : (R->chrom_off && fwrite(R->hdr, 1, R->chrom_off, F->fd) != R->chrom_off) ||
+                                      (R->rd.chrom_len && fwrite(R->rd.chrom_line, 1, R->rd.chrom_len, F->fd) != R->rd.chrom_len);
+        if (bad) { snprintf(g_err, sizeof g_err, "cannot write %s", F->path); return NULL; }
     }
     return F->fd;
 }
@@ -283,14 +391,20 @@ int write_split_batch(run_t *R, const run_batch_t *b) {
         const char *name = b->sp_names + b->sp_name[k];
         FILE *fd = split_file(R, name);
         if (!fd) return 1;
-        if (write_region(fd, b->text + pos, (size_t)b->sp_len[k], 0)) { snprintf(g_err, sizeof g_err, "cannot write the file of %s", name); return 1; }
-        pos += (size_t)b->sp_len[k];
+        const size_t len = (size_t)SP_LEN(b->sp_len[k]);
+        const int bad = b->sp_len[k] & SP_MEMBERS ? write_members(fd, b->text + pos, len, (b->sp_len[k] & SP_NEEDS_NL) != 0)
+                      : R->out_bgzf ? write_region_bgzf(fd, b->text + pos, len, 0) : write_region(fd, b->text + pos, len, 0);
+        if (bad) { snprintf(g_err, sizeof g_err, "cannot write the file of %s", name); return 1; }
+        pos += len;
     }
     return 0;
 }
-int split_files_close(split_files_t *S) {
+/* bgzf: every file ends with the EOF block, written here once -- a file closed under the open-files rule is opened again */
+int split_files_close(split_files_t *S, int bgzf) {
     int bad = 0;
     for (int k = 0; k < S->n; k++) {
+        if (bgzf && !S->f[k].fd && S->f[k].created) S->f[k].fd = fopen(S->f[k].path, "ab");
+        if (bgzf && (!S->f[k].fd || bgzf_write_eof(S->f[k].fd)) && !bad) { bad = 1; snprintf(g_err, sizeof g_err, "cannot write %s", S->f[k].path); }
         if (S->f[k].fd && fclose(S->f[k].fd) != 0 && !bad) { bad = 1; snprintf(g_err, sizeof g_err, "cannot write %s", S->f[k].path); }
         free(S->f[k].name); free(S->f[k].path);
     }

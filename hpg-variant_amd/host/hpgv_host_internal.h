@@ -156,12 +156,15 @@ typedef struct {
     uint8_t *keep; int keep_cap;                         /* filter: record_passes per line, then the partitioned text in `text` */
     uint64_t part_kept, part_total;                      /* ... its kept bytes first, part_total bytes in all */
     long n_pass, n_rej; int n_blank;                     /* ... records kept, records rejected, empty lines (in neither file) */
+    int part_bgzf; uint8_t part_last[2];                 /* HPGV_OUT_BGZF: `text` holds the two parts' BGZF members (part_kept / part_total: their bytes); the parts' last text bytes */
     /* split: the bucket of every line in keep (SPLIT_NO_FILE: none), the line ranges of one hpgv_text_multisplit each, and per
      * bucket (over all ranges, in order) its split name and its bytes; the buckets' lines back to back in `text`.  n_pass:
      * records written, n_skip: lines that go to no file */
     int *sp_range; int sp_n_ranges, sp_range_cap;         /* per range: first line, lines, buckets */
     uint64_t *sp_len; int *sp_name; int sp_n_buckets, sp_bucket_cap;      /* per bucket: bytes, offset of its name in sp_names */
     char *sp_names; size_t sp_names_len, sp_names_cap;    /* the split names, NUL-terminated, back to back */
+    /* HPGV_OUT_BGZF: sp_len's top bits say what a bucket's bytes are -- SP_MEMBERS: BGZF members (deflated on the device),
+     * SP_NEEDS_NL: whose text lacks its last newline */
     long n_skip;
 } run_batch_t;
 
@@ -188,6 +191,9 @@ typedef struct {
 
 /* hpg-var-vcf split: the output files, by lower-cased split name (host_vcftools.c) */
 enum { SPLIT_OPEN_MAX = 64 };
+#define SP_MEMBERS (1ull << 63)
+#define SP_NEEDS_NL (1ull << 62)
+#define SP_LEN(x) ((x) & ~(SP_MEMBERS | SP_NEEDS_NL))
 typedef struct { char *name, *path; FILE *fd; long last; int created; } split_file_t;
 typedef struct { split_file_t *f; int n, cap; sample_ids_t *ids; char *key; size_t key_cap; int open[SPLIT_OPEN_MAX], n_open; long clock; } split_files_t;
 
@@ -200,6 +206,7 @@ typedef struct run {
     hpgv_run_filters_t filters;                          /* the record filters as the run started (stats, split: all off) */
     rec_filters_t *rf;                                   /* ... and those of hpgv_run_set_record_filters (NULL: all off), held by run_file */
     int overwrite, save_rejected;                        /* aggregate: AC / AF / AN replaced; filter: the others to .rejected */
+    int out_bgzf;                                        /* filter, split: hpgv_run_set_output_compression as the run started */
     int criterion, n_iv; const long *iv; const char *dir; char base[512];  /* split: HPGV_SPLIT_*, coverage bounds, <dir>/<name>_<base> */
     long written, rejected;                              /* records written; filter: records written to (or meant for) .rejected */
     long files, skipped, key_ns;                         /* split: files created, lines to no file, host time of split_keys */
@@ -334,7 +341,10 @@ int split_partition(run_batch_t *b);
 int write_filter_header(FILE *f, const run_t *R);
 int write_filter_batch(FILE *kept, FILE *rejected, const run_batch_t *b);
 int write_split_batch(run_t *R, const run_batch_t *b);
-int split_files_close(split_files_t *S);
+int split_files_close(split_files_t *S, int bgzf);
+int out_compression_now(void);                           /* the setting of hpgv_run_set_output_compression */
+size_t out_batch_cap(const struct run *R, size_t batch_bytes);      /* room a batch's buffer needs for what the tool's engine step leaves in it */
+int bgzf_write_eof(FILE *f);
 
 /* host_records.c */
 int info_dp(const char *info, size_t n, long long *v);

@@ -438,6 +438,41 @@ size_t hpgv_lines_multisplit_scratch_bytes(int n_lines, int n_buckets);
 int  hpgv_lines_multisplit_dev(hpgv_ctx *ctx, const char *d_text, const uint64_t *d_line_off, int n_lines, const uint8_t *d_bucket,
                                int n_buckets, char *d_out, uint64_t *d_bucket_off, void *d_scratch, void *stream);
 
+/* BGZF written on the device: what the filter and split runners write with HPGV_OUT_BGZF.
+ * The device primitive: d_text in n_segs segments, segment s = bytes [d_seg_off[s], d_seg_off[s + 1]) (device memory,
+ * n_segs + 1 entries).  Every segment is cut into blocks of at most HPGV_BGZF_BLOCK_TEXT bytes and every block becomes a
+ * complete BGZF member: the 18-byte header bgzip writes (MTIME 0, XFL 0, OS 255, the BC subfield with BSIZE), a raw DEFLATE
+ * payload in one final block (fixed Huffman codes; stored when that would be no smaller than the text, so that a member
+ * never exceeds 65 536 bytes), CRC-32 and ISIZE.  The members lie back to back in d_out in segment order;
+ * d_seg_out_off (device memory, n_segs + 1 entries): segment s's members are d_out[d_seg_out_off[s] .. d_seg_out_off[s + 1]),
+ * an empty segment has none.  No EOF block is written: the caller ends a file with the 28-byte constant.  The same text and
+ * segments give the same bytes on every run.  Nothing outside [d_out, d_out + d_seg_out_off[n_segs]) is stored; d_text and
+ * d_out may have any alignment.  d_out holds hpgv_bgzf_deflate_bound(text_bytes, n_segs) bytes and d_scratch
+ * hpgv_bgzf_deflate_scratch_bytes(text_bytes, n_segs) bytes of device memory (16-byte aligned), text_bytes being no less
+ * than d_seg_off[n_segs] - d_seg_off[0].  Asynchronous on `stream`. */
+#define HPGV_BGZF_BLOCK_TEXT 65280
+size_t hpgv_bgzf_deflate_bound(uint64_t text_bytes, int n_segs);
+size_t hpgv_bgzf_deflate_scratch_bytes(uint64_t text_bytes, int n_segs);
+int  hpgv_bgzf_deflate_dev(hpgv_ctx *ctx, const char *d_text, const uint64_t *d_seg_off, int n_segs, uint8_t *d_out,
+                           uint64_t *d_seg_out_off, void *d_scratch, void *stream);
+/* The same on host buffers: `text` as one segment, its members into `out`, *out_bytes = their bytes.  When they exceed
+ * out_cap the call returns HPGV_ERR_INVALID and leaves `out` untouched: hpgv_bgzf_deflate_bound(text_bytes, 1) always
+ * fits.  Synchronous; thread-safe like the other host-buffer calls. */
+int  hpgv_bgzf_compress(hpgv_ctx *ctx, const char *text, size_t text_bytes, uint8_t *out, size_t out_cap, size_t *out_bytes);
+/* hpgv_text_partition with its two parts deflated on the device before they are copied back: `out` receives the kept
+ * lines' members, then -- unless want_rest is 0: the other lines are then neither deflated nor copied -- the other lines'
+ * members.  comp_bytes[2] = the bytes of the two runs of members; kept_bytes / total_bytes are the text's, as there.
+ * last_byte[2] = the last text byte of either part ('\n' for an empty one): what a writer needs to end a file's last
+ * line.  comp_bytes and last_byte may be NULL.  Holds, group contexts and aliased windows as hpgv_text_partition; members
+ * beyond out_cap: HPGV_ERR_INVALID, `out` untouched (hpgv_bgzf_deflate_bound(total_bytes, 2) always fits). */
+int  hpgv_text_partition_bgzf(hpgv_ctx *ctx, const char *text, const uint8_t *keep, int n_lines, uint8_t *out, size_t out_cap,
+                              int want_rest, uint64_t *kept_bytes, uint64_t *total_bytes, uint64_t *comp_bytes, uint8_t *last_byte);
+/* hpgv_text_multisplit with every bucket deflated: bucket b's members are out[bucket_off[b] .. bucket_off[b + 1]), a
+ * bucket without lines has none.  last_byte (n_buckets entries, may be NULL) as above.  Releases nothing, as the plain
+ * call; hpgv_bgzf_deflate_bound(bytes of the lines, n_buckets) always fits. */
+int  hpgv_text_multisplit_bgzf(hpgv_ctx *ctx, const char *text, const uint8_t *bucket, int first_line, int n_lines, int n_buckets,
+                               uint8_t *out, size_t out_cap, uint64_t *bucket_off, uint8_t *last_byte);
+
 /* the same rows from a batch of VCF text (tokenized on the device like hpgv_assoc_text): row v of `out` belongs to
  * line v; lines that are not records (field_off[10 v + 5] == 0xFFFFFFFF) leave their row undefined */
 int  hpgv_epi_dataset_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, int max_lines, int *n_lines,

@@ -353,6 +353,16 @@ typedef struct {
 } hpgv_run_record_filters_t;
 int hpgv_run_set_record_filters(const hpgv_run_record_filters_t *f);
 
+/* The form of what hpgv_run_filter and hpgv_run_split write (the other runners ignore it): HPGV_OUT_PLAIN, the default, is
+ * text; with HPGV_OUT_BGZF the files are bgzip -- <out_prefix>.filtered.gz and <out_prefix>.rejected.gz, <out_dir>/<split
+ * name>_<base>.gz -- that tabix, bcftools and these runners read: whole BGZF members of at most 65 280 text bytes and one
+ * EOF block at the end of every file, the records deflated on the device that partitioned them.  What the files inflate to
+ * is, byte for byte, what the plain run writes.  Without save_rejected the rejected records are neither deflated nor
+ * copied, and .rejected.gz is the EOF block alone: a valid, empty bgzip file.  A run takes the setting as it is when it
+ * starts.  An unknown mode returns HPGV_ERR_INVALID and the setting stays. */
+enum { HPGV_OUT_PLAIN = 0, HPGV_OUT_BGZF = 1 };
+int hpgv_run_set_output_compression(int mode);
+
 /* run_filter (src/vcf-tools/filter/filter_runner.c:23-260, hpg-var-vcf filter): the records that pass the filters of
  * hpgv_run_set_filters to <out_prefix>.filtered, the others to <out_prefix>.rejected when save_rejected != 0 (--save-rejected,
  * main_filter.c:85; without it .rejected is created empty, filter_runner.c:63-68) -- with those of hpgv_run_set_record_filters
@@ -399,7 +409,8 @@ int  hpgv_run_filter(const char *vcf_path, const char *ped_path, const char *out
  *   - a record whose INFO has no entry with the key exactly DP, or only a bare DP flag, goes to coverage_missing (the
  *     reference crashes in atoi(NULL)); entries are ';'-separated and the first DP counts; its value is read as atoi does --
  *     an optional sign, then digits up to the first non-digit, none giving 0 -- saturated at the int64 range;
- *   - a trailing .gz / .bgz is dropped from <base>: the files hold plain text;
+ *   - a trailing .gz / .bgz is dropped from <base>: the files hold plain text by default; with
+ *     hpgv_run_set_output_compression(HPGV_OUT_BGZF) they are bgzip and named <split name>_<base>.gz;
  *   - in file names only, '/' is written %2F and '%' is written %25, so no CHROM names a path outside out_dir;
  *   - lines with fewer than 8 fields (CHROM .. INFO), empty lines included, go to no file; a sites-only VCF is valid input;
  *   - a last line without a newline gets one;
