@@ -223,3 +223,32 @@ done:
 int hpgv_host_inflate_raw(const unsigned char *in, size_t in_len, unsigned char *out, size_t out_len) {
     return fast_inflate(in, in_len, out, out_len);
 }
+
+/* ---- one BGZF block on the host: its payload inflated, its text checked ---- */
+/* HPGV_BGZF_VERIFY (default 1): every BGZF block's text is checked against the CRC-32 of its trailer, as htslib's bgzf reader
+ * and zlib's gzread do -- a damaged stream can still inflate to ISIZE bytes.  On the device path the check runs on the device
+ * (hpgv_bgzf_verify_dev); a block it rejects comes here like any block the device decoder refused, and fails the run. */
+char g_input_err[192];
+/* in[clen .. clen + 4) is the block's CRC-32 (the BGZF trailer follows the payload) */
+static int block_crc_bad(const unsigned char *in, size_t clen, const unsigned char *out, size_t isize) {
+    const unsigned char *t = in + clen;
+    const uint32_t stored = (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
+    if ((uint32_t)crc32(crc32(0L, Z_NULL, 0), out, (uInt)isize) == stored) return 0;
+    /* written by a reader / stager thread while the run may be reporting what it saw fail downstream: kept apart, and put in
+     * front when the run ends with an error (run_file) */
+    snprintf(g_input_err, sizeof g_input_err, "bgzip input: a block's text does not have the CRC-32 its trailer gives (damaged file)");
+    return 1;
+}
+int inflate_block(const unsigned char *in, size_t clen, unsigned char *out, size_t isize) {
+    if (!g_env.zlib_inflate && fast_inflate(in, clen, out, isize) == 0)       /* anything unusual: zlib decides */
+        return g_env.bgzf_verify ? block_crc_bad(in, clen, out, isize) : 0;
+    z_stream zs;
+    memset(&zs, 0, sizeof zs);
+    if (inflateInit2(&zs, -15) != Z_OK) return 1;
+    zs.next_in = (Bytef *)in; zs.avail_in = (uInt)clen;
+    zs.next_out = (Bytef *)out; zs.avail_out = (uInt)isize;
+    int bad = inflate(&zs, Z_FINISH) != Z_STREAM_END || zs.total_out != isize;
+    inflateEnd(&zs);
+    if (!bad && g_env.bgzf_verify) bad = block_crc_bad(in, clen, out, isize);
+    return bad;
+}

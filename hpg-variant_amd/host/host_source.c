@@ -100,6 +100,27 @@ int bgzf_block(const unsigned char *p, size_t avail, size_t *bsize, size_t *cdat
     return 1;
 }
 
+/* the CPU path's team tasks (host_reader.c): a segment of a plain file read, a group of BGZF blocks inflated */
+void source_task_pread(void *v, int k) {
+    source_t *s = (source_t *)v;
+    size_t off = (size_t)k * PREAD_SEG, len = off + PREAD_SEG <= s->job_want ? (size_t)PREAD_SEG : s->job_want - off;
+    while (len > 0) {
+        ssize_t got = pread(s->fd, s->job_buf + off, len, s->pos + (off_t)off);
+        if (got <= 0) { __atomic_store_n(&s->job_bad, 1, __ATOMIC_RELAXED); return; }
+        off += (size_t)got; len -= (size_t)got;
+    }
+}
+void source_task_inflate(void *v, int g) {
+    source_t *s = (source_t *)v;
+    const size_t *b_in = s->blk, *b_clen = s->blk + MAXB, *b_out = s->blk + 2 * MAXB, *b_isize = s->blk + 3 * MAXB;
+    const int nb = (int)s->job_want;
+    for (int k = g * INFLATE_GROUP; k < nb && k < (g + 1) * INFLATE_GROUP; k++) {
+        if (b_isize[k] == 0) continue;                                /* e.g. the BGZF end-of-file marker */
+        if (inflate_block(s->map + b_in[k], b_clen[k], (unsigned char *)s->job_buf + b_out[k], b_isize[k]))
+            __atomic_store_n(&s->job_bad, 1, __ATOMIC_RELAXED);
+    }
+}
+
 int source_open(source_t *s, const char *path) {
     memset(s, 0, sizeof *s);
     s->fd = open(path, O_RDONLY);
@@ -131,24 +152,10 @@ void source_close(source_t *s) {
     }
     const ctx_saved_t saved = SRC_CTX(s);
     if (s->g_started) pthread_join(s->g_thread, NULL);               /* the stager reads the mapping: it goes first */
-    if (s->u_started) {
-        pthread_mutex_lock(&s->g_mu); s->u_cancel = 1; pthread_mutex_unlock(&s->g_mu);
-        pthread_join(s->u_thread, NULL); s->u_started = 0;
-    }
+    upload_cancel(s);
     if (s->kind == SRC_BGZF && s->map_base && !s->is_part) munmap((void *)s->map_base, s->map_len);
     free(s->pend); free(s->blk);
-    if (s->g_sync) { pthread_mutex_destroy(&s->g_mu); pthread_cond_destroy(&s->g_cv); }
-    free(s->g_in_off); free(s->g_out_off); free(s->g_in_len); free(s->g_out_len);
-    if (g_ctx) {
-        if (s->d_comp) (void)hpgv_dev_free(CTX, s->d_comp);
-        if (s->d_tab) (void)hpgv_dev_free(CTX, s->d_tab);
-        if (s->d_status) (void)hpgv_dev_free(CTX, s->d_status);
-        if (s->d_text) dev_text_put(s->d_text, s->d_text_cap, s->d_text_kind);
-        if (s->d_tiles) dev_tiles_put(s->d_tiles, s->d_tiles_cap);
-        if (s->d_scan) (void)hpgv_dev_free(CTX, s->d_scan);
-        stream_put(0, s->rstream);
-        stream_put(s->c_low, s->cstream);
-    }
+    bgzf_stage_release(s);
     if (s->kind == SRC_GZIP && s->gz) gzclose(s->gz);
     if (s->fd >= 0) close(s->fd);
     ctx_back(saved);

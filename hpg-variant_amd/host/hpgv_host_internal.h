@@ -82,6 +82,8 @@ typedef struct {
 } ped_table_t;
 
 enum { SRC_RAW = 0, SRC_BGZF = 1, SRC_GZIP = 2 };
+/* a BGZF block table, a row per block: its payload's place in the file, its text's place in the decoded text */
+typedef struct { uint64_t *in_off, *out_off; uint32_t *in_len, *out_len; size_t n, cap; } bgzf_rows_t;
 
 typedef struct {
     int kind, fd;
@@ -93,14 +95,16 @@ typedef struct {
     char *job_buf; size_t job_want; int job_bad;        /* the job the team is working on */
     gzFile gz;                                          /* GZIP */
     /* BGZF decoded on the GPU: the whole file's text in device memory, handed out window by window */
-    void *d_comp, *d_tab, *d_text, *d_status, *rstream, *cstream; size_t dev_len, dev_pos; int gpu_tried;
-    uint64_t *g_in_off, *g_out_off; uint32_t *g_in_len, *g_out_len; size_t g_nb, g_done;      /* the stager's block tables */
+    void *d_comp, *d_text, *rstream, *cstream; size_t dev_len, dev_pos; int gpu_tried;
+    struct bgzf_stager *stager;                         /* the stager thread's state (host_bgzf.c), while there is one */
+    bgzf_rows_t rows;                                   /* the whole file's table, when the host has walked it */
+    size_t g_nb, g_done;                                /* blocks in the file (when known), blocks decoded (under g_mu) */
     size_t dev_ready;                                   /* text bytes decoded so far (under g_mu) */
     size_t d_text_cap; int d_text_kind;
     void *d_tiles; size_t n_tiles, d_tiles_cap;                    /* the tokenizer's tile records of the decoded text, left by the CRC check (hpgv_bgzf_verify_tiles_dev) */
     size_t text_est;                                     /* about how much text the file holds (known when the stage has chosen its path) */
     int dev_len_known;                                  /* 0 while the stager is still finding the file's blocks (under g_mu) */
-    void *d_scan;                                       /* the streaming stager's tables, statuses and scan scratch */
+    void *d_scan;                                       /* the stager's slots (rows, statuses) and the device scan's scratch */
     int c_low;                                          /* cstream (and the slots' streams) have the lowest priority */
     pthread_t g_thread; pthread_mutex_t g_mu; pthread_cond_t g_cv; int g_started, g_sync, g_err, g_finished;
     /* the uploader: the compressed file goes up from the moment it is opened, beside the walk of its block headers */
@@ -266,7 +270,7 @@ typedef struct {
     long upload_inflight;
     /* tests only */
     long test_refuse_every;          /* HPGV_TEST_GPU_INFLATE_REFUSE_EVERY: every n-th block handed back to the host decoder */
-    long test_scan_rows;             /* HPGV_TEST_SCAN_ROWS: blocks per stretch of the streaming stager */
+    long test_scan_rows;             /* HPGV_TEST_SCAN_ROWS: no stretch of the stager longer than this many blocks */
     long test_text_estimate_percent; /* HPGV_TEST_TEXT_ESTIMATE_PERCENT: the first commitment as a share of the estimate */
     long bgzf_part_min_kb;           /* HPGV_BGZF_PART_MIN_KB: smallest part of a file staged in parts (default 65536) */
 } host_env_t;
@@ -314,13 +318,19 @@ double now_s(void);
 int bgzf_block(const unsigned char *p, size_t avail, size_t *bsize, size_t *cdata_off, size_t *isize);
 int source_open(source_t *s, const char *path);
 void source_close(source_t *s);
-/* host_inflate.c */
-int fast_inflate(const unsigned char *in, size_t in_len, unsigned char *out, size_t out_len);
-/* host_bgzf.c */
-int inflate_block(const unsigned char *in, size_t clen, unsigned char *out, size_t isize);
 void source_task_pread(void *v, int k);
 void source_task_inflate(void *v, int g);
+/* host_inflate.c */
+int fast_inflate(const unsigned char *in, size_t in_len, unsigned char *out, size_t out_len);
+int inflate_block(const unsigned char *in, size_t clen, unsigned char *out, size_t isize);
+/* host_bgzf.c */
+int bgzf_rows_reserve(bgzf_rows_t *t, size_t cap);       /* room for cap rows; 0 = no memory */
+void bgzf_rows_free(bgzf_rows_t *t);
+int bgzf_walk_parallel(int fd, size_t size, bgzf_rows_t *t, size_t *text);      /* the whole file's table by a team; non-zero: walk serially */
+int bgzf_walk_serial(const unsigned char *map, size_t size, bgzf_rows_t *t, size_t *text);
 int bgzf_gpu_stage(source_t *s);
+void upload_cancel(source_t *s);
+void bgzf_stage_release(source_t *s);
 /* host_reader.c */
 size_t read_lines_dev(line_reader_t *r, char *buf, size_t bufcap, size_t cap);
 size_t read_lines(line_reader_t *r, char *buf, size_t cap);
@@ -360,7 +370,7 @@ extern pthread_rwlock_t g_cohort_lock;   /* host_engine.c */
 extern char g_err[512];   /* host_engine.c */
 extern hpgv_run_filters_t g_filters;   /* host_source.c */
 extern double g_run_times[6];   /* host_source.c */
-extern char g_input_err[192];   /* host_bgzf.c */
+extern char g_input_err[192];   /* host_inflate.c */
 extern double g_write_split[2];   /* host_format.c */
 
 #pragma GCC visibility pop

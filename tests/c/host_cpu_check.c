@@ -7,6 +7,7 @@
  *   host_cpu_check copy <in> <out> <batch_bytes> [vcf]   the runners' line reader (plain / gzip / BGZF input)
  *   host_cpu_check stage <file>       file: "N V" then V lines "chrom format s1..sN";
  *                                     prints per line: is_x then the N code bytes (hex), strict and lax
+ *   host_cpu_check blocktable <file>  a bgzip file's block table by the team walk and by the serial walk
  */
 #define _GNU_SOURCE
 #include <pthread.h>
@@ -15,6 +16,7 @@
 #include <string.h>
 
 #include "hpgv_host.h"
+#include "hpgv_host_internal.h"
 
 static int failures = 0;
 #define CHECK(c, m) do { if (!(c)) { printf("FAIL %s\n", m); failures++; } else printf("PASS %s\n", m); } while (0)
@@ -227,11 +229,52 @@ static int cmd_pageedge(void) {
     return bad ? 1 : 0;
 }
 
+/* A bgzip file's block table as the device path's stage builds it on the host, by the team walk and by the serial walk:
+ * the same rows from both, text offsets that are the running sum of the text lengths, the last block ending where the file
+ * ends.  Prints "blocktable <blocks> <text bytes>", with " serial only" when the team declined the file, or "blocktable
+ * refused" (exit 1) when neither walk takes it. */
+static int cmd_blocktable(const char *path) {
+    source_t s;
+    if (source_open(&s, path) != 0) return 2;
+    if (s.kind != SRC_BGZF) { source_close(&s); return 2; }
+    const size_t size = (size_t)s.size;
+    bgzf_rows_t team, serial;
+    memset(&team, 0, sizeof team); memset(&serial, 0, sizeof serial);
+    size_t team_text = 0, text = 0;
+    const int declined = bgzf_walk_parallel(s.fd, size, &team, &team_text) != 0;
+    const int refused = bgzf_walk_serial(s.map, size, &serial, &text) != 0;
+    int rc = 0;
+    if (refused) {
+        CHECK(declined, "a file the serial walk refuses is not taken by the team either");
+        printf("blocktable refused\n");
+        rc = 1;
+    } else {
+        const size_t n = serial.n;
+        size_t sum = 0;
+        int sums = n > 0;
+        for (size_t i = 0; i < n; i++) { sums &= serial.out_off[i] == sum; sum += serial.out_len[i]; }
+        CHECK(sums && sum == text, "out_off is the running sum of out_len");
+        CHECK(n > 0 && serial.in_off[n - 1] + serial.in_len[n - 1] + 8 == size, "the table ends at the file's end");
+        if (!declined) {
+            int same = team.n == n && team_text == text;
+            for (size_t i = 0; same && i < n; i++)
+                same = team.in_off[i] == serial.in_off[i] && team.in_len[i] == serial.in_len[i]
+                    && team.out_off[i] == serial.out_off[i] && team.out_len[i] == serial.out_len[i];
+            CHECK(same, "team walk and serial walk give the same rows");
+        }
+        printf("blocktable %zu %zu%s\n", n, text, declined ? " serial only" : "");
+    }
+    bgzf_rows_free(&team); bgzf_rows_free(&serial);
+    source_close(&s);
+    return failures ? 3 : rc;
+}
+
 int main(int argc, char **argv) {
     if (argc >= 2 && !strcmp(argv[1], "containers")) return cmd_containers();
     if (argc >= 2 && !strcmp(argv[1], "pageedge")) return cmd_pageedge();
     if (argc >= 2 && !strcmp(argv[1], "inflate")) return cmd_inflate();
     if (argc >= 3 && !strcmp(argv[1], "stage")) return cmd_stage(argv[2]);
+    if (argc >= 3 && !strcmp(argv[1], "blocktable")) return cmd_blocktable(argv[2]);
     if (argc >= 3 && !strcmp(argv[1], "sort")) return hpgv_host_sort_output_file(argv[2]);
     if (argc >= 5 && !strcmp(argv[1], "copy")) {
         long nb = 0;

@@ -494,6 +494,50 @@ def test_run_assoc_from_bgzf_decoded_on_the_gpu(host, tmp_path, capfd):
             assert rc != 0, (tag, env, n.value)
 
 
+def test_run_assoc_bgzf_host_table_feeds_the_stager(host, tmp_path, capfd):
+    # the block table walked on the host (HPGV_BGZF_HOST_TABLE=1) is a source of rows for the same stager that the device scan
+    # feeds: blocks the device decoder refuses are patched in from it, and a table of 3 300 blocks cut into stretches of 300
+    # goes through the four slots in a dozen launches -- same result file as from the plain text every time
+    from test_host_logic_cpu import _bgzf
+    rng = np.random.default_rng(17)
+    people, names, rows = _write_inputs(tmp_path, rng, 50, 40, 4500)
+    vcf = _vcf_from_batch(tmp_path, names, rows)
+    data = open(vcf, "rb").read()
+    packed = str(tmp_path / "in.vcf.gz")
+    open(packed, "wb").write(_bgzf(data, 0x700))
+    n_blocks = -(-len(data) // 0x700)
+    assert 3200 < n_blocks < 3 * 4096 and len(names) > 60           # one launch unless the stretches are cut short
+    ped = str(tmp_path / "ped.txt").encode()
+
+    def run(path, tag, env):
+        os.environ.update(env)
+        try:
+            out = str(tmp_path / ("res_" + tag))
+            n = C.c_long(0)
+            rc = host.hpgv_run_assoc(path.encode(), ped, out.encode(), 1, 1 << 17, C.byref(n))
+            assert rc == 0 and n.value == len(rows), host.hpgv_host_last_error()
+            return open(out, "rb").read()
+        finally:
+            for k in env:
+                del os.environ[k]
+    plain = run(vcf, "plain", {})
+    assert plain.count(b"\n") == len(rows) + 1
+    table = {"HPGV_BGZF_HOST_TABLE": "1", "HPGV_RUN_TRACE": "1"}
+    capfd.readouterr()
+    assert run(packed, "patched", dict(table, HPGV_TEST_GPU_INFLATE_REFUSE_EVERY="7")) == plain
+    err = capfd.readouterr().err
+    assert "stage: walk" in err and "blocks found" not in err and err.count("is up, to byte") == 1
+    assert run(packed, "stretches", dict(table, HPGV_TEST_SCAN_ROWS="300")) == plain
+    err = capfd.readouterr().err
+    assert "stage: walk" in err and "serial walk" not in err and "blocks found" not in err
+    assert err.count("is up, to byte") == -(-n_blocks // 300) >= 10
+    assert run(packed, "stretches_patched", dict(table, HPGV_TEST_SCAN_ROWS="300", HPGV_TEST_GPU_INFLATE_REFUSE_EVERY="7")) == plain
+    assert capfd.readouterr().err.count("is up, to byte") >= 10
+    assert run(packed, "serial_stretches", {"HPGV_SERIAL_BGZF_WALK": "1", "HPGV_TEST_SCAN_ROWS": "300", "HPGV_RUN_TRACE": "1"}) == plain
+    err = capfd.readouterr().err
+    assert "serial walk" in err and "blocks found" not in err and err.count("is up, to byte") >= 10
+
+
 def test_run_assoc_bgzf_text_buffer_grows_during_the_run(host, tmp_path, capfd):
     # a text that outgrows what was committed for it when its first blocks were seen (here: the estimate cut to 30 %): the
     # device buffer grows -- more pieces mapped into its address range -- while the pipeline reads what is already there

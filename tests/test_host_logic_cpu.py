@@ -193,3 +193,60 @@ def test_deflate_decoder_against_zlib_under_sanitizers(exe):
     r = _run(exe, "inflate")
     assert r.returncode == 0 and "inflate ok" in r.stdout, r.stdout + r.stderr
     assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr
+
+
+def _bgzf_stored(ch):
+    """one BGZF block holding `ch` uncompressed (deflate level 0)"""
+    import struct
+    import zlib
+    co = zlib.compressobj(0, zlib.DEFLATED, -15)
+    comp = co.compress(ch) + co.flush()
+    return (b"\x1f\x8b\x08\x04\0\0\0\0\0\xff" + struct.pack("<H", 6) + b"BC" + struct.pack("<HH", 2, 12 + 6 + len(comp) + 8 - 1)
+            + comp + struct.pack("<II", zlib.crc32(ch), len(ch)))
+
+
+def _walk_bgzf(blob):
+    """(blocks, text bytes) of a well-formed BGZF file, from its headers' BC fields and its trailers' ISIZE"""
+    pos = n = text = 0
+    while pos < len(blob):
+        assert blob[pos:pos + 4] == b"\x1f\x8b\x08\x04"
+        off, bsize = pos + 12, None
+        end = off + int.from_bytes(blob[pos + 10:pos + 12], "little")
+        while off + 4 <= end:
+            slen = int.from_bytes(blob[off + 2:off + 4], "little")
+            if blob[off:off + 2] == b"BC" and slen == 2:
+                bsize = int.from_bytes(blob[off + 4:off + 6], "little") + 1
+            off += 4 + slen
+        text += int.from_bytes(blob[pos + bsize - 4:pos + bsize], "little")
+        pos += bsize
+        n += 1
+    assert pos == len(blob)
+    return n, text
+
+
+def test_block_table_team_walk_equals_serial_walk(exe, tmp_path):
+    # the table the device path's stager takes its rows from when the host builds it: by the team (64 segments, pread) and by
+    # one thread (the mapping), row for row the same, and the same block count and text length as a walk of the file here
+    rng = np.random.default_rng(19)
+    data = bytes(rng.integers(48, 58, size=1_500_000, dtype=np.uint8))
+    even = _bgzf(data)
+    assert len(even) >= 64 * 4096                                    # under that the team leaves the file to the serial walk
+    # blocks of very different sizes: a stored 64 KB block spans more than two of the 64 segments, so some hold no block start
+    n_big, big = 10, 0xfe00
+    mixed = b"".join(_bgzf_stored(data[i * big:(i + 1) * big]) for i in range(n_big)) + _bgzf(data[n_big * big:n_big * big + 300 * 0x700], 0x700)
+    assert len(mixed) >= 64 * 4096 and len(mixed) // 64 < big // 2
+    for tag, blob in (("even", even), ("mixed", mixed)):
+        (tmp_path / tag).write_bytes(blob)
+        r = _run(exe, "blocktable", str(tmp_path / tag))
+        assert r.returncode == 0 and "FAIL" not in r.stdout, r.stdout + r.stderr
+        assert "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr
+        last = r.stdout.strip().splitlines()[-1].split()
+        assert last[0] == "blocktable" and (int(last[1]), int(last[2])) == _walk_bgzf(blob), (tag, last)
+        assert "serial only" not in r.stdout, tag                    # both files are over the team's floor: it must take them
+        assert "team walk and serial walk give the same rows" in r.stdout
+    cut = even[:len(even) * 2 // 3 + 5]                              # cut off inside a block: neither walk takes it
+    assert len(cut) >= 64 * 4096
+    (tmp_path / "cut").write_bytes(cut)
+    r = _run(exe, "blocktable", str(tmp_path / "cut"))
+    assert r.returncode == 1 and "blocktable refused" in r.stdout and "FAIL" not in r.stdout, r.stdout + r.stderr
+    assert "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr
