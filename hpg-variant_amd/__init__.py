@@ -21,10 +21,11 @@ TASK_CHISQ, TASK_FISHER = 1, 2
 EPI_TESTING, EPI_TRAINING = 0, 1
 # the scan kernel a ranking call ran (hpgv_epi_last_rank_info; HPGV_EPI_KERNEL_* of include/hpgv.h)
 (EPI_KERNEL_NONE, EPI_KERNEL_PAIRS_MFMA, EPI_KERNEL_PAIRS_VALU, EPI_KERNEL_TRIPLES_MFMA, EPI_KERNEL_TRIPLES3, EPI_KERNEL_TRIPLES1,
- EPI_KERNEL_TRIPLES, EPI_KERNEL_COMBS) = range(8)
+ EPI_KERNEL_TRIPLES, EPI_KERNEL_COMBS, EPI_KERNEL_COMBS_WIDE) = range(9)
 EPI_KERNEL_NAMES = {EPI_KERNEL_NONE: "none", EPI_KERNEL_PAIRS_MFMA: "k_epi_pairs_mfma", EPI_KERNEL_PAIRS_VALU: "k_epi_pairs",
                     EPI_KERNEL_TRIPLES_MFMA: "k_epi_triples_mfma", EPI_KERNEL_TRIPLES3: "k_epi_triples3",
-                    EPI_KERNEL_TRIPLES1: "k_epi_triples1", EPI_KERNEL_TRIPLES: "k_epi_triples", EPI_KERNEL_COMBS: "k_epi_combs"}
+                    EPI_KERNEL_TRIPLES1: "k_epi_triples1", EPI_KERNEL_TRIPLES: "k_epi_triples", EPI_KERNEL_COMBS: "k_epi_combs",
+                    EPI_KERNEL_COMBS_WIDE: "k_epi_combs_wide"}
 COND_UNAFFECTED, COND_AFFECTED, COND_OTHER = 0, 1, 2
 SEX_MALE, SEX_FEMALE, SEX_UNKNOWN = 0, 1, 2
 LAYOUT_ASSOC, LAYOUT_TDT, LAYOUT_STATS, LAYOUT_STATS_GROUPS, LAYOUT_MENDEL, LAYOUT_EPI = 0, 1, 2, 3, 4, 5

@@ -17,6 +17,7 @@ void epi_free_folds(EpiState &E) {
     if (E.d_group_w0) (void)hipFree(E.d_group_w0);
     E.rev_off = 0;
     E.d_planes = nullptr; E.d_chunks = nullptr; E.d_folds = nullptr; E.d_group_w0 = nullptr;
+    E.n_chunks = 0; E.wide_only = false; E.fold_cap = 0;
     E.have_folds = false;
 }
 
@@ -36,6 +37,7 @@ void epi_free(EpiState &E) {
     if (E.d_tile_base) (void)hipFree(E.d_tile_base);
     E.d_tile_base = nullptr; E.tile_base_cap = 0;
     E.d_data = nullptr; E.d_cand = nullptr; E.d_cand_count = nullptr; E.d_thr = nullptr;
+    E.rank_fold_cap = 0;
     E.have_data = false;
 }
 
@@ -53,11 +55,17 @@ int epi_build_folds(hpgv_ctx *ctx, const int32_t *fold_of_sample, int num_folds)
     }
     std::vector<int32_t> src;
     std::vector<uint32_t> w0((size_t)num_folds * 2 + 1);
-    std::vector<int32_t> gsize(hpgv::EPI_MAX_FOLDS * 2, -1);
+    // past the packed kernels (option "epi_wide"): more folds than their tables hold, or a group too large for 16-bit counts
+    bool wide_only = num_folds > hpgv::EPI_MAX_FOLDS;
+    const int fold_cap = std::max(num_folds, hpgv::EPI_MAX_FOLDS);
+    std::vector<int32_t> gsize((size_t)fold_cap * 2, -1);
     std::vector<int> group_of_step;                                  // per 4-word step: the group it belongs to
     for (int g = 0; g < num_folds * 2; ++g) {
         const auto &m = members[(size_t)g];
-        if (m.size() >= 65536) return fail(ctx, HPGV_ERR_UNSUPPORTED, "%zu samples of one class in one fold: the pair scan keeps 16-bit counts per (fold, class)", m.size());
+        if (m.size() >= 65536) {
+            if (ctx->epi_wide < 1) return fail(ctx, HPGV_ERR_UNSUPPORTED, "%zu samples of one class in one fold: the pair scan keeps 16-bit counts per (fold, class)", m.size());
+            wide_only = true;
+        }
         gsize[(size_t)g] = (int32_t)m.size();
         w0[(size_t)g] = (uint32_t)(src.size() / 32);
         src.insert(src.end(), m.begin(), m.end());
@@ -72,9 +80,10 @@ int epi_build_folds(hpgv_ctx *ctx, const int32_t *fold_of_sample, int num_folds)
     w0[(size_t)num_folds * 2] = (uint32_t)(src.size() / 32);
     // staging blocks of up to EPI_CH words; a block may hold the runs of several groups: byte s of `flush` names the
     // group whose run ends with the block's step s
+    // (a wide-only layout has none: its kernel walks the groups' word runs by d_group_w0; the flush bytes name groups below 255)
     std::vector<hpgv::EpiChunk> chunks;
     std::vector<uint32_t> chunk_cls;
-    const size_t n_steps = group_of_step.size(), steps_per_block = hpgv::EPI_CH / 4;
+    const size_t n_steps = wide_only ? 0 : group_of_step.size(), steps_per_block = hpgv::EPI_CH / 4;
     for (size_t s0 = 0; s0 < n_steps; s0 += steps_per_block) {
         hpgv::EpiChunk c;
         const size_t ns = n_steps - s0 < steps_per_block ? n_steps - s0 : steps_per_block;
@@ -90,6 +99,8 @@ int epi_build_folds(hpgv_ctx *ctx, const int32_t *fold_of_sample, int num_folds)
     }
     E.W = (int)(src.size() / 32);
     E.num_folds = num_folds;
+    E.wide_only = wide_only;
+    E.fold_cap = fold_cap;
     E.n_chunks = (int)chunks.size();
     E.group_size = gsize;
     E.V_alloc = (E.V + 63) / 64 * 64 + 64;                           // whole tiles past the last SNP read zero planes
@@ -101,7 +112,7 @@ int epi_build_folds(hpgv_ctx *ctx, const int32_t *fold_of_sample, int num_folds)
     // + slack: the LDS-DMA staging fetches whole 32-word rows.  Behind the planes, while the scans' 32-bit word offsets reach it, their
     // copy with bits 0 and 2 of every nibble swapped (epm_swap02, hpgv_epi_mfma_kernels.h: the matrix-core scans' column side)
     const size_t plane_words = (size_t)E.V_alloc * 3 * (size_t)E.W + hpgv::EPI_CH;
-    E.rev_off = 2 * plane_words < (1ull << 32) ? (uint32_t)plane_words : 0u;
+    E.rev_off = !wide_only && 2 * plane_words < (1ull << 32) ? (uint32_t)plane_words : 0u;
     if (e == hipSuccess) {
         e = hipMalloc(&E.d_planes, (plane_words + E.rev_off) * sizeof(uint32_t));
         if (e != hipSuccess && E.rev_off) {                          // no room for the copy: the vector-ALU scans do without it
@@ -110,16 +121,16 @@ int epi_build_folds(hpgv_ctx *ctx, const int32_t *fold_of_sample, int num_folds)
             e = hipMalloc(&E.d_planes, plane_words * sizeof(uint32_t));
         }
     }
-    if (e == hipSuccess) e = hipMalloc(&E.d_chunks, chunks.size() * sizeof(hpgv::EpiChunk));
-    if (e == hipSuccess) e = hipMemcpy(E.d_chunks, chunks.data(), chunks.size() * sizeof(hpgv::EpiChunk), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc(&E.d_chunk_cls, chunk_cls.size() * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemcpy(E.d_chunk_cls, chunk_cls.data(), chunk_cls.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc(&E.d_folds, hpgv::EPI_MAX_FOLDS * sizeof(hpgv::EpiFold));
+    if (e == hipSuccess && !wide_only) e = hipMalloc(&E.d_chunks, chunks.size() * sizeof(hpgv::EpiChunk));
+    if (e == hipSuccess && !wide_only) e = hipMemcpy(E.d_chunks, chunks.data(), chunks.size() * sizeof(hpgv::EpiChunk), hipMemcpyHostToDevice);
+    if (e == hipSuccess && !wide_only) e = hipMalloc(&E.d_chunk_cls, chunk_cls.size() * sizeof(uint32_t));
+    if (e == hipSuccess && !wide_only) e = hipMemcpy(E.d_chunk_cls, chunk_cls.data(), chunk_cls.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc(&E.d_folds, (size_t)fold_cap * sizeof(hpgv::EpiFold));
     if (e == hipSuccess) e = hipMalloc(&E.d_group_w0, w0.size() * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMemcpy(E.d_group_w0, w0.data(), w0.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
     unsigned *d_flag = nullptr;
     unsigned flag = 1;
-    if (e == hipSuccess) e = hipMalloc(&E.d_marg, (size_t)E.V_alloc * 2 * hpgv::EPI_MAX_FOLDS * sizeof(uint32_t));
+    if (e == hipSuccess && !wide_only) e = hipMalloc(&E.d_marg, (size_t)E.V_alloc * 2 * hpgv::EPI_MAX_FOLDS * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMalloc(&d_flag, sizeof(unsigned));
     if (e == hipSuccess) e = hipMemset(d_flag, 0, sizeof(unsigned));
     if (e == hipSuccess) {
@@ -128,7 +139,7 @@ int epi_build_folds(hpgv_ctx *ctx, const int32_t *fold_of_sample, int num_folds)
         else
             hipLaunchKernelGGL(hpgv::k_epi_planes_gather, dim3((unsigned)E.V_alloc), dim3(256), 0, nullptr, E.d_data, E.V, n, d_src, E.W, E.d_planes, d_flag);
         // genotype counts per SNP and group: what the complete-data pair scan derives the cells with a genotype 2 from
-        hipLaunchKernelGGL(hpgv::k_epi_marginals, dim3((unsigned)E.V_alloc), dim3(256), 0, nullptr, E.d_planes, E.W, E.d_group_w0, num_folds * 2, E.d_marg);
+        if (!wide_only) hipLaunchKernelGGL(hpgv::k_epi_marginals, dim3((unsigned)E.V_alloc), dim3(256), 0, nullptr, E.d_planes, E.W, E.d_group_w0, num_folds * 2, E.d_marg);
         if (E.rev_off)                                               // the column side's copy for the matrix-core pair scan
             hipLaunchKernelGGL(hpgv::k_epi_planes_rev, dim3((unsigned)((plane_words + 255) / 256)), dim3(256), 0, nullptr, E.d_planes, plane_words, E.d_planes + E.rev_off);
         e = hipGetLastError();
@@ -252,7 +263,8 @@ int hpgv_epi_set_dataset(hpgv_ctx *ctx, const uint8_t *genotypes, int n_variants
     E.have_data = true;
     // until folds are given: one fold holding everybody -- unless a class is too large for one (fold, class) group of 16-bit
     // counts; such a cohort is scanned after hpgv_epi_set_folds splits it
-    if (n_affected >= 65536 || n_unaffected >= 65536) return HPGV_OK;
+    // (with option "epi_wide" that one group is a wide-only layout)
+    if ((n_affected >= 65536 || n_unaffected >= 65536) && ctx->epi_wide < 1) return HPGV_OK;
     return epi_build_folds(ctx, nullptr, 1);
 }
 
@@ -261,7 +273,8 @@ int hpgv_epi_set_folds(hpgv_ctx *ctx, const int32_t *fold_of_sample, int num_fol
     ctx = first_member(ctx);
     if (!ctx) return HPGV_ERR_INVALID;
     if (!ctx->epi.have_data) return fail(ctx, HPGV_ERR_STATE, "hpgv_epi_set_dataset has not been called");
-    if (num_folds < 1 || num_folds > hpgv::EPI_MAX_FOLDS) return fail(ctx, HPGV_ERR_UNSUPPORTED, "num_folds must be in [1, %d]", hpgv::EPI_MAX_FOLDS);
+    const int max_folds = ctx->epi_wide >= 1 ? hpgv::EPI_WIDE_MAX_FOLDS : hpgv::EPI_MAX_FOLDS;
+    if (num_folds < 1 || num_folds > max_folds) return fail(ctx, HPGV_ERR_UNSUPPORTED, "num_folds must be in [1, %d]", max_folds);
     if (!fold_of_sample && ctx->epi.nA + ctx->epi.nU > 0) return fail(ctx, HPGV_ERR_INVALID, "fold_of_sample is NULL");
     DeviceGuard g(ctx->device);
     std::lock_guard<std::mutex> lk(ctx->epi_mu);
@@ -275,7 +288,7 @@ int hpgv_epi_set_fold_masks(hpgv_ctx *ctx, const uint8_t *fold_masks, int num_fo
     ctx = first_member(ctx);
     if (!ctx) return HPGV_ERR_INVALID;
     if (!ctx->epi.have_data) return fail(ctx, HPGV_ERR_STATE, "hpgv_epi_set_dataset has not been called");
-    if (num_folds < 1 || num_folds > hpgv::EPI_MAX_FOLDS || !fold_masks) return fail(ctx, HPGV_ERR_INVALID, "bad fold mask arguments");
+    if (num_folds < 1 || num_folds > (ctx->epi_wide >= 1 ? hpgv::EPI_WIDE_MAX_FOLDS : hpgv::EPI_MAX_FOLDS) || !fold_masks) return fail(ctx, HPGV_ERR_INVALID, "bad fold mask arguments");
     const int nA = ctx->epi.nA, nU = ctx->epi.nU;
     const size_t padA = ((size_t)nA + 15) / 16 * 16, padded = padA + ((size_t)nU + 15) / 16 * 16;   // masks_info_init, model.c:212-214
     std::vector<int32_t> fold((size_t)(nA + nU), -1);
@@ -314,9 +327,10 @@ static int epi_infold_counts(hpgv_ctx *ctx, int order, const int32_t *combs, int
     if (e == hipSuccess) {
         const dim3 grid((unsigned)((n_combs + 3) / 4));
         int rc4 = HPGV_OK;
-        if (order == 2) hipLaunchKernelGGL((hpgv::k_epi_counts<2>), grid, dim3(256), 0, nullptr, E.d_planes, E.W, d_combs, n_combs, E.d_group_w0, ng, d_out);
-        else if (order == 3) hipLaunchKernelGGL((hpgv::k_epi_counts<3>), grid, dim3(256), 0, nullptr, E.d_planes, E.W, d_combs, n_combs, E.d_group_w0, ng, d_out);
-        else rc4 = hpgv_epi_generic_counts(ctx, order, d_combs, n_combs, d_out);      // one lane per cell (hpgv_epi_generic_kernels.h)
+        // past the packed kernels (or with "epi_wide" = 2) every order goes to the listed-combination launcher: its wide kernel
+        if (order >= 4 || epi_needs_wide(ctx) || ctx->epi_wide == 2) rc4 = hpgv_epi_generic_counts(ctx, order, d_combs, n_combs, d_out);      // one lane per cell (hpgv_epi_generic_kernels.h)
+        else if (order == 2) hipLaunchKernelGGL((hpgv::k_epi_counts<2>), grid, dim3(256), 0, nullptr, E.d_planes, E.W, d_combs, n_combs, E.d_group_w0, ng, d_out);
+        else hipLaunchKernelGGL((hpgv::k_epi_counts<3>), grid, dim3(256), 0, nullptr, E.d_planes, E.W, d_combs, n_combs, E.d_group_w0, ng, d_out);
         e = hipGetLastError();
         if (rc4) return rc4;
     }
@@ -395,6 +409,7 @@ int hpgv_epi_scan_pairs(hpgv_ctx *ctx, int i_begin, int i_end, int subset, doubl
     if (!ctx) return HPGV_ERR_INVALID;
     EpiState &E = ctx->epi;
     if (int rc = epi_check(ctx, subset)) return rc;
+    if (E.wide_only) return epi_refuse_dense_wide(ctx, "pair");
     if (i_begin < 0 || i_end < i_begin || i_end > E.V) return fail(ctx, HPGV_ERR_INVALID, "rows [%d, %d) outside the dataset", i_begin, i_end);
     const unsigned long long V = (unsigned long long)E.V;
     const unsigned long long base = epi_rank(V, (unsigned long long)i_begin);
@@ -480,6 +495,7 @@ int hpgv_epi_pairs_models(hpgv_ctx *ctx, int i_begin, int i_end, int subset, int
         return fail(ctx, HPGV_ERR_INVALID, "rows [%d, %d): the band must lie in the dataset and start on a multiple of 64", i_begin, i_end);
     if (int rc = epi_check(ctx, subset)) return rc;
     if (N < 1 || N > 65536 || !have_outputs) return fail(ctx, HPGV_ERR_INVALID, "bad ranking arguments");
+    if (E.wide_only) return hpgv_epi_order_models(ctx, 2, i_begin, i_end, subset, N, have_outputs, out, scan_ms);      // no pair scan reads a wide-only layout
     DeviceGuard g(ctx->device);
     std::lock_guard<std::mutex> lk(ctx->epi_mu);
     EpiPairOrder o(ctx, subset, i_begin, i_end, N);
@@ -662,9 +678,10 @@ int hpgv_epi_scan_triples(hpgv_ctx *ctx, int subset, double *accuracy, uint32_t 
     HPGV_ABI_TRY
     ctx = first_member(ctx);
     if (!ctx) return HPGV_ERR_INVALID;
+    EpiState &E = ctx->epi;
+    if (E.have_folds && E.wide_only) return epi_refuse_dense_wide(ctx, "triple");
     int rc = epi_triples_check(ctx, subset);
     if (rc) return rc;
-    EpiState &E = ctx->epi;
     if (!accuracy || !risky_mask) return fail(ctx, HPGV_ERR_INVALID, "outputs are NULL");
     if (E.V > 256) return fail(ctx, HPGV_ERR_UNSUPPORTED, "the dense triple scan is for small sets (<= 256 SNPs); use hpgv_epi_rank_triples");
     DeviceGuard g(ctx->device);
@@ -679,6 +696,8 @@ int hpgv_epi_scan_triples(hpgv_ctx *ctx, int subset, double *accuracy, uint32_t 
 }
 
 int hpgv_epi_triples_models(hpgv_ctx *ctx, int i_begin, int i_end, int subset, int N, bool have_outputs, std::vector<EpiModel> &out, float *scan_ms) {
+    // classes or groups past the 16-bit counts, or more than EPI_MAX_FOLDS folds: the any-order ranking at order 3 (k_epi_combs_wide)
+    if (ctx->epi.have_folds && epi_needs_wide(ctx)) return hpgv_epi_order_models(ctx, 3, i_begin, i_end, subset, N, have_outputs, out, scan_ms);
     if (int rc = epi_triples_check(ctx, subset)) return rc;
     if (i_begin < 0 || i_end < i_begin || i_end > ctx->epi.V) return fail(ctx, HPGV_ERR_INVALID, "first SNPs [%d, %d) outside the dataset", i_begin, i_end);
     if (N < 1 || N > 65536 || !have_outputs) return fail(ctx, HPGV_ERR_INVALID, "bad ranking arguments");

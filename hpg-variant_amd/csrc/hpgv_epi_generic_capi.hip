@@ -6,13 +6,14 @@
 // hpgv_epi_capi.hip compile for minutes.
 #include "hpgv_epi_host.h"
 #include "hpgv_epi_generic_kernels.h"
+#include "hpgv_epi_wide_kernels.h"
 
 namespace {
 
 int generic_check(hpgv_ctx *ctx, int order) {
     EpiState &E = ctx->epi;
     if (order < 2 || order > 5) return fail(ctx, HPGV_ERR_UNSUPPORTED, "combinations of %d SNPs are not supported (2 to 5)", order);
-    if (E.nA > 65535 || E.nU > 65535) return fail(ctx, HPGV_ERR_UNSUPPORTED, "the listed-combination kernel keeps 16-bit class totals: at most 65535 samples per class");
+    if ((E.nA > 65535 || E.nU > 65535) && !epi_needs_wide(ctx)) return fail(ctx, HPGV_ERR_UNSUPPORTED, "the listed-combination kernel keeps 16-bit class totals: at most 65535 samples per class");
     return HPGV_OK;
 }
 
@@ -22,10 +23,30 @@ int launch_combs(hpgv_ctx *ctx, int order, bool training, const int32_t *d_combs
     EpiState &E = ctx->epi;
     if (n_combs <= 0) return HPGV_OK;
     const hpgv::EpiFold *folds = evaluate ? E.d_folds : nullptr;
+    // the wide kernel (hpgv_epi_wide_kernels.h) where the packed one's 16-bit halves or fold arrays do not hold the shape, and
+    // everywhere with option "epi_wide" = 2
+    const bool wide = epi_needs_wide(ctx) || ctx->epi_wide == 2;
     if (d_cand) {                                                    // a ranking call's launch (hpgv_epi_last_rank_info)
-        E.rank_info.kernel = HPGV_EPI_KERNEL_COMBS;
+        E.rank_info.kernel = wide ? HPGV_EPI_KERNEL_COMBS_WIDE : HPGV_EPI_KERNEL_COMBS;
         ++E.rank_info.launches;
     }
+#define HPGV_COMBS_WIDE(ORD, TR)                                                                                                  \
+    hipLaunchKernelGGL((hpgv::k_epi_combs_wide<ORD, TR>), dim3((unsigned)((n_combs + (256 / hpgv::EpiCells<ORD>::value) - 1) / (256 / hpgv::EpiCells<ORD>::value))), \
+                       dim3(256), hpgv::epi_wide_lds_bytes<ORD>(E.num_folds), nullptr, E.d_planes, E.W, d_combs, n_combs, E.d_group_w0, E.num_folds, folds, E.nA, E.nU, \
+                       d_counts, d_acc, d_mask, d_thr, d_cand, d_cand_count, cap)
+#define HPGV_COMBS_WIDE_T(ORD) do { if (training) HPGV_COMBS_WIDE(ORD, true); else HPGV_COMBS_WIDE(ORD, false); } while (0)
+    if (wide) {
+        switch (order) {
+            case 2: HPGV_COMBS_WIDE_T(2); break;
+            case 3: HPGV_COMBS_WIDE_T(3); break;
+            case 4: HPGV_COMBS_WIDE_T(4); break;
+            default: HPGV_COMBS_WIDE_T(5); break;
+        }
+        HIPCHK(ctx, hipGetLastError());
+        return HPGV_OK;
+    }
+#undef HPGV_COMBS_WIDE_T
+#undef HPGV_COMBS_WIDE
 #define HPGV_COMBS(ORD, TR)                                                                                                       \
     hipLaunchKernelGGL((hpgv::k_epi_combs<ORD, TR>), dim3((unsigned)((n_combs + (256 / hpgv::EpiCells<ORD>::value) - 1) / (256 / hpgv::EpiCells<ORD>::value))), \
                        dim3(256), 0, nullptr, E.d_planes, E.W, d_combs, n_combs, E.d_group_w0, E.num_folds, folds, E.nA, E.nU, d_counts, \

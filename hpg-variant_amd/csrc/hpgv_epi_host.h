@@ -46,6 +46,17 @@ inline int epi_check_folds(const hpgv_ctx *ctx) {
     if (!ctx->epi.have_folds) return fail(ctx, HPGV_ERR_STATE, "no folds: hpgv_epi_set_dataset has not been called, or a class of 65536 samples or more waits for hpgv_epi_set_folds");
     return HPGV_OK;
 }
+// the shape is past the packed kernels (16-bit counts per group and per class, EPI_MAX_FOLDS folds): its listed-combination
+// launches are k_epi_combs_wide, and its triple (and, for a wide-only layout, pair) rankings go through the any-order ranking.
+// A wide-only layout exists only because option "epi_wide" allowed it; it stays wide whatever the option says later.
+inline bool epi_needs_wide(const hpgv_ctx *ctx) {
+    const EpiState &E = ctx->epi;
+    return E.wide_only || (ctx->epi_wide >= 1 && (E.nA > 65535 || E.nU > 65535));
+}
+inline int epi_refuse_dense_wide(const hpgv_ctx *ctx, const char *what) {
+    return fail(ctx, HPGV_ERR_UNSUPPORTED, "the dense %s scan does not take a wide layout (more than %d folds, or 65536 samples or more of one class in one fold): evaluate listed combinations with hpgv_epi_eval_combs",
+                what, hpgv::EPI_MAX_FOLDS);
+}
 inline int epi_check_subset(const hpgv_ctx *ctx, int subset) {
     if (subset != HPGV_EPI_TESTING && subset != HPGV_EPI_TRAINING) return fail(ctx, HPGV_ERR_INVALID, "subset must be HPGV_EPI_TESTING or HPGV_EPI_TRAINING");
     return HPGV_OK;
@@ -59,13 +70,13 @@ inline int epi_check(const hpgv_ctx *ctx, int subset) {
 // the scan kernels' evaluation
 inline int epi_upload_folds(hpgv_ctx *ctx, bool training, hipStream_t st) {
     EpiState &E = ctx->epi;
-    hpgv::EpiFold folds[hpgv::EPI_MAX_FOLDS];
-    for (int f = 0; f < hpgv::EPI_MAX_FOLDS; ++f) {
+    hpgv::EpiFold folds[hpgv::EPI_WIDE_MAX_FOLDS];
+    for (int f = 0; f < E.fold_cap; ++f) {                           // (slots past num_folds: test_a = -1, unused)
         folds[f].test_a = E.group_size[(size_t)2 * f]; folds[f].test_u = E.group_size[(size_t)2 * f + 1];
         const int sa = training ? E.nA - folds[f].test_a : folds[f].test_a, su = training ? E.nU - folds[f].test_u : folds[f].test_u;
         folds[f].inv_a = 1.0 / (double)sa; folds[f].inv_u = 1.0 / (double)su;
     }
-    HIPCHK(ctx, hipMemcpyAsync(E.d_folds, folds, sizeof folds, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(E.d_folds, folds, (size_t)E.fold_cap * sizeof(hpgv::EpiFold), hipMemcpyHostToDevice, st));
     return HPGV_OK;
 }
 
@@ -85,24 +96,30 @@ int epi_rank_loop(hpgv_ctx *ctx, Order &o, int N, std::vector<EpiModel> &out, fl
     EpiState &E = ctx->epi;
     E.rank_info = hpgv_epi_rank_info{};
     if (int rc = o.setup()) return rc;
-    if (!E.d_cand_count) HIPCHK(ctx, hipMalloc(&E.d_cand_count, hpgv::EPI_MAX_FOLDS * sizeof(unsigned)));
-    if (!E.d_thr) HIPCHK(ctx, hipMalloc(&E.d_thr, hpgv::EPI_MAX_FOLDS * sizeof(double)));
-    const int nf = E.num_folds;
+    const int nf = E.num_folds, slots = E.fold_cap;                  // the kernels instantiated per fold count read `slots` thresholds
+    if (E.rank_fold_cap < slots) {                                     // (the layout before this one had fewer folds)
+        if (E.d_cand_count) (void)hipFree(E.d_cand_count);
+        if (E.d_thr) (void)hipFree(E.d_thr);
+        E.d_cand_count = nullptr; E.d_thr = nullptr; E.rank_fold_cap = 0;
+        HIPCHK(ctx, hipMalloc(&E.d_cand_count, (size_t)slots * sizeof(unsigned)));
+        HIPCHK(ctx, hipMalloc(&E.d_thr, (size_t)slots * sizeof(double)));
+        E.rank_fold_cap = slots;
+    }
     using Top = std::decay_t<decltype(o.keep(std::declval<const Cand &>()))>;
     std::vector<std::vector<Top>> top((size_t)nf);
-    std::vector<double> thr(hpgv::EPI_MAX_FOLDS, -HUGE_VAL);
-    std::vector<unsigned> count(hpgv::EPI_MAX_FOLDS);
+    std::vector<double> thr((size_t)slots, -HUGE_VAL);
+    std::vector<unsigned> count((size_t)slots);
     std::vector<Cand> buf;
     EventPair ev;                                                    // destroyed on every return path
     float total_ms = 0.f;
     if (scan_ms) { HIPCHK(ctx, hipEventCreate(&ev.a)); HIPCHK(ctx, hipEventCreate(&ev.b)); }
     while (o.more()) {
-        HIPCHK(ctx, hipMemsetAsync(E.d_cand_count, 0, hpgv::EPI_MAX_FOLDS * sizeof(unsigned), nullptr));
-        HIPCHK(ctx, hipMemcpyAsync(E.d_thr, thr.data(), hpgv::EPI_MAX_FOLDS * sizeof(double), hipMemcpyHostToDevice, nullptr));
+        HIPCHK(ctx, hipMemsetAsync(E.d_cand_count, 0, (size_t)slots * sizeof(unsigned), nullptr));
+        HIPCHK(ctx, hipMemcpyAsync(E.d_thr, thr.data(), (size_t)slots * sizeof(double), hipMemcpyHostToDevice, nullptr));
         if (scan_ms) HIPCHK(ctx, hipEventRecord(ev.a, nullptr));
         if (int rc = o.launch()) return rc;
         if (scan_ms) HIPCHK(ctx, hipEventRecord(ev.b, nullptr));
-        HIPCHK(ctx, hipMemcpy(count.data(), E.d_cand_count, hpgv::EPI_MAX_FOLDS * sizeof(unsigned), hipMemcpyDeviceToHost));
+        HIPCHK(ctx, hipMemcpy(count.data(), E.d_cand_count, (size_t)slots * sizeof(unsigned), hipMemcpyDeviceToHost));
         if (scan_ms) { float ms = 0.f; HIPCHK(ctx, hipEventElapsedTime(&ms, ev.a, ev.b)); total_ms += ms; }
         unsigned worst = 0;
         for (int f = 0; f < nf; ++f) worst = std::max(worst, count[(size_t)f]);

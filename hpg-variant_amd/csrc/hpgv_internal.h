@@ -66,6 +66,10 @@ struct Staged {
 struct EpiState {
     bool have_data = false, have_folds = false;
     int V = 0, nA = 0, nU = 0, num_folds = 0, W = 0, V_alloc = 0, n_chunks = 0;
+    bool wide_only = false;           // the layout has more than EPI_MAX_FOLDS folds or a (fold, class) group of 65 536 samples or more (option "epi_wide"): planes and
+                                      // d_group_w0 only -- no marginals, swapped copy or staging chunks; every launch is k_epi_combs_wide
+    int fold_cap = 0;                 // fold slots of the layout's tables (group_size, d_folds; the ranking's thresholds and counters): max(num_folds, EPI_MAX_FOLDS)
+    int rank_fold_cap = 0;            // fold slots behind d_thr and d_cand_count
     uint8_t *d_data = nullptr;
     uint32_t *d_planes = nullptr;
     uint32_t rev_off = 0;             // words from the planes to their copy with bits 0 and 2 of every nibble swapped (epm_swap02; 0: no copy, the matrix-core scans do not run)
@@ -123,6 +127,8 @@ struct hpgv_ctx {
     long epi_pairs_mfma = 1;   // epistasis pair ranking, any fold count, data with or without missing calls: cell counts on the matrix cores (k_epi_pairs_mfma) while
                                // both classes stay below 65 536 samples, the samples fit EPM_MAX_CHUNKS staging chunks and the planes' swapped copy exists (rev_off); 0 = k_epi_pairs
     long epi_triples_mfma = 1; // epistasis triple ranking, any fold count: cell counts on the matrix cores (k_epi_triples_mfma) under the same three conditions; 0 = the vector-ALU scans below
+    long epi_wide = 0;         // epistasis: 0 = the packed kernels' limits hold (16 folds, 16-bit counts per group / class); 1 = layouts and launches past them go through the
+                               // wide listed-combination kernel (k_epi_combs_wide: 32-bit counts, up to EPI_WIDE_MAX_FOLDS folds); 2 = every listed-combination launch does
     long epi_triples_1pass = 1; // epistasis triple ranking with at most 10 folds: 1 = the 27 cells nine at a time (three walks, three waves per SIMD); 0 = the two-pass kernel; 2 (ablation build) = one pass with all counts in one lane
     long scan_lds = 0;         // bytes of (unused) LDS per workgroup of the stats / tdt scans: caps the waves in flight per CU
     long fisher_width = 16;    // lanes per variant in the Fisher p-pass (64, 32, 16 or 8): 64 / width variants per wave

@@ -100,9 +100,12 @@ int hpgv_run_epistasis_order(const char *dataset_path, int order, int num_folds,
     uint8_t *data = (uint8_t *)malloc(bytes + 1);
     if (!data || fread(data, 1, bytes, f) != bytes) { fclose(f); free(data); snprintf(g_err, sizeof g_err, "the dataset %s is shorter than its header says", dataset_path); return HPGV_ERR_INVALID; }
     fclose(f);
-    rc = hpgv_epi_set_dataset(g_ctx, data, (int)V, (int)nA, (int)nU);
+    /* for this run the engine takes what the reference takes: any --num-folds up to 64 and classes of any size (hpgv.h option
+     * "epi_wide": the wide kernel only where the shape is past the packed ones) */
+    rc = hpgv_set_option(g_ctx, "epi_wide", 1);
+    if (!rc) rc = hpgv_epi_set_dataset(g_ctx, data, (int)V, (int)nA, (int)nU);
     free(data);
-    if (rc) return host_fail("hpgv_epi_set_dataset", rc);
+    if (rc) { (void)host_fail("hpgv_epi_set_dataset", rc); (void)hpgv_set_option(g_ctx, "epi_wide", 0); return rc; }
     const size_t N = (size_t)max_ranking_size, K = (size_t)num_folds, O = (size_t)order;
     int32_t *ci = (int32_t *)malloc(sizeof(int32_t) * K * N), *cj = (int32_t *)malloc(sizeof(int32_t) * K * N), *cnt = (int32_t *)malloc(sizeof(int32_t) * K);
     int32_t *ck = (int32_t *)malloc(sizeof(int32_t) * K * N);
@@ -173,6 +176,7 @@ int hpgv_run_epistasis_order(const char *dataset_path, int order, int num_folds,
         fclose(fd);
     }
     free(ci); free(cj); free(ck); free(cn); free(cnt); free(risky); free(acc); free(all); free(path);
+    (void)hpgv_set_option(g_ctx, "epi_wide", 0);
     if (rc == HPGV_ERR_NOMEM) snprintf(g_err, sizeof g_err, "out of memory");
     return rc;
 }

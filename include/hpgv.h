@@ -97,6 +97,13 @@ const char *hpgv_last_error(const hpgv_ctx *ctx);
  *                                    whatever the option, the vector ALU when a class holds 65 536 samples or more or the
  *                                    samples with their padding need more than 128 staging chunks or the genotype planes'
  *                                    second copy finds no room: hpgv_epi_last_rank_info says which ran)
+ *   "epi_wide" 0/1/2 (default 0)  epistasis past the packed kernels' limits (16 folds; 16-bit counts: fewer than 65 536 samples per (fold, class)
+ *                                    group, at most 65 535 per class for triples and listed combinations).  0: those limits hold and are refused.
+ *                                    1: up to 64 folds and groups / classes of any size -- such shapes run on the wide listed-combination
+ *                                    kernel (k_epi_combs_wide: 32-bit counts), see "Wide limits" at the epistasis entry points; every shape
+ *                                    the packed kernels take keeps them.  2: the wide kernel for EVERY listed-combination launch (tests,
+ *                                    measurement).  On a group context the option goes to every member.  hpgv_run_epistasis[_order] of
+ *                                    the host library set 1 for their run.
  *   "group_self_exchange" 0/1    (group contexts; tests) member 0 hands its results over through the communicator too
  *   "part_aligned_loads" 0/1     hpgv_lines_partition_dev: the source of a granule by two aligned loads and v_alignbyte
  *                                (ablation build) instead of one unaligned dwordx4 load (shipped: 0)
@@ -486,18 +493,36 @@ int  hpgv_epi_dataset_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, i
  * (get_genotype_combinations, dataset.c:170-200): order 2 -> cell = g_i * 3 + g_j. */
 enum { HPGV_EPI_TESTING = 0, HPGV_EPI_TRAINING = 1 };                 /* enum evaluation_subset, model.h:73 */
 
+/* Wide limits.  Without option "epi_wide" the packed kernels' limits hold: at most 16 folds, fewer than 65 536 samples per
+ * (fold, class) group (every scan), at most 65 535 samples per class (triples, listed combinations, orders 4 and 5); what is
+ * past them is refused with HPGV_ERR_UNSUPPORTED.  With "epi_wide" >= 1:
+ *   - hpgv_epi_set_folds / _set_fold_masks take 1 .. 64 folds and groups of any size; hpgv_epi_set_dataset gives a class of
+ *     65 536 or more the implicit single fold too.  A layout with more than 16 folds or a group of 65 536 or more is WIDE-ONLY;
+ *   - hpgv_epi_eval_combs, hpgv_epi_rank_order[_rows], hpgv_epi_counts[_all_folds]: the wide kernel when the layout is wide-only
+ *     or a class exceeds 65 535;
+ *   - hpgv_epi_rank_triples[_rows]: in the same cases the any-order ranking at order 3 (same outputs; no "no empty fold" rule);
+ *   - hpgv_epi_rank_pairs[_rows]: the any-order ranking at order 2 for a wide-only layout; a class of 65 536 or more in
+ *     smaller groups keeps k_epi_pairs;
+ *   - hpgv_group_epi_rank: the same, member by member.
+ * Still refused, with or without the option:
+ *   - hpgv_epi_scan_pairs / hpgv_epi_scan_triples on a wide-only layout (the dense scans read the staging tables such a layout
+ *     does not have: use hpgv_epi_eval_combs), and hpgv_epi_scan_triples with a class above 65 535;
+ *   - more than 64 folds (the fold tables of the wide kernel's launches);
+ *   - order > 5 (the 64-byte model record holds 243 cells);
+ *   - genotype planes of 2^32 words or more (V x 3 x padded samples / 32: the kernels address them with 32-bit word offsets). */
 /* copies the dataset to the device; until folds are given all samples form one fold (none when a class holds 65536 samples
- * or more: such a cohort needs hpgv_epi_set_folds before any scan) */
+ * or more and "epi_wide" is 0: such a cohort needs hpgv_epi_set_folds before any scan) */
 int  hpgv_epi_set_dataset(hpgv_ctx *ctx, const uint8_t *genotypes, int n_variants, int n_affected, int n_unaffected);
 /* k-fold cross-validation: fold_of_sample[s] in [0, num_folds) = the fold whose TESTING part holds sample s
- * (get_k_folds, cross_validation.c:16-100); num_folds <= 16, fewer than 65536 samples per class and fold */
+ * (get_k_folds, cross_validation.c:16-100); num_folds <= 16, fewer than 65536 samples per class and fold ("epi_wide": 64 folds,
+ * any group size) */
 int  hpgv_epi_set_folds(hpgv_ctx *ctx, const int32_t *fold_of_sample, int num_folds);
 /* the same from the reference's own mask array (get_k_folds_masks, cross_validation.c:247-281):
  * num_folds x num_samples_with_padding bytes, 1 = training part, both classes padded to 16.  Masks that
  * are not a partition (a sample left out of no fold, or of two) are refused with HPGV_ERR_UNSUPPORTED. */
 int  hpgv_epi_set_fold_masks(hpgv_ctx *ctx, const uint8_t *fold_masks, int num_folds);
 /* combination_counts (model.c:76-124) of listed combinations (order 2 to 5, 3^order cells; combs = n_combs x order
- * SNP indices): counts_*[comb * cells + cell] */
+ * SNP indices): counts_*[comb * cells + cell].  Orders 4 and 5: at most 65535 samples per class ("epi_wide": any) */
 int  hpgv_epi_counts(hpgv_ctx *ctx, int order, const int32_t *combs, int n_combs,
                      int32_t *counts_aff, int32_t *counts_unaff);
 /* combination_counts_all_folds (model.c:126-206), the reference's layout for n_combs combinations in a
@@ -508,13 +533,13 @@ int  hpgv_epi_counts_all_folds(hpgv_ctx *ctx, int order, const int32_t *combs, i
  * per fold the MDR high-risk cells (mdr_high_risk_combinations2 on the training counts), the confusion
  * matrix on `subset` and the balanced accuracy (test_model, model.c:320-335).  Outputs, pairs in
  * lexicographic order: accuracy[fold * *n_pairs + p], risky_mask[...] (bit c = cell c is high risk).
- * Call with accuracy = risky_mask = NULL to get *n_pairs only. */
+ * Call with accuracy = risky_mask = NULL to get *n_pairs only.  Refuses a wide-only layout ("Wide limits"). */
 int  hpgv_epi_scan_pairs(hpgv_ctx *ctx, int i_begin, int i_end, int subset, double *accuracy,
                          uint16_t *risky_mask, unsigned long long *n_pairs);
 /* the whole scan with the per-fold ranking of the runner (add_to_model_ranking, model.c:478-517; ties:
  * higher accuracy, then smaller (i, j)): for every fold the best max_ranking_size pairs,
  * out[fold * max_ranking_size + k], n_ranked[fold] of them.  *scan_ms (may be NULL) = device time of
- * the scan kernels. */
+ * the scan kernels.  A wide-only layout ("epi_wide") is ranked by the any-order ranking at order 2. */
 int  hpgv_epi_rank_pairs(hpgv_ctx *ctx, int subset, int max_ranking_size, int32_t *comb_i, int32_t *comb_j,
                          double *accuracy, uint32_t *risky_mask, int32_t *n_ranked, float *scan_ms);
 /* the same over the pairs (i, j) with i_begin <= i < i_end only (i_begin a multiple of 64): the unit of work of
@@ -526,7 +551,8 @@ int  hpgv_epi_rank_pairs_rows(hpgv_ctx *ctx, int i_begin, int i_end, int subset,
 /* order 3: the same model for every triple i < j < k (27 cells, cell = (g_i * 3 + g_j) * 3 + g_k; at most 65535
  * samples per class, no empty fold).  hpgv_epi_scan_triples is the dense form for small sets (<= 256 SNPs):
  * accuracy / risky_mask[((fold * V + i) * V + j) * V + k], NaN / 0 where (i, j, k) is no triple;
- * hpgv_epi_rank_triples the per-fold ranking as for pairs. */
+ * hpgv_epi_rank_triples the per-fold ranking as for pairs.  With "epi_wide" hpgv_epi_rank_triples[_rows] take classes above
+ * 65535 and wide-only layouts (the any-order ranking at order 3); hpgv_epi_scan_triples refuses both. */
 int  hpgv_epi_scan_triples(hpgv_ctx *ctx, int subset, double *accuracy, uint32_t *risky_mask);
 int  hpgv_epi_rank_triples(hpgv_ctx *ctx, int subset, int max_ranking_size, int32_t *comb_i, int32_t *comb_j,
                            int32_t *comb_k, double *accuracy, uint32_t *risky_mask, int32_t *n_ranked, float *scan_ms);
@@ -537,7 +563,7 @@ int  hpgv_epi_rank_triples_rows(hpgv_ctx *ctx, int i_begin, int i_end, int subse
 
 /* ANY order the reference's --order takes (main_epistasis.c:128,142), here 2 <= order <= 5 (3^order cells, cell = the
  * genotypes of the SNPs as base-3 digits, the last SNP the lowest: get_genotype_combinations, dataset.c:170-200; at most
- * 65535 samples per class).  The pair and triple scans above are the fast forms of orders 2 and 3; these take the
+ * 65535 samples per class; "epi_wide": any class and group size, up to 64 folds, on k_epi_combs_wide).  The pair and triple scans above are the fast forms of orders 2 and 3; these take the
  * combinations as a LIST and work one lane per cell.
  * hpgv_epi_eval_combs: process_set_of_combinations (epistasis.c:14-95) of n_combs listed combinations (n_combs x order SNP
  * indices): accuracy[comb * num_folds + fold], risky_mask[(comb * num_folds + fold) * 8 + w] (bit c % 32 of word c / 32 =
@@ -566,7 +592,8 @@ enum {
     HPGV_EPI_KERNEL_TRIPLES3 = 4,        /* k_epi_triples3: the 27 cells nine at a time */
     HPGV_EPI_KERNEL_TRIPLES1 = 5,        /* k_epi_triples1 (ablation builds only) */
     HPGV_EPI_KERNEL_TRIPLES = 6,         /* k_epi_triples: two passes */
-    HPGV_EPI_KERNEL_COMBS = 7            /* k_epi_combs: listed combinations of any order */
+    HPGV_EPI_KERNEL_COMBS = 7,           /* k_epi_combs: listed combinations of any order */
+    HPGV_EPI_KERNEL_COMBS_WIDE = 8       /* k_epi_combs_wide: the same with 32-bit counts and up to 64 folds (option "epi_wide") */
 };
 typedef struct hpgv_epi_rank_info {
     int32_t kernel;                      /* HPGV_EPI_KERNEL_* */
