@@ -32,6 +32,18 @@ def _stale(target, sources):
     return any(os.path.getmtime(s) > t for s in sources)
 
 
+_include_names = {}
+
+
+def _included(path, hdrs):
+    """those of `hdrs` that the file at `path` names in an #include "..." line"""
+    if path not in _include_names:
+        with open(path) as f:
+            _include_names[path] = {line.split('"')[1].rsplit("/", 1)[-1] for line in f
+                                    if line.lstrip().startswith("#include") and line.count('"') >= 2}
+    return [h for h in hdrs if os.path.basename(h) in _include_names[path]]
+
+
 ABLATION_LIB = os.path.join(LIBDIR, "ablation", "libhpgv.so")
 
 
@@ -52,12 +64,13 @@ def build_device_lib(force=False, verbose=False, ablation=False):
     for u in units:
         o = os.path.join(objdir, os.path.basename(u)[:-4] + ".o")
         objs.append(o)
-        # a unit depends on the headers it includes (the epistasis unit does not see the other kernels' headers)
-        own = [h for h in hdrs if os.path.basename(h) in open(u).read() or os.path.basename(h) in ("hpgv.h", "hpgv_internal.h")]
-        deps = set(own)
-        for h in list(own):
-            txt = open(h).read()
-            deps.update(x for x in hdrs if os.path.basename(x) in txt)
+        # a unit depends on every header it reaches through #include "..." (the epistasis unit does not see the other kernels' headers)
+        deps, todo = set(), [u]
+        while todo:
+            for h in _included(todo.pop(), hdrs):
+                if h not in deps:
+                    deps.add(h)
+                    todo.append(h)
         if force or _stale(o, [u] + sorted(deps)):
             cmd = [_hipcc()] + flags + UNIT_FLAGS.get(os.path.basename(u), []) + ["-c", "-o", o, u]
             if verbose:

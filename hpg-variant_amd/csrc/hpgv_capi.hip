@@ -1,7 +1,7 @@
 // hpgv_capi.hip -- C ABI (include/hpgv.h) over the gfx950 kernels: contexts and their options, the cohort / pedigree /
 // group setters and their layouts, device and host memory, streams, copies, text aliases.  The launchers are in
-// hpgv_scan_capi.hip (device-resident *_dev calls), hpgv_tool_capi.hip (tokenizer, per-batch and text entry points) and
-// hpgv_lines_capi.hip (partition of lines).
+// hpgv_scan_capi.hip (device-resident *_dev calls), hpgv_text_capi.hip (tokenizer, front half of the text entry points),
+// hpgv_tool_capi.hip (per-batch and text entry points) and hpgv_lines_capi.hip (partition and split of lines).
 //
 // There is no CPU path in this library: every entry point that computes
 // launches HIP kernels, and hpgv_create() fails without a device.
@@ -142,20 +142,14 @@ void hpgv_destroy(hpgv_ctx *ctx) {
     DeviceGuard g(ctx->device);
     (void)hipDeviceSynchronize();
     if (ctx->d_mendel_male) (void)hipFree(ctx->d_mendel_male);
-    if (ctx->d_sg_chunks) (void)hipFree(ctx->d_sg_chunks);
-    if (ctx->d_group_of_col) (void)hipFree(ctx->d_group_of_col);
-    if (ctx->d_cond) (void)hipFree(ctx->d_cond);
-    for (Layout *L : {&ctx->assoc, &ctx->tdt, &ctx->stats, &ctx->sgroups, &ctx->mendel})
-        if (L->d_col_of_pos) (void)hipFree(L->d_col_of_pos);
+    for (DevBuf *b : {&ctx->d_sg_chunks, &ctx->d_group_of_col, &ctx->d_cond, &ctx->d_thr, &ctx->assoc.d_cols, &ctx->tdt.d_cols,
+                      &ctx->stats.d_cols, &ctx->sgroups.d_cols, &ctx->mendel.d_cols}) b->release();
     ctx->tdt_plan.release();
     if (ctx->d_lf_base) (void)hipFree(ctx->d_lf_base);
-    if (ctx->d_thr) (void)hipFree(ctx->d_thr);
     if (ctx->d_sink) (void)hipFree(ctx->d_sink);
     if (ctx->d_crc_tab) (void)hipFree(ctx->d_crc_tab);
     for (auto *t : ctx->tok_scratch) {
-        if (t->d_blocks) (void)hipFree(t->d_blocks);
-        if (t->d_line_off) (void)hipFree(t->d_line_off);
-        if (t->d_extra) (void)hipFree(t->d_extra);
+        for (DevBuf *b : {&t->blocks, &t->line_off, &t->extra}) b->release();
         delete t;
     }
     ctx->tok_scratch.clear();
@@ -163,9 +157,7 @@ void hpgv_destroy(hpgv_ctx *ctx) {
     ctx->grow.clear();
     hpgv_epi_release(ctx->epi);
     for (Slot *s : ctx->slots) {
-        for (int i = 0; i < 8; ++i) if (s->buf[i]) (void)hipFree(s->buf[i]);
-        if (s->h_res) (void)hipHostFree(s->h_res);
-        if (s->cnt_buf) (void)hipFree(s->cnt_buf);
+        s->release();
         if (s->stream) (void)hipStreamDestroy(s->stream);
         delete s;
     }
@@ -295,12 +287,8 @@ int hpgv_set_cohort(hpgv_ctx *ctx, const uint8_t *condition, int n_samples) {
     {   // the conditions themselves, for the kernel that counts in VCF column order with masks (k_assoc_rows)
         std::vector<uint8_t> cond(round_up((size_t)n_samples, 16) + 16, (uint8_t)HPGV_COND_OTHER);
         for (int j = 0; j < n_samples; ++j) cond[(size_t)j] = condition[j] == HPGV_COND_AFFECTED ? 1 : condition[j] == HPGV_COND_UNAFFECTED ? 0 : 2;
-        if (ctx->cond_cap < cond.size()) {
-            if (ctx->d_cond) { (void)hipFree(ctx->d_cond); ctx->d_cond = nullptr; ctx->cond_cap = 0; }
-            HIPCHK(ctx, hipMalloc(&ctx->d_cond, cond.size()));
-            ctx->cond_cap = cond.size();
-        }
-        HIPCHK(ctx, hipMemcpy(ctx->d_cond, cond.data(), cond.size(), hipMemcpyHostToDevice));
+        HIPCHK(ctx, ctx->d_cond.reserve(cond.size()));
+        HIPCHK(ctx, hipMemcpy(ctx->d_cond.p, cond.data(), cond.size(), hipMemcpyHostToDevice));
     }
     return upload_layout(ctx, L);
     HPGV_ABI_CATCH(ctx)
@@ -387,12 +375,8 @@ int hpgv_set_stats_groups(hpgv_ctx *ctx, const int32_t *group_of_sample, int n_s
             tab[(size_t)k] = (int32_t)(off[(size_t)k] / 16);
             tab[(size_t)n_groups + (size_t)k] = (int32_t)(round_up((size_t)size[(size_t)k], 16) / 16);
         }
-        if (ctx->sg_chunks_cap < tab.size()) {
-            if (ctx->d_sg_chunks) { (void)hipFree(ctx->d_sg_chunks); ctx->d_sg_chunks = nullptr; ctx->sg_chunks_cap = 0; }
-            HIPCHK(ctx, hipMalloc(&ctx->d_sg_chunks, tab.size() * sizeof(int32_t)));
-            ctx->sg_chunks_cap = tab.size();
-        }
-        HIPCHK(ctx, hipMemcpy(ctx->d_sg_chunks, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIPCHK(ctx, ctx->d_sg_chunks.reserve(tab.size() * sizeof(int32_t)));
+        HIPCHK(ctx, hipMemcpy(ctx->d_sg_chunks.p, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     }
     {   // the group of every column, for the kernel that counts groups with masks over the columns in VCF order (k_stats_all2)
         std::vector<uint8_t> gid(round_up((size_t)n_samples, 16) + 16, 0xFF);
@@ -402,12 +386,8 @@ int hpgv_set_stats_groups(hpgv_ctx *ctx, const int32_t *group_of_sample, int n_s
             else all = false;
         }
         ctx->all_grouped = all;
-        if (ctx->group_of_col_cap < gid.size()) {
-            if (ctx->d_group_of_col) { (void)hipFree(ctx->d_group_of_col); ctx->d_group_of_col = nullptr; ctx->group_of_col_cap = 0; }
-            HIPCHK(ctx, hipMalloc(&ctx->d_group_of_col, gid.size()));
-            ctx->group_of_col_cap = gid.size();
-        }
-        HIPCHK(ctx, hipMemcpy(ctx->d_group_of_col, gid.data(), gid.size(), hipMemcpyHostToDevice));
+        HIPCHK(ctx, ctx->d_group_of_col.reserve(gid.size()));
+        HIPCHK(ctx, hipMemcpy(ctx->d_group_of_col.p, gid.data(), gid.size(), hipMemcpyHostToDevice));
     }
     return upload_layout(ctx, L);
     HPGV_ABI_CATCH(ctx)

@@ -65,20 +65,20 @@ int hpgv_bgzf_compress(hpgv_ctx *ctx, const char *text, size_t text_bytes, uint8
     if (text_bytes == 0) return HPGV_OK;
     HPGV_LEASE_SLOT(ctx)
     const size_t scratch = hpgv_bgzf_deflate_scratch_bytes(text_bytes, 1), bound = hpgv_bgzf_deflate_bound(text_bytes, 1);
-    if ((rc = ensure(ctx, s, 0, text_bytes + 16))) return rc;
-    if ((rc = ensure(ctx, s, 1, bound + 16))) return rc;
-    if ((rc = ensure(ctx, s, 3, scratch + 64))) return rc;
-    unsigned long long *d_seg = (unsigned long long *)((char *)s->buf[3] + scratch);      // seg_off[2], seg_out_off[2]
+    HIPCHK(ctx, s->text.reserve_slack(text_bytes + 16));
+    HIPCHK(ctx, s->members.reserve_slack(bound + 16));
+    HIPCHK(ctx, s->dfl.reserve_slack(scratch + 64));
+    unsigned long long *d_seg = (unsigned long long *)(s->dfl.as<char>() + scratch);      // behind the kernels' scratch: seg_off[2], seg_out_off[2]
     const unsigned long long seg[2] = {0, (unsigned long long)text_bytes};
     unsigned long long got[2] = {0, 0};
-    HIPCHK(ctx, hipMemcpyAsync(s->buf[0], text, text_bytes, hipMemcpyHostToDevice, s->stream));
+    HIPCHK(ctx, hipMemcpyAsync(s->text.p, text, text_bytes, hipMemcpyHostToDevice, s->stream));
     HIPCHK(ctx, hipMemcpyAsync(d_seg, seg, sizeof seg, hipMemcpyHostToDevice, s->stream));
-    if ((rc = hpgv_bgzf_deflate_launch(ctx, (const char *)s->buf[0], d_seg, 1, (uint8_t *)s->buf[1], d_seg + 2, s->buf[3], s->stream))) return rc;
+    if ((rc = hpgv_bgzf_deflate_launch(ctx, s->text.as<const char>(), d_seg, 1, s->members.as<uint8_t>(), d_seg + 2, s->dfl.p, s->stream))) return rc;
     HIPCHK(ctx, hipMemcpyAsync(got, d_seg + 2, sizeof got, hipMemcpyDeviceToHost, s->stream));
     HIPCHK(ctx, hipStreamSynchronize(s->stream));
     const size_t made = (size_t)got[1];
     if (!out || made > out_cap) return fail(ctx, HPGV_ERR_INVALID, "the members take %zu bytes, out has room for %zu", made, out_cap);
-    HIPCHK(ctx, hipMemcpyAsync(out, s->buf[1], made, hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(ctx, hipMemcpyAsync(out, s->members.p, made, hipMemcpyDeviceToHost, s->stream));
     HIPCHK(ctx, hipStreamSynchronize(s->stream));
     *out_bytes = made;
     return HPGV_OK;

@@ -30,13 +30,11 @@ void epi_note_launch(EpiState &E, int kernel) {
 void epi_free(EpiState &E) {
     epi_free_folds(E);
     if (E.d_data) (void)hipFree(E.d_data);
-    if (E.d_cand) (void)hipFree(E.d_cand);
-    E.cand_bytes = 0;
+    E.cand.release();
+    E.tile_base.release();
     if (E.d_cand_count) (void)hipFree(E.d_cand_count);
     if (E.d_thr) (void)hipFree(E.d_thr);
-    if (E.d_tile_base) (void)hipFree(E.d_tile_base);
-    E.d_tile_base = nullptr; E.tile_base_cap = 0;
-    E.d_data = nullptr; E.d_cand = nullptr; E.d_cand_count = nullptr; E.d_thr = nullptr;
+    E.d_data = nullptr; E.d_cand_count = nullptr; E.d_thr = nullptr;
     E.rank_fold_cap = 0;
     E.have_data = false;
 }
@@ -155,12 +153,7 @@ int epi_build_folds(hpgv_ctx *ctx, const int32_t *fold_of_sample, int num_folds)
 
 // room for `words` entries of tile tables (kept between calls)
 int epi_tile_room(hpgv_ctx *ctx, size_t words) {
-    EpiState &E = ctx->epi;
-    if (E.tile_base_cap >= words) return HPGV_OK;
-    if (E.d_tile_base) (void)hipFree(E.d_tile_base);
-    E.d_tile_base = nullptr; E.tile_base_cap = 0;
-    HIPCHK(ctx, hipMalloc(&E.d_tile_base, (words + 64) * sizeof(unsigned)));
-    E.tile_base_cap = words + 64;
+    HIPCHK(ctx, ctx->epi.tile_base.reserve(words * sizeof(unsigned), (words + 64) * sizeof(unsigned)));
     return HPGV_OK;
 }
 
@@ -185,7 +178,7 @@ int epi_pair_tiles(hpgv_ctx *ctx, int ti, int &i_begin, int i_end, hipStream_t s
     if (total + 8 > 0x7FFFFFFFull / 256) return fail(ctx, HPGV_ERR_UNSUPPORTED, "row band too large for one launch");
     if (total == 0) return HPGV_OK;
     if (int rc = epi_tile_room(ctx, tile_base.size())) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(E.d_tile_base, tile_base.data(), tile_base.size() * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(E.tile_base.p, tile_base.data(), tile_base.size() * sizeof(unsigned), hipMemcpyHostToDevice, st));
     n_tiles = (unsigned)total;
     return HPGV_OK;
 }
@@ -204,13 +197,14 @@ int epi_launch_pairs2(hpgv_ctx *ctx, int i_begin, int i_end, double *d_acc, uint
     const dim3 grid((n_tiles + 7u) / 8u * 8u);                       // eight spans, one per XCD
     if (int rc = epi_upload_folds(ctx, TRAINING, st)) return rc;
     if (candidates) epi_note_launch(E, mfma ? HPGV_EPI_KERNEL_PAIRS_MFMA : HPGV_EPI_KERNEL_PAIRS_VALU);
-    hpgv::EpiCand *d_cand = candidates ? (hpgv::EpiCand *)E.d_cand : nullptr;
+    hpgv::EpiCand *d_cand = candidates ? E.cand.as<hpgv::EpiCand>() : nullptr;
+    const unsigned *d_tile_base = E.tile_base.as<unsigned>();
 #define HPGV_EPM_LAUNCH(COMPLETEV)                                                                                                   \
     hipLaunchKernelGGL((hpgv::k_epi_pairs_mfma<TRAINING, BALANCED, COMPLETEV>), grid, dim3(256), 0, st, E.d_planes, E.d_marg, E.rev_off, E.W, \
-                       E.V, i_begin, i_first, i_end, E.d_tile_base, n_cols, n_tiles, E.d_chunks, E.d_chunk_cls, E.n_chunks, E.d_folds, E.num_folds, E.nA, E.nU, E.d_thr, d_cand, E.d_cand_count, E.cand_cap)
+                       E.V, i_begin, i_first, i_end, d_tile_base, n_cols, n_tiles, E.d_chunks, E.d_chunk_cls, E.n_chunks, E.d_folds, E.num_folds, E.nA, E.nU, E.d_thr, d_cand, E.d_cand_count, E.cand_cap)
 #define HPGV_EPI_LAUNCH(KK, COMPLETEV)                                                                                              \
     hipLaunchKernelGGL((hpgv::k_epi_pairs<KK, TRAINING, BALANCED, COMPLETEV>), grid, dim3(256), 0, st, E.d_planes, E.d_marg, E.W, E.V, i_begin, i_first, i_end, \
-                       E.d_tile_base, n_cols, n_tiles, E.d_chunks, E.n_chunks, E.d_folds, E.nA, E.nU, d_acc, d_mask, n_pairs_out, rank_base,                          \
+                       d_tile_base, n_cols, n_tiles, E.d_chunks, E.n_chunks, E.d_folds, E.nA, E.nU, d_acc, d_mask, n_pairs_out, rank_base,                          \
                        candidates ? E.d_thr : nullptr, d_cand, E.d_cand_count, E.cand_cap)
 #define HPGV_EPI_LAUNCH_K(COMPLETEV)                                                                                                \
     do { const int k = E.num_folds;                                                                                                 \
@@ -437,14 +431,8 @@ struct EpiTileOrder {
     long long hi;                                                    // what is left: [i_begin, hi)
     EpiTileOrder(hpgv_ctx *c, int subset, int begin, long long last) : ctx(c), E(c->epi), training(subset == HPGV_EPI_TRAINING), V(c->epi.V), i_begin(begin), hi(last) {}
     int room(size_t lists, unsigned cap_) {                          // (kept between calls and only ever grown: 240 MB for the triples of 1 024 SNPs)
-        const size_t bytes = lists * cap_ * sizeof(Cand);
-        if (E.cand_bytes < bytes) {
-            if (E.d_cand) (void)hipFree(E.d_cand);
-            E.d_cand = nullptr; E.cand_bytes = 0;
-            HIPCHK(ctx, hipMalloc(&E.d_cand, bytes));
-            E.cand_bytes = bytes;
-        }
-        d_cand = (Cand *)E.d_cand; cap = E.cand_cap = cap_;
+        HIPCHK(ctx, E.cand.reserve(lists * cap_ * sizeof(Cand)));
+        d_cand = E.cand.template as<Cand>(); cap = E.cand_cap = cap_;
         return HPGV_OK;
     }
     bool more() const { return hi > i_begin; }
@@ -556,7 +544,7 @@ int epi_triple_tiles(hpgv_ctx *ctx, int tj, int i_first, int n_i, int &n_jb, uns
     if (total > (0x7FFFFFFFull >> 8)) return fail(ctx, HPGV_ERR_UNSUPPORTED, "too many first SNPs for one launch of the triple scan");
     if (total == 0) return HPGV_OK;
     if (int rc = epi_tile_room(ctx, jbp.size() + rb.size())) return rc;
-    d_jbp = E.d_tile_base; d_rb = E.d_tile_base + jbp.size();
+    d_jbp = E.tile_base.as<unsigned>(); d_rb = d_jbp + jbp.size();
     HIPCHK(ctx, hipMemcpyAsync(d_jbp, jbp.data(), jbp.size() * sizeof(unsigned), hipMemcpyHostToDevice, nullptr));
     HIPCHK(ctx, hipMemcpyAsync(d_rb, rb.data(), rb.size() * sizeof(unsigned), hipMemcpyHostToDevice, nullptr));
     total_out = (unsigned)total;

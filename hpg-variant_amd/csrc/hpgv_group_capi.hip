@@ -45,10 +45,8 @@ struct GroupMember {
     hipStream_t scan = nullptr, xfer = nullptr;
     hipEvent_t scan_done[2] = {nullptr, nullptr}, xfer_done[2] = {nullptr, nullptr};
     bool xfer_pending[2] = {false, false};
-    void *scratch[2] = {nullptr, nullptr};
-    size_t cap[2] = {0, 0};
-    int32_t *d_miss[2] = {nullptr, nullptr};   // per-sample counters of this member's shard, per generation like the scratch
-    size_t miss_cap[2] = {0, 0};
+    DevBuf scratch[2];              // this member's results on their way to member 0, one per generation of calls
+    DevBuf miss[2];                 // int32: per-sample counters of this member's shard, per generation like the scratch
     int rank = 0;                   // RCCL rank of the member's device
     bool local = false;             // shares member 0's device: results handed over by a device-local copy
 };
@@ -137,11 +135,7 @@ void shard_of(int64_t V, int G, int g, int64_t *lo, int64_t *hi) {
 }
 
 int ensure_scratch(hpgv_ctx *mc, GroupMember &M, int gen, size_t bytes) {
-    if (M.cap[gen] >= bytes) return HPGV_OK;
-    if (M.scratch[gen]) { (void)hipFree(M.scratch[gen]); M.scratch[gen] = nullptr; M.cap[gen] = 0; }
-    const size_t want = round_up(bytes + bytes / 16, 256);
-    HIPCHK(mc, hipMalloc(&M.scratch[gen], want));
-    M.cap[gen] = want;
+    HIPCHK(mc, M.scratch[gen].reserve(bytes, round_up(bytes + bytes / 16, 256)));
     return HPGV_OK;
 }
 
@@ -185,7 +179,7 @@ int plan_call(hpgv_ctx *g, int64_t V, size_t bytes_per_variant, Plan &P) {
         if (!P.via_scratch[k]) continue;
         const int e = ensure_scratch(mc, M, P.gen, (size_t)P.n[k] * bytes_per_variant + 256);
         if (e) return e;
-        P.base[k] = (char *)M.scratch[P.gen];
+        P.base[k] = M.scratch[P.gen].as<char>();
     }
     return HPGV_OK;
 }
@@ -283,11 +277,11 @@ void hpgv_group_release(hpgv_ctx *g) {
         GroupMember &M = S->m[k];
         DeviceGuard dg(g->members[k]->device);
         for (int i = 0; i < 2; ++i) {
-            if (M.scratch[i]) (void)hipFree(M.scratch[i]);
+            M.scratch[i].release();
+            M.miss[i].release();
             if (M.scan_done[i]) (void)hipEventDestroy(M.scan_done[i]);
             if (M.xfer_done[i]) (void)hipEventDestroy(M.xfer_done[i]);
         }
-        for (int i = 0; i < 2; ++i) if (M.d_miss[i]) (void)hipFree(M.d_miss[i]);
         if (M.scan) (void)hipStreamDestroy(M.scan);
         if (M.xfer) (void)hipStreamDestroy(M.xfer);
     }
@@ -502,13 +496,8 @@ int hpgv_group_stats(hpgv_ctx *g, const uint8_t *const *d_gt, int64_t V, int32_t
             // member 0 counts straight into the caller's array, everyone else into a counter array of its own
             if (k == 0) miss = d_sample_missing;
             else {
-                const size_t need = (size_t)n_samples * sizeof(int32_t);
-                if (M.miss_cap[P.gen] < need) {
-                    if (M.d_miss[P.gen]) { (void)hipFree(M.d_miss[P.gen]); M.d_miss[P.gen] = nullptr; M.miss_cap[P.gen] = 0; }
-                    HIPCHK(mc, hipMalloc(&M.d_miss[P.gen], need));
-                    M.miss_cap[P.gen] = need;
-                }
-                miss = M.d_miss[P.gen];
+                HIPCHK(mc, M.miss[P.gen].reserve((size_t)n_samples * sizeof(int32_t)));
+                miss = M.miss[P.gen].as<int32_t>();
             }
             HIPCHK(mc, hipMemsetAsync(miss, 0, (size_t)n_samples * sizeof(int32_t), M.scan));
         }
@@ -542,7 +531,7 @@ int hpgv_group_stats(hpgv_ctx *g, const uint8_t *const *d_gt, int64_t V, int32_t
             if (!M.local) continue;
             HIPCHK(g, hipStreamWaitEvent(M.xfer, M0.scan_done[P.gen], 0));      // member 0's memset of the counters is behind this event
             hipLaunchKernelGGL(k_add_i32, dim3((unsigned)((n_samples + 255) / 256)), dim3(256), 0, M.xfer, d_sample_missing,
-                               M.d_miss[P.gen], n_samples);
+                               M.miss[P.gen].as<int32_t>(), n_samples);
             HIPCHK(g, hipGetLastError());
             HIPCHK(g, hipEventRecord(M.xfer_done[P.gen], M.xfer));
             HIPCHK(g, hipStreamWaitEvent(M0.xfer, M.xfer_done[P.gen], 0));
@@ -553,7 +542,7 @@ int hpgv_group_stats(hpgv_ctx *g, const uint8_t *const *d_gt, int64_t V, int32_t
     for (int k = 1; k < P.G; ++k) {
         GroupMember &M = S->m[(size_t)k];
         if (M.local) continue;
-        NCCLCHK(g, S, S->Reduce(M.d_miss[P.gen], M.d_miss[P.gen], (size_t)n_samples, ncclInt32, ncclSum, 0, S->comms[(size_t)M.rank], M.xfer));
+        NCCLCHK(g, S, S->Reduce(M.miss[P.gen].as<int32_t>(), M.miss[P.gen].as<int32_t>(), (size_t)n_samples, ncclInt32, ncclSum, 0, S->comms[(size_t)M.rank], M.xfer));
     }
     NCCLCHK(g, S, S->GroupEnd());
     for (int k = 0; k < P.G; ++k) {

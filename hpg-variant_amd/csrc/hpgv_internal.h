@@ -1,8 +1,8 @@
 // hpgv_internal.h -- the context behind include/hpgv.h and the helpers shared by the translation units of
 // libhpgv.so: hpgv_capi.hip (contexts, options, cohorts, memory, streams, text aliases), hpgv_scan_capi.hip (the
-// device-resident *_dev launchers), hpgv_tool_capi.hip (tokenizer, per-batch and text entry points),
-// hpgv_lines_capi.hip (partition / multisplit of lines), and the units whose kernel instantiations compile on their
-// own (hpgv_epi_capi.hip, hpgv_epi_generic_capi.hip, hpgv_statsall_capi.hip, hpgv_inflate_capi.hip, hpgv_group_capi.hip).
+// device-resident *_dev launchers), hpgv_text_capi.hip (tokenizer, the text entry points' front half),
+// hpgv_tool_capi.hip (per-batch and text entry points), hpgv_lines_capi.hip (partition / multisplit of lines), and the
+// units whose kernel instantiations compile on their own (hpgv_epi_capi.hip, hpgv_epi_generic_capi.hip, hpgv_statsall_capi.hip, hpgv_inflate_capi.hip, hpgv_group_capi.hip).
 // The host side the epistasis units share is in hpgv_epi_host.h.
 #pragma once
 #include "../../include/hpgv.h"
@@ -26,36 +26,116 @@
 
 namespace { thread_local std::string g_create_error; }
 
+// a device allocation that only ever grows: kept while it is large enough (hipFree waits for every stream of the device), freed
+// and allocated anew when it is not -- what it held does not survive that
+struct DevBuf {
+    void *p = nullptr;
+    size_t cap = 0;                    // bytes behind p
+    template <typename T = void> T *as() const { return static_cast<T *>(p); }
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    // room for `bytes`: a block too small is replaced by one of `alloc` bytes -- the site's slack rule; less than `bytes` (the
+    // default) means exactly `bytes`
+    hipError_t reserve(size_t bytes, size_t alloc = 0) {
+        if (cap >= bytes) return hipSuccess;
+        release();
+        const size_t want = alloc > bytes ? alloc : bytes;
+        const hipError_t e = hipMalloc(&p, want);
+        if (e == hipSuccess) cap = want;
+        return e;
+    }
+    // the same for a block that work queued on `busy` may still use: the stream is waited for before the block is freed
+    hipError_t reserve_after_sync(hipStream_t busy, size_t bytes, size_t alloc = 0) {
+        if (cap >= bytes) return hipSuccess;
+        if (p) { const hipError_t e = hipStreamSynchronize(busy); if (e != hipSuccess) return e; }
+        return reserve(bytes, alloc);
+    }
+    // the slots' rule: a quarter more than asked for, in whole 256 bytes
+    hipError_t reserve_slack(size_t bytes) { return reserve(bytes, (bytes + bytes / 4 + 255) / 256 * 256); }
+};
+
+// its page-locked twin: host memory (h) the device reads and writes in place (d); half more than asked for, in whole 4 KiB
+struct PinnedBuf {
+    void *h = nullptr, *d = nullptr;
+    size_t cap = 0;
+    void release() { if (h) (void)hipHostFree(h); h = d = nullptr; cap = 0; }
+    hipError_t reserve(size_t bytes) {
+        if (cap >= bytes) return hipSuccess;
+        release();
+        const size_t want = (bytes + bytes / 2 + 4095) / 4096 * 4096;
+        hipError_t e = hipHostMalloc(&h, want, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipHostGetDevicePointer(&d, h, 0);
+        if (e == hipSuccess) cap = want;
+        return e;
+    }
+};
+
 struct Layout {
     bool set = false;
     int n_samples = 0;
     size_t pitch = 0;
     int chunks = 0;
     std::vector<int32_t> col_of_pos;   // size pitch; -1 = pad
-    int32_t *d_col_of_pos = nullptr;
-    size_t d_cap = 0;                  // bytes behind d_col_of_pos
+    DevBuf d_cols;                     // col_of_pos on the device
+    const int32_t *d_col_of_pos() const { return d_cols.as<int32_t>(); }
 };
 
-// per-call scratch of the synchronous host entry points
+// per-call scratch of the synchronous host entry points: one grow-only buffer per role.  A call reserves the ones it uses; what
+// they hold ends with the call -- but for `text` and `meta` under a hold (hpgv_ctx::TextHeld), which keeps the whole slot
 struct Slot {
     bool busy = false;
     hipStream_t stream = nullptr;
-    void *buf[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t cap[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    void *h_res = nullptr;             // page-locked result block of the fused per-batch kernel (the kernel stores into it)
-    void *d_res = nullptr;             // its device-side address
-    size_t res_cap = 0;
-    void *cnt_buf = nullptr;           // k_stats_all2's per-row counters between its two kernels
-    size_t cnt_cap = 0;
+    // the call's matrix (Staged)
+    DevBuf text;       // the host text of a *_text call, of hpgv_tokenize or of hpgv_bgzf_compress
+    DevBuf raw;        // genotype rows in VCF column order: the copy of a batch, or what the tokenizer wrote
+    DevBuf laid;       // the rows in a tool's layout (HPGV_LAYOUT_*); the record filters and the kernel chain lay out into it in turn
+    DevBuf isx;        // per row: on chromosome X
+    DevBuf status;     // per line of a text: the tokenizer's status
+    DevBuf meta;       // a text's n_lines, line offsets and field offsets (TextMeta)
+    // the tools' results on their way out
+    DevBuf tally;      // integer counters per row: allele counts, transmission counts, counts8.  The count filters' counts8 and
+                       // verdict bytes come first; record_filters has them on the host (its sync) before a tool's tallies follow
+    DevBuf dbl;        // doubles per row: odds, chi-square, p; Hardy-Weinberg
+    DevBuf gtally;     // the kernel chain's counts8 per phenotype group and row
+    DevBuf gdbl;       // their Hardy-Weinberg doubles
+    DevBuf ints;       // the allele counts as four arrays, for the copies into the caller's
+    DevBuf smiss;      // missing genotypes per sample (the one-pass kernel's child errors per trio behind them)
+    DevBuf merr;       // Mendelian errors per row, then child errors per trio: the Mendel filter's, on the host when record_filters
+                       // returns (its sync), then the kernel chain's
+    DevBuf inherit;    // the inheritance filter's counts8 and verdict bytes
+    DevBuf multi;      // multi-allelic rows: their indices, then their 256-bin tables
+    DevBuf row_cnt;    // k_stats_all2's per-row counters between its two kernels
+    PinnedBuf res;     // result block of the one-pass kernels (they store into it), staging of k_assoc_rows' results
+    // a buffer under two names holds two things that no call has at once:
+    DevBuf &heads = text;      // a text that lies on the device already (hpgv_text_alias) is not uploaded: its head offsets and heads
+    DevBuf &parts = laid;      // the line tools run on a held text, after its matrix is done with: the partition's / split's output,
+    DevBuf &members = isx;     //   the BGZF members made of it (and of hpgv_bgzf_compress's text),
+    DevBuf &aux = tally;       //   offsets scratch, keep / bucket bytes, segment tables,
+    DevBuf &dfl = dbl;         //   the deflate kernels' scratch
+    void release() {
+        for (DevBuf *b : {&text, &raw, &laid, &isx, &status, &meta, &tally, &dbl, &gtally, &gdbl, &ints, &smiss, &merr, &inherit, &multi, &row_cnt}) b->release();
+        res.release();
+    }
+};
+
+// where the tokenizer's outputs per text lie in Slot::meta: n_lines, the starts of max_lines + 1 lines and the text's end, ten field
+// offsets per line
+struct TextMeta {
+    char *base;
+    size_t max_lines;
+    TextMeta(const DevBuf &meta, int max_lines_) : base(meta.as<char>()), max_lines((size_t)max_lines_) {}
+    static size_t bytes(int max_lines) { return 16 + ((size_t)max_lines + 2) * sizeof(uint64_t) + (size_t)max_lines * 10 * sizeof(uint32_t) + 16; }
+    int *n_lines() const { return (int *)base; }
+    unsigned long long *line_off() const { return (unsigned long long *)(base + 16); }
+    uint32_t *field_off() const { return (uint32_t *)(base + 16 + (max_lines + 2) * sizeof(uint64_t)); }
 };
 
 // the genotype matrix of one synchronous call once it is on the device: what the per-tool back halves of
-// hpgv_tool_capi.hip read, whether a batch (batch_sources / stage_batch) or a text (text_front) put it there
+// hpgv_tool_capi.hip read, whether a batch (batch_sources / stage_batch) or a text (text_front, hpgv_text_capi.hip) put it there
 struct Staged {
-    const uint8_t *d_raw = nullptr;   // VCF column order: slot buf[0] or the caller's mapped rows (batch), buf[7] (text)
+    const uint8_t *d_raw = nullptr;   // VCF column order: the slot's `raw`, or the caller's rows where the device can read them
     size_t raw_pitch = 0;
-    const uint8_t *d_laid = nullptr;  // slot buf[1] in layout `which`; null when a one-pass kernel reads d_raw itself
-    int which = 0;                    // HPGV_LAYOUT_* of d_laid
+    const uint8_t *d_laid = nullptr;  // the slot's `laid` in layout `which`; null when a one-pass kernel reads d_raw itself
+    int which = 0;                    // HPGV_LAYOUT_* of d_laid (laid_as keeps both current when the chain lays out anew)
     const uint8_t *d_isx = nullptr;
     int n = 0;                        // rows
     size_t out_stride = 0;            // stride of the per-group outputs: n_variants (batch), max_lines (text)
@@ -81,13 +161,11 @@ struct EpiState {
     hpgv::EpiFold *d_folds = nullptr;
     uint32_t *d_group_w0 = nullptr;
     std::vector<int32_t> group_size;
-    void *d_cand = nullptr;           // the pair and triple rankings' candidate lists (EpiCand / EpiCand3), kept between calls and only ever grown
-    size_t cand_bytes = 0;
+    DevBuf cand;                      // the pair and triple rankings' candidate lists (EpiCand / EpiCand3), kept between calls and only ever grown
     unsigned *d_cand_count = nullptr;
     unsigned cand_cap = 0;            // records per fold's list in the current ranking call
     double *d_thr = nullptr;
-    unsigned *d_tile_base = nullptr;
-    size_t tile_base_cap = 0;
+    DevBuf tile_base;                 // unsigned: the tile tables of a launch
 };
 
 struct hpgv_ctx {
@@ -152,8 +230,7 @@ struct hpgv_ctx {
     // assoc
     Layout assoc;
     int nA = 0, nU = 0, chunksA = 0;
-    uint8_t *d_cond = nullptr;            // the condition of every column as given (padded with 2 to whole 16-byte chunks): k_assoc_rows' masks
-    size_t cond_cap = 0;
+    DevBuf d_cond;                        // the condition of every column as given (padded with 2 to whole 16-byte chunks): k_assoc_rows' masks
     // tdt
     Layout tdt;
     hpgv::TdtPlan tdt_plan;
@@ -162,10 +239,8 @@ struct hpgv_ctx {
     Layout sgroups;                       // [group 0 | pad16 | group 1 | ...]
     std::vector<uint32_t> sg_off;         // byte offset of every group's segment in the row
     std::vector<int> sg_size;             // samples per group
-    int32_t *d_sg_chunks = nullptr;       // device: first 16-byte chunk and chunk count of every group ([2 * n_groups])
-    size_t sg_chunks_cap = 0;
-    uint8_t *d_group_of_col = nullptr;    // device: group id of every column (0xFF: in no group), padded to whole 16-byte chunks -- k_stats_all2's masks
-    size_t group_of_col_cap = 0;
+    DevBuf d_sg_chunks;                   // int32: first 16-byte chunk and chunk count of every group ([2 * n_groups])
+    DevBuf d_group_of_col;                // uint8: group id of every column (0xFF: in no group), padded to whole 16-byte chunks -- k_stats_all2's masks
     bool all_grouped = false;             // every column is in a group: the last group's counters are "all minus the others"
     // mendelian errors
     Layout mendel;
@@ -178,8 +253,7 @@ struct hpgv_ctx {
     size_t n_lf = 0;
     size_t cap_lf = 0;                 // doubles behind d_lf (kept across tables: hipFree waits for the whole device)
     // synth scratch
-    uint32_t *d_thr = nullptr;
-    size_t thr_cap = 0;
+    DevBuf d_thr;                         // uint32
     // profiling
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     bool have_scan_ev = false, have_stats_ev = false;
@@ -191,9 +265,7 @@ struct hpgv_ctx {
     // concurrently on the device and must not share it.  The table is guarded by tok_mu.
     struct TokScratch {
         hipStream_t stream = nullptr;
-        int *d_blocks = nullptr; size_t blocks_cap = 0;
-        unsigned long long *d_line_off = nullptr; size_t line_cap = 0;
-        void *d_extra = nullptr; size_t extra_cap = 0;
+        DevBuf blocks, line_off, extra;
     };
     std::mutex tok_mu;
     std::vector<TokScratch *> tok_scratch;
@@ -296,13 +368,8 @@ struct DeviceGuard {
     // the table is kept when it is large enough: hipFree waits for every stream of the device, and a file run sets its
     // cohort while the decoder of the bgzip text is busy on streams of its own
     const size_t need = L.col_of_pos.size() * sizeof(int32_t);
-    if (L.d_cap < need) {
-        if (L.d_col_of_pos) { (void)hipFree(L.d_col_of_pos); L.d_col_of_pos = nullptr; L.d_cap = 0; }
-        HIPCHK(ctx, hipMalloc(&L.d_col_of_pos, need));
-        L.d_cap = need;
-    }
-    HIPCHK(ctx, hipMemcpy(L.d_col_of_pos, L.col_of_pos.data(), L.col_of_pos.size() * sizeof(int32_t),
-                          hipMemcpyHostToDevice));
+    HIPCHK(ctx, L.d_cols.reserve(need));
+    HIPCHK(ctx, hipMemcpy(L.d_cols.p, L.col_of_pos.data(), need, hipMemcpyHostToDevice));
     L.chunks = (int)(L.pitch / 16);
     L.set = true;
     return HPGV_OK;
@@ -312,15 +379,6 @@ struct DeviceGuard {
 constexpr int kScanUnroll = 8;       // unroll of the tdt/stats scans
 constexpr int kMaxUnroll = 16;       // largest assoc unroll option
 [[maybe_unused]] bool pitch_supported(size_t pitch) { return pitch / 16 / 64 + kMaxUnroll + 1 <= 2047; }
-
-[[maybe_unused]] int ensure(hpgv_ctx *ctx, Slot *s, int idx, size_t bytes) {
-    if (s->cap[idx] >= bytes) return HPGV_OK;
-    if (s->buf[idx]) { (void)hipFree(s->buf[idx]); s->buf[idx] = nullptr; s->cap[idx] = 0; }
-    size_t want = round_up(bytes + bytes / 4, 256);
-    HIPCHK(ctx, hipMalloc(&s->buf[idx], want));
-    s->cap[idx] = want;
-    return HPGV_OK;
-}
 
 [[maybe_unused]] int acquire_slot(hpgv_ctx *ctx, Slot **out) {
     std::lock_guard<std::mutex> lk(ctx->mu);
@@ -389,13 +447,14 @@ const char *text_on_device(hpgv_ctx *ctx, const char *host_text);
 hpgv_ctx *alias_owner(hpgv_ctx *group, const char *host_text);    // the member of a group on whose device `host_text` lies, or nullptr
 // defined in hpgv_tool_capi.hip: the largest raw-row window the one-pass kernels may stage in LDS on this device (hpgv_create)
 long hpgv_batch_lds_optin(const hipDeviceProp_t &prop, long fallback);
-// shared front half of the *_text entry points (and of hpgv_filter_text): text -> device, tokenize, record filters, lay out
+// defined in hpgv_text_capi.hip: the shared front half of the *_text entry points (and of hpgv_filter_text): text -> device,
+// tokenize, record filters, lay out
 int text_front(hpgv_ctx *ctx, Slot *s, int which, const Layout &L, const char *text, size_t text_bytes, int max_lines, int *n_lines,
                uint64_t *line_off, uint32_t *field_off, int32_t *status, Staged *S, bool final_layout = true);
 
 // defined in hpgv_statsall_capi.hip: k_stats_all2 on a batch (0 = launched, 1 = not a batch it takes: run k_stats_all)
 namespace hpgv { struct StatsAllArgs; }
-int hpgv_launch_stats_all2(hpgv_ctx *ctx, hpgv::StatsAllArgs &A, void **cnt_buf, size_t *cnt_cap, hipStream_t st);
+int hpgv_launch_stats_all2(hpgv_ctx *ctx, hpgv::StatsAllArgs &A, DevBuf &row_cnt, hipStream_t st);
 // k_assoc_rows: the allele counts from the tokenizer's raw rows (0 = launched, 1 = not a batch it takes: run k_batch)
 int hpgv_launch_assoc_rows(hpgv_ctx *ctx, const uint8_t *d_src, size_t src_pitch, int n_variants, const uint8_t *d_is_x, int32_t *d_counts, hipStream_t st);
 // defined in hpgv_epi_capi.hip

@@ -1,6 +1,6 @@
 // hpgv_lines_capi.hip -- C ABI of the line tools (include/hpgv.h): stable partition and multi-way split of a text's lines on
 // the device (hpg-var-vcf filter / split), on the caller's buffers (*_dev) or on the text hpgv_filter_text tokenized and
-// holds.  The tokenizer and text_front stay in hpgv_tool_capi.hip; this unit includes hpgv_text_kernels.h for the heads'
+// holds.  The tokenizer and text_front are in hpgv_text_capi.hip; this unit includes hpgv_text_kernels.h for the heads'
 // three-launch scan (k_head_bases), which the partition's offsets reuse.
 #include "hpgv_internal.h"
 #include <climits>
@@ -84,7 +84,7 @@ int hpgv_filter_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, int max
     HIPCHK(ctx, hipStreamSynchronize(s->stream));
     if (*n_lines > max_lines) return HPGV_OK;                      // the caller grows its arrays and calls again
     const char *d_src = text_on_device(ctx, text);
-    hpgv_ctx::TextHeld h{text, s, d_src ? d_src : (const char *)s->buf[0], (const unsigned long long *)((char *)s->buf[6] + 16), S.n};
+    hpgv_ctx::TextHeld h{text, s, d_src ? d_src : s->text.as<const char>(), TextMeta(s->meta, max_lines).line_off(), S.n};
     {
         std::lock_guard<std::mutex> lk(ctx->alias_mu);
         ctx->text_held.push_back(h);
@@ -111,14 +111,13 @@ static __global__ void k_part_segs(const unsigned long long *__restrict__ kept, 
     if (threadIdx.x == 0) { seg_off[0] = 0; seg_off[1] = *kept; seg_off[2] = want_rest ? total : *kept; }
 }
 
-// the text in s->buf[1], n_segs segments bounded by d_seg_off, as members in s->buf[2]; d_res: seg_out_off[n_segs + 1], then a
-// last byte per segment.  Queued on the slot's stream.
+// the text in the slot's `parts`, n_segs segments bounded by d_seg_off, as members in its `members`; d_res: seg_out_off[n_segs + 1],
+// then a last byte per segment.  Queued on the slot's stream.
 static int deflate_parts(hpgv_ctx *ctx, Slot *s, size_t total, const unsigned long long *d_seg_off, int n_segs, unsigned long long *d_res) {
-    int rc;
-    if ((rc = ensure(ctx, s, 2, hpgv_bgzf_deflate_bound(total, n_segs) + 16))) return rc;
-    if ((rc = ensure(ctx, s, 4, hpgv_bgzf_deflate_scratch_bytes(total, n_segs) + 16))) return rc;
-    if ((rc = hpgv_bgzf_deflate_launch(ctx, (const char *)s->buf[1], d_seg_off, n_segs, (uint8_t *)s->buf[2], d_res, s->buf[4], s->stream))) return rc;
-    hipLaunchKernelGGL(k_seg_last_bytes, dim3(1), dim3(256), 0, s->stream, (const char *)s->buf[1], d_seg_off, n_segs, (uint8_t *)(d_res + n_segs + 1));
+    HIPCHK(ctx, s->members.reserve_slack(hpgv_bgzf_deflate_bound(total, n_segs) + 16));
+    HIPCHK(ctx, s->dfl.reserve_slack(hpgv_bgzf_deflate_scratch_bytes(total, n_segs) + 16));
+    if (const int rc = hpgv_bgzf_deflate_launch(ctx, s->parts.as<const char>(), d_seg_off, n_segs, s->members.as<uint8_t>(), d_res, s->dfl.p, s->stream)) return rc;
+    hipLaunchKernelGGL(k_seg_last_bytes, dim3(1), dim3(256), 0, s->stream, s->parts.as<const char>(), d_seg_off, n_segs, (uint8_t *)(d_res + n_segs + 1));
     HIPCHK(ctx, hipGetLastError());
     return HPGV_OK;
 }
@@ -157,13 +156,13 @@ static int text_partition(hpgv_ctx *ctx, const char *text, const uint8_t *keep, 
     const size_t n = (size_t)n_lines, scratch = hpgv_lines_partition_scratch_bytes(n_lines);
     const size_t off_keep = round_up(scratch + sizeof(unsigned long long), 256), off_seg = round_up(off_keep + n, 256);
     int rc;
-    if ((rc = ensure(ctx, s, 3, off_seg + 64 + 16))) return rc;
-    if ((rc = ensure(ctx, s, 1, total + 16))) return rc;
-    char *d_aux = (char *)s->buf[3];
+    HIPCHK(ctx, s->aux.reserve_slack(off_seg + 64 + 16));
+    HIPCHK(ctx, s->parts.reserve_slack(total + 16));
+    char *d_aux = s->aux.as<char>();
     unsigned long long *d_kept = (unsigned long long *)(d_aux + scratch);
     uint8_t *d_keep = (uint8_t *)d_aux + off_keep;
     HIPCHK(ctx, hipMemcpyAsync(d_keep, keep, n, hipMemcpyHostToDevice, s->stream));
-    if ((rc = partition_launch(ctx, h.d_text, h.d_line_off, n_lines, d_keep, (char *)s->buf[1], d_kept, d_aux, s->stream))) return rc;
+    if ((rc = partition_launch(ctx, h.d_text, h.d_line_off, n_lines, d_keep, s->parts.as<char>(), d_kept, d_aux, s->stream))) return rc;
     unsigned long long kept = 0;
     HIPCHK(ctx, hipMemcpyAsync(&kept, d_kept, sizeof kept, hipMemcpyDeviceToHost, s->stream));
     if (Z) {                                                        // seg_off[3] | seg_out_off[3], last[2]
@@ -174,10 +173,10 @@ static int text_partition(hpgv_ctx *ctx, const char *text, const uint8_t *keep, 
         HIPCHK(ctx, hipStreamSynchronize(s->stream));
         const size_t made = (size_t)res[2];
         if (made > out_cap) return fail(ctx, HPGV_ERR_INVALID, "the members take %zu bytes, out has room for %zu", made, out_cap);
-        if (made) HIPCHK(ctx, hipMemcpyAsync(out, s->buf[2], made, hipMemcpyDeviceToHost, s->stream));
+        if (made) HIPCHK(ctx, hipMemcpyAsync(out, s->members.p, made, hipMemcpyDeviceToHost, s->stream));
         if (Z->comp) { Z->comp[0] = res[1]; Z->comp[1] = res[2] - res[1]; }
         if (Z->last) memcpy(Z->last, &res[3], 2);
-    } else if (total) HIPCHK(ctx, hipMemcpyAsync(out, s->buf[1], total, hipMemcpyDeviceToHost, s->stream));
+    } else if (total) HIPCHK(ctx, hipMemcpyAsync(out, s->parts.p, total, hipMemcpyDeviceToHost, s->stream));
     HIPCHK(ctx, hipStreamSynchronize(s->stream));
     if (kept_bytes) *kept_bytes = kept;
     if (total_bytes) *total_bytes = total;
@@ -294,13 +293,13 @@ static int text_multisplit(hpgv_ctx *ctx, const char *text, const uint8_t *bucke
     // bucket_off[nb1] | the members' offsets [nb1], the parts' last bytes | bucket
     const size_t off_boff = round_up(scratch, 256), off_bucket = round_up(off_boff + (2 * nb1 + 33) * sizeof(unsigned long long), 256);
     int rc;
-    if ((rc = ensure(ctx, s, 3, off_bucket + n + 16))) return rc;
-    if ((rc = ensure(ctx, s, 1, total + 16))) return rc;
-    char *d_aux = (char *)s->buf[3];
+    HIPCHK(ctx, s->aux.reserve_slack(off_bucket + n + 16));
+    HIPCHK(ctx, s->parts.reserve_slack(total + 16));
+    char *d_aux = s->aux.as<char>();
     unsigned long long *d_boff = (unsigned long long *)(d_aux + off_boff);
     uint8_t *d_bucket = (uint8_t *)d_aux + off_bucket;
     HIPCHK(ctx, hipMemcpyAsync(d_bucket, bucket, n, hipMemcpyHostToDevice, s->stream));
-    if ((rc = multisplit_launch(ctx, h.d_text, d_line_off, n_lines, d_bucket, n_buckets, (char *)s->buf[1], d_boff, d_aux, s->stream))) return rc;
+    if ((rc = multisplit_launch(ctx, h.d_text, d_line_off, n_lines, d_bucket, n_buckets, s->parts.as<char>(), d_boff, d_aux, s->stream))) return rc;
     if (Z) {
         if ((rc = deflate_parts(ctx, s, total, d_boff, n_buckets, d_boff + nb1))) return rc;
         std::vector<uint64_t> res(nb1 + 33);
@@ -311,7 +310,7 @@ static int text_multisplit(hpgv_ctx *ctx, const char *text, const uint8_t *bucke
         memcpy(bucket_off, res.data(), nb1 * sizeof(uint64_t));
         if (Z->last) memcpy(Z->last, res.data() + nb1, (size_t)n_buckets);
         if (made) {
-            HIPCHK(ctx, hipMemcpyAsync(out, s->buf[2], made, hipMemcpyDeviceToHost, s->stream));
+            HIPCHK(ctx, hipMemcpyAsync(out, s->members.p, made, hipMemcpyDeviceToHost, s->stream));
             HIPCHK(ctx, hipStreamSynchronize(s->stream));
         }
         return HPGV_OK;
@@ -321,7 +320,7 @@ static int text_multisplit(hpgv_ctx *ctx, const char *text, const uint8_t *bucke
     const size_t stored = (size_t)bucket_off[n_buckets];
     if (stored > out_cap || (stored && !out)) return fail(ctx, HPGV_ERR_INVALID, "the lines take %zu bytes, out has room for %zu", stored, out_cap);
     if (stored) {
-        HIPCHK(ctx, hipMemcpyAsync(out, s->buf[1], stored, hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(ctx, hipMemcpyAsync(out, s->parts.p, stored, hipMemcpyDeviceToHost, s->stream));
         HIPCHK(ctx, hipStreamSynchronize(s->stream));
     }
     return HPGV_OK;

@@ -78,19 +78,10 @@ int hpgv_layout_dev(hpgv_ctx *ctx, int which, const uint8_t *d_src, size_t src_p
         const int n = (int)std::min(slab, (long)n_variants - off);
         const long total = (long)n * L->chunks;
         hipLaunchKernelGGL(hpgv::k_layout, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                           d_src + (size_t)off * src_pitch, src_pitch, n, L->pitch, L->chunks, L->d_col_of_pos, strict, mode, p16,
+                           d_src + (size_t)off * src_pitch, src_pitch, n, L->pitch, L->chunks, L->d_col_of_pos(), strict, mode, p16,
                            d_dst + (size_t)off * L->pitch);
     }
     HIPCHK(ctx, hipGetLastError());
-    return HPGV_OK;
-}
-
-static int ensure_thr(hpgv_ctx *ctx, int n_variants) {
-    size_t need = (size_t)n_variants * 3 * sizeof(uint32_t);
-    if (ctx->thr_cap >= need) return HPGV_OK;
-    if (ctx->d_thr) { (void)hipFree(ctx->d_thr); ctx->d_thr = nullptr; ctx->thr_cap = 0; }
-    HIPCHK(ctx, hipMalloc(&ctx->d_thr, need));
-    ctx->thr_cap = need;
     return HPGV_OK;
 }
 
@@ -100,15 +91,15 @@ static int synth_common(hpgv_ctx *ctx, uint64_t v0, int n_variants, size_t pitch
     // chunk; a grid of more than 2^32 threads does not launch whole)
     const long by_threads = (1L << 31) / (chunks > 0 ? chunks : 1);
     const int slab = (int)std::max(1L, std::min((long)(1 << 20), by_threads));
-    int rc = ensure_thr(ctx, n_variants < slab ? n_variants : slab);
-    if (rc) return rc;
+    HIPCHK(ctx, ctx->d_thr.reserve((size_t)(n_variants < slab ? n_variants : slab) * 3 * sizeof(uint32_t)));
+    uint32_t *d_thr = ctx->d_thr.as<uint32_t>();
     for (int off = 0; off < n_variants; off += slab) {
         const int n = (n_variants - off) < slab ? (n_variants - off) : slab;
         hipLaunchKernelGGL(hpgv::k_synth_thresholds, dim3((n + 255) / 256), dim3(256), 0, st,
-                           v0 + (uint64_t)off, n, ctx->d_thr);
+                           v0 + (uint64_t)off, n, d_thr);
         const long total = (long)n * chunks;
         hipLaunchKernelGGL(hpgv::k_synth_layout, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
-                           v0 + (uint64_t)off, n, pitch, chunks, d_col, ctx->d_thr, mode, p16,
+                           v0 + (uint64_t)off, n, pitch, chunks, d_col, d_thr, mode, p16,
                            d_dst + (size_t)off * pitch);
         HIPCHK(ctx, hipGetLastError());
     }
@@ -127,7 +118,7 @@ int hpgv_synth_dev(hpgv_ctx *ctx, int which, uint64_t v0, int n_variants, uint8_
     int mode, p16;
     recode_of(ctx, which, &mode, &p16);
     std::lock_guard<std::mutex> lk(ctx->mu);   // shares ctx->d_thr
-    return synth_common(ctx, v0, n_variants, L->pitch, L->chunks, L->d_col_of_pos, mode, p16, d_dst, (hipStream_t)stream);
+    return synth_common(ctx, v0, n_variants, L->pitch, L->chunks, L->d_col_of_pos(), mode, p16, d_dst, (hipStream_t)stream);
 }
 
 int hpgv_synth_raw_dev(hpgv_ctx *ctx, uint64_t v0, int n_variants, int n_samples, size_t pitch,

@@ -41,8 +41,8 @@ int run(int cpt, int nm, int what, bool mendel, unsigned grid, unsigned bs, size
 }  // namespace
 
 // 0: launched; 1: this batch is not one the kernel takes (the caller runs k_stats_all); the rows of A are set by the caller;
-// cnt_buf / cnt_cap: device scratch of the calling slot for the rows' counters (grown here)
-int hpgv_launch_stats_all2(hpgv_ctx *ctx, hpgv::StatsAllArgs &A, void **cnt_buf, size_t *cnt_cap, hipStream_t st) {
+// row_cnt: device scratch of the calling slot for the rows' counters (grown here)
+int hpgv_launch_stats_all2(hpgv_ctx *ctx, hpgv::StatsAllArgs &A, DevBuf &row_cnt, hipStream_t st) {
     const int ns = A.n_samples, chunks = (ns + 15) / 16;
     if (ns <= 0 || chunks * 16 > 16384) return 1;                  // (the class buffers' fixed LDS offsets; columns as 16-bit indices)
     if (((uintptr_t)A.src & 15) || (A.src_pitch & 15) || A.src_pitch < (size_t)chunks * 16) return 1;
@@ -51,11 +51,11 @@ int hpgv_launch_stats_all2(hpgv_ctx *ctx, hpgv::StatsAllArgs &A, void **cnt_buf,
     hpgv::StatsAll2Cfg G = {nullptr, 0, 0, nullptr};
     if (A.group_out) {
         const int ng = A.n_groups;
-        if (!ctx->d_group_of_col || ng < 1) return 1;
+        if (!ctx->d_group_of_col.p || ng < 1) return 1;
         G.derive_last = ctx->all_grouped ? 1 : 0;
         G.n_masked = ng - G.derive_last;
         if (G.n_masked > 3) return 1;
-        G.group_of_col = ctx->d_group_of_col;
+        G.group_of_col = ctx->d_group_of_col.as<uint8_t>();
     }
     // chunks per thread (c) and threads per workgroup (the fewest that cover the row with c chunks each; with trios, sixteen
     // of them per thread at most): the pair that keeps the most USEFUL threads on a compute unit -- workgroups the unit holds
@@ -103,12 +103,8 @@ int hpgv_launch_stats_all2(hpgv_ctx *ctx, hpgv::StatsAllArgs &A, void **cnt_buf,
     if (lds > 64 * 1024) return 1;
     {   // the rows' packed counters between the two kernels (scratch of the calling slot)
         const size_t need = (size_t)A.n_variants * (size_t)hpgv::STATS2_W * sizeof(uint32_t);
-        if (*cnt_cap < need) {
-            if (*cnt_buf) { (void)hipFree(*cnt_buf); *cnt_buf = nullptr; *cnt_cap = 0; }
-            if (hipMalloc(cnt_buf, need + need / 4) != hipSuccess) { (void)hipGetLastError(); return 1; }
-            *cnt_cap = need + need / 4;
-        }
-        G.row_counters = (uint32_t *)*cnt_buf;
+        if (row_cnt.reserve(need, need + need / 4) != hipSuccess) { (void)hipGetLastError(); return 1; }
+        G.row_counters = row_cnt.as<uint32_t>();
     }
     const unsigned grid = (unsigned)((A.n_variants + A.rows_per_block - 1) / A.rows_per_block);
     (void)run(cpt, G.n_masked, 0, mendel, grid, bs, lds, st, A, G);
@@ -121,7 +117,7 @@ int hpgv_launch_stats_all2(hpgv_ctx *ctx, hpgv::StatsAllArgs &A, void **cnt_buf,
 // k_assoc_rows on the tokenizer's raw rows (0 = launched, 1 = not a batch it takes: the caller runs k_batch)
 int hpgv_launch_assoc_rows(hpgv_ctx *ctx, const uint8_t *d_src, size_t src_pitch, int n_variants, const uint8_t *d_is_x, int32_t *d_counts, hipStream_t st) {
     const int ns = ctx->assoc.n_samples, chunks = (ns + 15) / 16;
-    if (ns <= 0 || ns > 65535 || !ctx->d_cond) return 1;
+    if (ns <= 0 || ns > 65535 || !ctx->d_cond.p) return 1;
     if (((uintptr_t)d_src & 15) || (src_pitch & 15) || src_pitch < (size_t)chunks * 16 || ((uintptr_t)d_counts & 15)) return 1;
     int cpt = 0;
     unsigned bs = 0;
@@ -139,10 +135,10 @@ int hpgv_launch_assoc_rows(hpgv_ctx *ctx, const uint8_t *d_src, size_t src_pitch
     const unsigned grid = (unsigned)((n_variants + rows - 1) / rows);
     const size_t lds = (size_t)rows * 16 + 16;
     switch (cpt) {
-        case 1: hipLaunchKernelGGL(hpgv::k_assoc_rows<1>, dim3(grid), dim3(bs), lds, st, d_src, src_pitch, n_variants, ns, (int)rows, d_is_x, (const uint8_t *)ctx->d_cond, (int4 *)d_counts); break;
-        case 2: hipLaunchKernelGGL(hpgv::k_assoc_rows<2>, dim3(grid), dim3(bs), lds, st, d_src, src_pitch, n_variants, ns, (int)rows, d_is_x, (const uint8_t *)ctx->d_cond, (int4 *)d_counts); break;
-        case 3: hipLaunchKernelGGL(hpgv::k_assoc_rows<3>, dim3(grid), dim3(bs), lds, st, d_src, src_pitch, n_variants, ns, (int)rows, d_is_x, (const uint8_t *)ctx->d_cond, (int4 *)d_counts); break;
-        default: hipLaunchKernelGGL(hpgv::k_assoc_rows<4>, dim3(grid), dim3(bs), lds, st, d_src, src_pitch, n_variants, ns, (int)rows, d_is_x, (const uint8_t *)ctx->d_cond, (int4 *)d_counts); break;
+        case 1: hipLaunchKernelGGL(hpgv::k_assoc_rows<1>, dim3(grid), dim3(bs), lds, st, d_src, src_pitch, n_variants, ns, (int)rows, d_is_x, ctx->d_cond.as<const uint8_t>(), (int4 *)d_counts); break;
+        case 2: hipLaunchKernelGGL(hpgv::k_assoc_rows<2>, dim3(grid), dim3(bs), lds, st, d_src, src_pitch, n_variants, ns, (int)rows, d_is_x, ctx->d_cond.as<const uint8_t>(), (int4 *)d_counts); break;
+        case 3: hipLaunchKernelGGL(hpgv::k_assoc_rows<3>, dim3(grid), dim3(bs), lds, st, d_src, src_pitch, n_variants, ns, (int)rows, d_is_x, ctx->d_cond.as<const uint8_t>(), (int4 *)d_counts); break;
+        default: hipLaunchKernelGGL(hpgv::k_assoc_rows<4>, dim3(grid), dim3(bs), lds, st, d_src, src_pitch, n_variants, ns, (int)rows, d_is_x, ctx->d_cond.as<const uint8_t>(), (int4 *)d_counts); break;
     }
     return 0;
 }

@@ -1,4 +1,5 @@
-"""The batch and text entry points share one back half per tool (hpgv_tool_capi.hip).  Two things no other test pins:
+"""The batch and text entry points share one back half per tool (hpgv_tool_capi.hip; the text's front half is in
+hpgv_text_capi.hip).  Two things no other test pins:
 the clamp of the multi-allelic tables to the caller's capacity -- one function behind hpgv_stats_ex and
 hpgv_stats_text_groups, fused and as a kernel chain -- and the bad-argument codes of the entry points that are now
 guarded against C++ exceptions."""
