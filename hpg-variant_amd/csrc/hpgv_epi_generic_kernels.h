@@ -21,8 +21,6 @@
 
 namespace hpgv {
 
-constexpr int EPI_MASK_WORDS = 8;                                    // 243 cells of order 5 in 8 x 32 bits
-
 struct EpiCandN {                                                    // a listed combination that reached a fold's threshold
     double accuracy;
     uint32_t index;                                                  // its index in the launch's list

@@ -11,7 +11,7 @@ struct EpiModel {
     double accuracy;
     int32_t c[5];                      // its SNPs in ascending order, -1 past the order
     int32_t used;
-    uint32_t risky[8];                 // bit c = cell c is high risk; orders 2 and 3 fill word 0
+    uint32_t risky[hpgv::EPI_MASK_WORDS];      // bit c = cell c is high risk; orders 2 and 3 fill word 0
 };
 static_assert(sizeof(EpiModel) == 64, "one record of the gathered top lists");
 

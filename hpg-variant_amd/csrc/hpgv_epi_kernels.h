@@ -24,6 +24,7 @@ constexpr int EPI_CH = 32;            // words of one LDS chunk (1024 samples)
 constexpr int EPI_TJ = 64;            // tile: 64 columns (one per lane) ...
 constexpr int EPI_TI = 4;             // ... x 4 rows (one per wave)
 constexpr int EPI_MAX_FOLDS = 16;
+constexpr int EPI_MASK_WORDS = 8;     // words of a model's high-risk mask: the 243 cells of order 5 in 8 x 32 bits
 constexpr int EPI_WIDE_MAX_FOLDS = 64; // folds of the wide listed-combination kernel (hpgv_epi_wide_kernels.h, option "epi_wide"): the bound of the host's fold tables
 
 struct EpiChunk {                     // one staging block: up to EPI_CH consecutive words, possibly of several groups

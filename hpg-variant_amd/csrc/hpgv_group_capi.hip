@@ -4,16 +4,26 @@
 // (assoc_runner.c:106-207, tdt_runner.c:150-200, stats_runner.c:176-215); variants carry no state from one to the next
 // (assoc.c:38-82, tdt.c:41-271).  With the cohort resident in the HBM of G devices this becomes: member g scans the
 // contiguous shard [g*V/G, (g+1)*V/G) on a stream of its own -- no traffic between devices while scanning -- and the ONE
-// exchange is the gather of the per-variant result pieces onto member 0: grouped ncclSend / ncclRecv on a
-// communicator the group owns (ncclCommInitAll over the members' devices: one process, RCCL over xGMI, every peer on its
-// own link into member 0).  Per-sample counters (get_sample_stats) are sums over variants: ncclReduce onto member 0.
+// exchange is the hand-over of the per-variant result pieces onto member 0.  Per-sample counters
+// (get_sample_stats) are sums over variants: ncclReduce onto member 0.
+//
+// The unit in four parts:
+//   route      decided once per member when a call is planned (plan_call): member 0 produces IN PLACE; a second context on
+//              member 0's device hands over by a device-LOCAL copy; another device over the group's COMMunicator
+//              (ncclCommInitAll over the members' devices: one process, RCCL over xGMI, every peer on its own link into member 0)
+//   hand_over  the one routine that moves bytes onto member 0, given a list of transfers: grouped ncclSend / ncclRecv, or
+//              hipMemcpyAsync.  The scans' pieces and the epistasis ranking's top lists both go through it
+//   rccl_group the one place an RCCL group is opened; it is ended whatever happens in between
+//   group_scan the skeleton of hpgv_group_assoc / _tdt / _stats: an entry point brings its checks, its piece table and
+//              what one member queues on its scan stream
 //
 // librccl is loaded with dlopen when the communicator is first asked for: libhpgv.so itself has no RCCL dependency, a
 // single-device user never loads it, and inside a process that already holds an RCCL (torch's) the same copy is used.
 //
 // Streams: every member has a scan stream and a transfer stream.  A call queues, per member: [wait until the transfer
-// that last read this generation's scratch is done] scan + statistics kernels -> event -> (transfer stream) send of the
-// pieces.  Two generations of scratch per member let the transfers of call k run under the scans of call k + 1.
+// that last read this generation's scratch is done] scan + statistics kernels -> event -> (transfer stream) hand-over of the
+// pieces.  Two generations of scratch per member let the transfers of call k run under the scans of call k + 1.  A call
+// that fails after it has queued anything returns with every stream of the group idle (drain).
 #include "hpgv_epi_host.h"
 
 #include <dlfcn.h>
@@ -41,31 +51,28 @@ ncclResult_t ncclReduce(const void *sendbuff, void *recvbuff, size_t count, nccl
 }
 #endif
 
+// what the unit calls of librccl: GroupState holds nccl<name> as <name>, load_rccl resolves them, the probe asks for them
+#define RCCL_SYMBOLS(X) X(CommInitAll) X(CommDestroy) X(CommCount) X(GetErrorString) X(GroupStart) X(GroupEnd) X(Send) X(Recv) X(Reduce)
+
 struct GroupMember {
     hipStream_t scan = nullptr, xfer = nullptr;
     hipEvent_t scan_done[2] = {nullptr, nullptr}, xfer_done[2] = {nullptr, nullptr};
     bool xfer_pending[2] = {false, false};
     DevBuf scratch[2];              // this member's results on their way to member 0, one per generation of calls
     DevBuf miss[2];                 // int32: per-sample counters of this member's shard, per generation like the scratch
-    int rank = 0;                   // RCCL rank of the member's device
-    bool local = false;             // shares member 0's device: results handed over by a device-local copy
+    int rank = 0;                   // RCCL rank of the member's device; 0: member 0's device
 };
 
 struct GroupState {
     std::mutex mu;                  // one group call is queued at a time
     void *dl = nullptr;
-    decltype(&ncclCommInitAll) CommInitAll = nullptr;
-    decltype(&ncclCommDestroy) CommDestroy = nullptr;
-    decltype(&ncclCommCount) CommCount = nullptr;
-    decltype(&ncclGetErrorString) GetErrorString = nullptr;
-    decltype(&ncclGroupStart) GroupStart = nullptr;
-    decltype(&ncclGroupEnd) GroupEnd = nullptr;
-    decltype(&ncclSend) Send = nullptr;
-    decltype(&ncclRecv) Recv = nullptr;
-    decltype(&ncclReduce) Reduce = nullptr;
+#define X(name) decltype(&nccl##name) name = nullptr;
+    RCCL_SYMBOLS(X)
+#undef X
     std::vector<ncclComm_t> comms;  // one per distinct device, rank r = r-th distinct device in member order
     std::vector<int> devs;
     std::vector<GroupMember> m;
+    DevBuf lists;                   // member 0's device: the members' top lists of a ranking call, in member order
     unsigned gen = 0;
     bool ready = false;
 };
@@ -77,13 +84,6 @@ __global__ void k_add_i32(int32_t *__restrict__ dst, const int32_t *__restrict__
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n && src[i]) atomicAdd(&dst[i], src[i]);
 }
-
-#define NCCLCHK(g, S, call)                                                                       \
-    do {                                                                                          \
-        ncclResult_t r_ = (call);                                                                 \
-        if (r_ != ncclSuccess)                                                                    \
-            return fail(g, HPGV_ERR_HIP, "%s failed: %s (%s:%d)", #call, (S)->GetErrorString(r_), __FILE__, __LINE__); \
-    } while (0)
 
 // dlopen of librccl under its usual names ($HPGV_RCCL_LIB first); `tried` collects why each candidate failed
 void *open_rccl(std::string &tried) {
@@ -119,14 +119,43 @@ int load_rccl(hpgv_ctx *g, GroupState *S) {
     if (!S->dl)
         return fail(g, HPGV_ERR_UNSUPPORTED, "the group-wide scan gathers its results over RCCL and librccl could not be loaded (%s); "
                                              "set HPGV_RCCL_LIB to its path", tried.c_str());
-#define SYM(field, name)                                                                          \
-    S->field = (decltype(S->field))dlsym(S->dl, name);                                            \
-    if (!S->field) { dlclose(S->dl); S->dl = nullptr; return fail(g, HPGV_ERR_UNSUPPORTED, "librccl lacks %s", name); }
-    SYM(CommInitAll, "ncclCommInitAll") SYM(CommDestroy, "ncclCommDestroy") SYM(CommCount, "ncclCommCount")
-    SYM(GetErrorString, "ncclGetErrorString") SYM(GroupStart, "ncclGroupStart") SYM(GroupEnd, "ncclGroupEnd")
-    SYM(Send, "ncclSend") SYM(Recv, "ncclRecv") SYM(Reduce, "ncclReduce")
-#undef SYM
-    return HPGV_OK;
+    const char *lacks = nullptr;
+#define X(name) if (!lacks && !(S->name = (decltype(S->name))dlsym(S->dl, "nccl" #name))) lacks = "nccl" #name;
+    RCCL_SYMBOLS(X)
+#undef X
+    if (!lacks) return HPGV_OK;
+    dlclose(S->dl);
+    S->dl = nullptr;
+    return fail(g, HPGV_ERR_UNSUPPORTED, "librccl lacks %s", lacks);
+}
+
+// The ONE place an RCCL group is opened.  `calls` queues the group's operations and returns the first result that is not
+// ncclSuccess; the group is ended whatever it returns -- no path leaves this function with the group open -- and the first
+// failure of the three is the call's error.
+template <class Calls>
+int rccl_group(hpgv_ctx *g, GroupState *S, const char *what, Calls &&calls) {
+    ncclResult_t r = S->GroupStart();
+    if (r == ncclSuccess) {
+        r = calls();
+        const ncclResult_t ended = S->GroupEnd();
+        if (r == ncclSuccess) r = ended;
+    }
+    return r == ncclSuccess ? HPGV_OK : fail(g, HPGV_ERR_HIP, "%s over the group's communicator failed: %s", what, S->GetErrorString(r));
+}
+
+// every stream of the group idle and no transfer pending; the first error of the waits
+hipError_t quiesce(hpgv_ctx *g, GroupState *S) {
+    hipError_t first = hipSuccess;
+    for (size_t k = 0; k < S->m.size() && k < g->members.size(); ++k) {
+        GroupMember &M = S->m[k];
+        DeviceGuard dg(g->members[k]->device);
+        for (hipStream_t st : {M.scan, M.xfer}) {
+            const hipError_t e = st ? hipStreamSynchronize(st) : hipSuccess;
+            if (first == hipSuccess) first = e;
+        }
+        M.xfer_pending[0] = M.xfer_pending[1] = false;
+    }
+    return first;
 }
 
 void shard_of(int64_t V, int G, int g, int64_t *lo, int64_t *hi) {
@@ -134,41 +163,44 @@ void shard_of(int64_t V, int G, int g, int64_t *lo, int64_t *hi) {
     *hi = (int64_t)((__int128)V * (g + 1) / G);
 }
 
-int ensure_scratch(hpgv_ctx *mc, GroupMember &M, int gen, size_t bytes) {
-    HIPCHK(mc, M.scratch[gen].reserve(bytes, round_up(bytes + bytes / 16, 256)));
-    return HPGV_OK;
-}
-
-// one result piece: `elem` bytes per variant, gathered into dst (member 0's device, variant v at dst + v * elem)
+// one result piece: `elem` bytes per variant, gathered into dst (member 0's device, variant v at dst + v * elem); a piece
+// without a destination is computed into scratch and stays there
 struct Piece { size_t elem; void *dst; };
+
+// how a member's results reach member 0: it is member 0 and produces them where they belong; it is another context on member
+// 0's device and copies them there (RCCL refuses one device twice: the one-GPU test rig); it sits on another device and sends
+// them through the communicator -- as member 0 does to itself with the test switch group_self_exchange
+enum class Route { in_place, local_copy, comm };
+
+struct Transfer { int member; const void *src; void *dst; size_t bytes; };      // src on the member's device, dst on member 0's
 
 struct Plan {
     hpgv_ctx *g;
     GroupState *S;
     int G, gen;
-    int64_t V;
+    std::vector<Route> route;
     std::vector<int64_t> lo, n;
-    std::vector<bool> via_scratch;      // member's results go to its scratch first and are handed over
-    std::vector<char *> base;           // where member k's piece 0 starts (scratch, or the destination itself for member 0)
+    std::vector<char *> base;           // where member k's piece 0 starts in its scratch (in place: nowhere, see piece_at)
 };
 
-// validates, cuts the shards, makes the scratch of this generation ready and the scan stream wait for the transfer that
-// last read it
-int plan_call(hpgv_ctx *g, int64_t V, size_t bytes_per_variant, Plan &P) {
-    if (!is_group(g)) return fail(g, HPGV_ERR_INVALID, "hpgv_group_* needs a group context (hpgv_create_multi)");
+// cuts the shards, gives every member its route, makes the scratch of this generation ready and the scan stream wait for
+// the transfer that last read it
+int plan_call(hpgv_ctx *g, int64_t V, const std::vector<Piece> &pieces, Plan &P) {
     if (V < 0) return fail(g, HPGV_ERR_INVALID, "n_variants < 0");
     GroupState *S = g->grp;
-    P.g = g; P.S = S; P.G = (int)g->members.size(); P.V = V;
+    P.g = g; P.S = S; P.G = (int)g->members.size();
     P.gen = (int)(S->gen++ & 1u);
-    P.lo.resize(P.G); P.n.resize(P.G); P.via_scratch.resize(P.G); P.base.assign(P.G, nullptr);
+    P.lo.resize(P.G); P.n.resize(P.G); P.route.resize(P.G); P.base.assign(P.G, nullptr);
+    size_t bytes_per_variant = 0;
+    for (const Piece &pc : pieces) bytes_per_variant += pc.elem;
     for (int k = 0; k < P.G; ++k) {
         int64_t lo, hi;
         shard_of(V, P.G, k, &lo, &hi);
         if (hi - lo > 0x7fffffff) return fail(g, HPGV_ERR_UNSUPPORTED, "a member's shard has more than 2^31 - 1 variants");
         P.lo[k] = lo; P.n[k] = hi - lo;
-        P.via_scratch[k] = k > 0 || g->group_self_exchange;
         hpgv_ctx *mc = g->members[k];
         GroupMember &M = S->m[k];
+        P.route[k] = k == 0 ? (g->group_self_exchange ? Route::comm : Route::in_place) : M.rank == 0 ? Route::local_copy : Route::comm;
         DeviceGuard dg(mc->device);
         // the transfer of two calls ago read this generation's scratch (member 0: wrote the caller's arrays of that call,
         // which a caller alternating between two result sets hands in again now)
@@ -176,86 +208,210 @@ int plan_call(hpgv_ctx *g, int64_t V, size_t bytes_per_variant, Plan &P) {
             HIPCHK(mc, hipStreamWaitEvent(M.scan, M.xfer_done[P.gen], 0));
             M.xfer_pending[P.gen] = false;
         }
-        if (!P.via_scratch[k]) continue;
-        const int e = ensure_scratch(mc, M, P.gen, (size_t)P.n[k] * bytes_per_variant + 256);
-        if (e) return e;
+        if (P.route[k] == Route::in_place) continue;
+        const size_t bytes = (size_t)P.n[k] * bytes_per_variant + 256;
+        HIPCHK(mc, M.scratch[P.gen].reserve(bytes, round_up(bytes + bytes / 16, 256)));
         P.base[k] = M.scratch[P.gen].as<char>();
     }
     return HPGV_OK;
 }
 
-// a call that fails after plan_call has kernels queued on members' scan streams and no event recorded for them: the
-// streams are drained, so that the scratch of this generation and the caller's arrays are quiet when the error returns
+// a call that fails after plan_call may have work queued on members' streams and no event recorded for it: the streams are
+// drained, so that the scratch of this generation and the caller's arrays are quiet when the error returns
 int drain(const Plan &P, int rc) {
-    for (int k = 0; k < P.G; ++k) {
-        GroupMember &M = P.S->m[(size_t)k];
-        DeviceGuard dg(P.g->members[(size_t)k]->device);
-        if (M.scan) (void)hipStreamSynchronize(M.scan);
-        if (M.xfer) (void)hipStreamSynchronize(M.xfer);
-        M.xfer_pending[0] = M.xfer_pending[1] = false;
-    }
+    (void)quiesce(P.g, P.S);
     (void)hipGetLastError();
     return rc;
 }
 
-// address of member k's piece i (`before` = bytes per variant of the pieces in front of it)
-inline char *piece_src(const Plan &P, int k, const Piece &pc, size_t before) {
-    if (!P.via_scratch[k]) return (char *)pc.dst + (size_t)P.lo[k] * pc.elem;
+// where member k produces its piece i: in the destination itself, or in its scratch behind the pieces in front of it
+char *piece_at(const Plan &P, const std::vector<Piece> &pieces, int k, size_t i) {
+    if (P.route[k] == Route::in_place) return pieces[i].dst ? (char *)pieces[i].dst + (size_t)P.lo[k] * pieces[i].elem : nullptr;
+    size_t before = 0;
+    for (size_t j = 0; j < i; ++j) before += pieces[j].elem;
     return P.base[k] + (size_t)P.n[k] * before;
 }
 
-// after the members' kernels are queued: the hand-over of the pieces onto member 0
-int exchange(Plan &P, const std::vector<Piece> &pieces) {
+// the pieces of every member that does not produce in place, as transfers onto member 0
+std::vector<Transfer> piece_transfers(const Plan &P, const std::vector<Piece> &pieces) {
+    std::vector<Transfer> T;
+    for (int k = 0; k < P.G; ++k) {
+        if (P.route[k] == Route::in_place || P.n[k] == 0) continue;
+        for (size_t i = 0; i < pieces.size(); ++i)
+            if (pieces[i].dst)
+                T.push_back({k, piece_at(P, pieces, k, i), (char *)pieces[i].dst + (size_t)P.lo[k] * pieces[i].elem, (size_t)P.n[k] * pieces[i].elem});
+    }
+    return T;
+}
+
+// The ONE hand-over onto member 0, after the members' work is queued on their scan streams: every transfer stream waits for
+// its member's scan, then carries that member's transfers by its route -- the communicator's in one RCCL group, then member
+// by member the local copies -- and xfer_done marks the end of what it carried.
+int hand_over(Plan &P, const std::vector<Transfer> &T) {
     hpgv_ctx *g = P.g;
     GroupState *S = P.S;
-    GroupMember &M0 = S->m[0];
     for (int k = 0; k < P.G; ++k) {
         hpgv_ctx *mc = g->members[k];
         GroupMember &M = S->m[k];
         DeviceGuard dg(mc->device);
         HIPCHK(mc, hipEventRecord(M.scan_done[P.gen], M.scan));
-        if (P.via_scratch[k]) HIPCHK(mc, hipStreamWaitEvent(M.xfer, M.scan_done[P.gen], 0));
+        if (P.route[k] != Route::in_place) HIPCHK(mc, hipStreamWaitEvent(M.xfer, M.scan_done[P.gen], 0));
     }
-    // how member k hands its pieces over: a context on another device sends them through the communicator; a second context
-    // on member 0's device copies them (RCCL refuses one device twice: the one-GPU test rig); member 0 itself scans into the
-    // destination -- or, with the test switch group_self_exchange, sends to itself through the communicator
-    auto by_rccl = [&](int k) { return P.via_scratch[k] && (!S->m[(size_t)k].local || k == 0); };
-    bool any_rccl = false;
-    for (int k = 0; k < P.G; ++k) any_rccl = any_rccl || (by_rccl(k) && P.n[k] > 0);
-    if (any_rccl) {
-        NCCLCHK(g, S, S->GroupStart());
-        for (int k = 0; k < P.G; ++k) {
-            GroupMember &M = S->m[(size_t)k];
-            if (!by_rccl(k) || P.n[k] == 0) continue;
-            size_t before = 0;
-            for (const Piece &pc : pieces) {
-                if (pc.dst) {
-                    const size_t bytes = (size_t)P.n[k] * pc.elem;
-                    NCCLCHK(g, S, S->Send(piece_src(P, k, pc, before), bytes, ncclInt8, 0, S->comms[(size_t)M.rank], M.xfer));
-                    NCCLCHK(g, S, S->Recv((char *)pc.dst + (size_t)P.lo[k] * pc.elem, bytes, ncclInt8, M.rank, S->comms[0], M0.xfer));
-                }
-                before += pc.elem;
+    const auto goes = [&](const Transfer &t, Route r) { return P.route[t.member] == r; };
+    if (std::any_of(T.begin(), T.end(), [&](const Transfer &t) { return goes(t, Route::comm); })) {
+        const int rc = rccl_group(g, S, "the hand-over onto member 0", [&]() -> ncclResult_t {
+            for (const Transfer &t : T) {
+                if (!goes(t, Route::comm)) continue;
+                GroupMember &M = S->m[(size_t)t.member];
+                ncclResult_t r = S->Send(t.src, t.bytes, ncclInt8, 0, S->comms[(size_t)M.rank], M.xfer);
+                if (r == ncclSuccess) r = S->Recv(t.dst, t.bytes, ncclInt8, M.rank, S->comms[0], S->m[0].xfer);
+                if (r != ncclSuccess) return r;
             }
-        }
-        NCCLCHK(g, S, S->GroupEnd());
+            return ncclSuccess;
+        });
+        if (rc) return rc;
     }
     for (int k = 0; k < P.G; ++k) {
-        GroupMember &M = S->m[(size_t)k];
-        hpgv_ctx *mc = g->members[(size_t)k];
+        hpgv_ctx *mc = g->members[k];
+        GroupMember &M = S->m[k];
         DeviceGuard dg(mc->device);
-        if (P.via_scratch[k] && !by_rccl(k) && P.n[k] > 0) {
-            size_t before = 0;
-            for (const Piece &pc : pieces) {
-                if (pc.dst)
-                    HIPCHK(mc, hipMemcpyAsync((char *)pc.dst + (size_t)P.lo[k] * pc.elem, piece_src(P, k, pc, before),
-                                              (size_t)P.n[k] * pc.elem, hipMemcpyDeviceToDevice, M.xfer));
-                before += pc.elem;
-            }
+        for (const Transfer &t : T)
+            if (t.member == k && goes(t, Route::local_copy)) HIPCHK(mc, hipMemcpyAsync(t.dst, t.src, t.bytes, hipMemcpyDeviceToDevice, M.xfer));
+        HIPCHK(mc, hipEventRecord(M.xfer_done[P.gen], M.xfer));     // (member 0 in place: the event its next call of this generation waits for)
+        M.xfer_pending[P.gen] = true;
+    }
+    return HPGV_OK;
+}
+
+int no_step(Plan &) { return HPGV_OK; }
+
+// The skeleton of the three scans, after the entry point's own argument checks.  member(k, mc, stream, gt, n, at) queues
+// member k's *_dev calls for its n variants, piece i produced at at[i]; `before` and `after` are what a call queues
+// around the scans and their hand-over (the per-sample counters of hpgv_group_stats).
+template <class Member, class Before, class After>
+int group_scan(hpgv_ctx *g, const uint8_t *const *d_gt, int64_t V, const std::vector<Piece> &pieces, Member member, Before before, After after) {
+    int rc = hpgv_group_comm_init(g);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(g->grp->mu);
+    Plan P;
+    rc = plan_call(g, V, pieces, P);
+    if (rc) return rc;
+    rc = before(P);
+    std::vector<void *> at(pieces.size());
+    for (int k = 0; k < P.G && !rc; ++k) {
+        if (P.n[k] == 0) continue;
+        if (!d_gt[k]) { rc = fail(g, HPGV_ERR_INVALID, "member %d has %lld variants but no matrix", k, (long long)P.n[k]); break; }
+        for (size_t i = 0; i < pieces.size(); ++i) at[i] = piece_at(P, pieces, k, i);
+        rc = member(k, g->members[(size_t)k], P.S->m[(size_t)k].scan, d_gt[k], (int)P.n[k], at.data());
+    }
+    if (!rc) rc = hand_over(P, piece_transfers(P, pieces));
+    if (!rc) rc = after(P);
+    return rc ? drain(P, rc) : HPGV_OK;
+}
+
+// ---- the per-sample counters of hpgv_group_stats: sums over variants, so every member counts its shard and the counts are
+//      added up on member 0.  Member 0 is where they are added, whichever way its pieces go: it counts straight into the
+//      caller's array.  The others count into an array of their own and follow their route: a context on member 0's device adds
+//      with k_add_i32, another device takes part in the ncclReduce. ----
+
+// before the scans: where member k counts (miss[k]), zeroed on its scan stream.  d_total = nullptr: no counters are asked for
+int counters_begin(Plan &P, int32_t *d_total, int n_samples, std::vector<int32_t *> &miss) {
+    hpgv_ctx *g = P.g;
+    if (!d_total) return HPGV_OK;
+    if (!g->members[0]->stats.set) return fail(g, HPGV_ERR_STATE, "hpgv_set_stats_cohort has not been called");
+    for (int k = 0; k < P.G && n_samples > 0; ++k) {
+        hpgv_ctx *mc = g->members[(size_t)k];
+        GroupMember &M = P.S->m[(size_t)k];
+        DeviceGuard dg(mc->device);
+        if (k == 0) {
+            // the caller's array is the one destination every member ADDS into: the previous call's adds and its ncclReduce (the
+            // OTHER generation's transfers) may still be running when this call's memset is queued.  plan_call made member 0's
+            // scan wait for this generation only; with counters, it also waits for the other one.
+            if (M.xfer_pending[P.gen ^ 1]) HIPCHK(g, hipStreamWaitEvent(M.scan, M.xfer_done[P.gen ^ 1], 0));
+            miss[0] = d_total;
+        } else {
+            HIPCHK(mc, M.miss[P.gen].reserve((size_t)n_samples * sizeof(int32_t)));
+            miss[(size_t)k] = M.miss[P.gen].as<int32_t>();
         }
-        if (P.via_scratch[k] || k == 0) {
-            HIPCHK(mc, hipEventRecord(M.xfer_done[P.gen], M.xfer));
-            M.xfer_pending[P.gen] = true;
+        HIPCHK(mc, hipMemsetAsync(miss[(size_t)k], 0, (size_t)n_samples * sizeof(int32_t), M.scan));
+    }
+    return HPGV_OK;
+}
+
+// after the hand-over: a context on member 0's device adds its own on ITS transfer stream (which the next call of this
+// generation waits for before it overwrites them), then one ncclReduce (sum, in place on member 0) over the communicator's
+// ranks on member 0's transfer stream, behind those adds and member 0's own scan
+int counters_reduce(Plan &P, int32_t *d_total, int n_samples) {
+    if (!d_total || n_samples <= 0) return HPGV_OK;
+    hpgv_ctx *g = P.g;
+    GroupState *S = P.S;
+    GroupMember &M0 = S->m[0];
+    {
+        DeviceGuard dg(g->members[0]->device);
+        HIPCHK(g, hipStreamWaitEvent(M0.xfer, M0.scan_done[P.gen], 0));
+        for (int k = 1; k < P.G; ++k) {
+            GroupMember &M = S->m[(size_t)k];
+            if (P.route[k] != Route::local_copy) continue;
+            HIPCHK(g, hipStreamWaitEvent(M.xfer, M0.scan_done[P.gen], 0));      // member 0's memset of the counters is behind this event
+            hipLaunchKernelGGL(k_add_i32, dim3((unsigned)((n_samples + 255) / 256)), dim3(256), 0, M.xfer, d_total,
+                               M.miss[P.gen].as<int32_t>(), n_samples);
+            HIPCHK(g, hipGetLastError());
+            HIPCHK(g, hipEventRecord(M.xfer_done[P.gen], M.xfer));
+            HIPCHK(g, hipStreamWaitEvent(M0.xfer, M.xfer_done[P.gen], 0));
         }
+    }
+    const int rc = rccl_group(g, S, "the reduce of the per-sample counters", [&]() -> ncclResult_t {
+        ncclResult_t r = S->Reduce(d_total, d_total, (size_t)n_samples, ncclInt32, ncclSum, 0, S->comms[0], M0.xfer);
+        for (int k = 1; k < P.G && r == ncclSuccess; ++k) {
+            GroupMember &M = S->m[(size_t)k];
+            int32_t *own = M.miss[P.gen].as<int32_t>();
+            if (P.route[k] == Route::comm) r = S->Reduce(own, own, (size_t)n_samples, ncclInt32, ncclSum, 0, S->comms[(size_t)M.rank], M.xfer);
+        }
+        return r;
+    });
+    if (rc) return rc;
+    for (int k = 0; k < P.G; ++k) {
+        hpgv_ctx *mc = g->members[(size_t)k];
+        GroupMember &M = S->m[(size_t)k];
+        DeviceGuard dg(mc->device);
+        HIPCHK(mc, hipEventRecord(M.xfer_done[P.gen], M.xfer));
+        M.xfer_pending[P.gen] = true;
+    }
+    return HPGV_OK;
+}
+
+// ranks = the distinct devices in member order (a device may repeat only when it is member 0's), the communicator over
+// them, and every member's streams and events.  What a failure leaves behind, hpgv_group_release takes down.
+int comm_setup(hpgv_ctx *g, GroupState *S) {
+    const int G = (int)g->members.size();
+    S->devs.clear();
+    S->m.assign((size_t)G, GroupMember());
+    for (int k = 0; k < G; ++k) {
+        const int dev = g->members[(size_t)k]->device;
+        int r = -1;
+        for (size_t i = 0; i < S->devs.size(); ++i) if (S->devs[i] == dev) r = (int)i;
+        if (r > 0) return fail(g, HPGV_ERR_UNSUPPORTED, "device %d is listed twice and is not member 0's: only member 0's device may repeat (the one-GPU test rig)", dev);
+        if (r < 0) { r = (int)S->devs.size(); S->devs.push_back(dev); }
+        S->m[(size_t)k].rank = r;
+    }
+    if (int rc = load_rccl(g, S)) return rc;
+    S->comms.assign(S->devs.size(), nullptr);
+    const ncclResult_t r = S->CommInitAll(S->comms.data(), (int)S->devs.size(), S->devs.data());
+    if (r != ncclSuccess) {
+        S->comms.clear();
+        return fail(g, HPGV_ERR_HIP, "ncclCommInitAll over %d device(s) failed: %s", (int)S->devs.size(), S->GetErrorString(r));
+    }
+    for (int k = 0; k < G; ++k) {
+        hpgv_ctx *mc = g->members[(size_t)k];
+        GroupMember &M = S->m[(size_t)k];
+        DeviceGuard dg(mc->device);
+        hipError_t e = hipStreamCreateWithFlags(&M.scan, hipStreamNonBlocking);
+        if (e == hipSuccess) e = hipStreamCreateWithFlags(&M.xfer, hipStreamNonBlocking);
+        for (int i = 0; i < 2 && e == hipSuccess; ++i) {
+            e = hipEventCreateWithFlags(&M.scan_done[i], hipEventDisableTiming);
+            if (e == hipSuccess) e = hipEventCreateWithFlags(&M.xfer_done[i], hipEventDisableTiming);
+        }
+        if (e != hipSuccess) return fail(g, HPGV_ERR_HIP, "group streams on device %d: %s", mc->device, hipGetErrorString(e));
     }
     return HPGV_OK;
 }
@@ -265,17 +421,13 @@ int exchange(Plan &P, const std::vector<Piece> &pieces) {
 void hpgv_group_release(hpgv_ctx *g) {
     if (!g || !g->grp) return;
     GroupState *S = g->grp;
-    for (size_t k = 0; k < S->m.size() && k < g->members.size(); ++k) {
-        GroupMember &M = S->m[k];
-        DeviceGuard dg(g->members[k]->device);
-        if (M.scan) (void)hipStreamSynchronize(M.scan);
-        if (M.xfer) (void)hipStreamSynchronize(M.xfer);
-    }
+    (void)quiesce(g, S);
     if (S->CommDestroy)
         for (ncclComm_t c : S->comms) if (c) (void)S->CommDestroy(c);
     for (size_t k = 0; k < S->m.size() && k < g->members.size(); ++k) {
         GroupMember &M = S->m[k];
         DeviceGuard dg(g->members[k]->device);
+        if (k == 0) S->lists.release();
         for (int i = 0; i < 2; ++i) {
             M.scratch[i].release();
             M.miss[i].release();
@@ -298,50 +450,10 @@ int hpgv_group_comm_init(hpgv_ctx *g) {
     std::lock_guard<std::mutex> lk(g->mu);
     if (g->grp && g->grp->ready) return HPGV_OK;
     if (!g->grp) g->grp = new GroupState();
-    GroupState *S = g->grp;
-    const int G = (int)g->members.size();
-    // ranks = the distinct devices in member order; a device may repeat only when it is member 0's
-    S->devs.clear();
-    S->m.assign((size_t)G, GroupMember());
-    for (int k = 0; k < G; ++k) {
-        const int dev = g->members[(size_t)k]->device;
-        int r = -1;
-        for (size_t i = 0; i < S->devs.size(); ++i) if (S->devs[i] == dev) r = (int)i;
-        if (r > 0) { hpgv_group_release(g); return fail(g, HPGV_ERR_UNSUPPORTED, "device %d is listed twice and is not member 0's: only member 0's device may repeat (the one-GPU test rig)", dev); }
-        if (r < 0) { r = (int)S->devs.size(); S->devs.push_back(dev); }
-        S->m[(size_t)k].rank = r;
-        S->m[(size_t)k].local = (r == 0);
-    }
-    int rc = load_rccl(g, S);
-    if (rc) { hpgv_group_release(g); return rc; }
-    S->comms.assign(S->devs.size(), nullptr);
-    {
-        ncclResult_t r = S->CommInitAll(S->comms.data(), (int)S->devs.size(), S->devs.data());
-        if (r != ncclSuccess) {
-            rc = fail(g, HPGV_ERR_HIP, "ncclCommInitAll over %d device(s) failed: %s", (int)S->devs.size(), S->GetErrorString(r));
-            S->comms.clear();
-            hpgv_group_release(g);
-            return rc;
-        }
-    }
-    for (int k = 0; k < G; ++k) {
-        hpgv_ctx *mc = g->members[(size_t)k];
-        GroupMember &M = S->m[(size_t)k];
-        DeviceGuard dg(mc->device);
-        hipError_t e = hipStreamCreateWithFlags(&M.scan, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipStreamCreateWithFlags(&M.xfer, hipStreamNonBlocking);
-        for (int i = 0; i < 2 && e == hipSuccess; ++i) {
-            e = hipEventCreateWithFlags(&M.scan_done[i], hipEventDisableTiming);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&M.xfer_done[i], hipEventDisableTiming);
-        }
-        if (e != hipSuccess) {
-            rc = fail(g, HPGV_ERR_HIP, "group streams on device %d: %s", mc->device, hipGetErrorString(e));
-            hpgv_group_release(g);
-            return rc;
-        }
-    }
-    S->ready = true;
-    return HPGV_OK;
+    const int rc = comm_setup(g, g->grp);
+    if (rc) hpgv_group_release(g);
+    else g->grp->ready = true;
+    return rc;
     HPGV_ABI_CATCH(g)
 }
 
@@ -351,7 +463,9 @@ int hpgv_group_rccl_probe(char *why, size_t why_cap) {
         void *dl = open_rccl(tried);
         if (why && why_cap) snprintf(why, why_cap, "%s", tried.c_str());
         if (!dl) return HPGV_ERR_UNSUPPORTED;
-        const bool ok = dlsym(dl, "ncclCommInitAll") && dlsym(dl, "ncclSend") && dlsym(dl, "ncclRecv") && dlsym(dl, "ncclReduce");
+#define X(name) && dlsym(dl, "nccl" #name)
+        const bool ok = true RCCL_SYMBOLS(X);
+#undef X
         dlclose(dl);
         return ok ? HPGV_OK : HPGV_ERR_UNSUPPORTED;
     } catch (...) { return HPGV_ERR_NOMEM; }
@@ -384,14 +498,7 @@ int hpgv_group_sync(hpgv_ctx *g) {
     }
     if (!S) return HPGV_OK;
     std::lock_guard<std::mutex> lk(S->mu);
-    for (size_t k = 0; k < g->members.size(); ++k) {
-        hpgv_ctx *mc = g->members[k];
-        GroupMember &M = g->grp->m[k];
-        DeviceGuard dg(mc->device);
-        HIPCHK(g, hipStreamSynchronize(M.scan));
-        HIPCHK(g, hipStreamSynchronize(M.xfer));
-        M.xfer_pending[0] = M.xfer_pending[1] = false;
-    }
+    HIPCHK(g, quiesce(g, S));
     return HPGV_OK;
 }
 
@@ -404,28 +511,13 @@ int hpgv_group_assoc(hpgv_ctx *g, int task, const uint8_t *const *d_gt, const ui
         return fail(g, HPGV_ERR_INVALID, "bad group assoc arguments");
     const bool chisq = task == HPGV_TASK_CHISQ;
     const std::vector<Piece> pieces = {{16, d_counts}, {8, d_odds}, {8, chisq ? d_chisq : nullptr}, {8, d_p}};
-    int rc = hpgv_group_comm_init(g);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(g->grp->mu);
-    Plan P;
-    rc = plan_call(g, V, 40, P);
-    if (rc) return rc;
-    for (int k = 0; k < P.G; ++k) {
-        if (P.n[k] == 0) continue;
-        hpgv_ctx *mc = g->members[(size_t)k];
-        GroupMember &M = P.S->m[(size_t)k];
-        if (!d_gt[k]) return drain(P, fail(g, HPGV_ERR_INVALID, "member %d has %lld variants but no matrix", k, (long long)P.n[k]));
-        const int n = (int)P.n[k];
-        int32_t *c = (int32_t *)piece_src(P, k, pieces[0], 0);
-        double *o = (double *)piece_src(P, k, pieces[1], 16);
-        double *x = chisq ? (double *)piece_src(P, k, pieces[2], 24) : nullptr;
-        double *p = (double *)piece_src(P, k, pieces[3], 32);
-        rc = hpgv_assoc_scan_dev(mc, d_gt[k], n, d_is_x ? d_is_x[k] : nullptr, c, M.scan);
-        if (!rc) rc = chisq ? hpgv_assoc_chisq_dev(mc, c, n, o, x, p, M.scan) : hpgv_assoc_fisher_dev(mc, c, n, o, p, M.scan);
-        if (rc) return drain(P, rc);
-    }
-    rc = exchange(P, pieces);
-    return rc ? drain(P, rc) : HPGV_OK;
+    const auto member = [&](int k, hpgv_ctx *mc, hipStream_t st, const uint8_t *gt, int n, void *const *at) {
+        int32_t *c = (int32_t *)at[0];
+        double *o = (double *)at[1], *x = (double *)at[2], *p = (double *)at[3];
+        const int rc = hpgv_assoc_scan_dev(mc, gt, n, d_is_x ? d_is_x[k] : nullptr, c, st);
+        return rc ? rc : chisq ? hpgv_assoc_chisq_dev(mc, c, n, o, x, p, st) : hpgv_assoc_fisher_dev(mc, c, n, o, p, st);
+    };
+    return group_scan(g, d_gt, V, pieces, member, no_step, no_step);
     HPGV_ABI_CATCH(g)
 }
 
@@ -435,26 +527,12 @@ int hpgv_group_tdt(hpgv_ctx *g, const uint8_t *const *d_gt, const uint8_t *const
     if (!is_group(g)) return fail(g, HPGV_ERR_INVALID, "hpgv_group_tdt needs a group context (hpgv_create_multi)");
     if (!d_gt || (V > 0 && (!d_tu || !d_odds || !d_chisq || !d_p))) return fail(g, HPGV_ERR_INVALID, "bad group tdt arguments");
     const std::vector<Piece> pieces = {{8, d_tu}, {8, d_odds}, {8, d_chisq}, {8, d_p}};
-    int rc = hpgv_group_comm_init(g);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(g->grp->mu);
-    Plan P;
-    rc = plan_call(g, V, 32, P);
-    if (rc) return rc;
-    for (int k = 0; k < P.G; ++k) {
-        if (P.n[k] == 0) continue;
-        hpgv_ctx *mc = g->members[(size_t)k];
-        GroupMember &M = P.S->m[(size_t)k];
-        if (!d_gt[k]) return drain(P, fail(g, HPGV_ERR_INVALID, "member %d has %lld variants but no matrix", k, (long long)P.n[k]));
-        const int n = (int)P.n[k];
-        int32_t *tu = (int32_t *)piece_src(P, k, pieces[0], 0);
-        rc = hpgv_tdt_scan_dev(mc, d_gt[k], n, d_is_x ? d_is_x[k] : nullptr, tu, M.scan);
-        if (!rc) rc = hpgv_tdt_stats_dev(mc, tu, n, (double *)piece_src(P, k, pieces[1], 8), (double *)piece_src(P, k, pieces[2], 16),
-                                         (double *)piece_src(P, k, pieces[3], 24), M.scan);
-        if (rc) return drain(P, rc);
-    }
-    rc = exchange(P, pieces);
-    return rc ? drain(P, rc) : HPGV_OK;
+    const auto member = [&](int k, hpgv_ctx *mc, hipStream_t st, const uint8_t *gt, int n, void *const *at) {
+        int32_t *tu = (int32_t *)at[0];
+        const int rc = hpgv_tdt_scan_dev(mc, gt, n, d_is_x ? d_is_x[k] : nullptr, tu, st);
+        return rc ? rc : hpgv_tdt_stats_dev(mc, tu, n, (double *)at[1], (double *)at[2], (double *)at[3], st);
+    };
+    return group_scan(g, d_gt, V, pieces, member, no_step, no_step);
     HPGV_ABI_CATCH(g)
 }
 
@@ -464,98 +542,20 @@ int hpgv_group_stats(hpgv_ctx *g, const uint8_t *const *d_gt, int64_t V, int32_t
     if (!is_group(g)) return fail(g, HPGV_ERR_INVALID, "hpgv_group_stats needs a group context (hpgv_create_multi)");
     if (!d_gt || (V > 0 && (!d_counts8 || !d_hwe_chi2 || !d_hwe_p))) return fail(g, HPGV_ERR_INVALID, "bad group stats arguments");
     const std::vector<Piece> pieces = {{32, d_counts8}, {8, d_hwe_chi2}, {8, d_hwe_p}};
-    int rc = hpgv_group_comm_init(g);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(g->grp->mu);
-    Plan P;
-    rc = plan_call(g, V, 48, P);
-    if (rc) return rc;
-    GroupState *S = P.S;
     const int n_samples = g->members[0]->stats.n_samples;
-    // everything queued from here on is one unit: any failure inside it drains the members' streams before it returns
-    const auto queued = [&]() -> int {
-    if (d_sample_missing && !g->members[0]->stats.set) return drain(P, fail(g, HPGV_ERR_STATE, "hpgv_set_stats_cohort has not been called"));
-    if (d_sample_missing && n_samples > 0) {
-        // the counter array is the one destination every member ADDS into: the previous call's adds and its ncclReduce (the
-        // OTHER generation's transfers) may still be running when this call's memset is queued.  plan_call made member 0's
-        // scan wait for this generation only; with counters, it also waits for the other one.
-        GroupMember &M0 = S->m[0];
-        DeviceGuard dg(g->members[0]->device);
-        const int other = P.gen ^ 1;
-        if (M0.xfer_pending[other]) {
-            const hipError_t e = hipStreamWaitEvent(M0.scan, M0.xfer_done[other], 0);
-            if (e != hipSuccess) return drain(P, fail(g, HPGV_ERR_HIP, "hipStreamWaitEvent: %s", hipGetErrorString(e)));
-        }
-    }
-    for (int k = 0; k < P.G; ++k) {
-        hpgv_ctx *mc = g->members[(size_t)k];
-        GroupMember &M = S->m[(size_t)k];
-        DeviceGuard dg(mc->device);
-        int32_t *miss = nullptr;
-        if (d_sample_missing && n_samples > 0) {
-            // member 0 counts straight into the caller's array, everyone else into a counter array of its own
-            if (k == 0) miss = d_sample_missing;
-            else {
-                HIPCHK(mc, M.miss[P.gen].reserve((size_t)n_samples * sizeof(int32_t)));
-                miss = M.miss[P.gen].as<int32_t>();
-            }
-            HIPCHK(mc, hipMemsetAsync(miss, 0, (size_t)n_samples * sizeof(int32_t), M.scan));
-        }
-        if (P.n[k] == 0) continue;
-        if (!d_gt[k]) return drain(P, fail(g, HPGV_ERR_INVALID, "member %d has %lld variants but no matrix", k, (long long)P.n[k]));
-        const int n = (int)P.n[k];
-        int32_t *c8 = (int32_t *)piece_src(P, k, pieces[0], 0);
-        rc = hpgv_stats_scan_dev(mc, d_gt[k], n, c8, M.scan);
-        if (!rc) rc = hpgv_stats_hwe_dev(mc, c8, n, (double *)piece_src(P, k, pieces[1], 32), (double *)piece_src(P, k, pieces[2], 40), M.scan);
-        if (!rc && miss) {
-            // k_sample_missing takes at most 65535 bands of rows per launch
-            const int step = 65535 * hpgv::SAMPLE_STATS_ROWS;
-            const size_t pitch = mc->stats.pitch;
-            for (int v0 = 0; v0 < n && !rc; v0 += step)
-                rc = hpgv_sample_missing_dev(mc, d_gt[k] + (size_t)v0 * pitch, std::min(step, n - v0), miss, M.scan);
-        }
-        if (rc) return drain(P, rc);
-    }
-    rc = exchange(P, pieces);
-    if (rc) return drain(P, rc);
-    if (!d_sample_missing || n_samples <= 0) return HPGV_OK;
-    // the per-sample counters: a context on member 0's device adds its own on ITS transfer stream (which the next call of
-    // this generation waits for before it overwrites them), then one ncclReduce (sum, in place on member 0) over the
-    // communicator's ranks on member 0's transfer stream, behind those adds and member 0's own scan.
-    GroupMember &M0 = S->m[0];
-    {
-        DeviceGuard dg(g->members[0]->device);
-        HIPCHK(g, hipStreamWaitEvent(M0.xfer, M0.scan_done[P.gen], 0));
-        for (int k = 1; k < P.G; ++k) {
-            GroupMember &M = S->m[(size_t)k];
-            if (!M.local) continue;
-            HIPCHK(g, hipStreamWaitEvent(M.xfer, M0.scan_done[P.gen], 0));      // member 0's memset of the counters is behind this event
-            hipLaunchKernelGGL(k_add_i32, dim3((unsigned)((n_samples + 255) / 256)), dim3(256), 0, M.xfer, d_sample_missing,
-                               M.miss[P.gen].as<int32_t>(), n_samples);
-            HIPCHK(g, hipGetLastError());
-            HIPCHK(g, hipEventRecord(M.xfer_done[P.gen], M.xfer));
-            HIPCHK(g, hipStreamWaitEvent(M0.xfer, M.xfer_done[P.gen], 0));
-        }
-    }
-    NCCLCHK(g, S, S->GroupStart());
-    NCCLCHK(g, S, S->Reduce(d_sample_missing, d_sample_missing, (size_t)n_samples, ncclInt32, ncclSum, 0, S->comms[0], M0.xfer));
-    for (int k = 1; k < P.G; ++k) {
-        GroupMember &M = S->m[(size_t)k];
-        if (M.local) continue;
-        NCCLCHK(g, S, S->Reduce(M.miss[P.gen].as<int32_t>(), M.miss[P.gen].as<int32_t>(), (size_t)n_samples, ncclInt32, ncclSum, 0, S->comms[(size_t)M.rank], M.xfer));
-    }
-    NCCLCHK(g, S, S->GroupEnd());
-    for (int k = 0; k < P.G; ++k) {
-        hpgv_ctx *mc = g->members[(size_t)k];
-        GroupMember &M = S->m[(size_t)k];
-        DeviceGuard dg(mc->device);
-        HIPCHK(mc, hipEventRecord(M.xfer_done[P.gen], M.xfer));
-        M.xfer_pending[P.gen] = true;
-    }
-    return HPGV_OK;
+    std::vector<int32_t *> miss(g->members.size(), nullptr);          // where every member counts missing genotypes per sample, if asked for
+    const auto member = [&](int k, hpgv_ctx *mc, hipStream_t st, const uint8_t *gt, int n, void *const *at) {
+        int32_t *c8 = (int32_t *)at[0];
+        int rc = hpgv_stats_scan_dev(mc, gt, n, c8, st);
+        if (!rc) rc = hpgv_stats_hwe_dev(mc, c8, n, (double *)at[1], (double *)at[2], st);
+        // k_sample_missing takes at most 65535 bands of rows per launch
+        const int step = 65535 * hpgv::SAMPLE_STATS_ROWS;
+        for (int v0 = 0; v0 < n && !rc && miss[(size_t)k]; v0 += step)
+            rc = hpgv_sample_missing_dev(mc, gt + (size_t)v0 * mc->stats.pitch, std::min(step, n - v0), miss[(size_t)k], st);
+        return rc;
     };
-    rc = queued();
-    return rc ? drain(P, rc) : HPGV_OK;
+    return group_scan(g, d_gt, V, pieces, member, [&](Plan &P) { return counters_begin(P, d_sample_missing, n_samples, miss); },
+                      [&](Plan &P) { return counters_reduce(P, d_sample_missing, n_samples); });
     HPGV_ABI_CATCH(g)
 }
 
@@ -565,9 +565,9 @@ int hpgv_group_stats(hpgv_ctx *g, const uint8_t *const *d_gt, int64_t V, int32_t
 //      singlenode/epistasis_runner.c:114-145).  Every combination of `order` SNPs belongs to its FIRST SNP; the first SNPs are
 //      cut into G runs of (nearly) equal numbers of combinations -- for pairs at multiples of 64 rows, the tile scan's unit --
 //      member g ranks its run on its own device (hpgv_epi_{pairs,triples,order}_models, one host thread per member), and the
-//      ONE exchange is the gather of the members' per-fold top lists (num_folds x max_ranking_size records of 64 bytes) onto
-//      member 0 over the group's communicator, where they merge into the whole ranking: a model is in the whole top N only if
-//      it is in the top N of its own share.
+//      ONE exchange is the hand-over of the members' per-fold top lists (num_folds x max_ranking_size records of 64 bytes)
+//      onto member 0, where they merge into the whole ranking: a model is in the whole top N only if it is in the top N of its
+//      own share.
 
 namespace {
 
@@ -588,6 +588,34 @@ int epi_cut(int V, int order, int G, int k, int unit) {
         if (epi_combs_before(V, order, std::min(mid * unit, V)) >= target) hi = mid; else lo = mid + 1;
     }
     return std::min(lo * unit, V);
+}
+
+// The gather of a ranking: the members' lists (`bytes` each, on the host) onto member 0's device and back to the host in
+// member order.  To the hand-over this is a scan of G "variants" of `bytes` bytes: member k's shard is [k, k + 1), its one
+// piece is its list, uploaded where a scan would have produced it -- on the transfer stream, behind whatever still reads
+// this generation's scratch.
+int gather_lists(hpgv_ctx *g, const std::vector<std::vector<EpiModel>> &lists, size_t bytes, std::vector<EpiModel> &all) {
+    GroupState *S = g->grp;
+    const int G = (int)g->members.size();
+    { DeviceGuard dg(g->members[0]->device); HIPCHK(g, S->lists.reserve(bytes * (size_t)G)); }
+    const std::vector<Piece> pieces = {{bytes, S->lists.p}};
+    Plan P;
+    int rc = plan_call(g, G, pieces, P);
+    if (rc) return rc;
+    for (int k = 0; k < G && !rc; ++k) {
+        DeviceGuard dg(g->members[(size_t)k]->device);
+        const hipError_t e = hipMemcpyAsync(piece_at(P, pieces, k, 0), lists[(size_t)k].data(), bytes, hipMemcpyHostToDevice, S->m[(size_t)k].xfer);
+        if (e != hipSuccess) rc = fail(g, HPGV_ERR_HIP, "upload of member %d's top lists: %s", k, hipGetErrorString(e));
+    }
+    if (!rc) rc = hand_over(P, piece_transfers(P, pieces));
+    if (!rc) {
+        const hipError_t e = quiesce(g, S);
+        if (e != hipSuccess) rc = fail(g, HPGV_ERR_HIP, "the gather of the top lists: %s", hipGetErrorString(e));
+    }
+    if (rc) return drain(P, rc);
+    DeviceGuard dg(g->members[0]->device);
+    HIPCHK(g, hipMemcpy(all.data(), S->lists.p, bytes * (size_t)G, hipMemcpyDeviceToHost));
+    return HPGV_OK;
 }
 
 }  // namespace
@@ -622,7 +650,7 @@ int hpgv_group_epi_rank(hpgv_ctx *g, int order, int subset, int max_ranking_size
     for (int k = 1; k < G; ++k)
         if (!g->members[(size_t)k]->epi.have_folds || g->members[(size_t)k]->epi.V != g->members[0]->epi.V || g->members[(size_t)k]->epi.num_folds != nf)
             return fail(g, HPGV_ERR_STATE, "member %d does not hold the dataset and folds of member 0: set them through the group context", k);
-    const size_t n_rec = (size_t)nf * (size_t)N, bytes = n_rec * sizeof(EpiModel);
+    const size_t n_rec = (size_t)nf * (size_t)N;
     // ---- every member ranks its share on a host thread of its own ----
     std::vector<std::vector<EpiModel>> lists((size_t)G);
     std::vector<int> rcs((size_t)G, HPGV_OK);
@@ -646,57 +674,22 @@ int hpgv_group_epi_rank(hpgv_ctx *g, int order, int subset, int max_ranking_size
     }
     for (int k = 0; k < G; ++k)
         if (rcs[(size_t)k]) return fail(g, rcs[(size_t)k], "member %d: %s", k, hpgv_last_error(g->members[(size_t)k]));
-    // ---- the exchange: every member's lists onto member 0 (through the communicator from another device -- and from member 0
-    //      itself with the test switch group_self_exchange --, a device-local copy from a context on member 0's device) ----
-    struct Bufs { std::vector<void *> p; std::vector<int> dev; ~Bufs() { for (size_t i = 0; i < p.size(); ++i) if (p[i]) { DeviceGuard dg(dev[i]); (void)hipFree(p[i]); } } } bufs;
-    auto dev_alloc = [&](int dev, size_t n, void **out) -> hipError_t { DeviceGuard dg(dev); hipError_t e = hipMalloc(out, n); if (e == hipSuccess) { bufs.p.push_back(*out); bufs.dev.push_back(dev); } return e; };
-    const int dev0 = g->members[0]->device;
-    void *d_all = nullptr;                                            // member 0's device: G lists in member order
-    HIPCHK(g, dev_alloc(dev0, bytes * (size_t)G, &d_all));
-    std::vector<void *> d_send((size_t)G, nullptr);
-    auto by_rccl = [&](int k) { return (k > 0 || g->group_self_exchange) && (!S->m[(size_t)k].local || k == 0); };
-    for (int k = 0; k < G; ++k) {
-        hpgv_ctx *mc = g->members[(size_t)k];
-        GroupMember &M = S->m[(size_t)k];
-        DeviceGuard dg(mc->device);
-        if (k == 0 && !g->group_self_exchange) { HIPCHK(g, hipMemcpyAsync(d_all, lists[0].data(), bytes, hipMemcpyHostToDevice, M.xfer)); continue; }
-        HIPCHK(g, dev_alloc(mc->device, bytes, &d_send[(size_t)k]));
-        HIPCHK(g, hipMemcpyAsync(d_send[(size_t)k], lists[(size_t)k].data(), bytes, hipMemcpyHostToDevice, M.xfer));
-        if (!by_rccl(k)) HIPCHK(g, hipMemcpyAsync((char *)d_all + bytes * (size_t)k, d_send[(size_t)k], bytes, hipMemcpyDeviceToDevice, M.xfer));
-    }
-    bool any = false;
-    for (int k = 0; k < G; ++k) any = any || by_rccl(k);
-    if (any) {
-        GroupMember &M0 = S->m[0];
-        NCCLCHK(g, S, S->GroupStart());
-        for (int k = 0; k < G; ++k) {
-            if (!by_rccl(k)) continue;
-            GroupMember &M = S->m[(size_t)k];
-            NCCLCHK(g, S, S->Send(d_send[(size_t)k], bytes, ncclInt8, 0, S->comms[(size_t)M.rank], M.xfer));
-            NCCLCHK(g, S, S->Recv((char *)d_all + bytes * (size_t)k, bytes, ncclInt8, M.rank, S->comms[0], M0.xfer));
-        }
-        NCCLCHK(g, S, S->GroupEnd());
-    }
-    for (int k = 0; k < G; ++k) { DeviceGuard dg(g->members[(size_t)k]->device); HIPCHK(g, hipStreamSynchronize(S->m[(size_t)k].xfer)); }
     std::vector<EpiModel> all(n_rec * (size_t)G);
-    { DeviceGuard dg(dev0); HIPCHK(g, hipMemcpy(all.data(), d_all, bytes * (size_t)G, hipMemcpyDeviceToHost)); }
+    rc = gather_lists(g, lists, n_rec * sizeof(EpiModel), all);
+    if (rc) return rc;
     // ---- merge: per fold the best N of the members' lists (add_to_model_ranking, model.c:478-517: higher accuracy, then the
     //      smaller combination) ----
-    std::vector<EpiModel> t;
+    std::vector<EpiModel> merged(n_rec), t;
     for (int f = 0; f < nf; ++f) {
         t.clear();
         for (int k = 0; k < G; ++k)
             for (int e = 0; e < N; ++e) { const EpiModel &R = all[(size_t)k * n_rec + (size_t)f * (size_t)N + (size_t)e]; if (R.used) t.push_back(R); }
         std::sort(t.begin(), t.end(), epi_better<EpiModel>);
         if ((int)t.size() > N) t.resize((size_t)N);
-        n_ranked[f] = (int32_t)t.size();
-        for (size_t e = 0; e < t.size(); ++e) {
-            const size_t o = (size_t)f * (size_t)N + e;
-            for (int s2 = 0; s2 < order; ++s2) combs_out[o * (size_t)order + (size_t)s2] = t[e].c[s2];
-            accuracy[o] = t[e].accuracy;
-            for (int w = 0; w < 8; ++w) risky_mask[o * 8 + (size_t)w] = t[e].risky[w];
-        }
+        std::copy(t.begin(), t.end(), merged.begin() + (size_t)f * (size_t)N);
     }
+    int32_t *const comb[5] = {combs_out, combs_out + 1, combs_out + 2, combs_out + 3, combs_out + 4};
+    epi_scatter(merged, N, order, comb, (size_t)order, accuracy, risky_mask, hpgv::EPI_MASK_WORDS, n_ranked);
     if (scan_ms) { float m = 0.f; for (float x : ms) m = std::max(m, x); *scan_ms = m; }       // the members scan side by side: the slowest one
     return HPGV_OK;
     HPGV_ABI_CATCH(g)

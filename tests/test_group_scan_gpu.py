@@ -132,6 +132,121 @@ def test_group_scan_against_the_oracle():
     g.close()
 
 
+class _AssocCohort:
+    """61 samples x 301 variants on a group: every member's shard made on its device, and the oracle's result of the whole."""
+    N, V = 61, 301
+    cond = (np.arange(N) % 2).astype(np.uint8)
+    _oracle = None
+
+    @classmethod
+    def oracle(cls, v=V):
+        if cls._oracle is None:
+            cls._oracle = orc.assoc_counts(orc.synth_matrix(0, cls.V, cls.N, cls.N), cls.cond)
+        return tuple(a[:v] for a in cls._oracle)            # variant v's row does not depend on how many follow it
+
+    def __init__(self, devices, self_exchange, v=V):
+        self.v = v
+        self.g = hpgv.Engine(devices)
+        if self_exchange:
+            self.g.set_option("group_self_exchange", 1)
+        _, _, pitch = self.g.set_cohort(self.cond)
+        assert self.g.group_comm_init() == 1
+        self.mems, self.shards, self.n = [], [], []
+        for k in range(len(devices)):
+            lo, hi = self.g.group_shard(v, k)
+            m = self.g.member(k)
+            p = m.alloc(max(hi - lo, 1) * pitch)
+            m.synth(hpgv.LAYOUT_ASSOC, lo, hi - lo, p)
+            m.sync()
+            self.mems.append(m)
+            self.shards.append(p)
+            self.n.append(hi - lo)
+
+    def result_set(self):
+        m0, v = self.mems[0], max(self.v, 1)
+        return m0.alloc(16 * v), m0.alloc(8 * v), m0.alloc(8 * v), m0.alloc(8 * v)
+
+    def assoc(self, out, shards=None):
+        self.g.group_assoc(hpgv.TASK_CHISQ, self.shards if shards is None else shards, self.v, *out)
+
+    def check(self, out):
+        """counts exactly the oracle's; odds, chi-square and p within TOL"""
+        m0, v = self.mems[0], self.v
+        A1, A2, U1, U2 = self.oracle(v)
+        assert np.array_equal(m0.d2h(out[0], (v, 4), np.int32), np.stack([A1, A2, U1, U2], 1))
+        for d, exp in zip(out[1:], orc.assoc_stats(orc.TASK_CHISQ, A1, A2, U1, U2)):
+            got = m0.d2h(d, (v,), np.float64)
+            with np.errstate(invalid="ignore"):
+                assert np.all((np.abs(got - exp) <= TOL * np.maximum(1, np.abs(exp))) | (np.isnan(got) & np.isnan(exp)))
+
+    def close(self):
+        for m in self.mems:
+            m.close()
+        self.g.close()
+
+
+@pytest.mark.parametrize("self_exchange", [0, 1])
+def test_a_refused_group_call_leaves_the_group_usable(self_exchange):
+    """Argument errors the library returns -- after member 0's kernels are queued (the drain path) and before anything is --
+    and then two correct calls back to back into two result sets: both equal the oracle."""
+    c = _AssocCohort([0, 0, 0], self_exchange)
+    a, b = c.result_set(), c.result_set()
+    with pytest.raises(hpgv.HpgvError, match=r"member 1 .*no matrix"):
+        c.assoc(a, [c.shards[0], None, c.shards[2]])
+    with pytest.raises(hpgv.HpgvError, match=r"member 0 .*no matrix"):
+        c.assoc(a, [None, c.shards[1], c.shards[2]])
+    c.assoc(a)
+    c.assoc(b)
+    c.g.group_sync()
+    c.check(a)
+    c.check(b)
+    c.close()
+    # 3 variants over 4 members: the member whose shard is empty needs no matrix
+    c = _AssocCohort([0, 0, 0, 0], self_exchange, v=3)
+    empty = [k for k, n in enumerate(c.n) if n == 0]
+    assert len(empty) == 1
+    a = c.result_set()
+    c.assoc(a, [None if k in empty else p for k, p in enumerate(c.shards)])
+    c.g.group_sync()
+    c.check(a)
+    c.close()
+
+
+@pytest.mark.parametrize("self_exchange", [0, 1])
+def test_a_group_ranking_between_unsynced_scans(self_exchange):
+    """assoc into A, assoc into B, a ranking, assoc into A again, with no hpgv_group_sync between: the ranking's gather shares the
+    members' streams and scratch with the scans' hand-over.  A and B equal the oracle, the ranking the dense evaluation."""
+    from helpers import epi_random_dataset, epi_random_folds
+    rng = np.random.default_rng(11)
+    v, nA, nU, k, n = 130, 90, 110, 3, 5
+    data = epi_random_dataset(rng, v, nA, nU)
+    fold = epi_random_folds(rng, nA, nU, k)
+    c = _AssocCohort([0, 0], self_exchange)
+    c.g.epi_set_dataset(data, nA, nU)
+    c.g.epi_set_folds(fold, k)
+    assert [c.g.group_epi_share(2, m) for m in range(2)] == [(0, 64), (64, v)]       # both members rank a share
+    a, b = c.result_set(), c.result_set()
+    c.assoc(a)
+    c.assoc(b)
+    res = c.g.group_epi_rank(2, hpgv.EPI_TESTING, n)
+    c.assoc(a)
+    c.g.group_sync()
+    c.check(a)
+    c.check(b)
+    one = hpgv.Engine(0)
+    one.epi_set_dataset(data, nA, nU)
+    one.epi_set_folds(fold, k)
+    acc, rm = one.epi_scan_pairs(hpgv.EPI_TESTING)
+    pairs = [(i, j) for i in range(v) for j in range(i + 1, v)]
+    for f in range(k):
+        s = np.where(np.isnan(acc[f]), -np.inf, acc[f])
+        order = sorted(range(len(pairs)), key=lambda p: (-s[p], pairs[p]))[:n]
+        assert [tuple(x) for x in res["combs"][f].tolist()] == [pairs[p] for p in order]
+        assert np.array_equal(res["accuracy"][f], acc[f][order]) and np.array_equal(res["risky"][f][:, 0], rm[f][order].astype(np.uint32))
+    one.close()
+    c.close()
+
+
 def test_group_calls_refuse_an_ordinary_context():
     e = hpgv.Engine(0)
     assert e.L.hpgv_group_comm_init(e.h) == 1                  # HPGV_ERR_INVALID
