@@ -30,6 +30,14 @@ COND_UNAFFECTED, COND_AFFECTED, COND_OTHER = 0, 1, 2
 SEX_MALE, SEX_FEMALE, SEX_UNKNOWN = 0, 1, 2
 LAYOUT_ASSOC, LAYOUT_TDT, LAYOUT_STATS, LAYOUT_STATS_GROUPS, LAYOUT_MENDEL, LAYOUT_EPI = 0, 1, 2, 3, 4, 5
 GT_MISSING = 0xFF
+# the tokenizer's tile records that hpgv_bgzf_verify_tiles_dev leaves (csrc/hpgv_text2_kernels.h: TOK2_TILE, struct TokAgg2 { TokAgg
+# h[2]; }, struct TokAgg { int nl, tabs, last_nl, pad; }, enum TOK_AGG_*): one 32-byte record per 2 KiB tile of the decoded text, two
+# 16-byte halves of four 32-bit words each, the flags in the last word (pad) of a half; "count this tile again" is OR-ed into h[0]'s.
+# test_tile_record_constants_match_the_kernels_header holds them to the header.
+TOK_TILE_BYTES = 2048
+TOK_TILE_RECORD_BYTES, TOK_TILE_HALF_WORDS = 32, 4
+TOK_AGG_NL, TOK_AGG_TABS, TOK_AGG_LAST_NL, TOK_AGG_PAD = 0, 1, 2, 3
+TOK_AGG_WRITTEN, TOK_AGG_COMPLEX = 1, 2
 
 # every symbol include/hpgv.h declares (checked by the CPU suite)
 SYMBOLS = [

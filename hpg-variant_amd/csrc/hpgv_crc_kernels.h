@@ -101,8 +101,9 @@ __device__ __forceinline__ void bgzf_block_agg(const char *__restrict__ text, si
         if (lane == 63) bgzf_tile_store(agg2, tile, true, a);
     }
 }
-// text of block b that the decoder did not write (status != 0: the host decodes it and patches the text): its tiles are counted
-// again by the tokenizer
+// text of block b that the decoder did not write (status != 0 on entry) or wrote wrong (its CRC-32 does not match: the block leaves
+// with BGZF_STATUS_BAD_CRC) -- the host decodes it and patches the text: every tile the block touches, up to agg_tiles, is counted
+// again by the tokenizer, whatever records this or another block has stored or will store for it
 __device__ __forceinline__ void bgzf_block_agg_void(size_t o, size_t len, TokAgg2 *__restrict__ agg2, long agg_tiles) {
     if (len == 0) return;
     const size_t t_lo = o / TOK2_TILE, t_hi = (o + len - 1) / TOK2_TILE;
@@ -273,11 +274,17 @@ static __global__ __launch_bounds__(256) void k_bgzf_crc(const uint8_t *__restri
         p += (size_t)steps << 8; L -= steps << 8;
     }
     s = crc_bytes(t0, s, p, L);
-    if (lane == 0 && ~s != stored) status[b] = BGZF_STATUS_BAD_CRC;
+    // the verdict is the wave's: crc_fold XORs the lanes' registers into every lane, crc_bytes runs alike on all of them, the
+    // trailer is read by all -- taken from the first lane all the same, so that the branch below is a scalar one
+    const bool bad = (uint32_t)__builtin_amdgcn_readfirstlane((int)~s) != (uint32_t)__builtin_amdgcn_readfirstlane((int)stored);
+    if (lane == 0 && bad) status[b] = BGZF_STATUS_BAD_CRC;
     if constexpr (AGG) if (fused && ng > g_a) {                  // the tiles behind the last one the loop completed
         const size_t from = T0 + ng;
         if (from <= t_hi) bgzf_tiles_clipped((const char *)text, o, end, from, t_hi, agg2, agg_tiles);
     }
+    // the records above are those of a text that is not the block's: the host decodes the block again and patches the text, and the
+    // tokenizer counts its tiles again (behind the block's last record store; the flag is only ever OR-ed in, so it stays)
+    if constexpr (AGG) if (bad) bgzf_block_agg_void(o, out_len[b], agg2, agg_tiles);
 }
 
 }  // namespace hpgv

@@ -440,7 +440,25 @@ static size_t stretch_rows(const source_t *s, const stager_t *S, size_t launched
     return S->rows_cap && rows > S->rows_cap ? S->rows_cap : rows;
 }
 /* Block i of slot q, the file's block b, when the device decoder is through with it: one it did not take (or, in tests,
- * every HPGV_TEST_GPU_INFLATE_REFUSE_EVERY-th block) is decoded by the host and its text patched in.  0 = the block is bad. */
+ * every HPGV_TEST_GPU_INFLATE_REFUSE_EVERY-th block) is decoded by the host and its text patched in.  0 = the block is bad.
+ * That hook patches the text the device counted; HPGV_TEST_GPU_INFLATE_DAMAGE_EVERY=n stands for a decoder that wrote WRONG
+ * bytes: behind the decoder's launch and in front of the CRC check's (damage_decoded, on the slot's stream) 32 bytes in the
+ * middle of every block b with b % n == 0 and 64 bytes of text or more are overwritten with newlines and TABs.  The CRC check
+ * then refuses the block, the host patches it here, and the tile records the check counted from the damaged text must not be
+ * used (hpgv.h "hpgv_bgzf_verify_tiles_dev").  Both hooks number the blocks alike: from 0 in the file, or in the part. */
+#define NT4 '\n', '\t', '\n', '\t', '\n', '\t', '\n', '\t'
+static const char DAMAGE_PATTERN[32] = { NT4, NT4, NT4, NT4 };
+#undef NT4
+static int damage_decoded(source_t *s, const scan_slot_t *q, size_t first_block) {
+    const size_t every = (size_t)g_env.test_damage_every;
+    for (size_t i = 0; every && i < q->h.n; i++) {
+        if ((first_block + i) % every != 0 || q->h.out_len[i] < 64) continue;
+        /* (only queued; the pattern is static and never written, so it is "left alone" for as long as anyone may read it) */
+        if (hpgv_memcpy_h2d_async(CTX, (char *)s->d_text + q->h.out_off[i] + q->h.out_len[i] / 2 - sizeof DAMAGE_PATTERN / 2, DAMAGE_PATTERN,
+                                  sizeof DAMAGE_PATTERN, q->stream) != HPGV_OK) return 0;
+    }
+    return 1;
+}
 static int patch_if_refused(source_t *s, const scan_slot_t *q, size_t i, size_t b, int32_t status, unsigned char *tmp) {
     const size_t every = (size_t)g_env.test_refuse_every;
     if (!status && !(every && b % every == 0)) return 1;
@@ -537,6 +555,7 @@ static void *bgzf_stager(void *v) {
               || dev_text_grow(s->d_text, q->text_end + 16, &s->d_text_cap);
         ok = ok && hpgv_inflate_blocks_dev(CTX, (const uint8_t *)s->d_comp, q->d_in_off, q->d_in_len, q->d_out_off, q->d_out_len,
                                            (int)q->h.n, (uint8_t *)s->d_text, q->d_status, q->stream) == HPGV_OK;
+        ok = ok && damage_decoded(s, q, launched);                   /* (tests: a decoder that wrote wrong bytes) */
         if (g_env.bgzf_verify)                                       /* the blocks' CRC-32, on the device behind the decoder */
             ok = ok && hpgv_bgzf_verify_tiles_dev(CTX, (const uint8_t *)s->d_comp, q->d_in_off, q->d_in_len, q->d_out_off, q->d_out_len,
                                                   (int)q->h.n, (const uint8_t *)s->d_text, q->d_status, s->d_tiles, (uint64_t)s->n_tiles, q->stream) == HPGV_OK;

@@ -51,6 +51,7 @@ void host_env_read(void) {
     ENV_NUM("HPGV_UPLOAD_SEGMENT_MB", upload_segment_mb, 0, 1 << 20);
     ENV_NUM("HPGV_UPLOAD_INFLIGHT", upload_inflight, 0, 1 << 20);
     ENV_NUM("HPGV_TEST_GPU_INFLATE_REFUSE_EVERY", test_refuse_every, 0, 1L << 40);
+    ENV_NUM("HPGV_TEST_GPU_INFLATE_DAMAGE_EVERY", test_damage_every, 0, 1L << 40);
     ENV_NUM("HPGV_TEST_SCAN_ROWS", test_scan_rows, 0, 1L << 40);
     ENV_NUM("HPGV_TEST_TEXT_ESTIMATE_PERCENT", test_text_estimate_percent, 0, 1000);
     ENV_NUM("HPGV_BGZF_PART_MIN_KB", bgzf_part_min_kb, 0, 1L << 40);

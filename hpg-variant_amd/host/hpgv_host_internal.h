@@ -270,6 +270,7 @@ typedef struct {
     long upload_inflight;
     /* tests only */
     long test_refuse_every;          /* HPGV_TEST_GPU_INFLATE_REFUSE_EVERY: every n-th block handed back to the host decoder */
+    long test_damage_every;          /* HPGV_TEST_GPU_INFLATE_DAMAGE_EVERY: every n-th block's decoded text overwritten in its middle before the CRC check */
     long test_scan_rows;             /* HPGV_TEST_SCAN_ROWS: no stretch of the stager longer than this many blocks */
     long test_text_estimate_percent; /* HPGV_TEST_TEXT_ESTIMATE_PERCENT: the first commitment as a share of the estimate */
     long bgzf_part_min_kb;           /* HPGV_BGZF_PART_MIN_KB: smallest part of a file staged in parts (default 65536) */

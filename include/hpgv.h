@@ -643,7 +643,8 @@ int  hpgv_bgzf_verify_dev(hpgv_ctx *ctx, const uint8_t *d_comp, const uint64_t *
  * count, the TABs behind its last newline and where that newline is, which is all the tokenizer's first sweep computes.
  * d_tiles: hpgv_text_tiles_bytes(text bytes) bytes of device memory, ZEROED before the first call for a text; n_tiles: how
  * many records it may write (blocks whose text lies beyond are only checked).  Blocks the decoder refused (d_status != 0
- * on entry) mark their tiles "count again".  See hpgv_text_alias_tiles. */
+ * on entry) and blocks that leave with HPGV_BLOCK_BAD_CRC mark every tile they touch "count again": their text is the
+ * caller's to patch, and no record counted from the text that was there is used for it.  See hpgv_text_alias_tiles. */
 size_t hpgv_text_tiles_bytes(uint64_t text_bytes);
 int  hpgv_bgzf_verify_tiles_dev(hpgv_ctx *ctx, const uint8_t *d_comp, const uint64_t *d_in_off, const uint32_t *d_in_len,
                                 const uint64_t *d_out_off, const uint32_t *d_out_len, int n_blocks, const uint8_t *d_text,

@@ -509,7 +509,8 @@ void hpgv_host_adapter_times(double *seconds4, long *calls, int reset);
  * Diagnosis and tests (each switches one stage of the bgzip device path to its fall-back): HPGV_NO_DEVICE_WINDOWS,
  * HPGV_NO_LARGE_WINDOWS, HPGV_BGZF_HOST_TABLE, HPGV_SERIAL_BGZF_WALK, HPGV_NO_GROWING_TEXT, HPGV_NO_LOW_PRIORITY,
  * HPGV_NO_WRITER_THREAD, HPGV_UPLOAD_SEGMENT_MB, HPGV_UPLOAD_INFLIGHT, HPGV_TEST_GPU_INFLATE_REFUSE_EVERY,
- * HPGV_TEST_SCAN_ROWS (no stretch of the stager longer than this many blocks, whether its rows come from the device's scan
+ * HPGV_TEST_GPU_INFLATE_DAMAGE_EVERY (every n-th block's text is overwritten on the device between the decoder and the CRC
+ * check: the check must catch it and the host's patch put it right), HPGV_TEST_SCAN_ROWS (no stretch of the stager longer than this many blocks, whether its rows come from the device's scan
  * or from the host's table), HPGV_TEST_TEXT_ESTIMATE_PERCENT, HPGV_BGZF_PART_MIN_KB (host/hpgv_host_internal.h: host_env_t).
  * The engine underneath has its own short table: include/hpgv.h "Environment". */
 

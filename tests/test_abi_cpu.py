@@ -92,6 +92,22 @@ def test_status_codes_and_enums_match_header():
     assert "HPGV_SEX_MALE = 0" in text and hpgv.SEX_MALE == 0
 
 
+def test_tile_record_constants_match_the_kernels_header():
+    # the layout of the tokenizer's tile records that the package gives the tests, against csrc/hpgv_text2_kernels.h and hpgv.h
+    text = open(os.path.join(ROOT, "hpg-variant_amd", "csrc", "hpgv_text2_kernels.h")).read()
+    assert re.search(r"struct TokAgg \{ int nl, tabs, last_nl, pad; \};", text)
+    assert (hpgv.TOK_AGG_NL, hpgv.TOK_AGG_TABS, hpgv.TOK_AGG_LAST_NL, hpgv.TOK_AGG_PAD) == (0, 1, 2, 3) and hpgv.TOK_TILE_HALF_WORDS == 4
+    assert re.search(r"struct TokAgg2 \{ TokAgg h\[2\]; \};", text) and hpgv.TOK_TILE_RECORD_BYTES == 2 * 4 * hpgv.TOK_TILE_HALF_WORDS
+    m = re.search(r"enum \{ TOK_AGG_WRITTEN = (\d+), TOK_AGG_COMPLEX = (\d+) \};", text)
+    assert m and (int(m.group(1)), int(m.group(2))) == (hpgv.TOK_AGG_WRITTEN, hpgv.TOK_AGG_COMPLEX)
+    tb = int(re.search(r"constexpr int TOK2_TB = (\d+);", text).group(1))
+    threads = int(re.search(r"#define HPGV_TOK2_THREADS (\d+)", text).group(1))
+    assert re.search(r"constexpr int TOK2_TILE = TOK2_THREADS \* TOK2_TB;", text) and tb * threads == hpgv.TOK_TILE_BYTES
+    L = hpgv.load()
+    for n in (0, 1, 2048, 2049, 600_000):                           # one record per tile and one to spare
+        assert L.hpgv_text_tiles_bytes(n) == ((n + hpgv.TOK_TILE_BYTES - 1) // hpgv.TOK_TILE_BYTES + 1) * hpgv.TOK_TILE_RECORD_BYTES
+
+
 def test_format_f6_is_printf_percent_6f():
     # the writers' own "%6f" (hpgv_host_format_f6) against libc's snprintf, character for character: random doubles of every
     # magnitude, exact ties of the sixth decimal (j / 128 -> ...5 exactly), the fall-back range, denormals, signed zeros, NaN, inf

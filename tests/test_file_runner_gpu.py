@@ -494,6 +494,106 @@ def test_run_assoc_from_bgzf_decoded_on_the_gpu(host, tmp_path, capfd):
             assert rc != 0, (tag, env, n.value)
 
 
+def _damaged_decoder_inputs(tmp_path, seed):
+    """the smallest kind of file that is decoded on the device (256 blocks or more), long enough for three stretches of 300 blocks"""
+    from test_host_logic_cpu import _bgzf
+    rng = np.random.default_rng(seed)
+    people, names, rows = _write_inputs(tmp_path, rng, 50, 40, 1300)
+    vcf = _vcf_from_batch(tmp_path, names, rows)
+    data = open(vcf, "rb").read()
+    packed = str(tmp_path / "in.vcf.gz")
+    open(packed, "wb").write(_bgzf(data, 0x700))
+    n_blocks = -(-len(data) // 0x700)
+    assert 600 < n_blocks < 4096                                     # one launch unless the stretches are cut short
+    return vcf, packed, str(tmp_path / "ped.txt"), rows, n_blocks
+
+
+def test_run_assoc_when_the_device_decoder_writes_wrong_bytes(host, tmp_path, capfd):
+    # HPGV_TEST_GPU_INFLATE_DAMAGE_EVERY=3: every third block's decoded text is overwritten in its middle (32 bytes of newlines and
+    # TABs) between the device decoder and the CRC check -- a decoder that wrote wrong bytes.  The check refuses those blocks, the
+    # host decodes them again and patches the text, and the tile records the check had counted from the damaged text are not used:
+    # the same result file as from the plain text, by the device scan and by the host's table, in one stretch and in several, with
+    # the tile records and without them (the patch alone), and with other blocks refused by the decoder between the damaged ones
+    vcf, packed, ped, rows, n_blocks = _damaged_decoder_inputs(tmp_path, 18)
+    ped = ped.encode()
+
+    def run(path, tag, env):
+        os.environ.update(env)
+        try:
+            out = str(tmp_path / ("res_" + tag))
+            n = C.c_long(0)
+            rc = host.hpgv_run_assoc(path.encode(), ped, out.encode(), 1, 1 << 17, C.byref(n))
+            assert rc == 0 and n.value == len(rows), (tag, host.hpgv_host_last_error())
+            return open(out, "rb").read()
+        finally:
+            for k in env:
+                del os.environ[k]
+    plain = run(vcf, "plain", {})
+    assert plain.count(b"\n") == len(rows) + 1
+    damage = {"HPGV_TEST_GPU_INFLATE_DAMAGE_EVERY": "3", "HPGV_RUN_TRACE": "1"}
+    capfd.readouterr()
+    assert run(packed, "damaged", damage) == plain
+    err = capfd.readouterr().err
+    assert "blocks found" in err and "stage: walk" not in err        # (decoded on the device, the rows from the device's scan)
+    assert run(packed, "damaged_table", dict(damage, HPGV_BGZF_HOST_TABLE="1")) == plain
+    err = capfd.readouterr().err
+    assert "stage: walk" in err and "blocks found" not in err and "is up, to byte" in err
+    assert run(packed, "damaged_stretches", dict(damage, HPGV_TEST_SCAN_ROWS="300")) == plain
+    assert capfd.readouterr().err.count("blocks found") >= 3
+    assert run(packed, "damaged_table_stretches", dict(damage, HPGV_BGZF_HOST_TABLE="1", HPGV_TEST_SCAN_ROWS="300")) == plain
+    assert capfd.readouterr().err.count("is up, to byte") == -(-n_blocks // 300) >= 3
+    assert run(packed, "damaged_no_records", dict(damage, HPGV_DECODE_TILES="0")) == plain
+    assert run(packed, "damaged_and_refused", dict(damage, HPGV_TEST_GPU_INFLATE_REFUSE_EVERY="7")) == plain
+    assert run(packed, "damaged_and_refused_stretches", dict(damage, HPGV_TEST_GPU_INFLATE_REFUSE_EVERY="7", HPGV_TEST_SCAN_ROWS="300")) == plain
+    assert "blocks found" in capfd.readouterr().err
+
+
+_ASSOC_RUNNER = r"""
+import ctypes as C, sys, importlib
+sys.path.insert(0, %(root)r)
+b = importlib.import_module("hpg-variant_amd._build")
+L = C.CDLL(b.HOSTLIB)
+L.hpgv_run_assoc.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_size_t, C.POINTER(C.c_long)]
+L.hpgv_host_last_error.restype = C.c_char_p
+vcf, ped, out = [a.encode() for a in sys.argv[1:4]]
+n = C.c_long(0)
+rc = L.hpgv_run_assoc(vcf, ped, out, 1, 1 << 17, C.byref(n))
+print(rc, n.value, L.hpgv_host_device_count(), L.hpgv_host_last_error())
+L.hpgv_host_shutdown()
+"""
+
+
+def test_run_assoc_damaged_decoder_output_in_parts_and_unchecked(tmp_path):
+    # the same damage in processes of their own (the engine's devices are chosen once per process): with the file staged in parts,
+    # one per member of a group of two -- the blocks are numbered per part, each part's stager damages and patches its own -- the
+    # result file is the plain text's; and with the CRC check switched off (HPGV_BGZF_VERIFY=0) it is NOT: the hook really damages
+    # the text, and nothing but the check stands between that and the statistics
+    import sys
+    vcf, packed, ped, rows, n_blocks = _damaged_decoder_inputs(tmp_path, 19)
+    assert os.path.getsize(packed) >= 2 * (64 << 10)
+    script = tmp_path / "run.py"
+    script.write_text(_ASSOC_RUNNER % {"root": os.path.dirname(os.path.dirname(os.path.abspath(__file__)))})
+
+    def run(path, tag, more):
+        env = {k: v for k, v in os.environ.items() if k not in ("HPGV_DEVICES",)}
+        env.update(more)
+        out = str(tmp_path / ("res_" + tag))
+        r = subprocess.run([sys.executable, str(script), path, ped, out], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, (tag, r.returncode, r.stderr[-3000:])          # (the run may fail; the process may not)
+        rc, n, n_dev = [int(x) for x in r.stdout.split()[:3]]
+        return rc, n, n_dev, (open(out, "rb").read() if rc == 0 else None), r.stderr
+    rc, n, n_dev, plain, _ = run(vcf, "plain", {})
+    assert rc == 0 and n == len(rows) and n_dev == 1 and plain.count(b"\n") == len(rows) + 1
+    damage = {"HPGV_TEST_GPU_INFLATE_DAMAGE_EVERY": "3", "HPGV_RUN_TRACE": "1"}
+    rc, n, n_dev, res, err = run(packed, "parts", dict(damage, HPGV_DEVICES="0,0", HPGV_BGZF_PART_MIN_KB="64"))
+    assert rc == 0 and n == len(rows) and n_dev == 2, err[-3000:]
+    assert "stage: 2 parts, one per device" in err, err[-3000:]
+    assert res == plain
+    rc, n, n_dev, res, err = run(packed, "unchecked", dict(damage, HPGV_BGZF_VERIFY="0"))
+    assert "blocks found" in err                                     # (the device path, where the hook acts)
+    assert not (rc == 0 and res == plain)
+
+
 def test_run_assoc_bgzf_host_table_feeds_the_stager(host, tmp_path, capfd):
     # the block table walked on the host (HPGV_BGZF_HOST_TABLE=1) is a source of rows for the same stager that the device scan
     # feeds: blocks the device decoder refuses are patched in from it, and a table of 3 300 blocks cut into stretches of 300

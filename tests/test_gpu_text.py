@@ -564,10 +564,10 @@ def test_random_bytes_from_a_small_alphabet(eng):
             _check(eng, text, n_samples, strict, max_lines=max(1, text.count(b"\n") // 2))
 
 
-def test_bgzf_crc_check_on_the_gpu_against_zlib():
-    # hpgv_bgzf_verify_dev: CRC-32 of every decoded block against its BGZF trailer (ADVICE r02: a damaged stream can inflate to
-    # ISIZE bytes of the wrong text).  Lengths around every boundary of the kernel (the 0 - 3 bytes before the first aligned
-    # dword, whole 256-byte rows, the rest), text offsets of every alignment, blocks already refused by the decoder left alone
+def _crc_case():
+    """Blocks of random bytes for the CRC kernel.  Lengths around every boundary of the kernel (the 0 - 3 bytes before the first aligned
+    dword, whole 256-byte rows, the rest), text offsets of every alignment, some blocks with one flipped bit in the text, two that
+    arrive with a status the decoder left (not touched, not checked)."""
     import zlib
     rng = np.random.default_rng(5)
     lens = [0, 1, 2, 3, 4, 5, 7, 255, 256, 257, 258, 259, 260, 511, 512, 513, 1023, 1024, 4099, 65279, 65280, 65281, 65535, 65536]
@@ -601,19 +601,76 @@ def test_bgzf_crc_check_on_the_gpu_against_zlib():
     refused = [3, 30]                                                    # a status the decoder left: not touched, not checked
     status = np.zeros(n, np.int32)
     status[refused] = 4
-    e = hpgv.Engine(0)
-    d_comp, d_text = e.alloc(len(comp)), e.alloc(total)
-    d_io, d_il, d_oo, d_ol, d_st = e.alloc(8 * n), e.alloc(4 * n), e.alloc(8 * n), e.alloc(4 * n), e.alloc(4 * n)
-    for d, a in ((d_comp, np.frombuffer(bytes(comp), np.uint8)), (d_text, text), (d_io, in_off), (d_il, in_len), (d_oo, out_off),
-                 (d_ol, out_len), (d_st, status)):
-        e.h2d(d, a)
-    e.bgzf_verify(d_comp, d_io, d_il, d_oo, d_ol, n, d_text, d_st)
-    e.sync()
-    got = e.d2h(d_st, (n,), np.int32)
     exp = status.copy()
     exp[[k for k in wrong_text if k not in refused]] = 9                 # HPGV_BLOCK_BAD_CRC
+    return dict(n=n, lens=lens, comp=np.frombuffer(bytes(comp), np.uint8), text=text, total=total, in_off=in_off, in_len=in_len, out_off=out_off,
+                out_len=out_len, status=status, exp=exp, wrong_text=wrong_text, refused=refused)
+
+
+def _crc_upload(e, c, text_shift=0):
+    d_comp, d_text = e.alloc(len(c["comp"])), C.c_void_p(e.alloc(c["total"] + 16).value + text_shift)
+    n = c["n"]
+    d_io, d_il, d_oo, d_ol, d_st = e.alloc(8 * n), e.alloc(4 * n), e.alloc(8 * n), e.alloc(4 * n), e.alloc(4 * n)
+    for d, a in ((d_comp, c["comp"]), (d_text, c["text"]), (d_io, c["in_off"]), (d_il, c["in_len"]), (d_oo, c["out_off"]),
+                 (d_ol, c["out_len"]), (d_st, c["status"])):
+        e.h2d(d, a)
+    return d_comp, d_io, d_il, d_oo, d_ol, n, d_text, d_st
+
+
+def test_bgzf_crc_check_on_the_gpu_against_zlib():
+    # hpgv_bgzf_verify_dev: CRC-32 of every decoded block against its BGZF trailer (ADVICE r02: a damaged stream can inflate to
+    # ISIZE bytes of the wrong text).  Lengths around every boundary of the kernel (the 0 - 3 bytes before the first aligned
+    # dword, whole 256-byte rows, the rest), text offsets of every alignment, blocks already refused by the decoder left alone
+    c = _crc_case()
+    n, lens, exp = c["n"], c["lens"], c["exp"]
+    e = hpgv.Engine(0)
+    args = _crc_upload(e, c)
+    e.bgzf_verify(*args)
+    e.sync()
+    got = e.d2h(args[-1], (n,), np.int32)
     assert np.array_equal(got, exp), (np.nonzero(got != exp)[0], got[got != exp], [lens[k] for k in np.nonzero(got != exp)[0]])
     e.close()
+
+
+@pytest.mark.parametrize("text_shift", [0, 4], ids=["records_from_the_crc_loop", "records_from_their_own_sweep"])
+def test_bgzf_crc_check_with_tile_records_marks_the_tiles_of_wrong_blocks(text_shift):
+    """The same blocks through hpgv_bgzf_verify_tiles_dev, with zeroed tile records: the same statuses, and in the records "count this
+    tile again" (TOK_AGG_COMPLEX in h[0]'s flag word) for every tile that a block with a wrong CRC-32, or one the decoder had refused,
+    holds a byte of -- and for no tile that only blocks with the right CRC-32 touch, two of them at the most (a tile in which a
+    third block begins is counted again whatever the blocks are)."""
+    c = _crc_case()
+    n, lens, exp = c["n"], c["lens"], c["exp"]
+    TB = hpgv.TOK_TILE_BYTES
+    voided = sorted(set(c["wrong_text"]) | set(c["refused"]))
+    good = [k for k in range(n) if k not in voided]
+    # (the texts lie up to three bytes apart: where a tile's first byte falls into such a gap, two blocks BEGIN inside the tile and it is
+    # counted again as well -- the layout has no such tile among those the second assertion looks at)
+    covered = np.zeros(c["total"] + TB, bool)
+    for k in range(n):
+        covered[int(c["out_off"][k]): int(c["out_off"][k]) + lens[k]] = True
+    by_all = _tiles_touched(c["out_off"], c["out_len"], range(n))
+    assert all(covered[t * TB] for t, k in by_all.items() if k <= 2)
+    e = hpgv.Engine(0)
+    args = _crc_upload(e, c, text_shift)
+    tiles_bytes = int(e.L.hpgv_text_tiles_bytes(c["total"]))
+    n_tiles = tiles_bytes // hpgv.TOK_TILE_RECORD_BYTES - 1
+    d_tiles = e.alloc(tiles_bytes)
+    e.h2d(d_tiles, np.zeros(tiles_bytes, np.uint8))
+    e.bgzf_verify_tiles(*args, d_tiles, n_tiles)
+    e.sync()
+    got = e.d2h(args[-1], (n,), np.int32)
+    assert np.array_equal(got, exp), (np.nonzero(got != exp)[0], got[got != exp], [lens[k] for k in np.nonzero(got != exp)[0]])
+    words = e.d2h(d_tiles, (n_tiles + 1, 2, hpgv.TOK_TILE_HALF_WORDS), np.int32)
+    e.close()
+    must = _check_tile_flags(words[:, :, hpgv.TOK_AGG_PAD], n_tiles, c["out_off"], c["out_len"], voided, good)
+    assert len(must) > 40 and not words[n_tiles:].any()
+    # a tile whose only block is a good one: its record is written, and it is the record of that text
+    t = int(c["out_off"][21]) // TB + 3
+    assert by_all[t] == 1 and t not in must and lens[21] > 8 * TB
+    chunk = c["text"][t * TB: (t + 1) * TB].tobytes()
+    h0 = words[t, 0]
+    assert h0[hpgv.TOK_AGG_PAD] == hpgv.TOK_AGG_WRITTEN and h0[hpgv.TOK_AGG_NL] == chunk.count(b"\n")
+    assert h0[hpgv.TOK_AGG_LAST_NL] == chunk.rfind(b"\n") + 1 and h0[hpgv.TOK_AGG_TABS] == chunk[chunk.rfind(b"\n") + 1:].count(b"\t")
 
 
 def test_one_sweep_tokenizer_on_a_large_text_equals_two_sweeps():
@@ -688,6 +745,143 @@ def test_assoc_text_rows_kernel_on_random_widths():
         test_assoc_text_rows_kernel_equals_the_per_row_kernel(n_samples)
 
 
+class _DecodedText:
+    """A VCF text of about 600 KB cut into BGZF blocks (raw DEFLATE + trailer) of the sizes `block_bytes`, taken in turn, one block
+    of a type the device decoder refuses, and everything hpgv_inflate_blocks_dev / hpgv_bgzf_verify_tiles_dev need of it on the device
+    (text_shift: a text that does not begin on a 16-byte boundary -- the records then come from a sweep of their own, not out of the
+    CRC loop's loads).  n_tiles: how many of the tile records are valid (all of them, unless a test says otherwise)."""
+
+    def __init__(self, n_samples, block_bytes, text_shift):
+        import zlib
+        self.n_samples = n_samples
+        self.rng = rng = np.random.default_rng(n_samples)
+        fmts = ["GT", "GT:DP", "DP:GT", "GT"]
+        lines = [_line(rng, n_samples, fmts[i % 4], ["1", "X", "7"][i % 3], int(rng.integers(3, 300))) for i in range(max(40, 600_000 // (4 * n_samples + 60)))]
+        self.text = text = ("\n".join(lines) + "\n").encode()
+        raws, pos, k = [], 0, 0
+        while pos < len(text):
+            n = block_bytes[k % len(block_bytes)]; k += 1
+            raws.append(text[pos: pos + n]); pos += n
+        comps = []
+        for r in raws:
+            co = zlib.compressobj(6, zlib.DEFLATED, -15)
+            comps.append(co.compress(r) + co.flush() + zlib.crc32(r).to_bytes(4, "little") + len(r).to_bytes(4, "little"))      # payload + the BGZF trailer
+        self.raws = raws
+        self.refused = refused = len(raws) // 3
+        comps[refused] = bytes([comps[refused][0] | 0x06]) + comps[refused][1:]          # block type 3: the decoder refuses it
+        self.n = len(raws)
+        self.text_shift, self.comps, self.e = text_shift, comps, None
+        self.out_len = np.array([len(r) for r in raws], np.uint32)
+        self.out_off = np.concatenate([[0], np.cumsum(self.out_len[:-1], dtype=np.uint64)]).astype(np.uint64)
+        self.total = len(text)
+
+    def upload(self):
+        comps, n, total, out_len, out_off = self.comps, self.n, self.total, self.out_len, self.out_off
+        in_len = np.array([len(c) - 8 for c in comps], np.uint32)
+        in_off = np.concatenate([[0], np.cumsum([len(c) for c in comps[:-1]], dtype=np.uint64)]).astype(np.uint64)
+        cbytes = np.frombuffer(b"".join(comps) + b"\0" * 16, np.uint8)
+        self.e = e = hpgv.Engine(0)
+        self.d_comp, d_text_alloc = e.alloc(len(cbytes)), e.alloc(total + 64 + 16)
+        self.d_text = C.c_void_p(d_text_alloc.value + self.text_shift)
+        self.d_io, self.d_il, self.d_oo, self.d_ol, self.d_st = e.alloc(8 * n), e.alloc(4 * n), e.alloc(8 * n), e.alloc(4 * n), e.alloc(4 * n)
+        for d, a in ((self.d_comp, cbytes), (self.d_io, in_off), (self.d_il, in_len), (self.d_oo, out_off), (self.d_ol, out_len)):
+            e.h2d(d, a)
+        self.tiles_bytes = int(e.L.hpgv_text_tiles_bytes(total))
+        self.all_tiles = self.tiles_bytes // hpgv.TOK_TILE_RECORD_BYTES - 1
+        self.n_tiles = self.all_tiles
+        self.d_tiles = e.alloc(self.tiles_bytes)
+        e.h2d(self.d_tiles, np.zeros(self.tiles_bytes, np.uint8))
+        return self
+
+    def close(self):
+        if self.e:
+            self.e.close()
+
+    def inflate(self):
+        self.e.inflate_blocks(self.d_comp, self.d_io, self.d_il, self.d_oo, self.d_ol, self.n, self.d_text, self.d_st)
+
+    def verify(self):
+        self.e.bgzf_verify_tiles(self.d_comp, self.d_io, self.d_il, self.d_oo, self.d_ol, self.n, self.d_text, self.d_st, self.d_tiles, self.n_tiles)
+        self.e.sync()
+        return self.e.d2h(self.d_st, (self.n,), np.int32)
+
+    def patch(self, b):
+        """the host decodes block b and patches the text, as the file runner does"""
+        self.e.h2d(C.c_void_p(self.d_text.value + int(self.out_off[b])), np.frombuffer(self.raws[b], np.uint8))
+
+    def check_windows(self, more_picks=()):
+        """Windows of the text -- the whole of it, single lines, a dozen random line ranges -- tokenized with the tile records and
+        without them: the same matrix, chromosome flags, statuses, line and field offsets, bit for bit, and the oracle's."""
+        e, text, total, n_samples, rng = self.e, self.text, self.total, self.n_samples, self.rng
+        d_text, d_tiles, n_tiles = self.d_text, self.d_tiles, self.n_tiles
+        assert e.d2h(d_text, (total,), np.uint8).tobytes() == text
+        starts = [0] + [i + 1 for i, ch in enumerate(text) if ch == 10]
+        ends = starts[1:]
+        picks = [(0, len(ends) - 1), (1, len(ends) - 1), (0, 0), (len(ends) // 2, len(ends) // 2)]
+        picks += [tuple(sorted(int(x) for x in rng.integers(0, len(ends), 2))) for _ in range(12)]
+        picks += list(more_picks(starts, ends) if callable(more_picks) else more_picks)
+        max_lines = len(ends) + 2
+        pitch = (n_samples + 15) // 16 * 16
+        d_nl, d_lo, d_fo = e.alloc(16), e.alloc(8 * (max_lines + 2)), e.alloc(40 * max_lines + 16)
+        d_gt, d_x, d_stt = e.alloc(max_lines * pitch + 16), e.alloc(max_lines + 16), e.alloc(4 * max_lines + 16)
+        host_key = C.create_string_buffer(16)                            # the alias table is keyed by a host address: any will do
+        L = e.L
+        for first, last in picks:
+            a, b = starts[first], ends[last]
+            win = C.c_void_p(d_text.value + a)
+            out = {}
+            for mode in ("tiles", "plain"):
+                if mode == "tiles":
+                    assert L.hpgv_text_alias_tiles(e.h, host_key, win, d_text, d_tiles, n_tiles) == 0
+                else:
+                    assert L.hpgv_text_alias(e.h, host_key, None) == 0
+                for d, nb in ((d_gt, max_lines * pitch), (d_x, max_lines), (d_stt, 4 * max_lines), (d_fo, 40 * max_lines), (d_lo, 8 * (max_lines + 2))):
+                    e.h2d(d, np.full(nb, 0xA5, np.uint8))
+                e._chk(L.hpgv_tokenize_dev(e.h, win, b - a, n_samples, 1, max_lines, d_nl, d_lo, d_fo, d_gt, pitch, d_x, d_stt, None))
+                e.sync()
+                nl = int(e.d2h(d_nl, (1,), np.int32)[0])
+                out[mode] = dict(n=nl, gt=e.d2h(d_gt, (nl, pitch), np.uint8)[:, :n_samples], x=e.d2h(d_x, (nl,), np.uint8), st=e.d2h(d_stt, (nl,), np.int32),
+                                 lo=e.d2h(d_lo, (nl + 1,), np.uint64), fo=e.d2h(d_fo, (nl, 10), np.uint32))
+            assert L.hpgv_text_alias(e.h, host_key, None) == 0
+            assert out["tiles"]["n"] == out["plain"]["n"] == last - first + 1, (first, last)
+            for kk in ("gt", "x", "st", "lo", "fo"):
+                assert np.array_equal(out["tiles"][kk], out["plain"][kk]), (first, last, kk)
+            tok = orc.tokenize(text[a:b].decode(), n_samples, True)
+            assert np.array_equal(out["tiles"]["gt"], tok["gt"]) and np.array_equal(out["tiles"]["st"], tok["status"])
+            assert np.array_equal(out["tiles"]["x"], tok["is_x"])
+            assert out["tiles"]["lo"].tolist() == [s - a for s in starts[first: last + 2]]
+
+    def tile_flags(self):
+        """the flag words of the two halves of EVERY record of the buffer (the valid ones and those behind them), and the buffer"""
+        words = self.e.d2h(self.d_tiles, (self.tiles_bytes // hpgv.TOK_TILE_RECORD_BYTES, 2, hpgv.TOK_TILE_HALF_WORDS), np.int32)
+        return words[:, :, hpgv.TOK_AGG_PAD], words
+
+
+def _tiles_touched(out_off, out_len, blocks):
+    """the tiles of the absolute grid that hold a byte of one of `blocks`, with how many of them hold one"""
+    count = {}
+    for b in blocks:
+        o, ln = int(out_off[b]), int(out_len[b])
+        if ln:
+            for t in range(o // hpgv.TOK_TILE_BYTES, (o + ln - 1) // hpgv.TOK_TILE_BYTES + 1):
+                count[t] = count.get(t, 0) + 1
+    return count
+
+
+def _check_tile_flags(flags, n_tiles, out_off, out_len, voided, good):
+    """TOK_AGG_COMPLEX ("count this tile again") in h[0]'s flag word of every valid record whose tile a block of `voided` touches; in
+    no record whose tile only blocks of `good` touch, two of them at the most; and nothing at all written behind the valid records"""
+    must = _tiles_touched(out_off, out_len, voided)
+    by_good = _tiles_touched(out_off, out_len, good)
+    cplx = (flags[:, 0] & hpgv.TOK_AGG_COMPLEX) != 0
+    missing = [t for t in must if t < n_tiles and not cplx[t]]
+    assert not missing, missing[:10]
+    extra = [t for t, k in by_good.items() if t < n_tiles and t not in must and k <= 2 and cplx[t]]
+    assert not extra, extra[:10]
+    assert any(t < n_tiles and t not in must and k <= 2 for t, k in by_good.items())      # (the second assertion looked at something)
+    return must
+
+
 @pytest.mark.parametrize("n_samples,block_bytes,text_shift", [(200, [65280], 0), (2504, [65280], 0), (37, [65280, 1000, 500, 700, 3000, 65280, 10], 0),
                                                               (900, [4096, 65280, 2047, 2048, 2049], 0), (300, [65280, 5000], 4), (2504, [65280], 12)])
 def test_windows_of_decoded_text_tokenized_from_the_decoders_tile_records(n_samples, block_bytes, text_shift):
@@ -696,78 +890,162 @@ def test_windows_of_decoded_text_tokenized_from_the_decoders_tile_records(n_samp
     Same outputs, bit for bit, as the ordinary two-sweep call on the same window, and as the oracle: blocks of the size bgzip writes
     (seams inside tiles), blocks shorter than a tile (several seams in one tile: counted again), a block the decoder refused (its
     text patched afterwards: counted again)."""
-    import zlib
-    rng = np.random.default_rng(n_samples)
-    fmts = ["GT", "GT:DP", "DP:GT", "GT"]
-    lines = [_line(rng, n_samples, fmts[i % 4], ["1", "X", "7"][i % 3], int(rng.integers(3, 300))) for i in range(max(40, 600_000 // (4 * n_samples + 60)))]
-    text = ("\n".join(lines) + "\n").encode()
-    raws, pos, k = [], 0, 0
-    while pos < len(text):
-        n = block_bytes[k % len(block_bytes)]; k += 1
-        raws.append(text[pos: pos + n]); pos += n
-    comps = []
-    for r in raws:
-        co = zlib.compressobj(6, zlib.DEFLATED, -15)
-        comps.append(co.compress(r) + co.flush() + zlib.crc32(r).to_bytes(4, "little") + len(r).to_bytes(4, "little"))      # payload + the BGZF trailer
-    refused = len(raws) // 3
-    comps[refused] = bytes([comps[refused][0] | 0x06]) + comps[refused][1:]          # block type 3: the decoder refuses it
-    n = len(raws)
-    in_len = np.array([len(c) - 8 for c in comps], np.uint32); out_len = np.array([len(r) for r in raws], np.uint32)
-    in_off = np.concatenate([[0], np.cumsum([len(c) for c in comps[:-1]], dtype=np.uint64)]).astype(np.uint64)
-    out_off = np.concatenate([[0], np.cumsum(out_len[:-1], dtype=np.uint64)]).astype(np.uint64)
-    cbytes = np.frombuffer(b"".join(comps) + b"\0" * 16, np.uint8)
-    total = len(text)
-    e = hpgv.Engine(0)
-    # (text_shift: a text that does not begin on a 16-byte boundary -- the records then come from a sweep of their own, not out of
-    # the CRC loop's loads)
-    d_comp, d_text_alloc = e.alloc(len(cbytes)), e.alloc(total + 64 + 16)
-    d_text = C.c_void_p(d_text_alloc.value + text_shift)
-    d_io, d_il, d_oo, d_ol, d_st = e.alloc(8 * n), e.alloc(4 * n), e.alloc(8 * n), e.alloc(4 * n), e.alloc(4 * n)
-    for d, a in ((d_comp, cbytes), (d_io, in_off), (d_il, in_len), (d_oo, out_off), (d_ol, out_len)):
-        e.h2d(d, a)
-    tiles_bytes = int(e.L.hpgv_text_tiles_bytes(total))
-    n_tiles = tiles_bytes // 32 - 1
-    d_tiles = e.alloc(tiles_bytes)
-    e.h2d(d_tiles, np.zeros(tiles_bytes, np.uint8))
-    e.inflate_blocks(d_comp, d_io, d_il, d_oo, d_ol, n, d_text, d_st)
-    e.bgzf_verify_tiles(d_comp, d_io, d_il, d_oo, d_ol, n, d_text, d_st, d_tiles, n_tiles)
-    e.sync()
-    status = e.d2h(d_st, (n,), np.int32)
-    assert status[refused] != 0 and (np.delete(status, refused) == 0).all()
-    # the host decodes the refused block and patches the text, as the file runner does
-    e.h2d(C.c_void_p(d_text.value + int(out_off[refused])), np.frombuffer(raws[refused], np.uint8))
-    assert e.d2h(d_text, (total,), np.uint8).tobytes() == text
-    starts = [0] + [i + 1 for i, ch in enumerate(text) if ch == 10]
-    ends = starts[1:]
-    picks = [(0, len(ends) - 1), (1, len(ends) - 1), (0, 0), (len(ends) // 2, len(ends) // 2)]
-    picks += [tuple(sorted(int(x) for x in rng.integers(0, len(ends), 2))) for _ in range(12)]
-    max_lines = len(ends) + 2
-    pitch = (n_samples + 15) // 16 * 16
-    d_nl, d_lo, d_fo = e.alloc(16), e.alloc(8 * (max_lines + 2)), e.alloc(40 * max_lines + 16)
-    d_gt, d_x, d_stt = e.alloc(max_lines * pitch + 16), e.alloc(max_lines + 16), e.alloc(4 * max_lines + 16)
-    host_key = C.create_string_buffer(16)                            # the alias table is keyed by a host address: any will do
-    L = e.L
-    for first, last in picks:
-        a, b = starts[first], ends[last]
-        win = C.c_void_p(d_text.value + a)
-        out = {}
-        for mode in ("tiles", "plain"):
-            if mode == "tiles":
-                assert L.hpgv_text_alias_tiles(e.h, host_key, win, d_text, d_tiles, n_tiles) == 0
-            else:
-                assert L.hpgv_text_alias(e.h, host_key, None) == 0
-            for d, nb in ((d_gt, max_lines * pitch), (d_x, max_lines), (d_stt, 4 * max_lines), (d_fo, 40 * max_lines), (d_lo, 8 * (max_lines + 2))):
-                e.h2d(d, np.full(nb, 0xA5, np.uint8))
-            e._chk(L.hpgv_tokenize_dev(e.h, win, b - a, n_samples, 1, max_lines, d_nl, d_lo, d_fo, d_gt, pitch, d_x, d_stt, None))
-            e.sync()
-            nl = int(e.d2h(d_nl, (1,), np.int32)[0])
-            out[mode] = dict(n=nl, gt=e.d2h(d_gt, (nl, pitch), np.uint8)[:, :n_samples], x=e.d2h(d_x, (nl,), np.uint8), st=e.d2h(d_stt, (nl,), np.int32),
-                             lo=e.d2h(d_lo, (nl + 1,), np.uint64), fo=e.d2h(d_fo, (nl, 10), np.uint32))
-        assert L.hpgv_text_alias(e.h, host_key, None) == 0
-        assert out["tiles"]["n"] == out["plain"]["n"] == last - first + 1, (first, last)
-        for kk in ("gt", "x", "st", "lo", "fo"):
-            assert np.array_equal(out["tiles"][kk], out["plain"][kk]), (first, last, kk)
-        tok = orc.tokenize(text[a:b].decode(), n_samples, True)
-        assert np.array_equal(out["tiles"]["gt"], tok["gt"]) and np.array_equal(out["tiles"]["st"], tok["status"])
-        assert out["tiles"]["lo"].tolist() == [s - a for s in starts[first: last + 2]]
-    e.close()
+    S = _DecodedText(n_samples, block_bytes, text_shift)
+    try:
+        S.upload().inflate()
+        status = S.verify()
+        assert status[S.refused] != 0 and (np.delete(status, S.refused) == 0).all()
+        S.patch(S.refused)
+        S.check_windows()
+    finally:
+        S.close()
+
+
+# What a decoder that wrote wrong bytes may have done to a block's text, as (what is looked for in the TRUE text, the offset of the
+# byte to change inside the match, what it becomes, whether the last match is taken: a tile's record holds the TABs BEHIND its last
+# newline).  The tile records counted from the damaged text then see ...
+_DAMAGE = {
+    "newline_lost": (rb"\n", 0, lambda c: ord("x"), 0),                                 # ... one line fewer
+    "newline_more": (rb"[0-9][/|][0-9]", 1, lambda c: 10, 0),                           # ... one line more, another last newline
+    "tab_lost": (rb"\t", 0, lambda c: ord(" "), 1),                                     # ... the same lines, one TAB fewer
+    "digit": (rb"[01][/|][0-9]", 0, lambda c: c ^ 1, 0),                                # ... nothing different (0 <-> 1): the control
+}
+
+
+def _plan_damage(S):
+    """[(block, where, kind, text position)]: the blocks to damage, one byte each, so that every store path of k_bgzf_crc<true> has
+    counted damaged text -- found by searching the true text for the byte to change inside the part of the block that is meant."""
+    import re
+    TB = hpgv.TOK_TILE_BYTES
+    n, refused, text = S.n, S.refused, S.text
+    o_ = lambda b: int(S.out_off[b])
+    end_ = lambda b: int(S.out_off[b]) + int(S.out_len[b])
+
+    def part(b, where):                                              # the bytes [lo, hi) of block b that `where` names, or None
+        o, end = o_(b), end_(b)
+        t_lo, t_hi = o // TB, (end - 1) // TB
+        if where == "anywhere":
+            return o, end
+        if where == "first_tile":                                    # the block begins inside it: the block before owns h[0], this one h[1]
+            return (o, min(end, (t_lo + 1) * TB)) if o % TB and b > 0 else None
+        if where == "interior":                                      # tiles whole inside the block, two tiles away from its ends
+            return ((t_lo + 2) * TB, (t_hi - 1) * TB) if t_hi - t_lo >= 5 else None
+        if where == "last_tile":                                     # clipped, shared with the block behind
+            return (max(o, t_hi * TB), end) if end % TB and b < n - 1 and t_hi > t_lo else None
+        if where == "short_block":                                   # a block shorter than a tile
+            return (o, end) if end - o < TB else None
+        raise ValueError(where)
+    # (block, part, at most this many blocks damaged in such a part, the kind if it is given): the text's first and last block; the
+    # neighbours of the block the decoder refused, in the tile they share with it if they share one; then every part in turn, in the
+    # first blocks that have it; and the control
+    wanted = [(0, "anywhere", n, None), (n - 1, "anywhere", n, None), (refused - 1, "last_tile", n, None), (refused - 1, "anywhere", n, None),
+              (refused + 1, "first_tile", n, None), (refused + 1, "anywhere", n, None)]
+    for where in ("interior", "first_tile", "last_tile", "short_block"):
+        wanted += [(b, where, 2, None) for b in range(1, n - 1)]
+    wanted += [(b, "interior", 3, "digit") for b in range(1, n - 1)]
+    plan, taken, have = [], {refused}, {}
+    biting = [k for k in _DAMAGE if k != "digit"]
+    for b, where, at_most, kind in wanted:
+        lohi = part(b, where) if b not in taken and have.get(where, 0) < at_most else None
+        if lohi is None:
+            continue
+        # the kinds that change a count in turn, the first one that part of the text has a place for (a tile may hold no newline)
+        for kind in ([kind] if kind else biting[len(plan) % 3:] + biting[:len(plan) % 3] + ["digit"]):
+            pat, at, _, last = _DAMAGE[kind]
+            found = [m.start() for m in re.compile(pat).finditer(text, lohi[0], lohi[1])]
+            if found:
+                plan.append((b, where, kind, found[-1 if last else 0] + at))
+                taken.add(b)
+                have[where] = have.get(where, 0) + 1
+                break
+    return plan
+
+
+def _damage_and_verify(S, plan):
+    """inflate; the planned bytes overwritten on the device, as a decoder that wrote wrong bytes would have left them; verify"""
+    S.inflate()
+    S.e.sync()
+    for b, where, kind, pos in plan:
+        assert S.out_off[b] <= pos < int(S.out_off[b]) + int(S.out_len[b])
+        new = _DAMAGE[kind][2](S.text[pos])
+        assert new != S.text[pos]
+        S.e.h2d(C.c_void_p(S.d_text.value + pos), np.array([new], np.uint8))
+    return S.verify()
+
+
+_DAMAGE_SHAPES = [(200, [65280], 0), (2504, [65280], 0), (37, [65280, 1000, 500, 700, 3000, 65280, 10], 0), (300, [65280, 5000], 4), (2504, [65280], 12)]
+
+
+@pytest.mark.parametrize("n_samples,block_bytes,text_shift", _DAMAGE_SHAPES)
+def test_blocks_that_fail_their_crc_void_their_tile_records(n_samples, block_bytes, text_shift):
+    """A block whose text the device decoder got WRONG: hpgv_bgzf_verify_tiles_dev has counted the wrong text when it finds that the
+    CRC-32 does not match.  The block leaves with HPGV_BLOCK_BAD_CRC, the host patches its text -- and every tile it touches must be
+    marked "count again", or the tokenizer would walk the patched text with the newline and TAB counts of the damaged one.  One byte
+    of a block is changed between the decoder and the check: a newline lost, a newline too many, a TAB lost, a genotype digit (no
+    count changes: the control); in the block's first tile (begun by the block before), in tiles in its middle, in its last tile
+    (shared with the block behind), in blocks shorter than a tile, in the text's first and last block, next to the block the
+    decoder refused.  After the patch, windows tokenized with the records equal the ordinary call's and the oracle's, bit for bit.
+    Without the marks the first three kinds of damage give other line counts, line offsets or field offsets than the ordinary call.
+    (Not a test to run against a kernel without them: with records that see a line fewer than the text has, two lines get one
+    index, and the tokenizer's list of lines to parse again, sized by the line count, can be written past its end.)"""
+    S = _DecodedText(n_samples, block_bytes, text_shift)
+    try:
+        plan = _plan_damage(S)
+        wheres, kinds, blocks = {p[1] for p in plan}, {p[2] for p in plan}, [p[0] for p in plan]
+        assert kinds == set(_DAMAGE), plan                           # every kind of damage in every run
+        assert {"anywhere", "first_tile", "interior", "last_tile"} <= wheres, plan
+        assert ("short_block" in wheres) == (min(block_bytes) < hpgv.TOK_TILE_BYTES), plan
+        assert 0 in blocks and S.n - 1 in blocks and (S.refused - 1 in blocks or S.refused + 1 in blocks), plan
+        S.upload()
+        status = _damage_and_verify(S, plan)
+        exp = np.zeros(S.n, np.int32)
+        exp[blocks] = 9                                              # HPGV_BLOCK_BAD_CRC: exactly the damaged blocks
+        assert status[S.refused] not in (0, 9)                       # the decoder's own refusal stays
+        exp[S.refused] = status[S.refused]
+        assert np.array_equal(status, exp), (np.nonzero(status != exp)[0], plan)
+        good = [b for b in range(S.n) if b not in blocks and b != S.refused]
+        _check_tile_flags(S.tile_flags()[0], S.n_tiles, S.out_off, S.out_len, blocks + [S.refused], good)
+        for b in blocks + [S.refused]:
+            S.patch(b)
+        S.check_windows()
+    finally:
+        S.close()
+
+
+def test_blocks_that_fail_their_crc_beyond_the_valid_tile_records():
+    """... with fewer valid records than the text has tiles: the last valid record lies in the middle of a damaged block, other damaged
+    blocks lie wholly behind it.  Nothing is written behind the valid records, and windows on either side of the limit, and across
+    it, give the ordinary call's results."""
+    S = _DecodedText(200, [65280], 0)
+    TB = hpgv.TOK_TILE_BYTES
+    try:
+        plan = [p for p in _plan_damage(S) if p[0] > S.refused + 1]      # (the blocks in front stay good: their records are looked at)
+        cut = min(plan)                                              # the first damaged block, damaged in its first tile
+        assert cut[1] == "first_tile" and len(plan) >= 4
+        n_tiles = (int(S.out_off[cut[0]]) + int(S.out_len[cut[0]]) // 2) // TB
+        blocks = [p[0] for p in plan]
+        assert any(int(S.out_off[b]) // TB >= n_tiles for b in blocks)                     # a damaged block wholly behind the records
+        assert int(S.out_off[cut[0]]) // TB < n_tiles <= (int(S.out_off[cut[0]]) + int(S.out_len[cut[0]]) - 1) // TB      # one across their end
+        S.upload()
+        assert 0 < n_tiles < S.all_tiles
+        S.n_tiles = n_tiles
+        status = _damage_and_verify(S, plan)
+        exp = np.zeros(S.n, np.int32)
+        exp[blocks] = 9
+        exp[S.refused] = status[S.refused]
+        assert status[S.refused] not in (0, 9) and np.array_equal(status, exp), (status, plan)
+        flags, words = S.tile_flags()
+        assert not words[n_tiles:].any()                             # the records behind the valid ones: as zeroed
+        good = [b for b in range(S.n) if b not in blocks and b != S.refused]
+        _check_tile_flags(flags, n_tiles, S.out_off, S.out_len, blocks + [S.refused], good)
+        for b in blocks + [S.refused]:
+            S.patch(b)
+
+        def around_the_limit(starts, ends):
+            import bisect
+            k = bisect.bisect_left(ends, n_tiles * TB)               # the first line that ends behind the valid records
+            assert 3 < k < len(ends) - 3
+            return [(0, k - 1), (0, k), (k - 2, k - 1), (k - 1, k + 1), (k + 1, len(ends) - 1)]
+        S.check_windows(around_the_limit)
+    finally:
+        S.close()
