@@ -386,11 +386,12 @@ __device__ __forceinline__ void inf2_one_block(uint8_t *smem, const int b, const
         __syncthreads();
         int used_l = 0, used_d = 0;
         const int el = inf2_sort<5>(smem, INF2_LENS, nlen, INF2_SYM_L, INF2_CNT_L, &used_l);
-        if (el < 0 || (el > 0 && used_l != 1)) { rc = 11; break; }
+        // an incomplete code is taken only as zlib's inflate_table and the host decoder take it: one symbol, of one bit
+        if (el < 0 || (el > 0 && !(used_l == 1 && el == (1 << 14)))) { rc = 11; break; }
         __syncthreads();
         inf2_fill<INF2_ROOT_L, 0>(smem, INF2_CNT_L, INF2_SYM_L, INF2_LUT_L);
         const int ed = inf2_sort<1>(smem, (uint32_t)INF2_LENS + (uint32_t)nlen, ndist, INF2_SYM_D, INF2_CNT_D, &used_d);
-        if (type == 2 && (ed < 0 || (ed > 0 && used_d != 1))) { rc = 12; break; }       // the fixed distance code has 30 of its 32 codes
+        if (type == 2 && (ed < 0 || (ed > 0 && !(used_d == 1 && ed == (1 << 14))))) { rc = 12; break; }       // the fixed distance code has 30 of its 32 codes
         __syncthreads();
         inf2_fill<INF2_ROOT_D, 1>(smem, INF2_CNT_D, INF2_SYM_D, INF2_LUT_D);
         __syncthreads();

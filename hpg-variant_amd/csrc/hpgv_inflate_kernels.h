@@ -193,9 +193,9 @@ __device__ __forceinline__ void inflate_one_block(const uint8_t *__restrict__ co
             if (rc) break;
             if (lengths[256] == 0) { rc = 10; break; }
             int e = inflate_construct(lencode, lengths, nlen);
-            if (e < 0 || (e > 0 && nlen - lencode.count[0] != 1)) { rc = 11; break; }
+            if (e < 0 || (e > 0 && !(nlen - lencode.count[0] == 1 && lencode.count[1] == 1))) { rc = 11; break; }
             e = inflate_construct(distcode, lengths + nlen, ndist);
-            if (e < 0 || (e > 0 && ndist - distcode.count[0] != 1)) { rc = 12; break; }
+            if (e < 0 || (e > 0 && !(ndist - distcode.count[0] == 1 && distcode.count[1] == 1))) { rc = 12; break; }
         }
         const InflateCnt lc = inflate_counts(lencode), dc = inflate_counts(distcode);
         for (;;) {                                                  // the block's symbols
@@ -324,9 +324,9 @@ static __global__ void __launch_bounds__(64) k_inflate_blocks_lds(const uint8_t 
             if (rc) break;
             if (lengths[256] == 0) { rc = 10; break; }
             int e = inflate_construct_lds(lencode, lengths, nlen);
-            if (e < 0 || (e > 0 && nlen - lencode.count[0] != 1)) { rc = 11; break; }
+            if (e < 0 || (e > 0 && !(nlen - lencode.count[0] == 1 && lencode.count[1] == 1))) { rc = 11; break; }
             e = inflate_construct_lds(distcode, lengths + nlen, ndist);
-            if (e < 0 || (e > 0 && ndist - distcode.count[0] != 1)) { rc = 12; break; }
+            if (e < 0 || (e > 0 && !(ndist - distcode.count[0] == 1 && distcode.count[1] == 1))) { rc = 12; break; }
         }
         const InflateCnt lc = inflate_counts_lds(lencode), dc = inflate_counts_lds(distcode);
         for (;;) {                                                  // the block's symbols

@@ -8,6 +8,7 @@
  *   host_cpu_check stage <file>       file: "N V" then V lines "chrom format s1..sN";
  *                                     prints per line: is_x then the N code bytes (hex), strict and lax
  *   host_cpu_check blocktable <file>  a bgzip file's block table by the team walk and by the serial walk
+ *   host_cpu_check streams <file>     raw DEFLATE streams assembled by the tests, through hpgv_host_inflate_raw
  */
 #define _GNU_SOURCE
 #include <pthread.h>
@@ -194,6 +195,40 @@ static int cmd_inflate(void) {
     return 0;
 }
 
+/* Streams that zlib's encoder never emits (tests/deflate_corpus.py).  The file holds records [clen u32][rawlen u32][take u8]
+ * [comp: clen bytes][raw: rawlen bytes]; take = 1: a legal stream that must be decoded, 2: a legal one that may be refused,
+ * 0: zlib does not take the stream as rawlen bytes of text, so neither may the decoder.  The text goes into a buffer with 0xEE
+ * guards on both sides, and the stream is copied to a block of its own size so that ASan sees a read past its end.  Prints
+ * "FAIL <record> <why>" per failure, "refused <record>" per legal stream that was refused, then "streams ok" or "streams FAILED". */
+static int cmd_streams(const char *path) {
+    enum { GUARD = 64 };
+    FILE *f = fopen(path, "rb");
+    if (!f) return 2;
+    int n = 0, bad = 0;
+    for (;; n++) {
+        uint32_t head[2];
+        unsigned char take;
+        if (fread(head, 4, 2, f) != 2) break;
+        if (fread(&take, 1, 1, f) != 1) { bad++; break; }
+        const size_t clen = head[0], rawlen = head[1];
+        unsigned char *comp = malloc(clen ? clen : 1), *raw = malloc(rawlen ? rawlen : 1), *out = malloc(rawlen + 2 * GUARD);
+        if (fread(comp, 1, clen, f) != clen || fread(raw, 1, rawlen, f) != rawlen) { printf("FAIL %d short record\n", n); bad++; break; }
+        memset(out, 0xEE, rawlen + 2 * GUARD);
+        const int rc = hpgv_host_inflate_raw(comp, clen, out + GUARD, rawlen);
+        int touched = 0;
+        for (int k = 0; k < GUARD; k++) touched |= out[k] != 0xEE || out[GUARD + rawlen + k] != 0xEE;
+        if (touched) { printf("FAIL %d a guard byte was written\n", n); bad++; }
+        if (rc == 0 && take == 0) { printf("FAIL %d taken, and zlib does not take it\n", n); bad++; }
+        if (rc == 0 && take != 0 && memcmp(out + GUARD, raw, rawlen) != 0) { printf("FAIL %d wrong bytes\n", n); bad++; }
+        if (rc != 0 && take == 1) { printf("FAIL %d refused, and it must be taken\n", n); bad++; }
+        if (rc != 0 && take != 0) printf("refused %d\n", n);
+        free(comp); free(raw); free(out);
+    }
+    fclose(f);
+    printf("%s: %d records\n", bad ? "streams FAILED" : "streams ok", n);
+    return bad ? 1 : 0;
+}
+
 /* sample strings that end exactly at the end of a mapped page whose successor is not accessible: the staging's four-byte
  * loads must not reach over the edge */
 #include <sys/mman.h>
@@ -273,6 +308,7 @@ int main(int argc, char **argv) {
     if (argc >= 2 && !strcmp(argv[1], "containers")) return cmd_containers();
     if (argc >= 2 && !strcmp(argv[1], "pageedge")) return cmd_pageedge();
     if (argc >= 2 && !strcmp(argv[1], "inflate")) return cmd_inflate();
+    if (argc >= 3 && !strcmp(argv[1], "streams")) return cmd_streams(argv[2]);
     if (argc >= 3 && !strcmp(argv[1], "stage")) return cmd_stage(argv[2]);
     if (argc >= 3 && !strcmp(argv[1], "blocktable")) return cmd_blocktable(argv[2]);
     if (argc >= 3 && !strcmp(argv[1], "sort")) return hpgv_host_sort_output_file(argv[2]);

@@ -779,3 +779,97 @@ def test_run_fails_on_a_bgzf_block_with_a_wrong_crc(host, tmp_path):
         assert rc == 0 and res == ref
     rc, res, _ = run(bad, {"HPGV_BGZF_VERIFY": "0"})
     assert rc == 0 and res != ref                                     # unchecked: the wrong genotype is counted
+
+
+def _hand_assembled_payload(kind, text):
+    """the raw-DEFLATE payload of one BGZF block around `text`, as zlib's encoder would never write it: the constructs of the corpus
+    classes (tests/deflate_corpus.py) around a text the caller chose"""
+    import deflate_builder as db
+    s = db.Stream()
+    if kind == "many_blocks":                                            # ninety-odd blocks of all three types, some of them empty
+        at, k = 0, 0
+        while at < len(text):
+            n = min(len(text) - at, 40 + (k * 37) % 300)
+            if k % 4 == 0:
+                s.stored(text[at:at + n])
+            elif k % 4 == 3:
+                (s.fixed if k % 8 == 3 else s.auto_dynamic)([])
+                n = 0
+            else:
+                (s.fixed if k % 4 == 1 else s.auto_dynamic)(db.match_tokens(text, at, at + n))
+            at += n; k += 1
+        s.stored(b"", final=True)
+    elif kind == "cl_runs":                                              # the two tables' lengths run-length coded as one sequence
+        s.auto_dynamic(db.match_tokens(text, 0, len(text)), final=True, runs=True, hlit=286)
+        assert s.runs_across_the_tables == 1
+    elif kind == "long_codes":                                           # codes of up to 13 bits: past the decoders' first-level tables
+        s.auto_dynamic(db.match_tokens(text, 0, len(text)), final=True, shape=db.skewed_lengths)
+        assert max(l for _, l in s.ll.values()) > 10
+    elif kind == "full_distance":                                        # 32 KiB stored, then matches from 16 385 .. 32 768 bytes back
+        s.stored(text[:32768])
+        toks = db.match_tokens(text, 32768, len(text), window=32768, min_dist=16385)
+        assert sum(1 for t in toks if not isinstance(t, int)) > 100
+        s.fixed(toks, final=True)
+    else:                                                                # no distance code at all: a class the device decoder may refuse
+        lits = sorted(set(text) | {256})
+        ll = db.balanced_lengths(lits, 257)
+        cls = db.run_length_code_lengths(ll + [0])
+        s.dynamic(list(text), ll, [0], cls, db.balanced_lengths(sorted({c for c, _ in cls}), 19), final=True)
+    assert bytes(s.text) == text
+    return s.getvalue()
+
+
+def test_run_assoc_from_bgzf_blocks_of_hand_assembled_streams(host, tmp_path, capfd):
+    # a bgzip file as another encoder could have written it: thirteen of its blocks hold DEFLATE constructs that zlib's encoder never
+    # emits (many blocks of all types, code-length runs across the two tables, codes past the first-level tables, matches from
+    # 32 768 bytes back, a block without a distance code), the others are zlib's -- enough of them for the device path.  Same
+    # result file as from the same text compressed by zlib, by the device decoder, with every third block handed back to the
+    # host decoder, and by the host decoder alone; every block's text passes the CRC check on the way.
+    import zlib
+    from test_gpu_text import _bgzf_bytes
+    from test_host_logic_cpu import _bgzf
+    rng = np.random.default_rng(1951)
+    people, names, rows = _write_inputs(tmp_path, rng, 8, 13, 2800)
+    vcf = _vcf_from_batch(tmp_path, names, rows)
+    data = open(vcf, "rb").read()
+    special = [("many_blocks", 9000), ("cl_runs", 7000), ("long_codes", 8000), ("full_distance", 41000), ("no_distance_code", 900),
+               ("many_blocks", 15001), ("cl_runs", 2999), ("long_codes", 12345), ("full_distance", 36000), ("cl_runs", 65280),
+               ("many_blocks", 1), ("long_codes", 777), ("no_distance_code", 63)]
+    payloads, raws, at, k = [], [], 0, 0
+    while at < len(data):
+        if k % 18 == 5 and special:
+            kind, n = special.pop(0)
+            raw = data[at:at + n]
+            payloads.append(_hand_assembled_payload(kind, raw))
+        else:
+            raw = data[at:at + 0x700]
+            co = zlib.compressobj(6, zlib.DEFLATED, -15)
+            payloads.append(co.compress(raw) + co.flush())
+        assert zlib.decompressobj(-15).decompress(payloads[-1]) == raw
+        raws.append(raw); at += len(raw); k += 1
+    assert not special and len(payloads) >= 256                       # (from 256 blocks on a file is decoded on the device)
+    mine, theirs = str(tmp_path / "mine.vcf.gz"), str(tmp_path / "zlib.vcf.gz")
+    open(mine, "wb").write(_bgzf_bytes(payloads, raws)[0] + _bgzf(b""))
+    open(theirs, "wb").write(_bgzf(data, 0x700))
+    ped = str(tmp_path / "ped.txt").encode()
+
+    def run(path, tag, env):
+        os.environ.update(env)
+        try:
+            out = str(tmp_path / ("res_" + tag + ".chisq"))
+            n = C.c_long(0)
+            rc = host.hpgv_run_assoc(path.encode(), ped, out.encode(), 1, 1 << 17, C.byref(n))
+            assert rc == 0 and n.value == len(rows), (tag, host.hpgv_host_last_error())
+            return open(out, "rb").read()
+        finally:
+            for key in env:
+                del os.environ[key]
+    want = run(theirs, "zlib", {})
+    assert want.count(b"\n") == len(rows) + 1
+    capfd.readouterr()
+    assert run(mine, "device", {"HPGV_RUN_TRACE": "1"}) == want
+    assert "blocks found" in capfd.readouterr().err                     # (decoded on the device)
+    for every in ("2", "3"):                                              # ... with blocks handed back to the host decoder
+        assert run(mine, "handed_back_" + every, {"HPGV_TEST_GPU_INFLATE_REFUSE_EVERY": every}) == want
+    assert run(mine, "host", {"HPGV_NO_GPU_INFLATE": "1"}) == want
+    assert run(mine, "host_zlib", {"HPGV_NO_GPU_INFLATE": "1", "HPGV_ZLIB_INFLATE": "1"}) == want

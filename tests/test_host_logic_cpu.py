@@ -17,7 +17,16 @@ def _host_sources():
     return [os.path.join(hdir, f) for f in sorted(os.listdir(hdir)) if f.endswith(".c")]
 
 
+_COMPILED = {}                                       # one build of each kind per session, whichever modules ask for it
+
+
 def _compile(tmp_path_factory, name, flags):
+    if name not in _COMPILED:
+        _COMPILED[name] = _compile_once(tmp_path_factory, name, flags)
+    return _COMPILED[name]
+
+
+def _compile_once(tmp_path_factory, name, flags):
     hpgv.build()
     from importlib import import_module
     b = import_module("hpg-variant_amd._build")
