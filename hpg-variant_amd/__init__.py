@@ -62,6 +62,7 @@ SYMBOLS = [
     "hpgv_inheritance_scan_dev", "hpgv_set_text_inheritance_filters",
     "hpgv_bgzf_deflate_bound", "hpgv_bgzf_deflate_scratch_bytes", "hpgv_bgzf_deflate_dev", "hpgv_bgzf_compress",
     "hpgv_text_partition_bgzf", "hpgv_text_multisplit_bgzf",
+    "hpgv_set_perm_labels", "hpgv_assoc_perm_dev", "hpgv_assoc_perm", "hpgv_assoc_perm_text", "hpgv_perm_labels_shuffle", "hpgv_perm_pvalues",
 ]
 
 
@@ -209,8 +210,39 @@ def load():
     L.hpgv_bgzf_compress.argtypes = [vp, vp, sz, vp, sz, C.POINTER(sz)]
     L.hpgv_text_partition_bgzf.argtypes = [vp, vp, vp, i32, vp, sz, i32, vp, vp, vp, vp]
     L.hpgv_text_multisplit_bgzf.argtypes = [vp, vp, vp, i32, i32, i32, vp, sz, vp, vp]
+    L.hpgv_set_perm_labels.argtypes = [vp, vp, i32]
+    L.hpgv_assoc_perm_dev.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp]
+    L.hpgv_assoc_perm.argtypes = [vp, vp, sz, i32, vp] + [vp] * 9
+    L.hpgv_assoc_perm_text.argtypes = [vp, C.c_char_p, sz, i32, C.POINTER(i32), vp, vp, vp] + [vp] * 9
+    L.hpgv_perm_labels_shuffle.argtypes = [vp, i32, i32, u64, vp]
+    L.hpgv_perm_pvalues.argtypes = [vp, i32, vp, vp, i32, vp, vp]
     _lib = L
     return L
+
+
+def perm_labels_shuffle(condition, n_perms, seed):
+    """hpgv_perm_labels_shuffle: (n_perms, n_samples) uint8 label rows, each a uniform shuffle of the cohort columns'
+    conditions; deterministic in (seed, row).  No device needed."""
+    c = _np(condition, np.uint8)
+    out = np.zeros((n_perms, len(c)), np.uint8)
+    rc = load().hpgv_perm_labels_shuffle(_ptr(c), len(c), n_perms, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(out))
+    if rc != OK:
+        raise HpgvError("hpgv_perm_labels_shuffle -> %d" % rc)
+    return out
+
+
+def perm_pvalues(t_obs, n_ge, t_max):
+    """hpgv_perm_pvalues: (EMP1, EMP2) of every variant from its observed statistic, its count of permutations at or above
+    it, and the per-permutation maxima merged over the whole scan.  No device needed."""
+    t = _np(t_obs, np.float64)
+    g = _np(n_ge, np.int32)
+    m = _np(t_max, np.float64)
+    assert t.shape == g.shape and t.ndim == 1 and m.ndim == 1
+    emp1, emp2 = np.zeros(len(t), np.float64), np.zeros(len(t), np.float64)
+    rc = load().hpgv_perm_pvalues(_ptr(t), len(t), _ptr(g), _ptr(m), len(m), _ptr(emp1), _ptr(emp2))
+    if rc != OK:
+        raise HpgvError("hpgv_perm_pvalues -> %d" % rc)
+    return emp1, emp2
 
 
 def _np(a, dtype):
@@ -274,7 +306,19 @@ class Engine:
     def set_cohort(self, condition):
         c = _np(condition, np.uint8)
         self._chk(self.L.hpgv_set_cohort(self.h, _ptr(c), len(c)))
+        self._n_perms = 0               # a new cohort drops the label rows
         return self.assoc_layout()
+
+    def set_perm_labels(self, labels):
+        """hpgv_set_perm_labels: labels (n_perms, n_samples) of 0 / 1 in VCF column order; None or no rows drops them."""
+        if labels is None or len(labels) == 0:
+            self._chk(self.L.hpgv_set_perm_labels(self.h, None, 0))
+            self._n_perms = 0
+            return
+        lab = _np(labels, np.uint8)
+        assert lab.ndim == 2
+        self._chk(self.L.hpgv_set_perm_labels(self.h, _ptr(lab), lab.shape[0]))
+        self._n_perms = lab.shape[0]
 
     def assoc_layout(self):
         a, u, p = C.c_int(), C.c_int(), C.c_size_t()
@@ -378,6 +422,37 @@ class Engine:
                                     _ptr(chisq) if task == TASK_CHISQ else None, _ptr(p)))
         return dict(A1=A1, A2=A2, U1=U1, U2=U2, odds=odds,
                     chisq=chisq if task == TASK_CHISQ else None, p=p)
+
+    def assoc_perm(self, gt, is_x=None):
+        """hpgv_assoc_perm: hpgv_assoc with task CHISQ plus n_ge per variant and batch_max per permutation."""
+        gt = _np(gt, np.uint8)
+        nv, pitch = gt.shape
+        x = None if is_x is None else _np(is_x, np.uint8)
+        A1, A2, U1, U2, n_ge = (np.zeros(nv, np.int32) for _ in range(5))
+        odds, chisq, p = (np.zeros(nv, np.float64) for _ in range(3))
+        bmax = np.zeros(max(getattr(self, "_n_perms", 0), 1), np.float64)
+        self._chk(self.L.hpgv_assoc_perm(self.h, _ptr(gt), pitch, nv, _ptr(x), _ptr(A1), _ptr(A2), _ptr(U1), _ptr(U2),
+                                         _ptr(odds), _ptr(chisq), _ptr(p), _ptr(n_ge), _ptr(bmax)))
+        return dict(A1=A1, A2=A2, U1=U1, U2=U2, odds=odds, chisq=chisq, p=p, n_ge=n_ge, batch_max=bmax[:self._n_perms])
+
+    def assoc_perm_text(self, text, max_lines=None):
+        """hpgv_assoc_perm_text: hpgv_assoc_text with task CHISQ plus n_ge per line and batch_max per permutation."""
+        if isinstance(text, str):
+            text = text.encode()
+        if max_lines is None:
+            max_lines = text.count(b"\n") + 1
+        m = max(max_lines, 1)
+        A1, A2, U1, U2, n_ge = (np.zeros(m, np.int32) for _ in range(5))
+        odds, chisq, p = (np.zeros(m, np.float64) for _ in range(3))
+        status = np.zeros(m, np.int32)
+        bmax = np.zeros(max(getattr(self, "_n_perms", 0), 1), np.float64)
+        nl = C.c_int(0)
+        self._chk(self.L.hpgv_assoc_perm_text(self.h, text, len(text), max_lines, C.byref(nl), None, None, _ptr(status),
+                                              _ptr(A1), _ptr(A2), _ptr(U1), _ptr(U2), _ptr(odds), _ptr(chisq), _ptr(p),
+                                              _ptr(n_ge), _ptr(bmax)))
+        k = min(nl.value, max_lines)
+        return dict(n_lines=nl.value, status=status[:k], A1=A1[:k], A2=A2[:k], U1=U1[:k], U2=U2[:k], odds=odds[:k],
+                    chisq=chisq[:k], p=p[:k], n_ge=n_ge[:k], batch_max=bmax[:self._n_perms])
 
     def assoc_view(self, task, gt2d, n_samples, is_x=None):
         """hpgv_assoc on a 2-D uint8 VIEW as it lies in memory (row stride = pitch): nothing is copied on the way,
@@ -613,6 +688,9 @@ class Engine:
 
     def assoc_chisq(self, d_counts, n_variants, d_odds, d_chisq, d_p, stream=None):
         self._chk(self.L.hpgv_assoc_chisq_dev(self.h, d_counts, n_variants, d_odds, d_chisq, d_p, stream))
+
+    def assoc_perm_dev(self, d_gt, n_variants, d_counts, d_n_ge, d_batch_max, d_perm_counts=None, d_is_x=None, stream=None):
+        self._chk(self.L.hpgv_assoc_perm_dev(self.h, d_gt, n_variants, d_is_x, d_counts, d_n_ge, d_batch_max, d_perm_counts, stream))
 
     def assoc_fisher(self, d_counts, n_variants, d_odds, d_p, stream=None):
         self._chk(self.L.hpgv_assoc_fisher_dev(self.h, d_counts, n_variants, d_odds, d_p, stream))

@@ -2,7 +2,7 @@
 // libhpgv.so: hpgv_capi.hip (contexts, options, cohorts, memory, streams, text aliases), hpgv_scan_capi.hip (the
 // device-resident *_dev launchers), hpgv_text_capi.hip (tokenizer, the text entry points' front half),
 // hpgv_tool_capi.hip (per-batch and text entry points), hpgv_lines_capi.hip (partition / multisplit of lines), and the
-// units whose kernel instantiations compile on their own (hpgv_epi_capi.hip, hpgv_epi_generic_capi.hip, hpgv_statsall_capi.hip, hpgv_inflate_capi.hip, hpgv_group_capi.hip).
+// units whose kernel instantiations compile on their own (hpgv_perm_capi.hip, hpgv_epi_capi.hip, hpgv_epi_generic_capi.hip, hpgv_statsall_capi.hip, hpgv_inflate_capi.hip, hpgv_group_capi.hip).
 // The host side the epistasis units share is in hpgv_epi_host.h.
 #pragma once
 #include "../../include/hpgv.h"
@@ -104,6 +104,7 @@ struct Slot {
     DevBuf inherit;    // the inheritance filter's counts8 and verdict bytes
     DevBuf multi;      // multi-allelic rows: their indices, then their 256-bin tables
     DevBuf row_cnt;    // k_stats_all2's per-row counters between its two kernels
+    DevBuf perm;       // the permutation call's results: n_ge per row, the batch maxima per permutation, then the rows' skip bytes
     PinnedBuf res;     // result block of the one-pass kernels (they store into it), staging of k_assoc_rows' results
     // a buffer under two names holds two things that no call has at once:
     DevBuf &heads = text;      // a text that lies on the device already (hpgv_text_alias) is not uploaded: its head offsets and heads
@@ -112,7 +113,7 @@ struct Slot {
     DevBuf &aux = tally;       //   offsets scratch, keep / bucket bytes, segment tables,
     DevBuf &dfl = dbl;         //   the deflate kernels' scratch
     void release() {
-        for (DevBuf *b : {&text, &raw, &laid, &isx, &status, &meta, &tally, &dbl, &gtally, &gdbl, &ints, &smiss, &merr, &inherit, &multi, &row_cnt}) b->release();
+        for (DevBuf *b : {&text, &raw, &laid, &isx, &status, &meta, &tally, &dbl, &gtally, &gdbl, &ints, &smiss, &merr, &inherit, &multi, &row_cnt, &perm}) b->release();
         res.release();
     }
 };
@@ -231,6 +232,10 @@ struct hpgv_ctx {
     Layout assoc;
     int nA = 0, nU = 0, chunksA = 0;
     DevBuf d_cond;                        // the condition of every column as given (padded with 2 to whole 16-byte chunks): k_assoc_rows' masks
+    // label permutations of the association test (hpgv_set_perm_labels): one row per permutation in the assoc layout's column order
+    // and pitch, zeros under the pads, perm_rows = n_perms rounded up to 16 rows; dropped by a new cohort
+    DevBuf d_perm;
+    int n_perms = 0, perm_rows = 0;
     // tdt
     Layout tdt;
     hpgv::TdtPlan tdt_plan;

@@ -1,0 +1,242 @@
+// hpgv_perm_capi.hip -- C ABI of the max(T) label permutation of the association test (include/hpgv.h "label
+// permutation"): the label rows of a context, the device-resident launch of k_assoc_perm, the synchronous entry points on a
+// host batch and on a text, and the two host-only helpers (label shuffle, empirical p-values).
+#include "hpgv_internal.h"
+#include "hpgv_assoc_perm_kernels.h"
+
+namespace {
+
+constexpr int kMaxPerms = 1 << 20;      // PERM_PT permutations per workgroup row of the grid: far below the grid's 65 535 rows
+
+int perm_state_check(const hpgv_ctx *ctx) {
+    if (!ctx->assoc.set) return fail(ctx, HPGV_ERR_STATE, "hpgv_set_cohort has not been called");
+    if (ctx->n_perms <= 0) return fail(ctx, HPGV_ERR_STATE, "hpgv_set_perm_labels has not been called (a new cohort drops the labels)");
+    return HPGV_OK;
+}
+
+// the launch: n_ge and batch_max zeroed on the stream, then the kernel
+int perm_launch(hpgv_ctx *ctx, const uint8_t *d_gt, int n_variants, const uint8_t *d_is_x, const int32_t *d_counts, const uint8_t *d_skip,
+                int32_t *d_n_ge, double *d_batch_max, int32_t *d_perm_counts, hipStream_t st) {
+    HIPCHK(ctx, hipMemsetAsync(d_batch_max, 0, (size_t)ctx->n_perms * sizeof(double), st));
+    if (n_variants == 0) return HPGV_OK;
+    HIPCHK(ctx, hipMemsetAsync(d_n_ge, 0, (size_t)n_variants * sizeof(int32_t), st));
+    hpgv::PermArgs A;
+    A.gt = d_gt; A.pitch = ctx->assoc.pitch; A.chunks = ctx->assoc.chunks; A.n_variants = n_variants;
+    A.is_x = d_is_x; A.counts = (const int4 *)d_counts;
+    A.labels = ctx->d_perm.as<uint8_t>(); A.n_perms = ctx->n_perms; A.label_rows = ctx->perm_rows;
+    A.skip = d_skip; A.n_ge = d_n_ge; A.batch_max = (unsigned long long *)d_batch_max; A.perm_counts = d_perm_counts;
+    const dim3 grid((unsigned)((n_variants + hpgv::PERM_VT - 1) / hpgv::PERM_VT), (unsigned)((ctx->n_perms + hpgv::PERM_PT - 1) / hpgv::PERM_PT));
+    // (option "profile": the kernel's time is the statistics time of hpgv_last_kernel_ms)
+    return launch_profiled(ctx, st, 1, [&] { hipLaunchKernelGGL(hpgv::k_assoc_perm, grid, dim3(256), 0, st, A); });
+}
+
+// the back half of the two synchronous entry points: the laid-out matrix of a staged call -> scan, chi-square, permutation
+// kernel -> the caller's arrays.  skip (host, may be null): rows that take no part
+int perm_finish(hpgv_ctx *ctx, Slot *s, const Staged &S, const uint8_t *skip, int32_t *A1, int32_t *A2, int32_t *U1, int32_t *U2,
+                double *odds, double *chisq, double *p, int32_t *n_ge, double *batch_max) {
+    int rc;
+    const int nv = S.n;
+    const size_t n = (size_t)nv, np = (size_t)ctx->n_perms;
+    const size_t off_max = round_up(n * sizeof(int32_t), 16), off_skip = off_max + np * sizeof(double);
+    HIPCHK(ctx, s->tally.reserve_slack(n * 16 + 16));
+    HIPCHK(ctx, s->dbl.reserve_slack(n * 3 * sizeof(double) + 16));
+    HIPCHK(ctx, s->ints.reserve_slack(n * 4 * sizeof(int32_t) + 16));
+    HIPCHK(ctx, s->perm.reserve_slack(off_skip + n + 16));
+    int32_t *d_counts = s->tally.as<int32_t>(), *d_soa = s->ints.as<int32_t>();
+    double *d_odds = s->dbl.as<double>(), *d_chisq = d_odds + n, *d_p = d_odds + 2 * n;
+    int32_t *d_n_ge = s->perm.as<int32_t>();
+    double *d_max = (double *)(s->perm.as<char>() + off_max);
+    uint8_t *d_skip = nullptr;
+    if (skip && nv > 0) {
+        d_skip = s->perm.as<uint8_t>() + off_skip;
+        HIPCHK(ctx, hipMemcpyAsync(d_skip, skip, n, hipMemcpyHostToDevice, s->stream));
+    }
+    if (nv > 0) {
+        if ((rc = hpgv_assoc_scan_dev(ctx, S.d_laid, nv, S.d_isx, d_counts, s->stream))) return rc;
+        if ((rc = hpgv_assoc_chisq_dev(ctx, d_counts, nv, d_odds, d_chisq, d_p, s->stream))) return rc;
+    }
+    if ((rc = perm_launch(ctx, S.d_laid, nv, S.d_isx, d_counts, d_skip, d_n_ge, d_max, nullptr, s->stream))) return rc;
+    if (nv > 0) {
+        hipLaunchKernelGGL(hpgv::k_counts_to_soa, dim3((nv + 255) / 256), dim3(256), 0, s->stream,
+                           (const int4 *)d_counts, nv, d_soa, d_soa + n, d_soa + 2 * n, d_soa + 3 * n);
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipMemcpyAsync(A1, d_soa, n * 4, hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(ctx, hipMemcpyAsync(A2, d_soa + n, n * 4, hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(ctx, hipMemcpyAsync(U1, d_soa + 2 * n, n * 4, hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(ctx, hipMemcpyAsync(U2, d_soa + 3 * n, n * 4, hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(ctx, hipMemcpyAsync(odds, d_odds, n * 8, hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(ctx, hipMemcpyAsync(chisq, d_chisq, n * 8, hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(ctx, hipMemcpyAsync(p, d_p, n * 8, hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(ctx, hipMemcpyAsync(n_ge, d_n_ge, n * 4, hipMemcpyDeviceToHost, s->stream));
+    }
+    HIPCHK(ctx, hipMemcpyAsync(batch_max, d_max, np * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(ctx, hipStreamSynchronize(s->stream));
+    return HPGV_OK;
+}
+
+// SplitMix64 (Steele, Lea, Flood 2014): the finalizer of the generator named in include/hpgv.h
+inline uint64_t splitmix64(uint64_t z) {
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+}  // namespace
+
+extern "C" {
+
+int hpgv_set_perm_labels(hpgv_ctx *ctx, const uint8_t *labels, int n_perms) {
+    HPGV_ABI_TRY
+    GROUP_ALL(ctx, hpgv_set_perm_labels(m_, labels, n_perms))
+    if (!ctx) return HPGV_ERR_INVALID;
+    if (!ctx->assoc.set) return fail(ctx, HPGV_ERR_STATE, "hpgv_set_cohort has not been called");
+    if (n_perms < 0 || (n_perms > 0 && !labels)) return fail(ctx, HPGV_ERR_INVALID, "bad perm_labels arguments");
+    if (n_perms > kMaxPerms) return fail(ctx, HPGV_ERR_UNSUPPORTED, "%d permutations: at most %d per call", n_perms, kMaxPerms);
+    if (n_perms == 0) { ctx->n_perms = ctx->perm_rows = 0; return HPGV_OK; }
+    const Layout &L = ctx->assoc;
+    const size_t ns = (size_t)L.n_samples, rows = round_up((size_t)n_perms, 16);
+    std::vector<uint8_t> laid(rows * L.pitch, 0);
+    for (int q = 0; q < n_perms; ++q) {
+        const uint8_t *src = labels + (size_t)q * ns;
+        uint8_t *dst = laid.data() + (size_t)q * L.pitch;
+        for (size_t pos = 0; pos < L.pitch; ++pos) {
+            const int32_t j = L.col_of_pos[pos];
+            if (j < 0) continue;
+            if (src[j] > 1) return fail(ctx, HPGV_ERR_INVALID, "label %u of permutation %d, column %d: labels are 0 or 1", (unsigned)src[j], q, (int)j);
+            dst[pos] = src[j];
+        }
+    }
+    DeviceGuard g(ctx->device);
+    ctx->n_perms = ctx->perm_rows = 0;
+    {
+        const hipError_t e = ctx->d_perm.reserve(laid.size());
+        if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(ctx, HPGV_ERR_NOMEM, "the label matrix (%zu bytes) does not fit the device", laid.size()); }
+        HIPCHK(ctx, e);
+    }
+    HIPCHK(ctx, hipMemcpy(ctx->d_perm.p, laid.data(), laid.size(), hipMemcpyHostToDevice));
+    ctx->n_perms = n_perms; ctx->perm_rows = (int)rows;
+    return HPGV_OK;
+    HPGV_ABI_CATCH(ctx)
+}
+
+int hpgv_assoc_perm_dev(hpgv_ctx *ctx, const uint8_t *d_gt, int n_variants, const uint8_t *d_is_x, const int32_t *d_counts,
+                        int32_t *d_n_ge, double *d_batch_max, int32_t *d_perm_counts, void *stream) {
+    ctx = first_member(ctx);
+    if (!ctx) return HPGV_ERR_INVALID;
+    if (const int rc = perm_state_check(ctx)) return rc;
+    if (n_variants < 0 || !d_batch_max || (n_variants > 0 && (!d_gt || !d_counts || !d_n_ge))) return fail(ctx, HPGV_ERR_INVALID, "bad assoc_perm arguments");
+    if (((uintptr_t)d_gt & 15) || ((uintptr_t)d_counts & 15) || ((uintptr_t)d_batch_max & 7) || ((uintptr_t)d_perm_counts & 7))
+        return fail(ctx, HPGV_ERR_INVALID, "d_gt and d_counts must be 16-byte aligned, d_batch_max and d_perm_counts 8-byte aligned");
+    DeviceGuard g(ctx->device);
+    return perm_launch(ctx, d_gt, n_variants, d_is_x, d_counts, nullptr, d_n_ge, d_batch_max, d_perm_counts, (hipStream_t)stream);
+}
+
+int hpgv_assoc_perm(hpgv_ctx *ctx, const uint8_t *gt, size_t pitch, int n_variants, const uint8_t *is_x,
+                    int32_t *A1, int32_t *A2, int32_t *U1, int32_t *U2, double *odds, double *chisq, double *p,
+                    int32_t *n_ge, double *batch_max) {
+    HPGV_ABI_TRY
+    GROUP_DEAL(ctx, hpgv_assoc_perm(m_, gt, pitch, n_variants, is_x, A1, A2, U1, U2, odds, chisq, p, n_ge, batch_max))
+    if (!ctx) return HPGV_ERR_INVALID;
+    if (const int rc0 = perm_state_check(ctx)) return rc0;
+    if (n_variants < 0 || !batch_max || (n_variants > 0 && (!gt || !A1 || !A2 || !U1 || !U2 || !odds || !chisq || !p || !n_ge)))
+        return fail(ctx, HPGV_ERR_INVALID, "bad assoc_perm arguments");
+    if (pitch < (size_t)ctx->assoc.n_samples) return fail(ctx, HPGV_ERR_INVALID, "pitch %zu < n_samples %d", pitch, ctx->assoc.n_samples);
+    HPGV_LEASE_SLOT(ctx)
+    Staged S;
+    if (n_variants > 0) {
+        // the rows and is_x copied to the slot and laid out (the last row need not be a whole pitch)
+        const Layout &L = ctx->assoc;
+        const size_t bytes = (size_t)(n_variants - 1) * pitch + (size_t)L.n_samples;
+        HIPCHK(ctx, s->raw.reserve_slack(bytes + 16));
+        HIPCHK(ctx, s->laid.reserve_slack((size_t)n_variants * L.pitch + 16));
+        if (bytes) HIPCHK(ctx, hipMemcpyAsync(s->raw.p, gt, bytes, hipMemcpyHostToDevice, s->stream));
+        if (is_x) {
+            HIPCHK(ctx, s->isx.reserve_slack((size_t)n_variants));
+            HIPCHK(ctx, hipMemcpyAsync(s->isx.p, is_x, (size_t)n_variants, hipMemcpyHostToDevice, s->stream));
+            S.d_isx = s->isx.as<uint8_t>();
+        }
+        S.d_raw = s->raw.as<uint8_t>(); S.raw_pitch = pitch; S.d_laid = s->laid.as<uint8_t>(); S.which = HPGV_LAYOUT_ASSOC;
+        if ((rc = hpgv_layout_dev(ctx, HPGV_LAYOUT_ASSOC, S.d_raw, pitch, n_variants, s->laid.as<uint8_t>(), s->stream))) return rc;
+    }
+    S.n = n_variants; S.out_stride = (size_t)n_variants;
+    return perm_finish(ctx, s, S, nullptr, A1, A2, U1, U2, odds, chisq, p, n_ge, batch_max);
+    HPGV_ABI_CATCH(ctx)
+}
+
+int hpgv_assoc_perm_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, int max_lines, int *n_lines,
+                         uint64_t *line_off, uint32_t *field_off, int32_t *status, int32_t *A1, int32_t *A2,
+                         int32_t *U1, int32_t *U2, double *odds, double *chisq, double *p, int32_t *n_ge, double *batch_max) {
+    HPGV_ABI_TRY
+    GROUP_DEAL_TEXT(ctx, text, hpgv_assoc_perm_text(m_, text, text_bytes, max_lines, n_lines, line_off, field_off, status, A1, A2, U1, U2, odds, chisq, p, n_ge, batch_max))
+    if (!ctx) return HPGV_ERR_INVALID;
+    if (const int rc0 = perm_state_check(ctx)) return rc0;
+    if (!n_lines || !batch_max || max_lines < 0 || (text_bytes > 0 && !text) ||
+        (max_lines > 0 && (!A1 || !A2 || !U1 || !U2 || !odds || !chisq || !p || !n_ge)))
+        return fail(ctx, HPGV_ERR_INVALID, "bad assoc_perm_text arguments");
+    *n_lines = 0;
+    std::vector<int32_t> own_status;             // (before the lease: queued copies into them end with the lease)
+    std::vector<uint8_t> skip;
+    HPGV_LEASE_SLOT(ctx)
+    Staged S;
+    if (max_lines > 0) {
+        if (!status) { own_status.assign((size_t)max_lines, 0); status = own_status.data(); }
+        if ((rc = text_front(ctx, s, HPGV_LAYOUT_ASSOC, ctx->assoc, text, text_bytes, max_lines, n_lines, line_off, field_off, status, &S, true))) return rc;
+        // the lines hpgv_assoc_text's callers drop: not a record (status 1), or rejected by a record filter
+        HIPCHK(ctx, hipStreamSynchronize(s->stream));
+        skip.resize((size_t)S.n);
+        for (int i = 0; i < S.n; ++i) skip[(size_t)i] = ((status[i] & 0xFF) == 1 || (status[i] & HPGV_LINE_FILTERED)) ? 1 : 0;
+    }
+    return perm_finish(ctx, s, S, skip.empty() ? nullptr : skip.data(), A1, A2, U1, U2, odds, chisq, p, n_ge, batch_max);
+    HPGV_ABI_CATCH(ctx)
+}
+
+/* ---- host-only helpers: no GPU call, usable without a device ------------------------------------------------------- */
+
+int hpgv_perm_labels_shuffle(const uint8_t *condition, int n_samples, int n_perms, uint64_t seed, uint8_t *labels_out) {
+    if (n_samples < 0 || n_perms < 0 || (n_samples > 0 && !condition) || ((size_t)n_samples * (size_t)n_perms > 0 && !labels_out)) return HPGV_ERR_INVALID;
+    try {
+        std::vector<int32_t> cols;
+        std::vector<uint8_t> base;
+        for (int j = 0; j < n_samples; ++j)
+            if (condition[j] == HPGV_COND_AFFECTED || condition[j] == HPGV_COND_UNAFFECTED) { cols.push_back(j); base.push_back(condition[j] == HPGV_COND_AFFECTED ? 1 : 0); }
+        const size_t nc = cols.size();
+        std::vector<uint8_t> y(nc);
+        for (int q = 0; q < n_perms; ++q) {
+            uint8_t *row = labels_out + (size_t)q * (size_t)n_samples;
+            memset(row, 0, (size_t)n_samples);
+            y = base;
+            // the row's stream: key = SplitMix64(seed ^ SplitMix64(q)); draw number i of the row = SplitMix64(key + i)
+            const uint64_t key = splitmix64(seed ^ splitmix64((uint64_t)q));
+            uint64_t draw = 0;
+            for (size_t i = nc; i > 1; --i) {
+                // Fisher-Yates: position i - 1 swaps with j uniform in [0, i): the high 64 bits of draw x i (bias below i / 2^64)
+                const uint64_t r = splitmix64(key + draw++);
+                const size_t j = (size_t)(((unsigned __int128)r * (unsigned __int128)i) >> 64);
+                std::swap(y[i - 1], y[j]);
+            }
+            for (size_t k = 0; k < nc; ++k) row[cols[k]] = y[k];
+        }
+    } catch (...) { return HPGV_ERR_NOMEM; }
+    return HPGV_OK;
+}
+
+int hpgv_perm_pvalues(const double *t_obs, int n_variants, const int32_t *n_ge, const double *t_max, int n_perms, double *emp1, double *emp2) {
+    if (n_variants < 0 || n_perms < 1 || !t_max || (n_variants > 0 && (!t_obs || !n_ge || !emp1 || !emp2))) return HPGV_ERR_INVALID;
+    try {
+        std::vector<double> sorted(t_max, t_max + n_perms);
+        std::sort(sorted.begin(), sorted.end());
+        const double denom = (double)n_perms + 1.0;
+        for (int v = 0; v < n_variants; ++v) {
+            const double t = t_obs[v];
+            if (t != t) { emp1[v] = emp2[v] = t; continue; }
+            // permutations whose maximum is >= t: those from the first element not below t on
+            const size_t ge = (size_t)(sorted.end() - std::lower_bound(sorted.begin(), sorted.end(), t));
+            emp1[v] = ((double)n_ge[v] + 1.0) / denom;
+            emp2[v] = ((double)ge + 1.0) / denom;
+        }
+    } catch (...) { return HPGV_ERR_NOMEM; }
+    return HPGV_OK;
+}
+
+}  // extern "C"

@@ -23,6 +23,12 @@ static int run_batch_stats_arrays(run_batch_t *b) {
 /* the per-line arrays for max_lines lines (the ones there before freed) */
 static int run_batch_lines(run_batch_t *b) {
     free(b->line_off); free(b->field_off); free(b->status); free(b->ints); free(b->dbl);
+    if (b->run->tool == RUN_CHISQ_PERM) {
+        free(b->n_ge);
+        b->n_ge = (int32_t *)malloc(sizeof(int32_t) * (size_t)b->max_lines);
+        if (!b->bmax) b->bmax = (double *)malloc(sizeof(double) * (size_t)b->run->n_perms);
+        if (!b->n_ge || !b->bmax) return HPGV_ERR_NOMEM;
+    }
     b->line_off = (uint64_t *)malloc(sizeof(uint64_t) * ((size_t)b->max_lines + 1));
     b->field_off = (uint32_t *)malloc(sizeof(uint32_t) * 10 * (size_t)b->max_lines);
     b->status = (int32_t *)malloc(sizeof(int32_t) * (size_t)b->max_lines);
@@ -55,7 +61,7 @@ int run_batch_reserve(run_batch_t *b, int lines) {
 void run_batch_free(run_batch_t *b) {
     text_buf_put(b->text, b->text_cap);
     b->text = NULL;
-    free(b->line_off); free(b->field_off); free(b->status); free(b->ints); free(b->dbl); free(b->rows);
+    free(b->line_off); free(b->field_off); free(b->status); free(b->ints); free(b->dbl); free(b->rows); free(b->n_ge); free(b->bmax);
     free(b->c8); free(b->hw); free(b->merr); free(b->midx); free(b->mtab); free(b->smiss); free(b->cerr); free(b->gc8); free(b->ghw);
     free(b->keep);
     free(b->sp_range); free(b->sp_len); free(b->sp_name); free(b->sp_names);
@@ -152,7 +158,7 @@ static int format_record(char *dst, size_t room, const run_batch_t *b, int i) {
     p = put_i64(p, A2); *p++ = '\t'; p = put_i64(p, U2); *p++ = '\t';
     p = PUT_F6(p, fa2); *p++ = '\t'; p = PUT_F6(p, fu2); *p++ = '\t';
     p = PUT_F6(p, b->dbl[i]); *p++ = '\t';                            /* odds ratio */
-    if (tool == RUN_CHISQ) { p = PUT_F6(p, b->dbl[m + i]); *p++ = '\t'; }
+    if (tool_chisq(tool)) { p = PUT_F6(p, b->dbl[m + i]); *p++ = '\t'; }
     p = PUT_F6(p, b->dbl[2 * m + i]);
     *p++ = '\n'; *p = 0;
     return (int)(p - dst);

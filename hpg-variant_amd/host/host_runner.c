@@ -114,6 +114,10 @@ static void *pipe_engine(void *v) {
                 rc = hpgv_assoc_text(g_ctx, tool, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status,
                                      b->ints, b->ints + m, b->ints + 2 * m, b->ints + 3 * m,
                                      b->dbl, tool == RUN_CHISQ ? b->dbl + m : NULL, b->dbl + 2 * m); break;
+            case RUN_CHISQ_PERM: what = "hpgv_assoc_perm_text";
+                rc = hpgv_assoc_perm_text(g_ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status,
+                                          b->ints, b->ints + m, b->ints + 2 * m, b->ints + 3 * m,
+                                          b->dbl, b->dbl + m, b->dbl + 2 * m, b->n_ge, b->bmax); break;
             }
             if (rc || b->n_lines <= b->max_lines) break;
             free(b->mtab); b->mtab = NULL;
@@ -132,10 +136,77 @@ static void *pipe_engine(void *v) {
             pthread_mutex_unlock(&P->mu);
             return NULL;
         }
+        if (tool == RUN_CHISQ_PERM) {                     /* the batch's maxima into the run's: max is order-independent */
+            double *tmax = P->run->PM->tmax;
+            for (int q = 0; q < P->run->n_perms; q++) if (b->bmax[q] > tmax[q]) tmax[q] = b->bmax[q];
+        }
         P->state[k] = B_DONE;
         pthread_cond_broadcast(&P->cv);
         pthread_mutex_unlock(&P->mu);
     }
+}
+
+/* ---- RUN_CHISQ_PERM: the records of a written batch kept for <out>.mperm, and that file ---------------------------- */
+static int run_perm_add(run_t *R, const run_batch_t *b) {
+    run_perm_t *M = R->PM;
+    const int n = b->n_lines < b->max_lines ? b->n_lines : b->max_lines, m = b->max_lines;
+    for (int i = 0; i < n; i++) {
+        if (!record_passes(b, i)) continue;
+        if (M->n == M->cap) {
+            const size_t cap = M->cap ? M->cap * 2 : 4096;
+            double *t = (double *)realloc(M->t_obs, cap * sizeof *t);
+            if (t) M->t_obs = t;
+            int32_t *g = (int32_t *)realloc(M->n_ge, cap * sizeof *g);
+            if (g) M->n_ge = g;
+            size_t *h = (size_t *)realloc(M->head, cap * sizeof *h);
+            if (h) M->head = h;
+            if (!t || !g || !h) return 1;
+            M->cap = cap;
+        }
+        const uint32_t *fo = b->field_off + 10 * (size_t)i;
+        const char *l = b->text + b->line_off[i];
+        const int lc = (int)(fo[1] - 1 - fo[0]), li = (int)(fo[3] - 1 - fo[2]);
+        const size_t need = (size_t)lc + (size_t)li + 32;
+        if (M->heads_len + need > M->heads_cap) {
+            const size_t cap = (M->heads_cap ? M->heads_cap * 2 : (size_t)1 << 16) + need;
+            char *h = (char *)realloc(M->heads, cap);
+            if (!h) return 1;
+            M->heads = h; M->heads_cap = cap;
+        }
+        M->head[M->n] = M->heads_len;                    /* CHR, POS as the result file prints it, ID */
+        M->heads_len += (size_t)snprintf(M->heads + M->heads_len, need, "%.*s\t%ld\t%.*s", lc, l + fo[0], atol(l + fo[1]), li, l + fo[2]) + 1;
+        M->t_obs[M->n] = b->dbl[m + i];
+        M->n_ge[M->n] = b->n_ge[i];
+        M->n++;
+    }
+    return 0;
+}
+
+static int run_perm_write(run_t *R, const char *out_path) {
+    run_perm_t *M = R->PM;
+    double *emp = (double *)malloc(sizeof(double) * 2 * (M->n + 1));
+    char *path = (char *)malloc(strlen(out_path) + 8);
+    int rc = emp && path ? HPGV_OK : HPGV_ERR_NOMEM;
+    if (!rc && (rc = hpgv_perm_pvalues(M->t_obs, (int)M->n, M->n_ge, M->tmax, R->n_perms, emp, emp + M->n))) snprintf(g_err, sizeof g_err, "hpgv_perm_pvalues failed (%d)", rc);
+    FILE *f = NULL;
+    if (!rc) {
+        sprintf(path, "%s.mperm", out_path);
+        if (!(f = fopen(path, "wb"))) { snprintf(g_err, sizeof g_err, "cannot create %s", path); rc = HPGV_ERR_INVALID; }
+    }
+    if (!rc) {
+        setvbuf(f, NULL, _IOFBF, 1u << 20);
+        fputs("#CHR\tPOS\tID\tEMP1\tEMP2\n", f);
+        char num[2][320];
+        for (size_t i = 0; i < M->n; i++) {
+            hpgv_host_format_f6(emp[i], num[0]); hpgv_host_format_f6(emp[M->n + i], num[1]);
+            fprintf(f, "%s\t%s\t%s\n", M->heads + M->head[i], num[0], num[1]);
+        }
+        if (fclose(f) != 0) { snprintf(g_err, sizeof g_err, "cannot write %s", path); rc = HPGV_ERR_INVALID; }
+        /* the same order as the result file: by chromosome and position (a file in order as written is left alone) */
+        else if (hpgv_host_sort_output_file(path)) fprintf(stderr, "WARN: %s could not be sorted by chromosome and position\n", path);
+    }
+    free(emp); free(path);
+    return rc;
 }
 
 /* ---- one run, stage by stage: input (in run_file), cohort, outputs, pipeline, finish ---------------------- */
@@ -239,7 +310,7 @@ static int run_cohort(run_t *R, const char *vcf_path, const char *ped_path) {
         free(fcol); free(mcol); free(coff); free(ccol); free(csex); free(done);
         break;
     }
-    case RUN_CHISQ: case RUN_FISHER: case RUN_VCF2EPI: {
+    case RUN_CHISQ: case RUN_CHISQ_PERM: case RUN_FISHER: case RUN_VCF2EPI: {
         uint8_t *cond = (uint8_t *)malloc((size_t)n_samples + 1);
         for (int j = 0; j < n_samples; j++) cond[j] = HPGV_COND_OTHER;
         int matched = 0;
@@ -256,6 +327,13 @@ static int run_cohort(run_t *R, const char *vcf_path, const char *ped_path) {
         }
         if (!rc && (rc = hpgv_set_cohort(g_ctx, cond, n_samples))) host_fail("hpgv_set_cohort", rc);
         g_assoc_key.set = 0;
+        if (!rc && R->tool == RUN_CHISQ_PERM) {          /* the run's label rows, once: shuffles of the PED's conditions */
+            uint8_t *labels = (uint8_t *)malloc((size_t)R->n_perms * (size_t)(n_samples > 0 ? n_samples : 1));
+            if (!labels) rc = HPGV_ERR_NOMEM;
+            if (!rc && (rc = hpgv_perm_labels_shuffle(cond, n_samples, R->n_perms, R->perm_seed, labels))) host_fail("hpgv_perm_labels_shuffle", rc);
+            if (!rc && (rc = hpgv_set_perm_labels(g_ctx, labels, R->n_perms))) host_fail("hpgv_set_perm_labels", rc);
+            free(labels);
+        }
         free(cond);
         if (!rc && R->tool == RUN_FISHER) {
             double *lf = init_logarithm_array(n_samples * 10 > 16 ? n_samples * 10 : 16);     /* assoc_runner.c:164-166 */
@@ -279,7 +357,7 @@ static int run_cohort(run_t *R, const char *vcf_path, const char *ped_path) {
     /* --inh-dom / --inh-rec scan the assoc layout: the tools that have not installed it get it from the PED (PHENO 2
      * affected, 1 unaffected, as the assoc runner); vcf2epi keeps its own classes */
     if (!rc && rec_filters_inheritance(R->rf)) {
-        if (R->tool != RUN_CHISQ && R->tool != RUN_FISHER && R->tool != RUN_VCF2EPI) {
+        if (!tool_chisq(R->tool) && R->tool != RUN_FISHER && R->tool != RUN_VCF2EPI) {
             uint8_t *cond = (uint8_t *)malloc((size_t)n_samples + 1);
             if (!cond) rc = HPGV_ERR_NOMEM;
             for (int j = 0; cond && j < n_samples; j++) cond[j] = HPGV_COND_OTHER;
@@ -391,6 +469,11 @@ static int create_out(FILE **f, char **path, const char *prefix, const char *suf
 /* the tool's output files (split: its files as the records come).  The filter tool's .rejected is created empty without
  * save_rejected (filter_runner.c:63-68); stats: one file per phenotype (stats_runner.c:267-297), and its accumulator */
 static int run_outputs(run_t *R, const char *out_path) {
+    if (R->tool == RUN_CHISQ_PERM) {
+        R->PM = (run_perm_t *)calloc(1, sizeof *R->PM);
+        if (R->PM) R->PM->tmax = (double *)calloc((size_t)R->n_perms, sizeof(double));      /* 0: the identity of the merge */
+        if (!R->PM || !R->PM->tmax) return HPGV_ERR_NOMEM;
+    }
     const char *suffix = R->tool == RUN_STATS ? ".stats-variants" : R->tool == RUN_FILTER ? (R->out_bgzf ? ".filtered.gz" : ".filtered") : "";
     int rc = R->tool == RUN_SPLIT ? HPGV_OK : create_out(&R->out, &R->path, out_path, suffix);
     if (!rc && R->tool == RUN_FILTER) rc = create_out(&R->out_rej, &R->path_rej, out_path, R->out_bgzf ? ".rejected.gz" : ".rejected");
@@ -415,9 +498,9 @@ static int run_outputs(run_t *R, const char *out_path) {
 static int run_headers(run_t *R) {
     FILE *out = R->out;
     switch (R->tool) {
-    case RUN_CHISQ: case RUN_FISHER: {
-        assoc_write_output_header((enum ASSOC_task)R->tool, out);
-        const char *h = R->tool == RUN_CHISQ ? "#CHR\tPOS\tID\tA1\tC_A1\tC_U1\tF_A1\tF_U1\tA2\tC_A2\tC_U2\tF_A2\tF_U2\tOR\tCHISQ\tP-VALUE"
+    case RUN_CHISQ: case RUN_CHISQ_PERM: case RUN_FISHER: {
+        assoc_write_output_header(tool_chisq(R->tool) ? CHI_SQUARE : FISHER, out);
+        const char *h = tool_chisq(R->tool) ? "#CHR\tPOS\tID\tA1\tC_A1\tC_U1\tF_A1\tF_U1\tA2\tC_A2\tC_U2\tF_A2\tF_U2\tOR\tCHISQ\tP-VALUE"
                                              : "#CHR\tPOS\tID\tA1\tC_A1\tC_U1\tF_A1\tF_U1\tA2\tC_A2\tC_U2\tF_A2\tF_U2\tOR\tP-VALUE";
         order_track_keep(&R->ord, h, strlen(h));
         return HPGV_OK;
@@ -522,9 +605,10 @@ static int run_pipeline(run_t *R, size_t batch_bytes) {
                 if (write_split_batch(R, b)) bad = g_err;          /* (what split_file said) */
                 R->written += b->n_pass; R->skipped += b->n_skip;
                 break;
-            case RUN_CHISQ: case RUN_FISHER: case RUN_TDT: case RUN_VCF2EPI: case RUN_AGGREGATE: case RUN_STATS:
+            case RUN_CHISQ: case RUN_CHISQ_PERM: case RUN_FISHER: case RUN_TDT: case RUN_VCF2EPI: case RUN_AGGREGATE: case RUN_STATS:
                 if (write_batch(R->out, b, fmt + (fmt_set ? RUN_FMT_BUFS / 2 : 0), n_fmt, &wpool, &R->ord, use_fw ? &fw : NULL)) bad = "cannot write the result file";
                 for (int i = 0; i < b->n_lines; i++) if (record_passes(b, i)) R->written++;
+                if (R->tool == RUN_CHISQ_PERM && !bad && run_perm_add(R, b)) bad = "out of memory for the permutation results";
                 if (R->tool == RUN_STATS && !bad) { run_stats_add(R, b); if (R->gfd) write_group_lines(R->gfd, b); }      /* (the group files: by this thread) */
                 break;
             }
@@ -579,6 +663,11 @@ static int run_finish(run_t *R, int rc, const char *out_path) {
         R->t_sort = now_s() - t0;
     }
     if (R->tool == RUN_STATS && !rc) rc = run_stats_write(R, out_path);
+    if (R->tool == RUN_CHISQ_PERM) {
+        if (!rc && R->PM) rc = run_perm_write(R, out_path);
+        if (g_ctx) (void)hpgv_set_perm_labels(g_ctx, NULL, 0);
+        if (R->PM) { free(R->PM->tmax); free(R->PM->t_obs); free(R->PM->n_ge); free(R->PM->head); free(R->PM->heads); free(R->PM); R->PM = NULL; }
+    }
     if (R->RS) { free(R->RS->smiss); free(R->RS->serr); free(R->RS); }
     free(R->ord.last); free(R->gfd); free(R->group_names); free(R->path); free(R->path_rej); free(R->trio_child);
     const hpgv_run_filters_t *f = &R->filters;
@@ -610,7 +699,7 @@ static int run_file_held(run_t *R, const char *vcf_path, const char *ped_path, c
     if (rc) return rc;
     if (batch_bytes < (1u << 16)) batch_bytes = 1u << 16;
     const run_tool_t tool = R->tool; R->io_threads = default_io_threads();      /* the input: the PED (assoc, TDT, vcf2epi), the VCF's header */
-    if (!ped_path && (tool == RUN_CHISQ || tool == RUN_FISHER || tool == RUN_TDT || tool == RUN_VCF2EPI)) { snprintf(g_err, sizeof g_err, "this runner needs a PED file (ped_path is NULL)"); return HPGV_ERR_INVALID; }
+    if (!ped_path && (tool_chisq(tool) || tool == RUN_FISHER || tool == RUN_TDT || tool == RUN_VCF2EPI)) { snprintf(g_err, sizeof g_err, "this runner needs a PED file (ped_path is NULL)"); return HPGV_ERR_INVALID; }
     if (ped_path && (rc = ped_table_read(ped_path, &R->ped))) return rc;
     if (source_open(&R->rd.src, vcf_path)) { ped_table_free(&R->ped); snprintf(g_err, sizeof g_err, "cannot open VCF file %s", vcf_path); return HPGV_ERR_INVALID; }
     R->t_opened = now_s();
@@ -687,6 +776,15 @@ int hpgv_run_assoc(const char *vcf_path, const char *ped_path, const char *out_p
                    size_t batch_bytes, long *n_variants_out) {
     if (task != CHI_SQUARE && task != FISHER) { snprintf(g_err, sizeof g_err, "task must be CHI_SQUARE or FISHER"); return HPGV_ERR_INVALID; }
     return run_file(&(run_t){ .tool = (run_tool_t)task, .filters = g_filters }, vcf_path, ped_path, out_path, batch_bytes, n_variants_out);
+}
+
+/* the chi-square run with max(T) label permutation: hpgv_run_assoc(..., CHI_SQUARE, ...)'s file and <out_path>.mperm */
+int hpgv_run_assoc_perm(const char *vcf_path, const char *ped_path, const char *out_path, int n_perms, uint64_t seed,
+                        size_t batch_bytes, long *n_variants_out) {
+    if (n_variants_out) *n_variants_out = 0;
+    if (!vcf_path || !ped_path || !out_path) { snprintf(g_err, sizeof g_err, "vcf_path, ped_path and out_path must not be NULL"); return HPGV_ERR_INVALID; }
+    if (n_perms < 1) { snprintf(g_err, sizeof g_err, "n_perms must be at least 1"); return HPGV_ERR_INVALID; }
+    return run_file(&(run_t){ .tool = RUN_CHISQ_PERM, .filters = g_filters, .n_perms = n_perms, .perm_seed = seed }, vcf_path, ped_path, out_path, batch_bytes, n_variants_out);
 }
 
 int hpgv_run_tdt(const char *vcf_path, const char *ped_path, const char *out_path, size_t batch_bytes, long *n_variants_out) {

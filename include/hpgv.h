@@ -225,6 +225,37 @@ int  hpgv_assoc_chisq_dev(hpgv_ctx *ctx, const int32_t *d_counts, int n_variants
 int  hpgv_assoc_fisher_dev(hpgv_ctx *ctx, const int32_t *d_counts, int n_variants,
                            double *d_odds, double *d_p, void *stream);
 
+/* ---- label permutation of the chi-square association test: max(T) empirical p-values (PLINK's --mperm; no reference
+ *      counterpart).  For a 0/1 labelling p of the COHORT columns (those whose condition in hpgv_set_cohort is AFFECTED or
+ *      UNAFFECTED; HPGV_COND_OTHER columns take no part under any labelling) the permuted counts are
+ *          A1_p(v) = sum_j c1(v, j) y_p(j),   A2_p(v) = sum_j c2(v, j) y_p(j)
+ *      with the per-sample contributions (c1, c2) of column j's HPGV8 byte
+ *          autosome: c1 = nibbles equal to 0, c2 = nibbles that are neither 0 nor 0xF       (0xFF: 0, 0)
+ *          chr X   : c1 = 1 for byte 0x00, c2 = 1 for a byte whose nibbles are both neither 0 nor 0xF
+ *      (summed over the affected columns they are hpgv_assoc_scan_dev's {A1, A2}, over the unaffected ones {U1, U2}): an i8
+ *      matrix product with exact i32 sums on the matrix cores (csrc/hpgv_assoc_perm_kernels.h).  The permuted table is
+ *      a = A1_p, c = A2_p, b = R1 - A1_p, d = R2 - A2_p with R1 = A1 + U1, R2 = A2 + U2 of the observed counts;
+ *      T_p(v) is the chi-square of that table by the device function hpgv_assoc_chisq_dev uses, T_obs(v) the same on the
+ *      observed counts.  A NaN T_p(v) (an empty margin) is never >= anything and never enters a maximum.  Outputs per call:
+ *          n_ge[v]      = #{p : T_p(v) >= T_obs(v)}  (int32; 0 when T_obs(v) is NaN)
+ *          batch_max[p] = max over the call's variants of T_p(v)  (0.0 when every value is NaN or the call has no variants)
+ *      Calls are stateless: a scan in several batches sums nothing and merges batch_max by element-wise maximum (0 is the
+ *      identity: chi-square is never negative); hpgv_perm_pvalues turns the merged maxima into p-values. */
+/* labels[p * n_samples + j] in {0, 1} for VCF column j (ignored for HPGV_COND_OTHER columns), one row per permutation; a row
+ * need not keep the number of affected samples.  After hpgv_set_cohort (else HPGV_ERR_STATE); a group context gives every
+ * member the labels, as it does the cohort.  n_perms == 0 drops the labels; so does a new hpgv_set_cohort.  A value above 1
+ * in a cohort column: HPGV_ERR_INVALID.  Limits: more than 1 048 576 permutations per call is HPGV_ERR_UNSUPPORTED; the label
+ * matrix takes (n_perms rounded up to 16) x the assoc layout's pitch bytes of device memory and HPGV_ERR_NOMEM is returned
+ * when they are not there.  Not to be called while permutation calls of the context are in flight. */
+int  hpgv_set_perm_labels(hpgv_ctx *ctx, const uint8_t *labels, int n_perms);
+/* d_gt in assoc layout, d_counts what hpgv_assoc_scan_dev wrote for it -> d_n_ge (n_variants int32), d_batch_max (n_perms
+ * doubles), both overwritten.  d_perm_counts (may be NULL; for tests and for callers who want another statistic):
+ * {A1_p, A2_p} as int32[(v * n_perms + p) * 2 + k].  d_gt and d_counts 16-byte aligned, d_batch_max and d_perm_counts
+ * 8-byte aligned.  Asynchronous on `stream`.  HPGV_ERR_STATE without labels.  The launch reads the genotype matrix
+ * ceil(n_perms / 128) times. */
+int  hpgv_assoc_perm_dev(hpgv_ctx *ctx, const uint8_t *d_gt, int n_variants, const uint8_t *d_is_x, const int32_t *d_counts,
+                         int32_t *d_n_ge, double *d_batch_max, int32_t *d_perm_counts /* may be NULL */, void *stream);
+
 /* d_gt in tdt layout -> d_tu[v] = {t1, t2} (int32 x2) */
 int  hpgv_tdt_scan_dev(hpgv_ctx *ctx, const uint8_t *d_gt, int n_variants,
                        const uint8_t *d_is_x, int32_t *d_tu, void *stream);
@@ -338,6 +369,12 @@ int  hpgv_assoc(hpgv_ctx *ctx, int task, const uint8_t *gt, size_t pitch, int n_
                 const uint8_t *is_x,
                 int32_t *A1, int32_t *A2, int32_t *U1, int32_t *U2,
                 double *odds, double *chisq, double *p);
+/* hpgv_assoc with task CHISQ plus the label permutation's two outputs ("label permutation" above): n_ge (n_variants
+ * int32) and batch_max (n_perms doubles of the labels set with hpgv_set_perm_labels, overwritten).  Synchronous and
+ * thread-safe; a group context deals it to its members as hpgv_assoc.  HPGV_ERR_STATE without labels. */
+int  hpgv_assoc_perm(hpgv_ctx *ctx, const uint8_t *gt, size_t pitch, int n_variants, const uint8_t *is_x,
+                     int32_t *A1, int32_t *A2, int32_t *U1, int32_t *U2,
+                     double *odds, double *chisq, double *p, int32_t *n_ge, double *batch_max);
 int  hpgv_tdt(hpgv_ctx *ctx, const uint8_t *gt, size_t pitch, int n_variants,
               const uint8_t *is_x, int32_t *t1, int32_t *t2,
               double *odds, double *chisq, double *p);
@@ -692,9 +729,33 @@ int  hpgv_assoc_text(hpgv_ctx *ctx, int task, const char *text, size_t text_byte
                      uint64_t *line_off, uint32_t *field_off, int32_t *status,
                      int32_t *A1, int32_t *A2, int32_t *U1, int32_t *U2,
                      double *odds, double *chisq, double *p);
+/* hpgv_assoc_text with task CHISQ plus n_ge (sized max_lines) and batch_max (n_perms doubles, overwritten): tokenizer,
+ * HPGV_LAYOUT_ASSOC layout, scan, chi-square, then the permutation kernel.  The lines a caller of hpgv_assoc_text drops --
+ * status 1 (not a record) and lines a record filter rejected (HPGV_LINE_FILTERED) -- take no part in batch_max and get
+ * n_ge = 0. */
+int  hpgv_assoc_perm_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, int max_lines, int *n_lines,
+                          uint64_t *line_off, uint32_t *field_off, int32_t *status,
+                          int32_t *A1, int32_t *A2, int32_t *U1, int32_t *U2,
+                          double *odds, double *chisq, double *p, int32_t *n_ge, double *batch_max);
 int  hpgv_tdt_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, int max_lines, int *n_lines,
                    uint64_t *line_off, uint32_t *field_off, int32_t *status,
                    int32_t *t1, int32_t *t2, double *odds, double *chisq, double *p);
+
+/* ---- label permutation, host side: no GPU call, no context, usable without a device ------------------------------- */
+/* n_perms label rows for hpgv_set_perm_labels, labels_out[p * n_samples + j]: row p is a uniform shuffle of the cohort
+ * columns' conditions (1 = affected), so every row has as many ones as the cohort has affected samples; HPGV_COND_OTHER
+ * columns get 0.  Deterministic in (seed, p): the generator is counter-based, SplitMix64 (Steele, Lea and Flood 2014;
+ * mix(z): z += 0x9E3779B97F4A7C15, z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9, z = (z ^ z >> 27) * 0x94D049BB133111EB,
+ * z ^ z >> 31): row p's key is mix(seed ^ mix(p)), its draw number i is mix(key + i), i = 0, 1, ...  Fisher-Yates over the
+ * cohort columns in VCF order, from the last position down: position k - 1 swaps with position (draw * k) >> 64, k = n .. 2. */
+int  hpgv_perm_labels_shuffle(const uint8_t *condition, int n_samples, int n_perms, uint64_t seed, uint8_t *labels_out);
+/* With P = n_perms permutations, t_max the element-wise maximum of every batch's batch_max (in any order; it is sorted here
+ * and each variant's rank found by binary search):
+ *     emp1[v] = (n_ge[v] + 1) / (P + 1)                           pointwise
+ *     emp2[v] = (#{p : t_max[p] >= t_obs[v]} + 1) / (P + 1)       family-wise, max(T)
+ * both NaN where t_obs[v] is NaN.  n_perms < 1: HPGV_ERR_INVALID. */
+int  hpgv_perm_pvalues(const double *t_obs, int n_variants, const int32_t *n_ge, const double *t_max, int n_perms,
+                       double *emp1, double *emp2);
 
 /* streaming-read ceiling probe: reads `bytes` from d_buf with the scan's load
  * shape and no arithmetic; returns the kernel time in ms (diagnostic) */

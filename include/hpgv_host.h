@@ -291,6 +291,18 @@ int  hpgv_run_assoc(const char *vcf_path, const char *ped_path, const char *out_
                     enum ASSOC_task task, size_t batch_bytes, long *n_variants_out);
 int  hpgv_run_tdt(const char *vcf_path, const char *ped_path, const char *out_path,
                   size_t batch_bytes, long *n_variants_out);
+/* hpgv_run_assoc(..., CHI_SQUARE, ...) with max(T) label permutation (include/hpgv.h "label permutation"; PLINK's --mperm):
+ * out_path is written byte for byte as there, and <out_path>.mperm beside it: the header line "#CHR\tPOS\tID\tEMP1\tEMP2",
+ * then one line per written variant in the same sorted order -- EMP1 the pointwise empirical p-value, EMP2 the family-wise
+ * one from the per-permutation maximum over every record of the file the engine scanned (a record that only a host-side field
+ * filter drops still takes part; lines the engine's own record filters reject do not); numbers as hpgv_host_format_f6 prints them
+ * (NaN as in the result file).  The n_perms label rows are generated once per run by hpgv_perm_labels_shuffle(seed) from the
+ * PED's conditions; every batch goes through hpgv_assoc_perm_text and its maxima are merged into the run's by element-wise
+ * maximum, so the result depends neither on batch_bytes nor on the number of engine threads or devices.  Same cohort, filters,
+ * record filters and input forms (plain, gzip, bgzip) as hpgv_run_assoc.  n_perms < 1 or a NULL path: HPGV_ERR_INVALID before
+ * the engine is started, and no file is written. */
+int  hpgv_run_assoc_perm(const char *vcf_path, const char *ped_path, const char *out_path, int n_perms, uint64_t seed,
+                         size_t batch_bytes, long *n_variants_out);
 /* record filters of the file-level runners (filter_records on every batch, assoc_runner.c:191; options
  * shared_options.c:42-47,86-115).  A negative member switches that filter off; NULL switches all off.  The
  * count-derived ones run on the GPU from the same tokenized batch:
