@@ -175,6 +175,13 @@ void hpgv_destroy(hpgv_ctx *ctx) {
 
 int hpgv_set_option(hpgv_ctx *ctx, const char *key, long value) {
     if (is_group(ctx) && key && !strcmp(key, "group_self_exchange")) { ctx->group_self_exchange = value ? 1 : 0; return HPGV_OK; }
+    if (is_group(ctx) && key && !strcmp(key, "group_fake_ranks")) {
+        if (value < 0 || value > 65536) return fail(ctx, HPGV_ERR_INVALID, "group_fake_ranks must be 0 (ranks by distinct device) or the number of members that share rank 0");
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (ctx->grp) return fail(ctx, HPGV_ERR_STATE, "group_fake_ranks must be set before the group's communicator exists (hpgv_group_comm_init, the first group call)");
+        ctx->group_fake_ranks = value;
+        return HPGV_OK;
+    }
     GROUP_ALL(ctx, hpgv_set_option(m_, key, value))
     if (!ctx || !key) return HPGV_ERR_INVALID;
     if (!strcmp(key, "row_align")) {

@@ -17,6 +17,12 @@
 //   group_scan the skeleton of hpgv_group_assoc / _tdt / _stats: an entry point brings its checks, its piece table and
 //              what one member queues on its scan stream
 //
+// What has run where: RCCL itself at ONE rank only (the one-GPU test rig: every context on device 0 is rank 0, members 1 and
+// up take the local copy).  The exchange logic -- which communicator, which peer, which offset, several senders in one
+// group, the reduce over several ranks beside local adds -- has been executed at two to eight ranks over a stand-in
+// communicator (tests/c/fake_rccl.hip through HPGV_RCCL_LIB, ranks dealt by the test switch group_fake_ranks).  Several
+// GPUs are still unmeasured on hardware.
+//
 // librccl is loaded with dlopen when the communicator is first asked for: libhpgv.so itself has no RCCL dependency, a
 // single-device user never loads it, and inside a process that already holds an RCCL (torch's) the same copy is used.
 //
@@ -380,14 +386,23 @@ int counters_reduce(Plan &P, int32_t *d_total, int n_samples) {
     return HPGV_OK;
 }
 
-// ranks = the distinct devices in member order (a device may repeat only when it is member 0's), the communicator over
-// them, and every member's streams and events.  What a failure leaves behind, hpgv_group_release takes down.
+// ranks = the distinct devices in member order (a device may repeat only when it is member 0's; the test switch
+// group_fake_ranks deals ranks by member instead), the communicator over them, and every member's streams and events.
+// What a failure leaves behind, hpgv_group_release takes down.
 int comm_setup(hpgv_ctx *g, GroupState *S) {
     const int G = (int)g->members.size();
     S->devs.clear();
     S->m.assign((size_t)G, GroupMember());
+    // the test switch group_fake_ranks = n: the first n members share rank 0, every later member is a rank of its own in
+    // member order, and the device list has one entry per rank -- repeated devices, which only a stand-in communicator takes
+    const int shared = (int)std::min<long>(g->group_fake_ranks, G);
     for (int k = 0; k < G; ++k) {
         const int dev = g->members[(size_t)k]->device;
+        if (shared > 0) {
+            S->m[(size_t)k].rank = k < shared ? 0 : k - shared + 1;
+            if (k == 0 || k >= shared) S->devs.push_back(dev);
+            continue;
+        }
         int r = -1;
         for (size_t i = 0; i < S->devs.size(); ++i) if (S->devs[i] == dev) r = (int)i;
         if (r > 0) return fail(g, HPGV_ERR_UNSUPPORTED, "device %d is listed twice and is not member 0's: only member 0's device may repeat (the one-GPU test rig)", dev);

@@ -177,6 +177,7 @@ struct hpgv_ctx {
     hpgv_ctx *parent = nullptr;
     struct GroupState *grp = nullptr;   // streams, scratch and the RCCL communicator of the group-wide resident scans (hpgv_group_capi.hip)
     long group_self_exchange = 0;       // test switch: member 0 also hands its results over through the communicator (send / recv to itself)
+    long group_fake_ranks = 0;          // test switch, read in comm_setup only: n >= 1 = the first n members share rank 0, every later member is a rank of its own
     std::atomic<unsigned> deal_next{0};
     std::atomic<int> in_flight{0};
     int device = 0;

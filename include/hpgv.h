@@ -105,6 +105,11 @@ const char *hpgv_last_error(const hpgv_ctx *ctx);
  *                                    measurement).  On a group context the option goes to every member.  hpgv_run_epistasis[_order] of
  *                                    the host library set 1 for their run.
  *   "group_self_exchange" 0/1    (group contexts; tests) member 0 hands its results over through the communicator too
+ *   "group_fake_ranks" n         (group contexts; tests) 0 (default): communicator ranks by distinct device.  n >= 1: the first n
+ *                                members share rank 0 and every later member is a rank of its own, whatever its device, so the
+ *                                device list handed to ncclCommInitAll may repeat a device -- which RCCL refuses and only a
+ *                                stand-in communicator (HPGV_RCCL_LIB) accepts.  Before the communicator exists
+ *                                (hpgv_group_comm_init or the first group call); afterwards HPGV_ERR_STATE
  *   "part_aligned_loads" 0/1     hpgv_lines_partition_dev: the source of a granule by two aligned loads and v_alignbyte
  *                                (ablation build) instead of one unaligned dwordx4 load (shipped: 0)
  * Every kernel ships in ONE form.  The forms that lost their A/B comparisons (profiles/experiments_that_did_not_pay.md) are

@@ -1,13 +1,15 @@
 /* group_epi.c -- a C host deals the epistasis scan to the members of a group context (hpgv_group_epi_rank), the way the
  * reference deals block coordinates to its workers (singlenode/epistasis_runner.c:114-145).
  *
- *   group_epi <n_members> <n_variants> <n_affected> <n_unaffected> <num_folds> <order> [self]
+ *   group_epi <n_members> <n_variants> <n_affected> <n_unaffected> <num_folds> <order> [self] [ranks=<n>]
  *
  * A group of n_members contexts, ALL on device 0 (what a one-GPU box can do).  A seeded vcf2epi dataset and fold assignment
  * go to the group (every member receives them); the group's ranking must be BIT-IDENTICAL to the ranking one ordinary
  * context makes of the whole dataset (hpgv_epi_rank_pairs / hpgv_epi_rank_triples / hpgv_epi_rank_order), for both
  * evaluation subsets.  "self": member 0's list goes through ncclSend / ncclRecv to itself, so a one-member group moves its
- * records through RCCL.  The shares are printed: they tile [0, V) and, for pairs, start on multiples of 64. */
+ * records through RCCL.  The shares are printed: they tile [0, V) and, for pairs, start on multiples of 64.
+ * "ranks=<n>" (with a stand-in communicator in HPGV_RCCL_LIB): the test switch group_fake_ranks, as in group_scan.c -- the
+ * lists of the members past the first n reach member 0 through the communicator, and the rank count must fit. */
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -29,12 +31,18 @@ static hpgv_ctx *g, *one;
 int main(int argc, char **argv) {
     if (argc < 7) { fprintf(stderr, "usage: group_epi n_members n_variants n_affected n_unaffected num_folds order [self]\n"); return 2; }
     const int G = atoi(argv[1]), V = atoi(argv[2]), nA = atoi(argv[3]), nU = atoi(argv[4]), K = atoi(argv[5]), order = atoi(argv[6]);
-    const int self = argc > 7 && !strcmp(argv[7], "self");
-    if (G < 1 || G > 16 || V < 1 || nA < 1 || nU < 1 || K < 1 || K > 16) return 2;
+    int self = 0, fake = 0;
+    for (int a = 7; a < argc; ++a) {
+        if (!strcmp(argv[a], "self")) self = 1;
+        else if (!strncmp(argv[a], "ranks=", 6)) fake = atoi(argv[a] + 6);
+        else return 2;
+    }
+    if (G < 1 || G > 16 || V < 1 || nA < 1 || nU < 1 || K < 1 || K > 16 || fake < 0) return 2;
     int ids[16] = {0};
     CHECK(hpgv_create_multi(ids, G, &g));
     CHECK(hpgv_create(0, &one));
     if (self) CHECK(hpgv_set_option(g, "group_self_exchange", 1));
+    if (fake) CHECK(hpgv_set_option(g, "group_fake_ranks", fake));
 
     const int n = nA + nU, N = 24;
     uint8_t *data = malloc((size_t)V * (size_t)n);
@@ -92,6 +100,7 @@ int main(int argc, char **argv) {
         printf("subset %d: ranking bit-identical (%d folds, top model of fold 0: accuracy %.6f)\n", subset, K, gn[0] ? ga[0] : -1.0);
     }
     printf("rccl_ranks=%d\n", hpgv_group_comm_ranks(g));
+    if (fake && hpgv_group_comm_ranks(g) != G - (fake < G ? fake : G) + 1) { fprintf(stderr, "expected a communicator of %d ranks\n", G - (fake < G ? fake : G) + 1); bad = 1; }
     if (!bad) printf("group epistasis ok: %d member(s), %d SNPs, order %d\n", G, V, order);
     hpgv_destroy(g);
     hpgv_destroy(one);

@@ -1,14 +1,17 @@
 /* group_scan.c -- a C host drives the variant-sharded resident scan of a group context (hpgv_group_*), the way a C
  * runner would (the reference's runners are C: assoc_runner.c:106-207, tdt_runner.c:150-200, stats_runner.c:176-215).
  *
- *   group_scan <n_members> <n_variants> <n_samples> [self]
+ *   group_scan <n_members> <n_variants> <n_samples> [self] [ranks=<n>]
  *
  * A group of n_members contexts, ALL on device 0 (what a one-GPU box can do; on a node with several GPUs the ids would
  * differ and the hand-over would run over xGMI).  Every member's shard of a synthetic cohort is generated on its device
  * (hpgv_synth_dev with the shard's first variant id), the group scan runs twice (two generations of scratch), and all
  * results on member 0 must be BIT-IDENTICAL to one ordinary context scanning all variants.  "self": member 0 hands its own
  * results over through the communicator too (ncclSend / ncclRecv to itself), so a one-member group exercises RCCL.
- * The communicator is really created (ncclCommInitAll): hpgv_group_comm_ranks must say 1 here. */
+ * The communicator is really created (ncclCommInitAll): hpgv_group_comm_ranks must say 1 here.
+ * "ranks=<n>" (n >= 1; with a stand-in communicator in HPGV_RCCL_LIB, RCCL refuses a device twice): the test switch
+ * group_fake_ranks -- the first n members share rank 0, every later member is a rank of its own and hands over through the
+ * communicator; hpgv_group_comm_ranks must then say n_members - min(n, n_members) + 1. */
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -43,12 +46,19 @@ int main(int argc, char **argv) {
     const int G = atoi(argv[1]);
     const int64_t V = atoll(argv[2]);
     const int N = atoi(argv[3]);
-    const int self = argc > 4 && !strcmp(argv[4], "self");
-    if (G < 1 || G > 16 || V < 0 || N < 3) return 2;
+    int self = 0, fake = 0;
+    for (int a = 4; a < argc; ++a) {
+        if (!strcmp(argv[a], "self")) self = 1;
+        else if (!strncmp(argv[a], "ranks=", 6)) fake = atoi(argv[a] + 6);
+        else return 2;
+    }
+    if (G < 1 || G > 16 || V < 0 || N < 3 || fake < 0) return 2;
+    const int want_ranks = fake ? G - (fake < G ? fake : G) + 1 : 1;
     int ids[16] = {0};
     CHECK(hpgv_create_multi(ids, G, &g));
     CHECK(hpgv_create(0, &one));
     if (self) CHECK(hpgv_set_option(g, "group_self_exchange", 1));
+    if (fake) CHECK(hpgv_set_option(g, "group_fake_ranks", fake));
 
     /* cohort: odd samples are cases; trio k = columns (3k, 3k+1, 3k+2) */
     uint8_t *cond = malloc((size_t)N), *sex = malloc((size_t)N);
@@ -71,7 +81,7 @@ int main(int argc, char **argv) {
     CHECK(hpgv_group_comm_init(g));
     const int ranks = hpgv_group_comm_ranks(g);
     printf("members=%d rccl_ranks=%d self_exchange=%d\n", hpgv_group_size(g), ranks, self);
-    if (ranks != 1) { fprintf(stderr, "expected a 1-rank communicator over device 0\n"); return 1; }
+    if (ranks != want_ranks) { fprintf(stderr, fake ? "expected a communicator of %d ranks\n" : "expected a 1-rank communicator over device 0\n", want_ranks); return 1; }
 
     int bad = 0;
     for (int which = 0; which < 3; ++which) {              /* HPGV_LAYOUT_ASSOC, _TDT, _STATS */

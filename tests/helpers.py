@@ -33,6 +33,25 @@ def set_or_skip(engine, key, value):
         raise
 
 
+def build_fake_rccl(outdir):
+    """tests/c/fake_rccl.hip -> <outdir>/libfake_rccl.so with the library's own hipcc flags: the stand-in communicator that
+    HPGV_RCCL_LIB hands to libhpgv.so for the multi-rank hand-over tests.  A version script keeps its exports to the symbols
+    libhpgv.so resolves (RCCL_SYMBOLS in csrc/hpgv_group_capi.hip).  Returns (path, those symbol names)."""
+    import os
+    import re
+    import subprocess
+    b = importlib.import_module("hpg-variant_amd._build")
+    unit = open(os.path.join(b.CSRC, "hpgv_group_capi.hip")).read()
+    names = ["nccl" + n for n in re.findall(r"X\((\w+)\)", re.search(r"#define RCCL_SYMBOLS\(X\)(.*)", unit).group(1))]
+    vmap = os.path.join(str(outdir), "fake_rccl.map")
+    with open(vmap, "w") as f:
+        f.write("{ global: %s; local: *; };\n" % "; ".join(names))
+    lib = os.path.join(str(outdir), "libfake_rccl.so")
+    subprocess.check_call([b._hipcc()] + b.HIPCC_FLAGS + ["-Wl,--version-script=" + vmap, "-o", lib,
+                                                         os.path.join(b.ROOT, "tests", "c", "fake_rccl.hip")])
+    return lib, names
+
+
 TOL = 1e-10   # north_star: chi2 / Fisher / HWE p-values within 1e-10 of the reference path
 
 

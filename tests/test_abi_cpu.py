@@ -68,6 +68,27 @@ def test_rccl_loader_survives_a_wrong_library_path():
             assert "/nonexistent/librccl.so" in r.stdout      # the failed candidate is named in the message
 
 
+def test_rccl_probe_accepts_the_stand_in_communicator(tmp_path):
+    """tests/c/fake_rccl.hip, built as the GPU tests' fixture builds it, offers every symbol the group scan resolves
+    (RCCL_SYMBOLS) and exports nothing else: hpgv_group_rccl_probe with HPGV_RCCL_LIB set to it says HPGV_OK.  Own process:
+    the environment is the child's."""
+    from helpers import build_fake_rccl
+    lib, names = build_fake_rccl(tmp_path)
+    assert len(names) == 9
+    exported = subprocess.run(["nm", "-D", "--defined-only", lib], capture_output=True, text=True, check=True).stdout
+    assert sorted(line.split()[-1] for line in exported.splitlines() if line.strip()) == sorted(names)
+    code = ("import importlib, ctypes as C, sys; sys.path.insert(0, %r); h = importlib.import_module('hpg-variant_amd'); "
+            "L = h.load(); b = C.create_string_buffer(2048); rc = L.hpgv_group_rccl_probe(b, 2048); "
+            "print(rc, b.value.decode()); sys.exit(0 if rc == h.OK else 3)" % ROOT)
+    r = subprocess.run([os.sys.executable, "-c", code], env=dict(os.environ, HPGV_RCCL_LIB=lib), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.returncode, r.stdout, r.stderr)
+    # one symbol short, and the probe says so (the loader falls through to no other candidate: the file itself loads)
+    short = str(tmp_path / "libshort.so")
+    subprocess.run(["gcc", "-shared", "-fPIC", "-x", "c", "-o", short, "-"], input=b"int ncclSend(void) { return 0; }\n", check=True)
+    r = subprocess.run([os.sys.executable, "-c", code], env=dict(os.environ, HPGV_RCCL_LIB=short), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 3 and r.stdout.startswith("%d" % hpgv.ERR_UNSUPPORTED), (r.returncode, r.stdout, r.stderr)
+
+
 def test_product_does_not_link_or_import_the_oracle():
     pkg = os.path.join(ROOT, "hpg-variant_amd")
     for dirpath, _, files in os.walk(pkg):

@@ -2,7 +2,9 @@
 streams and the RCCL communicator (ncclCommInitAll), member g scans [g*V/G, (g+1)*V/G), results land on member 0.
 A one-GPU box can check: the communicator is really created (one rank), the shard split, the result placement, the
 two-generation overlap, and -- with the test switch group_self_exchange -- real ncclSend / ncclRecv / ncclReduce traffic.
-Everything is compared BIT FOR BIT with one ordinary context scanning all variants, and against the oracle."""
+Everything is compared BIT FOR BIT with one ordinary context scanning all variants, and against the oracle.
+What a one-rank communicator cannot reach -- members on ranks of their own, two to eight of them -- runs over a stand-in
+communicator in tests/test_group_ranks_gpu.py."""
 import ctypes as C
 import os
 import subprocess
@@ -144,13 +146,16 @@ class _AssocCohort:
             cls._oracle = orc.assoc_counts(orc.synth_matrix(0, cls.V, cls.N, cls.N), cls.cond)
         return tuple(a[:v] for a in cls._oracle)            # variant v's row does not depend on how many follow it
 
-    def __init__(self, devices, self_exchange, v=V):
+    def __init__(self, devices, self_exchange, v=V, fake_ranks=0):
+        """fake_ranks: the test switch group_fake_ranks (a stand-in communicator in HPGV_RCCL_LIB: tests/test_group_ranks_gpu.py)"""
         self.v = v
         self.g = hpgv.Engine(devices)
         if self_exchange:
             self.g.set_option("group_self_exchange", 1)
+        if fake_ranks:
+            self.g.set_option("group_fake_ranks", fake_ranks)
         _, _, pitch = self.g.set_cohort(self.cond)
-        assert self.g.group_comm_init() == 1
+        assert self.g.group_comm_init() == (len(devices) - min(fake_ranks, len(devices)) + 1 if fake_ranks else 1)
         self.mems, self.shards, self.n = [], [], []
         for k in range(len(devices)):
             lo, hi = self.g.group_shard(v, k)
@@ -185,16 +190,17 @@ class _AssocCohort:
         self.g.close()
 
 
-@pytest.mark.parametrize("self_exchange", [0, 1])
-def test_a_refused_group_call_leaves_the_group_usable(self_exchange):
-    """Argument errors the library returns -- after member 0's kernels are queued (the drain path) and before anything is --
-    and then two correct calls back to back into two result sets: both equal the oracle."""
-    c = _AssocCohort([0, 0, 0], self_exchange)
+def refused_group_call_scenario(self_exchange, fake_ranks=0, after_refusals=None):
+    """the body of test_a_refused_group_call_leaves_the_group_usable; fake_ranks as in _AssocCohort, after_refusals() is called
+    between the refused calls and the correct ones"""
+    c = _AssocCohort([0, 0, 0], self_exchange, fake_ranks=fake_ranks)
     a, b = c.result_set(), c.result_set()
     with pytest.raises(hpgv.HpgvError, match=r"member 1 .*no matrix"):
         c.assoc(a, [c.shards[0], None, c.shards[2]])
     with pytest.raises(hpgv.HpgvError, match=r"member 0 .*no matrix"):
         c.assoc(a, [None, c.shards[1], c.shards[2]])
+    if after_refusals:
+        after_refusals()
     c.assoc(a)
     c.assoc(b)
     c.g.group_sync()
@@ -202,7 +208,7 @@ def test_a_refused_group_call_leaves_the_group_usable(self_exchange):
     c.check(b)
     c.close()
     # 3 variants over 4 members: the member whose shard is empty needs no matrix
-    c = _AssocCohort([0, 0, 0, 0], self_exchange, v=3)
+    c = _AssocCohort([0, 0, 0, 0], self_exchange, v=3, fake_ranks=fake_ranks)
     empty = [k for k, n in enumerate(c.n) if n == 0]
     assert len(empty) == 1
     a = c.result_set()
@@ -213,15 +219,20 @@ def test_a_refused_group_call_leaves_the_group_usable(self_exchange):
 
 
 @pytest.mark.parametrize("self_exchange", [0, 1])
-def test_a_group_ranking_between_unsynced_scans(self_exchange):
-    """assoc into A, assoc into B, a ranking, assoc into A again, with no hpgv_group_sync between: the ranking's gather shares the
-    members' streams and scratch with the scans' hand-over.  A and B equal the oracle, the ranking the dense evaluation."""
+def test_a_refused_group_call_leaves_the_group_usable(self_exchange):
+    """Argument errors the library returns -- after member 0's kernels are queued (the drain path) and before anything is --
+    and then two correct calls back to back into two result sets: both equal the oracle."""
+    refused_group_call_scenario(self_exchange)
+
+
+def ranking_between_unsynced_scans_scenario(self_exchange, fake_ranks=0):
+    """the body of test_a_group_ranking_between_unsynced_scans; fake_ranks as in _AssocCohort"""
     from helpers import epi_random_dataset, epi_random_folds
     rng = np.random.default_rng(11)
     v, nA, nU, k, n = 130, 90, 110, 3, 5
     data = epi_random_dataset(rng, v, nA, nU)
     fold = epi_random_folds(rng, nA, nU, k)
-    c = _AssocCohort([0, 0], self_exchange)
+    c = _AssocCohort([0, 0], self_exchange, fake_ranks=fake_ranks)
     c.g.epi_set_dataset(data, nA, nU)
     c.g.epi_set_folds(fold, k)
     assert [c.g.group_epi_share(2, m) for m in range(2)] == [(0, 64), (64, v)]       # both members rank a share
@@ -245,6 +256,13 @@ def test_a_group_ranking_between_unsynced_scans(self_exchange):
         assert np.array_equal(res["accuracy"][f], acc[f][order]) and np.array_equal(res["risky"][f][:, 0], rm[f][order].astype(np.uint32))
     one.close()
     c.close()
+
+
+@pytest.mark.parametrize("self_exchange", [0, 1])
+def test_a_group_ranking_between_unsynced_scans(self_exchange):
+    """assoc into A, assoc into B, a ranking, assoc into A again, with no hpgv_group_sync between: the ranking's gather shares the
+    members' streams and scratch with the scans' hand-over.  A and B equal the oracle, the ranking the dense evaluation."""
+    ranking_between_unsynced_scans_scenario(self_exchange)
 
 
 def test_group_calls_refuse_an_ordinary_context():
