@@ -63,6 +63,7 @@ SYMBOLS = [
     "hpgv_bgzf_deflate_bound", "hpgv_bgzf_deflate_scratch_bytes", "hpgv_bgzf_deflate_dev", "hpgv_bgzf_compress",
     "hpgv_text_partition_bgzf", "hpgv_text_multisplit_bgzf",
     "hpgv_set_perm_labels", "hpgv_assoc_perm_dev", "hpgv_assoc_perm", "hpgv_assoc_perm_text", "hpgv_perm_labels_shuffle", "hpgv_perm_pvalues",
+    "hpgv_set_tdt_flips", "hpgv_tdt_perm_dev", "hpgv_tdt_perm", "hpgv_tdt_perm_text", "hpgv_perm_flips_shuffle",
 ]
 
 
@@ -216,6 +217,11 @@ def load():
     L.hpgv_assoc_perm_text.argtypes = [vp, C.c_char_p, sz, i32, C.POINTER(i32), vp, vp, vp] + [vp] * 9
     L.hpgv_perm_labels_shuffle.argtypes = [vp, i32, i32, u64, vp]
     L.hpgv_perm_pvalues.argtypes = [vp, i32, vp, vp, i32, vp, vp]
+    L.hpgv_set_tdt_flips.argtypes = [vp, vp, i32]
+    L.hpgv_tdt_perm_dev.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp]
+    L.hpgv_tdt_perm.argtypes = [vp, vp, sz, i32, vp] + [vp] * 7
+    L.hpgv_tdt_perm_text.argtypes = [vp, C.c_char_p, sz, i32, C.POINTER(i32), vp, vp, vp] + [vp] * 7
+    L.hpgv_perm_flips_shuffle.argtypes = [i32, i32, u64, vp]
     _lib = L
     return L
 
@@ -229,6 +235,31 @@ def perm_labels_shuffle(condition, n_perms, seed):
     if rc != OK:
         raise HpgvError("hpgv_perm_labels_shuffle -> %d" % rc)
     return out
+
+
+def perm_flips_shuffle(n_families, n_perms, seed):
+    """hpgv_perm_flips_shuffle: (n_perms, n_families) uint8 flip rows, every family flipped with probability 1/2;
+    deterministic in (seed, row, family).  No device needed."""
+    out = np.zeros((n_perms, n_families), np.uint8)
+    rc = load().hpgv_perm_flips_shuffle(n_families, n_perms, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(out))
+    if rc != OK:
+        raise HpgvError("hpgv_perm_flips_shuffle -> %d" % rc)
+    return out
+
+
+def run_tdt_perm(vcf_path, ped_path, out_path, n_perms, seed, batch_bytes=1 << 22):
+    """hpgv_run_tdt_perm of libhpgv_host.so (include/hpgv_host.h): the .tdt file of hpgv_run_tdt at out_path and EMP1 / EMP2 by
+    family flips in out_path + ".mperm".  Returns the number of variants written."""
+    _build.build_host_lib()
+    H = C.CDLL(_build.HOSTLIB)
+    H.hpgv_run_tdt_perm.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_uint64, C.c_size_t, C.POINTER(C.c_long)]
+    H.hpgv_host_last_error.restype = C.c_char_p
+    n = C.c_long(0)
+    rc = H.hpgv_run_tdt_perm(os.fsencode(vcf_path), os.fsencode(ped_path), os.fsencode(out_path), n_perms,
+                             int(seed) & 0xFFFFFFFFFFFFFFFF, batch_bytes, C.byref(n))
+    if rc != OK:
+        raise HpgvError("hpgv_run_tdt_perm -> %d: %s" % (rc, (H.hpgv_host_last_error() or b"").decode(errors="replace")))
+    return n.value
 
 
 def perm_pvalues(t_obs, n_ge, t_max):
@@ -331,7 +362,21 @@ class Engine:
         assert len(o) == len(f) + 1 and len(c) == len(s)
         self._chk(self.L.hpgv_set_families(self.h, n_samples, len(f), _ptr(f), _ptr(m), _ptr(o),
                                            _ptr(c), _ptr(s)))
+        self._n_flips = 0               # new families drop the flip rows
+        self._n_families = len(f)
         return self.tdt_layout()
+
+    def set_tdt_flips(self, flips):
+        """hpgv_set_tdt_flips: flips (n_perms, n_families) of 0 / 1 (1 = flipped) by the family index of set_families; None or no
+        rows drops them."""
+        if flips is None or len(flips) == 0:
+            self._chk(self.L.hpgv_set_tdt_flips(self.h, None, 0))
+            self._n_flips = 0
+            return
+        fl = _np(flips, np.uint8)
+        assert fl.ndim == 2 and fl.shape[1] == getattr(self, "_n_families", fl.shape[1])
+        self._chk(self.L.hpgv_set_tdt_flips(self.h, _ptr(fl), fl.shape[0]))
+        self._n_flips = fl.shape[0]
 
     def tdt_layout(self):
         a, b, p = C.c_int(), C.c_int(), C.c_size_t()
@@ -485,6 +530,19 @@ class Engine:
         self._chk(self.L.hpgv_tdt(self.h, _ptr(gt), pitch, nv, _ptr(x), _ptr(t1), _ptr(t2),
                                   _ptr(odds), _ptr(chisq), _ptr(p)))
         return dict(t1=t1, t2=t2, odds=odds, chisq=chisq, p=p)
+
+    def tdt_perm(self, gt, is_x=None):
+        """hpgv_tdt_perm: hpgv_tdt plus n_ge per variant and batch_max per permutation of the flips set with set_tdt_flips."""
+        gt = _np(gt, np.uint8)
+        nv, pitch = gt.shape
+        x = None if is_x is None else _np(is_x, np.uint8)
+        t1, t2, n_ge = (np.zeros(nv, np.int32) for _ in range(3))
+        odds, chisq, p = (np.zeros(nv, np.float64) for _ in range(3))
+        np_ = getattr(self, "_n_flips", 0)
+        bmax = np.zeros(max(np_, 1), np.float64)
+        self._chk(self.L.hpgv_tdt_perm(self.h, _ptr(gt), pitch, nv, _ptr(x), _ptr(t1), _ptr(t2),
+                                       _ptr(odds), _ptr(chisq), _ptr(p), _ptr(n_ge), _ptr(bmax)))
+        return dict(t1=t1, t2=t2, odds=odds, chisq=chisq, p=p, n_ge=n_ge, batch_max=bmax[:np_])
 
     def stats(self, gt):
         gt = _np(gt, np.uint8)
@@ -673,6 +731,25 @@ class Engine:
         k = min(nl.value, max_lines)
         return dict(n_lines=nl.value, status=status[:k], t1=t1[:k], t2=t2[:k], odds=odds[:k], chisq=chisq[:k], p=p[:k])
 
+    def tdt_perm_text(self, text, max_lines=None):
+        """hpgv_tdt_perm_text: hpgv_tdt_text plus n_ge per line and batch_max per permutation."""
+        if isinstance(text, str):
+            text = text.encode()
+        if max_lines is None:
+            max_lines = text.count(b"\n") + 1
+        m = max(max_lines, 1)
+        t1, t2, n_ge = (np.zeros(m, np.int32) for _ in range(3))
+        odds, chisq, p = (np.zeros(m, np.float64) for _ in range(3))
+        status = np.zeros(m, np.int32)
+        np_ = getattr(self, "_n_flips", 0)
+        bmax = np.zeros(max(np_, 1), np.float64)
+        nl = C.c_int(0)
+        self._chk(self.L.hpgv_tdt_perm_text(self.h, text, len(text), max_lines, C.byref(nl), None, None, _ptr(status),
+                                            _ptr(t1), _ptr(t2), _ptr(odds), _ptr(chisq), _ptr(p), _ptr(n_ge), _ptr(bmax)))
+        k = min(nl.value, max_lines)
+        return dict(n_lines=nl.value, status=status[:k], t1=t1[:k], t2=t2[:k], odds=odds[:k], chisq=chisq[:k], p=p[:k],
+                    n_ge=n_ge[:k], batch_max=bmax[:np_])
+
     # ---- device-resident path (raw pointers; ints or c_void_p) ---------------
     def synth(self, which, v0, n_variants, d_dst, stream=None):
         self._chk(self.L.hpgv_synth_dev(self.h, which, v0, n_variants, d_dst, stream))
@@ -732,6 +809,9 @@ class Engine:
 
     def tdt_stats(self, d_tu, n_variants, d_odds, d_chisq, d_p, stream=None):
         self._chk(self.L.hpgv_tdt_stats_dev(self.h, d_tu, n_variants, d_odds, d_chisq, d_p, stream))
+
+    def tdt_perm_dev(self, d_gt, n_variants, d_tu, d_n_ge, d_batch_max, d_perm_tu=None, d_is_x=None, stream=None):
+        self._chk(self.L.hpgv_tdt_perm_dev(self.h, d_gt, n_variants, d_is_x, d_tu, d_n_ge, d_batch_max, d_perm_tu, stream))
 
     def stats_scan(self, d_gt, n_variants, d_counts8, stream=None):
         self._chk(self.L.hpgv_stats_scan_dev(self.h, d_gt, n_variants, d_counts8, stream))

@@ -218,8 +218,7 @@ __global__ __launch_bounds__(256) void k_batch(BatchArgs A) {
         block_sum<2>(t, red);
         if (tid == 0) {                                        // tdt.c:255-260, 288-292
             const int t1 = t[0], t2 = t[1];
-            double x = -1;
-            if (t1 + t2 > 0) x = ((double)((t1 - t2) * (t1 - t2))) / (t1 + t2);
+            const double x = tdt_chisq_value(t1, t2);
             const double d1 = t1, d2 = t2;
             BatchTdtRec r = {t1, t2, (d2 == 0.0) ? __builtin_nan("") : (d1 / d2), x, chisq_p_value(x)};
             reinterpret_cast<BatchTdtRec *>(A.out)[v] = r;

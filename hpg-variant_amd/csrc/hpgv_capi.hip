@@ -142,7 +142,7 @@ void hpgv_destroy(hpgv_ctx *ctx) {
     DeviceGuard g(ctx->device);
     (void)hipDeviceSynchronize();
     if (ctx->d_mendel_male) (void)hipFree(ctx->d_mendel_male);
-    for (DevBuf *b : {&ctx->d_sg_chunks, &ctx->d_group_of_col, &ctx->d_cond, &ctx->d_perm, &ctx->d_thr, &ctx->assoc.d_cols, &ctx->tdt.d_cols,
+    for (DevBuf *b : {&ctx->d_sg_chunks, &ctx->d_group_of_col, &ctx->d_cond, &ctx->d_perm, &ctx->d_flips, &ctx->d_flip_tail, &ctx->d_thr, &ctx->assoc.d_cols, &ctx->tdt.d_cols,
                       &ctx->stats.d_cols, &ctx->sgroups.d_cols, &ctx->mendel.d_cols}) b->release();
     ctx->tdt_plan.release();
     if (ctx->d_lf_base) (void)hipFree(ctx->d_lf_base);
@@ -428,12 +428,14 @@ int hpgv_set_families(hpgv_ctx *ctx, int n_samples, int n_families, const int32_
         return fail(ctx, HPGV_ERR_INVALID, "bad family arguments");
     DeviceGuard g(ctx->device);
     Layout &L = ctx->tdt;
+    ctx->n_flips = ctx->flip_rows = ctx->flip_pitch = 0;      // the flip rows of hpgv_set_tdt_flips belong to the families they were given for
     std::string why;
     int rc = ctx->tdt_plan.build(n_samples, n_families, father_col, mother_col, child_off, child_col,
                                  child_sex, (size_t)ctx->row_align, L.col_of_pos, L.pitch, why);
     if (rc != HPGV_OK) return fail(ctx, rc, "%s", why.c_str());
     if (!pitch_supported(L.pitch)) return fail(ctx, HPGV_ERR_UNSUPPORTED, "pedigree exceeds the row-length limit");
     L.n_samples = n_samples;
+    ctx->tdt_families = n_families;
     return upload_layout(ctx, L);
     HPGV_ABI_CATCH(ctx)
 }

@@ -104,7 +104,8 @@ struct Slot {
     DevBuf inherit;    // the inheritance filter's counts8 and verdict bytes
     DevBuf multi;      // multi-allelic rows: their indices, then their 256-bin tables
     DevBuf row_cnt;    // k_stats_all2's per-row counters between its two kernels
-    DevBuf perm;       // the permutation call's results: n_ge per row, the batch maxima per permutation, then the rows' skip bytes
+    DevBuf perm;       // the permutation call's results: n_ge per row, the batch maxima per permutation, then the rows' skip bytes, then
+                       // (TDT flips) the slow families' i8 differences per row
     PinnedBuf res;     // result block of the one-pass kernels (they store into it), staging of k_assoc_rows' results
     // a buffer under two names holds two things that no call has at once:
     DevBuf &heads = text;      // a text that lies on the device already (hpgv_text_alias) is not uploaded: its head offsets and heads
@@ -240,6 +241,13 @@ struct hpgv_ctx {
     // tdt
     Layout tdt;
     hpgv::TdtPlan tdt_plan;
+    // family flips of the TDT (hpgv_set_tdt_flips): one row of i8 signs per permutation in K order (the fast trios in plane order,
+    // then the slow families, each part padded to whole 16-byte chunks: flip_pitch bytes), zeros under the pads, flip_rows = n_flips
+    // rounded up to 16 rows; dropped by a new hpgv_set_families
+    DevBuf d_flips;
+    int n_flips = 0, flip_rows = 0, flip_pitch = 0;
+    int tdt_families = 0;                 // n_families of hpgv_set_families: the length of a caller's flip row
+    DevBuf d_flip_tail;                   // hpgv_tdt_perm_dev's slow-family differences per row (the synchronous calls keep theirs in their slot)
     // stats
     Layout stats;
     Layout sgroups;                       // [group 0 | pad16 | group 1 | ...]

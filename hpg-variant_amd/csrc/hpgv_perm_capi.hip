@@ -1,8 +1,10 @@
-// hpgv_perm_capi.hip -- C ABI of the max(T) label permutation of the association test (include/hpgv.h "label
-// permutation"): the label rows of a context, the device-resident launch of k_assoc_perm, the synchronous entry points on a
-// host batch and on a text, and the two host-only helpers (label shuffle, empirical p-values).
+// hpgv_perm_capi.hip -- C ABI of the max(T) permutations (include/hpgv.h "label permutation", "family flips"): the label rows
+// of the association test and the flip rows of the TDT of a context, the device-resident launches of k_assoc_perm and
+// k_tdt_perm, the synchronous entry points on a host batch and on a text, and the host-only helpers (label shuffle, flip
+// generator, empirical p-values).
 #include "hpgv_internal.h"
 #include "hpgv_assoc_perm_kernels.h"
+#include "hpgv_tdt_perm_kernels.h"
 
 namespace {
 
@@ -71,6 +73,112 @@ int perm_finish(hpgv_ctx *ctx, Slot *s, const Staged &S, const uint8_t *skip, in
     }
     HIPCHK(ctx, hipMemcpyAsync(batch_max, d_max, np * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     HIPCHK(ctx, hipStreamSynchronize(s->stream));
+    return HPGV_OK;
+}
+
+// the front half of the two synchronous batch entry points: the rows and is_x copied to the slot and laid out for `which`
+// (the last row need not be a whole pitch)
+int perm_stage(hpgv_ctx *ctx, Slot *s, int which, const Layout &L, const uint8_t *gt, size_t pitch, int n_variants, const uint8_t *is_x, Staged *S) {
+    if (n_variants > 0) {
+        const size_t bytes = (size_t)(n_variants - 1) * pitch + (size_t)L.n_samples;
+        HIPCHK(ctx, s->raw.reserve_slack(bytes + 16));
+        HIPCHK(ctx, s->laid.reserve_slack((size_t)n_variants * L.pitch + 16));
+        if (bytes) HIPCHK(ctx, hipMemcpyAsync(s->raw.p, gt, bytes, hipMemcpyHostToDevice, s->stream));
+        if (is_x) {
+            HIPCHK(ctx, s->isx.reserve_slack((size_t)n_variants));
+            HIPCHK(ctx, hipMemcpyAsync(s->isx.p, is_x, (size_t)n_variants, hipMemcpyHostToDevice, s->stream));
+            S->d_isx = s->isx.as<uint8_t>();
+        }
+        S->d_raw = s->raw.as<uint8_t>(); S->raw_pitch = pitch; S->d_laid = s->laid.as<uint8_t>(); S->which = which;
+        if (const int rc = hpgv_layout_dev(ctx, which, S->d_raw, pitch, n_variants, s->laid.as<uint8_t>(), s->stream)) return rc;
+    }
+    S->n = n_variants; S->out_stride = (size_t)n_variants;
+    return HPGV_OK;
+}
+
+// the lines a caller of the plain *_text entry points drops: not a record (status 1), or rejected by a record filter
+void perm_skip_lines(const int32_t *status, int n, std::vector<uint8_t> &skip) {
+    skip.resize((size_t)n);
+    for (int i = 0; i < n; ++i) skip[(size_t)i] = ((status[i] & 0xFF) == 1 || (status[i] & HPGV_LINE_FILTERED)) ? 1 : 0;
+}
+
+/* ---- TDT, family flips ------------------------------------------------------------------------------------------- */
+
+int flip_state_check(const hpgv_ctx *ctx) {
+    if (!ctx->tdt.set) return fail(ctx, HPGV_ERR_STATE, "hpgv_set_families has not been called");
+    if (ctx->n_flips <= 0) return fail(ctx, HPGV_ERR_STATE, "hpgv_set_tdt_flips has not been called (new families drop the flips)");
+    return HPGV_OK;
+}
+
+int flip_tail_pitch(const hpgv_ctx *ctx) { return (int)round_up((size_t)ctx->tdt_plan.n_slow_families, 16); }
+
+// the launch: n_ge and batch_max zeroed on the stream, the slow families' differences into d_tail (flip_tail_pitch bytes per
+// row; unused without slow families), then the product kernel
+int flip_launch(hpgv_ctx *ctx, const uint8_t *d_gt, int n_variants, const uint8_t *d_is_x, const int32_t *d_tu, const uint8_t *d_skip,
+                int8_t *d_tail, int32_t *d_n_ge, double *d_batch_max, int32_t *d_perm_tu, hipStream_t st) {
+    HIPCHK(ctx, hipMemsetAsync(d_batch_max, 0, (size_t)ctx->n_flips * sizeof(double), st));
+    if (n_variants == 0) return HPGV_OK;
+    HIPCHK(ctx, hipMemsetAsync(d_n_ge, 0, (size_t)n_variants * sizeof(int32_t), st));
+    const hpgv::TdtPlan &P = ctx->tdt_plan;
+    const int tail_pitch = flip_tail_pitch(ctx);
+    hpgv::TdtPermArgs A;
+    A.gt = d_gt; A.pitch = ctx->tdt.pitch; A.pchunks = P.pchunks; A.kchunks = ctx->flip_pitch / 16; A.n_variants = n_variants;
+    A.is_x = d_is_x; A.luts = P.luts; A.male_plane = P.d_male_plane;
+    A.tail = tail_pitch ? d_tail : nullptr; A.tail_pitch = tail_pitch; A.tu = (const int2 *)d_tu;
+    A.signs = ctx->d_flips.as<uint8_t>(); A.n_perms = ctx->n_flips; A.sign_rows = ctx->flip_rows;
+    A.skip = d_skip; A.n_ge = d_n_ge; A.batch_max = (unsigned long long *)d_batch_max; A.perm_tu = d_perm_tu;
+    // one workgroup per (variant tile, pass), the tiles rounded up to 8 (k_tdt_perm "Grid")
+    A.passes = (ctx->n_flips + hpgv::PERM_PT - 1) / hpgv::PERM_PT;
+    const size_t wgs = round_up((size_t)((n_variants + hpgv::PERM_VT - 1) / hpgv::PERM_VT), 8) * (size_t)A.passes;
+    if (wgs > 0x7FFFFFFFu) return fail(ctx, HPGV_ERR_UNSUPPORTED, "%d variants x %d permutations in one call: give the variants in several", n_variants, ctx->n_flips);
+    const dim3 grid((unsigned)wgs);
+    // (option "profile": the two kernels' time is the statistics time of hpgv_last_kernel_ms)
+    return launch_profiled(ctx, st, 1, [&] {
+        if (tail_pitch) {
+            const size_t lanes = (size_t)n_variants * (size_t)tail_pitch;
+            hipLaunchKernelGGL(hpgv::k_tdt_perm_slow, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, d_gt, ctx->tdt.pitch, n_variants,
+                               P.n_slow_families, tail_pitch, P.d_slow_off, P.d_slow_male, P.slow_base, d_is_x, d_tail);
+        }
+        hipLaunchKernelGGL(hpgv::k_tdt_perm, grid, dim3(256), 0, st, A);
+    });
+}
+
+// the back half of the two synchronous entry points: the laid-out matrix of a staged call -> scan, statistics, the two
+// permutation kernels -> the caller's arrays.  skip (host, may be null): rows that take no part
+int flip_finish(hpgv_ctx *ctx, Slot *s, const Staged &S, const uint8_t *skip, int32_t *t1, int32_t *t2, double *odds, double *chisq, double *p,
+                int32_t *n_ge, double *batch_max) {
+    int rc;
+    const int nv = S.n;
+    const size_t n = (size_t)nv, np = (size_t)ctx->n_flips, tail = (size_t)flip_tail_pitch(ctx);
+    const size_t off_max = round_up(n * sizeof(int32_t), 16), off_skip = off_max + np * sizeof(double), off_tail = round_up(off_skip + n, 16);
+    HIPCHK(ctx, s->tally.reserve_slack(n * 8 + 16));
+    HIPCHK(ctx, s->dbl.reserve_slack(n * 3 * sizeof(double) + 16));
+    HIPCHK(ctx, s->perm.reserve_slack(off_tail + n * tail + 16));
+    int32_t *d_tu = s->tally.as<int32_t>();
+    double *d_odds = s->dbl.as<double>(), *d_chisq = d_odds + n, *d_p = d_odds + 2 * n;
+    int32_t *d_n_ge = s->perm.as<int32_t>();
+    double *d_max = (double *)(s->perm.as<char>() + off_max);
+    uint8_t *d_skip = nullptr;
+    if (skip && nv > 0) {
+        d_skip = s->perm.as<uint8_t>() + off_skip;
+        HIPCHK(ctx, hipMemcpyAsync(d_skip, skip, n, hipMemcpyHostToDevice, s->stream));
+    }
+    if (nv > 0) {
+        if ((rc = hpgv_tdt_scan_dev(ctx, S.d_laid, nv, S.d_isx, d_tu, s->stream))) return rc;
+        if ((rc = hpgv_tdt_stats_dev(ctx, d_tu, nv, d_odds, d_chisq, d_p, s->stream))) return rc;
+    }
+    if ((rc = flip_launch(ctx, S.d_laid, nv, S.d_isx, d_tu, d_skip, (int8_t *)(s->perm.as<char>() + off_tail), d_n_ge, d_max, nullptr, s->stream))) return rc;
+    std::vector<int32_t> tu(2 * n);
+    if (nv > 0) {
+        HIPCHK(ctx, hipMemcpyAsync(tu.data(), d_tu, n * 8, hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(ctx, hipMemcpyAsync(odds, d_odds, n * 8, hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(ctx, hipMemcpyAsync(chisq, d_chisq, n * 8, hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(ctx, hipMemcpyAsync(p, d_p, n * 8, hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(ctx, hipMemcpyAsync(n_ge, d_n_ge, n * 4, hipMemcpyDeviceToHost, s->stream));
+    }
+    HIPCHK(ctx, hipMemcpyAsync(batch_max, d_max, np * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(ctx, hipStreamSynchronize(s->stream));
+    for (size_t i = 0; i < n; ++i) { t1[i] = tu[2 * i]; t2[i] = tu[2 * i + 1]; }
     return HPGV_OK;
 }
 
@@ -144,22 +252,7 @@ int hpgv_assoc_perm(hpgv_ctx *ctx, const uint8_t *gt, size_t pitch, int n_varian
     if (pitch < (size_t)ctx->assoc.n_samples) return fail(ctx, HPGV_ERR_INVALID, "pitch %zu < n_samples %d", pitch, ctx->assoc.n_samples);
     HPGV_LEASE_SLOT(ctx)
     Staged S;
-    if (n_variants > 0) {
-        // the rows and is_x copied to the slot and laid out (the last row need not be a whole pitch)
-        const Layout &L = ctx->assoc;
-        const size_t bytes = (size_t)(n_variants - 1) * pitch + (size_t)L.n_samples;
-        HIPCHK(ctx, s->raw.reserve_slack(bytes + 16));
-        HIPCHK(ctx, s->laid.reserve_slack((size_t)n_variants * L.pitch + 16));
-        if (bytes) HIPCHK(ctx, hipMemcpyAsync(s->raw.p, gt, bytes, hipMemcpyHostToDevice, s->stream));
-        if (is_x) {
-            HIPCHK(ctx, s->isx.reserve_slack((size_t)n_variants));
-            HIPCHK(ctx, hipMemcpyAsync(s->isx.p, is_x, (size_t)n_variants, hipMemcpyHostToDevice, s->stream));
-            S.d_isx = s->isx.as<uint8_t>();
-        }
-        S.d_raw = s->raw.as<uint8_t>(); S.raw_pitch = pitch; S.d_laid = s->laid.as<uint8_t>(); S.which = HPGV_LAYOUT_ASSOC;
-        if ((rc = hpgv_layout_dev(ctx, HPGV_LAYOUT_ASSOC, S.d_raw, pitch, n_variants, s->laid.as<uint8_t>(), s->stream))) return rc;
-    }
-    S.n = n_variants; S.out_stride = (size_t)n_variants;
+    if ((rc = perm_stage(ctx, s, HPGV_LAYOUT_ASSOC, ctx->assoc, gt, pitch, n_variants, is_x, &S))) return rc;
     return perm_finish(ctx, s, S, nullptr, A1, A2, U1, U2, odds, chisq, p, n_ge, batch_max);
     HPGV_ABI_CATCH(ctx)
 }
@@ -184,10 +277,107 @@ int hpgv_assoc_perm_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, int
         if ((rc = text_front(ctx, s, HPGV_LAYOUT_ASSOC, ctx->assoc, text, text_bytes, max_lines, n_lines, line_off, field_off, status, &S, true))) return rc;
         // the lines hpgv_assoc_text's callers drop: not a record (status 1), or rejected by a record filter
         HIPCHK(ctx, hipStreamSynchronize(s->stream));
-        skip.resize((size_t)S.n);
-        for (int i = 0; i < S.n; ++i) skip[(size_t)i] = ((status[i] & 0xFF) == 1 || (status[i] & HPGV_LINE_FILTERED)) ? 1 : 0;
+        perm_skip_lines(status, S.n, skip);
     }
     return perm_finish(ctx, s, S, skip.empty() ? nullptr : skip.data(), A1, A2, U1, U2, odds, chisq, p, n_ge, batch_max);
+    HPGV_ABI_CATCH(ctx)
+}
+
+/* ---- TDT, family flips ------------------------------------------------------------------------------------------- */
+
+int hpgv_set_tdt_flips(hpgv_ctx *ctx, const uint8_t *flips, int n_perms) {
+    HPGV_ABI_TRY
+    GROUP_ALL(ctx, hpgv_set_tdt_flips(m_, flips, n_perms))
+    if (!ctx) return HPGV_ERR_INVALID;
+    if (!ctx->tdt.set) return fail(ctx, HPGV_ERR_STATE, "hpgv_set_families has not been called");
+    if (n_perms < 0 || (n_perms > 0 && !flips)) return fail(ctx, HPGV_ERR_INVALID, "bad tdt_flips arguments");
+    if (n_perms > kMaxPerms) return fail(ctx, HPGV_ERR_UNSUPPORTED, "%d permutations: at most %d per call", n_perms, kMaxPerms);
+    if (n_perms == 0) { ctx->n_flips = ctx->flip_rows = ctx->flip_pitch = 0; return HPGV_OK; }
+    const hpgv::TdtPlan &P = ctx->tdt_plan;
+    // |t1_f - t2_f| <= 2 x children must fit the i8 operand
+    if (P.max_children > 63) return fail(ctx, HPGV_ERR_UNSUPPORTED, "a family with %d counted children: at most 63 under family flips", P.max_children);
+    // the family behind every K position: the fast trios in plane order, then the slow families; -1 = pad
+    const size_t kpitch = (size_t)P.p16 + round_up((size_t)P.n_slow_families, 16), rows = round_up((size_t)n_perms, 16);
+    std::vector<int32_t> fam_of_k(kpitch, -1);
+    for (size_t t = 0; t < P.fast_family.size(); ++t) fam_of_k[t] = P.fast_family[t];
+    for (size_t k = 0; k < P.slow_family.size(); ++k) fam_of_k[(size_t)P.p16 + k] = P.slow_family[k];
+    const size_t nf = (size_t)ctx->tdt_families;
+    std::vector<uint8_t> laid(rows * kpitch, 0);
+    for (int q = 0; q < n_perms; ++q) {
+        const uint8_t *src = flips + (size_t)q * nf;
+        uint8_t *dst = laid.data() + (size_t)q * kpitch;
+        for (size_t k = 0; k < kpitch; ++k) {
+            const int32_t f = fam_of_k[k];
+            if (f < 0) continue;
+            if (src[f] > 1) return fail(ctx, HPGV_ERR_INVALID, "flip %u of permutation %d, family %d: flips are 0 or 1", (unsigned)src[f], q, (int)f);
+            dst[k] = src[f] ? 0xFF : 0x01;               // i8: flipped -1, kept +1
+        }
+    }
+    DeviceGuard g(ctx->device);
+    ctx->n_flips = ctx->flip_rows = ctx->flip_pitch = 0;
+    {
+        const hipError_t e = ctx->d_flips.reserve(laid.size() + 16);
+        if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(ctx, HPGV_ERR_NOMEM, "the sign matrix (%zu bytes) does not fit the device", laid.size()); }
+        HIPCHK(ctx, e);
+    }
+    if (!laid.empty()) HIPCHK(ctx, hipMemcpy(ctx->d_flips.p, laid.data(), laid.size(), hipMemcpyHostToDevice));
+    ctx->n_flips = n_perms; ctx->flip_rows = (int)rows; ctx->flip_pitch = (int)kpitch;
+    return HPGV_OK;
+    HPGV_ABI_CATCH(ctx)
+}
+
+int hpgv_tdt_perm_dev(hpgv_ctx *ctx, const uint8_t *d_gt, int n_variants, const uint8_t *d_is_x, const int32_t *d_tu,
+                      int32_t *d_n_ge, double *d_batch_max, int32_t *d_perm_tu, void *stream) {
+    ctx = first_member(ctx);
+    if (!ctx) return HPGV_ERR_INVALID;
+    if (const int rc = flip_state_check(ctx)) return rc;
+    if (n_variants < 0 || !d_batch_max || (n_variants > 0 && (!d_gt || !d_tu || !d_n_ge))) return fail(ctx, HPGV_ERR_INVALID, "bad tdt_perm arguments");
+    if (((uintptr_t)d_gt & 15) || ((uintptr_t)d_tu & 7) || ((uintptr_t)d_batch_max & 7) || ((uintptr_t)d_perm_tu & 7))
+        return fail(ctx, HPGV_ERR_INVALID, "d_gt must be 16-byte aligned, d_tu, d_batch_max and d_perm_tu 8-byte aligned");
+    DeviceGuard g(ctx->device);
+    // the slow families' differences: the context's own scratch, grown after the stream that may still read it
+    const size_t tail = (size_t)n_variants * (size_t)flip_tail_pitch(ctx);
+    if (tail) HIPCHK(ctx, ctx->d_flip_tail.reserve_after_sync((hipStream_t)stream, tail + 16, tail + tail / 4 + 256));
+    return flip_launch(ctx, d_gt, n_variants, d_is_x, d_tu, nullptr, ctx->d_flip_tail.as<int8_t>(), d_n_ge, d_batch_max, d_perm_tu, (hipStream_t)stream);
+}
+
+int hpgv_tdt_perm(hpgv_ctx *ctx, const uint8_t *gt, size_t pitch, int n_variants, const uint8_t *is_x,
+                  int32_t *t1, int32_t *t2, double *odds, double *chisq, double *p, int32_t *n_ge, double *batch_max) {
+    HPGV_ABI_TRY
+    GROUP_DEAL(ctx, hpgv_tdt_perm(m_, gt, pitch, n_variants, is_x, t1, t2, odds, chisq, p, n_ge, batch_max))
+    if (!ctx) return HPGV_ERR_INVALID;
+    if (const int rc0 = flip_state_check(ctx)) return rc0;
+    if (n_variants < 0 || !batch_max || (n_variants > 0 && (!gt || !t1 || !t2 || !odds || !chisq || !p || !n_ge)))
+        return fail(ctx, HPGV_ERR_INVALID, "bad tdt_perm arguments");
+    if (pitch < (size_t)ctx->tdt.n_samples) return fail(ctx, HPGV_ERR_INVALID, "pitch %zu < n_samples %d", pitch, ctx->tdt.n_samples);
+    HPGV_LEASE_SLOT(ctx)
+    Staged S;
+    if ((rc = perm_stage(ctx, s, HPGV_LAYOUT_TDT, ctx->tdt, gt, pitch, n_variants, is_x, &S))) return rc;
+    return flip_finish(ctx, s, S, nullptr, t1, t2, odds, chisq, p, n_ge, batch_max);
+    HPGV_ABI_CATCH(ctx)
+}
+
+int hpgv_tdt_perm_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, int max_lines, int *n_lines,
+                       uint64_t *line_off, uint32_t *field_off, int32_t *status, int32_t *t1, int32_t *t2,
+                       double *odds, double *chisq, double *p, int32_t *n_ge, double *batch_max) {
+    HPGV_ABI_TRY
+    GROUP_DEAL_TEXT(ctx, text, hpgv_tdt_perm_text(m_, text, text_bytes, max_lines, n_lines, line_off, field_off, status, t1, t2, odds, chisq, p, n_ge, batch_max))
+    if (!ctx) return HPGV_ERR_INVALID;
+    if (const int rc0 = flip_state_check(ctx)) return rc0;
+    if (!n_lines || !batch_max || max_lines < 0 || (text_bytes > 0 && !text) || (max_lines > 0 && (!t1 || !t2 || !odds || !chisq || !p || !n_ge)))
+        return fail(ctx, HPGV_ERR_INVALID, "bad tdt_perm_text arguments");
+    *n_lines = 0;
+    std::vector<int32_t> own_status;             // (before the lease: queued copies into them end with the lease)
+    std::vector<uint8_t> skip;
+    HPGV_LEASE_SLOT(ctx)
+    Staged S;
+    if (max_lines > 0) {
+        if (!status) { own_status.assign((size_t)max_lines, 0); status = own_status.data(); }
+        if ((rc = text_front(ctx, s, HPGV_LAYOUT_TDT, ctx->tdt, text, text_bytes, max_lines, n_lines, line_off, field_off, status, &S, true))) return rc;
+        HIPCHK(ctx, hipStreamSynchronize(s->stream));
+        perm_skip_lines(status, S.n, skip);
+    }
+    return flip_finish(ctx, s, S, skip.empty() ? nullptr : skip.data(), t1, t2, odds, chisq, p, n_ge, batch_max);
     HPGV_ABI_CATCH(ctx)
 }
 
@@ -218,6 +408,22 @@ int hpgv_perm_labels_shuffle(const uint8_t *condition, int n_samples, int n_perm
             for (size_t k = 0; k < nc; ++k) row[cols[k]] = y[k];
         }
     } catch (...) { return HPGV_ERR_NOMEM; }
+    return HPGV_OK;
+}
+
+int hpgv_perm_flips_shuffle(int n_families, int n_perms, uint64_t seed, uint8_t *flips_out) {
+    if (n_families < 0 || n_perms < 0 || ((size_t)n_families * (size_t)n_perms > 0 && !flips_out)) return HPGV_ERR_INVALID;
+    for (int q = 0; q < n_perms; ++q) {
+        uint8_t *row = flips_out + (size_t)q * (size_t)n_families;
+        // the row's stream is the label rows': key = SplitMix64(seed ^ SplitMix64(q)); word number w = SplitMix64(key + w) holds the
+        // flips of families 64 w .. 64 w + 63, family f in bit f & 63
+        const uint64_t key = splitmix64(seed ^ splitmix64((uint64_t)q));
+        uint64_t word = 0;
+        for (int f = 0; f < n_families; ++f) {
+            if ((f & 63) == 0) word = splitmix64(key + (uint64_t)(f >> 6));
+            row[f] = (uint8_t)((word >> (f & 63)) & 1u);
+        }
+    }
     return HPGV_OK;
 }
 

@@ -5,6 +5,7 @@
 #pragma once
 #include "hpgv_kernels.h"
 
+#include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -115,11 +116,11 @@ __device__ __forceinline__ uint32_t tdt_pair(const TdtLut &L, uint32_t idx) {
     return __builtin_amdgcn_perm(hi, lo, pick);
 }
 
+// the masked pair bytes of 4 trios: a trio's t1 is the number of bits set in its byte of w1, its t2 that of w2 (0 .. 2 each)
 template <bool X>
-__device__ __forceinline__ int2 tdt4(const TdtLuts &L, uint32_t f, uint32_t m, uint32_t c, uint32_t male) {
+__device__ __forceinline__ void tdt4_words(const TdtLuts &L, uint32_t f, uint32_t m, uint32_t c, uint32_t male, uint32_t &w1, uint32_t &w2) {
     const uint32_t idx = (m << 2) | f;
     const uint32_t kill = __builtin_amdgcn_perm(0u, 0u, f | m);       // 0xFF where a parent is unusable
-    uint32_t w1, w2;
     if constexpr (!X) {
         const uint32_t pair = tdt_pair(L.autosome, idx) & ~kill;
         w1 = pair & lut8(L.autosome.c1[0], L.autosome.c1[1], c);
@@ -132,7 +133,31 @@ __device__ __forceinline__ int2 tdt4(const TdtLuts &L, uint32_t f, uint32_t m, u
         w1 = ((male & x1) | (~male & a1)) & ~kill;                    // male: 0xFF per male child
         w2 = ((male & x2) | (~male & a2)) & ~kill;
     }
+}
+
+// {t1, t2} of the 4 trios together
+template <bool X>
+__device__ __forceinline__ int2 tdt4(const TdtLuts &L, uint32_t f, uint32_t m, uint32_t c, uint32_t male) {
+    uint32_t w1, w2;
+    tdt4_words<X>(L, f, m, c, male, w1, w2);
     return make_int2(__builtin_popcount(w1), __builtin_popcount(w2));
+}
+
+// bits set in every byte, as four bytes 0 .. 8
+__device__ __forceinline__ uint32_t popcount_bytes(uint32_t w) {
+    w = w - ((w >> 1) & 0x55555555u);
+    w = (w & 0x33333333u) + ((w >> 2) & 0x33333333u);
+    return (w + (w >> 4)) & 0x0F0F0F0Fu;
+}
+
+// the per-byte form: d = t1 - t2 of each of the 4 trios as one signed i8 per byte (-2 .. 2).  Both counts are below 128, so
+// setting bit 7 of every minuend byte keeps a borrow from crossing into the next byte, and taking it out again (xor: minus 128
+// modulo 256) leaves the two's complement difference
+template <bool X>
+__device__ __forceinline__ uint32_t tdt4_diff(const TdtLuts &L, uint32_t f, uint32_t m, uint32_t c, uint32_t male) {
+    uint32_t w1, w2;
+    tdt4_words<X>(L, f, m, c, male, w1, w2);
+    return ((popcount_bytes(w1) | 0x80808080u) - popcount_bytes(w2)) ^ 0x80808080u;
 }
 
 // Row layout: [F plane P16 | M plane P16 | C plane P16 | slow groups (HPGV8) | pad].
@@ -199,14 +224,22 @@ __global__ __launch_bounds__(256) void k_tdt_scan(const uint8_t *__restrict__ gt
     }
 }
 
-// tdt.c:255-260 (integer square before the cast) and tdt.c:288-292
+// the TDT chi-square, tdt.c:255-260: integer square before the cast; -1 when nothing was transmitted.  The one statement of it on
+// the device: k_tdt_stats, the one-pass kernel and the flip permutation's epilogue (hpgv_tdt_perm_kernels.h) call it, so equal
+// counts give equal bits
+__device__ __forceinline__ double tdt_chisq_value(int t1, int t2) {
+    double x = -1;
+    if (t1 + t2 > 0) x = ((double)((t1 - t2) * (t1 - t2))) / (t1 + t2);
+    return x;
+}
+
+// tdt.c:255-260 and tdt.c:288-292
 static __global__ __launch_bounds__(256) void k_tdt_stats(const int2 *__restrict__ tu, int n, double *__restrict__ odds,
                                                    double *__restrict__ chisq, double *__restrict__ pval) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int t1 = tu[i].x, t2 = tu[i].y;
-    double x = -1;
-    if (t1 + t2 > 0) x = ((double)((t1 - t2) * (t1 - t2))) / (t1 + t2);
+    const double x = tdt_chisq_value(t1, t2);
     const double d1 = t1, d2 = t2;
     odds[i] = (d2 == 0.0) ? __builtin_nan("") : (d1 / d2);
     chisq[i] = x;
@@ -302,6 +335,8 @@ struct TdtPlan {
     int pchunks = 0;
     int p16 = 0;
     int slow_base = 0;
+    int max_children = 0;                 // counted children of the largest slow family
+    std::vector<int32_t> fast_family, slow_family;     // family index (of hpgv_set_families) of fast trio t / of slow family s
     TdtLuts luts{};
     uint8_t *d_male_plane = nullptr;
     int32_t *d_slow_off = nullptr;
@@ -312,7 +347,8 @@ struct TdtPlan {
         if (d_slow_off) (void)hipFree(d_slow_off);
         if (d_slow_male) (void)hipFree(d_slow_male);
         d_male_plane = nullptr; d_slow_off = nullptr; d_slow_male = nullptr;
-        n_fast = n_slow_families = pchunks = p16 = slow_base = 0;
+        n_fast = n_slow_families = pchunks = p16 = slow_base = max_children = 0;
+        fast_family.clear(); slow_family.clear();
     }
 
     // return codes are hpgv status values (1 invalid, 3 hip, 6 unsupported)
@@ -333,6 +369,9 @@ struct TdtPlan {
         }
         n_fast = (int)fast.size();
         n_slow_families = (int)slow.size();
+        fast_family.assign(fast.begin(), fast.end());
+        slow_family.assign(slow.begin(), slow.end());
+        for (int f : slow) max_children = std::max(max_children, (int)(child_off[f + 1] - child_off[f]));
         const size_t P16 = ((size_t)n_fast + 15) / 16 * 16;
         pchunks = (int)(P16 / 16);
         p16 = (int)P16;

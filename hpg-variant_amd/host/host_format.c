@@ -23,7 +23,7 @@ static int run_batch_stats_arrays(run_batch_t *b) {
 /* the per-line arrays for max_lines lines (the ones there before freed) */
 static int run_batch_lines(run_batch_t *b) {
     free(b->line_off); free(b->field_off); free(b->status); free(b->ints); free(b->dbl);
-    if (b->run->tool == RUN_CHISQ_PERM) {
+    if (tool_perm(b->run->tool)) {
         free(b->n_ge);
         b->n_ge = (int32_t *)malloc(sizeof(int32_t) * (size_t)b->max_lines);
         if (!b->bmax) b->bmax = (double *)malloc(sizeof(double) * (size_t)b->run->n_perms);
@@ -140,7 +140,7 @@ static int format_record(char *dst, size_t room, const run_batch_t *b, int i) {
     p = put_i64(p, atol(l + fo[1])); *p++ = '\t';
     p = PUT_STR(p, l + fo[2], li); *p++ = '\t';
     p = PUT_STR(p, l + fo[3], lr); *p++ = '\t';
-    if (tool == RUN_TDT) {
+    if (tool_tdt(tool)) {
         const int t1 = b->ints[i], t2 = b->ints[m + i];
         p = PUT_STR(p, l + fo[4], la); *p++ = '\t';
         p = put_i64(p, t1); *p++ = '\t'; p = put_i64(p, t2); *p++ = '\t';

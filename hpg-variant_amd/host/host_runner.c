@@ -110,6 +110,9 @@ static void *pipe_engine(void *v) {
             case RUN_TDT: what = "hpgv_tdt_text";
                 rc = hpgv_tdt_text(g_ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status,
                                    b->ints, b->ints + m, b->dbl, b->dbl + m, b->dbl + 2 * m); break;
+            case RUN_TDT_PERM: what = "hpgv_tdt_perm_text";
+                rc = hpgv_tdt_perm_text(g_ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status,
+                                        b->ints, b->ints + m, b->dbl, b->dbl + m, b->dbl + 2 * m, b->n_ge, b->bmax); break;
             case RUN_CHISQ: case RUN_FISHER: what = "hpgv_assoc_text";
                 rc = hpgv_assoc_text(g_ctx, tool, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status,
                                      b->ints, b->ints + m, b->ints + 2 * m, b->ints + 3 * m,
@@ -136,7 +139,7 @@ static void *pipe_engine(void *v) {
             pthread_mutex_unlock(&P->mu);
             return NULL;
         }
-        if (tool == RUN_CHISQ_PERM) {                     /* the batch's maxima into the run's: max is order-independent */
+        if (tool_perm(tool)) {                            /* the batch's maxima into the run's: max is order-independent */
             double *tmax = P->run->PM->tmax;
             for (int q = 0; q < P->run->n_perms; q++) if (b->bmax[q] > tmax[q]) tmax[q] = b->bmax[q];
         }
@@ -146,7 +149,7 @@ static void *pipe_engine(void *v) {
     }
 }
 
-/* ---- RUN_CHISQ_PERM: the records of a written batch kept for <out>.mperm, and that file ---------------------------- */
+/* ---- the permutation tools: the records of a written batch kept for <out>.mperm, and that file ---------------------- */
 static int run_perm_add(run_t *R, const run_batch_t *b) {
     run_perm_t *M = R->PM;
     const int n = b->n_lines < b->max_lines ? b->n_lines : b->max_lines, m = b->max_lines;
@@ -176,6 +179,7 @@ static int run_perm_add(run_t *R, const run_batch_t *b) {
         M->head[M->n] = M->heads_len;                    /* CHR, POS as the result file prints it, ID */
         M->heads_len += (size_t)snprintf(M->heads + M->heads_len, need, "%.*s\t%ld\t%.*s", lc, l + fo[0], atol(l + fo[1]), li, l + fo[2]) + 1;
         M->t_obs[M->n] = b->dbl[m + i];
+        if (R->tool == RUN_TDT_PERM && M->t_obs[M->n] < 0) M->t_obs[M->n] = NAN;      /* chi-square -1: nothing transmitted, no statistic */
         M->n_ge[M->n] = b->n_ge[i];
         M->n++;
     }
@@ -271,7 +275,7 @@ static int run_cohort(run_t *R, const char *vcf_path, const char *ped_path) {
         if (!rc) rc = set_trios(R, ids, 1);
         break;
     }
-    case RUN_TDT: {
+    case RUN_TDT: case RUN_TDT_PERM: {
         /* families in order of first appearance; father / mother = founders by sex (tdt.c:62-73);
          * counted children = rows with both parents named, affected, present in the VCF (tdt.c:139-148) */
         int32_t *fcol = (int32_t *)malloc(sizeof(int32_t) * (size_t)(ped->n + 1)), *mcol = (int32_t *)malloc(sizeof(int32_t) * (size_t)(ped->n + 1));
@@ -307,6 +311,13 @@ static int run_cohort(run_t *R, const char *vcf_path, const char *ped_path) {
         rc = hpgv_set_families(g_ctx, n_samples, nf, fcol, mcol, coff, ccol, csex);
         g_tdt_key.set = 0;
         if (rc) host_fail("hpgv_set_families", rc);
+        if (!rc && R->tool == RUN_TDT_PERM) {            /* the run's flip rows, once: a fair coin per family and permutation */
+            uint8_t *flips = (uint8_t *)malloc((size_t)R->n_perms * (size_t)(nf > 0 ? nf : 1));
+            if (!flips) rc = HPGV_ERR_NOMEM;
+            if (!rc && (rc = hpgv_perm_flips_shuffle(nf, R->n_perms, R->perm_seed, flips))) host_fail("hpgv_perm_flips_shuffle", rc);
+            if (!rc && (rc = hpgv_set_tdt_flips(g_ctx, flips, R->n_perms))) host_fail("hpgv_set_tdt_flips", rc);
+            free(flips);
+        }
         free(fcol); free(mcol); free(coff); free(ccol); free(csex); free(done);
         break;
     }
@@ -469,7 +480,7 @@ static int create_out(FILE **f, char **path, const char *prefix, const char *suf
 /* the tool's output files (split: its files as the records come).  The filter tool's .rejected is created empty without
  * save_rejected (filter_runner.c:63-68); stats: one file per phenotype (stats_runner.c:267-297), and its accumulator */
 static int run_outputs(run_t *R, const char *out_path) {
-    if (R->tool == RUN_CHISQ_PERM) {
+    if (tool_perm(R->tool)) {
         R->PM = (run_perm_t *)calloc(1, sizeof *R->PM);
         if (R->PM) R->PM->tmax = (double *)calloc((size_t)R->n_perms, sizeof(double));      /* 0: the identity of the merge */
         if (!R->PM || !R->PM->tmax) return HPGV_ERR_NOMEM;
@@ -505,7 +516,7 @@ static int run_headers(run_t *R) {
         order_track_keep(&R->ord, h, strlen(h));
         return HPGV_OK;
     }
-    case RUN_TDT: tdt_write_output_header(out); order_track_keep(&R->ord, "#CHR\tPOS\tID\tA1\tA2\tT\tU\tOR\tCHISQ\tP-VALUE", 38); return HPGV_OK;
+    case RUN_TDT: case RUN_TDT_PERM: tdt_write_output_header(out); order_track_keep(&R->ord, "#CHR\tPOS\tID\tA1\tA2\tT\tU\tOR\tCHISQ\tP-VALUE", 38); return HPGV_OK;
     case RUN_VCF2EPI: {                                  /* room for the number of variants, then the class sizes (dataset_creator.c:186-193) */
         const uint32_t head[3] = {0, R->epi_aff, R->epi_unaff};
         return fwrite(head, sizeof(uint32_t), 3, out) != 3 ? HPGV_ERR_INVALID : HPGV_OK;
@@ -605,10 +616,10 @@ static int run_pipeline(run_t *R, size_t batch_bytes) {
                 if (write_split_batch(R, b)) bad = g_err;          /* (what split_file said) */
                 R->written += b->n_pass; R->skipped += b->n_skip;
                 break;
-            case RUN_CHISQ: case RUN_CHISQ_PERM: case RUN_FISHER: case RUN_TDT: case RUN_VCF2EPI: case RUN_AGGREGATE: case RUN_STATS:
+            case RUN_CHISQ: case RUN_CHISQ_PERM: case RUN_FISHER: case RUN_TDT: case RUN_TDT_PERM: case RUN_VCF2EPI: case RUN_AGGREGATE: case RUN_STATS:
                 if (write_batch(R->out, b, fmt + (fmt_set ? RUN_FMT_BUFS / 2 : 0), n_fmt, &wpool, &R->ord, use_fw ? &fw : NULL)) bad = "cannot write the result file";
                 for (int i = 0; i < b->n_lines; i++) if (record_passes(b, i)) R->written++;
-                if (R->tool == RUN_CHISQ_PERM && !bad && run_perm_add(R, b)) bad = "out of memory for the permutation results";
+                if (tool_perm(R->tool) && !bad && run_perm_add(R, b)) bad = "out of memory for the permutation results";
                 if (R->tool == RUN_STATS && !bad) { run_stats_add(R, b); if (R->gfd) write_group_lines(R->gfd, b); }      /* (the group files: by this thread) */
                 break;
             }
@@ -663,9 +674,9 @@ static int run_finish(run_t *R, int rc, const char *out_path) {
         R->t_sort = now_s() - t0;
     }
     if (R->tool == RUN_STATS && !rc) rc = run_stats_write(R, out_path);
-    if (R->tool == RUN_CHISQ_PERM) {
+    if (tool_perm(R->tool)) {
         if (!rc && R->PM) rc = run_perm_write(R, out_path);
-        if (g_ctx) (void)hpgv_set_perm_labels(g_ctx, NULL, 0);
+        if (g_ctx) (void)(R->tool == RUN_TDT_PERM ? hpgv_set_tdt_flips(g_ctx, NULL, 0) : hpgv_set_perm_labels(g_ctx, NULL, 0));
         if (R->PM) { free(R->PM->tmax); free(R->PM->t_obs); free(R->PM->n_ge); free(R->PM->head); free(R->PM->heads); free(R->PM); R->PM = NULL; }
     }
     if (R->RS) { free(R->RS->smiss); free(R->RS->serr); free(R->RS); }
@@ -699,7 +710,7 @@ static int run_file_held(run_t *R, const char *vcf_path, const char *ped_path, c
     if (rc) return rc;
     if (batch_bytes < (1u << 16)) batch_bytes = 1u << 16;
     const run_tool_t tool = R->tool; R->io_threads = default_io_threads();      /* the input: the PED (assoc, TDT, vcf2epi), the VCF's header */
-    if (!ped_path && (tool_chisq(tool) || tool == RUN_FISHER || tool == RUN_TDT || tool == RUN_VCF2EPI)) { snprintf(g_err, sizeof g_err, "this runner needs a PED file (ped_path is NULL)"); return HPGV_ERR_INVALID; }
+    if (!ped_path && (tool_chisq(tool) || tool == RUN_FISHER || tool_tdt(tool) || tool == RUN_VCF2EPI)) { snprintf(g_err, sizeof g_err, "this runner needs a PED file (ped_path is NULL)"); return HPGV_ERR_INVALID; }
     if (ped_path && (rc = ped_table_read(ped_path, &R->ped))) return rc;
     if (source_open(&R->rd.src, vcf_path)) { ped_table_free(&R->ped); snprintf(g_err, sizeof g_err, "cannot open VCF file %s", vcf_path); return HPGV_ERR_INVALID; }
     R->t_opened = now_s();
@@ -789,6 +800,15 @@ int hpgv_run_assoc_perm(const char *vcf_path, const char *ped_path, const char *
 
 int hpgv_run_tdt(const char *vcf_path, const char *ped_path, const char *out_path, size_t batch_bytes, long *n_variants_out) {
     return run_file(&(run_t){ .tool = RUN_TDT, .filters = g_filters }, vcf_path, ped_path, out_path, batch_bytes, n_variants_out);
+}
+
+/* the TDT run with max(T) family flips: hpgv_run_tdt's file and <out_path>.mperm */
+int hpgv_run_tdt_perm(const char *vcf_path, const char *ped_path, const char *out_path, int n_perms, uint64_t seed,
+                      size_t batch_bytes, long *n_variants_out) {
+    if (n_variants_out) *n_variants_out = 0;
+    if (!vcf_path || !ped_path || !out_path) { snprintf(g_err, sizeof g_err, "vcf_path, ped_path and out_path must not be NULL"); return HPGV_ERR_INVALID; }
+    if (n_perms < 1) { snprintf(g_err, sizeof g_err, "n_perms must be at least 1"); return HPGV_ERR_INVALID; }
+    return run_file(&(run_t){ .tool = RUN_TDT_PERM, .filters = g_filters, .n_perms = n_perms, .perm_seed = seed }, vcf_path, ped_path, out_path, batch_bytes, n_variants_out);
 }
 
 /* run_aggregate (src/vcf-tools/aggregate/aggregate_runner.c:23-222) */

@@ -139,10 +139,13 @@ typedef struct {
 } line_reader_t;
 
 /* the file runners' tools.  The first two are the assoc tasks, as hpgv_assoc_text takes them */
-/* RUN_CHISQ_PERM: the chi-square run with label permutation (hpgv_run_assoc_perm): RUN_CHISQ's file plus <out>.mperm */
-typedef enum { RUN_CHISQ = CHI_SQUARE, RUN_FISHER = FISHER, RUN_TDT, RUN_VCF2EPI, RUN_AGGREGATE, RUN_STATS, RUN_FILTER, RUN_SPLIT, RUN_CHISQ_PERM } run_tool_t;
+/* RUN_CHISQ_PERM: the chi-square run with label permutation (hpgv_run_assoc_perm): RUN_CHISQ's file plus <out>.mperm;
+ * RUN_TDT_PERM: the TDT run with family flips (hpgv_run_tdt_perm): RUN_TDT's file plus <out>.mperm */
+typedef enum { RUN_CHISQ = CHI_SQUARE, RUN_FISHER = FISHER, RUN_TDT, RUN_VCF2EPI, RUN_AGGREGATE, RUN_STATS, RUN_FILTER, RUN_SPLIT, RUN_CHISQ_PERM, RUN_TDT_PERM } run_tool_t;
 static inline int tool_chisq(run_tool_t t) { return t == RUN_CHISQ || t == RUN_CHISQ_PERM; }   /* writes the chi-square file */
-static inline int tool_sorts(run_tool_t t) { return tool_chisq(t) || t == RUN_FISHER || t == RUN_TDT; }   /* output sorted afterwards */
+static inline int tool_tdt(run_tool_t t) { return t == RUN_TDT || t == RUN_TDT_PERM; }         /* writes the TDT file */
+static inline int tool_perm(run_tool_t t) { return t == RUN_CHISQ_PERM || t == RUN_TDT_PERM; } /* writes <out>.mperm beside its file */
+static inline int tool_sorts(run_tool_t t) { return tool_chisq(t) || t == RUN_FISHER || tool_tdt(t); }   /* output sorted afterwards */
 static inline int tool_counts(run_tool_t t) { return t == RUN_AGGREGATE || t == RUN_STATS; }   /* engine: hpgv_stats_text_groups */
 
 typedef struct {
@@ -154,7 +157,7 @@ typedef struct {
     size_t bytes; int max_lines, n_lines;
     uint64_t *line_off; uint32_t *field_off; int32_t *status;
     int32_t *ints; double *dbl;                          /* 4 (assoc) or 2 (tdt) int arrays, 3 double arrays */
-    int32_t *n_ge; double *bmax;                         /* RUN_CHISQ_PERM: permutations at or above the observed statistic per line; the batch's maximum per permutation */
+    int32_t *n_ge; double *bmax;                         /* the permutation tools: permutations at or above the observed statistic per line; the batch's maximum per permutation */
     uint8_t *rows; size_t rows_cap; int row_width;       /* vcf2epi: one dataset row per line */
     int stats;                                           /* aggregate / stats: the counters of hpgv_stats_text */
     int32_t *c8, *merr, *midx, *mtab, *smiss, *cerr; double *hw;
@@ -207,7 +210,7 @@ typedef struct { split_file_t *f; int n, cap; sample_ids_t *ids; char *key; size
 /* the parsed setting of hpgv_run_set_record_filters (host_records.c), shared by reference with the runs started under it */
 typedef struct rec_filters rec_filters_t;
 
-/* RUN_CHISQ_PERM: what the run keeps for <out>.mperm -- the maxima merged over the batches (by the engine threads, under the
+/* the permutation tools (tool_perm): what the run keeps for <out>.mperm -- the maxima merged over the batches (by the engine threads, under the
  * pipeline's mutex) and, per written record in file order, "CHR\tPOS\tID", the observed statistic and its n_ge */
 typedef struct {
     double *tmax;
@@ -230,7 +233,7 @@ typedef struct run {
     uint32_t epi_aff, epi_unaff;                         /* vcf2epi: the class sizes */
     char *path, *path_rej; FILE *out, *out_rej, **gfd;   /* gfd: stats, one file per phenotype */
     split_files_t SF; run_stats_t *RS; order_track_t ord;
-    int n_perms; uint64_t perm_seed; run_perm_t *PM;      /* RUN_CHISQ_PERM */
+    int n_perms; uint64_t perm_seed; run_perm_t *PM;      /* the permutation tools */
     double t_opened, t_header, t_sort;
 } run_t;
 

@@ -267,6 +267,37 @@ int  hpgv_tdt_scan_dev(hpgv_ctx *ctx, const uint8_t *d_gt, int n_variants,
 int  hpgv_tdt_stats_dev(hpgv_ctx *ctx, const int32_t *d_tu, int n_variants,
                         double *d_odds, double *d_chisq, double *d_p, void *stream);
 
+/* ---- family flips of the TDT: max(T) empirical p-values (PLINK's tdt --mperm; no reference counterpart).  Shuffling labels is
+ *      the wrong null for the TDT; its permutation flips "transmitted" and "untransmitted" for every child of a family at once,
+ *      with probability 1/2 per family and permutation.  Family f contributes (t1_f, t2_f) to a variant's {t1, t2}
+ *      (tdt.c:175-239); flipped it contributes (t2_f, t1_f).  Under the signs s_p(f) = +1 (kept) / -1 (flipped)
+ *          t1_p + t2_p = t1 + t2 = n,       t1_p - t2_p = D_p = sum_f s_p(f) d_f,   d_f = t1_f - t2_f
+ *      so {t1_p, t2_p} = {(n + D_p) / 2, (n - D_p) / 2}, integral because t1_f + t2_f and t1_f - t2_f have the same parity: one i8
+ *      matrix product over the families with exact i32 sums on the matrix cores (csrc/hpgv_tdt_perm_kernels.h; K = the family
+ *      count, a third of the TDT row).  T_p(v) is the chi-square of {t1_p, t2_p} by the device function hpgv_tdt_stats_dev uses,
+ *      T_obs(v) the same on the observed counts.  A variant with t1 + t2 == 0 (chi-square -1) takes no part.  Outputs per call:
+ *          n_ge[v]      = #{p : T_p(v) >= T_obs(v)}  (int32; 0 when t1 + t2 == 0)
+ *          batch_max[p] = max over the call's variants of T_p(v)  (0.0 when no variant takes part)
+ *      Calls are stateless and merge as the label permutation's do: batch_max by element-wise maximum, then hpgv_perm_pvalues,
+ *      with NaN as t_obs for a variant whose chi-square is -1.  The resident sharded scan (hpgv_group_tdt) has no permutation form. */
+/* flips[p * n_families + f] in {0, 1} (1 = flipped) for family f of hpgv_set_families, one row per permutation; families the plan
+ * skips (a parent that is no column, no children) are ignored.  After hpgv_set_families (else HPGV_ERR_STATE); a group context
+ * gives every member the flips.  n_perms == 0 drops the flips; so does a new hpgv_set_families.  A value above 1 under a counted
+ * family: HPGV_ERR_INVALID.  Limits: more than 1 048 576 permutations per call, or a family with more than 63 counted children
+ * (|d_f| <= 2 x children must fit i8), is HPGV_ERR_UNSUPPORTED; the sign matrix takes (n_perms rounded up to 16) x (fast trios
+ * and slow families, each rounded up to 16) bytes of device memory and HPGV_ERR_NOMEM is returned when they are not there.  Not
+ * to be called while permutation calls of the context are in flight. */
+int  hpgv_set_tdt_flips(hpgv_ctx *ctx, const uint8_t *flips, int n_perms);
+/* d_gt in tdt layout, d_tu what hpgv_tdt_scan_dev wrote for it -> d_n_ge (n_variants int32), d_batch_max (n_perms doubles), both
+ * overwritten.  d_perm_tu (may be NULL; for tests and for callers who want another statistic): {t1_p, t2_p} as
+ * int32[(v * n_perms + p) * 2 + k].  d_gt 16-byte aligned, d_tu, d_batch_max and d_perm_tu 8-byte aligned.  Asynchronous on
+ * `stream`.  HPGV_ERR_STATE without flips.  With families of several children the call keeps their per-row differences in
+ * scratch of the context: such calls of one context go on one stream.  The launch reads the genotype matrix ceil(n_perms / 128)
+ * times, the passes of a row close together in time; ceil(n_variants / 512) x 8 x ceil(n_perms / 128) above 2^31 - 1 is
+ * HPGV_ERR_UNSUPPORTED (give the variants in several calls). */
+int  hpgv_tdt_perm_dev(hpgv_ctx *ctx, const uint8_t *d_gt, int n_variants, const uint8_t *d_is_x, const int32_t *d_tu,
+                       int32_t *d_n_ge, double *d_batch_max, int32_t *d_perm_tu /* may be NULL */, void *stream);
+
 /* d_gt in stats layout -> per variant 8 x int32:
  *   {n_00, n_01, n_10, n_11, missing_genotypes, missing_alleles, allele0, allele1}
  * (biallelic cells of genotypes_count[a1*2+a2]; allele counts include the called
@@ -383,6 +414,12 @@ int  hpgv_assoc_perm(hpgv_ctx *ctx, const uint8_t *gt, size_t pitch, int n_varia
 int  hpgv_tdt(hpgv_ctx *ctx, const uint8_t *gt, size_t pitch, int n_variants,
               const uint8_t *is_x, int32_t *t1, int32_t *t2,
               double *odds, double *chisq, double *p);
+/* hpgv_tdt plus the family flips' two outputs ("family flips" above): n_ge (n_variants int32) and batch_max (n_perms doubles of
+ * the flips set with hpgv_set_tdt_flips, overwritten).  Synchronous and thread-safe; a group context deals it to its members as
+ * hpgv_tdt.  HPGV_ERR_STATE without flips. */
+int  hpgv_tdt_perm(hpgv_ctx *ctx, const uint8_t *gt, size_t pitch, int n_variants,
+                   const uint8_t *is_x, int32_t *t1, int32_t *t2,
+                   double *odds, double *chisq, double *p, int32_t *n_ge, double *batch_max);
 int  hpgv_stats(hpgv_ctx *ctx, const uint8_t *gt, size_t pitch, int n_variants,
                 int32_t *counts8 /* n_variants x 8 */, double *hwe_chi2, double *hwe_p);
 /* same batch, additionally: sample_missing (n_samples ints, ACCUMULATED into; may be NULL) and, for
@@ -745,6 +782,12 @@ int  hpgv_assoc_perm_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, in
 int  hpgv_tdt_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, int max_lines, int *n_lines,
                    uint64_t *line_off, uint32_t *field_off, int32_t *status,
                    int32_t *t1, int32_t *t2, double *odds, double *chisq, double *p);
+/* hpgv_tdt_text plus n_ge (sized max_lines) and batch_max (n_perms doubles, overwritten): tokenizer, HPGV_LAYOUT_TDT layout, scan,
+ * statistics, then the flip kernels.  Lines that are not records (status 1) or that a record filter rejected
+ * (HPGV_LINE_FILTERED) take no part in batch_max and get n_ge = 0, as in hpgv_assoc_perm_text. */
+int  hpgv_tdt_perm_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, int max_lines, int *n_lines,
+                        uint64_t *line_off, uint32_t *field_off, int32_t *status,
+                        int32_t *t1, int32_t *t2, double *odds, double *chisq, double *p, int32_t *n_ge, double *batch_max);
 
 /* ---- label permutation, host side: no GPU call, no context, usable without a device ------------------------------- */
 /* n_perms label rows for hpgv_set_perm_labels, labels_out[p * n_samples + j]: row p is a uniform shuffle of the cohort
@@ -754,6 +797,10 @@ int  hpgv_tdt_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, int max_l
  * z ^ z >> 31): row p's key is mix(seed ^ mix(p)), its draw number i is mix(key + i), i = 0, 1, ...  Fisher-Yates over the
  * cohort columns in VCF order, from the last position down: position k - 1 swaps with position (draw * k) >> 64, k = n .. 2. */
 int  hpgv_perm_labels_shuffle(const uint8_t *condition, int n_samples, int n_perms, uint64_t seed, uint8_t *labels_out);
+/* n_perms flip rows for hpgv_set_tdt_flips, flips_out[p * n_families + f]: every family of every row flipped with probability
+ * 1/2, independently.  Deterministic in (seed, p, f), from the same counter-based generator and row keys as the label rows: row
+ * p's key is mix(seed ^ mix(p)), and family f's flip is bit f & 63 of mix(key + (f >> 6)) -- one 64-bit word per 64 families. */
+int  hpgv_perm_flips_shuffle(int n_families, int n_perms, uint64_t seed, uint8_t *flips_out);
 /* With P = n_perms permutations, t_max the element-wise maximum of every batch's batch_max (in any order; it is sorted here
  * and each variant's rank found by binary search):
  *     emp1[v] = (n_ge[v] + 1) / (P + 1)                           pointwise

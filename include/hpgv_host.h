@@ -303,6 +303,16 @@ int  hpgv_run_tdt(const char *vcf_path, const char *ped_path, const char *out_pa
  * the engine is started, and no file is written. */
 int  hpgv_run_assoc_perm(const char *vcf_path, const char *ped_path, const char *out_path, int n_perms, uint64_t seed,
                          size_t batch_bytes, long *n_variants_out);
+/* hpgv_run_tdt with max(T) family flips (include/hpgv.h "family flips"; PLINK's tdt --mperm): out_path is written byte for byte
+ * as hpgv_run_tdt writes it, and <out_path>.mperm beside it with the header and line format of hpgv_run_assoc_perm's
+ * ("#CHR\tPOS\tID\tEMP1\tEMP2", one line per written variant in the same sorted order, numbers as hpgv_host_format_f6 prints
+ * them); NaN where the variant's chi-square is -1 (nothing transmitted).  The n_perms flip rows are generated once per run by
+ * hpgv_perm_flips_shuffle(seed) over the PED's families (in order of first appearance, as hpgv_run_tdt builds them); every batch
+ * goes through hpgv_tdt_perm_text and its maxima are merged into the run's by element-wise maximum, so the result depends
+ * neither on batch_bytes nor on the number of engine threads or devices.  Same families, filters, record filters and input
+ * forms (plain, gzip, bgzip) as hpgv_run_tdt.  n_perms < 1 or a NULL path: HPGV_ERR_INVALID before anything is opened. */
+int  hpgv_run_tdt_perm(const char *vcf_path, const char *ped_path, const char *out_path, int n_perms, uint64_t seed,
+                       size_t batch_bytes, long *n_variants_out);
 /* record filters of the file-level runners (filter_records on every batch, assoc_runner.c:191; options
  * shared_options.c:42-47,86-115).  A negative member switches that filter off; NULL switches all off.  The
  * count-derived ones run on the GPU from the same tokenized batch:

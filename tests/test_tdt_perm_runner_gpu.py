@@ -1,0 +1,120 @@
+"""hpgv_run_tdt_perm: the TDT file runner with max(T) family flips.  Its result file is hpgv_run_tdt's byte for byte; its .mperm
+file holds hpgv_perm_pvalues of the reference's inputs -- the oracle's per-family counts under the flips of
+hpgv_perm_flips_shuffle, as tests/test_tdt_perm_gpu.py builds them -- whatever the batch size and the input form."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from helpers import hpgv
+from oracle import pyoracle as orc
+from test_host_logic_cpu import _bgzf
+from test_host_mirror_gpu import _families_csr, _write_inputs
+from test_tdt_perm_gpu import _chisq, _family_counts
+
+pytestmark = pytest.mark.gpu
+
+N_PERMS, SEED = 50, 20240611
+
+
+@pytest.fixture(scope="module")
+def host():
+    hpgv.build()
+    from importlib import import_module
+    b = import_module("hpg-variant_amd._build")
+    L = C.CDLL(b.HOSTLIB)
+    L.hpgv_run_tdt.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_long)]
+    L.hpgv_run_tdt_perm.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_uint64, C.c_size_t, C.POINTER(C.c_long)]
+    L.hpgv_host_format_f6.argtypes = [C.c_double, C.c_char_p]
+    L.hpgv_host_last_error.restype = C.c_char_p
+    yield L
+    L.hpgv_host_shutdown()
+
+
+@pytest.fixture(scope="module")
+def inputs(tmp_path_factory):
+    tmp = tmp_path_factory.mktemp("tdt_perm_runner")
+    rng = np.random.default_rng(23)
+    people, names, rows = _write_inputs(tmp, rng, 40, 6, 300)
+    rows.append(("22", "GT", ["0/0"] * len(names)))      # nothing transmitted: chi-square -1, NaN in the .mperm file
+    vcf = str(tmp / "in.vcf")
+    with open(vcf, "w") as f:
+        f.write("##fileformat=VCFv4.1\n##source=test\n")
+        f.write("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t" + "\t".join(names) + "\n")
+        for v, (chrom, fmt, samples) in enumerate(rows):
+            f.write("%s\t%d\trs%d\tA\tC\t.\tPASS\t.\t%s\t%s\n" % (chrom, 1000 + v, v, fmt, "\t".join(samples)))
+    packed = str(tmp / "in.vcf.gz")
+    open(packed, "wb").write(_bgzf(open(vcf, "rb").read(), 0x4000))
+    fam = tuple(np.array(a, np.uint8 if i == 4 else np.int32) for i, a in enumerate(_families_csr(people, names)))
+    codes = np.array([[orc.encode_sample(s, fmt.split(":").index("GT"), True) for s in samples] for _, fmt, samples in rows], np.uint8)
+    is_x = np.array([1 if c == "X" else 0 for c, _, _ in rows], np.uint8)
+    return dict(tmp=tmp, vcf=vcf, packed=packed, ped=str(tmp / "ped.txt").encode(), rows=rows, fam=fam, codes=codes, is_x=is_x)
+
+
+def _f6(host, x):
+    buf = C.create_string_buffer(320)
+    n = host.hpgv_host_format_f6(float(x), buf)
+    return buf.raw[:n].decode()
+
+
+def _expected_mperm(host, inputs, seed):
+    """the .mperm file by the reference: per-family counts of the oracle, flipped sums in numpy, chi-square of the oracle"""
+    fam, codes, is_x, rows = inputs["fam"], inputs["codes"], inputs["is_x"], inputs["rows"]
+    flips = hpgv.perm_flips_shuffle(len(fam[0]), N_PERMS, seed)
+    t1f, t2f = _family_counts(codes, fam, is_x)
+    F = flips.astype(np.int64).T
+    t1p, t2p = t1f @ (1 - F) + t2f @ F, t2f @ (1 - F) + t1f @ F
+    t1, t2 = t1f.sum(axis=1), t2f.sum(axis=1)
+    part = (t1 + t2) > 0
+    chi_obs, chi = _chisq(t1, t2), _chisq(t1p, t2p)
+    n_ge = np.where(part, (chi >= chi_obs[:, None]).sum(axis=1), 0).astype(np.int32)
+    tmax = np.max(np.where(part[:, None], chi, 0.0), axis=0, initial=0.0)
+    emp1, emp2 = hpgv.perm_pvalues(np.where(part, chi_obs, np.nan), n_ge, tmax)
+    assert part.sum() > 200 and (~part).any() and len(set(emp2[part])) > 5      # the comparison below says something
+    exp = inputs["tmp"] / ("expected_%d.mperm" % seed)
+    with open(exp, "w") as f:
+        f.write("#CHR\tPOS\tID\tEMP1\tEMP2\n")
+        for v, (chrom, _, _) in enumerate(rows):
+            f.write("%s\t%d\trs%d\t%s\t%s\n" % (chrom, 1000 + v, v, _f6(host, emp1[v]), _f6(host, emp2[v])))
+    return subprocess.run(["sort", "-k1,1h", "-k2,2n", str(exp)], capture_output=True, env=dict(os.environ, LC_ALL="C"), check=True).stdout
+
+
+def test_result_file_and_mperm(host, inputs):
+    tmp, rows = inputs["tmp"], inputs["rows"]
+    expected = _expected_mperm(host, inputs, SEED)
+    # the TDT runner's file
+    plain = str(tmp / "plain.tdt")
+    n = C.c_long(0)
+    assert host.hpgv_run_tdt(inputs["vcf"].encode(), inputs["ped"], plain.encode(), 1 << 16, C.byref(n)) == 0, host.hpgv_host_last_error()
+    assert n.value == len(rows)
+    want = open(plain, "rb").read()
+    for tag, path, batch in (("several", inputs["vcf"], 1 << 16), ("one", inputs["vcf"], 1 << 22), ("bgzf", inputs["packed"], 1 << 16)):
+        out = str(tmp / ("perm_%s.tdt" % tag))
+        n = C.c_long(0)
+        rc = host.hpgv_run_tdt_perm(path.encode(), inputs["ped"], out.encode(), N_PERMS, SEED, batch, C.byref(n))
+        assert rc == 0 and n.value == len(rows), (tag, host.hpgv_host_last_error())
+        assert open(out, "rb").read() == want, tag
+        assert open(out + ".mperm", "rb").read() == expected, tag
+    if os.path.getsize(inputs["vcf"]) <= (1 << 16):
+        pytest.fail("the VCF fits one batch of 64 KiB: the several-batches run is not one")
+
+
+def test_seed_fixes_the_file(host, inputs, tmp_path):
+    files = []
+    for tag, seed in (("a", SEED), ("b", SEED), ("c", SEED + 1)):
+        out = str(tmp_path / ("%s.tdt" % tag))
+        assert hpgv.run_tdt_perm(inputs["vcf"], inputs["ped"].decode(), out, N_PERMS, seed, 1 << 18) == len(inputs["rows"])
+        files.append(open(out + ".mperm", "rb").read())
+    assert files[0] == files[1] and files[0] != files[2]
+    assert files[2] == _expected_mperm(host, inputs, SEED + 1)
+
+
+def test_no_permutations_is_refused_and_writes_nothing(host, inputs):
+    out = str(inputs["tmp"] / "none.tdt")
+    for n_perms in (0, -3):
+        assert host.hpgv_run_tdt_perm(inputs["vcf"].encode(), inputs["ped"], out.encode(), n_perms, SEED, 1 << 16, None) == hpgv.ERR_INVALID
+    assert host.hpgv_run_tdt_perm(inputs["vcf"].encode(), inputs["ped"], None, N_PERMS, SEED, 1 << 16, None) == hpgv.ERR_INVALID
+    assert host.hpgv_run_tdt_perm(None, inputs["ped"], out.encode(), N_PERMS, SEED, 1 << 16, None) == hpgv.ERR_INVALID
+    assert not os.path.exists(out) and not os.path.exists(out + ".mperm")
