@@ -28,6 +28,8 @@ EPI_KERNEL_NAMES = {EPI_KERNEL_NONE: "none", EPI_KERNEL_PAIRS_MFMA: "k_epi_pairs
                     EPI_KERNEL_COMBS_WIDE: "k_epi_combs_wide"}
 COND_UNAFFECTED, COND_AFFECTED, COND_OTHER = 0, 1, 2
 SEX_MALE, SEX_FEMALE, SEX_UNKNOWN = 0, 1, 2
+# the model tests' order in chisq5 / p5 (HPGV_MODEL_* of include/hpgv.h)
+MODEL_GENO, MODEL_TREND, MODEL_ALLELIC, MODEL_DOM, MODEL_REC = range(5)
 LAYOUT_ASSOC, LAYOUT_TDT, LAYOUT_STATS, LAYOUT_STATS_GROUPS, LAYOUT_MENDEL, LAYOUT_EPI = 0, 1, 2, 3, 4, 5
 GT_MISSING = 0xFF
 # the tokenizer's tile records that hpgv_bgzf_verify_tiles_dev leaves (csrc/hpgv_text2_kernels.h: TOK2_TILE, struct TokAgg2 { TokAgg
@@ -64,6 +66,7 @@ SYMBOLS = [
     "hpgv_text_partition_bgzf", "hpgv_text_multisplit_bgzf",
     "hpgv_set_perm_labels", "hpgv_assoc_perm_dev", "hpgv_assoc_perm", "hpgv_assoc_perm_text", "hpgv_perm_labels_shuffle", "hpgv_perm_pvalues",
     "hpgv_set_tdt_flips", "hpgv_tdt_perm_dev", "hpgv_tdt_perm", "hpgv_tdt_perm_text", "hpgv_perm_flips_shuffle",
+    "hpgv_assoc_model_scan_dev", "hpgv_assoc_model_stats_dev", "hpgv_assoc_trend_perm_dev", "hpgv_assoc_model", "hpgv_assoc_model_text",
 ]
 
 
@@ -222,6 +225,11 @@ def load():
     L.hpgv_tdt_perm.argtypes = [vp, vp, sz, i32, vp] + [vp] * 7
     L.hpgv_tdt_perm_text.argtypes = [vp, C.c_char_p, sz, i32, C.POINTER(i32), vp, vp, vp] + [vp] * 7
     L.hpgv_perm_flips_shuffle.argtypes = [i32, i32, u64, vp]
+    L.hpgv_assoc_model_scan_dev.argtypes = [vp, vp, i32, vp, vp]
+    L.hpgv_assoc_model_stats_dev.argtypes = [vp, vp, i32, vp, vp, vp]
+    L.hpgv_assoc_trend_perm_dev.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
+    L.hpgv_assoc_model.argtypes = [vp, vp, sz, i32] + [vp] * 5
+    L.hpgv_assoc_model_text.argtypes = [vp, C.c_char_p, sz, i32, C.POINTER(i32), vp, vp, vp] + [vp] * 5
     _lib = L
     return L
 
@@ -259,6 +267,24 @@ def run_tdt_perm(vcf_path, ped_path, out_path, n_perms, seed, batch_bytes=1 << 2
                              int(seed) & 0xFFFFFFFFFFFFFFFF, batch_bytes, C.byref(n))
     if rc != OK:
         raise HpgvError("hpgv_run_tdt_perm -> %d: %s" % (rc, (H.hpgv_host_last_error() or b"").decode(errors="replace")))
+    return n.value
+
+
+def run_assoc_model(vcf_path, ped_path, out_path, n_perms=0, seed=0, batch_bytes=1 << 22):
+    """hpgv_run_assoc_model of libhpgv_host.so (include/hpgv_host.h): the model tests' file at out_path and, with n_perms >= 1,
+    EMP1 / EMP2 of the trend statistic in out_path + ".mperm".  Paths may be None (the call then fails with ERR_INVALID).
+    Returns the number of variants written."""
+    _build.build_host_lib()
+    H = C.CDLL(_build.HOSTLIB)
+    H.hpgv_run_assoc_model.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_uint64, C.c_size_t, C.POINTER(C.c_long)]
+    H.hpgv_host_last_error.restype = C.c_char_p
+    n = C.c_long(0)
+    enc = lambda q: None if q is None else os.fsencode(q)
+    rc = H.hpgv_run_assoc_model(enc(vcf_path), enc(ped_path), enc(out_path), n_perms, int(seed) & 0xFFFFFFFFFFFFFFFF, batch_bytes, C.byref(n))
+    if rc != OK:
+        e = HpgvError("hpgv_run_assoc_model -> %d: %s" % (rc, (H.hpgv_host_last_error() or b"").decode(errors="replace")))
+        e.code = rc
+        raise e
     return n.value
 
 
@@ -498,6 +524,42 @@ class Engine:
         k = min(nl.value, max_lines)
         return dict(n_lines=nl.value, status=status[:k], A1=A1[:k], A2=A2[:k], U1=U1[:k], U2=U2[:k], odds=odds[:k],
                     chisq=chisq[:k], p=p[:k], n_ge=n_ge[:k], batch_max=bmax[:self._n_perms])
+
+    def assoc_model(self, gt, perm=False):
+        """hpgv_assoc_model: counts8 (nv, 8), chisq5 and p5 (nv, 5; columns MODEL_*); perm=True adds the trend permutation's n_ge
+        per variant and batch_max per permutation of the labels set with set_perm_labels."""
+        gt = _np(gt, np.uint8)
+        nv, pitch = gt.shape
+        c8 = np.zeros((nv, 8), np.int32)
+        chisq5, p5 = np.zeros((nv, 5), np.float64), np.zeros((nv, 5), np.float64)
+        np_ = getattr(self, "_n_perms", 0)
+        n_ge, bmax = (np.zeros(nv, np.int32), np.zeros(max(np_, 1), np.float64)) if perm else (None, None)
+        self._chk(self.L.hpgv_assoc_model(self.h, _ptr(gt), pitch, nv, _ptr(c8), _ptr(chisq5), _ptr(p5), _ptr(n_ge), _ptr(bmax)))
+        res = dict(counts8=c8, chisq5=chisq5, p5=p5)
+        if perm:
+            res.update(n_ge=n_ge, batch_max=bmax[:np_])
+        return res
+
+    def assoc_model_text(self, text, max_lines=None, perm=False):
+        """hpgv_assoc_model_text: assoc_model on VCF data lines, the outputs per line; perm as in assoc_model."""
+        if isinstance(text, str):
+            text = text.encode()
+        if max_lines is None:
+            max_lines = text.count(b"\n") + 1
+        m = max(max_lines, 1)
+        c8 = np.zeros((m, 8), np.int32)
+        chisq5, p5 = np.zeros((m, 5), np.float64), np.zeros((m, 5), np.float64)
+        status = np.zeros(m, np.int32)
+        np_ = getattr(self, "_n_perms", 0)
+        n_ge, bmax = (np.zeros(m, np.int32), np.zeros(max(np_, 1), np.float64)) if perm else (None, None)
+        nl = C.c_int(0)
+        self._chk(self.L.hpgv_assoc_model_text(self.h, text, len(text), max_lines, C.byref(nl), None, None, _ptr(status),
+                                               _ptr(c8), _ptr(chisq5), _ptr(p5), _ptr(n_ge), _ptr(bmax)))
+        k = min(nl.value, max_lines)
+        res = dict(n_lines=nl.value, status=status[:k], counts8=c8[:k], chisq5=chisq5[:k], p5=p5[:k])
+        if perm:
+            res.update(n_ge=n_ge[:k], batch_max=bmax[:np_])
+        return res
 
     def assoc_view(self, task, gt2d, n_samples, is_x=None):
         """hpgv_assoc on a 2-D uint8 VIEW as it lies in memory (row stride = pitch): nothing is copied on the way,
@@ -768,6 +830,15 @@ class Engine:
 
     def assoc_perm_dev(self, d_gt, n_variants, d_counts, d_n_ge, d_batch_max, d_perm_counts=None, d_is_x=None, stream=None):
         self._chk(self.L.hpgv_assoc_perm_dev(self.h, d_gt, n_variants, d_is_x, d_counts, d_n_ge, d_batch_max, d_perm_counts, stream))
+
+    def assoc_model_scan(self, d_gt, n_variants, d_counts8, stream=None):
+        self._chk(self.L.hpgv_assoc_model_scan_dev(self.h, d_gt, n_variants, d_counts8, stream))
+
+    def assoc_model_stats(self, d_counts8, n_variants, d_chisq5, d_p5, stream=None):
+        self._chk(self.L.hpgv_assoc_model_stats_dev(self.h, d_counts8, n_variants, d_chisq5, d_p5, stream))
+
+    def assoc_trend_perm_dev(self, d_gt, n_variants, d_counts8, d_n_ge, d_batch_max, d_perm_sums=None, stream=None):
+        self._chk(self.L.hpgv_assoc_trend_perm_dev(self.h, d_gt, n_variants, d_counts8, d_n_ge, d_batch_max, d_perm_sums, stream))
 
     def assoc_fisher(self, d_counts, n_variants, d_odds, d_p, stream=None):
         self._chk(self.L.hpgv_assoc_fisher_dev(self.h, d_counts, n_variants, d_odds, d_p, stream))

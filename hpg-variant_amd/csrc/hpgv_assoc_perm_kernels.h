@@ -23,8 +23,15 @@
 // the 16 lanes of a row and added with one atomic per (variant, workgroup); the maxima are reduced over the lane groups,
 // over the four waves in LDS, and merged with one atomicMax per (permutation, workgroup) on the f64 bit pattern read as
 // an unsigned 64-bit integer (the values are >= +0 and never NaN, so the integer order is the numeric one).
+//
+// Forms.  The kernel has a compile-time form: the statistic decides what the two operand planes hold and what the epilogue
+// makes of the two sums; tile, lane maps, staging, reductions and atomics are the same code.
+//   PERM_ALLELIC  planes (c1, c2) above, sums {A1_p, A2_p}, assoc_chisq_value of the permuted 2 x 2 allele table
+//   PERM_TREND    planes (valid, dosage) of perm_planes_trend, sums {R_p, D_p}, trend_chisq_value(N, W1, W2, R_p, D_p)
+//                 (hpgv_assoc_model_kernels.h) with N, W1, W2 of the observed class counts: they do not depend on the labels
 #pragma once
 #include "hpgv_kernels.h"
+#include "hpgv_assoc_model_kernels.h"
 
 namespace hpgv {
 
@@ -51,21 +58,35 @@ __device__ __forceinline__ void perm_planes(uint32_t w, bool x, uint32_t &c1, ui
     c2 = x ? x2 : a2;
 }
 
+// the trend form's planes, one i8 per byte: valid = 1 for a byte without a 0xF nibble, dosage = its genotype class (the
+// nibbles of a valid byte that are not 0): 0, 1 or 2.  Summed over the labelled columns they give {R_p, D_p}
+__device__ __forceinline__ void perm_planes_trend(uint32_t w, uint32_t &valid, uint32_t &dosage) {
+    const uint32_t nf = nib_not_f(w);
+    const uint32_t vb = nf & (nf >> 4) & 0x08080808u;  // bit 3 of a byte: both nibbles are called
+    const uint32_t nz = nib_nonzero(w) & (vb | (vb << 4));
+    valid = vb >> 3;
+    dosage = ((nz >> 3) & 0x01010101u) + ((nz >> 7) & 0x01010101u);
+}
+
+enum { PERM_ALLELIC = 0, PERM_TREND = 1 };
+
 struct PermArgs {
     const uint8_t *gt;               // assoc layout, rows `pitch` bytes apart, pads 0xFF
     size_t pitch;
     int chunks;                      // pitch / 16
     int n_variants;
-    const uint8_t *is_x;             // per variant, may be null
-    const int4 *counts;              // observed {A1, A2, U1, U2} of hpgv_assoc_scan_dev
+    const uint8_t *is_x;             // per variant, may be null (PERM_TREND: not read)
+    const int4 *counts;              // observed {A1, A2, U1, U2} of hpgv_assoc_scan_dev; PERM_TREND: the counts8 of
+                                     // hpgv_assoc_model_scan_dev, two int4 per variant
     const uint8_t *labels;           // [label_rows x pitch] i8 0 / 1 in the layout's column order, 0 under the pads
     int n_perms, label_rows;
     const uint8_t *skip;             // per variant, may be null: != 0 = the row takes no part (n_ge stays 0)
     int *n_ge;                       // [n_variants], zeroed before the launch
     unsigned long long *batch_max;   // [n_perms] f64 bit patterns, zeroed before the launch
-    int *perm_counts;                // [(v * n_perms + p) * 2 + k] or null
+    int *perm_counts;                // [(v * n_perms + p) * 2 + k] or null: the two sums of the form
 };
 
+template <int FORM>
 __global__ __launch_bounds__(256) void k_assoc_perm(const PermArgs A) {
     __shared__ uint4 lbl[2][PERM_PT * PERM_LDS_ROW];
     __shared__ unsigned long long wg_max[PERM_PT];
@@ -74,7 +95,7 @@ __global__ __launch_bounds__(256) void k_assoc_perm(const PermArgs A) {
     const int v_lane = (int)blockIdx.x * PERM_VT + wave * 16 + col;       // the variant whose bytes this lane loads
     const int p0 = (int)blockIdx.y * PERM_PT;
     const bool v_ok = v_lane < A.n_variants;
-    const bool x = v_ok && A.is_x != nullptr && A.is_x[v_lane] != 0;
+    const bool x = FORM == PERM_ALLELIC && v_ok && A.is_x != nullptr && A.is_x[v_lane] != 0;
     const uint8_t *row = A.gt + (size_t)(v_ok ? v_lane : 0) * A.pitch;
     const int steps = (A.chunks + 3) / 4;
 
@@ -117,10 +138,17 @@ __global__ __launch_bounds__(256) void k_assoc_perm(const PermArgs A) {
         perm_i32x4 a1, a2;
         {
             uint32_t c1, c2;
-            perm_planes(g.x, x, c1, c2); a1[0] = (int)c1; a2[0] = (int)c2;
-            perm_planes(g.y, x, c1, c2); a1[1] = (int)c1; a2[1] = (int)c2;
-            perm_planes(g.z, x, c1, c2); a1[2] = (int)c1; a2[2] = (int)c2;
-            perm_planes(g.w, x, c1, c2); a1[3] = (int)c1; a2[3] = (int)c2;
+            if constexpr (FORM == PERM_TREND) {
+                perm_planes_trend(g.x, c1, c2); a1[0] = (int)c1; a2[0] = (int)c2;
+                perm_planes_trend(g.y, c1, c2); a1[1] = (int)c1; a2[1] = (int)c2;
+                perm_planes_trend(g.z, c1, c2); a1[2] = (int)c1; a2[2] = (int)c2;
+                perm_planes_trend(g.w, c1, c2); a1[3] = (int)c1; a2[3] = (int)c2;
+            } else {
+                perm_planes(g.x, x, c1, c2); a1[0] = (int)c1; a2[0] = (int)c2;
+                perm_planes(g.y, x, c1, c2); a1[1] = (int)c1; a2[1] = (int)c2;
+                perm_planes(g.z, x, c1, c2); a1[2] = (int)c1; a2[2] = (int)c2;
+                perm_planes(g.w, x, c1, c2); a1[3] = (int)c1; a2[3] = (int)c2;
+            }
         }
         const uint4 *buf = lbl[s & 1];
 #pragma unroll
@@ -150,10 +178,14 @@ __global__ __launch_bounds__(256) void k_assoc_perm(const PermArgs A) {
     for (int r = 0; r < 4; ++r) {
         const int v = vr0 + r;
         const bool ok = v < A.n_variants && !(A.skip != nullptr && A.skip[v] != 0);
-        int4 o = make_int4(0, 0, 0, 0);
-        if (ok) o = A.counts[v];
+        int4 o = make_int4(0, 0, 0, 0), o2 = o;                            // trend: {r0, r1, r2, s0}, {s1, s2, miss_aff, miss_unaff}
+        if constexpr (FORM == PERM_TREND) { if (ok) { o = A.counts[2 * (size_t)v]; o2 = A.counts[2 * (size_t)v + 1]; } }
+        else if (ok) o = A.counts[v];
         const int R1 = o.x + o.z, R2 = o.y + o.w;
-        const double t_obs = assoc_chisq_value(o.x, o.y, o.z, o.w);       // NaN for an empty margin (and for a row left out)
+        // trend: what does not depend on the labels
+        const int n1 = o.y + o2.x, n2 = o.z + o2.y, N = o.x + o.w + n1 + n2, W1 = n1 + 2 * n2, W2 = n1 + 4 * n2;
+        // NaN for an empty margin (and for a row left out)
+        const double t_obs = FORM == PERM_TREND ? trend_chisq_value(N, W1, W2, o.x + o.y + o.z, o.y + 2 * o.z) : assoc_chisq_value(o.x, o.y, o.z, o.w);
         int cnt = 0;
 #pragma unroll
         for (int n = 0; n < PERM_NT; ++n) {
@@ -162,7 +194,9 @@ __global__ __launch_bounds__(256) void k_assoc_perm(const PermArgs A) {
                 const int a = acc1[n][r], c = acc2[n][r];
                 if (A.perm_counts != nullptr)
                     *reinterpret_cast<int2 *>(A.perm_counts + ((size_t)v * (size_t)A.n_perms + (size_t)p) * 2) = make_int2(a, c);
-                const double t = assoc_chisq_value(a, c, R1 - a, R2 - c);
+                double t;
+                if constexpr (FORM == PERM_TREND) t = trend_chisq_value(N, W1, W2, a, c);
+                else t = assoc_chisq_value(a, c, R1 - a, R2 - c);
                 if (t >= t_obs) ++cnt;                                     // false when either is NaN
                 if (t > pmax[n]) pmax[n] = t;                              // a NaN never enters
             }

@@ -1,14 +1,19 @@
 // hpgv_perm_capi.hip -- C ABI of the max(T) permutations (include/hpgv.h "label permutation", "family flips"): the label rows
 // of the association test and the flip rows of the TDT of a context, the device-resident launches of k_assoc_perm and
 // k_tdt_perm, the synchronous entry points on a host batch and on a text, and the host-only helpers (label shuffle, flip
-// generator, empirical p-values).
+// generator, empirical p-values).  The genotypic model tests (include/hpgv.h "model tests") live here too: their class scan and
+// statistics kernels, and the trend form of k_assoc_perm behind the same launcher and staging as the allelic one.
 #include "hpgv_internal.h"
+#include "hpgv_assoc_model_kernels.h"
 #include "hpgv_assoc_perm_kernels.h"
 #include "hpgv_tdt_perm_kernels.h"
 
 namespace {
 
-constexpr int kMaxPerms = 1 << 20;      // PERM_PT permutations per workgroup row of the grid: far below the grid's 65 535 rows
+static_assert(hpgv::MODEL_GENO == HPGV_MODEL_GENO && hpgv::MODEL_TREND == HPGV_MODEL_TREND && hpgv::MODEL_ALLELIC == HPGV_MODEL_ALLELIC &&
+              hpgv::MODEL_DOM == HPGV_MODEL_DOM && hpgv::MODEL_REC == HPGV_MODEL_REC, "the kernels' test order is the header's");
+
+constexpr int kMaxPerms = 1 << 20;     // PERM_PT permutations per workgroup row of the grid: far below the grid's 65 535 rows
 
 int perm_state_check(const hpgv_ctx *ctx) {
     if (!ctx->assoc.set) return fail(ctx, HPGV_ERR_STATE, "hpgv_set_cohort has not been called");
@@ -16,8 +21,9 @@ int perm_state_check(const hpgv_ctx *ctx) {
     return HPGV_OK;
 }
 
-// the launch: n_ge and batch_max zeroed on the stream, then the kernel
-int perm_launch(hpgv_ctx *ctx, const uint8_t *d_gt, int n_variants, const uint8_t *d_is_x, const int32_t *d_counts, const uint8_t *d_skip,
+// the launch: n_ge and batch_max zeroed on the stream, then the kernel in its form (hpgv::PERM_ALLELIC: d_counts of
+// hpgv_assoc_scan_dev; hpgv::PERM_TREND: the counts8 of hpgv_assoc_model_scan_dev, no d_is_x)
+int perm_launch(hpgv_ctx *ctx, int form, const uint8_t *d_gt, int n_variants, const uint8_t *d_is_x, const int32_t *d_counts, const uint8_t *d_skip,
                 int32_t *d_n_ge, double *d_batch_max, int32_t *d_perm_counts, hipStream_t st) {
     HIPCHK(ctx, hipMemsetAsync(d_batch_max, 0, (size_t)ctx->n_perms * sizeof(double), st));
     if (n_variants == 0) return HPGV_OK;
@@ -29,7 +35,73 @@ int perm_launch(hpgv_ctx *ctx, const uint8_t *d_gt, int n_variants, const uint8_
     A.skip = d_skip; A.n_ge = d_n_ge; A.batch_max = (unsigned long long *)d_batch_max; A.perm_counts = d_perm_counts;
     const dim3 grid((unsigned)((n_variants + hpgv::PERM_VT - 1) / hpgv::PERM_VT), (unsigned)((ctx->n_perms + hpgv::PERM_PT - 1) / hpgv::PERM_PT));
     // (option "profile": the kernel's time is the statistics time of hpgv_last_kernel_ms)
-    return launch_profiled(ctx, st, 1, [&] { hipLaunchKernelGGL(hpgv::k_assoc_perm, grid, dim3(256), 0, st, A); });
+    return launch_profiled(ctx, st, 1, [&] {
+        if (form == hpgv::PERM_TREND) hipLaunchKernelGGL(hpgv::k_assoc_perm<hpgv::PERM_TREND>, grid, dim3(256), 0, st, A);
+        else hipLaunchKernelGGL(hpgv::k_assoc_perm<hpgv::PERM_ALLELIC>, grid, dim3(256), 0, st, A);
+    });
+}
+
+/* ---- model tests ---------------------------------------------------------------------------------------------------- */
+
+// the class scan on `st`: k_assoc_scan_pipe's grid (variants_per_wave consecutive rows per wave, four waves per workgroup)
+int model_scan_launch(hpgv_ctx *ctx, const uint8_t *d_gt, int n_variants, int32_t *d_counts8, hipStream_t st) {
+    const Layout &L = ctx->assoc;
+    if (L.chunks > hpgv::MODEL_MAX_CHUNKS)
+        return fail(ctx, HPGV_ERR_UNSUPPORTED, "rows of %d chunks: the class scan's packed 16-bit counters take at most %d", L.chunks, hpgv::MODEL_MAX_CHUNKS);
+    const int vpw = (int)ctx->vpw;
+    const long waves = ((long)n_variants + vpw - 1) / vpw;
+    const unsigned blocks = (unsigned)((waves + 3) / 4);
+    return launch_profiled(ctx, st, 0, [&] {
+        if (ctx->nontemporal)
+            hipLaunchKernelGGL((hpgv::k_assoc_model_scan<true, 4, 4>), dim3(blocks), dim3(256), 0, st, d_gt, L.pitch, n_variants, ctx->chunksA, L.chunks,
+                               ctx->nA, ctx->nU, (int4 *)d_counts8, vpw);
+        else
+            hipLaunchKernelGGL((hpgv::k_assoc_model_scan<false, 4, 4>), dim3(blocks), dim3(256), 0, st, d_gt, L.pitch, n_variants, ctx->chunksA, L.chunks,
+                               ctx->nA, ctx->nU, (int4 *)d_counts8, vpw);
+    });
+}
+
+int model_stats_launch(hpgv_ctx *ctx, const int32_t *d_counts8, int n_variants, double *d_chisq5, double *d_p5, hipStream_t st) {
+    return launch_profiled(ctx, st, 1, [&] {
+        hipLaunchKernelGGL(hpgv::k_assoc_model_stats, dim3((unsigned)((n_variants + 255) / 256)), dim3(256), 0, st, (const int4 *)d_counts8, n_variants, d_chisq5, d_p5);
+    });
+}
+
+// the back half of hpgv_assoc_model and hpgv_assoc_model_text: the laid-out matrix of a staged call -> class scan, the five
+// statistics, with `perm` the trend form of the permutation kernel -> the caller's arrays.  skip (host, may be null): rows
+// that take no part in the permutation
+int model_finish(hpgv_ctx *ctx, Slot *s, const Staged &S, bool perm, const uint8_t *skip, int32_t *counts8, double *chisq5, double *p5,
+                 int32_t *n_ge, double *batch_max) {
+    int rc;
+    const int nv = S.n;
+    const size_t n = (size_t)nv, np = perm ? (size_t)ctx->n_perms : 0;
+    const size_t off_max = round_up(n * sizeof(int32_t), 16), off_skip = off_max + np * sizeof(double);
+    HIPCHK(ctx, s->tally.reserve_slack(n * 32 + 16));
+    HIPCHK(ctx, s->dbl.reserve_slack(n * 10 * sizeof(double) + 16));
+    if (perm) HIPCHK(ctx, s->perm.reserve_slack(off_skip + n + 16));
+    int32_t *d_counts8 = s->tally.as<int32_t>();
+    double *d_chisq5 = s->dbl.as<double>(), *d_p5 = d_chisq5 + 5 * n;
+    int32_t *d_n_ge = perm ? s->perm.as<int32_t>() : nullptr;
+    double *d_max = perm ? (double *)(s->perm.as<char>() + off_max) : nullptr;
+    uint8_t *d_skip = nullptr;
+    if (perm && skip && nv > 0) {
+        d_skip = s->perm.as<uint8_t>() + off_skip;
+        HIPCHK(ctx, hipMemcpyAsync(d_skip, skip, n, hipMemcpyHostToDevice, s->stream));
+    }
+    if (nv > 0) {
+        if ((rc = model_scan_launch(ctx, S.d_laid, nv, d_counts8, s->stream))) return rc;
+        if ((rc = model_stats_launch(ctx, d_counts8, nv, d_chisq5, d_p5, s->stream))) return rc;
+    }
+    if (perm && (rc = perm_launch(ctx, hpgv::PERM_TREND, S.d_laid, nv, nullptr, d_counts8, d_skip, d_n_ge, d_max, nullptr, s->stream))) return rc;
+    if (nv > 0) {
+        HIPCHK(ctx, hipMemcpyAsync(counts8, d_counts8, n * 32, hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(ctx, hipMemcpyAsync(chisq5, d_chisq5, n * 40, hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(ctx, hipMemcpyAsync(p5, d_p5, n * 40, hipMemcpyDeviceToHost, s->stream));
+        if (perm) HIPCHK(ctx, hipMemcpyAsync(n_ge, d_n_ge, n * 4, hipMemcpyDeviceToHost, s->stream));
+    }
+    if (perm) HIPCHK(ctx, hipMemcpyAsync(batch_max, d_max, np * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(ctx, hipStreamSynchronize(s->stream));
+    return HPGV_OK;
 }
 
 // the back half of the two synchronous entry points: the laid-out matrix of a staged call -> scan, chi-square, permutation
@@ -57,7 +129,7 @@ int perm_finish(hpgv_ctx *ctx, Slot *s, const Staged &S, const uint8_t *skip, in
         if ((rc = hpgv_assoc_scan_dev(ctx, S.d_laid, nv, S.d_isx, d_counts, s->stream))) return rc;
         if ((rc = hpgv_assoc_chisq_dev(ctx, d_counts, nv, d_odds, d_chisq, d_p, s->stream))) return rc;
     }
-    if ((rc = perm_launch(ctx, S.d_laid, nv, S.d_isx, d_counts, d_skip, d_n_ge, d_max, nullptr, s->stream))) return rc;
+    if ((rc = perm_launch(ctx, hpgv::PERM_ALLELIC, S.d_laid, nv, S.d_isx, d_counts, d_skip, d_n_ge, d_max, nullptr, s->stream))) return rc;
     if (nv > 0) {
         hipLaunchKernelGGL(hpgv::k_counts_to_soa, dim3((nv + 255) / 256), dim3(256), 0, s->stream,
                            (const int4 *)d_counts, nv, d_soa, d_soa + n, d_soa + 2 * n, d_soa + 3 * n);
@@ -237,7 +309,93 @@ int hpgv_assoc_perm_dev(hpgv_ctx *ctx, const uint8_t *d_gt, int n_variants, cons
     if (((uintptr_t)d_gt & 15) || ((uintptr_t)d_counts & 15) || ((uintptr_t)d_batch_max & 7) || ((uintptr_t)d_perm_counts & 7))
         return fail(ctx, HPGV_ERR_INVALID, "d_gt and d_counts must be 16-byte aligned, d_batch_max and d_perm_counts 8-byte aligned");
     DeviceGuard g(ctx->device);
-    return perm_launch(ctx, d_gt, n_variants, d_is_x, d_counts, nullptr, d_n_ge, d_batch_max, d_perm_counts, (hipStream_t)stream);
+    return perm_launch(ctx, hpgv::PERM_ALLELIC, d_gt, n_variants, d_is_x, d_counts, nullptr, d_n_ge, d_batch_max, d_perm_counts, (hipStream_t)stream);
+}
+
+/* ---- model tests: class scan, the five statistics, trend permutation ------------------------------------------------ */
+
+int hpgv_assoc_model_scan_dev(hpgv_ctx *ctx, const uint8_t *d_gt, int n_variants, int32_t *d_counts8, void *stream) {
+    ctx = first_member(ctx);
+    if (!ctx) return HPGV_ERR_INVALID;
+    if (!ctx->assoc.set) return fail(ctx, HPGV_ERR_STATE, "hpgv_set_cohort has not been called");
+    if (n_variants < 0 || (n_variants > 0 && (!d_gt || !d_counts8))) return fail(ctx, HPGV_ERR_INVALID, "bad scan arguments");
+    if (n_variants == 0) return HPGV_OK;
+    if (((uintptr_t)d_gt & 15) || ((uintptr_t)d_counts8 & 15)) return fail(ctx, HPGV_ERR_INVALID, "device buffers must be 16-byte aligned");
+    DeviceGuard g(ctx->device);
+    return model_scan_launch(ctx, d_gt, n_variants, d_counts8, (hipStream_t)stream);
+}
+
+int hpgv_assoc_model_stats_dev(hpgv_ctx *ctx, const int32_t *d_counts8, int n_variants, double *d_chisq5, double *d_p5, void *stream) {
+    ctx = first_member(ctx);
+    if (!ctx) return HPGV_ERR_INVALID;
+    if (n_variants < 0 || (n_variants > 0 && (!d_counts8 || !d_chisq5 || !d_p5))) return fail(ctx, HPGV_ERR_INVALID, "bad model stats arguments");
+    if (n_variants == 0) return HPGV_OK;
+    if (((uintptr_t)d_counts8 & 15) || ((uintptr_t)d_chisq5 & 7) || ((uintptr_t)d_p5 & 7))
+        return fail(ctx, HPGV_ERR_INVALID, "d_counts8 must be 16-byte aligned, d_chisq5 and d_p5 8-byte aligned");
+    DeviceGuard g(ctx->device);
+    return model_stats_launch(ctx, d_counts8, n_variants, d_chisq5, d_p5, (hipStream_t)stream);
+}
+
+int hpgv_assoc_trend_perm_dev(hpgv_ctx *ctx, const uint8_t *d_gt, int n_variants, const int32_t *d_counts8,
+                              int32_t *d_n_ge, double *d_batch_max, int32_t *d_perm_sums, void *stream) {
+    ctx = first_member(ctx);
+    if (!ctx) return HPGV_ERR_INVALID;
+    if (const int rc = perm_state_check(ctx)) return rc;
+    if (n_variants < 0 || !d_batch_max || (n_variants > 0 && (!d_gt || !d_counts8 || !d_n_ge))) return fail(ctx, HPGV_ERR_INVALID, "bad assoc_trend_perm arguments");
+    if (((uintptr_t)d_gt & 15) || ((uintptr_t)d_counts8 & 15) || ((uintptr_t)d_batch_max & 7) || ((uintptr_t)d_perm_sums & 7))
+        return fail(ctx, HPGV_ERR_INVALID, "d_gt and d_counts8 must be 16-byte aligned, d_batch_max and d_perm_sums 8-byte aligned");
+    DeviceGuard g(ctx->device);
+    return perm_launch(ctx, hpgv::PERM_TREND, d_gt, n_variants, nullptr, d_counts8, nullptr, d_n_ge, d_batch_max, d_perm_sums, (hipStream_t)stream);
+}
+
+int hpgv_assoc_model(hpgv_ctx *ctx, const uint8_t *gt, size_t pitch, int n_variants, int32_t *counts8, double *chisq5, double *p5,
+                     int32_t *n_ge, double *batch_max) {
+    HPGV_ABI_TRY
+    GROUP_DEAL(ctx, hpgv_assoc_model(m_, gt, pitch, n_variants, counts8, chisq5, p5, n_ge, batch_max))
+    if (!ctx) return HPGV_ERR_INVALID;
+    if (!ctx->assoc.set) return fail(ctx, HPGV_ERR_STATE, "hpgv_set_cohort has not been called");
+    if ((n_ge == nullptr) != (batch_max == nullptr)) return fail(ctx, HPGV_ERR_INVALID, "n_ge and batch_max: both (the trend permutation) or neither");
+    const bool perm = batch_max != nullptr;
+    if (perm) if (const int rc0 = perm_state_check(ctx)) return rc0;
+    if (n_variants < 0 || (n_variants > 0 && (!gt || !counts8 || !chisq5 || !p5))) return fail(ctx, HPGV_ERR_INVALID, "bad assoc_model arguments");
+    if (pitch < (size_t)ctx->assoc.n_samples) return fail(ctx, HPGV_ERR_INVALID, "pitch %zu < n_samples %d", pitch, ctx->assoc.n_samples);
+    if (n_variants == 0 && !perm) return HPGV_OK;
+    HPGV_LEASE_SLOT(ctx)
+    Staged S;
+    if ((rc = perm_stage(ctx, s, HPGV_LAYOUT_ASSOC, ctx->assoc, gt, pitch, n_variants, nullptr, &S))) return rc;
+    return model_finish(ctx, s, S, perm, nullptr, counts8, chisq5, p5, n_ge, batch_max);
+    HPGV_ABI_CATCH(ctx)
+}
+
+int hpgv_assoc_model_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, int max_lines, int *n_lines,
+                          uint64_t *line_off, uint32_t *field_off, int32_t *status, int32_t *counts8, double *chisq5, double *p5,
+                          int32_t *n_ge, double *batch_max) {
+    HPGV_ABI_TRY
+    GROUP_DEAL_TEXT(ctx, text, hpgv_assoc_model_text(m_, text, text_bytes, max_lines, n_lines, line_off, field_off, status, counts8, chisq5, p5, n_ge, batch_max))
+    if (!ctx) return HPGV_ERR_INVALID;
+    if (!ctx->assoc.set) return fail(ctx, HPGV_ERR_STATE, "hpgv_set_cohort has not been called");
+    if ((n_ge == nullptr) != (batch_max == nullptr)) return fail(ctx, HPGV_ERR_INVALID, "n_ge and batch_max: both (the trend permutation) or neither");
+    const bool perm = batch_max != nullptr;
+    if (perm) if (const int rc0 = perm_state_check(ctx)) return rc0;
+    if (!n_lines || max_lines < 0 || (text_bytes > 0 && !text) || (max_lines > 0 && (!counts8 || !chisq5 || !p5)))
+        return fail(ctx, HPGV_ERR_INVALID, "bad assoc_model_text arguments");
+    *n_lines = 0;
+    if (max_lines == 0 && !perm) return HPGV_OK;
+    std::vector<int32_t> own_status;             // (before the lease: queued copies into them end with the lease)
+    std::vector<uint8_t> skip;
+    HPGV_LEASE_SLOT(ctx)
+    Staged S;
+    if (max_lines > 0) {
+        if (!status && perm) { own_status.assign((size_t)max_lines, 0); status = own_status.data(); }
+        if ((rc = text_front(ctx, s, HPGV_LAYOUT_ASSOC, ctx->assoc, text, text_bytes, max_lines, n_lines, line_off, field_off, status, &S, true))) return rc;
+        if (perm) {
+            // the lines hpgv_assoc_text's callers drop take no part, as in hpgv_assoc_perm_text
+            HIPCHK(ctx, hipStreamSynchronize(s->stream));
+            perm_skip_lines(status, S.n, skip);
+        }
+    }
+    return model_finish(ctx, s, S, perm, skip.empty() ? nullptr : skip.data(), counts8, chisq5, p5, n_ge, batch_max);
+    HPGV_ABI_CATCH(ctx)
 }
 
 int hpgv_assoc_perm(hpgv_ctx *ctx, const uint8_t *gt, size_t pitch, int n_variants, const uint8_t *is_x,

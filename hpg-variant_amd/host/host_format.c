@@ -32,8 +32,9 @@ static int run_batch_lines(run_batch_t *b) {
     b->line_off = (uint64_t *)malloc(sizeof(uint64_t) * ((size_t)b->max_lines + 1));
     b->field_off = (uint32_t *)malloc(sizeof(uint32_t) * 10 * (size_t)b->max_lines);
     b->status = (int32_t *)malloc(sizeof(int32_t) * (size_t)b->max_lines);
-    b->ints = (int32_t *)malloc(sizeof(int32_t) * 4 * (size_t)b->max_lines);
-    b->dbl = (double *)malloc(sizeof(double) * 3 * (size_t)b->max_lines);
+    const int model = tool_model(b->run->tool);
+    b->ints = (int32_t *)malloc(sizeof(int32_t) * (model ? 8 : 4) * (size_t)b->max_lines);
+    b->dbl = (double *)malloc(sizeof(double) * (model ? 10 : 3) * (size_t)b->max_lines);
     if (b->row_width > 0) {
         free(b->rows);
         b->rows_cap = (size_t)b->max_lines * (size_t)b->row_width;
@@ -133,13 +134,23 @@ static int format_record(char *dst, size_t room, const run_batch_t *b, int i) {
      *   tdt    "%s\t%ld\t%s\t%s\t%s\t%d\t%d\t%6f\t%6f\t%6f\n"
      *   chisq  "%s\t%ld\t%s\t%s\t%d\t%d\t%6f\t%6f\t%s\t%d\t%d\t%6f\t%6f\t%6f\t%6f\t%6f\n"     fisher: without the chi-square column);
      * printf's number parsing and its generic %f were a third of the writer's time */
-    const size_t worst = (size_t)(lc + li + lr + la) + 24 + 4 * 12 + 7 * 320 + 20;      /* %f of the largest double: 316 characters */
+    const size_t worst = (size_t)(lc + li + lr + la) + 24 + 6 * 12 + 10 * 320 + 20;      /* %f of the largest double: 316 characters */
     if (room <= worst) return (int)worst;                            /* the caller grows the buffer and comes again */
     char *p = dst;
     p = PUT_STR(p, l + fo[0], lc); *p++ = '\t';
     p = put_i64(p, atol(l + fo[1])); *p++ = '\t';
     p = PUT_STR(p, l + fo[2], li); *p++ = '\t';
     p = PUT_STR(p, l + fo[3], lr); *p++ = '\t';
+    if (tool_model(tool)) {                               /* CHR POS ID A1 A2 AFF UNAFF, then chi-square and p of the five tests */
+        const int32_t *c = b->ints + 8 * (size_t)i;
+        const double *x = b->dbl + 5 * (size_t)i, *pv = b->dbl + 5 * (size_t)m + 5 * (size_t)i;
+        p = PUT_STR(p, l + fo[4], la); *p++ = '\t';
+        p = put_i64(p, c[0]); *p++ = '/'; p = put_i64(p, c[1]); *p++ = '/'; p = put_i64(p, c[2]); *p++ = '\t';
+        p = put_i64(p, c[3]); *p++ = '/'; p = put_i64(p, c[4]); *p++ = '/'; p = put_i64(p, c[5]);
+        for (int t = 0; t < 5; t++) { *p++ = '\t'; p = PUT_F6(p, x[t]); *p++ = '\t'; p = PUT_F6(p, pv[t]); }
+        *p++ = '\n'; *p = 0;
+        return (int)(p - dst);
+    }
     if (tool_tdt(tool)) {
         const int t1 = b->ints[i], t2 = b->ints[m + i];
         p = PUT_STR(p, l + fo[4], la); *p++ = '\t';

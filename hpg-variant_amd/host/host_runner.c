@@ -121,6 +121,9 @@ static void *pipe_engine(void *v) {
                 rc = hpgv_assoc_perm_text(g_ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status,
                                           b->ints, b->ints + m, b->ints + 2 * m, b->ints + 3 * m,
                                           b->dbl, b->dbl + m, b->dbl + 2 * m, b->n_ge, b->bmax); break;
+            case RUN_MODEL: case RUN_MODEL_PERM: what = "hpgv_assoc_model_text";
+                rc = hpgv_assoc_model_text(g_ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status,
+                                           b->ints, b->dbl, b->dbl + 5 * (size_t)m, tool == RUN_MODEL_PERM ? b->n_ge : NULL, tool == RUN_MODEL_PERM ? b->bmax : NULL); break;
             }
             if (rc || b->n_lines <= b->max_lines) break;
             free(b->mtab); b->mtab = NULL;
@@ -178,7 +181,7 @@ static int run_perm_add(run_t *R, const run_batch_t *b) {
         }
         M->head[M->n] = M->heads_len;                    /* CHR, POS as the result file prints it, ID */
         M->heads_len += (size_t)snprintf(M->heads + M->heads_len, need, "%.*s\t%ld\t%.*s", lc, l + fo[0], atol(l + fo[1]), li, l + fo[2]) + 1;
-        M->t_obs[M->n] = b->dbl[m + i];
+        M->t_obs[M->n] = R->tool == RUN_MODEL_PERM ? b->dbl[5 * (size_t)i + HPGV_MODEL_TREND] : b->dbl[m + i];
         if (R->tool == RUN_TDT_PERM && M->t_obs[M->n] < 0) M->t_obs[M->n] = NAN;      /* chi-square -1: nothing transmitted, no statistic */
         M->n_ge[M->n] = b->n_ge[i];
         M->n++;
@@ -321,7 +324,7 @@ static int run_cohort(run_t *R, const char *vcf_path, const char *ped_path) {
         free(fcol); free(mcol); free(coff); free(ccol); free(csex); free(done);
         break;
     }
-    case RUN_CHISQ: case RUN_CHISQ_PERM: case RUN_FISHER: case RUN_VCF2EPI: {
+    case RUN_CHISQ: case RUN_CHISQ_PERM: case RUN_FISHER: case RUN_VCF2EPI: case RUN_MODEL: case RUN_MODEL_PERM: {
         uint8_t *cond = (uint8_t *)malloc((size_t)n_samples + 1);
         for (int j = 0; j < n_samples; j++) cond[j] = HPGV_COND_OTHER;
         int matched = 0;
@@ -338,7 +341,7 @@ static int run_cohort(run_t *R, const char *vcf_path, const char *ped_path) {
         }
         if (!rc && (rc = hpgv_set_cohort(g_ctx, cond, n_samples))) host_fail("hpgv_set_cohort", rc);
         g_assoc_key.set = 0;
-        if (!rc && R->tool == RUN_CHISQ_PERM) {          /* the run's label rows, once: shuffles of the PED's conditions */
+        if (!rc && (R->tool == RUN_CHISQ_PERM || R->tool == RUN_MODEL_PERM)) {          /* the run's label rows, once: shuffles of the PED's conditions */
             uint8_t *labels = (uint8_t *)malloc((size_t)R->n_perms * (size_t)(n_samples > 0 ? n_samples : 1));
             if (!labels) rc = HPGV_ERR_NOMEM;
             if (!rc && (rc = hpgv_perm_labels_shuffle(cond, n_samples, R->n_perms, R->perm_seed, labels))) host_fail("hpgv_perm_labels_shuffle", rc);
@@ -368,7 +371,7 @@ static int run_cohort(run_t *R, const char *vcf_path, const char *ped_path) {
     /* --inh-dom / --inh-rec scan the assoc layout: the tools that have not installed it get it from the PED (PHENO 2
      * affected, 1 unaffected, as the assoc runner); vcf2epi keeps its own classes */
     if (!rc && rec_filters_inheritance(R->rf)) {
-        if (!tool_chisq(R->tool) && R->tool != RUN_FISHER && R->tool != RUN_VCF2EPI) {
+        if (!tool_chisq(R->tool) && !tool_model(R->tool) && R->tool != RUN_FISHER && R->tool != RUN_VCF2EPI) {
             uint8_t *cond = (uint8_t *)malloc((size_t)n_samples + 1);
             if (!cond) rc = HPGV_ERR_NOMEM;
             for (int j = 0; cond && j < n_samples; j++) cond[j] = HPGV_COND_OTHER;
@@ -516,6 +519,12 @@ static int run_headers(run_t *R) {
         order_track_keep(&R->ord, h, strlen(h));
         return HPGV_OK;
     }
+    case RUN_MODEL: case RUN_MODEL_PERM: {
+        const char *h = "#CHR\tPOS\tID\tA1\tA2\tAFF\tUNAFF\tCHISQ_GENO\tP_GENO\tCHISQ_TREND\tP_TREND\tCHISQ_ALLELIC\tP_ALLELIC\tCHISQ_DOM\tP_DOM\tCHISQ_REC\tP_REC";
+        fprintf(out, "%s\n", h);
+        order_track_keep(&R->ord, h, strlen(h));
+        return HPGV_OK;
+    }
     case RUN_TDT: case RUN_TDT_PERM: tdt_write_output_header(out); order_track_keep(&R->ord, "#CHR\tPOS\tID\tA1\tA2\tT\tU\tOR\tCHISQ\tP-VALUE", 38); return HPGV_OK;
     case RUN_VCF2EPI: {                                  /* room for the number of variants, then the class sizes (dataset_creator.c:186-193) */
         const uint32_t head[3] = {0, R->epi_aff, R->epi_unaff};
@@ -617,6 +626,7 @@ static int run_pipeline(run_t *R, size_t batch_bytes) {
                 R->written += b->n_pass; R->skipped += b->n_skip;
                 break;
             case RUN_CHISQ: case RUN_CHISQ_PERM: case RUN_FISHER: case RUN_TDT: case RUN_TDT_PERM: case RUN_VCF2EPI: case RUN_AGGREGATE: case RUN_STATS:
+            case RUN_MODEL: case RUN_MODEL_PERM:
                 if (write_batch(R->out, b, fmt + (fmt_set ? RUN_FMT_BUFS / 2 : 0), n_fmt, &wpool, &R->ord, use_fw ? &fw : NULL)) bad = "cannot write the result file";
                 for (int i = 0; i < b->n_lines; i++) if (record_passes(b, i)) R->written++;
                 if (tool_perm(R->tool) && !bad && run_perm_add(R, b)) bad = "out of memory for the permutation results";
@@ -710,7 +720,7 @@ static int run_file_held(run_t *R, const char *vcf_path, const char *ped_path, c
     if (rc) return rc;
     if (batch_bytes < (1u << 16)) batch_bytes = 1u << 16;
     const run_tool_t tool = R->tool; R->io_threads = default_io_threads();      /* the input: the PED (assoc, TDT, vcf2epi), the VCF's header */
-    if (!ped_path && (tool_chisq(tool) || tool == RUN_FISHER || tool_tdt(tool) || tool == RUN_VCF2EPI)) { snprintf(g_err, sizeof g_err, "this runner needs a PED file (ped_path is NULL)"); return HPGV_ERR_INVALID; }
+    if (!ped_path && (tool_chisq(tool) || tool_model(tool) || tool == RUN_FISHER || tool_tdt(tool) || tool == RUN_VCF2EPI)) { snprintf(g_err, sizeof g_err, "this runner needs a PED file (ped_path is NULL)"); return HPGV_ERR_INVALID; }
     if (ped_path && (rc = ped_table_read(ped_path, &R->ped))) return rc;
     if (source_open(&R->rd.src, vcf_path)) { ped_table_free(&R->ped); snprintf(g_err, sizeof g_err, "cannot open VCF file %s", vcf_path); return HPGV_ERR_INVALID; }
     R->t_opened = now_s();
@@ -796,6 +806,16 @@ int hpgv_run_assoc_perm(const char *vcf_path, const char *ped_path, const char *
     if (!vcf_path || !ped_path || !out_path) { snprintf(g_err, sizeof g_err, "vcf_path, ped_path and out_path must not be NULL"); return HPGV_ERR_INVALID; }
     if (n_perms < 1) { snprintf(g_err, sizeof g_err, "n_perms must be at least 1"); return HPGV_ERR_INVALID; }
     return run_file(&(run_t){ .tool = RUN_CHISQ_PERM, .filters = g_filters, .n_perms = n_perms, .perm_seed = seed }, vcf_path, ped_path, out_path, batch_bytes, n_variants_out);
+}
+
+/* the model tests' run: one line of five chi-squares and p-values per variant and, with n_perms >= 1, <out_path>.mperm of the
+ * trend statistic */
+int hpgv_run_assoc_model(const char *vcf_path, const char *ped_path, const char *out_path, int n_perms, uint64_t seed,
+                         size_t batch_bytes, long *n_variants_out) {
+    if (n_variants_out) *n_variants_out = 0;
+    if (!vcf_path || !ped_path || !out_path) { snprintf(g_err, sizeof g_err, "vcf_path, ped_path and out_path must not be NULL"); return HPGV_ERR_INVALID; }
+    if (n_perms < 0) { snprintf(g_err, sizeof g_err, "n_perms must not be negative"); return HPGV_ERR_INVALID; }
+    return run_file(&(run_t){ .tool = n_perms ? RUN_MODEL_PERM : RUN_MODEL, .filters = g_filters, .n_perms = n_perms, .perm_seed = seed }, vcf_path, ped_path, out_path, batch_bytes, n_variants_out);
 }
 
 int hpgv_run_tdt(const char *vcf_path, const char *ped_path, const char *out_path, size_t batch_bytes, long *n_variants_out) {

@@ -140,12 +140,15 @@ typedef struct {
 
 /* the file runners' tools.  The first two are the assoc tasks, as hpgv_assoc_text takes them */
 /* RUN_CHISQ_PERM: the chi-square run with label permutation (hpgv_run_assoc_perm): RUN_CHISQ's file plus <out>.mperm;
- * RUN_TDT_PERM: the TDT run with family flips (hpgv_run_tdt_perm): RUN_TDT's file plus <out>.mperm */
-typedef enum { RUN_CHISQ = CHI_SQUARE, RUN_FISHER = FISHER, RUN_TDT, RUN_VCF2EPI, RUN_AGGREGATE, RUN_STATS, RUN_FILTER, RUN_SPLIT, RUN_CHISQ_PERM, RUN_TDT_PERM } run_tool_t;
+ * RUN_TDT_PERM: the TDT run with family flips (hpgv_run_tdt_perm): RUN_TDT's file plus <out>.mperm;
+ * RUN_MODEL / RUN_MODEL_PERM: the model tests (hpgv_run_assoc_model) without and with <out>.mperm of the trend statistic */
+typedef enum { RUN_CHISQ = CHI_SQUARE, RUN_FISHER = FISHER, RUN_TDT, RUN_VCF2EPI, RUN_AGGREGATE, RUN_STATS, RUN_FILTER, RUN_SPLIT, RUN_CHISQ_PERM, RUN_TDT_PERM,
+               RUN_MODEL, RUN_MODEL_PERM } run_tool_t;
 static inline int tool_chisq(run_tool_t t) { return t == RUN_CHISQ || t == RUN_CHISQ_PERM; }   /* writes the chi-square file */
 static inline int tool_tdt(run_tool_t t) { return t == RUN_TDT || t == RUN_TDT_PERM; }         /* writes the TDT file */
-static inline int tool_perm(run_tool_t t) { return t == RUN_CHISQ_PERM || t == RUN_TDT_PERM; } /* writes <out>.mperm beside its file */
-static inline int tool_sorts(run_tool_t t) { return tool_chisq(t) || t == RUN_FISHER || tool_tdt(t); }   /* output sorted afterwards */
+static inline int tool_model(run_tool_t t) { return t == RUN_MODEL || t == RUN_MODEL_PERM; }   /* writes the model tests' file */
+static inline int tool_perm(run_tool_t t) { return t == RUN_CHISQ_PERM || t == RUN_TDT_PERM || t == RUN_MODEL_PERM; } /* writes <out>.mperm beside its file */
+static inline int tool_sorts(run_tool_t t) { return tool_chisq(t) || t == RUN_FISHER || tool_tdt(t) || tool_model(t); }   /* output sorted afterwards */
 static inline int tool_counts(run_tool_t t) { return t == RUN_AGGREGATE || t == RUN_STATS; }   /* engine: hpgv_stats_text_groups */
 
 typedef struct {
@@ -156,7 +159,8 @@ typedef struct {
     const char *dev_base; const void *dev_tiles; size_t dev_n_tiles;      /* where the decoded text begins on the device, and its tile records (or NULL) */
     size_t bytes; int max_lines, n_lines;
     uint64_t *line_off; uint32_t *field_off; int32_t *status;
-    int32_t *ints; double *dbl;                          /* 4 (assoc) or 2 (tdt) int arrays, 3 double arrays */
+    int32_t *ints; double *dbl;                          /* 4 (assoc) or 2 (tdt) int arrays, 3 double arrays; the model tests: counts8 per line, then
+                                                          * chisq5 per line and, from dbl + 5 * max_lines, p5 per line */
     int32_t *n_ge; double *bmax;                         /* the permutation tools: permutations at or above the observed statistic per line; the batch's maximum per permutation */
     uint8_t *rows; size_t rows_cap; int row_width;       /* vcf2epi: one dataset row per line */
     int stats;                                           /* aggregate / stats: the counters of hpgv_stats_text */

@@ -261,6 +261,55 @@ int  hpgv_set_perm_labels(hpgv_ctx *ctx, const uint8_t *labels, int n_perms);
 int  hpgv_assoc_perm_dev(hpgv_ctx *ctx, const uint8_t *d_gt, int n_variants, const uint8_t *d_is_x, const int32_t *d_counts,
                          int32_t *d_n_ge, double *d_batch_max, int32_t *d_perm_counts /* may be NULL */, void *stream);
 
+/* ---- model tests: the genotypic tests of a case/control scan (PLINK's --model; no reference counterpart).  The allelic
+ *      chi-square counts every diploid sample twice and so assumes Hardy-Weinberg equilibrium; these work on genotypes.
+ *
+ *      Genotype class of an HPGV8 byte, in any layout:
+ *          missing      either nibble is 0xF (this covers 0xFF and the layout's pad bytes)
+ *          0 (hom-ref)  byte 0x00
+ *          1 (het)      exactly one nibble is 0 and the other is in 1..14
+ *          2 (hom-alt)  both nibbles are in 1..14 ("1/2" counts as hom-alt, as assoc.c:112 counts it as two alternate alleles)
+ *      Dosage equals the class index.  Chromosome X gets no special rule, because these are genotype tests: d_is_x is not a
+ *      parameter of any call below.
+ *
+ *      Counts per variant, int32 x 8:  {r0, r1, r2, s0, s1, s2, miss_aff, miss_unaff}
+ *      r counts the affected cohort columns and s the unaffected ones; miss_* counts the group's real columns whose genotype
+ *      is missing (pads are never counted).  On a row in the assoc layout 2 r0 + r1 == A1, r1 + 2 r2 == A2, 2 s0 + s1 == U1
+ *      and s1 + 2 s2 == U2 of hpgv_assoc_scan_dev with d_is_x == NULL.
+ *
+ *      Statistics.  R = sum r, S = sum s, N = R + S, n_k = r_k + s_k.  Five tests in a fixed order (HPGV_MODEL_*);
+ *      chisq5[v][t] and p5[v][t] are doubles, everything is f64 without contraction.  Nothing is rejected for small cells: a
+ *      zero margin gives 0 / 0 = NaN with p = NaN, as the allelic chi-square already does.
+ *          GENO     Pearson chi-square of the 2 x 3 table, each expected value rowtot * coltot / N.
+ *                   df 2: p = exp(-chi2 / 2), NaN in gives NaN out, chi2 <= 0 gives 1
+ *          TREND    Cochran-Armitage, weights 0, 1, 2.  With W1 = n1 + 2 n2, W2 = n1 + 4 n2, D = r1 + 2 r2:
+ *                   chi2 = N (N D - R W1)^2 / (R (N - R) (N W2 - W1^2)).                      df 1, p as hpgv_assoc_chisq_dev's
+ *          ALLELIC  the chi-square of hpgv_assoc_chisq_dev on (2 r0 + r1, r1 + 2 r2, 2 s0 + s1, s1 + 2 s2): the same device
+ *                   function and argument order, so it equals hpgv_assoc's chisq bit for bit on non-X rows.   df 1
+ *          DOM      the same function on (r1 + r2, r0, s1 + s2, s0).                                          df 1
+ *          REC      the same function on (r2, r0 + r1, s2, s0 + s1).                                          df 1
+ *
+ *      Trend permutation.  Under a labelling y_p (the rows of hpgv_set_perm_labels: same state, same limits, same rules for
+ *      HPGV_COND_OTHER columns)
+ *          R_p = sum_j valid(v, j) y_p(j),   D_p = sum_j dosage(v, j) y_p(j)
+ *      an i8 product on the matrix cores as the label permutation's; T_p = the TREND statistic with (R, D) replaced by
+ *      (R_p, D_p) -- N, W1 and W2 do not depend on the labels -- and T_obs the same function on the observed (R, D).  Outputs,
+ *      NaN rules and merge rule are those of hpgv_assoc_perm_dev: n_ge[v] overwritten, batch_max[p] 0.0 when nothing enters,
+ *      batches merge by element-wise maximum, then hpgv_perm_pvalues. */
+enum { HPGV_MODEL_GENO = 0, HPGV_MODEL_TREND = 1, HPGV_MODEL_ALLELIC = 2, HPGV_MODEL_DOM = 3, HPGV_MODEL_REC = 4 };
+/* d_gt in assoc layout -> d_counts8[v] (int32 x 8), both 16-byte aligned.  A cohort whose rows have more than 262 080 16-byte
+ * chunks is HPGV_ERR_UNSUPPORTED (the scan's packed 16-bit per-lane counters; hpgv_set_cohort's own limit is lower). */
+int  hpgv_assoc_model_scan_dev(hpgv_ctx *ctx, const uint8_t *d_gt, int n_variants, int32_t *d_counts8, void *stream);
+/* d_counts8 (16-byte aligned) -> d_chisq5, d_p5: n_variants x 5 doubles each, [v * 5 + HPGV_MODEL_*] */
+int  hpgv_assoc_model_stats_dev(hpgv_ctx *ctx, const int32_t *d_counts8, int n_variants, double *d_chisq5, double *d_p5,
+                                void *stream);
+/* d_gt in assoc layout, d_counts8 what hpgv_assoc_model_scan_dev wrote for it -> d_n_ge (n_variants int32), d_batch_max
+ * (n_perms doubles), both overwritten.  d_perm_sums (may be NULL): {R_p, D_p} as int32[(v * n_perms + p) * 2 + k].
+ * Alignment as hpgv_assoc_perm_dev: d_gt and d_counts8 16 bytes, d_batch_max and d_perm_sums 8.  Asynchronous on `stream`.
+ * HPGV_ERR_STATE without labels.  The launch reads the genotype matrix ceil(n_perms / 128) times. */
+int  hpgv_assoc_trend_perm_dev(hpgv_ctx *ctx, const uint8_t *d_gt, int n_variants, const int32_t *d_counts8,
+                               int32_t *d_n_ge, double *d_batch_max, int32_t *d_perm_sums /* may be NULL */, void *stream);
+
 /* d_gt in tdt layout -> d_tu[v] = {t1, t2} (int32 x2) */
 int  hpgv_tdt_scan_dev(hpgv_ctx *ctx, const uint8_t *d_gt, int n_variants,
                        const uint8_t *d_is_x, int32_t *d_tu, void *stream);
@@ -411,6 +460,13 @@ int  hpgv_assoc(hpgv_ctx *ctx, int task, const uint8_t *gt, size_t pitch, int n_
 int  hpgv_assoc_perm(hpgv_ctx *ctx, const uint8_t *gt, size_t pitch, int n_variants, const uint8_t *is_x,
                      int32_t *A1, int32_t *A2, int32_t *U1, int32_t *U2,
                      double *odds, double *chisq, double *p, int32_t *n_ge, double *batch_max);
+/* The model tests ("model tests" above) of a host batch in VCF column order: counts8 (n_variants x 8 int32), chisq5 and p5
+ * (n_variants x 5 doubles, [v * 5 + HPGV_MODEL_*]) through the assoc layout, the class scan and the statistics kernel.  n_ge and
+ * batch_max both NULL: no permutation, and no labels are needed; both non-NULL: the trend permutation's outputs as
+ * hpgv_assoc_perm's (HPGV_ERR_STATE without labels); exactly one of them NULL: HPGV_ERR_INVALID.  Synchronous and thread-safe; a
+ * group context deals it to its members as hpgv_assoc. */
+int  hpgv_assoc_model(hpgv_ctx *ctx, const uint8_t *gt, size_t pitch, int n_variants,
+                      int32_t *counts8, double *chisq5, double *p5, int32_t *n_ge, double *batch_max);
 int  hpgv_tdt(hpgv_ctx *ctx, const uint8_t *gt, size_t pitch, int n_variants,
               const uint8_t *is_x, int32_t *t1, int32_t *t2,
               double *odds, double *chisq, double *p);
@@ -779,6 +835,14 @@ int  hpgv_assoc_perm_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, in
                           uint64_t *line_off, uint32_t *field_off, int32_t *status,
                           int32_t *A1, int32_t *A2, int32_t *U1, int32_t *U2,
                           double *odds, double *chisq, double *p, int32_t *n_ge, double *batch_max);
+/* hpgv_assoc_model on a text: tokenizer, HPGV_LAYOUT_ASSOC layout, class scan, statistics and -- with n_ge (sized max_lines)
+ * and batch_max (n_perms doubles, overwritten) both non-NULL -- the trend form of the permutation kernel; counts8 sized
+ * max_lines x 8, chisq5 and p5 max_lines x 5.  n_ge / batch_max as in hpgv_assoc_model.  Lines that are not records (status
+ * 1) or that a record filter rejected (HPGV_LINE_FILTERED) take no part in the permutation, exactly as in
+ * hpgv_assoc_perm_text.  The text path runs the kernel chain; it has no one-pass form. */
+int  hpgv_assoc_model_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, int max_lines, int *n_lines,
+                           uint64_t *line_off, uint32_t *field_off, int32_t *status,
+                           int32_t *counts8, double *chisq5, double *p5, int32_t *n_ge, double *batch_max);
 int  hpgv_tdt_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, int max_lines, int *n_lines,
                    uint64_t *line_off, uint32_t *field_off, int32_t *status,
                    int32_t *t1, int32_t *t2, double *odds, double *chisq, double *p);

@@ -303,6 +303,20 @@ int  hpgv_run_tdt(const char *vcf_path, const char *ped_path, const char *out_pa
  * the engine is started, and no file is written. */
 int  hpgv_run_assoc_perm(const char *vcf_path, const char *ped_path, const char *out_path, int n_perms, uint64_t seed,
                          size_t batch_bytes, long *n_variants_out);
+/* The model tests of a case/control scan (include/hpgv.h "model tests"; PLINK's --model): out_path gets the header line
+ *     #CHR POS ID A1 A2 AFF UNAFF CHISQ_GENO P_GENO CHISQ_TREND P_TREND CHISQ_ALLELIC P_ALLELIC CHISQ_DOM P_DOM CHISQ_REC P_REC
+ * and one line per written variant, tab-separated, sorted by chromosome and position as hpgv_run_assoc's file: A1 is REF and A2 is
+ * ALT as in the chi-square file, AFF is r0/r1/r2 and UNAFF is s0/s1/s2 (the genotype-class counts of the affected and the
+ * unaffected cohort columns: hom-ref / het / hom-alt), and the five chi-squares and p-values are printed as
+ * hpgv_host_format_f6 prints them (NaN for a zero margin).  Every batch goes through hpgv_assoc_model_text.
+ *   n_perms == 0  writes that file only;
+ *   n_perms >= 1  also writes <out_path>.mperm for the TREND statistic: header, line format, label generation
+ *                 (hpgv_perm_labels_shuffle(seed)) and independence from batch_bytes, engine threads and devices are those of
+ *                 hpgv_run_assoc_perm;
+ *   n_perms < 0 or a NULL path: HPGV_ERR_INVALID before the engine is started, and no file is written.
+ * Same cohort, filters, record filters and input forms (plain, gzip, bgzip) as hpgv_run_assoc. */
+int  hpgv_run_assoc_model(const char *vcf_path, const char *ped_path, const char *out_path, int n_perms, uint64_t seed,
+                          size_t batch_bytes, long *n_variants_out);
 /* hpgv_run_tdt with max(T) family flips (include/hpgv.h "family flips"; PLINK's tdt --mperm): out_path is written byte for byte
  * as hpgv_run_tdt writes it, and <out_path>.mperm beside it with the header and line format of hpgv_run_assoc_perm's
  * ("#CHR\tPOS\tID\tEMP1\tEMP2", one line per written variant in the same sorted order, numbers as hpgv_host_format_f6 prints
