@@ -103,9 +103,10 @@ def cross_check(codes, cond, c8, chisq5):
 
 
 @functools.lru_cache(maxsize=None)
-def case(width, nv, n_perms, quirks, strict_codes=False):
+def case(width, nv, n_perms, quirks, strict_codes=False, special=()):
     """A cohort of width = (affected, unaffected) columns with HPGV_COND_OTHER columns mixed in, nv rows (row 1 all missing, row 2
-    monomorphic) and n_perms label rows (row 0 the observed labelling; nobody and everybody affected among them from 5 rows on)."""
+    monomorphic) and n_perms label rows (row 0 the observed labelling; nobody and everybody affected among them from 5 rows on).
+    special: further special label rows, (row, kind) with kind "observed", "nobody" or "everybody", set after the fixed ones."""
     nA, nU = width
     rng = np.random.default_rng(7000 + 1000 * nA + 10 * nv + n_perms + (1 if quirks else 0))
     nO = max(2, (nA + nU) // 8)
@@ -121,6 +122,8 @@ def case(width, nv, n_perms, quirks, strict_codes=False):
         labels[0] = cond == 1
     if n_perms >= 5:
         labels[2], labels[n_perms - 1] = 0, 1
+    for row, kind in special:
+        labels[row] = {"observed": cond == 1, "nobody": 0, "everybody": 1}[kind]
     labels[:, ~cohort] = rng.integers(0, 2, size=(n_perms, int((~cohort).sum())))      # ignored, whatever they hold
     sc = strict(codes)
     c8 = counts8(sc, cond)

@@ -60,12 +60,27 @@ def _sorted(path):
 
 
 @pytest.fixture(scope="module")
-def expected(host, inputs):
-    """the two files from the Python path over the whole file in one call"""
+def expected_of(host, inputs):
+    """n_perms -> the two files from the Python path over the whole file in one call"""
+    made = {}
+
+    def of(n_perms):
+        if n_perms not in made:
+            made[n_perms] = _expected(host, inputs, n_perms)
+        return made[n_perms]
+    return of
+
+
+@pytest.fixture(scope="module")
+def expected(expected_of):
+    return expected_of(N_PERMS)
+
+
+def _expected(host, inputs, n_perms):
     tmp, rows = inputs["tmp"], inputs["rows"]
     e = hpgv.Engine(0)
     e.set_cohort(inputs["cond"])
-    e.set_perm_labels(hpgv.perm_labels_shuffle(inputs["cond"], N_PERMS, SEED))
+    e.set_perm_labels(hpgv.perm_labels_shuffle(inputs["cond"], n_perms, SEED))
     res = e.assoc_model_text(inputs["body"], perm=True)
     e.close()
     assert res["n_lines"] == len(rows) and not res["status"].any()
@@ -73,7 +88,8 @@ def expected(host, inputs):
     emp1, emp2 = hpgv.perm_pvalues(t_obs, res["n_ge"], res["batch_max"])
     # the comparisons below say something: most rows have a statistic, and the p-values vary from row to row
     assert np.isfinite(emp2).sum() > 200 and len(set(emp1[np.isfinite(emp1)])) > 5 and len(set(emp2[np.isfinite(emp2)])) > 1
-    with open(tmp / "expected.model", "w") as f, open(tmp / "expected.mperm", "w") as g:
+    model, mperm = tmp / ("expected_%d.model" % n_perms), tmp / ("expected_%d.mperm" % n_perms)
+    with open(model, "w") as f, open(mperm, "w") as g:
         f.write(HEADER)
         g.write("#CHR\tPOS\tID\tEMP1\tEMP2\n")
         for v, (chrom, _, _) in enumerate(rows):
@@ -81,14 +97,16 @@ def expected(host, inputs):
             stats = "\t".join("%s\t%s" % (_f6(host, res["chisq5"][v, t]), _f6(host, res["p5"][v, t])) for t in range(5))
             f.write("%s\t%d\trs%d\tA\tC\t%d/%d/%d\t%d/%d/%d\t%s\n" % (chrom, 1000 + v, v, c[0], c[1], c[2], c[3], c[4], c[5], stats))
             g.write("%s\t%d\trs%d\t%s\t%s\n" % (chrom, 1000 + v, v, _f6(host, emp1[v]), _f6(host, emp2[v])))
-    return _sorted(tmp / "expected.model"), _sorted(tmp / "expected.mperm")
+    return _sorted(model), _sorted(mperm)
 
 
 @pytest.mark.parametrize("form", ["plain", "gzip", "bgzip"])
 @pytest.mark.parametrize("batch", [1 << 16, 1 << 22])
-def test_model_file_and_mperm(inputs, expected, form, batch):
-    out = str(inputs["tmp"] / ("perm_%s_%d.model" % (form, batch)))
-    n = hpgv.run_assoc_model(inputs["paths"][form], inputs["ped"], out, N_PERMS, SEED, batch)
+@pytest.mark.parametrize("n_perms", [N_PERMS, 150])      # one pass of the permutation kernel; two
+def test_model_file_and_mperm(inputs, expected_of, form, batch, n_perms):
+    expected = expected_of(n_perms)
+    out = str(inputs["tmp"] / ("perm_%s_%d_%d.model" % (form, batch, n_perms)))
+    n = hpgv.run_assoc_model(inputs["paths"][form], inputs["ped"], out, n_perms, SEED, batch)
     assert n == len(inputs["rows"])
     got = open(out, "rb").read()
     assert got.split(b"\n") == expected[0].split(b"\n")

@@ -23,8 +23,14 @@ def _strict(codes):
     return np.where(((codes >> 4) == 15) | ((codes & 15) == 15), 0xFF, codes).astype(np.uint8)
 
 
+def _special_rows(labels, special, observed):
+    """further special label rows, (row, kind) with kind "observed", "nobody" or "everybody": set after the fixed ones"""
+    for row, kind in special:
+        labels[row] = {"observed": observed, "nobody": 0, "everybody": 1}[kind]
+
+
 @functools.lru_cache(maxsize=None)
-def _case(width, nv, n_perms, strict):
+def _case(width, nv, n_perms, strict, special=()):
     nA, nU = width
     rng = np.random.default_rng(1000 * nA + 10 * nv + n_perms + (1 if strict else 0))
     nO = max(2, (nA + nU) // 8)
@@ -41,6 +47,7 @@ def _case(width, nv, n_perms, strict):
     labels[0] = cond == 1                                # the observed labelling
     if n_perms >= 5:
         labels[2], labels[n_perms - 1] = 0, 1            # nobody affected; everybody affected
+    _special_rows(labels, special, cond == 1)
     labels[:, ~cohort] = rng.integers(0, 2, size=(n_perms, int((~cohort).sum())))      # ignored, whatever they hold
     sc = _strict(codes)
     obs = np.stack(orc.assoc_counts(sc, cond, is_x), axis=1)                            # [nv, 4]
@@ -108,9 +115,9 @@ def _expected(chi, t_obs):
 
 
 @functools.lru_cache(maxsize=None)
-def _reference(width, nv, n_perms, strict):
+def _reference(width, nv, n_perms, strict, special=()):
     """(n_ge, batch_max, t_obs) of a case from the engine's chi-square kernel on the ORACLE's permuted counts"""
-    c = _case(width, nv, n_perms, strict)
+    c = _case(width, nv, n_perms, strict, special)
     e = hpgv.Engine(0)
     chi = _chisq_dev(e, c["perm"].reshape(-1, 4)).reshape(nv, n_perms)
     t_obs = _chisq_dev(e, c["obs"])

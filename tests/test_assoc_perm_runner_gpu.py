@@ -58,17 +58,18 @@ def _f6(host, x):
     return buf.raw[:n].decode()
 
 
-def test_result_file_and_mperm(host, inputs):
+@pytest.mark.parametrize("n_perms", [N_PERMS, 150])      # one pass of the permutation kernel; two
+def test_result_file_and_mperm(host, inputs, n_perms):
     tmp, rows = inputs["tmp"], inputs["rows"]
     # the Python path over the whole file in one call
     e = hpgv.Engine(0)
     e.set_cohort(inputs["cond"])
-    e.set_perm_labels(hpgv.perm_labels_shuffle(inputs["cond"], N_PERMS, SEED))
+    e.set_perm_labels(hpgv.perm_labels_shuffle(inputs["cond"], n_perms, SEED))
     res = e.assoc_perm(inputs["codes"], inputs["is_x"])
     e.close()
     emp1, emp2 = hpgv.perm_pvalues(res["chisq"], res["n_ge"], res["batch_max"])
     assert np.isfinite(emp2).sum() > 200 and len(set(emp2[np.isfinite(emp2)])) > 5      # the comparison below says something
-    exp = tmp / "expected.mperm"
+    exp = tmp / ("expected_%d.mperm" % n_perms)
     with open(exp, "w") as f:
         f.write("#CHR\tPOS\tID\tEMP1\tEMP2\n")
         for v, (chrom, _, _) in enumerate(rows):
@@ -81,9 +82,9 @@ def test_result_file_and_mperm(host, inputs):
     assert n.value == len(rows)
     want = open(plain, "rb").read()
     for tag, path, batch in (("several", inputs["vcf"], 1 << 16), ("one", inputs["vcf"], 1 << 22), ("bgzf", inputs["packed"], 1 << 16)):
-        out = str(tmp / ("perm_%s.chisq" % tag))
+        out = str(tmp / ("perm_%s_%d.chisq" % (tag, n_perms)))
         n = C.c_long(0)
-        rc = host.hpgv_run_assoc_perm(path.encode(), inputs["ped"], out.encode(), N_PERMS, SEED, batch, C.byref(n))
+        rc = host.hpgv_run_assoc_perm(path.encode(), inputs["ped"], out.encode(), n_perms, SEED, batch, C.byref(n))
         assert rc == 0 and n.value == len(rows), (tag, host.hpgv_host_last_error())
         assert open(out, "rb").read() == want, tag
         assert open(out + ".mperm", "rb").read() == expected, tag

@@ -27,10 +27,10 @@ def _expected(chi, t_obs):
 
 
 @functools.lru_cache(maxsize=None)
-def _reference(width, nv, n_perms, quirks):
+def _reference(width, nv, n_perms, quirks, special=()):
     """of a case: the sums [nv, P, 2] from numpy, then (n_ge, batch_max, t_obs) from the engine's statistics kernel on the
     permuted class tables (r_k from numpy, s_k = n_k - r_k) and the exact rational statistic [nv, P]"""
-    c = mg.case(width, nv, n_perms, quirks)
+    c = mg.case(width, nv, n_perms, quirks, special=special)
     valid, dosage = mg.classes(c["strict"])
     y = (c["labels"] * (c["cond"] != 2)).astype(np.int64)                  # [P, ns]: columns outside the cohort take no part
     sums = np.stack([valid.astype(np.int64) @ y.T, dosage @ y.T], axis=2).astype(np.int32)

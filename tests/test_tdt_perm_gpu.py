@@ -20,10 +20,10 @@ CASES = [(0, 3, 65, 17), (5, 0, 1, 1), (16, 3, 65, 17), (70, 20, 130, 130), (300
 MID = (70, 20, 130, 130)
 
 
-def _pedigree(rng, n_fast, n_slow):
-    """families in random order: n_fast with one child, n_slow with two or three, three whose father is no VCF column and one
-    without children (the plan skips those four); returns (n_samples, CSR arrays of hpgv_set_families)"""
-    kinds = [1] * n_fast + [int(rng.integers(2, 4)) for _ in range(n_slow)] + [-1, -1, -2, 0]
+def _pedigree(rng, n_fast, n_slow, slow_children=None):
+    """families in random order: n_fast with one child, n_slow with two or three (or slow_children each), three whose father is
+    no VCF column and one without children (the plan skips those four); returns (n_samples, CSR arrays of hpgv_set_families)"""
+    kinds = [1] * n_fast + [slow_children or int(rng.integers(2, 4)) for _ in range(n_slow)] + [-1, -1, -2, 0]
     kinds = [kinds[i] for i in rng.permutation(len(kinds))]
     n_samples = sum(2 + max(abs(k), 1) for k in kinds) + 7
     cols = [int(c) for c in rng.permutation(n_samples)]
@@ -56,7 +56,9 @@ def _chisq(t1, t2):
 
 
 @functools.lru_cache(maxsize=None)
-def _case(n_fast, n_slow, nv, n_perms):
+def _case(n_fast, n_slow, nv, n_perms, special=(), no_part=()):
+    """special: further special flip rows, (row, kind) with kind "none" or "all", set after the fixed ones; no_part: further
+    variants with every parent homozygous"""
     rng = np.random.default_rng(100000 * n_fast + 1000 * n_slow + 10 * nv + n_perms)
     ns, fam = _pedigree(rng, n_fast, n_slow)
     nf = len(fam[0])
@@ -68,10 +70,20 @@ def _case(n_fast, n_slow, nv, n_perms):
     if nv >= 3:
         codes[1] = 0x00                                  # every parent homozygous: t1 + t2 == 0
         is_x[0], is_x[nv - 1] = 0, 1
+    for v in no_part:
+        codes[v] = 0x00
     flips = (rng.random((n_perms, nf)) < rng.uniform(0.2, 0.8, size=(n_perms, 1))).astype(np.uint8)
     flips[0] = 0                                         # the observed transmission
     if n_perms >= 17:
         flips[n_perms - 1] = 1                           # every family flipped
+    for row, kind in special:
+        flips[row] = {"none": 0, "all": 1}[kind]
+    return _finish(ns, fam, codes, is_x, flips, n_fast, n_slow)
+
+
+def _finish(ns, fam, codes, is_x, flips, n_fast, n_slow):
+    """the case of a pedigree, a code matrix and flip rows: the reference's tallies, permuted tallies, n_ge and batch_max"""
+    nf, (nv, n_perms) = len(fam[0]), (codes.shape[0], flips.shape[0])
     t1f, t2f = _family_counts(codes, fam, is_x)
     F = flips.astype(np.int64).T                         # [nf, P]
     t1p, t2p = t1f @ (1 - F) + t2f @ F, t2f @ (1 - F) + t1f @ F
@@ -83,7 +95,7 @@ def _case(n_fast, n_slow, nv, n_perms):
     bmax = np.max(np.where(part[:, None], chi, 0.0), axis=0, initial=0.0)
     c = dict(ns=ns, fam=fam, nf=nf, codes=codes, is_x=is_x, flips=flips, t1=obs[0], t2=obs[1], chi_obs=chi_obs, part=part,
              perm_tu=np.stack([t1p, t2p], axis=2).astype(np.int32), n_ge=n_ge, bmax=bmax, nv=nv, n_perms=n_perms,
-             n_fast=n_fast, n_slow=n_slow)
+             n_fast=n_fast, n_slow=n_slow, d_f=t1f - t2f)
     for a in (codes, is_x, flips, c["perm_tu"], n_ge, bmax):
         a.setflags(write=False)
     return c

@@ -59,10 +59,10 @@ def _f6(host, x):
     return buf.raw[:n].decode()
 
 
-def _expected_mperm(host, inputs, seed):
+def _expected_mperm(host, inputs, seed, n_perms=N_PERMS):
     """the .mperm file by the reference: per-family counts of the oracle, flipped sums in numpy, chi-square of the oracle"""
     fam, codes, is_x, rows = inputs["fam"], inputs["codes"], inputs["is_x"], inputs["rows"]
-    flips = hpgv.perm_flips_shuffle(len(fam[0]), N_PERMS, seed)
+    flips = hpgv.perm_flips_shuffle(len(fam[0]), n_perms, seed)
     t1f, t2f = _family_counts(codes, fam, is_x)
     F = flips.astype(np.int64).T
     t1p, t2p = t1f @ (1 - F) + t2f @ F, t2f @ (1 - F) + t1f @ F
@@ -73,7 +73,7 @@ def _expected_mperm(host, inputs, seed):
     tmax = np.max(np.where(part[:, None], chi, 0.0), axis=0, initial=0.0)
     emp1, emp2 = hpgv.perm_pvalues(np.where(part, chi_obs, np.nan), n_ge, tmax)
     assert part.sum() > 200 and (~part).any() and len(set(emp2[part])) > 5      # the comparison below says something
-    exp = inputs["tmp"] / ("expected_%d.mperm" % seed)
+    exp = inputs["tmp"] / ("expected_%d_%d.mperm" % (seed, n_perms))
     with open(exp, "w") as f:
         f.write("#CHR\tPOS\tID\tEMP1\tEMP2\n")
         for v, (chrom, _, _) in enumerate(rows):
@@ -81,9 +81,10 @@ def _expected_mperm(host, inputs, seed):
     return subprocess.run(["sort", "-k1,1h", "-k2,2n", str(exp)], capture_output=True, env=dict(os.environ, LC_ALL="C"), check=True).stdout
 
 
-def test_result_file_and_mperm(host, inputs):
+@pytest.mark.parametrize("n_perms", [N_PERMS, 150])      # one pass of the permutation kernel; two
+def test_result_file_and_mperm(host, inputs, n_perms):
     tmp, rows = inputs["tmp"], inputs["rows"]
-    expected = _expected_mperm(host, inputs, SEED)
+    expected = _expected_mperm(host, inputs, SEED, n_perms)
     # the TDT runner's file
     plain = str(tmp / "plain.tdt")
     n = C.c_long(0)
@@ -91,9 +92,9 @@ def test_result_file_and_mperm(host, inputs):
     assert n.value == len(rows)
     want = open(plain, "rb").read()
     for tag, path, batch in (("several", inputs["vcf"], 1 << 16), ("one", inputs["vcf"], 1 << 22), ("bgzf", inputs["packed"], 1 << 16)):
-        out = str(tmp / ("perm_%s.tdt" % tag))
+        out = str(tmp / ("perm_%s_%d.tdt" % (tag, n_perms)))
         n = C.c_long(0)
-        rc = host.hpgv_run_tdt_perm(path.encode(), inputs["ped"], out.encode(), N_PERMS, SEED, batch, C.byref(n))
+        rc = host.hpgv_run_tdt_perm(path.encode(), inputs["ped"], out.encode(), n_perms, SEED, batch, C.byref(n))
         assert rc == 0 and n.value == len(rows), (tag, host.hpgv_host_last_error())
         assert open(out, "rb").read() == want, tag
         assert open(out + ".mperm", "rb").read() == expected, tag
