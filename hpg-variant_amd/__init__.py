@@ -67,6 +67,7 @@ SYMBOLS = [
     "hpgv_set_perm_labels", "hpgv_assoc_perm_dev", "hpgv_assoc_perm", "hpgv_assoc_perm_text", "hpgv_perm_labels_shuffle", "hpgv_perm_pvalues",
     "hpgv_set_tdt_flips", "hpgv_tdt_perm_dev", "hpgv_tdt_perm", "hpgv_tdt_perm_text", "hpgv_perm_flips_shuffle",
     "hpgv_assoc_model_scan_dev", "hpgv_assoc_model_stats_dev", "hpgv_assoc_trend_perm_dev", "hpgv_assoc_model", "hpgv_assoc_model_text",
+    "hpgv_ld_window_dev", "hpgv_ld", "hpgv_ld_text", "hpgv_ld_r2",
 ]
 
 
@@ -230,6 +231,11 @@ def load():
     L.hpgv_assoc_trend_perm_dev.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
     L.hpgv_assoc_model.argtypes = [vp, vp, sz, i32] + [vp] * 5
     L.hpgv_assoc_model_text.argtypes = [vp, C.c_char_p, sz, i32, C.POINTER(i32), vp, vp, vp] + [vp] * 5
+    L.hpgv_ld_window_dev.argtypes = [vp, vp, sz, i32, i32, i32, vp, vp, C.c_int64, vp, vp, vp, vp]
+    L.hpgv_ld.argtypes = [vp, vp, sz, i32, i32, vp, vp, C.c_int64, vp, vp]
+    L.hpgv_ld_text.argtypes = [vp, C.c_char_p, sz, i32, C.POINTER(i32), vp, vp, vp, i32, vp, vp]
+    L.hpgv_ld_r2.argtypes = [vp]
+    L.hpgv_ld_r2.restype = C.c_double
     _lib = L
     return L
 
@@ -300,6 +306,16 @@ def perm_pvalues(t_obs, n_ge, t_max):
     if rc != OK:
         raise HpgvError("hpgv_perm_pvalues -> %d" % rc)
     return emp1, emp2
+
+
+def ld_r2(counts6):
+    """hpgv_ld_r2: r^2 of six counts {n, sa, sb, saa, sbb, sab} (needs no device); counts6 of shape (..., 6) gives (...)."""
+    c = _np(counts6, np.int32)
+    assert c.shape[-1] == 6
+    flat = c.reshape(-1, 6)
+    L = load()
+    out = np.array([L.hpgv_ld_r2(_ptr(row)) for row in flat], np.float64)
+    return out.reshape(c.shape[:-1])
 
 
 def _np(a, dtype):
@@ -560,6 +576,33 @@ class Engine:
         if perm:
             res.update(n_ge=n_ge[:k], batch_max=bmax[:np_])
         return res
+
+    def ld(self, gt, window, chrom=None, pos=None, max_bp=-1, counts=True):
+        """hpgv_ld: r2 (nv, window) and, with counts, counts6 (nv, window, 6); element [b, d - 1] is the pair (b - d, b) over the
+        cohort columns.  chrom / pos (per row, both or neither) and max_bp bound the band."""
+        gt = _np(gt, np.uint8)
+        nv, pitch = gt.shape
+        ch = None if chrom is None else _np(chrom, np.int32)
+        po = None if pos is None else _np(pos, np.uint32)
+        r2 = np.zeros((nv, window), np.float64)
+        c6 = np.zeros((nv, window, 6), np.int32) if counts else None
+        self._chk(self.L.hpgv_ld(self.h, _ptr(gt), pitch, nv, window, _ptr(ch), _ptr(po), int(max_bp), _ptr(r2), _ptr(c6)))
+        return dict(r2=r2, counts6=c6)
+
+    def ld_text(self, text, window, max_lines=None, counts=True):
+        """hpgv_ld_text: ld on VCF data lines, one row of the window per line (skipped lines keep their slot)."""
+        if isinstance(text, str):
+            text = text.encode()
+        if max_lines is None:
+            max_lines = text.count(b"\n") + 1
+        m = max(max_lines, 1)
+        r2 = np.zeros((m, max(window, 1)), np.float64)
+        c6 = np.zeros((m, max(window, 1), 6), np.int32) if counts else None
+        status = np.zeros(m, np.int32)
+        nl = C.c_int(0)
+        self._chk(self.L.hpgv_ld_text(self.h, text, len(text), max_lines, C.byref(nl), None, None, _ptr(status), window, _ptr(r2), _ptr(c6)))
+        k = min(nl.value, max_lines)
+        return dict(n_lines=nl.value, status=status[:k], r2=r2[:k], counts6=None if c6 is None else c6[:k])
 
     def assoc_view(self, task, gt2d, n_samples, is_x=None):
         """hpgv_assoc on a 2-D uint8 VIEW as it lies in memory (row stride = pitch): nothing is copied on the way,
@@ -839,6 +882,11 @@ class Engine:
 
     def assoc_trend_perm_dev(self, d_gt, n_variants, d_counts8, d_n_ge, d_batch_max, d_perm_sums=None, stream=None):
         self._chk(self.L.hpgv_assoc_trend_perm_dev(self.h, d_gt, n_variants, d_counts8, d_n_ge, d_batch_max, d_perm_sums, stream))
+
+    def ld_window_dev(self, d_gt, pitch, n_variants, window, d_r2, d_counts6=None, b_begin=0, d_chrom=None, d_pos=None, max_bp=-1,
+                      d_skip=None, stream=None):
+        self._chk(self.L.hpgv_ld_window_dev(self.h, d_gt, pitch, n_variants, b_begin, window, d_chrom, d_pos, int(max_bp), d_skip,
+                                            d_r2, d_counts6, stream))
 
     def assoc_fisher(self, d_counts, n_variants, d_odds, d_p, stream=None):
         self._chk(self.L.hpgv_assoc_fisher_dev(self.h, d_counts, n_variants, d_odds, d_p, stream))

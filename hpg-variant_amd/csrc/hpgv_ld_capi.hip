@@ -1,0 +1,142 @@
+// hpgv_ld_capi.hip -- C ABI of the LD band (include/hpgv.h "LD"): the device-resident launch of k_ld_window, the synchronous
+// entry points on a host batch and on a text, and the host-only r^2 of six counts.
+#include "hpgv_internal.h"
+#include "hpgv_ld_kernels.h"
+
+namespace {
+
+static_assert(hpgv::LD_MAX_WINDOW == HPGV_LD_MAX_WINDOW, "the kernel's window limit is the header's");
+
+int ld_window_check(const hpgv_ctx *ctx, int window) {
+    if (window < 1 || window > hpgv::LD_MAX_WINDOW)
+        return fail(ctx, HPGV_ERR_UNSUPPORTED, "window %d: 1 .. %d variants", window, hpgv::LD_MAX_WINDOW);
+    return HPGV_OK;
+}
+
+// the launch: the pairs without an earlier row, then the band (the arguments checked, the device current)
+int ld_launch(hpgv_ctx *ctx, const uint8_t *d_gt, size_t pitch, int n_variants, int b_begin, int window, const int32_t *d_chrom,
+              const uint32_t *d_pos, int64_t max_bp, const uint8_t *d_skip, double *d_r2, int32_t *d_counts6, hipStream_t st) {
+    if (n_variants == b_begin) return HPGV_OK;
+    hpgv::LdArgs A;
+    A.gt = d_gt; A.pitch = pitch; A.chunks = (int)(pitch / 16); A.n_variants = n_variants; A.b_begin = b_begin; A.window = window;
+    A.passes = (63 + window) / 64 + 1;
+    A.tiles = (n_variants + hpgv::LD_VT - 1) / hpgv::LD_VT; A.tiles_per_range = (A.tiles + 7) / 8;
+    A.chrom = d_chrom; A.pos = d_pos; A.max_bp = max_bp; A.skip = d_skip; A.r2 = d_r2; A.counts6 = d_counts6;
+    const size_t wgs = (size_t)8 * (size_t)A.tiles_per_range * (size_t)A.passes;
+    if (wgs > 0x7FFFFFFFu) return fail(ctx, HPGV_ERR_UNSUPPORTED, "%d variants x window %d in one call: give the variants in several", n_variants, window);
+    const int head_end = n_variants < window ? n_variants : window;           // later variants below `window` lack earlier rows
+    const size_t head = head_end > b_begin ? (size_t)(head_end - b_begin) * (size_t)window : 0;
+    // (option "profile": the two kernels' time is the statistics time of hpgv_last_kernel_ms)
+    return launch_profiled(ctx, st, 1, [&] {
+        if (head) hipLaunchKernelGGL(hpgv::k_ld_head, dim3((unsigned)((head + 255) / 256)), dim3(256), 0, st, b_begin, head_end, window, d_r2, d_counts6);
+        hipLaunchKernelGGL(hpgv::k_ld_window, dim3((unsigned)wgs), dim3(256), 0, st, A);
+    });
+}
+
+// the back half of hpgv_ld and hpgv_ld_text: the laid-out matrix of a staged call -> the band -> the caller's arrays.  skip, chrom
+// and pos (host, may be null) are copied to the slot
+int ld_finish(hpgv_ctx *ctx, Slot *s, const Staged &S, int window, const uint8_t *skip, const int32_t *chrom, const uint32_t *pos, int64_t max_bp,
+              double *r2, int32_t *counts6) {
+    const int nv = S.n;
+    if (nv > 0) {
+        const size_t n = (size_t)nv, pairs = n * (size_t)window, off_pos = round_up(n * sizeof(int32_t), 16);
+        HIPCHK(ctx, s->dbl.reserve_slack(pairs * sizeof(double) + 16));
+        if (counts6) HIPCHK(ctx, s->tally.reserve_slack(pairs * 6 * sizeof(int32_t) + 16));
+        if (skip) HIPCHK(ctx, s->perm.reserve_slack(n + 16));
+        if (chrom) HIPCHK(ctx, s->ints.reserve_slack(off_pos + n * sizeof(uint32_t) + 16));
+        double *d_r2 = s->dbl.as<double>();
+        int32_t *d_counts6 = counts6 ? s->tally.as<int32_t>() : nullptr;
+        uint8_t *d_skip = skip ? s->perm.as<uint8_t>() : nullptr;
+        int32_t *d_chrom = chrom ? s->ints.as<int32_t>() : nullptr;
+        uint32_t *d_pos = chrom ? (uint32_t *)(s->ints.as<char>() + off_pos) : nullptr;
+        if (skip) HIPCHK(ctx, hipMemcpyAsync(d_skip, skip, n, hipMemcpyHostToDevice, s->stream));
+        if (chrom) {
+            HIPCHK(ctx, hipMemcpyAsync(d_chrom, chrom, n * sizeof(int32_t), hipMemcpyHostToDevice, s->stream));
+            HIPCHK(ctx, hipMemcpyAsync(d_pos, pos, n * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
+        }
+        if (const int rc = ld_launch(ctx, S.d_laid, ctx->assoc.pitch, nv, 0, window, d_chrom, d_pos, max_bp, d_skip, d_r2, d_counts6, s->stream)) return rc;
+        HIPCHK(ctx, hipMemcpyAsync(r2, d_r2, pairs * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        if (counts6) HIPCHK(ctx, hipMemcpyAsync(counts6, d_counts6, pairs * 6 * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
+    }
+    HIPCHK(ctx, hipStreamSynchronize(s->stream));
+    return HPGV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hpgv_ld_window_dev(hpgv_ctx *ctx, const uint8_t *d_gt, size_t pitch, int n_variants, int b_begin, int window,
+                       const int32_t *d_chrom, const uint32_t *d_pos, int64_t max_bp, const uint8_t *d_skip,
+                       double *d_r2, int32_t *d_counts6, void *stream) {
+    ctx = first_member(ctx);
+    if (!ctx) return HPGV_ERR_INVALID;
+    if (const int rc = ld_window_check(ctx, window)) return rc;
+    if (n_variants < 0 || b_begin < 0 || b_begin > n_variants || (n_variants > b_begin && (!d_gt || !d_r2)))
+        return fail(ctx, HPGV_ERR_INVALID, "bad ld_window arguments");
+    if ((d_chrom == nullptr) != (d_pos == nullptr)) return fail(ctx, HPGV_ERR_INVALID, "d_chrom and d_pos: both or neither");
+    if (pitch == 0 || (pitch & 15) || pitch > 0xFFFFFFF0u) return fail(ctx, HPGV_ERR_INVALID, "pitch %zu: a multiple of 16 below 4 GiB", pitch);
+    if (((uintptr_t)d_gt & 15) || ((uintptr_t)d_r2 & 7) || ((uintptr_t)d_counts6 & 7) || ((uintptr_t)d_chrom & 3) || ((uintptr_t)d_pos & 3))
+        return fail(ctx, HPGV_ERR_INVALID, "d_gt must be 16-byte aligned, d_r2 and d_counts6 8-byte aligned, d_chrom and d_pos 4-byte aligned");
+    DeviceGuard g(ctx->device);
+    return ld_launch(ctx, d_gt, pitch, n_variants, b_begin, window, d_chrom, d_pos, max_bp, d_skip, d_r2, d_counts6, (hipStream_t)stream);
+}
+
+int hpgv_ld(hpgv_ctx *ctx, const uint8_t *gt, size_t pitch, int n_variants, int window, const int32_t *chrom, const uint32_t *pos,
+            int64_t max_bp, double *r2, int32_t *counts6) {
+    HPGV_ABI_TRY
+    if (!ctx) return HPGV_ERR_INVALID;
+    if (is_group(ctx)) return fail(ctx, HPGV_ERR_UNSUPPORTED, "hpgv_ld on a group context: the members' shards have seams");
+    if (!ctx->assoc.set) return fail(ctx, HPGV_ERR_STATE, "hpgv_set_cohort has not been called");
+    if (const int rc0 = ld_window_check(ctx, window)) return rc0;
+    if (n_variants < 0 || (n_variants > 0 && (!gt || !r2))) return fail(ctx, HPGV_ERR_INVALID, "bad ld arguments");
+    if ((chrom == nullptr) != (pos == nullptr)) return fail(ctx, HPGV_ERR_INVALID, "chrom and pos: both or neither");
+    if (pitch < (size_t)ctx->assoc.n_samples) return fail(ctx, HPGV_ERR_INVALID, "pitch %zu < n_samples %d", pitch, ctx->assoc.n_samples);
+    if (n_variants == 0) return HPGV_OK;
+    HPGV_LEASE_SLOT(ctx)
+    // the rows copied to the slot and laid out (the last row need not be a whole pitch)
+    const Layout &L = ctx->assoc;
+    const size_t bytes = (size_t)(n_variants - 1) * pitch + (size_t)L.n_samples;
+    HIPCHK(ctx, s->raw.reserve_slack(bytes + 16));
+    HIPCHK(ctx, s->laid.reserve_slack((size_t)n_variants * L.pitch + 16));
+    if (bytes) HIPCHK(ctx, hipMemcpyAsync(s->raw.p, gt, bytes, hipMemcpyHostToDevice, s->stream));
+    if ((rc = hpgv_layout_dev(ctx, HPGV_LAYOUT_ASSOC, s->raw.as<uint8_t>(), pitch, n_variants, s->laid.as<uint8_t>(), s->stream))) return rc;
+    Staged S;
+    S.d_raw = s->raw.as<uint8_t>(); S.raw_pitch = pitch; S.d_laid = s->laid.as<uint8_t>(); S.which = HPGV_LAYOUT_ASSOC;
+    S.n = n_variants; S.out_stride = (size_t)n_variants;
+    return ld_finish(ctx, s, S, window, nullptr, chrom, pos, max_bp, r2, counts6);
+    HPGV_ABI_CATCH(ctx)
+}
+
+int hpgv_ld_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, int max_lines, int *n_lines, uint64_t *line_off, uint32_t *field_off,
+                 int32_t *status, int window, double *r2, int32_t *counts6) {
+    HPGV_ABI_TRY
+    if (!ctx) return HPGV_ERR_INVALID;
+    if (is_group(ctx)) return fail(ctx, HPGV_ERR_UNSUPPORTED, "hpgv_ld_text on a group context: the members' shards have seams");
+    if (!ctx->assoc.set) return fail(ctx, HPGV_ERR_STATE, "hpgv_set_cohort has not been called");
+    if (const int rc0 = ld_window_check(ctx, window)) return rc0;
+    if (!n_lines || max_lines < 0 || (text_bytes > 0 && !text) || (max_lines > 0 && !r2)) return fail(ctx, HPGV_ERR_INVALID, "bad ld_text arguments");
+    *n_lines = 0;
+    if (max_lines == 0) return HPGV_OK;
+    std::vector<int32_t> own_status;             // (before the lease: queued copies into them end with the lease)
+    std::vector<uint8_t> skip;
+    HPGV_LEASE_SLOT(ctx)
+    Staged S;
+    if (!status) { own_status.assign((size_t)max_lines, 0); status = own_status.data(); }
+    if ((rc = text_front(ctx, s, HPGV_LAYOUT_ASSOC, ctx->assoc, text, text_bytes, max_lines, n_lines, line_off, field_off, status, &S, true))) return rc;
+    // the lines hpgv_assoc_text's callers drop keep their slot in the window as skipped rows: not a record (status 1), or
+    // rejected by a record filter
+    HIPCHK(ctx, hipStreamSynchronize(s->stream));
+    skip.resize((size_t)S.n);
+    for (int i = 0; i < S.n; ++i) skip[(size_t)i] = ((status[i] & 0xFF) == 1 || (status[i] & HPGV_LINE_FILTERED)) ? 1 : 0;
+    return ld_finish(ctx, s, S, window, S.n > 0 ? skip.data() : nullptr, nullptr, nullptr, -1, r2, counts6);
+    HPGV_ABI_CATCH(ctx)
+}
+
+/* ---- host-only helper: no GPU call, usable without a device ------------------------------------------------------------ */
+
+double hpgv_ld_r2(const int32_t counts6[6]) {
+    return hpgv::ld_r2_value(counts6[0], counts6[1], counts6[2], counts6[3], counts6[4], counts6[5]);
+}
+
+}  // extern "C"

@@ -399,6 +399,45 @@ int  hpgv_stats_filter_dev(hpgv_ctx *ctx, const int32_t *d_counts8, int n_varian
  * d_gt and d_counts8 16-byte aligned.  Asynchronous on `stream`. */
 int  hpgv_inheritance_scan_dev(hpgv_ctx *ctx, const uint8_t *d_gt, int n_variants, int32_t *d_counts8, void *stream);
 
+/* ---- LD: the squared genotype correlation r^2 between variants that lie near each other (PLINK's --r2 --ld-window; no
+ *      reference counterpart): what clumping, pruning and the annotation of a hit with its neighbours start from.
+ *
+ *      The genotype class of an HPGV8 byte is the model tests' ("model tests" above): missing if either nibble is 0xF, else
+ *      0, 1 or 2 ("1/2" is 2); dosage equals class.  Chromosome X gets no special rule.  For rows a < b of one matrix, with
+ *      v = valid (0 / 1) and g = dosage (0 when missing), summed over the row's bytes:
+ *          n   = sum v_a v_b        sa  = sum g_a v_b        sb  = sum v_a g_b
+ *          saa = sum g_a^2 v_b      sbb = sum v_a g_b^2      sab = sum g_a g_b
+ *      the moments over the samples called in BOTH rows: six i8 products (planes v, g, g^2) with exact i32 sums on the matrix
+ *      cores (csrc/hpgv_ld_kernels.h).  counts6 = {n, sa, sb, saa, sbb, sab}, int32 x 6.
+ *
+ *      Statistic.  The three differences in int64 (exact: the largest, n saa, stays below 2^47 for any row the layouts
+ *      allow), the rest f64 without contraction, in this order:
+ *          cov = n sab - sa sb      va = n saa - sa^2      vb = n sbb - sb^2
+ *          r2  = ((double)cov * (double)cov) / ((double)va * (double)vb)
+ *      va == 0 or vb == 0 gives 0 / 0 = NaN: a monomorphic row, n = 0 and n = 1.  Nothing else is special-cased, as the
+ *      chi-square path special-cases no zero margin.  The sign of r is the sign of cov, which counts6 gives.
+ *
+ *      Band.  With `window` W the outputs are indexed by the LATER variant: r2[(b - b_begin) * W + (d - 1)] is the pair
+ *      (b - d, b) for d = 1 .. W and b = b_begin .. n_variants - 1; counts6 uses the same index x 6.  Every element of that
+ *      range is written.  A pair gets r2 = NaN and zero counts (it is "outside the band") when b - d < 0, when either row is
+ *      skipped, when chromosomes are given and the two differ, or when positions are given, max_bp >= 0 and
+ *      |pos_b - pos_a| > max_bp.  Only whether an r2 is NaN is defined, not which NaN. */
+#define HPGV_LD_MAX_WINDOW 1024
+/* d_gt: any matrix of HPGV8 rows `pitch` bytes apart whose pad bytes are 0xFF -- a matrix in the assoc layout is one, and the LD
+ * is then over the cohort columns.  Rows below b_begin serve as earlier partners only: a caller that walks a file in pieces
+ * prepends the last `window` rows of the previous piece and passes b_begin = window, which makes the seam exact without any
+ * engine state.  d_chrom (int32 per row) and d_pos (uint32 per row): both or both NULL (else HPGV_ERR_INVALID); max_bp < 0
+ * = no distance limit.  d_skip (may be NULL): != 0 = the row takes no part.  d_r2: (n_variants - b_begin) x window doubles;
+ * d_counts6 (may be NULL) x 6 int32.  Needs no cohort.  n_variants == b_begin succeeds and writes nothing.
+ * Refusals: window outside 1 .. HPGV_LD_MAX_WINDOW is HPGV_ERR_UNSUPPORTED (the passes of a tile grow with it), and so is a
+ * call whose (n_variants / 64) x (window / 64 + 2) exceeds 2^31 workgroups; HPGV_ERR_INVALID for b_begin outside
+ * 0 .. n_variants, a pitch that is 0, not a multiple of 16 or 4 GiB and more, d_gt not 16-byte aligned, d_r2 or d_counts6 not
+ * 8-byte aligned, d_chrom or d_pos not 4-byte aligned.  Asynchronous on `stream`; under option "profile" its time is the
+ * statistics time of hpgv_last_kernel_ms.  The launch reads each row window / 64 + 2 times at most, from L2 but for the first. */
+int  hpgv_ld_window_dev(hpgv_ctx *ctx, const uint8_t *d_gt, size_t pitch, int n_variants, int b_begin, int window,
+                        const int32_t *d_chrom /* may be NULL */, const uint32_t *d_pos /* may be NULL */, int64_t max_bp,
+                        const uint8_t *d_skip /* may be NULL */, double *d_r2, int32_t *d_counts6 /* may be NULL */, void *stream);
+
 /* ---- the variant-sharded resident scan of a GROUP context: what the runner's worker loop
  *      (assoc_runner.c:106-207, tdt_runner.c:150-200, stats_runner.c:176-215) becomes when the cohort lies in the HBM of
  *      the group's devices.  Variants are independent (assoc.c:38-82, tdt.c:41-271), so member g owns the contiguous
@@ -853,6 +892,23 @@ int  hpgv_tdt_perm_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, int 
                         uint64_t *line_off, uint32_t *field_off, int32_t *status,
                         int32_t *t1, int32_t *t2, double *odds, double *chisq, double *p, int32_t *n_ge, double *batch_max);
 
+/* ---- LD on a host batch and on a text ("LD" above; synchronous, thread-safe) ------------------------------------------- */
+/* gt: n_variants rows in VCF column order, `pitch` bytes apart (pitch >= n_samples).  The rows go through the
+ * HPGV_LAYOUT_ASSOC layout and then hpgv_ld_window_dev with b_begin = 0: the LD is over the cohort columns (AFFECTED and
+ * UNAFFECTED).  chrom / pos (host, per row): both or both NULL (else HPGV_ERR_INVALID); max_bp < 0 = no distance limit.
+ * r2: n_variants x window doubles; counts6 (may be NULL) x 6 int32.  HPGV_ERR_STATE without hpgv_set_cohort; window outside
+ * 1 .. HPGV_LD_MAX_WINDOW is HPGV_ERR_UNSUPPORTED.  A GROUP context returns HPGV_ERR_UNSUPPORTED: dealing batches to the
+ * members would cut the band at every seam. */
+int  hpgv_ld(hpgv_ctx *ctx, const uint8_t *gt, size_t pitch, int n_variants, int window, const int32_t *chrom /* may be NULL */,
+             const uint32_t *pos /* may be NULL */, int64_t max_bp, double *r2, int32_t *counts6 /* may be NULL */);
+/* tokenizer -> assoc layout -> hpgv_ld_window_dev with no matrix crossing the bus, as hpgv_assoc_model_text.  EVERY line of the
+ * text is one row of the window: a line with status 1 (not a record) or flagged HPGV_LINE_FILTERED is a skipped row -- it keeps
+ * its slot, and its pairs are NaN with zero counts.  No distance filter here: line_off / field_off come back for the caller,
+ * who knows the positions only then.  r2: max_lines x window doubles, min(*n_lines, max_lines) x window of them written;
+ * counts6 (may be NULL) x 6.  status may be NULL.  State and refusals as hpgv_ld, a GROUP context included. */
+int  hpgv_ld_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, int max_lines, int *n_lines,
+                  uint64_t *line_off, uint32_t *field_off, int32_t *status, int window, double *r2, int32_t *counts6 /* may be NULL */);
+
 /* ---- label permutation, host side: no GPU call, no context, usable without a device ------------------------------- */
 /* n_perms label rows for hpgv_set_perm_labels, labels_out[p * n_samples + j]: row p is a uniform shuffle of the cohort
  * columns' conditions (1 = affected), so every row has as many ones as the cohort has affected samples; HPGV_COND_OTHER
@@ -872,6 +928,9 @@ int  hpgv_perm_flips_shuffle(int n_families, int n_perms, uint64_t seed, uint8_t
  * both NaN where t_obs[v] is NaN.  n_perms < 1: HPGV_ERR_INVALID. */
 int  hpgv_perm_pvalues(const double *t_obs, int n_variants, const int32_t *n_ge, const double *t_max, int n_perms,
                        double *emp1, double *emp2);
+/* r2 of six counts {n, sa, sb, saa, sbb, sab} by the expression of "LD" above: the function the kernel's epilogue calls, built for
+ * the host.  No GPU call, no context. */
+double hpgv_ld_r2(const int32_t counts6[6]);
 
 /* streaming-read ceiling probe: reads `bytes` from d_buf with the scan's load
  * shape and no arithmetic; returns the kernel time in ms (diagnostic) */
