@@ -68,7 +68,12 @@ SYMBOLS = [
     "hpgv_set_tdt_flips", "hpgv_tdt_perm_dev", "hpgv_tdt_perm", "hpgv_tdt_perm_text", "hpgv_perm_flips_shuffle",
     "hpgv_assoc_model_scan_dev", "hpgv_assoc_model_stats_dev", "hpgv_assoc_trend_perm_dev", "hpgv_assoc_model", "hpgv_assoc_model_text",
     "hpgv_ld_window_dev", "hpgv_ld", "hpgv_ld_text", "hpgv_ld_r2",
+    "hpgv_ld_edges_dev", "hpgv_ld_edges", "hpgv_clump",
+    "hpgv_rows_gather_scratch_bytes", "hpgv_rows_gather_dev", "hpgv_assoc_select_text",
 ]
+
+# hpgv_ld_edge: {int32 a, b; double r2}, 16 bytes
+LD_EDGE = np.dtype([("a", np.int32), ("b", np.int32), ("r2", np.float64)])
 
 
 class HpgvError(RuntimeError):
@@ -236,6 +241,14 @@ def load():
     L.hpgv_ld_text.argtypes = [vp, C.c_char_p, sz, i32, C.POINTER(i32), vp, vp, vp, i32, vp, vp]
     L.hpgv_ld_r2.argtypes = [vp]
     L.hpgv_ld_r2.restype = C.c_double
+    L.hpgv_ld_edges_dev.argtypes = [vp, vp, sz, i32, i32, i32, vp, vp, C.c_int64, vp, C.c_double, vp, u64, vp, vp]
+    L.hpgv_ld_edges.argtypes = [vp, vp, sz, i32, i32, vp, vp, C.c_int64, C.c_double, vp, u64, vp]
+    L.hpgv_clump.argtypes = [i32, vp, vp, u64, C.c_double, vp, vp, C.POINTER(i32)]
+    L.hpgv_rows_gather_scratch_bytes.argtypes = [i32]
+    L.hpgv_rows_gather_scratch_bytes.restype = sz
+    L.hpgv_rows_gather_dev.argtypes = [vp, vp, sz, sz, i32, vp, vp, sz, vp, vp, vp, vp]
+    L.hpgv_assoc_select_text.argtypes = [vp, i32, C.c_char_p, sz, i32, C.POINTER(i32), vp, vp, vp] + [vp] * 7 + \
+                                        [C.c_double, vp, vp, sz, i32, C.POINTER(i32)]
     _lib = L
     return L
 
@@ -294,6 +307,35 @@ def run_assoc_model(vcf_path, ped_path, out_path, n_perms=0, seed=0, batch_bytes
     return n.value
 
 
+class RunClumpOptions(C.Structure):
+    """hpgv_run_clump_options_t, with PLINK's defaults"""
+    _fields_ = [("p1", C.c_double), ("p2", C.c_double), ("min_r2", C.c_double), ("max_bp", C.c_int64), ("window", C.c_int)]
+
+    def __init__(self, p1=1e-4, p2=1e-2, min_r2=0.5, max_bp=250000, window=1024):
+        super().__init__(p1, p2, min_r2, max_bp, window)
+
+
+def run_assoc_clump(vcf_path, ped_path, out_path, task=TASK_CHISQ, options=None, batch_bytes=1 << 22, **kw):
+    """hpgv_run_assoc_clump of libhpgv_host.so (include/hpgv_host.h): hpgv_run_assoc's file at out_path and the clumps of its
+    significant variants in out_path + ".clumped".  options: a RunClumpOptions (or its fields as keywords: p1, p2, min_r2, max_bp,
+    window); paths may be None and options False (a NULL pointer): the call then fails with ERR_INVALID.  Returns (variants written, clumps, truncated candidates)."""
+    _build.build_host_lib()
+    H = C.CDLL(_build.HOSTLIB)
+    H.hpgv_run_assoc_clump.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_void_p, C.c_size_t] + [C.POINTER(C.c_long)] * 3
+    H.hpgv_host_last_error.restype = C.c_char_p
+    if options is None or kw:
+        options = RunClumpOptions(**kw)
+    n, k, t = C.c_long(0), C.c_long(0), C.c_long(0)
+    enc = lambda q: None if q is None else os.fsencode(q)
+    rc = H.hpgv_run_assoc_clump(enc(vcf_path), enc(ped_path), enc(out_path), task, C.byref(options) if options is not False else None,
+                                batch_bytes, C.byref(n), C.byref(k), C.byref(t))
+    if rc != OK:
+        e = HpgvError("hpgv_run_assoc_clump -> %d: %s" % (rc, (H.hpgv_host_last_error() or b"").decode(errors="replace")))
+        e.code = rc
+        raise e
+    return n.value, k.value, t.value
+
+
 def perm_pvalues(t_obs, n_ge, t_max):
     """hpgv_perm_pvalues: (EMP1, EMP2) of every variant from its observed statistic, its count of permutations at or above
     it, and the per-permutation maxima merged over the whole scan.  No device needed."""
@@ -316,6 +358,27 @@ def ld_r2(counts6):
     L = load()
     out = np.array([L.hpgv_ld_r2(_ptr(row)) for row in flat], np.float64)
     return out.reshape(c.shape[:-1])
+
+
+def clump(p, edges, p1):
+    """hpgv_clump: PLINK's default --clump on candidates with p-values p and LD edges between them (an LD_EDGE array, or an (m, 2)
+    array of candidate numbers).  Returns (index_of [n]: the index candidate of each one's clump or -1, clump_order: the index
+    candidates in the order the clumps were opened).  No device needed."""
+    pv = _np(p, np.float64)
+    e = np.asarray(edges)
+    if e.dtype != LD_EDGE:
+        pairs = np.asarray(edges, np.int64).reshape(-1, 2)
+        e = np.zeros(len(pairs), LD_EDGE)
+        e["a"], e["b"] = pairs[:, 0], pairs[:, 1]
+    e = np.ascontiguousarray(e)
+    index_of, order = np.zeros(len(pv), np.int32), np.zeros(len(pv), np.int32)
+    k = C.c_int(0)
+    rc = load().hpgv_clump(len(pv), _ptr(pv), _ptr(e), len(e), float(p1), _ptr(index_of), _ptr(order), C.byref(k))
+    if rc != OK:
+        err = HpgvError("hpgv_clump -> %d" % rc)
+        err.code = rc
+        raise err
+    return index_of, order[:k.value].copy()
 
 
 def _np(a, dtype):
@@ -380,6 +443,7 @@ class Engine:
         c = _np(condition, np.uint8)
         self._chk(self.L.hpgv_set_cohort(self.h, _ptr(c), len(c)))
         self._n_perms = 0               # a new cohort drops the label rows
+        self._n_samples = len(c)
         return self.assoc_layout()
 
     def set_perm_labels(self, labels):
@@ -588,6 +652,26 @@ class Engine:
         c6 = np.zeros((nv, window, 6), np.int32) if counts else None
         self._chk(self.L.hpgv_ld(self.h, _ptr(gt), pitch, nv, window, _ptr(ch), _ptr(po), int(max_bp), _ptr(r2), _ptr(c6)))
         return dict(r2=r2, counts6=c6)
+
+    def ld_edges(self, gt, window, min_r2, chrom=None, pos=None, max_bp=-1, edge_cap=None):
+        """hpgv_ld_edges: the pairs of hpgv_ld's band with r2 >= min_r2 as an LD_EDGE array sorted by (b, a).  Without edge_cap the
+        call is repeated once with room when the first list was too short; with it, (edges or None, n_edges) comes back as is."""
+        gt = _np(gt, np.uint8)
+        nv, pitch = gt.shape
+        ch = None if chrom is None else _np(chrom, np.int32)
+        po = None if pos is None else _np(pos, np.uint32)
+        n = C.c_uint64(0)
+        cap = 4096 if edge_cap is None else int(edge_cap)
+        for _ in range(2):
+            e = np.zeros(max(cap, 1), LD_EDGE)
+            self._chk(self.L.hpgv_ld_edges(self.h, _ptr(gt), pitch, nv, window, _ptr(ch), _ptr(po), int(max_bp), float(min_r2),
+                                           _ptr(e), cap, C.byref(n)))
+            if edge_cap is not None:
+                return (e[:n.value] if n.value <= cap else None), n.value
+            if n.value <= cap:
+                return e[:n.value]
+            cap = n.value
+        raise HpgvError("hpgv_ld_edges: the count grew between two calls on the same rows")
 
     def ld_text(self, text, window, max_lines=None, counts=True):
         """hpgv_ld_text: ld on VCF data lines, one row of the window per line (skipped lines keep their slot)."""
@@ -821,6 +905,34 @@ class Engine:
         return dict(n_lines=nl.value, status=status[:k], A1=A1[:k], A2=A2[:k], U1=U1[:k], U2=U2[:k], odds=odds[:k],
                     chisq=chisq[:k] if task == TASK_CHISQ else None, p=p[:k])
 
+    def assoc_select_text(self, task, text, p_max, max_lines=None, rows_cap=None, rows_pitch=None):
+        """hpgv_assoc_select_text: assoc_text's dict plus sel (per line: its number among the selected lines or -1), n_sel, and
+        rows (n_sel, n_samples): the selected lines' genotype rows in VCF column order -- None when n_sel exceeds rows_cap
+        (default: room for every line)."""
+        if isinstance(text, str):
+            text = text.encode()
+        if max_lines is None:
+            max_lines = text.count(b"\n") + 1
+        m = max(max_lines, 1)
+        ns = getattr(self, "_n_samples", 0)     # (set_cohort; without one the call fails with ERR_STATE)
+        if rows_cap is None:
+            rows_cap = m
+        if rows_pitch is None:
+            rows_pitch = max(ns, 1)
+        A1, A2, U1, U2 = (np.zeros(m, np.int32) for _ in range(4))
+        odds, chisq, p = (np.zeros(m, np.float64) for _ in range(3))
+        status, sel = np.zeros(m, np.int32), np.full(m, -2, np.int32)
+        rows = np.full((max(rows_cap, 1), rows_pitch), 0xEE, np.uint8)
+        nl, nsel = C.c_int(0), C.c_int(0)
+        self._chk(self.L.hpgv_assoc_select_text(self.h, task, text, len(text), max_lines, C.byref(nl), None, None, _ptr(status),
+                                                _ptr(A1), _ptr(A2), _ptr(U1), _ptr(U2), _ptr(odds),
+                                                _ptr(chisq) if task == TASK_CHISQ else None, _ptr(p),
+                                                float(p_max), _ptr(sel), _ptr(rows), rows_pitch, rows_cap, C.byref(nsel)))
+        k = min(nl.value, max_lines)
+        return dict(n_lines=nl.value, status=status[:k], A1=A1[:k], A2=A2[:k], U1=U1[:k], U2=U2[:k], odds=odds[:k],
+                    chisq=chisq[:k] if task == TASK_CHISQ else None, p=p[:k], sel=sel[:k], n_sel=nsel.value,
+                    rows=rows[:nsel.value, :ns] if nsel.value <= rows_cap else None, rows_block=rows)
+
     def tdt_text(self, text, max_lines=None):
         if isinstance(text, str):
             text = text.encode()
@@ -887,6 +999,18 @@ class Engine:
                       d_skip=None, stream=None):
         self._chk(self.L.hpgv_ld_window_dev(self.h, d_gt, pitch, n_variants, b_begin, window, d_chrom, d_pos, int(max_bp), d_skip,
                                             d_r2, d_counts6, stream))
+
+    def ld_edges_dev(self, d_gt, pitch, n_variants, window, min_r2, d_edges, edge_cap, d_n_edges, b_begin=0, d_chrom=None, d_pos=None,
+                     max_bp=-1, d_skip=None, stream=None):
+        self._chk(self.L.hpgv_ld_edges_dev(self.h, d_gt, pitch, n_variants, b_begin, window, d_chrom, d_pos, int(max_bp), d_skip,
+                                           float(min_r2), d_edges, int(edge_cap), d_n_edges, stream))
+
+    def rows_gather_scratch_bytes(self, n_rows):
+        return self.L.hpgv_rows_gather_scratch_bytes(n_rows)
+
+    def rows_gather_dev(self, d_src, src_pitch, row_bytes, n_rows, d_keep, d_dst, dst_pitch, d_index, d_n_kept, d_scratch, stream=None):
+        self._chk(self.L.hpgv_rows_gather_dev(self.h, d_src, src_pitch, row_bytes, n_rows, d_keep, d_dst, dst_pitch, d_index, d_n_kept,
+                                              d_scratch, stream))
 
     def assoc_fisher(self, d_counts, n_variants, d_odds, d_p, stream=None):
         self._chk(self.L.hpgv_assoc_fisher_dev(self.h, d_counts, n_variants, d_odds, d_p, stream))

@@ -465,6 +465,10 @@ long hpgv_batch_lds_optin(const hipDeviceProp_t &prop, long fallback);
 // tokenize, record filters, lay out
 int text_front(hpgv_ctx *ctx, Slot *s, int which, const Layout &L, const char *text, size_t text_bytes, int max_lines, int *n_lines,
                uint64_t *line_off, uint32_t *field_off, int32_t *status, Staged *S, bool final_layout = true);
+// defined in hpgv_text_capi.hip: the back half of hpgv_assoc_select_text -- the candidate lines of a staged text (a record, not
+// filtered, p <= p_max; p_i at d_p + i * p_stride) numbered into sel, their raw rows compacted on the device and copied to rows_out
+int select_rows(hpgv_ctx *ctx, Slot *s, const Staged &S, int n_samples, const int32_t *status, const char *d_p, size_t p_stride, double p_max,
+                int32_t *sel, uint8_t *rows_out, size_t rows_pitch, int rows_cap, int *n_sel);
 
 // defined in hpgv_statsall_capi.hip: k_stats_all2 on a batch (0 = launched, 1 = not a batch it takes: run k_stats_all)
 namespace hpgv { struct StatsAllArgs; }

@@ -31,6 +31,9 @@
 // Epilogue.  Per pair inside the band the six sums, then r^2 by ld_r2_value.  A pair whose rows are skipped, lie on different
 // chromosomes or further apart than max_bp gets the quiet NaN and zero counts.  The pairs (b - d, b) with b - d < 0 belong to no
 // tile: k_ld_head writes them.
+//
+// Edge form.  k_ld_edges is the same tile with an epilogue that appends the pairs with r2 >= a threshold to a list and writes no
+// band (at the end of this file).
 #pragma once
 #include "hpgv_assoc_perm_kernels.h"
 
@@ -220,6 +223,166 @@ __global__ __launch_bounds__(256) void k_ld_window(const LdArgs A) {
             if (A.counts6 != nullptr) {
                 int2 *o = reinterpret_cast<int2 *>(A.counts6 + at * 6);
                 o[0] = make_int2(c[0], c[1]); o[1] = make_int2(c[2], c[3]); o[2] = make_int2(c[4], c[5]);
+            }
+        }
+    }
+}
+
+// The edge form (hpgv_ld_edges_dev): k_ld_window's tile, lane maps, staging and skip logic, word for word, with another epilogue.
+// It is a kernel of its own and not a compile-time form of one body, because k_ld_window's instructions are to stay what they
+// were: with the body shared through a template the compiler allocated the band form's registers differently.  A change to
+// the loop of one of the two belongs in the other.
+//
+// what the edge form writes instead of the band: the pairs with r2 >= min_r2 as records of 16 bytes
+struct LdEdgeOut {
+    double min_r2;                   // not NaN
+    uint4 *edges;                    // {a, b, r2 low word, r2 high word} per record: hpgv_ld_edge; may be null when cap is 0
+    unsigned long long cap;          // records behind `edges`: nothing is stored past them
+    unsigned long long *n_edges;     // zeroed before the launch; ends as the number of qualifying pairs, stored or not
+};
+
+__global__ __launch_bounds__(256) void k_ld_edges(const LdArgs A, const LdEdgeOut E) {
+    __shared__ uint4 bt[2][3][LD_BT * LD_LDS_ROW];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int col = lane & 15, kq = lane >> 4;
+    // workgroup -> (tile, pass), see "Grid" above
+    const int range = (int)(blockIdx.x & 7u);
+    const unsigned seq = blockIdx.x >> 3;
+    const int in_range = (int)(seq / (unsigned)A.passes), pass = (int)(seq % (unsigned)A.passes);
+    const int tile = range * A.tiles_per_range + in_range;
+    if (in_range >= A.tiles_per_range || tile >= A.tiles) return;          // (the whole workgroup)
+    const int a0 = tile * LD_VT, b0 = a0 + pass * LD_BT;
+    // nothing to write: the group lies past the last row or wholly below b_begin
+    if (b0 >= A.n_variants || b0 + LD_BT <= A.b_begin) return;
+
+    const int aw = a0 + wave * 16;                                         // the wave's 16 earlier variants
+    const int a_lane = aw + col;
+    const bool a_ok = a_lane < A.n_variants;
+    const uint8_t *arow = A.gt + (size_t)(a_ok ? a_lane : 0) * A.pitch;
+    const int steps = (A.chunks + 3) / 4;
+    // the chunk of the later rows this thread stages: row tid >> 2 of the group, chunk tid & 3 of the k-step
+    const int sr = tid >> 2, sc = tid & 3;
+    const bool b_ok = b0 + sr < A.n_variants;
+    const uint8_t *brow = A.gt + (size_t)(b_ok ? b0 + sr : 0) * A.pitch;
+
+    // block n of the wave holds the pairs (aw .. aw + 15) x (b0 + 16 n .. b0 + 16 n + 15); in the band when a pair of it is
+    bool live[LD_NT];
+    bool any = false;
+#pragma unroll
+    for (int n = 0; n < LD_NT; ++n) {
+        const int bc = b0 + n * 16;
+        live[n] = bc + 15 > aw && bc <= aw + 15 + A.window && bc + 15 >= A.b_begin && bc < A.n_variants && aw < A.n_variants;
+        any = any || live[n];
+    }
+
+    auto a_chunk = [&](int s) -> uint4 {
+        const int c = s * 4 + kq;
+        if (any && a_ok && c < A.chunks) return load16o<false>(arow, (uint32_t)c * 16u);
+        return make_uint4(~0u, ~0u, ~0u, ~0u);                             // all missing: contributes nothing
+    };
+    auto b_chunk = [&](int s) -> uint4 {
+        const int c = s * 4 + sc;
+        if (b_ok && c < A.chunks) return load16o<false>(brow, (uint32_t)c * 16u);
+        return make_uint4(~0u, ~0u, ~0u, ~0u);
+    };
+    auto stage = [&](int buf, const uint4 &raw) {
+        uint4 v, g, q;
+        ld_planes(raw.x, v.x, g.x, q.x);
+        ld_planes(raw.y, v.y, g.y, q.y);
+        ld_planes(raw.z, v.z, g.z, q.z);
+        ld_planes(raw.w, v.w, g.w, q.w);
+        bt[buf][0][sr * LD_LDS_ROW + sc] = v;
+        bt[buf][1][sr * LD_LDS_ROW + sc] = g;
+        bt[buf][2][sr * LD_LDS_ROW + sc] = q;
+    };
+
+    // per block the sums in counts6 order: n, sa, sb, saa, sbb, sab
+    perm_i32x4 acc[LD_NT][6];
+#pragma unroll
+    for (int n = 0; n < LD_NT; ++n)
+#pragma unroll
+        for (int k = 0; k < 6; ++k) acc[n][k] = perm_i32x4{0, 0, 0, 0};
+
+    stage(0, b_chunk(0));
+    uint4 ga = a_chunk(0);
+    __syncthreads();
+
+    for (int s = 0; s < steps; ++s) {
+        const bool more = s + 1 < steps;
+        uint4 gan = make_uint4(~0u, ~0u, ~0u, ~0u), gbn = gan;
+        if (more) { gan = a_chunk(s + 1); gbn = b_chunk(s + 1); }
+        if (any) {
+            perm_i32x4 av, ag, aq;
+            {
+                uint32_t v, g, q;
+                ld_planes(ga.x, v, g, q); av[0] = (int)v; ag[0] = (int)g; aq[0] = (int)q;
+                ld_planes(ga.y, v, g, q); av[1] = (int)v; ag[1] = (int)g; aq[1] = (int)q;
+                ld_planes(ga.z, v, g, q); av[2] = (int)v; ag[2] = (int)g; aq[2] = (int)q;
+                ld_planes(ga.w, v, g, q); av[3] = (int)v; ag[3] = (int)g; aq[3] = (int)q;
+            }
+            const int cur = s & 1;
+#pragma unroll
+            for (int n = 0; n < LD_NT; ++n) {
+                if (!live[n]) continue;
+                const int at = (n * 16 + col) * LD_LDS_ROW + kq;
+                const uint4 pv = bt[cur][0][at], pg = bt[cur][1][at], pq = bt[cur][2][at];
+                const perm_i32x4 bv = {(int)pv.x, (int)pv.y, (int)pv.z, (int)pv.w};
+                const perm_i32x4 bg = {(int)pg.x, (int)pg.y, (int)pg.z, (int)pg.w};
+                const perm_i32x4 bq = {(int)pq.x, (int)pq.y, (int)pq.z, (int)pq.w};
+                acc[n][0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(av, bv, acc[n][0], 0, 0, 0);
+                acc[n][1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(ag, bv, acc[n][1], 0, 0, 0);
+                acc[n][2] = __builtin_amdgcn_mfma_i32_16x16x64_i8(av, bg, acc[n][2], 0, 0, 0);
+                acc[n][3] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aq, bv, acc[n][3], 0, 0, 0);
+                acc[n][4] = __builtin_amdgcn_mfma_i32_16x16x64_i8(av, bq, acc[n][4], 0, 0, 0);
+                acc[n][5] = __builtin_amdgcn_mfma_i32_16x16x64_i8(ag, bg, acc[n][5], 0, 0, 0);
+            }
+        }
+        if (more) stage((s + 1) & 1, gbn);
+        __syncthreads();
+        ga = gan;
+    }
+
+    // ---- epilogue: acc[n][k][r] belongs to the pair (a, b) = (aw + 4 kq + r, b0 + 16 n + col)
+    const bool filter = A.chrom != nullptr;
+    // The edge form: the same r2 per pair (NaN where the band form writes NaN or nothing: NaN >= x is false), then per
+    // (block, register) the wave's qualifying lanes by ballot, ONE 64-bit add of their number for the wave, and each such
+    // lane's record at the returned base + its rank among them, one 16-byte store, when that index is below `cap`.  live[n]
+    // is the same for every lane of the wave, so every lane reaches the ballot.
+#pragma unroll
+    for (int n = 0; n < LD_NT; ++n) {
+        if (!live[n]) continue;
+        const int b = b0 + n * 16 + col;
+        const bool b_in = b >= A.b_begin && b < A.n_variants;
+        const bool b_skip = b_in && A.skip != nullptr && A.skip[b] != 0;
+        const int b_chrom = (b_in && filter) ? A.chrom[b] : 0;
+        const long long b_pos = (b_in && filter) ? (long long)A.pos[b] : 0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int a = aw + kq * 4 + r, d = b - a;
+            double v = ld_nan();
+            if (b_in && d >= 1 && d <= A.window) {                     // (so 0 <= a < b < n_variants)
+                bool out = b_skip || (A.skip != nullptr && A.skip[a] != 0);
+                if (filter && !out) {
+                    const long long dist = b_pos - (long long)A.pos[a];
+                    out = A.chrom[a] != b_chrom || (A.max_bp >= 0 && (dist < 0 ? -dist : dist) > A.max_bp);
+                }
+                if (!out) v = ld_r2_value(acc[n][0][r], acc[n][1][r], acc[n][2][r], acc[n][3][r], acc[n][4][r], acc[n][5][r]);
+            }
+            const bool hit = v >= E.min_r2;
+            const unsigned long long mask = __ballot(hit);
+            if (mask == 0) continue;                                   // (the whole wave)
+            const int leader = __builtin_amdgcn_readfirstlane(__ffsll((long long)mask) - 1);
+            unsigned long long base = 0;
+            if (lane == leader)
+                base = __hip_atomic_fetch_add(E.n_edges, (unsigned long long)__popcll(mask), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)base, leader);
+            const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(base >> 32), leader);
+            const unsigned long long rank = (unsigned long long)__popcll(mask & ((1ull << lane) - 1ull));
+            const unsigned long long at = (((unsigned long long)hi << 32) | lo) + rank;
+            if (hit && at < E.cap) {
+                const unsigned long long bits = (unsigned long long)__double_as_longlong(v);
+                E.edges[at] = make_uint4((unsigned)a, (unsigned)b, (unsigned)bits, (unsigned)(bits >> 32));
             }
         }
     }

@@ -6,6 +6,7 @@
 #include "hpgv_text_kernels.h"
 #include "hpgv_text2_kernels.h"
 #include "hpgv_inherit_kernels.h"
+#include "hpgv_rows_kernels.h"
 
 extern "C" {
 
@@ -280,7 +281,100 @@ int text_front(hpgv_ctx *ctx, Slot *s, int which, const Layout &L, const char *t
     return hpgv_layout_dev(ctx, which, S->d_raw, raw_pitch, nl, s->laid.as<uint8_t>(), s->stream);
 }
 
+namespace {
+
+// scratch of the gather: dst_row[n_rows + 1], then the scan's block sums
+size_t rows_scratch_bytes(int n_rows) { return ((size_t)n_rows + 1 + ((size_t)n_rows + 1023) / 1024 + 1) * sizeof(uint64_t); }
+
+// dst_row = the exclusive scan of the flags (n_rows > 0)
+int rows_scan(hpgv_ctx *ctx, const uint8_t *d_keep, int n_rows, unsigned long long *d_dst_row, hipStream_t st) {
+    const int hb = (n_rows + 1023) / 1024;
+    unsigned long long *d_block = d_dst_row + (size_t)n_rows + 1;
+    hipLaunchKernelGGL(hpgv::k_rows_kept_sums, dim3((unsigned)hb), dim3(1024), 0, st, d_keep, n_rows, d_block);
+    hipLaunchKernelGGL(hpgv::k_head_bases, dim3(1), dim3(1024), 0, st, d_block, hb);
+    hipLaunchKernelGGL(hpgv::k_rows_kept_offsets, dim3((unsigned)hb), dim3(1024), 0, st, d_keep, n_rows, (const unsigned long long *)d_block, d_dst_row);
+    HIPCHK(ctx, hipGetLastError());
+    return HPGV_OK;
+}
+
+// the kept rows to their places, the index array and the count (n_rows > 0, after rows_scan on the same stream)
+int rows_copy(hpgv_ctx *ctx, const uint8_t *d_src, size_t src_pitch, size_t row_bytes, int n_rows, const uint8_t *d_keep,
+              const unsigned long long *d_dst_row, uint8_t *d_dst, size_t dst_pitch, int32_t *d_index, int32_t *d_n_kept, hipStream_t st) {
+    const bool aligned = ((src_pitch | dst_pitch | (uintptr_t)d_src | (uintptr_t)d_dst) & 15) == 0;
+    int T = 1;
+    while (T < 64 && 16ull * (unsigned long long)T < row_bytes) T <<= 1;
+    const long long waves = ((long long)n_rows + 64 / T - 1) / (64 / T);
+    long long wgs = (waves + 3) / 4;
+    const long long most = (long long)ctx->n_cus * 8;
+    wgs = wgs < 1 ? 1 : (wgs > most ? most : wgs);
+    if (aligned)
+        hipLaunchKernelGGL(hpgv::k_rows_copy<true>, dim3((unsigned)wgs), dim3(256), 0, st, d_src, src_pitch, row_bytes, n_rows, d_keep, d_dst_row,
+                           d_dst, dst_pitch, d_index, d_n_kept);
+    else
+        hipLaunchKernelGGL(hpgv::k_rows_copy<false>, dim3((unsigned)wgs), dim3(256), 0, st, d_src, src_pitch, row_bytes, n_rows, d_keep, d_dst_row,
+                           d_dst, dst_pitch, d_index, d_n_kept);
+    HIPCHK(ctx, hipGetLastError());
+    return HPGV_OK;
+}
+
+}  // namespace
+
+// the back half of hpgv_assoc_select_text (hpgv_tool_capi.hip), once the tool's results are out and the stream is idle: flags from
+// the statuses (the caller's, with the record filters' verdicts in them) and the device p-values, the scan, and -- when they fit
+// rows_cap -- the candidate rows of the slot's raw matrix, compacted on the device, into rows_out
+int select_rows(hpgv_ctx *ctx, Slot *s, const Staged &S, int n_samples, const int32_t *status, const char *d_p, size_t p_stride, double p_max,
+                int32_t *sel, uint8_t *rows_out, size_t rows_pitch, int rows_cap, int *n_sel) {
+    int rc;
+    const int nl = S.n;
+    const size_t n = (size_t)nl, off_index = round_up(n, 16), off_count = off_index + n * sizeof(int32_t), off_scan = round_up(off_count + 4, 16);
+    HIPCHK(ctx, s->perm.reserve_slack(off_scan + rows_scratch_bytes(nl) + 16));
+    uint8_t *d_keep = s->perm.as<uint8_t>();
+    int32_t *d_index = (int32_t *)(s->perm.as<char>() + off_index), *d_count = (int32_t *)(s->perm.as<char>() + off_count);
+    unsigned long long *d_dst_row = (unsigned long long *)(s->perm.as<char>() + off_scan);
+    HIPCHK(ctx, hipMemcpyAsync(s->status.p, status, n * sizeof(int32_t), hipMemcpyHostToDevice, s->stream));
+    hipLaunchKernelGGL(hpgv::k_select_flags, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, s->stream, s->status.as<const int32_t>(), d_p, p_stride, nl,
+                       p_max, d_keep);
+    HIPCHK(ctx, hipGetLastError());
+    if ((rc = rows_scan(ctx, d_keep, nl, d_dst_row, s->stream))) return rc;
+    unsigned long long kept = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&kept, d_dst_row + n, sizeof kept, hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(ctx, hipStreamSynchronize(s->stream));
+    *n_sel = (int)kept;
+    // the compact block: the candidates alone, rows a raw pitch apart.  One row of room where there is no candidate or no room in
+    // the caller's block: the copy kernel still writes the index array, and stores no row byte then (no flag set, or none wanted)
+    const bool fits = (int)kept <= rows_cap;
+    const size_t dpitch = S.raw_pitch;
+    HIPCHK(ctx, s->gtally.reserve_slack((fits && kept ? (size_t)kept : 1) * dpitch + 16));
+    if ((rc = rows_copy(ctx, S.d_raw, S.raw_pitch, fits ? (size_t)n_samples : 0, nl, d_keep, d_dst_row, s->gtally.as<uint8_t>(), fits ? dpitch : 0, d_index,
+                        d_count, s->stream))) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(sel, d_index, n * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
+    if (fits && kept && n_samples > 0)
+        HIPCHK(ctx, hipMemcpy2DAsync(rows_out, rows_pitch, s->gtally.p, dpitch, (size_t)n_samples, (size_t)kept, hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(ctx, hipStreamSynchronize(s->stream));
+    return HPGV_OK;
+}
+
 extern "C" {
+
+size_t hpgv_rows_gather_scratch_bytes(int n_rows) { return n_rows > 0 ? rows_scratch_bytes(n_rows) : 16; }
+
+int hpgv_rows_gather_dev(hpgv_ctx *ctx, const uint8_t *d_src, size_t src_pitch, size_t row_bytes, int n_rows, const uint8_t *d_keep,
+                         uint8_t *d_dst, size_t dst_pitch, int32_t *d_index, int32_t *d_n_kept, void *d_scratch, void *stream) {
+    HPGV_ABI_TRY
+    ctx = first_member(ctx);
+    if (!ctx) return HPGV_ERR_INVALID;
+    if (n_rows < 0 || !d_n_kept || (n_rows > 0 && (!d_keep || !d_index || !d_scratch || (row_bytes > 0 && (!d_src || !d_dst)))))
+        return fail(ctx, HPGV_ERR_INVALID, "bad rows_gather arguments");
+    if (src_pitch < row_bytes || dst_pitch < row_bytes) return fail(ctx, HPGV_ERR_INVALID, "a pitch below row_bytes %zu", row_bytes);
+    if (((uintptr_t)d_scratch & 7) || ((uintptr_t)d_index & 3) || ((uintptr_t)d_n_kept & 3))
+        return fail(ctx, HPGV_ERR_INVALID, "d_scratch must be 8-byte aligned, d_index and d_n_kept 4-byte aligned");
+    DeviceGuard g(ctx->device);
+    hipStream_t st = (hipStream_t)stream;
+    if (n_rows == 0) { HIPCHK(ctx, hipMemsetAsync(d_n_kept, 0, sizeof(int32_t), st)); return HPGV_OK; }
+    if (const int rc = rows_scan(ctx, d_keep, n_rows, (unsigned long long *)d_scratch, st)) return rc;
+    return rows_copy(ctx, d_src, src_pitch, row_bytes, n_rows, d_keep, (const unsigned long long *)d_scratch, d_dst, dst_pitch, d_index, d_n_kept, st);
+    HPGV_ABI_CATCH(ctx)
+}
 
 int hpgv_tokenize(hpgv_ctx *ctx, const char *text, size_t text_bytes, int n_samples, int strict, int max_lines,
                   int *n_lines, uint64_t *line_off, uint32_t *field_off, uint8_t *gt, size_t pitch,

@@ -5,6 +5,8 @@
 // which is written once for both.
 #include "hpgv_internal.h"
 #include "hpgv_batch_kernels.h"
+#include <cstddef>
+#include <utility>
 
 namespace {
 
@@ -177,9 +179,10 @@ static int launch_batch(hpgv_ctx *ctx, Slot *s, const Staged &S, hpgv::BatchArgs
 // ---- the tools' back halves: from a staged matrix to the caller's arrays, written once for a batch and a text -------------
 
 // chi-square or Fisher per variant.  A text that skipped the layout is counted by k_assoc_rows where that kernel takes
-// the cohort; any matrix that skipped it goes through the fused kernel; a laid-out one through the scans' kernel chain
+// the cohort; any matrix that skipped it goes through the fused kernel; a laid-out one through the scans' kernel chain.
+// p_at (may be null): where the p-values lie on the device when this returns, p_i at p_at->first + i * p_at->second bytes
 static int assoc_finish(hpgv_ctx *ctx, Slot *s, int task, const Staged &S, int32_t *A1, int32_t *A2, int32_t *U1, int32_t *U2,
-                        double *odds, double *chisq, double *p) {
+                        double *odds, double *chisq, double *p, std::pair<const char *, size_t> *p_at = nullptr) {
     int rc;
     const int nv = S.n;
     const size_t n = (size_t)nv;
@@ -190,6 +193,7 @@ static int assoc_finish(hpgv_ctx *ctx, Slot *s, int task, const Staged &S, int32
     }
     int32_t *d_counts = s->tally.as<int32_t>();
     double *d_odds = s->dbl.as<double>(), *d_chisq = d_odds + n, *d_p = d_odds + 2 * n;
+    if (p_at) *p_at = {(const char *)d_p, sizeof(double)};
     auto statistics = [&] {
         return chi ? hpgv_assoc_chisq_dev(ctx, d_counts, nv, d_odds, d_chisq, d_p, s->stream)
                    : hpgv_assoc_fisher_dev(ctx, d_counts, nv, d_odds, d_p, s->stream);
@@ -224,6 +228,7 @@ static int assoc_finish(hpgv_ctx *ctx, Slot *s, int task, const Staged &S, int32
         rc = chi ? launch_batch<hpgv::BATCH_CHISQ>(ctx, s, S, A, sizeof(hpgv::BatchAssocRec))
                  : launch_batch<hpgv::BATCH_FISHER>(ctx, s, S, A, sizeof(hpgv::BatchAssocRec));
         if (rc) return rc;
+        if (p_at) *p_at = {(const char *)s->res.d + offsetof(hpgv::BatchAssocRec, p), sizeof(hpgv::BatchAssocRec)};
         const hpgv::BatchAssocRec *r = (const hpgv::BatchAssocRec *)s->res.h;
         for (size_t i = 0; i < n; ++i) {
             A1[i] = r[i].A1; A2[i] = r[i].A2; U1[i] = r[i].U1; U2[i] = r[i].U2;
@@ -484,6 +489,38 @@ int hpgv_assoc_text(hpgv_ctx *ctx, int task, const char *text, size_t text_bytes
     if ((rc = text_front(ctx, s, HPGV_LAYOUT_ASSOC, ctx->assoc, text, text_bytes, max_lines, n_lines, line_off, field_off, status, &S, !fused))) return rc;
     if (S.n == 0) { HIPCHK(ctx, hipStreamSynchronize(s->stream)); return HPGV_OK; }
     return assoc_finish(ctx, s, task, S, A1, A2, U1, U2, odds, chisq, p);
+    HPGV_ABI_CATCH(ctx)
+}
+
+int hpgv_assoc_select_text(hpgv_ctx *ctx, int task, const char *text, size_t text_bytes, int max_lines, int *n_lines,
+                           uint64_t *line_off, uint32_t *field_off, int32_t *status, int32_t *A1, int32_t *A2,
+                           int32_t *U1, int32_t *U2, double *odds, double *chisq, double *p,
+                           double p_max, int32_t *sel, uint8_t *rows_out, size_t rows_pitch, int rows_cap, int *n_sel) {
+    HPGV_ABI_TRY
+    GROUP_DEAL_TEXT(ctx, text, hpgv_assoc_select_text(m_, task, text, text_bytes, max_lines, n_lines, line_off, field_off, status, A1, A2, U1, U2, odds,
+                                                      chisq, p, p_max, sel, rows_out, rows_pitch, rows_cap, n_sel))
+    if (!ctx) return HPGV_ERR_INVALID;
+    if (task != HPGV_TASK_CHISQ && task != HPGV_TASK_FISHER) return fail(ctx, HPGV_ERR_INVALID, "task must be CHISQ or FISHER");
+    if (!ctx->assoc.set) return fail(ctx, HPGV_ERR_STATE, "hpgv_set_cohort has not been called");
+    if (!n_lines || max_lines < 0 || (text_bytes > 0 && !text) ||
+        (max_lines > 0 && (!A1 || !A2 || !U1 || !U2 || !odds || !p || (task == HPGV_TASK_CHISQ && !chisq))))
+        return fail(ctx, HPGV_ERR_INVALID, "bad assoc_text arguments");
+    if (!n_sel || rows_cap < 0 || (max_lines > 0 && !sel) || (rows_cap > 0 && (!rows_out || rows_pitch < (size_t)ctx->assoc.n_samples)) || p_max != p_max)
+        return fail(ctx, HPGV_ERR_INVALID, "bad assoc_select_text arguments");
+    *n_lines = 0;
+    *n_sel = 0;
+    if (max_lines == 0) return HPGV_OK;
+    std::vector<int32_t> own_status;             // (before the lease: queued copies into it end with the lease)
+    HPGV_LEASE_SLOT(ctx)
+    const bool fused = batch_fused_ok(ctx, ctx->assoc.n_samples);
+    if (fused && task == HPGV_TASK_FISHER && (rc = logfact_check(ctx))) return rc;
+    if (!status) { own_status.assign((size_t)max_lines, 0); status = own_status.data(); }
+    Staged S;
+    if ((rc = text_front(ctx, s, HPGV_LAYOUT_ASSOC, ctx->assoc, text, text_bytes, max_lines, n_lines, line_off, field_off, status, &S, !fused))) return rc;
+    if (S.n == 0) { HIPCHK(ctx, hipStreamSynchronize(s->stream)); return HPGV_OK; }
+    std::pair<const char *, size_t> p_at{nullptr, 0};
+    if ((rc = assoc_finish(ctx, s, task, S, A1, A2, U1, U2, odds, chisq, p, &p_at))) return rc;
+    return select_rows(ctx, s, S, ctx->assoc.n_samples, status, p_at.first, p_at.second, p_max, sel, rows_out, rows_pitch, rows_cap, n_sel);
     HPGV_ABI_CATCH(ctx)
 }
 

@@ -40,6 +40,12 @@ static int run_batch_lines(run_batch_t *b) {
         b->rows_cap = (size_t)b->max_lines * (size_t)b->row_width;
         if (!(b->rows = (uint8_t *)malloc(b->rows_cap + 1))) return HPGV_ERR_NOMEM;
     }
+    if (b->run->clump) {                                 /* a candidate in eight lines to begin with: the engine step grows the block */
+        free(b->sel);
+        b->sel = (int32_t *)malloc(sizeof(int32_t) * (size_t)b->max_lines);
+        if (!b->crows) { b->crows_cap = b->max_lines / 8 + 64; b->crows = (uint8_t *)malloc((size_t)b->crows_cap * (size_t)(b->n_smiss > 0 ? b->n_smiss : 1)); }
+        if (!b->sel || !b->crows) return HPGV_ERR_NOMEM;
+    }
     if (run_batch_stats_arrays(b)) return HPGV_ERR_NOMEM;
     return (b->line_off && b->field_off && b->status && b->ints && b->dbl) ? HPGV_OK : HPGV_ERR_NOMEM;
 }
@@ -64,7 +70,7 @@ void run_batch_free(run_batch_t *b) {
     b->text = NULL;
     free(b->line_off); free(b->field_off); free(b->status); free(b->ints); free(b->dbl); free(b->rows); free(b->n_ge); free(b->bmax);
     free(b->c8); free(b->hw); free(b->merr); free(b->midx); free(b->mtab); free(b->smiss); free(b->cerr); free(b->gc8); free(b->ghw);
-    free(b->keep);
+    free(b->keep); free(b->sel); free(b->crows);
     free(b->sp_range); free(b->sp_len); free(b->sp_name); free(b->sp_names);
 }
 

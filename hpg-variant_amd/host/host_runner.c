@@ -113,7 +113,23 @@ static void *pipe_engine(void *v) {
             case RUN_TDT_PERM: what = "hpgv_tdt_perm_text";
                 rc = hpgv_tdt_perm_text(g_ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status,
                                         b->ints, b->ints + m, b->dbl, b->dbl + m, b->dbl + 2 * m, b->n_ge, b->bmax); break;
-            case RUN_CHISQ: case RUN_FISHER: what = "hpgv_assoc_text";
+            case RUN_CHISQ: case RUN_FISHER:
+                if (P->run->clump) {                     /* the same call, which also leaves the batch's candidate rows (p <= p2) */
+                    what = "hpgv_assoc_select_text";
+                    rc = hpgv_assoc_select_text(g_ctx, tool, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status,
+                                                b->ints, b->ints + m, b->ints + 2 * m, b->ints + 3 * m,
+                                                b->dbl, tool == RUN_CHISQ ? b->dbl + m : NULL, b->dbl + 2 * m,
+                                                P->run->clump->p2, b->sel, b->crows, (size_t)P->run->n_samples, b->crows_cap, &b->n_sel);
+                    if (!rc && b->n_lines <= b->max_lines && b->n_sel > b->crows_cap) {      /* more candidates than rows: again, with room */
+                        free(b->crows);
+                        b->crows_cap = b->n_sel + b->n_sel / 8 + 16;
+                        b->crows = (uint8_t *)malloc((size_t)b->crows_cap * (size_t)(P->run->n_samples > 0 ? P->run->n_samples : 1));
+                        if (!b->crows) { b->crows_cap = 0; rc = HPGV_ERR_NOMEM; break; }
+                        continue;
+                    }
+                    break;
+                }
+                what = "hpgv_assoc_text";
                 rc = hpgv_assoc_text(g_ctx, tool, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status,
                                      b->ints, b->ints + m, b->ints + 2 * m, b->ints + 3 * m,
                                      b->dbl, tool == RUN_CHISQ ? b->dbl + m : NULL, b->dbl + 2 * m); break;
@@ -213,6 +229,133 @@ static int run_perm_write(run_t *R, const char *out_path) {
         else if (hpgv_host_sort_output_file(path)) fprintf(stderr, "WARN: %s could not be sorted by chromosome and position\n", path);
     }
     free(emp); free(path);
+    return rc;
+}
+
+/* ---- clumping: the candidates of a written batch kept for <out>.clumped, and that file ------------------------------------- */
+static int run_clump_add(run_t *R, const run_batch_t *b) {
+    run_clump_t *M = R->CL;
+    const int n = b->n_lines < b->max_lines ? b->n_lines : b->max_lines, m = b->max_lines;
+    const size_t ns = (size_t)R->n_samples;
+    for (int i = 0; i < n; i++) {
+        if (b->sel[i] < 0 || !record_passes(b, i)) continue;       /* (a candidate that only a host-side field filter drops leaves the store here) */
+        if (M->n == M->cap) {
+            const size_t cap = M->cap ? M->cap * 2 : 1024;
+            uint8_t *r = (uint8_t *)realloc(M->rows, cap * (ns ? ns : 1));
+            if (r) M->rows = r;
+            double *p = (double *)realloc(M->p, cap * sizeof *p);
+            if (p) M->p = p;
+            int32_t *c = (int32_t *)realloc(M->chrom, cap * sizeof *c);
+            if (c) M->chrom = c;
+            uint32_t *q = (uint32_t *)realloc(M->pos, cap * sizeof *q);
+            if (q) M->pos = q;
+            size_t *h = (size_t *)realloc(M->head, cap * sizeof *h);
+            if (h) M->head = h;
+            if (!r || !p || !c || !q || !h) return 1;
+            M->cap = cap;
+        }
+        const uint32_t *fo = b->field_off + 10 * (size_t)i;
+        const char *l = b->text + b->line_off[i];
+        const int lc = (int)(fo[1] - 1 - fo[0]), li = (int)(fo[3] - 1 - fo[2]);
+        const size_t need = (size_t)lc + (size_t)li + 32;
+        if (M->heads_len + need > M->heads_cap) {
+            const size_t cap = (M->heads_cap ? M->heads_cap * 2 : (size_t)1 << 16) + need;
+            char *h = (char *)realloc(M->heads, cap);
+            if (!h) return 1;
+            M->heads = h; M->heads_cap = cap;
+        }
+        int ch = -1;                                     /* chromosomes numbered in order of first appearance (a handful of names) */
+        for (int k = M->n_chroms - 1; k >= 0 && ch < 0; k--) if ((int)strlen(M->chrom_names[k]) == lc && !memcmp(M->chrom_names[k], l + fo[0], (size_t)lc)) ch = k;
+        if (ch < 0) {
+            if (M->n_chroms == M->chrom_cap) {
+                const int cap = M->chrom_cap ? M->chrom_cap * 2 : 32;
+                char **names = (char **)realloc(M->chrom_names, sizeof(char *) * (size_t)cap);
+                if (!names) return 1;
+                M->chrom_names = names; M->chrom_cap = cap;
+            }
+            if (!(M->chrom_names[M->n_chroms] = dupn(l + fo[0], lc))) return 1;
+            ch = M->n_chroms++;
+        }
+        const long pos = atol(l + fo[1]);
+        M->head[M->n] = M->heads_len;                    /* CHR, POS as the result file prints it, ID */
+        M->heads_len += (size_t)snprintf(M->heads + M->heads_len, need, "%.*s\t%ld\t%.*s", lc, l + fo[0], pos, li, l + fo[2]) + 1;
+        memcpy(M->rows + M->n * ns, b->crows + (size_t)b->sel[i] * ns, ns);
+        M->p[M->n] = b->dbl[2 * (size_t)m + (size_t)i];
+        M->chrom[M->n] = ch;
+        M->pos[M->n] = pos < 0 ? 0u : pos > 0xFFFFFFFFl ? 0xFFFFFFFFu : (uint32_t)pos;
+        M->n++;
+    }
+    return 0;
+}
+
+/* one hpgv_ld_edges over the store (a group: on member 0), hpgv_clump, the file */
+static int run_clump_write(run_t *R, const char *out_path) {
+    run_clump_t *M = R->CL;
+    const hpgv_run_clump_options_t *O = R->clump;
+    const size_t n = M->n;
+    int rc = HPGV_OK;
+    if (n > 0x7FFFFFFFu) { snprintf(g_err, sizeof g_err, "%zu candidates: more than one hpgv_ld_edges call takes", n); return HPGV_ERR_UNSUPPORTED; }
+    hpgv_ld_edge *edges = NULL;
+    uint64_t n_edges = 0, cap = (uint64_t)n * 4 + 1024;
+    hpgv_ctx *ctx = hpgv_group_size(g_ctx) > 1 ? hpgv_group_member(g_ctx, 0) : g_ctx;
+    for (int attempt = 0; attempt < 2 && !rc && n > 0; attempt++) {      /* the count exceeds the room: grow and repeat once */
+        free(edges);
+        if (!(edges = (hpgv_ld_edge *)malloc(sizeof *edges * (size_t)cap))) { rc = HPGV_ERR_NOMEM; break; }
+        if ((rc = hpgv_ld_edges(ctx, M->rows, (size_t)R->n_samples, (int)n, O->window, M->chrom, M->pos, O->max_bp, O->min_r2, edges, cap, &n_edges))) {
+            snprintf(g_err, sizeof g_err, "hpgv_ld_edges failed (%d): %s", rc, hpgv_last_error(ctx));
+            break;
+        }
+        if (n_edges <= cap) break;
+        if (attempt == 1) { snprintf(g_err, sizeof g_err, "hpgv_ld_edges: the number of edges grew between two calls"); rc = HPGV_ERR_INVALID; }
+        cap = n_edges;
+    }
+    int32_t *index_of = (int32_t *)malloc(sizeof(int32_t) * (n + 1)), *order = (int32_t *)malloc(sizeof(int32_t) * (n + 1));
+    size_t *first = (size_t *)calloc(n + 2, sizeof(size_t));
+    int32_t *member = (int32_t *)malloc(sizeof(int32_t) * (n + 1));
+    int n_clumps = 0;
+    if (!rc && (!index_of || !order || !first || !member)) rc = HPGV_ERR_NOMEM;
+    if (!rc && (rc = hpgv_clump((int)n, M->p, edges, n_edges, O->p1, index_of, order, &n_clumps))) snprintf(g_err, sizeof g_err, "hpgv_clump failed (%d)", rc);
+    char *path = (char *)malloc(strlen(out_path) + 12);
+    FILE *f = NULL;
+    if (!rc && !path) rc = HPGV_ERR_NOMEM;
+    if (!rc) {
+        sprintf(path, "%s.clumped", out_path);
+        if (!(f = fopen(path, "wb"))) { snprintf(g_err, sizeof g_err, "cannot create %s", path); rc = HPGV_ERR_INVALID; }
+    }
+    if (!rc) {
+        /* the claimed members of every index candidate, in file order: counts, offsets, fill */
+        for (size_t j = 0; j < n; j++) if (index_of[j] >= 0 && (size_t)index_of[j] != j) first[(size_t)index_of[j] + 1]++;
+        for (size_t j = 0; j < n; j++) first[j + 1] += first[j];
+        size_t *fill = (size_t *)malloc(sizeof(size_t) * (n + 1));
+        if (!fill) rc = HPGV_ERR_NOMEM;
+        else {
+            memcpy(fill, first, sizeof(size_t) * n);
+            for (size_t j = 0; j < n; j++) if (index_of[j] >= 0 && (size_t)index_of[j] != j) member[fill[index_of[j]]++] = (int32_t)j;
+            free(fill);
+            setvbuf(f, NULL, _IOFBF, 1u << 20);
+            fputs("#CHR\tPOS\tID\tP\tTOTAL\tSP2\n", f);
+            for (int k = 0; k < n_clumps; k++) {
+                const size_t i = (size_t)order[k], total = first[i + 1] - first[i];
+                fprintf(f, "%s\t%.6e\t%zu\t", M->heads + M->head[i], M->p[i], total);
+                if (!total) fputs("NONE", f);
+                for (size_t q = first[i]; q < first[i + 1]; q++) {
+                    const size_t j = (size_t)member[q];
+                    fprintf(f, "%s%s:%lu", q > first[i] ? "," : "", M->chrom_names[M->chrom[j]], (unsigned long)atol(strchr(M->heads + M->head[j], '\t') + 1));
+                }
+                fputc('\n', f);
+            }
+        }
+        if (fclose(f) != 0 && !rc) { snprintf(g_err, sizeof g_err, "cannot write %s", path); rc = HPGV_ERR_INVALID; }
+    }
+    /* the candidates whose distance window the candidate window cut short: candidate i + window + 1 is still in reach */
+    M->n_clumps = n_clumps; M->n_truncated = 0;
+    for (size_t i = 0; !rc && i + (size_t)O->window + 1 < n; i++) {
+        const size_t j = i + (size_t)O->window + 1;
+        const long long d = (long long)M->pos[j] - (long long)M->pos[i];
+        if (M->chrom[j] == M->chrom[i] && (O->max_bp < 0 || (d < 0 ? -d : d) <= O->max_bp)) M->n_truncated++;
+    }
+    if (!rc && M->n_truncated) fprintf(stderr, "WARN: the window of %d candidates cut the distance window of %ld candidates short\n", O->window, M->n_truncated);
+    free(edges); free(index_of); free(order); free(first); free(member); free(path);
     return rc;
 }
 
@@ -483,6 +626,7 @@ static int create_out(FILE **f, char **path, const char *prefix, const char *suf
 /* the tool's output files (split: its files as the records come).  The filter tool's .rejected is created empty without
  * save_rejected (filter_runner.c:63-68); stats: one file per phenotype (stats_runner.c:267-297), and its accumulator */
 static int run_outputs(run_t *R, const char *out_path) {
+    if (R->clump && !(R->CL = (run_clump_t *)calloc(1, sizeof *R->CL))) return HPGV_ERR_NOMEM;
     if (tool_perm(R->tool)) {
         R->PM = (run_perm_t *)calloc(1, sizeof *R->PM);
         if (R->PM) R->PM->tmax = (double *)calloc((size_t)R->n_perms, sizeof(double));      /* 0: the identity of the merge */
@@ -630,6 +774,7 @@ static int run_pipeline(run_t *R, size_t batch_bytes) {
                 if (write_batch(R->out, b, fmt + (fmt_set ? RUN_FMT_BUFS / 2 : 0), n_fmt, &wpool, &R->ord, use_fw ? &fw : NULL)) bad = "cannot write the result file";
                 for (int i = 0; i < b->n_lines; i++) if (record_passes(b, i)) R->written++;
                 if (tool_perm(R->tool) && !bad && run_perm_add(R, b)) bad = "out of memory for the permutation results";
+                if (R->CL && !bad && run_clump_add(R, b)) bad = "out of memory for the clumping candidates";
                 if (R->tool == RUN_STATS && !bad) { run_stats_add(R, b); if (R->gfd) write_group_lines(R->gfd, b); }      /* (the group files: by this thread) */
                 break;
             }
@@ -688,6 +833,12 @@ static int run_finish(run_t *R, int rc, const char *out_path) {
         if (!rc && R->PM) rc = run_perm_write(R, out_path);
         if (g_ctx) (void)(R->tool == RUN_TDT_PERM ? hpgv_set_tdt_flips(g_ctx, NULL, 0) : hpgv_set_perm_labels(g_ctx, NULL, 0));
         if (R->PM) { free(R->PM->tmax); free(R->PM->t_obs); free(R->PM->n_ge); free(R->PM->head); free(R->PM->heads); free(R->PM); R->PM = NULL; }
+    }
+    if (R->CL) {
+        run_clump_t *M = R->CL;
+        if (!rc) rc = run_clump_write(R, out_path);
+        for (int k = 0; k < M->n_chroms; k++) free(M->chrom_names[k]);
+        free(M->rows); free(M->p); free(M->chrom); free(M->pos); free(M->head); free(M->heads); free(M->chrom_names);
     }
     if (R->RS) { free(R->RS->smiss); free(R->RS->serr); free(R->RS); }
     free(R->ord.last); free(R->gfd); free(R->group_names); free(R->path); free(R->path_rej); free(R->trio_child);
@@ -806,6 +957,30 @@ int hpgv_run_assoc_perm(const char *vcf_path, const char *ped_path, const char *
     if (!vcf_path || !ped_path || !out_path) { snprintf(g_err, sizeof g_err, "vcf_path, ped_path and out_path must not be NULL"); return HPGV_ERR_INVALID; }
     if (n_perms < 1) { snprintf(g_err, sizeof g_err, "n_perms must be at least 1"); return HPGV_ERR_INVALID; }
     return run_file(&(run_t){ .tool = RUN_CHISQ_PERM, .filters = g_filters, .n_perms = n_perms, .perm_seed = seed }, vcf_path, ped_path, out_path, batch_bytes, n_variants_out);
+}
+
+/* the association run with LD clumping of its results: hpgv_run_assoc's file and <out_path>.clumped */
+int hpgv_run_assoc_clump(const char *vcf_path, const char *ped_path, const char *out_path, enum ASSOC_task task,
+                         const hpgv_run_clump_options_t *opt, size_t batch_bytes, long *n_variants_out,
+                         long *n_clumps_out, long *n_truncated_out) {
+    if (n_variants_out) *n_variants_out = 0;
+    if (n_clumps_out) *n_clumps_out = 0;
+    if (n_truncated_out) *n_truncated_out = 0;
+    if (!vcf_path || !ped_path || !out_path || !opt) { snprintf(g_err, sizeof g_err, "vcf_path, ped_path, out_path and the options must not be NULL"); return HPGV_ERR_INVALID; }
+    if (task != CHI_SQUARE && task != FISHER) { snprintf(g_err, sizeof g_err, "task must be CHI_SQUARE or FISHER"); return HPGV_ERR_INVALID; }
+    if (!(opt->p1 > 0.0 && opt->p1 <= 1.0) || !(opt->p2 > 0.0 && opt->p2 <= 1.0) || !(opt->p1 <= opt->p2)) {      /* (a NaN fails every comparison) */
+        snprintf(g_err, sizeof g_err, "clumping needs 0 < p1 <= p2 <= 1"); return HPGV_ERR_INVALID;
+    }
+    if (opt->min_r2 != opt->min_r2) { snprintf(g_err, sizeof g_err, "min_r2 is NaN"); return HPGV_ERR_INVALID; }
+    if (opt->window < 1 || opt->window > HPGV_LD_MAX_WINDOW) { snprintf(g_err, sizeof g_err, "window %d: 1 .. %d candidates", opt->window, HPGV_LD_MAX_WINDOW); return HPGV_ERR_INVALID; }
+    run_t R = { .tool = (run_tool_t)task, .filters = g_filters, .clump = opt };
+    const int rc = run_file(&R, vcf_path, ped_path, out_path, batch_bytes, n_variants_out);
+    if (R.CL) {
+        if (n_clumps_out) *n_clumps_out = R.CL->n_clumps;
+        if (n_truncated_out) *n_truncated_out = R.CL->n_truncated;
+        free(R.CL);
+    }
+    return rc;
 }
 
 /* the model tests' run: one line of five chi-squares and p-values per variant and, with n_perms >= 1, <out_path>.mperm of the

@@ -180,6 +180,9 @@ typedef struct {
     /* HPGV_OUT_BGZF: sp_len's top bits say what a bucket's bytes are -- SP_MEMBERS: BGZF members (deflated on the device),
      * SP_NEEDS_NL: whose text lacks its last newline */
     long n_skip;
+    /* clumping (run_t::clump): per line its number among the batch's candidates (p <= p2) or -1, and the candidates' genotype rows,
+     * n_samples bytes each, as hpgv_assoc_select_text leaves them */
+    int32_t *sel; uint8_t *crows; int crows_cap, n_sel;
 } run_batch_t;
 
 typedef struct { int na, miss_al, miss_gt, ac[15], gc[225]; } vcounts_t;
@@ -222,6 +225,15 @@ typedef struct {
     char *heads; size_t heads_len, heads_cap;
 } run_perm_t;
 
+/* clumping (hpgv_run_assoc_clump): the run's candidate store -- per written record with p <= p2, in file order, its genotype row
+ * (n_samples bytes), its p, its chromosome (numbered in order of first appearance) and position, and "CHR\tPOS\tID" */
+typedef struct {
+    uint8_t *rows; double *p; int32_t *chrom; uint32_t *pos; size_t *head; size_t n, cap;
+    char *heads; size_t heads_len, heads_cap;
+    char **chrom_names; int n_chroms, chrom_cap;
+    long n_clumps, n_truncated;
+} run_clump_t;
+
 /* one file run: built by its public entry (hpgv_run_*), its stages and the pipeline's threads (through the batches) share it */
 typedef struct run {
     run_tool_t tool;
@@ -238,6 +250,7 @@ typedef struct run {
     char *path, *path_rej; FILE *out, *out_rej, **gfd;   /* gfd: stats, one file per phenotype */
     split_files_t SF; run_stats_t *RS; order_track_t ord;
     int n_perms; uint64_t perm_seed; run_perm_t *PM;      /* the permutation tools */
+    const hpgv_run_clump_options_t *clump; run_clump_t *CL;      /* RUN_CHISQ / RUN_FISHER with <out>.clumped beside the file (NULL: without) */
     double t_opened, t_header, t_sort;
 } run_t;
 

@@ -437,6 +437,22 @@ int  hpgv_inheritance_scan_dev(hpgv_ctx *ctx, const uint8_t *d_gt, int n_variant
 int  hpgv_ld_window_dev(hpgv_ctx *ctx, const uint8_t *d_gt, size_t pitch, int n_variants, int b_begin, int window,
                         const int32_t *d_chrom /* may be NULL */, const uint32_t *d_pos /* may be NULL */, int64_t max_bp,
                         const uint8_t *d_skip /* may be NULL */, double *d_r2, int32_t *d_counts6 /* may be NULL */, void *stream);
+/* The EDGE form of the band: the same tile and loop with another epilogue (k_ld_edges, a kernel of its own), for a consumer that wants only the pairs
+ * above a threshold (PLINK's --clump-r2, --ld-window-r2) and would discard nearly all of a dense band.  The result is exactly the
+ * set {(a, b, r2) : a = b - d, r2 >= min_r2} over the band hpgv_ld_window_dev writes for the same arguments, r2 bit for bit the
+ * value written there.  NaN never compares >=, so no pair "outside the band" appears, and none without an earlier row.  The
+ * ORDER of the list is not defined (sort it where an order is needed).
+ * The call zeroes *d_n_edges itself on `stream`; it ends as the TRUE number of qualifying pairs even where that exceeds edge_cap.
+ * At most edge_cap records are stored and nothing past them; which of the qualifying pairs those are is not defined.
+ * edge_cap == 0 with d_edges == NULL is a legal count-only call.  Per wave and (16 x 16 block, register) the qualifying lanes are
+ * counted by ballot and claim their places with ONE relaxed 64-bit add; a record goes out as one 16-byte store.
+ * Refusals and alignment as hpgv_ld_window_dev (d_r2 aside); also HPGV_ERR_INVALID for a NaN min_r2, d_edges not 16-byte
+ * aligned or NULL with edge_cap > 0, d_n_edges NULL or not 8-byte aligned.  n_variants == b_begin succeeds with a count of 0. */
+typedef struct { int32_t a, b; double r2; } hpgv_ld_edge;   /* 16 bytes, a < b */
+int  hpgv_ld_edges_dev(hpgv_ctx *ctx, const uint8_t *d_gt, size_t pitch, int n_variants, int b_begin, int window,
+                       const int32_t *d_chrom /* may be NULL */, const uint32_t *d_pos /* may be NULL */, int64_t max_bp,
+                       const uint8_t *d_skip /* may be NULL */, double min_r2, hpgv_ld_edge *d_edges, uint64_t edge_cap,
+                       uint64_t *d_n_edges, void *stream);
 
 /* ---- the variant-sharded resident scan of a GROUP context: what the runner's worker loop
  *      (assoc_runner.c:106-207, tdt_runner.c:150-200, stats_runner.c:176-215) becomes when the cohort lies in the HBM of
@@ -618,6 +634,19 @@ int  hpgv_text_multisplit(hpgv_ctx *ctx, const char *text, const uint8_t *bucket
 size_t hpgv_lines_multisplit_scratch_bytes(int n_lines, int n_buckets);
 int  hpgv_lines_multisplit_dev(hpgv_ctx *ctx, const char *d_text, const uint64_t *d_line_off, int n_lines, const uint8_t *d_bucket,
                                int n_buckets, char *d_out, uint64_t *d_bucket_off, void *d_scratch, void *stream);
+/* The same for rows of one length: the rows i of d_src (src_pitch apart) with d_keep[i] != 0 go to consecutive rows of d_dst
+ * (dst_pitch apart) in source order, row_bytes of each.  d_index (n_rows int32): the destination row of row i, or -1;
+ * *d_n_kept: the number of kept rows (0 for n_rows == 0).  Three launches for flags -> exclusive scan (the partition's scan, over
+ * ones) and one copy kernel, which moves whole 16-byte granules where both pitches and both pointers are multiples of 16 and
+ * single bytes otherwise.  Nothing is stored outside the kept rows' row_bytes: the bytes between two destination rows and behind
+ * the last one keep what they held.  The caller sizes d_dst for the rows it keeps (n_rows of them at most).  d_scratch:
+ * hpgv_rows_gather_scratch_bytes(n_rows) bytes of device memory, 8-byte aligned.  HPGV_ERR_INVALID for n_rows < 0, a pitch below
+ * row_bytes, a NULL d_n_kept, and with n_rows > 0 a NULL d_keep, d_index or d_scratch (d_src and d_dst may be NULL only with
+ * row_bytes == 0).  Asynchronous on `stream`. */
+size_t hpgv_rows_gather_scratch_bytes(int n_rows);
+int  hpgv_rows_gather_dev(hpgv_ctx *ctx, const uint8_t *d_src, size_t src_pitch, size_t row_bytes, int n_rows,
+                          const uint8_t *d_keep, uint8_t *d_dst, size_t dst_pitch, int32_t *d_index /* n_rows: destination row or -1 */,
+                          int32_t *d_n_kept, void *d_scratch, void *stream);
 
 /* BGZF written on the device: what the filter and split runners write with HPGV_OUT_BGZF.
  * The device primitive: d_text in n_segs segments, segment s = bytes [d_seg_off[s], d_seg_off[s + 1]) (device memory,
@@ -866,6 +895,22 @@ int  hpgv_assoc_text(hpgv_ctx *ctx, int task, const char *text, size_t text_byte
                      uint64_t *line_off, uint32_t *field_off, int32_t *status,
                      int32_t *A1, int32_t *A2, int32_t *U1, int32_t *U2,
                      double *odds, double *chisq, double *p);
+/* hpgv_assoc_text -- every argument up to p unchanged, the same outputs bit for bit -- which then, in the same slot and on
+ * the same stream, SELECTS lines: a small kernel builds one flag per line from the p-values on the device and the statuses,
+ * and line i is selected iff it is a record (status byte 0), is not HPGV_LINE_FILTERED, and p[i] <= p_max.  A NaN p is never
+ * selected; p == p_max is.  sel (sized max_lines): the number of the line among this call's selected lines, in line order, or
+ * -1.  The selected lines' genotype rows -- VCF column order, n_samples bytes each, from the call's raw matrix, the form
+ * hpgv_ld and hpgv_ld_edges take -- are compacted on the device (hpgv_rows_gather_dev's kernels) and only that block is
+ * copied out: row k of rows_out (rows_pitch >= n_samples bytes apart) is the line with sel == k.  *n_sel is the number of
+ * selected lines; where it exceeds rows_cap no row is copied and sel is still valid (call again with room, or gather from a
+ * copy of the rows).  rows_out may be NULL when rows_cap is 0.  status may be NULL (the record filters then do not run, as in
+ * hpgv_assoc_text).  A NaN p_max, a NULL sel or n_sel, rows_cap < 0 and rows_pitch < n_samples are HPGV_ERR_INVALID.  On a
+ * GROUP context the call is dealt to a member exactly as hpgv_assoc_text is: batches are independent. */
+int  hpgv_assoc_select_text(hpgv_ctx *ctx, int task, const char *text, size_t text_bytes, int max_lines, int *n_lines,
+                            uint64_t *line_off, uint32_t *field_off, int32_t *status,
+                            int32_t *A1, int32_t *A2, int32_t *U1, int32_t *U2,
+                            double *odds, double *chisq, double *p,
+                            double p_max, int32_t *sel, uint8_t *rows_out, size_t rows_pitch, int rows_cap, int *n_sel);
 /* hpgv_assoc_text with task CHISQ plus n_ge (sized max_lines) and batch_max (n_perms doubles, overwritten): tokenizer,
  * HPGV_LAYOUT_ASSOC layout, scan, chi-square, then the permutation kernel.  The lines a caller of hpgv_assoc_text drops --
  * status 1 (not a record) and lines a record filter rejected (HPGV_LINE_FILTERED) -- take no part in batch_max and get
@@ -901,6 +946,14 @@ int  hpgv_tdt_perm_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, int 
  * members would cut the band at every seam. */
 int  hpgv_ld(hpgv_ctx *ctx, const uint8_t *gt, size_t pitch, int n_variants, int window, const int32_t *chrom /* may be NULL */,
              const uint32_t *pos /* may be NULL */, int64_t max_bp, double *r2, int32_t *counts6 /* may be NULL */);
+/* The edge form on a host batch: rows, layout, state and refusals as hpgv_ld (a GROUP context: HPGV_ERR_UNSUPPORTED), then
+ * hpgv_ld_edges_dev with b_begin = 0; a NaN min_r2 is HPGV_ERR_INVALID.  On return *n_edges is the true number of pairs with
+ * r2 >= min_r2.  Where it is <= edge_cap, edges[0 .. *n_edges) holds them sorted by (b, a) (sorted on the host after the copy);
+ * where it is larger the content of `edges` is unspecified and the caller calls again with room.  edges may be NULL when
+ * edge_cap is 0. */
+int  hpgv_ld_edges(hpgv_ctx *ctx, const uint8_t *gt, size_t pitch, int n_variants, int window, const int32_t *chrom /* may be NULL */,
+                   const uint32_t *pos /* may be NULL */, int64_t max_bp, double min_r2, hpgv_ld_edge *edges, uint64_t edge_cap,
+                   uint64_t *n_edges);
 /* tokenizer -> assoc layout -> hpgv_ld_window_dev with no matrix crossing the bus, as hpgv_assoc_model_text.  EVERY line of the
  * text is one row of the window: a line with status 1 (not a record) or flagged HPGV_LINE_FILTERED is a skipped row -- it keeps
  * its slot, and its pairs are NaN with zero counts.  No distance filter here: line_off / field_off come back for the caller,
@@ -931,6 +984,16 @@ int  hpgv_perm_pvalues(const double *t_obs, int n_variants, const int32_t *n_ge,
 /* r2 of six counts {n, sa, sb, saa, sbb, sab} by the expression of "LD" above: the function the kernel's epilogue calls, built for
  * the host.  No GPU call, no context. */
 double hpgv_ld_r2(const int32_t counts6[6]);
+/* Clump assignment (PLINK's default --clump, without overlap and without replication) of n candidates with p-values p and the
+ * undirected LD edges between them (hpgv_ld_edges' records; a and b are candidate numbers, duplicates are harmless, r2 is not
+ * read: the threshold was applied when the list was made).  Candidates are visited by ascending p, ties by ascending number; a
+ * NaN p is skipped; the visit stops at the first p > p1 (p == p1 is visited).  A visited candidate that is already claimed is
+ * skipped.  Otherwise it becomes the index of a new clump -- index_of[i] = i, and i is appended to clump_order -- and claims
+ * every not yet claimed candidate j joined to it by an edge: index_of[j] = i.  Everything else gets index_of = -1.
+ * clump_order (n entries of room, may be NULL) holds *n_clumps entries on return.  An endpoint outside 0 .. n - 1 is
+ * HPGV_ERR_INVALID, and so are n < 0 and a NULL p, index_of or n_clumps.  O(n log n + n_edges).  No GPU call, no context. */
+int  hpgv_clump(int n, const double *p, const hpgv_ld_edge *edges, uint64_t n_edges, double p1,
+                int32_t *index_of, int32_t *clump_order /* may be NULL */, int *n_clumps);
 
 /* streaming-read ceiling probe: reads `bytes` from d_buf with the scan's load
  * shape and no arithmetic; returns the kernel time in ms (diagnostic) */

@@ -317,6 +317,32 @@ int  hpgv_run_assoc_perm(const char *vcf_path, const char *ped_path, const char 
  * Same cohort, filters, record filters and input forms (plain, gzip, bgzip) as hpgv_run_assoc. */
 int  hpgv_run_assoc_model(const char *vcf_path, const char *ped_path, const char *out_path, int n_perms, uint64_t seed,
                           size_t batch_bytes, long *n_variants_out);
+/* hpgv_run_assoc with LD clumping of its results (PLINK's --clump, without overlap and without replication): out_path is
+ * written byte for byte as hpgv_run_assoc writes it, and <out_path>.clumped beside it, which groups the significant variants
+ * into clumps, each around its strongest variant.
+ *   Candidates.  Every batch goes through hpgv_assoc_select_text with p_max = p2: the rows with p <= p2 are compacted on the
+ *   device, and the writer stage appends the batch's candidate block and heads (CHR, POS, ID, p) to the run's store on the
+ *   host, in batch order.  Only records the result file also writes are kept: one dropped only by a host-side field filter
+ *   leaves the store there.  So the result depends neither on batch_bytes nor on the number of engine threads or devices.
+ *   Edges.  At the end ONE hpgv_ld_edges call over the candidate store (on a group context: member 0) with the chromosomes
+ *   numbered in order of first appearance, the positions, max_bp, min_r2, and `window` counted in CANDIDATES: a window of
+ *   1 024 candidates spans about 100 000 variants of a genome-wide file.  Where the count exceeds the room the list grows and
+ *   the call is repeated once.
+ *   Clumps.  hpgv_clump(p of the candidates, the edges, p1), then the file: the header "#CHR\tPOS\tID\tP\tTOTAL\tSP2" and one
+ *   line per clump in clump order (ascending p of the index variant, ties in file order): P printed with %.6e, TOTAL the
+ *   number of claimed members, SP2 the members as CHR:POS joined by commas in file order, or NONE.
+ *   *n_truncated_out (may be NULL) counts the candidates i for which candidate i + window + 1 exists, lies on the same
+ *   chromosome and within max_bp (max_bp < 0: the distance condition is dropped): for those the candidate window cut the
+ *   distance window short.  One WARN line on stderr when it is not 0.  *n_clumps_out (may be NULL): the clumps written.
+ * HPGV_ERR_INVALID before the engine is started, and no file written: a NULL path or NULL options, p1 or p2 outside (0, 1],
+ * p1 > p2, a NaN threshold, a window outside 1 .. HPGV_LD_MAX_WINDOW, a task other than CHI_SQUARE / FISHER.
+ * Same cohort, filters, record filters and input forms (plain, gzip, bgzip) as hpgv_run_assoc. */
+typedef struct { double p1, p2, min_r2; int64_t max_bp; int window; } hpgv_run_clump_options_t;
+/* PLINK's defaults: 1e-4, 1e-2, 0.5, 250000; window HPGV_LD_MAX_WINDOW */
+#define HPGV_RUN_CLUMP_DEFAULTS { 1e-4, 1e-2, 0.5, 250000, HPGV_LD_MAX_WINDOW }
+int  hpgv_run_assoc_clump(const char *vcf_path, const char *ped_path, const char *out_path, enum ASSOC_task task,
+                          const hpgv_run_clump_options_t *opt, size_t batch_bytes, long *n_variants_out,
+                          long *n_clumps_out, long *n_truncated_out);
 /* hpgv_run_tdt with max(T) family flips (include/hpgv.h "family flips"; PLINK's tdt --mperm): out_path is written byte for byte
  * as hpgv_run_tdt writes it, and <out_path>.mperm beside it with the header and line format of hpgv_run_assoc_perm's
  * ("#CHR\tPOS\tID\tEMP1\tEMP2", one line per written variant in the same sorted order, numbers as hpgv_host_format_f6 prints
