@@ -389,6 +389,24 @@ def _ptr(a):
     return None if a is None else C.c_void_p(a.ctypes.data)
 
 
+def _text_call(text, max_lines):
+    """what a *_text wrapper opens with: the text as bytes, max_lines (default: a line per newline and one more), the length m
+    of its per-line arrays (at least 1), a zeroed status [m] and the cell for n_lines"""
+    if isinstance(text, str):
+        text = text.encode()
+    if max_lines is None:
+        max_lines = text.count(b"\n") + 1
+    m = max(max_lines, 1)
+    return text, max_lines, m, np.zeros(m, np.int32), C.c_int(0)
+
+
+def _text_result(nl, max_lines, **per_line):
+    """and what it closes with: n_lines and every per-line array (None stays None) cut to the lines the call wrote,
+    min(n_lines, max_lines)"""
+    k = min(nl.value, max_lines)
+    return dict(n_lines=nl.value, **{key: None if a is None else a[:k] for key, a in per_line.items()})
+
+
 class Engine:
     """One engine context on one device (thin wrapper over hpgv_ctx)."""
 
@@ -588,22 +606,15 @@ class Engine:
 
     def assoc_perm_text(self, text, max_lines=None):
         """hpgv_assoc_perm_text: hpgv_assoc_text with task CHISQ plus n_ge per line and batch_max per permutation."""
-        if isinstance(text, str):
-            text = text.encode()
-        if max_lines is None:
-            max_lines = text.count(b"\n") + 1
-        m = max(max_lines, 1)
+        text, max_lines, m, status, nl = _text_call(text, max_lines)
         A1, A2, U1, U2, n_ge = (np.zeros(m, np.int32) for _ in range(5))
         odds, chisq, p = (np.zeros(m, np.float64) for _ in range(3))
-        status = np.zeros(m, np.int32)
         bmax = np.zeros(max(getattr(self, "_n_perms", 0), 1), np.float64)
-        nl = C.c_int(0)
         self._chk(self.L.hpgv_assoc_perm_text(self.h, text, len(text), max_lines, C.byref(nl), None, None, _ptr(status),
                                               _ptr(A1), _ptr(A2), _ptr(U1), _ptr(U2), _ptr(odds), _ptr(chisq), _ptr(p),
                                               _ptr(n_ge), _ptr(bmax)))
-        k = min(nl.value, max_lines)
-        return dict(n_lines=nl.value, status=status[:k], A1=A1[:k], A2=A2[:k], U1=U1[:k], U2=U2[:k], odds=odds[:k],
-                    chisq=chisq[:k], p=p[:k], n_ge=n_ge[:k], batch_max=bmax[:self._n_perms])
+        return dict(_text_result(nl, max_lines, status=status, A1=A1, A2=A2, U1=U1, U2=U2, odds=odds, chisq=chisq, p=p, n_ge=n_ge),
+                    batch_max=bmax[:self._n_perms])
 
     def assoc_model(self, gt, perm=False):
         """hpgv_assoc_model: counts8 (nv, 8), chisq5 and p5 (nv, 5; columns MODEL_*); perm=True adds the trend permutation's n_ge
@@ -622,24 +633,16 @@ class Engine:
 
     def assoc_model_text(self, text, max_lines=None, perm=False):
         """hpgv_assoc_model_text: assoc_model on VCF data lines, the outputs per line; perm as in assoc_model."""
-        if isinstance(text, str):
-            text = text.encode()
-        if max_lines is None:
-            max_lines = text.count(b"\n") + 1
-        m = max(max_lines, 1)
+        text, max_lines, m, status, nl = _text_call(text, max_lines)
         c8 = np.zeros((m, 8), np.int32)
         chisq5, p5 = np.zeros((m, 5), np.float64), np.zeros((m, 5), np.float64)
-        status = np.zeros(m, np.int32)
         np_ = getattr(self, "_n_perms", 0)
         n_ge, bmax = (np.zeros(m, np.int32), np.zeros(max(np_, 1), np.float64)) if perm else (None, None)
-        nl = C.c_int(0)
         self._chk(self.L.hpgv_assoc_model_text(self.h, text, len(text), max_lines, C.byref(nl), None, None, _ptr(status),
                                                _ptr(c8), _ptr(chisq5), _ptr(p5), _ptr(n_ge), _ptr(bmax)))
-        k = min(nl.value, max_lines)
-        res = dict(n_lines=nl.value, status=status[:k], counts8=c8[:k], chisq5=chisq5[:k], p5=p5[:k])
-        if perm:
-            res.update(n_ge=n_ge[:k], batch_max=bmax[:np_])
-        return res
+        if not perm:
+            return _text_result(nl, max_lines, status=status, counts8=c8, chisq5=chisq5, p5=p5)
+        return dict(_text_result(nl, max_lines, status=status, counts8=c8, chisq5=chisq5, p5=p5, n_ge=n_ge), batch_max=bmax[:np_])
 
     def ld(self, gt, window, chrom=None, pos=None, max_bp=-1, counts=True):
         """hpgv_ld: r2 (nv, window) and, with counts, counts6 (nv, window, 6); element [b, d - 1] is the pair (b - d, b) over the
@@ -675,18 +678,11 @@ class Engine:
 
     def ld_text(self, text, window, max_lines=None, counts=True):
         """hpgv_ld_text: ld on VCF data lines, one row of the window per line (skipped lines keep their slot)."""
-        if isinstance(text, str):
-            text = text.encode()
-        if max_lines is None:
-            max_lines = text.count(b"\n") + 1
-        m = max(max_lines, 1)
+        text, max_lines, m, status, nl = _text_call(text, max_lines)
         r2 = np.zeros((m, max(window, 1)), np.float64)
         c6 = np.zeros((m, max(window, 1), 6), np.int32) if counts else None
-        status = np.zeros(m, np.int32)
-        nl = C.c_int(0)
         self._chk(self.L.hpgv_ld_text(self.h, text, len(text), max_lines, C.byref(nl), None, None, _ptr(status), window, _ptr(r2), _ptr(c6)))
-        k = min(nl.value, max_lines)
-        return dict(n_lines=nl.value, status=status[:k], r2=r2[:k], counts6=None if c6 is None else c6[:k])
+        return _text_result(nl, max_lines, status=status, r2=r2, counts6=c6)
 
     def assoc_view(self, task, gt2d, n_samples, is_x=None):
         """hpgv_assoc on a 2-D uint8 VIEW as it lies in memory (row stride = pitch): nothing is copied on the way,
@@ -871,101 +867,67 @@ class Engine:
 
     def tokenize(self, text, n_samples, strict=True, max_lines=None):
         """VCF data lines (bytes) -> dict(gt [n_lines, n_samples], is_x, status, line_off, field_off, n_lines)."""
-        if isinstance(text, str):
-            text = text.encode()
-        if max_lines is None:
-            max_lines = text.count(b"\n") + 1
+        text, max_lines, m, status, nl = _text_call(text, max_lines)
         pitch = max(n_samples, 1)
-        gt = np.zeros((max_lines, pitch), np.uint8)
-        is_x = np.zeros(max_lines, np.uint8)
-        status = np.zeros(max_lines, np.int32)
-        line_off = np.zeros(max_lines + 1, np.uint64)
-        field_off = np.zeros((max_lines, 10), np.uint32)
-        nl = C.c_int(0)
+        gt = np.zeros((m, pitch), np.uint8)
+        is_x = np.zeros(m, np.uint8)
+        line_off = np.zeros(m + 1, np.uint64)
+        field_off = np.zeros((m, 10), np.uint32)
         self._chk(self.L.hpgv_tokenize(self.h, text, len(text), n_samples, 1 if strict else 0, max_lines, C.byref(nl),
                                        _ptr(line_off), _ptr(field_off), _ptr(gt), pitch, _ptr(is_x), _ptr(status)))
-        k = min(nl.value, max_lines)
-        return dict(n_lines=nl.value, gt=gt[:k, :n_samples], is_x=is_x[:k], status=status[:k], line_off=line_off[:k + 1],
-                    field_off=field_off[:k])
+        res = _text_result(nl, max_lines, gt=gt[:, :n_samples], is_x=is_x, status=status, field_off=field_off)
+        res["line_off"] = line_off[:len(res["status"]) + 1]                  # the end of the last line too
+        return res
 
     def assoc_text(self, task, text, max_lines=None):
-        if isinstance(text, str):
-            text = text.encode()
-        if max_lines is None:
-            max_lines = text.count(b"\n") + 1
-        m = max(max_lines, 1)
+        text, max_lines, m, status, nl = _text_call(text, max_lines)
         A1, A2, U1, U2 = (np.zeros(m, np.int32) for _ in range(4))
-        odds, chisq, p = (np.zeros(m, np.float64) for _ in range(3))
-        status = np.zeros(m, np.int32)
-        nl = C.c_int(0)
+        odds, p = np.zeros(m, np.float64), np.zeros(m, np.float64)
+        chisq = np.zeros(m, np.float64) if task == TASK_CHISQ else None
         self._chk(self.L.hpgv_assoc_text(self.h, task, text, len(text), max_lines, C.byref(nl), None, None, _ptr(status),
-                                         _ptr(A1), _ptr(A2), _ptr(U1), _ptr(U2), _ptr(odds),
-                                         _ptr(chisq) if task == TASK_CHISQ else None, _ptr(p)))
-        k = min(nl.value, max_lines)
-        return dict(n_lines=nl.value, status=status[:k], A1=A1[:k], A2=A2[:k], U1=U1[:k], U2=U2[:k], odds=odds[:k],
-                    chisq=chisq[:k] if task == TASK_CHISQ else None, p=p[:k])
+                                         _ptr(A1), _ptr(A2), _ptr(U1), _ptr(U2), _ptr(odds), _ptr(chisq), _ptr(p)))
+        return _text_result(nl, max_lines, status=status, A1=A1, A2=A2, U1=U1, U2=U2, odds=odds, chisq=chisq, p=p)
 
     def assoc_select_text(self, task, text, p_max, max_lines=None, rows_cap=None, rows_pitch=None):
         """hpgv_assoc_select_text: assoc_text's dict plus sel (per line: its number among the selected lines or -1), n_sel, and
         rows (n_sel, n_samples): the selected lines' genotype rows in VCF column order -- None when n_sel exceeds rows_cap
         (default: room for every line)."""
-        if isinstance(text, str):
-            text = text.encode()
-        if max_lines is None:
-            max_lines = text.count(b"\n") + 1
-        m = max(max_lines, 1)
+        text, max_lines, m, status, nl = _text_call(text, max_lines)
         ns = getattr(self, "_n_samples", 0)     # (set_cohort; without one the call fails with ERR_STATE)
         if rows_cap is None:
             rows_cap = m
         if rows_pitch is None:
             rows_pitch = max(ns, 1)
         A1, A2, U1, U2 = (np.zeros(m, np.int32) for _ in range(4))
-        odds, chisq, p = (np.zeros(m, np.float64) for _ in range(3))
-        status, sel = np.zeros(m, np.int32), np.full(m, -2, np.int32)
+        odds, p = np.zeros(m, np.float64), np.zeros(m, np.float64)
+        chisq = np.zeros(m, np.float64) if task == TASK_CHISQ else None
+        sel = np.full(m, -2, np.int32)
         rows = np.full((max(rows_cap, 1), rows_pitch), 0xEE, np.uint8)
-        nl, nsel = C.c_int(0), C.c_int(0)
+        nsel = C.c_int(0)
         self._chk(self.L.hpgv_assoc_select_text(self.h, task, text, len(text), max_lines, C.byref(nl), None, None, _ptr(status),
-                                                _ptr(A1), _ptr(A2), _ptr(U1), _ptr(U2), _ptr(odds),
-                                                _ptr(chisq) if task == TASK_CHISQ else None, _ptr(p),
+                                                _ptr(A1), _ptr(A2), _ptr(U1), _ptr(U2), _ptr(odds), _ptr(chisq), _ptr(p),
                                                 float(p_max), _ptr(sel), _ptr(rows), rows_pitch, rows_cap, C.byref(nsel)))
-        k = min(nl.value, max_lines)
-        return dict(n_lines=nl.value, status=status[:k], A1=A1[:k], A2=A2[:k], U1=U1[:k], U2=U2[:k], odds=odds[:k],
-                    chisq=chisq[:k] if task == TASK_CHISQ else None, p=p[:k], sel=sel[:k], n_sel=nsel.value,
-                    rows=rows[:nsel.value, :ns] if nsel.value <= rows_cap else None, rows_block=rows)
+        return dict(_text_result(nl, max_lines, status=status, A1=A1, A2=A2, U1=U1, U2=U2, odds=odds, chisq=chisq, p=p, sel=sel),
+                    n_sel=nsel.value, rows=rows[:nsel.value, :ns] if nsel.value <= rows_cap else None, rows_block=rows)
 
     def tdt_text(self, text, max_lines=None):
-        if isinstance(text, str):
-            text = text.encode()
-        if max_lines is None:
-            max_lines = text.count(b"\n") + 1
-        m = max(max_lines, 1)
+        text, max_lines, m, status, nl = _text_call(text, max_lines)
         t1, t2 = np.zeros(m, np.int32), np.zeros(m, np.int32)
         odds, chisq, p = (np.zeros(m, np.float64) for _ in range(3))
-        status = np.zeros(m, np.int32)
-        nl = C.c_int(0)
         self._chk(self.L.hpgv_tdt_text(self.h, text, len(text), max_lines, C.byref(nl), None, None, _ptr(status),
                                        _ptr(t1), _ptr(t2), _ptr(odds), _ptr(chisq), _ptr(p)))
-        k = min(nl.value, max_lines)
-        return dict(n_lines=nl.value, status=status[:k], t1=t1[:k], t2=t2[:k], odds=odds[:k], chisq=chisq[:k], p=p[:k])
+        return _text_result(nl, max_lines, status=status, t1=t1, t2=t2, odds=odds, chisq=chisq, p=p)
 
     def tdt_perm_text(self, text, max_lines=None):
         """hpgv_tdt_perm_text: hpgv_tdt_text plus n_ge per line and batch_max per permutation."""
-        if isinstance(text, str):
-            text = text.encode()
-        if max_lines is None:
-            max_lines = text.count(b"\n") + 1
-        m = max(max_lines, 1)
+        text, max_lines, m, status, nl = _text_call(text, max_lines)
         t1, t2, n_ge = (np.zeros(m, np.int32) for _ in range(3))
         odds, chisq, p = (np.zeros(m, np.float64) for _ in range(3))
-        status = np.zeros(m, np.int32)
         np_ = getattr(self, "_n_flips", 0)
         bmax = np.zeros(max(np_, 1), np.float64)
-        nl = C.c_int(0)
         self._chk(self.L.hpgv_tdt_perm_text(self.h, text, len(text), max_lines, C.byref(nl), None, None, _ptr(status),
                                             _ptr(t1), _ptr(t2), _ptr(odds), _ptr(chisq), _ptr(p), _ptr(n_ge), _ptr(bmax)))
-        k = min(nl.value, max_lines)
-        return dict(n_lines=nl.value, status=status[:k], t1=t1[:k], t2=t2[:k], odds=odds[:k], chisq=chisq[:k], p=p[:k],
-                    n_ge=n_ge[:k], batch_max=bmax[:np_])
+        return dict(_text_result(nl, max_lines, status=status, t1=t1, t2=t2, odds=odds, chisq=chisq, p=p, n_ge=n_ge), batch_max=bmax[:np_])
 
     # ---- device-resident path (raw pointers; ints or c_void_p) ---------------
     def synth(self, which, v0, n_variants, d_dst, stream=None):

@@ -2,7 +2,10 @@
 // libhpgv.so: hpgv_capi.hip (contexts, options, cohorts, memory, streams, text aliases), hpgv_scan_capi.hip (the
 // device-resident *_dev launchers), hpgv_text_capi.hip (tokenizer, the text entry points' front half),
 // hpgv_tool_capi.hip (per-batch and text entry points), hpgv_lines_capi.hip (partition / multisplit of lines), and the
-// units whose kernel instantiations compile on their own (hpgv_perm_capi.hip, hpgv_epi_capi.hip, hpgv_epi_generic_capi.hip, hpgv_statsall_capi.hip, hpgv_inflate_capi.hip, hpgv_group_capi.hip).
+// units whose kernel instantiations compile on their own (hpgv_perm_capi.hip, hpgv_ld_capi.hip, hpgv_epi_capi.hip, hpgv_epi_generic_capi.hip, hpgv_statsall_capi.hip, hpgv_inflate_capi.hip, hpgv_group_capi.hip).
+// A synchronous entry point has two halves that meet in a Staged: the front puts the call's matrix on the device -- text_front /
+// text_front_skip for a text, stage_chain for a host batch that goes through the kernel chain -- and the tool's back half takes it
+// from there; the permutation calls build theirs from the halves of hpgv_assoc's and hpgv_tdt's (assoc_chain, ..., below).
 // The host side the epistasis units share is in hpgv_epi_host.h.
 #pragma once
 #include "../../include/hpgv.h"
@@ -104,8 +107,8 @@ struct Slot {
     DevBuf inherit;    // the inheritance filter's counts8 and verdict bytes
     DevBuf multi;      // multi-allelic rows: their indices, then their 256-bin tables
     DevBuf row_cnt;    // k_stats_all2's per-row counters between its two kernels
-    DevBuf perm;       // the permutation call's results: n_ge per row, the batch maxima per permutation, then the rows' skip bytes, then
-                       // (TDT flips) the slow families' i8 differences per row
+    DevBuf perm;       // the permutation call's results and scratch: perm_plan (hpgv_perm_capi.hip) is the one place that knows where its
+                       // parts lie.  (hpgv_ld_text has no permutation: its rows' skip bytes lie at the front)
     PinnedBuf res;     // result block of the one-pass kernels (they store into it), staging of k_assoc_rows' results
     // a buffer under two names holds two things that no call has at once:
     DevBuf &heads = text;      // a text that lies on the device already (hpgv_text_alias) is not uploaded: its head offsets and heads
@@ -131,8 +134,9 @@ struct TextMeta {
     uint32_t *field_off() const { return (uint32_t *)(base + 16 + (max_lines + 2) * sizeof(uint64_t)); }
 };
 
-// the genotype matrix of one synchronous call once it is on the device: what the per-tool back halves of
-// hpgv_tool_capi.hip read, whether a batch (batch_sources / stage_batch) or a text (text_front, hpgv_text_capi.hip) put it there
+// the genotype matrix of one synchronous call once it is on the device: what the back halves of hpgv_tool_capi.hip,
+// hpgv_perm_capi.hip and hpgv_ld_capi.hip read, whether a batch (batch_sources / stage_chain) or a text (text_front,
+// hpgv_text_capi.hip) put it there
 struct Staged {
     const uint8_t *d_raw = nullptr;   // VCF column order: the slot's `raw`, or the caller's rows where the device can read them
     size_t raw_pitch = 0;
@@ -374,7 +378,7 @@ struct DeviceGuard {
     ~DeviceGuard() { if (changed) (void)hipSetDevice(prev); }
 };
 
-[[maybe_unused]] size_t round_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+[[maybe_unused]] constexpr size_t round_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 // pitch of the VCF-order matrix the tokenizer writes for the *_text entry points
 [[maybe_unused]] size_t raw_pitch_of(int n_samples) { return n_samples > 0 ? round_up((size_t)n_samples, 16) : 16; }
 
@@ -465,6 +469,36 @@ long hpgv_batch_lds_optin(const hipDeviceProp_t &prop, long fallback);
 // tokenize, record filters, lay out
 int text_front(hpgv_ctx *ctx, Slot *s, int which, const Layout &L, const char *text, size_t text_bytes, int max_lines, int *n_lines,
                uint64_t *line_off, uint32_t *field_off, int32_t *status, Staged *S, bool final_layout = true);
+// defined in hpgv_tool_capi.hip: its twin for a host batch that goes through the kernel chain -- rows, then is_x, copied to the slot,
+// the rows laid out for `which`.  The one place that says how much of the caller's matrix a chain call reads:
+// (n_variants - 1) * pitch + n_samples bytes, the last row need not be a whole pitch.  n_variants may be 0
+int stage_chain(hpgv_ctx *ctx, Slot *s, int which, const Layout &L, const uint8_t *gt, size_t pitch, int n_variants, const uint8_t *is_x,
+                Staged *S);
+// what a text call whose kernels skip lines keeps on the host while it runs: the status of its own when the caller gave none, and
+// one byte per line.  Declared BEFORE the lease: copies queued into it end with the lease
+struct TextSkip {
+    std::vector<int32_t> own_status;
+    std::vector<uint8_t> skip;
+    const uint8_t *bytes() const { return skip.empty() ? nullptr : skip.data(); }
+};
+// defined in hpgv_text_capi.hip: text_front with the final layout, then the synchronise, then K->skip: 1 for the lines that
+// hpgv_assoc_text's callers drop -- not a record, or rejected by a record filter (max_lines > 0)
+int text_front_skip(hpgv_ctx *ctx, Slot *s, int which, const Layout &L, const char *text, size_t text_bytes, int max_lines, int *n_lines,
+                    uint64_t *line_off, uint32_t *field_off, int32_t *status, TextSkip *K, Staged *S);
+// defined in hpgv_tool_capi.hip: the laid-out path of hpgv_assoc and hpgv_tdt in two halves, so that the permutation calls
+// (hpgv_perm_capi.hip) queue their kernels between them.  *_chain: room in the slot (tally, dbl), scan, statistics (n = 0: room
+// only).  *_copy_out: the copies into the caller's arrays, queued -- the caller synchronises (n = 0: nothing)
+struct ChainOut {
+    int32_t *d_tally = nullptr;                                   // per row, assoc: {A1, A2, U1, U2}; tdt: {t1, t2}
+    double *d_odds = nullptr, *d_chisq = nullptr, *d_p = nullptr;
+};
+int assoc_chain(hpgv_ctx *ctx, Slot *s, int task, const Staged &S, ChainOut *C);
+int assoc_copy_out(hpgv_ctx *ctx, Slot *s, int task, const Staged &S, const ChainOut &C, int32_t *A1, int32_t *A2, int32_t *U1, int32_t *U2,
+                   double *odds, double *chisq, double *p);
+int tdt_chain(hpgv_ctx *ctx, Slot *s, const Staged &S, ChainOut *C);
+// (tu: the interleaved counts on the host; tdt_split_counts once the caller has synchronised)
+int tdt_copy_out(hpgv_ctx *ctx, Slot *s, const Staged &S, const ChainOut &C, std::vector<int32_t> *tu, double *odds, double *chisq, double *p);
+void tdt_split_counts(const std::vector<int32_t> &tu, int32_t *t1, int32_t *t2);
 // defined in hpgv_text_capi.hip: the back half of hpgv_assoc_select_text -- the candidate lines of a staged text (a record, not
 // filtered, p <= p_max; p_i at d_p + i * p_stride) numbered into sel, their raw rows compacted on the device and copied to rows_out
 int select_rows(hpgv_ctx *ctx, Slot *s, const Staged &S, int n_samples, const int32_t *status, const char *d_p, size_t p_stride, double p_max,

@@ -1,5 +1,6 @@
-// hpgv_ld_capi.hip -- C ABI of the LD band (include/hpgv.h "LD"): the device-resident launch of k_ld_window, the synchronous
-// entry points on a host batch and on a text, and the host-only r^2 of six counts.
+// hpgv_ld_capi.hip -- C ABI of the LD band (include/hpgv.h "LD"): the device-resident launches of k_ld_window and k_ld_edges
+// (one grid set-up, ld_grid, for both), the synchronous entry points on a host batch and on a text -- staged like every tool's,
+// by stage_chain and text_front_skip (hpgv_internal.h) -- and the host-only helpers: r^2 of six counts, clumping of an edge list.
 #include "hpgv_internal.h"
 #include "hpgv_ld_kernels.h"
 #include <algorithm>
@@ -15,23 +16,34 @@ int ld_window_check(const hpgv_ctx *ctx, int window) {
     return HPGV_OK;
 }
 
+// the grid both forms of the band share (k_ld_window "Grid"): the rows and the bounds of the band into A -- its outputs, r2 and
+// counts6, are the caller's to set --, the workgroups into *wgs
+int ld_grid(hpgv_ctx *ctx, const uint8_t *d_gt, size_t pitch, int n_variants, int b_begin, int window, const int32_t *d_chrom,
+            const uint32_t *d_pos, int64_t max_bp, const uint8_t *d_skip, hpgv::LdArgs *A, unsigned *wgs) {
+    A->gt = d_gt; A->pitch = pitch; A->chunks = (int)(pitch / 16); A->n_variants = n_variants; A->b_begin = b_begin; A->window = window;
+    A->passes = (63 + window) / 64 + 1;
+    A->tiles = (n_variants + hpgv::LD_VT - 1) / hpgv::LD_VT; A->tiles_per_range = (A->tiles + 7) / 8;
+    A->chrom = d_chrom; A->pos = d_pos; A->max_bp = max_bp; A->skip = d_skip;
+    const size_t n = (size_t)8 * (size_t)A->tiles_per_range * (size_t)A->passes;
+    if (n > 0x7FFFFFFFu) return fail(ctx, HPGV_ERR_UNSUPPORTED, "%d variants x window %d in one call: give the variants in several", n_variants, window);
+    *wgs = (unsigned)n;
+    return HPGV_OK;
+}
+
 // the launch: the pairs without an earlier row, then the band (the arguments checked, the device current)
 int ld_launch(hpgv_ctx *ctx, const uint8_t *d_gt, size_t pitch, int n_variants, int b_begin, int window, const int32_t *d_chrom,
               const uint32_t *d_pos, int64_t max_bp, const uint8_t *d_skip, double *d_r2, int32_t *d_counts6, hipStream_t st) {
     if (n_variants == b_begin) return HPGV_OK;
     hpgv::LdArgs A;
-    A.gt = d_gt; A.pitch = pitch; A.chunks = (int)(pitch / 16); A.n_variants = n_variants; A.b_begin = b_begin; A.window = window;
-    A.passes = (63 + window) / 64 + 1;
-    A.tiles = (n_variants + hpgv::LD_VT - 1) / hpgv::LD_VT; A.tiles_per_range = (A.tiles + 7) / 8;
-    A.chrom = d_chrom; A.pos = d_pos; A.max_bp = max_bp; A.skip = d_skip; A.r2 = d_r2; A.counts6 = d_counts6;
-    const size_t wgs = (size_t)8 * (size_t)A.tiles_per_range * (size_t)A.passes;
-    if (wgs > 0x7FFFFFFFu) return fail(ctx, HPGV_ERR_UNSUPPORTED, "%d variants x window %d in one call: give the variants in several", n_variants, window);
+    unsigned wgs;
+    if (const int rc = ld_grid(ctx, d_gt, pitch, n_variants, b_begin, window, d_chrom, d_pos, max_bp, d_skip, &A, &wgs)) return rc;
+    A.r2 = d_r2; A.counts6 = d_counts6;
     const int head_end = n_variants < window ? n_variants : window;           // later variants below `window` lack earlier rows
     const size_t head = head_end > b_begin ? (size_t)(head_end - b_begin) * (size_t)window : 0;
     // (option "profile": the two kernels' time is the statistics time of hpgv_last_kernel_ms)
     return launch_profiled(ctx, st, 1, [&] {
         if (head) hipLaunchKernelGGL(hpgv::k_ld_head, dim3((unsigned)((head + 255) / 256)), dim3(256), 0, st, b_begin, head_end, window, d_r2, d_counts6);
-        hipLaunchKernelGGL(hpgv::k_ld_window, dim3((unsigned)wgs), dim3(256), 0, st, A);
+        hipLaunchKernelGGL(hpgv::k_ld_window, dim3(wgs), dim3(256), 0, st, A);
     });
 }
 
@@ -45,15 +57,12 @@ int ld_edges_launch(hpgv_ctx *ctx, const uint8_t *d_gt, size_t pitch, int n_vari
     HIPCHK(ctx, hipMemsetAsync(d_n_edges, 0, sizeof(uint64_t), st));
     if (n_variants == b_begin) return HPGV_OK;
     hpgv::LdArgs A;
-    A.gt = d_gt; A.pitch = pitch; A.chunks = (int)(pitch / 16); A.n_variants = n_variants; A.b_begin = b_begin; A.window = window;
-    A.passes = (63 + window) / 64 + 1;
-    A.tiles = (n_variants + hpgv::LD_VT - 1) / hpgv::LD_VT; A.tiles_per_range = (A.tiles + 7) / 8;
-    A.chrom = d_chrom; A.pos = d_pos; A.max_bp = max_bp; A.skip = d_skip; A.r2 = nullptr; A.counts6 = nullptr;
+    unsigned wgs;
+    if (const int rc = ld_grid(ctx, d_gt, pitch, n_variants, b_begin, window, d_chrom, d_pos, max_bp, d_skip, &A, &wgs)) return rc;
+    A.r2 = nullptr; A.counts6 = nullptr;
     hpgv::LdEdgeOut E;
     E.min_r2 = min_r2; E.edges = reinterpret_cast<uint4 *>(d_edges); E.cap = edge_cap; E.n_edges = (unsigned long long *)d_n_edges;
-    const size_t wgs = (size_t)8 * (size_t)A.tiles_per_range * (size_t)A.passes;
-    if (wgs > 0x7FFFFFFFu) return fail(ctx, HPGV_ERR_UNSUPPORTED, "%d variants x window %d in one call: give the variants in several", n_variants, window);
-    return launch_profiled(ctx, st, 1, [&] { hipLaunchKernelGGL(hpgv::k_ld_edges, dim3((unsigned)wgs), dim3(256), 0, st, A, E); });
+    return launch_profiled(ctx, st, 1, [&] { hipLaunchKernelGGL(hpgv::k_ld_edges, dim3(wgs), dim3(256), 0, st, A, E); });
 }
 
 // the back half of hpgv_ld and hpgv_ld_text: the laid-out matrix of a staged call -> the band -> the caller's arrays.  skip, chrom
@@ -117,16 +126,8 @@ int hpgv_ld(hpgv_ctx *ctx, const uint8_t *gt, size_t pitch, int n_variants, int 
     if (pitch < (size_t)ctx->assoc.n_samples) return fail(ctx, HPGV_ERR_INVALID, "pitch %zu < n_samples %d", pitch, ctx->assoc.n_samples);
     if (n_variants == 0) return HPGV_OK;
     HPGV_LEASE_SLOT(ctx)
-    // the rows copied to the slot and laid out (the last row need not be a whole pitch)
-    const Layout &L = ctx->assoc;
-    const size_t bytes = (size_t)(n_variants - 1) * pitch + (size_t)L.n_samples;
-    HIPCHK(ctx, s->raw.reserve_slack(bytes + 16));
-    HIPCHK(ctx, s->laid.reserve_slack((size_t)n_variants * L.pitch + 16));
-    if (bytes) HIPCHK(ctx, hipMemcpyAsync(s->raw.p, gt, bytes, hipMemcpyHostToDevice, s->stream));
-    if ((rc = hpgv_layout_dev(ctx, HPGV_LAYOUT_ASSOC, s->raw.as<uint8_t>(), pitch, n_variants, s->laid.as<uint8_t>(), s->stream))) return rc;
     Staged S;
-    S.d_raw = s->raw.as<uint8_t>(); S.raw_pitch = pitch; S.d_laid = s->laid.as<uint8_t>(); S.which = HPGV_LAYOUT_ASSOC;
-    S.n = n_variants; S.out_stride = (size_t)n_variants;
+    if ((rc = stage_chain(ctx, s, HPGV_LAYOUT_ASSOC, ctx->assoc, gt, pitch, n_variants, nullptr, &S))) return rc;
     return ld_finish(ctx, s, S, window, nullptr, chrom, pos, max_bp, r2, counts6);
     HPGV_ABI_CATCH(ctx)
 }
@@ -163,16 +164,13 @@ int hpgv_ld_edges(hpgv_ctx *ctx, const uint8_t *gt, size_t pitch, int n_variants
     *n_edges = 0;
     if (n_variants == 0) return HPGV_OK;
     HPGV_LEASE_SLOT(ctx)
-    const Layout &L = ctx->assoc;
-    const size_t n = (size_t)n_variants, bytes = (n - 1) * pitch + (size_t)L.n_samples, off_pos = round_up(n * sizeof(int32_t), 16);
+    Staged S;
+    if ((rc = stage_chain(ctx, s, HPGV_LAYOUT_ASSOC, ctx->assoc, gt, pitch, n_variants, nullptr, &S))) return rc;
+    const size_t n = (size_t)n_variants, off_pos = round_up(n * sizeof(int32_t), 16);
     // no more pairs than the band holds can qualify: the device list need not be longer
     const uint64_t band = (uint64_t)n * (uint64_t)window, cap = edge_cap < band ? edge_cap : band;
-    HIPCHK(ctx, s->raw.reserve_slack(bytes + 16));
-    HIPCHK(ctx, s->laid.reserve_slack(n * L.pitch + 16));
     HIPCHK(ctx, s->dbl.reserve_slack(16 + (size_t)cap * sizeof(hpgv_ld_edge)));           // the counter, then the list
     if (chrom) HIPCHK(ctx, s->ints.reserve_slack(off_pos + n * sizeof(uint32_t) + 16));
-    HIPCHK(ctx, hipMemcpyAsync(s->raw.p, gt, bytes, hipMemcpyHostToDevice, s->stream));
-    if ((rc = hpgv_layout_dev(ctx, HPGV_LAYOUT_ASSOC, s->raw.as<uint8_t>(), pitch, n_variants, s->laid.as<uint8_t>(), s->stream))) return rc;
     int32_t *d_chrom = chrom ? s->ints.as<int32_t>() : nullptr;
     uint32_t *d_pos = chrom ? (uint32_t *)(s->ints.as<char>() + off_pos) : nullptr;
     if (chrom) {
@@ -181,7 +179,7 @@ int hpgv_ld_edges(hpgv_ctx *ctx, const uint8_t *gt, size_t pitch, int n_variants
     }
     uint64_t *d_count = s->dbl.as<uint64_t>();
     hpgv_ld_edge *d_edges = cap ? (hpgv_ld_edge *)(s->dbl.as<char>() + 16) : nullptr;
-    if ((rc = ld_edges_launch(ctx, s->laid.as<uint8_t>(), L.pitch, n_variants, 0, window, d_chrom, d_pos, max_bp, nullptr, min_r2, d_edges, cap,
+    if ((rc = ld_edges_launch(ctx, S.d_laid, ctx->assoc.pitch, n_variants, 0, window, d_chrom, d_pos, max_bp, nullptr, min_r2, d_edges, cap,
                               d_count, s->stream))) return rc;
     uint64_t count = 0;
     HIPCHK(ctx, hipMemcpyAsync(&count, d_count, sizeof count, hipMemcpyDeviceToHost, s->stream));
@@ -205,18 +203,12 @@ int hpgv_ld_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, int max_lin
     if (!n_lines || max_lines < 0 || (text_bytes > 0 && !text) || (max_lines > 0 && !r2)) return fail(ctx, HPGV_ERR_INVALID, "bad ld_text arguments");
     *n_lines = 0;
     if (max_lines == 0) return HPGV_OK;
-    std::vector<int32_t> own_status;             // (before the lease: queued copies into them end with the lease)
-    std::vector<uint8_t> skip;
+    TextSkip K;                                  // (before the lease)
     HPGV_LEASE_SLOT(ctx)
     Staged S;
-    if (!status) { own_status.assign((size_t)max_lines, 0); status = own_status.data(); }
-    if ((rc = text_front(ctx, s, HPGV_LAYOUT_ASSOC, ctx->assoc, text, text_bytes, max_lines, n_lines, line_off, field_off, status, &S, true))) return rc;
-    // the lines hpgv_assoc_text's callers drop keep their slot in the window as skipped rows: not a record (status 1), or
-    // rejected by a record filter
-    HIPCHK(ctx, hipStreamSynchronize(s->stream));
-    skip.resize((size_t)S.n);
-    for (int i = 0; i < S.n; ++i) skip[(size_t)i] = ((status[i] & 0xFF) == 1 || (status[i] & HPGV_LINE_FILTERED)) ? 1 : 0;
-    return ld_finish(ctx, s, S, window, S.n > 0 ? skip.data() : nullptr, nullptr, nullptr, -1, r2, counts6);
+    // the lines hpgv_assoc_text's callers drop keep their slot in the window as skipped rows
+    if ((rc = text_front_skip(ctx, s, HPGV_LAYOUT_ASSOC, ctx->assoc, text, text_bytes, max_lines, n_lines, line_off, field_off, status, &K, &S))) return rc;
+    return ld_finish(ctx, s, S, window, K.bytes(), nullptr, nullptr, -1, r2, counts6);
     HPGV_ABI_CATCH(ctx)
 }
 

@@ -2,7 +2,11 @@
 // of the association test and the flip rows of the TDT of a context, the device-resident launches of k_assoc_perm and
 // k_tdt_perm, the synchronous entry points on a host batch and on a text, and the host-only helpers (label shuffle, flip
 // generator, empirical p-values).  The genotypic model tests (include/hpgv.h "model tests") live here too: their class scan and
-// statistics kernels, and the trend form of k_assoc_perm behind the same launcher and staging as the allelic one.
+// statistics kernels, and the trend form of k_assoc_perm behind the same launcher as the allelic one.
+// A synchronous entry point checks its arguments, leases a slot and stages like every tool's (stage_chain for a batch,
+// text_front_skip for a text: hpgv_internal.h); its back half is the tool's own chain with the permutation launch between the
+// chain's two halves (assoc_chain / assoc_copy_out, tdt_chain / tdt_copy_out: hpgv_tool_capi.hip) -- the model tests alone keep a
+// chain of their own -- and perm_plan lays out the call's scratch in Slot::perm.
 #include "hpgv_internal.h"
 #include "hpgv_assoc_model_kernels.h"
 #include "hpgv_assoc_perm_kernels.h"
@@ -67,6 +71,42 @@ int model_stats_launch(hpgv_ctx *ctx, const int32_t *d_counts8, int n_variants, 
     });
 }
 
+// where the parts of Slot::perm lie in a call over n rows and n_perms permutations: n_ge per row at 0, the batch maxima per
+// permutation at round_up(4 n, 16), the rows' skip bytes behind them, then -- TDT flips: tail_pitch bytes per row -- the slow
+// families' i8 differences from the next multiple of 16 on
+struct PermPlan {
+    int32_t *d_n_ge = nullptr;
+    double *d_max = nullptr;
+    uint8_t *d_skip = nullptr;         // null when every row takes part
+    int8_t *d_tail = nullptr;
+};
+struct PermOffsets { size_t max, skip, tail; };
+constexpr PermOffsets perm_offsets(size_t n, size_t n_perms) {
+    const size_t off_max = round_up(n * sizeof(int32_t), 16), off_skip = off_max + n_perms * sizeof(double);
+    return {off_max, off_skip, round_up(off_skip + n, 16)};
+}
+// the synchronous calls launch without the *_dev wrappers' alignment refusals: the kernels' 64-bit atomics on the maxima need 8
+// bytes, their 16-byte loads of the tail 16, at any row count -- odd ones above all
+constexpr bool perm_offsets_aligned(size_t n, size_t n_perms) {
+    return perm_offsets(n, n_perms).max % 16 == 0 && perm_offsets(n, n_perms).tail % 16 == 0 && perm_offsets(n, n_perms).skip >= perm_offsets(n, n_perms).max &&
+           perm_offsets(n, n_perms).max >= n * sizeof(int32_t);
+}
+static_assert(perm_offsets_aligned(0, 1) && perm_offsets_aligned(1, 1) && perm_offsets_aligned(3, 130) && perm_offsets_aligned(70, 130) &&
+              perm_offsets_aligned(71, 129) && perm_offsets_aligned(65, 17), "the plan of Slot::perm keeps the maxima and the tail aligned");
+
+// room in the slot, the four parts placed, and the skip bytes (host, may be null) on their way to theirs
+int perm_plan(hpgv_ctx *ctx, Slot *s, size_t n, size_t n_perms, const uint8_t *skip, size_t tail_pitch, PermPlan *P) {
+    const PermOffsets off = perm_offsets(n, n_perms);
+    HIPCHK(ctx, s->perm.reserve_slack(off.tail + n * tail_pitch + 16));
+    char *base = s->perm.as<char>();
+    P->d_n_ge = (int32_t *)base; P->d_max = (double *)(base + off.max); P->d_tail = (int8_t *)(base + off.tail);
+    if (skip && n > 0) {
+        P->d_skip = (uint8_t *)(base + off.skip);
+        HIPCHK(ctx, hipMemcpyAsync(P->d_skip, skip, n, hipMemcpyHostToDevice, s->stream));
+    }
+    return HPGV_OK;
+}
+
 // the back half of hpgv_assoc_model and hpgv_assoc_model_text: the laid-out matrix of a staged call -> class scan, the five
 // statistics, with `perm` the trend form of the permutation kernel -> the caller's arrays.  skip (host, may be null): rows
 // that take no part in the permutation
@@ -75,103 +115,45 @@ int model_finish(hpgv_ctx *ctx, Slot *s, const Staged &S, bool perm, const uint8
     int rc;
     const int nv = S.n;
     const size_t n = (size_t)nv, np = perm ? (size_t)ctx->n_perms : 0;
-    const size_t off_max = round_up(n * sizeof(int32_t), 16), off_skip = off_max + np * sizeof(double);
     HIPCHK(ctx, s->tally.reserve_slack(n * 32 + 16));
     HIPCHK(ctx, s->dbl.reserve_slack(n * 10 * sizeof(double) + 16));
-    if (perm) HIPCHK(ctx, s->perm.reserve_slack(off_skip + n + 16));
+    PermPlan P;
+    if (perm && (rc = perm_plan(ctx, s, n, np, skip, 0, &P))) return rc;
     int32_t *d_counts8 = s->tally.as<int32_t>();
     double *d_chisq5 = s->dbl.as<double>(), *d_p5 = d_chisq5 + 5 * n;
-    int32_t *d_n_ge = perm ? s->perm.as<int32_t>() : nullptr;
-    double *d_max = perm ? (double *)(s->perm.as<char>() + off_max) : nullptr;
-    uint8_t *d_skip = nullptr;
-    if (perm && skip && nv > 0) {
-        d_skip = s->perm.as<uint8_t>() + off_skip;
-        HIPCHK(ctx, hipMemcpyAsync(d_skip, skip, n, hipMemcpyHostToDevice, s->stream));
-    }
     if (nv > 0) {
         if ((rc = model_scan_launch(ctx, S.d_laid, nv, d_counts8, s->stream))) return rc;
         if ((rc = model_stats_launch(ctx, d_counts8, nv, d_chisq5, d_p5, s->stream))) return rc;
     }
-    if (perm && (rc = perm_launch(ctx, hpgv::PERM_TREND, S.d_laid, nv, nullptr, d_counts8, d_skip, d_n_ge, d_max, nullptr, s->stream))) return rc;
+    if (perm && (rc = perm_launch(ctx, hpgv::PERM_TREND, S.d_laid, nv, nullptr, d_counts8, P.d_skip, P.d_n_ge, P.d_max, nullptr, s->stream))) return rc;
     if (nv > 0) {
         HIPCHK(ctx, hipMemcpyAsync(counts8, d_counts8, n * 32, hipMemcpyDeviceToHost, s->stream));
         HIPCHK(ctx, hipMemcpyAsync(chisq5, d_chisq5, n * 40, hipMemcpyDeviceToHost, s->stream));
         HIPCHK(ctx, hipMemcpyAsync(p5, d_p5, n * 40, hipMemcpyDeviceToHost, s->stream));
-        if (perm) HIPCHK(ctx, hipMemcpyAsync(n_ge, d_n_ge, n * 4, hipMemcpyDeviceToHost, s->stream));
+        if (perm) HIPCHK(ctx, hipMemcpyAsync(n_ge, P.d_n_ge, n * 4, hipMemcpyDeviceToHost, s->stream));
     }
-    if (perm) HIPCHK(ctx, hipMemcpyAsync(batch_max, d_max, np * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    if (perm) HIPCHK(ctx, hipMemcpyAsync(batch_max, P.d_max, np * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     HIPCHK(ctx, hipStreamSynchronize(s->stream));
     return HPGV_OK;
 }
 
-// the back half of the two synchronous entry points: the laid-out matrix of a staged call -> scan, chi-square, permutation
-// kernel -> the caller's arrays.  skip (host, may be null): rows that take no part
+// the back half of hpgv_assoc_perm and hpgv_assoc_perm_text: hpgv_assoc's kernel chain (task CHISQ) with the permutation kernel
+// between its two halves.  On the slot's stream, in this order: the skip bytes (host, may be null: rows that take no part), scan,
+// chi-square, the two memsets and k_assoc_perm, k_counts_to_soa, the copies out, one synchronise
 int perm_finish(hpgv_ctx *ctx, Slot *s, const Staged &S, const uint8_t *skip, int32_t *A1, int32_t *A2, int32_t *U1, int32_t *U2,
                 double *odds, double *chisq, double *p, int32_t *n_ge, double *batch_max) {
     int rc;
-    const int nv = S.n;
-    const size_t n = (size_t)nv, np = (size_t)ctx->n_perms;
-    const size_t off_max = round_up(n * sizeof(int32_t), 16), off_skip = off_max + np * sizeof(double);
-    HIPCHK(ctx, s->tally.reserve_slack(n * 16 + 16));
-    HIPCHK(ctx, s->dbl.reserve_slack(n * 3 * sizeof(double) + 16));
-    HIPCHK(ctx, s->ints.reserve_slack(n * 4 * sizeof(int32_t) + 16));
-    HIPCHK(ctx, s->perm.reserve_slack(off_skip + n + 16));
-    int32_t *d_counts = s->tally.as<int32_t>(), *d_soa = s->ints.as<int32_t>();
-    double *d_odds = s->dbl.as<double>(), *d_chisq = d_odds + n, *d_p = d_odds + 2 * n;
-    int32_t *d_n_ge = s->perm.as<int32_t>();
-    double *d_max = (double *)(s->perm.as<char>() + off_max);
-    uint8_t *d_skip = nullptr;
-    if (skip && nv > 0) {
-        d_skip = s->perm.as<uint8_t>() + off_skip;
-        HIPCHK(ctx, hipMemcpyAsync(d_skip, skip, n, hipMemcpyHostToDevice, s->stream));
-    }
-    if (nv > 0) {
-        if ((rc = hpgv_assoc_scan_dev(ctx, S.d_laid, nv, S.d_isx, d_counts, s->stream))) return rc;
-        if ((rc = hpgv_assoc_chisq_dev(ctx, d_counts, nv, d_odds, d_chisq, d_p, s->stream))) return rc;
-    }
-    if ((rc = perm_launch(ctx, hpgv::PERM_ALLELIC, S.d_laid, nv, S.d_isx, d_counts, d_skip, d_n_ge, d_max, nullptr, s->stream))) return rc;
-    if (nv > 0) {
-        hipLaunchKernelGGL(hpgv::k_counts_to_soa, dim3((nv + 255) / 256), dim3(256), 0, s->stream,
-                           (const int4 *)d_counts, nv, d_soa, d_soa + n, d_soa + 2 * n, d_soa + 3 * n);
-        HIPCHK(ctx, hipGetLastError());
-        HIPCHK(ctx, hipMemcpyAsync(A1, d_soa, n * 4, hipMemcpyDeviceToHost, s->stream));
-        HIPCHK(ctx, hipMemcpyAsync(A2, d_soa + n, n * 4, hipMemcpyDeviceToHost, s->stream));
-        HIPCHK(ctx, hipMemcpyAsync(U1, d_soa + 2 * n, n * 4, hipMemcpyDeviceToHost, s->stream));
-        HIPCHK(ctx, hipMemcpyAsync(U2, d_soa + 3 * n, n * 4, hipMemcpyDeviceToHost, s->stream));
-        HIPCHK(ctx, hipMemcpyAsync(odds, d_odds, n * 8, hipMemcpyDeviceToHost, s->stream));
-        HIPCHK(ctx, hipMemcpyAsync(chisq, d_chisq, n * 8, hipMemcpyDeviceToHost, s->stream));
-        HIPCHK(ctx, hipMemcpyAsync(p, d_p, n * 8, hipMemcpyDeviceToHost, s->stream));
-        HIPCHK(ctx, hipMemcpyAsync(n_ge, d_n_ge, n * 4, hipMemcpyDeviceToHost, s->stream));
-    }
-    HIPCHK(ctx, hipMemcpyAsync(batch_max, d_max, np * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    const size_t n = (size_t)S.n, np = (size_t)ctx->n_perms;
+    PermPlan P;
+    ChainOut C;
+    if ((rc = perm_plan(ctx, s, n, np, skip, 0, &P))) return rc;
+    if ((rc = assoc_chain(ctx, s, HPGV_TASK_CHISQ, S, &C))) return rc;
+    if ((rc = perm_launch(ctx, hpgv::PERM_ALLELIC, S.d_laid, S.n, S.d_isx, C.d_tally, P.d_skip, P.d_n_ge, P.d_max, nullptr, s->stream))) return rc;
+    if ((rc = assoc_copy_out(ctx, s, HPGV_TASK_CHISQ, S, C, A1, A2, U1, U2, odds, chisq, p))) return rc;
+    if (n) HIPCHK(ctx, hipMemcpyAsync(n_ge, P.d_n_ge, n * 4, hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(ctx, hipMemcpyAsync(batch_max, P.d_max, np * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     HIPCHK(ctx, hipStreamSynchronize(s->stream));
     return HPGV_OK;
-}
-
-// the front half of the two synchronous batch entry points: the rows and is_x copied to the slot and laid out for `which`
-// (the last row need not be a whole pitch)
-int perm_stage(hpgv_ctx *ctx, Slot *s, int which, const Layout &L, const uint8_t *gt, size_t pitch, int n_variants, const uint8_t *is_x, Staged *S) {
-    if (n_variants > 0) {
-        const size_t bytes = (size_t)(n_variants - 1) * pitch + (size_t)L.n_samples;
-        HIPCHK(ctx, s->raw.reserve_slack(bytes + 16));
-        HIPCHK(ctx, s->laid.reserve_slack((size_t)n_variants * L.pitch + 16));
-        if (bytes) HIPCHK(ctx, hipMemcpyAsync(s->raw.p, gt, bytes, hipMemcpyHostToDevice, s->stream));
-        if (is_x) {
-            HIPCHK(ctx, s->isx.reserve_slack((size_t)n_variants));
-            HIPCHK(ctx, hipMemcpyAsync(s->isx.p, is_x, (size_t)n_variants, hipMemcpyHostToDevice, s->stream));
-            S->d_isx = s->isx.as<uint8_t>();
-        }
-        S->d_raw = s->raw.as<uint8_t>(); S->raw_pitch = pitch; S->d_laid = s->laid.as<uint8_t>(); S->which = which;
-        if (const int rc = hpgv_layout_dev(ctx, which, S->d_raw, pitch, n_variants, s->laid.as<uint8_t>(), s->stream)) return rc;
-    }
-    S->n = n_variants; S->out_stride = (size_t)n_variants;
-    return HPGV_OK;
-}
-
-// the lines a caller of the plain *_text entry points drops: not a record (status 1), or rejected by a record filter
-void perm_skip_lines(const int32_t *status, int n, std::vector<uint8_t> &skip) {
-    skip.resize((size_t)n);
-    for (int i = 0; i < n; ++i) skip[(size_t)i] = ((status[i] & 0xFF) == 1 || (status[i] & HPGV_LINE_FILTERED)) ? 1 : 0;
 }
 
 /* ---- TDT, family flips ------------------------------------------------------------------------------------------- */
@@ -215,42 +197,24 @@ int flip_launch(hpgv_ctx *ctx, const uint8_t *d_gt, int n_variants, const uint8_
     });
 }
 
-// the back half of the two synchronous entry points: the laid-out matrix of a staged call -> scan, statistics, the two
-// permutation kernels -> the caller's arrays.  skip (host, may be null): rows that take no part
+// the back half of hpgv_tdt_perm and hpgv_tdt_perm_text: hpgv_tdt's kernel chain with the permutation kernels between its two
+// halves.  On the slot's stream, in this order: the skip bytes (host, may be null: rows that take no part), scan, statistics, the
+// two memsets, k_tdt_perm_slow and k_tdt_perm, the copies out, one synchronise
 int flip_finish(hpgv_ctx *ctx, Slot *s, const Staged &S, const uint8_t *skip, int32_t *t1, int32_t *t2, double *odds, double *chisq, double *p,
                 int32_t *n_ge, double *batch_max) {
     int rc;
-    const int nv = S.n;
-    const size_t n = (size_t)nv, np = (size_t)ctx->n_flips, tail = (size_t)flip_tail_pitch(ctx);
-    const size_t off_max = round_up(n * sizeof(int32_t), 16), off_skip = off_max + np * sizeof(double), off_tail = round_up(off_skip + n, 16);
-    HIPCHK(ctx, s->tally.reserve_slack(n * 8 + 16));
-    HIPCHK(ctx, s->dbl.reserve_slack(n * 3 * sizeof(double) + 16));
-    HIPCHK(ctx, s->perm.reserve_slack(off_tail + n * tail + 16));
-    int32_t *d_tu = s->tally.as<int32_t>();
-    double *d_odds = s->dbl.as<double>(), *d_chisq = d_odds + n, *d_p = d_odds + 2 * n;
-    int32_t *d_n_ge = s->perm.as<int32_t>();
-    double *d_max = (double *)(s->perm.as<char>() + off_max);
-    uint8_t *d_skip = nullptr;
-    if (skip && nv > 0) {
-        d_skip = s->perm.as<uint8_t>() + off_skip;
-        HIPCHK(ctx, hipMemcpyAsync(d_skip, skip, n, hipMemcpyHostToDevice, s->stream));
-    }
-    if (nv > 0) {
-        if ((rc = hpgv_tdt_scan_dev(ctx, S.d_laid, nv, S.d_isx, d_tu, s->stream))) return rc;
-        if ((rc = hpgv_tdt_stats_dev(ctx, d_tu, nv, d_odds, d_chisq, d_p, s->stream))) return rc;
-    }
-    if ((rc = flip_launch(ctx, S.d_laid, nv, S.d_isx, d_tu, d_skip, (int8_t *)(s->perm.as<char>() + off_tail), d_n_ge, d_max, nullptr, s->stream))) return rc;
-    std::vector<int32_t> tu(2 * n);
-    if (nv > 0) {
-        HIPCHK(ctx, hipMemcpyAsync(tu.data(), d_tu, n * 8, hipMemcpyDeviceToHost, s->stream));
-        HIPCHK(ctx, hipMemcpyAsync(odds, d_odds, n * 8, hipMemcpyDeviceToHost, s->stream));
-        HIPCHK(ctx, hipMemcpyAsync(chisq, d_chisq, n * 8, hipMemcpyDeviceToHost, s->stream));
-        HIPCHK(ctx, hipMemcpyAsync(p, d_p, n * 8, hipMemcpyDeviceToHost, s->stream));
-        HIPCHK(ctx, hipMemcpyAsync(n_ge, d_n_ge, n * 4, hipMemcpyDeviceToHost, s->stream));
-    }
-    HIPCHK(ctx, hipMemcpyAsync(batch_max, d_max, np * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    const size_t n = (size_t)S.n, np = (size_t)ctx->n_flips;
+    PermPlan P;
+    ChainOut C;
+    std::vector<int32_t> tu;
+    if ((rc = perm_plan(ctx, s, n, np, skip, (size_t)flip_tail_pitch(ctx), &P))) return rc;
+    if ((rc = tdt_chain(ctx, s, S, &C))) return rc;
+    if ((rc = flip_launch(ctx, S.d_laid, S.n, S.d_isx, C.d_tally, P.d_skip, P.d_tail, P.d_n_ge, P.d_max, nullptr, s->stream))) return rc;
+    if ((rc = tdt_copy_out(ctx, s, S, C, &tu, odds, chisq, p))) return rc;
+    if (n) HIPCHK(ctx, hipMemcpyAsync(n_ge, P.d_n_ge, n * 4, hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(ctx, hipMemcpyAsync(batch_max, P.d_max, np * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     HIPCHK(ctx, hipStreamSynchronize(s->stream));
-    for (size_t i = 0; i < n; ++i) { t1[i] = tu[2 * i]; t2[i] = tu[2 * i + 1]; }
+    tdt_split_counts(tu, t1, t2);
     return HPGV_OK;
 }
 
@@ -362,7 +326,7 @@ int hpgv_assoc_model(hpgv_ctx *ctx, const uint8_t *gt, size_t pitch, int n_varia
     if (n_variants == 0 && !perm) return HPGV_OK;
     HPGV_LEASE_SLOT(ctx)
     Staged S;
-    if ((rc = perm_stage(ctx, s, HPGV_LAYOUT_ASSOC, ctx->assoc, gt, pitch, n_variants, nullptr, &S))) return rc;
+    if ((rc = stage_chain(ctx, s, HPGV_LAYOUT_ASSOC, ctx->assoc, gt, pitch, n_variants, nullptr, &S))) return rc;
     return model_finish(ctx, s, S, perm, nullptr, counts8, chisq5, p5, n_ge, batch_max);
     HPGV_ABI_CATCH(ctx)
 }
@@ -381,20 +345,16 @@ int hpgv_assoc_model_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, in
         return fail(ctx, HPGV_ERR_INVALID, "bad assoc_model_text arguments");
     *n_lines = 0;
     if (max_lines == 0 && !perm) return HPGV_OK;
-    std::vector<int32_t> own_status;             // (before the lease: queued copies into them end with the lease)
-    std::vector<uint8_t> skip;
+    TextSkip K;                                  // (before the lease)
     HPGV_LEASE_SLOT(ctx)
     Staged S;
     if (max_lines > 0) {
-        if (!status && perm) { own_status.assign((size_t)max_lines, 0); status = own_status.data(); }
-        if ((rc = text_front(ctx, s, HPGV_LAYOUT_ASSOC, ctx->assoc, text, text_bytes, max_lines, n_lines, line_off, field_off, status, &S, true))) return rc;
-        if (perm) {
-            // the lines hpgv_assoc_text's callers drop take no part, as in hpgv_assoc_perm_text
-            HIPCHK(ctx, hipStreamSynchronize(s->stream));
-            perm_skip_lines(status, S.n, skip);
-        }
+        // the lines hpgv_assoc_text's callers drop take no part in the permutation, as in hpgv_assoc_perm_text
+        rc = perm ? text_front_skip(ctx, s, HPGV_LAYOUT_ASSOC, ctx->assoc, text, text_bytes, max_lines, n_lines, line_off, field_off, status, &K, &S)
+                  : text_front(ctx, s, HPGV_LAYOUT_ASSOC, ctx->assoc, text, text_bytes, max_lines, n_lines, line_off, field_off, status, &S);
+        if (rc) return rc;
     }
-    return model_finish(ctx, s, S, perm, skip.empty() ? nullptr : skip.data(), counts8, chisq5, p5, n_ge, batch_max);
+    return model_finish(ctx, s, S, perm, K.bytes(), counts8, chisq5, p5, n_ge, batch_max);
     HPGV_ABI_CATCH(ctx)
 }
 
@@ -410,7 +370,7 @@ int hpgv_assoc_perm(hpgv_ctx *ctx, const uint8_t *gt, size_t pitch, int n_varian
     if (pitch < (size_t)ctx->assoc.n_samples) return fail(ctx, HPGV_ERR_INVALID, "pitch %zu < n_samples %d", pitch, ctx->assoc.n_samples);
     HPGV_LEASE_SLOT(ctx)
     Staged S;
-    if ((rc = perm_stage(ctx, s, HPGV_LAYOUT_ASSOC, ctx->assoc, gt, pitch, n_variants, is_x, &S))) return rc;
+    if ((rc = stage_chain(ctx, s, HPGV_LAYOUT_ASSOC, ctx->assoc, gt, pitch, n_variants, is_x, &S))) return rc;
     return perm_finish(ctx, s, S, nullptr, A1, A2, U1, U2, odds, chisq, p, n_ge, batch_max);
     HPGV_ABI_CATCH(ctx)
 }
@@ -426,18 +386,11 @@ int hpgv_assoc_perm_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, int
         (max_lines > 0 && (!A1 || !A2 || !U1 || !U2 || !odds || !chisq || !p || !n_ge)))
         return fail(ctx, HPGV_ERR_INVALID, "bad assoc_perm_text arguments");
     *n_lines = 0;
-    std::vector<int32_t> own_status;             // (before the lease: queued copies into them end with the lease)
-    std::vector<uint8_t> skip;
+    TextSkip K;                                  // (before the lease)
     HPGV_LEASE_SLOT(ctx)
     Staged S;
-    if (max_lines > 0) {
-        if (!status) { own_status.assign((size_t)max_lines, 0); status = own_status.data(); }
-        if ((rc = text_front(ctx, s, HPGV_LAYOUT_ASSOC, ctx->assoc, text, text_bytes, max_lines, n_lines, line_off, field_off, status, &S, true))) return rc;
-        // the lines hpgv_assoc_text's callers drop: not a record (status 1), or rejected by a record filter
-        HIPCHK(ctx, hipStreamSynchronize(s->stream));
-        perm_skip_lines(status, S.n, skip);
-    }
-    return perm_finish(ctx, s, S, skip.empty() ? nullptr : skip.data(), A1, A2, U1, U2, odds, chisq, p, n_ge, batch_max);
+    if (max_lines > 0 && (rc = text_front_skip(ctx, s, HPGV_LAYOUT_ASSOC, ctx->assoc, text, text_bytes, max_lines, n_lines, line_off, field_off, status, &K, &S))) return rc;
+    return perm_finish(ctx, s, S, K.bytes(), A1, A2, U1, U2, odds, chisq, p, n_ge, batch_max);
     HPGV_ABI_CATCH(ctx)
 }
 
@@ -510,7 +463,7 @@ int hpgv_tdt_perm(hpgv_ctx *ctx, const uint8_t *gt, size_t pitch, int n_variants
     if (pitch < (size_t)ctx->tdt.n_samples) return fail(ctx, HPGV_ERR_INVALID, "pitch %zu < n_samples %d", pitch, ctx->tdt.n_samples);
     HPGV_LEASE_SLOT(ctx)
     Staged S;
-    if ((rc = perm_stage(ctx, s, HPGV_LAYOUT_TDT, ctx->tdt, gt, pitch, n_variants, is_x, &S))) return rc;
+    if ((rc = stage_chain(ctx, s, HPGV_LAYOUT_TDT, ctx->tdt, gt, pitch, n_variants, is_x, &S))) return rc;
     return flip_finish(ctx, s, S, nullptr, t1, t2, odds, chisq, p, n_ge, batch_max);
     HPGV_ABI_CATCH(ctx)
 }
@@ -525,17 +478,11 @@ int hpgv_tdt_perm_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, int m
     if (!n_lines || !batch_max || max_lines < 0 || (text_bytes > 0 && !text) || (max_lines > 0 && (!t1 || !t2 || !odds || !chisq || !p || !n_ge)))
         return fail(ctx, HPGV_ERR_INVALID, "bad tdt_perm_text arguments");
     *n_lines = 0;
-    std::vector<int32_t> own_status;             // (before the lease: queued copies into them end with the lease)
-    std::vector<uint8_t> skip;
+    TextSkip K;                                  // (before the lease)
     HPGV_LEASE_SLOT(ctx)
     Staged S;
-    if (max_lines > 0) {
-        if (!status) { own_status.assign((size_t)max_lines, 0); status = own_status.data(); }
-        if ((rc = text_front(ctx, s, HPGV_LAYOUT_TDT, ctx->tdt, text, text_bytes, max_lines, n_lines, line_off, field_off, status, &S, true))) return rc;
-        HIPCHK(ctx, hipStreamSynchronize(s->stream));
-        perm_skip_lines(status, S.n, skip);
-    }
-    return flip_finish(ctx, s, S, skip.empty() ? nullptr : skip.data(), t1, t2, odds, chisq, p, n_ge, batch_max);
+    if (max_lines > 0 && (rc = text_front_skip(ctx, s, HPGV_LAYOUT_TDT, ctx->tdt, text, text_bytes, max_lines, n_lines, line_off, field_off, status, &K, &S))) return rc;
+    return flip_finish(ctx, s, S, K.bytes(), t1, t2, odds, chisq, p, n_ge, batch_max);
     HPGV_ABI_CATCH(ctx)
 }
 

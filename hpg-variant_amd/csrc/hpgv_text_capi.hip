@@ -1,7 +1,8 @@
 // hpgv_text_capi.hip -- the front half of every entry point that takes VCF text (include/hpgv.h): the tokenizer's launcher
 // (hpgv_tokenize_dev) and its host twin (hpgv_tokenize), the record filters' settings, and text_front -- text to the device,
 // tokenize, line heads of an aliased text, record filters, layout -- which hands a Staged to the tools' back halves in
-// hpgv_tool_capi.hip and to hpgv_filter_text in hpgv_lines_capi.hip.
+// hpgv_tool_capi.hip and to hpgv_filter_text in hpgv_lines_capi.hip; text_front_skip adds the skip byte per line that the
+// permutation and LD kernels read (hpgv_perm_capi.hip, hpgv_ld_capi.hip).
 #include "hpgv_internal.h"
 #include "hpgv_text_kernels.h"
 #include "hpgv_text2_kernels.h"
@@ -279,6 +280,20 @@ int text_front(hpgv_ctx *ctx, Slot *s, int which, const Layout &L, const char *t
     if (!final_layout) return HPGV_OK;                       // the caller's one-pass kernel reads the raw matrix itself
     S->d_laid = s->laid.as<uint8_t>(); S->which = which;
     return hpgv_layout_dev(ctx, which, S->d_raw, raw_pitch, nl, s->laid.as<uint8_t>(), s->stream);
+}
+
+// the lines a caller of the plain *_text entry points drops: not a record (status 1), or rejected by a record filter
+static bool line_skipped(int32_t status) { return (status & 0xFF) == 1 || (status & HPGV_LINE_FILTERED); }
+
+// the record filters run only into a status array, so the call brings its own when the caller gave none
+int text_front_skip(hpgv_ctx *ctx, Slot *s, int which, const Layout &L, const char *text, size_t text_bytes, int max_lines, int *n_lines,
+                    uint64_t *line_off, uint32_t *field_off, int32_t *status, TextSkip *K, Staged *S) {
+    if (!status) { K->own_status.assign((size_t)max_lines, 0); status = K->own_status.data(); }
+    if (const int rc = text_front(ctx, s, which, L, text, text_bytes, max_lines, n_lines, line_off, field_off, status, S, true)) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(s->stream));
+    K->skip.resize((size_t)S->n);
+    for (int i = 0; i < S->n; ++i) K->skip[(size_t)i] = line_skipped(status[i]) ? 1 : 0;
+    return HPGV_OK;
 }
 
 namespace {

@@ -1,8 +1,9 @@
 // hpgv_tool_capi.hip -- C ABI of the tools' synchronous entry points (include/hpgv.h): association, TDT, statistics,
 // Mendelian errors and the epistasis dataset on a host batch (hpgv_assoc, ...) or on a text (hpgv_assoc_text, ...).  An
-// entry point checks its arguments, leases a slot, puts the matrix on the device -- a batch through batch_sources /
-// stage_batch, a text through text_front (hpgv_text_capi.hip) -- and hands the result (a Staged) to its tool's back half,
-// which is written once for both.
+// entry point checks its arguments, leases a slot, puts the matrix on the device -- a batch through stage_batch (batch_sources
+// for a one-pass kernel, stage_chain for the kernel chain), a text through text_front (hpgv_text_capi.hip) -- and hands the
+// result (a Staged) to its tool's back half, which is written once for both.  stage_chain and the two halves of the association
+// and TDT chains are shared with the permutation and LD entry points (hpgv_perm_capi.hip, hpgv_ld_capi.hip).
 #include "hpgv_internal.h"
 #include "hpgv_batch_kernels.h"
 #include <cstddef>
@@ -32,10 +33,13 @@ static bool batch_fused_ok(const hpgv_ctx *ctx, int n_samples) {
     return ctx->batch_fused && (size_t)n_samples + 32 <= (size_t)ctx->batch_lds_max;
 }
 
+// what a batch entry point reads of the caller's matrix (n_variants > 0): the last row need not be a whole pitch
+static size_t batch_bytes(int n_variants, size_t pitch, int n_samples) { return (size_t)(n_variants - 1) * pitch + (size_t)n_samples; }
+
 // sources of a fused call: the caller's buffers as they are when the device can read them, the slot's copies otherwise
 static int batch_sources(hpgv_ctx *ctx, Slot *s, const uint8_t *gt, size_t pitch, int n_variants, int n_samples, const uint8_t *is_x,
                          Staged *S) {
-    const size_t bytes = (size_t)(n_variants - 1) * pitch + (size_t)n_samples;     // the last row need not be a whole pitch
+    const size_t bytes = batch_bytes(n_variants, pitch, n_samples);
     // page-locked rows are read in place by the kernel -- unless batch_copy asks for the copy engine first (it moves 2 MB in
     // 35 us where the kernel's own reads over the bus take 44; the kernel then runs on device memory)
     const void *src = ctx->batch_copy ? nullptr : mapped_view(gt, bytes);
@@ -58,22 +62,12 @@ static int batch_sources(hpgv_ctx *ctx, Slot *s, const uint8_t *gt, size_t pitch
     return HPGV_OK;
 }
 
-// a batch on the device.  one_pass: for a kernel that reads the raw rows itself (batch_sources); else for the kernel chain:
-// raw rows and is_x copied to the slot, the rows laid out for the tool (`which`)
+// a batch on the device.  one_pass: for a kernel that reads the raw rows itself (batch_sources); else for the kernel chain
+// (stage_chain, below the back halves)
 static int stage_batch(hpgv_ctx *ctx, Slot *s, bool one_pass, int which, const Layout &L, const uint8_t *gt, size_t pitch,
                        int n_variants, const uint8_t *is_x, Staged *S) {
     if (one_pass) return batch_sources(ctx, s, gt, pitch, n_variants, L.n_samples, is_x, S);
-    HIPCHK(ctx, s->raw.reserve_slack((size_t)n_variants * pitch));
-    HIPCHK(ctx, s->laid.reserve_slack((size_t)n_variants * L.pitch));
-    HIPCHK(ctx, hipMemcpyAsync(s->raw.p, gt, (size_t)n_variants * pitch, hipMemcpyHostToDevice, s->stream));
-    if (is_x) {
-        HIPCHK(ctx, s->isx.reserve_slack((size_t)n_variants));
-        HIPCHK(ctx, hipMemcpyAsync(s->isx.p, is_x, (size_t)n_variants, hipMemcpyHostToDevice, s->stream));
-        S->d_isx = s->isx.as<uint8_t>();
-    }
-    S->d_raw = s->raw.as<uint8_t>(); S->raw_pitch = pitch; S->d_laid = s->laid.as<uint8_t>(); S->which = which;
-    S->n = n_variants; S->out_stride = (size_t)n_variants;
-    return hpgv_layout_dev(ctx, which, S->d_raw, pitch, n_variants, s->laid.as<uint8_t>(), s->stream);
+    return stage_chain(ctx, s, which, L, gt, pitch, n_variants, is_x, S);
 }
 
 // ---- k_stats_all on a matrix the device can read (the tokenizer's raw matrix, or a host batch through batch_sources): every
@@ -178,6 +172,11 @@ static int launch_batch(hpgv_ctx *ctx, Slot *s, const Staged &S, hpgv::BatchArgs
 
 // ---- the tools' back halves: from a staged matrix to the caller's arrays, written once for a batch and a text -------------
 
+static int assoc_statistics(hpgv_ctx *ctx, int task, const int32_t *d_counts, int nv, double *d_odds, double *d_chisq, double *d_p, hipStream_t st) {
+    return task == HPGV_TASK_CHISQ ? hpgv_assoc_chisq_dev(ctx, d_counts, nv, d_odds, d_chisq, d_p, st)
+                                   : hpgv_assoc_fisher_dev(ctx, d_counts, nv, d_odds, d_p, st);
+}
+
 // chi-square or Fisher per variant.  A text that skipped the layout is counted by k_assoc_rows where that kernel takes
 // the cohort; any matrix that skipped it goes through the fused kernel; a laid-out one through the scans' kernel chain.
 // p_at (may be null): where the p-values lie on the device when this returns, p_i at p_at->first + i * p_at->second bytes
@@ -187,23 +186,25 @@ static int assoc_finish(hpgv_ctx *ctx, Slot *s, int task, const Staged &S, int32
     const int nv = S.n;
     const size_t n = (size_t)nv;
     const bool chi = task == HPGV_TASK_CHISQ, rows = !S.d_laid && S.text && ctx->assoc_rows;
-    if (S.d_laid || rows) {
-        HIPCHK(ctx, s->tally.reserve_slack(n * 16));
-        HIPCHK(ctx, s->dbl.reserve_slack(n * 3 * sizeof(double)));
+    if (S.d_laid) {
+        ChainOut C;
+        if ((rc = assoc_chain(ctx, s, task, S, &C))) return rc;
+        if (p_at) *p_at = {(const char *)C.d_p, sizeof(double)};
+        if ((rc = assoc_copy_out(ctx, s, task, S, C, A1, A2, U1, U2, odds, chisq, p))) return rc;
+        HIPCHK(ctx, hipStreamSynchronize(s->stream));
+        return HPGV_OK;
     }
-    int32_t *d_counts = s->tally.as<int32_t>();
-    double *d_odds = s->dbl.as<double>(), *d_chisq = d_odds + n, *d_p = d_odds + 2 * n;
-    if (p_at) *p_at = {(const char *)d_p, sizeof(double)};
-    auto statistics = [&] {
-        return chi ? hpgv_assoc_chisq_dev(ctx, d_counts, nv, d_odds, d_chisq, d_p, s->stream)
-                   : hpgv_assoc_fisher_dev(ctx, d_counts, nv, d_odds, d_p, s->stream);
-    };
     if (rows) {
         // the raw matrix read once by threads that own columns (k_assoc_rows), then the scans' own statistics kernels
+        HIPCHK(ctx, s->tally.reserve_slack(n * 16));
+        HIPCHK(ctx, s->dbl.reserve_slack(n * 3 * sizeof(double)));
         HIPCHK(ctx, s->res.reserve(n * 40 + 64));
+        int32_t *d_counts = s->tally.as<int32_t>();
+        double *d_odds = s->dbl.as<double>(), *d_chisq = d_odds + n, *d_p = d_odds + 2 * n;
         if (hpgv_launch_assoc_rows(ctx, S.d_raw, S.raw_pitch, nv, S.d_isx, d_counts, s->stream) == 0) {
             HIPCHK(ctx, hipGetLastError());
-            if ((rc = statistics())) { (void)hipStreamSynchronize(s->stream); return rc; }
+            if (p_at) *p_at = {(const char *)d_p, sizeof(double)};
+            if ((rc = assoc_statistics(ctx, task, d_counts, nv, d_odds, d_chisq, d_p, s->stream))) { (void)hipStreamSynchronize(s->stream); return rc; }
             // results come back through the slot's page-locked block (one copy each at the bus rate), then into the caller's arrays
             char *h = (char *)s->res.h;
             HIPCHK(ctx, hipMemcpyAsync(h, d_counts, n * 16, hipMemcpyDeviceToHost, s->stream));
@@ -218,47 +219,28 @@ static int assoc_finish(hpgv_ctx *ctx, Slot *s, int task, const Staged &S, int32
             return HPGV_OK;
         }
     }
-    if (!S.d_laid) {
-        // one kernel; the only other work of the call is unpacking its records
-        hpgv::BatchArgs A;
-        memset(&A, 0, sizeof A);
-        A.n_samples = ctx->assoc.n_samples;
-        A.col_of_pos = ctx->assoc.d_col_of_pos(); A.chunks = ctx->assoc.chunks; A.chunksA = ctx->chunksA;
-        A.lf = ctx->d_lf; A.rel_cut = pow(10.0, -(double)ctx->fisher_cut_exp);
-        rc = chi ? launch_batch<hpgv::BATCH_CHISQ>(ctx, s, S, A, sizeof(hpgv::BatchAssocRec))
-                 : launch_batch<hpgv::BATCH_FISHER>(ctx, s, S, A, sizeof(hpgv::BatchAssocRec));
-        if (rc) return rc;
-        if (p_at) *p_at = {(const char *)s->res.d + offsetof(hpgv::BatchAssocRec, p), sizeof(hpgv::BatchAssocRec)};
-        const hpgv::BatchAssocRec *r = (const hpgv::BatchAssocRec *)s->res.h;
-        for (size_t i = 0; i < n; ++i) {
-            A1[i] = r[i].A1; A2[i] = r[i].A2; U1[i] = r[i].U1; U2[i] = r[i].U2;
-            odds[i] = r[i].odds; p[i] = r[i].p;
-        }
-        if (chi) for (size_t i = 0; i < n; ++i) chisq[i] = r[i].chisq;
-        return HPGV_OK;
+    // one kernel; the only other work of the call is unpacking its records
+    hpgv::BatchArgs A;
+    memset(&A, 0, sizeof A);
+    A.n_samples = ctx->assoc.n_samples;
+    A.col_of_pos = ctx->assoc.d_col_of_pos(); A.chunks = ctx->assoc.chunks; A.chunksA = ctx->chunksA;
+    A.lf = ctx->d_lf; A.rel_cut = pow(10.0, -(double)ctx->fisher_cut_exp);
+    rc = chi ? launch_batch<hpgv::BATCH_CHISQ>(ctx, s, S, A, sizeof(hpgv::BatchAssocRec))
+             : launch_batch<hpgv::BATCH_FISHER>(ctx, s, S, A, sizeof(hpgv::BatchAssocRec));
+    if (rc) return rc;
+    if (p_at) *p_at = {(const char *)s->res.d + offsetof(hpgv::BatchAssocRec, p), sizeof(hpgv::BatchAssocRec)};
+    const hpgv::BatchAssocRec *r = (const hpgv::BatchAssocRec *)s->res.h;
+    for (size_t i = 0; i < n; ++i) {
+        A1[i] = r[i].A1; A2[i] = r[i].A2; U1[i] = r[i].U1; U2[i] = r[i].U2;
+        odds[i] = r[i].odds; p[i] = r[i].p;
     }
-    HIPCHK(ctx, s->ints.reserve_slack(n * 4 * sizeof(int32_t)));
-    int32_t *d_soa = s->ints.as<int32_t>();
-    if ((rc = hpgv_assoc_scan_dev(ctx, S.d_laid, nv, S.d_isx, d_counts, s->stream))) return rc;
-    if ((rc = statistics())) return rc;
-    hipLaunchKernelGGL(hpgv::k_counts_to_soa, dim3((nv + 255) / 256), dim3(256), 0, s->stream,
-                       (const int4 *)d_counts, nv, d_soa, d_soa + n, d_soa + 2 * n, d_soa + 3 * n);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(A1, d_soa, n * 4, hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(ctx, hipMemcpyAsync(A2, d_soa + n, n * 4, hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(ctx, hipMemcpyAsync(U1, d_soa + 2 * n, n * 4, hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(ctx, hipMemcpyAsync(U2, d_soa + 3 * n, n * 4, hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(ctx, hipMemcpyAsync(odds, d_odds, n * 8, hipMemcpyDeviceToHost, s->stream));
-    if (chi) HIPCHK(ctx, hipMemcpyAsync(chisq, d_chisq, n * 8, hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(ctx, hipMemcpyAsync(p, d_p, n * 8, hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(ctx, hipStreamSynchronize(s->stream));
+    if (chi) for (size_t i = 0; i < n; ++i) chisq[i] = r[i].chisq;
     return HPGV_OK;
 }
 
 static int tdt_finish(hpgv_ctx *ctx, Slot *s, const Staged &S, int32_t *t1, int32_t *t2, double *odds, double *chisq, double *p) {
     int rc;
-    const int nv = S.n;
-    const size_t n = (size_t)nv;
+    const size_t n = (size_t)S.n;
     if (!S.d_laid) {
         hpgv::BatchArgs A;
         memset(&A, 0, sizeof A);
@@ -272,19 +254,12 @@ static int tdt_finish(hpgv_ctx *ctx, Slot *s, const Staged &S, int32_t *t1, int3
         for (size_t i = 0; i < n; ++i) { t1[i] = r[i].t1; t2[i] = r[i].t2; odds[i] = r[i].odds; chisq[i] = r[i].chisq; p[i] = r[i].p; }
         return HPGV_OK;
     }
-    HIPCHK(ctx, s->tally.reserve_slack(n * 8));
-    HIPCHK(ctx, s->dbl.reserve_slack(n * 3 * sizeof(double)));
-    int32_t *d_tu = s->tally.as<int32_t>();
-    double *d_odds = s->dbl.as<double>(), *d_chisq = d_odds + n, *d_p = d_odds + 2 * n;
-    if ((rc = hpgv_tdt_scan_dev(ctx, S.d_laid, nv, S.d_isx, d_tu, s->stream))) return rc;
-    if ((rc = hpgv_tdt_stats_dev(ctx, d_tu, nv, d_odds, d_chisq, d_p, s->stream))) return rc;
-    std::vector<int32_t> tu(2 * n);
-    HIPCHK(ctx, hipMemcpyAsync(tu.data(), d_tu, n * 8, hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(ctx, hipMemcpyAsync(odds, d_odds, n * 8, hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(ctx, hipMemcpyAsync(chisq, d_chisq, n * 8, hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(ctx, hipMemcpyAsync(p, d_p, n * 8, hipMemcpyDeviceToHost, s->stream));
+    ChainOut C;
+    std::vector<int32_t> tu;
+    if ((rc = tdt_chain(ctx, s, S, &C))) return rc;
+    if ((rc = tdt_copy_out(ctx, s, S, C, &tu, odds, chisq, p))) return rc;
     HIPCHK(ctx, hipStreamSynchronize(s->stream));
-    for (size_t i = 0; i < n; ++i) { t1[i] = tu[2 * i]; t2[i] = tu[2 * i + 1]; }
+    tdt_split_counts(tu, t1, t2);
     return HPGV_OK;
 }
 
@@ -429,6 +404,83 @@ static int epi_rows_out(hpgv_ctx *ctx, Slot *s, const Staged &S, uint8_t *out) {
 }
 
 }  // namespace
+
+// ---- shared with hpgv_perm_capi.hip and hpgv_ld_capi.hip (hpgv_internal.h) ----------------------------------------------------
+
+int stage_chain(hpgv_ctx *ctx, Slot *s, int which, const Layout &L, const uint8_t *gt, size_t pitch, int n_variants, const uint8_t *is_x,
+                Staged *S) {
+    S->n = n_variants; S->out_stride = (size_t)n_variants;
+    if (n_variants == 0) return HPGV_OK;
+    // what the chain reads of the raw rows (k_layout, k_genotype_table) is the first n_samples bytes of each, byte by byte; 16 bytes
+    // of room behind the last row are reserved all the same
+    const size_t bytes = batch_bytes(n_variants, pitch, L.n_samples);
+    HIPCHK(ctx, s->raw.reserve_slack(bytes + 16));
+    HIPCHK(ctx, s->laid.reserve_slack((size_t)n_variants * L.pitch + 16));
+    if (bytes) HIPCHK(ctx, hipMemcpyAsync(s->raw.p, gt, bytes, hipMemcpyHostToDevice, s->stream));
+    if (is_x) {
+        HIPCHK(ctx, s->isx.reserve_slack((size_t)n_variants));
+        HIPCHK(ctx, hipMemcpyAsync(s->isx.p, is_x, (size_t)n_variants, hipMemcpyHostToDevice, s->stream));
+        S->d_isx = s->isx.as<uint8_t>();
+    }
+    S->d_raw = s->raw.as<uint8_t>(); S->raw_pitch = pitch; S->d_laid = s->laid.as<uint8_t>(); S->which = which;
+    return hpgv_layout_dev(ctx, which, S->d_raw, pitch, n_variants, s->laid.as<uint8_t>(), s->stream);
+}
+
+int assoc_chain(hpgv_ctx *ctx, Slot *s, int task, const Staged &S, ChainOut *C) {
+    const size_t n = (size_t)S.n;
+    HIPCHK(ctx, s->tally.reserve_slack(n * 16 + 16));
+    HIPCHK(ctx, s->dbl.reserve_slack(n * 3 * sizeof(double) + 16));
+    HIPCHK(ctx, s->ints.reserve_slack(n * 4 * sizeof(int32_t) + 16));
+    C->d_tally = s->tally.as<int32_t>();
+    C->d_odds = s->dbl.as<double>(); C->d_chisq = C->d_odds + n; C->d_p = C->d_odds + 2 * n;
+    if (S.n == 0) return HPGV_OK;
+    if (const int rc = hpgv_assoc_scan_dev(ctx, S.d_laid, S.n, S.d_isx, C->d_tally, s->stream)) return rc;
+    return assoc_statistics(ctx, task, C->d_tally, S.n, C->d_odds, C->d_chisq, C->d_p, s->stream);
+}
+
+int assoc_copy_out(hpgv_ctx *ctx, Slot *s, int task, const Staged &S, const ChainOut &C, int32_t *A1, int32_t *A2, int32_t *U1, int32_t *U2,
+                   double *odds, double *chisq, double *p) {
+    if (S.n == 0) return HPGV_OK;
+    const size_t n = (size_t)S.n;
+    int32_t *d_soa = s->ints.as<int32_t>();
+    hipLaunchKernelGGL(hpgv::k_counts_to_soa, dim3((S.n + 255) / 256), dim3(256), 0, s->stream,
+                       (const int4 *)C.d_tally, S.n, d_soa, d_soa + n, d_soa + 2 * n, d_soa + 3 * n);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(A1, d_soa, n * 4, hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(ctx, hipMemcpyAsync(A2, d_soa + n, n * 4, hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(ctx, hipMemcpyAsync(U1, d_soa + 2 * n, n * 4, hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(ctx, hipMemcpyAsync(U2, d_soa + 3 * n, n * 4, hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(ctx, hipMemcpyAsync(odds, C.d_odds, n * 8, hipMemcpyDeviceToHost, s->stream));
+    if (task == HPGV_TASK_CHISQ) HIPCHK(ctx, hipMemcpyAsync(chisq, C.d_chisq, n * 8, hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(ctx, hipMemcpyAsync(p, C.d_p, n * 8, hipMemcpyDeviceToHost, s->stream));
+    return HPGV_OK;
+}
+
+int tdt_chain(hpgv_ctx *ctx, Slot *s, const Staged &S, ChainOut *C) {
+    const size_t n = (size_t)S.n;
+    HIPCHK(ctx, s->tally.reserve_slack(n * 8 + 16));
+    HIPCHK(ctx, s->dbl.reserve_slack(n * 3 * sizeof(double) + 16));
+    C->d_tally = s->tally.as<int32_t>();
+    C->d_odds = s->dbl.as<double>(); C->d_chisq = C->d_odds + n; C->d_p = C->d_odds + 2 * n;
+    if (S.n == 0) return HPGV_OK;
+    if (const int rc = hpgv_tdt_scan_dev(ctx, S.d_laid, S.n, S.d_isx, C->d_tally, s->stream)) return rc;
+    return hpgv_tdt_stats_dev(ctx, C->d_tally, S.n, C->d_odds, C->d_chisq, C->d_p, s->stream);
+}
+
+int tdt_copy_out(hpgv_ctx *ctx, Slot *s, const Staged &S, const ChainOut &C, std::vector<int32_t> *tu, double *odds, double *chisq, double *p) {
+    const size_t n = (size_t)S.n;
+    tu->resize(2 * n);
+    if (S.n == 0) return HPGV_OK;
+    HIPCHK(ctx, hipMemcpyAsync(tu->data(), C.d_tally, n * 8, hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(ctx, hipMemcpyAsync(odds, C.d_odds, n * 8, hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(ctx, hipMemcpyAsync(chisq, C.d_chisq, n * 8, hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(ctx, hipMemcpyAsync(p, C.d_p, n * 8, hipMemcpyDeviceToHost, s->stream));
+    return HPGV_OK;
+}
+
+void tdt_split_counts(const std::vector<int32_t> &tu, int32_t *t1, int32_t *t2) {
+    for (size_t i = 0; 2 * i < tu.size(); ++i) { t1[i] = tu[2 * i]; t2[i] = tu[2 * i + 1]; }
+}
 
 // the fused per-batch kernels stage one raw row in LDS: ask for the whole 160 KiB where the device has it
 long hpgv_batch_lds_optin(const hipDeviceProp_t &prop, long fallback) {

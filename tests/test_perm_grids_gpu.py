@@ -2,7 +2,9 @@
 csrc/hpgv_assoc_perm_kernels.h; k_tdt_perm and k_tdt_perm_slow, csrc/hpgv_tdt_perm_kernels.h; csrc/hpgv_perm_capi.hip):
 passes past the first of the label kernel, the folded (tile, pass) grid of the TDT kernel past its first eight tiles, the signed
 i8 operand at +-126, rows of 68 k-steps and more, the layout options that change the pitch and the chunk count the kernels
-walk, and the refusal at the permutation limit.  The case builders, device drivers and references are those of
+walk, the refusal at the permutation limit, and (section F) the host plumbing of the synchronous permutation and LD entry
+points: a text call without a status array, calls without rows or lines, and a batch whose last row is no whole pitch.  The
+case builders, device drivers and references are those of
 test_assoc_perm_gpu.py, model_golden.py / test_assoc_trend_perm_gpu.py and test_tdt_perm_gpu.py, with further special label
 and flip rows placed where later passes see them.
 
@@ -18,6 +20,7 @@ import functools
 import numpy as np
 import pytest
 
+import ld_golden as lg
 import model_golden as mg
 import test_assoc_perm_gpu as ap
 import test_assoc_trend_perm_gpu as tp
@@ -413,3 +416,220 @@ def test_too_many_flip_rows_are_refused_and_the_earlier_stay():
         _check_tdt(c, (), tu, n_ge, bmax, pt)
         assert e.L.hpgv_set_tdt_flips(e.h, C.c_void_p(fl.ctypes.data), TOO_MANY) == hpgv.ERR_UNSUPPORTED
     e.close()
+
+
+# ------------------------------------------------------------------------------------------------ F. host plumbing of the entry points
+
+# Shapes that cross every boundary of the plumbing once: 37 columns (no multiple of 16), 70 rows or lines (a second, ragged
+# 64-variant tile), 130 permutations (a second pass); the pedigree has two two-child families, so that the slow tail exists
+PLUMB = ((16, 17), 70, 130, True)
+PLUMB_WINDOW = 12
+LINE_FILTERED = 0x100                                                    # HPGV_LINE_FILTERED of include/hpgv.h
+CUT, RARE = 40, 66                                                       # the line cut short; the record below the frequency filter
+I32, F64 = np.int32, np.float64
+
+# the per-line outputs of the text forms in the order of their C signatures: (name, dtype, shape of one line's part)
+TEXT_FORMS = {
+    "assoc_perm": ("hpgv_assoc_perm_text", [(k, I32, ()) for k in ("A1", "A2", "U1", "U2")] + [(k, F64, ()) for k in ("odds", "chisq", "p")] + [("n_ge", I32, ())]),
+    "model": ("hpgv_assoc_model_text", [("counts8", I32, (8,)), ("chisq5", F64, (5,)), ("p5", F64, (5,)), ("n_ge", I32, ())]),
+    "tdt_perm": ("hpgv_tdt_perm_text", [("t1", I32, ()), ("t2", I32, ())] + [(k, F64, ()) for k in ("odds", "chisq", "p")] + [("n_ge", I32, ())]),
+    "ld": ("hpgv_ld_text", [("r2", F64, (PLUMB_WINDOW,)), ("counts6", I32, (PLUMB_WINDOW, 6))]),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def _plumb_labels():
+    """mg.case(PLUMB) with chromosome flags; row RARE is all reference but for one heterozygous call in a cohort column"""
+    c = dict(mg.case(*PLUMB))
+    assert c["ns"] == 37
+    codes = c["codes"].copy()
+    codes[RARE] = 0x00
+    codes[RARE, np.flatnonzero(c["cond"] == 1)[2]] = 0x01
+    c.update(codes=codes, is_x=(np.arange(c["nv"]) % 5 == 3).astype(np.uint8))
+    return c
+
+
+@functools.lru_cache(maxsize=None)
+def _plumb_families():
+    """three trios and two two-child families over 37 columns; row RARE is all reference but for one heterozygous father of a trio"""
+    rng = np.random.default_rng(3737)
+    ns, fam = td._pedigree(rng, 3, 2, slow_children=2)
+    assert ns == 37
+    nv, n_perms = PLUMB[1], PLUMB[2]
+    codes = random_codes(rng, nv, ns, quirks=True)
+    codes[nv // 2:] = random_codes(rng, nv - nv // 2, ns, quirks=False)
+    fcol, _, coff, _, _ = fam
+    trio = [f for f in range(len(fcol)) if fcol[f] >= 0 and coff[f + 1] - coff[f] == 1][0]
+    codes[RARE] = 0x00
+    codes[RARE, fcol[trio]] = 0x01
+    is_x = (np.arange(nv) % 5 == 3).astype(np.uint8)
+    assert not is_x[RARE]
+    flips = (rng.random((n_perms, len(fcol))) < rng.uniform(0.2, 0.8, size=(n_perms, 1))).astype(np.uint8)
+    flips[0], flips[n_perms - 1] = 0, 1
+    c = td._finish(ns, fam, codes, is_x, flips, 3, 2)
+    assert c["part"][RARE] and c["part"][CUT]
+    return c
+
+
+def _plumb_engine(form, filters=False):
+    c = _plumb_families() if form == "tdt_perm" else _plumb_labels()
+    e = td._engine(c) if form == "tdt_perm" else mg.engine(c)
+    if filters:                                                          # a frequency filter that rejects row RARE (1 / 74 alleles)
+        assert e.L.hpgv_set_stats_cohort(e.h, c["ns"]) == hpgv.OK
+        assert e.L.hpgv_set_text_filters(e.h, C.c_double(0.02), C.c_double(-1.0), C.c_long(-1)) == hpgv.OK
+    return c, e
+
+
+def _call_text(e, form, text, max_lines, n_perms, with_status):
+    """the form's C entry point on buffers pre-filled with sentinels: (n_lines, dict of every output)"""
+    fn, outs = TEXT_FORMS[form]
+    m = max(max_lines, 1)
+    res = {k: np.full((m,) + shape, 0x5A5A5A5A if dt is I32 else -7.0, dt) for k, dt, shape in outs}
+    status = np.full(m, -1, I32) if with_status else None
+    nl = C.c_int(-1)
+    args = [e.h, text, len(text), max_lines, C.byref(nl), None, None, hpgv._ptr(status)] + ([PLUMB_WINDOW] if form == "ld" else [])
+    args += [hpgv._ptr(res[k]) for k, _, _ in outs]
+    if form != "ld":
+        res["batch_max"] = np.full(n_perms, -7.0)
+        args.append(hpgv._ptr(res["batch_max"]))
+    assert getattr(e.L, fn)(*args) == hpgv.OK
+    return nl.value, res, status
+
+
+def _raw(a):
+    return np.ascontiguousarray(a).view(np.uint8)
+
+
+@pytest.mark.parametrize("form", sorted(TEXT_FORMS))
+def test_text_without_a_status_array(form):
+    """status == NULL: the call brings the status array that the record filters and the skip bytes need; every output is that of
+    the call with one, and the lines that are no records or were filtered take no part"""
+    c, e = _plumb_engine(form, filters=True)
+    nv, n_perms = c["nv"], c["n_perms"]
+    lines = ap._text(c["codes"], c["is_x"]).split(b"\n")[:-1]
+    text = b"".join((b"7\t5\trs" if i == CUT else l) + b"\n" for i, l in enumerate(lines))
+    nl, res, status = _call_text(e, form, text, nv, n_perms, True)
+    nl0, res0, _ = _call_text(e, form, text, nv, n_perms, False)
+    assert nl == nl0 == nv
+    for k in res:
+        assert np.array_equal(_raw(res[k]), _raw(res0[k])), k
+    assert (status[CUT] & 0xFF) == 1 and (status[RARE] & LINE_FILTERED) and (status[RARE] & 0xFF) == 0
+    skip = ((status & 0xFF) == 1) | ((status & LINE_FILTERED) != 0)
+    assert 2 <= skip.sum() < nv // 2
+    keep = ~skip
+    sub = dict(c, codes=c["codes"][keep], is_x=c["is_x"][keep])
+    if form == "ld":
+        cohort = c["cond"] != 2
+        exp = lg.band(c["codes"][:, cohort], PLUMB_WINDOW, skip=skip.astype(np.uint8))
+        lg.assert_same((res0["r2"], res0["counts6"]), exp)
+        assert np.isnan(res0["r2"][skip]).all() and np.isfinite(res0["r2"]).sum() > nv
+        # and no later row pairs with a skipped one: slot d - 1 of row b is the pair (b - d, b)
+        for b in np.flatnonzero(skip):
+            for d in range(1, min(PLUMB_WINDOW, nv - 1 - b) + 1):
+                assert np.isnan(res0["r2"][b + d, d - 1])
+    else:
+        if form == "assoc_perm":
+            _, n_ge, bmax, _ = ap._run_dev(e, sub)
+        elif form == "model":
+            got = mg.run_dev(e, sub, perm=True)
+            n_ge, bmax = got["n_ge"], got["batch_max"]
+        else:
+            _, n_ge, bmax, _ = td._run_dev(e, sub)
+        assert not res0["n_ge"][skip].any() and np.array_equal(res0["n_ge"][keep], n_ge) and n_ge.any()
+        assert np.array_equal(mg.bits(res0["batch_max"]), mg.bits(bmax)) and bmax.any()
+        # row RARE would have counted: with every line a record and no filter it reaches its own statistic at least once
+        full = {"assoc_perm": lambda: ap._run_dev(e, c)[1], "model": lambda: mg.run_dev(e, c, perm=True)["n_ge"], "tdt_perm": lambda: td._run_dev(e, c)[1]}[form]()
+        assert full[RARE] >= 1
+    e.close()
+
+
+@pytest.mark.parametrize("form", ["assoc_perm", "model", "tdt_perm"])
+def test_empty_permutation_calls_zero_batch_max(form):
+    """no variants, no lines: HPGV_OK, nothing per row, and batch_max -- the identity of the merge by maximum -- written all the same"""
+    c, e = _plumb_engine(form)
+    n_perms = c["n_perms"]
+    fn, outs = TEXT_FORMS[form]
+    bmax = np.full(n_perms + 1, -7.0)
+    dummy = np.zeros(64, np.uint8)                                       # (the model call wants n_ge with batch_max)
+    rows = [None, c["ns"], 0] + ([] if form == "model" else [None])      # gt, pitch, n_variants[, is_x]
+    assert getattr(e.L, fn[:-len("_text")])(e.h, *rows, *[hpgv._ptr(dummy)] * len(outs), hpgv._ptr(bmax)) == hpgv.OK
+    assert not bmax[:n_perms].any() and bmax[n_perms] == -7.0
+    nl, res, _ = _call_text(e, form, b"", 0, n_perms, True)
+    assert nl == 0 and not res["batch_max"].any()
+    assert all(np.all(res[k] == (0x5A5A5A5A if dt is I32 else -7.0)) for k, dt, _ in outs)
+    e.close()
+
+
+def test_empty_ld_calls():
+    """hpgv_ld_edges without rows (hpgv_ld without rows: test_ld_gpu.py::test_host_and_text_entry_points), hpgv_ld_text without lines"""
+    c, e = _plumb_engine("ld")
+    n = C.c_uint64(99)
+    assert e.L.hpgv_ld_edges(e.h, None, c["ns"], 0, PLUMB_WINDOW, None, None, -1, 0.5, None, 0, C.byref(n)) == hpgv.OK and n.value == 0
+    nl, res, _ = _call_text(e, "ld", b"", 0, 0, True)
+    assert nl == 0 and np.all(res["r2"] == -7.0)
+    e.close()
+
+
+def _tight(codes, pad=11):
+    """the rows at a pitch of n_samples + pad in a buffer that ends with the last row's last sample: (buffer, pitch)"""
+    nv, ns = codes.shape
+    pitch = ns + pad
+    buf = np.full((nv - 1) * pitch + ns, 0xEE, np.uint8)
+    view = np.lib.stride_tricks.as_strided(buf, shape=(nv, ns), strides=(pitch, 1))
+    view[:] = codes
+    return buf, pitch
+
+
+@pytest.mark.parametrize("fused", [0, 1])
+@pytest.mark.parametrize("form", ["labels", "families"])
+def test_last_row_need_not_be_a_whole_pitch(form, fused):
+    """(n_variants - 1) * pitch + n_samples bytes are all a batch entry point may read of the caller's matrix: on a buffer of exactly
+    that size, through the one-pass kernel and through the kernel chain, the results are those of the packed matrix.  (This pins
+    the contract; an over-read of the last row's pad would need a guard page to show)"""
+    c, e = _plumb_engine("tdt_perm" if form == "families" else "assoc_perm")
+    e.set_option("batch_fused", fused)
+    nv, n_perms, codes = c["nv"], c["n_perms"], np.ascontiguousarray(c["codes"])
+    buf, pitch = _tight(codes)
+    assert buf.size == (nv - 1) * pitch + c["ns"] and pitch == c["ns"] + 11
+    view = np.lib.stride_tricks.as_strided(buf, shape=codes.shape, strides=(pitch, 1))
+    names = TEXT_FORMS["tdt_perm" if form == "families" else "assoc_perm"][1]
+
+    def perm_call(fn):
+        res = {k: np.zeros(nv, dt) for k, dt, _ in names}
+        res["batch_max"] = np.full(n_perms, -7.0)
+        assert fn(e.h, hpgv._ptr(buf), pitch, nv, hpgv._ptr(c["is_x"]), *[hpgv._ptr(res[k]) for k, _, _ in names], hpgv._ptr(res["batch_max"])) == hpgv.OK
+        return res
+
+    if form == "families":
+        plain, plain_exp = e.tdt_view(view, c["ns"], c["is_x"]), e.tdt(codes, c["is_x"])
+        perm, perm_exp = perm_call(e.L.hpgv_tdt_perm), e.tdt_perm(codes, c["is_x"])
+        assert np.array_equal(plain_exp["t1"], c["t1"]) and np.array_equal(perm_exp["n_ge"], c["n_ge"])
+    else:
+        plain, plain_exp = e.assoc_view(hpgv.TASK_CHISQ, view, c["ns"], c["is_x"]), e.assoc(hpgv.TASK_CHISQ, codes, c["is_x"])
+        perm, perm_exp = perm_call(e.L.hpgv_assoc_perm), e.assoc_perm(codes, c["is_x"])
+        assert perm_exp["n_ge"].any()
+        r2, c6 = np.zeros((nv, PLUMB_WINDOW)), np.zeros((nv, PLUMB_WINDOW, 6), I32)
+        assert e.L.hpgv_ld(e.h, hpgv._ptr(buf), pitch, nv, PLUMB_WINDOW, None, None, -1, hpgv._ptr(r2), hpgv._ptr(c6)) == hpgv.OK
+        ld_exp = e.ld(codes, PLUMB_WINDOW)
+        assert np.array_equal(mg.bits(r2), mg.bits(ld_exp["r2"])) and np.array_equal(c6, ld_exp["counts6"]) and c6.any()
+    for got, exp in ((plain, plain_exp), (perm, perm_exp)):
+        for k in exp:
+            assert np.array_equal(_raw(got[k]), _raw(exp[k])), k
+    e.close()
+
+
+def test_text_wrappers_cut_their_outputs_to_the_capacity():
+    """n_lines counts every line of the text while the per-line arrays end at the capacity.  With room for five lines the arrays
+    have five rows whatever the slice asks for, so that half pins the shapes and values only; the wrappers' min(n_lines, max_lines)
+    is pinned by the call with room for none, where their own arrays still hold one row"""
+    c, e = _plumb_engine("ld")
+    nv, ns = c["nv"], c["ns"]
+    text = ap._text(c["codes"], c["is_x"])
+    full, five = e.ld_text(text, PLUMB_WINDOW), e.ld_text(text, PLUMB_WINDOW, max_lines=5)
+    assert five["n_lines"] == nv and five["r2"].shape == (5, PLUMB_WINDOW) and five["counts6"].shape == (5, PLUMB_WINDOW, 6) and five["status"].shape == (5,)
+    assert np.array_equal(mg.bits(five["r2"]), mg.bits(full["r2"][:5])) and np.array_equal(five["counts6"], full["counts6"][:5])
+    none = e.tokenize(text, ns, max_lines=0)
+    e.close()
+    assert none["n_lines"] == nv
+    assert none["gt"].shape == (0, ns) and none["is_x"].shape == (0,) and none["status"].shape == (0,) and none["field_off"].shape == (0, 10)
+    assert none["line_off"].shape == (1,)
