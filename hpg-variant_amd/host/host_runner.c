@@ -1,5 +1,6 @@
 /* host_runner.c -- the file runners: reader -> engine threads -> writer (hpgv_run_assoc / tdt / aggregate / stats / vcf2epi /
- * filter / split).  The VCF tools' own batch steps and writers are in host_vcftools.c.
+ * filter / split).  The VCF tools' own batch steps and writers are in host_vcftools.c, what a run keeps beside its result file in
+ * host_sideout.c.
  * Part of libhpgv_host.so (see hpgv_host_internal.h for the map of its units). */
 #include "hpgv_host_internal.h"
 #include <errno.h>
@@ -55,6 +56,77 @@ static void *pipe_reader(void *v) {
     }
 }
 
+/* the tool's engine call over a batch; *what: its name, for the failure message.  *again: the batch held more of something than
+ * there was room for, which there now is -- the call is to be repeated */
+static int engine_call(run_t *R, run_batch_t *b, const char **what, int *again) {
+    const run_tool_t tool = R->tool;
+    const int m = b->max_lines;
+    int rc = HPGV_OK;
+    switch (tool) {
+    case RUN_AGGREGATE: case RUN_STATS: { *what = "hpgv_stats_text";
+        memset(b->smiss, 0, sizeof(int32_t) * (size_t)b->n_smiss);
+        memset(b->cerr, 0, sizeof(int32_t) * (size_t)b->n_cerr);
+        /* the 256-bin tables of multi-allelic lines: room for 4 096 of them (4 MB), grown to what a batch really holds -- one
+         * per possible line is 1 KB x max_lines, hundreds of MB per batch for a narrow cohort in 256 MB windows */
+        if (!b->mtab) { b->multi_cap = m < 4096 ? m : 4096; b->mtab = (int32_t *)malloc(sizeof(int32_t) * 256 * (size_t)b->multi_cap); if (!b->mtab) return HPGV_ERR_NOMEM; }
+        b->n_multi = b->multi_cap;
+        const int mend = tool == RUN_STATS && b->n_cerr > 0;
+        const size_t gm = (size_t)m * (size_t)b->n_groups;
+        rc = hpgv_stats_text_groups(g_ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status, b->c8, b->hw, b->hw + m,
+                                    tool == RUN_STATS ? b->smiss : NULL, b->midx, b->mtab, &b->n_multi, mend ? b->merr : NULL, mend ? b->cerr : NULL,
+                                    b->n_groups ? b->gc8 : NULL, b->n_groups ? b->ghw : NULL, b->n_groups ? b->ghw + gm : NULL);
+        if (!rc && b->n_lines <= b->max_lines && b->n_multi > b->multi_cap) {      /* more multi-allelic lines than tables: again, with room */
+            free(b->mtab);
+            b->multi_cap = b->n_multi + b->n_multi / 8 + 16;
+            if (b->multi_cap > b->max_lines) b->multi_cap = b->max_lines;
+            b->mtab = (int32_t *)malloc(sizeof(int32_t) * 256 * (size_t)b->multi_cap);
+            if (!b->mtab) return HPGV_ERR_NOMEM;
+            *again = 1;
+        }
+        return rc;
+    }
+    case RUN_FILTER: case RUN_SPLIT:                       /* then the lines partitioned on the device (pipe_engine) */
+        *what = tool == RUN_FILTER ? "hpgv_filter_text / hpgv_text_partition" : "hpgv_filter_text / hpgv_text_multisplit";
+        return hpgv_filter_text(g_ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status);
+    case RUN_VCF2EPI: *what = "hpgv_epi_dataset_text";
+        return hpgv_epi_dataset_text(g_ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status, b->rows);
+    case RUN_TDT: *what = "hpgv_tdt_text";
+        return hpgv_tdt_text(g_ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status,
+                             b->ints, b->ints + m, b->dbl, b->dbl + m, b->dbl + 2 * m);
+    case RUN_TDT_PERM: *what = "hpgv_tdt_perm_text";
+        return hpgv_tdt_perm_text(g_ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status,
+                                  b->ints, b->ints + m, b->dbl, b->dbl + m, b->dbl + 2 * m, b->n_ge, b->bmax);
+    case RUN_CHISQ: case RUN_FISHER:
+        if (R->clump) {                                  /* the same call, which also leaves the batch's candidate rows (p <= p2) */
+            *what = "hpgv_assoc_select_text";
+            rc = hpgv_assoc_select_text(g_ctx, tool, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status,
+                                        b->ints, b->ints + m, b->ints + 2 * m, b->ints + 3 * m,
+                                        b->dbl, tool == RUN_CHISQ ? b->dbl + m : NULL, b->dbl + 2 * m,
+                                        R->clump->p2, b->sel, b->crows, (size_t)R->n_samples, b->crows_cap, &b->n_sel);
+            if (!rc && b->n_lines <= b->max_lines && b->n_sel > b->crows_cap) {      /* more candidates than rows: again, with room */
+                free(b->crows);
+                b->crows_cap = b->n_sel + b->n_sel / 8 + 16;
+                b->crows = (uint8_t *)malloc((size_t)b->crows_cap * (size_t)(R->n_samples > 0 ? R->n_samples : 1));
+                if (!b->crows) { b->crows_cap = 0; return HPGV_ERR_NOMEM; }
+                *again = 1;
+            }
+            return rc;
+        }
+        *what = "hpgv_assoc_text";
+        return hpgv_assoc_text(g_ctx, tool, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status,
+                               b->ints, b->ints + m, b->ints + 2 * m, b->ints + 3 * m,
+                               b->dbl, tool == RUN_CHISQ ? b->dbl + m : NULL, b->dbl + 2 * m);
+    case RUN_CHISQ_PERM: *what = "hpgv_assoc_perm_text";
+        return hpgv_assoc_perm_text(g_ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status,
+                                    b->ints, b->ints + m, b->ints + 2 * m, b->ints + 3 * m,
+                                    b->dbl, b->dbl + m, b->dbl + 2 * m, b->n_ge, b->bmax);
+    case RUN_MODEL: case RUN_MODEL_PERM: *what = "hpgv_assoc_model_text";
+        return hpgv_assoc_model_text(g_ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status,
+                                     b->ints, b->dbl, b->dbl + 5 * (size_t)m, tool == RUN_MODEL_PERM ? b->n_ge : NULL, tool == RUN_MODEL_PERM ? b->bmax : NULL);
+    }
+    return rc;
+}
+
 static void *pipe_engine(void *v) {
     run_pipe_t *P = (run_pipe_t *)v;
     const run_tool_t tool = P->run->tool;
@@ -78,69 +150,9 @@ static void *pipe_engine(void *v) {
         /* max_lines is sized for complete records; a batch of short (damaged) lines can hold more: the
          * engine reports the true count, the arrays grow and the batch is done again */
         for (int attempt = 0; attempt < 4; attempt++) {
-            const int m = b->max_lines;
-            switch (tool) {
-            case RUN_AGGREGATE: case RUN_STATS: { what = "hpgv_stats_text";
-                memset(b->smiss, 0, sizeof(int32_t) * (size_t)b->n_smiss);
-                memset(b->cerr, 0, sizeof(int32_t) * (size_t)b->n_cerr);
-                /* the 256-bin tables of multi-allelic lines: room for 4 096 of them (4 MB), grown to what a batch really holds -- one
-                 * per possible line is 1 KB x max_lines, hundreds of MB per batch for a narrow cohort in 256 MB windows */
-                if (!b->mtab) { b->multi_cap = m < 4096 ? m : 4096; b->mtab = (int32_t *)malloc(sizeof(int32_t) * 256 * (size_t)b->multi_cap); if (!b->mtab) { rc = HPGV_ERR_NOMEM; break; } }
-                b->n_multi = b->multi_cap;
-                const int mend = tool == RUN_STATS && b->n_cerr > 0;
-                const size_t gm = (size_t)m * (size_t)b->n_groups;
-                rc = hpgv_stats_text_groups(g_ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status, b->c8, b->hw, b->hw + m,
-                                            tool == RUN_STATS ? b->smiss : NULL, b->midx, b->mtab, &b->n_multi, mend ? b->merr : NULL, mend ? b->cerr : NULL,
-                                            b->n_groups ? b->gc8 : NULL, b->n_groups ? b->ghw : NULL, b->n_groups ? b->ghw + gm : NULL);
-                if (!rc && b->n_lines <= b->max_lines && b->n_multi > b->multi_cap) {      /* more multi-allelic lines than tables: again, with room */
-                    free(b->mtab);
-                    b->multi_cap = b->n_multi + b->n_multi / 8 + 16;
-                    if (b->multi_cap > b->max_lines) b->multi_cap = b->max_lines;
-                    b->mtab = (int32_t *)malloc(sizeof(int32_t) * 256 * (size_t)b->multi_cap);
-                    if (!b->mtab) { rc = HPGV_ERR_NOMEM; break; }
-                    continue;
-                }
-                break;
-            }
-            case RUN_FILTER: case RUN_SPLIT:                       /* then the lines partitioned on the device (below) */
-                what = tool == RUN_FILTER ? "hpgv_filter_text / hpgv_text_partition" : "hpgv_filter_text / hpgv_text_multisplit";
-                rc = hpgv_filter_text(g_ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status); break;
-            case RUN_VCF2EPI: what = "hpgv_epi_dataset_text";
-                rc = hpgv_epi_dataset_text(g_ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status, b->rows); break;
-            case RUN_TDT: what = "hpgv_tdt_text";
-                rc = hpgv_tdt_text(g_ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status,
-                                   b->ints, b->ints + m, b->dbl, b->dbl + m, b->dbl + 2 * m); break;
-            case RUN_TDT_PERM: what = "hpgv_tdt_perm_text";
-                rc = hpgv_tdt_perm_text(g_ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status,
-                                        b->ints, b->ints + m, b->dbl, b->dbl + m, b->dbl + 2 * m, b->n_ge, b->bmax); break;
-            case RUN_CHISQ: case RUN_FISHER:
-                if (P->run->clump) {                     /* the same call, which also leaves the batch's candidate rows (p <= p2) */
-                    what = "hpgv_assoc_select_text";
-                    rc = hpgv_assoc_select_text(g_ctx, tool, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status,
-                                                b->ints, b->ints + m, b->ints + 2 * m, b->ints + 3 * m,
-                                                b->dbl, tool == RUN_CHISQ ? b->dbl + m : NULL, b->dbl + 2 * m,
-                                                P->run->clump->p2, b->sel, b->crows, (size_t)P->run->n_samples, b->crows_cap, &b->n_sel);
-                    if (!rc && b->n_lines <= b->max_lines && b->n_sel > b->crows_cap) {      /* more candidates than rows: again, with room */
-                        free(b->crows);
-                        b->crows_cap = b->n_sel + b->n_sel / 8 + 16;
-                        b->crows = (uint8_t *)malloc((size_t)b->crows_cap * (size_t)(P->run->n_samples > 0 ? P->run->n_samples : 1));
-                        if (!b->crows) { b->crows_cap = 0; rc = HPGV_ERR_NOMEM; break; }
-                        continue;
-                    }
-                    break;
-                }
-                what = "hpgv_assoc_text";
-                rc = hpgv_assoc_text(g_ctx, tool, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status,
-                                     b->ints, b->ints + m, b->ints + 2 * m, b->ints + 3 * m,
-                                     b->dbl, tool == RUN_CHISQ ? b->dbl + m : NULL, b->dbl + 2 * m); break;
-            case RUN_CHISQ_PERM: what = "hpgv_assoc_perm_text";
-                rc = hpgv_assoc_perm_text(g_ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status,
-                                          b->ints, b->ints + m, b->ints + 2 * m, b->ints + 3 * m,
-                                          b->dbl, b->dbl + m, b->dbl + 2 * m, b->n_ge, b->bmax); break;
-            case RUN_MODEL: case RUN_MODEL_PERM: what = "hpgv_assoc_model_text";
-                rc = hpgv_assoc_model_text(g_ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status,
-                                           b->ints, b->dbl, b->dbl + 5 * (size_t)m, tool == RUN_MODEL_PERM ? b->n_ge : NULL, tool == RUN_MODEL_PERM ? b->bmax : NULL); break;
-            }
+            int again = 0;
+            rc = engine_call(P->run, b, &what, &again);
+            if (again) continue;
             if (rc || b->n_lines <= b->max_lines) break;
             free(b->mtab); b->mtab = NULL;
             if (run_batch_reserve(b, b->n_lines)) { rc = HPGV_ERR_NOMEM; break; }
@@ -168,197 +180,6 @@ static void *pipe_engine(void *v) {
     }
 }
 
-/* ---- the permutation tools: the records of a written batch kept for <out>.mperm, and that file ---------------------- */
-static int run_perm_add(run_t *R, const run_batch_t *b) {
-    run_perm_t *M = R->PM;
-    const int n = b->n_lines < b->max_lines ? b->n_lines : b->max_lines, m = b->max_lines;
-    for (int i = 0; i < n; i++) {
-        if (!record_passes(b, i)) continue;
-        if (M->n == M->cap) {
-            const size_t cap = M->cap ? M->cap * 2 : 4096;
-            double *t = (double *)realloc(M->t_obs, cap * sizeof *t);
-            if (t) M->t_obs = t;
-            int32_t *g = (int32_t *)realloc(M->n_ge, cap * sizeof *g);
-            if (g) M->n_ge = g;
-            size_t *h = (size_t *)realloc(M->head, cap * sizeof *h);
-            if (h) M->head = h;
-            if (!t || !g || !h) return 1;
-            M->cap = cap;
-        }
-        const uint32_t *fo = b->field_off + 10 * (size_t)i;
-        const char *l = b->text + b->line_off[i];
-        const int lc = (int)(fo[1] - 1 - fo[0]), li = (int)(fo[3] - 1 - fo[2]);
-        const size_t need = (size_t)lc + (size_t)li + 32;
-        if (M->heads_len + need > M->heads_cap) {
-            const size_t cap = (M->heads_cap ? M->heads_cap * 2 : (size_t)1 << 16) + need;
-            char *h = (char *)realloc(M->heads, cap);
-            if (!h) return 1;
-            M->heads = h; M->heads_cap = cap;
-        }
-        M->head[M->n] = M->heads_len;                    /* CHR, POS as the result file prints it, ID */
-        M->heads_len += (size_t)snprintf(M->heads + M->heads_len, need, "%.*s\t%ld\t%.*s", lc, l + fo[0], atol(l + fo[1]), li, l + fo[2]) + 1;
-        M->t_obs[M->n] = R->tool == RUN_MODEL_PERM ? b->dbl[5 * (size_t)i + HPGV_MODEL_TREND] : b->dbl[m + i];
-        if (R->tool == RUN_TDT_PERM && M->t_obs[M->n] < 0) M->t_obs[M->n] = NAN;      /* chi-square -1: nothing transmitted, no statistic */
-        M->n_ge[M->n] = b->n_ge[i];
-        M->n++;
-    }
-    return 0;
-}
-
-static int run_perm_write(run_t *R, const char *out_path) {
-    run_perm_t *M = R->PM;
-    double *emp = (double *)malloc(sizeof(double) * 2 * (M->n + 1));
-    char *path = (char *)malloc(strlen(out_path) + 8);
-    int rc = emp && path ? HPGV_OK : HPGV_ERR_NOMEM;
-    if (!rc && (rc = hpgv_perm_pvalues(M->t_obs, (int)M->n, M->n_ge, M->tmax, R->n_perms, emp, emp + M->n))) snprintf(g_err, sizeof g_err, "hpgv_perm_pvalues failed (%d)", rc);
-    FILE *f = NULL;
-    if (!rc) {
-        sprintf(path, "%s.mperm", out_path);
-        if (!(f = fopen(path, "wb"))) { snprintf(g_err, sizeof g_err, "cannot create %s", path); rc = HPGV_ERR_INVALID; }
-    }
-    if (!rc) {
-        setvbuf(f, NULL, _IOFBF, 1u << 20);
-        fputs("#CHR\tPOS\tID\tEMP1\tEMP2\n", f);
-        char num[2][320];
-        for (size_t i = 0; i < M->n; i++) {
-            hpgv_host_format_f6(emp[i], num[0]); hpgv_host_format_f6(emp[M->n + i], num[1]);
-            fprintf(f, "%s\t%s\t%s\n", M->heads + M->head[i], num[0], num[1]);
-        }
-        if (fclose(f) != 0) { snprintf(g_err, sizeof g_err, "cannot write %s", path); rc = HPGV_ERR_INVALID; }
-        /* the same order as the result file: by chromosome and position (a file in order as written is left alone) */
-        else if (hpgv_host_sort_output_file(path)) fprintf(stderr, "WARN: %s could not be sorted by chromosome and position\n", path);
-    }
-    free(emp); free(path);
-    return rc;
-}
-
-/* ---- clumping: the candidates of a written batch kept for <out>.clumped, and that file ------------------------------------- */
-static int run_clump_add(run_t *R, const run_batch_t *b) {
-    run_clump_t *M = R->CL;
-    const int n = b->n_lines < b->max_lines ? b->n_lines : b->max_lines, m = b->max_lines;
-    const size_t ns = (size_t)R->n_samples;
-    for (int i = 0; i < n; i++) {
-        if (b->sel[i] < 0 || !record_passes(b, i)) continue;       /* (a candidate that only a host-side field filter drops leaves the store here) */
-        if (M->n == M->cap) {
-            const size_t cap = M->cap ? M->cap * 2 : 1024;
-            uint8_t *r = (uint8_t *)realloc(M->rows, cap * (ns ? ns : 1));
-            if (r) M->rows = r;
-            double *p = (double *)realloc(M->p, cap * sizeof *p);
-            if (p) M->p = p;
-            int32_t *c = (int32_t *)realloc(M->chrom, cap * sizeof *c);
-            if (c) M->chrom = c;
-            uint32_t *q = (uint32_t *)realloc(M->pos, cap * sizeof *q);
-            if (q) M->pos = q;
-            size_t *h = (size_t *)realloc(M->head, cap * sizeof *h);
-            if (h) M->head = h;
-            if (!r || !p || !c || !q || !h) return 1;
-            M->cap = cap;
-        }
-        const uint32_t *fo = b->field_off + 10 * (size_t)i;
-        const char *l = b->text + b->line_off[i];
-        const int lc = (int)(fo[1] - 1 - fo[0]), li = (int)(fo[3] - 1 - fo[2]);
-        const size_t need = (size_t)lc + (size_t)li + 32;
-        if (M->heads_len + need > M->heads_cap) {
-            const size_t cap = (M->heads_cap ? M->heads_cap * 2 : (size_t)1 << 16) + need;
-            char *h = (char *)realloc(M->heads, cap);
-            if (!h) return 1;
-            M->heads = h; M->heads_cap = cap;
-        }
-        int ch = -1;                                     /* chromosomes numbered in order of first appearance (a handful of names) */
-        for (int k = M->n_chroms - 1; k >= 0 && ch < 0; k--) if ((int)strlen(M->chrom_names[k]) == lc && !memcmp(M->chrom_names[k], l + fo[0], (size_t)lc)) ch = k;
-        if (ch < 0) {
-            if (M->n_chroms == M->chrom_cap) {
-                const int cap = M->chrom_cap ? M->chrom_cap * 2 : 32;
-                char **names = (char **)realloc(M->chrom_names, sizeof(char *) * (size_t)cap);
-                if (!names) return 1;
-                M->chrom_names = names; M->chrom_cap = cap;
-            }
-            if (!(M->chrom_names[M->n_chroms] = dupn(l + fo[0], lc))) return 1;
-            ch = M->n_chroms++;
-        }
-        const long pos = atol(l + fo[1]);
-        M->head[M->n] = M->heads_len;                    /* CHR, POS as the result file prints it, ID */
-        M->heads_len += (size_t)snprintf(M->heads + M->heads_len, need, "%.*s\t%ld\t%.*s", lc, l + fo[0], pos, li, l + fo[2]) + 1;
-        memcpy(M->rows + M->n * ns, b->crows + (size_t)b->sel[i] * ns, ns);
-        M->p[M->n] = b->dbl[2 * (size_t)m + (size_t)i];
-        M->chrom[M->n] = ch;
-        M->pos[M->n] = pos < 0 ? 0u : pos > 0xFFFFFFFFl ? 0xFFFFFFFFu : (uint32_t)pos;
-        M->n++;
-    }
-    return 0;
-}
-
-/* one hpgv_ld_edges over the store (a group: on member 0), hpgv_clump, the file */
-static int run_clump_write(run_t *R, const char *out_path) {
-    run_clump_t *M = R->CL;
-    const hpgv_run_clump_options_t *O = R->clump;
-    const size_t n = M->n;
-    int rc = HPGV_OK;
-    if (n > 0x7FFFFFFFu) { snprintf(g_err, sizeof g_err, "%zu candidates: more than one hpgv_ld_edges call takes", n); return HPGV_ERR_UNSUPPORTED; }
-    hpgv_ld_edge *edges = NULL;
-    uint64_t n_edges = 0, cap = (uint64_t)n * 4 + 1024;
-    hpgv_ctx *ctx = hpgv_group_size(g_ctx) > 1 ? hpgv_group_member(g_ctx, 0) : g_ctx;
-    for (int attempt = 0; attempt < 2 && !rc && n > 0; attempt++) {      /* the count exceeds the room: grow and repeat once */
-        free(edges);
-        if (!(edges = (hpgv_ld_edge *)malloc(sizeof *edges * (size_t)cap))) { rc = HPGV_ERR_NOMEM; break; }
-        if ((rc = hpgv_ld_edges(ctx, M->rows, (size_t)R->n_samples, (int)n, O->window, M->chrom, M->pos, O->max_bp, O->min_r2, edges, cap, &n_edges))) {
-            snprintf(g_err, sizeof g_err, "hpgv_ld_edges failed (%d): %s", rc, hpgv_last_error(ctx));
-            break;
-        }
-        if (n_edges <= cap) break;
-        if (attempt == 1) { snprintf(g_err, sizeof g_err, "hpgv_ld_edges: the number of edges grew between two calls"); rc = HPGV_ERR_INVALID; }
-        cap = n_edges;
-    }
-    int32_t *index_of = (int32_t *)malloc(sizeof(int32_t) * (n + 1)), *order = (int32_t *)malloc(sizeof(int32_t) * (n + 1));
-    size_t *first = (size_t *)calloc(n + 2, sizeof(size_t));
-    int32_t *member = (int32_t *)malloc(sizeof(int32_t) * (n + 1));
-    int n_clumps = 0;
-    if (!rc && (!index_of || !order || !first || !member)) rc = HPGV_ERR_NOMEM;
-    if (!rc && (rc = hpgv_clump((int)n, M->p, edges, n_edges, O->p1, index_of, order, &n_clumps))) snprintf(g_err, sizeof g_err, "hpgv_clump failed (%d)", rc);
-    char *path = (char *)malloc(strlen(out_path) + 12);
-    FILE *f = NULL;
-    if (!rc && !path) rc = HPGV_ERR_NOMEM;
-    if (!rc) {
-        sprintf(path, "%s.clumped", out_path);
-        if (!(f = fopen(path, "wb"))) { snprintf(g_err, sizeof g_err, "cannot create %s", path); rc = HPGV_ERR_INVALID; }
-    }
-    if (!rc) {
-        /* the claimed members of every index candidate, in file order: counts, offsets, fill */
-        for (size_t j = 0; j < n; j++) if (index_of[j] >= 0 && (size_t)index_of[j] != j) first[(size_t)index_of[j] + 1]++;
-        for (size_t j = 0; j < n; j++) first[j + 1] += first[j];
-        size_t *fill = (size_t *)malloc(sizeof(size_t) * (n + 1));
-        if (!fill) rc = HPGV_ERR_NOMEM;
-        else {
-            memcpy(fill, first, sizeof(size_t) * n);
-            for (size_t j = 0; j < n; j++) if (index_of[j] >= 0 && (size_t)index_of[j] != j) member[fill[index_of[j]]++] = (int32_t)j;
-            free(fill);
-            setvbuf(f, NULL, _IOFBF, 1u << 20);
-            fputs("#CHR\tPOS\tID\tP\tTOTAL\tSP2\n", f);
-            for (int k = 0; k < n_clumps; k++) {
-                const size_t i = (size_t)order[k], total = first[i + 1] - first[i];
-                fprintf(f, "%s\t%.6e\t%zu\t", M->heads + M->head[i], M->p[i], total);
-                if (!total) fputs("NONE", f);
-                for (size_t q = first[i]; q < first[i + 1]; q++) {
-                    const size_t j = (size_t)member[q];
-                    fprintf(f, "%s%s:%lu", q > first[i] ? "," : "", M->chrom_names[M->chrom[j]], (unsigned long)atol(strchr(M->heads + M->head[j], '\t') + 1));
-                }
-                fputc('\n', f);
-            }
-        }
-        if (fclose(f) != 0 && !rc) { snprintf(g_err, sizeof g_err, "cannot write %s", path); rc = HPGV_ERR_INVALID; }
-    }
-    /* the candidates whose distance window the candidate window cut short: candidate i + window + 1 is still in reach */
-    M->n_clumps = n_clumps; M->n_truncated = 0;
-    for (size_t i = 0; !rc && i + (size_t)O->window + 1 < n; i++) {
-        const size_t j = i + (size_t)O->window + 1;
-        const long long d = (long long)M->pos[j] - (long long)M->pos[i];
-        if (M->chrom[j] == M->chrom[i] && (O->max_bp < 0 || (d < 0 ? -d : d) <= O->max_bp)) M->n_truncated++;
-    }
-    if (!rc && M->n_truncated) fprintf(stderr, "WARN: the window of %d candidates cut the distance window of %ld candidates short\n", O->window, M->n_truncated);
-    free(edges); free(index_of); free(order); free(first); free(member); free(path);
-    return rc;
-}
-
 /* ---- one run, stage by stage: input (in run_file), cohort, outputs, pipeline, finish ---------------------- */
 /* the pedigree: the trios of the PED whose three members are VCF columns (every row with both parents named, whatever its
  * phenotype).  For stats, installed when there is one and their child columns kept; for the Mendelian filter, always */
@@ -382,6 +203,15 @@ static int set_trios(run_t *R, const sample_ids_t *ids, int for_stats) {
     free(tf); free(tm); free(ts);
     if (for_stats) { R->trio_child = tc; R->n_trios = nt; } else free(tc);
     return rc;
+}
+
+/* the condition of every VCF column by the PED's PHENO (a column without a PED row: HPGV_COND_OTHER), malloc'ed, or NULL without
+ * memory; *matched: the PED rows that are columns */
+static uint8_t *cohort_conditions(const run_t *R, const sample_ids_t *ids, int *matched) {
+    uint8_t *cond = (uint8_t *)malloc((size_t)R->n_samples + 1);
+    for (int j = 0; cond && j < R->n_samples; j++) cond[j] = HPGV_COND_OTHER;
+    for (int i = 0; cond && i < R->ped.n; i++) { const int j = sample_ids_get(ids, R->ped.iid[i]); if (j >= 0) { cond[j] = (uint8_t)R->ped.pheno[i]; (*matched)++; } }
+    return cond;
 }
 
 /* the tool's cohort on the device(s), PED rows looked up by sample name (associate_samples_and_positions +
@@ -468,10 +298,9 @@ static int run_cohort(run_t *R, const char *vcf_path, const char *ped_path) {
         break;
     }
     case RUN_CHISQ: case RUN_CHISQ_PERM: case RUN_FISHER: case RUN_VCF2EPI: case RUN_MODEL: case RUN_MODEL_PERM: {
-        uint8_t *cond = (uint8_t *)malloc((size_t)n_samples + 1);
-        for (int j = 0; j < n_samples; j++) cond[j] = HPGV_COND_OTHER;
         int matched = 0;
-        for (int i = 0; i < ped->n; i++) { int j = sample_ids_get(ids, ped->iid[i]); if (j >= 0) { cond[j] = (uint8_t)ped->pheno[i]; matched++; } }
+        uint8_t *cond = cohort_conditions(R, ids, &matched);
+        if (!cond) { rc = HPGV_ERR_NOMEM; break; }
         if (matched == 0 && n_samples > 0) {             /* assert(individual) of assoc.c:92: a VCF whose samples the PED does not know */
             snprintf(g_err, sizeof g_err, "no sample of %s is a row of %s", vcf_path, ped_path);
             rc = HPGV_ERR_INVALID;
@@ -515,10 +344,9 @@ static int run_cohort(run_t *R, const char *vcf_path, const char *ped_path) {
      * affected, 1 unaffected, as the assoc runner); vcf2epi keeps its own classes */
     if (!rc && rec_filters_inheritance(R->rf)) {
         if (!tool_chisq(R->tool) && !tool_model(R->tool) && R->tool != RUN_FISHER && R->tool != RUN_VCF2EPI) {
-            uint8_t *cond = (uint8_t *)malloc((size_t)n_samples + 1);
+            int matched = 0;
+            uint8_t *cond = cohort_conditions(R, ids, &matched);
             if (!cond) rc = HPGV_ERR_NOMEM;
-            for (int j = 0; cond && j < n_samples; j++) cond[j] = HPGV_COND_OTHER;
-            for (int i = 0; cond && i < ped->n; i++) { const int j = sample_ids_get(ids, ped->iid[i]); if (j >= 0) cond[j] = (uint8_t)ped->pheno[i]; }
             if (!rc && (rc = hpgv_set_cohort(g_ctx, cond, n_samples))) host_fail("hpgv_set_cohort", rc);
             g_assoc_key.set = 0;
             free(cond);
@@ -528,90 +356,6 @@ static int run_cohort(run_t *R, const char *vcf_path, const char *ped_path) {
     }
     sample_ids_free(ids);
     return rc;
-}
-
-/* ---- hpg-var-vcf stats: what the run accumulates besides the per-variant lines (run_stats_t; the report writers live in
- *      hpg-libs, so the two files below are this project's rendering) ---- */
-static void run_stats_add(run_t *run, const run_batch_t *b) {
-    run_stats_t *R = run->RS;
-    for (int j = 0; j < run->n_samples; j++) R->smiss[j] += b->smiss[j];      /* counted over every line of the batch, as get_sample_stats does */
-    for (int t = 0; t < b->n_cerr; t++) R->serr[run->trio_child[t]] += b->cerr[t];
-    const int n = b->n_lines < b->max_lines ? b->n_lines : b->max_lines;
-    for (int i = 0; i < n; i++) {
-        if (!record_passes(b, i)) continue;
-        const uint32_t *fo = b->field_off + 10 * (size_t)i;
-        const char *l = b->text + b->line_off[i];
-        const char *ref = l + fo[3], *alt = l + fo[4];
-        const int lr = (int)(fo[4] - 1 - fo[3]), la = (int)(fo[5] - 1 - fo[4]);
-        vcounts_t v;
-        record_counts(b, i, alt, la, &v);
-        R->variants++;
-        if (v.na > 2) R->multiallelic++; else R->biallelic++;
-        int snp = lr == 1, n_alt = 0;                      /* a SNP: REF and every ALT allele one base long */
-        for (int k = 0, start = 0; k <= la; k++)
-            if (k == la || alt[k] == ',') { n_alt++; if (k - start != 1 || alt[start] == '.') snp = 0; start = k + 1; }
-        if (snp) {
-            R->snps++;
-            if (n_alt == 1) {
-                const char a = (char)(ref[0] & ~0x20), c = (char)(alt[0] & ~0x20);
-                const int purine_a = a == 'A' || a == 'G', purine_c = c == 'A' || c == 'G';
-                if (purine_a == purine_c) R->transitions++; else R->transversions++;
-            }
-        } else if (!(la == 1 && alt[0] == '.')) R->indels++;
-        if (fo[6] != 0xFFFFFFFFu) {
-            const char *q = l + fo[5];
-            if (*q != '.' && *q != '\t') { R->quality_sum += strtod(q, NULL); R->with_quality++; }
-            const char *f = l + fo[6];
-            const int lf = fo[7] != 0xFFFFFFFFu ? (int)(fo[7] - 1 - fo[6]) : 0;
-            if (lf == 4 && !strncmp(f, "PASS", 4)) R->pass++;
-        }
-    }
-}
-
-static int run_stats_write(const run_t *run, const char *prefix) {
-    const run_stats_t *R = run->RS;
-    const int n_samples = run->n_samples;
-    char *path = (char *)malloc(strlen(prefix) + 32);
-    if (!path) return HPGV_ERR_NOMEM;
-    sprintf(path, "%s.stats-samples", prefix);
-    FILE *f = fopen(path, "w");
-    if (!f) goto fail;
-    fprintf(f, "#SAMPLE\tMISS_GT\tMEND_ER\n");
-    for (int j = 0; j < n_samples; j++) fprintf(f, "%s\t%ld\t%ld\n", run->names[j], R->smiss[j], R->serr[j]);
-    fclose(f);
-    sprintf(path, "%s.stats-summary", prefix);
-    if (!(f = fopen(path, "w"))) goto fail;
-    fprintf(f, "Number of variants = %ld\nNumber of samples = %d\nNumber of biallelic variants = %ld\nNumber of multiallelic variants = %ld\n\n",
-            run->written, n_samples, R->biallelic, R->multiallelic);
-    fprintf(f, "Number of SNP = %ld\nNumber of indels = %ld\n\n", R->snps, R->indels);
-    fprintf(f, "Number of transitions = %ld\nNumber of transversions = %ld\nTi/TV ratio = %.4f\n\n", R->transitions, R->transversions,
-            R->transversions ? (double)R->transitions / (double)R->transversions : 0.0);
-    fprintf(f, "Percentage of PASS = %.2f%%\nAverage quality = %.2f\n", R->variants ? 100.0 * (double)R->pass / (double)R->variants : 0.0,
-            R->with_quality ? R->quality_sum / (double)R->with_quality : 0.0);
-    fclose(f);
-    free(path);
-    return HPGV_OK;
-fail:
-    snprintf(g_err, sizeof g_err, "cannot create %s", path); free(path); return HPGV_ERR_INVALID;
-}
-
-/* the per-phenotype lines of a batch: the counters of the first two alleles within the group (variant_stats_t per
- * phenotype, stats_runner.c:319-323) */
-static void write_group_lines(FILE **gfd, const run_batch_t *b) {
-    const int n = b->n_lines < b->max_lines ? b->n_lines : b->max_lines, m = b->max_lines;
-    for (int g = 0; g < b->n_groups; g++)
-        for (int i = 0; i < n; i++) {
-            if (!record_passes(b, i)) continue;
-            const uint32_t *fo = b->field_off + 10 * (size_t)i;
-            const char *l = b->text + b->line_off[i];
-            const int32_t *c = b->gc8 + ((size_t)g * m + (size_t)i) * 8;
-            const int ta = c[6] + c[7];
-            const float f0 = ta ? (float)c[6] / ta : 0.0f, f1 = ta ? (float)c[7] / ta : 0.0f;
-            fprintf(gfd[g], "%.*s\t%ld\t%.*s\t%.*s\t%d,%d\t%.4f,%.4f\t0/0:%d,0/1:%d,1/1:%d,./.:%d\t%d\t%d\t%.4f\t%.6g\t%.6g\n",
-                    (int)(fo[1] - 1 - fo[0]), l + fo[0], atol(l + fo[1]), (int)(fo[4] - 1 - fo[3]), l + fo[3], (int)(fo[5] - 1 - fo[4]), l + fo[4],
-                    c[6], c[7], f0, f1, c[0], c[1] + c[2], c[3], c[4], c[5], c[4], f0 < f1 ? f0 : f1,
-                    b->ghw[(size_t)g * m + (size_t)i], b->ghw[((size_t)b->n_groups + (size_t)g) * m + (size_t)i]);
-        }
 }
 
 /* <prefix><suffix> created for writing; *path keeps its name for the messages */
@@ -626,12 +370,7 @@ static int create_out(FILE **f, char **path, const char *prefix, const char *suf
 /* the tool's output files (split: its files as the records come).  The filter tool's .rejected is created empty without
  * save_rejected (filter_runner.c:63-68); stats: one file per phenotype (stats_runner.c:267-297), and its accumulator */
 static int run_outputs(run_t *R, const char *out_path) {
-    if (R->clump && !(R->CL = (run_clump_t *)calloc(1, sizeof *R->CL))) return HPGV_ERR_NOMEM;
-    if (tool_perm(R->tool)) {
-        R->PM = (run_perm_t *)calloc(1, sizeof *R->PM);
-        if (R->PM) R->PM->tmax = (double *)calloc((size_t)R->n_perms, sizeof(double));      /* 0: the identity of the merge */
-        if (!R->PM || !R->PM->tmax) return HPGV_ERR_NOMEM;
-    }
+    if ((R->clump && run_clump_new(R)) || (tool_perm(R->tool) && run_perm_new(R))) return HPGV_ERR_NOMEM;
     const char *suffix = R->tool == RUN_STATS ? ".stats-variants" : R->tool == RUN_FILTER ? (R->out_bgzf ? ".filtered.gz" : ".filtered") : "";
     int rc = R->tool == RUN_SPLIT ? HPGV_OK : create_out(&R->out, &R->path, out_path, suffix);
     if (!rc && R->tool == RUN_FILTER) rc = create_out(&R->out_rej, &R->path_rej, out_path, R->out_bgzf ? ".rejected.gz" : ".rejected");
@@ -647,9 +386,7 @@ static int run_outputs(run_t *R, const char *out_path) {
         free(gp);
         if (!R->gfd) return HPGV_ERR_NOMEM;
     }
-    run_stats_t *RS = R->RS = rc ? NULL : (run_stats_t *)calloc(1, sizeof *RS);
-    if (RS) { RS->smiss = (long *)calloc((size_t)R->n_samples + 1, sizeof(long)); RS->serr = (long *)calloc((size_t)R->n_samples + 1, sizeof(long)); }
-    return rc ? rc : !RS || !RS->smiss || !RS->serr ? HPGV_ERR_NOMEM : HPGV_OK;
+    return rc ? rc : run_stats_new(R);
 }
 
 /* the output files' headers, once the batches are allocated */
@@ -775,7 +512,7 @@ static int run_pipeline(run_t *R, size_t batch_bytes) {
                 for (int i = 0; i < b->n_lines; i++) if (record_passes(b, i)) R->written++;
                 if (tool_perm(R->tool) && !bad && run_perm_add(R, b)) bad = "out of memory for the permutation results";
                 if (R->CL && !bad && run_clump_add(R, b)) bad = "out of memory for the clumping candidates";
-                if (R->tool == RUN_STATS && !bad) { run_stats_add(R, b); if (R->gfd) write_group_lines(R->gfd, b); }      /* (the group files: by this thread) */
+                if (R->tool == RUN_STATS && !bad) run_stats_add(R, b);      /* (and the group files' lines: by this thread) */
                 break;
             }
             fmt_set ^= use_fw;
@@ -832,15 +569,14 @@ static int run_finish(run_t *R, int rc, const char *out_path) {
     if (tool_perm(R->tool)) {
         if (!rc && R->PM) rc = run_perm_write(R, out_path);
         if (g_ctx) (void)(R->tool == RUN_TDT_PERM ? hpgv_set_tdt_flips(g_ctx, NULL, 0) : hpgv_set_perm_labels(g_ctx, NULL, 0));
-        if (R->PM) { free(R->PM->tmax); free(R->PM->t_obs); free(R->PM->n_ge); free(R->PM->head); free(R->PM->heads); free(R->PM); R->PM = NULL; }
+        run_perm_free(R);
     }
     if (R->CL) {
-        run_clump_t *M = R->CL;
         if (!rc) rc = run_clump_write(R, out_path);
-        for (int k = 0; k < M->n_chroms; k++) free(M->chrom_names[k]);
-        free(M->rows); free(M->p); free(M->chrom); free(M->pos); free(M->head); free(M->heads); free(M->chrom_names);
+        R->n_clumps = R->CL->n_clumps; R->n_truncated = R->CL->n_truncated;      /* for hpgv_run_assoc_clump, past the store */
+        run_clump_free(R);
     }
-    if (R->RS) { free(R->RS->smiss); free(R->RS->serr); free(R->RS); }
+    run_stats_free(R);
     free(R->ord.last); free(R->gfd); free(R->group_names); free(R->path); free(R->path_rej); free(R->trio_child);
     const hpgv_run_filters_t *f = &R->filters;
     if (f->min_maf >= 0.0 || f->max_missing >= 0.0 || f->max_mendel_errors >= 0) (void)hpgv_set_text_filters(g_ctx, -1.0, -1.0, -1);
@@ -950,11 +686,17 @@ int hpgv_run_assoc(const char *vcf_path, const char *ped_path, const char *out_p
     return run_file(&(run_t){ .tool = (run_tool_t)task, .filters = g_filters }, vcf_path, ped_path, out_path, batch_bytes, n_variants_out);
 }
 
+/* how the runs that check their arguments open: the count zeroed, then none of the paths (or the options) NULL -- msg: the run's own wording */
+static int run_args(long *n_variants_out, int all_given, const char *msg) {
+    if (n_variants_out) *n_variants_out = 0;
+    if (!all_given) snprintf(g_err, sizeof g_err, "%s", msg);
+    return !all_given;
+}
+
 /* the chi-square run with max(T) label permutation: hpgv_run_assoc(..., CHI_SQUARE, ...)'s file and <out_path>.mperm */
 int hpgv_run_assoc_perm(const char *vcf_path, const char *ped_path, const char *out_path, int n_perms, uint64_t seed,
                         size_t batch_bytes, long *n_variants_out) {
-    if (n_variants_out) *n_variants_out = 0;
-    if (!vcf_path || !ped_path || !out_path) { snprintf(g_err, sizeof g_err, "vcf_path, ped_path and out_path must not be NULL"); return HPGV_ERR_INVALID; }
+    if (run_args(n_variants_out, vcf_path && ped_path && out_path, "vcf_path, ped_path and out_path must not be NULL")) return HPGV_ERR_INVALID;
     if (n_perms < 1) { snprintf(g_err, sizeof g_err, "n_perms must be at least 1"); return HPGV_ERR_INVALID; }
     return run_file(&(run_t){ .tool = RUN_CHISQ_PERM, .filters = g_filters, .n_perms = n_perms, .perm_seed = seed }, vcf_path, ped_path, out_path, batch_bytes, n_variants_out);
 }
@@ -963,10 +705,9 @@ int hpgv_run_assoc_perm(const char *vcf_path, const char *ped_path, const char *
 int hpgv_run_assoc_clump(const char *vcf_path, const char *ped_path, const char *out_path, enum ASSOC_task task,
                          const hpgv_run_clump_options_t *opt, size_t batch_bytes, long *n_variants_out,
                          long *n_clumps_out, long *n_truncated_out) {
-    if (n_variants_out) *n_variants_out = 0;
     if (n_clumps_out) *n_clumps_out = 0;
     if (n_truncated_out) *n_truncated_out = 0;
-    if (!vcf_path || !ped_path || !out_path || !opt) { snprintf(g_err, sizeof g_err, "vcf_path, ped_path, out_path and the options must not be NULL"); return HPGV_ERR_INVALID; }
+    if (run_args(n_variants_out, vcf_path && ped_path && out_path && opt, "vcf_path, ped_path, out_path and the options must not be NULL")) return HPGV_ERR_INVALID;
     if (task != CHI_SQUARE && task != FISHER) { snprintf(g_err, sizeof g_err, "task must be CHI_SQUARE or FISHER"); return HPGV_ERR_INVALID; }
     if (!(opt->p1 > 0.0 && opt->p1 <= 1.0) || !(opt->p2 > 0.0 && opt->p2 <= 1.0) || !(opt->p1 <= opt->p2)) {      /* (a NaN fails every comparison) */
         snprintf(g_err, sizeof g_err, "clumping needs 0 < p1 <= p2 <= 1"); return HPGV_ERR_INVALID;
@@ -975,11 +716,8 @@ int hpgv_run_assoc_clump(const char *vcf_path, const char *ped_path, const char 
     if (opt->window < 1 || opt->window > HPGV_LD_MAX_WINDOW) { snprintf(g_err, sizeof g_err, "window %d: 1 .. %d candidates", opt->window, HPGV_LD_MAX_WINDOW); return HPGV_ERR_INVALID; }
     run_t R = { .tool = (run_tool_t)task, .filters = g_filters, .clump = opt };
     const int rc = run_file(&R, vcf_path, ped_path, out_path, batch_bytes, n_variants_out);
-    if (R.CL) {
-        if (n_clumps_out) *n_clumps_out = R.CL->n_clumps;
-        if (n_truncated_out) *n_truncated_out = R.CL->n_truncated;
-        free(R.CL);
-    }
+    if (n_clumps_out) *n_clumps_out = R.n_clumps;
+    if (n_truncated_out) *n_truncated_out = R.n_truncated;
     return rc;
 }
 
@@ -987,8 +725,7 @@ int hpgv_run_assoc_clump(const char *vcf_path, const char *ped_path, const char 
  * trend statistic */
 int hpgv_run_assoc_model(const char *vcf_path, const char *ped_path, const char *out_path, int n_perms, uint64_t seed,
                          size_t batch_bytes, long *n_variants_out) {
-    if (n_variants_out) *n_variants_out = 0;
-    if (!vcf_path || !ped_path || !out_path) { snprintf(g_err, sizeof g_err, "vcf_path, ped_path and out_path must not be NULL"); return HPGV_ERR_INVALID; }
+    if (run_args(n_variants_out, vcf_path && ped_path && out_path, "vcf_path, ped_path and out_path must not be NULL")) return HPGV_ERR_INVALID;
     if (n_perms < 0) { snprintf(g_err, sizeof g_err, "n_perms must not be negative"); return HPGV_ERR_INVALID; }
     return run_file(&(run_t){ .tool = n_perms ? RUN_MODEL_PERM : RUN_MODEL, .filters = g_filters, .n_perms = n_perms, .perm_seed = seed }, vcf_path, ped_path, out_path, batch_bytes, n_variants_out);
 }
@@ -1000,8 +737,7 @@ int hpgv_run_tdt(const char *vcf_path, const char *ped_path, const char *out_pat
 /* the TDT run with max(T) family flips: hpgv_run_tdt's file and <out_path>.mperm */
 int hpgv_run_tdt_perm(const char *vcf_path, const char *ped_path, const char *out_path, int n_perms, uint64_t seed,
                       size_t batch_bytes, long *n_variants_out) {
-    if (n_variants_out) *n_variants_out = 0;
-    if (!vcf_path || !ped_path || !out_path) { snprintf(g_err, sizeof g_err, "vcf_path, ped_path and out_path must not be NULL"); return HPGV_ERR_INVALID; }
+    if (run_args(n_variants_out, vcf_path && ped_path && out_path, "vcf_path, ped_path and out_path must not be NULL")) return HPGV_ERR_INVALID;
     if (n_perms < 1) { snprintf(g_err, sizeof g_err, "n_perms must be at least 1"); return HPGV_ERR_INVALID; }
     return run_file(&(run_t){ .tool = RUN_TDT_PERM, .filters = g_filters, .n_perms = n_perms, .perm_seed = seed }, vcf_path, ped_path, out_path, batch_bytes, n_variants_out);
 }

@@ -1,0 +1,322 @@
+/* host_sideout.c -- what a file run keeps beside its result file, and the files written from it at the end: the permutation
+ * results (<out>.mperm), the clumping candidates (<out>.clumped), the stats report.  Each is a run_*_t of the run with four
+ * functions: _new (run_outputs), _add (the writer loop, per written batch), _write and _free (run_finish).
+ * Part of libhpgv_host.so (see hpgv_host_internal.h for the map of its units). */
+#include "hpgv_host_internal.h"
+
+/* the array at *arr (of any element type) grown to cap elements of `size` bytes; 0, and the array as it was, when memory runs out */
+static int grown(void *arr, size_t cap, size_t size) {
+    void *p;
+    memcpy(&p, arr, sizeof p);                           /* (the pointer read and written as bytes: arr is a double **, an int32_t ** ...) */
+    if (!(p = realloc(p, cap * size))) return 0;
+    memcpy(arr, &p, sizeof p);
+    return 1;
+}
+
+/* ---- the record heads: "CHR\tPOS\tID" of every kept record, an offset per record into one arena ---------------------- */
+int rec_heads_init(rec_heads_t *H, size_t first_cap) {
+    memset(H, 0, sizeof *H);
+    H->cap = grown(&H->head, first_cap, sizeof *H->head) ? first_cap : 0;
+    return !H->cap;
+}
+
+int rec_heads_add(rec_heads_t *H, const char *chr, int lc, long pos, const char *id, int li) {
+    if (H->n == H->cap) {
+        const size_t cap = H->cap ? H->cap * 2 : 1;
+        if (!grown(&H->head, cap, sizeof *H->head)) return 1;
+        H->cap = cap;
+    }
+    const size_t need = (size_t)lc + (size_t)li + 32;
+    if (H->heads_len + need > H->heads_cap) {
+        const size_t cap = (H->heads_cap ? H->heads_cap * 2 : (size_t)1 << 16) + need;
+        if (!grown(&H->heads, cap, 1)) return 1;
+        H->heads_cap = cap;
+    }
+    H->head[H->n++] = H->heads_len;                      /* CHR, POS as the result file prints it, ID */
+    H->heads_len += (size_t)snprintf(H->heads + H->heads_len, need, "%.*s\t%ld\t%.*s", lc, chr, pos, li, id) + 1;
+    return 0;
+}
+
+const char *rec_heads_get(const rec_heads_t *H, size_t i) { return H->heads + H->head[i]; }
+void rec_heads_free(rec_heads_t *H) { free(H->head); free(H->heads); memset(H, 0, sizeof *H); }
+
+/* CHR, POS and ID of line i of a batch, as rec_heads_add takes them */
+typedef struct { const char *chr, *id; int lc, li; long pos; } line_head_t;
+static line_head_t line_head(const run_batch_t *b, int i) {
+    const uint32_t *fo = b->field_off + 10 * (size_t)i;
+    const char *l = b->text + b->line_off[i];
+    return (line_head_t){ l + fo[0], l + fo[2], (int)(fo[1] - 1 - fo[0]), (int)(fo[3] - 1 - fo[2]), atol(l + fo[1]) };
+}
+
+/* ---- the permutation tools: the records of a written batch kept for <out>.mperm, and that file ---------------------- */
+static int run_perm_room(run_perm_t *M) {               /* the parallel arrays as long as the heads' offsets; 0: no memory */
+    return grown(&M->t_obs, M->H.cap, sizeof *M->t_obs) & grown(&M->n_ge, M->H.cap, sizeof *M->n_ge);
+}
+
+int run_perm_new(run_t *R) {
+    run_perm_t *M = R->PM = (run_perm_t *)calloc(1, sizeof *M);
+    if (M) M->tmax = (double *)calloc((size_t)R->n_perms, sizeof(double));      /* 0: the identity of the merge */
+    return M && M->tmax && !rec_heads_init(&M->H, 4096) && run_perm_room(M) ? HPGV_OK : HPGV_ERR_NOMEM;
+}
+
+int run_perm_add(run_t *R, const run_batch_t *b) {
+    run_perm_t *M = R->PM;
+    const int n = b->n_lines < b->max_lines ? b->n_lines : b->max_lines, m = b->max_lines;
+    for (int i = 0; i < n; i++) {
+        if (!record_passes(b, i)) continue;
+        const line_head_t h = line_head(b, i);
+        const size_t k = M->H.n, cap = M->H.cap;
+        if (rec_heads_add(&M->H, h.chr, h.lc, h.pos, h.id, h.li) || (M->H.cap != cap && !run_perm_room(M))) return 1;
+        M->t_obs[k] = R->tool == RUN_MODEL_PERM ? b->dbl[5 * (size_t)i + HPGV_MODEL_TREND] : b->dbl[m + i];
+        if (R->tool == RUN_TDT_PERM && M->t_obs[k] < 0) M->t_obs[k] = NAN;      /* chi-square -1: nothing transmitted, no statistic */
+        M->n_ge[k] = b->n_ge[i];
+    }
+    return 0;
+}
+
+int run_perm_write(run_t *R, const char *out_path) {
+    run_perm_t *M = R->PM;
+    const size_t n = M->H.n;
+    double *emp = (double *)malloc(sizeof(double) * 2 * (n + 1));
+    char *path = (char *)malloc(strlen(out_path) + 8);
+    int rc = emp && path ? HPGV_OK : HPGV_ERR_NOMEM;
+    if (!rc && (rc = hpgv_perm_pvalues(M->t_obs, (int)n, M->n_ge, M->tmax, R->n_perms, emp, emp + n))) snprintf(g_err, sizeof g_err, "hpgv_perm_pvalues failed (%d)", rc);
+    FILE *f = NULL;
+    if (!rc) {
+        sprintf(path, "%s.mperm", out_path);
+        if (!(f = fopen(path, "wb"))) { snprintf(g_err, sizeof g_err, "cannot create %s", path); rc = HPGV_ERR_INVALID; }
+    }
+    if (!rc) {
+        setvbuf(f, NULL, _IOFBF, 1u << 20);
+        fputs("#CHR\tPOS\tID\tEMP1\tEMP2\n", f);
+        char num[2][320];
+        for (size_t i = 0; i < n; i++) {
+            hpgv_host_format_f6(emp[i], num[0]); hpgv_host_format_f6(emp[n + i], num[1]);
+            fprintf(f, "%s\t%s\t%s\n", rec_heads_get(&M->H, i), num[0], num[1]);
+        }
+        if (fclose(f) != 0) { snprintf(g_err, sizeof g_err, "cannot write %s", path); rc = HPGV_ERR_INVALID; }
+        /* the same order as the result file: by chromosome and position (a file in order as written is left alone) */
+        else if (hpgv_host_sort_output_file(path)) fprintf(stderr, "WARN: %s could not be sorted by chromosome and position\n", path);
+    }
+    free(emp); free(path);
+    return rc;
+}
+
+void run_perm_free(run_t *R) {
+    run_perm_t *M = R->PM;
+    if (M) { free(M->tmax); free(M->t_obs); free(M->n_ge); rec_heads_free(&M->H); free(M); }
+    R->PM = NULL;
+}
+
+/* ---- clumping: the candidates of a written batch kept for <out>.clumped, and that file ------------------------------------- */
+static int run_clump_room(run_clump_t *M, size_t ns) {   /* the parallel arrays as long as the heads' offsets; 0: no memory */
+    return grown(&M->rows, M->H.cap, ns ? ns : 1) & grown(&M->p, M->H.cap, sizeof *M->p)
+         & grown(&M->chrom, M->H.cap, sizeof *M->chrom) & grown(&M->pos, M->H.cap, sizeof *M->pos);
+}
+
+int run_clump_new(run_t *R) {
+    run_clump_t *M = R->CL = (run_clump_t *)calloc(1, sizeof *M);
+    return M && !rec_heads_init(&M->H, 1024) && run_clump_room(M, (size_t)R->n_samples) ? HPGV_OK : HPGV_ERR_NOMEM;
+}
+
+int run_clump_add(run_t *R, const run_batch_t *b) {
+    run_clump_t *M = R->CL;
+    const int n = b->n_lines < b->max_lines ? b->n_lines : b->max_lines, m = b->max_lines;
+    const size_t ns = (size_t)R->n_samples;
+    for (int i = 0; i < n; i++) {
+        if (b->sel[i] < 0 || !record_passes(b, i)) continue;       /* (a candidate that only a host-side field filter drops leaves the store here) */
+        const line_head_t h = line_head(b, i);
+        int ch = -1;                                     /* chromosomes numbered in order of first appearance (a handful of names) */
+        for (int k = M->n_chroms - 1; k >= 0 && ch < 0; k--) if ((int)strlen(M->chrom_names[k]) == h.lc && !memcmp(M->chrom_names[k], h.chr, (size_t)h.lc)) ch = k;
+        if (ch < 0) {
+            if (M->n_chroms == M->chrom_cap) {
+                const int cap = M->chrom_cap ? M->chrom_cap * 2 : 32;
+                if (!grown(&M->chrom_names, (size_t)cap, sizeof(char *))) return 1;
+                M->chrom_cap = cap;
+            }
+            if (!(M->chrom_names[M->n_chroms] = dupn(h.chr, h.lc))) return 1;
+            ch = M->n_chroms++;
+        }
+        const size_t k = M->H.n, cap = M->H.cap;
+        if (rec_heads_add(&M->H, h.chr, h.lc, h.pos, h.id, h.li) || (M->H.cap != cap && !run_clump_room(M, ns))) return 1;
+        memcpy(M->rows + k * ns, b->crows + (size_t)b->sel[i] * ns, ns);
+        M->p[k] = b->dbl[2 * (size_t)m + (size_t)i];
+        M->chrom[k] = ch;
+        M->pos[k] = h.pos < 0 ? 0u : h.pos > 0xFFFFFFFFl ? 0xFFFFFFFFu : (uint32_t)h.pos;
+    }
+    return 0;
+}
+
+/* one hpgv_ld_edges over the store (a group: on member 0), hpgv_clump, the file */
+int run_clump_write(run_t *R, const char *out_path) {
+    run_clump_t *M = R->CL;
+    const hpgv_run_clump_options_t *O = R->clump;
+    const size_t n = M->H.n;
+    int rc = HPGV_OK;
+    if (n > 0x7FFFFFFFu) { snprintf(g_err, sizeof g_err, "%zu candidates: more than one hpgv_ld_edges call takes", n); return HPGV_ERR_UNSUPPORTED; }
+    hpgv_ld_edge *edges = NULL;
+    uint64_t n_edges = 0, cap = (uint64_t)n * 4 + 1024;
+    hpgv_ctx *ctx = hpgv_group_size(g_ctx) > 1 ? hpgv_group_member(g_ctx, 0) : g_ctx;
+    for (int attempt = 0; attempt < 2 && !rc && n > 0; attempt++) {      /* the count exceeds the room: grow and repeat once */
+        free(edges);
+        if (!(edges = (hpgv_ld_edge *)malloc(sizeof *edges * (size_t)cap))) { rc = HPGV_ERR_NOMEM; break; }
+        if ((rc = hpgv_ld_edges(ctx, M->rows, (size_t)R->n_samples, (int)n, O->window, M->chrom, M->pos, O->max_bp, O->min_r2, edges, cap, &n_edges))) {
+            snprintf(g_err, sizeof g_err, "hpgv_ld_edges failed (%d): %s", rc, hpgv_last_error(ctx));
+            break;
+        }
+        if (n_edges <= cap) break;
+        if (attempt == 1) { snprintf(g_err, sizeof g_err, "hpgv_ld_edges: the number of edges grew between two calls"); rc = HPGV_ERR_INVALID; }
+        cap = n_edges;
+    }
+    int32_t *index_of = (int32_t *)malloc(sizeof(int32_t) * (n + 1)), *order = (int32_t *)malloc(sizeof(int32_t) * (n + 1));
+    size_t *first = (size_t *)calloc(n + 2, sizeof(size_t));
+    int32_t *member = (int32_t *)malloc(sizeof(int32_t) * (n + 1));
+    int n_clumps = 0;
+    if (!rc && (!index_of || !order || !first || !member)) rc = HPGV_ERR_NOMEM;
+    if (!rc && (rc = hpgv_clump((int)n, M->p, edges, n_edges, O->p1, index_of, order, &n_clumps))) snprintf(g_err, sizeof g_err, "hpgv_clump failed (%d)", rc);
+    char *path = (char *)malloc(strlen(out_path) + 12);
+    FILE *f = NULL;
+    if (!rc && !path) rc = HPGV_ERR_NOMEM;
+    if (!rc) {
+        sprintf(path, "%s.clumped", out_path);
+        if (!(f = fopen(path, "wb"))) { snprintf(g_err, sizeof g_err, "cannot create %s", path); rc = HPGV_ERR_INVALID; }
+    }
+    if (!rc) {
+        /* the claimed members of every index candidate, in file order: counts, offsets, fill */
+        for (size_t j = 0; j < n; j++) if (index_of[j] >= 0 && (size_t)index_of[j] != j) first[(size_t)index_of[j] + 1]++;
+        for (size_t j = 0; j < n; j++) first[j + 1] += first[j];
+        size_t *fill = (size_t *)malloc(sizeof(size_t) * (n + 1));
+        if (!fill) rc = HPGV_ERR_NOMEM;
+        else {
+            memcpy(fill, first, sizeof(size_t) * n);
+            for (size_t j = 0; j < n; j++) if (index_of[j] >= 0 && (size_t)index_of[j] != j) member[fill[index_of[j]]++] = (int32_t)j;
+            free(fill);
+            setvbuf(f, NULL, _IOFBF, 1u << 20);
+            fputs("#CHR\tPOS\tID\tP\tTOTAL\tSP2\n", f);
+            for (int k = 0; k < n_clumps; k++) {
+                const size_t i = (size_t)order[k], total = first[i + 1] - first[i];
+                fprintf(f, "%s\t%.6e\t%zu\t", rec_heads_get(&M->H, i), M->p[i], total);
+                if (!total) fputs("NONE", f);
+                for (size_t q = first[i]; q < first[i + 1]; q++) {
+                    const size_t j = (size_t)member[q];
+                    fprintf(f, "%s%s:%lu", q > first[i] ? "," : "", M->chrom_names[M->chrom[j]], (unsigned long)atol(strchr(rec_heads_get(&M->H, j), '\t') + 1));
+                }
+                fputc('\n', f);
+            }
+        }
+        if (fclose(f) != 0 && !rc) { snprintf(g_err, sizeof g_err, "cannot write %s", path); rc = HPGV_ERR_INVALID; }
+    }
+    /* the candidates whose distance window the candidate window cut short: candidate i + window + 1 is still in reach */
+    M->n_clumps = n_clumps; M->n_truncated = 0;
+    for (size_t i = 0; !rc && i + (size_t)O->window + 1 < n; i++) {
+        const size_t j = i + (size_t)O->window + 1;
+        const long long d = (long long)M->pos[j] - (long long)M->pos[i];
+        if (M->chrom[j] == M->chrom[i] && (O->max_bp < 0 || (d < 0 ? -d : d) <= O->max_bp)) M->n_truncated++;
+    }
+    if (!rc && M->n_truncated) fprintf(stderr, "WARN: the window of %d candidates cut the distance window of %ld candidates short\n", O->window, M->n_truncated);
+    free(edges); free(index_of); free(order); free(first); free(member); free(path);
+    return rc;
+}
+
+void run_clump_free(run_t *R) {
+    run_clump_t *M = R->CL;
+    for (int k = 0; M && k < M->n_chroms; k++) free(M->chrom_names[k]);
+    if (M) { free(M->rows); free(M->p); free(M->chrom); free(M->pos); rec_heads_free(&M->H); free(M->chrom_names); free(M); }
+    R->CL = NULL;
+}
+
+/* ---- hpg-var-vcf stats: what the run accumulates besides the per-variant lines (run_stats_t; the report writers live in
+ *      hpg-libs, so the two files below are this project's rendering) ---- */
+int run_stats_new(run_t *R) {
+    run_stats_t *RS = R->RS = (run_stats_t *)calloc(1, sizeof *RS);
+    if (RS) { RS->smiss = (long *)calloc((size_t)R->n_samples + 1, sizeof(long)); RS->serr = (long *)calloc((size_t)R->n_samples + 1, sizeof(long)); }
+    return RS && RS->smiss && RS->serr ? HPGV_OK : HPGV_ERR_NOMEM;
+}
+
+/* the per-phenotype lines of a batch: the counters of the first two alleles within the group (variant_stats_t per
+ * phenotype, stats_runner.c:319-323) */
+static void write_group_lines(FILE **gfd, const run_batch_t *b) {
+    const int n = b->n_lines < b->max_lines ? b->n_lines : b->max_lines, m = b->max_lines;
+    for (int g = 0; g < b->n_groups; g++)
+        for (int i = 0; i < n; i++) {
+            if (!record_passes(b, i)) continue;
+            const uint32_t *fo = b->field_off + 10 * (size_t)i;
+            const char *l = b->text + b->line_off[i];
+            const int32_t *c = b->gc8 + ((size_t)g * m + (size_t)i) * 8;
+            const int ta = c[6] + c[7];
+            const float f0 = ta ? (float)c[6] / ta : 0.0f, f1 = ta ? (float)c[7] / ta : 0.0f;
+            fprintf(gfd[g], "%.*s\t%ld\t%.*s\t%.*s\t%d,%d\t%.4f,%.4f\t0/0:%d,0/1:%d,1/1:%d,./.:%d\t%d\t%d\t%.4f\t%.6g\t%.6g\n",
+                    (int)(fo[1] - 1 - fo[0]), l + fo[0], atol(l + fo[1]), (int)(fo[4] - 1 - fo[3]), l + fo[3], (int)(fo[5] - 1 - fo[4]), l + fo[4],
+                    c[6], c[7], f0, f1, c[0], c[1] + c[2], c[3], c[4], c[5], c[4], f0 < f1 ? f0 : f1,
+                    b->ghw[(size_t)g * m + (size_t)i], b->ghw[((size_t)b->n_groups + (size_t)g) * m + (size_t)i]);
+        }
+}
+
+void run_stats_add(run_t *run, const run_batch_t *b) {
+    run_stats_t *R = run->RS;
+    for (int j = 0; j < run->n_samples; j++) R->smiss[j] += b->smiss[j];      /* counted over every line of the batch, as get_sample_stats does */
+    for (int t = 0; t < b->n_cerr; t++) R->serr[run->trio_child[t]] += b->cerr[t];
+    const int n = b->n_lines < b->max_lines ? b->n_lines : b->max_lines;
+    for (int i = 0; i < n; i++) {
+        if (!record_passes(b, i)) continue;
+        const uint32_t *fo = b->field_off + 10 * (size_t)i;
+        const char *l = b->text + b->line_off[i];
+        const char *ref = l + fo[3], *alt = l + fo[4];
+        const int lr = (int)(fo[4] - 1 - fo[3]), la = (int)(fo[5] - 1 - fo[4]);
+        vcounts_t v;
+        record_counts(b, i, alt, la, &v);
+        R->variants++;
+        if (v.na > 2) R->multiallelic++; else R->biallelic++;
+        int snp = lr == 1, n_alt = 0;                      /* a SNP: REF and every ALT allele one base long */
+        for (int k = 0, start = 0; k <= la; k++)
+            if (k == la || alt[k] == ',') { n_alt++; if (k - start != 1 || alt[start] == '.') snp = 0; start = k + 1; }
+        if (snp) {
+            R->snps++;
+            if (n_alt == 1) {
+                const char a = (char)(ref[0] & ~0x20), c = (char)(alt[0] & ~0x20);
+                const int purine_a = a == 'A' || a == 'G', purine_c = c == 'A' || c == 'G';
+                if (purine_a == purine_c) R->transitions++; else R->transversions++;
+            }
+        } else if (!(la == 1 && alt[0] == '.')) R->indels++;
+        if (fo[6] != 0xFFFFFFFFu) {
+            const char *q = l + fo[5];
+            if (*q != '.' && *q != '\t') { R->quality_sum += strtod(q, NULL); R->with_quality++; }
+            const char *f = l + fo[6];
+            const int lf = fo[7] != 0xFFFFFFFFu ? (int)(fo[7] - 1 - fo[6]) : 0;
+            if (lf == 4 && !strncmp(f, "PASS", 4)) R->pass++;
+        }
+    }
+    if (run->gfd) write_group_lines(run->gfd, b);         /* (the group files: by the writer loop's thread) */
+}
+
+int run_stats_write(const run_t *run, const char *prefix) {
+    const run_stats_t *R = run->RS;
+    const int n_samples = run->n_samples;
+    char *path = (char *)malloc(strlen(prefix) + 32);
+    if (!path) return HPGV_ERR_NOMEM;
+    sprintf(path, "%s.stats-samples", prefix);
+    FILE *f = fopen(path, "w");
+    if (!f) goto fail;
+    fprintf(f, "#SAMPLE\tMISS_GT\tMEND_ER\n");
+    for (int j = 0; j < n_samples; j++) fprintf(f, "%s\t%ld\t%ld\n", run->names[j], R->smiss[j], R->serr[j]);
+    fclose(f);
+    sprintf(path, "%s.stats-summary", prefix);
+    if (!(f = fopen(path, "w"))) goto fail;
+    fprintf(f, "Number of variants = %ld\nNumber of samples = %d\nNumber of biallelic variants = %ld\nNumber of multiallelic variants = %ld\n\n",
+            run->written, n_samples, R->biallelic, R->multiallelic);
+    fprintf(f, "Number of SNP = %ld\nNumber of indels = %ld\n\n", R->snps, R->indels);
+    fprintf(f, "Number of transitions = %ld\nNumber of transversions = %ld\nTi/TV ratio = %.4f\n\n", R->transitions, R->transversions,
+            R->transversions ? (double)R->transitions / (double)R->transversions : 0.0);
+    fprintf(f, "Percentage of PASS = %.2f%%\nAverage quality = %.2f\n", R->variants ? 100.0 * (double)R->pass / (double)R->variants : 0.0,
+            R->with_quality ? R->quality_sum / (double)R->with_quality : 0.0);
+    fclose(f);
+    free(path);
+    return HPGV_OK;
+fail:
+    snprintf(g_err, sizeof g_err, "cannot create %s", path); free(path); return HPGV_ERR_INVALID;
+}
+
+void run_stats_free(run_t *R) {
+    if (R->RS) { free(R->RS->smiss); free(R->RS->serr); free(R->RS); }
+    R->RS = NULL;
+}

@@ -18,7 +18,8 @@
  *   host_format.c      result lines of a batch, the writer thread
  *   host_vcftools.c    the VCF tools' batch steps and writers: filter partition, split keys and files
  *   host_records.c     the record filters of hpgv_run_set_record_filters: regions, coverage, variant types, inheritance
- *   host_runner.c      the file runners' pipeline and their runs (hpgv_run_*), the stats report
+ *   host_sideout.c     what a run keeps beside its result file and writes at its end: .mperm, .clumped, the stats report
+ *   host_runner.c      the file runners' pipeline and their runs (hpgv_run_*)
  */
 #ifndef HPGV_HOST_INTERNAL_H
 #define HPGV_HOST_INTERNAL_H
@@ -217,19 +218,18 @@ typedef struct { split_file_t *f; int n, cap; sample_ids_t *ids; char *key; size
 /* the parsed setting of hpgv_run_set_record_filters (host_records.c), shared by reference with the runs started under it */
 typedef struct rec_filters rec_filters_t;
 
+/* "CHR\tPOS\tID" of the records a side output keeps, in file order: n of them, NUL-terminated in the arena `heads`, head[i] the
+ * offset of record i's (host_sideout.c: rec_heads_*).  The arrays a store keeps beside it have H.cap elements, as head has */
+typedef struct { size_t *head; size_t n, cap; char *heads; size_t heads_len, heads_cap; } rec_heads_t;
+
 /* the permutation tools (tool_perm): what the run keeps for <out>.mperm -- the maxima merged over the batches (by the engine threads, under the
  * pipeline's mutex) and, per written record in file order, "CHR\tPOS\tID", the observed statistic and its n_ge */
-typedef struct {
-    double *tmax;
-    double *t_obs; int32_t *n_ge; size_t *head; size_t n, cap;      /* head: offset of the record's text in heads */
-    char *heads; size_t heads_len, heads_cap;
-} run_perm_t;
+typedef struct { double *tmax; double *t_obs; int32_t *n_ge; rec_heads_t H; } run_perm_t;
 
 /* clumping (hpgv_run_assoc_clump): the run's candidate store -- per written record with p <= p2, in file order, its genotype row
  * (n_samples bytes), its p, its chromosome (numbered in order of first appearance) and position, and "CHR\tPOS\tID" */
 typedef struct {
-    uint8_t *rows; double *p; int32_t *chrom; uint32_t *pos; size_t *head; size_t n, cap;
-    char *heads; size_t heads_len, heads_cap;
+    uint8_t *rows; double *p; int32_t *chrom; uint32_t *pos; rec_heads_t H;
     char **chrom_names; int n_chroms, chrom_cap;
     long n_clumps, n_truncated;
 } run_clump_t;
@@ -251,6 +251,7 @@ typedef struct run {
     split_files_t SF; run_stats_t *RS; order_track_t ord;
     int n_perms; uint64_t perm_seed; run_perm_t *PM;      /* the permutation tools */
     const hpgv_run_clump_options_t *clump; run_clump_t *CL;      /* RUN_CHISQ / RUN_FISHER with <out>.clumped beside the file (NULL: without) */
+    long n_clumps, n_truncated;                          /* ... what run_clump_write counted, kept past the store */
     double t_opened, t_header, t_sort;
 } run_t;
 
@@ -378,6 +379,23 @@ void order_track_keep(order_track_t *o, const char *line, size_t len);
 int file_writer_start(file_writer_t *w, FILE *fd);
 int file_writer_stop(file_writer_t *w);
 int write_batch(FILE *fd, const run_batch_t *b, out_buf_t *bufs, int n_bufs, io_pool_t *pool, order_track_t *ord, file_writer_t *fw);
+/* host_sideout.c: per side output, _new in run_outputs, _add per written batch, _write and _free (which clears the run's pointer) in run_finish */
+int rec_heads_init(rec_heads_t *H, size_t first_cap);    /* head allocated for first_cap records, doubled from there; these two: non-zero = no memory */
+int rec_heads_add(rec_heads_t *H, const char *chr, int lc, long pos, const char *id, int li);
+const char *rec_heads_get(const rec_heads_t *H, size_t i);
+void rec_heads_free(rec_heads_t *H);
+int run_perm_new(run_t *R);
+int run_perm_add(run_t *R, const run_batch_t *b);        /* the _adds of .mperm and .clumped: non-zero = no memory */
+int run_perm_write(run_t *R, const char *out_path);
+void run_perm_free(run_t *R);
+int run_clump_new(run_t *R);
+int run_clump_add(run_t *R, const run_batch_t *b);
+int run_clump_write(run_t *R, const char *out_path);
+void run_clump_free(run_t *R);
+int run_stats_new(run_t *R);
+void run_stats_add(run_t *R, const run_batch_t *b);      /* and the batch's lines to the per-phenotype files */
+int run_stats_write(const run_t *R, const char *prefix);
+void run_stats_free(run_t *R);
 /* host_vcftools.c */
 int filter_partition(run_batch_t *b);
 int split_partition(run_batch_t *b);

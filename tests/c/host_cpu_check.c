@@ -9,6 +9,7 @@
  *                                     prints per line: is_x then the N code bytes (hex), strict and lax
  *   host_cpu_check blocktable <file>  a bgzip file's block table by the team walk and by the serial walk
  *   host_cpu_check streams <file>     raw DEFLATE streams assembled by the tests, through hpgv_host_inflate_raw
+ *   host_cpu_check heads              the record-head store of the runs' side outputs (rec_heads_*), self-checking
  */
 #define _GNU_SOURCE
 #include <pthread.h>
@@ -304,8 +305,48 @@ static int cmd_blocktable(const char *path) {
     return failures ? 3 : rc;
 }
 
+/* The record-head store of the runs' side outputs (rec_heads_*): 70 000 records from a first capacity of 4, so the offsets
+ * double many times and the arena (from 64 KiB, about 12 MB of text) several times; every record read back and compared with
+ * the snprintf of its fields.  Then a store whose first record alone is longer than the arena's first 64 KiB, and the free of
+ * a store that was never used.  What is not freed, ASan's leak check reports when the program ends. */
+static int cmd_heads(void) {
+    enum { N = 70000, ID_MAX = 300 };
+    static const char *const chrs[3] = {"1", "22", "chrUn"};
+    static const long poss[4] = {0, 1, 2147483647L, -12345L};
+    char id[ID_MAX + 1], want[ID_MAX + 64];
+    rec_heads_t H;
+    int bad = rec_heads_init(&H, 4) != 0;
+    for (int i = 0; i < N && !bad; i++) {
+        memset(id, 'A' + i % 26, (size_t)(i % (ID_MAX + 1)));
+        bad = rec_heads_add(&H, chrs[i % 3], (int)strlen(chrs[i % 3]), poss[i % 4], id, i % (ID_MAX + 1)) != 0;
+    }
+    CHECK(!bad && H.n == N && H.cap >= N && H.heads_cap > (size_t)1 << 23, "heads: 70000 records added, offsets and arena grown");
+    int same = !bad;
+    for (int i = 0; i < N && same; i++) {
+        memset(id, 'A' + i % 26, (size_t)(i % (ID_MAX + 1)));
+        snprintf(want, sizeof want, "%s\t%ld\t%.*s", chrs[i % 3], poss[i % 4], i % (ID_MAX + 1), id);
+        same = !strcmp(rec_heads_get(&H, (size_t)i), want);
+        if (!same) printf("record %d: '%s', expected '%s'\n", i, rec_heads_get(&H, (size_t)i), want);
+    }
+    CHECK(same, "heads: every record reads back as the snprintf of its fields");
+    rec_heads_free(&H);
+    const int big = 100000;                              /* longer than the arena's first capacity */
+    char *long_id = (char *)malloc((size_t)big), *long_want = (char *)malloc((size_t)big + 64);
+    memset(long_id, 'z', (size_t)big);
+    snprintf(long_want, (size_t)big + 64, "X\t7\t%.*s", big, long_id);
+    bad = rec_heads_init(&H, 4) || rec_heads_add(&H, "X", 1, 7, long_id, big) || rec_heads_add(&H, "X", 1, 7, long_id, 0);
+    CHECK(!bad && !strcmp(rec_heads_get(&H, 0), long_want) && !strcmp(rec_heads_get(&H, 1), "X\t7\t"), "heads: a first record longer than 64 KiB");
+    rec_heads_free(&H);
+    free(long_id); free(long_want);
+    memset(&H, 0, sizeof H);
+    rec_heads_free(&H);
+    printf("%s\n", failures ? "HEADS FAILED" : "HEADS OK");
+    return failures ? 1 : 0;
+}
+
 int main(int argc, char **argv) {
     if (argc >= 2 && !strcmp(argv[1], "containers")) return cmd_containers();
+    if (argc >= 2 && !strcmp(argv[1], "heads")) return cmd_heads();
     if (argc >= 2 && !strcmp(argv[1], "pageedge")) return cmd_pageedge();
     if (argc >= 2 && !strcmp(argv[1], "inflate")) return cmd_inflate();
     if (argc >= 3 && !strcmp(argv[1], "streams")) return cmd_streams(argv[2]);
