@@ -70,10 +70,14 @@ SYMBOLS = [
     "hpgv_ld_window_dev", "hpgv_ld", "hpgv_ld_text", "hpgv_ld_r2",
     "hpgv_ld_edges_dev", "hpgv_ld_edges", "hpgv_clump",
     "hpgv_rows_gather_scratch_bytes", "hpgv_rows_gather_dev", "hpgv_assoc_select_text",
+    "hpgv_ibs_pairs_dev", "hpgv_ibs_class_counts_dev", "hpgv_ibs_select_dev", "hpgv_ibs", "hpgv_ibs_text", "hpgv_ibs_terms", "hpgv_ibs_genome",
 ]
 
 # hpgv_ld_edge: {int32 a, b; double r2}, 16 bytes
 LD_EDGE = np.dtype([("a", np.int32), ("b", np.int32), ("r2", np.float64)])
+# hpgv_ibs_counts: {int32 n, ibs0, ibs1, ibs2}, 16 bytes; hpgv_ibs_pair: {int32 i, j; hpgv_ibs_counts c; double pi_hat}, 32 bytes
+IBS_COUNTS = np.dtype([("n", np.int32), ("ibs0", np.int32), ("ibs1", np.int32), ("ibs2", np.int32)])
+IBS_PAIR = np.dtype([("i", np.int32), ("j", np.int32), ("c", IBS_COUNTS), ("pi_hat", np.float64)])
 
 
 class HpgvError(RuntimeError):
@@ -244,6 +248,15 @@ def load():
     L.hpgv_ld_edges_dev.argtypes = [vp, vp, sz, i32, i32, i32, vp, vp, C.c_int64, vp, C.c_double, vp, u64, vp, vp]
     L.hpgv_ld_edges.argtypes = [vp, vp, sz, i32, i32, vp, vp, C.c_int64, C.c_double, vp, u64, vp]
     L.hpgv_clump.argtypes = [i32, vp, vp, u64, C.c_double, vp, vp, C.POINTER(i32)]
+    L.hpgv_memset_dev.argtypes = [vp, vp, i32, sz, vp]
+    L.hpgv_ibs_pairs_dev.argtypes = [vp, vp, sz, i32, i32, vp, vp, vp]
+    L.hpgv_ibs_class_counts_dev.argtypes = [vp, vp, sz, i32, i32, vp, vp, vp]
+    L.hpgv_ibs_select_dev.argtypes = [vp, vp, i32, vp, C.c_double, vp, u64, vp, vp]
+    L.hpgv_ibs.argtypes = [vp, vp, sz, i32, vp, vp, vp]
+    L.hpgv_ibs_text.argtypes = [vp, C.c_char_p, sz, i32, C.POINTER(i32), vp, vp, vp, vp, vp]
+    L.hpgv_ibs_terms.argtypes = [i32, i32, i32, vp]
+    L.hpgv_ibs_genome.argtypes = [vp, vp, vp]
+    L.hpgv_ibs_genome.restype = None
     L.hpgv_rows_gather_scratch_bytes.argtypes = [i32]
     L.hpgv_rows_gather_scratch_bytes.restype = sz
     L.hpgv_rows_gather_dev.argtypes = [vp, vp, sz, sz, i32, vp, vp, sz, vp, vp, vp, vp]
@@ -307,6 +320,23 @@ def run_assoc_model(vcf_path, ped_path, out_path, n_perms=0, seed=0, batch_bytes
     return n.value
 
 
+def run_genome(vcf_path, out_path, min_pi_hat=0.0, batch_bytes=1 << 22):
+    """hpgv_run_genome of libhpgv_host.so (include/hpgv_host.h): the sample pairs with PI_HAT >= min_pi_hat at out_path.  Paths may
+    be None (the call then fails with ERR_INVALID).  Returns (records that took part, pairs written)."""
+    _build.build_host_lib()
+    H = C.CDLL(_build.HOSTLIB)
+    H.hpgv_run_genome.argtypes = [C.c_char_p, C.c_char_p, C.c_double, C.c_size_t, C.POINTER(C.c_long), C.POINTER(C.c_long)]
+    H.hpgv_host_last_error.restype = C.c_char_p
+    n, k = C.c_long(0), C.c_long(0)
+    enc = lambda q: None if q is None else os.fsencode(q)
+    rc = H.hpgv_run_genome(enc(vcf_path), enc(out_path), float(min_pi_hat), batch_bytes, C.byref(n), C.byref(k))
+    if rc != OK:
+        e = HpgvError("hpgv_run_genome -> %d: %s" % (rc, (H.hpgv_host_last_error() or b"").decode(errors="replace")))
+        e.code = rc
+        raise e
+    return n.value, k.value
+
+
 class RunClumpOptions(C.Structure):
     """hpgv_run_clump_options_t, with PLINK's defaults"""
     _fields_ = [("p1", C.c_double), ("p2", C.c_double), ("min_r2", C.c_double), ("max_bp", C.c_int64), ("window", C.c_int)]
@@ -358,6 +388,49 @@ def ld_r2(counts6):
     L = load()
     out = np.array([L.hpgv_ld_r2(_ptr(row)) for row in flat], np.float64)
     return out.reshape(c.shape[:-1])
+
+
+def ibs_terms(class4):
+    """hpgv_ibs_terms on rows of class counts (..., >= 3) = {n0, n1, n2[, missing]}: (used (...) bool, terms (..., 5)).  No device
+    needed."""
+    c = _np(class4, np.int32)
+    flat = c.reshape(-1, c.shape[-1])
+    L = load()
+    used, terms = np.zeros(len(flat), bool), np.zeros((len(flat), 5), np.float64)
+    for k, row in enumerate(flat):
+        used[k] = L.hpgv_ibs_terms(int(row[0]), int(row[1]), int(row[2]), _ptr(terms[k])) != 0
+    return used.reshape(c.shape[:-1]), terms.reshape(c.shape[:-1] + (5,))
+
+
+def ibs_expected(class4):
+    """E = {E00, E01, E02, E11, E12} of rows of class counts in file order: hpgv_ibs_terms of every row, the used rows' terms added
+    sequentially, divided by their number (NaN without a used row).  A skipped row's class4 is zeros: it is not used."""
+    used, terms = ibs_terms(class4)
+    total = [0.0] * 5
+    m = 0
+    for u, t in zip(used.reshape(-1).tolist(), terms.reshape(-1, 5).tolist()):
+        if u:
+            m += 1
+            total = [a + b for a, b in zip(total, t)]
+    with np.errstate(invalid="ignore"):
+        return np.array(total, np.float64) / np.float64(m)
+
+
+def ibs_genome(counts, E):
+    """hpgv_ibs_genome on an IBS_COUNTS array (or (..., 4) int32): (..., 5) = {Z0, Z1, Z2, PI_HAT, DST}.  No device needed."""
+    c = np.ascontiguousarray(counts)
+    if c.dtype == IBS_COUNTS:
+        shape, flat = c.shape, c.reshape(-1)
+    else:
+        c = _np(counts, np.int32)
+        shape, flat = c.shape[:-1], c.reshape(-1, 4)
+    e = _np(E, np.float64)
+    assert e.shape == (5,)
+    L = load()
+    out = np.zeros((len(flat), 5), np.float64)
+    for k in range(len(flat)):
+        L.hpgv_ibs_genome(C.c_void_p(flat[k:k + 1].ctypes.data), _ptr(e), _ptr(out[k]))
+    return out.reshape(shape + (5,))
 
 
 def clump(p, edges, p1):
@@ -684,6 +757,49 @@ class Engine:
         self._chk(self.L.hpgv_ld_text(self.h, text, len(text), max_lines, C.byref(nl), None, None, _ptr(status), window, _ptr(r2), _ptr(c6)))
         return _text_result(nl, max_lines, status=status, r2=r2, counts6=c6)
 
+    def ibs(self, gt, d_counts, skip=None):
+        """hpgv_ibs: class4 (nv, 4) of the rows; their pair counts are ADDED to the device records d_counts (n_samples x n_samples
+        IBS_COUNTS, zeroed by the caller: memset_dev)."""
+        gt = _np(gt, np.uint8)
+        nv, pitch = gt.shape
+        sk = None if skip is None else _np(skip, np.uint8)
+        class4 = np.zeros((nv, 4), np.int32)
+        self._chk(self.L.hpgv_ibs(self.h, _ptr(gt), pitch, nv, _ptr(sk), _ptr(class4), d_counts))
+        return class4
+
+    def ibs_text(self, text, d_counts, max_lines=None):
+        """hpgv_ibs_text: ibs on VCF data lines (dropped lines and chromosome-X lines are skipped rows): status and class4 per line."""
+        text, max_lines, m, status, nl = _text_call(text, max_lines)
+        class4 = np.zeros((m, 4), np.int32)
+        self._chk(self.L.hpgv_ibs_text(self.h, text, len(text), max_lines, C.byref(nl), None, None, _ptr(status), _ptr(class4), d_counts))
+        return _text_result(nl, max_lines, status=status, class4=class4)
+
+    def ibs_select(self, d_counts, n_cols, E, min_pi_hat, cap=None):
+        """hpgv_ibs_select_dev on device records: the pairs with PI_HAT >= min_pi_hat as an IBS_PAIR array sorted by (i, j).  Without
+        cap the call is repeated once with room when the first list was too short; with it, (pairs or None, count) comes back."""
+        e = _np(E, np.float64)
+        room = 4096 if cap is None else int(cap)
+        d_n = self.alloc(16)
+        try:
+            for _ in range(2):
+                d_pairs = self.alloc(max(room, 1) * 32)
+                try:
+                    self.ibs_select_dev(d_counts, n_cols, e, min_pi_hat, d_pairs if room else None, room, d_n)
+                    self.sync()
+                    n = int(self.d2h(d_n, (1,), np.uint64)[0])
+                    pairs = self.d2h(d_pairs, (min(n, room),), IBS_PAIR) if min(n, room) else np.zeros(0, IBS_PAIR)
+                finally:
+                    self.free(d_pairs)
+                pairs = pairs[np.lexsort((pairs["j"], pairs["i"]))]
+                if cap is not None:
+                    return (pairs if n <= room else None), n
+                if n <= room:
+                    return pairs
+                room = n
+        finally:
+            self.free(d_n)
+        raise HpgvError("hpgv_ibs_select_dev: the count grew between two calls on the same records")
+
     def assoc_view(self, task, gt2d, n_samples, is_x=None):
         """hpgv_assoc on a 2-D uint8 VIEW as it lies in memory (row stride = pitch): nothing is copied on the way,
         so a view of page-locked memory (host_array) is read by the kernel in place."""
@@ -966,6 +1082,19 @@ class Engine:
                      max_bp=-1, d_skip=None, stream=None):
         self._chk(self.L.hpgv_ld_edges_dev(self.h, d_gt, pitch, n_variants, b_begin, window, d_chrom, d_pos, int(max_bp), d_skip,
                                            float(min_r2), d_edges, int(edge_cap), d_n_edges, stream))
+
+    def memset_dev(self, dptr, byte_value, nbytes, stream=None):
+        self._chk(self.L.hpgv_memset_dev(self.h, dptr, byte_value, nbytes, stream))
+
+    def ibs_pairs_dev(self, d_gt, pitch, n_variants, n_cols, d_counts, d_skip=None, stream=None):
+        self._chk(self.L.hpgv_ibs_pairs_dev(self.h, d_gt, pitch, n_variants, n_cols, d_skip, d_counts, stream))
+
+    def ibs_class_counts_dev(self, d_gt, pitch, n_variants, n_cols, d_class4, d_skip=None, stream=None):
+        self._chk(self.L.hpgv_ibs_class_counts_dev(self.h, d_gt, pitch, n_variants, n_cols, d_skip, d_class4, stream))
+
+    def ibs_select_dev(self, d_counts, n_cols, E, min_pi_hat, d_pairs, cap, d_n, stream=None):
+        e = _np(E, np.float64)
+        self._chk(self.L.hpgv_ibs_select_dev(self.h, d_counts, n_cols, _ptr(e), float(min_pi_hat), d_pairs, int(cap), d_n, stream))
 
     def rows_gather_scratch_bytes(self, n_rows):
         return self.L.hpgv_rows_gather_scratch_bytes(n_rows)

@@ -2,7 +2,7 @@
 // libhpgv.so: hpgv_capi.hip (contexts, options, cohorts, memory, streams, text aliases), hpgv_scan_capi.hip (the
 // device-resident *_dev launchers), hpgv_text_capi.hip (tokenizer, the text entry points' front half),
 // hpgv_tool_capi.hip (per-batch and text entry points), hpgv_lines_capi.hip (partition / multisplit of lines), and the
-// units whose kernel instantiations compile on their own (hpgv_perm_capi.hip, hpgv_ld_capi.hip, hpgv_epi_capi.hip, hpgv_epi_generic_capi.hip, hpgv_statsall_capi.hip, hpgv_inflate_capi.hip, hpgv_group_capi.hip).
+// units whose kernel instantiations compile on their own (hpgv_perm_capi.hip, hpgv_ld_capi.hip, hpgv_ibs_capi.hip, hpgv_epi_capi.hip, hpgv_epi_generic_capi.hip, hpgv_statsall_capi.hip, hpgv_inflate_capi.hip, hpgv_group_capi.hip).
 // A synchronous entry point has two halves that meet in a Staged: the front puts the call's matrix on the device -- text_front /
 // text_front_skip for a text, stage_chain for a host batch that goes through the kernel chain -- and the tool's back half takes it
 // from there; the permutation calls build theirs from the halves of hpgv_assoc's and hpgv_tdt's (assoc_chain, ..., below).
@@ -135,7 +135,7 @@ struct TextMeta {
 };
 
 // the genotype matrix of one synchronous call once it is on the device: what the back halves of hpgv_tool_capi.hip,
-// hpgv_perm_capi.hip and hpgv_ld_capi.hip read, whether a batch (batch_sources / stage_chain) or a text (text_front,
+// hpgv_perm_capi.hip, hpgv_ld_capi.hip and hpgv_ibs_capi.hip read, whether a batch (batch_sources / stage_chain) or a text (text_front,
 // hpgv_text_capi.hip) put it there
 struct Staged {
     const uint8_t *d_raw = nullptr;   // VCF column order: the slot's `raw`, or the caller's rows where the device can read them
@@ -481,10 +481,11 @@ struct TextSkip {
     std::vector<uint8_t> skip;
     const uint8_t *bytes() const { return skip.empty() ? nullptr : skip.data(); }
 };
-// defined in hpgv_text_capi.hip: text_front with the final layout, then the synchronise, then K->skip: 1 for the lines that
-// hpgv_assoc_text's callers drop -- not a record, or rejected by a record filter (max_lines > 0)
+// defined in hpgv_text_capi.hip: text_front with the final layout (without it for a caller whose kernels read the raw matrix:
+// hpgv_ibs_text), then the synchronise, then K->skip: 1 for the lines that hpgv_assoc_text's callers drop -- not a record, or
+// rejected by a record filter (max_lines > 0)
 int text_front_skip(hpgv_ctx *ctx, Slot *s, int which, const Layout &L, const char *text, size_t text_bytes, int max_lines, int *n_lines,
-                    uint64_t *line_off, uint32_t *field_off, int32_t *status, TextSkip *K, Staged *S);
+                    uint64_t *line_off, uint32_t *field_off, int32_t *status, TextSkip *K, Staged *S, bool final_layout = true);
 // defined in hpgv_tool_capi.hip: the laid-out path of hpgv_assoc and hpgv_tdt in two halves, so that the permutation calls
 // (hpgv_perm_capi.hip) queue their kernels between them.  *_chain: room in the slot (tally, dbl), scan, statistics (n = 0: room
 // only).  *_copy_out: the copies into the caller's arrays, queued -- the caller synchronises (n = 0: nothing)

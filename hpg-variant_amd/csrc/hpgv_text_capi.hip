@@ -287,9 +287,9 @@ static bool line_skipped(int32_t status) { return (status & 0xFF) == 1 || (statu
 
 // the record filters run only into a status array, so the call brings its own when the caller gave none
 int text_front_skip(hpgv_ctx *ctx, Slot *s, int which, const Layout &L, const char *text, size_t text_bytes, int max_lines, int *n_lines,
-                    uint64_t *line_off, uint32_t *field_off, int32_t *status, TextSkip *K, Staged *S) {
+                    uint64_t *line_off, uint32_t *field_off, int32_t *status, TextSkip *K, Staged *S, bool final_layout) {
     if (!status) { K->own_status.assign((size_t)max_lines, 0); status = K->own_status.data(); }
-    if (const int rc = text_front(ctx, s, which, L, text, text_bytes, max_lines, n_lines, line_off, field_off, status, S, true)) return rc;
+    if (const int rc = text_front(ctx, s, which, L, text, text_bytes, max_lines, n_lines, line_off, field_off, status, S, final_layout)) return rc;
     HIPCHK(ctx, hipStreamSynchronize(s->stream));
     K->skip.resize((size_t)S->n);
     for (int i = 0; i < S->n; ++i) K->skip[(size_t)i] = line_skipped(status[i]) ? 1 : 0;

@@ -1,5 +1,5 @@
 /* host_runner.c -- the file runners: reader -> engine threads -> writer (hpgv_run_assoc / tdt / aggregate / stats / vcf2epi /
- * filter / split).  The VCF tools' own batch steps and writers are in host_vcftools.c, what a run keeps beside its result file in
+ * filter / split / genome).  The VCF tools' own batch steps and writers are in host_vcftools.c, what a run keeps beside its result file in
  * host_sideout.c.
  * Part of libhpgv_host.so (see hpgv_host_internal.h for the map of its units). */
 #include "hpgv_host_internal.h"
@@ -123,6 +123,11 @@ static int engine_call(run_t *R, run_batch_t *b, const char **what, int *again) 
     case RUN_MODEL: case RUN_MODEL_PERM: *what = "hpgv_assoc_model_text";
         return hpgv_assoc_model_text(g_ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status,
                                      b->ints, b->dbl, b->dbl + 5 * (size_t)m, tool == RUN_MODEL_PERM ? b->n_ge : NULL, tool == RUN_MODEL_PERM ? b->bmax : NULL);
+    case RUN_GENOME: { *what = "hpgv_ibs_text";            /* on one device of the run, into that device's counts (a batch with more lines than room adds nothing) */
+        hpgv_ibs_counts *d_counts = NULL;
+        hpgv_ctx *ctx = run_genome_device(R, b, &d_counts);
+        return hpgv_ibs_text(ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status, b->ints, d_counts);
+    }
     }
     return rc;
 }
@@ -223,8 +228,8 @@ static int run_cohort(run_t *R, const char *vcf_path, const char *ped_path) {
     sample_ids_t *ids = sample_ids_new((size_t)n_samples);
     for (int j = 0; j < n_samples; j++) sample_ids_put(ids, R->names[j], j);
     switch (R->tool) {
-    case RUN_AGGREGATE: case RUN_STATS: case RUN_FILTER: case RUN_SPLIT: {
-        /* the engine scans the stats layout of all columns (get_variants_stats / get_sample_stats, hpgv_filter_text); stats with a
+    case RUN_AGGREGATE: case RUN_STATS: case RUN_FILTER: case RUN_SPLIT: case RUN_GENOME: {
+        /* the engine scans the stats layout of all columns (get_variants_stats / get_sample_stats, hpgv_filter_text, hpgv_ibs_text); stats with a
          * PED: its phenotype groups, and its trios give the Mendelian errors (stats_runner.c:165-170,194-198) */
         rc = hpgv_set_stats_cohort(g_ctx, n_samples);
         g_stats_key.set = 0;
@@ -371,6 +376,7 @@ static int create_out(FILE **f, char **path, const char *prefix, const char *suf
  * save_rejected (filter_runner.c:63-68); stats: one file per phenotype (stats_runner.c:267-297), and its accumulator */
 static int run_outputs(run_t *R, const char *out_path) {
     if ((R->clump && run_clump_new(R)) || (tool_perm(R->tool) && run_perm_new(R))) return HPGV_ERR_NOMEM;
+    if (R->tool == RUN_GENOME) return run_genome_new(R);      /* (its one file is written when the run ends: run_genome_write) */
     const char *suffix = R->tool == RUN_STATS ? ".stats-variants" : R->tool == RUN_FILTER ? (R->out_bgzf ? ".filtered.gz" : ".filtered") : "";
     int rc = R->tool == RUN_SPLIT ? HPGV_OK : create_out(&R->out, &R->path, out_path, suffix);
     if (!rc && R->tool == RUN_FILTER) rc = create_out(&R->out_rej, &R->path_rej, out_path, R->out_bgzf ? ".rejected.gz" : ".rejected");
@@ -429,6 +435,7 @@ static int run_headers(run_t *R) {
         return HPGV_OK;
     case RUN_FILTER: return write_filter_header(out, R) || (R->save_rejected && write_filter_header(R->out_rej, R)) ? HPGV_ERR_INVALID : HPGV_OK;
     case RUN_SPLIT: break;                               /* (each file gets the input's header when it is created) */
+    case RUN_GENOME: break;                              /* (no file yet) */
     }
     return HPGV_OK;
 }
@@ -514,6 +521,7 @@ static int run_pipeline(run_t *R, size_t batch_bytes) {
                 if (R->CL && !bad && run_clump_add(R, b)) bad = "out of memory for the clumping candidates";
                 if (R->tool == RUN_STATS && !bad) run_stats_add(R, b);      /* (and the group files' lines: by this thread) */
                 break;
+            case RUN_GENOME: run_genome_add(R, b); break;       /* no line per record: the records' terms, in file order */
             }
             fmt_set ^= use_fw;
             const double dt = now_s() - t0;
@@ -576,6 +584,11 @@ static int run_finish(run_t *R, int rc, const char *out_path) {
         R->n_clumps = R->CL->n_clumps; R->n_truncated = R->CL->n_truncated;      /* for hpgv_run_assoc_clump, past the store */
         run_clump_free(R);
     }
+    if (R->GN) {
+        if (!rc) rc = run_genome_write(R, out_path);
+        R->n_pairs = R->GN->n_pairs;                     /* for hpgv_run_genome, past the counts */
+    }
+    run_genome_free(R);
     run_stats_free(R);
     free(R->ord.last); free(R->gfd); free(R->group_names); free(R->path); free(R->path_rej); free(R->trio_child);
     const hpgv_run_filters_t *f = &R->filters;
@@ -585,9 +598,9 @@ static int run_finish(run_t *R, int rc, const char *out_path) {
 }
 
 static int run_file_held(run_t *R, const char *vcf_path, const char *ped_path, const char *out_path, size_t batch_bytes, long *n_variants_out);
-/* the run holds the record filters of hpgv_run_set_record_filters as they are when it starts (stats and split: none) */
+/* the run holds the record filters of hpgv_run_set_record_filters as they are when it starts (stats, split and genome: none) */
 static int run_file(run_t *R, const char *vcf_path, const char *ped_path, const char *out_path, size_t batch_bytes, long *n_variants_out) {
-    R->rf = R->tool == RUN_STATS || R->tool == RUN_SPLIT ? NULL : rec_filters_take();
+    R->rf = R->tool == RUN_STATS || R->tool == RUN_SPLIT || R->tool == RUN_GENOME ? NULL : rec_filters_take();
     int rc = HPGV_OK;
     if (rec_filters_inheritance(R->rf) && !ped_path) {                /* filter_options_parsing.c:149-153 */
         snprintf(g_err, sizeof g_err, "the inheritance filters (--inh-dom / --inh-rec) need a PED file (ped_path is NULL)");
@@ -751,6 +764,18 @@ int hpgv_run_aggregate(const char *vcf_path, const char *out_path, int overwrite
 int hpgv_run_stats(const char *vcf_path, const char *ped_path, const char *out_prefix, size_t batch_bytes, long *n_variants_out) {
     /* the per-sample counters are sums over every data line of a batch, so the record filters are not applied here */
     return run_file(&(run_t){ .tool = RUN_STATS, .filters = filters_off }, vcf_path, ped_path, out_prefix, batch_bytes, n_variants_out);
+}
+
+/* sample relatedness (include/hpgv.h "IBS"; PLINK's --genome): the pairs of samples with PI_HAT >= min_pi_hat in one file.  As in
+ * hpgv_run_stats the record filters are not applied: the counts are sums over every record of a batch */
+int hpgv_run_genome(const char *vcf_path, const char *out_path, double min_pi_hat, size_t batch_bytes, long *n_variants_out, long *n_pairs_out) {
+    if (n_pairs_out) *n_pairs_out = 0;
+    if (run_args(n_variants_out, vcf_path && out_path, "vcf_path and out_path must not be NULL")) return HPGV_ERR_INVALID;
+    if (min_pi_hat != min_pi_hat) { snprintf(g_err, sizeof g_err, "min_pi_hat is NaN"); return HPGV_ERR_INVALID; }
+    run_t R = { .tool = RUN_GENOME, .filters = filters_off, .min_pi_hat = min_pi_hat };
+    const int rc = run_file(&R, vcf_path, NULL, out_path, batch_bytes, n_variants_out);
+    if (n_pairs_out) *n_pairs_out = R.n_pairs;
+    return rc;
 }
 
 /* run_filter (src/vcf-tools/filter/filter_runner.c:23-260): the records of the VCF that pass the filters of

@@ -1,6 +1,6 @@
 /* host_sideout.c -- what a file run keeps beside its result file, and the files written from it at the end: the permutation
- * results (<out>.mperm), the clumping candidates (<out>.clumped), the stats report.  Each is a run_*_t of the run with four
- * functions: _new (run_outputs), _add (the writer loop, per written batch), _write and _free (run_finish).
+ * results (<out>.mperm), the clumping candidates (<out>.clumped), the stats report, the sample pairs of the genome run.  Each is
+ * a run_*_t of the run with four functions: _new (run_outputs), _add (the writer loop, per written batch), _write and _free (run_finish).
  * Part of libhpgv_host.so (see hpgv_host_internal.h for the map of its units). */
 #include "hpgv_host_internal.h"
 
@@ -223,6 +223,129 @@ void run_clump_free(run_t *R) {
     for (int k = 0; M && k < M->n_chroms; k++) free(M->chrom_names[k]);
     if (M) { free(M->rows); free(M->p); free(M->chrom); free(M->pos); rec_heads_free(&M->H); free(M->chrom_names); free(M); }
     R->CL = NULL;
+}
+
+/* ---- sample relatedness: the pair counts of the run on its devices, the expected values' sums, and the file of pairs ---------- */
+static size_t genome_bytes(const run_t *R) {
+    const size_t ns = (size_t)R->n_samples, b = ns * ns * sizeof(hpgv_ibs_counts);
+    return b ? b : sizeof(hpgv_ibs_counts);
+}
+
+int run_genome_new(run_t *R) {
+    run_genome_t *G = R->GN = (run_genome_t *)calloc(1, sizeof *G);
+    if (!G) return HPGV_ERR_NOMEM;
+    const int devs = hpgv_group_size(g_ctx);
+    G->n_dev = devs > 1 ? devs : 1;
+    G->ctx = (hpgv_ctx **)calloc((size_t)G->n_dev, sizeof *G->ctx);
+    G->d_counts = (hpgv_ibs_counts **)calloc((size_t)G->n_dev, sizeof *G->d_counts);
+    if (!G->ctx || !G->d_counts) return HPGV_ERR_NOMEM;
+    for (int d = 0; d < G->n_dev; d++) {
+        G->ctx[d] = devs > 1 ? hpgv_group_member(g_ctx, d) : g_ctx;
+        void *p = NULL;
+        int rc = hpgv_dev_alloc(G->ctx[d], genome_bytes(R), &p);
+        if (rc) { snprintf(g_err, sizeof g_err, "%d samples: no device memory for their %zu bytes of pair counts (%d)", R->n_samples, genome_bytes(R), rc); return rc; }
+        G->d_counts[d] = (hpgv_ibs_counts *)p;
+        if ((rc = hpgv_memset_dev(G->ctx[d], p, 0, genome_bytes(R), NULL))) return host_fail("hpgv_memset_dev", rc);
+    }
+    return HPGV_OK;
+}
+
+hpgv_ctx *run_genome_device(run_t *R, const run_batch_t *b, hpgv_ibs_counts **d_counts) {
+    run_genome_t *G = R->GN;
+    int d = 0;
+    if (b->dev_text) { for (int k = 0; k < G->n_dev; k++) if (G->ctx[k] == b->dev_ctx) d = k; }      /* (no dev_ctx: the text lies on the first device) */
+    else d = (int)(__atomic_fetch_add(&G->next, 1u, __ATOMIC_RELAXED) % (unsigned)G->n_dev);
+    *d_counts = G->d_counts[d];
+    return G->ctx[d];
+}
+
+/* the written records of a batch in file order: a record whose class counts are all zero was a skipped row (chromosome X) and
+ * took no part; the terms of the others are added where the row is used */
+void run_genome_add(run_t *R, const run_batch_t *b) {
+    run_genome_t *G = R->GN;
+    const int n = b->n_lines < b->max_lines ? b->n_lines : b->max_lines;
+    for (int i = 0; i < n; i++) {
+        const int32_t *c = b->ints + 4 * (size_t)i;
+        if (!record_passes(b, i) || !(c[0] | c[1] | c[2] | c[3])) continue;
+        R->written++;
+        double t[5];
+        if (!hpgv_ibs_terms(c[0], c[1], c[2], t)) continue;
+        G->used++;
+        for (int k = 0; k < 5; k++) G->sum[k] += t[k];
+    }
+}
+
+static int genome_pair_cmp(const void *a, const void *b) {
+    const hpgv_ibs_pair *x = (const hpgv_ibs_pair *)a, *y = (const hpgv_ibs_pair *)b;
+    return x->i != y->i ? (x->i < y->i ? -1 : 1) : x->j != y->j ? (x->j < y->j ? -1 : 1) : 0;
+}
+
+/* the devices' buffers added into the first one's (integers: any order), hpgv_ibs_select_dev there -- once more with room when the
+ * list was too short --, the pairs sorted by (i, j), the file */
+int run_genome_write(run_t *R, const char *out_path) {
+    run_genome_t *G = R->GN;
+    const int ns = R->n_samples;
+    const size_t bytes = genome_bytes(R);
+    int rc = HPGV_OK;
+    if (G->n_dev > 1) {
+        int32_t *sum = (int32_t *)calloc(bytes / 4, 4), *part = (int32_t *)malloc(bytes);
+        if (!sum || !part) rc = HPGV_ERR_NOMEM;
+        for (int d = 0; d < G->n_dev && !rc; d++) {
+            if ((rc = hpgv_memcpy_d2h(G->ctx[d], part, G->d_counts[d], bytes, NULL))) { host_fail("hpgv_memcpy_d2h", rc); break; }
+            for (size_t k = 0; k < bytes / 4; k++) sum[k] += part[k];
+        }
+        if (!rc && (rc = hpgv_memcpy_h2d(G->ctx[0], G->d_counts[0], sum, bytes, NULL))) host_fail("hpgv_memcpy_h2d", rc);
+        free(sum); free(part);
+        if (rc) return rc;
+    }
+    double E[5];
+    for (int k = 0; k < 5; k++) E[k] = G->sum[k] / (double)G->used;      /* (no used record: NaN, and no pair qualifies) */
+    hpgv_ctx *ctx = G->ctx[0];
+    uint64_t cap = (uint64_t)ns * 8 + 16, n = 0;
+    hpgv_ibs_pair *pairs = NULL;
+    void *d_n = NULL, *d_pairs = NULL;
+    if ((rc = hpgv_dev_alloc(ctx, 16, &d_n))) return host_fail("hpgv_dev_alloc", rc);
+    for (int attempt = 0; attempt < 2 && !rc; attempt++) {      /* the count exceeds the room: grow and repeat once */
+        if ((rc = hpgv_dev_alloc(ctx, (size_t)cap * sizeof(hpgv_ibs_pair), &d_pairs))) { host_fail("hpgv_dev_alloc", rc); break; }
+        if ((rc = hpgv_ibs_select_dev(ctx, G->d_counts[0], ns, E, R->min_pi_hat, (hpgv_ibs_pair *)d_pairs, cap, (uint64_t *)d_n, NULL)) ||
+            (rc = hpgv_memcpy_d2h(ctx, &n, d_n, sizeof n, NULL))) {
+            snprintf(g_err, sizeof g_err, "hpgv_ibs_select_dev failed (%d): %s", rc, hpgv_last_error(ctx));
+        } else if (n <= cap) {
+            if (!(pairs = (hpgv_ibs_pair *)malloc(sizeof *pairs * (size_t)(n + 1)))) rc = HPGV_ERR_NOMEM;
+            else if (n && (rc = hpgv_memcpy_d2h(ctx, pairs, d_pairs, (size_t)n * sizeof *pairs, NULL))) host_fail("hpgv_memcpy_d2h", rc);
+        } else if (attempt == 1) { snprintf(g_err, sizeof g_err, "hpgv_ibs_select_dev: the number of pairs grew between two calls"); rc = HPGV_ERR_INVALID; }
+        (void)hpgv_dev_free(ctx, d_pairs);
+        if (pairs || rc) break;
+        cap = n;
+    }
+    (void)hpgv_dev_free(ctx, d_n);
+    FILE *f = NULL;
+    if (!rc && !(f = fopen(out_path, "wb"))) { snprintf(g_err, sizeof g_err, "cannot create %s", out_path); rc = HPGV_ERR_INVALID; }
+    if (!rc) {
+        qsort(pairs, (size_t)n, sizeof *pairs, genome_pair_cmp);
+        setvbuf(f, NULL, _IOFBF, 1u << 20);
+        fputs("#IID1\tIID2\tNM\tIBS0\tIBS1\tIBS2\tZ0\tZ1\tZ2\tPI_HAT\tDST\n", f);
+        char num[5][320];
+        for (uint64_t q = 0; q < n; q++) {
+            const hpgv_ibs_pair *p = pairs + q;
+            double g[5];
+            hpgv_ibs_genome(&p->c, E, g);
+            for (int k = 0; k < 5; k++) hpgv_host_format_f6(g[k], num[k]);
+            fprintf(f, "%s\t%s\t%d\t%d\t%d\t%d\t%s\t%s\t%s\t%s\t%s\n", R->names[p->i], R->names[p->j], p->c.n, p->c.ibs0, p->c.ibs1, p->c.ibs2,
+                    num[0], num[1], num[2], num[3], num[4]);
+        }
+        if (fclose(f) != 0) { snprintf(g_err, sizeof g_err, "cannot write %s", out_path); rc = HPGV_ERR_INVALID; }
+        else G->n_pairs = (long)n;
+    }
+    free(pairs);
+    return rc;
+}
+
+void run_genome_free(run_t *R) {
+    run_genome_t *G = R->GN;
+    for (int d = 0; G && G->d_counts && G->ctx && d < G->n_dev; d++) if (G->d_counts[d]) (void)hpgv_dev_free(G->ctx[d], G->d_counts[d]);
+    if (G) { free(G->ctx); free(G->d_counts); free(G); }
+    R->GN = NULL;
 }
 
 /* ---- hpg-var-vcf stats: what the run accumulates besides the per-variant lines (run_stats_t; the report writers live in

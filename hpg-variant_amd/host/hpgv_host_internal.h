@@ -142,9 +142,10 @@ typedef struct {
 /* the file runners' tools.  The first two are the assoc tasks, as hpgv_assoc_text takes them */
 /* RUN_CHISQ_PERM: the chi-square run with label permutation (hpgv_run_assoc_perm): RUN_CHISQ's file plus <out>.mperm;
  * RUN_TDT_PERM: the TDT run with family flips (hpgv_run_tdt_perm): RUN_TDT's file plus <out>.mperm;
- * RUN_MODEL / RUN_MODEL_PERM: the model tests (hpgv_run_assoc_model) without and with <out>.mperm of the trend statistic */
+ * RUN_MODEL / RUN_MODEL_PERM: the model tests (hpgv_run_assoc_model) without and with <out>.mperm of the trend statistic;
+ * RUN_GENOME: sample relatedness (hpgv_run_genome): no line per record, one file of sample pairs written when the run ends */
 typedef enum { RUN_CHISQ = CHI_SQUARE, RUN_FISHER = FISHER, RUN_TDT, RUN_VCF2EPI, RUN_AGGREGATE, RUN_STATS, RUN_FILTER, RUN_SPLIT, RUN_CHISQ_PERM, RUN_TDT_PERM,
-               RUN_MODEL, RUN_MODEL_PERM } run_tool_t;
+               RUN_MODEL, RUN_MODEL_PERM, RUN_GENOME } run_tool_t;
 static inline int tool_chisq(run_tool_t t) { return t == RUN_CHISQ || t == RUN_CHISQ_PERM; }   /* writes the chi-square file */
 static inline int tool_tdt(run_tool_t t) { return t == RUN_TDT || t == RUN_TDT_PERM; }         /* writes the TDT file */
 static inline int tool_model(run_tool_t t) { return t == RUN_MODEL || t == RUN_MODEL_PERM; }   /* writes the model tests' file */
@@ -161,7 +162,7 @@ typedef struct {
     size_t bytes; int max_lines, n_lines;
     uint64_t *line_off; uint32_t *field_off; int32_t *status;
     int32_t *ints; double *dbl;                          /* 4 (assoc) or 2 (tdt) int arrays, 3 double arrays; the model tests: counts8 per line, then
-                                                          * chisq5 per line and, from dbl + 5 * max_lines, p5 per line */
+                                                          * chisq5 per line and, from dbl + 5 * max_lines, p5 per line; genome: class4 per line in ints */
     int32_t *n_ge; double *bmax;                         /* the permutation tools: permutations at or above the observed statistic per line; the batch's maximum per permutation */
     uint8_t *rows; size_t rows_cap; int row_width;       /* vcf2epi: one dataset row per line */
     int stats;                                           /* aggregate / stats: the counters of hpgv_stats_text */
@@ -234,6 +235,16 @@ typedef struct {
     long n_clumps, n_truncated;
 } run_clump_t;
 
+/* sample relatedness (hpgv_run_genome): one n_samples x n_samples buffer of pair counts per device of the run, zeroed when the
+ * run starts, which the batches' hpgv_ibs_text calls add to (a batch goes to the device that holds its text, else the devices take
+ * turns); the terms of the written records that are used, added in file order by the writer loop, and their number */
+typedef struct {
+    int n_dev; hpgv_ctx **ctx; hpgv_ibs_counts **d_counts;
+    unsigned next;
+    double sum[5]; long used;
+    long n_pairs;                                        /* pairs written to the file */
+} run_genome_t;
+
 /* one file run: built by its public entry (hpgv_run_*), its stages and the pipeline's threads (through the batches) share it */
 typedef struct run {
     run_tool_t tool;
@@ -252,6 +263,7 @@ typedef struct run {
     int n_perms; uint64_t perm_seed; run_perm_t *PM;      /* the permutation tools */
     const hpgv_run_clump_options_t *clump; run_clump_t *CL;      /* RUN_CHISQ / RUN_FISHER with <out>.clumped beside the file (NULL: without) */
     long n_clumps, n_truncated;                          /* ... what run_clump_write counted, kept past the store */
+    double min_pi_hat; run_genome_t *GN; long n_pairs;   /* RUN_GENOME: the threshold, the run's counts, the pairs written (kept past them) */
     double t_opened, t_header, t_sort;
 } run_t;
 
@@ -392,6 +404,11 @@ int run_clump_new(run_t *R);
 int run_clump_add(run_t *R, const run_batch_t *b);
 int run_clump_write(run_t *R, const char *out_path);
 void run_clump_free(run_t *R);
+int run_genome_new(run_t *R);                            /* an hpgv status, the message in g_err */
+hpgv_ctx *run_genome_device(run_t *R, const run_batch_t *b, hpgv_ibs_counts **d_counts);      /* the context and buffer a batch's engine call uses */
+void run_genome_add(run_t *R, const run_batch_t *b);     /* and the run's count of records that took part */
+int run_genome_write(run_t *R, const char *out_path);
+void run_genome_free(run_t *R);
 int run_stats_new(run_t *R);
 void run_stats_add(run_t *R, const run_batch_t *b);      /* and the batch's lines to the per-phenotype files */
 int run_stats_write(const run_t *R, const char *prefix);

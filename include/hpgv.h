@@ -454,6 +454,68 @@ int  hpgv_ld_edges_dev(hpgv_ctx *ctx, const uint8_t *d_gt, size_t pitch, int n_v
                        const uint8_t *d_skip /* may be NULL */, double min_r2, hpgv_ld_edge *d_edges, uint64_t edge_cap,
                        uint64_t *d_n_edges, void *stream);
 
+/* ---- IBS: pairwise identity-by-state counts between SAMPLES and the relatedness estimates made of them (PLINK's --genome; no
+ *      reference counterpart): duplicates, undeclared relatives and sample swaps, the first QC step of a cohort.  Parity with
+ *      PLINK is UNPINNED, as Fisher's is: no PLINK was at hand, and the formulas below are this project's definition.
+ *
+ *      The genotype class g of an HPGV8 byte is LD's ("LD" above): missing if either nibble is 0xF, else the number of non-zero
+ *      nibbles, 0, 1 or 2 ("1/2" is 2); pad bytes are 0xFF.  For byte COLUMNS i < j of one matrix, summed over the rows that are
+ *      not skipped and where both columns are called:
+ *          n = rows where both are called      ibs0 = rows with |g_i - g_j| = 2      ibs2 = rows with g_i = g_j
+ *          ibs1 = n - ibs0 - ibs2
+ *      The contraction runs over the ROWS of the variant-major matrix: four i8 products with exact i32 sums on the matrix cores
+ *      (csrc/hpgv_ibs_kernels.h).  With the planes v = valid, h = [g = 1], m = v - h and s = g - 1 on valid bytes (else 0):
+ *          P1 = s.s   P2 = m.m   P3 = h.h   P4 = v.v      ibs0 = (P2 - P1) / 2   ibs2 = (P2 + P1) / 2 + P3   n = P4
+ *
+ *      Expected IBS under IBD (method of moments).  Per row, over the columns: the class counts n0, n1, n2;
+ *      X = 2 n0 + n1, Y = n1 + 2 n2, T = X + Y.  A row is USED iff it is not skipped and T >= 4.  fall(x, k) =
+ *      x (x - 1) ... (x - k + 1), x converted to double first, the factors multiplied left to right, fall(x, 0) = 1;
+ *      F(a, b) = (fall(X, a) * fall(Y, b)) / fall(T, a + b), the unbiased estimate of p^a q^b when drawing without replacement.
+ *      The terms of a row, in this operation order:
+ *          t00 = 2 F(2,2)                          t01 = 4 F(3,1) + 4 F(1,3)        t02 = (F(4,0) + F(0,4)) + 4 F(2,2)
+ *          t11 = 2 F(2,1) + 2 F(1,2)               t12 = ((F(3,0) + F(0,3)) + F(2,1)) + F(1,2)
+ *      E = {E00, E01, E02, E11, E12}: the sums of the terms over the used rows, added sequentially in file order in f64, divided
+ *      by the number of used rows.
+ *
+ *      Per pair, f64 without contraction, in this order, S = (double)n:
+ *          z0 = ibs0 / (E00 S)      z1 = (ibs1 - z0 (E01 S)) / (E11 S)      z2 = (ibs2 - z0 (E02 S) - z1 (E12 S)) / S
+ *          clamps, in sequence:           z0 > 1: (1, 0, 0);   z1 > 1: (0, 1, 0);   z2 > 1: (0, 0, 1)
+ *          renormalisations, in sequence: z0 < 0: t = z1 + z2, z1 /= t, z2 /= t, z0 = 0; the same for z1 < 0 over z0 and z2;
+ *                                         the same for z2 < 0 over z0 and z1
+ *          PI_HAT = z1 / 2 + z2      DST = ((double)ibs2 + 0.5 (double)ibs1) / S
+ *      Nothing else is special-cased: n = 0 or a zero E give the IEEE NaN or inf that flow through these steps.  Only WHETHER a
+ *      value is NaN is defined, not which NaN.
+ *
+ *      Out of scope: PLINK's PPC and RATIO columns, its re-projection of (z0, z1, z2) onto the "biologically plausible" region,
+ *      a genetic relationship matrix, and a group form of the batch calls. */
+typedef struct { int32_t n, ibs0, ibs1, ibs2; } hpgv_ibs_counts;                       /* 16 bytes */
+typedef struct { int32_t i, j; hpgv_ibs_counts c; double pi_hat; } hpgv_ibs_pair;      /* 32 bytes, i < j */
+/* d_gt: any matrix of HPGV8 rows `pitch` bytes apart; the bytes of a row at and past n_cols are never counted, whatever they
+ * hold.  d_skip (may be NULL): != 0 = the row takes no part.  The call ADDS the counts of these rows to d_counts[i * n_cols + j]
+ * for 0 <= i < j < n_cols with relaxed device-scope atomics -- calls on pieces of a matrix, on several streams and from several
+ * threads accumulate into one buffer -- and never touches any other element.  The caller zeroes the n_cols x n_cols records
+ * (hpgv_memset_dev) before the first call and keeps the rows accumulated into one buffer below 2^31.  Needs no cohort.
+ * n_variants == 0 or n_cols < 2 succeed and write nothing.  Refusals: HPGV_ERR_INVALID for n_variants < 0, n_cols < 0 or
+ * n_cols > pitch, a pitch that is 0, not a multiple of 16 or 4 GiB and more, d_gt or d_counts not 16-byte aligned;
+ * HPGV_ERR_UNSUPPORTED where ceil(n_cols / 64)^2 / 2 tile pairs times the row ranges exceed 2^31 workgroups.  Asynchronous on
+ * `stream`; under option "profile" its time is the statistics time of hpgv_last_kernel_ms.  A launch reads the matrix
+ * ceil(n_cols / 64) times, from L2 where the workgroups of an XCD share their rows. */
+int  hpgv_ibs_pairs_dev(hpgv_ctx *ctx, const uint8_t *d_gt, size_t pitch, int n_variants, int n_cols,
+                        const uint8_t *d_skip /* may be NULL */, hpgv_ibs_counts *d_counts /* n_cols x n_cols */, void *stream);
+/* d_class4[4 * row + k] = {n0, n1, n2, missing} of the row over the columns below n_cols, zeros for a skipped row: every
+ * element written, one wave per row.  Matrix, refusals and alignment as hpgv_ibs_pairs_dev (d_class4 16-byte aligned). */
+int  hpgv_ibs_class_counts_dev(hpgv_ctx *ctx, const uint8_t *d_gt, size_t pitch, int n_variants, int n_cols,
+                               const uint8_t *d_skip /* may be NULL */, int32_t *d_class4, void *stream);
+/* The pairs of a counts matrix with PI_HAT >= min_pi_hat, hpgv_ld_edges_dev's contract: exactly the set {i < j : PI_HAT >=
+ * min_pi_hat} with pi_hat bit for bit hpgv_ibs_genome's; NaN never compares >=, so a pair with a NaN PI_HAT never appears.  The
+ * ORDER of the list is not defined.  The call zeroes *d_n itself on `stream`; it ends as the TRUE number of qualifying pairs
+ * even where that exceeds cap.  At most cap records are stored and nothing past them; cap == 0 with d_pairs == NULL is a legal
+ * count-only call.  Per wave the qualifying lanes are counted by ballot and claim their places with ONE relaxed 64-bit add.
+ * HPGV_ERR_INVALID for a NaN min_pi_hat, n_cols < 0, a NULL E or d_n, d_pairs NULL with cap > 0, d_counts or d_pairs not 16-byte
+ * aligned, d_n not 8-byte aligned; HPGV_ERR_UNSUPPORTED for n_cols x ceil(n_cols / 256) above 2^31 - 1. */
+int  hpgv_ibs_select_dev(hpgv_ctx *ctx, const hpgv_ibs_counts *d_counts, int n_cols, const double E[5], double min_pi_hat,
+                         hpgv_ibs_pair *d_pairs, uint64_t cap, uint64_t *d_n, void *stream);
+
 /* ---- the variant-sharded resident scan of a GROUP context: what the runner's worker loop
  *      (assoc_runner.c:106-207, tdt_runner.c:150-200, stats_runner.c:176-215) becomes when the cohort lies in the HBM of
  *      the group's devices.  Variants are independent (assoc.c:38-82, tdt.c:41-271), so member g owns the contiguous
@@ -962,6 +1024,26 @@ int  hpgv_ld_edges(hpgv_ctx *ctx, const uint8_t *gt, size_t pitch, int n_variant
 int  hpgv_ld_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, int max_lines, int *n_lines,
                   uint64_t *line_off, uint32_t *field_off, int32_t *status, int window, double *r2, int32_t *counts6 /* may be NULL */);
 
+/* ---- IBS on a host batch and on a text ("IBS" above; synchronous, thread-safe) ------------------------------------------ */
+/* gt: n_variants rows in VCF column order, `pitch` bytes apart (pitch >= n_samples).  The columns are those of the
+ * HPGV_LAYOUT_STATS layout -- every sample, in VCF order; its bytes are stats flags, so the kernels read the HPGV8 rows
+ * themselves, in the stats layout's pitch -- for hpgv_ibs_class_counts_dev and hpgv_ibs_pairs_dev with n_cols = n_samples.
+ * skip (host, per row, may be NULL): != 0 = the row takes no part.  class4 (host): 4 int32 per row, zeros for a skipped row.
+ * d_counts: DEVICE memory, n_samples x n_samples records, 16-byte aligned, zeroed by the caller before the first batch and
+ * ACCUMULATED into; calls from several threads may share it.  HPGV_ERR_STATE without hpgv_set_stats_cohort.  A GROUP context
+ * returns HPGV_ERR_UNSUPPORTED: the counts of a run lie on one device (a caller with several devices keeps one buffer per
+ * device and adds them: integers, any order). */
+int  hpgv_ibs(hpgv_ctx *ctx, const uint8_t *gt, size_t pitch, int n_variants, const uint8_t *skip /* may be NULL */,
+              int32_t *class4, hpgv_ibs_counts *d_counts);
+/* tokenizer -> stats layout -> the same two kernels with no matrix crossing the bus.  A line with status 1 (not a record) or
+ * flagged HPGV_LINE_FILTERED -- the lines a caller of hpgv_assoc_text drops -- is a skipped row, and so is a line the tokenizer
+ * flags as chromosome X (CHROM exactly "X"; Y and MT get no rule, as elsewhere).  class4: max_lines x 4 int32,
+ * *n_lines x 4 of them written, zeros for a skipped line.  Where *n_lines comes back larger than max_lines NOTHING was added to
+ * d_counts and class4 is not written: the counts accumulate, so the caller calls again with room and no line is counted twice.
+ * status may be NULL.  State and refusals as hpgv_ibs. */
+int  hpgv_ibs_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, int max_lines, int *n_lines,
+                   uint64_t *line_off, uint32_t *field_off, int32_t *status, int32_t *class4, hpgv_ibs_counts *d_counts);
+
 /* ---- label permutation, host side: no GPU call, no context, usable without a device ------------------------------- */
 /* n_perms label rows for hpgv_set_perm_labels, labels_out[p * n_samples + j]: row p is a uniform shuffle of the cohort
  * columns' conditions (1 = affected), so every row has as many ones as the cohort has affected samples; HPGV_COND_OTHER
@@ -994,6 +1076,12 @@ double hpgv_ld_r2(const int32_t counts6[6]);
  * HPGV_ERR_INVALID, and so are n < 0 and a NULL p, index_of or n_clumps.  O(n log n + n_edges).  No GPU call, no context. */
 int  hpgv_clump(int n, const double *p, const hpgv_ld_edge *edges, uint64_t n_edges, double p1,
                 int32_t *index_of, int32_t *clump_order /* may be NULL */, int *n_clumps);
+/* The five terms {t00, t01, t02, t11, t12} of one row's class counts by the expressions of "IBS" above; returns 1 for a used row
+ * (T >= 4), else 0 with zeros (a negative count included).  Whether the row is skipped is the caller's to know.  No GPU call. */
+int  hpgv_ibs_terms(int32_t n0, int32_t n1, int32_t n2, double t[5]);
+/* out = {Z0, Z1, Z2, PI_HAT, DST} of one pair's counts with E = {E00, E01, E02, E11, E12}: the function k_ibs_select calls,
+ * built for the host.  No GPU call, no context. */
+void hpgv_ibs_genome(const hpgv_ibs_counts *c, const double E[5], double out[5]);
 
 /* streaming-read ceiling probe: reads `bytes` from d_buf with the scan's load
  * shape and no arithmetic; returns the kernel time in ms (diagnostic) */

@@ -506,6 +506,21 @@ int  hpgv_run_aggregate(const char *vcf_path, const char *out_path, int overwrit
  * (header lines name the columns). */
 int  hpgv_run_stats(const char *vcf_path, const char *ped_path, const char *out_prefix, size_t batch_bytes,
                     long *n_variants_out);
+/* Sample relatedness (include/hpgv.h "IBS"; PLINK's --genome, parity unpinned): duplicates, undeclared relatives, sample swaps.
+ * Every batch goes through hpgv_ibs_text into one buffer of pair counts per device of the run (the kernel's atomics make the
+ * engine threads safe; the devices' buffers are added when the run ends: integers, any order).  The lines hpgv_run_assoc would
+ * not count -- not a record -- and the lines on chromosome "X" take no part.  The writer stage adds hpgv_ibs_terms of the
+ * records' class counts in file order, so E, and with it the file, does not depend on batch_bytes, engine threads or devices.
+ * As in hpgv_run_stats, the filters of hpgv_run_set_filters and hpgv_run_set_record_filters are not applied.  When the input is
+ * read, hpgv_ibs_select_dev gives the pairs with PI_HAT >= min_pi_hat (a NaN PI_HAT never qualifies; the call is repeated once
+ * with room when the list was too short), and out_path gets the header line
+ *     #IID1 IID2 NM IBS0 IBS1 IBS2 Z0 Z1 Z2 PI_HAT DST
+ * and one line per pair, tab-separated, sorted by (column of IID1, column of IID2): the sample names of the #CHROM line, the four
+ * counts, and hpgv_ibs_genome's five values as hpgv_host_format_f6 prints them.  *n_variants_out: the records that took part;
+ * *n_pairs_out: the pairs written.  Input forms (plain, gzip, bgzip) as hpgv_run_assoc.  A NULL path or a NaN min_pi_hat:
+ * HPGV_ERR_INVALID before anything is opened, and no file is written.  The counts take 16 n_samples^2 bytes of device memory. */
+int  hpgv_run_genome(const char *vcf_path, const char *out_path, double min_pi_hat, size_t batch_bytes,
+                     long *n_variants_out, long *n_pairs_out);
 /* stage times of the last run on this process: {read, engine, write, sort, total} seconds and the number of
  * batches; read / engine / write overlap (three threads, three batch buffers in rotation).  The reader and
  * formatter teams use HPGV_IO_THREADS threads (environment; default half the cores, at most 16);
