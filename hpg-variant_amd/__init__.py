@@ -71,6 +71,7 @@ SYMBOLS = [
     "hpgv_ld_edges_dev", "hpgv_ld_edges", "hpgv_clump",
     "hpgv_rows_gather_scratch_bytes", "hpgv_rows_gather_dev", "hpgv_assoc_select_text",
     "hpgv_ibs_pairs_dev", "hpgv_ibs_class_counts_dev", "hpgv_ibs_select_dev", "hpgv_ibs", "hpgv_ibs_text", "hpgv_ibs_terms", "hpgv_ibs_genome",
+    "hpgv_grm_table_dev", "hpgv_grm_pairs_dev", "hpgv_grm", "hpgv_grm_text", "hpgv_grm_table", "hpgv_grm_frac_bits", "hpgv_grm_value", "hpgv_grm_plan_rows",
 ]
 
 # hpgv_ld_edge: {int32 a, b; double r2}, 16 bytes
@@ -78,6 +79,9 @@ LD_EDGE = np.dtype([("a", np.int32), ("b", np.int32), ("r2", np.float64)])
 # hpgv_ibs_counts: {int32 n, ibs0, ibs1, ibs2}, 16 bytes; hpgv_ibs_pair: {int32 i, j; hpgv_ibs_counts c; double pi_hat}, 32 bytes
 IBS_COUNTS = np.dtype([("n", np.int32), ("ibs0", np.int32), ("ibs1", np.int32), ("ibs2", np.int32)])
 IBS_PAIR = np.dtype([("i", np.int32), ("j", np.int32), ("c", IBS_COUNTS), ("pi_hat", np.float64)])
+# hpgv_grm_acc: {int64 sq, n}, 16 bytes; a row's table record of hpgv_grm_table_dev: {int8 hi[4], lo[4]}, 8 bytes
+GRM_ACC = np.dtype([("sq", np.int64), ("n", np.int64)])
+GRM_TAB = np.dtype([("hi", np.int8, 4), ("lo", np.int8, 4)])
 
 
 class HpgvError(RuntimeError):
@@ -257,6 +261,15 @@ def load():
     L.hpgv_ibs_terms.argtypes = [i32, i32, i32, vp]
     L.hpgv_ibs_genome.argtypes = [vp, vp, vp]
     L.hpgv_ibs_genome.restype = None
+    L.hpgv_grm_table_dev.argtypes = [vp, vp, i32, i32, C.c_double, vp, vp, vp, vp]
+    L.hpgv_grm_pairs_dev.argtypes = [vp, vp, sz, i32, i32, vp, vp, vp, vp]
+    L.hpgv_grm.argtypes = [vp, vp, sz, i32, vp, i32, C.c_double, vp, vp]
+    L.hpgv_grm_text.argtypes = [vp, C.c_char_p, sz, i32, C.POINTER(i32), vp, vp, vp, i32, C.c_double, vp, vp]
+    L.hpgv_grm_table.argtypes = [i32, i32, i32, i32, C.c_double, vp, vp]
+    L.hpgv_grm_frac_bits.argtypes = [C.c_double]
+    L.hpgv_grm_value.argtypes = [vp, i32]
+    L.hpgv_grm_value.restype = C.c_double
+    L.hpgv_grm_plan_rows.argtypes = [i32, i32, i32]
     L.hpgv_rows_gather_scratch_bytes.argtypes = [i32]
     L.hpgv_rows_gather_scratch_bytes.restype = sz
     L.hpgv_rows_gather_dev.argtypes = [vp, vp, sz, sz, i32, vp, vp, sz, vp, vp, vp, vp]
@@ -332,6 +345,23 @@ def run_genome(vcf_path, out_path, min_pi_hat=0.0, batch_bytes=1 << 22):
     rc = H.hpgv_run_genome(enc(vcf_path), enc(out_path), float(min_pi_hat), batch_bytes, C.byref(n), C.byref(k))
     if rc != OK:
         e = HpgvError("hpgv_run_genome -> %d: %s" % (rc, (H.hpgv_host_last_error() or b"").decode(errors="replace")))
+        e.code = rc
+        raise e
+    return n.value, k.value
+
+
+def run_grm(vcf_path, out_prefix, min_maf=0.01, batch_bytes=1 << 22):
+    """hpgv_run_grm of libhpgv_host.so (include/hpgv_host.h): <out_prefix>.grm.bin, .grm.N.bin and .grm.id of the VCF's samples at
+    hpgv_grm_frac_bits(min_maf).  Paths may be None (the call then fails with ERR_INVALID).  Returns (variants used, samples)."""
+    _build.build_host_lib()
+    H = C.CDLL(_build.HOSTLIB)
+    H.hpgv_run_grm.argtypes = [C.c_char_p, C.c_char_p, C.c_double, C.c_size_t, C.POINTER(C.c_long), C.POINTER(C.c_long)]
+    H.hpgv_host_last_error.restype = C.c_char_p
+    n, k = C.c_long(0), C.c_long(0)
+    enc = lambda q: None if q is None else os.fsencode(q)
+    rc = H.hpgv_run_grm(enc(vcf_path), enc(out_prefix), float(min_maf), batch_bytes, C.byref(n), C.byref(k))
+    if rc != OK:
+        e = HpgvError("hpgv_run_grm -> %d: %s" % (rc, (H.hpgv_host_last_error() or b"").decode(errors="replace")))
         e.code = rc
         raise e
     return n.value, k.value
@@ -431,6 +461,44 @@ def ibs_genome(counts, E):
     for k in range(len(flat)):
         L.hpgv_ibs_genome(C.c_void_p(flat[k:k + 1].ctypes.data), _ptr(e), _ptr(out[k]))
     return out.reshape(shape + (5,))
+
+
+def grm_table(class4, frac_bits, min_maf):
+    """hpgv_grm_table on rows of class counts (..., >= 3) = {n0, n1, n2[, missing]}: (used (...) bool, table (...) GRM_TAB).  No
+    device needed."""
+    c = _np(class4, np.int32)
+    flat = c.reshape(-1, c.shape[-1])
+    L = load()
+    used, tab = np.zeros(len(flat), bool), np.zeros(len(flat), GRM_TAB)
+    raw = tab.view(np.int8).reshape(len(flat), 8)
+    for k, row in enumerate(flat):
+        used[k] = L.hpgv_grm_table(int(row[0]), int(row[1]), int(row[2]), int(frac_bits), float(min_maf), _ptr(raw[k, :4]), _ptr(raw[k, 4:])) != 0
+    return used.reshape(c.shape[:-1]), tab.reshape(c.shape[:-1])
+
+
+def grm_frac_bits(min_maf):
+    """hpgv_grm_frac_bits: the largest frac_bits that loses no row with MAF >= min_maf, -1 for min_maf outside (0, 0.5]"""
+    return int(load().hpgv_grm_frac_bits(float(min_maf)))
+
+
+def grm_value(acc, frac_bits):
+    """hpgv_grm_value on a GRM_ACC array (or (..., 2) int64 = {sq, n}): (...) float64.  No device needed."""
+    a = np.ascontiguousarray(acc)
+    if a.dtype == GRM_ACC:
+        shape, flat = a.shape, a.reshape(-1)
+    else:
+        a = _np(acc, np.int64)
+        shape, flat = a.shape[:-1], a.reshape(-1, 2)
+    L = load()
+    out = np.zeros(len(flat), np.float64)
+    for k in range(len(flat)):
+        out[k] = L.hpgv_grm_value(C.c_void_p(flat[k:k + 1].ctypes.data), int(frac_bits))
+    return out.reshape(shape)
+
+
+def grm_plan_rows(n_variants, n_cols, n_cus):
+    """hpgv_grm_plan_rows: rows per row range of hpgv_grm_pairs_dev's launch"""
+    return int(load().hpgv_grm_plan_rows(int(n_variants), int(n_cols), int(n_cus)))
 
 
 def clump(p, edges, p1):
@@ -774,6 +842,24 @@ class Engine:
         self._chk(self.L.hpgv_ibs_text(self.h, text, len(text), max_lines, C.byref(nl), None, None, _ptr(status), _ptr(class4), d_counts))
         return _text_result(nl, max_lines, status=status, class4=class4)
 
+    def grm(self, gt, d_acc, frac_bits, min_maf, skip=None):
+        """hpgv_grm: class4 (nv, 4) of the rows; their pair sums are ADDED to the device records d_acc (n_samples x n_samples
+        GRM_ACC, zeroed by the caller: memset_dev)."""
+        gt = _np(gt, np.uint8)
+        nv, pitch = gt.shape
+        sk = None if skip is None else _np(skip, np.uint8)
+        class4 = np.zeros((nv, 4), np.int32)
+        self._chk(self.L.hpgv_grm(self.h, _ptr(gt), pitch, nv, _ptr(sk), int(frac_bits), float(min_maf), _ptr(class4), d_acc))
+        return class4
+
+    def grm_text(self, text, d_acc, frac_bits, min_maf, max_lines=None):
+        """hpgv_grm_text: grm on VCF data lines (dropped lines and chromosome-X lines are skipped rows): status and class4 per line."""
+        text, max_lines, m, status, nl = _text_call(text, max_lines)
+        class4 = np.zeros((m, 4), np.int32)
+        self._chk(self.L.hpgv_grm_text(self.h, text, len(text), max_lines, C.byref(nl), None, None, _ptr(status), int(frac_bits), float(min_maf),
+                                       _ptr(class4), d_acc))
+        return _text_result(nl, max_lines, status=status, class4=class4)
+
     def ibs_select(self, d_counts, n_cols, E, min_pi_hat, cap=None):
         """hpgv_ibs_select_dev on device records: the pairs with PI_HAT >= min_pi_hat as an IBS_PAIR array sorted by (i, j).  Without
         cap the call is repeated once with room when the first list was too short; with it, (pairs or None, count) comes back."""
@@ -1091,6 +1177,12 @@ class Engine:
 
     def ibs_class_counts_dev(self, d_gt, pitch, n_variants, n_cols, d_class4, d_skip=None, stream=None):
         self._chk(self.L.hpgv_ibs_class_counts_dev(self.h, d_gt, pitch, n_variants, n_cols, d_skip, d_class4, stream))
+
+    def grm_table_dev(self, d_class4, n_variants, frac_bits, min_maf, d_skip, d_tab, d_n_used=None, stream=None):
+        self._chk(self.L.hpgv_grm_table_dev(self.h, d_class4, n_variants, int(frac_bits), float(min_maf), d_skip, d_tab, d_n_used, stream))
+
+    def grm_pairs_dev(self, d_gt, pitch, n_variants, n_cols, d_tab, d_acc, d_skip=None, stream=None):
+        self._chk(self.L.hpgv_grm_pairs_dev(self.h, d_gt, pitch, n_variants, n_cols, d_skip, d_tab, d_acc, stream))
 
     def ibs_select_dev(self, d_counts, n_cols, E, min_pi_hat, d_pairs, cap, d_n, stream=None):
         e = _np(E, np.float64)

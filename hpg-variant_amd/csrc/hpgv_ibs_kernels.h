@@ -127,7 +127,7 @@ struct IbsArgs {
     unsigned per_xcd;                // ceil(items / 8)
 };
 
-__global__ __launch_bounds__(256) void k_ibs_pairs(const IbsArgs A) {
+static __global__ __launch_bounds__(256) void k_ibs_pairs(const IbsArgs A) {
     __shared__ uint4 img[2][2][4][IBS_T * IBS_LDS_COL];                    // [buffer][side I / J][plane v, h, m, s]
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -259,8 +259,8 @@ __global__ __launch_bounds__(256) void k_ibs_pairs(const IbsArgs A) {
 // {n0, n1, n2, missing} of every row over the columns below n_cols, one wave per row; a skipped row gets zeros.  No scan of the
 // engine yields these for a matrix without a cohort: the stats counters split the calls by allele pair (a "1/2" is in none of
 // their four cells) and the model scan's classes are per phenotype group of the assoc layout.
-__global__ __launch_bounds__(256) void k_ibs_class_counts(const uint8_t *__restrict__ gt, size_t pitch, int n_variants, int n_cols,
-                                                          const uint8_t *__restrict__ skip, int4 *__restrict__ class4) {
+static __global__ __launch_bounds__(256) void k_ibs_class_counts(const uint8_t *__restrict__ gt, size_t pitch, int n_variants, int n_cols,
+                                                                 const uint8_t *__restrict__ skip, int4 *__restrict__ class4) {
     const int lane = threadIdx.x & 63;
     const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= n_variants) return;                                         // (the whole wave)
@@ -300,8 +300,8 @@ struct IbsE { double e[5]; };
 // the matrix, blocks_per_row workgroups of 256 columns per row i, a workgroup wholly at or below the diagonal returns.  Per wave
 // the qualifying lanes are counted by ballot and claim their places with ONE relaxed 64-bit add, as k_ld_edges does; a record
 // goes out as two 16-byte stores when its index is below `cap`.  NaN >= x is false: a NaN PI_HAT never qualifies.
-__global__ __launch_bounds__(256) void k_ibs_select(const int4 *__restrict__ counts, int n_cols, int blocks_per_row, const IbsE E, double min_pi_hat,
-                                                    uint4 *__restrict__ pairs, unsigned long long cap, unsigned long long *__restrict__ n_pairs) {
+static __global__ __launch_bounds__(256) void k_ibs_select(const int4 *__restrict__ counts, int n_cols, int blocks_per_row, const IbsE E, double min_pi_hat,
+                                                           uint4 *__restrict__ pairs, unsigned long long cap, unsigned long long *__restrict__ n_pairs) {
     const int lane = threadIdx.x & 63;
     const int i = (int)(blockIdx.x / (unsigned)blocks_per_row);
     const int jb = (int)(blockIdx.x % (unsigned)blocks_per_row) * 256;

@@ -2,7 +2,7 @@
 // libhpgv.so: hpgv_capi.hip (contexts, options, cohorts, memory, streams, text aliases), hpgv_scan_capi.hip (the
 // device-resident *_dev launchers), hpgv_text_capi.hip (tokenizer, the text entry points' front half),
 // hpgv_tool_capi.hip (per-batch and text entry points), hpgv_lines_capi.hip (partition / multisplit of lines), and the
-// units whose kernel instantiations compile on their own (hpgv_perm_capi.hip, hpgv_ld_capi.hip, hpgv_ibs_capi.hip, hpgv_epi_capi.hip, hpgv_epi_generic_capi.hip, hpgv_statsall_capi.hip, hpgv_inflate_capi.hip, hpgv_group_capi.hip).
+// units whose kernel instantiations compile on their own (hpgv_perm_capi.hip, hpgv_ld_capi.hip, hpgv_ibs_capi.hip, hpgv_grm_capi.hip, hpgv_epi_capi.hip, hpgv_epi_generic_capi.hip, hpgv_statsall_capi.hip, hpgv_inflate_capi.hip, hpgv_group_capi.hip).
 // A synchronous entry point has two halves that meet in a Staged: the front puts the call's matrix on the device -- text_front /
 // text_front_skip for a text, stage_chain for a host batch that goes through the kernel chain -- and the tool's back half takes it
 // from there; the permutation calls build theirs from the halves of hpgv_assoc's and hpgv_tdt's (assoc_chain, ..., below).
@@ -135,7 +135,7 @@ struct TextMeta {
 };
 
 // the genotype matrix of one synchronous call once it is on the device: what the back halves of hpgv_tool_capi.hip,
-// hpgv_perm_capi.hip, hpgv_ld_capi.hip and hpgv_ibs_capi.hip read, whether a batch (batch_sources / stage_chain) or a text (text_front,
+// hpgv_perm_capi.hip, hpgv_ld_capi.hip, hpgv_ibs_capi.hip and hpgv_grm_capi.hip read, whether a batch (batch_sources / stage_chain) or a text (text_front,
 // hpgv_text_capi.hip) put it there
 struct Staged {
     const uint8_t *d_raw = nullptr;   // VCF column order: the slot's `raw`, or the caller's rows where the device can read them
@@ -504,6 +504,17 @@ void tdt_split_counts(const std::vector<int32_t> &tu, int32_t *t1, int32_t *t2);
 // filtered, p <= p_max; p_i at d_p + i * p_stride) numbered into sel, their raw rows compacted on the device and copied to rows_out
 int select_rows(hpgv_ctx *ctx, Slot *s, const Staged &S, int n_samples, const int32_t *status, const char *d_p, size_t p_stride, double p_max,
                 int32_t *sel, uint8_t *rows_out, size_t rows_pitch, int rows_cap, int *n_sel);
+// defined in hpgv_ibs_capi.hip, shared with hpgv_grm_capi.hip: the checks of a device matrix whose COLUMNS are contracted, and
+// the front of the synchronous calls' back halves -- the raw matrix of a staged call in a pitch the kernels take, the rows' skip
+// bytes on the device (null where none is set and need_skip is false), k_ibs_class_counts queued on the slot's stream
+int ibs_matrix_check(const hpgv_ctx *ctx, const uint8_t *d_gt, size_t pitch, int n_variants, int n_cols);
+struct ColsFront {
+    const uint8_t *d_gt = nullptr;
+    size_t pitch = 0;
+    uint8_t *d_skip = nullptr;
+    int32_t *d_class4 = nullptr;
+};
+int cols_front(hpgv_ctx *ctx, Slot *s, const Staged &S, const uint8_t *skip, bool x_too, bool need_skip, ColsFront *F);
 
 // defined in hpgv_statsall_capi.hip: k_stats_all2 on a batch (0 = launched, 1 = not a batch it takes: run k_stats_all)
 namespace hpgv { struct StatsAllArgs; }

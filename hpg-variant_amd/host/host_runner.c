@@ -1,5 +1,5 @@
 /* host_runner.c -- the file runners: reader -> engine threads -> writer (hpgv_run_assoc / tdt / aggregate / stats / vcf2epi /
- * filter / split / genome).  The VCF tools' own batch steps and writers are in host_vcftools.c, what a run keeps beside its result file in
+ * filter / split / genome / grm).  The VCF tools' own batch steps and writers are in host_vcftools.c, what a run keeps beside its result file in
  * host_sideout.c.
  * Part of libhpgv_host.so (see hpgv_host_internal.h for the map of its units). */
 #include "hpgv_host_internal.h"
@@ -128,6 +128,11 @@ static int engine_call(run_t *R, run_batch_t *b, const char **what, int *again) 
         hpgv_ctx *ctx = run_genome_device(R, b, &d_counts);
         return hpgv_ibs_text(ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status, b->ints, d_counts);
     }
+    case RUN_GRM: { *what = "hpgv_grm_text";               /* the same dealing, into that device's pair sums */
+        hpgv_ibs_counts *d_acc = NULL;
+        hpgv_ctx *ctx = run_genome_device(R, b, &d_acc);
+        return hpgv_grm_text(ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status, R->frac_bits, R->min_maf, b->ints, (hpgv_grm_acc *)d_acc);
+    }
     }
     return rc;
 }
@@ -228,8 +233,8 @@ static int run_cohort(run_t *R, const char *vcf_path, const char *ped_path) {
     sample_ids_t *ids = sample_ids_new((size_t)n_samples);
     for (int j = 0; j < n_samples; j++) sample_ids_put(ids, R->names[j], j);
     switch (R->tool) {
-    case RUN_AGGREGATE: case RUN_STATS: case RUN_FILTER: case RUN_SPLIT: case RUN_GENOME: {
-        /* the engine scans the stats layout of all columns (get_variants_stats / get_sample_stats, hpgv_filter_text, hpgv_ibs_text); stats with a
+    case RUN_AGGREGATE: case RUN_STATS: case RUN_FILTER: case RUN_SPLIT: case RUN_GENOME: case RUN_GRM: {
+        /* the engine scans the stats layout of all columns (get_variants_stats / get_sample_stats, hpgv_filter_text, hpgv_ibs_text, hpgv_grm_text); stats with a
          * PED: its phenotype groups, and its trios give the Mendelian errors (stats_runner.c:165-170,194-198) */
         rc = hpgv_set_stats_cohort(g_ctx, n_samples);
         g_stats_key.set = 0;
@@ -376,7 +381,7 @@ static int create_out(FILE **f, char **path, const char *prefix, const char *suf
  * save_rejected (filter_runner.c:63-68); stats: one file per phenotype (stats_runner.c:267-297), and its accumulator */
 static int run_outputs(run_t *R, const char *out_path) {
     if ((R->clump && run_clump_new(R)) || (tool_perm(R->tool) && run_perm_new(R))) return HPGV_ERR_NOMEM;
-    if (R->tool == RUN_GENOME) return run_genome_new(R);      /* (its one file is written when the run ends: run_genome_write) */
+    if (R->tool == RUN_GENOME || R->tool == RUN_GRM) return run_genome_new(R);      /* (their files are written when the run ends: run_genome_write, run_grm_write) */
     const char *suffix = R->tool == RUN_STATS ? ".stats-variants" : R->tool == RUN_FILTER ? (R->out_bgzf ? ".filtered.gz" : ".filtered") : "";
     int rc = R->tool == RUN_SPLIT ? HPGV_OK : create_out(&R->out, &R->path, out_path, suffix);
     if (!rc && R->tool == RUN_FILTER) rc = create_out(&R->out_rej, &R->path_rej, out_path, R->out_bgzf ? ".rejected.gz" : ".rejected");
@@ -435,7 +440,7 @@ static int run_headers(run_t *R) {
         return HPGV_OK;
     case RUN_FILTER: return write_filter_header(out, R) || (R->save_rejected && write_filter_header(R->out_rej, R)) ? HPGV_ERR_INVALID : HPGV_OK;
     case RUN_SPLIT: break;                               /* (each file gets the input's header when it is created) */
-    case RUN_GENOME: break;                              /* (no file yet) */
+    case RUN_GENOME: case RUN_GRM: break;                /* (no file yet) */
     }
     return HPGV_OK;
 }
@@ -522,6 +527,7 @@ static int run_pipeline(run_t *R, size_t batch_bytes) {
                 if (R->tool == RUN_STATS && !bad) run_stats_add(R, b);      /* (and the group files' lines: by this thread) */
                 break;
             case RUN_GENOME: run_genome_add(R, b); break;       /* no line per record: the records' terms, in file order */
+            case RUN_GRM: run_grm_add(R, b); break;             /* no line per record: the used records are counted */
             }
             fmt_set ^= use_fw;
             const double dt = now_s() - t0;
@@ -584,7 +590,9 @@ static int run_finish(run_t *R, int rc, const char *out_path) {
         R->n_clumps = R->CL->n_clumps; R->n_truncated = R->CL->n_truncated;      /* for hpgv_run_assoc_clump, past the store */
         run_clump_free(R);
     }
-    if (R->GN) {
+    if (R->GN && R->tool == RUN_GRM) {
+        if (!rc) rc = run_grm_write(R, out_path);
+    } else if (R->GN) {
         if (!rc) rc = run_genome_write(R, out_path);
         R->n_pairs = R->GN->n_pairs;                     /* for hpgv_run_genome, past the counts */
     }
@@ -598,9 +606,9 @@ static int run_finish(run_t *R, int rc, const char *out_path) {
 }
 
 static int run_file_held(run_t *R, const char *vcf_path, const char *ped_path, const char *out_path, size_t batch_bytes, long *n_variants_out);
-/* the run holds the record filters of hpgv_run_set_record_filters as they are when it starts (stats, split and genome: none) */
+/* the run holds the record filters of hpgv_run_set_record_filters as they are when it starts (stats, split, genome and grm: none) */
 static int run_file(run_t *R, const char *vcf_path, const char *ped_path, const char *out_path, size_t batch_bytes, long *n_variants_out) {
-    R->rf = R->tool == RUN_STATS || R->tool == RUN_SPLIT || R->tool == RUN_GENOME ? NULL : rec_filters_take();
+    R->rf = R->tool == RUN_STATS || R->tool == RUN_SPLIT || R->tool == RUN_GENOME || R->tool == RUN_GRM ? NULL : rec_filters_take();
     int rc = HPGV_OK;
     if (rec_filters_inheritance(R->rf) && !ped_path) {                /* filter_options_parsing.c:149-153 */
         snprintf(g_err, sizeof g_err, "the inheritance filters (--inh-dom / --inh-rec) need a PED file (ped_path is NULL)");
@@ -775,6 +783,20 @@ int hpgv_run_genome(const char *vcf_path, const char *out_path, double min_pi_ha
     run_t R = { .tool = RUN_GENOME, .filters = filters_off, .min_pi_hat = min_pi_hat };
     const int rc = run_file(&R, vcf_path, NULL, out_path, batch_bytes, n_variants_out);
     if (n_pairs_out) *n_pairs_out = R.n_pairs;
+    return rc;
+}
+
+/* the genetic relationship matrix (include/hpgv.h "GRM"; GCTA's --make-grm-bin) of the VCF's samples at hpgv_grm_frac_bits(min_maf):
+ * <out_prefix>.grm.bin, .grm.N.bin and .grm.id.  As in hpgv_run_genome neither filter setter is applied.  *n_variants_out: the
+ * USED records */
+int hpgv_run_grm(const char *vcf_path, const char *out_prefix, double min_maf, size_t batch_bytes, long *n_variants_out, long *n_samples_out) {
+    if (n_samples_out) *n_samples_out = 0;
+    if (run_args(n_variants_out, vcf_path && out_prefix, "vcf_path and out_prefix must not be NULL")) return HPGV_ERR_INVALID;
+    const int frac_bits = hpgv_grm_frac_bits(min_maf);
+    if (frac_bits < 0) { snprintf(g_err, sizeof g_err, "min_maf %g: above 0, at most 0.5 (and not below 2e-9)", min_maf); return HPGV_ERR_INVALID; }
+    run_t R = { .tool = RUN_GRM, .filters = filters_off, .min_maf = min_maf, .frac_bits = frac_bits };
+    const int rc = run_file(&R, vcf_path, NULL, out_prefix, batch_bytes, n_variants_out);
+    if (n_samples_out && !rc) *n_samples_out = R.n_samples;
     return rc;
 }
 

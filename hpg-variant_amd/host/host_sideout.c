@@ -1,5 +1,6 @@
 /* host_sideout.c -- what a file run keeps beside its result file, and the files written from it at the end: the permutation
- * results (<out>.mperm), the clumping candidates (<out>.clumped), the stats report, the sample pairs of the genome run.  Each is
+ * results (<out>.mperm), the clumping candidates (<out>.clumped), the stats report, the sample pairs of the genome run, the
+ * relationship matrix of the GRM run.  Each is
  * a run_*_t of the run with four functions: _new (run_outputs), _add (the writer loop, per written batch), _write and _free (run_finish).
  * Part of libhpgv_host.so (see hpgv_host_internal.h for the map of its units). */
 #include "hpgv_host_internal.h"
@@ -346,6 +347,73 @@ void run_genome_free(run_t *R) {
     for (int d = 0; G && G->d_counts && G->ctx && d < G->n_dev; d++) if (G->d_counts[d]) (void)hpgv_dev_free(G->ctx[d], G->d_counts[d]);
     if (G) { free(G->ctx); free(G->d_counts); free(G); }
     R->GN = NULL;
+}
+
+/* ---- genetic relationship matrix: the pair sums of the run lie in the genome run's device buffers (run_genome_new / _device /
+ *      _free: one n_samples x n_samples buffer of 16-byte records per device, whichever record) ---------------------------------- */
+_Static_assert(sizeof(hpgv_grm_acc) == sizeof(hpgv_ibs_counts), "the GRM run keeps its sums in run_genome_t's buffers");
+
+/* the written records of a batch: a record whose class counts are all zero was a skipped row; the run counts the USED ones, by the
+ * function the device's table kernel is */
+void run_grm_add(run_t *R, const run_batch_t *b) {
+    const int n = b->n_lines < b->max_lines ? b->n_lines : b->max_lines;
+    for (int i = 0; i < n; i++) {
+        const int32_t *c = b->ints + 4 * (size_t)i;
+        int8_t hi[4], lo[4];
+        if (!record_passes(b, i) || !(c[0] | c[1] | c[2] | c[3])) continue;
+        if (hpgv_grm_table(c[0], c[1], c[2], R->frac_bits, R->min_maf, hi, lo)) R->written++;
+    }
+}
+
+static int grm_put(const char *prefix, const char *suffix, const void *data, size_t bytes) {
+    char *path = (char *)malloc(strlen(prefix) + strlen(suffix) + 1);
+    if (!path) return HPGV_ERR_NOMEM;
+    strcpy(path, prefix); strcat(path, suffix);
+    FILE *f = fopen(path, "wb");
+    int rc = HPGV_OK;
+    if (!f) { snprintf(g_err, sizeof g_err, "cannot create %s", path); rc = HPGV_ERR_INVALID; }
+    else if ((fwrite(data, 1, bytes, f) != bytes) | (fclose(f) != 0)) { snprintf(g_err, sizeof g_err, "cannot write %s", path); rc = HPGV_ERR_INVALID; }
+    free(path);
+    return rc;
+}
+
+/* the devices' sums added as integers (any order), then GCTA's binary triplet: <prefix>.grm.bin, float32 of hpgv_grm_value for
+ * rows i = 0 .. n - 1 and columns j = 0 .. i (the device holds the element at [min][max]); <prefix>.grm.N.bin, float32 of n in the
+ * same order; <prefix>.grm.id, "name<TAB>name" per sample */
+int run_grm_write(run_t *R, const char *out_prefix) {
+    run_genome_t *G = R->GN;
+    const size_t ns = (size_t)R->n_samples, recs = ns * ns, tri = ns * (ns + 1) / 2;
+    int rc = HPGV_OK;
+    hpgv_grm_acc *sum = (hpgv_grm_acc *)calloc(recs ? recs : 1, sizeof *sum), *part = G->n_dev > 1 ? (hpgv_grm_acc *)malloc((recs ? recs : 1) * sizeof *part) : NULL;
+    float *val = (float *)malloc((tri ? tri : 1) * sizeof *val), *cnt = (float *)malloc((tri ? tri : 1) * sizeof *cnt);
+    if (!sum || !val || !cnt || (G->n_dev > 1 && !part)) rc = HPGV_ERR_NOMEM;
+    for (int d = 0; d < G->n_dev && !rc && recs; d++) {
+        hpgv_grm_acc *to = d == 0 ? sum : part;
+        if ((rc = hpgv_memcpy_d2h(G->ctx[d], to, G->d_counts[d], recs * sizeof *to, NULL))) { host_fail("hpgv_memcpy_d2h", rc); break; }
+        for (size_t k = 0; d > 0 && k < recs; k++) { sum[k].sq += part[k].sq; sum[k].n += part[k].n; }
+    }
+    if (!rc) {
+        size_t at = 0;
+        for (size_t i = 0; i < ns; i++)
+            for (size_t j = 0; j <= i; j++, at++) {
+                const hpgv_grm_acc *a = sum + j * ns + i;
+                val[at] = (float)hpgv_grm_value(a, R->frac_bits);
+                cnt[at] = (float)a->n;
+            }
+        rc = grm_put(out_prefix, ".grm.bin", val, tri * sizeof *val);
+        if (!rc) rc = grm_put(out_prefix, ".grm.N.bin", cnt, tri * sizeof *cnt);
+    }
+    if (!rc) {
+        size_t len = 0;
+        for (size_t j = 0; j < ns; j++) len += 2 * strlen(R->names[j]) + 2;
+        char *ids = (char *)malloc(len + 1), *w = ids;
+        if (!ids) rc = HPGV_ERR_NOMEM;
+        for (size_t j = 0; j < ns && !rc; j++) w += sprintf(w, "%s\t%s\n", R->names[j], R->names[j]);
+        if (!rc) rc = grm_put(out_prefix, ".grm.id", ids, (size_t)(w - ids));
+        free(ids);
+    }
+    free(sum); free(part); free(val); free(cnt);
+    return rc;
 }
 
 /* ---- hpg-var-vcf stats: what the run accumulates besides the per-variant lines (run_stats_t; the report writers live in

@@ -143,9 +143,10 @@ typedef struct {
 /* RUN_CHISQ_PERM: the chi-square run with label permutation (hpgv_run_assoc_perm): RUN_CHISQ's file plus <out>.mperm;
  * RUN_TDT_PERM: the TDT run with family flips (hpgv_run_tdt_perm): RUN_TDT's file plus <out>.mperm;
  * RUN_MODEL / RUN_MODEL_PERM: the model tests (hpgv_run_assoc_model) without and with <out>.mperm of the trend statistic;
- * RUN_GENOME: sample relatedness (hpgv_run_genome): no line per record, one file of sample pairs written when the run ends */
+ * RUN_GENOME: sample relatedness (hpgv_run_genome): no line per record, one file of sample pairs written when the run ends;
+ * RUN_GRM: the genetic relationship matrix (hpgv_run_grm): no line per record, three files written when the run ends */
 typedef enum { RUN_CHISQ = CHI_SQUARE, RUN_FISHER = FISHER, RUN_TDT, RUN_VCF2EPI, RUN_AGGREGATE, RUN_STATS, RUN_FILTER, RUN_SPLIT, RUN_CHISQ_PERM, RUN_TDT_PERM,
-               RUN_MODEL, RUN_MODEL_PERM, RUN_GENOME } run_tool_t;
+               RUN_MODEL, RUN_MODEL_PERM, RUN_GENOME, RUN_GRM } run_tool_t;
 static inline int tool_chisq(run_tool_t t) { return t == RUN_CHISQ || t == RUN_CHISQ_PERM; }   /* writes the chi-square file */
 static inline int tool_tdt(run_tool_t t) { return t == RUN_TDT || t == RUN_TDT_PERM; }         /* writes the TDT file */
 static inline int tool_model(run_tool_t t) { return t == RUN_MODEL || t == RUN_MODEL_PERM; }   /* writes the model tests' file */
@@ -162,7 +163,7 @@ typedef struct {
     size_t bytes; int max_lines, n_lines;
     uint64_t *line_off; uint32_t *field_off; int32_t *status;
     int32_t *ints; double *dbl;                          /* 4 (assoc) or 2 (tdt) int arrays, 3 double arrays; the model tests: counts8 per line, then
-                                                          * chisq5 per line and, from dbl + 5 * max_lines, p5 per line; genome: class4 per line in ints */
+                                                          * chisq5 per line and, from dbl + 5 * max_lines, p5 per line; genome and grm: class4 per line in ints */
     int32_t *n_ge; double *bmax;                         /* the permutation tools: permutations at or above the observed statistic per line; the batch's maximum per permutation */
     uint8_t *rows; size_t rows_cap; int row_width;       /* vcf2epi: one dataset row per line */
     int stats;                                           /* aggregate / stats: the counters of hpgv_stats_text */
@@ -264,6 +265,7 @@ typedef struct run {
     const hpgv_run_clump_options_t *clump; run_clump_t *CL;      /* RUN_CHISQ / RUN_FISHER with <out>.clumped beside the file (NULL: without) */
     long n_clumps, n_truncated;                          /* ... what run_clump_write counted, kept past the store */
     double min_pi_hat; run_genome_t *GN; long n_pairs;   /* RUN_GENOME: the threshold, the run's counts, the pairs written (kept past them) */
+    double min_maf; int frac_bits;                       /* RUN_GRM: the rows' rule and hpgv_grm_frac_bits of it; its sums lie in GN's buffers (16-byte records too) */
     double t_opened, t_header, t_sort;
 } run_t;
 
@@ -409,6 +411,8 @@ hpgv_ctx *run_genome_device(run_t *R, const run_batch_t *b, hpgv_ibs_counts **d_
 void run_genome_add(run_t *R, const run_batch_t *b);     /* and the run's count of records that took part */
 int run_genome_write(run_t *R, const char *out_path);
 void run_genome_free(run_t *R);
+void run_grm_add(run_t *R, const run_batch_t *b);        /* the run's count of USED records */
+int run_grm_write(run_t *R, const char *out_prefix);
 int run_stats_new(run_t *R);
 void run_stats_add(run_t *R, const run_batch_t *b);      /* and the batch's lines to the per-phenotype files */
 int run_stats_write(const run_t *R, const char *prefix);

@@ -487,7 +487,7 @@ int  hpgv_ld_edges_dev(hpgv_ctx *ctx, const uint8_t *d_gt, size_t pitch, int n_v
  *      value is NaN is defined, not which NaN.
  *
  *      Out of scope: PLINK's PPC and RATIO columns, its re-projection of (z0, z1, z2) onto the "biologically plausible" region,
- *      a genetic relationship matrix, and a group form of the batch calls. */
+ *      and a group form of the batch calls. */
 typedef struct { int32_t n, ibs0, ibs1, ibs2; } hpgv_ibs_counts;                       /* 16 bytes */
 typedef struct { int32_t i, j; hpgv_ibs_counts c; double pi_hat; } hpgv_ibs_pair;      /* 32 bytes, i < j */
 /* d_gt: any matrix of HPGV8 rows `pitch` bytes apart; the bytes of a row at and past n_cols are never counted, whatever they
@@ -515,6 +515,57 @@ int  hpgv_ibs_class_counts_dev(hpgv_ctx *ctx, const uint8_t *d_gt, size_t pitch,
  * aligned, d_n not 8-byte aligned; HPGV_ERR_UNSUPPORTED for n_cols x ceil(n_cols / 256) above 2^31 - 1. */
 int  hpgv_ibs_select_dev(hpgv_ctx *ctx, const hpgv_ibs_counts *d_counts, int n_cols, const double E[5], double min_pi_hat,
                          hpgv_ibs_pair *d_pairs, uint64_t cap, uint64_t *d_n, void *stream);
+
+/* ---- GRM: the genetic relationship matrix between SAMPLES (GCTA's --make-grm, PLINK's --make-grm-bin; no reference
+ *      counterpart), what PCA covariates, mixed models and a relatedness cut-off start from.  Parity with GCTA / PLINK is
+ *      UNPINNED, as for "IBS": the expressions below are this project's definition.  The form is GCTA's per-pair-N estimator
+ *      with the diagonal computed as every other element is (PLINK 1.9's default diagonal).
+ *
+ *      A GRM weights every variant by 1 / (2 p (1 - p)) INSIDE the sum, so no product of genotype planes gives it exactly.  The
+ *      standardised genotypes are therefore quantised, BY DEFINITION, to 16-bit fixed point, and the matrix is an exact integer
+ *      computation: it does not depend on tile order, row ranges, batches, streams or devices.
+ *
+ *      Genotype class g and validity of an HPGV8 byte are exactly those of "IBS"; n0, n1, n2 are a row's class counts over the
+ *      columns below n_cols (hpgv_ibs_class_counts_dev).  Per row, with frac_bits s in [0, 14] and min_maf, f64 without
+ *      contraction in this order:
+ *          X = 2 n0 + n1      Y = n1 + 2 n2      T = X + Y      p = (double)Y / (double)T      d = sqrt(2.0 * p * (1.0 - p))
+ *          z_c = ((double)c - 2.0 * p) / d   for c = 0, 1, 2      q_c = rint(z_c * 2^s), ties to even
+ *      A row is USED iff it is not skipped, 0 < Y < T, (double)min(X, Y) / (double)T >= min_maf, and every |q_c| <= 32512
+ *      (= 127 * 256).  An unused row's table is all zeros and the row takes no part, not even in n.  The limbs of q are
+ *      lo = (int8)(q & 0xFF) and hi = (q - lo) / 256: q = 256 hi + lo exactly, hi in [-127, 127], lo in [-128, 127].  A missing
+ *      byte has q = 0 and valid = 0.
+ *
+ *      Per pair i <= j, DIAGONAL INCLUDED, summed over the used rows where both columns are valid:
+ *          sq = sum q_i q_j  (int64, exact)      n = sum 1      A_ij = ((double)sq * 2^(-2s)) / (double)n
+ *      n = 0 gives the IEEE result (NaN).  On the matrix cores (csrc/hpgv_grm_kernels.h) sq = 65536 hi.hi + 256 (hi.lo + lo.hi)
+ *      + lo.lo: five i8 products with exact i32 sums per range of at most 32 768 rows (|hi_i lo_j + lo_i hi_j| <= 32 512 per row),
+ *      combined in int64.
+ *
+ *      Quantisation bound: |q_c 2^-s - z_c| <= delta = 2^-(s+1), so a pair's value lies within
+ *      sum [delta (|z_i| + |z_j|) + delta^2] / n of the unquantised f64 sum of z_i z_j over n.  hpgv_grm_frac_bits(min_maf) is
+ *      the largest s <= 14 with sqrt(2 (1 - min_maf) / min_maf) * 2^s <= 32512 -- no row at or above that MAF is lost to the
+ *      |q_c| rule: 14 / 12 / 12 / 11 / 9 for min_maf 0.5 / 0.1 / 0.05 / 0.01 / 0.001, and -1 for min_maf outside (0, 0.5].
+ *
+ *      Out of scope: GCTA's Fhat3 diagonal, a text .grm.gz, a relatedness cut-off list, PCA, a 24-bit (three-limb) form, and a
+ *      group form of the batch calls. */
+typedef struct { int64_t sq, n; } hpgv_grm_acc;                                         /* 16 bytes */
+/* d_class4: 4 int32 per row, {n0, n1, n2, missing} (hpgv_ibs_class_counts_dev).  d_skip, IN-OUT and required: a row that comes in
+ * != 0 is unused whatever its counts; the call sets d_skip[row] = 1 for every unused row and leaves the others as they are.
+ * d_tab: 8 bytes per row, {int8 hi[4], int8 lo[4]}, entries 0 .. 2 the classes and entry 3 zero; all zeros for an unused row:
+ * every record written.  d_n_used (may be NULL): the call zeroes it on `stream` and counts the used rows into it.  One lane per
+ * row; the table is bit for bit hpgv_grm_table's.  n_variants == 0 succeeds (and zeroes d_n_used).  HPGV_ERR_INVALID for
+ * n_variants < 0, frac_bits outside [0, 14], min_maf outside [0, 0.5] or NaN, a NULL d_class4, d_skip or d_tab, d_class4 not
+ * 16-byte, d_tab not 8-byte, d_n_used not 4-byte aligned.  Asynchronous on `stream`. */
+int  hpgv_grm_table_dev(hpgv_ctx *ctx, const int32_t *d_class4, int n_variants, int frac_bits, double min_maf,
+                        uint8_t *d_skip /* in-out, required */, uint8_t *d_tab, int32_t *d_n_used /* may be NULL */, void *stream);
+/* Matrix, d_skip, alignment, refusals, streams and "profile" timing as hpgv_ibs_pairs_dev; d_tab and d_skip as
+ * hpgv_grm_table_dev left them (with d_skip NULL every row takes part with its table: an unused row would then count in n).
+ * The call ADDS {sq, n} of these rows to d_acc[i * n_cols + j] for 0 <= i <= j < n_cols with relaxed device-scope 64-bit
+ * atomics and never touches an element with i > j; the caller zeroes the n_cols x n_cols records before the first call.
+ * n_variants == 0 or n_cols < 1 succeed and write nothing.  d_tab must be 8-byte, d_acc 16-byte aligned.  A workgroup's row
+ * range is never longer than 32 768 rows (hpgv_grm_plan_rows), so no i32 sum overflows whatever the shape. */
+int  hpgv_grm_pairs_dev(hpgv_ctx *ctx, const uint8_t *d_gt, size_t pitch, int n_variants, int n_cols,
+                        const uint8_t *d_skip, const uint8_t *d_tab, hpgv_grm_acc *d_acc /* n_cols x n_cols */, void *stream);
 
 /* ---- the variant-sharded resident scan of a GROUP context: what the runner's worker loop
  *      (assoc_runner.c:106-207, tdt_runner.c:150-200, stats_runner.c:176-215) becomes when the cohort lies in the HBM of
@@ -1044,6 +1095,20 @@ int  hpgv_ibs(hpgv_ctx *ctx, const uint8_t *gt, size_t pitch, int n_variants, co
 int  hpgv_ibs_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, int max_lines, int *n_lines,
                    uint64_t *line_off, uint32_t *field_off, int32_t *status, int32_t *class4, hpgv_ibs_counts *d_counts);
 
+/* ---- GRM on a host batch and on a text ("GRM" above; synchronous, thread-safe) ------------------------------------------ */
+/* hpgv_ibs with the GRM's kernels: matrix, skip, class4 (zeros for a skipped row; a row that is unused for another reason keeps
+ * its counts -- hpgv_grm_table of them tells), state and refusals as hpgv_ibs, plus HPGV_ERR_INVALID for frac_bits outside
+ * [0, 14] or min_maf outside [0, 0.5].  Class counts, table and pair sums run on one stream; d_acc: DEVICE memory,
+ * n_samples x n_samples records, 16-byte aligned, zeroed by the caller before the first batch and ACCUMULATED into, the
+ * diagonal included.  A GROUP context returns HPGV_ERR_UNSUPPORTED. */
+int  hpgv_grm(hpgv_ctx *ctx, const uint8_t *gt, size_t pitch, int n_variants, const uint8_t *skip /* may be NULL */,
+              int frac_bits, double min_maf, int32_t *class4, hpgv_grm_acc *d_acc);
+/* hpgv_ibs_text with the GRM's kernels: dropped lines and chromosome-X lines are skipped rows, and where *n_lines comes back
+ * larger than max_lines NOTHING was added to d_acc and class4 is not written. */
+int  hpgv_grm_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, int max_lines, int *n_lines,
+                   uint64_t *line_off, uint32_t *field_off, int32_t *status, int frac_bits, double min_maf,
+                   int32_t *class4, hpgv_grm_acc *d_acc);
+
 /* ---- label permutation, host side: no GPU call, no context, usable without a device ------------------------------- */
 /* n_perms label rows for hpgv_set_perm_labels, labels_out[p * n_samples + j]: row p is a uniform shuffle of the cohort
  * columns' conditions (1 = affected), so every row has as many ones as the cohort has affected samples; HPGV_COND_OTHER
@@ -1082,6 +1147,16 @@ int  hpgv_ibs_terms(int32_t n0, int32_t n1, int32_t n2, double t[5]);
 /* out = {Z0, Z1, Z2, PI_HAT, DST} of one pair's counts with E = {E00, E01, E02, E11, E12}: the function k_ibs_select calls,
  * built for the host.  No GPU call, no context. */
 void hpgv_ibs_genome(const hpgv_ibs_counts *c, const double E[5], double out[5]);
+/* One row's table by the expressions of "GRM" above: hi[c], lo[c] for the classes c = 0, 1, 2, entry 3 zero; returns 1 for a
+ * used row, else 0 with zeros (a negative count or a frac_bits outside [0, 14] included).  Whether the row is skipped is the
+ * caller's to know.  The function k_grm_table calls, built for the host.  No GPU call. */
+int  hpgv_grm_table(int32_t n0, int32_t n1, int32_t n2, int frac_bits, double min_maf, int8_t hi[4], int8_t lo[4]);
+/* the largest frac_bits at which no row with MAF >= min_maf is lost ("GRM" above); -1 for min_maf outside (0, 0.5] */
+int  hpgv_grm_frac_bits(double min_maf);
+/* A_ij of one record: ((double)sq * 2^(-2 frac_bits)) / (double)n */
+double hpgv_grm_value(const hpgv_grm_acc *a, int frac_bits);
+/* rows per row range of hpgv_grm_pairs_dev's launch on a device with n_cus compute units: a multiple of 64, never above 32 768 */
+int  hpgv_grm_plan_rows(int n_variants, int n_cols, int n_cus);
 
 /* streaming-read ceiling probe: reads `bytes` from d_buf with the scan's load
  * shape and no arithmetic; returns the kernel time in ms (diagnostic) */

@@ -521,6 +521,18 @@ int  hpgv_run_stats(const char *vcf_path, const char *ped_path, const char *out_
  * HPGV_ERR_INVALID before anything is opened, and no file is written.  The counts take 16 n_samples^2 bytes of device memory. */
 int  hpgv_run_genome(const char *vcf_path, const char *out_path, double min_pi_hat, size_t batch_bytes,
                      long *n_variants_out, long *n_pairs_out);
+/* The genetic relationship matrix of the VCF's samples (include/hpgv.h "GRM"; GCTA's --make-grm-bin, parity unpinned) at
+ * frac_bits = hpgv_grm_frac_bits(min_maf).  Every batch goes through hpgv_grm_text into one buffer of pair sums per device of
+ * the run, 16 n_samples^2 bytes each, dealt as hpgv_run_genome deals them; the devices' buffers are added as integers when the
+ * run ends.  Lines that are not records and lines on chromosome "X" take no part; as in hpgv_run_genome neither filter setter is
+ * applied.  The sums are integers, so the three files do not depend on batch_bytes, engine threads, input form or devices:
+ *     <out_prefix>.grm.bin     float32 of hpgv_grm_value, rows i = 0 .. n - 1, columns j = 0 .. i (native byte order)
+ *     <out_prefix>.grm.N.bin   float32 of the pair's n, in the same order
+ *     <out_prefix>.grm.id      "name<TAB>name" per sample of the #CHROM line
+ * *n_variants_out: the USED records (not X, 0 < Y < T, MAF >= min_maf); *n_samples_out: n.  Input forms as hpgv_run_assoc.  A
+ * NULL path or a min_maf outside (0, 0.5] (NaN included): HPGV_ERR_INVALID before anything is opened, and no file is written. */
+int  hpgv_run_grm(const char *vcf_path, const char *out_prefix, double min_maf, size_t batch_bytes,
+                  long *n_variants_out, long *n_samples_out);
 /* stage times of the last run on this process: {read, engine, write, sort, total} seconds and the number of
  * batches; read / engine / write overlap (three threads, three batch buffers in rotation).  The reader and
  * formatter teams use HPGV_IO_THREADS threads (environment; default half the cores, at most 16);
