@@ -72,6 +72,7 @@ SYMBOLS = [
     "hpgv_rows_gather_scratch_bytes", "hpgv_rows_gather_dev", "hpgv_assoc_select_text",
     "hpgv_ibs_pairs_dev", "hpgv_ibs_class_counts_dev", "hpgv_ibs_select_dev", "hpgv_ibs", "hpgv_ibs_text", "hpgv_ibs_terms", "hpgv_ibs_genome",
     "hpgv_grm_table_dev", "hpgv_grm_pairs_dev", "hpgv_grm", "hpgv_grm_text", "hpgv_grm_table", "hpgv_grm_frac_bits", "hpgv_grm_value", "hpgv_grm_plan_rows",
+    "hpgv_grm_matrix_dev", "hpgv_pca_apply_dev", "hpgv_pca_dev", "hpgv_pca_block", "hpgv_pca_jacobi", "hpgv_pca_chol_inv",
 ]
 
 # hpgv_ld_edge: {int32 a, b; double r2}, 16 bytes
@@ -270,6 +271,12 @@ def load():
     L.hpgv_grm_value.argtypes = [vp, i32]
     L.hpgv_grm_value.restype = C.c_double
     L.hpgv_grm_plan_rows.argtypes = [i32, i32, i32]
+    L.hpgv_grm_matrix_dev.argtypes = [vp, vp, i32, i32, vp, sz, vp, vp]
+    L.hpgv_pca_apply_dev.argtypes = [vp, vp, i32, sz, vp, i32, vp, vp]
+    L.hpgv_pca_dev.argtypes = [vp, vp, i32, sz, i32, C.c_double, i32, u64, vp, vp, vp, C.POINTER(i32), C.POINTER(i32)]
+    L.hpgv_pca_block.argtypes = [i32]
+    L.hpgv_pca_jacobi.argtypes = [i32, vp, vp]
+    L.hpgv_pca_chol_inv.argtypes = [i32, vp, vp]
     L.hpgv_rows_gather_scratch_bytes.argtypes = [i32]
     L.hpgv_rows_gather_scratch_bytes.restype = sz
     L.hpgv_rows_gather_dev.argtypes = [vp, vp, sz, sz, i32, vp, vp, sz, vp, vp, vp, vp]
@@ -365,6 +372,39 @@ def run_grm(vcf_path, out_prefix, min_maf=0.01, batch_bytes=1 << 22):
         e.code = rc
         raise e
     return n.value, k.value
+
+
+def _run_pca_result(what, H, rc, counts):
+    if rc != OK:
+        e = HpgvError("%s -> %d: %s" % (what, rc, (H.hpgv_host_last_error() or b"").decode(errors="replace")))
+        e.code = rc
+        raise e
+    return tuple(c.value for c in counts)
+
+
+def run_pca(vcf_path, out_prefix, min_maf=0.01, n_pcs=10, write_grm=False, batch_bytes=1 << 22):
+    """hpgv_run_pca of libhpgv_host.so (include/hpgv_host.h): <out_prefix>.eigenval and .eigenvec of the VCF's GRM and, with
+    write_grm, hpgv_run_grm's three files.  Returns (variants used, samples, sweeps; negative: not converged)."""
+    _build.build_host_lib()
+    H = C.CDLL(_build.HOSTLIB)
+    H.hpgv_run_pca.argtypes = [C.c_char_p, C.c_char_p, C.c_double, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_int)]
+    H.hpgv_host_last_error.restype = C.c_char_p
+    n, k, it = C.c_long(0), C.c_long(0), C.c_int(0)
+    enc = lambda q: None if q is None else os.fsencode(q)
+    rc = H.hpgv_run_pca(enc(vcf_path), enc(out_prefix), float(min_maf), int(n_pcs), 1 if write_grm else 0, batch_bytes, C.byref(n), C.byref(k), C.byref(it))
+    return _run_pca_result("hpgv_run_pca", H, rc, (n, k, it))
+
+
+def run_pca_grm(grm_prefix, out_prefix, n_pcs=10):
+    """hpgv_run_pca_grm: the same solver on <grm_prefix>.grm.bin / .grm.id.  Returns (samples, sweeps; negative: not converged)."""
+    _build.build_host_lib()
+    H = C.CDLL(_build.HOSTLIB)
+    H.hpgv_run_pca_grm.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_long), C.POINTER(C.c_int)]
+    H.hpgv_host_last_error.restype = C.c_char_p
+    k, it = C.c_long(0), C.c_int(0)
+    enc = lambda q: None if q is None else os.fsencode(q)
+    rc = H.hpgv_run_pca_grm(enc(grm_prefix), enc(out_prefix), int(n_pcs), C.byref(k), C.byref(it))
+    return _run_pca_result("hpgv_run_pca_grm", H, rc, (k, it))
 
 
 class RunClumpOptions(C.Structure):
@@ -494,6 +534,34 @@ def grm_value(acc, frac_bits):
     for k in range(len(flat)):
         out[k] = L.hpgv_grm_value(C.c_void_p(flat[k:k + 1].ctypes.data), int(frac_bits))
     return out.reshape(shape)
+
+
+def pca_block(k):
+    """hpgv_pca_block: the solver's block width for k pairs (16, 32 or -1)"""
+    return int(load().hpgv_pca_block(int(k)))
+
+
+def pca_jacobi(H):
+    """hpgv_pca_jacobi of a symmetric (L, L) matrix: (theta (L,), W (L, L)) with W[:, j] the unit eigenvector of theta[j], the pairs
+    by decreasing |theta|.  No device needed."""
+    W = np.array(H, np.float64, order="C")
+    L = W.shape[0]
+    theta = np.zeros(L, np.float64)
+    rc = load().hpgv_pca_jacobi(L, _ptr(W), _ptr(theta))
+    if rc != OK:
+        raise HpgvError("hpgv_pca_jacobi -> %d" % rc)
+    return theta, W
+
+
+def pca_chol_inv(G):
+    """hpgv_pca_chol_inv of an (L, L) matrix: (failed, M) with M = R^-1 of G = R^T R; failed: a pivot fell to or below
+    L * eps * max diag.  No device needed."""
+    G = np.ascontiguousarray(G, np.float64)
+    M = np.zeros_like(G)
+    rc = load().hpgv_pca_chol_inv(G.shape[0], _ptr(G), _ptr(M))
+    if rc < 0:
+        raise HpgvError("hpgv_pca_chol_inv -> %d" % rc)
+    return rc != 0, M
 
 
 def grm_plan_rows(n_variants, n_cols, n_cus):
@@ -1183,6 +1251,21 @@ class Engine:
 
     def grm_pairs_dev(self, d_gt, pitch, n_variants, n_cols, d_tab, d_acc, d_skip=None, stream=None):
         self._chk(self.L.hpgv_grm_pairs_dev(self.h, d_gt, pitch, n_variants, n_cols, d_skip, d_tab, d_acc, stream))
+
+    def grm_matrix_dev(self, d_acc, n_cols, frac_bits, d_A, lda, d_n_empty, stream=None):
+        self._chk(self.L.hpgv_grm_matrix_dev(self.h, d_acc, n_cols, int(frac_bits), d_A, lda, d_n_empty, stream))
+
+    def pca_apply_dev(self, d_A, n, lda, d_Q, L, d_Y, stream=None):
+        self._chk(self.L.hpgv_pca_apply_dev(self.h, d_A, n, lda, d_Q, L, d_Y, stream))
+
+    def pca_dev(self, d_A, n, lda, k, tol=1e-8, max_iter=1000, seed=1):
+        """hpgv_pca_dev: dict of eigval (k,), vec (n, k), resid (k,), n_iter, converged"""
+        kk = max(int(k), 1)
+        eigval, vec, resid = np.zeros(kk), np.zeros((max(n, 1), kk)), np.zeros(kk)
+        it, conv = C.c_int(0), C.c_int(0)
+        self._chk(self.L.hpgv_pca_dev(self.h, d_A, n, lda, int(k), float(tol), int(max_iter), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(eigval), _ptr(vec), _ptr(resid),
+                                      C.byref(it), C.byref(conv)))
+        return dict(eigval=eigval, vec=vec[:n], resid=resid, n_iter=it.value, converged=conv.value)
 
     def ibs_select_dev(self, d_counts, n_cols, E, min_pi_hat, d_pairs, cap, d_n, stream=None):
         e = _np(E, np.float64)

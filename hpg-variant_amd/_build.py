@@ -59,6 +59,8 @@ def build_device_lib(force=False, verbose=False, ablation=False):
     os.makedirs(objdir, exist_ok=True)
     flags = [f for f in HIPCC_FLAGS if f != "-shared"] + (["-DHPGV_ABLATION"] if ablation else [])
     LIB = ABLATION_LIB if ablation else globals()["LIB"]
+    if not force and not _stale(LIB, units + hdrs):      # newer than every source: current, even where the objects are gone
+        return LIB
     jobs = []
     objs = []
     for u in units:

@@ -255,6 +255,9 @@ int hpgv_set_option(hpgv_ctx *ctx, const char *key, long value) {
     } else if (!strcmp(key, "part_aligned_loads")) {
         HPGV_SHIPPED_ONLY(value == 0, "part_aligned_loads = 1")
         ctx->part_aligned = value ? 1 : 0;
+    } else if (!strcmp(key, "pca_apply_vector")) {
+        HPGV_SHIPPED_ONLY(value == 0, "pca_apply_vector = 1")
+        ctx->pca_apply_vector = value ? 1 : 0;
     } else if (!strcmp(key, "blocks_per_cu")) {
         if (value < 1 || value > 8) return fail(ctx, HPGV_ERR_INVALID, "blocks_per_cu must be in 1..8");
         ctx->blocks_per_cu = value;

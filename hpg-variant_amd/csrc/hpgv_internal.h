@@ -2,7 +2,7 @@
 // libhpgv.so: hpgv_capi.hip (contexts, options, cohorts, memory, streams, text aliases), hpgv_scan_capi.hip (the
 // device-resident *_dev launchers), hpgv_text_capi.hip (tokenizer, the text entry points' front half),
 // hpgv_tool_capi.hip (per-batch and text entry points), hpgv_lines_capi.hip (partition / multisplit of lines), and the
-// units whose kernel instantiations compile on their own (hpgv_perm_capi.hip, hpgv_ld_capi.hip, hpgv_ibs_capi.hip, hpgv_grm_capi.hip, hpgv_epi_capi.hip, hpgv_epi_generic_capi.hip, hpgv_statsall_capi.hip, hpgv_inflate_capi.hip, hpgv_group_capi.hip).
+// units whose kernel instantiations compile on their own (hpgv_perm_capi.hip, hpgv_ld_capi.hip, hpgv_ibs_capi.hip, hpgv_grm_capi.hip, hpgv_pca_capi.hip, hpgv_epi_capi.hip, hpgv_epi_generic_capi.hip, hpgv_statsall_capi.hip, hpgv_inflate_capi.hip, hpgv_group_capi.hip).
 // A synchronous entry point has two halves that meet in a Staged: the front puts the call's matrix on the device -- text_front /
 // text_front_skip for a text, stage_chain for a host batch that goes through the kernel chain -- and the tool's back half takes it
 // from there; the permutation calls build theirs from the halves of hpgv_assoc's and hpgv_tdt's (assoc_chain, ..., below).
@@ -202,6 +202,7 @@ struct hpgv_ctx {
     struct TextHeld { const char *host_text; Slot *slot; const char *d_text; const unsigned long long *d_line_off; int n_lines; };
     std::vector<TextHeld> text_held;                                 // (under alias_mu)
     long part_aligned = 0;     // hpgv_lines_partition_dev: 0 = unaligned dwordx4 loads of the source; 1 = aligned loads + v_alignbyte (ablation build)
+    long pca_apply_vector = 0; // hpgv_pca_apply_dev: 0 = k_pca_apply on the f64 MFMA; 1 = the lane-per-row v_fma_f64 form (ablation build)
     long scan_unroll = 4;
     long persistent = 0;       // 0: one wave per vpw consecutive rows; 1: persistent strided grid
     long blocks_per_cu = 8;

@@ -591,7 +591,7 @@ static int run_finish(run_t *R, int rc, const char *out_path) {
         run_clump_free(R);
     }
     if (R->GN && R->tool == RUN_GRM) {
-        if (!rc) rc = run_grm_write(R, out_path);
+        if (!rc) rc = R->n_pcs ? run_pca_write(R, out_path) : run_grm_write(R, out_path);
     } else if (R->GN) {
         if (!rc) rc = run_genome_write(R, out_path);
         R->n_pairs = R->GN->n_pairs;                     /* for hpgv_run_genome, past the counts */
@@ -797,6 +797,23 @@ int hpgv_run_grm(const char *vcf_path, const char *out_prefix, double min_maf, s
     run_t R = { .tool = RUN_GRM, .filters = filters_off, .min_maf = min_maf, .frac_bits = frac_bits };
     const int rc = run_file(&R, vcf_path, NULL, out_prefix, batch_bytes, n_variants_out);
     if (n_samples_out && !rc) *n_samples_out = R.n_samples;
+    return rc;
+}
+
+/* the principal components of that matrix (include/hpgv.h "PCA"): hpgv_run_grm's pass unchanged, then run_pca_write (host_pca.c)
+ * in place of the three files -- or before them, with write_grm */
+int hpgv_run_pca(const char *vcf_path, const char *out_prefix, double min_maf, int n_pcs, int write_grm, size_t batch_bytes,
+                 long *n_variants_out, long *n_samples_out, int *n_iter_out) {
+    if (n_samples_out) *n_samples_out = 0;
+    if (n_iter_out) *n_iter_out = 0;
+    if (run_args(n_variants_out, vcf_path && out_prefix, "vcf_path and out_prefix must not be NULL")) return HPGV_ERR_INVALID;
+    const int frac_bits = hpgv_grm_frac_bits(min_maf);
+    if (frac_bits < 0) { snprintf(g_err, sizeof g_err, "min_maf %g: above 0, at most 0.5 (and not below 2e-9)", min_maf); return HPGV_ERR_INVALID; }
+    if (n_pcs < 1 || n_pcs > 24) { snprintf(g_err, sizeof g_err, "n_pcs %d: 1 .. 24", n_pcs); return HPGV_ERR_INVALID; }
+    run_t R = { .tool = RUN_GRM, .filters = filters_off, .min_maf = min_maf, .frac_bits = frac_bits, .n_pcs = n_pcs, .write_grm = write_grm != 0 };
+    const int rc = run_file(&R, vcf_path, NULL, out_prefix, batch_bytes, n_variants_out);
+    if (n_samples_out && !rc) *n_samples_out = R.n_samples;
+    if (n_iter_out && !rc) *n_iter_out = R.n_iter;
     return rc;
 }
 

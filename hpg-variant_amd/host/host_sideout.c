@@ -365,7 +365,7 @@ void run_grm_add(run_t *R, const run_batch_t *b) {
     }
 }
 
-static int grm_put(const char *prefix, const char *suffix, const void *data, size_t bytes) {
+int grm_put(const char *prefix, const char *suffix, const void *data, size_t bytes) {
     char *path = (char *)malloc(strlen(prefix) + strlen(suffix) + 1);
     if (!path) return HPGV_ERR_NOMEM;
     strcpy(path, prefix); strcat(path, suffix);
@@ -377,21 +377,32 @@ static int grm_put(const char *prefix, const char *suffix, const void *data, siz
     return rc;
 }
 
-/* the devices' sums added as integers (any order), then GCTA's binary triplet: <prefix>.grm.bin, float32 of hpgv_grm_value for
- * rows i = 0 .. n - 1 and columns j = 0 .. i (the device holds the element at [min][max]); <prefix>.grm.N.bin, float32 of n in the
- * same order; <prefix>.grm.id, "name<TAB>name" per sample */
-int run_grm_write(run_t *R, const char *out_prefix) {
+/* the devices' sums added as integers (any order): *sum_out, n_samples x n_samples records, the caller's to free */
+int run_grm_sum(run_t *R, hpgv_grm_acc **sum_out) {
     run_genome_t *G = R->GN;
-    const size_t ns = (size_t)R->n_samples, recs = ns * ns, tri = ns * (ns + 1) / 2;
+    const size_t ns = (size_t)R->n_samples, recs = ns * ns;
     int rc = HPGV_OK;
     hpgv_grm_acc *sum = (hpgv_grm_acc *)calloc(recs ? recs : 1, sizeof *sum), *part = G->n_dev > 1 ? (hpgv_grm_acc *)malloc((recs ? recs : 1) * sizeof *part) : NULL;
-    float *val = (float *)malloc((tri ? tri : 1) * sizeof *val), *cnt = (float *)malloc((tri ? tri : 1) * sizeof *cnt);
-    if (!sum || !val || !cnt || (G->n_dev > 1 && !part)) rc = HPGV_ERR_NOMEM;
+    if (!sum || (G->n_dev > 1 && !part)) rc = HPGV_ERR_NOMEM;
     for (int d = 0; d < G->n_dev && !rc && recs; d++) {
         hpgv_grm_acc *to = d == 0 ? sum : part;
         if ((rc = hpgv_memcpy_d2h(G->ctx[d], to, G->d_counts[d], recs * sizeof *to, NULL))) { host_fail("hpgv_memcpy_d2h", rc); break; }
         for (size_t k = 0; d > 0 && k < recs; k++) { sum[k].sq += part[k].sq; sum[k].n += part[k].n; }
     }
+    free(part);
+    if (rc) { free(sum); sum = NULL; }
+    *sum_out = sum;
+    return rc;
+}
+
+/* GCTA's binary triplet of the summed records: <prefix>.grm.bin, float32 of hpgv_grm_value for rows i = 0 .. n - 1 and columns
+ * j = 0 .. i (the record lies at [min][max]); <prefix>.grm.N.bin, float32 of n in the same order; <prefix>.grm.id,
+ * "name<TAB>name" per sample */
+int run_grm_files(run_t *R, const char *out_prefix, const hpgv_grm_acc *sum) {
+    const size_t ns = (size_t)R->n_samples, tri = ns * (ns + 1) / 2;
+    int rc = HPGV_OK;
+    float *val = (float *)malloc((tri ? tri : 1) * sizeof *val), *cnt = (float *)malloc((tri ? tri : 1) * sizeof *cnt);
+    if (!val || !cnt) rc = HPGV_ERR_NOMEM;
     if (!rc) {
         size_t at = 0;
         for (size_t i = 0; i < ns; i++)
@@ -412,7 +423,15 @@ int run_grm_write(run_t *R, const char *out_prefix) {
         if (!rc) rc = grm_put(out_prefix, ".grm.id", ids, (size_t)(w - ids));
         free(ids);
     }
-    free(sum); free(part); free(val); free(cnt);
+    free(val); free(cnt);
+    return rc;
+}
+
+int run_grm_write(run_t *R, const char *out_prefix) {
+    hpgv_grm_acc *sum = NULL;
+    int rc = run_grm_sum(R, &sum);
+    if (!rc) rc = run_grm_files(R, out_prefix, sum);
+    free(sum);
     return rc;
 }
 

@@ -19,6 +19,7 @@
  *   host_vcftools.c    the VCF tools' batch steps and writers: filter partition, split keys and files
  *   host_records.c     the record filters of hpgv_run_set_record_filters: regions, coverage, variant types, inheritance
  *   host_sideout.c     what a run keeps beside its result file and writes at its end: .mperm, .clumped, the stats report
+ *   host_pca.c         the principal components of a run's relationship matrix, or of .grm.bin files: .eigenval, .eigenvec
  *   host_runner.c      the file runners' pipeline and their runs (hpgv_run_*)
  */
 #ifndef HPGV_HOST_INTERNAL_H
@@ -266,6 +267,7 @@ typedef struct run {
     long n_clumps, n_truncated;                          /* ... what run_clump_write counted, kept past the store */
     double min_pi_hat; run_genome_t *GN; long n_pairs;   /* RUN_GENOME: the threshold, the run's counts, the pairs written (kept past them) */
     double min_maf; int frac_bits;                       /* RUN_GRM: the rows' rule and hpgv_grm_frac_bits of it; its sums lie in GN's buffers (16-byte records too) */
+    int n_pcs, write_grm, n_iter;                        /* RUN_GRM with n_pcs >= 1 (hpgv_run_pca): pairs to write, the .grm.* files too, the sweeps done (kept past the run) */
     double t_opened, t_header, t_sort;
 } run_t;
 
@@ -413,6 +415,10 @@ int run_genome_write(run_t *R, const char *out_path);
 void run_genome_free(run_t *R);
 void run_grm_add(run_t *R, const run_batch_t *b);        /* the run's count of USED records */
 int run_grm_write(run_t *R, const char *out_prefix);
+int run_grm_sum(run_t *R, hpgv_grm_acc **sum_out);       /* the devices' records added on the host; run_grm_files: the three files of the sum */
+int run_grm_files(run_t *R, const char *out_prefix, const hpgv_grm_acc *sum);
+int grm_put(const char *prefix, const char *suffix, const void *data, size_t bytes);      /* <prefix><suffix> written whole */
+int run_pca_write(run_t *R, const char *out_prefix);     /* host_pca.c: the GRM run's end when principal components are asked for */
 int run_stats_new(run_t *R);
 void run_stats_add(run_t *R, const run_batch_t *b);      /* and the batch's lines to the per-phenotype files */
 int run_stats_write(const run_t *R, const char *prefix);

@@ -112,10 +112,12 @@ const char *hpgv_last_error(const hpgv_ctx *ctx);
  *                                (hpgv_group_comm_init or the first group call); afterwards HPGV_ERR_STATE
  *   "part_aligned_loads" 0/1     hpgv_lines_partition_dev: the source of a granule by two aligned loads and v_alignbyte
  *                                (ablation build) instead of one unaligned dwordx4 load (shipped: 0)
+ *   "pca_apply_vector" 0/1       hpgv_pca_apply_dev: the lane-per-row v_fma_f64 form (ablation build) instead of the f64
+ *                                matrix-core form (shipped: 0)
  * Every kernel ships in ONE form.  The forms that lost their A/B comparisons (profiles/experiments_that_did_not_pay.md) are
  * compiled only into an ablation build (-DHPGV_ABLATION: tools/build_ablation.py, used by tools/ only); there the keys
- * "pipeline", "persistent", "scan_unroll", "pipe_waves", "nontemporal", "fisher_width", "inflate_wave", "tokenizer_tiles"
- * select them, and in the shipped library any value but the shipped one is refused with HPGV_ERR_UNSUPPORTED.
+ * "pipeline", "persistent", "scan_unroll", "pipe_waves", "nontemporal", "fisher_width", "inflate_wave", "tokenizer_tiles",
+ * "pca_apply_vector" select them, and in the shipped library any value but the shipped one is refused with HPGV_ERR_UNSUPPORTED.
  *
  * Environment.  The library reads the environment in exactly two places: hpgv_create (the table below, once per context,
  * into the context) and hpgv_group_comm_init (HPGV_RCCL_LIB).  No entry point that launches work reads it.
@@ -546,8 +548,8 @@ int  hpgv_ibs_select_dev(hpgv_ctx *ctx, const hpgv_ibs_counts *d_counts, int n_c
  *      the largest s <= 14 with sqrt(2 (1 - min_maf) / min_maf) * 2^s <= 32512 -- no row at or above that MAF is lost to the
  *      |q_c| rule: 14 / 12 / 12 / 11 / 9 for min_maf 0.5 / 0.1 / 0.05 / 0.01 / 0.001, and -1 for min_maf outside (0, 0.5].
  *
- *      Out of scope: GCTA's Fhat3 diagonal, a text .grm.gz, a relatedness cut-off list, PCA, a 24-bit (three-limb) form, and a
- *      group form of the batch calls. */
+ *      Out of scope: GCTA's Fhat3 diagonal, a text .grm.gz, a relatedness cut-off list, a 24-bit (three-limb) form, and a
+ *      group form of the batch calls.  The principal components of the matrix: "PCA" below. */
 typedef struct { int64_t sq, n; } hpgv_grm_acc;                                         /* 16 bytes */
 /* d_class4: 4 int32 per row, {n0, n1, n2, missing} (hpgv_ibs_class_counts_dev).  d_skip, IN-OUT and required: a row that comes in
  * != 0 is unused whatever its counts; the call sets d_skip[row] = 1 for every unused row and leaves the others as they are.
@@ -566,6 +568,56 @@ int  hpgv_grm_table_dev(hpgv_ctx *ctx, const int32_t *d_class4, int n_variants, 
  * range is never longer than 32 768 rows (hpgv_grm_plan_rows), so no i32 sum overflows whatever the shape. */
 int  hpgv_grm_pairs_dev(hpgv_ctx *ctx, const uint8_t *d_gt, size_t pitch, int n_variants, int n_cols,
                         const uint8_t *d_skip, const uint8_t *d_tab, hpgv_grm_acc *d_acc /* n_cols x n_cols */, void *stream);
+
+/* ---- PCA: the principal components of the GRM (GCTA's --pca, PLINK's --pca; no reference counterpart): the eigenpairs of
+ *      largest magnitude of a symmetric f64 matrix that lies in device memory, by block subspace iteration with Rayleigh-Ritz.
+ *      Parity with GCTA / PLINK is UNPINNED, as for "IBS" and "GRM": what follows is this project's definition.
+ *
+ *      With L = hpgv_pca_block(k) (16 for k <= 8, 32 for k <= 24) the solver keeps an n x L block Q with orthonormal columns:
+ *        start    Q[i][c] = u - 0.5 with u the top 53 bits, as a fraction, of splitmix64's finaliser
+ *                     x = seed + 0x9E3779B97F4A7C15 (32 i + c + 1);  x = (x ^ x >> 30) 0xBF58476D1CE4E5B9;
+ *                     x = (x ^ x >> 27) 0x94D049BB133111EB;  x ^= x >> 31;  u = (x >> 11) 2^-53
+ *                 (64-bit wrapping arithmetic: a function of (seed, row, column), not of a launch), then orthonormalised by
+ *                 CholQR done twice: G = Q^T Q, G = R^T R (hpgv_pca_chol_inv), Q <- Q R^-1.
+ *        sweep    Y = A Q (hpgv_pca_apply_dev);  H = Q^T Y, symmetrised (H + H^T) / 2 on the host;  H = W Theta W^T by
+ *                 hpgv_pca_jacobi, the pairs by decreasing |theta|;  the residual block R = Y W - Q W Theta formed on the device and
+ *                 its column norms taken (NOT w^T G w - theta^2, which cancels at about sqrt(eps));  converged when
+ *                 max over i < k of ||r_i|| <= tol max|theta|;  otherwise Q <- Y orthonormalised as at the start.
+ *        result   the k Ritz pairs of largest |theta|, written by DECREASING theta; vectors x = Q w of unit 2-norm, each with its
+ *                 component of largest magnitude positive (the lowest index on a tie).
+ *      Every sum over the n rows is taken in a fixed order (chunks of 256 rows, the partials added in chunk order; the block
+ *      product's order is csrc/hpgv_pca_kernels.h's) and no floating-point atomic is used: the result depends on (A, n, k, tol,
+ *      max_iter, seed) and nothing else -- not the device, its CU count, a stream or the run.
+ *      The error of eigenvalue i falls by about lambda_{L+1} / lambda_i per sweep (in magnitudes).  A cohort with population
+ *      structure has a few values well above the bulk and converges in some tens of sweeps; one WITHOUT structure, whose spectrum
+ *      is one bulk, needs many.  Out of scope: Chebyshev or Krylov acceleration, a product that reads only the upper triangle of A
+ *      (half the traffic, but a deterministic partial-sum scheme is needed), more than 24 pairs, a group form. */
+/* The n_cols x n_cols records of hpgv_grm_pairs_dev as a full f64 matrix with row pitch lda (in elements; >= n_cols and even):
+ * A[i][j] = A[j][i] = hpgv_grm_value of record [i][j] for i <= j, bit for bit.  Only records with i <= j are read.  A pair with
+ * n = 0 gets 0.0 on both sides and is counted ONCE in *d_n_empty, which the call zeroes on `stream` first.  Elements with a
+ * column index >= n_cols are not written.  n_cols == 0 succeeds.  HPGV_ERR_INVALID for frac_bits outside [0, 14], n_cols < 0,
+ * lda < n_cols or odd, a NULL d_acc, d_A or d_n_empty, d_acc or d_A not 16-byte, d_n_empty not 8-byte aligned; HPGV_ERR_UNSUPPORTED
+ * above 2 097 120 columns.  Asynchronous on `stream`. */
+int  hpgv_grm_matrix_dev(hpgv_ctx *ctx, const hpgv_grm_acc *d_acc, int n_cols, int frac_bits,
+                         double *d_A, size_t lda, uint64_t *d_n_empty, void *stream);
+/* Y = A Q: A symmetric n x n f64, stored FULL with row pitch lda (elements; >= n and even; d_A 16-byte aligned), Q and Y n x L
+ * row-major with pitch L, L = 16 or 32.  Elements of A at a row or column index >= n are never read; only the n x L elements of Y
+ * are written.  Every element of Y is summed in ONE fixed order that depends on (n, L) only; no floating-point atomics: the
+ * result is bit-identical from run to run.  A that is not symmetric gives A^T Q (a panel of rows is read as a panel of columns).
+ * n == 0 succeeds.  HPGV_ERR_INVALID for another L, n < 0, lda < n or odd, a NULL pointer, a misaligned one.  Asynchronous on
+ * `stream`; "profile" timing as hpgv_grm_pairs_dev. */
+int  hpgv_pca_apply_dev(hpgv_ctx *ctx, const double *d_A, int n, size_t lda, const double *d_Q, int L,
+                        double *d_Y, void *stream);
+/* The solver above on d_A (as hpgv_pca_apply_dev's; complete before the call).  Synchronous.  eigval[k], resid[k] = ||A x -
+ * theta x|| as the last sweep measured it, vec[n x k] row-major, *n_iter the sweeps done, *converged 1 or 0 (all host memory).  At
+ * max_iter without convergence the call still returns HPGV_OK with *converged = 0 and the last Ritz pairs with their true
+ * residuals.  For n <= L the answer is hpgv_pca_jacobi of A copied to the host: *n_iter = 0, residuals computed on the host.
+ * HPGV_ERR_INVALID for k < 1, k > 24, k > n, tol not positive or not finite, max_iter < 1, a NULL pointer, lda < n or odd, d_A not
+ * 16-byte aligned.  HPGV_ERR_UNSUPPORTED when a Cholesky pivot fails: the matrix has RANK BELOW L (the block cannot keep L
+ * independent columns), or is not finite. */
+int  hpgv_pca_dev(hpgv_ctx *ctx, const double *d_A, int n, size_t lda, int k, double tol, int max_iter, uint64_t seed,
+                  double *eigval /* host, k */, double *vec /* host, n x k row-major */, double *resid /* host, k */,
+                  int *n_iter, int *converged);
 
 /* ---- the variant-sharded resident scan of a GROUP context: what the runner's worker loop
  *      (assoc_runner.c:106-207, tdt_runner.c:150-200, stats_runner.c:176-215) becomes when the cohort lies in the HBM of
@@ -1157,6 +1209,17 @@ int  hpgv_grm_frac_bits(double min_maf);
 double hpgv_grm_value(const hpgv_grm_acc *a, int frac_bits);
 /* rows per row range of hpgv_grm_pairs_dev's launch on a device with n_cus compute units: a multiple of 64, never above 32 768 */
 int  hpgv_grm_plan_rows(int n_variants, int n_cols, int n_cus);
+/* The host pieces of "PCA" above.  No GPU call. */
+/* the block width of a k-pair solve: 16 for 1 <= k <= 8, 32 for k <= 24, -1 otherwise */
+int  hpgv_pca_block(int k);
+/* Cyclic Jacobi eigen-decomposition of the symmetric L x L matrix H (row-major, L <= 32; (H + H^T) / 2 is what is solved): on
+ * return column j of H is the unit eigenvector of theta[j], the pairs by decreasing |theta| (the lower diagonal position first
+ * among equals).  HPGV_ERR_INVALID for L outside [1, 32] or a NULL pointer. */
+int  hpgv_pca_jacobi(int L, double *H, double *theta);
+/* G = R^T R by Cholesky (R upper triangular) and M = R^-1, L x L row-major, L <= 32.  Returns 0, or 1 when a pivot fell to or
+ * below L * DBL_EPSILON * (the largest diagonal element of G) or is NaN: G is singular to working precision or indefinite, and
+ * M is then not to be used.  -1 for L outside [1, 32] or a NULL pointer. */
+int  hpgv_pca_chol_inv(int L, const double *G, double *M);
 
 /* streaming-read ceiling probe: reads `bytes` from d_buf with the scan's load
  * shape and no arithmetic; returns the kernel time in ms (diagnostic) */

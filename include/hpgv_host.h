@@ -533,6 +533,28 @@ int  hpgv_run_genome(const char *vcf_path, const char *out_path, double min_pi_h
  * NULL path or a min_maf outside (0, 0.5] (NaN included): HPGV_ERR_INVALID before anything is opened, and no file is written. */
 int  hpgv_run_grm(const char *vcf_path, const char *out_prefix, double min_maf, size_t batch_bytes,
                   long *n_variants_out, long *n_samples_out);
+/* The first n_pcs principal components of that matrix (include/hpgv.h "PCA"; GCTA's and PLINK's --pca, parity unpinned).  The
+ * pass over the VCF is hpgv_run_grm's, unchanged; then the integer sum of the devices' buffers goes to the first device,
+ * hpgv_grm_matrix_dev makes the f64 matrix there and hpgv_pca_dev solves it with tol = HPGV_RUN_PCA_TOL, max_iter =
+ * HPGV_RUN_PCA_MAX_ITER and seed = HPGV_RUN_PCA_SEED.  The sums are integers and the solver is deterministic, so the files do not
+ * depend on batch_bytes, engine threads, input form or devices:
+ *     <out_prefix>.eigenval    one "%.8g" value per line, decreasing
+ *     <out_prefix>.eigenvec    per sample "name<TAB>name" and n_pcs values in "%.8g", tab-separated
+ * and, with write_grm != 0, hpgv_run_grm's three files, byte for byte.  *n_iter_out: the sweeps done.  A run that does NOT
+ * converge within max_iter (a cohort without structure: include/hpgv.h "PCA") still writes the files, with the last Ritz pairs,
+ * and returns HPGV_OK; it says so by *n_iter_out = -max_iter.  No file at all is written by: a pair of samples with n = 0 (a
+ * sample without calls: drop it) -- HPGV_ERR_UNSUPPORTED; n_pcs outside [1, 24] or above the sample count, a NULL path, a bad
+ * min_maf -- HPGV_ERR_INVALID. */
+#define HPGV_RUN_PCA_TOL 1e-8
+#define HPGV_RUN_PCA_MAX_ITER 1000
+#define HPGV_RUN_PCA_SEED 1ull
+int  hpgv_run_pca(const char *vcf_path, const char *out_prefix, double min_maf, int n_pcs, int write_grm, size_t batch_bytes,
+                  long *n_variants_out, long *n_samples_out, int *n_iter_out);
+/* The same solver on <grm_prefix>.grm.bin and .grm.id of an earlier run (as gcta --grm X --pca): the float32 lower triangle
+ * widened to f64 and mirrored, the lines of .grm.id copied in front of the vectors.  Files, constants and *n_iter_out as
+ * hpgv_run_pca.  A NaN element (a pair with n = 0): HPGV_ERR_UNSUPPORTED; a NULL path, unreadable files, sizes that do not
+ * agree, n_pcs outside [1, 24] or above the sample count: HPGV_ERR_INVALID; no file is written by any of them. */
+int  hpgv_run_pca_grm(const char *grm_prefix, const char *out_prefix, int n_pcs, long *n_samples_out, int *n_iter_out);
 /* stage times of the last run on this process: {read, engine, write, sort, total} seconds and the number of
  * batches; read / engine / write overlap (three threads, three batch buffers in rotation).  The reader and
  * formatter teams use HPGV_IO_THREADS threads (environment; default half the cores, at most 16);
