@@ -30,6 +30,9 @@ COND_UNAFFECTED, COND_AFFECTED, COND_OTHER = 0, 1, 2
 SEX_MALE, SEX_FEMALE, SEX_UNKNOWN = 0, 1, 2
 # the model tests' order in chisq5 / p5 (HPGV_MODEL_* of include/hpgv.h)
 MODEL_GENO, MODEL_TREND, MODEL_ALLELIC, MODEL_DOM, MODEL_REC = range(5)
+# the logistic regression's limits and row status (HPGV_LOGISTIC_MAX_COVAR, HPGV_LOGIT_* of include/hpgv.h)
+LOGISTIC_MAX_COVAR = 14
+LOGIT_OK, LOGIT_NOT_CONVERGED, LOGIT_SINGULAR = 0, 1, 2
 LAYOUT_ASSOC, LAYOUT_TDT, LAYOUT_STATS, LAYOUT_STATS_GROUPS, LAYOUT_MENDEL, LAYOUT_EPI = 0, 1, 2, 3, 4, 5
 GT_MISSING = 0xFF
 # the tokenizer's tile records that hpgv_bgzf_verify_tiles_dev leaves (csrc/hpgv_text2_kernels.h: TOK2_TILE, struct TokAgg2 { TokAgg
@@ -67,6 +70,7 @@ SYMBOLS = [
     "hpgv_set_perm_labels", "hpgv_assoc_perm_dev", "hpgv_assoc_perm", "hpgv_assoc_perm_text", "hpgv_perm_labels_shuffle", "hpgv_perm_pvalues",
     "hpgv_set_tdt_flips", "hpgv_tdt_perm_dev", "hpgv_tdt_perm", "hpgv_tdt_perm_text", "hpgv_perm_flips_shuffle",
     "hpgv_assoc_model_scan_dev", "hpgv_assoc_model_stats_dev", "hpgv_assoc_trend_perm_dev", "hpgv_assoc_model", "hpgv_assoc_model_text",
+    "hpgv_set_covariates", "hpgv_assoc_logistic_dev", "hpgv_assoc_logistic", "hpgv_assoc_logistic_text", "hpgv_logistic_fit",
     "hpgv_ld_window_dev", "hpgv_ld", "hpgv_ld_text", "hpgv_ld_r2",
     "hpgv_ld_edges_dev", "hpgv_ld_edges", "hpgv_clump",
     "hpgv_rows_gather_scratch_bytes", "hpgv_rows_gather_dev", "hpgv_assoc_select_text",
@@ -83,6 +87,9 @@ IBS_PAIR = np.dtype([("i", np.int32), ("j", np.int32), ("c", IBS_COUNTS), ("pi_h
 # hpgv_grm_acc: {int64 sq, n}, 16 bytes; a row's table record of hpgv_grm_table_dev: {int8 hi[4], lo[4]}, 8 bytes
 GRM_ACC = np.dtype([("sq", np.int64), ("n", np.int64)])
 GRM_TAB = np.dtype([("hi", np.int8, 4), ("lo", np.int8, 4)])
+# hpgv_logistic_result: {double beta, se, stat, p; int32 n_obs, iters, status, pad}, 48 bytes
+LOGISTIC_RESULT = np.dtype([("beta", np.float64), ("se", np.float64), ("stat", np.float64), ("p", np.float64),
+                            ("n_obs", np.int32), ("iters", np.int32), ("status", np.int32), ("pad", np.int32)])
 
 
 class HpgvError(RuntimeError):
@@ -245,6 +252,11 @@ def load():
     L.hpgv_assoc_trend_perm_dev.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
     L.hpgv_assoc_model.argtypes = [vp, vp, sz, i32] + [vp] * 5
     L.hpgv_assoc_model_text.argtypes = [vp, C.c_char_p, sz, i32, C.POINTER(i32), vp, vp, vp] + [vp] * 5
+    L.hpgv_set_covariates.argtypes = [vp, vp, i32, i32]
+    L.hpgv_assoc_logistic_dev.argtypes = [vp, vp, i32, i32, C.c_double, vp, vp, vp]
+    L.hpgv_assoc_logistic.argtypes = [vp, vp, sz, i32, i32, C.c_double, vp, vp]
+    L.hpgv_assoc_logistic_text.argtypes = [vp, C.c_char_p, sz, i32, C.POINTER(i32), vp, vp, vp, i32, C.c_double, vp, vp]
+    L.hpgv_logistic_fit.argtypes = [vp, vp, vp, i32, i32, i32, C.c_double, vp, vp]
     L.hpgv_ld_window_dev.argtypes = [vp, vp, sz, i32, i32, i32, vp, vp, C.c_int64, vp, vp, vp, vp]
     L.hpgv_ld.argtypes = [vp, vp, sz, i32, i32, vp, vp, C.c_int64, vp, vp]
     L.hpgv_ld_text.argtypes = [vp, C.c_char_p, sz, i32, C.POINTER(i32), vp, vp, vp, i32, vp, vp]
@@ -338,6 +350,61 @@ def run_assoc_model(vcf_path, ped_path, out_path, n_perms=0, seed=0, batch_bytes
         e.code = rc
         raise e
     return n.value
+
+
+def run_assoc_logistic(vcf_path, ped_path, covar_path, out_path, n_covar=0, batch_bytes=1 << 22):
+    """hpgv_run_assoc_logistic of libhpgv_host.so (include/hpgv_host.h): one logistic regression per variant with the first n_covar
+    value columns of the covariate file (0: all of them; covar_path None: no covariates) at out_path.  Paths may be None (the call
+    then fails with ERR_INVALID).  Returns (variants written, cohort samples used)."""
+    _build.build_host_lib()
+    H = C.CDLL(_build.HOSTLIB)
+    H.hpgv_run_assoc_logistic.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_long), C.POINTER(C.c_long)]
+    H.hpgv_host_last_error.restype = C.c_char_p
+    n, used = C.c_long(0), C.c_long(0)
+    enc = lambda q: None if q is None else os.fsencode(q)
+    rc = H.hpgv_run_assoc_logistic(enc(vcf_path), enc(ped_path), enc(covar_path), n_covar, enc(out_path), batch_bytes, C.byref(n), C.byref(used))
+    if rc != OK:
+        e = HpgvError("hpgv_run_assoc_logistic -> %d: %s" % (rc, (H.hpgv_host_last_error() or b"").decode(errors="replace")))
+        e.code = rc
+        raise e
+    return n.value, used.value
+
+
+def covar_read(covar_path, names, n_covar=0):
+    """hpgv_host_covar_read of libhpgv_host.so: the covariate file's values for the samples `names` (a list of str).  Returns
+    (cov (n, C) float64, have (n,) uint8: 1 where the sample has a line of finite values).  Raises HpgvError (code ERR_INVALID) on a
+    duplicate id, a ragged line, more than LOGISTIC_MAX_COVAR columns in use or an unreadable file."""
+    _build.build_host_lib()
+    H = C.CDLL(_build.HOSTLIB)
+    H.hpgv_host_covar_read.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p]
+    H.hpgv_host_last_error.restype = C.c_char_p
+    arr = (C.c_char_p * max(len(names), 1))(*[os.fsencode(q) for q in names])
+    cov = np.zeros((max(len(names), 1), LOGISTIC_MAX_COVAR), np.float64)
+    have = np.zeros(max(len(names), 1), np.uint8)
+    nc = C.c_int(0)
+    rc = H.hpgv_host_covar_read(None if covar_path is None else os.fsencode(covar_path), arr, len(names), n_covar, C.byref(nc), _ptr(cov), _ptr(have))
+    if rc != OK:
+        e = HpgvError("hpgv_host_covar_read -> %d: %s" % (rc, (H.hpgv_host_last_error() or b"").decode(errors="replace")))
+        e.code = rc
+        raise e
+    return cov[:len(names), :nc.value].copy(), have[:len(names)].copy()
+
+
+def logistic_fit(cls, y, cov=None, max_iter=25, tol=1e-10):
+    """hpgv_logistic_fit: the logistic regression of include/hpgv.h on the host, samples in index order.  cls: genotype classes
+    (0, 1, 2; anything else missing), y: 1 = affected, cov (n, C) or None.  Returns (a LOGISTIC_RESULT record, coef (2, p): beta
+    then se).  No device needed."""
+    c, yy = _np(cls, np.uint8), _np(y, np.uint8)
+    cv = np.zeros((len(c), 0), np.float64) if cov is None else _np(cov, np.float64).reshape(len(c), -1)
+    nc = cv.shape[1]
+    out = np.zeros(1, LOGISTIC_RESULT)
+    coef = np.zeros((2, min(nc, LOGISTIC_MAX_COVAR) + 2), np.float64)
+    rc = load().hpgv_logistic_fit(_ptr(c), _ptr(yy), _ptr(cv) if nc else None, len(c), nc, int(max_iter), float(tol), _ptr(out), _ptr(coef))
+    if rc != OK:
+        e = HpgvError("hpgv_logistic_fit -> %d" % rc)
+        e.code = rc
+        raise e
+    return out[0], coef
 
 
 def run_genome(vcf_path, out_path, min_pi_hat=0.0, batch_bytes=1 << 22):
@@ -670,6 +737,7 @@ class Engine:
         c = _np(condition, np.uint8)
         self._chk(self.L.hpgv_set_cohort(self.h, _ptr(c), len(c)))
         self._n_perms = 0               # a new cohort drops the label rows
+        self._n_covar = 0               # and the covariates
         self._n_samples = len(c)
         return self.assoc_layout()
 
@@ -852,6 +920,35 @@ class Engine:
         if not perm:
             return _text_result(nl, max_lines, status=status, counts8=c8, chisq5=chisq5, p5=p5)
         return dict(_text_result(nl, max_lines, status=status, counts8=c8, chisq5=chisq5, p5=p5, n_ge=n_ge), batch_max=bmax[:np_])
+
+    def set_covariates(self, cov):
+        """hpgv_set_covariates: cov (n_samples, C) in VCF column order; None or no columns clears them."""
+        if cov is None or np.asarray(cov).size == 0:
+            self._chk(self.L.hpgv_set_covariates(self.h, None, getattr(self, "_n_samples", 0), 0))
+            self._n_covar = 0
+            return
+        cv = _np(cov, np.float64)
+        assert cv.ndim == 2
+        self._chk(self.L.hpgv_set_covariates(self.h, _ptr(cv), cv.shape[0], cv.shape[1]))
+        self._n_covar = cv.shape[1]
+
+    def assoc_logistic(self, gt, max_iter=25, tol=1e-10, coef=False):
+        """hpgv_assoc_logistic: a LOGISTIC_RESULT array (nv,) and, with coef, (nv, 2, p): beta then se of every coefficient."""
+        gt = _np(gt, np.uint8)
+        nv, pitch = gt.shape
+        out = np.zeros(nv, LOGISTIC_RESULT)
+        cf = np.zeros((nv, 2, getattr(self, "_n_covar", 0) + 2), np.float64) if coef else None
+        self._chk(self.L.hpgv_assoc_logistic(self.h, _ptr(gt), pitch, nv, int(max_iter), float(tol), _ptr(out), _ptr(cf)))
+        return (out, cf) if coef else out
+
+    def assoc_logistic_text(self, text, max_lines=None, max_iter=25, tol=1e-10, coef=False):
+        """hpgv_assoc_logistic_text: assoc_logistic on VCF data lines, the outputs per line."""
+        text, max_lines, m, status, nl = _text_call(text, max_lines)
+        out = np.zeros(m, LOGISTIC_RESULT)
+        cf = np.zeros((m, 2, getattr(self, "_n_covar", 0) + 2), np.float64) if coef else None
+        self._chk(self.L.hpgv_assoc_logistic_text(self.h, text, len(text), max_lines, C.byref(nl), None, None, _ptr(status),
+                                                  int(max_iter), float(tol), _ptr(out), _ptr(cf)))
+        return _text_result(nl, max_lines, status=status, out=out, coef=cf)
 
     def ld(self, gt, window, chrom=None, pos=None, max_bp=-1, counts=True):
         """hpgv_ld: r2 (nv, window) and, with counts, counts6 (nv, window, 6); element [b, d - 1] is the pair (b - d, b) over the
@@ -1226,6 +1323,9 @@ class Engine:
 
     def assoc_trend_perm_dev(self, d_gt, n_variants, d_counts8, d_n_ge, d_batch_max, d_perm_sums=None, stream=None):
         self._chk(self.L.hpgv_assoc_trend_perm_dev(self.h, d_gt, n_variants, d_counts8, d_n_ge, d_batch_max, d_perm_sums, stream))
+
+    def assoc_logistic_dev(self, d_gt, n_variants, d_out, d_coef=None, max_iter=25, tol=1e-10, stream=None):
+        self._chk(self.L.hpgv_assoc_logistic_dev(self.h, d_gt, n_variants, int(max_iter), float(tol), d_out, d_coef, stream))
 
     def ld_window_dev(self, d_gt, pitch, n_variants, window, d_r2, d_counts6=None, b_begin=0, d_chrom=None, d_pos=None, max_bp=-1,
                       d_skip=None, stream=None):

@@ -1,5 +1,5 @@
 /* host_runner.c -- the file runners: reader -> engine threads -> writer (hpgv_run_assoc / tdt / aggregate / stats / vcf2epi /
- * filter / split / genome / grm).  The VCF tools' own batch steps and writers are in host_vcftools.c, what a run keeps beside its result file in
+ * filter / split / genome / grm / logistic).  The VCF tools' own batch steps and writers are in host_vcftools.c, what a run keeps beside its result file in
  * host_sideout.c.
  * Part of libhpgv_host.so (see hpgv_host_internal.h for the map of its units). */
 #include "hpgv_host_internal.h"
@@ -123,6 +123,9 @@ static int engine_call(run_t *R, run_batch_t *b, const char **what, int *again) 
     case RUN_MODEL: case RUN_MODEL_PERM: *what = "hpgv_assoc_model_text";
         return hpgv_assoc_model_text(g_ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status,
                                      b->ints, b->dbl, b->dbl + 5 * (size_t)m, tool == RUN_MODEL_PERM ? b->n_ge : NULL, tool == RUN_MODEL_PERM ? b->bmax : NULL);
+    case RUN_LOGISTIC: *what = "hpgv_assoc_logistic_text";
+        return hpgv_assoc_logistic_text(g_ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status,
+                                        HPGV_RUN_LOGISTIC_MAX_ITER, HPGV_RUN_LOGISTIC_TOL, (hpgv_logistic_result *)b->dbl, NULL);
     case RUN_GENOME: { *what = "hpgv_ibs_text";            /* on one device of the run, into that device's counts (a batch with more lines than room adds nothing) */
         hpgv_ibs_counts *d_counts = NULL;
         hpgv_ctx *ctx = run_genome_device(R, b, &d_counts);
@@ -307,7 +310,7 @@ static int run_cohort(run_t *R, const char *vcf_path, const char *ped_path) {
         free(fcol); free(mcol); free(coff); free(ccol); free(csex); free(done);
         break;
     }
-    case RUN_CHISQ: case RUN_CHISQ_PERM: case RUN_FISHER: case RUN_VCF2EPI: case RUN_MODEL: case RUN_MODEL_PERM: {
+    case RUN_CHISQ: case RUN_CHISQ_PERM: case RUN_FISHER: case RUN_VCF2EPI: case RUN_MODEL: case RUN_MODEL_PERM: case RUN_LOGISTIC: {
         int matched = 0;
         uint8_t *cond = cohort_conditions(R, ids, &matched);
         if (!cond) { rc = HPGV_ERR_NOMEM; break; }
@@ -321,8 +324,20 @@ static int run_cohort(run_t *R, const char *vcf_path, const char *ped_path) {
                 if (cond[j] == HPGV_COND_AFFECTED) R->epi_aff++; else R->epi_unaff++;
             }
         }
+        double *cov = NULL;
+        if (!rc && R->tool == RUN_LOGISTIC && R->covar) {             /* a cohort sample without a line of finite values leaves the cohort */
+            uint8_t *have = (uint8_t *)malloc((size_t)n_samples + 1);
+            cov = (double *)malloc(sizeof(double) * ((size_t)n_samples * (size_t)R->n_covar + 1));
+            if (!have || !cov) rc = HPGV_ERR_NOMEM;
+            if (!rc) rc = covar_table_match(R->covar, R->names, n_samples, R->n_covar, cov, (size_t)R->n_covar, have);
+            for (int j = 0; !rc && j < n_samples; j++) if (!have[j]) cond[j] = HPGV_COND_OTHER;
+            free(have);
+        }
+        if (R->tool == RUN_LOGISTIC) for (int j = 0; j < n_samples; j++) R->n_used += cond[j] == HPGV_COND_AFFECTED || cond[j] == HPGV_COND_UNAFFECTED;
         if (!rc && (rc = hpgv_set_cohort(g_ctx, cond, n_samples))) host_fail("hpgv_set_cohort", rc);
         g_assoc_key.set = 0;
+        if (!rc && cov && R->n_covar > 0 && (rc = hpgv_set_covariates(g_ctx, cov, n_samples, R->n_covar))) host_fail("hpgv_set_covariates", rc);
+        free(cov);
         if (!rc && (R->tool == RUN_CHISQ_PERM || R->tool == RUN_MODEL_PERM)) {          /* the run's label rows, once: shuffles of the PED's conditions */
             uint8_t *labels = (uint8_t *)malloc((size_t)R->n_perms * (size_t)(n_samples > 0 ? n_samples : 1));
             if (!labels) rc = HPGV_ERR_NOMEM;
@@ -353,7 +368,7 @@ static int run_cohort(run_t *R, const char *vcf_path, const char *ped_path) {
     /* --inh-dom / --inh-rec scan the assoc layout: the tools that have not installed it get it from the PED (PHENO 2
      * affected, 1 unaffected, as the assoc runner); vcf2epi keeps its own classes */
     if (!rc && rec_filters_inheritance(R->rf)) {
-        if (!tool_chisq(R->tool) && !tool_model(R->tool) && R->tool != RUN_FISHER && R->tool != RUN_VCF2EPI) {
+        if (!tool_chisq(R->tool) && !tool_model(R->tool) && R->tool != RUN_FISHER && R->tool != RUN_VCF2EPI && R->tool != RUN_LOGISTIC) {
             int matched = 0;
             uint8_t *cond = cohort_conditions(R, ids, &matched);
             if (!cond) rc = HPGV_ERR_NOMEM;
@@ -413,6 +428,12 @@ static int run_headers(run_t *R) {
     }
     case RUN_MODEL: case RUN_MODEL_PERM: {
         const char *h = "#CHR\tPOS\tID\tA1\tA2\tAFF\tUNAFF\tCHISQ_GENO\tP_GENO\tCHISQ_TREND\tP_TREND\tCHISQ_ALLELIC\tP_ALLELIC\tCHISQ_DOM\tP_DOM\tCHISQ_REC\tP_REC";
+        fprintf(out, "%s\n", h);
+        order_track_keep(&R->ord, h, strlen(h));
+        return HPGV_OK;
+    }
+    case RUN_LOGISTIC: {
+        const char *h = "#CHR\tPOS\tID\tA1\tA2\tNOBS\tBETA\tSE\tOR\tSTAT\tP\tITER";
         fprintf(out, "%s\n", h);
         order_track_keep(&R->ord, h, strlen(h));
         return HPGV_OK;
@@ -519,7 +540,7 @@ static int run_pipeline(run_t *R, size_t batch_bytes) {
                 R->written += b->n_pass; R->skipped += b->n_skip;
                 break;
             case RUN_CHISQ: case RUN_CHISQ_PERM: case RUN_FISHER: case RUN_TDT: case RUN_TDT_PERM: case RUN_VCF2EPI: case RUN_AGGREGATE: case RUN_STATS:
-            case RUN_MODEL: case RUN_MODEL_PERM:
+            case RUN_MODEL: case RUN_MODEL_PERM: case RUN_LOGISTIC:
                 if (write_batch(R->out, b, fmt + (fmt_set ? RUN_FMT_BUFS / 2 : 0), n_fmt, &wpool, &R->ord, use_fw ? &fw : NULL)) bad = "cannot write the result file";
                 for (int i = 0; i < b->n_lines; i++) if (record_passes(b, i)) R->written++;
                 if (tool_perm(R->tool) && !bad && run_perm_add(R, b)) bad = "out of memory for the permutation results";
@@ -585,6 +606,7 @@ static int run_finish(run_t *R, int rc, const char *out_path) {
         if (g_ctx) (void)(R->tool == RUN_TDT_PERM ? hpgv_set_tdt_flips(g_ctx, NULL, 0) : hpgv_set_perm_labels(g_ctx, NULL, 0));
         run_perm_free(R);
     }
+    if (R->tool == RUN_LOGISTIC && g_ctx) (void)hpgv_set_covariates(g_ctx, NULL, 0, 0);
     if (R->CL) {
         if (!rc) rc = run_clump_write(R, out_path);
         R->n_clumps = R->CL->n_clumps; R->n_truncated = R->CL->n_truncated;      /* for hpgv_run_assoc_clump, past the store */
@@ -628,7 +650,7 @@ static int run_file_held(run_t *R, const char *vcf_path, const char *ped_path, c
     if (rc) return rc;
     if (batch_bytes < (1u << 16)) batch_bytes = 1u << 16;
     const run_tool_t tool = R->tool; R->io_threads = default_io_threads();      /* the input: the PED (assoc, TDT, vcf2epi), the VCF's header */
-    if (!ped_path && (tool_chisq(tool) || tool_model(tool) || tool == RUN_FISHER || tool_tdt(tool) || tool == RUN_VCF2EPI)) { snprintf(g_err, sizeof g_err, "this runner needs a PED file (ped_path is NULL)"); return HPGV_ERR_INVALID; }
+    if (!ped_path && (tool_chisq(tool) || tool_model(tool) || tool == RUN_LOGISTIC || tool == RUN_FISHER || tool_tdt(tool) || tool == RUN_VCF2EPI)) { snprintf(g_err, sizeof g_err, "this runner needs a PED file (ped_path is NULL)"); return HPGV_ERR_INVALID; }
     if (ped_path && (rc = ped_table_read(ped_path, &R->ped))) return rc;
     if (source_open(&R->rd.src, vcf_path)) { ped_table_free(&R->ped); snprintf(g_err, sizeof g_err, "cannot open VCF file %s", vcf_path); return HPGV_ERR_INVALID; }
     R->t_opened = now_s();
@@ -749,6 +771,28 @@ int hpgv_run_assoc_model(const char *vcf_path, const char *ped_path, const char 
     if (run_args(n_variants_out, vcf_path && ped_path && out_path, "vcf_path, ped_path and out_path must not be NULL")) return HPGV_ERR_INVALID;
     if (n_perms < 0) { snprintf(g_err, sizeof g_err, "n_perms must not be negative"); return HPGV_ERR_INVALID; }
     return run_file(&(run_t){ .tool = n_perms ? RUN_MODEL_PERM : RUN_MODEL, .filters = g_filters, .n_perms = n_perms, .perm_seed = seed }, vcf_path, ped_path, out_path, batch_bytes, n_variants_out);
+}
+
+/* the logistic regression's run: the covariate file read and checked before the engine starts, then RUN_MODEL's pipeline with
+ * hpgv_assoc_logistic_text as its engine call */
+int hpgv_run_assoc_logistic(const char *vcf_path, const char *ped_path, const char *covar_path, int n_covar, const char *out_path,
+                            size_t batch_bytes, long *n_variants_out, long *n_samples_used_out) {
+    if (n_samples_used_out) *n_samples_used_out = 0;
+    if (run_args(n_variants_out, vcf_path && ped_path && out_path, "vcf_path, ped_path and out_path must not be NULL")) return HPGV_ERR_INVALID;
+    if (n_covar < 0 || (n_covar > 0 && !covar_path)) { snprintf(g_err, sizeof g_err, "n_covar %d: not negative, and 0 without a covariate file", n_covar); return HPGV_ERR_INVALID; }
+    covar_table_t T;
+    memset(&T, 0, sizeof T);
+    int use = 0;
+    if (covar_path) {
+        const int rc0 = covar_table_read(covar_path, &T);
+        if (rc0) return rc0;
+        if ((use = covar_table_columns(&T, n_covar)) < 0) { covar_table_free(&T); return HPGV_ERR_INVALID; }
+    }
+    run_t R = { .tool = RUN_LOGISTIC, .filters = g_filters, .covar = covar_path ? &T : NULL, .n_covar = use };
+    const int rc = run_file(&R, vcf_path, ped_path, out_path, batch_bytes, n_variants_out);
+    if (n_samples_used_out && !rc) *n_samples_used_out = R.n_used;
+    covar_table_free(&T);
+    return rc;
 }
 
 int hpgv_run_tdt(const char *vcf_path, const char *ped_path, const char *out_path, size_t batch_bytes, long *n_variants_out) {

@@ -312,6 +312,71 @@ int  hpgv_assoc_model_stats_dev(hpgv_ctx *ctx, const int32_t *d_counts8, int n_v
 int  hpgv_assoc_trend_perm_dev(hpgv_ctx *ctx, const uint8_t *d_gt, int n_variants, const int32_t *d_counts8,
                                int32_t *d_n_ge, double *d_batch_max, int32_t *d_perm_sums /* may be NULL */, void *stream);
 
+/* ---- Logistic regression: the association test with covariates (PLINK's --logistic --covar; no reference counterpart, and
+ *      parity with PLINK is unpinned: this block is the specification).  One regression per variant, of the phenotype on the
+ *      ALT allele count and up to HPGV_LOGISTIC_MAX_COVAR covariates per sample -- the principal components of hpgv_pca_dev, say.
+ *
+ *      Observations of a row v in the assoc layout: the cohort columns whose genotype at v is not missing, by the byte rule of
+ *      "model tests" above (missing / 0 / 1 / 2, "1/2" is hom-alt).  d = class index = number of ALT alleles; y = 1 for an
+ *      affected column, 0 for an unaffected one.  Pad bytes are never observations.  Chromosome X gets no special rule.
+ *
+ *      Design row x = [1, d, c_1 .. c_C], p = C + 2 coefficients, 0 <= C <= HPGV_LOGISTIC_MAX_COVAR (so p <= 16).
+ *
+ *      Fit: Newton-Raphson from beta = 0, everything f64.  Per iteration, over the observations:
+ *          eta = x . beta   (fma chain: beta_0, then i = 1 .. p - 1 in order)
+ *          mu = 1 / (1 + exp(-eta)),   w = mu (1 - mu)
+ *          H = sum w x x^T  (term (w x_i) x_j added with one fma),   u = sum (y - mu) x  (one fma per term)
+ *      H = L L^T by Cholesky (right-looking, no pivoting); a pivot <= 1e-12 x the diagonal element of H it came from -- or a NaN
+ *      one -- ends the fit as SINGULAR.  V = H^-1 = L^-T L^-1, the step delta_i = sum_j V_ij u_j (j ascending), beta += delta.
+ *      Converged when max_i |delta_i| <= tol.  max_iter in 1 .. 100, tol finite and >= 0.
+ *      The order in which the observations are summed is fixed per implementation (the device: hpgv_assoc_logistic_dev below;
+ *      the host: index order), so results are reproducible; the two orders differ by rounding only.
+ *
+ *      Covariance: V of the H that produced the LAST step (no further pass over the samples).  se_i = sqrt(V_ii);
+ *      stat = (beta_1 / se_1)^2 for the genotype coefficient; p = the 1-df chi-square tail by the device function
+ *      hpgv_assoc_chisq_dev uses (the host form: the same expression on libm's erf / erfc).
+ *
+ *      Status per row:
+ *          HPGV_LOGIT_OK             converged
+ *          HPGV_LOGIT_NOT_CONVERGED  max_iter steps were taken without convergence, or a non-finite beta appeared
+ *          HPGV_LOGIT_SINGULAR       the pivot rule above: a row monomorphic among its observations, d collinear with the
+ *                                    intercept or a covariate, n_obs < p (n_obs = 0 included), and most separated data
+ *      On any status but OK beta, se, stat and p are NaN; n_obs and iters (the steps taken, i.e. additions to beta) are
+ *      still written. */
+enum { HPGV_LOGISTIC_MAX_COVAR = 14 };
+enum { HPGV_LOGIT_OK = 0, HPGV_LOGIT_NOT_CONVERGED = 1, HPGV_LOGIT_SINGULAR = 2 };
+/* 48 bytes; arrays of it are 16-byte aligned.  beta, se: of the genotype coefficient (index 1) */
+typedef struct { double beta, se, stat, p; int32_t n_obs, iters, status, pad; } hpgv_logistic_result;
+/* cov[j * n_covar + k]: covariate k of VCF column j, the indexing of hpgv_set_cohort's condition[].  Kept on the device in the
+ * assoc layout's column order, one row of pitch doubles per covariate, zeros under the pads.  After
+ * hpgv_set_cohort (else HPGV_ERR_STATE); n_samples must be the cohort's (else HPGV_ERR_INVALID); n_covar above
+ * HPGV_LOGISTIC_MAX_COVAR is HPGV_ERR_UNSUPPORTED; a non-finite value in a cohort column is HPGV_ERR_INVALID (columns with
+ * HPGV_COND_OTHER may hold anything).  n_covar == 0 clears them; so does a new hpgv_set_cohort.  A group context gives every
+ * member the covariates.  Not to be called while logistic calls of the context are in flight. */
+int  hpgv_set_covariates(hpgv_ctx *ctx, const double *cov, int n_samples, int n_covar);
+/* d_gt in assoc layout (16-byte aligned) -> d_out[v] (16-byte aligned) and, unless NULL, d_coef (8-byte aligned):
+ * n_variants x 2p doubles, beta_0 .. beta_{p-1} then se_0 .. se_{p-1}, NaN on failure.  Without covariates C = 0.  One launch
+ * runs the whole fit of every row; asynchronous on `stream`.  A row's results depend on that row only: one workgroup of four
+ * waves per row, every lane sums its samples in position order, lanes are added by a fixed butterfly, waves in wave order, no
+ * floating-point atomics -- a matrix passed in one call or in pieces gives bit-identical records, and so do two runs.
+ * HPGV_ERR_INVALID for max_iter outside 1 .. 100, a tol that is negative or not finite, n_variants < 0, a NULL or
+ * misaligned pointer. */
+int  hpgv_assoc_logistic_dev(hpgv_ctx *ctx, const uint8_t *d_gt, int n_variants, int max_iter, double tol,
+                             hpgv_logistic_result *d_out, double *d_coef /* may be NULL */, void *stream);
+/* The same on a host batch in VCF column order (as hpgv_assoc_model: chain stager, HPGV_LAYOUT_ASSOC layout) and on a text (as
+ * hpgv_assoc_model_text: tokenizer, record filters, line status).  out: n_variants (max_lines) records; coef (may be NULL):
+ * n_variants (max_lines) x 2p doubles.  Synchronous and thread-safe; a group context deals the call to a member. */
+int  hpgv_assoc_logistic(hpgv_ctx *ctx, const uint8_t *gt, size_t pitch, int n_variants, int max_iter, double tol,
+                         hpgv_logistic_result *out, double *coef /* may be NULL */);
+int  hpgv_assoc_logistic_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, int max_lines, int *n_lines,
+                              uint64_t *line_off, uint32_t *field_off, int32_t *status, int max_iter, double tol,
+                              hpgv_logistic_result *out, double *coef /* may be NULL */);
+/* The definition on the host, samples in index order: cls[i] in {0, 1, 2} or anything else for missing, y[i] 1 = affected,
+ * cov[i * n_covar + k].  coef (may be NULL): 2p doubles.  No GPU call, no context.  HPGV_ERR_INVALID for n < 0, n_covar
+ * outside 0 .. HPGV_LOGISTIC_MAX_COVAR, a bad max_iter or tol, a NULL pointer it needs. */
+int  hpgv_logistic_fit(const uint8_t *cls, const uint8_t *y, const double *cov, int n, int n_covar, int max_iter, double tol,
+                       hpgv_logistic_result *out, double *coef /* may be NULL */);
+
 /* d_gt in tdt layout -> d_tu[v] = {t1, t2} (int32 x2) */
 int  hpgv_tdt_scan_dev(hpgv_ctx *ctx, const uint8_t *d_gt, int n_variants,
                        const uint8_t *d_is_x, int32_t *d_tu, void *stream);

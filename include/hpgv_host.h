@@ -317,6 +317,35 @@ int  hpgv_run_assoc_perm(const char *vcf_path, const char *ped_path, const char 
  * Same cohort, filters, record filters and input forms (plain, gzip, bgzip) as hpgv_run_assoc. */
 int  hpgv_run_assoc_model(const char *vcf_path, const char *ped_path, const char *out_path, int n_perms, uint64_t seed,
                           size_t batch_bytes, long *n_variants_out);
+/* The association test with covariates (include/hpgv.h "Logistic regression"; PLINK's --logistic --covar, parity unpinned): one
+ * logistic regression per variant of the phenotype on the ALT allele count and the covariates.  out_path gets the header line
+ *     #CHR POS ID A1 A2 NOBS BETA SE OR STAT P ITER
+ * and one line per written variant, tab-separated, sorted as hpgv_run_assoc_model's file.  A1 is REF and A2 is ALT as there; the
+ * TESTED allele is ALT (PLINK tests the minor allele: a sign flip of BETA where ALT is the major one).  NOBS, ITER: n_obs and
+ * iters of the row's hpgv_logistic_result; BETA, SE, STAT, P of the genotype coefficient and OR = exp(BETA), printed as
+ * hpgv_host_format_f6 prints them; a failed fit (status not HPGV_LOGIT_OK) prints nan in the five.  Every batch goes through
+ * hpgv_assoc_logistic_text with max_iter HPGV_RUN_LOGISTIC_MAX_ITER and tol HPGV_RUN_LOGISTIC_TOL; a row's result depends on
+ * that row only, so the file does not depend on batch_bytes, engine threads, input form or devices.
+ *   covar_path (may be NULL: no covariates): lines of whitespace-separated columns, two ids and then the values -- PLINK's
+ *     --covar shape, and exactly what hpgv_run_pca writes as .eigenvec.  A first line whose first token is FID, #FID or #IID is a
+ *     header.  The SECOND id is matched byte for byte against the VCF's sample names; lines of other samples are ignored.
+ *   n_covar: the first n_covar value columns are used; 0 = all columns of the file.
+ *   A cohort sample (PED PHENO 2 or 1) with no line, or with a value among the used columns that is not a finite number ("NA",
+ *   "nan"), leaves the cohort: it becomes HPGV_COND_OTHER before hpgv_set_cohort.  *n_samples_used_out (may be NULL): the
+ *   cohort samples that stayed.  The covariates are set on every device's context.
+ * HPGV_ERR_INVALID before the engine is started, and no file written: a NULL path other than covar_path, n_covar < 0, n_covar > 0
+ * without a file, a file that cannot be read, a line with fewer than two ids, a ragged line, a second id that appears twice, more
+ * than HPGV_LOGISTIC_MAX_COVAR columns in use, n_covar above the file's columns.
+ * Same cohort, filters, record filters and input forms (plain, gzip, bgzip) as hpgv_run_assoc_model. */
+#define HPGV_RUN_LOGISTIC_MAX_ITER 25
+#define HPGV_RUN_LOGISTIC_TOL 1e-10
+int  hpgv_run_assoc_logistic(const char *vcf_path, const char *ped_path, const char *covar_path, int n_covar, const char *out_path,
+                             size_t batch_bytes, long *n_variants_out, long *n_samples_used_out);
+/* The covariate file's reader on its own: the first n_covar value columns (0: all) for the samples names[0 .. n_names), cov with
+ * HPGV_LOGISTIC_MAX_COVAR doubles per name, have[j] = 1 where names[j] has a line of finite values (else 0, and zeros in cov);
+ * *n_covar_out: the columns used.  HPGV_ERR_INVALID as above (message in hpgv_host_last_error).  No GPU call. */
+int  hpgv_host_covar_read(const char *covar_path, const char *const *names, int n_names, int n_covar, int *n_covar_out,
+                          double *cov, uint8_t *have);
 /* hpgv_run_assoc with LD clumping of its results (PLINK's --clump, without overlap and without replication): out_path is
  * written byte for byte as hpgv_run_assoc writes it, and <out_path>.clumped beside it, which groups the significant variants
  * into clumps, each around its strongest variant.
