@@ -33,6 +33,8 @@ MODEL_GENO, MODEL_TREND, MODEL_ALLELIC, MODEL_DOM, MODEL_REC = range(5)
 # the logistic regression's limits and row status (HPGV_LOGISTIC_MAX_COVAR, HPGV_LOGIT_* of include/hpgv.h)
 LOGISTIC_MAX_COVAR = 14
 LOGIT_OK, LOGIT_NOT_CONVERGED, LOGIT_SINGULAR = 0, 1, 2
+# the linear regression's row status (HPGV_LINEAR_* of include/hpgv.h)
+LINEAR_OK, LINEAR_SINGULAR, LINEAR_EXACT = 0, 1, 2
 LAYOUT_ASSOC, LAYOUT_TDT, LAYOUT_STATS, LAYOUT_STATS_GROUPS, LAYOUT_MENDEL, LAYOUT_EPI = 0, 1, 2, 3, 4, 5
 GT_MISSING = 0xFF
 # the tokenizer's tile records that hpgv_bgzf_verify_tiles_dev leaves (csrc/hpgv_text2_kernels.h: TOK2_TILE, struct TokAgg2 { TokAgg
@@ -71,6 +73,7 @@ SYMBOLS = [
     "hpgv_set_tdt_flips", "hpgv_tdt_perm_dev", "hpgv_tdt_perm", "hpgv_tdt_perm_text", "hpgv_perm_flips_shuffle",
     "hpgv_assoc_model_scan_dev", "hpgv_assoc_model_stats_dev", "hpgv_assoc_trend_perm_dev", "hpgv_assoc_model", "hpgv_assoc_model_text",
     "hpgv_set_covariates", "hpgv_assoc_logistic_dev", "hpgv_assoc_logistic", "hpgv_assoc_logistic_text", "hpgv_logistic_fit",
+    "hpgv_set_phenotype", "hpgv_assoc_linear_dev", "hpgv_assoc_linear", "hpgv_assoc_linear_text", "hpgv_linear_fit", "hpgv_linear_t_p",
     "hpgv_ld_window_dev", "hpgv_ld", "hpgv_ld_text", "hpgv_ld_r2",
     "hpgv_ld_edges_dev", "hpgv_ld_edges", "hpgv_clump",
     "hpgv_rows_gather_scratch_bytes", "hpgv_rows_gather_dev", "hpgv_assoc_select_text",
@@ -90,6 +93,9 @@ GRM_TAB = np.dtype([("hi", np.int8, 4), ("lo", np.int8, 4)])
 # hpgv_logistic_result: {double beta, se, stat, p; int32 n_obs, iters, status, pad}, 48 bytes
 LOGISTIC_RESULT = np.dtype([("beta", np.float64), ("se", np.float64), ("stat", np.float64), ("p", np.float64),
                             ("n_obs", np.int32), ("iters", np.int32), ("status", np.int32), ("pad", np.int32)])
+# hpgv_linear_result: {double beta, se, stat, p; int32 n_obs, df, status, pad}, 48 bytes
+LINEAR_RESULT = np.dtype([("beta", np.float64), ("se", np.float64), ("stat", np.float64), ("p", np.float64),
+                          ("n_obs", np.int32), ("df", np.int32), ("status", np.int32), ("pad", np.int32)])
 
 
 class HpgvError(RuntimeError):
@@ -257,6 +263,13 @@ def load():
     L.hpgv_assoc_logistic.argtypes = [vp, vp, sz, i32, i32, C.c_double, vp, vp]
     L.hpgv_assoc_logistic_text.argtypes = [vp, C.c_char_p, sz, i32, C.POINTER(i32), vp, vp, vp, i32, C.c_double, vp, vp]
     L.hpgv_logistic_fit.argtypes = [vp, vp, vp, i32, i32, i32, C.c_double, vp, vp]
+    L.hpgv_set_phenotype.argtypes = [vp, vp, i32]
+    L.hpgv_assoc_linear_dev.argtypes = [vp, vp, i32, vp, vp, vp]
+    L.hpgv_assoc_linear.argtypes = [vp, vp, sz, i32, vp, vp]
+    L.hpgv_assoc_linear_text.argtypes = [vp, C.c_char_p, sz, i32, C.POINTER(i32), vp, vp, vp, vp, vp]
+    L.hpgv_linear_fit.argtypes = [vp, vp, vp, i32, i32, vp, vp]
+    L.hpgv_linear_t_p.argtypes = [C.c_double, i32]
+    L.hpgv_linear_t_p.restype = C.c_double
     L.hpgv_ld_window_dev.argtypes = [vp, vp, sz, i32, i32, i32, vp, vp, C.c_int64, vp, vp, vp, vp]
     L.hpgv_ld.argtypes = [vp, vp, sz, i32, i32, vp, vp, C.c_int64, vp, vp]
     L.hpgv_ld_text.argtypes = [vp, C.c_char_p, sz, i32, C.POINTER(i32), vp, vp, vp, i32, vp, vp]
@@ -405,6 +418,47 @@ def logistic_fit(cls, y, cov=None, max_iter=25, tol=1e-10):
         e.code = rc
         raise e
     return out[0], coef
+
+
+def run_assoc_linear(vcf_path, ped_path, pheno_path, covar_path, out_path, n_covar=0, batch_bytes=1 << 22):
+    """hpgv_run_assoc_linear of libhpgv_host.so (include/hpgv_host.h): one linear regression per variant of the trait -- the first
+    value column of pheno_path, or the PED's sixth column without one -- with the first n_covar value columns of the covariate file
+    (0: all of them; covar_path None: no covariates) at out_path.  Paths may be None.  Returns (variants written, cohort samples
+    used)."""
+    _build.build_host_lib()
+    H = C.CDLL(_build.HOSTLIB)
+    H.hpgv_run_assoc_linear.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_long), C.POINTER(C.c_long)]
+    H.hpgv_host_last_error.restype = C.c_char_p
+    n, used = C.c_long(0), C.c_long(0)
+    enc = lambda q: None if q is None else os.fsencode(q)
+    rc = H.hpgv_run_assoc_linear(enc(vcf_path), enc(ped_path), enc(pheno_path), enc(covar_path), n_covar, enc(out_path), batch_bytes, C.byref(n), C.byref(used))
+    if rc != OK:
+        e = HpgvError("hpgv_run_assoc_linear -> %d: %s" % (rc, (H.hpgv_host_last_error() or b"").decode(errors="replace")))
+        e.code = rc
+        raise e
+    return n.value, used.value
+
+
+def linear_fit(cls, y, cov=None):
+    """hpgv_linear_fit: the linear regression of include/hpgv.h on the host, samples in index order.  cls: genotype classes (0, 1,
+    2; anything else missing), y: the trait, cov (n, C) or None.  Returns (a LINEAR_RESULT record, coef (2, p): beta then se).  No
+    device needed."""
+    c, yy = _np(cls, np.uint8), _np(y, np.float64)
+    cv = np.zeros((len(c), 0), np.float64) if cov is None else _np(cov, np.float64).reshape(len(c), -1)
+    nc = cv.shape[1]
+    out = np.zeros(1, LINEAR_RESULT)
+    coef = np.zeros((2, min(nc, LOGISTIC_MAX_COVAR) + 2), np.float64)
+    rc = load().hpgv_linear_fit(_ptr(c), _ptr(yy), _ptr(cv) if nc else None, len(c), nc, _ptr(out), _ptr(coef))
+    if rc != OK:
+        e = HpgvError("hpgv_linear_fit -> %d" % rc)
+        e.code = rc
+        raise e
+    return out[0], coef
+
+
+def linear_t_p(t, df):
+    """hpgv_linear_t_p: the two-sided tail of Student's t with df degrees of freedom.  No device needed."""
+    return float(load().hpgv_linear_t_p(float(t), int(df)))
 
 
 def run_genome(vcf_path, out_path, min_pi_hat=0.0, batch_bytes=1 << 22):
@@ -950,6 +1004,31 @@ class Engine:
                                                   int(max_iter), float(tol), _ptr(out), _ptr(cf)))
         return _text_result(nl, max_lines, status=status, out=out, coef=cf)
 
+    def set_phenotype(self, y):
+        """hpgv_set_phenotype: y (n_samples,) in VCF column order; None clears it."""
+        if y is None:
+            self._chk(self.L.hpgv_set_phenotype(self.h, None, 0))
+            return
+        yy = _np(y, np.float64)
+        self._chk(self.L.hpgv_set_phenotype(self.h, _ptr(yy), len(yy)))
+
+    def assoc_linear(self, gt, coef=False):
+        """hpgv_assoc_linear: a LINEAR_RESULT array (nv,) and, with coef, (nv, 2, p): beta then se of every coefficient."""
+        gt = _np(gt, np.uint8)
+        nv, pitch = gt.shape
+        out = np.zeros(nv, LINEAR_RESULT)
+        cf = np.zeros((nv, 2, getattr(self, "_n_covar", 0) + 2), np.float64) if coef else None
+        self._chk(self.L.hpgv_assoc_linear(self.h, _ptr(gt), pitch, nv, _ptr(out), _ptr(cf)))
+        return (out, cf) if coef else out
+
+    def assoc_linear_text(self, text, max_lines=None, coef=False):
+        """hpgv_assoc_linear_text: assoc_linear on VCF data lines, the outputs per line."""
+        text, max_lines, m, status, nl = _text_call(text, max_lines)
+        out = np.zeros(m, LINEAR_RESULT)
+        cf = np.zeros((m, 2, getattr(self, "_n_covar", 0) + 2), np.float64) if coef else None
+        self._chk(self.L.hpgv_assoc_linear_text(self.h, text, len(text), max_lines, C.byref(nl), None, None, _ptr(status), _ptr(out), _ptr(cf)))
+        return _text_result(nl, max_lines, status=status, out=out, coef=cf)
+
     def ld(self, gt, window, chrom=None, pos=None, max_bp=-1, counts=True):
         """hpgv_ld: r2 (nv, window) and, with counts, counts6 (nv, window, 6); element [b, d - 1] is the pair (b - d, b) over the
         cohort columns.  chrom / pos (per row, both or neither) and max_bp bound the band."""
@@ -1326,6 +1405,9 @@ class Engine:
 
     def assoc_logistic_dev(self, d_gt, n_variants, d_out, d_coef=None, max_iter=25, tol=1e-10, stream=None):
         self._chk(self.L.hpgv_assoc_logistic_dev(self.h, d_gt, n_variants, int(max_iter), float(tol), d_out, d_coef, stream))
+
+    def assoc_linear_dev(self, d_gt, n_variants, d_out, d_coef=None, stream=None):
+        self._chk(self.L.hpgv_assoc_linear_dev(self.h, d_gt, n_variants, d_out, d_coef, stream))
 
     def ld_window_dev(self, d_gt, pitch, n_variants, window, d_r2, d_counts6=None, b_begin=0, d_chrom=None, d_pos=None, max_bp=-1,
                       d_skip=None, stream=None):

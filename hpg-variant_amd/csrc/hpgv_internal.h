@@ -2,7 +2,7 @@
 // libhpgv.so: hpgv_capi.hip (contexts, options, cohorts, memory, streams, text aliases), hpgv_scan_capi.hip (the
 // device-resident *_dev launchers), hpgv_text_capi.hip (tokenizer, the text entry points' front half),
 // hpgv_tool_capi.hip (per-batch and text entry points), hpgv_lines_capi.hip (partition / multisplit of lines), and the
-// units whose kernel instantiations compile on their own (hpgv_perm_capi.hip, hpgv_ld_capi.hip, hpgv_ibs_capi.hip, hpgv_grm_capi.hip, hpgv_pca_capi.hip, hpgv_logistic_capi.hip, hpgv_epi_capi.hip, hpgv_epi_generic_capi.hip, hpgv_statsall_capi.hip, hpgv_inflate_capi.hip, hpgv_group_capi.hip).
+// units whose kernel instantiations compile on their own (hpgv_perm_capi.hip, hpgv_ld_capi.hip, hpgv_ibs_capi.hip, hpgv_grm_capi.hip, hpgv_pca_capi.hip, hpgv_logistic_capi.hip, hpgv_linear_capi.hip, hpgv_epi_capi.hip, hpgv_epi_generic_capi.hip, hpgv_statsall_capi.hip, hpgv_inflate_capi.hip, hpgv_group_capi.hip).
 // A synchronous entry point has two halves that meet in a Staged: the front puts the call's matrix on the device -- text_front /
 // text_front_skip for a text, stage_chain for a host batch that goes through the kernel chain -- and the tool's back half takes it
 // from there; the permutation calls build theirs from the halves of hpgv_assoc's and hpgv_tdt's (assoc_chain, ..., below).
@@ -247,6 +247,11 @@ struct hpgv_ctx {
     // column order, zeros under the pads; dropped by a new cohort
     DevBuf d_cov;
     int n_covar = 0;
+    // the linear regression's model (hpgv_set_phenotype): the trait per VCF column and a host copy of the covariates, kept so that
+    // either set call can rebuild the device image d_lin (hpgv_linear_kernels.h "LinArgs"); dropped by a new cohort
+    std::vector<double> lin_y, lin_cov;
+    bool has_pheno = false;
+    DevBuf d_lin;
     // tdt
     Layout tdt;
     hpgv::TdtPlan tdt_plan;
@@ -472,6 +477,9 @@ hpgv_ctx *alias_owner(hpgv_ctx *group, const char *host_text);    // the member 
 long hpgv_batch_lds_optin(const hipDeviceProp_t &prop, long fallback);
 // defined in hpgv_text_capi.hip: the shared front half of the *_text entry points (and of hpgv_filter_text): text -> device,
 // tokenize, record filters, lay out
+// hpgv_linear_capi.hip: the linear model's device image from ctx->lin_y and ctx->lin_cov (a no-op without a phenotype)
+int linear_image_rebuild(hpgv_ctx *ctx);
+
 int text_front(hpgv_ctx *ctx, Slot *s, int which, const Layout &L, const char *text, size_t text_bytes, int max_lines, int *n_lines,
                uint64_t *line_off, uint32_t *field_off, int32_t *status, Staged *S, bool final_layout = true);
 // defined in hpgv_tool_capi.hip: its twin for a host batch that goes through the kernel chain -- rows, then is_x, copied to the slot,

@@ -70,7 +70,7 @@ int hpgv_set_covariates(hpgv_ctx *ctx, const double *cov, int n_samples, int n_c
     if (!ctx) return HPGV_ERR_INVALID;
     if (!ctx->assoc.set) return fail(ctx, HPGV_ERR_STATE, "hpgv_set_cohort has not been called");
     if (n_covar < 0 || (n_covar > 0 && !cov)) return fail(ctx, HPGV_ERR_INVALID, "bad covariates arguments");
-    if (n_covar == 0) { ctx->n_covar = 0; return HPGV_OK; }
+    if (n_covar == 0) { ctx->n_covar = 0; ctx->lin_cov.clear(); return linear_image_rebuild(ctx); }
     const Layout &L = ctx->assoc;
     if (n_samples != L.n_samples) return fail(ctx, HPGV_ERR_INVALID, "covariates for %d samples: the cohort has %d columns", n_samples, L.n_samples);
     if (n_covar > HPGV_LOGISTIC_MAX_COVAR) return fail(ctx, HPGV_ERR_UNSUPPORTED, "%d covariates: at most %d", n_covar, (int)HPGV_LOGISTIC_MAX_COVAR);
@@ -93,7 +93,8 @@ int hpgv_set_covariates(hpgv_ctx *ctx, const double *cov, int n_samples, int n_c
     }
     HIPCHK(ctx, hipMemcpy(ctx->d_cov.p, laid.data(), laid.size() * sizeof(double), hipMemcpyHostToDevice));
     ctx->n_covar = n_covar;
-    return HPGV_OK;
+    ctx->lin_cov.assign(cov, cov + (size_t)n_samples * (size_t)n_covar);      // the linear model's image follows the covariates
+    return linear_image_rebuild(ctx);
     HPGV_ABI_CATCH(ctx)
 }
 

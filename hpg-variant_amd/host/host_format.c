@@ -34,7 +34,7 @@ static int run_batch_lines(run_batch_t *b) {
     b->status = (int32_t *)malloc(sizeof(int32_t) * (size_t)b->max_lines);
     const int model = tool_model(b->run->tool);
     b->ints = (int32_t *)malloc(sizeof(int32_t) * (model ? 8 : 4) * (size_t)b->max_lines);
-    b->dbl = (double *)malloc(sizeof(double) * (model ? 10 : b->run->tool == RUN_LOGISTIC ? 6 : 3) * (size_t)b->max_lines);
+    b->dbl = (double *)malloc(sizeof(double) * (model ? 10 : b->run->tool == RUN_LOGISTIC || b->run->tool == RUN_LINEAR ? 6 : 3) * (size_t)b->max_lines);
     if (b->row_width > 0) {
         free(b->rows);
         b->rows_cap = (size_t)b->max_lines * (size_t)b->row_width;
@@ -164,6 +164,15 @@ static int format_record(char *dst, size_t room, const run_batch_t *b, int i) {
         p = put_i64(p, r->n_obs);
         for (int t = 0; t < 5; t++) { *p++ = '\t'; p = five[t] != five[t] ? PUT_STR(p, "nan", 3) : PUT_F6(p, five[t]); }
         *p++ = '\t'; p = put_i64(p, r->iters);
+        *p++ = '\n'; *p = 0;
+        return (int)(p - dst);
+    }
+    if (tool == RUN_LINEAR) {                             /* CHR POS ID A1 A2 NOBS BETA SE STAT P; a singular fit: nan in the four, an exact one: BETA, SE 0, nan, nan */
+        const hpgv_linear_result *r = (const hpgv_linear_result *)b->dbl + i;
+        const double four[4] = { r->beta, r->se, r->stat, r->p };
+        p = PUT_STR(p, l + fo[4], la); *p++ = '\t';
+        p = put_i64(p, r->n_obs);
+        for (int t = 0; t < 4; t++) { *p++ = '\t'; p = four[t] != four[t] ? PUT_STR(p, "nan", 3) : PUT_F6(p, four[t]); }
         *p++ = '\n'; *p = 0;
         return (int)(p - dst);
     }

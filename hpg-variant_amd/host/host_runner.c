@@ -1,5 +1,5 @@
 /* host_runner.c -- the file runners: reader -> engine threads -> writer (hpgv_run_assoc / tdt / aggregate / stats / vcf2epi /
- * filter / split / genome / grm / logistic).  The VCF tools' own batch steps and writers are in host_vcftools.c, what a run keeps beside its result file in
+ * filter / split / genome / grm / logistic / linear).  The VCF tools' own batch steps and writers are in host_vcftools.c, what a run keeps beside its result file in
  * host_sideout.c.
  * Part of libhpgv_host.so (see hpgv_host_internal.h for the map of its units). */
 #include "hpgv_host_internal.h"
@@ -126,6 +126,8 @@ static int engine_call(run_t *R, run_batch_t *b, const char **what, int *again) 
     case RUN_LOGISTIC: *what = "hpgv_assoc_logistic_text";
         return hpgv_assoc_logistic_text(g_ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status,
                                         HPGV_RUN_LOGISTIC_MAX_ITER, HPGV_RUN_LOGISTIC_TOL, (hpgv_logistic_result *)b->dbl, NULL);
+    case RUN_LINEAR: *what = "hpgv_assoc_linear_text";
+        return hpgv_assoc_linear_text(g_ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status, (hpgv_linear_result *)b->dbl, NULL);
     case RUN_GENOME: { *what = "hpgv_ibs_text";            /* on one device of the run, into that device's counts (a batch with more lines than room adds nothing) */
         hpgv_ibs_counts *d_counts = NULL;
         hpgv_ctx *ctx = run_genome_device(R, b, &d_counts);
@@ -355,6 +357,38 @@ static int run_cohort(run_t *R, const char *vcf_path, const char *ped_path) {
         }
         break;
     }
+    case RUN_LINEAR: {                                    /* the cohort: every sample with a trait and, with covariates, a line of finite ones */
+        uint8_t *cond = (uint8_t *)malloc((size_t)n_samples + 1), *have = (uint8_t *)malloc((size_t)n_samples + 1);
+        double *y = (double *)calloc((size_t)n_samples + 1, sizeof(double)), *cov = NULL;
+        if (!cond || !have || !y) rc = HPGV_ERR_NOMEM;
+        for (int j = 0; !rc && j < n_samples; j++) cond[j] = HPGV_COND_OTHER;
+        if (!rc && R->pheno) {                            /* the phenotype file's first value column */
+            rc = covar_table_match(R->pheno, R->names, n_samples, 1, y, 1, have);
+            for (int j = 0; !rc && j < n_samples; j++) if (have[j]) cond[j] = HPGV_COND_UNAFFECTED;
+        } else if (!rc) {                                 /* the PED's sixth column as a number: not finite, or -9, is missing */
+            for (int i = 0; i < ped->n; i++) {
+                const int j = sample_ids_get(ids, ped->iid[i]);
+                if (j < 0) continue;
+                char *end;
+                const double v = strtod(ped->phe[i], &end);
+                if (end == ped->phe[i] || *end != 0 || !isfinite(v) || v == -9.0) continue;
+                cond[j] = HPGV_COND_UNAFFECTED; y[j] = v;
+            }
+        }
+        if (!rc && R->covar) {
+            cov = (double *)malloc(sizeof(double) * ((size_t)n_samples * (size_t)R->n_covar + 1));
+            if (!cov) rc = HPGV_ERR_NOMEM;
+            if (!rc) rc = covar_table_match(R->covar, R->names, n_samples, R->n_covar, cov, (size_t)R->n_covar, have);
+            for (int j = 0; !rc && j < n_samples; j++) if (!have[j]) cond[j] = HPGV_COND_OTHER;
+        }
+        for (int j = 0; !rc && j < n_samples; j++) R->n_used += cond[j] == HPGV_COND_UNAFFECTED;
+        if (!rc && (rc = hpgv_set_cohort(g_ctx, cond, n_samples))) host_fail("hpgv_set_cohort", rc);
+        g_assoc_key.set = 0;
+        if (!rc && cov && R->n_covar > 0 && (rc = hpgv_set_covariates(g_ctx, cov, n_samples, R->n_covar))) host_fail("hpgv_set_covariates", rc);
+        if (!rc && (rc = hpgv_set_phenotype(g_ctx, y, n_samples))) host_fail("hpgv_set_phenotype", rc);
+        free(cond); free(have); free(y); free(cov);
+        break;
+    }
     }
     /* device-side record filters: the count filters scan the stats layout of all columns, the Mendelian filter the trios */
     const hpgv_run_filters_t *f = &R->filters;
@@ -368,7 +402,7 @@ static int run_cohort(run_t *R, const char *vcf_path, const char *ped_path) {
     /* --inh-dom / --inh-rec scan the assoc layout: the tools that have not installed it get it from the PED (PHENO 2
      * affected, 1 unaffected, as the assoc runner); vcf2epi keeps its own classes */
     if (!rc && rec_filters_inheritance(R->rf)) {
-        if (!tool_chisq(R->tool) && !tool_model(R->tool) && R->tool != RUN_FISHER && R->tool != RUN_VCF2EPI && R->tool != RUN_LOGISTIC) {
+        if (!tool_chisq(R->tool) && !tool_model(R->tool) && R->tool != RUN_FISHER && R->tool != RUN_VCF2EPI && R->tool != RUN_LOGISTIC && R->tool != RUN_LINEAR) {
             int matched = 0;
             uint8_t *cond = cohort_conditions(R, ids, &matched);
             if (!cond) rc = HPGV_ERR_NOMEM;
@@ -434,6 +468,12 @@ static int run_headers(run_t *R) {
     }
     case RUN_LOGISTIC: {
         const char *h = "#CHR\tPOS\tID\tA1\tA2\tNOBS\tBETA\tSE\tOR\tSTAT\tP\tITER";
+        fprintf(out, "%s\n", h);
+        order_track_keep(&R->ord, h, strlen(h));
+        return HPGV_OK;
+    }
+    case RUN_LINEAR: {
+        const char *h = "#CHR\tPOS\tID\tA1\tA2\tNOBS\tBETA\tSE\tSTAT\tP";
         fprintf(out, "%s\n", h);
         order_track_keep(&R->ord, h, strlen(h));
         return HPGV_OK;
@@ -540,7 +580,7 @@ static int run_pipeline(run_t *R, size_t batch_bytes) {
                 R->written += b->n_pass; R->skipped += b->n_skip;
                 break;
             case RUN_CHISQ: case RUN_CHISQ_PERM: case RUN_FISHER: case RUN_TDT: case RUN_TDT_PERM: case RUN_VCF2EPI: case RUN_AGGREGATE: case RUN_STATS:
-            case RUN_MODEL: case RUN_MODEL_PERM: case RUN_LOGISTIC:
+            case RUN_MODEL: case RUN_MODEL_PERM: case RUN_LOGISTIC: case RUN_LINEAR:
                 if (write_batch(R->out, b, fmt + (fmt_set ? RUN_FMT_BUFS / 2 : 0), n_fmt, &wpool, &R->ord, use_fw ? &fw : NULL)) bad = "cannot write the result file";
                 for (int i = 0; i < b->n_lines; i++) if (record_passes(b, i)) R->written++;
                 if (tool_perm(R->tool) && !bad && run_perm_add(R, b)) bad = "out of memory for the permutation results";
@@ -606,7 +646,8 @@ static int run_finish(run_t *R, int rc, const char *out_path) {
         if (g_ctx) (void)(R->tool == RUN_TDT_PERM ? hpgv_set_tdt_flips(g_ctx, NULL, 0) : hpgv_set_perm_labels(g_ctx, NULL, 0));
         run_perm_free(R);
     }
-    if (R->tool == RUN_LOGISTIC && g_ctx) (void)hpgv_set_covariates(g_ctx, NULL, 0, 0);
+    if ((R->tool == RUN_LOGISTIC || R->tool == RUN_LINEAR) && g_ctx) (void)hpgv_set_covariates(g_ctx, NULL, 0, 0);
+    if (R->tool == RUN_LINEAR && g_ctx) (void)hpgv_set_phenotype(g_ctx, NULL, 0);
     if (R->CL) {
         if (!rc) rc = run_clump_write(R, out_path);
         R->n_clumps = R->CL->n_clumps; R->n_truncated = R->CL->n_truncated;      /* for hpgv_run_assoc_clump, past the store */
@@ -792,6 +833,28 @@ int hpgv_run_assoc_logistic(const char *vcf_path, const char *ped_path, const ch
     const int rc = run_file(&R, vcf_path, ped_path, out_path, batch_bytes, n_variants_out);
     if (n_samples_used_out && !rc) *n_samples_used_out = R.n_used;
     covar_table_free(&T);
+    return rc;
+}
+
+/* the linear regression's run: the phenotype and covariate files read and checked before the engine starts, then RUN_LOGISTIC's
+ * pipeline with hpgv_assoc_linear_text as its engine call */
+int hpgv_run_assoc_linear(const char *vcf_path, const char *ped_path, const char *pheno_path, const char *covar_path, int n_covar,
+                          const char *out_path, size_t batch_bytes, long *n_variants_out, long *n_samples_used_out) {
+    if (n_samples_used_out) *n_samples_used_out = 0;
+    if (run_args(n_variants_out, vcf_path && out_path, "vcf_path and out_path must not be NULL")) return HPGV_ERR_INVALID;
+    if (!ped_path && !pheno_path) { snprintf(g_err, sizeof g_err, "the trait needs a PED file or a phenotype file (ped_path and pheno_path are NULL)"); return HPGV_ERR_INVALID; }
+    if (n_covar < 0 || (n_covar > 0 && !covar_path)) { snprintf(g_err, sizeof g_err, "n_covar %d: not negative, and 0 without a covariate file", n_covar); return HPGV_ERR_INVALID; }
+    covar_table_t T, P;
+    memset(&T, 0, sizeof T); memset(&P, 0, sizeof P);
+    int use = 0, rc = HPGV_OK;
+    if (pheno_path && !(rc = covar_table_read(pheno_path, &P)) && covar_table_columns(&P, 1) < 0) rc = HPGV_ERR_INVALID;
+    if (!rc && covar_path && !(rc = covar_table_read(covar_path, &T)) && (use = covar_table_columns(&T, n_covar)) < 0) rc = HPGV_ERR_INVALID;
+    if (!rc) {
+        run_t R = { .tool = RUN_LINEAR, .filters = g_filters, .covar = covar_path ? &T : NULL, .n_covar = use, .pheno = pheno_path ? &P : NULL };
+        rc = run_file(&R, vcf_path, ped_path, out_path, batch_bytes, n_variants_out);
+        if (n_samples_used_out && !rc) *n_samples_used_out = R.n_used;
+    }
+    covar_table_free(&T); covar_table_free(&P);
     return rc;
 }
 

@@ -19,7 +19,7 @@
  *   host_vcftools.c    the VCF tools' batch steps and writers: filter partition, split keys and files
  *   host_records.c     the record filters of hpgv_run_set_record_filters: regions, coverage, variant types, inheritance
  *   host_sideout.c     what a run keeps beside its result file and writes at its end: .mperm, .clumped, the stats report
- *   host_covar.c       the covariate file of the logistic run: read whole, matched to the VCF's sample names
+ *   host_covar.c       the covariate file of the logistic and linear runs (and the latter's phenotype file): read whole, matched to the VCF's sample names
  *   host_pca.c         the principal components of a run's relationship matrix, or of .grm.bin files: .eigenval, .eigenvec
  *   host_runner.c      the file runners' pipeline and their runs (hpgv_run_*)
  */
@@ -147,14 +147,15 @@ typedef struct {
  * RUN_MODEL / RUN_MODEL_PERM: the model tests (hpgv_run_assoc_model) without and with <out>.mperm of the trend statistic;
  * RUN_GENOME: sample relatedness (hpgv_run_genome): no line per record, one file of sample pairs written when the run ends;
  * RUN_GRM: the genetic relationship matrix (hpgv_run_grm): no line per record, three files written when the run ends;
- * RUN_LOGISTIC: the logistic regression with covariates (hpgv_run_assoc_logistic) */
+ * RUN_LOGISTIC: the logistic regression with covariates (hpgv_run_assoc_logistic);
+ * RUN_LINEAR: the linear regression of a quantitative trait with covariates (hpgv_run_assoc_linear) */
 typedef enum { RUN_CHISQ = CHI_SQUARE, RUN_FISHER = FISHER, RUN_TDT, RUN_VCF2EPI, RUN_AGGREGATE, RUN_STATS, RUN_FILTER, RUN_SPLIT, RUN_CHISQ_PERM, RUN_TDT_PERM,
-               RUN_MODEL, RUN_MODEL_PERM, RUN_GENOME, RUN_GRM, RUN_LOGISTIC } run_tool_t;
+               RUN_MODEL, RUN_MODEL_PERM, RUN_GENOME, RUN_GRM, RUN_LOGISTIC, RUN_LINEAR } run_tool_t;
 static inline int tool_chisq(run_tool_t t) { return t == RUN_CHISQ || t == RUN_CHISQ_PERM; }   /* writes the chi-square file */
 static inline int tool_tdt(run_tool_t t) { return t == RUN_TDT || t == RUN_TDT_PERM; }         /* writes the TDT file */
 static inline int tool_model(run_tool_t t) { return t == RUN_MODEL || t == RUN_MODEL_PERM; }   /* writes the model tests' file */
 static inline int tool_perm(run_tool_t t) { return t == RUN_CHISQ_PERM || t == RUN_TDT_PERM || t == RUN_MODEL_PERM; } /* writes <out>.mperm beside its file */
-static inline int tool_sorts(run_tool_t t) { return tool_chisq(t) || t == RUN_FISHER || tool_tdt(t) || tool_model(t) || t == RUN_LOGISTIC; }   /* output sorted afterwards */
+static inline int tool_sorts(run_tool_t t) { return tool_chisq(t) || t == RUN_FISHER || tool_tdt(t) || tool_model(t) || t == RUN_LOGISTIC || t == RUN_LINEAR; }   /* output sorted afterwards */
 static inline int tool_counts(run_tool_t t) { return t == RUN_AGGREGATE || t == RUN_STATS; }   /* engine: hpgv_stats_text_groups */
 
 typedef struct {
@@ -167,7 +168,7 @@ typedef struct {
     uint64_t *line_off; uint32_t *field_off; int32_t *status;
     int32_t *ints; double *dbl;                          /* 4 (assoc) or 2 (tdt) int arrays, 3 double arrays; the model tests: counts8 per line, then
                                                           * chisq5 per line and, from dbl + 5 * max_lines, p5 per line; genome and grm: class4 per line in ints;
-                                                          * logistic: one hpgv_logistic_result (six doubles' room) per line in dbl */
+                                                          * logistic, linear: one hpgv_logistic_result / hpgv_linear_result (six doubles' room) per line in dbl */
     int32_t *n_ge; double *bmax;                         /* the permutation tools: permutations at or above the observed statistic per line; the batch's maximum per permutation */
     uint8_t *rows; size_t rows_cap; int row_width;       /* vcf2epi: one dataset row per line */
     int stats;                                           /* aggregate / stats: the counters of hpgv_stats_text */
@@ -275,7 +276,8 @@ typedef struct run {
     double min_pi_hat; run_genome_t *GN; long n_pairs;   /* RUN_GENOME: the threshold, the run's counts, the pairs written (kept past them) */
     double min_maf; int frac_bits;                       /* RUN_GRM: the rows' rule and hpgv_grm_frac_bits of it; its sums lie in GN's buffers (16-byte records too) */
     int n_pcs, write_grm, n_iter;                        /* RUN_GRM with n_pcs >= 1 (hpgv_run_pca): pairs to write, the .grm.* files too, the sweeps done (kept past the run) */
-    const covar_table_t *covar; int n_covar; long n_used; /* RUN_LOGISTIC: the covariate file (NULL: none) and its columns in use; the cohort samples that stayed */
+    const covar_table_t *covar; int n_covar; long n_used; /* RUN_LOGISTIC, RUN_LINEAR: the covariate file (NULL: none) and its columns in use; the cohort samples that stayed */
+    const covar_table_t *pheno;                          /* RUN_LINEAR: the phenotype file (NULL: the PED's sixth column) */
     double t_opened, t_header, t_sort;
 } run_t;
 

@@ -377,6 +377,73 @@ int  hpgv_assoc_logistic_text(hpgv_ctx *ctx, const char *text, size_t text_bytes
 int  hpgv_logistic_fit(const uint8_t *cls, const uint8_t *y, const double *cov, int n, int n_covar, int max_iter, double tol,
                        hpgv_logistic_result *out, double *coef /* may be NULL */);
 
+/* ---- Linear regression: the association test of a quantitative trait with covariates (PLINK's --linear --covar; no reference
+ *      counterpart, and parity with PLINK is unpinned: this block is the specification).  One ordinary least squares fit per
+ *      variant, of the trait y on the ALT allele count and up to HPGV_LOGISTIC_MAX_COVAR covariates per sample.
+ *
+ *      Observations of a row v, the byte rule and the class d in {0, 1, 2}: those of "Logistic regression" above.  Both segments
+ *      of the assoc layout are cohort columns (the condition only places a column); pads are never observations; chromosome X
+ *      gets no special rule.  y is a finite double per cohort column (hpgv_set_phenotype).
+ *
+ *      Design row x = [1, d, c_1 .. c_C], p = C + 2.  Everything f64:
+ *          beta = (X^T X)^-1 X^T y,   RSS = y^T y - |L^-1 X^T y|^2 with X^T X = L L^T,   df = n_obs - p,   sigma^2 = RSS / df,
+ *          se_i = sqrt(sigma^2 V_ii) with V = (X^T X)^-1,   stat = beta_1 / se_1 (a signed t statistic),
+ *          p = the two-sided Student-t tail with df degrees of freedom (hpgv_linear_t_p).
+ *
+ *      Moments by class sums -- the device kernel and the host fit use the same identity.  f_s = [1, c_1 - m_1, .., c_C - m_C,
+ *      y - m_y] is the feature row of cohort column s (q = C + 2 entries); the means m and G = sum_cohort f f^T are taken over
+ *      the cohort columns in layout order (the host fit: index order) once per set call, one fma per term.  For a row:
+ *          h = sum_obs d_s f_s (the dense product),   n_1, n_2 the class counts,   n_miss, n_obs
+ *          dd = n_1 + 4 n_2,   sum_obs d = n_1 + 2 n_2 (both exact, from the integers)
+ *          S = G - sum_missing f f^T  when n_miss <= n_obs,   S = sum_obs f f^T  otherwise
+ *      either sum over its positions in ascending order, one fma per term.  The normal equations in the order [1, d, c ..] are
+ *      read off S, h and dd; y^T y = S[y][y]; X^T y is the y column of S and h[y] for d.  Cholesky and inverse as in the logistic
+ *      fit (same function, same pivot rule).  The centring is internal; the reported intercept is transformed back:
+ *          beta_0 = beta'_0 + m_y - sum_k beta_k m_k,   se_0 = sqrt(sigma^2 a^T V a) with a = (1, 0, -m_1, .., -m_C).
+ *
+ *      Status per row:
+ *          HPGV_LINEAR_OK
+ *          HPGV_LINEAR_SINGULAR  the pivot rule fired or df < 1: all-missing and monomorphic rows, d collinear with a covariate,
+ *                                n_obs <= p.  All doubles are NaN.
+ *          HPGV_LINEAR_EXACT     RSS <= 1e-12 S[y][y]: a perfect fit.  beta is written, se = 0, stat and p are NaN.
+ *      n_obs and df are always written. */
+enum { HPGV_LINEAR_OK = 0, HPGV_LINEAR_SINGULAR = 1, HPGV_LINEAR_EXACT = 2 };
+/* 48 bytes; arrays of it are 16-byte aligned.  beta, se: of the genotype coefficient (index 1) */
+typedef struct { double beta, se, stat, p; int32_t n_obs, df, status, pad; } hpgv_linear_result;
+/* y[j]: the trait of VCF column j, the indexing of hpgv_set_cohort's condition[].  After hpgv_set_cohort (else HPGV_ERR_STATE);
+ * n_samples must be the cohort's (else HPGV_ERR_INVALID); a non-finite value in a cohort column is HPGV_ERR_INVALID (columns
+ * with HPGV_COND_OTHER may hold anything).  y == NULL clears the phenotype; so does a new hpgv_set_cohort.  A group context
+ * gives every member the phenotype.  This call and hpgv_set_covariates each rebuild the linear model's device image while a
+ * phenotype is set: the centred features, sample-major, 16 doubles per layout position (zeros under pads and in unused
+ * columns), then G and the means.  Not to be called while linear calls of the context are in flight. */
+int  hpgv_set_phenotype(hpgv_ctx *ctx, const double *y, int n_samples);
+/* d_gt in assoc layout (16-byte aligned) -> d_out[v] (16-byte aligned) and, unless NULL, d_coef (8-byte aligned):
+ * n_variants x 2p doubles, beta_0 .. beta_{p-1} then se_0 .. se_{p-1} (NaN when SINGULAR; se 0 when EXACT).  One launch,
+ * asynchronous on `stream`: a workgroup of four waves owns 16 rows, h is their product with the feature image on
+ * v_mfma_f64_16x16x4_f64 (the waves take the positions in a fixed pattern and are added in wave order), the counts are
+ * integers, the correction of S walks a row's flagged positions in ascending order, no floating-point atomics.  A row's record
+ * depends on that row only: a matrix passed in one call or in pieces gives bit-identical records, and so do two runs.
+ * HPGV_ERR_STATE without a cohort or without a phenotype; HPGV_ERR_INVALID for n_variants < 0, a NULL or misaligned pointer. */
+int  hpgv_assoc_linear_dev(hpgv_ctx *ctx, const uint8_t *d_gt, int n_variants, hpgv_linear_result *d_out,
+                           double *d_coef /* may be NULL */, void *stream);
+/* The same on a host batch in VCF column order and on a text, built as hpgv_assoc_logistic and hpgv_assoc_logistic_text are.
+ * Synchronous and thread-safe; a group context deals the call to a member. */
+int  hpgv_assoc_linear(hpgv_ctx *ctx, const uint8_t *gt, size_t pitch, int n_variants, hpgv_linear_result *out,
+                       double *coef /* may be NULL */);
+int  hpgv_assoc_linear_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, int max_lines, int *n_lines,
+                            uint64_t *line_off, uint32_t *field_off, int32_t *status, hpgv_linear_result *out,
+                            double *coef /* may be NULL */);
+/* The definition on the host, samples in index order (every one of the n samples is a cohort column): cls[i] in {0, 1, 2} or
+ * anything else for missing, y[i], cov[i * n_covar + k].  coef (may be NULL): 2p doubles.  No GPU call, no context.
+ * HPGV_ERR_INVALID for n < 0, n_covar outside 0 .. HPGV_LOGISTIC_MAX_COVAR, a NULL pointer it needs, a y or covariate that is
+ * not finite. */
+int  hpgv_linear_fit(const uint8_t *cls, const double *y, const double *cov, int n, int n_covar, hpgv_linear_result *out,
+                     double *coef /* may be NULL */);
+/* The two-sided tail of Student's t with df degrees of freedom at t: I_x(df / 2, 1 / 2) with x = df / (df + t^2), the
+ * regularised incomplete beta function by its continued fraction (through the complement 1 - I_{1 - x}(1 / 2, df / 2) where x
+ * is large).  NaN for a NaN t or df < 1.  The function the kernel compiles too. */
+double hpgv_linear_t_p(double t, int df);
+
 /* d_gt in tdt layout -> d_tu[v] = {t1, t2} (int32 x2) */
 int  hpgv_tdt_scan_dev(hpgv_ctx *ctx, const uint8_t *d_gt, int n_variants,
                        const uint8_t *d_is_x, int32_t *d_tu, void *stream);

@@ -341,6 +341,29 @@ int  hpgv_run_assoc_model(const char *vcf_path, const char *ped_path, const char
 #define HPGV_RUN_LOGISTIC_TOL 1e-10
 int  hpgv_run_assoc_logistic(const char *vcf_path, const char *ped_path, const char *covar_path, int n_covar, const char *out_path,
                              size_t batch_bytes, long *n_variants_out, long *n_samples_used_out);
+/* The association test of a quantitative trait with covariates (include/hpgv.h "Linear regression"; PLINK's --linear --covar,
+ * parity unpinned): one ordinary least squares fit per variant of the trait on the ALT allele count and the covariates.  out_path
+ * gets the header line
+ *     #CHR POS ID A1 A2 NOBS BETA SE STAT P
+ * and one line per written variant, tab-separated, sorted and formatted as hpgv_run_assoc_logistic's file; the tested allele is
+ * ALT.  NOBS: n_obs of the row's hpgv_linear_result; BETA, SE, STAT (a signed t statistic), P of the genotype coefficient.  A
+ * row with status HPGV_LINEAR_SINGULAR prints nan in the four, one with HPGV_LINEAR_EXACT its BETA, SE 0 and nan for STAT and P.
+ * Every batch goes through hpgv_assoc_linear_text; a row's result depends on that row only, so the file does not depend on
+ * batch_bytes, engine threads, input form or devices.
+ *   pheno_path (PLINK's --pheno; may be NULL): a file of the covariate file's shape, whose first value column is the trait;
+ *     ped_path may then be NULL.  Without it the trait is the PED's sixth column read as a number: a value that is not a
+ *     finite number, or equals -9, is missing.
+ *   covar_path, n_covar: as for hpgv_run_assoc_logistic.
+ *   A sample enters the cohort (as HPGV_COND_UNAFFECTED: the condition only places a column) when it has a trait and, if
+ *   covariates are used, a line of finite covariates; everyone else is HPGV_COND_OTHER.  *n_samples_used_out (may be NULL): the
+ *   cohort's size.  The trait and the covariates are set on every device's context.  The inheritance record filters see no
+ *   affected sample in this run.
+ * HPGV_ERR_INVALID before the engine is started, and no file written: what hpgv_run_assoc_logistic refuses (ped_path may be NULL
+ * here when pheno_path is not), both ped_path and pheno_path NULL, a phenotype file that cannot be read, is malformed as a
+ * covariate file can be, or has no value column.
+ * Same filters, record filters and input forms (plain, gzip, bgzip) as hpgv_run_assoc_logistic. */
+int  hpgv_run_assoc_linear(const char *vcf_path, const char *ped_path, const char *pheno_path, const char *covar_path, int n_covar,
+                           const char *out_path, size_t batch_bytes, long *n_variants_out, long *n_samples_used_out);
 /* The covariate file's reader on its own: the first n_covar value columns (0: all) for the samples names[0 .. n_names), cov with
  * HPGV_LOGISTIC_MAX_COVAR doubles per name, have[j] = 1 where names[j] has a line of finite values (else 0, and zeros in cov);
  * *n_covar_out: the columns used.  HPGV_ERR_INVALID as above (message in hpgv_host_last_error).  No GPU call. */
