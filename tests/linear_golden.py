@@ -28,7 +28,8 @@ LD = np.longdouble
 # coefficient, class_sum_fit in both directions against ref_fit.  Measured on the CPU by measure_E() (tests/test_linear_cpu.py
 # asserts that the constant still covers it):
 #   measured 2.7e-13 (5 .. 511 cohort samples, C = 0 .. 14, 67 random and 7 or 8 named rows per case, one case with a trait of mean 1000 and
-#   sd 10)
+#   sd 10; measured again with the four cases of COVARS_DEAL, C = 8 and 9 at 199 and 511 cohort samples: they reach 3.4e-14 by themselves,
+#   the maximum stays where it was)
 E = 2.7e-13
 # what a host or device result may differ by, in the same units
 DEVICE_TOL = max(64 * E, 1e-12)
@@ -290,7 +291,14 @@ def case_id(k):
     return "%dx%d_C%d_%s" % k
 
 
-CASES = [(nA, nU, C, "unit") for nA, nU in SHAPES for C in COVARS] + [(300, 211, 3, "mean1000")]
+# k_linear deals the ne = q (q + 1) / 2 entries of S, q = C + 2, to the 64 lanes of a wave: entry lane + 64 t, t = 0, 1, 2.  COVARS
+# gives ne = 3, 6, 15, 120 and 136; COVARS_DEAL stands on either side of the step from one entry per lane to two: C = 8 has ne = 55,
+# C = 9 has ne = 66, the lanes 0 and 1 alone with a second entry.
+SHAPES_DEAL = [(129, 70), (300, 211)]
+COVARS_DEAL = [8, 9]
+
+CASES = ([(nA, nU, C, "unit") for nA, nU in SHAPES for C in COVARS] + [(300, 211, 3, "mean1000")]
+         + [(nA, nU, C, "unit") for nA, nU in SHAPES_DEAL for C in COVARS_DEAL])
 
 
 def measure_E():

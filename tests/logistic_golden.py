@@ -15,10 +15,11 @@ OK, NOT_CONVERGED, SINGULAR = 0, 1, 2
 PIVOT_EPS = 1e-12
 MAX_ITER, TOL = 25, 1e-10          # the runner's, and the tests'
 
-# The yardstick: max over all rows expected OK of every case of CASES of |beta_fwd - beta_rev| / se and |se_fwd - se_rev| / se, every
-# coefficient.  Measured on the CPU by measure_E() (tests/test_logistic_cpu.py asserts that the constant still covers it):
-#   measured 5.2e-14 (70 .. 530 samples, C = 0 .. 14, 67 + 8 rows per case)
-E = 5.2e-14
+# The yardstick: max over all rows expected OK of every case of CASES and of the nested cases of |beta_fwd - beta_rev| / se and
+# |se_fwd - se_rev| / se, every coefficient.  Measured on the CPU by measure_E() (tests/test_logistic_cpu.py asserts that the constant still covers it):
+#   measured 7.0e-14 (32 .. 1300 cohort samples, C = 0 .. 14, 67 + 8 rows per case of CASES and the 67 rows of the four nested
+#   cases; 5.2e-14 over SHAPES x COVARS alone, 70 .. 530 samples)
+E = 7.0e-14
 # what a device result may differ by, in the same units: another summation tree, fma, another exp
 DEVICE_TOL = max(64 * E, 1e-12)
 
@@ -186,11 +187,10 @@ def cohort_view(case, row):
 #   "singular"  singular by construction: status SINGULAR, NaN
 #   "nan"       separated or close to it (not OK in some order): NaN with status NOT_CONVERGED or SINGULAR
 #   "loose"     converges, but slowly or badly conditioned: n_obs only, and NaN unless the status is OK
-@functools.lru_cache(maxsize=None)
-def expectations(nA, nU, C):
-    case = make_case(nA, nU, C)
+def _expect_rows(case, rows):
+    C = case["C"]
     out = []
-    for r in range(len(case["gt"])):
+    for r in rows:
         cls, y, cov = cohort_view(case, r)
         f, b = fit(cls, y, cov), fit(cls, y, cov, reverse=True)
         name = STATUS_ROWS[r - N_ROWS] if r >= N_ROWS else "random"
@@ -205,7 +205,25 @@ def expectations(nA, nU, C):
         else:
             kind = "loose"
         out.append(dict(kind=kind, name=name, fwd=f, rev=b))
-    return case, out
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def expectations(nA, nU, C):
+    case = make_case(nA, nU, C)
+    return case, _expect_rows(case, range(len(case["gt"])))
+
+
+@functools.lru_cache(maxsize=None)
+def nested_expectations(C):
+    """the random rows of the NESTED cohort with the first C of its covariate columns: the same cohort, the same rows and nested
+    designs at every C, so that two neighbouring C differ in the kernel that runs them and in one column.  (The status rows are built
+    for the widest design and stay out.)"""
+    nA, nU, widest = NESTED
+    assert C <= widest
+    full = make_case(nA, nU, widest)
+    case = dict(full, C=C, cov=np.ascontiguousarray(full["cov"][:, :C]), gt=np.ascontiguousarray(full["gt"][:N_ROWS]))
+    return case, _expect_rows(case, range(N_ROWS))
 
 
 def well_sized(nA, nU, C):
@@ -213,13 +231,32 @@ def well_sized(nA, nU, C):
     return nA + nU >= 12 * (C + 2)
 
 
-CASES = [(nA, nU, C) for nA, nU in SHAPES for C in COVARS]
+# k_logistic<P, DEAL> by p = C + 2 (logistic_launch), and the zero pad coordinates P - p:
+#   C = 0         <2, 1>   pad 0            C = 5, 6      <8, 1>   pad 1, 0
+#   C = 1, 2      <4, 1>   pad 1, 0         C = 7 .. 10   <12, 2>  pad 3, 2, 1, 0
+#   C = 3, 4      <6, 1>   pad 1, 0         C = 11 .. 14  <16, 4>  pad 3, 2, 1, 0
+# COVARS reaches <2,1>, <4,1>, <6,1> and <16,4> with pads 0 and 1; COVARS_MORE the other two kernels, every P filled exactly
+# (C = 2, 4, 6, 10) and three pad coordinates (C = 7).  (15, 17) is small for these p: its status rows stay honest, its random rows
+# are mostly "loose"; the two larger shapes are well_sized at every C of COVARS_MORE.
+SHAPES_MORE = [(15, 17), (129, 70), (300, 211)]
+COVARS_MORE = [2, 4, 5, 6, 7, 9, 10]
+# One long cohort: a pitch above 1024 positions.  A lane's sample loop advances 512 positions per turn with DEAL = 1, 256 with
+# DEAL = 2 and 128 with DEAL = 4, so the waves take 2 or 3 (C = 3: <6,1>, C = 6: <8,1>), 5 or 6 (C = 10: <12,2>) and 10 or 11
+# (C = 14: <16,4>) turns, and the last turn is ragged in each.
+LONG = (700, 600)
+COVARS_LONG = [3, 6, 10, 14]
+# The dispatch edges: one cohort, the same rows, the first C columns of one covariate matrix -- <8,1> | <12,2> between C = 6 and 7,
+# <12,2> | <16,4> between C = 10 and 11 (nested_expectations)
+NESTED = (129, 70, 11)
+COVARS_NESTED = [6, 7, 10, 11]
+
+CASES = ([(nA, nU, C) for nA, nU in SHAPES for C in COVARS] + [(nA, nU, C) for nA, nU in SHAPES_MORE for C in COVARS_MORE]
+         + [LONG + (C,) for C in COVARS_LONG])
 
 
 def measure_E():
     worst = 0.0
-    for key in CASES:
-        _, exp = expectations(*key)
+    for exp in [expectations(*key)[1] for key in CASES] + [nested_expectations(C)[1] for C in COVARS_NESTED]:
         for e in exp:
             if e["kind"] != "ok":
                 continue

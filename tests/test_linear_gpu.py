@@ -97,7 +97,8 @@ def test_rows_longer_than_one_step_of_the_correction_scan():
     e.close()
 
 
-@pytest.mark.parametrize("key", [(37, 29, 3, "unit"), (129, 70, 13, "unit"), (300, 211, 14, "unit"), (15, 17, 0, "unit")], ids=ln.case_id)
+@pytest.mark.parametrize("key", [(37, 29, 3, "unit"), (129, 70, 13, "unit"), (300, 211, 14, "unit"), (15, 17, 0, "unit"), (129, 70, 9, "unit")],
+                         ids=ln.case_id)
 def test_split_calls_and_repeated_runs_are_bit_identical(key):
     case, _ = ln.expectations(*key)
     n_all = len(case["gt"])

@@ -1,6 +1,7 @@
 """The host pieces of the logistic regression (include/hpgv.h "Logistic regression"), which need no device: the exported symbols,
-the conditions the oracle's cases must meet, hpgv_logistic_fit against the oracle, against the score equation and against a
-scipy.optimize fit of the same likelihood, the status rows, argument errors, and the covariate-file reader."""
+the conditions the oracle's cases must meet (every shipped kernel shape among them), hpgv_logistic_fit against the oracle, against
+the score equation and against a scipy.optimize fit of the same likelihood, the status rows, argument errors, and the
+covariate-file reader."""
 import ctypes as C
 import os
 import re
@@ -65,6 +66,35 @@ def test_the_cases_meet_their_conditions():
     assert sum(lg.well_sized(*k) for k in lg.CASES) >= 15 and n_ok > 1500
 
 
+def test_every_shipped_kernel_shape_has_well_sized_cases_and_the_nested_ones_meet_their_conditions():
+    """by p = C + 2 as logistic_launch dispatches: every instantiation, every P filled exactly, pads of 1 and of 3 coordinates --
+    each with well-sized cases, whose random rows the oracle alone fits nine times in ten"""
+    shipped = [2, 4, 6, 8, 12, 16]
+    well = {}
+    for nA, nU, C in lg.CASES:
+        if lg.well_sized(nA, nU, C):
+            P = min(P for P in shipped if P >= C + 2)
+            well.setdefault((P, P - C - 2), []).append((nA, nU))
+    for P in shipped:
+        assert len(well.get((P, 0), [])) >= 2, P                   # p fills P
+    for P in shipped[1:]:
+        assert len(well.get((P, 1), [])) >= 2, P                   # one pad coordinate
+    assert len(well[(12, 3)]) >= 2
+    for C in lg.COVARS_LONG:                                       # the long cohort: one case per DEAL, and <8,1>
+        assert lg.well_sized(*lg.LONG, C) and lg.LONG + (C,) in lg.CASES
+    assert lg.well_sized(*lg.NESTED) and lg.COVARS_NESTED == [6, 7, 10, 11]
+    wide, _ = lg.nested_expectations(lg.NESTED[2])
+    for C in lg.COVARS_NESTED:
+        case, exp = lg.nested_expectations(C)
+        assert case["cov"].shape[1] == C and len(exp) == len(case["gt"]) == lg.N_ROWS
+        assert np.array_equal(case["cov"], wide["cov"][:, :C], equal_nan=True) and np.array_equal(case["gt"], wide["gt"])
+        assert sum(e["kind"] == "ok" for e in exp) >= 0.9 * lg.N_ROWS, C
+        for r in range(0, lg.N_ROWS, 4):                           # and the host fit, which shares logit_chol_inv with the kernel
+            cls, y, cov = lg.cohort_view(case, r)
+            rec, coef = hpgv.logistic_fit(cls, y, cov)
+            lg.check_row(rec, coef, exp[r], (C, r))
+
+
 def test_the_yardstick_covers_the_two_summation_orders():
     measured = lg.measure_E()
     print("E measured %.3g, constant %.3g, device tolerance %.3g" % (measured, lg.E, lg.DEVICE_TOL))
@@ -91,7 +121,7 @@ def test_the_host_fit_agrees_with_the_oracle(key):
 
 def test_the_score_vanishes_at_the_fit():
     """u(beta) recomputed in numpy from the returned coefficients: not the oracle's solver"""
-    for key in [(37, 29, 3), (129, 70, 14), (300, 211, 0), (300, 211, 13)]:
+    for key in [(37, 29, 3), (129, 70, 14), (300, 211, 0), (300, 211, 13), (129, 70, 6), (300, 211, 9), (129, 70, 10), (700, 600, 10)]:
         case, exp = lg.expectations(*key)
         for r in range(0, lg.N_ROWS, 7):
             if exp[r]["kind"] != "ok":
@@ -109,7 +139,7 @@ def test_the_score_vanishes_at_the_fit():
 
 def test_a_scipy_fit_of_the_same_likelihood_agrees():
     from scipy.optimize import minimize
-    for key, r in [((300, 211, 3), 0), ((129, 70, 1), 5), ((64, 64, 0), 11)]:
+    for key, r in [((300, 211, 3), 0), ((129, 70, 1), 5), ((64, 64, 0), 11), ((300, 211, 6), 2), ((300, 211, 10), 4), ((700, 600, 6), 9)]:
         case, exp = lg.expectations(*key)
         assert exp[r]["kind"] == "ok"
         cls, y, cov = lg.cohort_view(case, r)

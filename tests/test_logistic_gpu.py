@@ -1,7 +1,8 @@
 """The logistic regression on the device (include/hpgv.h "Logistic regression"): k_logistic through hpgv_assoc_logistic_dev, the
 host-batch and the text entry points against the numpy oracle of logistic_golden under its tolerances -- every cohort shape that
-moves the pads, the lane steps and the ragged last step, every instantiation of p -- then bit identity of split calls and
-repeated runs, a stream of the caller's, the covariates' life with the cohort, and the error codes."""
+moves the pads, the lane steps and the ragged last step, every instantiation of k_logistic<P, DEAL> with p filling P and with pad
+coordinates, one cohort long enough for several turns of every wave's sample loop -- then the dispatch edges on nested covariate
+columns, bit identity of split calls and repeated runs, a stream of the caller's, the covariates' life with the cohort, and the error codes."""
 import ctypes as C
 
 import numpy as np
@@ -76,19 +77,65 @@ def test_the_three_entry_points_against_the_oracle(key):
     e.close()
 
 
-@pytest.mark.parametrize("key", [(37, 29, 3), (129, 70, 13), (300, 211, 14), (15, 17, 0)], ids=lambda k: "%dx%d_C%d" % k)
+def test_the_long_cohort_takes_every_kernel_through_several_ragged_turns():
+    """what the LONG cases of test_the_three_entry_points_against_the_oracle rest on: a pitch above 1024 positions, so that the
+    sample loop of logit_pass -- 64 * NSUB pairs per turn -- takes 3 turns in its first waves and lanes and 2 in the others with
+    DEAL = 1, 5 or 6 with DEAL = 2, 10 or 11 with DEAL = 4"""
+    case, _ = lg.expectations(*lg.LONG, lg.COVARS_LONG[0])
+    e = engine(case, covariates=False)
+    pitch = e.assoc_layout()[2]
+    e.close()
+    assert pitch > 1024 and pitch % 16 == 0
+    for deal, turns in ((1, (2, 3)), (2, (5, 6)), (4, (10, 11))):
+        step = 64 * (4 // deal)                            # pairs of positions per turn
+        assert (pitch // 2) % step != 0                    # ragged
+        assert ((pitch // 2) // step, -(-(pitch // 2) // step)) == turns, (deal, pitch)
+    assert [C_ for C_ in lg.COVARS_LONG if lg.LONG + (C_,) in lg.CASES] == [3, 6, 10, 14]       # <6,1>, <8,1>, <12,2>, <16,4>
+
+
+@pytest.mark.parametrize("key", [(37, 29, 3), (129, 70, 13), (300, 211, 14), (15, 17, 0), (129, 70, 6), (300, 211, 10)],
+                         ids=lambda k: "%dx%d_C%d" % k)
 def test_split_calls_and_repeated_runs_are_bit_identical(key):
     case, _ = lg.expectations(*key)
     e = engine(case)
     whole, wc = run_dev(e, case)
     again, ac = run_dev(e, case)
     assert same(whole, again) and same(wc, ac)
-    at = 0
-    for nv in (1, 5, 67, N_ALL - 73):                      # n_variants 1, 5 and 67, then the rest
-        part, pc = run_dev(e, case, slice(at, at + nv))
-        assert same(part, whole[at:at + nv]) and same(pc, wc[at:at + nv]), (at, nv)
-        at += nv
-    assert at == N_ALL
+    for pieces in ((1, 5, 67), (1, 5, 15, 16, 17)):        # n_variants 1, 5 and 67, or 1, 5, 15, 16 and 17, then the rest
+        at = 0
+        for nv in pieces + (N_ALL - sum(pieces),):
+            part, pc = run_dev(e, case, slice(at, at + nv))
+            assert same(part, whole[at:at + nv]) and same(pc, wc[at:at + nv]), (at, nv)
+            at += nv
+        assert at == N_ALL
+    e.close()
+
+
+def test_the_dispatch_edges_on_nested_covariates():
+    """One cohort, the same rows, the first 6, 7, 10 and 11 columns of one covariate matrix: k_logistic<8,1> | <12,2> | <16,4>.
+    Every fit agrees with its own oracle fit, so an error of one instantiation is a jump at its edge: the figures are printed side
+    by side."""
+    e, ref = None, None
+    for C_ in lg.COVARS_NESTED:
+        case, exp = lg.nested_expectations(C_)
+        if e is None:
+            e = engine(case, covariates=False)
+        e.set_covariates(case["cov"])
+        out, cf = run_dev(e, case)
+        assert cf.shape == (lg.N_ROWS, 2, C_ + 2)
+        worst_b = worst_s = 0.0
+        n_ok = 0
+        for r, x in enumerate(exp):
+            lg.check_row(out[r], cf[r], x, (C_, r))
+            if x["kind"] == "ok":
+                n_ok += 1
+                worst_b = max(worst_b, np.max(np.abs(cf[r][0] - x["fwd"]["coef_beta"]) / x["fwd"]["coef_se"]))
+                worst_s = max(worst_s, np.max(np.abs(cf[r][1] - x["fwd"]["coef_se"]) / x["fwd"]["coef_se"]))
+        print("C = %d: %d rows ok, worst |d beta| / se %.3g, |d se| / se %.3g, tolerance %.3g" % (C_, n_ok, worst_b, worst_s, lg.DEVICE_TOL))
+        assert n_ok >= 0.9 * lg.N_ROWS and (out["status"] == lg.OK).sum() >= 0.9 * lg.N_ROWS
+        if ref is not None:                                # the same genotypes: the same observations at every C
+            assert np.array_equal(out["n_obs"], ref["n_obs"]) and not same(out["beta"], ref["beta"])
+        ref = out
     e.close()
 
 

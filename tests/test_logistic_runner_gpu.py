@@ -1,5 +1,6 @@
 """hpgv_run_assoc_logistic: the logistic regression's file runner.  Its file is the numpy oracle's fit of every record, formatted
-line by line; the bytes do not depend on the batch size or the input form; a sample without covariates leaves the cohort; the
+line by line, with 3 covariates and, on a second cohort, with 10 and with the first 6 of 10 (k_logistic<12,2> and <8,1>); the bytes
+do not depend on the batch size or the input form; a sample without covariates leaves the cohort; the
 .eigenvec file of hpgv_run_pca is a covariate file as it stands; what is refused before the engine starts writes no file."""
 import gzip
 import os
@@ -20,33 +21,31 @@ HEADER = "#CHR\tPOS\tID\tA1\tA2\tNOBS\tBETA\tSE\tOR\tSTAT\tP\tITER\n"
 N_SAMPLES, N_RECORDS, N_COV = 60, 40, 3
 
 
-@pytest.fixture(scope="module")
-def inputs(tmp_path_factory):
-    tmp = tmp_path_factory.mktemp("logistic_runner")
-    rng = np.random.default_rng(77)
-    names = ["S%d" % i for i in rng.permutation(N_SAMPLES)]
-    pheno = rng.choice([1, 2, 2, 1, 0], N_SAMPLES)                   # 0: in no class
+def _make_inputs(tmp, seed, n_samples, n_records, n_cov):
+    rng = np.random.default_rng(seed)
+    names = ["S%d" % i for i in rng.permutation(n_samples)]
+    pheno = rng.choice([1, 2, 2, 1, 0], n_samples)                   # 0: in no class
     with open(tmp / "ped.txt", "w") as f:
-        for k in rng.permutation(N_SAMPLES):                         # PED order is not the VCF's
+        for k in rng.permutation(n_samples):                         # PED order is not the VCF's
             f.write("fam%d %s 0 0 %d %d\n" % (k, names[k], 1 + k % 2, pheno[k]))
-    cov = rng.standard_normal((N_SAMPLES, N_COV))
+    cov = rng.standard_normal((n_samples, n_cov))
     cohort = np.flatnonzero(pheno != 0)
     absent, na = int(cohort[4]), int(cohort[9])                      # one cohort sample without a line, one with NA in the last column
     with open(tmp / "covar.txt", "w") as f:
-        f.write("FID IID PC1 PC2 PC3\n")
-        for k in rng.permutation(N_SAMPLES):
+        f.write("FID IID %s\n" % " ".join("PC%d" % (k + 1) for k in range(n_cov)))
+        for k in rng.permutation(n_samples):
             if k == absent:
                 continue
             vals = ["%.17g" % x for x in cov[k]]
             if k == na:
-                vals[2] = "NA"
+                vals[n_cov - 1] = "NA"
             f.write("fam%d\t%s  %s\n" % (k, names[k], " ".join(vals)))
-        f.write("famX nobody 1 2 3\n")                               # a line of a sample the VCF does not have
+        f.write("famX nobody %s\n" % " ".join(str(k + 1) for k in range(n_cov)))      # a line of a sample the VCF does not have
     gts = np.array(["0/0", "0/1", "1/0", "1/1", "./."])
     rows, lines = [], []
-    for v in range(N_RECORDS):
+    for v in range(n_records):
         chrom = ("1", "X", "22", "3")[v % 4]
-        g = gts[rng.choice(5, N_SAMPLES, p=[0.3, 0.2, 0.2, 0.25, 0.05])]
+        g = gts[rng.choice(5, n_samples, p=[0.3, 0.2, 0.2, 0.25, 0.05])]
         if v == 7:
             g[:] = "0/0"                                              # monomorphic: a failed fit in the file
         cls = np.array([{"0/0": 0, "0/1": 1, "1/0": 1, "1/1": 2, "./.": 255}[x] for x in g], np.uint8)
@@ -59,7 +58,25 @@ def inputs(tmp_path_factory):
     open(paths["gzip"], "wb").write(gzip.compress(data))
     open(paths["bgzip"], "wb").write(_bgzf(data, 0x1000))
     return dict(tmp=tmp, paths=paths, ped=str(tmp / "ped.txt"), covar=str(tmp / "covar.txt"), names=names, pheno=pheno, cov=cov, rows=rows,
-                absent=absent, na=na)
+                absent=absent, na=na, n_data_bytes=len("".join(lines)))
+
+
+@pytest.fixture(scope="module")
+def inputs(tmp_path_factory):
+    return _make_inputs(tmp_path_factory.mktemp("logistic_runner"), 77, N_SAMPLES, N_RECORDS, N_COV)
+
+
+# ten covariate columns, as the ten principal components of a .eigenvec file: all of them -> p = 12, k_logistic<12,2>; the first six
+# -> p = 8, k_logistic<8,1>.  About 125 of the 170 samples are in a class: more than ten observations per coefficient.  The
+# records fill more than one batch of the smallest size (64 KiB).
+WIDE_SAMPLES, WIDE_RECORDS, WIDE_COV = 170, 110, 10
+
+
+@pytest.fixture(scope="module")
+def wide_inputs(tmp_path_factory):
+    w = _make_inputs(tmp_path_factory.mktemp("logistic_runner_wide"), 78, WIDE_SAMPLES, WIDE_RECORDS, WIDE_COV)
+    assert w["n_data_bytes"] > (1 << 16) and (w["pheno"] != 0).sum() - 2 >= 10 * (WIDE_COV + 2)
+    return w
 
 
 def _sorted(text):
@@ -74,7 +91,7 @@ def _expected(inputs, used, cov):
         r = lg.fit(cls[used], y, cov[used] if cov is not None else None)
         n_ok += r["status"] == lg.OK
         out.append(lg.format_line(chrom, pos, vid, "A", "C", r) + "\n")
-    assert n_ok >= N_RECORDS - 2                                      # the comparison says something
+    assert n_ok >= len(inputs["rows"]) - 2                            # the comparison says something
     return _sorted("".join(out))
 
 
@@ -93,6 +110,25 @@ def test_the_file_is_the_oracles(inputs, expected, form, batch):
     got = open(out, "rb").read()
     assert got.split(b"\n") == expected[0].split(b"\n")
     assert b"\tnan\tnan\tnan\tnan\tnan\t0\n" in got                   # the monomorphic record: five nan, no step
+
+
+@pytest.mark.parametrize("n_covar", [0, 6], ids=["all_10_columns", "first_6_columns"])
+def test_the_file_with_ten_and_with_six_covariates_is_the_oracles(wide_inputs, n_covar):
+    """k_logistic<12,2> and <8,1> through the runner: line by line the oracle's, the same bytes whatever the batch size"""
+    w = wide_inputs
+    used = w["pheno"] != 0
+    used[w["absent"]] = False
+    if n_covar == 0:
+        used[w["na"]] = False                                         # the NA is in the tenth column
+    want = _expected(w, used, w["cov"][:, :n_covar or WIDE_COV])
+    files = []
+    for batch in (1 << 16, 1 << 22):                                  # two batches, one batch
+        out = str(w["tmp"] / ("out_%d_%d.logistic" % (n_covar, batch)))
+        assert hpgv.run_assoc_logistic(w["paths"]["plain"], w["ped"], w["covar"], out, n_covar, batch) == (WIDE_RECORDS, int(used.sum()))
+        files.append(open(out, "rb").read())
+        assert files[-1].split(b"\n") == want.split(b"\n")
+    assert files[0] == files[1]
+    assert files[0].count(b"\tnan\tnan\tnan\tnan\tnan\t") == 1      # the monomorphic record alone failed
 
 
 def test_a_sample_without_covariates_leaves_the_cohort_only_where_the_column_is_used(inputs, expected):
