@@ -467,6 +467,24 @@ template <typename F>
     return HPGV_OK;
 }
 
+// the back half of the regressions' batch and text entry points (hpgv_assoc_logistic*, hpgv_assoc_linear*): room in the slot for a
+// 48-byte record per row and, with coef, 2 (n_covar + 2) doubles per row behind them; launch(ctx, d_laid, n, args..., d_out, d_coef,
+// stream) queues the kernel; then the caller's arrays, copied and waited for
+template <typename Rec, typename F, typename... Args>
+[[maybe_unused]] int regression_finish(hpgv_ctx *ctx, Slot *s, const Staged &S, Rec *out, double *coef, F launch, Args... args) {
+    static_assert(sizeof(Rec) == 48, "the records of include/hpgv.h");
+    if (S.n == 0) return HPGV_OK;
+    const size_t n = (size_t)S.n, coef_bytes = coef ? n * (size_t)(2 * (ctx->n_covar + 2)) * sizeof(double) : 0;
+    HIPCHK(ctx, s->dbl.reserve_slack(n * sizeof(Rec) + coef_bytes + 16));
+    Rec *d_out = s->dbl.template as<Rec>();
+    double *d_coef = coef ? (double *)(d_out + n) : nullptr;
+    if (const int rc = launch(ctx, S.d_laid, S.n, args..., d_out, d_coef, s->stream)) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(out, d_out, n * sizeof(Rec), hipMemcpyDeviceToHost, s->stream));
+    if (coef) HIPCHK(ctx, hipMemcpyAsync(coef, d_coef, coef_bytes, hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(ctx, hipStreamSynchronize(s->stream));
+    return HPGV_OK;
+}
+
 }  // namespace
 
 // defined in hpgv_capi.hip: the text aliases of a context (hpgv_text_alias, hpgv_text_alias_tiles)

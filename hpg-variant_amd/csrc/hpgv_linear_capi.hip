@@ -1,6 +1,6 @@
 // hpgv_linear_capi.hip -- C ABI of the linear regression (include/hpgv.h "Linear regression"): the phenotype of a context and the
 // model's device image, the device-resident launch of k_linear, the synchronous entry points on a host batch and on a text --
-// built as hpgv_assoc_logistic's are: arguments, a slot, stage_chain / text_front, then the back half below -- the host-only fit
+// built as hpgv_assoc_logistic's are: arguments, a slot, stage_chain / text_front, then the regressions' back half (regression_finish, hpgv_internal.h) -- the host-only fit
 // and the t tail.
 #include "hpgv_internal.h"
 #include "hpgv_linear_kernels.h"
@@ -66,22 +66,6 @@ int linear_launch(hpgv_ctx *ctx, const uint8_t *d_gt, int n_variants, hpgv_linea
     return launch_profiled(ctx, st, 1, [&] { hipLaunchKernelGGL(hpgv::k_linear, grid, block, 0, st, A); });
 }
 
-// the back half of hpgv_assoc_linear and hpgv_assoc_linear_text: the laid-out matrix of a staged call -> k_linear -> the
-// caller's arrays
-int linear_finish(hpgv_ctx *ctx, Slot *s, const Staged &S, hpgv_linear_result *out, double *coef) {
-    int rc;
-    if (S.n == 0) return HPGV_OK;
-    const size_t n = (size_t)S.n, coef_bytes = coef ? n * (size_t)(2 * (ctx->n_covar + 2)) * sizeof(double) : 0;
-    HIPCHK(ctx, s->dbl.reserve_slack(n * sizeof(hpgv_linear_result) + coef_bytes + 16));
-    hpgv_linear_result *d_out = s->dbl.as<hpgv_linear_result>();
-    double *d_coef = coef ? (double *)(d_out + n) : nullptr;
-    if ((rc = linear_launch(ctx, S.d_laid, S.n, d_out, d_coef, s->stream))) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(out, d_out, n * sizeof(hpgv_linear_result), hipMemcpyDeviceToHost, s->stream));
-    if (coef) HIPCHK(ctx, hipMemcpyAsync(coef, d_coef, coef_bytes, hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(ctx, hipStreamSynchronize(s->stream));
-    return HPGV_OK;
-}
-
 }  // namespace
 
 // the image of the context's phenotype and covariates, or nothing without a phenotype
@@ -144,7 +128,7 @@ int hpgv_assoc_linear(hpgv_ctx *ctx, const uint8_t *gt, size_t pitch, int n_vari
     HPGV_LEASE_SLOT(ctx)
     Staged S;
     if ((rc = stage_chain(ctx, s, HPGV_LAYOUT_ASSOC, ctx->assoc, gt, pitch, n_variants, nullptr, &S))) return rc;
-    return linear_finish(ctx, s, S, out, coef);
+    return regression_finish(ctx, s, S, out, coef, linear_launch);
     HPGV_ABI_CATCH(ctx)
 }
 
@@ -160,7 +144,7 @@ int hpgv_assoc_linear_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, i
     HPGV_LEASE_SLOT(ctx)
     Staged S;
     if ((rc = text_front(ctx, s, HPGV_LAYOUT_ASSOC, ctx->assoc, text, text_bytes, max_lines, n_lines, line_off, field_off, status, &S))) return rc;
-    return linear_finish(ctx, s, S, out, coef);
+    return regression_finish(ctx, s, S, out, coef, linear_launch);
     HPGV_ABI_CATCH(ctx)
 }
 

@@ -1,6 +1,6 @@
 // hpgv_logistic_capi.hip -- C ABI of the logistic regression (include/hpgv.h "Logistic regression"): the covariates of a context,
 // the device-resident launch of k_logistic, the synchronous entry points on a host batch and on a text -- built as
-// hpgv_assoc_model's are: arguments, a slot, stage_chain / text_front, then the back half below -- and the host-only fit.
+// hpgv_assoc_model's are: arguments, a slot, stage_chain / text_front, then the regressions' back half (regression_finish, hpgv_internal.h) -- and the host-only fit.
 #include "hpgv_internal.h"
 #include "hpgv_logistic_kernels.h"
 
@@ -33,22 +33,6 @@ int logistic_launch(hpgv_ctx *ctx, const uint8_t *d_gt, int n_variants, int max_
         else if (p <= 12) hipLaunchKernelGGL((hpgv::k_logistic<12, 2>), grid, block, 0, st, A);
         else hipLaunchKernelGGL((hpgv::k_logistic<16, 4>), grid, block, 0, st, A);
     });
-}
-
-// the back half of hpgv_assoc_logistic and hpgv_assoc_logistic_text: the laid-out matrix of a staged call -> k_logistic -> the
-// caller's arrays
-int logistic_finish(hpgv_ctx *ctx, Slot *s, const Staged &S, int max_iter, double tol, hpgv_logistic_result *out, double *coef) {
-    int rc;
-    if (S.n == 0) return HPGV_OK;
-    const size_t n = (size_t)S.n, coef_bytes = coef ? n * (size_t)(2 * (ctx->n_covar + 2)) * sizeof(double) : 0;
-    HIPCHK(ctx, s->dbl.reserve_slack(n * sizeof(hpgv_logistic_result) + coef_bytes + 16));
-    hpgv_logistic_result *d_out = s->dbl.as<hpgv_logistic_result>();
-    double *d_coef = coef ? (double *)(d_out + n) : nullptr;
-    if ((rc = logistic_launch(ctx, S.d_laid, S.n, max_iter, tol, d_out, d_coef, s->stream))) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(out, d_out, n * sizeof(hpgv_logistic_result), hipMemcpyDeviceToHost, s->stream));
-    if (coef) HIPCHK(ctx, hipMemcpyAsync(coef, d_coef, coef_bytes, hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(ctx, hipStreamSynchronize(s->stream));
-    return HPGV_OK;
 }
 
 // the 1-df chi-square tail as hpgv::chisq_p_value writes it, on libm
@@ -124,7 +108,7 @@ int hpgv_assoc_logistic(hpgv_ctx *ctx, const uint8_t *gt, size_t pitch, int n_va
     HPGV_LEASE_SLOT(ctx)
     Staged S;
     if ((rc = stage_chain(ctx, s, HPGV_LAYOUT_ASSOC, ctx->assoc, gt, pitch, n_variants, nullptr, &S))) return rc;
-    return logistic_finish(ctx, s, S, max_iter, tol, out, coef);
+    return regression_finish(ctx, s, S, out, coef, logistic_launch, max_iter, tol);
     HPGV_ABI_CATCH(ctx)
 }
 
@@ -142,7 +126,7 @@ int hpgv_assoc_logistic_text(hpgv_ctx *ctx, const char *text, size_t text_bytes,
     HPGV_LEASE_SLOT(ctx)
     Staged S;
     if ((rc = text_front(ctx, s, HPGV_LAYOUT_ASSOC, ctx->assoc, text, text_bytes, max_lines, n_lines, line_off, field_off, status, &S))) return rc;
-    return logistic_finish(ctx, s, S, max_iter, tol, out, coef);
+    return regression_finish(ctx, s, S, out, coef, logistic_launch, max_iter, tol);
     HPGV_ABI_CATCH(ctx)
 }
 

@@ -23,7 +23,8 @@ static int run_batch_stats_arrays(run_batch_t *b) {
 /* the per-line arrays for max_lines lines (the ones there before freed) */
 static int run_batch_lines(run_batch_t *b) {
     free(b->line_off); free(b->field_off); free(b->status); free(b->ints); free(b->dbl);
-    if (tool_perm(b->run->tool)) {
+    const tool_traits_t *T = tool_of(b->run->tool);
+    if (T->mperm) {
         free(b->n_ge);
         b->n_ge = (int32_t *)malloc(sizeof(int32_t) * (size_t)b->max_lines);
         if (!b->bmax) b->bmax = (double *)malloc(sizeof(double) * (size_t)b->run->n_perms);
@@ -32,9 +33,8 @@ static int run_batch_lines(run_batch_t *b) {
     b->line_off = (uint64_t *)malloc(sizeof(uint64_t) * ((size_t)b->max_lines + 1));
     b->field_off = (uint32_t *)malloc(sizeof(uint32_t) * 10 * (size_t)b->max_lines);
     b->status = (int32_t *)malloc(sizeof(int32_t) * (size_t)b->max_lines);
-    const int model = tool_model(b->run->tool);
-    b->ints = (int32_t *)malloc(sizeof(int32_t) * (model ? 8 : 4) * (size_t)b->max_lines);
-    b->dbl = (double *)malloc(sizeof(double) * (model ? 10 : b->run->tool == RUN_LOGISTIC || b->run->tool == RUN_LINEAR ? 6 : 3) * (size_t)b->max_lines);
+    b->ints = (int32_t *)malloc(sizeof(int32_t) * (size_t)T->ints * (size_t)b->max_lines);
+    b->dbl = (double *)malloc(sizeof(double) * (size_t)T->dbls * (size_t)b->max_lines);
     if (b->row_width > 0) {
         free(b->rows);
         b->rows_cap = (size_t)b->max_lines * (size_t)b->row_width;
@@ -53,7 +53,7 @@ int run_batch_alloc(run_batch_t *b, run_t *run, size_t cap_bytes, int n_samples,
     memset(b, 0, sizeof *b);
     b->run = run;
     b->row_width = run->tool == RUN_VCF2EPI ? n_samples : 0;        /* vcf2epi: one dataset row per line */
-    b->stats = tool_counts(run->tool); b->n_smiss = n_samples; b->n_cerr = n_trios; b->n_groups = n_groups;
+    b->stats = tool_of(run->tool)->counts; b->n_smiss = n_samples; b->n_cerr = n_trios; b->n_groups = n_groups;
     size_t min_line = (size_t)(2 * (n_samples > 0 ? n_samples : 1) + 18);
     b->max_lines = (int)(cap_bytes / min_line) + 2;
     b->text = NULL; b->text_cap = cap_bytes + 1;         /* taken by the reader at the batch's first use: the pipeline starts meanwhile */
@@ -127,6 +127,13 @@ int hpgv_host_format_f6(double x, char *dst) {
 static int format_aggregate(char *dst, size_t room, const run_batch_t *b, int i);
 static int format_stats_variant(char *dst, size_t room, const run_batch_t *b, int i);
 
+/* the regressions' columns: NOBS, then k doubles, a NaN of either sign spelled "nan" */
+static char *put_fit(char *p, int n_obs, const double *v, int k) {
+    p = put_i64(p, n_obs);
+    for (int t = 0; t < k; t++) { *p++ = '\t'; p = v[t] != v[t] ? PUT_STR(p, "nan", 3) : PUT_F6(p, v[t]); }
+    return p;
+}
+
 static int format_record(char *dst, size_t room, const run_batch_t *b, int i) {
     const run_tool_t tool = b->run->tool;
     if (tool == RUN_AGGREGATE) return format_aggregate(dst, room, b, i);
@@ -147,55 +154,49 @@ static int format_record(char *dst, size_t room, const run_batch_t *b, int i) {
     p = put_i64(p, atol(l + fo[1])); *p++ = '\t';
     p = PUT_STR(p, l + fo[2], li); *p++ = '\t';
     p = PUT_STR(p, l + fo[3], lr); *p++ = '\t';
-    if (tool_model(tool)) {                               /* CHR POS ID A1 A2 AFF UNAFF, then chi-square and p of the five tests */
+    const run_tool_t file = tool_of(tool)->file;          /* the layout is that of the file the tool writes */
+    if (file != RUN_CHISQ && file != RUN_FISHER) { p = PUT_STR(p, l + fo[4], la); *p++ = '\t'; }      /* (theirs has A2 further on) */
+    switch (file) {
+    case RUN_MODEL: {                                     /* CHR POS ID A1 A2 AFF UNAFF, then chi-square and p of the five tests */
         const int32_t *c = b->ints + 8 * (size_t)i;
         const double *x = b->dbl + 5 * (size_t)i, *pv = b->dbl + 5 * (size_t)m + 5 * (size_t)i;
-        p = PUT_STR(p, l + fo[4], la); *p++ = '\t';
         p = put_i64(p, c[0]); *p++ = '/'; p = put_i64(p, c[1]); *p++ = '/'; p = put_i64(p, c[2]); *p++ = '\t';
         p = put_i64(p, c[3]); *p++ = '/'; p = put_i64(p, c[4]); *p++ = '/'; p = put_i64(p, c[5]);
         for (int t = 0; t < 5; t++) { *p++ = '\t'; p = PUT_F6(p, x[t]); *p++ = '\t'; p = PUT_F6(p, pv[t]); }
-        *p++ = '\n'; *p = 0;
-        return (int)(p - dst);
+        break;
     }
-    if (tool == RUN_LOGISTIC) {                           /* CHR POS ID A1 A2 NOBS BETA SE OR STAT P ITER; a failed fit: nan, whatever the NaN's sign */
+    case RUN_LOGISTIC: {                                  /* CHR POS ID A1 A2 NOBS BETA SE OR STAT P ITER; a failed fit: nan, whatever the NaN's sign */
         const hpgv_logistic_result *r = (const hpgv_logistic_result *)b->dbl + i;
         const double five[5] = { r->beta, r->se, exp(r->beta), r->stat, r->p };
-        p = PUT_STR(p, l + fo[4], la); *p++ = '\t';
-        p = put_i64(p, r->n_obs);
-        for (int t = 0; t < 5; t++) { *p++ = '\t'; p = five[t] != five[t] ? PUT_STR(p, "nan", 3) : PUT_F6(p, five[t]); }
+        p = put_fit(p, r->n_obs, five, 5);
         *p++ = '\t'; p = put_i64(p, r->iters);
-        *p++ = '\n'; *p = 0;
-        return (int)(p - dst);
+        break;
     }
-    if (tool == RUN_LINEAR) {                             /* CHR POS ID A1 A2 NOBS BETA SE STAT P; a singular fit: nan in the four, an exact one: BETA, SE 0, nan, nan */
+    case RUN_LINEAR: {                                    /* CHR POS ID A1 A2 NOBS BETA SE STAT P; a singular fit: nan in the four, an exact one: BETA, SE 0, nan, nan */
         const hpgv_linear_result *r = (const hpgv_linear_result *)b->dbl + i;
         const double four[4] = { r->beta, r->se, r->stat, r->p };
-        p = PUT_STR(p, l + fo[4], la); *p++ = '\t';
-        p = put_i64(p, r->n_obs);
-        for (int t = 0; t < 4; t++) { *p++ = '\t'; p = four[t] != four[t] ? PUT_STR(p, "nan", 3) : PUT_F6(p, four[t]); }
-        *p++ = '\n'; *p = 0;
-        return (int)(p - dst);
+        p = put_fit(p, r->n_obs, four, 4);
+        break;
     }
-    if (tool_tdt(tool)) {
-        const int t1 = b->ints[i], t2 = b->ints[m + i];
-        p = PUT_STR(p, l + fo[4], la); *p++ = '\t';
-        p = put_i64(p, t1); *p++ = '\t'; p = put_i64(p, t2); *p++ = '\t';
+    case RUN_TDT:
+        p = put_i64(p, b->ints[i]); *p++ = '\t'; p = put_i64(p, b->ints[m + i]); *p++ = '\t';
         p = PUT_F6(p, b->dbl[i]); *p++ = '\t'; p = PUT_F6(p, b->dbl[m + i]); *p++ = '\t'; p = PUT_F6(p, b->dbl[2 * m + i]);
-        *p++ = '\n'; *p = 0;
-        return (int)(p - dst);
+        break;
+    default: {                                            /* the chi-square and Fisher files */
+        const int A1 = b->ints[i], A2 = b->ints[m + i], U1 = b->ints[2 * m + i], U2 = b->ints[3 * m + i];
+        const int na = A1 + A2, nu = U1 + U2;
+        const double fa1 = na > 0 ? (double)A1 / na : 0.0, fu1 = nu > 0 ? (double)U1 / nu : 0.0;
+        const double fa2 = na > 0 ? (double)A2 / na : 0.0, fu2 = nu > 0 ? (double)U2 / nu : 0.0;
+        p = put_i64(p, A1); *p++ = '\t'; p = put_i64(p, U1); *p++ = '\t';
+        p = PUT_F6(p, fa1); *p++ = '\t'; p = PUT_F6(p, fu1); *p++ = '\t';
+        p = PUT_STR(p, l + fo[4], la); *p++ = '\t';
+        p = put_i64(p, A2); *p++ = '\t'; p = put_i64(p, U2); *p++ = '\t';
+        p = PUT_F6(p, fa2); *p++ = '\t'; p = PUT_F6(p, fu2); *p++ = '\t';
+        p = PUT_F6(p, b->dbl[i]); *p++ = '\t';                        /* odds ratio */
+        if (file == RUN_CHISQ) { p = PUT_F6(p, b->dbl[m + i]); *p++ = '\t'; }
+        p = PUT_F6(p, b->dbl[2 * m + i]);
     }
-    const int A1 = b->ints[i], A2 = b->ints[m + i], U1 = b->ints[2 * m + i], U2 = b->ints[3 * m + i];
-    const int na = A1 + A2, nu = U1 + U2;
-    const double fa1 = na > 0 ? (double)A1 / na : 0.0, fu1 = nu > 0 ? (double)U1 / nu : 0.0;
-    const double fa2 = na > 0 ? (double)A2 / na : 0.0, fu2 = nu > 0 ? (double)U2 / nu : 0.0;
-    p = put_i64(p, A1); *p++ = '\t'; p = put_i64(p, U1); *p++ = '\t';
-    p = PUT_F6(p, fa1); *p++ = '\t'; p = PUT_F6(p, fu1); *p++ = '\t';
-    p = PUT_STR(p, l + fo[4], la); *p++ = '\t';
-    p = put_i64(p, A2); *p++ = '\t'; p = put_i64(p, U2); *p++ = '\t';
-    p = PUT_F6(p, fa2); *p++ = '\t'; p = PUT_F6(p, fu2); *p++ = '\t';
-    p = PUT_F6(p, b->dbl[i]); *p++ = '\t';                            /* odds ratio */
-    if (tool_chisq(tool)) { p = PUT_F6(p, b->dbl[m + i]); *p++ = '\t'; }
-    p = PUT_F6(p, b->dbl[2 * m + i]);
+    }
     *p++ = '\n'; *p = 0;
     return (int)(p - dst);
 }
@@ -376,7 +377,7 @@ static void fmt_task(void *v, int t) {
     fmt_job_t *j = (fmt_job_t *)v;
     const run_batch_t *b = j->b;
     out_buf_t *o = &j->bufs[t];
-    const int track = tool_sorts(b->run->tool) && b->field_off;      /* results that are sorted afterwards: in order so far? */
+    const int track = tool_of(b->run->tool)->sorts && b->field_off;      /* results that are sorted afterwards: in order so far? */
     o->len = 0;
     o->disorder = 0;
     const int lo = (int)((long)j->n * t / j->parts), hi = (int)((long)j->n * (t + 1) / j->parts);
@@ -492,7 +493,7 @@ int write_batch(FILE *fd, const run_batch_t *b, out_buf_t *bufs, int n_bufs, io_
     const double t_w0 = now_s();
     for (int t = 0; t < j.parts; t++) {
         if (!bufs[t].len) continue;
-        if (ord && tool_sorts(b->run->tool)) {                       /* the seam before this task's lines, and its own verdict */
+        if (ord && tool_of(b->run->tool)->sorts) {                       /* the seam before this task's lines, and its own verdict */
             const char *first_end = (const char *)memchr(bufs[t].p, '\n', bufs[t].len);
             const char *lastl = (const char *)memrchr(bufs[t].p, '\n', bufs[t].len - 1);
             lastl = lastl ? lastl + 1 : bufs[t].p;

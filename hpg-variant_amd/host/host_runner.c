@@ -185,7 +185,7 @@ static void *pipe_engine(void *v) {
             pthread_mutex_unlock(&P->mu);
             return NULL;
         }
-        if (tool_perm(tool)) {                            /* the batch's maxima into the run's: max is order-independent */
+        if (tool_of(tool)->mperm) {                       /* the batch's maxima into the run's: max is order-independent */
             double *tmax = P->run->PM->tmax;
             for (int q = 0; q < P->run->n_perms; q++) if (b->bmax[q] > tmax[q]) tmax[q] = b->bmax[q];
         }
@@ -229,6 +229,30 @@ static uint8_t *cohort_conditions(const run_t *R, const sample_ids_t *ids, int *
     return cond;
 }
 
+/* the assoc cohort of the case-control and trait stages on the device(s), from the condition vector as built so far; y: the trait,
+ * or NULL.  With a covariate file (the regressions) a cohort sample without a line of finite values leaves the cohort first, and
+ * the matched covariates follow the cohort; n_used: the samples that stayed */
+static int assoc_cohort_install(run_t *R, uint8_t *cond, const double *y) {
+    const int n_samples = R->n_samples;
+    int rc = HPGV_OK;
+    double *cov = NULL;
+    if (R->covar) {
+        uint8_t *have = (uint8_t *)malloc((size_t)n_samples + 1);
+        cov = (double *)malloc(sizeof(double) * ((size_t)n_samples * (size_t)R->n_covar + 1));
+        if (!have || !cov) rc = HPGV_ERR_NOMEM;
+        if (!rc) rc = covar_table_match(R->covar, R->names, n_samples, R->n_covar, cov, (size_t)R->n_covar, have);
+        for (int j = 0; !rc && j < n_samples; j++) if (!have[j]) cond[j] = HPGV_COND_OTHER;
+        free(have);
+    }
+    for (int j = 0; !rc && j < n_samples; j++) R->n_used += cond[j] == HPGV_COND_AFFECTED || cond[j] == HPGV_COND_UNAFFECTED;
+    if (!rc && (rc = hpgv_set_cohort(g_ctx, cond, n_samples))) host_fail("hpgv_set_cohort", rc);
+    g_assoc_key.set = 0;
+    if (!rc && cov && R->n_covar > 0 && (rc = hpgv_set_covariates(g_ctx, cov, n_samples, R->n_covar))) host_fail("hpgv_set_covariates", rc);
+    if (!rc && y && (rc = hpgv_set_phenotype(g_ctx, y, n_samples))) host_fail("hpgv_set_phenotype", rc);
+    free(cov);
+    return rc;
+}
+
 /* the tool's cohort on the device(s), PED rows looked up by sample name (associate_samples_and_positions +
  * sort_individuals), then the device-side record filters */
 static int run_cohort(run_t *R, const char *vcf_path, const char *ped_path) {
@@ -237,8 +261,9 @@ static int run_cohort(run_t *R, const char *vcf_path, const char *ped_path) {
     int rc = HPGV_OK;
     sample_ids_t *ids = sample_ids_new((size_t)n_samples);
     for (int j = 0; j < n_samples; j++) sample_ids_put(ids, R->names[j], j);
-    switch (R->tool) {
-    case RUN_AGGREGATE: case RUN_STATS: case RUN_FILTER: case RUN_SPLIT: case RUN_GENOME: case RUN_GRM: {
+    const tool_traits_t *T = tool_of(R->tool);
+    switch (T->cohort) {
+    case COHORT_COLUMNS: {
         /* the engine scans the stats layout of all columns (get_variants_stats / get_sample_stats, hpgv_filter_text, hpgv_ibs_text, hpgv_grm_text); stats with a
          * PED: its phenotype groups, and its trios give the Mendelian errors (stats_runner.c:165-170,194-198) */
         rc = hpgv_set_stats_cohort(g_ctx, n_samples);
@@ -266,7 +291,7 @@ static int run_cohort(run_t *R, const char *vcf_path, const char *ped_path) {
         if (!rc) rc = set_trios(R, ids, 1);
         break;
     }
-    case RUN_TDT: case RUN_TDT_PERM: {
+    case COHORT_FAMILIES: {
         /* families in order of first appearance; father / mother = founders by sex (tdt.c:62-73);
          * counted children = rows with both parents named, affected, present in the VCF (tdt.c:139-148) */
         int32_t *fcol = (int32_t *)malloc(sizeof(int32_t) * (size_t)(ped->n + 1)), *mcol = (int32_t *)malloc(sizeof(int32_t) * (size_t)(ped->n + 1));
@@ -302,7 +327,7 @@ static int run_cohort(run_t *R, const char *vcf_path, const char *ped_path) {
         rc = hpgv_set_families(g_ctx, n_samples, nf, fcol, mcol, coff, ccol, csex);
         g_tdt_key.set = 0;
         if (rc) host_fail("hpgv_set_families", rc);
-        if (!rc && R->tool == RUN_TDT_PERM) {            /* the run's flip rows, once: a fair coin per family and permutation */
+        if (!rc && T->mperm) {                           /* the run's flip rows, once: a fair coin per family and permutation */
             uint8_t *flips = (uint8_t *)malloc((size_t)R->n_perms * (size_t)(nf > 0 ? nf : 1));
             if (!flips) rc = HPGV_ERR_NOMEM;
             if (!rc && (rc = hpgv_perm_flips_shuffle(nf, R->n_perms, R->perm_seed, flips))) host_fail("hpgv_perm_flips_shuffle", rc);
@@ -312,7 +337,7 @@ static int run_cohort(run_t *R, const char *vcf_path, const char *ped_path) {
         free(fcol); free(mcol); free(coff); free(ccol); free(csex); free(done);
         break;
     }
-    case RUN_CHISQ: case RUN_CHISQ_PERM: case RUN_FISHER: case RUN_VCF2EPI: case RUN_MODEL: case RUN_MODEL_PERM: case RUN_LOGISTIC: {
+    case COHORT_CASE_CONTROL: {
         int matched = 0;
         uint8_t *cond = cohort_conditions(R, ids, &matched);
         if (!cond) { rc = HPGV_ERR_NOMEM; break; }
@@ -326,21 +351,8 @@ static int run_cohort(run_t *R, const char *vcf_path, const char *ped_path) {
                 if (cond[j] == HPGV_COND_AFFECTED) R->epi_aff++; else R->epi_unaff++;
             }
         }
-        double *cov = NULL;
-        if (!rc && R->tool == RUN_LOGISTIC && R->covar) {             /* a cohort sample without a line of finite values leaves the cohort */
-            uint8_t *have = (uint8_t *)malloc((size_t)n_samples + 1);
-            cov = (double *)malloc(sizeof(double) * ((size_t)n_samples * (size_t)R->n_covar + 1));
-            if (!have || !cov) rc = HPGV_ERR_NOMEM;
-            if (!rc) rc = covar_table_match(R->covar, R->names, n_samples, R->n_covar, cov, (size_t)R->n_covar, have);
-            for (int j = 0; !rc && j < n_samples; j++) if (!have[j]) cond[j] = HPGV_COND_OTHER;
-            free(have);
-        }
-        if (R->tool == RUN_LOGISTIC) for (int j = 0; j < n_samples; j++) R->n_used += cond[j] == HPGV_COND_AFFECTED || cond[j] == HPGV_COND_UNAFFECTED;
-        if (!rc && (rc = hpgv_set_cohort(g_ctx, cond, n_samples))) host_fail("hpgv_set_cohort", rc);
-        g_assoc_key.set = 0;
-        if (!rc && cov && R->n_covar > 0 && (rc = hpgv_set_covariates(g_ctx, cov, n_samples, R->n_covar))) host_fail("hpgv_set_covariates", rc);
-        free(cov);
-        if (!rc && (R->tool == RUN_CHISQ_PERM || R->tool == RUN_MODEL_PERM)) {          /* the run's label rows, once: shuffles of the PED's conditions */
+        if (!rc) rc = assoc_cohort_install(R, cond, NULL);
+        if (!rc && T->mperm) {                                        /* the run's label rows, once: shuffles of the PED's conditions */
             uint8_t *labels = (uint8_t *)malloc((size_t)R->n_perms * (size_t)(n_samples > 0 ? n_samples : 1));
             if (!labels) rc = HPGV_ERR_NOMEM;
             if (!rc && (rc = hpgv_perm_labels_shuffle(cond, n_samples, R->n_perms, R->perm_seed, labels))) host_fail("hpgv_perm_labels_shuffle", rc);
@@ -357,9 +369,9 @@ static int run_cohort(run_t *R, const char *vcf_path, const char *ped_path) {
         }
         break;
     }
-    case RUN_LINEAR: {                                    /* the cohort: every sample with a trait and, with covariates, a line of finite ones */
+    case COHORT_TRAIT: {                                  /* the cohort: every sample with a trait and, with covariates, a line of finite ones */
         uint8_t *cond = (uint8_t *)malloc((size_t)n_samples + 1), *have = (uint8_t *)malloc((size_t)n_samples + 1);
-        double *y = (double *)calloc((size_t)n_samples + 1, sizeof(double)), *cov = NULL;
+        double *y = (double *)calloc((size_t)n_samples + 1, sizeof(double));
         if (!cond || !have || !y) rc = HPGV_ERR_NOMEM;
         for (int j = 0; !rc && j < n_samples; j++) cond[j] = HPGV_COND_OTHER;
         if (!rc && R->pheno) {                            /* the phenotype file's first value column */
@@ -375,18 +387,8 @@ static int run_cohort(run_t *R, const char *vcf_path, const char *ped_path) {
                 cond[j] = HPGV_COND_UNAFFECTED; y[j] = v;
             }
         }
-        if (!rc && R->covar) {
-            cov = (double *)malloc(sizeof(double) * ((size_t)n_samples * (size_t)R->n_covar + 1));
-            if (!cov) rc = HPGV_ERR_NOMEM;
-            if (!rc) rc = covar_table_match(R->covar, R->names, n_samples, R->n_covar, cov, (size_t)R->n_covar, have);
-            for (int j = 0; !rc && j < n_samples; j++) if (!have[j]) cond[j] = HPGV_COND_OTHER;
-        }
-        for (int j = 0; !rc && j < n_samples; j++) R->n_used += cond[j] == HPGV_COND_UNAFFECTED;
-        if (!rc && (rc = hpgv_set_cohort(g_ctx, cond, n_samples))) host_fail("hpgv_set_cohort", rc);
-        g_assoc_key.set = 0;
-        if (!rc && cov && R->n_covar > 0 && (rc = hpgv_set_covariates(g_ctx, cov, n_samples, R->n_covar))) host_fail("hpgv_set_covariates", rc);
-        if (!rc && (rc = hpgv_set_phenotype(g_ctx, y, n_samples))) host_fail("hpgv_set_phenotype", rc);
-        free(cond); free(have); free(y); free(cov);
+        if (!rc) rc = assoc_cohort_install(R, cond, y);
+        free(cond); free(have); free(y);
         break;
     }
     }
@@ -400,9 +402,9 @@ static int run_cohort(run_t *R, const char *vcf_path, const char *ped_path) {
     if (!rc && f->max_mendel_errors >= 0) rc = set_trios(R, ids, 0);
     if (!rc) (void)hpgv_set_text_filters(g_ctx, f->min_maf, f->max_missing, (long)f->max_mendel_errors);
     /* --inh-dom / --inh-rec scan the assoc layout: the tools that have not installed it get it from the PED (PHENO 2
-     * affected, 1 unaffected, as the assoc runner); vcf2epi keeps its own classes */
+     * affected, 1 unaffected, as the assoc runner); vcf2epi and the regressions keep their own classes */
     if (!rc && rec_filters_inheritance(R->rf)) {
-        if (!tool_chisq(R->tool) && !tool_model(R->tool) && R->tool != RUN_FISHER && R->tool != RUN_VCF2EPI && R->tool != RUN_LOGISTIC && R->tool != RUN_LINEAR) {
+        if (!tool_installs_assoc_cohort(R->tool)) {
             int matched = 0;
             uint8_t *cond = cohort_conditions(R, ids, &matched);
             if (!cond) rc = HPGV_ERR_NOMEM;
@@ -429,8 +431,8 @@ static int create_out(FILE **f, char **path, const char *prefix, const char *suf
 /* the tool's output files (split: its files as the records come).  The filter tool's .rejected is created empty without
  * save_rejected (filter_runner.c:63-68); stats: one file per phenotype (stats_runner.c:267-297), and its accumulator */
 static int run_outputs(run_t *R, const char *out_path) {
-    if ((R->clump && run_clump_new(R)) || (tool_perm(R->tool) && run_perm_new(R))) return HPGV_ERR_NOMEM;
-    if (R->tool == RUN_GENOME || R->tool == RUN_GRM) return run_genome_new(R);      /* (their files are written when the run ends: run_genome_write, run_grm_write) */
+    if ((R->clump && run_clump_new(R)) || (tool_of(R->tool)->mperm && run_perm_new(R))) return HPGV_ERR_NOMEM;
+    if (tool_of(R->tool)->pairs) return run_genome_new(R);      /* (their files are written when the run ends: run_genome_write, run_grm_write) */
     const char *suffix = R->tool == RUN_STATS ? ".stats-variants" : R->tool == RUN_FILTER ? (R->out_bgzf ? ".filtered.gz" : ".filtered") : "";
     int rc = R->tool == RUN_SPLIT ? HPGV_OK : create_out(&R->out, &R->path, out_path, suffix);
     if (!rc && R->tool == RUN_FILTER) rc = create_out(&R->out_rej, &R->path_rej, out_path, R->out_bgzf ? ".rejected.gz" : ".rejected");
@@ -452,33 +454,15 @@ static int run_outputs(run_t *R, const char *out_path) {
 /* the output files' headers, once the batches are allocated */
 static int run_headers(run_t *R) {
     FILE *out = R->out;
+    const tool_traits_t *T = tool_of(R->tool);
+    if (T->header) {                                     /* the sorted results: the first line, which the order check starts from */
+        if (T->file == RUN_TDT) tdt_write_output_header(out);
+        else if (T->file == RUN_CHISQ || T->file == RUN_FISHER) assoc_write_output_header((enum ASSOC_task)T->file, out);      /* (the reference's writers) */
+        else fprintf(out, "%s\n", T->header);
+        order_track_keep(&R->ord, T->header, strlen(T->header));
+        return HPGV_OK;
+    }
     switch (R->tool) {
-    case RUN_CHISQ: case RUN_CHISQ_PERM: case RUN_FISHER: {
-        assoc_write_output_header(tool_chisq(R->tool) ? CHI_SQUARE : FISHER, out);
-        const char *h = tool_chisq(R->tool) ? "#CHR\tPOS\tID\tA1\tC_A1\tC_U1\tF_A1\tF_U1\tA2\tC_A2\tC_U2\tF_A2\tF_U2\tOR\tCHISQ\tP-VALUE"
-                                             : "#CHR\tPOS\tID\tA1\tC_A1\tC_U1\tF_A1\tF_U1\tA2\tC_A2\tC_U2\tF_A2\tF_U2\tOR\tP-VALUE";
-        order_track_keep(&R->ord, h, strlen(h));
-        return HPGV_OK;
-    }
-    case RUN_MODEL: case RUN_MODEL_PERM: {
-        const char *h = "#CHR\tPOS\tID\tA1\tA2\tAFF\tUNAFF\tCHISQ_GENO\tP_GENO\tCHISQ_TREND\tP_TREND\tCHISQ_ALLELIC\tP_ALLELIC\tCHISQ_DOM\tP_DOM\tCHISQ_REC\tP_REC";
-        fprintf(out, "%s\n", h);
-        order_track_keep(&R->ord, h, strlen(h));
-        return HPGV_OK;
-    }
-    case RUN_LOGISTIC: {
-        const char *h = "#CHR\tPOS\tID\tA1\tA2\tNOBS\tBETA\tSE\tOR\tSTAT\tP\tITER";
-        fprintf(out, "%s\n", h);
-        order_track_keep(&R->ord, h, strlen(h));
-        return HPGV_OK;
-    }
-    case RUN_LINEAR: {
-        const char *h = "#CHR\tPOS\tID\tA1\tA2\tNOBS\tBETA\tSE\tSTAT\tP";
-        fprintf(out, "%s\n", h);
-        order_track_keep(&R->ord, h, strlen(h));
-        return HPGV_OK;
-    }
-    case RUN_TDT: case RUN_TDT_PERM: tdt_write_output_header(out); order_track_keep(&R->ord, "#CHR\tPOS\tID\tA1\tA2\tT\tU\tOR\tCHISQ\tP-VALUE", 38); return HPGV_OK;
     case RUN_VCF2EPI: {                                  /* room for the number of variants, then the class sizes (dataset_creator.c:186-193) */
         const uint32_t head[3] = {0, R->epi_aff, R->epi_unaff};
         return fwrite(head, sizeof(uint32_t), 3, out) != 3 ? HPGV_ERR_INVALID : HPGV_OK;
@@ -500,8 +484,7 @@ static int run_headers(run_t *R) {
         fprintf(out, "#CHROM\tPOS\tREF\tALT\tNUM_ALLELES\tALLELES_COUNT\tALLELES_FREQ\tGENOTYPES_COUNT\tMISS_AL\tMISS_GT\tMAF\tMEND_ER\tHWE_CHI2\tHWE_P\n");
         return HPGV_OK;
     case RUN_FILTER: return write_filter_header(out, R) || (R->save_rejected && write_filter_header(R->out_rej, R)) ? HPGV_ERR_INVALID : HPGV_OK;
-    case RUN_SPLIT: break;                               /* (each file gets the input's header when it is created) */
-    case RUN_GENOME: case RUN_GRM: break;                /* (no file yet) */
+    default: break;                                      /* split: each file gets the input's header when it is created; genome, grm: no file yet */
     }
     return HPGV_OK;
 }
@@ -549,7 +532,7 @@ static int run_pipeline(run_t *R, size_t batch_bytes) {
         file_writer_t fw;
         memset(&fw, 0, sizeof fw);
         /* a thread of its own writes the formatted result lines (write_batch) */
-        const int use_fw = (tool_sorts(R->tool) || tool_counts(R->tool)) && !g_env.no_writer_thread && file_writer_start(&fw, R->out);
+        const int use_fw = tool_writer_thread(R->tool) && !g_env.no_writer_thread && file_writer_start(&fw, R->out);
         int fmt_set = 0;
         pthread_t th[1 + RUN_ENGINES_MAX];
         int n_th = 0;
@@ -570,7 +553,13 @@ static int run_pipeline(run_t *R, size_t batch_bytes) {
             const double t0 = now_s();
             const run_batch_t *b = &P->bt[k];
             const char *bad = NULL;                      /* what went wrong */
-            switch (R->tool) {                           /* the batch's records to the tool's files, and what the run counts of them */
+            if (tool_of(R->tool)->lines) {               /* the batch's records to the tool's file, and what the run counts of them */
+                if (write_batch(R->out, b, fmt + (fmt_set ? RUN_FMT_BUFS / 2 : 0), n_fmt, &wpool, &R->ord, use_fw ? &fw : NULL)) bad = "cannot write the result file";
+                for (int i = 0; i < b->n_lines; i++) if (record_passes(b, i)) R->written++;
+                if (R->PM && !bad && run_perm_add(R, b)) bad = "out of memory for the permutation results";
+                if (R->CL && !bad && run_clump_add(R, b)) bad = "out of memory for the clumping candidates";
+                if (R->RS && !bad) run_stats_add(R, b);      /* (and the group files' lines: by this thread) */
+            } else switch (R->tool) {
             case RUN_FILTER:                             /* two fwrites (the batch's text is the partition now) */
                 if (write_filter_batch(R->out, R->save_rejected ? R->out_rej : NULL, b)) bad = "cannot write the result file";
                 R->written += b->n_pass; R->rejected += b->n_rej;
@@ -579,16 +568,9 @@ static int run_pipeline(run_t *R, size_t batch_bytes) {
                 if (write_split_batch(R, b)) bad = g_err;          /* (what split_file said) */
                 R->written += b->n_pass; R->skipped += b->n_skip;
                 break;
-            case RUN_CHISQ: case RUN_CHISQ_PERM: case RUN_FISHER: case RUN_TDT: case RUN_TDT_PERM: case RUN_VCF2EPI: case RUN_AGGREGATE: case RUN_STATS:
-            case RUN_MODEL: case RUN_MODEL_PERM: case RUN_LOGISTIC: case RUN_LINEAR:
-                if (write_batch(R->out, b, fmt + (fmt_set ? RUN_FMT_BUFS / 2 : 0), n_fmt, &wpool, &R->ord, use_fw ? &fw : NULL)) bad = "cannot write the result file";
-                for (int i = 0; i < b->n_lines; i++) if (record_passes(b, i)) R->written++;
-                if (tool_perm(R->tool) && !bad && run_perm_add(R, b)) bad = "out of memory for the permutation results";
-                if (R->CL && !bad && run_clump_add(R, b)) bad = "out of memory for the clumping candidates";
-                if (R->tool == RUN_STATS && !bad) run_stats_add(R, b);      /* (and the group files' lines: by this thread) */
-                break;
             case RUN_GENOME: run_genome_add(R, b); break;       /* no line per record: the records' terms, in file order */
             case RUN_GRM: run_grm_add(R, b); break;             /* no line per record: the used records are counted */
+            default: break;
             }
             fmt_set ^= use_fw;
             const double dt = now_s() - t0;
@@ -620,6 +602,7 @@ static int run_pipeline(run_t *R, size_t batch_bytes) {
 
 /* the outputs completed and closed, and the tool's last steps; rc: the run's so far */
 static int run_finish(run_t *R, int rc, const char *out_path) {
+    const tool_traits_t *T = tool_of(R->tool);
     if (R->tool == RUN_VCF2EPI && R->out && !rc) {       /* finally the real number of variants (dataset_creator.c:208-212) */
         const uint32_t nv = (uint32_t)R->written;
         if (fseek(R->out, 0, SEEK_SET) != 0 || fwrite(&nv, sizeof nv, 1, R->out) != 1) { snprintf(g_err, sizeof g_err, "cannot write %s", out_path); rc = HPGV_ERR_INVALID; }
@@ -631,7 +614,7 @@ static int run_finish(run_t *R, int rc, const char *out_path) {
     if (R->out_rej && fclose(R->out_rej) != 0 && !rc) { snprintf(g_err, sizeof g_err, "cannot write %s", R->path_rej); rc = HPGV_ERR_INVALID; }
     if (split_files_close(&R->SF, R->out_bgzf) && !rc) rc = HPGV_ERR_INVALID;
     for (int k = 0; R->gfd && k < R->n_groups; k++) if (R->gfd[k]) fclose(R->gfd[k]);
-    if (tool_sorts(R->tool)) {
+    if (T->sorts) {
         /* assoc_runner.c:255-261 (only a warning there); in order as written: nothing to do (HPGV_ALWAYS_SORT=1 reads the file
          * back and checks all the same) */
         const double t0 = now_s();
@@ -641,13 +624,13 @@ static int run_finish(run_t *R, int rc, const char *out_path) {
         R->t_sort = now_s() - t0;
     }
     if (R->tool == RUN_STATS && !rc) rc = run_stats_write(R, out_path);
-    if (tool_perm(R->tool)) {
+    if (T->mperm) {
         if (!rc && R->PM) rc = run_perm_write(R, out_path);
-        if (g_ctx) (void)(R->tool == RUN_TDT_PERM ? hpgv_set_tdt_flips(g_ctx, NULL, 0) : hpgv_set_perm_labels(g_ctx, NULL, 0));
+        if (g_ctx) (void)(T->cohort == COHORT_FAMILIES ? hpgv_set_tdt_flips(g_ctx, NULL, 0) : hpgv_set_perm_labels(g_ctx, NULL, 0));
         run_perm_free(R);
     }
-    if ((R->tool == RUN_LOGISTIC || R->tool == RUN_LINEAR) && g_ctx) (void)hpgv_set_covariates(g_ctx, NULL, 0, 0);
-    if (R->tool == RUN_LINEAR && g_ctx) (void)hpgv_set_phenotype(g_ctx, NULL, 0);
+    if (T->covar && g_ctx) (void)hpgv_set_covariates(g_ctx, NULL, 0, 0);
+    if (T->cohort == COHORT_TRAIT && g_ctx) (void)hpgv_set_phenotype(g_ctx, NULL, 0);
     if (R->CL) {
         if (!rc) rc = run_clump_write(R, out_path);
         R->n_clumps = R->CL->n_clumps; R->n_truncated = R->CL->n_truncated;      /* for hpgv_run_assoc_clump, past the store */
@@ -671,7 +654,7 @@ static int run_finish(run_t *R, int rc, const char *out_path) {
 static int run_file_held(run_t *R, const char *vcf_path, const char *ped_path, const char *out_path, size_t batch_bytes, long *n_variants_out);
 /* the run holds the record filters of hpgv_run_set_record_filters as they are when it starts (stats, split, genome and grm: none) */
 static int run_file(run_t *R, const char *vcf_path, const char *ped_path, const char *out_path, size_t batch_bytes, long *n_variants_out) {
-    R->rf = R->tool == RUN_STATS || R->tool == RUN_SPLIT || R->tool == RUN_GENOME || R->tool == RUN_GRM ? NULL : rec_filters_take();
+    R->rf = tool_of(R->tool)->rec_filters ? rec_filters_take() : NULL;
     int rc = HPGV_OK;
     if (rec_filters_inheritance(R->rf) && !ped_path) {                /* filter_options_parsing.c:149-153 */
         snprintf(g_err, sizeof g_err, "the inheritance filters (--inh-dom / --inh-rec) need a PED file (ped_path is NULL)");
@@ -691,7 +674,7 @@ static int run_file_held(run_t *R, const char *vcf_path, const char *ped_path, c
     if (rc) return rc;
     if (batch_bytes < (1u << 16)) batch_bytes = 1u << 16;
     const run_tool_t tool = R->tool; R->io_threads = default_io_threads();      /* the input: the PED (assoc, TDT, vcf2epi), the VCF's header */
-    if (!ped_path && (tool_chisq(tool) || tool_model(tool) || tool == RUN_LOGISTIC || tool == RUN_FISHER || tool_tdt(tool) || tool == RUN_VCF2EPI)) { snprintf(g_err, sizeof g_err, "this runner needs a PED file (ped_path is NULL)"); return HPGV_ERR_INVALID; }
+    if (!ped_path && tool_of(tool)->needs_ped) { snprintf(g_err, sizeof g_err, "this runner needs a PED file (ped_path is NULL)"); return HPGV_ERR_INVALID; }
     if (ped_path && (rc = ped_table_read(ped_path, &R->ped))) return rc;
     if (source_open(&R->rd.src, vcf_path)) { ped_table_free(&R->ped); snprintf(g_err, sizeof g_err, "cannot open VCF file %s", vcf_path); return HPGV_ERR_INVALID; }
     R->t_opened = now_s();
@@ -814,35 +797,10 @@ int hpgv_run_assoc_model(const char *vcf_path, const char *ped_path, const char 
     return run_file(&(run_t){ .tool = n_perms ? RUN_MODEL_PERM : RUN_MODEL, .filters = g_filters, .n_perms = n_perms, .perm_seed = seed }, vcf_path, ped_path, out_path, batch_bytes, n_variants_out);
 }
 
-/* the logistic regression's run: the covariate file read and checked before the engine starts, then RUN_MODEL's pipeline with
- * hpgv_assoc_logistic_text as its engine call */
-int hpgv_run_assoc_logistic(const char *vcf_path, const char *ped_path, const char *covar_path, int n_covar, const char *out_path,
-                            size_t batch_bytes, long *n_variants_out, long *n_samples_used_out) {
-    if (n_samples_used_out) *n_samples_used_out = 0;
-    if (run_args(n_variants_out, vcf_path && ped_path && out_path, "vcf_path, ped_path and out_path must not be NULL")) return HPGV_ERR_INVALID;
-    if (n_covar < 0 || (n_covar > 0 && !covar_path)) { snprintf(g_err, sizeof g_err, "n_covar %d: not negative, and 0 without a covariate file", n_covar); return HPGV_ERR_INVALID; }
-    covar_table_t T;
-    memset(&T, 0, sizeof T);
-    int use = 0;
-    if (covar_path) {
-        const int rc0 = covar_table_read(covar_path, &T);
-        if (rc0) return rc0;
-        if ((use = covar_table_columns(&T, n_covar)) < 0) { covar_table_free(&T); return HPGV_ERR_INVALID; }
-    }
-    run_t R = { .tool = RUN_LOGISTIC, .filters = g_filters, .covar = covar_path ? &T : NULL, .n_covar = use };
-    const int rc = run_file(&R, vcf_path, ped_path, out_path, batch_bytes, n_variants_out);
-    if (n_samples_used_out && !rc) *n_samples_used_out = R.n_used;
-    covar_table_free(&T);
-    return rc;
-}
-
-/* the linear regression's run: the phenotype and covariate files read and checked before the engine starts, then RUN_LOGISTIC's
- * pipeline with hpgv_assoc_linear_text as its engine call */
-int hpgv_run_assoc_linear(const char *vcf_path, const char *ped_path, const char *pheno_path, const char *covar_path, int n_covar,
+/* the regressions' run: n_covar checked, the phenotype file (linear; NULL: the PED's sixth column), then the covariate file (NULL: none),
+ * read and checked before the engine starts; then RUN_MODEL's pipeline with the tool's own engine call */
+static int run_regression(run_tool_t tool, const char *vcf_path, const char *ped_path, const char *pheno_path, const char *covar_path, int n_covar,
                           const char *out_path, size_t batch_bytes, long *n_variants_out, long *n_samples_used_out) {
-    if (n_samples_used_out) *n_samples_used_out = 0;
-    if (run_args(n_variants_out, vcf_path && out_path, "vcf_path and out_path must not be NULL")) return HPGV_ERR_INVALID;
-    if (!ped_path && !pheno_path) { snprintf(g_err, sizeof g_err, "the trait needs a PED file or a phenotype file (ped_path and pheno_path are NULL)"); return HPGV_ERR_INVALID; }
     if (n_covar < 0 || (n_covar > 0 && !covar_path)) { snprintf(g_err, sizeof g_err, "n_covar %d: not negative, and 0 without a covariate file", n_covar); return HPGV_ERR_INVALID; }
     covar_table_t T, P;
     memset(&T, 0, sizeof T); memset(&P, 0, sizeof P);
@@ -850,12 +808,27 @@ int hpgv_run_assoc_linear(const char *vcf_path, const char *ped_path, const char
     if (pheno_path && !(rc = covar_table_read(pheno_path, &P)) && covar_table_columns(&P, 1) < 0) rc = HPGV_ERR_INVALID;
     if (!rc && covar_path && !(rc = covar_table_read(covar_path, &T)) && (use = covar_table_columns(&T, n_covar)) < 0) rc = HPGV_ERR_INVALID;
     if (!rc) {
-        run_t R = { .tool = RUN_LINEAR, .filters = g_filters, .covar = covar_path ? &T : NULL, .n_covar = use, .pheno = pheno_path ? &P : NULL };
+        run_t R = { .tool = tool, .filters = g_filters, .covar = covar_path ? &T : NULL, .n_covar = use, .pheno = pheno_path ? &P : NULL };
         rc = run_file(&R, vcf_path, ped_path, out_path, batch_bytes, n_variants_out);
         if (n_samples_used_out && !rc) *n_samples_used_out = R.n_used;
     }
     covar_table_free(&T); covar_table_free(&P);
     return rc;
+}
+
+int hpgv_run_assoc_logistic(const char *vcf_path, const char *ped_path, const char *covar_path, int n_covar, const char *out_path,
+                            size_t batch_bytes, long *n_variants_out, long *n_samples_used_out) {
+    if (n_samples_used_out) *n_samples_used_out = 0;
+    if (run_args(n_variants_out, vcf_path && ped_path && out_path, "vcf_path, ped_path and out_path must not be NULL")) return HPGV_ERR_INVALID;
+    return run_regression(RUN_LOGISTIC, vcf_path, ped_path, NULL, covar_path, n_covar, out_path, batch_bytes, n_variants_out, n_samples_used_out);
+}
+
+int hpgv_run_assoc_linear(const char *vcf_path, const char *ped_path, const char *pheno_path, const char *covar_path, int n_covar,
+                          const char *out_path, size_t batch_bytes, long *n_variants_out, long *n_samples_used_out) {
+    if (n_samples_used_out) *n_samples_used_out = 0;
+    if (run_args(n_variants_out, vcf_path && out_path, "vcf_path and out_path must not be NULL")) return HPGV_ERR_INVALID;
+    if (!ped_path && !pheno_path) { snprintf(g_err, sizeof g_err, "the trait needs a PED file or a phenotype file (ped_path and pheno_path are NULL)"); return HPGV_ERR_INVALID; }
+    return run_regression(RUN_LINEAR, vcf_path, ped_path, pheno_path, covar_path, n_covar, out_path, batch_bytes, n_variants_out, n_samples_used_out);
 }
 
 int hpgv_run_tdt(const char *vcf_path, const char *ped_path, const char *out_path, size_t batch_bytes, long *n_variants_out) {

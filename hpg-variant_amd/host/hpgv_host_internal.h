@@ -151,12 +151,52 @@ typedef struct {
  * RUN_LINEAR: the linear regression of a quantitative trait with covariates (hpgv_run_assoc_linear) */
 typedef enum { RUN_CHISQ = CHI_SQUARE, RUN_FISHER = FISHER, RUN_TDT, RUN_VCF2EPI, RUN_AGGREGATE, RUN_STATS, RUN_FILTER, RUN_SPLIT, RUN_CHISQ_PERM, RUN_TDT_PERM,
                RUN_MODEL, RUN_MODEL_PERM, RUN_GENOME, RUN_GRM, RUN_LOGISTIC, RUN_LINEAR } run_tool_t;
-static inline int tool_chisq(run_tool_t t) { return t == RUN_CHISQ || t == RUN_CHISQ_PERM; }   /* writes the chi-square file */
-static inline int tool_tdt(run_tool_t t) { return t == RUN_TDT || t == RUN_TDT_PERM; }         /* writes the TDT file */
-static inline int tool_model(run_tool_t t) { return t == RUN_MODEL || t == RUN_MODEL_PERM; }   /* writes the model tests' file */
-static inline int tool_perm(run_tool_t t) { return t == RUN_CHISQ_PERM || t == RUN_TDT_PERM || t == RUN_MODEL_PERM; } /* writes <out>.mperm beside its file */
-static inline int tool_sorts(run_tool_t t) { return tool_chisq(t) || t == RUN_FISHER || tool_tdt(t) || tool_model(t) || t == RUN_LOGISTIC || t == RUN_LINEAR; }   /* output sorted afterwards */
-static inline int tool_counts(run_tool_t t) { return t == RUN_AGGREGATE || t == RUN_STATS; }   /* engine: hpgv_stats_text_groups */
+enum { RUN_N_TOOLS = RUN_LINEAR + 1 };                /* (index 0, the assoc task NONE, is no tool) */
+
+/* What a tool is: one row per tool, the one place that lists tools by property (tool_of).  A switch over the tools stays only
+ * where each does something of its own: engine_call, the cohort per stage, the line layouts.
+ *   cohort      what run_cohort installs: all columns (hpgv_set_stats_cohort), the PED's cases and controls, its families, or the
+ *               samples with a trait.  The second and the last install the assoc cohort themselves, and --inh-dom / --inh-rec scan
+ *               that one -- under RUN_LINEAR every sample with a trait, as unaffected; the others get the PED's conditions for them
+ *   covar       ... with the regressions' covariates;  needs_ped: refused without a PED (RUN_LINEAR: its entry asks for one or a phenotype file)
+ *   rec_filters runs under hpgv_run_set_record_filters;  sorts: result file sorted afterwards, `header` its first line, kept for the order check
+ *   mperm       <out>.mperm beside the file;  counts: the counters of hpgv_stats_text_groups;  lines: a line (vcf2epi: a row) per record
+ *   pairs       adds to the run's per-device sample-pair buffers, files written when the run ends
+ *   file        the tool whose result file, line for line, this one writes;  ints, dbls: elements per line of run_batch_t::ints, ::dbl */
+typedef enum { COHORT_COLUMNS, COHORT_CASE_CONTROL, COHORT_FAMILIES, COHORT_TRAIT } cohort_stage_t;
+typedef struct {
+    const char *name; cohort_stage_t cohort;
+    unsigned covar : 1, needs_ped : 1, rec_filters : 1, sorts : 1, mperm : 1, counts : 1, lines : 1, pairs : 1;
+    run_tool_t file; int ints, dbls; const char *header;
+} tool_traits_t;
+#define HDR_CHISQ "#CHR\tPOS\tID\tA1\tC_A1\tC_U1\tF_A1\tF_U1\tA2\tC_A2\tC_U2\tF_A2\tF_U2\tOR\tCHISQ\tP-VALUE"
+#define HDR_FISHER "#CHR\tPOS\tID\tA1\tC_A1\tC_U1\tF_A1\tF_U1\tA2\tC_A2\tC_U2\tF_A2\tF_U2\tOR\tP-VALUE"
+#define HDR_TDT "#CHR\tPOS\tID\tA1\tA2\tT\tU\tOR\tCHISQ\tP-VALUE"
+#define HDR_MODEL "#CHR\tPOS\tID\tA1\tA2\tAFF\tUNAFF\tCHISQ_GENO\tP_GENO\tCHISQ_TREND\tP_TREND\tCHISQ_ALLELIC\tP_ALLELIC\tCHISQ_DOM\tP_DOM\tCHISQ_REC\tP_REC"
+#define HDR_LOGISTIC "#CHR\tPOS\tID\tA1\tA2\tNOBS\tBETA\tSE\tOR\tSTAT\tP\tITER"
+#define HDR_LINEAR "#CHR\tPOS\tID\tA1\tA2\tNOBS\tBETA\tSE\tSTAT\tP"
+static const tool_traits_t g_tool_traits[RUN_N_TOOLS] = {
+    /*                    name          cohort               cov ped rf srt mp cnt ln pr  file           ints dbls header */
+    [RUN_CHISQ]      = { "chisq",      COHORT_CASE_CONTROL, 0, 1, 1, 1, 0, 0, 1, 0, RUN_CHISQ,      4, 3,  HDR_CHISQ },
+    [RUN_FISHER]     = { "fisher",     COHORT_CASE_CONTROL, 0, 1, 1, 1, 0, 0, 1, 0, RUN_FISHER,     4, 3,  HDR_FISHER },
+    [RUN_TDT]        = { "tdt",        COHORT_FAMILIES,     0, 1, 1, 1, 0, 0, 1, 0, RUN_TDT,        4, 3,  HDR_TDT },
+    [RUN_VCF2EPI]    = { "vcf2epi",    COHORT_CASE_CONTROL, 0, 1, 1, 0, 0, 0, 1, 0, RUN_VCF2EPI,    4, 3,  NULL },
+    [RUN_AGGREGATE]  = { "aggregate",  COHORT_COLUMNS,      0, 0, 1, 0, 0, 1, 1, 0, RUN_AGGREGATE,  4, 3,  NULL },
+    [RUN_STATS]      = { "stats",      COHORT_COLUMNS,      0, 0, 0, 0, 0, 1, 1, 0, RUN_STATS,      4, 3,  NULL },
+    [RUN_FILTER]     = { "filter",     COHORT_COLUMNS,      0, 0, 1, 0, 0, 0, 0, 0, RUN_FILTER,     4, 3,  NULL },
+    [RUN_SPLIT]      = { "split",      COHORT_COLUMNS,      0, 0, 0, 0, 0, 0, 0, 0, RUN_SPLIT,      4, 3,  NULL },
+    [RUN_CHISQ_PERM] = { "chisq_perm", COHORT_CASE_CONTROL, 0, 1, 1, 1, 1, 0, 1, 0, RUN_CHISQ,      4, 3,  HDR_CHISQ },
+    [RUN_TDT_PERM]   = { "tdt_perm",   COHORT_FAMILIES,     0, 1, 1, 1, 1, 0, 1, 0, RUN_TDT,        4, 3,  HDR_TDT },
+    [RUN_MODEL]      = { "model",      COHORT_CASE_CONTROL, 0, 1, 1, 1, 0, 0, 1, 0, RUN_MODEL,      8, 10, HDR_MODEL },
+    [RUN_MODEL_PERM] = { "model_perm", COHORT_CASE_CONTROL, 0, 1, 1, 1, 1, 0, 1, 0, RUN_MODEL,      8, 10, HDR_MODEL },
+    [RUN_GENOME]     = { "genome",     COHORT_COLUMNS,      0, 0, 0, 0, 0, 0, 0, 1, RUN_GENOME,     4, 3,  NULL },
+    [RUN_GRM]        = { "grm",        COHORT_COLUMNS,      0, 0, 0, 0, 0, 0, 0, 1, RUN_GRM,        4, 3,  NULL },
+    [RUN_LOGISTIC]   = { "logistic",   COHORT_CASE_CONTROL, 1, 1, 1, 1, 0, 0, 1, 0, RUN_LOGISTIC,   4, 6,  HDR_LOGISTIC },
+    [RUN_LINEAR]     = { "linear",     COHORT_TRAIT,        1, 0, 1, 1, 0, 0, 1, 0, RUN_LINEAR,     4, 6,  HDR_LINEAR },
+};
+static inline const tool_traits_t *tool_of(run_tool_t t) { return &g_tool_traits[t]; }
+static inline int tool_installs_assoc_cohort(run_tool_t t) { return tool_of(t)->cohort == COHORT_CASE_CONTROL || tool_of(t)->cohort == COHORT_TRAIT; }
+static inline int tool_writer_thread(run_tool_t t) { return tool_of(t)->sorts || tool_of(t)->counts; }      /* its lines may go through a thread of their own */
 
 typedef struct {
     struct run *run;                                     /* the run the batch belongs to */
@@ -229,7 +269,7 @@ typedef struct rec_filters rec_filters_t;
  * offset of record i's (host_sideout.c: rec_heads_*).  The arrays a store keeps beside it have H.cap elements, as head has */
 typedef struct { size_t *head; size_t n, cap; char *heads; size_t heads_len, heads_cap; } rec_heads_t;
 
-/* the permutation tools (tool_perm): what the run keeps for <out>.mperm -- the maxima merged over the batches (by the engine threads, under the
+/* the permutation tools (tool_traits_t::mperm): what the run keeps for <out>.mperm -- the maxima merged over the batches (by the engine threads, under the
  * pipeline's mutex) and, per written record in file order, "CHR\tPOS\tID", the observed statistic and its n_ge */
 typedef struct { double *tmax; double *t_obs; int32_t *n_ge; rec_heads_t H; } run_perm_t;
 

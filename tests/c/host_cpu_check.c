@@ -10,6 +10,8 @@
  *   host_cpu_check blocktable <file>  a bgzip file's block table by the team walk and by the serial walk
  *   host_cpu_check streams <file>     raw DEFLATE streams assembled by the tests, through hpgv_host_inflate_raw
  *   host_cpu_check heads              the record-head store of the runs' side outputs (rec_heads_*), self-checking
+ *   host_cpu_check traits             the tools' traits table, a line per tool, then every tool's per-line batch arrays written
+ *                                     through as wide as the table says, before and after they are rebuilt
  */
 #define _GNU_SOURCE
 #include <pthread.h>
@@ -344,9 +346,56 @@ static int cmd_heads(void) {
     return failures ? 1 : 0;
 }
 
+/* The tools' traits table (tool_of), a line per tool for the test to compare with its own copy; then, per tool, a batch of
+ * 64 KiB for 60 samples (the permutation tools: 3 permutations) whose per-line arrays are written through to the widths the table
+ * gives -- ints and dbl, and what the tool has beside them: n_ge and bmax, the counters, the dataset rows -- once as allocated and once
+ * after run_batch_reserve has rebuilt them for three times the lines: arrays that do not follow the rows, or did not grow, ASan
+ * reports.  (That an engine call writes no more per line than its row says is the GPU suite's: test_runner_traits_gpu.py.)  Neither
+ * call touches the device. */
+static void batch_write_through(run_batch_t *b, const tool_traits_t *T, int n_perms) {
+    const size_t m = (size_t)b->max_lines;
+    for (size_t k = 0; k < (size_t)T->ints * m; k++) b->ints[k] = (int32_t)k;
+    for (size_t k = 0; k < (size_t)T->dbls * m; k++) b->dbl[k] = (double)k;
+    for (size_t k = 0; k < m; k++) { b->line_off[k] = k; b->status[k] = 0; }
+    b->line_off[m] = m;
+    for (size_t k = 0; k < 10 * m; k++) b->field_off[k] = 0;
+    for (size_t k = 0; T->mperm && k < m; k++) b->n_ge[k] = 0;
+    for (int q = 0; T->mperm && q < n_perms; q++) b->bmax[q] = 0.0;
+    for (size_t k = 0; T->counts && k < 8 * m; k++) b->c8[k] = 0;
+    for (size_t k = 0; T->counts && k < 2 * m; k++) b->hw[k] = 0.0;
+    for (size_t k = 0; T->counts && k < m; k++) { b->merr[k] = 0; b->midx[k] = 0; }
+    for (size_t k = 0; k < m * (size_t)b->row_width; k++) b->rows[k] = 0;
+}
+static int cmd_traits(void) {
+    static const char *const stages[] = {"columns", "case-control", "families", "trait"};
+    for (int t = RUN_CHISQ; t < RUN_N_TOOLS; t++) {
+        const tool_traits_t *T = tool_of((run_tool_t)t);
+        printf("tool %d %s cohort=%s covar=%d ped=%d rec_filters=%d sorts=%d mperm=%d counts=%d lines=%d pairs=%d file=%s ints=%d dbls=%d installs=%d writer=%d header=%s\n",
+               t, T->name, stages[T->cohort], T->covar, T->needs_ped, T->rec_filters, T->sorts, T->mperm, T->counts, T->lines, T->pairs,
+               tool_of(T->file)->name, T->ints, T->dbls, tool_installs_assoc_cohort((run_tool_t)t), tool_writer_thread((run_tool_t)t), T->header ? T->header : "-");
+    }
+    for (int t = RUN_CHISQ; t < RUN_N_TOOLS; t++) {
+        const tool_traits_t *T = tool_of((run_tool_t)t);
+        run_t R;
+        memset(&R, 0, sizeof R);
+        R.tool = (run_tool_t)t; R.n_perms = T->mperm ? 3 : 0;
+        run_batch_t b;
+        int bad = run_batch_alloc(&b, &R, (size_t)1 << 16, 60, 0, 0) != 0;
+        const int m0 = b.max_lines;
+        if (!bad) batch_write_through(&b, T, R.n_perms);
+        bad = bad || run_batch_reserve(&b, 3 * m0) != 0;
+        if (!bad) batch_write_through(&b, T, R.n_perms);
+        CHECK(!bad && m0 == 65536 / 138 + 2 && b.max_lines >= 3 * m0, T->name);
+        run_batch_free(&b);
+    }
+    printf("%s\n", failures ? "TRAITS FAILED" : "TRAITS OK");
+    return failures ? 1 : 0;
+}
+
 int main(int argc, char **argv) {
     if (argc >= 2 && !strcmp(argv[1], "containers")) return cmd_containers();
     if (argc >= 2 && !strcmp(argv[1], "heads")) return cmd_heads();
+    if (argc >= 2 && !strcmp(argv[1], "traits")) return cmd_traits();
     if (argc >= 2 && !strcmp(argv[1], "pageedge")) return cmd_pageedge();
     if (argc >= 2 && !strcmp(argv[1], "inflate")) return cmd_inflate();
     if (argc >= 3 && !strcmp(argv[1], "streams")) return cmd_streams(argv[2]);

@@ -120,6 +120,59 @@ def test_record_head_store_grows_and_reads_back(exe, exe_plain, build):
     assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr
 
 
+_HDR_ASSOC = "#CHR\tPOS\tID\tA1\tC_A1\tC_U1\tF_A1\tF_U1\tA2\tC_A2\tC_U2\tF_A2\tF_U2\tOR\t%sP-VALUE"
+_HDR = {
+    "chisq": _HDR_ASSOC % "CHISQ\t", "fisher": _HDR_ASSOC % "", "tdt": "#CHR\tPOS\tID\tA1\tA2\tT\tU\tOR\tCHISQ\tP-VALUE",
+    "model": "#CHR\tPOS\tID\tA1\tA2\tAFF\tUNAFF\tCHISQ_GENO\tP_GENO\tCHISQ_TREND\tP_TREND\tCHISQ_ALLELIC\tP_ALLELIC\tCHISQ_DOM\tP_DOM\tCHISQ_REC\tP_REC",
+    "logistic": "#CHR\tPOS\tID\tA1\tA2\tNOBS\tBETA\tSE\tOR\tSTAT\tP\tITER", "linear": "#CHR\tPOS\tID\tA1\tA2\tNOBS\tBETA\tSE\tSTAT\tP",
+}
+# The tools' traits, written out a second time on purpose: an edit to a row of the table in hpgv_host_internal.h has to be made here too.
+# number, name: (cohort stage, covariates, PED required, takes hpgv_run_set_record_filters, sorted afterwards, .mperm, stats counters,
+# per-record lines, sample-pair buffers, the tool whose file it writes, ints per line, doubles per line)
+_TRAITS = {
+    (1, "chisq"): ("case-control", 0, 1, 1, 1, 0, 0, 1, 0, "chisq", 4, 3),
+    (2, "fisher"): ("case-control", 0, 1, 1, 1, 0, 0, 1, 0, "fisher", 4, 3),
+    (3, "tdt"): ("families", 0, 1, 1, 1, 0, 0, 1, 0, "tdt", 4, 3),
+    (4, "vcf2epi"): ("case-control", 0, 1, 1, 0, 0, 0, 1, 0, "vcf2epi", 4, 3),
+    (5, "aggregate"): ("columns", 0, 0, 1, 0, 0, 1, 1, 0, "aggregate", 4, 3),
+    (6, "stats"): ("columns", 0, 0, 0, 0, 0, 1, 1, 0, "stats", 4, 3),
+    (7, "filter"): ("columns", 0, 0, 1, 0, 0, 0, 0, 0, "filter", 4, 3),
+    (8, "split"): ("columns", 0, 0, 0, 0, 0, 0, 0, 0, "split", 4, 3),
+    (9, "chisq_perm"): ("case-control", 0, 1, 1, 1, 1, 0, 1, 0, "chisq", 4, 3),
+    (10, "tdt_perm"): ("families", 0, 1, 1, 1, 1, 0, 1, 0, "tdt", 4, 3),
+    (11, "model"): ("case-control", 0, 1, 1, 1, 0, 0, 1, 0, "model", 8, 10),
+    (12, "model_perm"): ("case-control", 0, 1, 1, 1, 1, 0, 1, 0, "model", 8, 10),
+    (13, "genome"): ("columns", 0, 0, 0, 0, 0, 0, 0, 1, "genome", 4, 3),
+    (14, "grm"): ("columns", 0, 0, 0, 0, 0, 0, 0, 1, "grm", 4, 3),
+    (15, "logistic"): ("case-control", 1, 1, 1, 1, 0, 0, 1, 0, "logistic", 4, 6),
+    (16, "linear"): ("trait", 1, 0, 1, 1, 0, 0, 1, 0, "linear", 4, 6),
+}
+
+
+@pytest.mark.parametrize("build", ["asan", "plain"])
+def test_tool_traits_table_and_batch_arrays_at_every_width(exe, exe_plain, build):
+    # the table row by row against the copy above, its derived properties against their definitions, and every tool's per-line
+    # arrays written through at the table's widths before and after they are rebuilt (host_cpu_check.c: cmd_traits)
+    r = _run(exe if build == "asan" else exe_plain, "traits")
+    assert r.returncode == 0 and "TRAITS OK" in r.stdout and "FAIL" not in r.stdout, r.stdout + r.stderr
+    assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr
+    got = {}
+    for line in r.stdout.splitlines():
+        if not line.startswith("tool "):
+            continue
+        head, header = line.split(" header=")
+        f = head.split(" ")
+        kv = dict(x.split("=") for x in f[3:])
+        row = (kv["cohort"],) + tuple(int(kv[k]) for k in ("covar", "ped", "rec_filters", "sorts", "mperm", "counts", "lines", "pairs")) \
+            + (kv["file"], int(kv["ints"]), int(kv["dbls"]))
+        got[(int(f[1]), f[2])] = row
+        assert int(kv["installs"]) == (row[0] in ("case-control", "trait")), line      # installs the assoc cohort itself
+        assert int(kv["writer"]) == (row[4] or row[6]), line                           # its lines may go through the writer thread
+        assert header == (_HDR[row[9]] if row[4] else "-"), line                       # a header kept for the order check: the sorted tools
+    assert got == _TRAITS
+    assert sum(l.startswith("PASS ") for l in r.stdout.splitlines()) == len(_TRAITS)
+
+
 def test_in_process_sort_equals_gnu_sort(exe, tmp_path):
     # assoc_runner.c:255-258 shells out to `sort -k1,1h -k2,2n`; the in-process replacement must give
     # the same file (C locale), header line included
