@@ -80,6 +80,8 @@ SYMBOLS = [
     "hpgv_ibs_pairs_dev", "hpgv_ibs_class_counts_dev", "hpgv_ibs_select_dev", "hpgv_ibs", "hpgv_ibs_text", "hpgv_ibs_terms", "hpgv_ibs_genome",
     "hpgv_grm_table_dev", "hpgv_grm_pairs_dev", "hpgv_grm", "hpgv_grm_text", "hpgv_grm_table", "hpgv_grm_frac_bits", "hpgv_grm_value", "hpgv_grm_plan_rows",
     "hpgv_grm_matrix_dev", "hpgv_pca_apply_dev", "hpgv_pca_dev", "hpgv_pca_block", "hpgv_pca_jacobi", "hpgv_pca_chol_inv",
+    "hpgv_score_table_dev", "hpgv_score_cols_dev", "hpgv_score", "hpgv_score_text", "hpgv_score_table", "hpgv_score_frac_bits", "hpgv_score_value",
+    "hpgv_score_plan_rows",
 ]
 
 # hpgv_ld_edge: {int32 a, b; double r2}, 16 bytes
@@ -90,6 +92,11 @@ IBS_PAIR = np.dtype([("i", np.int32), ("j", np.int32), ("c", IBS_COUNTS), ("pi_h
 # hpgv_grm_acc: {int64 sq, n}, 16 bytes; a row's table record of hpgv_grm_table_dev: {int8 hi[4], lo[4]}, 8 bytes
 GRM_ACC = np.dtype([("sq", np.int64), ("n", np.int64)])
 GRM_TAB = np.dtype([("hi", np.int8, 4), ("lo", np.int8, 4)])
+# "Score" of include/hpgv.h: the most scores per call, a row's flag bits, and hpgv_score_text's callback
+SCORE_MAX = 32
+SCORE_SKIP, SCORE_FLIP = 1, 2
+SCORE_WEIGH_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_int32),
+                             C.POINTER(C.c_double), C.POINTER(C.c_uint8))
 # hpgv_logistic_result: {double beta, se, stat, p; int32 n_obs, iters, status, pad}, 48 bytes
 LOGISTIC_RESULT = np.dtype([("beta", np.float64), ("se", np.float64), ("stat", np.float64), ("p", np.float64),
                             ("n_obs", np.int32), ("iters", np.int32), ("status", np.int32), ("pad", np.int32)])
@@ -297,6 +304,15 @@ def load():
     L.hpgv_grm_value.restype = C.c_double
     L.hpgv_grm_plan_rows.argtypes = [i32, i32, i32]
     L.hpgv_grm_matrix_dev.argtypes = [vp, vp, i32, i32, vp, sz, vp, vp]
+    L.hpgv_score_table_dev.argtypes = [vp, vp, i32, vp, vp, i32, vp, i32, vp, vp, sz, vp, vp]
+    L.hpgv_score_cols_dev.argtypes = [vp, vp, sz, i32, i32, vp, vp, sz, i32, vp, sz, vp]
+    L.hpgv_score.argtypes = [vp, vp, sz, i32, vp, vp, i32, vp, i32, vp, vp, sz, vp]
+    L.hpgv_score_text.argtypes = [vp, C.c_char_p, sz, i32, C.POINTER(i32), vp, vp, vp, SCORE_WEIGH_FN, vp, i32, vp, i32, vp, vp, sz, vp]
+    L.hpgv_score_table.argtypes = [i32, i32, i32, vp, i32, vp, i32, i32, vp, vp]
+    L.hpgv_score_frac_bits.argtypes = [C.c_double]
+    L.hpgv_score_value.argtypes = [C.c_int64, C.c_int64, i32]
+    L.hpgv_score_value.restype = C.c_double
+    L.hpgv_score_plan_rows.argtypes = [i32, i32, i32, i32]
     L.hpgv_pca_apply_dev.argtypes = [vp, vp, i32, sz, vp, i32, vp, vp]
     L.hpgv_pca_dev.argtypes = [vp, vp, i32, sz, i32, C.c_double, i32, u64, vp, vp, vp, C.POINTER(i32), C.POINTER(i32)]
     L.hpgv_pca_block.argtypes = [i32]
@@ -495,6 +511,23 @@ def run_grm(vcf_path, out_prefix, min_maf=0.01, batch_bytes=1 << 22):
     return n.value, k.value
 
 
+def run_score(vcf_path, score_path, out_path, impute=True, batch_bytes=1 << 22):
+    """hpgv_run_score of libhpgv_host.so (include/hpgv_host.h): the .profile of the VCF's samples for the score file's weights at
+    out_path.  Paths may be None (the call then fails with ERR_INVALID).  Returns (variants used, samples, unmatched records)."""
+    _build.build_host_lib()
+    H = C.CDLL(_build.HOSTLIB)
+    H.hpgv_run_score.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_size_t, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_long)]
+    H.hpgv_host_last_error.restype = C.c_char_p
+    n, k, u = C.c_long(0), C.c_long(0), C.c_long(0)
+    enc = lambda q: None if q is None else os.fsencode(q)
+    rc = H.hpgv_run_score(enc(vcf_path), enc(score_path), enc(out_path), 1 if impute else 0, batch_bytes, C.byref(n), C.byref(k), C.byref(u))
+    if rc != OK:
+        e = HpgvError("hpgv_run_score -> %d: %s" % (rc, (H.hpgv_host_last_error() or b"").decode(errors="replace")))
+        e.code = rc
+        raise e
+    return n.value, k.value, u.value
+
+
 def _run_pca_result(what, H, rc, counts):
     if rc != OK:
         e = HpgvError("%s -> %d: %s" % (what, rc, (H.hpgv_host_last_error() or b"").decode(errors="replace")))
@@ -688,6 +721,43 @@ def pca_chol_inv(G):
 def grm_plan_rows(n_variants, n_cols, n_cus):
     """hpgv_grm_plan_rows: rows per row range of hpgv_grm_pairs_dev's launch"""
     return int(load().hpgv_grm_plan_rows(int(n_variants), int(n_cols), int(n_cus)))
+
+
+def score_table(class4, w, frac_bits, flags, impute):
+    """hpgv_score_table on rows of class counts (n, >= 3), weights (n, n_scores) and flag bytes (n,): (used (n,) bool, limbs
+    (n, n_scores, 8) int8 = the limbs of qg then of qm, c (n, n_scores) int64).  No device needed."""
+    c4 = _np(class4, np.int32)
+    c4 = c4.reshape(-1, c4.shape[-1])
+    wv = _np(w, np.float64).reshape(len(c4), -1)
+    ns = wv.shape[1]
+    s = _np(frac_bits, np.int32).reshape(-1)
+    fl = _np(flags, np.uint8).reshape(-1)
+    L = load()
+    used, limbs, c = np.zeros(len(c4), bool), np.zeros((len(c4), ns, 8), np.int8), np.zeros((len(c4), ns), np.int64)
+    for k, row in enumerate(c4):
+        used[k] = L.hpgv_score_table(int(row[0]), int(row[1]), int(row[2]), _ptr(wv[k]), ns, _ptr(s), int(fl[k]), 1 if impute else 0,
+                                     _ptr(limbs[k]), _ptr(c[k])) != 0
+    return used, limbs, c
+
+
+def score_frac_bits(max_abs_w):
+    """hpgv_score_frac_bits: the largest frac_bits at which no weight at or below max_abs_w makes its row unused"""
+    return int(load().hpgv_score_frac_bits(float(max_abs_w)))
+
+
+def score_value(sums, cnst, frac_bits):
+    """hpgv_score_value, element-wise on int64 sums with one constant: float64 of the same shape.  No device needed."""
+    a = _np(sums, np.int64)
+    L = load()
+    out = np.zeros(a.size, np.float64)
+    for k, v in enumerate(a.reshape(-1)):
+        out[k] = L.hpgv_score_value(int(v), int(cnst), int(frac_bits))
+    return out.reshape(a.shape)
+
+
+def score_plan_rows(n_variants, n_cols, n_scores, n_cus):
+    """hpgv_score_plan_rows: rows per row range of hpgv_score_cols_dev's launch"""
+    return int(load().hpgv_score_plan_rows(int(n_variants), int(n_cols), int(n_scores), int(n_cus)))
 
 
 def clump(p, edges, p1):
@@ -1104,6 +1174,37 @@ class Engine:
                                        _ptr(class4), d_acc))
         return _text_result(nl, max_lines, status=status, class4=class4)
 
+    def score(self, gt, w, flags, frac_bits, impute, d_acc, acc_pitch, d_const):
+        """hpgv_score: class4 (nv, 4) of the rows; their sums are ADDED to the device arrays d_acc ((n_scores + 2) x acc_pitch
+        int64) and d_const (n_scores + 1 int64), both zeroed by the caller: memset_dev."""
+        gt = _np(gt, np.uint8)
+        nv, pitch = gt.shape
+        wv = _np(w, np.float64).reshape(nv, -1)
+        s = _np(frac_bits, np.int32).reshape(-1)
+        fl = _np(flags, np.uint8).reshape(-1)
+        class4 = np.zeros((nv, 4), np.int32)
+        self._chk(self.L.hpgv_score(self.h, _ptr(gt), pitch, nv, _ptr(wv), _ptr(fl), len(s), _ptr(s), 1 if impute else 0, _ptr(class4), d_acc, acc_pitch,
+                                    d_const))
+        return class4
+
+    def score_text(self, text, weigh, n_scores, frac_bits, impute, d_acc, acc_pitch, d_const, max_lines=None):
+        """hpgv_score_text: score on VCF data lines.  weigh(text, n_lines, line_off, field_off, status, w, flags) is called once with
+        numpy views -- line_off (n_lines + 1,), field_off (n_lines, 10), status (n_lines,), and w (n_lines, n_scores) and flags
+        (n_lines,) to fill -- and returns 0 (or None) to go on.  status and class4 per line come back."""
+        text, max_lines, m, status, nl = _text_call(text, max_lines)
+        class4 = np.zeros((m, 4), np.int32)
+        s = _np(frac_bits, np.int32).reshape(-1)
+
+        def thunk(_user, _text, n, line_off, field_off, st, w, flags):
+            arr = np.ctypeslib.as_array
+            rc = weigh(text, n, arr(line_off, (n + 1,)), arr(field_off, (n, 10)), arr(st, (n,)), arr(w, (n, int(n_scores))), arr(flags, (n,)))
+            return int(rc or 0)
+
+        cb = SCORE_WEIGH_FN(thunk)
+        self._chk(self.L.hpgv_score_text(self.h, text, len(text), max_lines, C.byref(nl), None, None, _ptr(status), cb, None, int(n_scores), _ptr(s),
+                                         1 if impute else 0, _ptr(class4), d_acc, acc_pitch, d_const))
+        return _text_result(nl, max_lines, status=status, class4=class4)
+
     def ibs_select(self, d_counts, n_cols, E, min_pi_hat, cap=None):
         """hpgv_ibs_select_dev on device records: the pairs with PI_HAT >= min_pi_hat as an IBS_PAIR array sorted by (i, j).  Without
         cap the call is repeated once with room when the first list was too short; with it, (pairs or None, count) comes back."""
@@ -1433,6 +1534,14 @@ class Engine:
 
     def grm_pairs_dev(self, d_gt, pitch, n_variants, n_cols, d_tab, d_acc, d_skip=None, stream=None):
         self._chk(self.L.hpgv_grm_pairs_dev(self.h, d_gt, pitch, n_variants, n_cols, d_skip, d_tab, d_acc, stream))
+
+    def score_table_dev(self, d_class4, n_variants, d_w, d_flags, frac_bits, impute, d_skip, d_tab, tab_pitch, d_const, stream=None, n_scores=None):
+        s = _np(frac_bits, np.int32).reshape(-1)
+        self._chk(self.L.hpgv_score_table_dev(self.h, d_class4, n_variants, d_w, d_flags, len(s) if n_scores is None else int(n_scores), _ptr(s),
+                                              1 if impute else 0, d_skip, d_tab, tab_pitch, d_const, stream))
+
+    def score_cols_dev(self, d_gt, pitch, n_variants, n_cols, d_tab, tab_pitch, n_scores, d_acc, acc_pitch, d_skip=None, stream=None):
+        self._chk(self.L.hpgv_score_cols_dev(self.h, d_gt, pitch, n_variants, n_cols, d_skip, d_tab, tab_pitch, int(n_scores), d_acc, acc_pitch, stream))
 
     def grm_matrix_dev(self, d_acc, n_cols, frac_bits, d_A, lda, d_n_empty, stream=None):
         self._chk(self.L.hpgv_grm_matrix_dev(self.h, d_acc, n_cols, int(frac_bits), d_A, lda, d_n_empty, stream))

@@ -136,6 +136,14 @@ static int engine_call(run_t *R, run_batch_t *b, const char **what, int *again) 
     case RUN_GRM: { *what = "hpgv_grm_text";               /* the same dealing, into that device's pair sums */
         hpgv_ibs_counts *d_acc = NULL;
         hpgv_ctx *ctx = run_genome_device(R, b, &d_acc);
+        if (R->score) {                                  /* a score run: the plan weighs the lines, the sums and the constants lie in one buffer */
+            *what = "hpgv_score_text";
+            const run_score_t *S = R->score;
+            const size_t pitch = run_score_acc_pitch(R);
+            int64_t *acc = (int64_t *)d_acc;
+            return hpgv_score_text(ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status, run_score_weigh, R->score, S->n_scores, S->frac_bits,
+                                   S->impute, b->ints, acc, pitch, acc + ((size_t)S->n_scores + 2) * pitch);
+        }
         return hpgv_grm_text(ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status, R->frac_bits, R->min_maf, b->ints, (hpgv_grm_acc *)d_acc);
     }
     }
@@ -569,7 +577,7 @@ static int run_pipeline(run_t *R, size_t batch_bytes) {
                 R->written += b->n_pass; R->skipped += b->n_skip;
                 break;
             case RUN_GENOME: run_genome_add(R, b); break;       /* no line per record: the records' terms, in file order */
-            case RUN_GRM: run_grm_add(R, b); break;             /* no line per record: the used records are counted */
+            case RUN_GRM: if (!R->score) run_grm_add(R, b); break;      /* no line per record: the used records are counted (a score run: on the device) */
             default: break;
             }
             fmt_set ^= use_fw;
@@ -637,7 +645,7 @@ static int run_finish(run_t *R, int rc, const char *out_path) {
         run_clump_free(R);
     }
     if (R->GN && R->tool == RUN_GRM) {
-        if (!rc) rc = R->n_pcs ? run_pca_write(R, out_path) : run_grm_write(R, out_path);
+        if (!rc) rc = R->score ? run_score_write(R, out_path) : R->n_pcs ? run_pca_write(R, out_path) : run_grm_write(R, out_path);
     } else if (R->GN) {
         if (!rc) rc = run_genome_write(R, out_path);
         R->n_pairs = R->GN->n_pairs;                     /* for hpgv_run_genome, past the counts */
@@ -877,6 +885,25 @@ int hpgv_run_grm(const char *vcf_path, const char *out_prefix, double min_maf, s
     run_t R = { .tool = RUN_GRM, .filters = filters_off, .min_maf = min_maf, .frac_bits = frac_bits };
     const int rc = run_file(&R, vcf_path, NULL, out_prefix, batch_bytes, n_variants_out);
     if (n_samples_out && !rc) *n_samples_out = R.n_samples;
+    return rc;
+}
+
+/* allele scoring (include/hpgv.h "Score"; PLINK's --score): the per-sample sums of the score file's weights over the records it names,
+ * at out_path.  A RUN_GRM run with a score plan: the same dealing of batches to devices, hpgv_score_text in place of hpgv_grm_text,
+ * the devices' integers added when the run ends.  Neither filter setter is applied */
+int hpgv_run_score(const char *vcf_path, const char *score_path, const char *out_path, int impute, size_t batch_bytes,
+                   long *n_variants_out, long *n_samples_out, long *n_unmatched_out) {
+    if (n_samples_out) *n_samples_out = 0;
+    if (n_unmatched_out) *n_unmatched_out = 0;
+    if (run_args(n_variants_out, vcf_path && score_path && out_path, "vcf_path, score_path and out_path must not be NULL")) return HPGV_ERR_INVALID;
+    run_score_t S;
+    int rc = run_score_read(score_path, impute, &S);     /* before the engine starts: a bad file writes nothing */
+    if (rc) return rc;
+    run_t R = { .tool = RUN_GRM, .filters = filters_off, .score = &S };
+    rc = run_file(&R, vcf_path, NULL, out_path, batch_bytes, n_variants_out);
+    if (n_samples_out && !rc) *n_samples_out = R.n_samples;
+    if (n_unmatched_out && !rc) *n_unmatched_out = S.n_unmatched;
+    run_score_free(&S);
     return rc;
 }
 

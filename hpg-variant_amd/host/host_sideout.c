@@ -227,7 +227,9 @@ void run_clump_free(run_t *R) {
 }
 
 /* ---- sample relatedness: the pair counts of the run on its devices, the expected values' sums, and the file of pairs ---------- */
+size_t run_score_bytes(const run_t *R);
 static size_t genome_bytes(const run_t *R) {
+    if (R->score) return run_score_bytes(R);             /* a score run: its sums and constants, not n x n records */
     const size_t ns = (size_t)R->n_samples, b = ns * ns * sizeof(hpgv_ibs_counts);
     return b ? b : sizeof(hpgv_ibs_counts);
 }
@@ -431,6 +433,195 @@ int run_grm_write(run_t *R, const char *out_prefix) {
     hpgv_grm_acc *sum = NULL;
     int rc = run_grm_sum(R, &sum);
     if (!rc) rc = run_grm_files(R, out_prefix, sum);
+    free(sum);
+    return rc;
+}
+
+/* ---- allele scoring (include/hpgv.h "Score"): a GRM-shaped run with a score plan (run_t::score) -- the score file's ids in a hash,
+ *      the callback that weighs a batch's lines by them, the devices' sums added on the host, and the .profile.  The sums of a
+ *      device lie in the genome run's buffer of that device: (n_scores + 2) x acc_pitch int64, then the n_scores + 1 constants -- */
+size_t run_score_acc_pitch(const run_t *R) { return ((size_t)(R->n_samples > 0 ? R->n_samples : 1) + 1) / 2 * 2; }
+static size_t score_words(const run_t *R) { return ((size_t)R->score->n_scores + 2) * run_score_acc_pitch(R) + (size_t)R->score->n_scores + 1; }
+
+static uint64_t score_hash(const char *s, size_t n) {
+    uint64_t h = 0xCBF29CE484222325ull;                  /* FNV-1a */
+    for (size_t i = 0; i < n; i++) h = (h ^ (unsigned char)s[i]) * 0x100000001B3ull;
+    return h;
+}
+
+/* the line of the id s[0 .. n), or -1; add >= 0: the id goes in as line `add` when it is new (-2: it was there) */
+static long score_find(run_score_t *S, const char *s, size_t n, long add) {
+    for (size_t at = (size_t)score_hash(s, n) & S->mask; ; at = (at + 1) & S->mask) {
+        const long k = S->slot[at];
+        if (k < 0) { if (add >= 0) S->slot[at] = add; return -1; }
+        if (strlen(S->id[k]) == n && !memcmp(S->id[k], s, n)) return add >= 0 ? -2 : k;
+    }
+}
+
+void run_score_free(run_score_t *S) {
+    if (!S) return;
+    free(S->blob); free(S->id); free(S->allele); free(S->w); free(S->slot); free(S->name);
+    memset(S, 0, sizeof *S);
+}
+
+static int score_is_space(char c) { return c == ' ' || c == '\t' || c == '\r'; }
+
+/* the score file: whitespace-separated id, allele and 1 .. HPGV_SCORE_MAX weights per line, the same number on every line; a first
+ * line whose first token is ID, #ID or SNP names the columns.  frac_bits[k] = hpgv_score_frac_bits of column k's largest |w| */
+int run_score_read(const char *path, int impute, run_score_t *S) {
+    memset(S, 0, sizeof *S);
+    S->impute = impute != 0;
+    FILE *f = fopen(path, "rb");
+    if (!f) { snprintf(g_err, sizeof g_err, "cannot open score file %s", path); return HPGV_ERR_INVALID; }
+    size_t len = 0, cap = 1u << 16;
+    char *blob = (char *)malloc(cap + 1);
+    for (size_t got; blob && (got = fread(blob + len, 1, cap - len, f)) > 0; ) {
+        len += got;
+        if (len == cap) { char *nb = (char *)realloc(blob, (cap *= 2) + 1); if (!nb) { free(blob); } blob = nb; }
+    }
+    const int io_bad = ferror(f);
+    fclose(f);
+    if (!blob) return HPGV_ERR_NOMEM;
+    if (io_bad) { free(blob); snprintf(g_err, sizeof g_err, "cannot read score file %s", path); return HPGV_ERR_INVALID; }
+    blob[len] = 0;
+    S->blob = blob;
+    size_t n_lines = 1;
+    for (size_t i = 0; i < len; i++) n_lines += blob[i] == '\n';
+    S->id = (char **)calloc(n_lines, sizeof *S->id); S->allele = (char **)calloc(n_lines, sizeof *S->allele);
+    size_t slots = 16;
+    while (slots < 2 * n_lines) slots *= 2;
+    S->slot = (long *)malloc(slots * sizeof *S->slot); S->mask = slots - 1;
+    S->name = (char (*)[64])calloc(HPGV_SCORE_MAX, sizeof S->name[0]);
+    if (!S->id || !S->allele || !S->slot || !S->name) { run_score_free(S); return HPGV_ERR_NOMEM; }
+    for (size_t i = 0; i < slots; i++) S->slot[i] = -1;
+    int rc = HPGV_OK, first = 1;
+    double big[HPGV_SCORE_MAX] = { 0 };
+    char *tok[HPGV_SCORE_MAX + 3];
+    for (char *line = blob, *end = blob + len, *next; line < end && !rc; line = next) {
+        char *nl = (char *)memchr(line, '\n', (size_t)(end - line));
+        next = nl ? nl + 1 : end;
+        if (nl) *nl = 0;
+        int nt = 0;
+        for (char *c = line; *c; ) {
+            while (score_is_space(*c)) *c++ = 0;
+            if (!*c) break;
+            if (nt < HPGV_SCORE_MAX + 3) tok[nt] = c;
+            nt++;
+            while (*c && !score_is_space(*c)) c++;
+        }
+        if (nt == 0) continue;                           /* an empty line */
+        const long line_no = S->n + (S->have_header ? 2 : 1);
+        if (nt > HPGV_SCORE_MAX + 2) { snprintf(g_err, sizeof g_err, "%s: line %ld has %d weight columns, at most %d", path, line_no, nt - 2, HPGV_SCORE_MAX); rc = HPGV_ERR_INVALID; break; }
+        if (nt < 3) { snprintf(g_err, sizeof g_err, "%s: line %ld has %d columns: id, allele and at least one weight", path, line_no, nt); rc = HPGV_ERR_INVALID; break; }
+        if (first) {
+            first = 0;
+            S->n_scores = nt - 2;
+            S->w = (double *)malloc(n_lines * (size_t)S->n_scores * sizeof *S->w);
+            if (!S->w) { rc = HPGV_ERR_NOMEM; break; }
+            S->have_header = !strcmp(tok[0], "ID") || !strcmp(tok[0], "#ID") || !strcmp(tok[0], "SNP");
+            for (int k = 0; k < S->n_scores; k++) {
+                if (S->have_header) snprintf(S->name[k], sizeof S->name[k], "%.*s", (int)sizeof S->name[k] - 1, tok[2 + k]);
+                else snprintf(S->name[k], sizeof S->name[k], "SCORE%d", k + 1);
+            }
+            if (S->have_header) continue;
+        }
+        if (nt - 2 != S->n_scores) { snprintf(g_err, sizeof g_err, "%s: line %ld has %d weight columns, the first line %d", path, line_no, nt - 2, S->n_scores); rc = HPGV_ERR_INVALID; break; }
+        if (score_find(S, tok[0], strlen(tok[0]), S->n) == -2) { snprintf(g_err, sizeof g_err, "%s: line %ld: the id %.100s appears twice", path, line_no, tok[0]); rc = HPGV_ERR_INVALID; break; }
+        S->id[S->n] = tok[0]; S->allele[S->n] = tok[1];
+        for (int k = 0; k < S->n_scores; k++) {
+            char *e = NULL;
+            const double v = strtod(tok[2 + k], &e);
+            if (e == tok[2 + k] || *e || !isfinite(v)) { snprintf(g_err, sizeof g_err, "%s: line %ld: the weight %.100s is not a finite number", path, line_no, tok[2 + k]); rc = HPGV_ERR_INVALID; break; }
+            S->w[(size_t)S->n * (size_t)S->n_scores + (size_t)k] = v;
+            if (fabs(v) > big[k]) big[k] = fabs(v);
+        }
+        S->n++;
+    }
+    if (!rc && S->n == 0) { snprintf(g_err, sizeof g_err, "%s holds no line of weights", path); rc = HPGV_ERR_INVALID; }
+    for (int k = 0; k < S->n_scores && !rc; k++) S->frac_bits[k] = hpgv_score_frac_bits(big[k]);
+    if (rc) run_score_free(S);
+    return rc;
+}
+
+/* hpgv_score_text's callback (on the engine thread that made the call): a record takes part when its id is in the file and the
+ * file's allele is its ALT (byte for byte) or its REF (the row is flipped); a record with a ',' in ALT, with the id "." or an id
+ * that is not in the file is skipped; one whose allele is neither REF nor ALT is skipped and counted */
+int run_score_weigh(void *user, const char *text, int n_lines, const uint64_t *line_off, const uint32_t *field_off, const int32_t *status,
+                    double *w, uint8_t *flags) {
+    run_score_t *S = (run_score_t *)user;
+    long unmatched = 0;
+    for (int i = 0; i < n_lines; i++) {
+        const uint32_t *fo = field_off + 10 * (size_t)i;
+        flags[i] = HPGV_SCORE_SKIP;
+        if ((status[i] & 0xFF) == 1 || fo[5] == 0xFFFFFFFFu) continue;
+        const char *l = text + line_off[i];
+        const char *id = l + fo[2], *ref = l + fo[3], *alt = l + fo[4];
+        const size_t n_id = fo[3] - 1 - fo[2], n_ref = fo[4] - 1 - fo[3], n_alt = fo[5] - 1 - fo[4];
+        if (memchr(alt, ',', n_alt) || (n_id == 1 && id[0] == '.')) continue;
+        const long k = score_find(S, id, n_id, -1);
+        if (k < 0) continue;
+        const size_t n_a = strlen(S->allele[k]);
+        if (n_a == n_alt && !memcmp(S->allele[k], alt, n_alt)) flags[i] = 0;
+        else if (n_a == n_ref && !memcmp(S->allele[k], ref, n_ref)) flags[i] = HPGV_SCORE_FLIP;
+        else { unmatched++; continue; }
+        memcpy(w + (size_t)i * (size_t)S->n_scores, S->w + (size_t)k * (size_t)S->n_scores, (size_t)S->n_scores * sizeof *w);
+    }
+    if (unmatched) __atomic_fetch_add(&S->n_unmatched, unmatched, __ATOMIC_RELAXED);
+    return 0;
+}
+
+size_t run_score_bytes(const run_t *R) { return score_words(R) * sizeof(int64_t); }
+
+/* the devices' sums and constants added as integers (any order): *sum_out, score_words of them, the caller's to free */
+int run_score_sum(run_t *R, int64_t **sum_out) {
+    run_genome_t *G = R->GN;
+    const size_t words = score_words(R);
+    int rc = HPGV_OK;
+    int64_t *sum = (int64_t *)calloc(words, sizeof *sum), *part = G->n_dev > 1 ? (int64_t *)malloc(words * sizeof *part) : NULL;
+    if (!sum || (G->n_dev > 1 && !part)) rc = HPGV_ERR_NOMEM;
+    for (int d = 0; d < G->n_dev && !rc; d++) {
+        int64_t *to = d == 0 ? sum : part;
+        if ((rc = hpgv_memcpy_d2h(G->ctx[d], to, G->d_counts[d], words * sizeof *to, NULL))) { host_fail("hpgv_memcpy_d2h", rc); break; }
+        for (size_t k = 0; d > 0 && k < words; k++) sum[k] += part[k];
+    }
+    free(part);
+    if (rc) { free(sum); sum = NULL; }
+    *sum_out = sum;
+    return rc;
+}
+
+static void score_put_g8(FILE *f, double v) {
+    if (v != v) fputs("\tnan", f);                       /* (whichever NaN) */
+    else fprintf(f, "\t%.8g", v);
+}
+
+/* the .profile: "#FID IID CNT CNT2" and <name>_SUM, <name>_AVG per score, one line per sample in VCF order */
+int run_score_write(run_t *R, const char *out_path) {
+    const run_score_t *S = R->score;
+    const size_t ns = (size_t)R->n_samples, pitch = run_score_acc_pitch(R);
+    const int K = S->n_scores;
+    int64_t *sum = NULL;
+    int rc = run_score_sum(R, &sum);
+    if (rc) return rc;
+    const int64_t *cnst = sum + ((size_t)K + 2) * pitch, n_used = cnst[K];
+    R->written = (long)n_used;
+    FILE *f = fopen(out_path, "wb");
+    if (!f) { snprintf(g_err, sizeof g_err, "cannot create %s", out_path); free(sum); return HPGV_ERR_INVALID; }
+    setvbuf(f, NULL, _IOFBF, 1u << 20);
+    fputs("#FID\tIID\tCNT\tCNT2", f);
+    for (int k = 0; k < K; k++) fprintf(f, "\t%s_SUM\t%s_AVG", S->name[k], S->name[k]);
+    fputc('\n', f);
+    for (size_t j = 0; j < ns; j++) {
+        const int64_t n = S->impute ? n_used : sum[(size_t)K * pitch + j];
+        fprintf(f, "%s\t%s\t%lld\t%lld", R->names[j], R->names[j], (long long)(2 * n), (long long)sum[((size_t)K + 1) * pitch + j]);
+        for (int k = 0; k < K; k++) {
+            const double v = hpgv_score_value(sum[(size_t)k * pitch + j], cnst[k], S->frac_bits[k]);
+            score_put_g8(f, v);
+            score_put_g8(f, v / (2.0 * (double)n));
+        }
+        fputc('\n', f);
+    }
+    if ((ferror(f) != 0) | (fclose(f) != 0)) { snprintf(g_err, sizeof g_err, "cannot write %s", out_path); rc = HPGV_ERR_INVALID; }
     free(sum);
     return rc;
 }

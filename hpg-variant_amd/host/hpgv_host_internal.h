@@ -291,6 +291,16 @@ typedef struct {
     long n_pairs;                                        /* pairs written to the file */
 } run_genome_t;
 
+/* allele scoring (hpgv_run_score): the score file -- n lines of id, allele and n_scores weights, the ids in an open-addressing hash
+ * (slot: a line or -1) --, the scale of every column, and the records whose allele matched neither REF nor ALT, counted by the
+ * engine threads.  The strings lie in blob */
+typedef struct {
+    int n_scores, impute, have_header; int frac_bits[HPGV_SCORE_MAX];
+    long n; char **id, **allele; double *w; long *slot; size_t mask; char *blob;
+    char (*name)[64];                                    /* the columns' names */
+    long n_unmatched;
+} run_score_t;
+
 /* the covariate file of the logistic run (host_covar.c): n lines of ncols value columns, iid[i] the line's second id (in blob),
  * val[i * ncols + k] NaN where the text is not a finite number */
 typedef struct { int n, ncols, ncols_set; char **iid; double *val; char *blob; } covar_table_t;
@@ -316,6 +326,7 @@ typedef struct run {
     double min_pi_hat; run_genome_t *GN; long n_pairs;   /* RUN_GENOME: the threshold, the run's counts, the pairs written (kept past them) */
     double min_maf; int frac_bits;                       /* RUN_GRM: the rows' rule and hpgv_grm_frac_bits of it; its sums lie in GN's buffers (16-byte records too) */
     int n_pcs, write_grm, n_iter;                        /* RUN_GRM with n_pcs >= 1 (hpgv_run_pca): pairs to write, the .grm.* files too, the sweeps done (kept past the run) */
+    run_score_t *score;                                  /* RUN_GRM with a score plan (hpgv_run_score): GN's buffers hold the score sums, the run ends in a .profile */
     const covar_table_t *covar; int n_covar; long n_used; /* RUN_LOGISTIC, RUN_LINEAR: the covariate file (NULL: none) and its columns in use; the cohort samples that stayed */
     const covar_table_t *pheno;                          /* RUN_LINEAR: the phenotype file (NULL: the PED's sixth column) */
     double t_opened, t_header, t_sort;
@@ -468,6 +479,13 @@ int run_grm_write(run_t *R, const char *out_prefix);
 int run_grm_sum(run_t *R, hpgv_grm_acc **sum_out);       /* the devices' records added on the host; run_grm_files: the three files of the sum */
 int run_grm_files(run_t *R, const char *out_prefix, const hpgv_grm_acc *sum);
 int grm_put(const char *prefix, const char *suffix, const void *data, size_t bytes);      /* <prefix><suffix> written whole */
+int run_score_read(const char *path, int impute, run_score_t *S);      /* the score file; run_score_free: what it allocated */
+void run_score_free(run_score_t *S);
+int run_score_weigh(void *user, const char *text, int n_lines, const uint64_t *line_off, const uint32_t *field_off, const int32_t *status,
+                    double *w, uint8_t *flags);          /* hpgv_score_text's callback, user: the run's run_score_t */
+size_t run_score_acc_pitch(const run_t *R);              /* int64 per plane of a device's sums; the constants lie behind the n_scores + 2 planes */
+int run_score_sum(run_t *R, int64_t **sum_out);          /* the devices' sums and constants added on the host; run_score_write: the .profile of them */
+int run_score_write(run_t *R, const char *out_path);
 int run_pca_write(run_t *R, const char *out_prefix);     /* host_pca.c: the GRM run's end when principal components are asked for */
 int run_stats_new(run_t *R);
 void run_stats_add(run_t *R, const run_batch_t *b);      /* and the batch's lines to the per-phenotype files */

@@ -751,6 +751,82 @@ int  hpgv_pca_dev(hpgv_ctx *ctx, const double *d_A, int n, size_t lda, int k, do
                   double *eigval /* host, k */, double *vec /* host, n x k row-major */, double *resid /* host, k */,
                   int *n_iter, int *converged);
 
+/* ---- Score: per-SAMPLE sums of per-variant weights times ALT counts (PLINK's --score; no reference counterpart): polygenic
+ *      scores; with several weight columns the projection of a cohort onto principal-component loadings; with 0 / 1 weights a
+ *      burden count per sample.  Parity with PLINK is UNPINNED, as for "IBS" and "GRM": what follows is this project's definition.
+ *
+ *      A score is one sum over every variant of a file -- across batches, engine threads and devices -- so, as the GRM is, it is
+ *      quantised BY DEFINITION and summed as integers: 32-bit fixed-point weights in four i8 limbs on the matrix cores
+ *      (csrc/hpgv_score_kernels.h).  The sums do not depend on tile order, row ranges, batches, streams or devices.
+ *
+ *      Genotype class g (0 / 1 / 2 ALT alleles), validity and pads of an HPGV8 byte are exactly those of "IBS"; n0, n1, n2 are a
+ *      row's class counts over the columns below n_cols (hpgv_ibs_class_counts_dev).  Up to HPGV_SCORE_MAX = 32 scores per call
+ *      (hpgv_pca_dev writes up to 24 components).
+ *
+ *      Inputs.  Per score k a frac_bits s_k in [-900, 900].  Per row the weights w[row * n_scores + k] (f64) and a flag byte:
+ *      bit 0 = skip; bit 1 = flip, the weight names REF and the row contributes w (2 - g).  Per call one `impute` switch: != 0 is
+ *      PLINK's default mean imputation, 0 its no-mean-imputation.
+ *
+ *      A row is USED iff it is not skipped, T = 2 (n0 + n1 + n2) > 0, every weight is finite, and every |q| <= 2^28 below.  An
+ *      unused row takes no part in anything.  With p = (double)(n1 + 2 n2) / (double)T, per used row and score, f64 without
+ *      contraction, rint to nearest with ties to even:
+ *          q = rint(ldexp(w, s))
+ *          not flipped:  qg = q    c = 0     qm = impute ? rint(ldexp(w * (2.0 * p), s))              : 0
+ *          flipped:      qg = -q   c = 2 q   qm = impute ? rint(ldexp(w * (2.0 * (1.0 - p)), s)) - 2 q : -2 q
+ *      A used row contributes c + qg g to column j on a called byte and c + qm on a missing one: a flipped called byte gives
+ *      q (2 - g); a missing byte with imputation the imputed dosage times the weight; a missing byte without imputation exactly 0,
+ *      flipped or not.  |qg|, |qm| and |c| are at most 2^30.  qg and qm are split into four BALANCED i8 limbs as the GRM splits q
+ *      into two: l_0 = (int8)(v & 0xFF), v <- (v - l_0) / 256, and so on; v = l_0 + 256 l_1 + 65536 l_2 + 2^24 l_3 with the three
+ *      low limbs in [-128, 127] and the top limb the rest (in [-64, 64]).
+ *
+ *      Accumulated, all int64 and exact:
+ *          sum_k[j]    = sum over used rows of (qg_k g_j where j is called, qm_k where it is missing)
+ *          const_k     = sum over used rows of c_k
+ *          n_called[j] = used rows where j is called        n_alt[j] = sum over used rows of g_j        n_used = used rows
+ *      Per sample:
+ *          value_k[j] = ldexp((double)(sum_k[j] + const_k), -s_k)          (hpgv_score_value)
+ *          avg_k[j]   = value_k[j] / (2.0 * (double)(impute ? n_used : n_called[j]))      (the IEEE result for 0)
+ *
+ *      Quantisation bound: |q 2^-s - w| <= 2^-(s+1), and likewise for the imputed term, so each used row moves a column's value
+ *      by at most 2^-s (g <= 2) from the unquantised term w g (w (2 - g), w 2 p, w 2 (1 - p)).  hpgv_score_frac_bits(max_abs_w)
+ *      returns 28 - e where frexp(max_abs_w) = m 2^e, 0.5 <= m < 1: |w| <= max_abs_w < 2^e gives |w 2^s| < 2^28, so no weight at or
+ *      below max_abs_w trips the |q| rule (for max_abs_w below 2^928: above it the result is clamped to -900).
+ *
+ *      The table of a call's rows is LIMB-PLANE-MAJOR: int8 tab[(k * 8 + l) * tab_pitch + row], l = 0 .. 3 the limbs of qg_k and
+ *      l = 4 .. 7 those of qm_k; tab_pitch a multiple of 64 and >= n_variants, zeros from n_variants to tab_pitch and for an
+ *      unused row.  An operand of the matrix cores -- 16 rows of (score, limb) x 64 variants -- is then plain 16-byte loads.  Row 0
+ *      of the table is row 0 of the matrix it is used with: a piece of a matrix has a table of its own.
+ *
+ *      Out of scope: dosage or probability input; multi-allelic records; PLINK's `center` and `variance-standardize` modifiers;
+ *      computing SNP loadings from a PCA (a second pass shaped like the linear regression's product: the follow-up); a group form
+ *      of the batch calls; more than 32 scores per call. */
+#define HPGV_SCORE_MAX 32
+#define HPGV_SCORE_SKIP 1                                                                /* flag bits of a row */
+#define HPGV_SCORE_FLIP 2
+/* d_class4 and d_skip (IN-OUT, required) as hpgv_grm_table_dev's: a row that comes in != 0 is unused, and the call sets
+ * d_skip[row] = 1 for every unused row.  d_w: n_variants x n_scores doubles; d_flags: one byte per row; frac_bits: HOST array of
+ * n_scores.  d_tab: 8 n_scores planes of tab_pitch bytes, every byte written (layout above).  d_const: int64[n_scores + 1]; the
+ * call ADDS const_k of these rows to d_const[k] and their n_used to d_const[n_scores] with relaxed device-scope 64-bit atomics
+ * (the caller zeroes it before the first call).  One lane per row; the table is bit for bit hpgv_score_table's.  tab_pitch == 0
+ * succeeds.  HPGV_ERR_INVALID for n_variants < 0, n_scores outside 1 .. 32, a frac_bits outside [-900, 900], tab_pitch not a
+ * multiple of 64 or < n_variants, a NULL pointer, d_class4 or d_tab not 16-byte, d_w or d_const not 8-byte aligned.  A non-finite
+ * weight makes its row unused.  Asynchronous on `stream`. */
+int  hpgv_score_table_dev(hpgv_ctx *ctx, const int32_t *d_class4, int n_variants, const double *d_w, const uint8_t *d_flags,
+                          int n_scores, const int *frac_bits, int impute, uint8_t *d_skip /* in-out, required */,
+                          int8_t *d_tab, size_t tab_pitch, int64_t *d_const, void *stream);
+/* Matrix, d_skip, refusals, streams and "profile" timing as hpgv_ibs_pairs_dev; d_tab and d_skip as hpgv_score_table_dev left
+ * them (with d_skip NULL every row takes part with its table: an unused row would then count in n_called and n_alt).  The call
+ * ADDS sum_k[j] of these rows to d_acc[k * acc_pitch + j] for k < n_scores, n_called[j] to plane n_scores and n_alt[j] to plane
+ * n_scores + 1, j < n_cols, with relaxed device-scope 64-bit integer atomics -- calls on pieces of a matrix, on several streams
+ * and from several threads accumulate into one buffer -- and touches no other element; the caller zeroes the (n_scores + 2) x
+ * acc_pitch int64 before the first call.  No floating-point atomics.  n_variants == 0 or n_cols < 1 succeed and write nothing.
+ * HPGV_ERR_INVALID also for n_scores outside 1 .. 32, tab_pitch not a multiple of 64 or < n_variants, acc_pitch < n_cols, d_tab
+ * not 16-byte or d_acc not 8-byte aligned.  A workgroup's row range is never longer than 2^22 rows (hpgv_score_plan_rows), so no
+ * i32 sum overflows whatever the shape. */
+int  hpgv_score_cols_dev(hpgv_ctx *ctx, const uint8_t *d_gt, size_t pitch, int n_variants, int n_cols,
+                         const uint8_t *d_skip, const int8_t *d_tab, size_t tab_pitch, int n_scores,
+                         int64_t *d_acc, size_t acc_pitch, void *stream);
+
 /* ---- the variant-sharded resident scan of a GROUP context: what the runner's worker loop
  *      (assoc_runner.c:106-207, tdt_runner.c:150-200, stats_runner.c:176-215) becomes when the cohort lies in the HBM of
  *      the group's devices.  Variants are independent (assoc.c:38-82, tdt.c:41-271), so member g owns the contiguous
@@ -1293,6 +1369,33 @@ int  hpgv_grm_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, int max_l
                    uint64_t *line_off, uint32_t *field_off, int32_t *status, int frac_bits, double min_maf,
                    int32_t *class4, hpgv_grm_acc *d_acc);
 
+/* ---- Score on a host batch and on a text ("Score" above; synchronous, thread-safe) -------------------------------------- */
+/* hpgv_grm with the score's kernels: matrix, class4 (zeros for a skipped row), state and refusals as hpgv_ibs.  w: n_variants x
+ * n_scores doubles, flags: one byte per row (HPGV_SCORE_SKIP, HPGV_SCORE_FLIP), frac_bits: n_scores ints, all host memory.
+ * d_acc: DEVICE memory, (n_scores + 2) x acc_pitch int64 (hpgv_score_cols_dev), d_const: DEVICE memory, int64[n_scores + 1]
+ * (hpgv_score_table_dev); both zeroed by the caller before the first batch and ACCUMULATED into; calls from several threads may
+ * share them.  HPGV_ERR_INVALID -- before anything is launched -- for a weight that is not finite, n_scores outside 1 .. 32, a
+ * frac_bits outside [-900, 900], acc_pitch < n_samples, d_acc or d_const NULL or not 8-byte aligned.  A GROUP context returns
+ * HPGV_ERR_UNSUPPORTED (a caller with several devices keeps one pair of buffers per device and adds them: integers, any order). */
+int  hpgv_score(hpgv_ctx *ctx, const uint8_t *gt, size_t pitch, int n_variants, const double *w, const uint8_t *flags,
+                int n_scores, const int *frac_bits, int impute, int32_t *class4, int64_t *d_acc, size_t acc_pitch, int64_t *d_const);
+/* The first CALLBACK of this ABI.  The weights of a text's rows depend on the ID and allele fields of its lines, which only the
+ * tokenizer finds: the line heads must come back to the host before the weights can be known, and the matrix the tokenizer wrote
+ * must not cross the bus in between.  So hpgv_score_text, after tokenisation and before the score kernels, invokes `weigh` ONCE, on
+ * the calling thread, with the text, the n_lines line_off / field_off / status entries of hpgv_assoc_text (they lie on the host
+ * even where the caller passed NULL for them), and w (n_lines x n_scores) and flags (n_lines), both zeroed, to fill.  A non-zero
+ * return ends the call with HPGV_ERR_INVALID and nothing added.  The callback runs while the call holds one of the context's slots:
+ * it reads what it is given and fills w and flags, and makes no call on the same context. */
+typedef int (*hpgv_score_weigh_fn)(void *user, const char *text, int n_lines, const uint64_t *line_off,
+                                   const uint32_t *field_off, const int32_t *status, double *w, uint8_t *flags);
+/* hpgv_grm_text with the score's kernels: dropped lines (status 1, HPGV_LINE_FILTERED) and chromosome-X lines are skipped rows
+ * WHATEVER the callback says, and where *n_lines comes back larger than max_lines NOTHING was added, class4 is not written and
+ * `weigh` was not invoked.  A non-finite weight from the callback is HPGV_ERR_INVALID with nothing added.  Otherwise as hpgv_score. */
+int  hpgv_score_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, int max_lines, int *n_lines,
+                     uint64_t *line_off, uint32_t *field_off, int32_t *status, hpgv_score_weigh_fn weigh, void *user,
+                     int n_scores, const int *frac_bits, int impute, int32_t *class4,
+                     int64_t *d_acc, size_t acc_pitch, int64_t *d_const);
+
 /* ---- label permutation, host side: no GPU call, no context, usable without a device ------------------------------- */
 /* n_perms label rows for hpgv_set_perm_labels, labels_out[p * n_samples + j]: row p is a uniform shuffle of the cohort
  * columns' conditions (1 = affected), so every row has as many ones as the cohort has affected samples; HPGV_COND_OTHER
@@ -1341,6 +1444,20 @@ int  hpgv_grm_frac_bits(double min_maf);
 double hpgv_grm_value(const hpgv_grm_acc *a, int frac_bits);
 /* rows per row range of hpgv_grm_pairs_dev's launch on a device with n_cus compute units: a multiple of 64, never above 32 768 */
 int  hpgv_grm_plan_rows(int n_variants, int n_cols, int n_cus);
+/* One row's table by the expressions of "Score" above: limbs[k * 8 + l], l = 0 .. 3 the limbs of qg_k and 4 .. 7 those of qm_k,
+ * and c[k], for k < n_scores; returns 1 for a used row, else 0 with zeros (a negative count, n_scores outside 1 .. 32 or a
+ * frac_bits outside [-900, 900] included; nothing is written for a NULL pointer or a bad n_scores).  flags: HPGV_SCORE_SKIP,
+ * HPGV_SCORE_FLIP.  The function k_score_table calls, built for the host.  No GPU call. */
+int  hpgv_score_table(int32_t n0, int32_t n1, int32_t n2, const double *w, int n_scores, const int *frac_bits, int flags,
+                      int impute, int8_t *limbs /* n_scores x 8 */, int64_t *c /* n_scores */);
+/* 28 - e with frexp(max_abs_w) = m 2^e, clamped to [-900, 900]: the largest frac_bits at which no weight with |w| <= max_abs_w
+ * makes its row unused ("Score" above, with the argument; it holds for max_abs_w < 2^928).  0 for 0; INT_MIN for a NaN, an
+ * infinity or a negative number. */
+int  hpgv_score_frac_bits(double max_abs_w);
+/* value of one sum: ldexp((double)(sum + cnst), -frac_bits) */
+double hpgv_score_value(int64_t sum, int64_t cnst, int frac_bits);
+/* rows per row range of hpgv_score_cols_dev's launch on a device with n_cus compute units: a multiple of 64, never above 2^22 */
+int  hpgv_score_plan_rows(int n_variants, int n_cols, int n_scores, int n_cus);
 /* The host pieces of "PCA" above.  No GPU call. */
 /* the block width of a k-pair solve: 16 for 1 <= k <= 8, 32 for k <= 24, -1 otherwise */
 int  hpgv_pca_block(int k);

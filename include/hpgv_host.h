@@ -607,6 +607,28 @@ int  hpgv_run_pca(const char *vcf_path, const char *out_prefix, double min_maf, 
  * hpgv_run_pca.  A NaN element (a pair with n = 0): HPGV_ERR_UNSUPPORTED; a NULL path, unreadable files, sizes that do not
  * agree, n_pcs outside [1, 24] or above the sample count: HPGV_ERR_INVALID; no file is written by any of them. */
 int  hpgv_run_pca_grm(const char *grm_prefix, const char *out_prefix, int n_pcs, long *n_samples_out, int *n_iter_out);
+/* Allele scoring (include/hpgv.h "Score"; PLINK's --score, parity unpinned): per sample the sums of per-variant weights times ALT
+ * counts -- polygenic scores, the projection of a cohort onto SNP loadings, burden counts.
+ *   score_path: lines of whitespace-separated columns: a variant ID, an allele, then 1 .. 32 weight columns, the same number on
+ *     every line.  A first line whose first token is ID, #ID or SNP is a header and names the score columns; otherwise they are
+ *     SCORE1, SCORE2, ...  Column k is scored at frac_bits hpgv_score_frac_bits(max |w| of the column over the file): known before
+ *     the pass, so every batch uses the same scale.
+ *   A record takes part when its ID is in the file and the file's allele equals its ALT byte for byte, or equals its REF -- the
+ *     weight then counts REF alleles (HPGV_SCORE_FLIP).  Skipped: a record whose ALT holds a ',', whose ID is "." or is not in the
+ *     file, on chromosome X (hpgv_score_text's rule); and one whose allele is neither REF nor ALT, which is also counted in
+ *     *n_unmatched_out (wherever it lies).  impute != 0: PLINK's default mean imputation; 0: no-mean-imputation.
+ *   out_path: the header "#FID IID CNT CNT2" and "<name>_SUM <name>_AVG" per score, then one line per sample of the #CHROM line, in
+ *     VCF order, tab-separated: FID = IID = the sample name (as .grm.id), CNT = 2 (impute ? n_used : n_called), CNT2 = n_alt,
+ *     the values in "%.8g" (nan for 0 / 0) as .eigenvec's -- a projection goes straight into hpgv_run_assoc_logistic's covar_path,
+ *     whose reader takes the header by its #FID rule.
+ * *n_variants_out: the USED records (n_used), *n_samples_out: the samples.  Every sum is an integer, added over batches, engine
+ * threads and devices (the devices' buffers on the host when the run ends), so the file does not depend on batch_bytes, engine
+ * threads, input form or devices.  Neither filter setter is applied, as in hpgv_run_grm; input forms as hpgv_run_assoc.
+ * HPGV_ERR_INVALID before the engine is started, and no file written: a NULL path, a score file that cannot be read or holds no
+ * line of weights, a line with fewer than three columns, a ragged line, a weight that is not a finite number, an ID that appears twice, more
+ * than 32 weight columns. */
+int  hpgv_run_score(const char *vcf_path, const char *score_path, const char *out_path, int impute, size_t batch_bytes,
+                    long *n_variants_out, long *n_samples_out, long *n_unmatched_out);
 /* stage times of the last run on this process: {read, engine, write, sort, total} seconds and the number of
  * batches; read / engine / write overlap (three threads, three batch buffers in rotation).  The reader and
  * formatter teams use HPGV_IO_THREADS threads (environment; default half the cores, at most 16);
