@@ -78,6 +78,7 @@ SYMBOLS = [
     "hpgv_ld_edges_dev", "hpgv_ld_edges", "hpgv_clump",
     "hpgv_rows_gather_scratch_bytes", "hpgv_rows_gather_dev", "hpgv_assoc_select_text",
     "hpgv_ibs_pairs_dev", "hpgv_ibs_class_counts_dev", "hpgv_ibs_select_dev", "hpgv_ibs", "hpgv_ibs_text", "hpgv_ibs_terms", "hpgv_ibs_genome",
+    "hpgv_ibs_plan_rows",
     "hpgv_grm_table_dev", "hpgv_grm_pairs_dev", "hpgv_grm", "hpgv_grm_text", "hpgv_grm_table", "hpgv_grm_frac_bits", "hpgv_grm_value", "hpgv_grm_plan_rows",
     "hpgv_grm_matrix_dev", "hpgv_pca_apply_dev", "hpgv_pca_dev", "hpgv_pca_block", "hpgv_pca_jacobi", "hpgv_pca_chol_inv",
     "hpgv_score_table_dev", "hpgv_score_cols_dev", "hpgv_score", "hpgv_score_text", "hpgv_score_table", "hpgv_score_frac_bits", "hpgv_score_value",
@@ -294,6 +295,7 @@ def load():
     L.hpgv_ibs_terms.argtypes = [i32, i32, i32, vp]
     L.hpgv_ibs_genome.argtypes = [vp, vp, vp]
     L.hpgv_ibs_genome.restype = None
+    L.hpgv_ibs_plan_rows.argtypes = [i32, i32, i32]
     L.hpgv_grm_table_dev.argtypes = [vp, vp, i32, i32, C.c_double, vp, vp, vp, vp]
     L.hpgv_grm_pairs_dev.argtypes = [vp, vp, sz, i32, i32, vp, vp, vp, vp]
     L.hpgv_grm.argtypes = [vp, vp, sz, i32, vp, i32, C.c_double, vp, vp]
@@ -655,6 +657,11 @@ def ibs_genome(counts, E):
     for k in range(len(flat)):
         L.hpgv_ibs_genome(C.c_void_p(flat[k:k + 1].ctypes.data), _ptr(e), _ptr(out[k]))
     return out.reshape(shape + (5,))
+
+
+def ibs_plan_rows(n_variants, n_cols, n_cus):
+    """hpgv_ibs_plan_rows: rows per row range of hpgv_ibs_pairs_dev's launch"""
+    return int(load().hpgv_ibs_plan_rows(int(n_variants), int(n_cols), int(n_cus)))
 
 
 def grm_table(class4, frac_bits, min_maf):

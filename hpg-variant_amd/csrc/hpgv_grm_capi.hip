@@ -1,6 +1,6 @@
 // hpgv_grm_capi.hip -- C ABI of the genetic relationship matrix (include/hpgv.h "GRM"): the device-resident launches of k_grm_table
 // and k_grm_pairs, the synchronous entry points on a host batch and on a text -- staged as hpgv_ibs / hpgv_ibs_text are, their
-// front shared with them (cols_front, hpgv_internal.h) -- and the host-only helpers: a row's table, the recommended frac_bits,
+// back half shared with them (cols_back, hpgv_cols_capi.hip) -- and the host-only helpers: a row's table, the recommended frac_bits,
 // the value of a pair's sums, the row-range plan.
 #include "hpgv_internal.h"
 #include "hpgv_grm_kernels.h"
@@ -29,37 +29,25 @@ int grm_table_launch(hpgv_ctx *ctx, const int32_t *d_class4, int n_variants, int
 int grm_pairs_launch(hpgv_ctx *ctx, const uint8_t *d_gt, size_t pitch, int n_variants, int n_cols, const uint8_t *d_skip, const uint8_t *d_tab, hpgv_grm_acc *d_acc,
                      hipStream_t st) {
     hpgv::GrmArgs A;
-    A.gt = d_gt; A.pitch = pitch; A.n_variants = n_variants; A.n_cols = n_cols; A.skip = d_skip; A.tab = reinterpret_cast<const uint2 *>(d_tab);
+    A.tab = reinterpret_cast<const uint2 *>(d_tab);
     A.acc = reinterpret_cast<long long *>(d_acc);
-    const long long tiles = ((long long)n_cols + hpgv::IBS_T - 1) / hpgv::IBS_T;
-    A.pairs = tiles * (tiles + 1) / 2;
-    A.rows_per_split = hpgv::grm_plan_rows(n_variants, n_cols, ctx->n_cus);
-    A.splits = (int)(((long long)n_variants + A.rows_per_split - 1) / A.rows_per_split);
-    A.items = (unsigned long long)A.pairs * (unsigned long long)A.splits;
-    const unsigned long long per_xcd = (A.items + 7) / 8;
-    if (per_xcd * 8 > 0x7FFFFFFFull)
-        return fail(ctx, HPGV_ERR_UNSUPPORTED, "%d columns, %d rows: %lld tile pairs in %d row ranges exceed the grid", n_cols, n_variants, A.pairs, A.splits);
-    A.per_xcd = (unsigned)per_xcd;
+    if (const int rc = cols_grid_fill(ctx, d_gt, pitch, n_variants, n_cols, d_skip, hpgv::cols_tile_pairs(n_cols), hpgv::grm_plan_rows(n_variants, n_cols, ctx->n_cus),
+                                      "tile pairs", &A.G))
+        return rc;
     // (option "profile": the kernel's time is the statistics time of hpgv_last_kernel_ms)
-    return launch_profiled(ctx, st, 1, [&] { hipLaunchKernelGGL(hpgv::k_grm_pairs, dim3((unsigned)(per_xcd * 8)), dim3(256), 0, st, A); });
+    return launch_profiled(ctx, st, 1, [&] { hipLaunchKernelGGL(hpgv::k_grm_pairs, dim3(A.G.per_xcd * 8), dim3(256), 0, st, A); });
 }
 
-// the back half of hpgv_grm and hpgv_grm_text: cols_front's matrix and class counts, the rows' tables (which mark the unused
-// rows skipped), the pair sums added into the caller's device buffer, the class counts to the caller
+// the back half of hpgv_grm and hpgv_grm_text: the rows' tables (which mark the unused rows skipped), the pair sums added into the
+// caller's device buffer, from 1 sample on
 int grm_finish(hpgv_ctx *ctx, Slot *s, const Staged &S, const uint8_t *skip, bool x_too, int frac_bits, double min_maf, int32_t *class4, hpgv_grm_acc *d_acc) {
     const int nv = S.n, ns = ctx->stats.n_samples;
-    if (nv > 0) {
-        ColsFront F;
-        if (const int rc = cols_front(ctx, s, S, skip, x_too, true, &F)) return rc;
-        if (ns >= 1) {
-            HIPCHK(ctx, s->dbl.reserve_slack((size_t)nv * 8 + 16));
-            if (const int rc = grm_table_launch(ctx, F.d_class4, nv, frac_bits, min_maf, F.d_skip, s->dbl.as<uint8_t>(), nullptr, s->stream)) return rc;
-            if (const int rc = grm_pairs_launch(ctx, F.d_gt, F.pitch, nv, ns, F.d_skip, s->dbl.as<uint8_t>(), d_acc, s->stream)) return rc;
-        }
-        HIPCHK(ctx, hipMemcpyAsync(class4, F.d_class4, (size_t)nv * 16, hipMemcpyDeviceToHost, s->stream));
-    }
-    HIPCHK(ctx, hipStreamSynchronize(s->stream));
-    return HPGV_OK;
+    return cols_back(ctx, s, S, skip, x_too, true, class4, [&](const ColsFront &F) {
+        if (ns < 1) return (int)HPGV_OK;
+        HIPCHK(ctx, s->dbl.reserve_slack((size_t)nv * 8 + 16));
+        if (const int rc = grm_table_launch(ctx, F.d_class4, nv, frac_bits, min_maf, F.d_skip, s->dbl.as<uint8_t>(), nullptr, s->stream)) return rc;
+        return grm_pairs_launch(ctx, F.d_gt, F.pitch, nv, ns, F.d_skip, s->dbl.as<uint8_t>(), d_acc, s->stream);
+    });
 }
 
 int grm_host_check(hpgv_ctx *ctx, const char *what, int frac_bits, double min_maf, const hpgv_grm_acc *d_acc) {
@@ -96,7 +84,7 @@ int hpgv_grm_pairs_dev(hpgv_ctx *ctx, const uint8_t *d_gt, size_t pitch, int n_v
                        hpgv_grm_acc *d_acc, void *stream) {
     ctx = first_member(ctx);
     if (!ctx) return HPGV_ERR_INVALID;
-    if (const int rc = ibs_matrix_check(ctx, d_gt, pitch, n_variants, n_cols)) return rc;
+    if (const int rc = cols_matrix_check(ctx, d_gt, pitch, n_variants, n_cols)) return rc;
     if (((uintptr_t)d_acc & 15) || ((uintptr_t)d_tab & 7)) return fail(ctx, HPGV_ERR_INVALID, "d_acc must be 16-byte aligned, d_tab 8-byte aligned");
     if (n_variants == 0 || n_cols < 1) return HPGV_OK;
     if (!d_gt || !d_tab || !d_acc) return fail(ctx, HPGV_ERR_INVALID, "bad grm_pairs arguments");

@@ -22,6 +22,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <new>
 #include <string>
@@ -535,10 +536,18 @@ void tdt_split_counts(const std::vector<int32_t> &tu, int32_t *t1, int32_t *t2);
 // filtered, p <= p_max; p_i at d_p + i * p_stride) numbered into sel, their raw rows compacted on the device and copied to rows_out
 int select_rows(hpgv_ctx *ctx, Slot *s, const Staged &S, int n_samples, const int32_t *status, const char *d_p, size_t p_stride, double p_max,
                 int32_t *sel, uint8_t *rows_out, size_t rows_pitch, int rows_cap, int *n_sel);
-// defined in hpgv_ibs_capi.hip, shared with hpgv_grm_capi.hip: the checks of a device matrix whose COLUMNS are contracted, and
-// the front of the synchronous calls' back halves -- the raw matrix of a staged call in a pitch the kernels take, the rows' skip
-// bytes on the device (null where none is set and need_skip is false), k_ibs_class_counts queued on the slot's stream
-int ibs_matrix_check(const hpgv_ctx *ctx, const uint8_t *d_gt, size_t pitch, int n_variants, int n_cols);
+// defined in hpgv_cols_capi.hip, shared by the IBS, GRM and score units: the checks of a device matrix whose COLUMNS are contracted;
+// the grid of a launch over `work` units in row ranges of `rows` rows (hpgv_cols_kernels.h "Grid"; `what` names the units where
+// the grid is refused); the launch of the class counts {n0, n1, n2, missing} per row
+namespace hpgv { struct ColsGrid; }
+int cols_matrix_check(const hpgv_ctx *ctx, const uint8_t *d_gt, size_t pitch, int n_variants, int n_cols);
+int cols_grid_fill(hpgv_ctx *ctx, const uint8_t *d_gt, size_t pitch, int n_variants, int n_cols, const uint8_t *d_skip, long long work, int rows, const char *what,
+                   hpgv::ColsGrid *G);
+int cols_class_launch(hpgv_ctx *ctx, const uint8_t *d_gt, size_t pitch, int n_variants, int n_cols, const uint8_t *d_skip, int32_t *d_class4, hipStream_t st);
+// The front of the synchronous calls' back halves (S.n > 0): the matrix of a staged call as the kernels over sample COLUMNS read
+// it -- the raw matrix in a pitch they take -- the rows' skip bytes on the device, the class counts queued on the slot's stream.
+// skip (host, may be null) is copied to the slot; x_too: the rows the tokenizer flagged as chromosome X are skipped as well;
+// need_skip: the caller's kernels write skip bytes, so they exist even where none is set (else d_skip may be null)
 struct ColsFront {
     const uint8_t *d_gt = nullptr;
     size_t pitch = 0;
@@ -546,6 +555,9 @@ struct ColsFront {
     int32_t *d_class4 = nullptr;
 };
 int cols_front(hpgv_ctx *ctx, Slot *s, const Staged &S, const uint8_t *skip, bool x_too, bool need_skip, ColsFront *F);
+// the whole back half: cols_front, the tool's launches body(F) on s->stream, the class counts to the caller's class4, the
+// synchronise (S.n = 0: the synchronise alone)
+int cols_back(hpgv_ctx *ctx, Slot *s, const Staged &S, const uint8_t *skip, bool x_too, bool need_skip, int32_t *class4, const std::function<int(const ColsFront &)> &body);
 
 // defined in hpgv_statsall_capi.hip: k_stats_all2 on a batch (0 = launched, 1 = not a batch it takes: run k_stats_all)
 namespace hpgv { struct StatsAllArgs; }

@@ -1,6 +1,6 @@
 // hpgv_score_capi.hip -- C ABI of allele scoring (include/hpgv.h "Score"): the device-resident launches of k_score_table and
-// k_score_cols, the synchronous entry points on a host batch and on a text -- staged as hpgv_grm / hpgv_grm_text are, their front
-// shared with them (cols_front, hpgv_internal.h); the text form asks the caller for the rows' weights once the line heads are
+// k_score_cols, the synchronous entry points on a host batch and on a text -- staged as hpgv_grm / hpgv_grm_text are, their back half
+// shared with them (cols_back, hpgv_cols_capi.hip); the text form asks the caller for the rows' weights once the line heads are
 // back -- and the host-only helpers: a row's table, the recommended frac_bits, the value of a sum, the row-range plan.
 #include "hpgv_internal.h"
 #include "hpgv_score_kernels.h"
@@ -41,17 +41,12 @@ int score_table_launch(hpgv_ctx *ctx, const int32_t *d_class4, int n_variants, c
 int score_cols_launch(hpgv_ctx *ctx, const uint8_t *d_gt, size_t pitch, int n_variants, int n_cols, const uint8_t *d_skip, const int8_t *d_tab, size_t tab_pitch,
                       int n_scores, int64_t *d_acc, size_t acc_pitch, hipStream_t st) {
     hpgv::ScoreArgs A;
-    A.gt = d_gt; A.pitch = pitch; A.n_variants = n_variants; A.n_cols = n_cols; A.skip = d_skip; A.tab = d_tab; A.tab_pitch = tab_pitch; A.n_scores = n_scores;
+    A.tab = d_tab; A.tab_pitch = tab_pitch; A.n_scores = n_scores;
     A.acc = reinterpret_cast<long long *>(d_acc); A.acc_pitch = acc_pitch;
-    A.tiles = (int)(((long long)n_cols + hpgv::IBS_T - 1) / hpgv::IBS_T);
-    A.rows_per_split = hpgv::score_plan_rows(n_variants, n_cols, n_scores, ctx->n_cus);
-    A.splits = (int)(((long long)n_variants + A.rows_per_split - 1) / A.rows_per_split);
-    A.items = (unsigned long long)A.tiles * (unsigned long long)A.splits;
-    const unsigned long long per_xcd = (A.items + 7) / 8;
-    if (per_xcd * 8 > 0x7FFFFFFFull)
-        return fail(ctx, HPGV_ERR_UNSUPPORTED, "%d columns, %d rows: %d column tiles in %d row ranges exceed the grid", n_cols, n_variants, A.tiles, A.splits);
-    A.per_xcd = (unsigned)per_xcd;
-    const dim3 grid((unsigned)(per_xcd * 8)), block(256);
+    if (const int rc = cols_grid_fill(ctx, d_gt, pitch, n_variants, n_cols, d_skip, hpgv::cols_tiles(n_cols), hpgv::score_plan_rows(n_variants, n_cols, n_scores, ctx->n_cus),
+                                      "column tiles", &A.G))
+        return rc;
+    const dim3 grid(A.G.per_xcd * 8), block(256);
     // (option "profile": the kernel's time is the statistics time of hpgv_last_kernel_ms)
     return launch_profiled(ctx, st, 1, [&] {
         switch ((n_scores + 3) / 4) {
@@ -86,27 +81,20 @@ int score_room(hpgv_ctx *ctx, Slot *s, int nv, int n_scores, ScoreRoom *R) {
     return HPGV_OK;
 }
 
-// the back half of hpgv_score and hpgv_score_text: cols_front's matrix and class counts (skip: bit 0 of the flags, and what the
-// text form skips), the rows' tables (which mark the unused rows skipped), the sums added into the caller's device buffers, the
-// class counts to the caller
+// the back half of hpgv_score and hpgv_score_text (skip: bit 0 of the flags, and what the text form skips): the rows' tables (which
+// mark the unused rows skipped), the sums added into the caller's device buffers, from 1 sample on
 int score_finish(hpgv_ctx *ctx, Slot *s, const Staged &S, const uint8_t *skip, bool x_too, const double *w, const uint8_t *flags, int n_scores, const int *frac_bits,
                  int impute, int32_t *class4, int64_t *d_acc, size_t acc_pitch, int64_t *d_const) {
     const int nv = S.n, ns = ctx->stats.n_samples;
-    if (nv > 0) {
-        ColsFront F;
-        if (const int rc = cols_front(ctx, s, S, skip, x_too, true, &F)) return rc;
+    return cols_back(ctx, s, S, skip, x_too, true, class4, [&](const ColsFront &F) {
         ScoreRoom R;
         if (const int rc = score_room(ctx, s, nv, n_scores, &R)) return rc;
         HIPCHK(ctx, hipMemcpyAsync(R.d_w, w, (size_t)nv * (size_t)n_scores * sizeof(double), hipMemcpyHostToDevice, s->stream));
         HIPCHK(ctx, hipMemcpyAsync(R.d_flags, flags, (size_t)nv, hipMemcpyHostToDevice, s->stream));
         if (const int rc = score_table_launch(ctx, F.d_class4, nv, R.d_w, R.d_flags, n_scores, frac_bits, impute, F.d_skip, R.d_tab, R.tab_pitch, d_const, s->stream))
             return rc;
-        if (ns >= 1)
-            if (const int rc = score_cols_launch(ctx, F.d_gt, F.pitch, nv, ns, F.d_skip, R.d_tab, R.tab_pitch, n_scores, d_acc, acc_pitch, s->stream)) return rc;
-        HIPCHK(ctx, hipMemcpyAsync(class4, F.d_class4, (size_t)nv * 16, hipMemcpyDeviceToHost, s->stream));
-    }
-    HIPCHK(ctx, hipStreamSynchronize(s->stream));
-    return HPGV_OK;
+        return ns >= 1 ? score_cols_launch(ctx, F.d_gt, F.pitch, nv, ns, F.d_skip, R.d_tab, R.tab_pitch, n_scores, d_acc, acc_pitch, s->stream) : (int)HPGV_OK;
+    });
 }
 
 int score_host_check(hpgv_ctx *ctx, const char *what, int n_scores, const int *frac_bits, const int64_t *d_acc, size_t acc_pitch, const int64_t *d_const) {
@@ -149,7 +137,7 @@ int hpgv_score_cols_dev(hpgv_ctx *ctx, const uint8_t *d_gt, size_t pitch, int n_
                         int n_scores, int64_t *d_acc, size_t acc_pitch, void *stream) {
     ctx = first_member(ctx);
     if (!ctx) return HPGV_ERR_INVALID;
-    if (const int rc = ibs_matrix_check(ctx, d_gt, pitch, n_variants, n_cols)) return rc;
+    if (const int rc = cols_matrix_check(ctx, d_gt, pitch, n_variants, n_cols)) return rc;
     if (n_scores < 1 || n_scores > hpgv::SCORE_MAX) return fail(ctx, HPGV_ERR_INVALID, "n_scores %d: 1 .. %d", n_scores, hpgv::SCORE_MAX);
     if (const int rc = score_pitch_check(ctx, n_variants, tab_pitch)) return rc;
     if (((uintptr_t)d_tab & 15) || ((uintptr_t)d_acc & 7)) return fail(ctx, HPGV_ERR_INVALID, "d_tab must be 16-byte aligned, d_acc 8-byte aligned");

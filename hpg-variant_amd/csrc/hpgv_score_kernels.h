@@ -18,7 +18,7 @@
 // numbering of k inside a lane group cancels.  Here A comes from table memory and B from the transposition, and what must hold is
 // this: byte p of the 16 bytes that lane (m, kq) gives as A and byte p of the 16 bytes that lane (n, kq) gives as B belong to the
 // SAME variant.  The hardware pairs the operands' k at equal (lane group, byte), whatever it calls that k, so nothing more is needed.
-// B: ibs_transpose4 leaves the four rows of a column in byte order (row 0 in byte 0: v_perm_b32's selector byte i names the source
+// B: cols_transpose4 leaves the four rows of a column in byte order (row 0 in byte 0: v_perm_b32's selector byte i names the source
 // of OUTPUT byte i, and sources 0 .. 3 are the second operand), thread rg = tid >> 4 stores rows 4 rg .. 4 rg + 3 as dword rg of
 // the column's 64 k bytes, and lane group kq reads bytes 16 kq .. 16 kq + 15: variant k0 + 16 kq + p at byte p.  A: the table is
 // limb-plane-major, tab[(k * 8 + l) * tab_pitch + row], and lane (m, kq) loads the 16 bytes at row k0 + 16 kq of its plane: the
@@ -29,16 +29,16 @@
 // side by side, and the row ranges are cut eight workgroups per CU deep.  The fragments held a step ahead cost 8 registers per
 // score group and plane: 7 waves per SIMD fit at one group, 4 at two, 2 at six, 1 at eight (the compiler's report).
 //
-// Tile.  A workgroup of four waves owns IBS_T = 64 columns (16 per wave: its B block) and a range of rows; tile geometry, LDS
-// image (columns IBS_LDS_COL uint4 apart), lane maps and transposition are k_ibs_pairs's, one side only: 2 buffers x 2 planes x
-// 64 columns x 80 bytes = 20 KiB.  A fragments are plain 16-byte loads of the table, the same for the four waves (L1 / L2).
+// Tile.  A workgroup of four waves owns COLS_T = 64 columns (16 per wave: its B block) and a range of rows; tile geometry, LDS
+// image, lane maps, transposition and grid (its unit a tile) are the column tile's (hpgv_cols_kernels.h), one side only: 2 buffers
+// x 2 planes x 64 columns x 80 bytes = 20 KiB.  A fragments are plain 16-byte loads of the table, the same for the four waves (L1 / L2).
 // C/D: col = l & 15 (the column), row = (l >> 4) * 4 + reg = (score of the group, limb): a lane holds the four limb sums of one
 // (score, column) and combines them itself.
 //
 // Epilogue.  ADDS sum_k[j] into acc[k * acc_pitch + j], n_called into plane n_scores and n_alt into plane n_scores + 1 with
 // relaxed device-scope 64-bit integer atomics.  n_called = (rows of the range that are not skipped) - (m-sum of the column).
 #pragma once
-#include "hpgv_ibs_kernels.h"
+#include "hpgv_cols_kernels.h"
 
 namespace hpgv {
 
@@ -111,30 +111,14 @@ __host__ __device__ inline int score_table_value(int n0, int n1, int n2, const d
 __host__ __device__ inline double score_value(long long sum, long long cnst, int frac_bits) { return ldexp((double)(sum + cnst), -frac_bits); }
 
 // rows per row range of k_score_cols: the ranges fill the device about eight workgroups deep where the column tiles alone do not
-// (200 columns are 4 tiles on 256 CUs), none shorter than IBS_SPLIT_ROWS rows, with at least as many ranges as the cap of
-// SCORE_MAX_RANGE_ROWS asks for.  A multiple of 64, at least 64, at most the cap.  n_scores does not enter: a workgroup walks its
-// rows once whatever the number of scores, and more scores only make each step longer
+// (200 columns are 4 tiles on 256 CUs), with at least as many ranges as the cap of SCORE_MAX_RANGE_ROWS asks for.  n_scores does
+// not enter: a workgroup walks its rows once whatever the number of scores, and more scores only make each step longer
 inline int score_plan_rows(int n_variants, int n_cols, int n_scores, int n_cus) {
     (void)n_scores;
-    const long long nv = n_variants > 0 ? n_variants : 0;
-    const long long tiles = ((long long)(n_cols > 0 ? n_cols : 1) + IBS_T - 1) / IBS_T;
-    const long long want = (8ll * (n_cus > 0 ? n_cus : 1) + tiles - 1) / tiles, room = (nv + IBS_SPLIT_ROWS - 1) / IBS_SPLIT_ROWS;
-    long long splits = want < room ? (want > 1 ? want : 1) : (room > 1 ? room : 1);
-    const long long least = (nv + SCORE_MAX_RANGE_ROWS - 1) / SCORE_MAX_RANGE_ROWS;
-    if (splits < least) splits = least;
-    // EQUAL ranges, not ranges of the cap and a rest: the grid deals contiguous runs of (range, tile) items to the XCDs, and a short
-    // last range would leave the XCDs that draw it idle (measured on k_grm_pairs, whose grid this is: hpgv_grm_kernels.h)
-    const long long rows = ((nv + splits - 1) / splits + 63) / 64 * 64;             // <= the cap: the cap is a multiple of 64
-    return (int)(rows < 64 ? 64 : rows);
+    return cols_plan_rows(n_variants, cols_tiles(n_cols), 8, SCORE_MAX_RANGE_ROWS, n_cus);
 }
 
 struct ScoreS { int s[SCORE_MAX]; };
-
-__device__ __forceinline__ long long wave_sum_i64(long long v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 
 // class4 {n0, n1, n2, missing}, the weights and the flag byte of every row -> its limb planes tab[(k * 8 + l) * tab_pitch + row];
 // an unused row gets zeros and skip[row] = 1 (a row that comes in skipped is unused whatever else holds); rows from n_variants to
@@ -167,7 +151,7 @@ static __global__ __launch_bounds__(256) void k_score_table(const int4 *__restri
 #pragma unroll
             for (int i = 0; i < 8; ++i) tab[((size_t)k * 8 + i) * tab_pitch + row] = l[i];
         }
-        const long long sum = wave_sum_i64(ck);
+        const long long sum = cols_wave_sum_i64(ck);
         if (lane == 0 && sum != 0) __hip_atomic_fetch_add(cnst + k, sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     const unsigned long long mask = __ballot(used);
@@ -175,47 +159,34 @@ static __global__ __launch_bounds__(256) void k_score_table(const int4 *__restri
 }
 
 struct ScoreArgs {
-    const uint8_t *gt;               // rows of HPGV8 bytes `pitch` apart
-    size_t pitch;
-    int n_variants, n_cols;
-    const uint8_t *skip;             // per row, may be null
+    ColsGrid G;                      // its unit a column tile; a row range has at most SCORE_MAX_RANGE_ROWS rows
     const int8_t *tab;               // limb planes, tab_pitch apart
     size_t tab_pitch;
     int n_scores;
     long long *acc;                  // [k * acc_pitch + col], planes n_scores (n_called) and n_scores + 1 (n_alt) behind the scores
     size_t acc_pitch;
-    int tiles;                       // ceil(n_cols / IBS_T)
-    int splits, rows_per_split;      // row ranges; rows of each, a multiple of 64, at most SCORE_MAX_RANGE_ROWS
-    unsigned long long items;        // tiles * splits
-    unsigned per_xcd;                // ceil(items / 8)
 };
 
 // NG: groups of four scores, ceil(n_scores / 4)
 template <int NG>
 static __global__ __launch_bounds__(256) void k_score_cols(const ScoreArgs A) {
-    __shared__ uint4 img[2][2][IBS_T * IBS_LDS_COL];                       // [buffer][plane g, m]
+    __shared__ uint4 img[2][2][COLS_T * COLS_LDS_COL];                     // [buffer][plane g, m]
     __shared__ int used_rows;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int col = lane & 15, kq = lane >> 4;
-    // workgroup -> (row range, column tile): "Grid" of hpgv_ibs_kernels.h, the tile fastest
-    const unsigned seq = blockIdx.x >> 3;
-    const unsigned long long item = (unsigned long long)(blockIdx.x & 7u) * A.per_xcd + seq;
-    if (seq >= A.per_xcd || item >= A.items) return;                       // (the whole workgroup)
-    const int split = (int)(item / (unsigned long long)A.tiles);
-    const int j0 = (int)(item % (unsigned long long)A.tiles) * IBS_T;
-    const long long k_first = (long long)split * A.rows_per_split;
-    if (k_first >= A.n_variants) return;
-    const int k_begin = (int)k_first;
-    const int k_end = (int)min((long long)A.n_variants, k_first + A.rows_per_split);
-    const int steps = (k_end - k_begin + 63) / 64;
+    const ColsGrid &G = A.G;
+    const ColsItem it = cols_item(G);
+    if (it.steps == 0) return;                                             // (the whole workgroup)
+    const int j0 = (int)it.unit * COLS_T;
+    const int k_begin = it.k_begin, k_end = it.k_end, steps = it.steps;
     if (tid == 0) used_rows = 0;
 
     // what this thread stages: columns 4 cg .. 4 cg + 3 of the tile, rows 4 rg .. 4 rg + 3 of the k-step
     const int cg = tid & 15, rg = tid >> 4;
     const int cj = j0 + 4 * cg;
-    const bool cj_ok = cj < A.n_cols;                                      // (cj + 4 <= pitch then: a multiple of 16 >= n_cols)
-    const bool live = j0 + wave * 16 < A.n_cols;                           // (wave-uniform)
+    const bool cj_ok = cj < G.n_cols;                                      // (cj + 4 <= pitch then: a multiple of 16 >= n_cols)
+    const bool live = j0 + wave * 16 < G.n_cols;                           // (wave-uniform)
 
     // a row that is skipped or past the range loads as 0x00 (g = 0, m = 0) and its table is zeros: it adds to no sum
     int n_ok = 0;
@@ -224,22 +195,21 @@ static __global__ __launch_bounds__(256) void k_score_cols(const ScoreArgs A) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int k = kb + i;
-            const bool in = k < k_end, ok = in && (A.skip == nullptr || A.skip[k] == 0);
+            const bool in = k < k_end, ok = in && (G.skip == nullptr || G.skip[k] == 0);
             n_ok += ok ? 1 : 0;
             // (the genotypes do not wait for the skip byte: both loads are in flight together)
-            const uint32_t w = (in && cj_ok) ? *reinterpret_cast<const uint32_t *>(A.gt + (size_t)k * A.pitch + cj) : 0u;
+            const uint32_t w = (in && cj_ok) ? *reinterpret_cast<const uint32_t *>(G.gt + (size_t)k * G.pitch + cj) : 0u;
             r[i] = ok ? w : 0u;
         }
     };
     auto stage = [&](int buf, uint32_t (&r)[4]) {
-        ibs_transpose4(r);
+        cols_transpose4(r);
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             uint32_t v, g;
             perm_planes_trend(r[c], v, g);
-            const int at = (4 * cg + c) * (IBS_LDS_COL * 4) + rg;          // in dwords
-            reinterpret_cast<uint32_t *>(img[buf][0])[at] = g;
-            reinterpret_cast<uint32_t *>(img[buf][1])[at] = v ^ 0x01010101u;
+            cols_staged(img[buf][0], cg, c, rg) = g;
+            cols_staged(img[buf][1], cg, c, rg) = v ^ 0x01010101u;
         }
     };
 
@@ -279,9 +249,7 @@ static __global__ __launch_bounds__(256) void k_score_cols(const ScoreArgs A) {
         }
         if (live) {
             const int cur = s & 1;
-            const int at_b = (wave * 16 + col) * IBS_LDS_COL + kq;
-            const uint4 qg = img[cur][0][at_b], qm = img[cur][1][at_b];
-            const perm_i32x4 bg{(int)qg.x, (int)qg.y, (int)qg.z, (int)qg.w}, bm{(int)qm.x, (int)qm.y, (int)qm.z, (int)qm.w};
+            const perm_i32x4 bg = cols_frag(img[cur][0], wave * 16 + col, kq), bm = cols_frag(img[cur][1], wave * 16 + col, kq);
 #pragma unroll
             for (int n = 0; n < NG; ++n) {
                 acc[n] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a_cur[n][0], bg, acc[n], 0, 0, 0);
@@ -307,7 +275,7 @@ static __global__ __launch_bounds__(256) void k_score_cols(const ScoreArgs A) {
 
     // ---- epilogue: acc[n][reg] of lane (col, kq) is limb reg of score 4 n + kq in column j
     const int j = j0 + wave * 16 + col;
-    if (j >= A.n_cols) return;
+    if (j >= G.n_cols) return;
 #pragma unroll
     for (int n = 0; n < NG; ++n) {
         const int k = n * 4 + kq;

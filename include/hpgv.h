@@ -1434,6 +1434,8 @@ int  hpgv_ibs_terms(int32_t n0, int32_t n1, int32_t n2, double t[5]);
 /* out = {Z0, Z1, Z2, PI_HAT, DST} of one pair's counts with E = {E00, E01, E02, E11, E12}: the function k_ibs_select calls,
  * built for the host.  No GPU call, no context. */
 void hpgv_ibs_genome(const hpgv_ibs_counts *c, const double E[5], double out[5]);
+/* rows per row range of hpgv_ibs_pairs_dev's launch on a device with n_cus compute units: a multiple of 64, never above 2^31 - 64 */
+int  hpgv_ibs_plan_rows(int n_variants, int n_cols, int n_cus);
 /* One row's table by the expressions of "GRM" above: hi[c], lo[c] for the classes c = 0, 1, 2, entry 3 zero; returns 1 for a
  * used row, else 0 with zeros (a negative count or a frac_bits outside [0, 14] included).  Whether the row is skipped is the
  * caller's to know.  The function k_grm_table calls, built for the host.  No GPU call. */

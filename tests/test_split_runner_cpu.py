@@ -20,6 +20,7 @@ def host():
     L.hpgv_run_split.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_long), C.c_int, C.c_size_t,
                                  C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_long)]
     L.hpgv_host_last_error.restype = C.c_char_p
+    L.hpgv_host_shutdown()                                     # no engine bound by an earlier test of the same process
     return L
 
 

@@ -36,8 +36,7 @@ def work(n_cols, n_variants, n_cus):
     16 x 16 blocks that run MFMAs per k-step)"""
     tiles = -(-n_cols // 64)
     pairs = tiles * (tiles + 1) // 2
-    splits = max(1, min(-(-4 * n_cus // pairs), -(-n_variants // 256)))
-    rows = -(-(-(-n_variants // splits)) // 64) * 64
+    rows = hpgv.ibs_plan_rows(n_variants, n_cols, n_cus)
     splits = -(-n_variants // rows)
     steps = sum(-(-min(rows, n_variants - s * rows) // 64) for s in range(splits))
     blocks = 0
