@@ -74,6 +74,7 @@ SYMBOLS = [
     "hpgv_assoc_model_scan_dev", "hpgv_assoc_model_stats_dev", "hpgv_assoc_trend_perm_dev", "hpgv_assoc_model", "hpgv_assoc_model_text",
     "hpgv_set_covariates", "hpgv_assoc_logistic_dev", "hpgv_assoc_logistic", "hpgv_assoc_logistic_text", "hpgv_logistic_fit",
     "hpgv_set_phenotype", "hpgv_assoc_linear_dev", "hpgv_assoc_linear", "hpgv_assoc_linear_text", "hpgv_linear_fit", "hpgv_linear_t_p",
+    "hpgv_perm_order_shuffle", "hpgv_set_linear_perms", "hpgv_assoc_linear_perm_dev", "hpgv_assoc_linear_perm", "hpgv_assoc_linear_perm_text", "hpgv_linear_perm_fit", "hpgv_mfma_f64_probe",
     "hpgv_ld_window_dev", "hpgv_ld", "hpgv_ld_text", "hpgv_ld_r2",
     "hpgv_ld_edges_dev", "hpgv_ld_edges", "hpgv_clump",
     "hpgv_rows_gather_scratch_bytes", "hpgv_rows_gather_dev", "hpgv_assoc_select_text",
@@ -278,6 +279,13 @@ def load():
     L.hpgv_linear_fit.argtypes = [vp, vp, vp, i32, i32, vp, vp]
     L.hpgv_linear_t_p.argtypes = [C.c_double, i32]
     L.hpgv_linear_t_p.restype = C.c_double
+    L.hpgv_perm_order_shuffle.argtypes = [vp, i32, i32, u64, vp]
+    L.hpgv_set_linear_perms.argtypes = [vp, vp, i32]
+    L.hpgv_assoc_linear_perm_dev.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
+    L.hpgv_assoc_linear_perm.argtypes = [vp, vp, sz, i32, vp, vp, vp, vp]
+    L.hpgv_assoc_linear_perm_text.argtypes = [vp, C.c_char_p, sz, i32, C.POINTER(i32), vp, vp, vp, vp, vp, vp, vp]
+    L.hpgv_linear_perm_fit.argtypes = [vp, vp, vp, i32, i32, vp, i32, vp, vp]
+    L.hpgv_mfma_f64_probe.argtypes = [vp, i32, i32, C.POINTER(C.c_float), C.POINTER(C.c_double)]
     L.hpgv_ld_window_dev.argtypes = [vp, vp, sz, i32, i32, i32, vp, vp, C.c_int64, vp, vp, vp, vp]
     L.hpgv_ld.argtypes = [vp, vp, sz, i32, i32, vp, vp, C.c_int64, vp, vp]
     L.hpgv_ld_text.argtypes = [vp, C.c_char_p, sz, i32, C.POINTER(i32), vp, vp, vp, i32, vp, vp]
@@ -337,6 +345,17 @@ def perm_labels_shuffle(condition, n_perms, seed):
     rc = load().hpgv_perm_labels_shuffle(_ptr(c), len(c), n_perms, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(out))
     if rc != OK:
         raise HpgvError("hpgv_perm_labels_shuffle -> %d" % rc)
+    return out
+
+
+def perm_order_shuffle(condition, n_perms, seed):
+    """hpgv_perm_order_shuffle: (n_perms, n_samples) int32 rows, row p column j = the VCF column whose residual column j takes: a
+    uniform shuffle of the cohort columns among themselves, OTHER columns fixed; deterministic in (seed, row).  No device needed."""
+    c = _np(condition, np.uint8)
+    out = np.zeros((n_perms, len(c)), np.int32)
+    rc = load().hpgv_perm_order_shuffle(_ptr(c), len(c), n_perms, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(out))
+    if rc != OK:
+        raise HpgvError("hpgv_perm_order_shuffle -> %d" % rc)
     return out
 
 
@@ -457,6 +476,26 @@ def run_assoc_linear(vcf_path, ped_path, pheno_path, covar_path, out_path, n_cov
     return n.value, used.value
 
 
+def run_assoc_linear_perm(vcf_path, ped_path, pheno_path, covar_path, out_path, n_perms, seed, n_covar=0, batch_bytes=1 << 22):
+    """hpgv_run_assoc_linear_perm of libhpgv_host.so (include/hpgv_host.h): run_assoc_linear's file at out_path and the max(T)
+    empirical p-values of n_perms permutations of the reduced model's residuals at out_path + ".mperm".  Paths may be None.  Returns
+    (variants written, cohort samples used)."""
+    _build.build_host_lib()
+    H = C.CDLL(_build.HOSTLIB)
+    H.hpgv_run_assoc_linear_perm.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_int, C.c_uint64, C.c_size_t,
+                                             C.POINTER(C.c_long), C.POINTER(C.c_long)]
+    H.hpgv_host_last_error.restype = C.c_char_p
+    n, used = C.c_long(0), C.c_long(0)
+    enc = lambda q: None if q is None else os.fsencode(q)
+    rc = H.hpgv_run_assoc_linear_perm(enc(vcf_path), enc(ped_path), enc(pheno_path), enc(covar_path), n_covar, enc(out_path), int(n_perms),
+                                      int(seed) & 0xFFFFFFFFFFFFFFFF, batch_bytes, C.byref(n), C.byref(used))
+    if rc != OK:
+        e = HpgvError("hpgv_run_assoc_linear_perm -> %d: %s" % (rc, (H.hpgv_host_last_error() or b"").decode(errors="replace")))
+        e.code = rc
+        raise e
+    return n.value, used.value
+
+
 def linear_fit(cls, y, cov=None):
     """hpgv_linear_fit: the linear regression of include/hpgv.h on the host, samples in index order.  cls: genotype classes (0, 1,
     2; anything else missing), y: the trait, cov (n, C) or None.  Returns (a LINEAR_RESULT record, coef (2, p): beta then se).  No
@@ -472,6 +511,23 @@ def linear_fit(cls, y, cov=None):
         e.code = rc
         raise e
     return out[0], coef
+
+
+def linear_perm_fit(cls, y, cov, order):
+    """hpgv_linear_perm_fit: the permuted linear statistic of include/hpgv.h on the host for one row, samples in index order.  cls,
+    y, cov as linear_fit takes them; order (n_perms, n): row p column j = the sample whose residual sample j takes.  Returns (t_obs,
+    t_perm (n_perms,)).  No device needed."""
+    c, yy = _np(cls, np.uint8), _np(y, np.float64)
+    cv = np.zeros((len(c), 0), np.float64) if cov is None else _np(cov, np.float64).reshape(len(c), -1)
+    nc = cv.shape[1]
+    od = _np(order, np.int32).reshape(-1, len(c)) if len(c) else np.zeros((0, 0), np.int32)
+    t_obs, t_perm = np.zeros(1, np.float64), np.zeros(max(len(od), 1), np.float64)
+    rc = load().hpgv_linear_perm_fit(_ptr(c), _ptr(yy), _ptr(cv) if nc else None, len(c), nc, _ptr(od) if len(od) else None, len(od), _ptr(t_obs), _ptr(t_perm))
+    if rc != OK:
+        e = HpgvError("hpgv_linear_perm_fit -> %d" % rc)
+        e.code = rc
+        raise e
+    return float(t_obs[0]), t_perm[:len(od)]
 
 
 def linear_t_p(t, df):
@@ -1106,6 +1162,39 @@ class Engine:
         self._chk(self.L.hpgv_assoc_linear_text(self.h, text, len(text), max_lines, C.byref(nl), None, None, _ptr(status), _ptr(out), _ptr(cf)))
         return _text_result(nl, max_lines, status=status, out=out, coef=cf)
 
+    def set_linear_perms(self, order):
+        """hpgv_set_linear_perms: order (n_perms, n_samples) int32 as perm_order_shuffle writes it; None or no rows drops them."""
+        if order is None or len(order) == 0:
+            self._chk(self.L.hpgv_set_linear_perms(self.h, None, 0))
+            self._n_linperms = 0
+            return
+        od = _np(order, np.int32)
+        assert od.ndim == 2
+        self._n_linperms = 0
+        self._chk(self.L.hpgv_set_linear_perms(self.h, _ptr(od), od.shape[0]))
+        self._n_linperms = od.shape[0]
+
+    def assoc_linear_perm(self, gt):
+        """hpgv_assoc_linear_perm: the LINEAR_RESULT records of assoc_linear plus t_obs and n_ge per variant and batch_max per
+        permutation."""
+        gt = _np(gt, np.uint8)
+        nv, pitch = gt.shape
+        np_ = getattr(self, "_n_linperms", 0)
+        out, t_obs, n_ge = np.zeros(nv, LINEAR_RESULT), np.zeros(nv, np.float64), np.zeros(nv, np.int32)
+        bmax = np.zeros(max(np_, 1), np.float64)
+        self._chk(self.L.hpgv_assoc_linear_perm(self.h, _ptr(gt), pitch, nv, _ptr(out), _ptr(t_obs), _ptr(n_ge), _ptr(bmax)))
+        return dict(out=out, t_obs=t_obs, n_ge=n_ge, batch_max=bmax[:np_])
+
+    def assoc_linear_perm_text(self, text, max_lines=None):
+        """hpgv_assoc_linear_perm_text: assoc_linear_perm on VCF data lines, the outputs per line."""
+        text, max_lines, m, status, nl = _text_call(text, max_lines)
+        np_ = getattr(self, "_n_linperms", 0)
+        out, t_obs, n_ge = np.zeros(m, LINEAR_RESULT), np.zeros(m, np.float64), np.zeros(m, np.int32)
+        bmax = np.zeros(max(np_, 1), np.float64)
+        self._chk(self.L.hpgv_assoc_linear_perm_text(self.h, text, len(text), max_lines, C.byref(nl), None, None, _ptr(status), _ptr(out), _ptr(t_obs),
+                                                     _ptr(n_ge), _ptr(bmax)))
+        return dict(_text_result(nl, max_lines, status=status, out=out, t_obs=t_obs, n_ge=n_ge), batch_max=bmax[:np_])
+
     def ld(self, gt, window, chrom=None, pos=None, max_bp=-1, counts=True):
         """hpgv_ld: r2 (nv, window) and, with counts, counts6 (nv, window, 6); element [b, d - 1] is the pair (b - d, b) over the
         cohort columns.  chrom / pos (per row, both or neither) and max_bp bound the band."""
@@ -1517,6 +1606,9 @@ class Engine:
     def assoc_linear_dev(self, d_gt, n_variants, d_out, d_coef=None, stream=None):
         self._chk(self.L.hpgv_assoc_linear_dev(self.h, d_gt, n_variants, d_out, d_coef, stream))
 
+    def assoc_linear_perm_dev(self, d_gt, n_variants, d_t_obs, d_n_ge, d_batch_max, d_perm_t=None, stream=None):
+        self._chk(self.L.hpgv_assoc_linear_perm_dev(self.h, d_gt, n_variants, d_t_obs, d_n_ge, d_batch_max, d_perm_t, stream))
+
     def ld_window_dev(self, d_gt, pitch, n_variants, window, d_r2, d_counts6=None, b_begin=0, d_chrom=None, d_pos=None, max_bp=-1,
                       d_skip=None, stream=None):
         self._chk(self.L.hpgv_ld_window_dev(self.h, d_gt, pitch, n_variants, b_begin, window, d_chrom, d_pos, int(max_bp), d_skip,
@@ -1699,6 +1791,12 @@ class Engine:
 
     def group_sync(self):
         self._chk(self.L.hpgv_group_sync(self.h))
+
+    def mfma_f64_probe(self, steps=4096, iters=5):
+        """hpgv_mfma_f64_probe: (kernel ms, flop per launch) of the f64 matrix cores with no memory traffic"""
+        ms, flop = C.c_float(), C.c_double()
+        self._chk(self.L.hpgv_mfma_f64_probe(self.h, steps, iters, C.byref(ms), C.byref(flop)))
+        return ms.value, flop.value
 
     def read_probe(self, d_buf, nbytes, iters=5):
         ms = C.c_float()

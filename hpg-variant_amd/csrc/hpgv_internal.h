@@ -253,6 +253,11 @@ struct hpgv_ctx {
     std::vector<double> lin_y, lin_cov;
     bool has_pheno = false;
     DevBuf d_lin;
+    // permutations of the linear statistic (hpgv_set_linear_perms): the image of hpgv_linear_perm_kernels.h -- tile 0 with Q and e, a
+    // tile per 16 permutations -- and the 1 + n_linperms ss values behind it; dropped by a new cohort, phenotype or covariates
+    DevBuf d_linperm;
+    int n_linperms = 0;
+    DevBuf d_linperm_rows;                // hpgv_assoc_linear_perm_dev's {mu, D} per row (the synchronous calls keep theirs in their slot)
     // tdt
     Layout tdt;
     hpgv::TdtPlan tdt_plan;
@@ -465,6 +470,43 @@ template <typename F>
     if (!ctx->d_lf) return fail(ctx, HPGV_ERR_STATE, "hpgv_set_logfact has not been called");
     if (ctx->assoc.set && ctx->n_lf < (size_t)2 * (ctx->nA + ctx->nU) + 1)
         return fail(ctx, HPGV_ERR_STATE, "log-factorial table has %zu entries, need %d", ctx->n_lf, 2 * (ctx->nA + ctx->nU) + 1);
+    return HPGV_OK;
+}
+
+// where the parts of Slot::perm lie in a call over n rows and n_perms permutations: n_ge per row at 0, the batch maxima per
+// permutation at round_up(4 n, 16), the rows' skip bytes behind them, then -- TDT flips: tail_pitch bytes per row -- the slow
+// families' i8 differences from the next multiple of 16 on (the linear permutations: 24 bytes per row there, {mu, D} of every row,
+// then t_obs of every row)
+struct PermPlan {
+    int32_t *d_n_ge = nullptr;
+    double *d_max = nullptr;
+    uint8_t *d_skip = nullptr;         // null when every row takes part
+    int8_t *d_tail = nullptr;
+};
+struct PermOffsets { size_t max, skip, tail; };
+constexpr PermOffsets perm_offsets(size_t n, size_t n_perms) {
+    const size_t off_max = round_up(n * sizeof(int32_t), 16), off_skip = off_max + n_perms * sizeof(double);
+    return {off_max, off_skip, round_up(off_skip + n, 16)};
+}
+// the synchronous calls launch without the *_dev wrappers' alignment refusals: the kernels' 64-bit atomics on the maxima need 8
+// bytes, their 16-byte loads of the tail 16, at any row count -- odd ones above all
+constexpr bool perm_offsets_aligned(size_t n, size_t n_perms) {
+    return perm_offsets(n, n_perms).max % 16 == 0 && perm_offsets(n, n_perms).tail % 16 == 0 && perm_offsets(n, n_perms).skip >= perm_offsets(n, n_perms).max &&
+           perm_offsets(n, n_perms).max >= n * sizeof(int32_t);
+}
+static_assert(perm_offsets_aligned(0, 1) && perm_offsets_aligned(1, 1) && perm_offsets_aligned(3, 130) && perm_offsets_aligned(70, 130) &&
+              perm_offsets_aligned(71, 129) && perm_offsets_aligned(65, 17), "the plan of Slot::perm keeps the maxima and the tail aligned");
+
+// room in the slot, the four parts placed, and the skip bytes (host, may be null) on their way to theirs
+[[maybe_unused]] int perm_plan(hpgv_ctx *ctx, Slot *s, size_t n, size_t n_perms, const uint8_t *skip, size_t tail_pitch, PermPlan *P) {
+    const PermOffsets off = perm_offsets(n, n_perms);
+    HIPCHK(ctx, s->perm.reserve_slack(off.tail + n * tail_pitch + 16));
+    char *base = s->perm.as<char>();
+    P->d_n_ge = (int32_t *)base; P->d_max = (double *)(base + off.max); P->d_tail = (int8_t *)(base + off.tail);
+    if (skip && n > 0) {
+        P->d_skip = (uint8_t *)(base + off.skip);
+        HIPCHK(ctx, hipMemcpyAsync(P->d_skip, skip, n, hipMemcpyHostToDevice, s->stream));
+    }
     return HPGV_OK;
 }
 

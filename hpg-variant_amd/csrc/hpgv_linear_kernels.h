@@ -3,7 +3,7 @@
 // --covar).
 //
 // k_linear: one workgroup of four waves owns a tile of 16 rows.
-//   1. The dense product h = sum_obs d f on v_mfma_f64_16x16x4_f64.  Lane (r = lane & 15, kq = lane >> 4) of a wave loads 16
+//   1. The dense product h = sum_obs d f on v_mfma_f64_16x16x4_f64 (linear_tile_walk, shared with the permutations' row pass).  Lane (r = lane & 15, kq = lane >> 4) of a wave loads 16
 //      genotype bytes of row r at position chunk * 64 + 16 kq with one 16-byte load; MFMA step s of the chunk takes the dosage
 //      of byte s as its A operand (missing, pad, a row past the matrix: 0.0) and feature r of position chunk * 64 + 16 kq + s
 //      as its B operand: 16 MFMAs per 64 positions, the lanes of one kq read 128 contiguous bytes of the image.  The
@@ -186,6 +186,37 @@ __device__ __forceinline__ unsigned linear_class(unsigned byte) {
 
 constexpr int LINEAR_ROWS = 16, LINEAR_BATCH = 64, LINEAR_SCAN = 1024;
 
+// The tile walk of a workgroup of four waves over the 16 rows from row0 on (k_linear's step 1 and 2, and the row pass of the
+// permutations, hpgv_linear_perm_kernels.h): wave `wave` takes the chunks of 64 positions wave, wave + 4, ..; lane (r, kq) loads the
+// 16 bytes of row row0 + r at chunk * 64 + 16 kq, and MFMA step s takes the dosage of byte s as A and image column r of that
+// position as B.  acc: the wave's part of sum_obs d f; with VALID accv: its part of sum_obs f, the same steps with A = 1.0 on an
+// observed call; c0, c1, c2: the lane's class counts.  `feat`: 16 doubles per position, padded to whole chunks of 64.
+template <bool VALID>
+__device__ __forceinline__ void linear_tile_walk(const uint8_t *gt, size_t pitch, int n_variants, int row0, const double *feat, int wave, int lane,
+                                                 lin_d4 &acc, lin_d4 &accv, int &c0, int &c1, int &c2) {
+    const int r = lane & 15, kq = lane >> 4;
+    const bool row_ok = row0 + r < n_variants;
+    const uint8_t *rp = gt + (size_t)(row_ok ? row0 + r : row0) * pitch;
+    for (size_t base = (size_t)wave * 64; base < pitch; base += 256) {
+        const size_t pos = base + 16 * (size_t)kq;
+        uint4 g = make_uint4(~0u, ~0u, ~0u, ~0u);
+        if (row_ok && pos < pitch) g = *reinterpret_cast<const uint4 *>(rp + pos);     // (the pitch is a multiple of 16)
+        const double *fp = feat + pos * LINEAR_Q + r;                                     // (the image is padded to 64 positions)
+        double f[16];
+#pragma unroll
+        for (int s = 0; s < 16; ++s) f[s] = fp[s * LINEAR_Q];
+        const unsigned w4[4] = {g.x, g.y, g.z, g.w};
+#pragma unroll
+        for (int s = 0; s < 16; ++s) {
+            const unsigned cls = linear_class((w4[s >> 2] >> (8 * (s & 3))) & 0xFFu);
+            c0 += cls == 0u; c1 += cls == 1u; c2 += cls == 2u;
+            const double d = cls == 3u ? 0.0 : (double)cls;
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(d, f[s], acc, 0, 0, 0);
+            if constexpr (VALID) accv = __builtin_amdgcn_mfma_f64_16x16x4f64(cls == 3u ? 0.0 : 1.0, f[s], accv, 0, 0, 0);
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void k_linear(LinArgs A) {
     // per wave: the feature rows of a batch of flagged positions (64 x 16 doubles), afterwards the solve's A, X, V (3 x 2 KiB)
     // and the row's S (2 KiB); before either, the waves' partial h tiles (4 doubles x 64 lanes each)
@@ -201,27 +232,9 @@ __global__ __launch_bounds__(256) void k_linear(LinArgs A) {
 
     /* 1, 2: the product and the counts */
     {
-        const bool row_ok = row0 + r < A.n_variants;
-        const uint8_t *rp = A.gt + (size_t)(row_ok ? row0 + r : row0) * pitch;
-        lin_d4 acc = {0.0, 0.0, 0.0, 0.0};
+        lin_d4 acc = {0.0, 0.0, 0.0, 0.0}, unused = acc;
         int c0 = 0, c1 = 0, c2 = 0;
-        for (size_t base = (size_t)wave * 64; base < pitch; base += 256) {
-            const size_t pos = base + 16 * (size_t)kq;
-            uint4 g = make_uint4(~0u, ~0u, ~0u, ~0u);
-            if (row_ok && pos < pitch) g = *reinterpret_cast<const uint4 *>(rp + pos);     // (the pitch is a multiple of 16)
-            const double *fp = A.feat + pos * LINEAR_Q + r;                                   // (the image is padded to 64 positions)
-            double f[16];
-#pragma unroll
-            for (int s = 0; s < 16; ++s) f[s] = fp[s * LINEAR_Q];
-            const unsigned w4[4] = {g.x, g.y, g.z, g.w};
-#pragma unroll
-            for (int s = 0; s < 16; ++s) {
-                const unsigned cls = linear_class((w4[s >> 2] >> (8 * (s & 3))) & 0xFFu);
-                c0 += cls == 0u; c1 += cls == 1u; c2 += cls == 2u;
-                const double d = cls == 3u ? 0.0 : (double)cls;
-                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(d, f[s], acc, 0, 0, 0);
-            }
-        }
+        linear_tile_walk<false>(A.gt, pitch, A.n_variants, row0, A.feat, wave, lane, acc, unused, c0, c1, c2);
         c0 += __shfl_xor(c0, 16, 64); c1 += __shfl_xor(c1, 16, 64); c2 += __shfl_xor(c2, 16, 64);
         c0 += __shfl_xor(c0, 32, 64); c1 += __shfl_xor(c1, 32, 64); c2 += __shfl_xor(c2, 32, 64);
         if (kq == 0) { s_cnt[wave][r][0] = c0; s_cnt[wave][r][1] = c1; s_cnt[wave][r][2] = c2; }

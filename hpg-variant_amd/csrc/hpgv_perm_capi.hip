@@ -6,7 +6,7 @@
 // A synchronous entry point checks its arguments, leases a slot and stages like every tool's (stage_chain for a batch,
 // text_front_skip for a text: hpgv_internal.h); its back half is the tool's own chain with the permutation launch between the
 // chain's two halves (assoc_chain / assoc_copy_out, tdt_chain / tdt_copy_out: hpgv_tool_capi.hip) -- the model tests alone keep a
-// chain of their own -- and perm_plan lays out the call's scratch in Slot::perm.
+// chain of their own -- and perm_plan (hpgv_internal.h) lays out the call's scratch in Slot::perm.
 #include "hpgv_internal.h"
 #include "hpgv_assoc_model_kernels.h"
 #include "hpgv_assoc_perm_kernels.h"
@@ -69,42 +69,6 @@ int model_stats_launch(hpgv_ctx *ctx, const int32_t *d_counts8, int n_variants, 
     return launch_profiled(ctx, st, 1, [&] {
         hipLaunchKernelGGL(hpgv::k_assoc_model_stats, dim3((unsigned)((n_variants + 255) / 256)), dim3(256), 0, st, (const int4 *)d_counts8, n_variants, d_chisq5, d_p5);
     });
-}
-
-// where the parts of Slot::perm lie in a call over n rows and n_perms permutations: n_ge per row at 0, the batch maxima per
-// permutation at round_up(4 n, 16), the rows' skip bytes behind them, then -- TDT flips: tail_pitch bytes per row -- the slow
-// families' i8 differences from the next multiple of 16 on
-struct PermPlan {
-    int32_t *d_n_ge = nullptr;
-    double *d_max = nullptr;
-    uint8_t *d_skip = nullptr;         // null when every row takes part
-    int8_t *d_tail = nullptr;
-};
-struct PermOffsets { size_t max, skip, tail; };
-constexpr PermOffsets perm_offsets(size_t n, size_t n_perms) {
-    const size_t off_max = round_up(n * sizeof(int32_t), 16), off_skip = off_max + n_perms * sizeof(double);
-    return {off_max, off_skip, round_up(off_skip + n, 16)};
-}
-// the synchronous calls launch without the *_dev wrappers' alignment refusals: the kernels' 64-bit atomics on the maxima need 8
-// bytes, their 16-byte loads of the tail 16, at any row count -- odd ones above all
-constexpr bool perm_offsets_aligned(size_t n, size_t n_perms) {
-    return perm_offsets(n, n_perms).max % 16 == 0 && perm_offsets(n, n_perms).tail % 16 == 0 && perm_offsets(n, n_perms).skip >= perm_offsets(n, n_perms).max &&
-           perm_offsets(n, n_perms).max >= n * sizeof(int32_t);
-}
-static_assert(perm_offsets_aligned(0, 1) && perm_offsets_aligned(1, 1) && perm_offsets_aligned(3, 130) && perm_offsets_aligned(70, 130) &&
-              perm_offsets_aligned(71, 129) && perm_offsets_aligned(65, 17), "the plan of Slot::perm keeps the maxima and the tail aligned");
-
-// room in the slot, the four parts placed, and the skip bytes (host, may be null) on their way to theirs
-int perm_plan(hpgv_ctx *ctx, Slot *s, size_t n, size_t n_perms, const uint8_t *skip, size_t tail_pitch, PermPlan *P) {
-    const PermOffsets off = perm_offsets(n, n_perms);
-    HIPCHK(ctx, s->perm.reserve_slack(off.tail + n * tail_pitch + 16));
-    char *base = s->perm.as<char>();
-    P->d_n_ge = (int32_t *)base; P->d_max = (double *)(base + off.max); P->d_tail = (int8_t *)(base + off.tail);
-    if (skip && n > 0) {
-        P->d_skip = (uint8_t *)(base + off.skip);
-        HIPCHK(ctx, hipMemcpyAsync(P->d_skip, skip, n, hipMemcpyHostToDevice, s->stream));
-    }
-    return HPGV_OK;
 }
 
 // the back half of hpgv_assoc_model and hpgv_assoc_model_text: the laid-out matrix of a staged call -> class scan, the five
@@ -506,6 +470,32 @@ int hpgv_perm_labels_shuffle(const uint8_t *condition, int n_samples, int n_perm
             uint64_t draw = 0;
             for (size_t i = nc; i > 1; --i) {
                 // Fisher-Yates: position i - 1 swaps with j uniform in [0, i): the high 64 bits of draw x i (bias below i / 2^64)
+                const uint64_t r = splitmix64(key + draw++);
+                const size_t j = (size_t)(((unsigned __int128)r * (unsigned __int128)i) >> 64);
+                std::swap(y[i - 1], y[j]);
+            }
+            for (size_t k = 0; k < nc; ++k) row[cols[k]] = y[k];
+        }
+    } catch (...) { return HPGV_ERR_NOMEM; }
+    return HPGV_OK;
+}
+
+int hpgv_perm_order_shuffle(const uint8_t *condition, int n_samples, int n_perms, uint64_t seed, int32_t *order_out) {
+    if (n_samples < 0 || n_perms < 0 || (n_samples > 0 && !condition) || ((size_t)n_samples * (size_t)n_perms > 0 && !order_out)) return HPGV_ERR_INVALID;
+    try {
+        std::vector<int32_t> cols;
+        for (int j = 0; j < n_samples; ++j)
+            if (condition[j] == HPGV_COND_AFFECTED || condition[j] == HPGV_COND_UNAFFECTED) cols.push_back(j);
+        const size_t nc = cols.size();
+        std::vector<int32_t> y(nc);
+        for (int q = 0; q < n_perms; ++q) {
+            int32_t *row = order_out + (size_t)q * (size_t)n_samples;
+            for (int j = 0; j < n_samples; ++j) row[j] = j;
+            y = cols;
+            // the keys, the draws and the walk of hpgv_perm_labels_shuffle, over the cohort columns in place of their labels
+            const uint64_t key = splitmix64(seed ^ splitmix64((uint64_t)q));
+            uint64_t draw = 0;
+            for (size_t i = nc; i > 1; --i) {
                 const uint64_t r = splitmix64(key + draw++);
                 const size_t j = (size_t)(((unsigned __int128)r * (unsigned __int128)i) >> 64);
                 std::swap(y[i - 1], y[j]);

@@ -24,11 +24,15 @@ static int run_batch_stats_arrays(run_batch_t *b) {
 static int run_batch_lines(run_batch_t *b) {
     free(b->line_off); free(b->field_off); free(b->status); free(b->ints); free(b->dbl);
     const tool_traits_t *T = tool_of(b->run->tool);
-    if (T->mperm) {
+    if (run_mperm(b->run)) {
         free(b->n_ge);
         b->n_ge = (int32_t *)malloc(sizeof(int32_t) * (size_t)b->max_lines);
         if (!b->bmax) b->bmax = (double *)malloc(sizeof(double) * (size_t)b->run->n_perms);
         if (!b->n_ge || !b->bmax) return HPGV_ERR_NOMEM;
+        if (b->run->tool == RUN_LINEAR) {
+            free(b->t_obs);
+            if (!(b->t_obs = (double *)malloc(sizeof(double) * (size_t)b->max_lines))) return HPGV_ERR_NOMEM;
+        }
     }
     b->line_off = (uint64_t *)malloc(sizeof(uint64_t) * ((size_t)b->max_lines + 1));
     b->field_off = (uint32_t *)malloc(sizeof(uint32_t) * 10 * (size_t)b->max_lines);
@@ -68,7 +72,7 @@ int run_batch_reserve(run_batch_t *b, int lines) {
 void run_batch_free(run_batch_t *b) {
     text_buf_put(b->text, b->text_cap);
     b->text = NULL;
-    free(b->line_off); free(b->field_off); free(b->status); free(b->ints); free(b->dbl); free(b->rows); free(b->n_ge); free(b->bmax);
+    free(b->line_off); free(b->field_off); free(b->status); free(b->ints); free(b->dbl); free(b->rows); free(b->n_ge); free(b->bmax); free(b->t_obs);
     free(b->c8); free(b->hw); free(b->merr); free(b->midx); free(b->mtab); free(b->smiss); free(b->cerr); free(b->gc8); free(b->ghw);
     free(b->keep); free(b->sel); free(b->crows);
     free(b->sp_range); free(b->sp_len); free(b->sp_name); free(b->sp_names);

@@ -126,7 +126,12 @@ static int engine_call(run_t *R, run_batch_t *b, const char **what, int *again) 
     case RUN_LOGISTIC: *what = "hpgv_assoc_logistic_text";
         return hpgv_assoc_logistic_text(g_ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status,
                                         HPGV_RUN_LOGISTIC_MAX_ITER, HPGV_RUN_LOGISTIC_TOL, (hpgv_logistic_result *)b->dbl, NULL);
-    case RUN_LINEAR: *what = "hpgv_assoc_linear_text";
+    case RUN_LINEAR:
+        if (run_mperm(R)) { *what = "hpgv_assoc_linear_perm_text";      /* the records and the permutation of the same batch in one call */
+            return hpgv_assoc_linear_perm_text(g_ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status, (hpgv_linear_result *)b->dbl,
+                                               b->t_obs, b->n_ge, b->bmax);
+        }
+        *what = "hpgv_assoc_linear_text";
         return hpgv_assoc_linear_text(g_ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status, (hpgv_linear_result *)b->dbl, NULL);
     case RUN_GENOME: { *what = "hpgv_ibs_text";            /* on one device of the run, into that device's counts (a batch with more lines than room adds nothing) */
         hpgv_ibs_counts *d_counts = NULL;
@@ -193,7 +198,7 @@ static void *pipe_engine(void *v) {
             pthread_mutex_unlock(&P->mu);
             return NULL;
         }
-        if (tool_of(tool)->mperm) {                       /* the batch's maxima into the run's: max is order-independent */
+        if (run_mperm(P->run)) {                          /* the batch's maxima into the run's: max is order-independent */
             double *tmax = P->run->PM->tmax;
             for (int q = 0; q < P->run->n_perms; q++) if (b->bmax[q] > tmax[q]) tmax[q] = b->bmax[q];
         }
@@ -396,6 +401,13 @@ static int run_cohort(run_t *R, const char *vcf_path, const char *ped_path) {
             }
         }
         if (!rc) rc = assoc_cohort_install(R, cond, y);
+        if (!rc && run_mperm(R)) {                        /* the run's orders, once: shuffles of the cohort that stayed */
+            int32_t *order = (int32_t *)malloc(sizeof(int32_t) * (size_t)R->n_perms * (size_t)(n_samples > 0 ? n_samples : 1));
+            if (!order) rc = HPGV_ERR_NOMEM;
+            if (!rc && (rc = hpgv_perm_order_shuffle(cond, n_samples, R->n_perms, R->perm_seed, order))) host_fail("hpgv_perm_order_shuffle", rc);
+            if (!rc && (rc = hpgv_set_linear_perms(g_ctx, order, R->n_perms))) host_fail("hpgv_set_linear_perms", rc);
+            free(order);
+        }
         free(cond); free(have); free(y);
         break;
     }
@@ -439,7 +451,7 @@ static int create_out(FILE **f, char **path, const char *prefix, const char *suf
 /* the tool's output files (split: its files as the records come).  The filter tool's .rejected is created empty without
  * save_rejected (filter_runner.c:63-68); stats: one file per phenotype (stats_runner.c:267-297), and its accumulator */
 static int run_outputs(run_t *R, const char *out_path) {
-    if ((R->clump && run_clump_new(R)) || (tool_of(R->tool)->mperm && run_perm_new(R))) return HPGV_ERR_NOMEM;
+    if ((R->clump && run_clump_new(R)) || (run_mperm(R) && run_perm_new(R))) return HPGV_ERR_NOMEM;
     if (tool_of(R->tool)->pairs) return run_genome_new(R);      /* (their files are written when the run ends: run_genome_write, run_grm_write) */
     const char *suffix = R->tool == RUN_STATS ? ".stats-variants" : R->tool == RUN_FILTER ? (R->out_bgzf ? ".filtered.gz" : ".filtered") : "";
     int rc = R->tool == RUN_SPLIT ? HPGV_OK : create_out(&R->out, &R->path, out_path, suffix);
@@ -632,9 +644,10 @@ static int run_finish(run_t *R, int rc, const char *out_path) {
         R->t_sort = now_s() - t0;
     }
     if (R->tool == RUN_STATS && !rc) rc = run_stats_write(R, out_path);
-    if (T->mperm) {
+    if (run_mperm(R)) {
         if (!rc && R->PM) rc = run_perm_write(R, out_path);
-        if (g_ctx) (void)(T->cohort == COHORT_FAMILIES ? hpgv_set_tdt_flips(g_ctx, NULL, 0) : hpgv_set_perm_labels(g_ctx, NULL, 0));
+        if (g_ctx) (void)(T->cohort == COHORT_FAMILIES ? hpgv_set_tdt_flips(g_ctx, NULL, 0) : T->cohort == COHORT_TRAIT ? hpgv_set_linear_perms(g_ctx, NULL, 0)
+                                                                                                     : hpgv_set_perm_labels(g_ctx, NULL, 0));
         run_perm_free(R);
     }
     if (T->covar && g_ctx) (void)hpgv_set_covariates(g_ctx, NULL, 0, 0);
@@ -808,7 +821,7 @@ int hpgv_run_assoc_model(const char *vcf_path, const char *ped_path, const char 
 /* the regressions' run: n_covar checked, the phenotype file (linear; NULL: the PED's sixth column), then the covariate file (NULL: none),
  * read and checked before the engine starts; then RUN_MODEL's pipeline with the tool's own engine call */
 static int run_regression(run_tool_t tool, const char *vcf_path, const char *ped_path, const char *pheno_path, const char *covar_path, int n_covar,
-                          const char *out_path, size_t batch_bytes, long *n_variants_out, long *n_samples_used_out) {
+                          const char *out_path, int n_perms, uint64_t seed, size_t batch_bytes, long *n_variants_out, long *n_samples_used_out) {
     if (n_covar < 0 || (n_covar > 0 && !covar_path)) { snprintf(g_err, sizeof g_err, "n_covar %d: not negative, and 0 without a covariate file", n_covar); return HPGV_ERR_INVALID; }
     covar_table_t T, P;
     memset(&T, 0, sizeof T); memset(&P, 0, sizeof P);
@@ -816,7 +829,7 @@ static int run_regression(run_tool_t tool, const char *vcf_path, const char *ped
     if (pheno_path && !(rc = covar_table_read(pheno_path, &P)) && covar_table_columns(&P, 1) < 0) rc = HPGV_ERR_INVALID;
     if (!rc && covar_path && !(rc = covar_table_read(covar_path, &T)) && (use = covar_table_columns(&T, n_covar)) < 0) rc = HPGV_ERR_INVALID;
     if (!rc) {
-        run_t R = { .tool = tool, .filters = g_filters, .covar = covar_path ? &T : NULL, .n_covar = use, .pheno = pheno_path ? &P : NULL };
+        run_t R = { .tool = tool, .filters = g_filters, .covar = covar_path ? &T : NULL, .n_covar = use, .pheno = pheno_path ? &P : NULL, .n_perms = n_perms, .perm_seed = seed };
         rc = run_file(&R, vcf_path, ped_path, out_path, batch_bytes, n_variants_out);
         if (n_samples_used_out && !rc) *n_samples_used_out = R.n_used;
     }
@@ -828,7 +841,7 @@ int hpgv_run_assoc_logistic(const char *vcf_path, const char *ped_path, const ch
                             size_t batch_bytes, long *n_variants_out, long *n_samples_used_out) {
     if (n_samples_used_out) *n_samples_used_out = 0;
     if (run_args(n_variants_out, vcf_path && ped_path && out_path, "vcf_path, ped_path and out_path must not be NULL")) return HPGV_ERR_INVALID;
-    return run_regression(RUN_LOGISTIC, vcf_path, ped_path, NULL, covar_path, n_covar, out_path, batch_bytes, n_variants_out, n_samples_used_out);
+    return run_regression(RUN_LOGISTIC, vcf_path, ped_path, NULL, covar_path, n_covar, out_path, 0, 0, batch_bytes, n_variants_out, n_samples_used_out);
 }
 
 int hpgv_run_assoc_linear(const char *vcf_path, const char *ped_path, const char *pheno_path, const char *covar_path, int n_covar,
@@ -836,7 +849,17 @@ int hpgv_run_assoc_linear(const char *vcf_path, const char *ped_path, const char
     if (n_samples_used_out) *n_samples_used_out = 0;
     if (run_args(n_variants_out, vcf_path && out_path, "vcf_path and out_path must not be NULL")) return HPGV_ERR_INVALID;
     if (!ped_path && !pheno_path) { snprintf(g_err, sizeof g_err, "the trait needs a PED file or a phenotype file (ped_path and pheno_path are NULL)"); return HPGV_ERR_INVALID; }
-    return run_regression(RUN_LINEAR, vcf_path, ped_path, pheno_path, covar_path, n_covar, out_path, batch_bytes, n_variants_out, n_samples_used_out);
+    return run_regression(RUN_LINEAR, vcf_path, ped_path, pheno_path, covar_path, n_covar, out_path, 0, 0, batch_bytes, n_variants_out, n_samples_used_out);
+}
+
+/* the linear run with max(T) permutations of the reduced model's residuals: hpgv_run_assoc_linear's file and <out_path>.mperm */
+int hpgv_run_assoc_linear_perm(const char *vcf_path, const char *ped_path, const char *pheno_path, const char *covar_path, int n_covar,
+                               const char *out_path, int n_perms, uint64_t seed, size_t batch_bytes, long *n_variants_out, long *n_samples_used_out) {
+    if (n_samples_used_out) *n_samples_used_out = 0;
+    if (run_args(n_variants_out, vcf_path && out_path, "vcf_path and out_path must not be NULL")) return HPGV_ERR_INVALID;
+    if (n_perms < 1) { snprintf(g_err, sizeof g_err, "n_perms must be at least 1"); return HPGV_ERR_INVALID; }
+    if (!ped_path && !pheno_path) { snprintf(g_err, sizeof g_err, "the trait needs a PED file or a phenotype file (ped_path and pheno_path are NULL)"); return HPGV_ERR_INVALID; }
+    return run_regression(RUN_LINEAR, vcf_path, ped_path, pheno_path, covar_path, n_covar, out_path, n_perms, seed, batch_bytes, n_variants_out, n_samples_used_out);
 }
 
 int hpgv_run_tdt(const char *vcf_path, const char *ped_path, const char *out_path, size_t batch_bytes, long *n_variants_out) {

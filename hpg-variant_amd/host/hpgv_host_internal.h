@@ -148,7 +148,9 @@ typedef struct {
  * RUN_GENOME: sample relatedness (hpgv_run_genome): no line per record, one file of sample pairs written when the run ends;
  * RUN_GRM: the genetic relationship matrix (hpgv_run_grm): no line per record, three files written when the run ends;
  * RUN_LOGISTIC: the logistic regression with covariates (hpgv_run_assoc_logistic);
- * RUN_LINEAR: the linear regression of a quantitative trait with covariates (hpgv_run_assoc_linear) */
+ * RUN_LINEAR: the linear regression of a quantitative trait with covariates (hpgv_run_assoc_linear) and, in a run with n_perms >= 1
+ * (hpgv_run_assoc_linear_perm), the max(T) permutations of the reduced model's residuals: the same file plus <out>.mperm -- the one
+ * tool whose .mperm is a property of the run, not of the table (run_mperm) */
 typedef enum { RUN_CHISQ = CHI_SQUARE, RUN_FISHER = FISHER, RUN_TDT, RUN_VCF2EPI, RUN_AGGREGATE, RUN_STATS, RUN_FILTER, RUN_SPLIT, RUN_CHISQ_PERM, RUN_TDT_PERM,
                RUN_MODEL, RUN_MODEL_PERM, RUN_GENOME, RUN_GRM, RUN_LOGISTIC, RUN_LINEAR } run_tool_t;
 enum { RUN_N_TOOLS = RUN_LINEAR + 1 };                /* (index 0, the assoc task NONE, is no tool) */
@@ -210,6 +212,7 @@ typedef struct {
                                                           * chisq5 per line and, from dbl + 5 * max_lines, p5 per line; genome and grm: class4 per line in ints;
                                                           * logistic, linear: one hpgv_logistic_result / hpgv_linear_result (six doubles' room) per line in dbl */
     int32_t *n_ge; double *bmax;                         /* the permutation tools: permutations at or above the observed statistic per line; the batch's maximum per permutation */
+    double *t_obs;                                       /* the linear run with permutations: the permuted statistic's observed value per line (the others' stands in ::dbl) */
     uint8_t *rows; size_t rows_cap; int row_width;       /* vcf2epi: one dataset row per line */
     int stats;                                           /* aggregate / stats: the counters of hpgv_stats_text */
     int32_t *c8, *merr, *midx, *mtab, *smiss, *cerr; double *hw;
@@ -331,6 +334,8 @@ typedef struct run {
     const covar_table_t *pheno;                          /* RUN_LINEAR: the phenotype file (NULL: the PED's sixth column) */
     double t_opened, t_header, t_sort;
 } run_t;
+/* the run writes <out>.mperm: the permutation tools of the table, and the linear run when it is given permutations */
+static inline int run_mperm(const run_t *R) { return tool_of(R->tool)->mperm || (R->tool == RUN_LINEAR && R->n_perms > 0); }
 
 enum { RUN_ENGINES_MAX = 16, RUN_NB_MAX = RUN_ENGINES_MAX + 3, RUN_FMT_BUFS = 64 };
 

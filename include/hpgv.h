@@ -444,6 +444,76 @@ int  hpgv_linear_fit(const uint8_t *cls, const double *y, const double *cov, int
  * is large).  NaN for a NaN t or df < 1.  The function the kernel compiles too. */
 double hpgv_linear_t_p(double t, int df);
 
+/* ---- permutations of the linear statistic: max(T) empirical p-values of the quantitative-trait regression (PLINK's --linear
+ *      --mperm; no reference counterpart, and parity with PLINK is unpinned: this block is the specification).
+ *
+ *      Cohort columns, the byte rule, the dosage d in {0, 1, 2} and the design [1, d, c_1 .. c_C] are those of "Linear regression".
+ *      N = the number of cohort columns, p = C + 2, df = N - p for every row: missing calls are imputed by the row's mean dosage.
+ *      The reduced model's fitted values stay in place and its residuals are permuted (Freedman and Lane 1983).
+ *
+ *      Once per hpgv_set_linear_perms, on the host, in f64, over the cohort positions in layout order (the host fit: index
+ *      order), every dot product one fma per term:
+ *          Q_1 .. Q_C   an orthonormal basis of the centred covariates by modified Gram-Schmidt in column order: column k, centred
+ *                       by its mean, loses Q_j (Q_j . v) for j = 1 .. k - 1 one after the other, v what the earlier steps left, and
+ *                       is scaled to length 1.  A column whose remaining squared norm is <= 1e-12 x its centred squared norm makes
+ *                       the covariates collinear: HPGV_ERR_INVALID.
+ *          e            = y - m_y with Q_1 .. Q_C taken out the same way: the residual of the reduced model.  ss_0 = e . e.
+ *          eps_p(j)     = e(order_p(j)) for permutation p of the cohort columns.
+ *          E_p          = eps_p - mean(eps_p) with Q_1 .. Q_C taken out the same way.  ss_p = E_p . E_p.
+ *      Per row v, O its observed cohort positions, n_obs, n_1, n_2 its integer class counts:
+ *          mu = (n_1 + 2 n_2) / n_obs,   w_s = d_s - mu on O and 0 on a missing call (the mean-imputed, centred dosage),
+ *          sw2 = (n_1 + 4 n_2) - n_obs mu^2,   D = sw2 - sum_k (sum_O d Q_k - mu sum_O Q_k)^2.
+ *          The row takes no part if n_obs = 0, sw2 <= 0, D <= 1e-12 sw2 or df < 1: t_obs = NaN, n_ge = 0, never in a maximum.
+ *      Per (v, p):
+ *          u = sum_O d E_p - mu sum_O E_p  (two products, over the dosage plane and the valid plane),   r2 = u^2 / (D ss_p),
+ *          T_p = sign(u) sqrt(df r2 / (1 - r2)) when r2 < 1 - 1e-12, else NaN (a NaN r2 gives NaN).
+ *      T_obs is the same function of e and ss_0.  |T| is what is compared and what enters the maxima.
+ *
+ *      For a row without missing calls T_obs equals hpgv_assoc_linear's stat up to rounding (Frisch-Waugh-Lovell).  For a row with
+ *      missing calls T_obs is the statistic of the mean-imputed row, NOT of the observed subset that hpgv_assoc_linear fits: an
+ *      exact refit per subset needs a p x p solve per (row, permutation), while under imputation the projection is shared by all
+ *      rows and a (row, permutation) costs two dot products whatever C is -- the whole scan is one f64 matrix product.  Mean
+ *      imputation is what hpgv_score does with a missing call.
+ *
+ *      Outputs per call, by the rules of hpgv_assoc_perm_dev: t_obs[v]; n_ge[v] = #{p : |T_p| >= |T_obs|}; batch_max[p] = max_v
+ *      |T_p(v)| over the rows that take part (0.0 when none does; a NaN never enters).  Batches merge by the element-wise maximum;
+ *      then hpgv_perm_pvalues with |t_obs|. */
+/* Host only.  order_out[p * n_samples + j] = the VCF column whose residual column j takes under permutation p: the counter-based
+ * SplitMix64 keys and the Fisher-Yates walk of hpgv_perm_labels_shuffle over the list of cohort columns in VCF order (row p does
+ * not depend on n_perms).  HPGV_COND_OTHER columns map to themselves. */
+int  hpgv_perm_order_shuffle(const uint8_t *condition, int n_samples, int n_perms, uint64_t seed, int32_t *order_out);
+/* order: n_perms rows of n_samples columns as hpgv_perm_order_shuffle writes them (what a row holds in HPGV_COND_OTHER columns is
+ * not read).  After hpgv_set_cohort and hpgv_set_phenotype (else HPGV_ERR_STATE).  A row that is not a bijection of the cohort
+ * columns and collinear covariates are HPGV_ERR_INVALID; more than 1 048 576 permutations HPGV_ERR_UNSUPPORTED; an image that does
+ * not fit the device HPGV_ERR_NOMEM.  n_perms == 0 drops the permutations; so do hpgv_set_phenotype, hpgv_set_covariates and
+ * hpgv_set_cohort.  A group context gives every member the permutations.  The device image has the layout of the linear model's
+ * features in tiles of 16 columns -- [tile][position][16 doubles], positions rounded up to 64, zeros under pads: tile 0 holds
+ * Q_1 .. Q_C and e, tile 1 + p / 16 holds E_p in column p % 16 -- with ss_0, ss_1 .. behind it. */
+int  hpgv_set_linear_perms(hpgv_ctx *ctx, const int32_t *order, int n_perms);
+/* d_gt in assoc layout (16-byte aligned) -> d_t_obs[v], d_n_ge[v], d_batch_max[p] (8-byte aligned) and, unless NULL, d_perm_t
+ * [v * n_perms + p] (8-byte aligned): every T_p(v), NaN where the definition says so.  Two launches, asynchronous on `stream`: the
+ * row pass (mu, D, T_obs per row) and the product of 64 rows x 128 permutations per workgroup on v_mfma_f64_16x16x4_f64.  The sum
+ * over the positions has a fixed order and integer atomics alone merge the workgroups: T_p(v) depends on row v only, a matrix
+ * passed whole or in pieces gives bit-identical d_perm_t, and so do two runs.  Not to be called on two streams at once (the row
+ * pass's scratch is the context's).  HPGV_ERR_STATE without a cohort, a phenotype or permutations; HPGV_ERR_INVALID for
+ * n_variants < 0, a NULL or misaligned pointer. */
+int  hpgv_assoc_linear_perm_dev(hpgv_ctx *ctx, const uint8_t *d_gt, int n_variants, double *d_t_obs, int32_t *d_n_ge,
+                                double *d_batch_max, double *d_perm_t /* may be NULL */, void *stream);
+/* The same on a host batch in VCF column order and on a text, built as hpgv_assoc_perm and hpgv_assoc_perm_text are; out[v]: the
+ * hpgv_assoc_linear record of the same row.  A line of a text that is no record or that a record filter rejects takes no part.
+ * batch_max is written for n_variants == 0 too.  Synchronous and thread-safe; a group context deals the call to a member. */
+int  hpgv_assoc_linear_perm(hpgv_ctx *ctx, const uint8_t *gt, size_t pitch, int n_variants, hpgv_linear_result *out,
+                            double *t_obs, int32_t *n_ge, double *batch_max);
+int  hpgv_assoc_linear_perm_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, int max_lines, int *n_lines,
+                                 uint64_t *line_off, uint32_t *field_off, int32_t *status, hpgv_linear_result *out,
+                                 double *t_obs, int32_t *n_ge, double *batch_max);
+/* The definition on the host, samples in index order (every one of the n samples is a cohort column), for one row: cls, y and cov
+ * as hpgv_linear_fit takes them, order[p * n + j] the sample whose residual sample j takes -> *t_obs and t_perm[p].  It compiles
+ * the functions the kernels compile: row scalars -> D, and (u, D, ss, df) -> T.  No GPU call, no context.  HPGV_ERR_INVALID for
+ * what hpgv_linear_fit refuses, an order row that is no bijection of 0 .. n - 1, collinear covariates. */
+int  hpgv_linear_perm_fit(const uint8_t *cls, const double *y, const double *cov, int n, int n_covar, const int32_t *order,
+                          int n_perms, double *t_obs, double *t_perm);
+
 /* d_gt in tdt layout -> d_tu[v] = {t1, t2} (int32 x2) */
 int  hpgv_tdt_scan_dev(hpgv_ctx *ctx, const uint8_t *d_gt, int n_variants,
                        const uint8_t *d_is_x, int32_t *d_tu, void *stream);
@@ -1475,6 +1545,11 @@ int  hpgv_pca_chol_inv(int L, const double *G, double *M);
 /* streaming-read ceiling probe: reads `bytes` from d_buf with the scan's load
  * shape and no arithmetic; returns the kernel time in ms (diagnostic) */
 int  hpgv_read_probe(hpgv_ctx *ctx, const uint8_t *d_buf, size_t bytes, int iters, float *ms);
+/* f64 matrix-core ceiling probe: 8 workgroups of four waves per CU, every wave `steps` rounds of eight independent
+ * v_mfma_f64_16x16x4_f64 and no memory traffic; *ms: the kernel time (mean of iters launches after one), *flop: the floating-point
+ * operations of one launch, 2 x 16 x 16 x 4 per instruction (diagnostic: what tools/bench_linear_perm.py holds the permutation
+ * kernel against) */
+int  hpgv_mfma_f64_probe(hpgv_ctx *ctx, int steps, int iters, float *ms, double *flop);
 
 #ifdef __cplusplus
 }

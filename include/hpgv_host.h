@@ -364,6 +364,17 @@ int  hpgv_run_assoc_logistic(const char *vcf_path, const char *ped_path, const c
  * Same filters, record filters and input forms (plain, gzip, bgzip) as hpgv_run_assoc_logistic. */
 int  hpgv_run_assoc_linear(const char *vcf_path, const char *ped_path, const char *pheno_path, const char *covar_path, int n_covar,
                            const char *out_path, size_t batch_bytes, long *n_variants_out, long *n_samples_used_out);
+/* The same run with max(T) permutations of the linear statistic (include/hpgv.h "permutations of the linear statistic"; PLINK's
+ * --linear --mperm): out_path is hpgv_run_assoc_linear's file byte for byte, and <out_path>.mperm holds "#CHR POS ID EMP1 EMP2" in
+ * the format of the other permutation runs, nan where a row takes no part.  The orders are hpgv_perm_order_shuffle(seed) over the
+ * cohort that stayed; every batch goes through hpgv_assoc_linear_perm_text (the records and the permutation in one call) and the
+ * batches' maxima merge by maximum, so neither file depends on batch_bytes, engine threads, input form or devices.  A row with
+ * missing calls is permuted with its mean-imputed dosage: its EMP1 / EMP2 belong to that statistic, not to the STAT column's fit
+ * of the observed subset.  HPGV_ERR_INVALID before anything is opened for n_perms < 1 or a NULL path, and for what
+ * hpgv_run_assoc_linear refuses; collinear covariates fail the run when the permutations are set. */
+int  hpgv_run_assoc_linear_perm(const char *vcf_path, const char *ped_path, const char *pheno_path, const char *covar_path, int n_covar,
+                                const char *out_path, int n_perms, uint64_t seed, size_t batch_bytes, long *n_variants_out,
+                                long *n_samples_used_out);
 /* The covariate file's reader on its own: the first n_covar value columns (0: all) for the samples names[0 .. n_names), cov with
  * HPGV_LOGISTIC_MAX_COVAR doubles per name, have[j] = 1 where names[j] has a line of finite values (else 0, and zeros in cov);
  * *n_covar_out: the columns used.  HPGV_ERR_INVALID as above (message in hpgv_host_last_error).  No GPU call. */
