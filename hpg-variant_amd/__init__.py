@@ -72,6 +72,7 @@ SYMBOLS = [
     "hpgv_set_perm_labels", "hpgv_assoc_perm_dev", "hpgv_assoc_perm", "hpgv_assoc_perm_text", "hpgv_perm_labels_shuffle", "hpgv_perm_pvalues",
     "hpgv_set_tdt_flips", "hpgv_tdt_perm_dev", "hpgv_tdt_perm", "hpgv_tdt_perm_text", "hpgv_perm_flips_shuffle",
     "hpgv_assoc_model_scan_dev", "hpgv_assoc_model_stats_dev", "hpgv_assoc_trend_perm_dev", "hpgv_assoc_model", "hpgv_assoc_model_text",
+    "hpgv_set_strata", "hpgv_assoc_cmh_dev", "hpgv_assoc_cmh", "hpgv_assoc_cmh_text", "hpgv_cmh_fit",
     "hpgv_set_covariates", "hpgv_assoc_logistic_dev", "hpgv_assoc_logistic", "hpgv_assoc_logistic_text", "hpgv_logistic_fit",
     "hpgv_set_phenotype", "hpgv_assoc_linear_dev", "hpgv_assoc_linear", "hpgv_assoc_linear_text", "hpgv_linear_fit", "hpgv_linear_t_p",
     "hpgv_perm_order_shuffle", "hpgv_set_linear_perms", "hpgv_assoc_linear_perm_dev", "hpgv_assoc_linear_perm", "hpgv_assoc_linear_perm_text", "hpgv_linear_perm_fit", "hpgv_mfma_f64_probe",
@@ -102,6 +103,10 @@ SCORE_WEIGH_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER
 # hpgv_logistic_result: {double beta, se, stat, p; int32 n_obs, iters, status, pad}, 48 bytes
 LOGISTIC_RESULT = np.dtype([("beta", np.float64), ("se", np.float64), ("stat", np.float64), ("p", np.float64),
                             ("n_obs", np.int32), ("iters", np.int32), ("status", np.int32), ("pad", np.int32)])
+# hpgv_cmh_result: {int32 n_strata_cmh, n_strata_bd; double chisq, p, or_mh, se, l95, u95, chisq_bd, p_bd}, 72 bytes
+CMH_RESULT = np.dtype([("n_strata_cmh", np.int32), ("n_strata_bd", np.int32), ("chisq", np.float64), ("p", np.float64), ("or_mh", np.float64),
+                       ("se", np.float64), ("l95", np.float64), ("u95", np.float64), ("chisq_bd", np.float64), ("p_bd", np.float64)])
+CMH_MAX_STRATA = 1024               # HPGV_CMH_MAX_STRATA
 # hpgv_linear_result: {double beta, se, stat, p; int32 n_obs, df, status, pad}, 48 bytes
 LINEAR_RESULT = np.dtype([("beta", np.float64), ("se", np.float64), ("stat", np.float64), ("p", np.float64),
                           ("n_obs", np.int32), ("df", np.int32), ("status", np.int32), ("pad", np.int32)])
@@ -268,6 +273,11 @@ def load():
     L.hpgv_assoc_model.argtypes = [vp, vp, sz, i32] + [vp] * 5
     L.hpgv_assoc_model_text.argtypes = [vp, C.c_char_p, sz, i32, C.POINTER(i32), vp, vp, vp] + [vp] * 5
     L.hpgv_set_covariates.argtypes = [vp, vp, i32, i32]
+    L.hpgv_set_strata.argtypes = [vp, vp, i32, i32]
+    L.hpgv_assoc_cmh_dev.argtypes = [vp, vp, i32, vp, vp, vp, vp]
+    L.hpgv_assoc_cmh.argtypes = [vp, vp, sz, i32, vp, vp, vp]
+    L.hpgv_assoc_cmh_text.argtypes = [vp, C.c_char_p, sz, i32, C.POINTER(i32), vp, vp, vp, vp, vp]
+    L.hpgv_cmh_fit.argtypes = [vp, i32, vp]
     L.hpgv_assoc_logistic_dev.argtypes = [vp, vp, i32, i32, C.c_double, vp, vp, vp]
     L.hpgv_assoc_logistic.argtypes = [vp, vp, sz, i32, i32, C.c_double, vp, vp]
     L.hpgv_assoc_logistic_text.argtypes = [vp, C.c_char_p, sz, i32, C.POINTER(i32), vp, vp, vp, i32, C.c_double, vp, vp]
@@ -418,6 +428,58 @@ def run_assoc_logistic(vcf_path, ped_path, covar_path, out_path, n_covar=0, batc
         e.code = rc
         raise e
     return n.value, used.value
+
+
+def run_assoc_cmh(vcf_path, ped_path, within_path, out_path, batch_bytes=1 << 22):
+    """hpgv_run_assoc_cmh of libhpgv_host.so (include/hpgv_host.h): the stratified association test per variant over the strata of
+    the within file at out_path.  Paths may be None (the call then fails with ERR_INVALID).  Returns (variants written, cohort
+    samples used, strata)."""
+    _build.build_host_lib()
+    H = C.CDLL(_build.HOSTLIB)
+    H.hpgv_run_assoc_cmh.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_int)]
+    H.hpgv_host_last_error.restype = C.c_char_p
+    n, used, k = C.c_long(0), C.c_long(0), C.c_int(0)
+    enc = lambda q: None if q is None else os.fsencode(q)
+    rc = H.hpgv_run_assoc_cmh(enc(vcf_path), enc(ped_path), enc(within_path), enc(out_path), batch_bytes, C.byref(n), C.byref(used), C.byref(k))
+    if rc != OK:
+        e = HpgvError("hpgv_run_assoc_cmh -> %d: %s" % (rc, (H.hpgv_host_last_error() or b"").decode(errors="replace")))
+        e.code = rc
+        raise e
+    return n.value, used.value, k.value
+
+
+def within_read(within_path, names, take=None):
+    """hpgv_host_within_read of libhpgv_host.so: the stratum of every sample of `names` (a list of str) by the within file, -1
+    without a line or where take (n,) is 0; strata numbered by first appearance among the samples taken.  Returns (stratum (n,)
+    int32, n_strata).  Raises HpgvError (code ERR_INVALID) on a short or ragged line, a duplicate id, more than CMH_MAX_STRATA
+    cluster names or an unreadable file."""
+    _build.build_host_lib()
+    H = C.CDLL(_build.HOSTLIB)
+    H.hpgv_host_within_read.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+    H.hpgv_host_last_error.restype = C.c_char_p
+    arr = (C.c_char_p * max(len(names), 1))(*[os.fsencode(q) for q in names])
+    stratum = np.full(max(len(names), 1), -1, np.int32)
+    tk = None if take is None else _np(take, np.uint8)
+    k = C.c_int(0)
+    rc = H.hpgv_host_within_read(None if within_path is None else os.fsencode(within_path), arr, len(names), _ptr(tk), _ptr(stratum), C.byref(k))
+    if rc != OK:
+        e = HpgvError("hpgv_host_within_read -> %d: %s" % (rc, (H.hpgv_host_last_error() or b"").decode(errors="replace")))
+        e.code = rc
+        raise e
+    return stratum[:len(names)].copy(), k.value
+
+
+def cmh_fit(tables):
+    """hpgv_cmh_fit: the stratified association of include/hpgv.h on the host.  tables: (K, 4) int32 {A1, A2, U1, U2} per stratum.
+    Returns a CMH_RESULT record.  No device needed."""
+    t = _np(tables, np.int32).reshape(-1, 4)
+    out = np.zeros(1, CMH_RESULT)
+    rc = load().hpgv_cmh_fit(_ptr(t) if len(t) else None, len(t), _ptr(out))
+    if rc != OK:
+        e = HpgvError("hpgv_cmh_fit -> %d" % rc)
+        e.code = rc
+        raise e
+    return out[0]
 
 
 def covar_read(covar_path, names, n_covar=0):
@@ -925,6 +987,7 @@ class Engine:
         self._chk(self.L.hpgv_set_cohort(self.h, _ptr(c), len(c)))
         self._n_perms = 0               # a new cohort drops the label rows
         self._n_covar = 0               # and the covariates
+        self._n_strata = 0              # and the strata
         self._n_samples = len(c)
         return self.assoc_layout()
 
@@ -1107,6 +1170,39 @@ class Engine:
         if not perm:
             return _text_result(nl, max_lines, status=status, counts8=c8, chisq5=chisq5, p5=p5)
         return dict(_text_result(nl, max_lines, status=status, counts8=c8, chisq5=chisq5, p5=p5, n_ge=n_ge), batch_max=bmax[:np_])
+
+    def set_strata(self, stratum, n_strata=None):
+        """hpgv_set_strata: stratum (n_samples,) int32 in VCF column order, negative = in no stratum; n_strata defaults to the largest
+        value + 1.  None, or n_strata 0, drops the strata."""
+        if stratum is None or n_strata == 0:
+            self._chk(self.L.hpgv_set_strata(self.h, None, 0, 0))
+            self._n_strata = 0
+            return
+        st = _np(stratum, np.int32)
+        k = int(st.max()) + 1 if n_strata is None else int(n_strata)
+        self._chk(self.L.hpgv_set_strata(self.h, _ptr(st), len(st), k))
+        self._n_strata = k
+
+    def assoc_cmh(self, gt, is_x=None, tables=False):
+        """hpgv_assoc_cmh: a CMH_RESULT array (nv,) and, with tables, (nv, K, 4) int32 {A1, A2, U1, U2} per stratum."""
+        gt = _np(gt, np.uint8)
+        nv, pitch = gt.shape
+        x = None if is_x is None else _np(is_x, np.uint8)
+        out = np.zeros(nv, CMH_RESULT)
+        tb = np.zeros((nv, getattr(self, "_n_strata", 0), 4), np.int32) if tables else None
+        self._chk(self.L.hpgv_assoc_cmh(self.h, _ptr(gt), pitch, nv, _ptr(x), _ptr(out), _ptr(tb)))
+        return (out, tb) if tables else out
+
+    def assoc_cmh_text(self, text, max_lines=None, tables=False, out=None):
+        """hpgv_assoc_cmh_text: assoc_cmh on VCF data lines, the outputs per line.  out: a CMH_RESULT array to write into (the
+        records of skipped lines stay as they are)."""
+        text, max_lines, m, status, nl = _text_call(text, max_lines)
+        if out is None:
+            out = np.zeros(m, CMH_RESULT)
+        assert out.dtype == CMH_RESULT and len(out) >= m and out.flags.c_contiguous
+        tb = np.zeros((m, getattr(self, "_n_strata", 0), 4), np.int32) if tables else None
+        self._chk(self.L.hpgv_assoc_cmh_text(self.h, text, len(text), max_lines, C.byref(nl), None, None, _ptr(status), _ptr(out), _ptr(tb)))
+        return _text_result(nl, max_lines, status=status, out=out, tables=tb)
 
     def set_covariates(self, cov):
         """hpgv_set_covariates: cov (n_samples, C) in VCF column order; None or no columns clears them."""
@@ -1599,6 +1695,9 @@ class Engine:
 
     def assoc_trend_perm_dev(self, d_gt, n_variants, d_counts8, d_n_ge, d_batch_max, d_perm_sums=None, stream=None):
         self._chk(self.L.hpgv_assoc_trend_perm_dev(self.h, d_gt, n_variants, d_counts8, d_n_ge, d_batch_max, d_perm_sums, stream))
+
+    def assoc_cmh_dev(self, d_gt, n_variants, d_out, d_tables=None, d_is_x=None, stream=None):
+        self._chk(self.L.hpgv_assoc_cmh_dev(self.h, d_gt, n_variants, d_is_x, d_out, d_tables, stream))
 
     def assoc_logistic_dev(self, d_gt, n_variants, d_out, d_coef=None, max_iter=25, tol=1e-10, stream=None):
         self._chk(self.L.hpgv_assoc_logistic_dev(self.h, d_gt, n_variants, int(max_iter), float(tol), d_out, d_coef, stream))

@@ -142,7 +142,7 @@ void hpgv_destroy(hpgv_ctx *ctx) {
     DeviceGuard g(ctx->device);
     (void)hipDeviceSynchronize();
     if (ctx->d_mendel_male) (void)hipFree(ctx->d_mendel_male);
-    for (DevBuf *b : {&ctx->d_sg_chunks, &ctx->d_group_of_col, &ctx->d_cond, &ctx->d_perm, &ctx->d_cov, &ctx->d_lin, &ctx->d_linperm, &ctx->d_linperm_rows, &ctx->d_flips, &ctx->d_flip_tail, &ctx->d_thr, &ctx->assoc.d_cols, &ctx->tdt.d_cols,
+    for (DevBuf *b : {&ctx->d_sg_chunks, &ctx->d_group_of_col, &ctx->d_cond, &ctx->d_perm, &ctx->d_strata, &ctx->d_cmh_tables, &ctx->d_cov, &ctx->d_lin, &ctx->d_linperm, &ctx->d_linperm_rows, &ctx->d_flips, &ctx->d_flip_tail, &ctx->d_thr, &ctx->assoc.d_cols, &ctx->tdt.d_cols,
                       &ctx->stats.d_cols, &ctx->sgroups.d_cols, &ctx->mendel.d_cols}) b->release();
     ctx->tdt_plan.release();
     if (ctx->d_lf_base) (void)hipFree(ctx->d_lf_base);
@@ -287,6 +287,7 @@ int hpgv_set_cohort(hpgv_ctx *ctx, const uint8_t *condition, int n_samples) {
     Layout &L = ctx->assoc;
     ctx->n_perms = ctx->perm_rows = 0;             // the label rows of hpgv_set_perm_labels belong to the cohort they were given for
     ctx->n_covar = 0;                              // and so do the covariates of hpgv_set_covariates
+    ctx->n_strata = ctx->strata_rows = 0;          // and the strata of hpgv_set_strata
     ctx->has_pheno = false; ctx->lin_y.clear(); ctx->lin_cov.clear();      // and the phenotype of hpgv_set_phenotype
     ctx->n_linperms = 0;                           // with the permutations of its residuals (hpgv_set_linear_perms)
     L.n_samples = n_samples;

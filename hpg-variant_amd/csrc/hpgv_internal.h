@@ -2,7 +2,7 @@
 // libhpgv.so: hpgv_capi.hip (contexts, options, cohorts, memory, streams, text aliases), hpgv_scan_capi.hip (the
 // device-resident *_dev launchers), hpgv_text_capi.hip (tokenizer, the text entry points' front half),
 // hpgv_tool_capi.hip (per-batch and text entry points), hpgv_lines_capi.hip (partition / multisplit of lines), and the
-// units whose kernel instantiations compile on their own (hpgv_perm_capi.hip, hpgv_ld_capi.hip, hpgv_ibs_capi.hip, hpgv_grm_capi.hip, hpgv_pca_capi.hip, hpgv_logistic_capi.hip, hpgv_linear_capi.hip, hpgv_epi_capi.hip, hpgv_epi_generic_capi.hip, hpgv_statsall_capi.hip, hpgv_inflate_capi.hip, hpgv_group_capi.hip).
+// units whose kernel instantiations compile on their own (hpgv_perm_capi.hip, hpgv_ld_capi.hip, hpgv_ibs_capi.hip, hpgv_grm_capi.hip, hpgv_pca_capi.hip, hpgv_logistic_capi.hip, hpgv_cmh_capi.hip, hpgv_linear_capi.hip, hpgv_epi_capi.hip, hpgv_epi_generic_capi.hip, hpgv_statsall_capi.hip, hpgv_inflate_capi.hip, hpgv_group_capi.hip).
 // A synchronous entry point has two halves that meet in a Staged: the front puts the call's matrix on the device -- text_front /
 // text_front_skip for a text, stage_chain for a host batch that goes through the kernel chain -- and the tool's back half takes it
 // from there; the permutation calls build theirs from the halves of hpgv_assoc's and hpgv_tdt's (assoc_chain, ..., below).
@@ -244,6 +244,11 @@ struct hpgv_ctx {
     // and pitch, zeros under the pads, perm_rows = n_perms rounded up to 16 rows; dropped by a new cohort
     DevBuf d_perm;
     int n_perms = 0, perm_rows = 0;
+    // strata of the stratified association (hpgv_set_strata): the stratum image in the label matrix's format -- row 2k "stratum k and
+    // affected", row 2k + 1 "stratum k and unaffected", strata_rows = 2 n_strata rounded up to 16 rows; dropped by a new cohort
+    DevBuf d_strata;
+    int n_strata = 0, strata_rows = 0;
+    DevBuf d_cmh_tables;                  // hpgv_assoc_cmh_dev's tables when the caller gives no buffer (the synchronous calls keep theirs in their slot)
     // covariates of the logistic regression (hpgv_set_covariates): one row of assoc.pitch doubles per covariate in the assoc layout's
     // column order, zeros under the pads; dropped by a new cohort
     DevBuf d_cov;

@@ -247,7 +247,7 @@ __global__ __launch_bounds__(256, WAVES) void k_assoc_scan_pipe(const uint8_t *_
 // One thread per variant; same operation order as the reference (the file is
 // built with -ffp-contract=off so no FMA is formed).
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ double chisq_p_value(double x) {
+__host__ __device__ __forceinline__ double chisq_p_value(double x) {
     // 1 - gsl_cdf_chisq_P(x, 1): see oracle/hpgv_oracle.c orc_chisq_p_value
     if (x != x) return x;
     if (x <= 0.0) return 1.0;
@@ -256,6 +256,28 @@ __device__ __forceinline__ double chisq_p_value(double x) {
     if (y > 0.5) P = 1.0 - erfc(sqrt(y));
     else         P = erf(sqrt(y));
     return 1.0 - P;
+}
+
+// the upper chi-square tail for an integer df >= 1 by the finite closed forms (include/hpgv.h "stratified association"):
+//   even df:  e^(-x/2) sum_{i < df/2} (x/2)^i / i!
+//   odd df :  erfc(sqrt(x/2)) + sqrt(2x/pi) e^(-x/2) sum_{i = 1 .. (df-1)/2} x^(i-1) / (1 . 3 ... (2i-1))
+// every sum by the term recurrence, smallest index first.  df == 1 is chisq_p_value itself; NaN in gives NaN out, x <= 0 gives 1,
+// df < 1 gives NaN.  Where e^(-x/2) underflows (x above 1490) every term is 0 and so is the tail
+__host__ __device__ __forceinline__ double chisq_p_value_df(double x, int df) {
+    if (df == 1) return chisq_p_value(x);
+    if (x != x) return x;
+    if (df < 1) return __builtin_nan("");
+    if (x <= 0.0) return 1.0;
+    const double h = x / 2.0, e = exp(-h);
+    if ((df & 1) == 0) {
+        double term = e, sum = e;
+        for (int i = 1; i < df / 2; ++i) { term = term * h / (double)i; sum += term; }
+        return sum < 1.0 ? sum : 1.0;
+    }
+    double term = sqrt(2.0 * x / 3.14159265358979323846) * e, sum = term;
+    for (int i = 2; i <= (df - 1) / 2; ++i) { term = term * x / (double)(2 * i - 1); sum += term; }
+    const double p = erfc(sqrt(h)) + sum;
+    return p < 1.0 ? p : 1.0;
 }
 
 __device__ __forceinline__ double assoc_odds(int A1, int A2, int U1, int U2) {

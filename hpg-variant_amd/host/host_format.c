@@ -161,7 +161,14 @@ static int format_record(char *dst, size_t room, const run_batch_t *b, int i) {
     const run_tool_t file = tool_of(tool)->file;          /* the layout is that of the file the tool writes */
     if (file != RUN_CHISQ && file != RUN_FISHER) { p = PUT_STR(p, l + fo[4], la); *p++ = '\t'; }      /* (theirs has A2 further on) */
     switch (file) {
-    case RUN_MODEL: {                                     /* CHR POS ID A1 A2 AFF UNAFF, then chi-square and p of the five tests */
+    case RUN_MODEL: {
+        if (run_cmh(b->run)) {                            /* the stratified association: CHR POS ID A1 A2 NSTRATA CHISQ_CMH P_CMH OR_MH SE L95 U95 CHISQ_BD P_BD; nan whatever the NaN's sign */
+            const hpgv_cmh_result *r = (const hpgv_cmh_result *)b->dbl + i;
+            const double eight[8] = { r->chisq, r->p, r->or_mh, r->se, r->l95, r->u95, r->chisq_bd, r->p_bd };
+            p = put_fit(p, r->n_strata_cmh, eight, 8);
+            break;
+        }
+        /* CHR POS ID A1 A2 AFF UNAFF, then chi-square and p of the five tests */
         const int32_t *c = b->ints + 8 * (size_t)i;
         const double *x = b->dbl + 5 * (size_t)i, *pv = b->dbl + 5 * (size_t)m + 5 * (size_t)i;
         p = put_i64(p, c[0]); *p++ = '/'; p = put_i64(p, c[1]); *p++ = '/'; p = put_i64(p, c[2]); *p++ = '\t';

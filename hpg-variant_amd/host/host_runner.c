@@ -1,5 +1,5 @@
 /* host_runner.c -- the file runners: reader -> engine threads -> writer (hpgv_run_assoc / tdt / aggregate / stats / vcf2epi /
- * filter / split / genome / grm / logistic / linear).  The VCF tools' own batch steps and writers are in host_vcftools.c, what a run keeps beside its result file in
+ * filter / split / genome / grm / logistic / linear / cmh).  The VCF tools' own batch steps and writers are in host_vcftools.c, what a run keeps beside its result file in
  * host_sideout.c.
  * Part of libhpgv_host.so (see hpgv_host_internal.h for the map of its units). */
 #include "hpgv_host_internal.h"
@@ -120,7 +120,11 @@ static int engine_call(run_t *R, run_batch_t *b, const char **what, int *again) 
         return hpgv_assoc_perm_text(g_ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status,
                                     b->ints, b->ints + m, b->ints + 2 * m, b->ints + 3 * m,
                                     b->dbl, b->dbl + m, b->dbl + 2 * m, b->n_ge, b->bmax);
-    case RUN_MODEL: case RUN_MODEL_PERM: *what = "hpgv_assoc_model_text";
+    case RUN_MODEL: case RUN_MODEL_PERM:
+        if (run_cmh(R)) { *what = "hpgv_assoc_cmh_text";      /* the stratified association: its records in the model tests' doubles */
+            return hpgv_assoc_cmh_text(g_ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status, (hpgv_cmh_result *)b->dbl, NULL);
+        }
+        *what = "hpgv_assoc_model_text";
         return hpgv_assoc_model_text(g_ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status,
                                      b->ints, b->dbl, b->dbl + 5 * (size_t)m, tool == RUN_MODEL_PERM ? b->n_ge : NULL, tool == RUN_MODEL_PERM ? b->bmax : NULL);
     case RUN_LOGISTIC: *what = "hpgv_assoc_logistic_text";
@@ -244,7 +248,8 @@ static uint8_t *cohort_conditions(const run_t *R, const sample_ids_t *ids, int *
 
 /* the assoc cohort of the case-control and trait stages on the device(s), from the condition vector as built so far; y: the trait,
  * or NULL.  With a covariate file (the regressions) a cohort sample without a line of finite values leaves the cohort first, and
- * the matched covariates follow the cohort; n_used: the samples that stayed */
+ * the matched covariates follow the cohort; with a within file (run_cmh) a cohort sample without a line leaves it, and the strata
+ * of those that stay -- numbered by first appearance in VCF column order -- follow the cohort; n_used: the samples that stayed */
 static int assoc_cohort_install(run_t *R, uint8_t *cond, const double *y) {
     const int n_samples = R->n_samples;
     int rc = HPGV_OK;
@@ -257,12 +262,24 @@ static int assoc_cohort_install(run_t *R, uint8_t *cond, const double *y) {
         for (int j = 0; !rc && j < n_samples; j++) if (!have[j]) cond[j] = HPGV_COND_OTHER;
         free(have);
     }
+    int32_t *stratum = NULL;
+    if (!rc && R->within) {
+        uint8_t *take = (uint8_t *)malloc((size_t)n_samples + 1);
+        stratum = (int32_t *)malloc(sizeof(int32_t) * ((size_t)n_samples + 1));
+        if (!take || !stratum) rc = HPGV_ERR_NOMEM;
+        for (int j = 0; !rc && j < n_samples; j++) take[j] = cond[j] == HPGV_COND_AFFECTED || cond[j] == HPGV_COND_UNAFFECTED;
+        if (!rc) rc = within_table_match(R->within, R->names, n_samples, take, stratum, &R->n_strata);
+        for (int j = 0; !rc && j < n_samples; j++) if (stratum[j] < 0) cond[j] = HPGV_COND_OTHER;
+        if (!rc && R->n_strata == 0) { snprintf(g_err, sizeof g_err, "no cohort sample has a line in the within file"); rc = HPGV_ERR_INVALID; }
+        free(take);
+    }
     for (int j = 0; !rc && j < n_samples; j++) R->n_used += cond[j] == HPGV_COND_AFFECTED || cond[j] == HPGV_COND_UNAFFECTED;
     if (!rc && (rc = hpgv_set_cohort(g_ctx, cond, n_samples))) host_fail("hpgv_set_cohort", rc);
     g_assoc_key.set = 0;
     if (!rc && cov && R->n_covar > 0 && (rc = hpgv_set_covariates(g_ctx, cov, n_samples, R->n_covar))) host_fail("hpgv_set_covariates", rc);
     if (!rc && y && (rc = hpgv_set_phenotype(g_ctx, y, n_samples))) host_fail("hpgv_set_phenotype", rc);
-    free(cov);
+    if (!rc && stratum && (rc = hpgv_set_strata(g_ctx, stratum, n_samples, R->n_strata))) host_fail("hpgv_set_strata", rc);
+    free(cov); free(stratum);
     return rc;
 }
 
@@ -478,8 +495,8 @@ static int run_headers(run_t *R) {
     if (T->header) {                                     /* the sorted results: the first line, which the order check starts from */
         if (T->file == RUN_TDT) tdt_write_output_header(out);
         else if (T->file == RUN_CHISQ || T->file == RUN_FISHER) assoc_write_output_header((enum ASSOC_task)T->file, out);      /* (the reference's writers) */
-        else fprintf(out, "%s\n", T->header);
-        order_track_keep(&R->ord, T->header, strlen(T->header));
+        else fprintf(out, "%s\n", run_header(R));
+        order_track_keep(&R->ord, run_header(R), strlen(run_header(R)));
         return HPGV_OK;
     }
     switch (R->tool) {
@@ -651,6 +668,7 @@ static int run_finish(run_t *R, int rc, const char *out_path) {
         run_perm_free(R);
     }
     if (T->covar && g_ctx) (void)hpgv_set_covariates(g_ctx, NULL, 0, 0);
+    if (run_cmh(R) && g_ctx) (void)hpgv_set_strata(g_ctx, NULL, 0, 0);
     if (T->cohort == COHORT_TRAIT && g_ctx) (void)hpgv_set_phenotype(g_ctx, NULL, 0);
     if (R->CL) {
         if (!rc) rc = run_clump_write(R, out_path);
@@ -842,6 +860,24 @@ int hpgv_run_assoc_logistic(const char *vcf_path, const char *ped_path, const ch
     if (n_samples_used_out) *n_samples_used_out = 0;
     if (run_args(n_variants_out, vcf_path && ped_path && out_path, "vcf_path, ped_path and out_path must not be NULL")) return HPGV_ERR_INVALID;
     return run_regression(RUN_LOGISTIC, vcf_path, ped_path, NULL, covar_path, n_covar, out_path, 0, 0, batch_bytes, n_variants_out, n_samples_used_out);
+}
+
+/* the stratified association's run: the within file read and checked before the engine starts, then RUN_MODEL's pipeline with the
+ * tool's own engine call */
+int hpgv_run_assoc_cmh(const char *vcf_path, const char *ped_path, const char *within_path, const char *out_path,
+                       size_t batch_bytes, long *n_variants_out, long *n_samples_used_out, int *n_strata_out) {
+    if (n_samples_used_out) *n_samples_used_out = 0;
+    if (n_strata_out) *n_strata_out = 0;
+    if (run_args(n_variants_out, vcf_path && ped_path && within_path && out_path, "vcf_path, ped_path, within_path and out_path must not be NULL")) return HPGV_ERR_INVALID;
+    covar_table_t W;
+    int rc = within_table_read(within_path, &W);
+    if (rc) return rc;
+    run_t R = { .tool = RUN_MODEL, .filters = g_filters, .within = &W };
+    rc = run_file(&R, vcf_path, ped_path, out_path, batch_bytes, n_variants_out);
+    if (n_samples_used_out && !rc) *n_samples_used_out = R.n_used;
+    if (n_strata_out && !rc) *n_strata_out = R.n_strata;
+    covar_table_free(&W);
+    return rc;
 }
 
 int hpgv_run_assoc_linear(const char *vcf_path, const char *ped_path, const char *pheno_path, const char *covar_path, int n_covar,

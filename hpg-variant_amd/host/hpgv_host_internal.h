@@ -19,7 +19,7 @@
  *   host_vcftools.c    the VCF tools' batch steps and writers: filter partition, split keys and files
  *   host_records.c     the record filters of hpgv_run_set_record_filters: regions, coverage, variant types, inheritance
  *   host_sideout.c     what a run keeps beside its result file and writes at its end: .mperm, .clumped, the stats report
- *   host_covar.c       the covariate file of the logistic and linear runs (and the latter's phenotype file): read whole, matched to the VCF's sample names
+ *   host_covar.c       the covariate file of the logistic and linear runs (and the latter's phenotype file): read whole, matched to the VCF's sample names; the within file of the CMH run by the same reader
  *   host_pca.c         the principal components of a run's relationship matrix, or of .grm.bin files: .eigenval, .eigenvec
  *   host_runner.c      the file runners' pipeline and their runs (hpgv_run_*)
  */
@@ -150,7 +150,9 @@ typedef struct {
  * RUN_LOGISTIC: the logistic regression with covariates (hpgv_run_assoc_logistic);
  * RUN_LINEAR: the linear regression of a quantitative trait with covariates (hpgv_run_assoc_linear) and, in a run with n_perms >= 1
  * (hpgv_run_assoc_linear_perm), the max(T) permutations of the reduced model's residuals: the same file plus <out>.mperm -- the one
- * tool whose .mperm is a property of the run, not of the table (run_mperm) */
+ * tool whose .mperm is a property of the run, not of the table (run_mperm).
+ * The stratified association (hpgv_run_assoc_cmh) is RUN_MODEL with a within file (run_cmh): the model run's cohort stage, filters,
+ * sorting and per-line arrays -- one hpgv_cmh_result (nine doubles) in the model tests' ten per line -- with its own strata, engine call, header and line */
 typedef enum { RUN_CHISQ = CHI_SQUARE, RUN_FISHER = FISHER, RUN_TDT, RUN_VCF2EPI, RUN_AGGREGATE, RUN_STATS, RUN_FILTER, RUN_SPLIT, RUN_CHISQ_PERM, RUN_TDT_PERM,
                RUN_MODEL, RUN_MODEL_PERM, RUN_GENOME, RUN_GRM, RUN_LOGISTIC, RUN_LINEAR } run_tool_t;
 enum { RUN_N_TOOLS = RUN_LINEAR + 1 };                /* (index 0, the assoc task NONE, is no tool) */
@@ -177,6 +179,7 @@ typedef struct {
 #define HDR_MODEL "#CHR\tPOS\tID\tA1\tA2\tAFF\tUNAFF\tCHISQ_GENO\tP_GENO\tCHISQ_TREND\tP_TREND\tCHISQ_ALLELIC\tP_ALLELIC\tCHISQ_DOM\tP_DOM\tCHISQ_REC\tP_REC"
 #define HDR_LOGISTIC "#CHR\tPOS\tID\tA1\tA2\tNOBS\tBETA\tSE\tOR\tSTAT\tP\tITER"
 #define HDR_LINEAR "#CHR\tPOS\tID\tA1\tA2\tNOBS\tBETA\tSE\tSTAT\tP"
+#define HDR_CMH "#CHR\tPOS\tID\tA1\tA2\tNSTRATA\tCHISQ_CMH\tP_CMH\tOR_MH\tSE\tL95\tU95\tCHISQ_BD\tP_BD"
 static const tool_traits_t g_tool_traits[RUN_N_TOOLS] = {
     /*                    name          cohort               cov ped rf srt mp cnt ln pr  file           ints dbls header */
     [RUN_CHISQ]      = { "chisq",      COHORT_CASE_CONTROL, 0, 1, 1, 1, 0, 0, 1, 0, RUN_CHISQ,      4, 3,  HDR_CHISQ },
@@ -210,7 +213,8 @@ typedef struct {
     uint64_t *line_off; uint32_t *field_off; int32_t *status;
     int32_t *ints; double *dbl;                          /* 4 (assoc) or 2 (tdt) int arrays, 3 double arrays; the model tests: counts8 per line, then
                                                           * chisq5 per line and, from dbl + 5 * max_lines, p5 per line; genome and grm: class4 per line in ints;
-                                                          * logistic, linear: one hpgv_logistic_result / hpgv_linear_result (six doubles' room) per line in dbl */
+                                                          * logistic, linear: one hpgv_logistic_result / hpgv_linear_result (six doubles' room) per line in dbl; a model run with a
+                                                          * within file (run_cmh): one hpgv_cmh_result per line in dbl, nine of the model tests' ten doubles */
     int32_t *n_ge; double *bmax;                         /* the permutation tools: permutations at or above the observed statistic per line; the batch's maximum per permutation */
     double *t_obs;                                       /* the linear run with permutations: the permuted statistic's observed value per line (the others' stands in ::dbl) */
     uint8_t *rows; size_t rows_cap; int row_width;       /* vcf2epi: one dataset row per line */
@@ -306,7 +310,7 @@ typedef struct {
 
 /* the covariate file of the logistic run (host_covar.c): n lines of ncols value columns, iid[i] the line's second id (in blob),
  * val[i * ncols + k] NaN where the text is not a finite number */
-typedef struct { int n, ncols, ncols_set; char **iid; double *val; char *blob; } covar_table_t;
+typedef struct { int n, ncols, ncols_set; char **iid, **c1; double *val; char *blob; } covar_table_t;      /* c1[i]: the first value column's text (the within file's cluster name), or NULL */
 
 /* one file run: built by its public entry (hpgv_run_*), its stages and the pipeline's threads (through the batches) share it */
 typedef struct run {
@@ -332,9 +336,13 @@ typedef struct run {
     run_score_t *score;                                  /* RUN_GRM with a score plan (hpgv_run_score): GN's buffers hold the score sums, the run ends in a .profile */
     const covar_table_t *covar; int n_covar; long n_used; /* RUN_LOGISTIC, RUN_LINEAR: the covariate file (NULL: none) and its columns in use; the cohort samples that stayed */
     const covar_table_t *pheno;                          /* RUN_LINEAR: the phenotype file (NULL: the PED's sixth column) */
+    const covar_table_t *within; int n_strata;           /* RUN_MODEL as the stratified association: the within file; the strata among the cohort that stayed */
     double t_opened, t_header, t_sort;
 } run_t;
 /* the run writes <out>.mperm: the permutation tools of the table, and the linear run when it is given permutations */
+/* the run is the stratified association: the model tool with a within file */
+static inline int run_cmh(const run_t *R) { return R->tool == RUN_MODEL && R->within != NULL; }
+static inline const char *run_header(const run_t *R) { return run_cmh(R) ? HDR_CMH : tool_of(R->tool)->header; }
 static inline int run_mperm(const run_t *R) { return tool_of(R->tool)->mperm || (R->tool == RUN_LINEAR && R->n_perms > 0); }
 
 enum { RUN_ENGINES_MAX = 16, RUN_NB_MAX = RUN_ENGINES_MAX + 3, RUN_FMT_BUFS = 64 };
@@ -501,6 +509,8 @@ int covar_table_read(const char *path, covar_table_t *T);      /* these: an hpgv
 int covar_table_columns(const covar_table_t *T, int n_covar);  /* the columns a run uses, or -1 */
 int covar_table_match(const covar_table_t *T, char *const *names, int n, int use, double *cov, size_t stride, uint8_t *have);
 void covar_table_free(covar_table_t *T);
+int within_table_read(const char *path, covar_table_t *T);     /* the within file: one value column, the cluster's name */
+int within_table_match(const covar_table_t *T, char *const *names, int n, const uint8_t *take, int32_t *stratum, int *n_strata);
 /* host_vcftools.c */
 int filter_partition(run_batch_t *b);
 int split_partition(run_batch_t *b);

@@ -312,6 +312,78 @@ int  hpgv_assoc_model_stats_dev(hpgv_ctx *ctx, const int32_t *d_counts8, int n_v
 int  hpgv_assoc_trend_perm_dev(hpgv_ctx *ctx, const uint8_t *d_gt, int n_variants, const int32_t *d_counts8,
                                int32_t *d_n_ge, double *d_batch_max, int32_t *d_perm_sums /* may be NULL */, void *stream);
 
+/* ---- stratified association: the allelic test within the strata of a discrete stratification -- site, batch, ancestry
+ *      cluster, matched set -- and the homogeneity of its odds ratio across them (PLINK's --mh / --bd with --within; no reference
+ *      counterpart, and parity with PLINK is unpinned: this block is the specification).
+ *
+ *      Tables.  Stratum k of K has the 2 x 2 allele table a = A1_k, b = A2_k (affected), c = U1_k, d = U2_k (unaffected): the
+ *      integers hpgv_assoc_scan_dev would count over that stratum's cohort columns alone, i.e. the sums of the contributions
+ *      (c1, c2) of "label permutation" above -- with its chr-X rule for a row whose d_is_x is set -- over the stratum's affected
+ *      and unaffected columns.  A missing call contributes nothing.  A column with a negative stratum or with HPGV_COND_OTHER is
+ *      in no table.  tables[v * K + k] = {A1_k, A2_k, U1_k, U2_k} (int32 x 4), exact, from an i8 product on the matrix cores
+ *      (csrc/hpgv_assoc_cmh_kernels.h).  Below m1 = a + b, m0 = c + d, n1 = a + c, n0 = b + d, n = m1 + m0, everything f64 without
+ *      contraction, every sum over the strata in the order 0 .. K - 1.
+ *
+ *      CMH.  The strata with n >= 2 take part (n_strata_cmh of them).
+ *          E_k = (m1 n1) / n,   V_k = ((m1 m0) (n1 n0)) / ((n n) (n - 1))
+ *          chisq = (sum a - sum E)^2 / sum V      no continuity correction
+ *      NaN -- never an infinity -- unless sum V > 0: a monomorphic row, a row with all calls missing, a row with no stratum taking
+ *      part.  p = the 1-df tail by the device function hpgv_assoc_chisq_dev uses.
+ *
+ *      Mantel-Haenszel odds ratio, in the orientation of hpgv_assoc's odds (a d / (b c)), over the same strata:
+ *          R_k = (a d) / n,   S_k = (b c) / n,   or_mh = sum R / sum S        NaN unless sum R > 0 and sum S > 0
+ *      se of ln or_mh by Robins, Breslow and Greenland (1986): with P_k = (a + d) / n, Q_k = (b + c) / n
+ *          se^2 = sum P R / (2 (sum R)^2) + sum (P S + Q R) / (2 (sum R)(sum S)) + sum Q S / (2 (sum S)^2)
+ *          l95, u95 = exp(ln or_mh -/+ z se),   z = 1.959963984540054          all three NaN where or_mh is
+ *
+ *      Breslow-Day homogeneity of the odds ratio, without Tarone's correction.  A stratum enters when m1, m0, n1 and n0 are all
+ *      positive (n_strata_bd of them).  With psi = or_mh the fitted count A_k is the root of
+ *          (1 - psi) A^2 + qb A - psi m1 n1 = 0,   qb = (m0 - n1) + psi (m1 + n1)
+ *      that lies in [max(0, n1 - m0), min(m1, n1)]: always the root with + sqrt(disc), disc = qb^2 + 4 (1 - psi) psi m1 n1.  It is
+ *      evaluated in the form that does not cancel: for qb >= 0 as 2 psi m1 n1 / (qb + sqrt(disc)), for qb < 0 (which needs
+ *      psi < 1) as (sqrt(disc) - qb) / (2 (1 - psi)); where |1 - psi| < 1e-12 by the linear equation, A_k = psi m1 n1 / qb.
+ *          W_k = 1 / (1 / A + 1 / (m1 - A) + 1 / (n1 - A) + 1 / ((m0 - n1) + A))
+ *          chisq_bd = sum (a - A_k)^2 / W_k,   df = n_strata_bd - 1
+ *      NaN when df < 1, when or_mh is NaN, or when a fitted cell of an entered stratum is not positive.  p_bd = the upper chi-square
+ *      tail for the integer df by the finite closed forms
+ *          even df:  e^(-x/2) sum_{i < df/2} (x/2)^i / i!
+ *          odd df :  erfc(sqrt(x/2)) + sqrt(2x/pi) e^(-x/2) sum_{i = 1 .. (df-1)/2} x^(i-1) / (1 . 3 ... (2i-1))
+ *      each sum by its term recurrence from the smallest index; df = 1 is the 1-df tail above, bit for bit.  Where e^(-x/2)
+ *      underflows (x above 1490) the tail is 0.
+ *
+ *      A row's record depends on that row only, and no step uses an atomic: a matrix passed in one call or in pieces, on any
+ *      stream or device, gives identical bytes. */
+enum { HPGV_CMH_MAX_STRATA = 1024 };
+/* 72 bytes; arrays of it are 8-byte aligned */
+typedef struct { int32_t n_strata_cmh, n_strata_bd; double chisq, p, or_mh, se, l95, u95, chisq_bd, p_bd; } hpgv_cmh_result;
+/* stratum_of_sample[j] for VCF column j, the indexing of hpgv_set_cohort's condition[]: 0 .. n_strata - 1, or negative for "in no
+ * stratum" (what a HPGV_COND_OTHER column holds is not read).  After hpgv_set_cohort (else HPGV_ERR_STATE); n_samples must be the
+ * cohort's and a value >= n_strata in a cohort column is HPGV_ERR_INVALID; n_strata above HPGV_CMH_MAX_STRATA is
+ * HPGV_ERR_UNSUPPORTED.  n_strata == 0 drops the strata; so does a new hpgv_set_cohort.  A group context gives every member the
+ * strata.  The stratum image -- 2 n_strata rows rounded up to 16, of the assoc layout's pitch bytes: row 2k "stratum k and
+ * affected", row 2k + 1 "stratum k and unaffected", in the label matrix's format -- is a buffer of its own (HPGV_ERR_NOMEM when it
+ * does not fit): the labels of hpgv_set_perm_labels are untouched.  Not to be called while CMH calls of the context are in flight. */
+int  hpgv_set_strata(hpgv_ctx *ctx, const int32_t *stratum_of_sample, int n_samples, int n_strata);
+/* d_gt in assoc layout (16-byte aligned) -> d_out[v] (8-byte aligned) and d_tables (16-byte aligned; n_variants x n_strata x 4
+ * int32; NULL: the context's own scratch, grown after `stream` has drained).  Two launches, asynchronous on `stream`: the tables
+ * (the genotype matrix is read ceil(2 n_strata / 128) times), then one thread per variant for the record.  HPGV_ERR_STATE without
+ * strata; HPGV_ERR_INVALID for n_variants < 0, a NULL or misaligned pointer. */
+int  hpgv_assoc_cmh_dev(hpgv_ctx *ctx, const uint8_t *d_gt, int n_variants, const uint8_t *d_is_x /* may be NULL */,
+                        hpgv_cmh_result *d_out, int32_t *d_tables /* may be NULL */, void *stream);
+/* The same on a host batch in VCF column order (as hpgv_assoc_perm: chain stager, HPGV_LAYOUT_ASSOC layout, is_x per row or NULL)
+ * and on a text (as hpgv_assoc_model_text: tokenizer, record filters, line status; a line that is not a record or that a record
+ * filter rejected has its status set and its record and tables left as they were).  out: n_variants (max_lines) records; tables
+ * (may be NULL): n_variants (max_lines) x n_strata x 4 int32.  Synchronous and thread-safe; a group context deals the call to a
+ * member. */
+int  hpgv_assoc_cmh(hpgv_ctx *ctx, const uint8_t *gt, size_t pitch, int n_variants, const uint8_t *is_x /* may be NULL */,
+                    hpgv_cmh_result *out, int32_t *tables /* may be NULL */);
+int  hpgv_assoc_cmh_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, int max_lines, int *n_lines,
+                         uint64_t *line_off, uint32_t *field_off, int32_t *status,
+                         hpgv_cmh_result *out, int32_t *tables /* may be NULL */);
+/* The definition on the host, by the function the statistics kernel compiles: tables = n_strata x {A1, A2, U1, U2}.  No GPU call,
+ * no context.  HPGV_ERR_INVALID for n_strata < 0, a NULL pointer it needs, a negative count. */
+int  hpgv_cmh_fit(const int32_t *tables, int n_strata, hpgv_cmh_result *out);
+
 /* ---- Logistic regression: the association test with covariates (PLINK's --logistic --covar; no reference counterpart, and
  *      parity with PLINK is unpinned: this block is the specification).  One regression per variant, of the phenotype on the
  *      ALT allele count and up to HPGV_LOGISTIC_MAX_COVAR covariates per sample -- the principal components of hpgv_pca_dev, say.

@@ -380,6 +380,32 @@ int  hpgv_run_assoc_linear_perm(const char *vcf_path, const char *ped_path, cons
  * *n_covar_out: the columns used.  HPGV_ERR_INVALID as above (message in hpgv_host_last_error).  No GPU call. */
 int  hpgv_host_covar_read(const char *covar_path, const char *const *names, int n_names, int n_covar, int *n_covar_out,
                           double *cov, uint8_t *have);
+/* The stratified association test (include/hpgv.h "stratified association"; PLINK's --mh / --bd with --within, parity unpinned):
+ * Cochran-Mantel-Haenszel, the Mantel-Haenszel odds ratio and Breslow-Day per variant over the strata of within_path.  out_path
+ * gets the header line
+ *     #CHR POS ID A1 A2 NSTRATA CHISQ_CMH P_CMH OR_MH SE L95 U95 CHISQ_BD P_BD
+ * and one line per written variant, tab-separated, sorted as hpgv_run_assoc_model's file.  A1 is REF and A2 is ALT; NSTRATA is
+ * n_strata_cmh of the row's hpgv_cmh_result, the numbers are its fields as hpgv_host_format_f6 prints them, nan for a NaN.  Every
+ * batch goes through hpgv_assoc_cmh_text (rows on chromosome X by its rule); a row's result depends on that row only, so the file
+ * does not depend on batch_bytes, engine threads, input form or devices.
+ *   within_path: PLINK's --within shape, lines of two ids and a cluster name, whitespace-separated (further columns are ignored),
+ *     with the header rule of the covariate file.  The SECOND id is matched byte for byte against the VCF's sample names; lines of
+ *     other samples are ignored.  Strata are numbered by first appearance in VCF column order among the cohort samples.
+ *   A cohort sample (PED PHENO 2 or 1) without a line becomes HPGV_COND_OTHER before hpgv_set_cohort, as a sample without
+ *     covariates does in hpgv_run_assoc_logistic.  *n_samples_used_out (may be NULL): the cohort samples that stayed;
+ *     *n_strata_out (may be NULL): their strata.  No cohort sample with a line: HPGV_ERR_INVALID.
+ * HPGV_ERR_INVALID before the engine is started, and no file written: a NULL path, a within file that cannot be read, a line with
+ * fewer than three columns, a ragged line, a second id that appears twice, more than HPGV_CMH_MAX_STRATA distinct cluster names in
+ * the file.
+ * Same cohort, filters, record filters and input forms (plain, gzip, bgzip) as hpgv_run_assoc_model. */
+int  hpgv_run_assoc_cmh(const char *vcf_path, const char *ped_path, const char *within_path, const char *out_path,
+                        size_t batch_bytes, long *n_variants_out, long *n_samples_used_out, int *n_strata_out);
+/* The within file's reader on its own: stratum[j] for the samples names[0 .. n_names) -- the number of the cluster on the line
+ * whose second id is names[j], -1 without one or where take[j] (take may be NULL: everyone) is 0 -- clusters numbered by first
+ * appearance in the order of names among the samples taken; *n_strata_out: how many.  HPGV_ERR_INVALID as above (message in
+ * hpgv_host_last_error).  No GPU call. */
+int  hpgv_host_within_read(const char *within_path, const char *const *names, int n_names, const uint8_t *take,
+                           int32_t *stratum, int *n_strata_out);
 /* hpgv_run_assoc with LD clumping of its results (PLINK's --clump, without overlap and without replication): out_path is
  * written byte for byte as hpgv_run_assoc writes it, and <out_path>.clumped beside it, which groups the significant variants
  * into clumps, each around its strongest variant.
