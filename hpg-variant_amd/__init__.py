@@ -73,6 +73,7 @@ SYMBOLS = [
     "hpgv_set_tdt_flips", "hpgv_tdt_perm_dev", "hpgv_tdt_perm", "hpgv_tdt_perm_text", "hpgv_perm_flips_shuffle",
     "hpgv_assoc_model_scan_dev", "hpgv_assoc_model_stats_dev", "hpgv_assoc_trend_perm_dev", "hpgv_assoc_model", "hpgv_assoc_model_text",
     "hpgv_set_strata", "hpgv_assoc_cmh_dev", "hpgv_assoc_cmh", "hpgv_assoc_cmh_text", "hpgv_cmh_fit",
+    "hpgv_assoc_cmh_perm_dev", "hpgv_assoc_cmh_perm", "hpgv_assoc_cmh_perm_text", "hpgv_perm_labels_shuffle_within",
     "hpgv_set_covariates", "hpgv_assoc_logistic_dev", "hpgv_assoc_logistic", "hpgv_assoc_logistic_text", "hpgv_logistic_fit",
     "hpgv_set_phenotype", "hpgv_assoc_linear_dev", "hpgv_assoc_linear", "hpgv_assoc_linear_text", "hpgv_linear_fit", "hpgv_linear_t_p",
     "hpgv_perm_order_shuffle", "hpgv_set_linear_perms", "hpgv_assoc_linear_perm_dev", "hpgv_assoc_linear_perm", "hpgv_assoc_linear_perm_text", "hpgv_linear_perm_fit", "hpgv_mfma_f64_probe",
@@ -278,6 +279,10 @@ def load():
     L.hpgv_assoc_cmh.argtypes = [vp, vp, sz, i32, vp, vp, vp]
     L.hpgv_assoc_cmh_text.argtypes = [vp, C.c_char_p, sz, i32, C.POINTER(i32), vp, vp, vp, vp, vp]
     L.hpgv_cmh_fit.argtypes = [vp, i32, vp]
+    L.hpgv_assoc_cmh_perm_dev.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp]
+    L.hpgv_assoc_cmh_perm.argtypes = [vp, vp, sz, i32, vp, vp, vp, vp]
+    L.hpgv_assoc_cmh_perm_text.argtypes = [vp, C.c_char_p, sz, i32, C.POINTER(i32), vp, vp, vp, vp, vp, vp]
+    L.hpgv_perm_labels_shuffle_within.argtypes = [vp, vp, i32, i32, u64, vp]
     L.hpgv_assoc_logistic_dev.argtypes = [vp, vp, i32, i32, C.c_double, vp, vp, vp]
     L.hpgv_assoc_logistic.argtypes = [vp, vp, sz, i32, i32, C.c_double, vp, vp]
     L.hpgv_assoc_logistic_text.argtypes = [vp, C.c_char_p, sz, i32, C.POINTER(i32), vp, vp, vp, i32, C.c_double, vp, vp]
@@ -355,6 +360,21 @@ def perm_labels_shuffle(condition, n_perms, seed):
     rc = load().hpgv_perm_labels_shuffle(_ptr(c), len(c), n_perms, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(out))
     if rc != OK:
         raise HpgvError("hpgv_perm_labels_shuffle -> %d" % rc)
+    return out
+
+
+def perm_labels_shuffle_within(condition, stratum, n_perms, seed):
+    """hpgv_perm_labels_shuffle_within: (n_perms, n_samples) uint8 label rows, the cohort columns' conditions shuffled inside
+    every stratum (stratum (n_samples,) int32, negative = in no stratum: the observed label stays); deterministic in (seed, row).
+    No device needed."""
+    c, st = _np(condition, np.uint8), _np(stratum, np.int32)
+    assert len(c) == len(st)
+    out = np.zeros((n_perms, len(c)), np.uint8)
+    rc = load().hpgv_perm_labels_shuffle_within(_ptr(c), _ptr(st), len(c), n_perms, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(out))
+    if rc != OK:
+        e = HpgvError("hpgv_perm_labels_shuffle_within -> %d" % rc)
+        e.code = rc
+        raise e
     return out
 
 
@@ -443,6 +463,26 @@ def run_assoc_cmh(vcf_path, ped_path, within_path, out_path, batch_bytes=1 << 22
     rc = H.hpgv_run_assoc_cmh(enc(vcf_path), enc(ped_path), enc(within_path), enc(out_path), batch_bytes, C.byref(n), C.byref(used), C.byref(k))
     if rc != OK:
         e = HpgvError("hpgv_run_assoc_cmh -> %d: %s" % (rc, (H.hpgv_host_last_error() or b"").decode(errors="replace")))
+        e.code = rc
+        raise e
+    return n.value, used.value, k.value
+
+
+def run_assoc_cmh_perm(vcf_path, ped_path, within_path, out_path, n_perms, seed, batch_bytes=1 << 22):
+    """hpgv_run_assoc_cmh_perm of libhpgv_host.so (include/hpgv_host.h): run_assoc_cmh's file at out_path and the max(T) empirical
+    p-values of CHISQ_CMH under n_perms label shuffles within the strata at out_path + ".mperm".  Paths may be None.  Returns
+    (variants written, cohort samples used, strata)."""
+    _build.build_host_lib()
+    H = C.CDLL(_build.HOSTLIB)
+    H.hpgv_run_assoc_cmh_perm.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_uint64, C.c_size_t,
+                                          C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_int)]
+    H.hpgv_host_last_error.restype = C.c_char_p
+    n, used, k = C.c_long(0), C.c_long(0), C.c_int(0)
+    enc = lambda q: None if q is None else os.fsencode(q)
+    rc = H.hpgv_run_assoc_cmh_perm(enc(vcf_path), enc(ped_path), enc(within_path), enc(out_path), int(n_perms), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                   batch_bytes, C.byref(n), C.byref(used), C.byref(k))
+    if rc != OK:
+        e = HpgvError("hpgv_run_assoc_cmh_perm -> %d: %s" % (rc, (H.hpgv_host_last_error() or b"").decode(errors="replace")))
         e.code = rc
         raise e
     return n.value, used.value, k.value
@@ -1204,6 +1244,32 @@ class Engine:
         self._chk(self.L.hpgv_assoc_cmh_text(self.h, text, len(text), max_lines, C.byref(nl), None, None, _ptr(status), _ptr(out), _ptr(tb)))
         return _text_result(nl, max_lines, status=status, out=out, tables=tb)
 
+    def assoc_cmh_perm(self, gt, is_x=None):
+        """hpgv_assoc_cmh_perm: assoc_cmh's records plus the permutation within strata of the labels set with set_perm_labels: a
+        dict of out (CMH_RESULT (nv,)), n_ge per variant and batch_max per permutation."""
+        gt = _np(gt, np.uint8)
+        nv, pitch = gt.shape
+        x = None if is_x is None else _np(is_x, np.uint8)
+        out, n_ge = np.zeros(nv, CMH_RESULT), np.zeros(nv, np.int32)
+        np_ = getattr(self, "_n_perms", 0)
+        bmax = np.zeros(max(np_, 1), np.float64)
+        self._chk(self.L.hpgv_assoc_cmh_perm(self.h, _ptr(gt), pitch, nv, _ptr(x), _ptr(out), _ptr(n_ge), _ptr(bmax)))
+        return dict(out=out, n_ge=n_ge, batch_max=bmax[:np_])
+
+    def assoc_cmh_perm_text(self, text, max_lines=None, out=None):
+        """hpgv_assoc_cmh_perm_text: assoc_cmh_perm on VCF data lines, out and n_ge per line.  out: a CMH_RESULT array to write into
+        (the records of skipped lines stay as they are)."""
+        text, max_lines, m, status, nl = _text_call(text, max_lines)
+        if out is None:
+            out = np.zeros(m, CMH_RESULT)
+        assert out.dtype == CMH_RESULT and len(out) >= m and out.flags.c_contiguous
+        n_ge = np.zeros(m, np.int32)
+        np_ = getattr(self, "_n_perms", 0)
+        bmax = np.zeros(max(np_, 1), np.float64)
+        self._chk(self.L.hpgv_assoc_cmh_perm_text(self.h, text, len(text), max_lines, C.byref(nl), None, None, _ptr(status), _ptr(out),
+                                                  _ptr(n_ge), _ptr(bmax)))
+        return dict(_text_result(nl, max_lines, status=status, out=out, n_ge=n_ge), batch_max=bmax[:np_])
+
     def set_covariates(self, cov):
         """hpgv_set_covariates: cov (n_samples, C) in VCF column order; None or no columns clears them."""
         if cov is None or np.asarray(cov).size == 0:
@@ -1698,6 +1764,9 @@ class Engine:
 
     def assoc_cmh_dev(self, d_gt, n_variants, d_out, d_tables=None, d_is_x=None, stream=None):
         self._chk(self.L.hpgv_assoc_cmh_dev(self.h, d_gt, n_variants, d_is_x, d_out, d_tables, stream))
+
+    def assoc_cmh_perm_dev(self, d_gt, n_variants, d_tables, d_n_ge, d_batch_max, d_perm_chisq=None, d_is_x=None, stream=None):
+        self._chk(self.L.hpgv_assoc_cmh_perm_dev(self.h, d_gt, n_variants, d_is_x, d_tables, d_n_ge, d_batch_max, d_perm_chisq, stream))
 
     def assoc_logistic_dev(self, d_gt, n_variants, d_out, d_coef=None, max_iter=25, tol=1e-10, stream=None):
         self._chk(self.L.hpgv_assoc_logistic_dev(self.h, d_gt, n_variants, int(max_iter), float(tol), d_out, d_coef, stream))

@@ -133,6 +133,21 @@ __host__ __device__ __forceinline__ void cmh_load_burst(const int4 *tables, int 
     for (int j = 0; j < CMH_BURST; ++j) tb[j] = k0 + j < K ? tables[k0 + j] : make_int4(0, 0, 0, 0);
 }
 
+// One stratum's share of the CMH sums, shared with the permutation kernel (hpgv_assoc_cmh_perm_kernels.h): false when the stratum
+// takes no part (n < 2; E and V are then not written), else E_k and V_k by the header's expressions; the caller adds a, E, V
+__host__ __device__ __forceinline__ bool cmh_term(double a, double b, double c, double d, double &E, double &V) {
+    const double m1 = a + b, m0 = c + d, n1 = a + c, n0 = b + d, n = m1 + m0;
+    if (n < 2.0) return false;
+    E = (m1 * n1) / n;
+    V = ((m1 * m0) * (n1 * n0)) / ((n * n) * (n - 1.0));
+    return true;
+}
+// ... and the statistic of the three sums: NaN unless sum V > 0
+__host__ __device__ __forceinline__ double cmh_chisq(double sa, double sE, double sV) {
+    const double diff = sa - sE;
+    return sV > 0.0 ? (diff * diff) / sV : __builtin_nan("");
+}
+
 __host__ __device__ __forceinline__ hpgv_cmh_result cmh_fit_one(const int4 *tables, int K) {
     hpgv_cmh_result res;
     const double nan = __builtin_nan("");
@@ -145,20 +160,20 @@ __host__ __device__ __forceinline__ hpgv_cmh_result cmh_fit_one(const int4 *tabl
     for (int j = 0; j < CMH_BURST; ++j) {
         const int4 t = tb[j];
         const double a = t.x, b = t.y, c = t.z, d = t.w;
-        const double m1 = a + b, m0 = c + d, n1 = a + c, n0 = b + d, n = m1 + m0;
-        if (n < 2.0) continue;
+        const double n = (a + b) + (c + d);
+        double E, V;
+        if (!cmh_term(a, b, c, d, E, V)) continue;
         ++n_cmh;
         sa += a;
-        sE += (m1 * n1) / n;
-        sV += ((m1 * m0) * (n1 * n0)) / ((n * n) * (n - 1.0));
+        sE += E;
+        sV += V;
         const double R = (a * d) / n, S = (b * c) / n, P = (a + d) / n, Q = (b + c) / n;
         sR += R; sS += S;
         sPR += P * R; sPSQR += P * S + Q * R; sQS += Q * S;
     }
     }
-    const double diff = sa - sE;
     res.n_strata_cmh = n_cmh;
-    res.chisq = sV > 0.0 ? (diff * diff) / sV : nan;
+    res.chisq = cmh_chisq(sa, sE, sV);
     res.p = chisq_p_value(res.chisq);
     const bool has_or = sR > 0.0 && sS > 0.0;
     const double psi = has_or ? sR / sS : nan;              // (from here on a NaN psi carries itself through)

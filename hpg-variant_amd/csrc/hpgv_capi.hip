@@ -142,7 +142,7 @@ void hpgv_destroy(hpgv_ctx *ctx) {
     DeviceGuard g(ctx->device);
     (void)hipDeviceSynchronize();
     if (ctx->d_mendel_male) (void)hipFree(ctx->d_mendel_male);
-    for (DevBuf *b : {&ctx->d_sg_chunks, &ctx->d_group_of_col, &ctx->d_cond, &ctx->d_perm, &ctx->d_strata, &ctx->d_cmh_tables, &ctx->d_cov, &ctx->d_lin, &ctx->d_linperm, &ctx->d_linperm_rows, &ctx->d_flips, &ctx->d_flip_tail, &ctx->d_thr, &ctx->assoc.d_cols, &ctx->tdt.d_cols,
+    for (DevBuf *b : {&ctx->d_sg_chunks, &ctx->d_group_of_col, &ctx->d_cond, &ctx->d_perm, &ctx->d_strata, &ctx->d_strata_steps, &ctx->d_cmh_tables, &ctx->d_cov, &ctx->d_lin, &ctx->d_linperm, &ctx->d_linperm_rows, &ctx->d_flips, &ctx->d_flip_tail, &ctx->d_thr, &ctx->assoc.d_cols, &ctx->tdt.d_cols,
                       &ctx->stats.d_cols, &ctx->sgroups.d_cols, &ctx->mendel.d_cols}) b->release();
     ctx->tdt_plan.release();
     if (ctx->d_lf_base) (void)hipFree(ctx->d_lf_base);

@@ -248,6 +248,9 @@ struct hpgv_ctx {
     // affected", row 2k + 1 "stratum k and unaffected", strata_rows = 2 n_strata rounded up to 16 rows; dropped by a new cohort
     DevBuf d_strata;
     int n_strata = 0, strata_rows = 0;
+    // ... and, for the permutation within strata (k_assoc_cmh_perm), the 64-column k-steps of the assoc layout that hold a member of
+    // each stratum: CSR int32, n_strata + 1 offsets, then the ascending steps of stratum 0, 1, ..
+    DevBuf d_strata_steps;
     DevBuf d_cmh_tables;                  // hpgv_assoc_cmh_dev's tables when the caller gives no buffer (the synchronous calls keep theirs in their slot)
     // covariates of the logistic regression (hpgv_set_covariates): one row of assoc.pitch doubles per covariate in the assoc layout's
     // column order, zeros under the pads; dropped by a new cohort

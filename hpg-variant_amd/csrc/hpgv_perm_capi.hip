@@ -480,6 +480,43 @@ int hpgv_perm_labels_shuffle(const uint8_t *condition, int n_samples, int n_perm
     return HPGV_OK;
 }
 
+int hpgv_perm_labels_shuffle_within(const uint8_t *condition, const int32_t *stratum_of_sample, int n_samples, int n_perms, uint64_t seed, uint8_t *labels_out) {
+    if (n_samples < 0 || n_perms < 0 || (n_samples > 0 && (!condition || !stratum_of_sample)) || ((size_t)n_samples * (size_t)n_perms > 0 && !labels_out)) return HPGV_ERR_INVALID;
+    try {
+        // the cohort columns that are in a stratum, by (stratum, VCF column); `ends`: where each stratum's run ends
+        std::vector<int32_t> cols;
+        for (int j = 0; j < n_samples; ++j)
+            if ((condition[j] == HPGV_COND_AFFECTED || condition[j] == HPGV_COND_UNAFFECTED) && stratum_of_sample[j] >= 0) cols.push_back(j);
+        std::stable_sort(cols.begin(), cols.end(), [&](int32_t a, int32_t b) { return stratum_of_sample[a] < stratum_of_sample[b]; });
+        const size_t nc = cols.size();
+        std::vector<size_t> ends;
+        for (size_t k = 0; k < nc; ++k)
+            if (k + 1 == nc || stratum_of_sample[cols[k + 1]] != stratum_of_sample[cols[k]]) ends.push_back(k + 1);
+        std::vector<uint8_t> base(nc), y(nc);
+        for (size_t k = 0; k < nc; ++k) base[k] = condition[cols[k]] == HPGV_COND_AFFECTED ? 1 : 0;
+        for (int q = 0; q < n_perms; ++q) {
+            uint8_t *row = labels_out + (size_t)q * (size_t)n_samples;
+            // outside the strata: the observed label of a cohort column, 0 for the others
+            for (int j = 0; j < n_samples; ++j) row[j] = condition[j] == HPGV_COND_AFFECTED ? 1 : 0;
+            y = base;
+            // the row's stream is hpgv_perm_labels_shuffle's; the strata take their draws from it one after the other, in ascending order
+            const uint64_t key = splitmix64(seed ^ splitmix64((uint64_t)q));
+            uint64_t draw = 0;
+            size_t lo = 0;
+            for (const size_t hi : ends) {
+                for (size_t i = hi - lo; i > 1; --i) {
+                    const uint64_t r = splitmix64(key + draw++);
+                    const size_t j = (size_t)(((unsigned __int128)r * (unsigned __int128)i) >> 64);
+                    std::swap(y[lo + i - 1], y[lo + j]);
+                }
+                lo = hi;
+            }
+            for (size_t k = 0; k < nc; ++k) row[cols[k]] = y[k];
+        }
+    } catch (...) { return HPGV_ERR_NOMEM; }
+    return HPGV_OK;
+}
+
 int hpgv_perm_order_shuffle(const uint8_t *condition, int n_samples, int n_perms, uint64_t seed, int32_t *order_out) {
     if (n_samples < 0 || n_perms < 0 || (n_samples > 0 && !condition) || ((size_t)n_samples * (size_t)n_perms > 0 && !order_out)) return HPGV_ERR_INVALID;
     try {

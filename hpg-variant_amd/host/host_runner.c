@@ -121,6 +121,9 @@ static int engine_call(run_t *R, run_batch_t *b, const char **what, int *again) 
                                     b->ints, b->ints + m, b->ints + 2 * m, b->ints + 3 * m,
                                     b->dbl, b->dbl + m, b->dbl + 2 * m, b->n_ge, b->bmax);
     case RUN_MODEL: case RUN_MODEL_PERM:
+        if (run_cmh(R) && run_mperm(R)) { *what = "hpgv_assoc_cmh_perm_text";      /* ... with the permutation within strata of the same batch in one call */
+            return hpgv_assoc_cmh_perm_text(g_ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status, (hpgv_cmh_result *)b->dbl, b->n_ge, b->bmax);
+        }
         if (run_cmh(R)) { *what = "hpgv_assoc_cmh_text";      /* the stratified association: its records in the model tests' doubles */
             return hpgv_assoc_cmh_text(g_ctx, b->text, b->bytes, m, &b->n_lines, b->line_off, b->field_off, b->status, (hpgv_cmh_result *)b->dbl, NULL);
         }
@@ -279,6 +282,13 @@ static int assoc_cohort_install(run_t *R, uint8_t *cond, const double *y) {
     if (!rc && cov && R->n_covar > 0 && (rc = hpgv_set_covariates(g_ctx, cov, n_samples, R->n_covar))) host_fail("hpgv_set_covariates", rc);
     if (!rc && y && (rc = hpgv_set_phenotype(g_ctx, y, n_samples))) host_fail("hpgv_set_phenotype", rc);
     if (!rc && stratum && (rc = hpgv_set_strata(g_ctx, stratum, n_samples, R->n_strata))) host_fail("hpgv_set_strata", rc);
+    if (!rc && stratum && run_mperm(R)) {                 /* the run's label rows, once: shuffles within the strata of the cohort that stayed */
+        uint8_t *labels = (uint8_t *)malloc((size_t)R->n_perms * (size_t)(n_samples > 0 ? n_samples : 1));
+        if (!labels) rc = HPGV_ERR_NOMEM;
+        if (!rc && (rc = hpgv_perm_labels_shuffle_within(cond, stratum, n_samples, R->n_perms, R->perm_seed, labels))) host_fail("hpgv_perm_labels_shuffle_within", rc);
+        if (!rc && (rc = hpgv_set_perm_labels(g_ctx, labels, R->n_perms))) host_fail("hpgv_set_perm_labels", rc);
+        free(labels);
+    }
     free(cov); free(stratum);
     return rc;
 }
@@ -873,6 +883,24 @@ int hpgv_run_assoc_cmh(const char *vcf_path, const char *ped_path, const char *w
     int rc = within_table_read(within_path, &W);
     if (rc) return rc;
     run_t R = { .tool = RUN_MODEL, .filters = g_filters, .within = &W };
+    rc = run_file(&R, vcf_path, ped_path, out_path, batch_bytes, n_variants_out);
+    if (n_samples_used_out && !rc) *n_samples_used_out = R.n_used;
+    if (n_strata_out && !rc) *n_strata_out = R.n_strata;
+    covar_table_free(&W);
+    return rc;
+}
+
+/* the same run with max(T) label permutation within the strata: hpgv_run_assoc_cmh's file and <out_path>.mperm */
+int hpgv_run_assoc_cmh_perm(const char *vcf_path, const char *ped_path, const char *within_path, const char *out_path, int n_perms, uint64_t seed,
+                            size_t batch_bytes, long *n_variants_out, long *n_samples_used_out, int *n_strata_out) {
+    if (n_samples_used_out) *n_samples_used_out = 0;
+    if (n_strata_out) *n_strata_out = 0;
+    if (run_args(n_variants_out, vcf_path && ped_path && within_path && out_path, "vcf_path, ped_path, within_path and out_path must not be NULL")) return HPGV_ERR_INVALID;
+    if (n_perms < 1) { snprintf(g_err, sizeof g_err, "n_perms must be at least 1"); return HPGV_ERR_INVALID; }
+    covar_table_t W;
+    int rc = within_table_read(within_path, &W);
+    if (rc) return rc;
+    run_t R = { .tool = RUN_MODEL, .filters = g_filters, .within = &W, .n_perms = n_perms, .perm_seed = seed };
     rc = run_file(&R, vcf_path, ped_path, out_path, batch_bytes, n_variants_out);
     if (n_samples_used_out && !rc) *n_samples_used_out = R.n_used;
     if (n_strata_out && !rc) *n_strata_out = R.n_strata;

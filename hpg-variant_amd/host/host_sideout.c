@@ -68,7 +68,8 @@ int run_perm_add(run_t *R, const run_batch_t *b) {
         const line_head_t h = line_head(b, i);
         const size_t k = M->H.n, cap = M->H.cap;
         if (rec_heads_add(&M->H, h.chr, h.lc, h.pos, h.id, h.li) || (M->H.cap != cap && !run_perm_room(M))) return 1;
-        M->t_obs[k] = R->tool == RUN_MODEL_PERM ? b->dbl[5 * (size_t)i + HPGV_MODEL_TREND] : R->tool == RUN_LINEAR ? fabs(b->t_obs[i]) : b->dbl[m + i];
+        M->t_obs[k] = R->tool == RUN_MODEL_PERM ? b->dbl[5 * (size_t)i + HPGV_MODEL_TREND] : R->tool == RUN_LINEAR ? fabs(b->t_obs[i])
+                      : run_cmh(R) ? ((const hpgv_cmh_result *)b->dbl)[i].chisq : b->dbl[m + i];
         if (R->tool == RUN_TDT_PERM && M->t_obs[k] < 0) M->t_obs[k] = NAN;      /* chi-square -1: nothing transmitted, no statistic */
         M->n_ge[k] = b->n_ge[i];
     }
@@ -93,7 +94,7 @@ int run_perm_write(run_t *R, const char *out_path) {
         char num[2][320];
         for (size_t i = 0; i < n; i++) {
             hpgv_host_format_f6(emp[i], num[0]); hpgv_host_format_f6(emp[n + i], num[1]);
-            if (R->tool == RUN_LINEAR && emp[i] != emp[i]) { strcpy(num[0], "nan"); strcpy(num[1], "nan"); }      /* as the regressions' own columns spell it */
+            if ((R->tool == RUN_LINEAR || run_cmh(R)) && emp[i] != emp[i]) { strcpy(num[0], "nan"); strcpy(num[1], "nan"); }      /* as the run's own columns spell it */
             fprintf(f, "%s\t%s\t%s\n", rec_heads_get(&M->H, i), num[0], num[1]);
         }
         if (fclose(f) != 0) { snprintf(g_err, sizeof g_err, "cannot write %s", path); rc = HPGV_ERR_INVALID; }

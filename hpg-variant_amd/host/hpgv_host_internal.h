@@ -152,7 +152,8 @@ typedef struct {
  * (hpgv_run_assoc_linear_perm), the max(T) permutations of the reduced model's residuals: the same file plus <out>.mperm -- the one
  * tool whose .mperm is a property of the run, not of the table (run_mperm).
  * The stratified association (hpgv_run_assoc_cmh) is RUN_MODEL with a within file (run_cmh): the model run's cohort stage, filters,
- * sorting and per-line arrays -- one hpgv_cmh_result (nine doubles) in the model tests' ten per line -- with its own strata, engine call, header and line */
+ * sorting and per-line arrays -- one hpgv_cmh_result (nine doubles) in the model tests' ten per line -- with its own strata, engine call, header and line;
+ * given n_perms >= 1 (hpgv_run_assoc_cmh_perm) it also writes <out>.mperm of CHISQ_CMH under labels shuffled within the strata, as the linear run does */
 typedef enum { RUN_CHISQ = CHI_SQUARE, RUN_FISHER = FISHER, RUN_TDT, RUN_VCF2EPI, RUN_AGGREGATE, RUN_STATS, RUN_FILTER, RUN_SPLIT, RUN_CHISQ_PERM, RUN_TDT_PERM,
                RUN_MODEL, RUN_MODEL_PERM, RUN_GENOME, RUN_GRM, RUN_LOGISTIC, RUN_LINEAR } run_tool_t;
 enum { RUN_N_TOOLS = RUN_LINEAR + 1 };                /* (index 0, the assoc task NONE, is no tool) */
@@ -339,11 +340,12 @@ typedef struct run {
     const covar_table_t *within; int n_strata;           /* RUN_MODEL as the stratified association: the within file; the strata among the cohort that stayed */
     double t_opened, t_header, t_sort;
 } run_t;
-/* the run writes <out>.mperm: the permutation tools of the table, and the linear run when it is given permutations */
+/* the run writes <out>.mperm: the permutation tools of the table, and the linear run and the stratified association when they are
+ * given permutations */
 /* the run is the stratified association: the model tool with a within file */
 static inline int run_cmh(const run_t *R) { return R->tool == RUN_MODEL && R->within != NULL; }
 static inline const char *run_header(const run_t *R) { return run_cmh(R) ? HDR_CMH : tool_of(R->tool)->header; }
-static inline int run_mperm(const run_t *R) { return tool_of(R->tool)->mperm || (R->tool == RUN_LINEAR && R->n_perms > 0); }
+static inline int run_mperm(const run_t *R) { return tool_of(R->tool)->mperm || ((R->tool == RUN_LINEAR || run_cmh(R)) && R->n_perms > 0); }
 
 enum { RUN_ENGINES_MAX = 16, RUN_NB_MAX = RUN_ENGINES_MAX + 3, RUN_FMT_BUFS = 64 };
 

@@ -383,6 +383,42 @@ int  hpgv_assoc_cmh_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, int
 /* The definition on the host, by the function the statistics kernel compiles: tables = n_strata x {A1, A2, U1, U2}.  No GPU call,
  * no context.  HPGV_ERR_INVALID for n_strata < 0, a NULL pointer it needs, a negative count. */
 int  hpgv_cmh_fit(const int32_t *tables, int n_strata, hpgv_cmh_result *out);
+/*      Permutation within strata: max(T) empirical p-values of CHISQ_CMH (PLINK's --mh --mperm with --within).  Shuffling the
+ *      labels across the whole cohort is the wrong null for a stratified test; here a labelling moves labels inside a stratum only
+ *      (hpgv_perm_labels_shuffle_within makes such rows; the kernel itself takes any 0/1 rows).  Under a labelling y_p -- the rows
+ *      of hpgv_set_perm_labels: same state, same limits, same rules for HPGV_COND_OTHER columns; a row need not keep the class
+ *      sizes -- stratum k has the permuted counts
+ *          a_p,k = sum_{j in stratum k} c1(v, j) y_p(j)      b_p,k = sum_{j in stratum k} c2(v, j) y_p(j)
+ *          c_p,k = (A1_k + U1_k) - a_p,k                     d_p,k = (A2_k + U2_k) - b_p,k
+ *      with (c1, c2) of "label permutation" and its chr-X rule and {A1_k, A2_k, U1_k, U2_k} the observed table above: exact
+ *      integers, K i8 products on the matrix cores (csrc/hpgv_assoc_cmh_perm_kernels.h).  T_p(v) is chisq of the CMH paragraph on
+ *      the K permuted tables -- the same strata rule (n >= 2), the same E_k and V_k expressions, f64 without contraction, sums over
+ *      k = 0 .. K - 1 in that order, NaN unless sum V > 0 -- so it is bit for bit what hpgv_cmh_fit returns as chisq for those
+ *      tables; T_obs(v) is the record's chisq.  No mean imputation and no variance held fixed: with missing calls m1_k changes
+ *      with the labelling and is recomputed.  Outputs, NaN rules and merge rule are those of hpgv_assoc_perm_dev: n_ge[v],
+ *      batch_max[p], element-wise maximum over batches, then hpgv_perm_pvalues.  They come from integer atomics and a maximum on
+ *      the f64 bit pattern only: a matrix passed whole or in pieces, on any stream or device, gives identical bytes.
+ *      Cost: only the 64-column steps of the assoc layout that hold a member of stratum k are multiplied for it.  Where every
+ *      stratum is a contiguous block of layout columns the launch does about the matrix-core work of hpgv_assoc_perm_dev at the same
+ *      n_perms; with fully interleaved strata up to n_strata times that.
+ *      Not here: permutation of the Breslow-Day statistic, adaptive permutation, a layout sorted by stratum, a resident group form. */
+/* d_gt in assoc layout, d_tables what hpgv_assoc_cmh_dev wrote for the same rows -> d_n_ge (n_variants int32), d_batch_max (n_perms
+ * doubles), both overwritten.  d_perm_chisq (may be NULL): T_p(v) as double[v * n_perms + p].  d_gt and d_tables 16-byte aligned,
+ * d_batch_max and d_perm_chisq 8-byte aligned.  Asynchronous on `stream`.  HPGV_ERR_STATE without strata or without labels;
+ * HPGV_ERR_UNSUPPORTED for a grid over 2^31 - 1 workgroups (ceil(n_variants / 64) x ceil(n_perms / 64)): give the variants in
+ * several calls.  The launch reads the genotype matrix at least ceil(n_perms / 64) times. */
+int  hpgv_assoc_cmh_perm_dev(hpgv_ctx *ctx, const uint8_t *d_gt, int n_variants, const uint8_t *d_is_x /* may be NULL */,
+                             const int32_t *d_tables, int32_t *d_n_ge, double *d_batch_max, double *d_perm_chisq /* may be NULL */,
+                             void *stream);
+/* hpgv_assoc_cmh / hpgv_assoc_cmh_text plus the permutation's two outputs: out[v] is hpgv_assoc_cmh's record byte for byte, n_ge
+ * (n_variants / max_lines int32) and batch_max (n_perms doubles) are overwritten.  A text line that is not a record or that a
+ * record filter rejected takes no part in batch_max, gets n_ge 0 and has its record left as it was.  Synchronous and thread-safe;
+ * a group context deals the call to a member (there is no resident group form). */
+int  hpgv_assoc_cmh_perm(hpgv_ctx *ctx, const uint8_t *gt, size_t pitch, int n_variants, const uint8_t *is_x /* may be NULL */,
+                         hpgv_cmh_result *out, int32_t *n_ge, double *batch_max);
+int  hpgv_assoc_cmh_perm_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, int max_lines, int *n_lines,
+                              uint64_t *line_off, uint32_t *field_off, int32_t *status,
+                              hpgv_cmh_result *out, int32_t *n_ge, double *batch_max);
 
 /* ---- Logistic regression: the association test with covariates (PLINK's --logistic --covar; no reference counterpart, and
  *      parity with PLINK is unpinned: this block is the specification).  One regression per variant, of the phenotype on the
@@ -1546,6 +1582,14 @@ int  hpgv_score_text(hpgv_ctx *ctx, const char *text, size_t text_bytes, int max
  * z ^ z >> 31): row p's key is mix(seed ^ mix(p)), its draw number i is mix(key + i), i = 0, 1, ...  Fisher-Yates over the
  * cohort columns in VCF order, from the last position down: position k - 1 swaps with position (draw * k) >> 64, k = n .. 2. */
 int  hpgv_perm_labels_shuffle(const uint8_t *condition, int n_samples, int n_perms, uint64_t seed, uint8_t *labels_out);
+/* The same within strata, for hpgv_assoc_cmh_perm*: stratum_of_sample as hpgv_set_strata takes it (any non-negative value is a
+ * stratum here; what a HPGV_COND_OTHER column holds is not read).  Row p has hpgv_perm_labels_shuffle's key and draws; the strata
+ * are walked in ascending order of their number and each runs the same Fisher-Yates walk over ITS cohort columns in VCF order, the
+ * draw counter running on from one stratum to the next.  So every stratum keeps its number of affected samples in every row, and
+ * row p does not depend on n_perms.  A cohort column with a negative stratum keeps its observed label; HPGV_COND_OTHER columns
+ * get 0.  HPGV_ERR_INVALID for a negative count or a NULL pointer it needs. */
+int  hpgv_perm_labels_shuffle_within(const uint8_t *condition, const int32_t *stratum_of_sample, int n_samples, int n_perms,
+                                     uint64_t seed, uint8_t *labels_out);
 /* n_perms flip rows for hpgv_set_tdt_flips, flips_out[p * n_families + f]: every family of every row flipped with probability
  * 1/2, independently.  Deterministic in (seed, p, f), from the same counter-based generator and row keys as the label rows: row
  * p's key is mix(seed ^ mix(p)), and family f's flip is bit f & 63 of mix(key + (f >> 6)) -- one 64-bit word per 64 families. */

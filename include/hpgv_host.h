@@ -400,6 +400,16 @@ int  hpgv_host_covar_read(const char *covar_path, const char *const *names, int 
  * Same cohort, filters, record filters and input forms (plain, gzip, bgzip) as hpgv_run_assoc_model. */
 int  hpgv_run_assoc_cmh(const char *vcf_path, const char *ped_path, const char *within_path, const char *out_path,
                         size_t batch_bytes, long *n_variants_out, long *n_samples_used_out, int *n_strata_out);
+/* The same run with max(T) label permutation within the strata (include/hpgv.h "Permutation within strata"; PLINK's --mh --mperm
+ * with --within): out_path is hpgv_run_assoc_cmh's file byte for byte, and <out_path>.mperm holds "#CHR POS ID EMP1 EMP2" of
+ * CHISQ_CMH in the format of the other permutation runs, nan where CHISQ_CMH is NaN.  The label rows are
+ * hpgv_perm_labels_shuffle_within(seed) over the cohort that stayed and its strata; every batch goes through
+ * hpgv_assoc_cmh_perm_text (the records and the permutation in one call) and the batches' maxima merge by maximum, so both files do
+ * not depend on batch_bytes, engine threads, input form or devices.  n_perms < 1 is HPGV_ERR_INVALID before the engine starts, and
+ * nothing is written; otherwise what hpgv_run_assoc_cmh refuses. */
+int  hpgv_run_assoc_cmh_perm(const char *vcf_path, const char *ped_path, const char *within_path, const char *out_path,
+                             int n_perms, uint64_t seed, size_t batch_bytes, long *n_variants_out, long *n_samples_used_out,
+                             int *n_strata_out);
 /* The within file's reader on its own: stratum[j] for the samples names[0 .. n_names) -- the number of the cluster on the line
  * whose second id is names[j], -1 without one or where take[j] (take may be NULL: everyone) is 0 -- clusters numbered by first
  * appearance in the order of names among the samples taken; *n_strata_out: how many.  HPGV_ERR_INVALID as above (message in
